@@ -12,7 +12,10 @@ torch.distributed.run (the driver's way: RANK / WORLD_SIZE in the environment) o
 `--gpus N` and no WORLD_SIZE it starts `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a child
 BEFORE anything in this process touches HIP and relays rank 0's line.
 
-Prints ONE JSON line on rank 0.
+A plain run sets up, settles and warms up, times the K steps and prints ONE JSON line on rank 0 (`value`, `ms_per_step`, ...).
+`--full` adds everything else the line used to carry: the per-kernel event pass and roofline, the comparison with the oracle,
+the CPU baseline and the extra legs.  `--dump-outputs DIR` writes what the timed path computed in its last step as
+DIR/<name>.npy (same arguments, same inputs: two builds can be compared output for output).
 """
 import argparse
 import json
@@ -178,6 +181,23 @@ def cost_vs_oracle(F, T, r, n_it, final_cost):
     return {"iterations": int(n_it), "oracle_cost": ref, "rel_diff": abs(final_cost - ref) / ref}
 
 
+H_SAMPLE = 8192  # frames of H written by --dump-outputs (the whole H at the headline size is 100 MB)
+
+
+def h_sample_frames(T):
+    """The fixed, seeded frame sample of H that --dump-outputs writes (sorted global frame indices)."""
+    return np.sort(np.random.default_rng(7).choice(T, size=min(T, H_SAMPLE), replace=False))
+
+
+def dump_outputs(dirname, w, h_sample, div, cost, n_rec):
+    """What a caller of the timed path receives after its last step: W (fp64), the sampled frames of H (fp32, r x H_SAMPLE)
+    and the n_rec objective values recorded so far (fp64; the last launched iteration's is not recorded yet)."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in (("w", np.asarray(w, np.float64)), ("h_sample", np.asarray(h_sample, np.float32)),
+                    ("div", np.asarray(div[:n_rec], np.float64)), ("cost", np.asarray(cost[:n_rec], np.float64))):
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
+
+
 def self_launch(args):
     """--gpus N without a launcher: start the N ranks as children (torch.distributed.run, one process per GPU) and
     relay rank 0's JSON line.  Nothing in THIS process has touched HIP (no torch.cuda call, no libsnmf call)."""
@@ -195,6 +215,10 @@ def self_launch(args):
            "--dim-F", str(args.F), "--dim-T", str(args.T), "--dim-r", str(args.r), "--c5-T", str(args.c5_T), "--c4-T", str(args.c4_T)]
     if args.no_cpu_baseline:
         cmd.append("--no-cpu-baseline")
+    if args.full:
+        cmd.append("--full")
+    if args.dump_outputs:
+        cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     pr = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, text=True)
     line = None
     for ln in pr.stdout.splitlines():
@@ -290,6 +314,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the per-kernel event pass and roofline, "
+                         "the oracle comparison, the solves from a random start, the drop-in call, the CPU baseline (N = 1); "
+                         "the W replica check and the C5 / C4 / one-shot legs (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the timed path computed (W, a fixed sample of H's frames, the "
+                         "objective) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-dropin", action="store_true",
                     help="skip the legs behind the timed region -- the host-array drop-in call and the solves from a random start -- (profiling "
@@ -319,22 +350,24 @@ def main():
         ctx = Context(0)
         V, W0, H0 = make_problem(F, T, r)
         plans = []
-        for _ in range(2):  # [0]: per-kernel HIP-event pass, [1]: the headline pass (events add a little host work)
+        for _ in range(2 if args.full else 1):  # --full: [0] per-kernel HIP-event pass; [-1]: the headline pass (events add host work)
             pl = Plan(ctx, F, T, r, beta=1.0, max_iter=SETTLE + W + K + 1, conv_eps=0.0, cost_check=True, sparsity=SPARSITY)
             pl.set_v(V.astype(np.float32))
             pl.set_w(W0)
             pl.set_h(H0.astype(np.float32))
             pl.init()
             plans.append(pl)
-        plan, plan2 = plans
-        desc = plan.describe()
-        plan.run_async(SETTLE + W)
-        ctx.sync()
-        ctx.timing(True)
-        plan.run_async(K)
-        ctx.sync()
-        fam = {f: ctx.timing_get(f) for f in ("hstep", "wstats", "reduce", "wapply", "wfin")}
-        ctx.timing(False)
+        plan2 = plans[-1]
+        desc = plan2.describe()
+        if args.full:
+            plan = plans[0]
+            plan.run_async(SETTLE + W)
+            ctx.sync()
+            ctx.timing(True)
+            plan.run_async(K)
+            ctx.sync()
+            fam = {f: ctx.timing_get(f) for f in ("hstep", "wstats", "reduce", "wapply", "wfin")}
+            ctx.timing(False)
         plan2.run_async(SETTLE + W)
         ctx.sync()
         t = time.perf_counter()
@@ -343,6 +376,22 @@ def main():
         dt = time.perf_counter() - t
         div, cost, n_it = plan2.get_objective()
         ms = dt / K * 1e3
+        last_cost = [c for c in cost if c != 0.0]
+        out = {
+            "metric": "NMF multiplicative-update iterations/sec (FxTxr)", "value": K / dt, "unit": "iterations/s",
+            "n_gpus": 1, "steps": K, "warmup": W, "ms_per_step": ms, "higher_is_better": True, "scaling": "strong",
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": f"single-MI355X sparse NMF basis train (BASELINE configs[1]): {F}x{T} frames, "
+                                   f"r={r}, KL, sparsity={SPARSITY}, full W+H update + objective per step",
+                       "F": F, "T": T, "r": r, "beta": 1, "settle_steps": SETTLE, "geometry": desc},
+            "final_cost": float(last_cost[-1]) if last_cost else None,
+        }
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, plan2.get_w(), plan2.get_h(np.float32)[:, h_sample_frames(T)], div, cost, len(last_cost))
+        if not args.full:
+            plan2.close()
+            print(json.dumps(out))
+            return
         dom = max(("hstep", "wstats"), key=lambda f: fam[f][0])
         # the kernel(s) actually launched for the dominant half-step (from the plan's own description)
         if dom == "hstep":
@@ -356,15 +405,8 @@ def main():
         traffic, traffic_source, frac_rocprof = None, None, None
         if (F, T, r) == (F_, T_, R_):
             traffic, traffic_source, frac_rocprof = committed_traffic(kname, flops_half, alg_bytes)
-        last_cost = [c for c in cost if c != 0.0]
         ach = flops_half / (fam[dom][0] * 1e-3) / 1e12 if fam[dom][0] > 0 else 0.0
-        out = {
-            "metric": "NMF multiplicative-update iterations/sec (FxTxr)", "value": K / dt, "unit": "iterations/s",
-            "n_gpus": 1, "steps": K, "warmup": W, "ms_per_step": ms, "higher_is_better": True, "scaling": "strong",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"single-MI355X sparse NMF basis train (BASELINE configs[1]): {F}x{T} frames, "
-                                   f"r={r}, KL, sparsity={SPARSITY}, full W+H update + objective per step",
-                       "F": F, "T": T, "r": r, "beta": 1, "settle_steps": SETTLE, "geometry": desc},
+        out.update({
             "roofline": {"bound": "mfma", "kernel": kname, "achieved": ach, "peak": PEAK_F32_MFMA_TFLOPS,
                          "unit": "TFLOP/s", "frac": ach / PEAK_F32_MFMA_TFLOPS, "traffic": traffic,
                          "traffic_unit": "HBM bytes per launch (rocprofv3 FETCH_SIZE/WRITE_SIZE passes)",
@@ -380,8 +422,7 @@ def main():
                                            "wfin = k_wfin, the chunk reduction and the W update in one launch (the step API "
                                            "and the multi-GPU loops run them as k_reduce + k_wapply)",
                          "whole_iteration_TFLOPs": 2 * flops_half / (ms * 1e-3) / 1e12},
-            "final_cost": float(last_cost[-1]) if last_cost else None,
-        }
+        })
         out["cost_vs_oracle"] = cost_vs_oracle(F, T, r, len(last_cost), out["final_cost"])
         # The same resident loop FROM A RANDOM START (no settle steps): kernel time depends on the iterate (dense random
         # activations toggle more operand bits than the sparse ones the L1 penalty leaves; the clock follows the power), so
@@ -449,7 +490,7 @@ def main():
         return
 
     # ---- multi-GPU: one rank per GPU, frames sharded, RCCL all-reduce of the W statistics ----
-    oneshot = start_oneshot_child(args) if (rank == 0 and world > 1) else None  # (before this process touches HIP)
+    oneshot = start_oneshot_child(args) if (args.full and rank == 0 and world > 1) else None  # (before this process touches HIP)
     import torch
     import torch.distributed as dist
     from se_snmf_nat_amd.dist import ShardedTrainer, shard_bounds
@@ -471,13 +512,14 @@ def main():
     tr = ShardedTrainer(V.astype(np.float32), W0, H0.astype(np.float32), beta=1.0, sparsity=SPARSITY,
                         max_iter=SETTLE + 2 * W + K + 1, conv_eps=0.0, cost_check=True, device=local_rank)
     desc = tr.plan.describe()
-    # per-kernel HIP-event pass (own, untimed): the events add host work, so the headline pass below runs without them
+    # --full: per-kernel HIP-event pass (own, untimed): the events add host work, so the headline pass below runs without them.
+    # A plain run runs the same W iterations uninstrumented, so that both reach the timed region at the same iterate.
     tr.run(SETTLE)
     tr.sync()
-    tr.ctx.timing(True)
+    tr.ctx.timing(args.full)
     tr.run(W)
     tr.sync()
-    fam = {f: tr.ctx.timing_get(f)[0] for f in ("hstep", "wstats", "reduce", "wapply", "wfin")}
+    fam = {f: tr.ctx.timing_get(f)[0] for f in ("hstep", "wstats", "reduce", "wapply", "wfin")} if args.full else None
     tr.ctx.timing(False)
     tr.run(W)  # the contract's W warm-up steps, directly ahead of the timed region
     tr.sync()
@@ -497,9 +539,19 @@ def main():
     dt = float(dtt.item())
     div, cost, n_it = tr.plan.get_objective()
     last_cost = [c for c in cost if c != 0.0]
+    if args.dump_outputs:
+        # every rank contributes its columns of the global frame sample; the shards are contiguous and in rank order
+        idx = h_sample_frames(T)
+        h_loc = tr.plan.get_h(np.float32)[:, idx[(idx >= t0) & (idx < t1)] - t0]
+        parts = [h_loc]
+        if world > 1:
+            parts = [None] * world
+            dist.all_gather_object(parts, h_loc)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, tr.plan.get_w(), np.concatenate(parts, axis=1), div, cost, len(last_cost))
     fams = [fam]
     replicas_identical = None
-    if world > 1:
+    if args.full and world > 1:
         fams = [None] * world
         dist.all_gather_object(fams, fam)
         # every rank applies the same deterministic W update to the same summed statistics: the replicas of W must agree BIT FOR BIT
@@ -521,20 +573,21 @@ def main():
                                    f"KL, sparsity={SPARSITY}, one {backend} all-reduce of the W statistics per step",
                        "F": F, "T": T, "r": r, "beta": 1, "parallelism": f"frames/{world}", "settle_steps": SETTLE + W,
                        "geometry": desc},
-            "roofline": {"bound": "mfma", "kernel": "whole iteration (all ranks)", "achieved": tot,
-                         "peak": PEAK_F32_MFMA_TFLOPS * world, "unit": "TFLOP/s",
-                         "frac": tot / (PEAK_F32_MFMA_TFLOPS * world), "traffic": None,
-                         "kernel_ms_per_rank": fams},
             "final_cost": float(last_cost[-1]) if last_cost else None,
         }
+        if args.full:
+            out["roofline"] = {"bound": "mfma", "kernel": "whole iteration (all ranks)", "achieved": tot,
+                               "peak": PEAK_F32_MFMA_TFLOPS * world, "unit": "TFLOP/s",
+                               "frac": tot / (PEAK_F32_MFMA_TFLOPS * world), "traffic": None,
+                               "kernel_ms_per_rank": fams}
+            out["cost_vs_oracle"] = cost_vs_oracle(F, T, r, len(last_cost), out["final_cost"])
         if replicas_identical is not None:
             out["w_replicas_bit_identical"] = replicas_identical
-        out["cost_vs_oracle"] = cost_vs_oracle(F, T, r, len(last_cost), out["final_cost"])
         # the contract times the CPU baseline on rank 0 at N = 1 only
     del tr
     torch.cuda.empty_cache()
     guard = None
-    if world > 1:
+    if args.full and world > 1:
         # The extra legs below must never cost the headline measurement: if a rank fails INSIDE one of their loops its peers sit in
         # a collective until the backend's own time-out (ten minutes) kills the job -- and the line with it.  A timer on every rank
         # ends the process first; rank 0 prints what it has.
@@ -551,7 +604,7 @@ def main():
         guard = threading.Timer(float(os.environ.get("SNMF_BENCH_EXTRA_TIMEOUT", "420")), bail)
         guard.daemon = True
         guard.start()
-    if world > 1:
+    if args.full and world > 1:
         # SURVEY.md section 8d asks strong scaling on "C2 and C5": the SAME loop on BASELINE configs[4] (513 x 500000, r = 512,
         # beta = 2, lambda = 50: 11 ms per iteration on one GPU, the config where the fixed costs of an iteration are small
         # beside its compute).  Reported beside `value`, never instead of it; a failure of this extra leg never fails the bench.
@@ -564,10 +617,11 @@ def main():
         c4 = c4_dnmf_leg(world, rank, local_rank, torch, dist, T_total=args.c4_T)
         if rank == 0:
             out["c4_dnmf"] = c4
+    if world > 1:
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        if world > 1:
+        if args.full and world > 1:
             # the same problem through the one-shot peer-store exchange behind the C ABI, AFTER the timed RCCL leg (the
             # other ranks are gone or idle by now); reported beside `value`, never instead of it
             out["exchange_oneshot"] = finish_oneshot_child(oneshot)

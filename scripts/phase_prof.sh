@@ -7,7 +7,7 @@ cd "$(dirname "$0")/.."
 PROF=scripts/prof_build/libsnmf_hip_prof.so
 python scripts/build_variant.py hip_prof -DSNMF_PROF > /dev/null   # (rebuilds only the translation units whose sources changed)
 export SNMF_LIB_PATH="$PWD/$PROF"
-run() { echo "== $*"; env "$@" python bench.py --steps 200 --warmup 2 --no-cpu-baseline 2>&1 | grep -E "SNMF_PROF|kernel_ms" | python -c "
+run() { echo "== $*"; env "$@" python bench.py --full --steps 200 --warmup 2 --no-cpu-baseline 2>&1 | grep -E "SNMF_PROF|kernel_ms" | python -c "
 import sys,json
 last=''
 for l in sys.stdin:

@@ -4,7 +4,7 @@ cd "$(dirname "$0")/.."
 export SNMF_LIB_PATH="$PWD/scripts/prof_build/libsnmf_hip_prof.so"
 for v in "$@"; do
   echo "== $v"
-  env $v python bench.py --steps ${STEPS:-200} --warmup 2 --no-cpu-baseline > /tmp/pp.out 2> /tmp/pp.err
+  env $v python bench.py --full --steps ${STEPS:-200} --warmup 2 --no-cpu-baseline > /tmp/pp.out 2> /tmp/pp.err
   grep "SNMF_PROF" /tmp/pp.err | tail -2
   python -c "
 import json

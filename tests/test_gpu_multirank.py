@@ -143,12 +143,12 @@ def test_rccl_all_reduce_call_path_at_world_size_one(gpu_ctx):
     assert np.array_equal(w0, w2) and np.array_equal(h0, h2) and np.array_equal(c0, c2)  # ... and through the C-side ncclAllReduce
 
 
-def test_bench_launches_its_own_ranks():
+def test_bench_launches_its_own_ranks(tmp_path):
     """`python bench.py --gpus N` with no launcher around it (no WORLD_SIZE) must start the N ranks itself and print
     ONE line with n_gpus = N (it used to solve the whole problem on one GPU and report n_gpus 1).  The
     parent never touches HIP; the two children share this box's one GPU over gloo (SNMF_DIST_BACKEND /
     SNMF_FORCE_DEVICE are the single-GPU dry-run switches of bench.py) -- on an 8-GPU node the same code path runs one
-    rank per GPU over RCCL."""
+    rank per GPU over RCCL.  --dump-outputs gathers the sampled frames of H from both ranks."""
     import json
     import subprocess
     import sys
@@ -156,7 +156,8 @@ def test_bench_launches_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(SNMF_DIST_BACKEND="gloo", SNMF_FORCE_DEVICE="0")
     pr = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
-                         "--T", "6400", "--r", "64", "--no-cpu-baseline", "--c5-T", "12800", "--c4-T", "9600"], env=env, stdout=subprocess.PIPE,
+                         "--T", "6400", "--r", "64", "--no-cpu-baseline", "--c5-T", "12800", "--c4-T", "9600", "--full",
+                         "--dump-outputs", str(tmp_path)], env=env, stdout=subprocess.PIPE,
                         stderr=subprocess.PIPE, text=True, timeout=900)
     assert pr.returncode == 0, pr.stderr[-2000:]
     lines = [ln for ln in pr.stdout.splitlines() if ln.startswith("{")]
@@ -167,6 +168,9 @@ def test_bench_launches_its_own_ranks():
     assert d["scaling"] == "strong" and "frames/2" in d["config"]["parallelism"]
     assert len(d["roofline"]["kernel_ms_per_rank"]) == 2 and all(k["hstep"] > 0 for k in d["roofline"]["kernel_ms_per_rank"])
     assert d["final_cost"] and d["final_cost"] > 0
+    w, h, cost = (np.load(tmp_path / f"{n}.npy") for n in ("w", "h_sample", "cost"))
+    assert w.shape == (257, 64) and w.dtype == np.float64 and h.shape == (64, 6400) and h.dtype == np.float32
+    assert cost[-1] == d["final_cost"] and np.isfinite(h).all() and (h >= 0).all()
     # the same sharded problem through the one-shot peer-store exchange behind the C ABI, reported beside the RCCL leg
     # (here: two ranks on the one device, hipEvents ordering); a failure of this leg would be an "error" string, not a crash
     one = d["exchange_oneshot"]
@@ -198,7 +202,7 @@ def test_bench_extra_legs_cannot_cost_the_headline_line():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(SNMF_DIST_BACKEND="gloo", SNMF_FORCE_DEVICE="0", SNMF_BENCH_EXTRA_TIMEOUT="0.001")
     pr = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
-                         "--T", "6400", "--r", "64", "--no-cpu-baseline"], env=env, stdout=subprocess.PIPE,
+                         "--T", "6400", "--r", "64", "--no-cpu-baseline", "--full"], env=env, stdout=subprocess.PIPE,
                         stderr=subprocess.PIPE, text=True, timeout=900)
     assert pr.returncode == 0, pr.stderr[-2000:]
     lines = [ln for ln in pr.stdout.splitlines() if ln.startswith("{")]
@@ -209,7 +213,7 @@ def test_bench_extra_legs_cannot_cost_the_headline_line():
 
 
 def test_bench_single_gpu_line_keeps_the_contract():
-    """One GPU, default launcher-less invocation: ONE JSON line with the contract's keys, the roofline object (bound,
+    """One GPU, launcher-less --full invocation: ONE JSON line with the contract's keys, the roofline object (bound,
     achieved, peak, unit, frac, traffic, measured on the engine's stream with HIP events) and -- with the CPU leg on -- the
     cpu_baseline object.  Small T so that the oracle's sample takes seconds."""
     import json
@@ -217,7 +221,7 @@ def test_bench_single_gpu_line_keeps_the_contract():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
-    pr = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "5", "--warmup", "2", "--T", "6400", "--r", "64"],
+    pr = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "5", "--warmup", "2", "--T", "6400", "--r", "64", "--full"],
                         env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert pr.returncode == 0, pr.stderr[-2000:]
     lines = [ln for ln in pr.stdout.splitlines() if ln.startswith("{")]
@@ -252,6 +256,42 @@ def test_bench_single_gpu_line_keeps_the_contract():
     assert 0 < d["from_random_start"] <= 3.0 * d["value"]  # (observed on this shape: 0.9 .. 1.4 x `value`, whose five steps are mostly launch jitter)
     fr = d["from_random_start_detail"]
     assert fr["iters_200"]["iterations_per_s"] == d["from_random_start"] and fr["iters_100"]["iterations_per_s"] > 0
+
+
+def test_bench_plain_run_is_lean_and_dumps_what_it_computed(tmp_path):
+    """A plain run prints the headline line and nothing it does not need (no event pass, no extra legs, no CPU baseline); with
+    --dump-outputs it writes what the timed plan holds after its last step -- W, the seeded frame sample of H, the objective of
+    every iteration -- and a --full run of the same arguments, whose timed plan starts from the same inputs, writes the same bits."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    import bench
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    lines = {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline", "--no-dropin"])):
+        pr = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "5", "--warmup", "2", "--T", "20000", "--r", "64",
+                             "--dump-outputs", str(tmp_path / mode)] + extra, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                            text=True, timeout=900)
+        assert pr.returncode == 0, pr.stderr[-2000:]
+        out = [ln for ln in pr.stdout.splitlines() if ln.startswith("{")]
+        assert len(out) == 1, pr.stdout
+        lines[mode] = json.loads(out[0])
+    d = lines["plain"]
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "final_cost"):
+        assert k in d, k
+    for k in ("roofline", "cost_vs_oracle", "from_random_start", "dropin", "cpu_baseline"):
+        assert k not in d, k
+    assert "roofline" in lines["full"] and d["steps"] == 5 and d["value"] == pytest.approx(1e3 / d["ms_per_step"])
+    got = {m: {n: np.load(tmp_path / m / f"{n}.npy") for n in ("w", "h_sample", "div", "cost")} for m in lines}
+    p = got["plain"]
+    assert p["w"].shape == (257, 64) and p["w"].dtype == np.float64
+    assert p["h_sample"].shape == (64, bench.H_SAMPLE) and p["h_sample"].dtype == np.float32
+    assert bench.SETTLE + 5 <= len(p["cost"]) == len(p["div"]) <= bench.SETTLE + 2 + 5 and (p["cost"] > 0).all()
+    assert p["cost"][-1] == d["final_cost"]
+    assert sum(a.nbytes for a in p.values()) <= 64 << 20
+    for n in p:
+        np.testing.assert_array_equal(p[n], got["full"][n], err_msg=n)
 
 
 def _dnmf_worker(rank, world, port, prob, q):
