@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SNMF_ABI_VERSION 5  /* 5: snmf_multi_release_cache, snmf_multi_cached_teams, snmf_rccl_*, snmf_plan_run_sharded_rccl (the device RNG of snmf_plan_set_h_random changed with 4: draws seeded under ABI 3 are not reproducible); 4: snmf_run_basis_dnmf_multi_*; 3: snmf_run_basis_dnmf_*, snmf_run_basis_train_audio_f64, snmf_sparse_nmf_oop_*, snmf_plan_set_h_random, snmf_ctx_xfer_stats; 2: snmf_multi_* */
+#define SNMF_ABI_VERSION 5  /* 5: snmf_online_batch_* (added within 5: new entries only), snmf_multi_release_cache, snmf_multi_cached_teams, snmf_rccl_*, snmf_plan_run_sharded_rccl (the device RNG of snmf_plan_set_h_random changed with 4: draws seeded under ABI 3 are not reproducible); 4: snmf_run_basis_dnmf_multi_*; 3: snmf_run_basis_dnmf_*, snmf_run_basis_train_audio_f64, snmf_sparse_nmf_oop_*, snmf_plan_set_h_random, snmf_ctx_xfer_stats; 2: snmf_multi_* */
 
 typedef enum snmf_status {
     SNMF_OK = 0,
@@ -398,6 +398,34 @@ int snmf_online_get_basis_f32(snmf_online* o, float* B_DFT_d, int64_t ld);
  * runs unbounded); copies the oldest min(cap, *n) of them in order, *n = frames held (= all frames for shorter runs). */
 int snmf_online_trace(snmf_online* o, snmf_online_frame* out, int64_t cap, int64_t* n);
 void snmf_online_destroy(snmf_online* o);
+
+/* ---- batched online separation: S independent streams per launch ------------------------
+ * The reference's real workload enhances many recordings, each an independent chain of the per-frame function
+ * with its own adapted dictionary (Do_MultiBatch_IS16_20160324.m:178-205: one NTF_sep_event_RT per noise type x SNR,
+ * B_D_u.mat deleted between the chains at :187).  Here S such chains share one snmf_online_params and advance frame by
+ * frame in shared launches, with no host round trip per frame: stream k has its own PCM, its own noise dictionary and
+ * its own state g (src/init_buff.m:17-42), and its output equals what snmf_online_* produces for it alone.
+ * Scope: DFT mode (no Mel entry), the supervised frame solve of the register-resident frame kernel (F <= 513,
+ * R_x + R_d <= 200), R_a and m_a <= 128; anything else returns SNMF_ERR_UNSUPPORTED. */
+typedef struct snmf_online_batch snmf_online_batch;
+/* src/init_buff.m for S streams.  B_DFT_x: F x R_x, shared; B_DFT_d0: F x R_d x S, the initial noise dictionary of
+ * every stream (e.g. each stream's B_D_u.mat, src/NTF_sep_event_RT.m:27-31); H0: r x S (rand(r,1) of
+ * src/sparse_nmf.m:133-134 per stream); Ad_blk0: R_a x m_a x S (rand(R_a, m_a) of src/init_buff.m:39 per stream);
+ * the windows are shared.  All column-major. */
+int snmf_online_batch_create(snmf_ctx* ctx, const snmf_online_params* p, int32_t S, const float* B_DFT_x,
+                             const float* B_DFT_d0, const float* H0, const float* Ad_blk0, const float* win_stft,
+                             const float* win_istft, snmf_online_batch** out);
+/* The driver loop of src/NTF_sep_event_RT.m:54-135 for every stream, as snmf_online_process_f32 per stream: pcm[k] holds
+ * n[k] samples of stream k (n[k] may be 0); flush (may be NULL) ends stream k where flush[k] != 0.  Outputs are arrays
+ * of S host pointers (each array and each entry may be NULL), capacity cap[k] samples; n_out[k] samples written. */
+int snmf_online_batch_process_f32(snmf_online_batch* b, const float* const* pcm, const int64_t* n, const int32_t* flush,
+                                  float* const* x_tilde_f32, int16_t* const* x_tilde_i16, float* const* x_hat_f32,
+                                  float* const* d_hat_f32, const int64_t* cap, int64_t* n_out);
+/* Current B_DFT_d of stream k (src/NTF_sep_event_RT.m:138-140). */
+int snmf_online_batch_get_basis_f32(snmf_online_batch* b, int32_t k, float* B_DFT_d, int64_t ld);
+/* Diagnostics of stream k's most recent frames (the newest 65536 per stream), as snmf_online_trace. */
+int snmf_online_batch_trace(snmf_online_batch* b, int32_t k, snmf_online_frame* out, int64_t cap, int64_t* n);
+void snmf_online_batch_destroy(snmf_online_batch* b);
 
 /* ---- multi-GPU solves: one process, several devices ------------------------------------- */
 /* The reference's host is ONE MATLAB interpreter (run_basis_train.m:88, run_basis_DNMF.m:40,47,53 call sparse_nmf from

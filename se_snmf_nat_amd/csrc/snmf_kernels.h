@@ -3033,21 +3033,33 @@ __device__ __forceinline__ void hsolve_frame_p1(const f32x2 (&wr)[FB / 2][KB], c
     }
 }
 
-template <int FB, int KB, int BM, bool OBJ, bool RECON = false>
+// BATCH (the batched online separator, snmf_tu_online_batch.hip): grid = (frames, streams) and every stream has its own
+// dictionary.  Slot c = blockIdx.x * gridDim.y + blockIdx.y (frame-major) addresses V, Hout, divh / costh, st and recon as
+// the plain kernel's blockIdx.x does; stream s = blockIdx.y addresses Wcf (stride rp * Fp), Hin, wx, dphv and wn (stride rp).
+template <int FB, int KB, int BM, bool OBJ, bool RECON = false, bool BATCH = false>
 __global__ __launch_bounds__(512, 2) void k_hsolve_frame(StepArgs a, SmallArgs sa, const float* __restrict__ Wcf) {
     constexpr int NTHR = 512, RB = 8 * KB, LDP = RB + 1;  // LDP odd: the partial rows hit distinct banks
     constexpr int NPR = 16;  // partial rows of the W^T product after the quad pre-reduction
     constexpr int NV = (BM == BM_KL) ? 1 : 2;
     extern __shared__ __attribute__((aligned(16))) float lds[];
+    const size_t slot = BATCH ? (size_t)blockIdx.x * gridDim.y + blockIdx.y : (size_t)blockIdx.x;
+    if (BATCH) {  // this stream's dictionary and start
+        const size_t s = blockIdx.y;
+        Wcf += s * a.rp * a.Fp;
+        a.Hin += s * a.rp;
+        a.wx += s * a.rp;
+        a.dphv += s * a.rp;
+        sa.wn += s * a.rp;
+    }
     {   // this workgroup's frame
-        const size_t c0 = (size_t)blockIdx.x;
+        const size_t c0 = slot;
         a.V += c0 * a.Fp;
-        a.Hin += c0 * a.rp;
+        if (!BATCH) a.Hin += c0 * a.rp;  // (BATCH: one start per stream)
         a.Hout += c0 * a.rp;
         if (a.S) a.S += c0 * a.rp;
-        sa.divh += (size_t)blockIdx.x * sa.max_iter;
-        sa.costh += (size_t)blockIdx.x * sa.max_iter;
-        sa.st += blockIdx.x;
+        sa.divh += c0 * sa.max_iter;
+        sa.costh += c0 * sa.max_iter;
+        sa.st += c0;
     }
     const int tid = threadIdx.x, lane = tid & 63, kb = tid >> 6, fb = lane;
     const int Fm = 64 * FB;              // rows held in registers (>= F - xr; rows >= F are zero)
@@ -3250,7 +3262,7 @@ __global__ __launch_bounds__(512, 2) void k_hsolve_frame(StepArgs a, SmallArgs s
         // block keeps the allocation of the solve's loop: with the class select inside the unrolled products this variant --
         // the one the online loop launches -- had 32 spilled VGPRs and 36 B of scratch) over two masked copies of h .* wn,
         // the first with the columns k < Rx, the second with the rest; they live in sps / dps, which are dead by now.
-        float* out = sa.recon + (size_t)blockIdx.x * 2 * F;
+        float* out = sa.recon + slot * 2 * F;
         __syncthreads();  // H has been copied out and nobody reads sps / dps any more
         if (lane < KB) {
             const int k = kb * KB + lane;

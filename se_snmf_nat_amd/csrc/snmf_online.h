@@ -66,15 +66,10 @@ struct OStftArgs {
     int n_frames;
 };
 
-// src/bnmf_sep_event_RT_IS16.m:65-81
+// src/bnmf_sep_event_RT_IS16.m:65-81 for the frame whose samples start at s; magnitude / phase columns om / op
 template <int LOGN>
-__global__ __launch_bounds__(256) void k_ostft(OStftArgs a) {
+__device__ __forceinline__ void ostft_frame(const OStftArgs& a, const float* s, float* om, float2* op, float2* bufA, float2* bufB) {
     constexpr int N = 1 << LOGN;
-    __shared__ float2 bufA[N];
-    __shared__ float2 bufB[N];
-    const int t = blockIdx.x;
-    if (t >= a.n_frames) return;
-    const float* s = a.sig + (int64_t)t * a.hop;
     for (int n = threadIdx.x; n < N; n += 256) {
         float x = 0.f;
         if (n < a.sz) {
@@ -86,8 +81,6 @@ __global__ __launch_bounds__(256) void k_ostft(OStftArgs a) {
     }
     __syncthreads();
     const float2* X = fft_lds<LOGN>(bufA, bufB, a.tw);
-    float* om = a.Ym + (int64_t)t * a.ld;
-    float2* op = a.Yph + (int64_t)t * a.ld;
     for (int f = threadIdx.x; f <= N / 2; f += 256) {
         const float2 c = X[f];
         const float mag = sqrtf(c.x * c.x + c.y * c.y);
@@ -99,6 +92,16 @@ __global__ __launch_bounds__(256) void k_ostft(OStftArgs a) {
         om[f] = v + a.floorv;                            // :77
         op[f] = mag > 0.f ? make_float2(c.x / mag, c.y / mag) : make_float2(1.f, 0.f);  // angle(0) = 0
     }
+}
+
+template <int LOGN>
+__global__ __launch_bounds__(256) void k_ostft(OStftArgs a) {
+    constexpr int N = 1 << LOGN;
+    __shared__ float2 bufA[N];
+    __shared__ float2 bufB[N];
+    const int t = blockIdx.x;
+    if (t >= a.n_frames) return;
+    ostft_frame<LOGN>(a, a.sig + (int64_t)t * a.hop, a.Ym + (int64_t)t * a.ld, a.Yph + (int64_t)t * a.ld, bufA, bufB);
 }
 
 __device__ __forceinline__ double wave_sum_d(double v) {
@@ -377,6 +380,7 @@ __device__ __forceinline__ void opost_frame(const OPostArgs& a, float* sm, doubl
     }
 }
 
+#ifndef SNMF_ONLINE_NO_KERNELS  // (the batched separator's TU takes the device functions only)
 // One workgroup; dynamic LDS = (r + 7*F + 3*n1) floats.  The post-filter recurrences (smoothed noise PSD, the
 // previous frame's G.*Y, the SNR ring) make the frames sequential, but when the dictionary is fixed
 // (no adaptation) nothing the host must decide sits between them: the frame solves of a whole batch run
@@ -507,6 +511,8 @@ __global__ void k_oassemble(const double* __restrict__ Bd_old, const double* __r
     }
 }
 
+#endif  // SNMF_ONLINE_NO_KERNELS (k_opost .. k_oassemble)
+
 struct OIstftArgs {
     const float* mag;   // column i at mag + i*ld  (magnitude^pow domain)
     const float2* ph;
@@ -518,16 +524,11 @@ struct OIstftArgs {
     float* syn;         // frame i at syn + i*sz
 };
 
-// src/synth_ifft_buff.m:10-28 (+ the overlapscale of src/bnmf_sep_event_RT_IS16.m:363)
+// src/synth_ifft_buff.m:10-28 (+ the overlapscale of src/bnmf_sep_event_RT_IS16.m:363): magnitude / phase columns mg / ph
+// -> the windowed frame o
 template <int LOGN>
-__global__ __launch_bounds__(256) void k_oistft(OIstftArgs a) {
+__device__ __forceinline__ void oistft_frame(const OIstftArgs& a, const float* mg, const float2* ph, float* o, float2* bufA, float2* bufB) {
     constexpr int N = 1 << LOGN;
-    __shared__ float2 bufA[N];
-    __shared__ float2 bufB[N];
-    const int t = blockIdx.x;
-    if (t >= a.n_frames) return;
-    const float* mg = a.mag + (int64_t)t * a.ld;
-    const float2* ph = a.ph + (int64_t)t * a.ld;
     // real(ifft(X)) = real(fft(conj(X)))/N with X(N-k) = conj(X(k)) for k = 1..N/2-1 (:16-18)
     for (int k = threadIdx.x; k < N; k += 256) {
         const int kk = k <= N / 2 ? k : N - k;
@@ -539,7 +540,6 @@ __global__ __launch_bounds__(256) void k_oistft(OIstftArgs a) {
     }
     __syncthreads();
     float2* X = fft_lds<LOGN>(bufA, bufB, a.tw);
-    float* o = a.syn + (int64_t)t * a.sz;
     if (a.preemph == 0.f) {
         for (int n = threadIdx.x; n < a.sz; n += 256) o[n] = X[n].x * a.scale * a.win[n];  // :19-24
     } else {
@@ -555,6 +555,17 @@ __global__ __launch_bounds__(256) void k_oistft(OIstftArgs a) {
     }
 }
 
+template <int LOGN>
+__global__ __launch_bounds__(256) void k_oistft(OIstftArgs a) {
+    constexpr int N = 1 << LOGN;
+    __shared__ float2 bufA[N];
+    __shared__ float2 bufB[N];
+    const int t = blockIdx.x;
+    if (t >= a.n_frames) return;
+    oistft_frame<LOGN>(a, a.mag + (int64_t)t * a.ld, a.ph + (int64_t)t * a.ld, a.syn + (int64_t)t * a.sz, bufA, bufB);
+}
+
+#ifndef SNMF_ONLINE_NO_KERNELS  // (the batched separator's TU takes the device functions only)
 // Overlap-add of src/NTF_sep_event_RT.m:104-124 in closed form: the hop written at frame l is the sum
 // over the frames l-q (q = nov-1 .. 0, oldest first, only frames > delay were ever accumulated) of
 // their samples [q*hop, q*hop + hop).  syn holds nov-1 frames of the previous call, then the new ones.
@@ -578,6 +589,8 @@ __global__ void k_oola(const float* __restrict__ syn, int n_new, int l0, int del
         }
     }
 }
+
+#endif  // SNMF_ONLINE_NO_KERNELS (k_oola)
 
 // ---------------------------------------------------------------------------------------------
 // k_wadapt: the whole W-only adaptation solve (src/bnmf_sep_event_RT_IS16.m:330-335 ->
@@ -678,6 +691,7 @@ __device__ __forceinline__ bool grid_bar(unsigned* ctr, unsigned nwg, unsigned& 
     return ok_s != 0;
 }
 
+#ifndef SNMF_ONLINE_NO_KERNELS  // (the batched separator's TU takes the device functions only)
 #ifdef SNMF_PROF_WA  // diagnostic builds only: cycles of workgroup 0 by phase, summed over the solves of a run
 __device__ unsigned long long g_wa_prof[10];
 #define WA_STAMP(i) do { if (blockIdx.x == 0 && threadIdx.x == 0) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); \
@@ -973,5 +987,7 @@ __global__ __launch_bounds__(kWaNT) void k_wadapt(WAdaptArgs a) {
     if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&g_wa_prof[9], 1ull);
 #endif
 }
+
+#endif  // SNMF_ONLINE_NO_KERNELS (k_wadapt)
 
 }  // namespace snmf

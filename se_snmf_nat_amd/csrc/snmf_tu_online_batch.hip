@@ -1,0 +1,615 @@
+// snmf_tu_online_batch.hip -- the batched online separator behind the C ABI (snmf_online_batch_*), kernels in
+// snmf_online_batch.h.  A translation unit of its own, so that the single-stream kernels' code does not move.
+#include "snmf_internal.h"
+#include "snmf_online_batch.h"
+
+// Host side: per stream, the hop queue / history / flush logic of snmf_online_process_f32 (snmf_tu_online.hip); on the
+// device, one fixed sequence of launches per frame step for all streams (frame solve, post-filter, gated adaptation,
+// gated re-assembly + dictionary refresh) -- with the dictionary fixed, one launch of each for the whole chunk.  A
+// chunk synchronises ONCE: outputs, statuses and adaptation verdicts are copied back together at its end.
+namespace {
+constexpr size_t kBTraceCap = 1u << 16;   // per stream: the newest 65536 frames, as snmf_online_trace
+constexpr int64_t kBChunkSlots = 16384;  // (frame, stream) slots of one device chunk
+}
+
+struct snmf_online_batch {
+    snmf_ctx* ctx = nullptr;
+    snmf_online_params p{};
+    int S = 0, F = 0, r = 0, N = 0, nov = 0, Ra = 1, ma = 1, Pl = 1, RA2 = 64;
+    snmf_plan* hp = nullptr;  // the frame solve's geometry, sparsity and beta (one plan serves every stream)
+    // per stream, device
+    double *B = nullptr, *Bfix = nullptr, *Btmp = nullptr, *wn = nullptr, *Wu = nullptr;
+    float *Wcf = nullptr, *wx = nullptr, *dphv = nullptr, *Hin = nullptr, *H0 = nullptr;
+    float *lambda_dav = nullptr, *Xm_tilde = nullptr, *r_blk = nullptr, *ldblk = nullptr, *adblk = nullptr;
+    float *G = nullptr, *P = nullptr, *Vt = nullptr;
+    float *tail = nullptr, *tail_x = nullptr, *tail_d = nullptr;
+    uint8_t* rup = nullptr;
+    OnlineDev* dev = nullptr;
+    float *win_s = nullptr, *win_i = nullptr;
+    float2* tw = nullptr;
+    // per chunk, device (grown on demand)
+    int C = 0;  // frames per stream per chunk
+    size_t cap_sig = 0, cap_out = 0;
+    float *sig = nullptr, *Ym = nullptr, *Vp = nullptr, *Hout = nullptr, *reco = nullptr, *Xt = nullptr, *Xh = nullptr, *Dh = nullptr;
+    float *syn = nullptr, *outf = nullptr;
+    float2* Yph = nullptr;
+    int16_t* out16 = nullptr;
+    DevState* st = nullptr;
+    double *divh = nullptr, *costh = nullptr;
+    OnlineStatus* status = nullptr;
+    int* iters = nullptr;
+    int* meta_i = nullptr;        // [6][S] nfr, nreal, l0, i_first, n_out, (pad)
+    int64_t* meta_l = nullptr;    // [3][S] off, zoff, out_off
+    // host state, per stream
+    std::vector<std::vector<float>> pending, hist;
+    std::vector<int64_t> l;
+    std::vector<uint8_t> finished;
+    std::vector<std::deque<snmf_online_frame>> trace;
+    bool failed = false;
+};
+
+static void ob_free_chunk(snmf_online_batch* o) {
+    void* ptrs[] = {o->sig, o->Ym, o->Vp, o->Hout, o->reco, o->Xt, o->Xh, o->Dh, o->syn, o->outf, o->Yph, o->out16,
+                    o->st, o->divh, o->costh, o->status, o->iters};
+    for (void* q : ptrs)
+        if (q) hipFree(q);
+    o->sig = o->Ym = o->Vp = o->Hout = o->reco = o->Xt = o->Xh = o->Dh = o->syn = o->outf = nullptr;
+    o->Yph = nullptr;
+    o->out16 = nullptr;
+    o->st = nullptr;
+    o->divh = o->costh = nullptr;
+    o->status = nullptr;
+    o->iters = nullptr;
+    o->C = 0;
+    o->cap_sig = o->cap_out = 0;
+}
+
+extern "C" void snmf_online_batch_destroy(snmf_online_batch* o) {
+    if (!o) return;
+    hipSetDevice(o->ctx->device);
+    hipStreamSynchronize(o->ctx->stream);
+    if (o->hp) snmf_plan_destroy(o->hp);
+    ob_free_chunk(o);
+    void* ptrs[] = {o->B, o->Bfix, o->Btmp, o->wn, o->Wu, o->Wcf, o->wx, o->dphv, o->Hin, o->H0, o->lambda_dav, o->Xm_tilde,
+                    o->r_blk, o->ldblk, o->adblk, o->G, o->P, o->Vt, o->tail, o->tail_x, o->tail_d, o->rup, o->dev, o->win_s,
+                    o->win_i, o->tw, o->meta_i, o->meta_l};
+    for (void* q : ptrs)
+        if (q) hipFree(q);
+    delete o;
+}
+
+// the single-stream separator's checks (snmf_tu_online.hip: online_validate) plus the batch's scope
+static int ob_validate(const snmf_online_params* p, int32_t S) {
+    if (!p) return fail(SNMF_ERR_INVALID, "online params is NULL");
+    if (S < 1) return fail(SNMF_ERR_INVALID, "the batch needs at least one stream");
+    const int N = p->fftlength;
+    if (N < 64 || N > 4096 || (N & (N - 1))) return fail(SNMF_ERR_UNSUPPORTED, "fftlength must be a power of two in [64,4096]");
+    if (p->framelength < 1 || p->framelength > N || p->frameshift < 1 || p->frameshift > p->framelength)
+        return fail(SNMF_ERR_INVALID, "need 1 <= frameshift <= framelength <= fftlength");
+    const int F = N / 2 + 1;
+    if (p->dcbin < 0 || p->dcbin > F || p->dcbin_back < 0 || p->dcbin_back > F || p->delay < 0)
+        return fail(SNMF_ERR_INVALID, "bad DCbin / DCbin_back / delay");
+    if (p->R_x < 1 || p->R_d < 1) return fail(SNMF_ERR_INVALID, "R_x and R_d must be positive");
+    if (p->max_iter < 1) return fail(SNMF_ERR_INVALID, "max_iter must be positive");
+    if (p->enhance_method != 0 && p->enhance_method != 1) return fail(SNMF_ERR_INVALID, "enhance_method: 0 Wiener, 1 MMSE");
+    if (p->blk_sparse) {
+        if (p->blk_gap < 1 || p->blk_gap % 2 == 0) return fail(SNMF_ERR_INVALID, "blk_gap must be odd (src/blk_sparse.m:4)");
+        if (p->P_len_k < 2 || p->P_len_k % 2 || p->P_len_l < 1) return fail(SNMF_ERR_INVALID, "P_len_k must be even and >= 2, P_len_l >= 1");
+        if (p->P_len_k + p->dcbin > F) return fail(SNMF_ERR_INVALID, "P_len_k + DCbin exceeds the number of bins");
+    }
+    if (p->adapt_train_N) {
+        if (p->R_a < 1 || p->R_a > p->R_d || p->m_a < 1) return fail(SNMF_ERR_INVALID, "need 1 <= R_a <= R_d and m_a >= 1");
+        if (p->R_a > 128 || p->m_a > 128)
+            return fail(SNMF_ERR_UNSUPPORTED, "batched adaptation: R_a and m_a must be <= 128 (k_wadapt_batch's lanes)");
+    }
+    if (p->basis_update_N || p->basis_update_E)
+        return fail(SNMF_ERR_UNSUPPORTED, "batched separator: semi-supervised frame solves (basis_update_N / _E) are not supported");
+    return SNMF_OK;
+}
+
+extern "C" int snmf_online_batch_create(snmf_ctx* ctx, const snmf_online_params* p, int32_t S, const float* Bx, const float* Bd0,
+                                        const float* H0, const float* Ad0, const float* win_stft, const float* win_istft,
+                                        snmf_online_batch** out) {
+    if (!ctx || !out || !Bx || !Bd0 || !H0 || !win_stft || !win_istft) return fail(SNMF_ERR_INVALID, "NULL argument");
+    *out = nullptr;
+    SN_TRY(ob_validate(p, S));
+    if (p->adapt_train_N && !Ad0) return fail(SNMF_ERR_INVALID, "Ad_blk0 is required when adapt_train_N is set");
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const int N = p->fftlength, F = N / 2 + 1, r = p->R_x + p->R_d, sz = p->framelength, hop = p->frameshift, Rd = p->R_d;
+    snmf_online_batch* o = new snmf_online_batch();
+    o->ctx = ctx;
+    o->p = *p;
+    o->S = S;
+    o->F = F;
+    o->r = r;
+    o->N = N;
+    o->nov = (sz + hop - 1) / hop;
+    o->Ra = p->adapt_train_N ? p->R_a : 1;
+    o->ma = p->adapt_train_N ? p->m_a : 1;
+    o->Pl = p->blk_sparse ? p->P_len_l : 1;
+    o->RA2 = (o->Ra + 63) / 64 * 64;
+    int s = SNMF_OK;
+    auto A = [&](int v) { if (s == SNMF_OK) s = v; };
+    {   // the frame solve's plan: F x 1, rank r, H-only (its register-resident kernel must admit the shape)
+        snmf_params hp{};
+        hp.F = F; hp.T = 1; hp.r = r; hp.beta = p->beta_div; hp.max_iter = p->max_iter; hp.conv_eps = p->conv_eps;
+        hp.cost_check = p->cost_check; hp.floor_v = 1; hp.sparsity_kind = SNMF_SPARSITY_SCALAR; hp.sparsity_scalar = p->sparsity;
+        std::vector<uint8_t> zeros(r, 0), ones(r, 1);
+        hp.w_update_ind = zeros.data();
+        hp.h_update_ind = ones.data();
+        A(snmf_plan_create(ctx, &hp, &o->hp));
+        if (s == SNMF_OK && !o->hp->frame_fb)
+            A(fail(SNMF_ERR_UNSUPPORTED, "batched separator: F = %d, r = %d is outside the frame kernel's envelope (F <= 513, r <= 200)", F, r));
+    }
+    if (s == SNMF_OK && p->adapt_train_N && wbatch_lds(o->Ra, o->ma, o->RA2, p->beta_div == 1.0) > ctx->lds_max)
+        A(fail(SNMF_ERR_UNSUPPORTED, "batched adaptation: R_a x m_a too large for one workgroup's LDS"));
+    if (s != SNMF_OK) {
+        snmf_online_batch_destroy(o);
+        return s;
+    }
+    const size_t SS = (size_t)S, rp = o->hp->rp, Fp = o->hp->Fp, Fb = (size_t)(F + kWbRB - 1) / kWbRB * kWbRB;
+    const size_t ntail = (size_t)std::max(1, o->nov - 1) * sz;
+    auto D = [&](auto** ptr, size_t n) { if (s == SNMF_OK) s = dalloc(ptr, n); };
+    D(&o->B, SS * r * F); D(&o->Bfix, SS * Rd * F); D(&o->Btmp, SS * Rd * F); D(&o->wn, SS * rp);
+    D(&o->Wcf, SS * rp * Fp); D(&o->wx, SS * rp); D(&o->dphv, SS * rp); D(&o->Hin, SS * rp); D(&o->H0, SS * r);
+    D(&o->lambda_dav, SS * F); D(&o->Xm_tilde, SS * F); D(&o->r_blk, SS * F * o->Pl); D(&o->ldblk, SS * F * o->ma);
+    D(&o->adblk, SS * o->Ra * o->ma); D(&o->rup, SS * o->Ra); D(&o->dev, SS); D(&o->tail, SS * ntail);
+    if (p->class_outputs) {
+        D(&o->tail_x, SS * ntail);
+        D(&o->tail_d, SS * ntail);
+    }
+    if (p->adapt_train_N) {
+        D(&o->Wu, SS * o->Ra * F); D(&o->G, SS * Fb * o->RA2); D(&o->Vt, SS * Fb * o->ma);
+        if (p->beta_div != 1.0) D(&o->P, SS * Fb * o->RA2);
+    }
+    D(&o->win_s, (size_t)sz); D(&o->win_i, (size_t)sz); D(&o->tw, (size_t)N / 2);
+    D(&o->meta_i, 6 * SS); D(&o->meta_l, 3 * SS);
+    if (s != SNMF_OK) {
+        snmf_online_batch_destroy(o);
+        return s == SNMF_ERR_NOMEM ? fail(SNMF_ERR_NOMEM, "batched separator: device memory for %d streams", S) : s;
+    }
+    std::vector<float2> htw(N / 2);
+    for (int q = 0; q < N / 2; ++q) {
+        const double ang = -2.0 * M_PI * (double)q / (double)N;
+        htw[q] = make_float2((float)cos(ang), (float)sin(ang));
+    }
+    std::vector<double> hB(SS * r * F), hfix(SS * Rd * F);
+    for (size_t k = 0; k < SS; ++k) {
+        double* b = hB.data() + k * r * F;
+        for (size_t i = 0; i < (size_t)F * p->R_x; ++i) b[i] = (double)Bx[i];
+        for (size_t i = 0; i < (size_t)F * Rd; ++i) b[(size_t)F * p->R_x + i] = hfix[k * Rd * F + i] = (double)Bd0[k * Rd * F + i];
+    }
+    std::vector<OnlineDev> d0(SS, OnlineDev{0, 1, 0, 0});  // update_switch = 1 (src/init_buff.m:42)
+    int e = 0;
+    auto H = [&](hipError_t x) { if (x != hipSuccess && !e) e = (int)x; };
+    H(hipMemcpyAsync(o->B, hB.data(), hB.size() * 8, hipMemcpyHostToDevice, st));
+    H(hipMemcpyAsync(o->Bfix, hfix.data(), hfix.size() * 8, hipMemcpyHostToDevice, st));  // B_Mel_d in DFT mode (:328)
+    H(hipMemcpyAsync(o->H0, H0, SS * r * 4, hipMemcpyHostToDevice, st));
+    H(hipMemcpyAsync(o->win_s, win_stft, (size_t)sz * 4, hipMemcpyHostToDevice, st));
+    H(hipMemcpyAsync(o->win_i, win_istft, (size_t)sz * 4, hipMemcpyHostToDevice, st));
+    H(hipMemcpyAsync(o->tw, htw.data(), htw.size() * 8, hipMemcpyHostToDevice, st));
+    H(hipMemcpyAsync(o->dev, d0.data(), SS * sizeof(OnlineDev), hipMemcpyHostToDevice, st));
+    H(hipMemsetAsync(o->Wcf, 0, SS * rp * Fp * 4, st));
+    H(hipMemsetAsync(o->wx, 0, SS * rp * 4, st));
+    H(hipMemsetAsync(o->dphv, 0, SS * rp * 4, st));
+    H(hipMemsetAsync(o->Hin, 0, SS * rp * 4, st));
+    H(hipMemsetAsync(o->wn, 0, SS * rp * 8, st));
+    H(hipMemsetAsync(o->lambda_dav, 0, SS * F * 4, st));
+    H(hipMemsetAsync(o->Xm_tilde, 0, SS * F * 4, st));
+    H(hipMemsetAsync(o->r_blk, 0, SS * F * o->Pl * 4, st));
+    H(hipMemsetAsync(o->ldblk, 0, SS * F * o->ma * 4, st));
+    H(hipMemsetAsync(o->adblk, 0, SS * o->Ra * o->ma * 4, st));
+    H(hipMemsetAsync(o->rup, 0, SS * o->Ra, st));
+    H(hipMemsetAsync(o->tail, 0, SS * ntail * 4, st));
+    if (p->class_outputs) {
+        H(hipMemsetAsync(o->tail_x, 0, SS * ntail * 4, st));
+        H(hipMemsetAsync(o->tail_d, 0, SS * ntail * 4, st));
+    }
+    if (p->adapt_train_N) H(hipMemcpyAsync(o->adblk, Ad0, SS * o->Ra * o->ma * 4, hipMemcpyHostToDevice, st));  // R_a x m_a per stream
+    // every stream's dictionary images (set_w + the init mode of k_wapply)
+    ORefreshArgs ra{};
+    ra.S = S; ra.B = o->B; ra.Wcf = o->Wcf; ra.wx = o->wx; ra.dphv = o->dphv; ra.wn = o->wn; ra.Hin = o->Hin; ra.H0 = o->H0;
+    ra.lamk = o->hp->lamk; ra.F = F; ra.r = r; ra.Rx = p->R_x; ra.rp = (int)rp; ra.Fp = (int)Fp; ra.xr = F > 64 * o->hp->frame_fb;
+    ra.k0 = 0;
+    hipLaunchKernelGGL(k_obrefresh, dim3(r, S), dim3(256), 0, st, ra);
+    H(hipGetLastError());
+    H(hipStreamSynchronize(st));
+    if (e) {
+        snmf_online_batch_destroy(o);
+        return fail(e == (int)hipErrorOutOfMemory ? SNMF_ERR_NOMEM : SNMF_ERR_NO_DEVICE, "online batch create: %s",
+                    hipGetErrorString((hipError_t)e));
+    }
+    o->pending.assign(SS, {});
+    o->hist.assign(SS, std::vector<float>((size_t)(sz - hop), 0.f));
+    o->l.assign(SS, 0);
+    o->finished.assign(SS, 0);
+    o->trace.resize(SS);
+    *out = o;
+    return SNMF_OK;
+}
+
+// chunk buffers for C frames per stream and the given signal / output sizes
+static int ob_reserve(snmf_online_batch* o, int C, size_t n_sig, size_t n_out) {
+    if (C <= o->C && n_sig <= o->cap_sig && n_out <= o->cap_out) return SNMF_OK;
+    hipStreamSynchronize(o->ctx->stream);
+    C = std::max(C, o->C);
+    n_sig = std::max(n_sig, o->cap_sig);
+    n_out = std::max(n_out, o->cap_out);
+    ob_free_chunk(o);
+    const size_t slots = (size_t)C * o->S, F = o->F, sz = o->p.framelength;
+    const snmf_plan* pl = o->hp;
+    SN_TRY(dalloc(&o->sig, n_sig));
+    SN_TRY(dalloc(&o->Ym, F * slots));
+    SN_TRY(dalloc(&o->Yph, F * slots));
+    SN_TRY(dalloc(&o->Vp, (size_t)pl->Fp * slots));
+    SN_TRY(dalloc(&o->Hout, (size_t)pl->rp * slots));
+    SN_TRY(dalloc(&o->reco, 2 * F * slots));
+    SN_TRY(dalloc(&o->Xt, F * slots));
+    if (o->p.class_outputs) {
+        SN_TRY(dalloc(&o->Xh, F * slots));
+        SN_TRY(dalloc(&o->Dh, F * slots));
+    }
+    SN_TRY(dalloc(&o->syn, (size_t)o->S * (C + o->nov - 1) * sz));
+    SN_TRY(dalloc(&o->outf, 3 * std::max<size_t>(n_out, 1)));  // x_tilde | x_hat | d_hat
+    SN_TRY(dalloc(&o->out16, std::max<size_t>(n_out, 1)));
+    SN_TRY(dalloc(&o->st, slots));
+    SN_TRY(dalloc(&o->divh, slots * o->p.max_iter));
+    SN_TRY(dalloc(&o->costh, slots * o->p.max_iter));
+    SN_TRY(dalloc(&o->status, slots));
+    SN_TRY(dalloc(&o->iters, slots));
+    o->C = C;
+    o->cap_sig = n_sig;
+    o->cap_out = n_out;
+    return SNMF_OK;
+}
+
+template <typename K>
+static void ob_by_logn(K&& f, int N) {
+    switch (N) {
+        case 64: f(std::integral_constant<int, 6>{}); break;
+        case 128: f(std::integral_constant<int, 7>{}); break;
+        case 256: f(std::integral_constant<int, 8>{}); break;
+        case 512: f(std::integral_constant<int, 9>{}); break;
+        case 1024: f(std::integral_constant<int, 10>{}); break;
+        case 2048: f(std::integral_constant<int, 11>{}); break;
+        default: f(std::integral_constant<int, 12>{}); break;
+    }
+}
+
+// the frame solves of `nf` frames per stream (slots [step * S, (step + nf) * S)), one workgroup per (frame, stream)
+static int ob_frame_solve(snmf_online_batch* o, int step, int nf) {
+    snmf_plan* pl = o->hp;
+    const size_t off = (size_t)step * o->S;
+    StepArgs a = make_args(pl);
+    a.V = o->Vp + off * pl->Fp;
+    a.Hin = o->Hin;
+    a.Hout = o->Hout + off * pl->rp;
+    a.n_tiles = 1;
+    a.wx = o->wx;
+    a.dphv = o->dphv;
+    a.S = nullptr;
+    SmallArgs sa{};
+    sa.max_iter = pl->p.max_iter;
+    sa.cost_check = pl->p.cost_check;
+    sa.conv_eps = pl->p.conv_eps;
+    sa.divh = o->divh + off * pl->p.max_iter;
+    sa.costh = o->costh + off * pl->p.max_iter;
+    sa.st = o->st + off;
+    sa.tps = 1;
+    sa.recon = o->reco + off * 2 * o->F;
+    sa.wn = o->wn;
+    sa.Rx = o->p.R_x;
+    const bool obj = pl->p.cost_check != 0;
+    auto launch = [&](auto kern) -> int {
+        SN_TRY(ensure_dyn_lds(o->ctx->device, (const void*)kern, pl->lds_frame));
+        hipLaunchKernelGGL(kern, dim3(nf, o->S), dim3(512), pl->lds_frame, o->ctx->stream, a, sa, (const float*)o->Wcf);
+        HIP_TRY(hipGetLastError());
+        return SNMF_OK;
+    };
+    auto by_bm = [&](auto fbc, auto kbc) -> int {
+        constexpr int FB = decltype(fbc)::value, KB = decltype(kbc)::value;
+        auto by_obj = [&](auto bmc) -> int {
+            constexpr int BM = decltype(bmc)::value;
+            return obj ? launch(k_hsolve_frame<FB, KB, BM, true, true, true>) : launch(k_hsolve_frame<FB, KB, BM, false, true, true>);
+        };
+        if (pl->bm == BM_KL) return by_obj(std::integral_constant<int, BM_KL>{});
+        if (pl->bm == BM_EUC) return by_obj(std::integral_constant<int, BM_EUC>{});
+        return by_obj(std::integral_constant<int, BM_GEN>{});
+    };
+    using I4 = std::integral_constant<int, 4>;
+    using I8 = std::integral_constant<int, 8>;
+    using I16 = std::integral_constant<int, 16>;
+    using I25 = std::integral_constant<int, 25>;
+    if (pl->frame_fb == 4) return pl->frame_kb == 16 ? by_bm(I4{}, I16{}) : by_bm(I4{}, I25{});
+    return pl->frame_kb == 16 ? by_bm(I8{}, I16{}) : by_bm(I8{}, I25{});
+}
+
+// adaptation (gated on the device) + re-assembly + dictionary refresh after frame `step` of every stream
+static int ob_adapt(snmf_online_batch* o, const OBatchFrames& fr, int step) {
+    const snmf_online_params& p = o->p;
+    hipStream_t st = o->ctx->stream;
+    snmf_plan* pl = o->hp;
+    const StepArgs sa = make_args(pl);
+    WBatchArgs w{};
+    w.status = o->status; w.nfr = fr.nfr; w.step = step; w.S = o->S; w.ldblk = o->ldblk; w.adblk = o->adblk; w.rup = o->rup;
+    w.dev = o->dev; w.B = o->B; w.Wu = o->Wu; w.G = o->G; w.P = o->P; w.Vt = o->Vt; w.iters = o->iters;
+    w.F = o->F; w.r = o->r; w.Rx = p.R_x; w.Ra = o->Ra; w.ma = o->ma; w.max_iter = p.max_iter; w.cost_check = p.cost_check;
+    w.RA2 = o->RA2; w.sparsity = (float)p.sparsity; w.flr = kFlr; w.beta = sa.beta; w.inv_bb1 = sa.inv_bb1; w.conv_eps = p.conv_eps;
+    const size_t lds = wbatch_lds(o->Ra, o->ma, o->RA2, pl->bm == BM_KL);
+    auto launch = [&](auto kern) -> int {
+        SN_TRY(ensure_dyn_lds(o->ctx->device, (const void*)kern, lds));
+        hipLaunchKernelGGL(kern, dim3(o->S), dim3(kWbNT), lds, st, w);
+        HIP_TRY(hipGetLastError());
+        return SNMF_OK;
+    };
+    if (pl->bm == BM_KL) SN_TRY(launch(k_wadapt_batch<BM_KL>));
+    else if (pl->bm == BM_EUC) SN_TRY(launch(k_wadapt_batch<BM_EUC>));
+    else SN_TRY(launch(k_wadapt_batch<BM_GEN>));
+    hipLaunchKernelGGL(k_obassemble, dim3(p.R_d, o->S), dim3(256), 0, st, (const OnlineStatus*)o->status, fr.nfr, step, o->S,
+                       (const double*)o->B, (const double*)o->Wu, (const double*)o->Bfix, (const uint8_t*)o->rup, o->F, o->r, p.R_x,
+                       o->Ra, p.R_d, o->Btmp);
+    HIP_TRY(hipGetLastError());
+    ORefreshArgs ra{};
+    ra.status = o->status; ra.nfr = fr.nfr; ra.step = step; ra.S = o->S; ra.Btmp = o->Btmp; ra.B = o->B; ra.Wcf = o->Wcf;
+    ra.wx = o->wx; ra.dphv = o->dphv; ra.wn = o->wn; ra.Hin = o->Hin; ra.H0 = o->H0; ra.lamk = pl->lamk; ra.F = o->F; ra.r = o->r;
+    ra.Rx = p.R_x; ra.rp = pl->rp; ra.Fp = pl->Fp; ra.xr = o->F > 64 * pl->frame_fb; ra.k0 = p.R_x;
+    hipLaunchKernelGGL(k_obrefresh, dim3(p.R_d, o->S), dim3(256), 0, st, ra);  // next frame's init_w (:140-146)
+    HIP_TRY(hipGetLastError());
+    return SNMF_OK;
+}
+
+// One device chunk: stream s runs nfr[s] frames (its next nreal[s] PCM frames, then nfr - nreal flush frames).  Appends
+// every stream's output hops and trace records.
+struct ObSink {
+    std::vector<float> f, x, d;
+    std::vector<int16_t> i16;
+};
+static int ob_run_chunk(snmf_online_batch* o, const std::vector<int>& nfr, const std::vector<int>& nreal,
+                        const std::vector<int64_t>& consumed, bool want_f, bool want_i16, bool want_cls, std::vector<ObSink>& sink) {
+    const snmf_online_params& p = o->p;
+    const int S = o->S, F = o->F, sz = p.framelength, hop = p.frameshift, nov = o->nov;
+    hipStream_t st = o->ctx->stream;
+    const int C = *std::max_element(nfr.begin(), nfr.end());
+    if (C == 0) return SNMF_OK;
+    // host framing: stream s's samples = [history | its hops of this chunk], then sz zeros for its flush frames
+    std::vector<int> mi(6 * (size_t)S, 0);
+    std::vector<int64_t> ml(3 * (size_t)S, 0);
+    int* h_nfr = mi.data(); int* h_nreal = h_nfr + S; int* h_l0 = h_nreal + S; int* h_if = h_l0 + S; int* h_no = h_if + S;
+    int64_t* h_off = ml.data(); int64_t* h_zoff = h_off + S; int64_t* h_oo = h_zoff + S;
+    size_t n_sig = 0, n_out = 0;
+    for (int s = 0; s < S; ++s) {
+        h_nfr[s] = nfr[s];
+        h_nreal[s] = nreal[s];
+        h_l0[s] = (int)std::min<int64_t>(o->l[s] + 1, 1 << 30);
+        h_if[s] = (int)std::max<int64_t>(0, (int64_t)p.delay + 1 - h_l0[s]);
+        h_no[s] = std::max(0, nfr[s] - h_if[s]);
+        h_off[s] = (int64_t)n_sig;
+        if (nreal[s] > 0) n_sig += (size_t)(sz - hop) + (size_t)nreal[s] * hop;
+        h_zoff[s] = (int64_t)n_sig;
+        if (nfr[s] > nreal[s]) n_sig += (size_t)sz;
+        h_oo[s] = (int64_t)n_out;
+        n_out += (size_t)h_no[s] * hop;
+    }
+    std::vector<float> sig(std::max<size_t>(n_sig, 1), 0.f);
+    for (int s = 0; s < S; ++s) {
+        if (nreal[s] <= 0) continue;
+        float* d = sig.data() + h_off[s];
+        std::copy(o->hist[s].begin(), o->hist[s].end(), d);
+        std::copy(o->pending[s].begin() + consumed[s] * hop, o->pending[s].begin() + (consumed[s] + nreal[s]) * hop, d + (sz - hop));
+    }
+    SN_TRY(ob_reserve(o, C, sig.size(), n_out));
+    HIP_TRY(hipMemcpyAsync(o->sig, sig.data(), sig.size() * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(o->meta_i, mi.data(), mi.size() * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(o->meta_l, ml.data(), ml.size() * 8, hipMemcpyHostToDevice, st));
+    OBatchFrames fr{};
+    fr.nfr = o->meta_i; fr.nreal = o->meta_i + S; fr.l0 = o->meta_i + 2 * S; fr.off = o->meta_l; fr.zoff = o->meta_l + S; fr.S = S;
+    const int* d_if = o->meta_i + 3 * S;
+    const int* d_no = o->meta_i + 4 * S;
+    const int64_t* d_oo = o->meta_l + 2 * S;
+    // STFT of every frame of the chunk
+    OStftArgs sa{};
+    sa.sig = o->sig; sa.sz = sz; sa.hop = hop; sa.dcbin = p.dcbin; sa.preemph = (float)p.preemph; sa.win = o->win_s; sa.tw = o->tw;
+    sa.powv = (float)p.pow; sa.floorv = (float)p.nonzerofloor; sa.Ym = o->Ym; sa.Yph = o->Yph; sa.ld = F; sa.n_frames = C;
+    ob_by_logn([&](auto L) { hipLaunchKernelGGL(k_obstft<decltype(L)::value>, dim3(C, S), dim3(256), 0, st, sa, fr, o->Vp, o->hp->Fp); }, o->N);
+    HIP_TRY(hipGetLastError());
+    // post-filter arguments (stream 0's pointers; k_obpost re-bases them)
+    OPostArgs a{};
+    a.A = o->Hout; a.hst = o->st; a.B = nullptr; a.recon = o->reco; a.Ym = o->Ym; a.lambda_dav = o->lambda_dav; a.Xm_tilde = o->Xm_tilde;
+    a.r_blk = o->r_blk; a.ldblk = o->ldblk; a.adblk = o->adblk; a.rup = o->rup; a.dev = o->dev; a.status = o->status;
+    a.Xt_out = o->Xt; a.Xh_out = o->Xh; a.Dh_out = o->Dh;
+    a.F = F; a.Rx = p.R_x; a.Rd = p.R_d; a.Ra = o->Ra; a.ma = o->ma; a.Pl = o->Pl; a.Pk = p.P_len_k; a.dcbin = p.dcbin; a.gap = p.blk_gap;
+    a.l = 1; a.blk_sparse = p.blk_sparse; a.adapt = p.adapt_train_N; a.wiener = p.enhance_method == 0; a.init_N_len = p.init_N_len;
+    a.switch_at = (int)std::floor(p.overlap_m_a * p.m_a);
+    a.alpha_p = (float)p.alpha_p; a.alpha_eta = (float)p.alpha_eta; a.alpha_d = (float)p.alpha_d; a.beta0 = (float)p.beta;
+    a.beta_max = (float)p.beta_max; a.Ar_up = (float)p.Ar_up; a.flr = (float)p.nonzerofloor;
+    a.mel = 0; a.mel_conv = 0; a.n1 = 0; a.melmat = nullptr; a.Ymel = nullptr; a.Bmf = nullptr; a.recon_len = F; a.n = 1; a.a_stride = 0;
+    OBatchPost bp{};
+    bp.fr = fr; bp.rp = o->hp->rp; bp.sB = 0;
+    const size_t lds_post = (size_t)(o->r + 7 * F) * 4;
+    HIP_TRY(hipMemsetAsync(o->iters, 0, (size_t)C * S * 4, st));
+    if (!p.adapt_train_N) {
+        // fixed dictionaries: every frame solve of the chunk in one launch, then one post-filter launch (snmf_tu_online.hip)
+        SN_TRY(ob_frame_solve(o, 0, C));
+        bp.step = -1;
+        hipLaunchKernelGGL(k_obpost, dim3(S), dim3(1024), lds_post, st, a, bp);
+        HIP_TRY(hipGetLastError());
+    } else {
+        for (int i = 0; i < C; ++i) {  // one frame step of every stream: four launches, nothing decided on the host
+            SN_TRY(ob_frame_solve(o, i, 1));
+            bp.step = i;
+            hipLaunchKernelGGL(k_obpost, dim3(S), dim3(1024), lds_post, st, a, bp);
+            HIP_TRY(hipGetLastError());
+            SN_TRY(ob_adapt(o, fr, i));
+        }
+    }
+    // inverse STFT behind each stream's kept frames, overlap-add
+    const int64_t syn_stride = (int64_t)(C + nov - 1) * sz;
+    auto synth = [&](const float* mag, float* tail, float* of, int16_t* o16) -> int {
+        if (nov > 1) {
+            hipLaunchKernelGGL(k_obtail, dim3(S), dim3(256), 0, st, o->syn, tail, fr.nfr, syn_stride, nov, sz, 0);
+            HIP_TRY(hipGetLastError());
+        }
+        OIstftArgs ia{};
+        ia.mag = mag; ia.ph = o->Yph; ia.ld = F; ia.n_frames = C; ia.sz = sz; ia.dcb = p.dcbin_back; ia.powv = (float)p.pow;
+        ia.scale = (float)(p.overlapscale / (double)o->N); ia.preemph = (float)p.preemph; ia.win = o->win_i; ia.tw = o->tw; ia.syn = o->syn;
+        ob_by_logn([&](auto L) { hipLaunchKernelGGL(k_obistft<decltype(L)::value>, dim3(C, S), dim3(256), 0, st, ia, fr.nfr, S, syn_stride, nov); },
+                   o->N);
+        HIP_TRY(hipGetLastError());
+        if (n_out > 0) {
+            const int gx = std::max(1, std::min(64, (int)((size_t)C * hop / 256 + 1)));
+            hipLaunchKernelGGL(k_obola, dim3(gx, S), dim3(256), 0, st, (const float*)o->syn, syn_stride, fr, d_if, d_no, d_oo, p.delay, sz, hop,
+                               nov, of, o16);
+            HIP_TRY(hipGetLastError());
+        }
+        if (nov > 1) {
+            hipLaunchKernelGGL(k_obtail, dim3(S), dim3(256), 0, st, o->syn, tail, fr.nfr, syn_stride, nov, sz, 1);
+            HIP_TRY(hipGetLastError());
+        }
+        return SNMF_OK;
+    };
+    // the three signals go to the thirds of outf: x_tilde, x_hat, d_hat
+    std::vector<float> hf, hx, hd;
+    std::vector<int16_t> h16;
+    auto fetch = [&](std::vector<float>& v, const float* src) -> int {
+        v.resize(n_out);
+        if (n_out) HIP_TRY(hipMemcpyAsync(v.data(), src, n_out * 4, hipMemcpyDeviceToHost, st));
+        return SNMF_OK;
+    };
+    SN_TRY(synth(o->Xt, o->tail, o->outf, want_i16 ? o->out16 : nullptr));
+    if (want_f) SN_TRY(fetch(hf, o->outf));
+    if (want_i16) {
+        h16.resize(n_out);
+        if (n_out) HIP_TRY(hipMemcpyAsync(h16.data(), o->out16, n_out * 2, hipMemcpyDeviceToHost, st));
+    }
+    if (p.class_outputs) {  // x_hat / d_hat of :350-361, same synthesis
+        SN_TRY(synth(o->Xh, o->tail_x, o->outf + n_out, nullptr));
+        SN_TRY(synth(o->Dh, o->tail_d, o->outf + 2 * n_out, nullptr));
+        if (want_cls) {
+            SN_TRY(fetch(hx, o->outf + n_out));
+            SN_TRY(fetch(hd, o->outf + 2 * n_out));
+        }
+    }
+    // statuses + adaptation verdicts of the chunk: one copy each
+    std::vector<OnlineStatus> hs((size_t)C * S);
+    std::vector<int> hit((size_t)C * S);
+    HIP_TRY(hipMemcpyAsync(hs.data(), o->status, hs.size() * sizeof(OnlineStatus), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(hit.data(), o->iters, hit.size() * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int s = 0; s < S; ++s) {
+        for (int i = 0; i < nfr[s]; ++i) {
+            const OnlineStatus& q = hs[(size_t)i * S + s];
+            snmf_online_frame tr{};
+            tr.n_iter = q.n_iter; tr.trig = q.trig; tr.n_up = q.n_up; tr.beta = q.beta; tr.A_x_mag = q.A_x_mag; tr.A_d_mag = q.A_d_mag;
+            tr.Q_control = q.Q_control;
+            if (p.adapt_train_N && q.do_solve && q.n_up > 0) {
+                tr.solved = 1;
+                tr.adapt_iters = hit[(size_t)i * S + s];
+            }
+            o->trace[s].push_back(tr);
+            if (o->trace[s].size() > kBTraceCap) o->trace[s].pop_front();
+        }
+        const size_t a0 = (size_t)h_oo[s], n = (size_t)h_no[s] * hop;
+        if (want_f) sink[s].f.insert(sink[s].f.end(), hf.begin() + a0, hf.begin() + a0 + n);
+        if (want_i16) sink[s].i16.insert(sink[s].i16.end(), h16.begin() + a0, h16.begin() + a0 + n);
+        if (want_cls) {
+            sink[s].x.insert(sink[s].x.end(), hx.begin() + a0, hx.begin() + a0 + n);
+            sink[s].d.insert(sink[s].d.end(), hd.begin() + a0, hd.begin() + a0 + n);
+        }
+        if (nreal[s] > 0) {  // history for the next chunk: the last sz - hop samples this stream framed
+            const float* end = sig.data() + h_off[s] + (sz - hop) + (size_t)nreal[s] * hop;
+            o->hist[s].assign(end - (sz - hop), end);
+        }
+        o->l[s] += nfr[s];
+    }
+    return SNMF_OK;
+}
+
+extern "C" int snmf_online_batch_process_f32(snmf_online_batch* o, const float* const* pcm, const int64_t* n, const int32_t* flush,
+                                             float* const* xt_f32, int16_t* const* xt_i16, float* const* xh_f32, float* const* dh_f32,
+                                             const int64_t* cap, int64_t* n_out) {
+    if (!o) return fail(SNMF_ERR_INVALID, "online batch handle is NULL");
+    if (!n || !pcm) return fail(SNMF_ERR_INVALID, "pcm / n is NULL");
+    const int S = o->S;
+    const snmf_online_params& p = o->p;
+    const int hop = p.frameshift;
+    if (n_out)
+        for (int s = 0; s < S; ++s) n_out[s] = 0;
+    if (o->failed) return fail(SNMF_ERR_STATE, "an earlier call failed midway through a chunk; the batch state is not reusable, create a new one");
+    if ((xh_f32 || dh_f32) && !p.class_outputs) return fail(SNMF_ERR_STATE, "class outputs were not requested at creation");
+    const bool any_out = xt_f32 || xt_i16 || xh_f32 || dh_f32;
+    if (any_out && !cap) return fail(SNMF_ERR_INVALID, "cap is NULL");
+    std::vector<int64_t> nfr_tot(S), tail(S);
+    for (int s = 0; s < S; ++s) {
+        if (n[s] < 0 || (n[s] > 0 && !pcm[s])) return fail(SNMF_ERR_INVALID, "stream %d: pcm is NULL", s);
+        if (o->finished[s] && (n[s] > 0 || (flush && flush[s]))) return fail(SNMF_ERR_STATE, "stream %d was flushed; create a new batch", s);
+        nfr_tot[s] = ((int64_t)o->pending[s].size() + n[s]) / hop;
+        tail[s] = (flush && flush[s] && !o->finished[s]) ? p.delay + 1 : 0;
+        const int64_t need = (nfr_tot[s] + tail[s]) * hop;
+        auto short_cap = [&](const void* const* v) { return v && v[s] && cap[s] < need; };
+        if (short_cap((const void* const*)xt_f32) || short_cap((const void* const*)xt_i16) || short_cap((const void* const*)xh_f32) ||
+            short_cap((const void* const*)dh_f32))
+            return fail(SNMF_ERR_INVALID, "stream %d: output capacity %lld < %lld samples", s, (long long)cap[s], (long long)need);
+    }
+    (void)hipGetLastError();  // clean sticky error state, see PLAN_CHECK
+    HIP_TRY(hipSetDevice(o->ctx->device));
+    for (int s = 0; s < S; ++s) o->pending[s].insert(o->pending[s].end(), pcm[s] ? pcm[s] : nullptr, pcm[s] ? pcm[s] + n[s] : nullptr);
+    // chunks: up to C frames per stream, each stream's PCM frames first, then its flush frames
+    const int C = (int)std::max<int64_t>(1, std::min<int64_t>(4096, kBChunkSlots / S));
+    std::vector<int64_t> done(S, 0);
+    std::vector<ObSink> sink(S);
+    const bool wf = xt_f32 != nullptr, wi = xt_i16 != nullptr, wc = xh_f32 || dh_f32;
+    for (;;) {
+        std::vector<int> nfr(S), nreal(S);
+        bool any = false;
+        for (int s = 0; s < S; ++s) {
+            const int64_t left = nfr_tot[s] + tail[s] - done[s];
+            nfr[s] = (int)std::min<int64_t>(C, left);
+            nreal[s] = (int)std::max<int64_t>(0, std::min<int64_t>(nfr[s], nfr_tot[s] - done[s]));
+            any |= nfr[s] > 0;
+        }
+        if (!any) break;
+        if (int rc = ob_run_chunk(o, nfr, nreal, done, wf, wi, wc, sink)) {
+            o->failed = true;  // frames of this call were consumed and the device state advanced: never retry on it
+            return rc;
+        }
+        for (int s = 0; s < S; ++s) done[s] += nfr[s];
+    }
+    for (int s = 0; s < S; ++s) {
+        o->pending[s].erase(o->pending[s].begin(), o->pending[s].begin() + nfr_tot[s] * hop);
+        if (tail[s]) {
+            o->pending[s].clear();  // a partial hop is dropped (src/NTF_sep_event_RT.m:69-76)
+            o->finished[s] = 1;
+        }
+        const ObSink& k = sink[s];
+        if (wf && xt_f32[s]) std::memcpy(xt_f32[s], k.f.data(), k.f.size() * 4);
+        if (wi && xt_i16[s]) std::memcpy(xt_i16[s], k.i16.data(), k.i16.size() * 2);
+        if (xh_f32 && xh_f32[s]) std::memcpy(xh_f32[s], k.x.data(), k.x.size() * 4);
+        if (dh_f32 && dh_f32[s]) std::memcpy(dh_f32[s], k.d.data(), k.d.size() * 4);
+        if (n_out) n_out[s] = (int64_t)std::max(std::max(k.f.size(), k.i16.size()), std::max(k.x.size(), k.d.size()));
+    }
+    return SNMF_OK;
+}
+
+extern "C" int snmf_online_batch_get_basis_f32(snmf_online_batch* o, int32_t k, float* Bd, int64_t ld) {
+    if (!o || !Bd) return fail(SNMF_ERR_INVALID, "NULL argument");
+    if (k < 0 || k >= o->S) return fail(SNMF_ERR_INVALID, "stream %d out of range [0, %d)", k, o->S);
+    if (ld < o->F) return fail(SNMF_ERR_INVALID, "ld < F");
+    HIP_TRY(hipSetDevice(o->ctx->device));
+    HIP_TRY(hipStreamSynchronize(o->ctx->stream));
+    const size_t F = o->F, Rd = o->p.R_d;
+    std::vector<double> h(F * Rd);
+    HIP_TRY(hipMemcpy(h.data(), o->B + (size_t)k * o->r * F + (size_t)o->p.R_x * F, h.size() * 8, hipMemcpyDeviceToHost));
+    for (size_t j = 0; j < Rd; ++j)
+        for (size_t f = 0; f < F; ++f) Bd[j * ld + f] = (float)h[j * F + f];  // the single-stream separator's fp32 mirror
+    return SNMF_OK;
+}
+
+extern "C" int snmf_online_batch_trace(snmf_online_batch* o, int32_t k, snmf_online_frame* out, int64_t cap, int64_t* n) {
+    if (!o) return fail(SNMF_ERR_INVALID, "online batch handle is NULL");
+    if (k < 0 || k >= o->S) return fail(SNMF_ERR_INVALID, "stream %d out of range [0, %d)", k, o->S);
+    const auto& tr = o->trace[k];
+    if (n) *n = (int64_t)tr.size();
+    if (out && cap > 0) std::copy_n(tr.begin(), (size_t)std::min<int64_t>(cap, (int64_t)tr.size()), out);
+    return SNMF_OK;
+}

@@ -22,10 +22,10 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import SnmfOnlineFrame, SnmfOnlineParams
+from ._lib import SnmfError, SnmfOnlineFrame, SnmfOnlineParams
 from .api import default_context
 
-__all__ = ["default_settings", "OnlineSeparator", "ntf_sep_event_rt"]
+__all__ = ["default_settings", "OnlineSeparator", "ntf_sep_event_rt", "OnlineBatchSeparator", "ntf_sep_event_rt_batch"]
 
 
 def default_settings():
@@ -52,6 +52,30 @@ def default_settings():
 def _beta_div(p):
     cf = p.get("cf", "kl")
     return {"is": 0.0, "kl": 1.0, "ed": 2.0}.get(cf, float(p.get("beta_div", 1.0)))  # src/sparse_nmf.m:99-110
+
+
+def _online_params(p, R_x, R_d, adapt, R_a, m_a, method, class_outputs):
+    """settings/initial_setting_SNMF_NAT.m -> snmf_online_params (shared by OnlineSeparator and OnlineBatchSeparator)."""
+    q = SnmfOnlineParams()
+    q.fftlength, q.framelength, q.frameshift = int(p["fftlength"]), int(p["framelength"]), int(p["frameshift"])
+    q.dcbin, q.dcbin_back, q.delay = int(p["DCbin"]), int(p.get("DCbin_back", p["DCbin"])), int(p["delay"])
+    q.preemph, q.pow, q.nonzerofloor = float(p.get("preemph", 0.0)), float(p.get("pow", 2)), float(p.get("nonzerofloor", 1e-9))
+    q.overlapscale = float(p["overlapscale"])
+    q.R_x, q.R_d = R_x, R_d
+    q.beta_div, q.sparsity = _beta_div(p), float(p.get("sparsity", 0))
+    q.max_iter, q.cost_check, q.conv_eps = int(p.get("max_iter", 100)), int(bool(p["cost_check"])), float(p.get("conv_eps", 0))
+    q.enhance_method = 0 if method == "Wiener" else 1
+    q.init_N_len = int(p.get("init_N_len", 0))
+    q.alpha_eta, q.alpha_d = float(p.get("alpha_eta", 0.4)), float(p.get("alpha_d", 0.6))
+    q.beta, q.beta_max = float(p.get("beta", 1.0)), float(p.get("beta_max", 1000.0))
+    q.blk_sparse = int(bool(p.get("blk_sparse", 0)))
+    q.P_len_k, q.P_len_l, q.blk_gap = int(p.get("P_len_k", 60)), int(p.get("P_len_l", 20)), int(p.get("blk_gap", 3))
+    q.alpha_p = float(p.get("alpha_p", 0.4))
+    q.adapt_train_N, q.R_a, q.m_a = adapt, R_a, m_a
+    q.overlap_m_a, q.Ar_up = float(p.get("overlap_m_a", 0.01)), float(p.get("Ar_up", 1.0))
+    q.class_outputs = int(bool(class_outputs))
+    q.basis_update_N, q.basis_update_E = int(bool(p.get("basis_update_N", 0))), int(bool(p.get("basis_update_E", 0)))
+    return q
 
 
 class OnlineSeparator:
@@ -94,25 +118,7 @@ class OnlineSeparator:
                 raise ValueError("Ad_blk0 must be R_a x m_a")
         ws = np.ascontiguousarray(p["win_STFT"], dtype=np.float32)
         wi = np.ascontiguousarray(p["win_ISTFT"], dtype=np.float32)
-        q = SnmfOnlineParams()
-        q.fftlength, q.framelength, q.frameshift = int(p["fftlength"]), int(p["framelength"]), int(p["frameshift"])
-        q.dcbin, q.dcbin_back, q.delay = int(p["DCbin"]), int(p.get("DCbin_back", p["DCbin"])), int(p["delay"])
-        q.preemph, q.pow, q.nonzerofloor = float(p.get("preemph", 0.0)), float(p.get("pow", 2)), float(p.get("nonzerofloor", 1e-9))
-        q.overlapscale = float(p["overlapscale"])
-        q.R_x, q.R_d = self.R_x, self.R_d
-        q.beta_div, q.sparsity = _beta_div(p), float(p.get("sparsity", 0))
-        q.max_iter, q.cost_check, q.conv_eps = int(p.get("max_iter", 100)), int(bool(p["cost_check"])), float(p.get("conv_eps", 0))
-        q.enhance_method = 0 if method == "Wiener" else 1
-        q.init_N_len = int(p.get("init_N_len", 0))
-        q.alpha_eta, q.alpha_d = float(p.get("alpha_eta", 0.4)), float(p.get("alpha_d", 0.6))
-        q.beta, q.beta_max = float(p.get("beta", 1.0)), float(p.get("beta_max", 1000.0))
-        q.blk_sparse = int(bool(p.get("blk_sparse", 0)))
-        q.P_len_k, q.P_len_l, q.blk_gap = int(p.get("P_len_k", 60)), int(p.get("P_len_l", 20)), int(p.get("blk_gap", 3))
-        q.alpha_p = float(p.get("alpha_p", 0.4))
-        q.adapt_train_N, q.R_a, q.m_a = adapt, R_a, m_a
-        q.overlap_m_a, q.Ar_up = float(p.get("overlap_m_a", 0.01)), float(p.get("Ar_up", 1.0))
-        q.class_outputs = int(bool(class_outputs))
-        q.basis_update_N, q.basis_update_E = int(bool(p.get("basis_update_N", 0))), int(bool(p.get("basis_update_E", 0)))
+        q = _online_params(p, self.R_x, self.R_d, adapt, R_a, m_a, method, class_outputs)
         self._q = q
         self.class_outputs = bool(class_outputs)
         self.hop, self.delay = q.frameshift, q.delay
@@ -203,5 +209,164 @@ def ntf_sep_event_rt(pcm, B_DFT_x, B_DFT_d, p, H0=None, Ad_blk0=None, ctx=None, 
             i16 = np.concatenate([q["x_tilde"] for q in parts])
             f32 = np.concatenate([q["x_tilde_f"] for q in parts])
         return i16.copy(), f32.astype(np.float64), (sep.mel_basis() if sep.mel else sep.basis())
+    finally:
+        sep.close()
+
+
+def _invalid(msg):
+    return SnmfError(1, msg)  # SNMF_ERR_INVALID, raised before anything reaches the device
+
+
+def _per_stream(x, S, shape, name, order):
+    """One array for every stream, a list of S arrays or an array stacked along the last axis -> float32 [S, ...]."""
+    if isinstance(x, (list, tuple)):
+        if len(x) != S:
+            raise _invalid(f"{name}: {len(x)} entries for {S} streams")
+        arrs = [np.asarray(a, dtype=np.float64) for a in x]
+    else:
+        a = np.asarray(x, dtype=np.float64)
+        if a.shape == tuple(shape) + (S,):
+            arrs = [a[..., k] for k in range(S)]
+        else:
+            arrs = [a] * S
+    out = []
+    for k, a in enumerate(arrs):
+        if a.size == int(np.prod(shape)) and len(shape) == 1:
+            a = a.reshape(-1)
+        if a.shape != tuple(shape):
+            raise _invalid(f"{name} of stream {k} is {a.shape}, expected {tuple(shape)}")
+        out.append(np.asarray(a, dtype=np.float32).ravel(order=order))
+    return np.ascontiguousarray(np.concatenate(out))
+
+
+class OnlineBatchSeparator:
+    """S independent online streams (snmf_online_batch in include/snmf.h) sharing one set of settings `p`: each stream
+    has its own PCM, noise dictionary and state `g`, and they all advance frame by frame in shared launches.  Stream k's
+    output is what `OnlineSeparator` produces for it alone.  `B_DFT_d` is one F x R_d array (copied to every stream) or
+    a list of S arrays; `H0` / `Ad_blk0` are lists or arrays stacked along the last axis, by default drawn per stream
+    from RandomState(random_seed + k).  DFT mode and the supervised frame solve only (SNMF_ERR_UNSUPPORTED otherwise)."""
+
+    def __init__(self, B_DFT_x, B_DFT_d, p, n_streams, H0=None, Ad_blk0=None, ctx=None, class_outputs=False):
+        S = int(n_streams)
+        if S < 1:
+            raise _invalid("n_streams must be >= 1")
+        if p.get("Splice", 0) != 0 or p.get("blk_len_sep", 1) != 1:
+            raise NotImplementedError("online path: only Splice=0, blk_len_sep=1 (the shipped settings)")
+        if p.get("B_sep_mode", "DFT") != "DFT":
+            raise SnmfError(8, "batched separator: B_sep_mode 'Mel' is not supported")  # SNMF_ERR_UNSUPPORTED
+        if "cost_check" not in p:
+            raise KeyError("Reference to non-existent field 'cost_check'.")  # src/sparse_nmf.m:260
+        method = p.get("ENHANCE_METHOD", "MMSE")
+        if method not in ("Wiener", "MMSE"):
+            raise ValueError("ENHANCE_METHOD must be 'Wiener' or 'MMSE'")
+        F = p["fftlength"] // 2 + 1
+        Bx = np.asfortranarray(B_DFT_x, dtype=np.float32)
+        if Bx.ndim != 2 or Bx.shape[0] != F:
+            raise _invalid(f"B_DFT_x must have fftlength/2+1 = {F} rows")
+        R_x = Bx.shape[1]
+        Bd_list = B_DFT_d if isinstance(B_DFT_d, (list, tuple)) else None
+        Bd_first = np.asarray(Bd_list[0] if Bd_list else B_DFT_d)
+        if Bd_first.ndim not in (2, 3) or Bd_first.shape[0] != F:
+            raise _invalid(f"B_DFT_d must have fftlength/2+1 = {F} rows")
+        R_d = Bd_first.shape[1]
+        r = R_x + R_d
+        adapt = int(bool(p.get("adapt_train_N", 0)))
+        R_a, m_a = int(p.get("R_a", 1)), int(p.get("m_a", 1))
+        seed = int(p.get("random_seed", 1))
+        if H0 is None or (adapt and Ad_blk0 is None):
+            draws_h, draws_a = [], []
+            for k in range(S):  # OnlineSeparator's stand-ins, seeded per stream
+                rs = np.random.RandomState(seed + k)
+                draws_h.append(rs.random_sample(r))
+                if adapt:
+                    draws_a.append(rs.random_sample((R_a, m_a)))
+            H0 = draws_h if H0 is None else H0
+            Ad_blk0 = draws_a if (adapt and Ad_blk0 is None) else Ad_blk0
+        Bd = _per_stream(B_DFT_d, S, (F, R_d), "B_DFT_d", "F")
+        H = _per_stream(H0, S, (r,), "H0", "F")
+        Ad = _per_stream(Ad_blk0, S, (R_a, m_a), "Ad_blk0", "F") if adapt else None
+        self._lib = _lib.load()
+        self.ctx = ctx or default_context()
+        self.F, self.R_x, self.R_d, self.S = F, R_x, R_d, S
+        ws = np.ascontiguousarray(p["win_STFT"], dtype=np.float32)
+        wi = np.ascontiguousarray(p["win_ISTFT"], dtype=np.float32)
+        q = _online_params(p, R_x, R_d, adapt, R_a, m_a, method, class_outputs)
+        self._q = q
+        self.class_outputs = bool(class_outputs)
+        self.hop, self.delay = q.frameshift, q.delay
+        h = C.c_void_p()
+        _lib.check(self._lib.snmf_online_batch_create(self.ctx._h, C.byref(q), S, Bx.ctypes.data, Bd.ctypes.data, H.ctypes.data,
+                                                      Ad.ctypes.data if Ad is not None else None, ws.ctypes.data, wi.ctypes.data,
+                                                      C.byref(h)))
+        self._h = h
+        self.ctx._plans.add(self)  # destroyed before the context
+
+    def process(self, pcms, flush=False):
+        """Feed every stream: `pcms` is a list of S sample arrays (any may be empty); `flush` a bool for all or a list of
+        S bools.  Returns a list of S dicts, each as OnlineSeparator.process returns."""
+        S = self.S
+        if len(pcms) != S:
+            raise _invalid(f"{len(pcms)} PCM arrays for {S} streams")
+        fl = [bool(flush)] * S if np.isscalar(flush) or flush is None else [bool(x) for x in flush]
+        if len(fl) != S:
+            raise _invalid(f"{len(fl)} flush flags for {S} streams")
+        xs = [np.ascontiguousarray(np.asarray(x).reshape(-1), dtype=np.float32) for x in pcms]
+        caps = np.array([(x.size // self.hop + self.delay + 3) * self.hop for x in xs], dtype=np.int64)
+        of = [np.zeros(c, np.float32) for c in caps]
+        o16 = [np.zeros(c, np.int16) for c in caps]
+        xh = [np.zeros(c, np.float32) for c in caps] if self.class_outputs else None
+        dh = [np.zeros(c, np.float32) for c in caps] if self.class_outputs else None
+        P = C.c_void_p * S
+        ptrs = lambda arrs: P(*[a.ctypes.data if a.size else None for a in arrs])  # noqa: E731
+        n = np.array([x.size for x in xs], dtype=np.int64)
+        f32 = np.array(fl, dtype=np.int32)
+        n_out = np.zeros(S, dtype=np.int64)
+        _lib.check(self._lib.snmf_online_batch_process_f32(
+            self._h, ptrs(xs), n.ctypes.data, f32.ctypes.data, P(*[a.ctypes.data for a in of]), P(*[a.ctypes.data for a in o16]),
+            P(*[a.ctypes.data for a in xh]) if xh else None, P(*[a.ctypes.data for a in dh]) if dh else None, caps.ctypes.data,
+            n_out.ctypes.data))
+        outs = []
+        for k in range(S):
+            m = int(n_out[k])
+            o = {"x_tilde": o16[k][:m], "x_tilde_f": of[k][:m]}
+            if self.class_outputs:
+                o["x_hat"], o["d_hat"] = xh[k][:m], dh[k][:m]
+            outs.append(o)
+        return outs
+
+    def basis(self, k):
+        """Current B_DFT_d of stream k."""
+        B = np.zeros((self.F, self.R_d), dtype=np.float32, order="F")
+        _lib.check(self._lib.snmf_online_batch_get_basis_f32(self._h, int(k), B.ctypes.data, self.F))
+        return B.astype(np.float64)
+
+    def trace(self, k):
+        """Per-frame diagnostics of stream k, as OnlineSeparator.trace."""
+        n = C.c_int64()
+        _lib.check(self._lib.snmf_online_batch_trace(self._h, int(k), None, 0, C.byref(n)))
+        arr = (SnmfOnlineFrame * max(1, n.value))()
+        _lib.check(self._lib.snmf_online_batch_trace(self._h, int(k), C.cast(arr, C.c_void_p), n.value, C.byref(n)))
+        return [{f: getattr(arr[i], f) for f, _ in SnmfOnlineFrame._fields_} for i in range(n.value)]
+
+    def close(self):
+        if getattr(self, "_h", None):
+            if getattr(self.ctx, "_h", None):
+                self._lib.snmf_online_batch_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def ntf_sep_event_rt_batch(pcms, B_DFT_x, B_DFT_d, p, H0=None, Ad_blk0=None, ctx=None):
+    """src/NTF_sep_event_RT.m for several recordings at once (the per-target loop of Do_MultiBatch_IS16_20160324.m:183-205
+    as one batch): returns a list of the (int16, float, final B_DFT_d) triples ntf_sep_event_rt returns."""
+    sep = OnlineBatchSeparator(B_DFT_x, B_DFT_d, p, len(pcms), H0=H0, Ad_blk0=Ad_blk0, ctx=ctx)
+    try:
+        outs = sep.process(list(pcms), flush=True)
+        return [(o["x_tilde"].copy(), o["x_tilde_f"].astype(np.float64), sep.basis(k)) for k, o in enumerate(outs)]
     finally:
         sep.close()
