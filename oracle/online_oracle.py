@@ -234,6 +234,8 @@ def sep_frame(y, l, g, p, H0):
                 qa = dict(cf=p["cf"], sparsity=p["sparsity"], max_iter=p["max_iter"], conv_eps=p["conv_eps"],
                           cost_check=p["cost_check"], init_w=up, init_h=Ad_up,
                           w_update_ind=np.ones(up.shape[1], bool), h_update_ind=np.zeros(up.shape[1], bool))
+                if "beta_div" in p:  # the same p (hence the same divergence) as the frame solve above (:315 / :335)
+                    qa["beta"] = p["beta_div"]
                 B_tmp, _, oa = sparse_nmf(Vad, qa)  # :315 / :335
                 adapt_iters = oa["n_iter"]
                 g["B_Mel_d" if mel else "B_DFT_d"] = np.concatenate([rem, B_tmp, fix], axis=1)  # :318 / :336

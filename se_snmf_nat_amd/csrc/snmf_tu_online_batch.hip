@@ -192,7 +192,9 @@ extern "C" int snmf_online_batch_create(snmf_ctx* ctx, const snmf_online_params*
     H(hipMemcpyAsync(o->dev, d0.data(), SS * sizeof(OnlineDev), hipMemcpyHostToDevice, st));
     H(hipMemsetAsync(o->Wcf, 0, SS * rp * Fp * 4, st));
     H(hipMemsetAsync(o->wx, 0, SS * rp * 4, st));
-    H(hipMemsetAsync(o->dphv, 0, SS * rp * 4, st));
+    // 1.0f everywhere: k_obrefresh writes the r real columns; the pad columns r..rp-1 that k_hsolve_frame's register block
+    // spans (r < 8 * KB) must divide by something finite (0 * 0 / 0 was NaN in every pad activation and cost)
+    H(hipMemsetD32Async((hipDeviceptr_t)o->dphv, 0x3f800000, SS * rp, st));
     H(hipMemsetAsync(o->Hin, 0, SS * rp * 4, st));
     H(hipMemsetAsync(o->wn, 0, SS * rp * 8, st));
     H(hipMemsetAsync(o->lambda_dav, 0, SS * F * 4, st));

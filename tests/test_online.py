@@ -99,7 +99,7 @@ def test_blk_sparse_literal_semantics():
 def _device(s, Bx, Bd, p, H0, Ad0, **kw):
     from se_snmf_nat_amd.online import OnlineSeparator, default_settings
     ps = default_settings()
-    ps.update({k: v for k, v in p.items() if k in ps})
+    ps.update({k: v for k, v in p.items() if k in ps or k == "beta_div"})  # (beta_div: the divergence of cf = 'x')
     sep = OnlineSeparator(Bx, Bd, ps, H0=H0, Ad_blk0=Ad0, **kw)
     out = sep.process(s, flush=True)
     tr, Bn = sep.trace(), sep.basis()
@@ -157,6 +157,16 @@ VARIANTS = [
     dict(conv_eps=0.0, max_iter=12),
     dict(basis_update_N=1, max_iter=30),   # semi-supervised frame solve (:125-127)
     dict(basis_update_E=1, max_iter=30, adapt_train_N=0),
+    # generic beta (src/sparse_nmf.m:200-205): k_hsolve_frame<BM_GEN, RECON> for the frame solve.  The beta = 0.5 / 1.5
+    # runs carry no stop test and no adaptation: on the all-zero flush frames (src/NTF_sep_event_RT.m:69-76, V at the 1e-9
+    # floor) their divergence terms cancel from O(v^beta) in fp32, and the stop index of those frames moved by one or two
+    # iterations (measured: 6 against 7, 79 against 81) and, with adaptation, the trigger of the first flush frame
+    # (Q_control * A_d_mag > A_x_mag between numbers at the floor) flipped, while every other frame's decision matched.
+    # The generic-beta adaptation runs in tests/test_online_batch.py's WADAPT_CASES (k_wadapt_batch<BM_GEN>).
+    # (Found with them: the oracle's adaptation solve ignored beta_div and ran KL; the reference passes one p to both solves.)
+    dict(cf="x", beta_div=1.5, adapt_train_N=0, conv_eps=0.0, max_iter=30),
+    dict(cf="x", beta_div=0.5, adapt_train_N=0, conv_eps=0.0, max_iter=30),
+    dict(cf="is", adapt_train_N=0),
 ]
 REL_OUT_ED_ADAPT = 2e-3  # see the module docstring
 
@@ -237,6 +247,14 @@ GEOMETRIES = [
     # does not fit the persistent frame-solve kernels; the frame solve runs through the plan loop on 16-frame tiles
     (1024, 640, 160, 500, 500, dict()),
     (1024, 640, 160, 500, 500, dict(adapt_train_N=0)),
+    # the smallest transforms (k_ostft / k_oistft at LOGN 6 and 7: F = 33, 65)
+    (64, 64, 16, 8, 12, dict(R_a=6, m_a=12, overlap_m_a=0.2, Ar_up=2.0, P_len_k=8, P_len_l=4, init_N_len=4, DCbin=1, DCbin_back=1, delay=2)),
+    (128, 100, 25, 16, 20, dict(R_a=12, m_a=16, overlap_m_a=0.1, Ar_up=2.0, P_len_k=12, P_len_l=5, init_N_len=5, DCbin=2, DCbin_back=2)),
+    # the largest (LOGN 11 and 12: F = 1025, 2049): the frame solve leaves the register-resident frame kernel (F > 513)
+    (2048, 1600, 400, 40, 40, dict(R_a=24, m_a=30, overlap_m_a=0.05, Ar_up=2.0, P_len_k=100, P_len_l=6, init_N_len=4, DCbin=5, DCbin_back=5)),
+    (4096, 3200, 400, 32, 32, dict(R_a=16, m_a=20, overlap_m_a=0.1, Ar_up=2.0, P_len_k=200, P_len_l=6, init_N_len=4, DCbin=10, DCbin_back=10)),
+    # R_a > 64 (kWaRP): the adaptation solve takes the plan path instead of the cooperative kernel
+    (1024, 640, 160, 72, 128, dict(R_a=80, m_a=80, overlap_m_a=0.05, Ar_up=2.0, sparsity=1.0)),
 ]
 
 

@@ -12,6 +12,9 @@ from oracle.online_oracle import default_params, ntf_sep_event_rt
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 REL_OUT = 1e-4
 REL_OUT_ED_ADAPT = 2e-3  # tests/test_online.py: the Euclidean variant with adaptation carries its own bound
+# beta = 0.5 / 1.5 with 30 un-stopped frame iterations: the third stream of the beta = 0.5 variant measured 1.1e-4 (every
+# decision equal); the generic update's fp32 pow (lam^(beta-2) through den) leaves a little more per frame than KL's ratio
+REL_OUT_GEN = 3e-4
 
 
 def _fixture():
@@ -45,7 +48,7 @@ def _streams(n_hops, S=5, seed=11):
 def _settings(p):
     from se_snmf_nat_amd.online import default_settings
     ps = default_settings()
-    ps.update({k: v for k, v in p.items() if k in ps})
+    ps.update({k: v for k, v in p.items() if k in ps or k == "beta_div"})  # (beta_div: the divergence of cf = 'x')
     return ps
 
 
@@ -222,6 +225,10 @@ VARIANTS = [
     dict(preemph=0.92, pow=1),
     dict(cf="ed", sparsity=50.0),
     dict(conv_eps=0.0, max_iter=12),
+    # generic beta: k_hsolve_frame<BM_GEN, RECON, BATCH> (tests/test_online.py's VARIANTS).  beta = 1.5 runs in WADAPT_CASES
+    # instead: here the 2-hop stream's class outputs decay to ~1e-65 under it (fp64), below fp32's range
+    dict(cf="x", beta_div=0.5, adapt_train_N=0, conv_eps=0.0, max_iter=30),
+    dict(cf="is", adapt_train_N=0),
 ]
 
 
@@ -232,9 +239,115 @@ def test_variants_match_the_oracle(gpu_ctx, var):
     pcms, Bx, Bds, H0s, Ads = _streams(36, S=3, seed=3)
     res = _run_batch(gpu_ctx, pcms, Bx, Bds, p, H0s, Ads, class_outputs=True)
     tol = REL_OUT_ED_ADAPT if (var.get("cf") == "ed" and p.get("adapt_train_N", 1)) else REL_OUT
+    if var.get("cf") == "x":
+        tol = REL_OUT_GEN
     for k in range(3):
         ref = ntf_sep_event_rt(pcms[k], Bx, Bds[k], p, H0s[k], Ads[k], return_trace=True, class_outputs=True)
         _check_vs_oracle(*res[k], ref, tol=tol, cls=True)
+
+
+KB = 1024
+
+
+def wbatch_lds(Ra, ma, beta_div):
+    """Dynamic LDS of k_wadapt_batch in bytes: wbatch_lds() of snmf_online_batch.h with kWbNW = 16 waves, kWbRB = 4 rows per
+    block and RA2 = R_a rounded up to 64 (the lane layout: a second column per lane when R_a > 64)."""
+    NW, RB, RA2 = 16, 4, (Ra + 63) // 64 * 64
+    doubles = 5 * RA2 + NW * 2 * RA2 + 2 * NW
+    floats = ((Ra * ma + 3) & ~3) + ma * RA2 + NW * (RB * Ra + RB * ma * (1 if beta_div == 1.0 else 2))
+    return doubles * 8 + floats * 4
+
+
+def _geo_streams(geo, n_hops, S=3, seed=11):
+    """_streams for another geometry (tests/test_online.py's GEOMETRIES form): S streams with different signals (offset,
+    scale, noise), lengths, H0 / Ad_blk0 and initial noise dictionaries."""
+    from test_online import _random_setup
+    fft, sz, hop, R_x, R_d, over = geo
+    Bx, Bd, win = _random_setup(fft, fft, sz, hop, R_x, R_d)
+    p = dict(default_params(), fftlength=fft, framelength=sz, frameshift=hop, win_STFT=win, win_ISTFT=win.copy(),
+             overlapscale=2 * hop / sz)
+    p.update(over)
+    s, _, _ = _fixture()
+    rs = np.random.RandomState(seed)
+    lens = [n_hops * hop, (n_hops - 7) * hop + hop // 3, (n_hops - 3) * hop][:S]
+    pcms, Bds, H0s, Ads = [], [], [], []
+    for k in range(S):
+        off = (k * 1733) % (len(s) - lens[k])
+        pcms.append(np.round(s[off:off + lens[k]] * (0.5 + 0.25 * k) + rs.randn(lens[k]) * 30.0 * k))
+        Bds.append(Bd[:, rs.permutation(R_d)] if k % 2 else (Bd * (1.0 + 0.05 * rs.random_sample(Bd.shape)) if k else Bd.copy()))
+        H0s.append(rs.random_sample(R_x + R_d))
+        Ads.append(rs.random_sample((p["R_a"], p["m_a"])))
+    return p, pcms, Bx, Bds, H0s, Ads
+
+
+def _batch_geometries():
+    from test_online import GEOMETRIES
+    # (the R_a = 80 entry is WADAPT_CASES' first, on a shorter stream)
+    return [g for g in GEOMETRIES if g[0] in (64, 128, 256, 512, 1024) and g[3] + g[4] <= 200 and g[5].get("R_a", 50) <= 64]
+
+
+# k_wadapt_batch off the shipped 50 x 100 ring (R_x = 72, R_d = 128 at the shipped transform): R_a > 64 puts a second
+# column on every lane (RA2 = 128), m_a <= 64 takes one trip of the frame loop.  The ring stays at least as long as R_a
+# except in the R_a = 128 case, which is short (an under-determined ring lets fp32 rounding move stop decisions,
+# tests/test_online.py's geometry docstring).
+WADAPT_CASES = [
+    (dict(R_a=80, m_a=80), 30),
+    (dict(R_a=64, m_a=128), 30),
+    (dict(R_a=72, m_a=72, cf="x", beta_div=1.5, conv_eps=0.0, max_iter=30), 30),
+    (dict(R_a=128, m_a=40), 14),
+    (dict(R_a=40, m_a=48), 30),
+]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", [("geo", g) for g in _batch_geometries()] + [("wadapt", c) for c in WADAPT_CASES],
+                         ids=lambda c: (f"fft{c[1][0]}-sz{c[1][1]}-hop{c[1][2]}-r{c[1][3]}+{c[1][4]}" if c[0] == "geo" else
+                                        "wadapt-" + "-".join(f"{k}={v}" for k, v in c[1][0].items())))
+def test_heterogeneous_batch_off_the_shipped_geometry(gpu_ctx, case):
+    """S = 3 heterogeneous streams per launch at other transforms (k_obstft / k_obistft at LOGN 6..10), dictionary sizes
+    (k_hsolve_frame<FB, KB, ..., BATCH = true> at FB = 4 and 8: the per-stream strides rp * Fp with other Fp) and
+    adaptation rings (k_wadapt_batch with R_a > 64, m_a = 128, m_a <= 64, generic beta); every stream against its own
+    fp64 oracle run (src/NTF_sep_event_RT.m:67-124, src/bnmf_sep_event_RT_IS16.m:65-363).
+    Found here: snmf_online_batch_create left the pad entries r..rp-1 of dphv at 0, so whenever r < 8 * KB (r = 20, 36,
+    120) every pad activation became 0 * 0 / 0 = NaN and every frame solve ran to max_iter."""
+    kind, c = case
+    if kind == "geo":
+        geo, n_hops = c, 36
+    else:
+        over, n_hops = c
+        geo = (1024, 640, 160, 72, 128, dict(overlap_m_a=0.05, Ar_up=2.0, sparsity=1.0, **over))
+        assert wbatch_lds(over["R_a"], over["m_a"], over.get("beta_div", 1.0)) < 160 * KB
+    p, pcms, Bx, Bds, H0s, Ads = _geo_streams(geo, n_hops)
+    res = _run_batch(gpu_ctx, pcms, Bx, Bds, p, H0s, Ads, class_outputs=True)
+    for k in range(len(pcms)):
+        ref = ntf_sep_event_rt(pcms[k], Bx, Bds[k], p, H0s[k], Ads[k], return_trace=True, class_outputs=True)
+        _check_vs_oracle(*res[k], ref, cls=True)
+    if p["adapt_train_N"]:
+        assert sum(t["solved"] for t in res[0][1]) > 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("geo", [(512, 400, 100, 24, 40, dict(P_len_k=30, P_len_l=6, init_N_len=4, DCbin=3, DCbin_back=3)),
+                                 (128, 100, 25, 16, 20, dict(P_len_k=12, P_len_l=5, init_N_len=5, DCbin=2, DCbin_back=2))],
+                         ids=["fft512-r24+40", "fft128-r16+20"])
+def test_batch_equals_single_stream_without_adaptation(gpu_ctx, geo):
+    """With adapt_train_N = 0 a batch stream runs the same per-frame work as OnlineSeparator: identical decision traces
+    and x_tilde_f within 1e-6.  (Not bit-identical: the single-stream separator solves each frame through the plan's
+    launch_small and its own STFT / post-filter kernels, the batch through the BATCH forms with another reduction order.)"""
+    from se_snmf_nat_amd.online import OnlineSeparator
+    fft, sz, hop, R_x, R_d, over = geo
+    p, pcms, Bx, Bds, H0s, Ads = _geo_streams((fft, sz, hop, R_x, R_d, dict(over, adapt_train_N=0, R_a=4, m_a=4)), 30)
+    res = _run_batch(gpu_ctx, pcms, Bx, Bds, p, H0s, Ads)
+    for k in range(len(pcms)):
+        sep = OnlineSeparator(Bx, Bds[k], _settings(p), H0=H0s[k], Ad_blk0=Ads[k], ctx=gpu_ctx)
+        out = sep.process(pcms[k], flush=True)
+        tr = sep.trace()
+        sep.close()
+        assert _decisions(res[k][1]) == _decisions(tr)
+        a, b = res[k][0]["x_tilde_f"], out["x_tilde_f"]
+        assert len(a) == len(b) and np.array_equal(np.isfinite(a), np.isfinite(b))
+        ok = np.isfinite(b)
+        assert np.linalg.norm(a[ok] - b[ok]) / np.linalg.norm(b[ok]) < 1e-6
 
 
 @pytest.mark.gpu
@@ -279,6 +392,30 @@ def test_error_codes(gpu_ctx):
     with pytest.raises(_lib.SnmfError) as e:
         OnlineBatchSeparator(Bx, Bd[:, :50].T, p, 2, ctx=gpu_ctx)
     assert e.value.status == 1
+    # outside the batch envelope: the frame kernel's F <= 513 and r <= 200, k_wadapt_batch's LDS (snmf_online_batch.h:
+    # wbatch_lds); after each refusal a valid separator is still made and still runs
+    from test_online import _random_setup
+    s, _, _ = _fixture()
+    Bx2, Bd2, win2 = _random_setup(2048, 2048, 1600, 400, 40, 40)
+    p2048 = dict(p, fftlength=2048, framelength=1600, frameshift=400, win_STFT=win2, win_ISTFT=win2.copy(), overlapscale=0.5,
+                 R_a=24, m_a=30, P_len_k=100)
+    refused = [(Bx2, Bd2, p2048), (rs.random_sample((Bx.shape[0], 100)), rs.random_sample((Bx.shape[0], 101)), p)]
+    Bx3, Bd3 = rs.random_sample((Bx.shape[0], 72)), rs.random_sample((Bx.shape[0], 128))
+    for Ra, ma in ((128, 128), (100, 100)):
+        assert wbatch_lds(Ra, ma, 1.0) > 160 * KB
+        refused.append((Bx3, Bd3, dict(p, R_a=Ra, m_a=ma)))
+    def valid_run():
+        ok = OnlineBatchSeparator(Bx, Bd, p, 2, ctx=gpu_ctx)
+        outs = ok.process([s[:1600], s[800:2400]], flush=True)
+        ok.close()
+        return [o["x_tilde_f"] for o in outs]
+    before = valid_run()
+    for bx, bd, q in refused:
+        with pytest.raises(_lib.SnmfError) as e:
+            OnlineBatchSeparator(bx, bd, q, 2, ctx=gpu_ctx, Ad_blk0=[np.ones((q["R_a"], q["m_a"]))] * 2)
+        assert e.value.status == 8
+        after = valid_run()
+        assert all(np.array_equal(a, b, equal_nan=True) for a, b in zip(before, after))
     # the C entry itself: S = 0 is INVALID
     sep = OnlineBatchSeparator(Bx, Bd, p, 2, ctx=gpu_ctx)
     h = C.c_void_p()
