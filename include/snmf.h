@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SNMF_ABI_VERSION 5  /* 5: snmf_online_batch_* (added within 5: new entries only), snmf_multi_release_cache, snmf_multi_cached_teams, snmf_rccl_*, snmf_plan_run_sharded_rccl (the device RNG of snmf_plan_set_h_random changed with 4: draws seeded under ABI 3 are not reproducible); 4: snmf_run_basis_dnmf_multi_*; 3: snmf_run_basis_dnmf_*, snmf_run_basis_train_audio_f64, snmf_sparse_nmf_oop_*, snmf_plan_set_h_random, snmf_ctx_xfer_stats; 2: snmf_multi_* */
+#define SNMF_ABI_VERSION 5  /* 5: snmf_online_batch_* incl. _restart / _get_basis_f64 (added within 5: new entries only), snmf_multi_release_cache, snmf_multi_cached_teams, snmf_rccl_*, snmf_plan_run_sharded_rccl (the device RNG of snmf_plan_set_h_random changed with 4: draws seeded under ABI 3 are not reproducible); 4: snmf_run_basis_dnmf_multi_*; 3: snmf_run_basis_dnmf_*, snmf_run_basis_train_audio_f64, snmf_sparse_nmf_oop_*, snmf_plan_set_h_random, snmf_ctx_xfer_stats; 2: snmf_multi_* */
 
 typedef enum snmf_status {
     SNMF_OK = 0,
@@ -423,6 +423,21 @@ int snmf_online_batch_process_f32(snmf_online_batch* b, const float* const* pcm,
                                   float* const* d_hat_f32, const int64_t* cap, int64_t* n_out);
 /* Current B_DFT_d of stream k (src/NTF_sep_event_RT.m:138-140). */
 int snmf_online_batch_get_basis_f32(snmf_online_batch* b, int32_t k, float* B_DFT_d, int64_t ld);
+/* Added within 5.  src/NTF_sep_event_RT.m:27-38 + init_buff for the streams slots[0..n) (distinct): each starts a new
+ * recording, as Do_MultiBatch_IS16_20160324.m:183-205 runs file after file.  Every piece of the stream's state returns to
+ * what snmf_online_batch_create gives a stream with these inputs (rings, smoothed statistics, overlap-add tails, the
+ * dictionary images; the host queue, history, frame count and trace are cleared).
+ * B_DFT_d: F x R_d x n column-major fp64, or NULL = keep each stream's current (adapted) dictionary, i.e.
+ *          load('B_D_u.mat'); the fp64 master is kept as it is, without an fp32 round trip.  A new dictionary also
+ *          becomes the stream's fixed columns (B_Mel_d in DFT mode, src/bnmf_sep_event_RT_IS16.m:328); a carry keeps them.
+ * H0: r x n, Ad_blk0: R_a x m_a x n, or NULL = the values the stream last started with.
+ * A stream that has consumed samples and has not been flushed returns SNMF_ERR_STATE, and so does a failed batch; a
+ * stream that has never been fed may be restarted.  The other streams do not change.  Ordered on the context's stream
+ * before the next process call; no synchronise beyond the uploads. */
+int snmf_online_batch_restart(snmf_online_batch* b, int32_t n, const int32_t* slots, const double* B_DFT_d,
+                              const float* H0, const float* Ad_blk0);
+/* Added within 5.  Stream k's fp64 master of B_DFT_d (what a carry by snmf_online_batch_restart keeps). */
+int snmf_online_batch_get_basis_f64(snmf_online_batch* b, int32_t k, double* B_DFT_d, int64_t ld);
 /* Diagnostics of stream k's most recent frames (the newest 65536 per stream), as snmf_online_trace. */
 int snmf_online_batch_trace(snmf_online_batch* b, int32_t k, snmf_online_frame* out, int64_t cap, int64_t* n);
 void snmf_online_batch_destroy(snmf_online_batch* b);

@@ -7,6 +7,7 @@
 //   k_wadapt_batch the W-only adaptation solve of :296-336, one workgroup per stream, gated on the device
 //   k_obassemble / k_obrefresh  the re-assembly of :336 and the next frame solve's dictionary images, gated
 //   k_obistft / k_obtail / k_obola  inverse STFT and overlap-add of src/NTF_sep_event_RT.m:104-124
+//   k_obrestart   the state of the listed streams back to init_buff (a new recording; creation restarts all streams)
 // Frame-indexed buffers are frame-major: the slot of frame i of stream s is i * S + s.  A stream's own state sits at a
 // fixed stride per stream.  Nothing is shared between the streams' workgroups, so a stream's bits do not depend on
 // the other streams of its batch.
@@ -453,9 +454,93 @@ __global__ __launch_bounds__(256) void k_obassemble(const OnlineStatus* status, 
     for (int f = threadIdx.x; f < F; f += blockDim.x) dst[f] = src[f];
 }
 
+// ---------------------------------------------------------------------------------------------
+// k_obrestart: src/NTF_sep_event_RT.m:27-38 + src/init_buff.m:17-42 for the listed streams -- the one initialisation path
+// (snmf_online_batch_create restarts every stream through it).  Grid (listed stream, array, part): each workgroup resets
+// one part of one per-stream array of one listed stream.  No array is both read and written by the launch except
+// through disjoint (stream, array) pairs, so the workgroups are independent.  k_obrefresh (slot list form) follows.
+// ---------------------------------------------------------------------------------------------
+enum : int {
+    kRsBx, kRsBd, kRsBfix, kRsH0, kRsAd0, kRsAdblk, kRsLdblk, kRsRup, kRsLam, kRsXm, kRsRblk, kRsTail, kRsTailX, kRsTailD,
+    kRsDev, kRsWcf, kRsImg, kRsN
+};
+constexpr int kRsParts = 8;  // workgroups per (stream, array)
+
+struct ORestartArgs {
+    const int* slots;       // [n] the streams to restart (distinct, in range: checked on the host)
+    const double* Bx;       // [Rx][F] the shared speech dictionary
+    const double* Bd;       // [n][Rd][F] new noise dictionaries, or NULL = keep each stream's (carry; Bfix untouched)
+    const float* H0n;       // [n][r] or NULL = keep
+    const float* Adn;       // [n][Ra][ma] or NULL = the values the stream last started with (Ad0)
+    double *B, *Bfix;       // [S][r][F], [S][Rd][F]
+    float *H0, *Ad0, *adblk, *ldblk, *lambda_dav, *Xm_tilde, *r_blk, *tail, *tail_x, *tail_d;
+    uint8_t* rup;
+    OnlineDev* dev;
+    float *Wcf, *wx, *dphv, *Hin;
+    double* wn;
+    int F, r, Rx, Rd, Ra, ma, Pl, rp, Fp, adapt;
+    int64_t ntail;
+};
+
+__global__ __launch_bounds__(256) void k_obrestart(ORestartArgs a) {
+    const int i = blockIdx.x, arr = blockIdx.y, s = a.slots[i];
+    const size_t F = a.F, q0 = (size_t)blockIdx.z * 256 + threadIdx.x, qs = (size_t)kRsParts * 256;
+    auto copy = [&](auto* dst, const auto* src, size_t n) {
+        for (size_t e = q0; e < n; e += qs) dst[e] = src[e];
+    };
+    auto fill = [&](auto* dst, auto v, size_t n) {
+        for (size_t e = q0; e < n; e += qs) dst[e] = v;
+    };
+    const size_t nA = (size_t)a.Ra * a.ma;
+    switch (arr) {
+        case kRsBx: copy(a.B + (size_t)s * a.r * F, a.Bx, (size_t)a.Rx * F); break;
+        case kRsBd:
+            if (a.Bd) copy(a.B + (size_t)s * a.r * F + (size_t)a.Rx * F, a.Bd + (size_t)i * a.Rd * F, (size_t)a.Rd * F);
+            break;
+        case kRsBfix:  // B_Mel_d in DFT mode (:328): set with a new dictionary, never adapted (:392)
+            if (a.Bd) copy(a.Bfix + (size_t)s * a.Rd * F, a.Bd + (size_t)i * a.Rd * F, (size_t)a.Rd * F);
+            break;
+        case kRsH0:
+            if (a.H0n) copy(a.H0 + (size_t)s * a.r, a.H0n + (size_t)i * a.r, (size_t)a.r);
+            break;
+        case kRsAd0:
+            if (a.Adn) copy(a.Ad0 + s * nA, a.Adn + i * nA, nA);
+            break;
+        case kRsAdblk:  // rand(R_a, m_a) (src/init_buff.m:39); zeros without adaptation
+            if (!a.adapt) fill(a.adblk + s * nA, 0.f, nA);
+            else copy(a.adblk + s * nA, a.Adn ? a.Adn + i * nA : a.Ad0 + s * nA, nA);
+            break;
+        case kRsLdblk: fill(a.ldblk + (size_t)s * F * a.ma, 0.f, F * a.ma); break;
+        case kRsRup: fill(a.rup + (size_t)s * a.Ra, (uint8_t)0, (size_t)a.Ra); break;
+        case kRsLam: fill(a.lambda_dav + s * F, 0.f, F); break;
+        case kRsXm: fill(a.Xm_tilde + s * F, 0.f, F); break;
+        case kRsRblk: fill(a.r_blk + s * F * a.Pl, 0.f, F * a.Pl); break;
+        case kRsTail: fill(a.tail + s * a.ntail, 0.f, (size_t)a.ntail); break;
+        case kRsTailX:
+            if (a.tail_x) fill(a.tail_x + s * a.ntail, 0.f, (size_t)a.ntail);
+            break;
+        case kRsTailD:
+            if (a.tail_d) fill(a.tail_d + s * a.ntail, 0.f, (size_t)a.ntail);
+            break;
+        case kRsDev:
+            if (q0 == 0) a.dev[s] = OnlineDev{0, 1, 0, 0};  // update_switch = 1 (src/init_buff.m:42)
+            break;
+        case kRsWcf: fill(a.Wcf + (size_t)s * a.rp * a.Fp, 0.f, (size_t)a.rp * a.Fp); break;  // rows >= F stay zero
+        default: {  // kRsImg: k_obrefresh writes the r real columns of these; pads: dphv 1.0f (r < 8 * KB must divide by
+                    // something finite: 0 * 0 / 0 was NaN in every pad activation and cost), the rest 0
+            const size_t o = (size_t)s * a.rp;
+            fill(a.wx + o, 0.f, (size_t)a.rp);
+            fill(a.dphv + o, 1.f, (size_t)a.rp);
+            fill(a.Hin + o, 0.f, (size_t)a.rp);
+            fill(a.wn + o, 0.0, (size_t)a.rp);
+        }
+    }
+}
+
 struct ORefreshArgs {
-    const OnlineStatus* status;  // NULL: every stream, every column (creation)
+    const OnlineStatus* status;  // NULL: every listed stream, every column from k0 (restart)
     const int* nfr;
+    const int* slots;            // NULL: stream blockIdx.y; else stream slots[blockIdx.y]
     int step, S;
     const double* Btmp;  // [S][Rd][F] (status != NULL: the re-assembled noise columns)
     double* B;           // [S][r][F]
@@ -472,7 +557,7 @@ struct ORefreshArgs {
 // The next frame solve's images of the dictionary (set_w + k_wapply's init mode, src/sparse_nmf.m:157-160): per
 // column the norm, W ./ wn in fp32, its column sum, and H0 .* wn.  One workgroup (256 threads) per (column, stream).
 __global__ __launch_bounds__(256) void k_obrefresh(ORefreshArgs a) {
-    const int s = blockIdx.y, k = a.k0 + blockIdx.x, tid = threadIdx.x;
+    const int s = a.slots ? a.slots[blockIdx.y] : blockIdx.y, k = a.k0 + blockIdx.x, tid = threadIdx.x;
     if (k >= a.r) return;
     if (a.status && !ob_due(a.status, a.nfr, a.step, a.S, s)) return;
     __shared__ double red[256];

@@ -19,7 +19,7 @@ struct snmf_online_batch {
     snmf_plan* hp = nullptr;  // the frame solve's geometry, sparsity and beta (one plan serves every stream)
     // per stream, device
     double *B = nullptr, *Bfix = nullptr, *Btmp = nullptr, *wn = nullptr, *Wu = nullptr;
-    float *Wcf = nullptr, *wx = nullptr, *dphv = nullptr, *Hin = nullptr, *H0 = nullptr;
+    float *Wcf = nullptr, *wx = nullptr, *dphv = nullptr, *Hin = nullptr, *H0 = nullptr, *Ad0 = nullptr;
     float *lambda_dav = nullptr, *Xm_tilde = nullptr, *r_blk = nullptr, *ldblk = nullptr, *adblk = nullptr;
     float *G = nullptr, *P = nullptr, *Vt = nullptr;
     float *tail = nullptr, *tail_x = nullptr, *tail_d = nullptr;
@@ -27,6 +27,12 @@ struct snmf_online_batch {
     OnlineDev* dev = nullptr;
     float *win_s = nullptr, *win_i = nullptr;
     float2* tw = nullptr;
+    double* Bxd = nullptr;  // B_DFT_x in fp64, shared
+    // restart uploads (sized for all S streams)
+    int* rs_slots = nullptr;
+    double* rs_B = nullptr;
+    float *rs_H = nullptr, *rs_A = nullptr;
+    size_t ntail = 0;
     // per chunk, device (grown on demand)
     int C = 0;  // frames per stream per chunk
     size_t cap_sig = 0, cap_out = 0;
@@ -70,9 +76,9 @@ extern "C" void snmf_online_batch_destroy(snmf_online_batch* o) {
     hipStreamSynchronize(o->ctx->stream);
     if (o->hp) snmf_plan_destroy(o->hp);
     ob_free_chunk(o);
-    void* ptrs[] = {o->B, o->Bfix, o->Btmp, o->wn, o->Wu, o->Wcf, o->wx, o->dphv, o->Hin, o->H0, o->lambda_dav, o->Xm_tilde,
+    void* ptrs[] = {o->B, o->Bfix, o->Btmp, o->wn, o->Wu, o->Wcf, o->wx, o->dphv, o->Hin, o->H0, o->Ad0, o->lambda_dav, o->Xm_tilde,
                     o->r_blk, o->ldblk, o->adblk, o->G, o->P, o->Vt, o->tail, o->tail_x, o->tail_d, o->rup, o->dev, o->win_s,
-                    o->win_i, o->tw, o->meta_i, o->meta_l};
+                    o->win_i, o->tw, o->Bxd, o->rs_slots, o->rs_B, o->rs_H, o->rs_A, o->meta_i, o->meta_l};
     for (void* q : ptrs)
         if (q) hipFree(q);
     delete o;
@@ -104,6 +110,46 @@ static int ob_validate(const snmf_online_params* p, int32_t S) {
     }
     if (p->basis_update_N || p->basis_update_E)
         return fail(SNMF_ERR_UNSUPPORTED, "batched separator: semi-supervised frame solves (basis_update_N / _E) are not supported");
+    return SNMF_OK;
+}
+
+// The streams slots[0..n) start a new recording (src/NTF_sep_event_RT.m:27-38 + src/init_buff.m): the uploads, one
+// k_obrestart, one k_obrefresh over their columns, and their host state.  Arguments are checked by the caller; Bd is
+// n x Rd x F fp64 or NULL (carry), H0 n x r or NULL, Ad n x Ra x ma or NULL.  Ordered on ctx->stream, no synchronise
+// (the uploads come from pageable host memory, which the runtime copies before it returns).
+static int ob_restart(snmf_online_batch* o, int n, const int32_t* slots, const double* Bd, const float* H0, const float* Ad) {
+    const snmf_online_params& p = o->p;
+    hipStream_t st = o->ctx->stream;
+    const size_t F = o->F, nA = (size_t)o->Ra * o->ma;
+    HIP_TRY(hipMemcpyAsync(o->rs_slots, slots, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    if (Bd) HIP_TRY(hipMemcpyAsync(o->rs_B, Bd, (size_t)n * p.R_d * F * 8, hipMemcpyHostToDevice, st));
+    if (H0) HIP_TRY(hipMemcpyAsync(o->rs_H, H0, (size_t)n * o->r * 4, hipMemcpyHostToDevice, st));
+    if (Ad) HIP_TRY(hipMemcpyAsync(o->rs_A, Ad, (size_t)n * nA * 4, hipMemcpyHostToDevice, st));
+    ORestartArgs a{};
+    a.slots = o->rs_slots; a.Bx = o->Bxd; a.Bd = Bd ? o->rs_B : nullptr; a.H0n = H0 ? o->rs_H : nullptr; a.Adn = Ad ? o->rs_A : nullptr;
+    a.B = o->B; a.Bfix = o->Bfix; a.H0 = o->H0; a.Ad0 = o->Ad0; a.adblk = o->adblk; a.ldblk = o->ldblk; a.lambda_dav = o->lambda_dav;
+    a.Xm_tilde = o->Xm_tilde; a.r_blk = o->r_blk; a.tail = o->tail; a.tail_x = o->tail_x; a.tail_d = o->tail_d; a.rup = o->rup;
+    a.dev = o->dev; a.Wcf = o->Wcf; a.wx = o->wx; a.dphv = o->dphv; a.Hin = o->Hin; a.wn = o->wn;
+    a.F = o->F; a.r = o->r; a.Rx = p.R_x; a.Rd = p.R_d; a.Ra = o->Ra; a.ma = o->ma; a.Pl = o->Pl; a.rp = o->hp->rp; a.Fp = o->hp->Fp;
+    a.adapt = p.adapt_train_N; a.ntail = (int64_t)o->ntail;
+    hipLaunchKernelGGL(k_obrestart, dim3(n, kRsN, kRsParts), dim3(256), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    // every column's dictionary images (set_w + the init mode of k_wapply)
+    ORefreshArgs ra{};
+    ra.slots = o->rs_slots; ra.S = o->S; ra.B = o->B; ra.Wcf = o->Wcf; ra.wx = o->wx; ra.dphv = o->dphv; ra.wn = o->wn; ra.Hin = o->Hin;
+    ra.H0 = o->H0; ra.lamk = o->hp->lamk; ra.F = o->F; ra.r = o->r; ra.Rx = p.R_x; ra.rp = o->hp->rp; ra.Fp = o->hp->Fp;
+    ra.xr = o->F > 64 * o->hp->frame_fb; ra.k0 = 0;
+    hipLaunchKernelGGL(k_obrefresh, dim3(o->r, n), dim3(256), 0, st, ra);
+    HIP_TRY(hipGetLastError());
+    const int sz = p.framelength, hop = p.frameshift;
+    for (int i = 0; i < n; ++i) {
+        const int s = slots[i];
+        o->pending[s].clear();
+        o->hist[s].assign((size_t)(sz - hop), 0.f);
+        o->l[s] = 0;
+        o->finished[s] = 0;
+        o->trace[s].clear();
+    }
     return SNMF_OK;
 }
 
@@ -150,11 +196,12 @@ extern "C" int snmf_online_batch_create(snmf_ctx* ctx, const snmf_online_params*
     }
     const size_t SS = (size_t)S, rp = o->hp->rp, Fp = o->hp->Fp, Fb = (size_t)(F + kWbRB - 1) / kWbRB * kWbRB;
     const size_t ntail = (size_t)std::max(1, o->nov - 1) * sz;
+    o->ntail = ntail;
     auto D = [&](auto** ptr, size_t n) { if (s == SNMF_OK) s = dalloc(ptr, n); };
     D(&o->B, SS * r * F); D(&o->Bfix, SS * Rd * F); D(&o->Btmp, SS * Rd * F); D(&o->wn, SS * rp);
     D(&o->Wcf, SS * rp * Fp); D(&o->wx, SS * rp); D(&o->dphv, SS * rp); D(&o->Hin, SS * rp); D(&o->H0, SS * r);
     D(&o->lambda_dav, SS * F); D(&o->Xm_tilde, SS * F); D(&o->r_blk, SS * F * o->Pl); D(&o->ldblk, SS * F * o->ma);
-    D(&o->adblk, SS * o->Ra * o->ma); D(&o->rup, SS * o->Ra); D(&o->dev, SS); D(&o->tail, SS * ntail);
+    D(&o->adblk, SS * o->Ra * o->ma); D(&o->Ad0, SS * o->Ra * o->ma); D(&o->rup, SS * o->Ra); D(&o->dev, SS); D(&o->tail, SS * ntail);
     if (p->class_outputs) {
         D(&o->tail_x, SS * ntail);
         D(&o->tail_d, SS * ntail);
@@ -163,7 +210,8 @@ extern "C" int snmf_online_batch_create(snmf_ctx* ctx, const snmf_online_params*
         D(&o->Wu, SS * o->Ra * F); D(&o->G, SS * Fb * o->RA2); D(&o->Vt, SS * Fb * o->ma);
         if (p->beta_div != 1.0) D(&o->P, SS * Fb * o->RA2);
     }
-    D(&o->win_s, (size_t)sz); D(&o->win_i, (size_t)sz); D(&o->tw, (size_t)N / 2);
+    D(&o->win_s, (size_t)sz); D(&o->win_i, (size_t)sz); D(&o->tw, (size_t)N / 2); D(&o->Bxd, (size_t)F * p->R_x);
+    D(&o->rs_slots, SS); D(&o->rs_B, SS * Rd * F); D(&o->rs_H, SS * r); D(&o->rs_A, SS * o->Ra * o->ma);
     D(&o->meta_i, 6 * SS); D(&o->meta_l, 3 * SS);
     if (s != SNMF_OK) {
         snmf_online_batch_destroy(o);
@@ -174,59 +222,31 @@ extern "C" int snmf_online_batch_create(snmf_ctx* ctx, const snmf_online_params*
         const double ang = -2.0 * M_PI * (double)q / (double)N;
         htw[q] = make_float2((float)cos(ang), (float)sin(ang));
     }
-    std::vector<double> hB(SS * r * F), hfix(SS * Rd * F);
-    for (size_t k = 0; k < SS; ++k) {
-        double* b = hB.data() + k * r * F;
-        for (size_t i = 0; i < (size_t)F * p->R_x; ++i) b[i] = (double)Bx[i];
-        for (size_t i = 0; i < (size_t)F * Rd; ++i) b[(size_t)F * p->R_x + i] = hfix[k * Rd * F + i] = (double)Bd0[k * Rd * F + i];
-    }
-    std::vector<OnlineDev> d0(SS, OnlineDev{0, 1, 0, 0});  // update_switch = 1 (src/init_buff.m:42)
+    std::vector<double> hx((size_t)F * p->R_x), hd(SS * Rd * F);
+    for (size_t i = 0; i < hx.size(); ++i) hx[i] = (double)Bx[i];
+    for (size_t i = 0; i < hd.size(); ++i) hd[i] = (double)Bd0[i];
     int e = 0;
     auto H = [&](hipError_t x) { if (x != hipSuccess && !e) e = (int)x; };
-    H(hipMemcpyAsync(o->B, hB.data(), hB.size() * 8, hipMemcpyHostToDevice, st));
-    H(hipMemcpyAsync(o->Bfix, hfix.data(), hfix.size() * 8, hipMemcpyHostToDevice, st));  // B_Mel_d in DFT mode (:328)
-    H(hipMemcpyAsync(o->H0, H0, SS * r * 4, hipMemcpyHostToDevice, st));
     H(hipMemcpyAsync(o->win_s, win_stft, (size_t)sz * 4, hipMemcpyHostToDevice, st));
     H(hipMemcpyAsync(o->win_i, win_istft, (size_t)sz * 4, hipMemcpyHostToDevice, st));
     H(hipMemcpyAsync(o->tw, htw.data(), htw.size() * 8, hipMemcpyHostToDevice, st));
-    H(hipMemcpyAsync(o->dev, d0.data(), SS * sizeof(OnlineDev), hipMemcpyHostToDevice, st));
-    H(hipMemsetAsync(o->Wcf, 0, SS * rp * Fp * 4, st));
-    H(hipMemsetAsync(o->wx, 0, SS * rp * 4, st));
-    // 1.0f everywhere: k_obrefresh writes the r real columns; the pad columns r..rp-1 that k_hsolve_frame's register block
-    // spans (r < 8 * KB) must divide by something finite (0 * 0 / 0 was NaN in every pad activation and cost)
-    H(hipMemsetD32Async((hipDeviceptr_t)o->dphv, 0x3f800000, SS * rp, st));
-    H(hipMemsetAsync(o->Hin, 0, SS * rp * 4, st));
-    H(hipMemsetAsync(o->wn, 0, SS * rp * 8, st));
-    H(hipMemsetAsync(o->lambda_dav, 0, SS * F * 4, st));
-    H(hipMemsetAsync(o->Xm_tilde, 0, SS * F * 4, st));
-    H(hipMemsetAsync(o->r_blk, 0, SS * F * o->Pl * 4, st));
-    H(hipMemsetAsync(o->ldblk, 0, SS * F * o->ma * 4, st));
-    H(hipMemsetAsync(o->adblk, 0, SS * o->Ra * o->ma * 4, st));
-    H(hipMemsetAsync(o->rup, 0, SS * o->Ra, st));
-    H(hipMemsetAsync(o->tail, 0, SS * ntail * 4, st));
-    if (p->class_outputs) {
-        H(hipMemsetAsync(o->tail_x, 0, SS * ntail * 4, st));
-        H(hipMemsetAsync(o->tail_d, 0, SS * ntail * 4, st));
-    }
-    if (p->adapt_train_N) H(hipMemcpyAsync(o->adblk, Ad0, SS * o->Ra * o->ma * 4, hipMemcpyHostToDevice, st));  // R_a x m_a per stream
-    // every stream's dictionary images (set_w + the init mode of k_wapply)
-    ORefreshArgs ra{};
-    ra.S = S; ra.B = o->B; ra.Wcf = o->Wcf; ra.wx = o->wx; ra.dphv = o->dphv; ra.wn = o->wn; ra.Hin = o->Hin; ra.H0 = o->H0;
-    ra.lamk = o->hp->lamk; ra.F = F; ra.r = r; ra.Rx = p->R_x; ra.rp = (int)rp; ra.Fp = (int)Fp; ra.xr = F > 64 * o->hp->frame_fb;
-    ra.k0 = 0;
-    hipLaunchKernelGGL(k_obrefresh, dim3(r, S), dim3(256), 0, st, ra);
-    H(hipGetLastError());
-    H(hipStreamSynchronize(st));
-    if (e) {
-        snmf_online_batch_destroy(o);
-        return fail(e == (int)hipErrorOutOfMemory ? SNMF_ERR_NOMEM : SNMF_ERR_NO_DEVICE, "online batch create: %s",
-                    hipGetErrorString((hipError_t)e));
-    }
+    H(hipMemcpyAsync(o->Bxd, hx.data(), hx.size() * 8, hipMemcpyHostToDevice, st));
     o->pending.assign(SS, {});
-    o->hist.assign(SS, std::vector<float>((size_t)(sz - hop), 0.f));
+    o->hist.assign(SS, {});
     o->l.assign(SS, 0);
     o->finished.assign(SS, 0);
     o->trace.resize(SS);
+    // every stream's state g: a restart of all S streams (the one initialisation path)
+    std::vector<int32_t> all(SS);
+    for (int k = 0; k < S; ++k) all[k] = k;
+    const int rc = e ? SNMF_OK : ob_restart(o, S, all.data(), hd.data(), H0, p->adapt_train_N ? Ad0 : nullptr);
+    H(hipStreamSynchronize(st));
+    if (e || rc) {
+        snmf_online_batch_destroy(o);
+        if (!e) return rc;
+        return fail(e == (int)hipErrorOutOfMemory ? SNMF_ERR_NOMEM : SNMF_ERR_NO_DEVICE, "online batch create: %s",
+                    hipGetErrorString((hipError_t)e));
+    }
     *out = o;
     return SNMF_OK;
 }
@@ -544,7 +564,8 @@ extern "C" int snmf_online_batch_process_f32(snmf_online_batch* o, const float* 
     std::vector<int64_t> nfr_tot(S), tail(S);
     for (int s = 0; s < S; ++s) {
         if (n[s] < 0 || (n[s] > 0 && !pcm[s])) return fail(SNMF_ERR_INVALID, "stream %d: pcm is NULL", s);
-        if (o->finished[s] && (n[s] > 0 || (flush && flush[s]))) return fail(SNMF_ERR_STATE, "stream %d was flushed; create a new batch", s);
+        if (o->finished[s] && (n[s] > 0 || (flush && flush[s])))
+            return fail(SNMF_ERR_STATE, "stream %d was flushed; restart it before feeding it", s);
         nfr_tot[s] = ((int64_t)o->pending[s].size() + n[s]) / hop;
         tail[s] = (flush && flush[s] && !o->finished[s]) ? p.delay + 1 : 0;
         const int64_t need = (nfr_tot[s] + tail[s]) * hop;
@@ -604,6 +625,47 @@ extern "C" int snmf_online_batch_get_basis_f32(snmf_online_batch* o, int32_t k, 
     HIP_TRY(hipMemcpy(h.data(), o->B + (size_t)k * o->r * F + (size_t)o->p.R_x * F, h.size() * 8, hipMemcpyDeviceToHost));
     for (size_t j = 0; j < Rd; ++j)
         for (size_t f = 0; f < F; ++f) Bd[j * ld + f] = (float)h[j * F + f];  // the single-stream separator's fp32 mirror
+    return SNMF_OK;
+}
+
+extern "C" int snmf_online_batch_get_basis_f64(snmf_online_batch* o, int32_t k, double* Bd, int64_t ld) {
+    if (!o || !Bd) return fail(SNMF_ERR_INVALID, "NULL argument");
+    if (k < 0 || k >= o->S) return fail(SNMF_ERR_INVALID, "stream %d out of range [0, %d)", k, o->S);
+    if (ld < o->F) return fail(SNMF_ERR_INVALID, "ld < F");
+    HIP_TRY(hipSetDevice(o->ctx->device));
+    HIP_TRY(hipStreamSynchronize(o->ctx->stream));
+    const size_t F = o->F, Rd = o->p.R_d;
+    std::vector<double> h(F * Rd);
+    HIP_TRY(hipMemcpy(h.data(), o->B + (size_t)k * o->r * F + (size_t)o->p.R_x * F, h.size() * 8, hipMemcpyDeviceToHost));
+    for (size_t j = 0; j < Rd; ++j) std::copy_n(h.data() + j * F, F, Bd + j * ld);  // the fp64 master, as a carry keeps it
+    return SNMF_OK;
+}
+
+extern "C" int snmf_online_batch_restart(snmf_online_batch* o, int32_t n, const int32_t* slots, const double* Bd, const float* H0,
+                                         const float* Ad) {
+    if (!o) return fail(SNMF_ERR_INVALID, "online batch handle is NULL");
+    if (n < 0 || n > o->S) return fail(SNMF_ERR_INVALID, "restart of %d streams in a batch of %d", n, o->S);
+    if (n > 0 && !slots) return fail(SNMF_ERR_INVALID, "slots is NULL");
+    std::vector<uint8_t> seen(o->S, 0);
+    for (int i = 0; i < n; ++i) {
+        const int s = slots[i];
+        if (s < 0 || s >= o->S) return fail(SNMF_ERR_INVALID, "stream %d out of range [0, %d)", s, o->S);
+        if (seen[s]) return fail(SNMF_ERR_INVALID, "stream %d listed twice", s);
+        seen[s] = 1;
+    }
+    if (o->failed) return fail(SNMF_ERR_STATE, "an earlier call failed midway through a chunk; the batch state is not reusable, create a new one");
+    for (int i = 0; i < n; ++i) {
+        const int s = slots[i];
+        if (!o->finished[s] && (o->l[s] > 0 || !o->pending[s].empty()))
+            return fail(SNMF_ERR_STATE, "stream %d is in the middle of a recording; flush it before a restart", s);
+    }
+    if (n == 0) return SNMF_OK;
+    (void)hipGetLastError();  // clean sticky error state, see PLAN_CHECK
+    HIP_TRY(hipSetDevice(o->ctx->device));
+    if (int rc = ob_restart(o, n, slots, Bd, H0, o->p.adapt_train_N ? Ad : nullptr)) {
+        o->failed = true;  // some of the listed streams may be half reset
+        return rc;
+    }
     return SNMF_OK;
 }
 

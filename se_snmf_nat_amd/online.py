@@ -25,7 +25,8 @@ from . import _lib
 from ._lib import SnmfError, SnmfOnlineFrame, SnmfOnlineParams
 from .api import default_context
 
-__all__ = ["default_settings", "OnlineSeparator", "ntf_sep_event_rt", "OnlineBatchSeparator", "ntf_sep_event_rt_batch"]
+__all__ = ["default_settings", "OnlineSeparator", "ntf_sep_event_rt", "OnlineBatchSeparator", "ntf_sep_event_rt_batch",
+           "ntf_sep_event_rt_chains"]
 
 
 def default_settings():
@@ -217,8 +218,8 @@ def _invalid(msg):
     return SnmfError(1, msg)  # SNMF_ERR_INVALID, raised before anything reaches the device
 
 
-def _per_stream(x, S, shape, name, order):
-    """One array for every stream, a list of S arrays or an array stacked along the last axis -> float32 [S, ...]."""
+def _per_stream(x, S, shape, name, order, dtype=np.float32):
+    """One array for every stream, a list of S arrays or an array stacked along the last axis -> dtype [S, ...]."""
     if isinstance(x, (list, tuple)):
         if len(x) != S:
             raise _invalid(f"{name}: {len(x)} entries for {S} streams")
@@ -235,7 +236,7 @@ def _per_stream(x, S, shape, name, order):
             a = a.reshape(-1)
         if a.shape != tuple(shape):
             raise _invalid(f"{name} of stream {k} is {a.shape}, expected {tuple(shape)}")
-        out.append(np.asarray(a, dtype=np.float32).ravel(order=order))
+        out.append(np.asarray(a, dtype=dtype).ravel(order=order))
     return np.ascontiguousarray(np.concatenate(out))
 
 
@@ -288,6 +289,7 @@ class OnlineBatchSeparator:
         self._lib = _lib.load()
         self.ctx = ctx or default_context()
         self.F, self.R_x, self.R_d, self.S = F, R_x, R_d, S
+        self.adapt, self.R_a, self.m_a = adapt, R_a, m_a
         ws = np.ascontiguousarray(p["win_STFT"], dtype=np.float32)
         wi = np.ascontiguousarray(p["win_ISTFT"], dtype=np.float32)
         q = _online_params(p, R_x, R_d, adapt, R_a, m_a, method, class_outputs)
@@ -334,11 +336,39 @@ class OnlineBatchSeparator:
             outs.append(o)
         return outs
 
+    def restart(self, streams, B_DFT_d=None, H0=None, Ad_blk0=None):
+        """Streams `streams` (an index or a list of distinct indices) start a new recording: src/NTF_sep_event_RT.m:27-38
+        + init_buff, every piece of their state as a new separator gives it, the other streams untouched.  Each of
+        `B_DFT_d` (F x R_d, fp64), `H0` and `Ad_blk0` is None, one array for all listed streams or one per stream.  None
+        keeps the stream's current, adapted B_DFT_d at full fp64 precision (load('B_D_u.mat')) and the H0 / Ad_blk0 it
+        last started with.  A stream that has consumed samples and was not flushed raises SnmfError(7)."""
+        ks = [int(streams)] if np.isscalar(streams) else [int(k) for k in streams]
+        n = len(ks)
+        bad = [k for k in ks if not 0 <= k < self.S]
+        if bad:
+            raise _invalid(f"stream {bad[0]} out of range [0, {self.S})")
+        if len(set(ks)) != n:
+            raise _invalid("a stream is listed twice")
+        Bd = None if B_DFT_d is None else _per_stream(B_DFT_d, n, (self.F, self.R_d), "B_DFT_d", "F", np.float64)
+        H = None if H0 is None else _per_stream(H0, n, (self.R_x + self.R_d,), "H0", "F")
+        Ad = None if (Ad_blk0 is None or not self.adapt) else _per_stream(Ad_blk0, n, (self.R_a, self.m_a), "Ad_blk0", "F")
+        if n == 0:
+            return
+        sl = np.array(ks, dtype=np.int32)
+        ptr = lambda a: a.ctypes.data if a is not None else None  # noqa: E731
+        _lib.check(self._lib.snmf_online_batch_restart(self._h, n, sl.ctypes.data, ptr(Bd), ptr(H), ptr(Ad)))
+
     def basis(self, k):
         """Current B_DFT_d of stream k."""
         B = np.zeros((self.F, self.R_d), dtype=np.float32, order="F")
         _lib.check(self._lib.snmf_online_batch_get_basis_f32(self._h, int(k), B.ctypes.data, self.F))
         return B.astype(np.float64)
+
+    def basis_f64(self, k):
+        """Stream k's fp64 master of B_DFT_d: what a carry (restart with B_DFT_d=None) keeps."""
+        B = np.zeros((self.F, self.R_d), dtype=np.float64, order="F")
+        _lib.check(self._lib.snmf_online_batch_get_basis_f64(self._h, int(k), B.ctypes.data, self.F))
+        return B
 
     def trace(self, k):
         """Per-frame diagnostics of stream k, as OnlineSeparator.trace."""
@@ -368,5 +398,131 @@ def ntf_sep_event_rt_batch(pcms, B_DFT_x, B_DFT_d, p, H0=None, Ad_blk0=None, ctx
     try:
         outs = sep.process(list(pcms), flush=True)
         return [(o["x_tilde"].copy(), o["x_tilde_f"].astype(np.float64), sep.basis(k)) for k, o in enumerate(outs)]
+    finally:
+        sep.close()
+
+
+_B_CHUNK_SLOTS = 16384  # (frame, stream) slots of one device chunk (kBChunkSlots, snmf_tu_online_batch.hip)
+
+
+def _per_chain(x, n, shape, name, dtype):
+    """One array for every chain or a list of n arrays -> a list of n fp64 arrays of `shape` holding `dtype` values (a
+    shared array is checked and converted once)."""
+    if isinstance(x, (list, tuple)):
+        if len(x) != n:
+            raise _invalid(f"{name}: {len(x)} entries for {n} chains")
+        arrs = list(x)
+    else:
+        arrs = [x] * n
+    done, out = {}, []
+    for c, a in enumerate(arrs):
+        if id(a) not in done:
+            b = np.asarray(a, dtype=dtype)
+            if len(shape) == 1 and b.size == shape[0]:
+                b = b.reshape(-1)
+            if b.shape != tuple(shape):
+                raise _invalid(f"{name} of chain {c} is {b.shape}, expected {tuple(shape)}")
+            done[id(a)] = np.asfortranarray(b, dtype=np.float64)
+        out.append(done[id(a)])
+    return out
+
+
+def ntf_sep_event_rt_chains(chains, B_DFT_x, B_DFT_d, p, n_streams=None, H0=None, Ad_blk0=None, ctx=None, chunk_hops=None):
+    """Do_MultiBatch_IS16_20160324.m:183-205 + run_ntf_sep_RT.m:10-41 on one batch: `chains` is a list of chains, each a
+    list of PCM arrays enhanced in turn by src/NTF_sep_event_RT.m.  Chain c starts from B_DFT_d (one array or one per
+    chain; the delete('B_D_u.mat') of :187), and every later file starts from the dictionary its predecessor adapted,
+    carried on the device in fp64 (:27-38, :137-140).  Returns, per chain, the list of its files' (int16, float, final
+    B_DFT_d) triples, as ntf_sep_event_rt_batch returns them.
+
+    `n_streams` slots (default min(len(chains), 256)) take chains from a queue; each call feeds every busy slot at most
+    `chunk_hops` hops (default one device chunk), and a slot whose file ended is restarted at the next call -- with the
+    carried dictionary or with its next chain's.  Chain c uses its own H0 / Ad_blk0 (one array or one per chain; by
+    default drawn from RandomState(random_seed + c), as OnlineBatchSeparator draws for stream k) for all its files, so
+    its bits depend neither on its slot, `n_streams` or `chunk_hops` nor on the other chains.  Start dictionaries enter
+    in fp32, as in ntf_sep_event_rt_batch."""
+    chains = [[np.asarray(x).reshape(-1) for x in c] for c in chains]
+    nc = len(chains)
+    if nc == 0:
+        return []
+    S = min(nc, 256) if n_streams is None else int(n_streams)
+    if S < 1:
+        raise _invalid("n_streams must be >= 1")
+    F = p["fftlength"] // 2 + 1
+    Bx = np.asarray(B_DFT_x)
+    if Bx.ndim != 2 or Bx.shape[0] != F:
+        raise _invalid(f"B_DFT_x must have fftlength/2+1 = {F} rows")
+    Bd_first = np.asarray(B_DFT_d[0] if isinstance(B_DFT_d, (list, tuple)) and len(B_DFT_d) else B_DFT_d)
+    if Bd_first.ndim != 2 or Bd_first.shape[0] != F:
+        raise _invalid(f"B_DFT_d must have fftlength/2+1 = {F} rows")
+    R_x, R_d = Bx.shape[1], Bd_first.shape[1]
+    r = R_x + R_d
+    adapt = int(bool(p.get("adapt_train_N", 0)))
+    R_a, m_a = int(p.get("R_a", 1)), int(p.get("m_a", 1))
+    Bds = _per_chain(B_DFT_d, nc, (F, R_d), "B_DFT_d", np.float32)  # (fp32 values, restarted with in fp64)
+    if H0 is not None:
+        H0 = _per_chain(H0, nc, (r,), "H0", np.float64)
+    if adapt and Ad_blk0 is not None:
+        Ad_blk0 = _per_chain(Ad_blk0, nc, (R_a, m_a), "Ad_blk0", np.float64)
+    seed = int(p.get("random_seed", 1))
+
+    def draws(c):  # OnlineBatchSeparator's stand-ins for stream c
+        rs = np.random.RandomState(seed + c)
+        h = rs.random_sample(r)
+        a = rs.random_sample((R_a, m_a)) if adapt else None
+        if H0 is not None:
+            h = H0[c]
+        if adapt and Ad_blk0 is not None:
+            a = Ad_blk0[c]
+        return h, a
+
+    results = [[] for _ in range(nc)]
+    queue = [c for c in range(nc) if chains[c]][::-1]  # popped from the end: chain order
+    if not queue:
+        return results
+    first = [queue.pop() for _ in range(min(S, len(queue)))]
+    init = [first[k] if k < len(first) else first[0] for k in range(S)]
+    dr = {c: draws(c) for c in set(init)}
+    sep = OnlineBatchSeparator(Bx, [Bds[c] for c in init], p, S, H0=[dr[c][0] for c in init],
+                               Ad_blk0=[dr[c][1] for c in init] if adapt else None, ctx=ctx)
+    hop = sep.hop
+    step = int(chunk_hops) if chunk_hops else max(1, min(4096, _B_CHUNK_SLOTS // S))
+    if step < 1:
+        raise _invalid("chunk_hops must be >= 1")
+    try:
+        # slot -> [chain, file, samples fed, int16 parts, float parts]
+        busy = {k: [c, 0, 0, [], []] for k, c in enumerate(first)}
+        carry, fresh = [], []
+        while busy:
+            if carry:
+                sep.restart(carry)  # same chain: the adapted fp64 dictionary, the chain's own H0 / Ad_blk0
+            if fresh:
+                cs = [busy[k][0] for k in fresh]
+                ds = [draws(c) for c in cs]
+                sep.restart(fresh, [Bds[c] for c in cs], [d[0] for d in ds], [d[1] for d in ds] if adapt else None)
+            carry, fresh = [], []
+            pcms, flush = [np.zeros(0, np.float32)] * S, [False] * S
+            for k, st in busy.items():
+                x = chains[st[0]][st[1]]
+                pcms[k] = x[st[2]:st[2] + step * hop]
+                st[2] += len(pcms[k])
+                flush[k] = st[2] >= len(x)
+            outs = sep.process(pcms, flush)
+            for k in list(busy):
+                st = busy[k]
+                st[3].append(outs[k]["x_tilde"])
+                st[4].append(outs[k]["x_tilde_f"])
+                if not flush[k]:
+                    continue
+                c, i = st[0], st[1]
+                results[c].append((np.concatenate(st[3]).astype(np.int16), np.concatenate(st[4]).astype(np.float64), sep.basis(k)))
+                if i + 1 < len(chains[c]):
+                    busy[k] = [c, i + 1, 0, [], []]
+                    carry.append(k)
+                elif queue:
+                    busy[k] = [queue.pop(), 0, 0, [], []]
+                    fresh.append(k)
+                else:
+                    del busy[k]
+        return results
     finally:
         sep.close()
