@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SNMF_ABI_VERSION 5  /* 5: snmf_online_batch_* incl. _restart / _get_basis_f64 (added within 5: new entries only), snmf_multi_release_cache, snmf_multi_cached_teams, snmf_rccl_*, snmf_plan_run_sharded_rccl (the device RNG of snmf_plan_set_h_random changed with 4: draws seeded under ABI 3 are not reproducible); 4: snmf_run_basis_dnmf_multi_*; 3: snmf_run_basis_dnmf_*, snmf_run_basis_train_audio_f64, snmf_sparse_nmf_oop_*, snmf_plan_set_h_random, snmf_ctx_xfer_stats; 2: snmf_multi_* */
+#define SNMF_ABI_VERSION 5  /* 5: snmf_online_batch_* incl. _restart / _get_basis_f64 / _set_mel / _restart_mel / _get_mel_basis_f32 / _f64 (added within 5: new entries only), snmf_multi_release_cache, snmf_multi_cached_teams, snmf_rccl_*, snmf_plan_run_sharded_rccl (the device RNG of snmf_plan_set_h_random changed with 4: draws seeded under ABI 3 are not reproducible); 4: snmf_run_basis_dnmf_multi_*; 3: snmf_run_basis_dnmf_*, snmf_run_basis_train_audio_f64, snmf_sparse_nmf_oop_*, snmf_plan_set_h_random, snmf_ctx_xfer_stats; 2: snmf_multi_* */
 
 typedef enum snmf_status {
     SNMF_OK = 0,
@@ -405,8 +405,8 @@ void snmf_online_destroy(snmf_online* o);
  * B_D_u.mat deleted between the chains at :187).  Here S such chains share one snmf_online_params and advance frame by
  * frame in shared launches, with no host round trip per frame: stream k has its own PCM, its own noise dictionary and
  * its own state g (src/init_buff.m:17-42), and its output equals what snmf_online_* produces for it alone.
- * Scope: DFT mode (no Mel entry), the supervised frame solve of the register-resident frame kernel (F <= 513,
- * R_x + R_d <= 200), R_a and m_a <= 128; anything else returns SNMF_ERR_UNSUPPORTED. */
+ * Scope: B_sep_mode 'DFT', or 'Mel' through snmf_online_batch_set_mel; the supervised frame solve of the register-resident
+ * frame kernel (F <= 513, R_x + R_d <= 200), R_a and m_a <= 128; anything else returns SNMF_ERR_UNSUPPORTED. */
 typedef struct snmf_online_batch snmf_online_batch;
 /* src/init_buff.m for S streams.  B_DFT_x: F x R_x, shared; B_DFT_d0: F x R_d x S, the initial noise dictionary of
  * every stream (e.g. each stream's B_D_u.mat, src/NTF_sep_event_RT.m:27-31); H0: r x S (rand(r,1) of
@@ -433,11 +433,30 @@ int snmf_online_batch_get_basis_f32(snmf_online_batch* b, int32_t k, float* B_DF
  * H0: r x n, Ad_blk0: R_a x m_a x n, or NULL = the values the stream last started with.
  * A stream that has consumed samples and has not been flushed returns SNMF_ERR_STATE, and so does a failed batch; a
  * stream that has never been fed may be restarted.  The other streams do not change.  Ordered on the context's stream
- * before the next process call; no synchronise beyond the uploads. */
+ * before the next process call; no synchronise beyond the uploads.
+ * On a Mel-mode batch this is exactly snmf_online_batch_restart_mel with B_Mel_d = NULL (each stream keeps its B_Mel_d). */
 int snmf_online_batch_restart(snmf_online_batch* b, int32_t n, const int32_t* slots, const double* B_DFT_d,
                               const float* H0, const float* Ad_blk0);
 /* Added within 5.  Stream k's fp64 master of B_DFT_d (what a carry by snmf_online_batch_restart keeps). */
 int snmf_online_batch_get_basis_f64(snmf_online_batch* b, int32_t k, double* B_DFT_d, int64_t ld);
+/* Added within 5.  B_sep_mode = 'Mel' for every stream (src/bnmf_sep_event_RT_IS16.m:106-120, :165-171, :205-211, :298-318),
+ * as snmf_online_set_mel: call after create and before the first process call (after it: SNMF_ERR_STATE).
+ * melmat: F_order x F ROW-major, shared; B_Mel_x: F_order x R_x, shared; B_Mel_d: F_order x R_d x S, every stream's start
+ * (column-major per stream, streams consecutive, fp32).  F_order outside [2, F] or a NULL argument: SNMF_ERR_INVALID.
+ * The frame solve runs at F_order rows on [B_Mel_x | B_Mel_d] and the adaptation updates B_Mel_d (its fp64 master);
+ * B_DFT_d is never adapted.  mel_conv = p.MelConv (0: the Mel activations drive the stream's B_DFT bases).  Every stream
+ * restarts with its B_Mel_d and keeps its B_DFT_d, H0 and Ad_blk0. */
+int snmf_online_batch_set_mel(snmf_online_batch* b, int32_t F_order, int32_t mel_conv, const float* melmat, const float* B_Mel_x,
+                              const float* B_Mel_d);
+/* Added within 5.  snmf_online_batch_restart with the Mel dictionary too (src/NTF_sep_event_RT.m:27-38, :137-139 save and
+ * load both): B_Mel_d F_order x R_d x n column-major fp64, or NULL = keep each stream's current fp64 master (no fp32 round
+ * trip).  A non-NULL B_Mel_d on a batch that is not in Mel mode returns SNMF_ERR_STATE. */
+int snmf_online_batch_restart_mel(snmf_online_batch* b, int32_t n, const int32_t* slots, const double* B_DFT_d,
+                                  const double* B_Mel_d, const float* H0, const float* Ad_blk0);
+/* Added within 5.  Stream k's current B_Mel_d (F_order x R_d; f64: the master a carry keeps).  SNMF_ERR_STATE when the
+ * batch is not in Mel mode. */
+int snmf_online_batch_get_mel_basis_f32(snmf_online_batch* b, int32_t k, float* B_Mel_d, int64_t ld);
+int snmf_online_batch_get_mel_basis_f64(snmf_online_batch* b, int32_t k, double* B_Mel_d, int64_t ld);
 /* Diagnostics of stream k's most recent frames (the newest 65536 per stream), as snmf_online_trace. */
 int snmf_online_batch_trace(snmf_online_batch* b, int32_t k, snmf_online_frame* out, int64_t cap, int64_t* n);
 void snmf_online_batch_destroy(snmf_online_batch* b);

@@ -61,7 +61,8 @@ SYMBOLS = [
     "snmf_online_create", "snmf_online_set_mel", "snmf_online_get_mel_basis_f32", "snmf_online_process_f32", "snmf_online_get_basis_f32", "snmf_online_trace",
     "snmf_online_destroy",
     "snmf_online_batch_create", "snmf_online_batch_process_f32", "snmf_online_batch_get_basis_f32", "snmf_online_batch_trace",
-    "snmf_online_batch_destroy", "snmf_online_batch_restart", "snmf_online_batch_get_basis_f64",
+    "snmf_online_batch_destroy", "snmf_online_batch_restart", "snmf_online_batch_get_basis_f64", "snmf_online_batch_set_mel",
+    "snmf_online_batch_restart_mel", "snmf_online_batch_get_mel_basis_f32", "snmf_online_batch_get_mel_basis_f64",
     "snmf_multi_create", "snmf_multi_destroy", "snmf_multi_set_v_f64", "snmf_multi_set_v_f32", "snmf_multi_set_w_f64",
     "snmf_multi_set_w_f32", "snmf_multi_set_h_f64", "snmf_multi_set_h_f32", "snmf_multi_set_sparsity_f64",
     "snmf_multi_set_sparsity_f32", "snmf_multi_init", "snmf_multi_run", "snmf_multi_get_w_f64", "snmf_multi_get_w_f32",
@@ -265,6 +266,10 @@ def load():
     sig["snmf_online_batch_destroy"] = (None, [vp])
     sig["snmf_online_batch_restart"] = (C.c_int, [vp, i32, vp, vp, vp, vp])
     sig["snmf_online_batch_get_basis_f64"] = (C.c_int, [vp, i32, vp, i64])
+    sig["snmf_online_batch_set_mel"] = (C.c_int, [vp, i32, i32, vp, vp, vp])
+    sig["snmf_online_batch_restart_mel"] = (C.c_int, [vp, i32, vp, vp, vp, vp, vp])
+    sig["snmf_online_batch_get_mel_basis_f32"] = (C.c_int, [vp, i32, vp, i64])
+    sig["snmf_online_batch_get_mel_basis_f64"] = (C.c_int, [vp, i32, vp, i64])
     for ty in ("f64", "f32"):
         sig[f"snmf_plan_solve_frames_{ty}"] = (C.c_int, [vp, i32, vp, i64, i32, vp, vp, vp, vp])
     for nm in ("v", "w", "h", "mask"):

@@ -2,8 +2,10 @@
 // streams of src/bnmf_sep_event_RT_IS16.m, one set of settings, each stream with its own PCM, noise dictionary and
 // state g (src/init_buff.m:17-42).  The per-frame work is that of snmf_online.h; here every launch covers all streams:
 //   k_obstft      framing + STFT of the S x n frames of a chunk (one workgroup per (frame, stream))
+//   k_obmel       B_sep_mode = 'Mel': the normalised Mel features of every (frame, stream), the solve's input
 //   k_hsolve_frame<..., BATCH = true> (snmf_kernels.h) the frame solves, one workgroup per (frame, stream)
 //   k_obpost      the post-filter, one workgroup per stream walking its frames in order
+//   k_obprep_mel  Mel mode: melmat * lambda_d_blk of every stream whose adaptation is due (k_wadapt_batch's V)
 //   k_wadapt_batch the W-only adaptation solve of :296-336, one workgroup per stream, gated on the device
 //   k_obassemble / k_obrefresh  the re-assembly of :336 and the next frame solve's dictionary images, gated
 //   k_obistft / k_obtail / k_obola  inverse STFT and overlap-add of src/NTF_sep_event_RT.m:104-124
@@ -11,6 +13,8 @@
 // Frame-indexed buffers are frame-major: the slot of frame i of stream s is i * S + s.  A stream's own state sits at a
 // fixed stride per stream.  Nothing is shared between the streams' workgroups, so a stream's bits do not depend on
 // the other streams of its batch.
+// In Mel mode (snmf_online_batch_set_mel) the frame solve, the adaptation and the re-assembly run at F_order rows on the
+// per-stream fp64 Mel master [B_Mel_x | B_Mel_d]; B_DFT_d is set on restart and never adapted (src/bnmf_sep_event_RT_IS16.m).
 #pragma once
 #define SNMF_ONLINE_NO_KERNELS 1  // the device functions of snmf_online.h only (its kernels live in snmf_tu_online.hip)
 #include "snmf_online.h"
@@ -27,8 +31,9 @@ struct OBatchFrames {
     int S;
 };
 
-// src/bnmf_sep_event_RT_IS16.m:65-81 for every (frame, stream); also writes the floored solve input (k_pack's floor)
-template <int LOGN>
+// src/bnmf_sep_event_RT_IS16.m:65-81 for every (frame, stream); PACK (DFT mode) also writes the floored solve input (k_pack's
+// floor) -- in Mel mode k_obmel writes it, at F_order rows
+template <int LOGN, bool PACK = true>
 __global__ __launch_bounds__(256) void k_obstft(OStftArgs a, OBatchFrames b, float* __restrict__ Vp, int Fp) {
     constexpr int N = 1 << LOGN;
     __shared__ float2 bufA[N];
@@ -39,6 +44,7 @@ __global__ __launch_bounds__(256) void k_obstft(OStftArgs a, OBatchFrames b, flo
     const size_t slot = (size_t)i * b.S + s;
     float* om = a.Ym + slot * a.ld;
     ostft_frame<LOGN>(a, src, om, a.Yph + slot * a.ld, bufA, bufB);
+    if (!PACK) return;
     __syncthreads();
     float* vp = Vp + slot * Fp;
     for (int f = threadIdx.x; f < (int)a.ld; f += 256) {
@@ -47,12 +53,50 @@ __global__ __launch_bounds__(256) void k_obstft(OStftArgs a, OBatchFrames b, flo
     }
 }
 
+// :106-120 for every (frame, stream): Ym_Mel = melmat * Ym, normalised to unit norm (+1e-9) and scaled to ||Ym|| -- the
+// arithmetic of k_omel_frame (snmf_online.h), so a stream's features are the single-stream separator's bits -- into Ymel
+// (the post-filter's, MelConv = 1) and, floored, into the solve input Vp at the plan's Fp stride.  Grid (C, S), 256 threads.
+__global__ __launch_bounds__(256) void k_obmel(const float* __restrict__ Ym, const float* __restrict__ melmat, const int* nfr, int S,
+                                               int F, int n1, float* __restrict__ Ymel, float* __restrict__ Vp, int Fp) {
+    extern __shared__ float sm[];  // [n1]
+    __shared__ float part[4];
+    const int i = blockIdx.x, s = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    if (i >= nfr[s]) return;
+    const size_t slot = (size_t)i * S + s;
+    const float* y = Ym + slot * F;
+    float tn2 = 0.f;
+    for (int f = tid; f < F; f += 256) tn2 = fmaf(y[f], y[f], tn2);
+    tn2 = wave_sum_f(tn2);
+    if (lane == 0) part[w] = tn2;
+    for (int m = w; m < n1; m += 4) {
+        float v = 0.f;
+        for (int f = lane; f < F; f += 64) v = fmaf(melmat[(size_t)m * F + f], y[f], v);
+        v = wave_sum_f(v);
+        if (lane == 0) sm[m] = v;
+    }
+    __syncthreads();
+    const float tn = sqrtf(part[0] + part[1] + part[2] + part[3]);
+    float vn2 = 0.f;
+    for (int m = tid; m < n1; m += 256) vn2 = fmaf(sm[m], sm[m], vn2);
+    vn2 = wave_sum_f(vn2);
+    __syncthreads();
+    if (lane == 0) part[w] = vn2;
+    __syncthreads();
+    const float vn = sqrtf(part[0] + part[1] + part[2] + part[3]);
+    for (int m = tid; m < n1; m += 256) {
+        const float v = (sm[m] / vn + 1e-9f) * tn;
+        Ymel[slot * n1 + m] = v;
+        Vp[slot * Fp + m] = v > kFlr ? v : kFlr;
+    }
+}
+
 // per-stream strides of the post-filter state (OPostArgs holds stream 0's pointers)
 struct OBatchPost {
     OBatchFrames fr;
     int step;           // >= 0: frame `step` of every stream that has it; < 0: all frames of the chunk in order
     int rp;             // stride of the activation vectors
-    int64_t sB;         // Bf stride (unused when the reconstructions come from the frame solve)
+    int64_t sB;         // B stride: the fp32 [B_DFT_x | B_DFT_d] of Mel mode without MelConv (unused when the reconstructions
+                        // come from the frame solve)
 };
 
 // One workgroup per stream: opost_frame (snmf_online.h) on that stream's state, its frames one after the other.
@@ -77,6 +121,7 @@ __global__ __launch_bounds__(1024) void k_obpost(OPostArgs a0, OBatchPost b) {
         a.A = a0.A + slot * b.rp;
         a.hst = a0.hst + slot;
         if (a.recon) a.recon = a0.recon + slot * 2 * a0.recon_len;
+        if (a.Ymel) a.Ymel = a0.Ymel + slot * a0.n1;
         a.Ym = a0.Ym + slot * F;
         a.Xt_out = a0.Xt_out + slot * F;
         if (a.Xh_out) a.Xh_out = a0.Xh_out + slot * F;
@@ -93,6 +138,23 @@ __device__ __forceinline__ bool ob_due(const OnlineStatus* status, const int* nf
     if (step >= nfr[s]) return false;
     const OnlineStatus& st = status[(size_t)step * S + s];
     return st.do_solve && st.n_up > 0;
+}
+
+// Mel mode's V of the adaptation solve (:298-303): melmat * lambda_d_blk, column c of stream s's ring into column c of Vm
+// (ring order: k_wadapt_batch reads it as it reads the ring, at F_order rows) for every stream whose adaptation is due.
+// k_oprep_mel's arithmetic.  Grid (m_a, S), 256 threads.
+__global__ __launch_bounds__(256) void k_obprep_mel(const OnlineStatus* status, const int* nfr, int step, int S, const float* __restrict__ ldblk,
+                                                    const float* __restrict__ melmat, int F, int n1, int ma, float* __restrict__ Vm) {
+    const int c = blockIdx.x, s = blockIdx.y, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (!ob_due(status, nfr, step, S, s)) return;
+    const float* col = ldblk + ((size_t)s * ma + c) * F;
+    float* out = Vm + ((size_t)s * ma + c) * n1;
+    for (int m = w; m < n1; m += 4) {
+        float v = 0.f;
+        for (int f = lane; f < F; f += 64) v = fmaf(melmat[(size_t)m * F + f], col[f], v);
+        v = wave_sum_f(v);
+        if (lane == 0) out[m] = v;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -425,18 +487,19 @@ __global__ __launch_bounds__(kWbNT) void k_wadapt_batch(WBatchArgs a) {
     if (tid == 0) a.iters[(size_t)a.step * a.S + s] = stopped ? n_rec : a.max_iter;
 }
 
-// B_DFT_d = [B_d_rem, B_d_tmp, B_d_fix] (:336) of every stream whose adaptation ran: one workgroup per (column, stream),
-// into Btmp (the kept columns are read from the dictionary the next launch overwrites).
+// B_DFT_d = [B_d_rem, B_d_tmp, B_d_fix] (:336), resp. B_Mel_d (:318), of every stream whose adaptation ran: one workgroup per
+// (column, stream), into Btmp (the kept columns are read from the dictionary the next launch overwrites).  Stream s's fixed
+// columns are at Bfix + s * sfix (DFT: the dictionary it started with, :328; Mel: its own B_Mel_d, :309).
 __global__ __launch_bounds__(256) void k_obassemble(const OnlineStatus* status, const int* nfr, int step, int S, const double* B,
-                                                    const double* Wu, const double* Bfix, const uint8_t* rupa, int F, int r,
-                                                    int Rx, int Ra, int Rd, double* Btmp) {
+                                                    const double* Wu, const double* Bfix, int64_t sfix, const uint8_t* rupa, int F,
+                                                    int r, int Rx, int Ra, int Rd, double* Btmp) {
     const int j = blockIdx.x, s = blockIdx.y;
     if (j >= Rd || !ob_due(status, nfr, step, S, s)) return;
     const double* Bd_old = B + (size_t)s * r * F + (size_t)Rx * F;
     const uint8_t* rup = rupa + (size_t)s * Ra;
     const double* src;
     if (j >= Ra) {
-        src = Bfix + (size_t)s * Rd * F + (size_t)j * F;
+        src = Bfix + (size_t)s * sfix + (size_t)j * F;
     } else {
         int n_rem = 0;
         for (int k = 0; k < Ra; ++k) n_rem += rup[k] ? 0 : 1;
@@ -462,7 +525,7 @@ __global__ __launch_bounds__(256) void k_obassemble(const OnlineStatus* status, 
 // ---------------------------------------------------------------------------------------------
 enum : int {
     kRsBx, kRsBd, kRsBfix, kRsH0, kRsAd0, kRsAdblk, kRsLdblk, kRsRup, kRsLam, kRsXm, kRsRblk, kRsTail, kRsTailX, kRsTailD,
-    kRsDev, kRsWcf, kRsImg, kRsN
+    kRsDev, kRsWcf, kRsBmx, kRsBmd, kRsBdf, kRsImg, kRsN
 };
 constexpr int kRsParts = 8;  // workgroups per (stream, array)
 
@@ -478,7 +541,12 @@ struct ORestartArgs {
     OnlineDev* dev;
     float *Wcf, *wx, *dphv, *Hin;
     double* wn;
-    int F, r, Rx, Rd, Ra, ma, Pl, rp, Fp, adapt;
+    // Mel mode (NULL otherwise)
+    const double* Bmx;      // [Rx][n1] the shared B_Mel_x
+    const double* Bmd;      // [n][Rd][n1] new B_Mel_d, or NULL = keep each stream's (carry)
+    double* Bm;             // [S][r][n1] the fp64 Mel masters [B_Mel_x | B_Mel_d]: the solve's dictionary
+    float* Bdf;             // [S][r][F] fp32 [B_DFT_x | B_DFT_d] (MelConv = 0: the post-filter's DFT bases)
+    int F, r, Rx, Rd, Ra, ma, Pl, rp, Fp, adapt, n1;
     int64_t ntail;
 };
 
@@ -526,6 +594,20 @@ __global__ __launch_bounds__(256) void k_obrestart(ORestartArgs a) {
             if (q0 == 0) a.dev[s] = OnlineDev{0, 1, 0, 0};  // update_switch = 1 (src/init_buff.m:42)
             break;
         case kRsWcf: fill(a.Wcf + (size_t)s * a.rp * a.Fp, 0.f, (size_t)a.rp * a.Fp); break;  // rows >= F stay zero
+        case kRsBmx:
+            if (a.Bm) copy(a.Bm + (size_t)s * a.r * a.n1, a.Bmx, (size_t)a.Rx * a.n1);
+            break;
+        case kRsBmd:
+            if (a.Bm && a.Bmd) copy(a.Bm + (size_t)s * a.r * a.n1 + (size_t)a.Rx * a.n1, a.Bmd + (size_t)i * a.Rd * a.n1, (size_t)a.Rd * a.n1);
+            break;
+        case kRsBdf:  // the fp32 image of the DFT dictionary this restart leaves (kRsBd writes B only when a.Bd is given)
+            if (a.Bdf) {
+                float* d = a.Bdf + (size_t)s * a.r * F;
+                const double* src = a.Bd ? a.Bd + (size_t)i * a.Rd * F : a.B + (size_t)s * a.r * F + (size_t)a.Rx * F;
+                for (size_t e = q0; e < (size_t)a.Rx * F; e += qs) d[e] = (float)a.Bx[e];
+                for (size_t e = q0; e < (size_t)a.Rd * F; e += qs) d[(size_t)a.Rx * F + e] = (float)src[e];
+            }
+            break;
         default: {  // kRsImg: k_obrefresh writes the r real columns of these; pads: dphv 1.0f (r < 8 * KB must divide by
                     // something finite: 0 * 0 / 0 was NaN in every pad activation and cost), the rest 0
             const size_t o = (size_t)s * a.rp;

@@ -16,6 +16,9 @@ struct snmf_online_batch {
     snmf_ctx* ctx = nullptr;
     snmf_online_params p{};
     int S = 0, F = 0, r = 0, N = 0, nov = 0, Ra = 1, ma = 1, Pl = 1, RA2 = 64;
+    int Fs = 0;                                // rows of the solves: F, or F_order in Mel mode
+    int mel = 0, mel_conv = 0, n1 = 0;         // B_sep_mode = 'Mel' (snmf_online_batch_set_mel)
+    bool started = false;                      // a process call was made (set_mel must come first)
     snmf_plan* hp = nullptr;  // the frame solve's geometry, sparsity and beta (one plan serves every stream)
     // per stream, device
     double *B = nullptr, *Bfix = nullptr, *Btmp = nullptr, *wn = nullptr, *Wu = nullptr;
@@ -28,6 +31,10 @@ struct snmf_online_batch {
     float *win_s = nullptr, *win_i = nullptr;
     float2* tw = nullptr;
     double* Bxd = nullptr;  // B_DFT_x in fp64, shared
+    // Mel mode: melmat [n1][F] and B_Mel_x [Rx][n1] (fp64) shared; per stream the fp64 Mel master [r][n1], the adaptation's
+    // melmat * lambda_d_blk [ma][n1] and, with MelConv = 0, the fp32 [B_DFT_x | B_DFT_d] [r][F]
+    float *melmat = nullptr, *Vm = nullptr, *Bdf = nullptr;
+    double *Bmx = nullptr, *Bm = nullptr, *rs_Bm = nullptr;
     // restart uploads (sized for all S streams)
     int* rs_slots = nullptr;
     double* rs_B = nullptr;
@@ -37,7 +44,7 @@ struct snmf_online_batch {
     int C = 0;  // frames per stream per chunk
     size_t cap_sig = 0, cap_out = 0;
     float *sig = nullptr, *Ym = nullptr, *Vp = nullptr, *Hout = nullptr, *reco = nullptr, *Xt = nullptr, *Xh = nullptr, *Dh = nullptr;
-    float *syn = nullptr, *outf = nullptr;
+    float *syn = nullptr, *outf = nullptr, *Ymel = nullptr;
     float2* Yph = nullptr;
     int16_t* out16 = nullptr;
     DevState* st = nullptr;
@@ -56,10 +63,10 @@ struct snmf_online_batch {
 
 static void ob_free_chunk(snmf_online_batch* o) {
     void* ptrs[] = {o->sig, o->Ym, o->Vp, o->Hout, o->reco, o->Xt, o->Xh, o->Dh, o->syn, o->outf, o->Yph, o->out16,
-                    o->st, o->divh, o->costh, o->status, o->iters};
+                    o->st, o->divh, o->costh, o->status, o->iters, o->Ymel};
     for (void* q : ptrs)
         if (q) hipFree(q);
-    o->sig = o->Ym = o->Vp = o->Hout = o->reco = o->Xt = o->Xh = o->Dh = o->syn = o->outf = nullptr;
+    o->sig = o->Ym = o->Vp = o->Hout = o->reco = o->Xt = o->Xh = o->Dh = o->syn = o->outf = o->Ymel = nullptr;
     o->Yph = nullptr;
     o->out16 = nullptr;
     o->st = nullptr;
@@ -78,7 +85,8 @@ extern "C" void snmf_online_batch_destroy(snmf_online_batch* o) {
     ob_free_chunk(o);
     void* ptrs[] = {o->B, o->Bfix, o->Btmp, o->wn, o->Wu, o->Wcf, o->wx, o->dphv, o->Hin, o->H0, o->Ad0, o->lambda_dav, o->Xm_tilde,
                     o->r_blk, o->ldblk, o->adblk, o->G, o->P, o->Vt, o->tail, o->tail_x, o->tail_d, o->rup, o->dev, o->win_s,
-                    o->win_i, o->tw, o->Bxd, o->rs_slots, o->rs_B, o->rs_H, o->rs_A, o->meta_i, o->meta_l};
+                    o->win_i, o->tw, o->Bxd, o->rs_slots, o->rs_B, o->rs_H, o->rs_A, o->meta_i, o->meta_l, o->melmat, o->Vm, o->Bdf,
+                    o->Bmx, o->Bm, o->rs_Bm};
     for (void* q : ptrs)
         if (q) hipFree(q);
     delete o;
@@ -115,14 +123,17 @@ static int ob_validate(const snmf_online_params* p, int32_t S) {
 
 // The streams slots[0..n) start a new recording (src/NTF_sep_event_RT.m:27-38 + src/init_buff.m): the uploads, one
 // k_obrestart, one k_obrefresh over their columns, and their host state.  Arguments are checked by the caller; Bd is
-// n x Rd x F fp64 or NULL (carry), H0 n x r or NULL, Ad n x Ra x ma or NULL.  Ordered on ctx->stream, no synchronise
-// (the uploads come from pageable host memory, which the runtime copies before it returns).
-static int ob_restart(snmf_online_batch* o, int n, const int32_t* slots, const double* Bd, const float* H0, const float* Ad) {
+// n x Rd x F fp64 or NULL (carry), Bmd (Mel mode) n x Rd x n1 fp64 or NULL (carry), H0 n x r or NULL, Ad n x Ra x ma or
+// NULL.  Ordered on ctx->stream, no synchronise (the uploads come from pageable host memory, which the runtime copies
+// before it returns).
+static int ob_restart(snmf_online_batch* o, int n, const int32_t* slots, const double* Bd, const double* Bmd, const float* H0,
+                      const float* Ad) {
     const snmf_online_params& p = o->p;
     hipStream_t st = o->ctx->stream;
     const size_t F = o->F, nA = (size_t)o->Ra * o->ma;
     HIP_TRY(hipMemcpyAsync(o->rs_slots, slots, (size_t)n * 4, hipMemcpyHostToDevice, st));
     if (Bd) HIP_TRY(hipMemcpyAsync(o->rs_B, Bd, (size_t)n * p.R_d * F * 8, hipMemcpyHostToDevice, st));
+    if (Bmd) HIP_TRY(hipMemcpyAsync(o->rs_Bm, Bmd, (size_t)n * p.R_d * o->n1 * 8, hipMemcpyHostToDevice, st));
     if (H0) HIP_TRY(hipMemcpyAsync(o->rs_H, H0, (size_t)n * o->r * 4, hipMemcpyHostToDevice, st));
     if (Ad) HIP_TRY(hipMemcpyAsync(o->rs_A, Ad, (size_t)n * nA * 4, hipMemcpyHostToDevice, st));
     ORestartArgs a{};
@@ -132,13 +143,14 @@ static int ob_restart(snmf_online_batch* o, int n, const int32_t* slots, const d
     a.dev = o->dev; a.Wcf = o->Wcf; a.wx = o->wx; a.dphv = o->dphv; a.Hin = o->Hin; a.wn = o->wn;
     a.F = o->F; a.r = o->r; a.Rx = p.R_x; a.Rd = p.R_d; a.Ra = o->Ra; a.ma = o->ma; a.Pl = o->Pl; a.rp = o->hp->rp; a.Fp = o->hp->Fp;
     a.adapt = p.adapt_train_N; a.ntail = (int64_t)o->ntail;
+    a.Bmx = o->Bmx; a.Bmd = Bmd ? o->rs_Bm : nullptr; a.Bm = o->Bm; a.Bdf = o->Bdf; a.n1 = o->n1;
     hipLaunchKernelGGL(k_obrestart, dim3(n, kRsN, kRsParts), dim3(256), 0, st, a);
     HIP_TRY(hipGetLastError());
-    // every column's dictionary images (set_w + the init mode of k_wapply)
+    // every column's dictionary images (set_w + the init mode of k_wapply) from the solve's dictionary (Mel: the Mel master)
     ORefreshArgs ra{};
-    ra.slots = o->rs_slots; ra.S = o->S; ra.B = o->B; ra.Wcf = o->Wcf; ra.wx = o->wx; ra.dphv = o->dphv; ra.wn = o->wn; ra.Hin = o->Hin;
-    ra.H0 = o->H0; ra.lamk = o->hp->lamk; ra.F = o->F; ra.r = o->r; ra.Rx = p.R_x; ra.rp = o->hp->rp; ra.Fp = o->hp->Fp;
-    ra.xr = o->F > 64 * o->hp->frame_fb; ra.k0 = 0;
+    ra.slots = o->rs_slots; ra.S = o->S; ra.B = o->mel ? o->Bm : o->B; ra.Wcf = o->Wcf; ra.wx = o->wx; ra.dphv = o->dphv; ra.wn = o->wn;
+    ra.Hin = o->Hin; ra.H0 = o->H0; ra.lamk = o->hp->lamk; ra.F = o->Fs; ra.r = o->r; ra.Rx = p.R_x; ra.rp = o->hp->rp; ra.Fp = o->hp->Fp;
+    ra.xr = o->Fs > 64 * o->hp->frame_fb; ra.k0 = 0;
     hipLaunchKernelGGL(k_obrefresh, dim3(o->r, n), dim3(256), 0, st, ra);
     HIP_TRY(hipGetLastError());
     const int sz = p.framelength, hop = p.frameshift;
@@ -150,6 +162,21 @@ static int ob_restart(snmf_online_batch* o, int n, const int32_t* slots, const d
         o->finished[s] = 0;
         o->trace[s].clear();
     }
+    return SNMF_OK;
+}
+
+// the frame solve's plan: rows x 1, rank r, H-only (its register-resident kernel must admit the shape)
+static int ob_make_plan(snmf_ctx* ctx, const snmf_online_params* p, int rows, snmf_plan** out) {
+    const int r = p->R_x + p->R_d;
+    snmf_params hp{};
+    hp.F = rows; hp.T = 1; hp.r = r; hp.beta = p->beta_div; hp.max_iter = p->max_iter; hp.conv_eps = p->conv_eps;
+    hp.cost_check = p->cost_check; hp.floor_v = 1; hp.sparsity_kind = SNMF_SPARSITY_SCALAR; hp.sparsity_scalar = p->sparsity;
+    std::vector<uint8_t> zeros(r, 0), ones(r, 1);
+    hp.w_update_ind = zeros.data();
+    hp.h_update_ind = ones.data();
+    SN_TRY(snmf_plan_create(ctx, &hp, out));
+    if (!(*out)->frame_fb)
+        return fail(SNMF_ERR_UNSUPPORTED, "batched separator: F = %d, r = %d is outside the frame kernel's envelope (F <= 513, r <= 200)", rows, r);
     return SNMF_OK;
 }
 
@@ -175,19 +202,10 @@ extern "C" int snmf_online_batch_create(snmf_ctx* ctx, const snmf_online_params*
     o->ma = p->adapt_train_N ? p->m_a : 1;
     o->Pl = p->blk_sparse ? p->P_len_l : 1;
     o->RA2 = (o->Ra + 63) / 64 * 64;
+    o->Fs = F;
     int s = SNMF_OK;
     auto A = [&](int v) { if (s == SNMF_OK) s = v; };
-    {   // the frame solve's plan: F x 1, rank r, H-only (its register-resident kernel must admit the shape)
-        snmf_params hp{};
-        hp.F = F; hp.T = 1; hp.r = r; hp.beta = p->beta_div; hp.max_iter = p->max_iter; hp.conv_eps = p->conv_eps;
-        hp.cost_check = p->cost_check; hp.floor_v = 1; hp.sparsity_kind = SNMF_SPARSITY_SCALAR; hp.sparsity_scalar = p->sparsity;
-        std::vector<uint8_t> zeros(r, 0), ones(r, 1);
-        hp.w_update_ind = zeros.data();
-        hp.h_update_ind = ones.data();
-        A(snmf_plan_create(ctx, &hp, &o->hp));
-        if (s == SNMF_OK && !o->hp->frame_fb)
-            A(fail(SNMF_ERR_UNSUPPORTED, "batched separator: F = %d, r = %d is outside the frame kernel's envelope (F <= 513, r <= 200)", F, r));
-    }
+    A(ob_make_plan(ctx, p, F, &o->hp));
     if (s == SNMF_OK && p->adapt_train_N && wbatch_lds(o->Ra, o->ma, o->RA2, p->beta_div == 1.0) > ctx->lds_max)
         A(fail(SNMF_ERR_UNSUPPORTED, "batched adaptation: R_a x m_a too large for one workgroup's LDS"));
     if (s != SNMF_OK) {
@@ -239,7 +257,7 @@ extern "C" int snmf_online_batch_create(snmf_ctx* ctx, const snmf_online_params*
     // every stream's state g: a restart of all S streams (the one initialisation path)
     std::vector<int32_t> all(SS);
     for (int k = 0; k < S; ++k) all[k] = k;
-    const int rc = e ? SNMF_OK : ob_restart(o, S, all.data(), hd.data(), H0, p->adapt_train_N ? Ad0 : nullptr);
+    const int rc = e ? SNMF_OK : ob_restart(o, S, all.data(), hd.data(), nullptr, H0, p->adapt_train_N ? Ad0 : nullptr);
     H(hipStreamSynchronize(st));
     if (e || rc) {
         snmf_online_batch_destroy(o);
@@ -248,6 +266,60 @@ extern "C" int snmf_online_batch_create(snmf_ctx* ctx, const snmf_online_params*
                     hipGetErrorString((hipError_t)e));
     }
     *out = o;
+    return SNMF_OK;
+}
+
+// B_sep_mode = 'Mel' (src/bnmf_sep_event_RT_IS16.m:106-120, src/init_buff.m:45-47), as snmf_online_set_mel: the frame solve
+// is rebuilt at F_order rows and every stream restarts through ob_restart with the given B_Mel_d (its B_DFT_d, H0 and
+// Ad_blk0 are kept).
+extern "C" int snmf_online_batch_set_mel(snmf_online_batch* o, int32_t F_order, int32_t mel_conv, const float* melmat, const float* BMx,
+                                         const float* BMd) {
+    if (!o || !melmat || !BMx || !BMd) return fail(SNMF_ERR_INVALID, "NULL argument");
+    if (o->failed) return fail(SNMF_ERR_STATE, "an earlier call failed midway through a chunk; the batch state is not reusable, create a new one");
+    if (o->started) return fail(SNMF_ERR_STATE, "snmf_online_batch_set_mel must precede the first process call");
+    if (F_order < 2 || F_order > o->F) return fail(SNMF_ERR_INVALID, "F_order must be in [2, fftlength/2+1]");
+    (void)hipGetLastError();  // clean sticky error state, see PLAN_CHECK
+    HIP_TRY(hipSetDevice(o->ctx->device));
+    hipStream_t st = o->ctx->stream;
+    HIP_TRY(hipStreamSynchronize(st));
+    const snmf_online_params& p = o->p;
+    const int n1 = F_order, S = o->S, r = o->r, F = o->F, Rx = p.R_x, Rd = p.R_d;
+    snmf_plan* hp = nullptr;
+    if (int rc = ob_make_plan(o->ctx, &p, n1, &hp)) {
+        if (hp) snmf_plan_destroy(hp);
+        return rc;
+    }
+    // from here on a failure leaves the batch half converted
+    o->failed = true;
+    snmf_plan_destroy(o->hp);
+    o->hp = hp;
+    ob_free_chunk(o);  // Vp / Ymel / reco depend on the solve's rows
+    for (void** q : {(void**)&o->Wcf, (void**)&o->melmat, (void**)&o->Vm, (void**)&o->Bdf, (void**)&o->Bmx, (void**)&o->Bm, (void**)&o->rs_Bm}) {
+        if (*q) hipFree(*q);
+        *q = nullptr;
+    }
+    const size_t SS = (size_t)S;
+    SN_TRY(dalloc(&o->Wcf, SS * hp->rp * hp->Fp));
+    SN_TRY(dalloc(&o->melmat, (size_t)n1 * F));
+    SN_TRY(dalloc(&o->Bmx, (size_t)n1 * Rx));
+    SN_TRY(dalloc(&o->Bm, SS * r * n1));
+    SN_TRY(dalloc(&o->rs_Bm, SS * Rd * n1));
+    if (p.adapt_train_N) SN_TRY(dalloc(&o->Vm, SS * o->ma * n1));
+    if (!mel_conv) SN_TRY(dalloc(&o->Bdf, SS * r * F));
+    std::vector<double> hx((size_t)n1 * Rx), hd(SS * Rd * n1);
+    for (size_t i = 0; i < hx.size(); ++i) hx[i] = (double)BMx[i];
+    for (size_t i = 0; i < hd.size(); ++i) hd[i] = (double)BMd[i];
+    HIP_TRY(hipMemcpyAsync(o->melmat, melmat, (size_t)n1 * F * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(o->Bmx, hx.data(), hx.size() * 8, hipMemcpyHostToDevice, st));
+    o->mel = 1;
+    o->mel_conv = mel_conv != 0;
+    o->n1 = n1;
+    o->Fs = n1;
+    std::vector<int32_t> all(SS);
+    for (int k = 0; k < S; ++k) all[k] = k;
+    SN_TRY(ob_restart(o, S, all.data(), nullptr, hd.data(), nullptr, nullptr));
+    HIP_TRY(hipStreamSynchronize(st));
+    o->failed = false;
     return SNMF_OK;
 }
 
@@ -265,8 +337,9 @@ static int ob_reserve(snmf_online_batch* o, int C, size_t n_sig, size_t n_out) {
     SN_TRY(dalloc(&o->Ym, F * slots));
     SN_TRY(dalloc(&o->Yph, F * slots));
     SN_TRY(dalloc(&o->Vp, (size_t)pl->Fp * slots));
+    if (o->mel) SN_TRY(dalloc(&o->Ymel, (size_t)o->n1 * slots));
     SN_TRY(dalloc(&o->Hout, (size_t)pl->rp * slots));
-    SN_TRY(dalloc(&o->reco, 2 * F * slots));
+    SN_TRY(dalloc(&o->reco, 2 * (size_t)o->Fs * slots));
     SN_TRY(dalloc(&o->Xt, F * slots));
     if (o->p.class_outputs) {
         SN_TRY(dalloc(&o->Xh, F * slots));
@@ -319,7 +392,7 @@ static int ob_frame_solve(snmf_online_batch* o, int step, int nf) {
     sa.costh = o->costh + off * pl->p.max_iter;
     sa.st = o->st + off;
     sa.tps = 1;
-    sa.recon = o->reco + off * 2 * o->F;
+    sa.recon = o->reco + off * 2 * o->Fs;  // (Mel without MelConv leaves them unread: k_obpost forms B_DFT * A)
     sa.wn = o->wn;
     sa.Rx = o->p.R_x;
     const bool obj = pl->p.cost_check != 0;
@@ -353,10 +426,18 @@ static int ob_adapt(snmf_online_batch* o, const OBatchFrames& fr, int step) {
     hipStream_t st = o->ctx->stream;
     snmf_plan* pl = o->hp;
     const StepArgs sa = make_args(pl);
+    // DFT mode adapts B_DFT_d on lambda_d_blk (:320-338); Mel mode adapts the Mel master's B_Mel_d on melmat * lambda_d_blk
+    // (:298-318), whose fixed columns are its own (:309)
+    double* Bs = o->mel ? o->Bm : o->B;
+    if (o->mel) {
+        hipLaunchKernelGGL(k_obprep_mel, dim3(o->ma, o->S), dim3(256), 0, st, (const OnlineStatus*)o->status, fr.nfr, step, o->S,
+                           (const float*)o->ldblk, (const float*)o->melmat, o->F, o->n1, o->ma, o->Vm);
+        HIP_TRY(hipGetLastError());
+    }
     WBatchArgs w{};
-    w.status = o->status; w.nfr = fr.nfr; w.step = step; w.S = o->S; w.ldblk = o->ldblk; w.adblk = o->adblk; w.rup = o->rup;
-    w.dev = o->dev; w.B = o->B; w.Wu = o->Wu; w.G = o->G; w.P = o->P; w.Vt = o->Vt; w.iters = o->iters;
-    w.F = o->F; w.r = o->r; w.Rx = p.R_x; w.Ra = o->Ra; w.ma = o->ma; w.max_iter = p.max_iter; w.cost_check = p.cost_check;
+    w.status = o->status; w.nfr = fr.nfr; w.step = step; w.S = o->S; w.ldblk = o->mel ? o->Vm : o->ldblk; w.adblk = o->adblk;
+    w.rup = o->rup; w.dev = o->dev; w.B = Bs; w.Wu = o->Wu; w.G = o->G; w.P = o->P; w.Vt = o->Vt; w.iters = o->iters;
+    w.F = o->Fs; w.r = o->r; w.Rx = p.R_x; w.Ra = o->Ra; w.ma = o->ma; w.max_iter = p.max_iter; w.cost_check = p.cost_check;
     w.RA2 = o->RA2; w.sparsity = (float)p.sparsity; w.flr = kFlr; w.beta = sa.beta; w.inv_bb1 = sa.inv_bb1; w.conv_eps = p.conv_eps;
     const size_t lds = wbatch_lds(o->Ra, o->ma, o->RA2, pl->bm == BM_KL);
     auto launch = [&](auto kern) -> int {
@@ -368,14 +449,16 @@ static int ob_adapt(snmf_online_batch* o, const OBatchFrames& fr, int step) {
     if (pl->bm == BM_KL) SN_TRY(launch(k_wadapt_batch<BM_KL>));
     else if (pl->bm == BM_EUC) SN_TRY(launch(k_wadapt_batch<BM_EUC>));
     else SN_TRY(launch(k_wadapt_batch<BM_GEN>));
+    const double* Bfix = o->mel ? o->Bm + (size_t)p.R_x * o->n1 : o->Bfix;
+    const int64_t sfix = o->mel ? (int64_t)o->r * o->n1 : (int64_t)p.R_d * o->F;
     hipLaunchKernelGGL(k_obassemble, dim3(p.R_d, o->S), dim3(256), 0, st, (const OnlineStatus*)o->status, fr.nfr, step, o->S,
-                       (const double*)o->B, (const double*)o->Wu, (const double*)o->Bfix, (const uint8_t*)o->rup, o->F, o->r, p.R_x,
-                       o->Ra, p.R_d, o->Btmp);
+                       (const double*)Bs, (const double*)o->Wu, Bfix, sfix, (const uint8_t*)o->rup, o->Fs, o->r, p.R_x, o->Ra, p.R_d,
+                       o->Btmp);
     HIP_TRY(hipGetLastError());
     ORefreshArgs ra{};
-    ra.status = o->status; ra.nfr = fr.nfr; ra.step = step; ra.S = o->S; ra.Btmp = o->Btmp; ra.B = o->B; ra.Wcf = o->Wcf;
-    ra.wx = o->wx; ra.dphv = o->dphv; ra.wn = o->wn; ra.Hin = o->Hin; ra.H0 = o->H0; ra.lamk = pl->lamk; ra.F = o->F; ra.r = o->r;
-    ra.Rx = p.R_x; ra.rp = pl->rp; ra.Fp = pl->Fp; ra.xr = o->F > 64 * pl->frame_fb; ra.k0 = p.R_x;
+    ra.status = o->status; ra.nfr = fr.nfr; ra.step = step; ra.S = o->S; ra.Btmp = o->Btmp; ra.B = Bs; ra.Wcf = o->Wcf;
+    ra.wx = o->wx; ra.dphv = o->dphv; ra.wn = o->wn; ra.Hin = o->Hin; ra.H0 = o->H0; ra.lamk = pl->lamk; ra.F = o->Fs; ra.r = o->r;
+    ra.Rx = p.R_x; ra.rp = pl->rp; ra.Fp = pl->Fp; ra.xr = o->Fs > 64 * pl->frame_fb; ra.k0 = p.R_x;
     hipLaunchKernelGGL(k_obrefresh, dim3(p.R_d, o->S), dim3(256), 0, st, ra);  // next frame's init_w (:140-146)
     HIP_TRY(hipGetLastError());
     return SNMF_OK;
@@ -433,8 +516,17 @@ static int ob_run_chunk(snmf_online_batch* o, const std::vector<int>& nfr, const
     OStftArgs sa{};
     sa.sig = o->sig; sa.sz = sz; sa.hop = hop; sa.dcbin = p.dcbin; sa.preemph = (float)p.preemph; sa.win = o->win_s; sa.tw = o->tw;
     sa.powv = (float)p.pow; sa.floorv = (float)p.nonzerofloor; sa.Ym = o->Ym; sa.Yph = o->Yph; sa.ld = F; sa.n_frames = C;
-    ob_by_logn([&](auto L) { hipLaunchKernelGGL(k_obstft<decltype(L)::value>, dim3(C, S), dim3(256), 0, st, sa, fr, o->Vp, o->hp->Fp); }, o->N);
-    HIP_TRY(hipGetLastError());
+    if (!o->mel) {
+        ob_by_logn([&](auto L) { hipLaunchKernelGGL(k_obstft<decltype(L)::value>, dim3(C, S), dim3(256), 0, st, sa, fr, o->Vp, o->hp->Fp); }, o->N);
+        HIP_TRY(hipGetLastError());
+    } else {  // the solve input is the Mel features (:106-120)
+        ob_by_logn([&](auto L) { hipLaunchKernelGGL((k_obstft<decltype(L)::value, false>), dim3(C, S), dim3(256), 0, st, sa, fr, o->Vp, o->hp->Fp); },
+                   o->N);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_obmel, dim3(C, S), dim3(256), (size_t)o->n1 * 4, st, (const float*)o->Ym, (const float*)o->melmat, fr.nfr, S, F,
+                           o->n1, o->Ymel, o->Vp, o->hp->Fp);
+        HIP_TRY(hipGetLastError());
+    }
     // post-filter arguments (stream 0's pointers; k_obpost re-bases them)
     OPostArgs a{};
     a.A = o->Hout; a.hst = o->st; a.B = nullptr; a.recon = o->reco; a.Ym = o->Ym; a.lambda_dav = o->lambda_dav; a.Xm_tilde = o->Xm_tilde;
@@ -445,10 +537,16 @@ static int ob_run_chunk(snmf_online_batch* o, const std::vector<int>& nfr, const
     a.switch_at = (int)std::floor(p.overlap_m_a * p.m_a);
     a.alpha_p = (float)p.alpha_p; a.alpha_eta = (float)p.alpha_eta; a.alpha_d = (float)p.alpha_d; a.beta0 = (float)p.beta;
     a.beta_max = (float)p.beta_max; a.Ar_up = (float)p.Ar_up; a.flr = (float)p.nonzerofloor;
-    a.mel = 0; a.mel_conv = 0; a.n1 = 0; a.melmat = nullptr; a.Ymel = nullptr; a.Bmf = nullptr; a.recon_len = F; a.n = 1; a.a_stride = 0;
+    a.mel = o->mel; a.mel_conv = o->mel_conv; a.n1 = o->n1; a.melmat = o->melmat; a.Ymel = o->mel ? o->Ymel : nullptr; a.Bmf = nullptr;
+    a.recon_len = o->Fs; a.n = 1; a.a_stride = 0;
     OBatchPost bp{};
     bp.fr = fr; bp.rp = o->hp->rp; bp.sB = 0;
-    const size_t lds_post = (size_t)(o->r + 7 * F) * 4;
+    if (o->mel && !o->mel_conv) {  // coupled dictionaries: the Mel activations on the stream's DFT bases (:158-202)
+        a.recon = nullptr;
+        a.B = o->Bdf;
+        bp.sB = (int64_t)o->r * F;
+    }
+    const size_t lds_post = (size_t)(o->r + 7 * F + 3 * o->n1) * 4;
     HIP_TRY(hipMemsetAsync(o->iters, 0, (size_t)C * S * 4, st));
     if (!p.adapt_train_N) {
         // fixed dictionaries: every frame solve of the chunk in one launch, then one post-filter launch (snmf_tu_online.hip)
@@ -574,6 +672,7 @@ extern "C" int snmf_online_batch_process_f32(snmf_online_batch* o, const float* 
             short_cap((const void* const*)dh_f32))
             return fail(SNMF_ERR_INVALID, "stream %d: output capacity %lld < %lld samples", s, (long long)cap[s], (long long)need);
     }
+    o->started = true;
     (void)hipGetLastError();  // clean sticky error state, see PLAN_CHECK
     HIP_TRY(hipSetDevice(o->ctx->device));
     for (int s = 0; s < S; ++s) o->pending[s].insert(o->pending[s].end(), pcm[s] ? pcm[s] : nullptr, pcm[s] ? pcm[s] + n[s] : nullptr);
@@ -641,9 +740,8 @@ extern "C" int snmf_online_batch_get_basis_f64(snmf_online_batch* o, int32_t k, 
     return SNMF_OK;
 }
 
-extern "C" int snmf_online_batch_restart(snmf_online_batch* o, int32_t n, const int32_t* slots, const double* Bd, const float* H0,
-                                         const float* Ad) {
-    if (!o) return fail(SNMF_ERR_INVALID, "online batch handle is NULL");
+static int ob_restart_checked(snmf_online_batch* o, int32_t n, const int32_t* slots, const double* Bd, const double* Bmd, const float* H0,
+                              const float* Ad) {
     if (n < 0 || n > o->S) return fail(SNMF_ERR_INVALID, "restart of %d streams in a batch of %d", n, o->S);
     if (n > 0 && !slots) return fail(SNMF_ERR_INVALID, "slots is NULL");
     std::vector<uint8_t> seen(o->S, 0);
@@ -662,10 +760,55 @@ extern "C" int snmf_online_batch_restart(snmf_online_batch* o, int32_t n, const 
     if (n == 0) return SNMF_OK;
     (void)hipGetLastError();  // clean sticky error state, see PLAN_CHECK
     HIP_TRY(hipSetDevice(o->ctx->device));
-    if (int rc = ob_restart(o, n, slots, Bd, H0, o->p.adapt_train_N ? Ad : nullptr)) {
+    if (int rc = ob_restart(o, n, slots, Bd, Bmd, H0, o->p.adapt_train_N ? Ad : nullptr)) {
         o->failed = true;  // some of the listed streams may be half reset
         return rc;
     }
+    return SNMF_OK;
+}
+
+extern "C" int snmf_online_batch_restart(snmf_online_batch* o, int32_t n, const int32_t* slots, const double* Bd, const float* H0,
+                                         const float* Ad) {
+    if (!o) return fail(SNMF_ERR_INVALID, "online batch handle is NULL");
+    return ob_restart_checked(o, n, slots, Bd, nullptr, H0, Ad);  // Mel mode: B_Mel_d carried
+}
+
+extern "C" int snmf_online_batch_restart_mel(snmf_online_batch* o, int32_t n, const int32_t* slots, const double* Bd, const double* Bmd,
+                                             const float* H0, const float* Ad) {
+    if (!o) return fail(SNMF_ERR_INVALID, "online batch handle is NULL");
+    if (Bmd && !o->mel) return fail(SNMF_ERR_STATE, "B_Mel_d given to a batch that is not in Mel mode");
+    return ob_restart_checked(o, n, slots, Bd, Bmd, H0, Ad);
+}
+
+// stream k's B_Mel_d (the fp64 master), n1 x Rd
+static int ob_mel_basis(snmf_online_batch* o, int32_t k, int64_t ld, std::vector<double>& h) {
+    if (!o->mel) return fail(SNMF_ERR_STATE, "not in Mel mode");
+    if (k < 0 || k >= o->S) return fail(SNMF_ERR_INVALID, "stream %d out of range [0, %d)", k, o->S);
+    if (ld < o->n1) return fail(SNMF_ERR_INVALID, "ld < F_order");
+    HIP_TRY(hipSetDevice(o->ctx->device));
+    HIP_TRY(hipStreamSynchronize(o->ctx->stream));
+    const size_t n1 = o->n1;
+    h.resize(n1 * o->p.R_d);
+    HIP_TRY(hipMemcpy(h.data(), o->Bm + (size_t)k * o->r * n1 + (size_t)o->p.R_x * n1, h.size() * 8, hipMemcpyDeviceToHost));
+    return SNMF_OK;
+}
+
+extern "C" int snmf_online_batch_get_mel_basis_f32(snmf_online_batch* o, int32_t k, float* BMd, int64_t ld) {
+    if (!o || !BMd) return fail(SNMF_ERR_INVALID, "NULL argument");
+    std::vector<double> h;
+    SN_TRY(ob_mel_basis(o, k, ld, h));
+    const size_t n1 = o->n1;
+    for (size_t j = 0; j < (size_t)o->p.R_d; ++j)
+        for (size_t m = 0; m < n1; ++m) BMd[j * ld + m] = (float)h[j * n1 + m];  // the single-stream separator's fp32 mirror
+    return SNMF_OK;
+}
+
+extern "C" int snmf_online_batch_get_mel_basis_f64(snmf_online_batch* o, int32_t k, double* BMd, int64_t ld) {
+    if (!o || !BMd) return fail(SNMF_ERR_INVALID, "NULL argument");
+    std::vector<double> h;
+    SN_TRY(ob_mel_basis(o, k, ld, h));
+    const size_t n1 = o->n1;
+    for (size_t j = 0; j < (size_t)o->p.R_d; ++j) std::copy_n(h.data() + j * n1, n1, BMd + j * ld);  // what a carry keeps
     return SNMF_OK;
 }
 

@@ -245,16 +245,22 @@ class OnlineBatchSeparator:
     has its own PCM, noise dictionary and state `g`, and they all advance frame by frame in shared launches.  Stream k's
     output is what `OnlineSeparator` produces for it alone.  `B_DFT_d` is one F x R_d array (copied to every stream) or
     a list of S arrays; `H0` / `Ad_blk0` are lists or arrays stacked along the last axis, by default drawn per stream
-    from RandomState(random_seed + k).  DFT mode and the supervised frame solve only (SNMF_ERR_UNSUPPORTED otherwise)."""
+    from RandomState(random_seed + k).  B_sep_mode 'DFT', or 'Mel' with `B_Mel_x` (F_order x R_x, shared) and `B_Mel_d`
+    (one F_order x R_d array or S of them, like B_DFT_d); the supervised frame solve only (SNMF_ERR_UNSUPPORTED otherwise).
+    In DFT mode the Mel arguments are ignored, as in OnlineSeparator."""
 
-    def __init__(self, B_DFT_x, B_DFT_d, p, n_streams, H0=None, Ad_blk0=None, ctx=None, class_outputs=False):
+    def __init__(self, B_DFT_x, B_DFT_d, p, n_streams, H0=None, Ad_blk0=None, ctx=None, class_outputs=False, B_Mel_x=None,
+                 B_Mel_d=None):
         S = int(n_streams)
         if S < 1:
             raise _invalid("n_streams must be >= 1")
         if p.get("Splice", 0) != 0 or p.get("blk_len_sep", 1) != 1:
             raise NotImplementedError("online path: only Splice=0, blk_len_sep=1 (the shipped settings)")
-        if p.get("B_sep_mode", "DFT") != "DFT":
-            raise SnmfError(8, "batched separator: B_sep_mode 'Mel' is not supported")  # SNMF_ERR_UNSUPPORTED
+        mode = p.get("B_sep_mode", "DFT")
+        if mode not in ("DFT", "Mel"):
+            raise SnmfError(8, f"batched separator: B_sep_mode {mode!r} is not supported")  # SNMF_ERR_UNSUPPORTED
+        if mode == "Mel" and (B_Mel_x is None or B_Mel_d is None):
+            raise SnmfError(8, "batched separator: B_sep_mode 'Mel' needs B_Mel_x and B_Mel_d")
         if "cost_check" not in p:
             raise KeyError("Reference to non-existent field 'cost_check'.")  # src/sparse_nmf.m:260
         method = p.get("ENHANCE_METHOD", "MMSE")
@@ -286,6 +292,16 @@ class OnlineBatchSeparator:
         Bd = _per_stream(B_DFT_d, S, (F, R_d), "B_DFT_d", "F")
         H = _per_stream(H0, S, (r,), "H0", "F")
         Ad = _per_stream(Ad_blk0, S, (R_a, m_a), "Ad_blk0", "F") if adapt else None
+        self.mel = mode == "Mel"
+        if self.mel:
+            n1 = int(p.get("F_order", 64))
+            if not 2 <= n1 <= F:
+                raise _invalid(f"F_order = {n1} outside [2, fftlength/2+1 = {F}]")
+            BMx = np.asfortranarray(B_Mel_x, dtype=np.float32)
+            if BMx.shape != (n1, R_x):
+                raise _invalid(f"B_Mel_x is {BMx.shape}, expected {(n1, R_x)}")
+            BMd = _per_stream(B_Mel_d, S, (n1, R_d), "B_Mel_d", "F")
+            self.n1 = n1
         self._lib = _lib.load()
         self.ctx = ctx or default_context()
         self.F, self.R_x, self.R_d, self.S = F, R_x, R_d, S
@@ -302,6 +318,11 @@ class OnlineBatchSeparator:
                                                       C.byref(h)))
         self._h = h
         self.ctx._plans.add(self)  # destroyed before the context
+        if self.mel:
+            from .frontend import mel_matrix
+            melmat = np.ascontiguousarray(mel_matrix(p["fs"], self.n1, p["fftlength"], 1.0, p["fs"] / 2).T, dtype=np.float32)  # init_buff.m:46
+            _lib.check(self._lib.snmf_online_batch_set_mel(self._h, self.n1, int(bool(p.get("MelConv", 1))), melmat.ctypes.data,
+                                                           BMx.ctypes.data, BMd.ctypes.data))
 
     def process(self, pcms, flush=False):
         """Feed every stream: `pcms` is a list of S sample arrays (any may be empty); `flush` a bool for all or a list of
@@ -336,12 +357,13 @@ class OnlineBatchSeparator:
             outs.append(o)
         return outs
 
-    def restart(self, streams, B_DFT_d=None, H0=None, Ad_blk0=None):
+    def restart(self, streams, B_DFT_d=None, H0=None, Ad_blk0=None, B_Mel_d=None):
         """Streams `streams` (an index or a list of distinct indices) start a new recording: src/NTF_sep_event_RT.m:27-38
         + init_buff, every piece of their state as a new separator gives it, the other streams untouched.  Each of
-        `B_DFT_d` (F x R_d, fp64), `H0` and `Ad_blk0` is None, one array for all listed streams or one per stream.  None
-        keeps the stream's current, adapted B_DFT_d at full fp64 precision (load('B_D_u.mat')) and the H0 / Ad_blk0 it
-        last started with.  A stream that has consumed samples and was not flushed raises SnmfError(7)."""
+        `B_DFT_d` (F x R_d, fp64), `B_Mel_d` (Mel mode: F_order x R_d, fp64), `H0` and `Ad_blk0` is None, one array for all
+        listed streams or one per stream.  None keeps the stream's current, adapted dictionary at full fp64 precision
+        (load('B_D_u.mat'), :27-38 load both) and the H0 / Ad_blk0 it last started with.  A stream that has consumed
+        samples and was not flushed raises SnmfError(7), and so does a B_Mel_d outside Mel mode."""
         ks = [int(streams)] if np.isscalar(streams) else [int(k) for k in streams]
         n = len(ks)
         bad = [k for k in ks if not 0 <= k < self.S]
@@ -352,11 +374,17 @@ class OnlineBatchSeparator:
         Bd = None if B_DFT_d is None else _per_stream(B_DFT_d, n, (self.F, self.R_d), "B_DFT_d", "F", np.float64)
         H = None if H0 is None else _per_stream(H0, n, (self.R_x + self.R_d,), "H0", "F")
         Ad = None if (Ad_blk0 is None or not self.adapt) else _per_stream(Ad_blk0, n, (self.R_a, self.m_a), "Ad_blk0", "F")
+        if B_Mel_d is not None and not self.mel:
+            raise SnmfError(7, "B_Mel_d given to a batch that is not in Mel mode")  # SNMF_ERR_STATE, as the C entry
+        Bm = None if B_Mel_d is None else _per_stream(B_Mel_d, n, (self.n1, self.R_d), "B_Mel_d", "F", np.float64)
         if n == 0:
             return
         sl = np.array(ks, dtype=np.int32)
         ptr = lambda a: a.ctypes.data if a is not None else None  # noqa: E731
-        _lib.check(self._lib.snmf_online_batch_restart(self._h, n, sl.ctypes.data, ptr(Bd), ptr(H), ptr(Ad)))
+        if self.mel:
+            _lib.check(self._lib.snmf_online_batch_restart_mel(self._h, n, sl.ctypes.data, ptr(Bd), ptr(Bm), ptr(H), ptr(Ad)))
+        else:
+            _lib.check(self._lib.snmf_online_batch_restart(self._h, n, sl.ctypes.data, ptr(Bd), ptr(H), ptr(Ad)))
 
     def basis(self, k):
         """Current B_DFT_d of stream k."""
@@ -368,6 +396,22 @@ class OnlineBatchSeparator:
         """Stream k's fp64 master of B_DFT_d: what a carry (restart with B_DFT_d=None) keeps."""
         B = np.zeros((self.F, self.R_d), dtype=np.float64, order="F")
         _lib.check(self._lib.snmf_online_batch_get_basis_f64(self._h, int(k), B.ctypes.data, self.F))
+        return B
+
+    def mel_basis(self, k):
+        """Current B_Mel_d of stream k (Mel mode: the dictionary the adaptation updates, :318)."""
+        if not self.mel:
+            raise SnmfError(7, "not in Mel mode")
+        B = np.zeros((self.n1, self.R_d), dtype=np.float32, order="F")
+        _lib.check(self._lib.snmf_online_batch_get_mel_basis_f32(self._h, int(k), B.ctypes.data, self.n1))
+        return B.astype(np.float64)
+
+    def mel_basis_f64(self, k):
+        """Stream k's fp64 master of B_Mel_d: what a carry (restart with B_Mel_d=None) keeps."""
+        if not self.mel:
+            raise SnmfError(7, "not in Mel mode")
+        B = np.zeros((self.n1, self.R_d), dtype=np.float64, order="F")
+        _lib.check(self._lib.snmf_online_batch_get_mel_basis_f64(self._h, int(k), B.ctypes.data, self.n1))
         return B
 
     def trace(self, k):
@@ -391,13 +435,15 @@ class OnlineBatchSeparator:
             pass
 
 
-def ntf_sep_event_rt_batch(pcms, B_DFT_x, B_DFT_d, p, H0=None, Ad_blk0=None, ctx=None):
+def ntf_sep_event_rt_batch(pcms, B_DFT_x, B_DFT_d, p, H0=None, Ad_blk0=None, ctx=None, B_Mel_x=None, B_Mel_d=None):
     """src/NTF_sep_event_RT.m for several recordings at once (the per-target loop of Do_MultiBatch_IS16_20160324.m:183-205
-    as one batch): returns a list of the (int16, float, final B_DFT_d) triples ntf_sep_event_rt returns."""
-    sep = OnlineBatchSeparator(B_DFT_x, B_DFT_d, p, len(pcms), H0=H0, Ad_blk0=Ad_blk0, ctx=ctx)
+    as one batch): returns a list of the (int16, float, final B_DFT_d) triples ntf_sep_event_rt returns (Mel mode: the
+    final B_Mel_d)."""
+    sep = OnlineBatchSeparator(B_DFT_x, B_DFT_d, p, len(pcms), H0=H0, Ad_blk0=Ad_blk0, ctx=ctx, B_Mel_x=B_Mel_x, B_Mel_d=B_Mel_d)
     try:
         outs = sep.process(list(pcms), flush=True)
-        return [(o["x_tilde"].copy(), o["x_tilde_f"].astype(np.float64), sep.basis(k)) for k, o in enumerate(outs)]
+        fin = sep.mel_basis if sep.mel else sep.basis
+        return [(o["x_tilde"].copy(), o["x_tilde_f"].astype(np.float64), fin(k)) for k, o in enumerate(outs)]
     finally:
         sep.close()
 
@@ -427,7 +473,8 @@ def _per_chain(x, n, shape, name, dtype):
     return out
 
 
-def ntf_sep_event_rt_chains(chains, B_DFT_x, B_DFT_d, p, n_streams=None, H0=None, Ad_blk0=None, ctx=None, chunk_hops=None):
+def ntf_sep_event_rt_chains(chains, B_DFT_x, B_DFT_d, p, n_streams=None, H0=None, Ad_blk0=None, ctx=None, chunk_hops=None,
+                            B_Mel_x=None, B_Mel_d=None):
     """Do_MultiBatch_IS16_20160324.m:183-205 + run_ntf_sep_RT.m:10-41 on one batch: `chains` is a list of chains, each a
     list of PCM arrays enhanced in turn by src/NTF_sep_event_RT.m.  Chain c starts from B_DFT_d (one array or one per
     chain; the delete('B_D_u.mat') of :187), and every later file starts from the dictionary its predecessor adapted,
@@ -439,7 +486,8 @@ def ntf_sep_event_rt_chains(chains, B_DFT_x, B_DFT_d, p, n_streams=None, H0=None
     carried dictionary or with its next chain's.  Chain c uses its own H0 / Ad_blk0 (one array or one per chain; by
     default drawn from RandomState(random_seed + c), as OnlineBatchSeparator draws for stream k) for all its files, so
     its bits depend neither on its slot, `n_streams` or `chunk_hops` nor on the other chains.  Start dictionaries enter
-    in fp32, as in ntf_sep_event_rt_batch."""
+    in fp32, as in ntf_sep_event_rt_batch.  In Mel mode (B_Mel_x, and B_Mel_d as one array or one per chain) a chain
+    carries both dictionaries (:137-139) and its triples hold the final B_Mel_d."""
     chains = [[np.asarray(x).reshape(-1) for x in c] for c in chains]
     nc = len(chains)
     if nc == 0:
@@ -459,6 +507,12 @@ def ntf_sep_event_rt_chains(chains, B_DFT_x, B_DFT_d, p, n_streams=None, H0=None
     adapt = int(bool(p.get("adapt_train_N", 0)))
     R_a, m_a = int(p.get("R_a", 1)), int(p.get("m_a", 1))
     Bds = _per_chain(B_DFT_d, nc, (F, R_d), "B_DFT_d", np.float32)  # (fp32 values, restarted with in fp64)
+    mel = p.get("B_sep_mode", "DFT") == "Mel"
+    Bms = None
+    if mel:
+        if B_Mel_x is None or B_Mel_d is None:
+            raise SnmfError(8, "batched separator: B_sep_mode 'Mel' needs B_Mel_x and B_Mel_d")
+        Bms = _per_chain(B_Mel_d, nc, (int(p.get("F_order", 64)), R_d), "B_Mel_d", np.float32)
     if H0 is not None:
         H0 = _per_chain(H0, nc, (r,), "H0", np.float64)
     if adapt and Ad_blk0 is not None:
@@ -483,7 +537,9 @@ def ntf_sep_event_rt_chains(chains, B_DFT_x, B_DFT_d, p, n_streams=None, H0=None
     init = [first[k] if k < len(first) else first[0] for k in range(S)]
     dr = {c: draws(c) for c in set(init)}
     sep = OnlineBatchSeparator(Bx, [Bds[c] for c in init], p, S, H0=[dr[c][0] for c in init],
-                               Ad_blk0=[dr[c][1] for c in init] if adapt else None, ctx=ctx)
+                               Ad_blk0=[dr[c][1] for c in init] if adapt else None, ctx=ctx, B_Mel_x=B_Mel_x,
+                               B_Mel_d=[Bms[c] for c in init] if mel else None)
+    fin = sep.mel_basis if mel else sep.basis
     hop = sep.hop
     step = int(chunk_hops) if chunk_hops else max(1, min(4096, _B_CHUNK_SLOTS // S))
     if step < 1:
@@ -494,11 +550,12 @@ def ntf_sep_event_rt_chains(chains, B_DFT_x, B_DFT_d, p, n_streams=None, H0=None
         carry, fresh = [], []
         while busy:
             if carry:
-                sep.restart(carry)  # same chain: the adapted fp64 dictionary, the chain's own H0 / Ad_blk0
+                sep.restart(carry)  # same chain: the adapted fp64 dictionaries, the chain's own H0 / Ad_blk0
             if fresh:
                 cs = [busy[k][0] for k in fresh]
                 ds = [draws(c) for c in cs]
-                sep.restart(fresh, [Bds[c] for c in cs], [d[0] for d in ds], [d[1] for d in ds] if adapt else None)
+                sep.restart(fresh, [Bds[c] for c in cs], [d[0] for d in ds], [d[1] for d in ds] if adapt else None,
+                            B_Mel_d=[Bms[c] for c in cs] if mel else None)
             carry, fresh = [], []
             pcms, flush = [np.zeros(0, np.float32)] * S, [False] * S
             for k, st in busy.items():
@@ -514,7 +571,7 @@ def ntf_sep_event_rt_chains(chains, B_DFT_x, B_DFT_d, p, n_streams=None, H0=None
                 if not flush[k]:
                     continue
                 c, i = st[0], st[1]
-                results[c].append((np.concatenate(st[3]).astype(np.int16), np.concatenate(st[4]).astype(np.float64), sep.basis(k)))
+                results[c].append((np.concatenate(st[3]).astype(np.int16), np.concatenate(st[4]).astype(np.float64), fin(k)))
                 if i + 1 < len(chains[c]):
                     busy[k] = [c, i + 1, 0, [], []]
                     carry.append(k)
