@@ -554,6 +554,9 @@ int snmf_ctx_xfer_stats(snmf_ctx* ctx, double* out8, int reset);
 int snmf_ctx_timing_get(snmf_ctx* ctx, const char* family, double* avg_ms, int64_t* launches);
 /* Kernel geometry chosen for a plan, for DESIGN.md / profiles bookkeeping. */
 int snmf_plan_describe(const snmf_plan* plan, char* buf, size_t buflen);
+/* The same text for a plan of parameters p on a device of n_cu compute units, without a device: p is validated as by
+ * snmf_plan_create, and the text is what snmf_plan_describe gives for such a plan without an observed/missing mask. */
+int snmf_plan_geometry_describe(const snmf_params* p, int32_t n_cu, char* buf, size_t buflen);
 
 #ifdef __cplusplus
 }

@@ -17,9 +17,6 @@ LIB_PATH = os.path.join(_HERE, "libsnmf_hip.so")
 import glob as _glob
 # The library is several translation units compiled in parallel and linked once (csrc/snmf_internal.h says which is which).
 SRC = sorted(_glob.glob(os.path.join(_HERE, "csrc", "*.hip")))
-# experiment kernels (csrc/experiments/: k_hstep_m, the merged-role H step -- 15 % slower than the shipped kernel, kept for its
-# counters): only in builds that ask for them, SNMF_EXPERIMENTS=1 python scripts/build_variant.py exp -> -DSNMF_EXPERIMENTS
-SRC_EXPERIMENTS = sorted(_glob.glob(os.path.join(_HERE, "csrc", "experiments", "*.hip")))
 OBJ_DIR = os.path.join(_ROOT, "build", "obj")
 # headers each translation unit includes beyond the ones every unit does (an edit to a header rebuilds only its users)
 _COMMON_HDRS = ["snmf_internal.h", "snmf_kernels.h", os.path.join(_ROOT, "include", "snmf.h")]
@@ -38,7 +35,7 @@ _TU_HDRS = {
     "snmf_tu_smallf.hip": ["snmf_smallf.h"],
     "snmf_tu_itersf.hip": ["snmf_smallf.h"],
     "snmf_tu_smallr.hip": ["snmf_smallf.h", "snmf_smallr.h"],
-    "snmf_tu_hstep_m.hip": ["experiments/snmf_hstep_m.h"],
+    "snmf_tu_geometry.hip": ["snmf_generic.h"],
 }
 HDRS = sorted(_glob.glob(os.path.join(_HERE, "csrc", "*.h"))) + [os.path.join(_ROOT, "include", "snmf.h")]
 
@@ -55,7 +52,7 @@ SYMBOLS = [
     "snmf_plan_stopped", "snmf_plan_run_sharded",
     "snmf_plan_get_w_f64", "snmf_plan_get_w_f32", "snmf_plan_get_h_f64", "snmf_plan_get_h_f32",
     "snmf_plan_get_objective", "snmf_plan_solve_frames_f64", "snmf_plan_solve_frames_f32",
-    "snmf_ctx_timing", "snmf_ctx_timing_get", "snmf_plan_describe",
+    "snmf_ctx_timing", "snmf_ctx_timing_get", "snmf_plan_describe", "snmf_plan_geometry_describe",
     "snmf_stft_num_frames", "snmf_stft_features_f32", "snmf_plan_set_v_from_audio_f32", "snmf_mel_features_f32", "snmf_tf_dd_f32",
     "snmf_plan_set_mask_f64", "snmf_plan_set_mask_f32", "snmf_plan_get_v_mdi_f64", "snmf_plan_get_v_mdi_f32",
     "snmf_online_create", "snmf_online_set_mel", "snmf_online_get_mel_basis_f32", "snmf_online_process_f32", "snmf_online_get_basis_f32", "snmf_online_trace",
@@ -150,11 +147,8 @@ def build(force=False, verbose=False, jobs=None, extra_flags=(), lib_path=None, 
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     flags = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-Wno-unused-value",
              "-I" + os.path.join(_ROOT, "include"), "-I" + os.path.join(_HERE, "csrc")] + list(extra_flags)
-    experiments = os.environ.get("SNMF_EXPERIMENTS", "0") == "1" or "-DSNMF_EXPERIMENTS" in flags
-    if experiments and "-DSNMF_EXPERIMENTS" not in flags:
-        flags.append("-DSNMF_EXPERIMENTS")
     todo, objs = [], []
-    for src in SRC + (SRC_EXPERIMENTS if experiments else []):
+    for src in SRC:
         obj = os.path.join(obj_dir, os.path.splitext(os.path.basename(src))[0] + ".o")
         objs.append(obj)
         deps = [d for d in _tu_deps(src) if os.path.exists(d)]
@@ -244,6 +238,7 @@ def load():
         "snmf_ctx_timing": (C.c_int, [vp, C.c_int]),
         "snmf_ctx_timing_get": (C.c_int, [vp, C.c_char_p, C.POINTER(dbl), C.POINTER(i64)]),
         "snmf_plan_describe": (C.c_int, [vp, C.c_char_p, C.c_size_t]),
+        "snmf_plan_geometry_describe": (C.c_int, [PP, i32, C.c_char_p, C.c_size_t]),
     }
     SP = C.POINTER(SnmfStftParams)
     sig["snmf_stft_num_frames"] = (i64, [SP, i64])

@@ -461,6 +461,17 @@ class RcclComm:
             pass
 
 
+def geometry_describe(F, T, r, *, beta=1.0, n_cu=256, w_update_ind=None, h_update_ind=None):
+    """What Plan(...).describe() reports for a plan of this shape on a device of n_cu compute units, computed without a
+    device (snmf_plan_geometry_describe)."""
+    w = None if w_update_ind is None else np.ascontiguousarray(np.asarray(w_update_ind) != 0, np.uint8)
+    h = None if h_update_ind is None else np.ascontiguousarray(np.asarray(h_update_ind) != 0, np.uint8)
+    sp = _make_params(F, T, r, beta, 1, 0.0, True, True, 0, 0.0, w, h)
+    buf = C.create_string_buffer(1024)
+    _lib.check(_lib.load().snmf_plan_geometry_describe(C.byref(sp), int(n_cu), buf, 1024))
+    return buf.value.decode()
+
+
 class Plan:
     """snmf_plan: a problem resident in HBM (V, W, H + workspaces).  Arrays may be numpy (host)
     or anything exposing ``data_ptr()``/``dtype`` on the context's device (torch tensors)."""

@@ -211,392 +211,19 @@ static int hupd_parts(const snmf_plan* pl);  // (objective partials of an H-upda
 extern "C" int snmf_plan_create(snmf_ctx* ctx, const snmf_params* p, snmf_plan** out) {
     if (!ctx || !out) return fail(SNMF_ERR_INVALID, "NULL argument");
     *out = nullptr;
-    SN_TRY(validate_params(p));
+    PlanGeometry geo;
+    SN_TRY(plan_geometry(p, ctx->n_cu, &geo));
     (void)hipGetLastError();  // start from a clean (sticky, per-thread) HIP error state, see PLAN_CHECK
     HIP_TRY(hipSetDevice(ctx->device));
     snmf_plan* pl = new snmf_plan();
+    static_cast<PlanGeometry&>(*pl) = geo;
     pl->ctx = ctx;
     pl->p = *p;
     pl->p.w_update_ind = nullptr;
     pl->p.h_update_ind = nullptr;
-    const int F = p->F, T = p->T, r = p->r;
-    // masks (src/sparse_nmf.m:142-148, :176-179)
-    int n_h = 0, n_w = 0;
+    const int r = p->r;
     pl->h_w_ind.assign(r, 1);
-    for (int k = 0; k < r; ++k) {
-        const bool hk = p->h_update_ind ? p->h_update_ind[k] != 0 : true;
-        const bool wk = p->w_update_ind ? p->w_update_ind[k] != 0 : true;
-        n_h += hk;
-        n_w += wk;
-        pl->h_w_ind[k] = wk;
-    }
-    if (n_h != 0 && n_h != r) {
-        delete pl;
-        // bsxfun(@plus, sum(w(:,h_ind))', p.sparsity) with sum(h_ind) ~= r rows: MATLAB size error
-        return fail(SNMF_ERR_DIM,
-                    "partial h_update_ind (%d of %d rows): dimension mismatch in src/sparse_nmf.m:192/197/202", n_h, r);
-    }
-    pl->upd_h = n_h > 0;
-    pl->upd_w = n_w > 0;
-    pl->bm = (p->beta == 1.0) ? BM_KL : (p->beta == 2.0 ? BM_EUC : BM_GEN);
-    pl->n_mat = pl->bm == BM_KL ? 1 : 2;
-
-    // row geometry (see snmf_kernels.h): F = 32*nf + 1 (257, 513, ...) -> extra-row mode
-    pl->xr = (F % 32 == 1 && F > 32) ? 1 : 0;
-    pl->nf = pl->xr ? F / 32 : (int)roundup(F, 32) / 32;
-    pl->Fm = 32 * pl->nf;
-    pl->Fp = pl->Fm + 4 * pl->xr;
-    pl->Fq = pl->Fm + 8 * pl->xr;
-    pl->rp = (int)roundup(r, 32);
-    pl->Tp = (int)roundup(T + 32, 64);  // >= 32 zero columns of slack: a 32-frame tile may start at any frame
-    pl->nk = pl->rp / 32;
-    pl->ldh = pl->rp + 4;
-    pl->ldr = pl->Fq + 4;
-    // k_hstep geometry: prefer two 4-wave workgroups per CU on 32-frame tiles (their phases
-    // de-synchronise and keep the matrix pipe fed); otherwise one 8-wave workgroup per CU on the
-    // widest tile whose H image + ratio image fit the 160 KiB LDS.
-    const size_t per_col = (size_t)(pl->ldh + pl->ldr) * 4;
-    const size_t lds_cap = 160 * 1024;  // gfx950: 160 KiB per CU, one workgroup may take all of it
-    const size_t lds_extra = (size_t)pl->rp * 4 + 128;  // extra row of W + the roles' progress slots (6 signals x 4 waves) + the split tile's flag
-    const size_t lds1 = 32 * per_col + lds_extra, lds2 = 64 * per_col + lds_extra;
-    if (2 * lds1 - lds_extra <= lds_cap) { pl->NWH = 8; pl->NT = 1; pl->NLH = 4; }  // double-buffered
-    else if (lds2 <= lds_cap && pl->Tp / 64 >= ctx->n_cu) { pl->NWH = 8; pl->NT = 2; }
-    else if (lds1 <= lds_cap) { pl->NWH = 8; pl->NT = 1; }
-    else if (16 * per_col + lds_extra <= lds_cap) {
-        // the H image + ratio image of 32 frames do not fit (F + r > 1272, e.g. the reference's exemplar setting
-        // R_x = R_d = 500 at F = 513, settings/bak_IS16_results/initial_setting_Exemplar.m:47-48): 16-frame tiles
-        pl->NWH = 8; pl->NT = 1; pl->TTH = 16;
-    } else {
-        // F + r beyond what a 16-frame tile's H block + ratio image take of the LDS (~2540): the out-of-envelope path
-        pl->generic = true;
-        pl->NWH = 8; pl->NT = 1; pl->TTH = 16;
-    }
-    if (const char* e = getenv("SNMF_HSTEP_RP")) pl->hstep_rp = atoi(e) != 0;
-    // A workgroup with a single tile has nothing to pipeline: the role pipelines' hand-offs then only add latency (C1,
-    // 257 x 2000 r = 40, 63 tiles: k_hstep 16.9 us against k_hstep_rp 18.5), so such problems take the barrier-phased kernel
-    if ((T + 31) / 32 <= ctx->n_cu) pl->hstep_rp = false;
-    // F = 513 (9..16 row tiles): two whole tile buffers do not fit, but two H blocks + ONE ratio image do -- k_hstep_rh
-    // pipelines on half tiles.  One pair of column tiles per wave of its P2 team: rp <= 256.
-    pl->lds_rh = std::max<size_t>(((size_t)2 * 32 * pl->ldh + (size_t)32 * pl->ldr + pl->rp) * 4 + 160, 2 * kMaxNW * 64 * sizeof(double));
-    pl->rh = pl->hstep_rp && pl->NLH != 4 && pl->bm == BM_KL && pl->nf >= 9 && pl->nf <= 16 && pl->rp <= 256 && pl->lds_rh <= lds_cap;
-    // r = 97..100 on 16 row tiles (the reference's R = 100 at F = 513): P2 cut over the contraction, the 1..4 real columns of
-    // the fourth column tile as 4x4x1 MFMAs on the same ratio fragments (k_hstep_rh<OBJ, LXH>); needs 52 KB more LDS for the waves' partial tiles
-    {
-        const size_t lx = pl->lds_rh + 4 * 3 * 1024 * 4 + 4 * 64 * 16;  // the B waves' partial tiles + partial leftover columns
-        pl->rh_lxh = (pl->rh && pl->nf == 16 && pl->nk == 4 && r > 96 && r <= 100 && lx <= lds_cap) ? 1 : 0;
-        if (pl->rh_lxh) pl->lds_rh = lx;
-        // r = 193..200 on 16 row tiles (R_x + R_d = 200 at F = 513, run_basis_DNMF.m:40): seven column tiles -> the B waves work
-        // in pairs over three full tiles each, cut in two over the contraction (k_hstep_rh<OBJ, 2>); 29 KB more LDS
-        const size_t lx2 = pl->lds_rh + (size_t)(4 * 6 * 256 + 4 * 64 * 4 + pl->rp) * 4;
-        const char* ec = getenv("SNMF_RH_CUT2");
-        if (pl->rh && !pl->rh_lxh && pl->nf == 16 && pl->nk == 7 && r > 192 && r <= 200 && lx2 <= lds_cap && !(ec && atoi(ec) == 0)) {
-            pl->rh_lxh = 2;
-            pl->lds_rh = lx2;
-        }
-    }
-    pl->lds_h = std::max<size_t>(pl->NLH ? 2 * lds1 - lds_extra : (pl->NT == 1 ? (size_t)pl->TTH * per_col + lds_extra : lds2),
-                                 2 * kMaxNW * 64 * sizeof(double));
-    // one or two column tiles (r <= 64) on the double-buffered role pipeline: P2 cut over the contraction (k_hstep_rp<., CUT>):
-    // 32 KB of partial tiles + 1 ./ dph + two more signals behind the buffers
-    {
-        const char* e = getenv("SNMF_RP_CUT");
-        const size_t more = 32 + (size_t)4 * pl->nk * 1024 * 4 + (size_t)pl->rp * 4;
-        const bool shape_ok = pl->NLH == 4 && pl->NWH == 8 && pl->bm == BM_KL && pl->nk <= 2 && pl->nf >= 4 && !(e && atoi(e) == 0);
-        // (rp_cut = 2: the PAIR form -- two column tiles, 8 KB of partials -- where the four-way form's 32 KB do not fit: 513 rows, r = 33..64)
-        const size_t more2 = 32 + (size_t)2048 * 4 + (size_t)pl->rp * 4;
-        pl->rp_cut = !shape_ok ? 0 : pl->lds_h + more <= lds_cap ? 1 : (pl->nk == 2 && pl->lds_h + more2 <= lds_cap) ? 2 : 0;
-        if (pl->rp_cut) pl->lds_h += pl->rp_cut == 2 ? more2 : more;
-    }
-    pl->lds_mdi = std::max<size_t>(lds1, 2 * kMaxNW * 64 * sizeof(double));  // MDI pass: (NW=8, NT=1, NL=0)
-    pl->grid_mdi = std::max(1, std::min(pl->Tp / 32, ctx->n_cu));
-    const int n_tiles_h = pl->Tp / (pl->TTH * pl->NT);
-    // without loaders the NT == 1 kernels are register-bounded for two workgroups per CU
-    int wg_per_cu = (pl->lds_h * 2 <= lds_cap && pl->NT == 1 && !pl->NLH) ? 2 : 1;
-    pl->grid_h = std::max(1, std::min(n_tiles_h, ctx->n_cu * wg_per_cu));
-    // k_hstep_rp: only tiles that hold a frame (the pad tiles of both H buffers are zero and stay zero), and the last
-    // PARTIAL round split by rows over the workgroups that would idle through it (snmf_kernels.h, "the split last round"):
-    // 4 parts per tile when 4 * (tiles of that round) workgroups exist, else 2, else the round stays whole.
-    // SNMF_HSTEP_SPLIT=0 keeps every tile in the pipeline (tests compare the two).
-    {
-        const int G = ctx->n_cu;
-        pl->rp_tiles = (T + 31) / 32;
-        pl->rp_full = pl->rp_tiles;
-        pl->rp_grid = std::max(1, std::min(pl->rp_tiles, G));  // (k_hstep_rh launches on the same grid)
-        pl->rp_S = 0;
-        const char* e = getenv("SNMF_HSTEP_SPLIT");
-        // (k_hstep_rh splits by CONTIGUOUS row tiles within a half: 16 row tiles only, F = 505..513)
-        if ((pl->NLH == 4 || (pl->rh && pl->nf == 16)) && !pl->rp_cut && !(e && atoi(e) == 0)) {
-            // (only a partial round BEHIND whole ones: a problem of fewer tiles than workgroups is latency-bound, and there
-            //  the split's extra steps -- partial stores, the arrival counter, the finishing pass -- cost more than the
-            //  shorter MFMA loops save: C1, 257 x 2000 r = 40, ran 23.3 k iterations/s split against 26.7 k whole)
-            const int full = (pl->rp_tiles / G) * G, R = pl->rp_tiles - full;
-            int S = (full > 0 && R > 0) ? (4 * R <= G ? 4 : (2 * R <= G ? 2 : 0)) : 0;
-            while (S > pl->nf) S >>= 1;
-            if (S >= 2) {
-                pl->rp_S = S;
-                pl->rp_full = full;
-                pl->rp_grid = G;
-            }
-        }
-    }
-    // k_hstep_m (merged roles: one wave per SIMD runs P1, both epilogues and P2 of its own rows / columns, snmf_hstep_m.h): the
-    // double-buffered geometry with exactly 8 row tiles and 8 column tiles (C2).  SNMF_HSTEP_M=1 selects it (A/B against k_hstep_rp).
-    // An EXPERIMENT (15 % slower than k_hstep_rp, kept as the vehicle of the counters in profiles/r05_experiments.md section 1): only
-    // in builds with -DSNMF_EXPERIMENTS (SNMF_EXPERIMENTS=1 python scripts/build_variant.py exp), whose sources then include
-    // csrc/experiments/; the product library has neither the kernel nor the switch.
-#ifdef SNMF_EXPERIMENTS
-    {
-        const char* e = getenv("SNMF_HSTEP_M");
-        pl->hm = e && atoi(e) != 0 && pl->hstep_rp && pl->NWH == 8 && pl->NLH == 4 && pl->bm == BM_KL && pl->nf == 8 && pl->nk == 8 && !pl->generic;
-        pl->hm_grid = std::max(1, std::min(pl->rp_tiles, ctx->n_cu));
-    }
-#endif
-    // At most two row tiles and eight column tiles (the Mel solves, r <= 256): a tile per WAVE, nothing handed between waves
-    // (snmf_smallf.h).  Follows SNMF_HSTEP_RP (tests compare against the barrier-phased kernels); SNMF_HSTEP_SF=0 keeps the
-    // role pipeline.
-    {
-        const char* e = getenv("SNMF_HSTEP_RP");
-        const char* e2 = getenv("SNMF_HSTEP_SF");
-        pl->lds_sf = ((size_t)pl->nf * pl->rp * 32 + (size_t)pl->nk * pl->Fq * 32 + 2 * (size_t)pl->rp) * 4 + 2 * 8 * sizeof(double);
-        pl->sf = pl->bm == BM_KL && pl->upd_h && !pl->xr && pl->nf <= 2 && pl->nk <= 8 && pl->lds_sf <= lds_cap && !pl->generic &&
-                 !(e && atoi(e) == 0) && !(e2 && atoi(e2) == 0);
-        pl->sf_grid = std::max(1, std::min((T + 31) / 32, ctx->n_cu));
-        // the shared last tile: when the partial wave level behind the whole ones is the FIRST on its SIMDs (level 0 or 4 of 8: any other
-        // level runs beside whole tiles of the same round on other SIMDs and sharing it would not end the launch earlier).  SNMF_HSTEP_SPLIT=0
-        // keeps every tile whole, like the split last round of k_hstep_rp.
-        {
-            const int nw = 8 * pl->sf_grid, R = pl->rp_tiles % nw, wfull = R / pl->sf_grid, xb = R % pl->sf_grid;
-            const char* e4 = getenv("SNMF_HSTEP_SPLIT");
-            const size_t more = (size_t)pl->nf * 16384 + 16;
-            pl->sf_share = 0;
-            pl->sf_nfull = pl->rp_tiles;
-            // (not for the full updates that snmf_plan_run fuses into k_iter_sf: the step API's two launches -- the sharded loop -- stay
-            //  bit for bit what the fused launch computes with every tile whole, tests/test_gpu_parity.py::test_fused_small_f_iteration_equals_the_two_launches;
-            //  k_iter_sf shares a chunk's remainder tile in its own way, isf_share)
-            const bool isf_shape = pl->upd_h && pl->upd_w && pl->nf == 2 && pl->nk >= 3 && pl->nk <= 4;
-            if (pl->sf && !isf_shape && xb > 0 && (wfull == 0 || wfull == 4) && pl->nk >= 2 && pl->lds_sf + more <= lds_cap && !(e4 && atoi(e4) == 0)) {
-                pl->sf_share = xb;
-                pl->sf_nfull = pl->rp_tiles - xb;
-                pl->lds_sf += more;
-            }
-        }
-        pl->sf_stagger = 8000;
-        if (const char* e3 = getenv("SNMF_SF_STAG")) pl->sf_stagger = atoi(e3);
-    }
-    // k_wstats geometry: 4-wave workgroups, each wave owns one 32-row tile x NKT 32-column tiles of
-    // the statistics in registers.  NKT <= 8 (128 accumulator VGPRs): two workgroups per CU.
-    if (pl->nk <= 4) { pl->NKT = 4; pl->WPS = 2; }
-    else if (pl->nk <= 8) { pl->NKT = 8; pl->WPS = 2; }
-    else { pl->NKT = 16; pl->WPS = 1; }
-    // (eight consumer waves, two per SIMD, for narrow statistics over at least eight row tiles: see the kernel)
-    pl->NWB = (pl->NKT == 4 && pl->nf >= 8) ? 8 : 4;
-    pl->n_kg = (pl->nk + pl->NKT - 1) / pl->NKT;
-    pl->n_fg = (pl->nf + pl->NWB - 1) / pl->NWB;
-    // H image of k_wstats: rows padded to whole NKT-tile groups (branch-free P4, see the kernel)
-    pl->ldhw = std::max(pl->rp, 32 * pl->NKT * pl->n_kg) + 4;  // (NKT = 4: always 132 -- k_wstats<4, ...> has it as a compile-time constant)
-    if (((size_t)32 * pl->ldhw + (size_t)32 * 32 * pl->NWB) * 4 + (size_t)pl->rp * 4 + 320 > lds_cap && pl->NKT == 16)
-        pl->TTW = 16;  // large r: 16-frame tiles (the 32-frame H + V images do not fit the LDS)
-    const int n_tiles_w = (T + pl->TTW - 1) / pl->TTW;  // tiles that hold a frame (an all-padding tile adds exact zeros: skipped)
-    {
-        // loaders + double buffering when the accumulators allow 2 waves per SIMD and LDS has room; the loader waves
-        // stage only the row group's 32 * NWB columns of V (the kernel's ldv), so F = 513 fits as well
-        const size_t buf_ld = ((size_t)pl->TTW * pl->ldhw + (size_t)pl->TTW * 32 * pl->NWB) * 4;
-        pl->NLW = (pl->WPS == 2 && 2 * buf_ld + (size_t)pl->rp * 4 + 512 + (size_t)pl->NWB * std::min(pl->rp, 256) * 4 <= lds_cap) ? 4 : 0;
-        // (loader waves pay from the second tile of a workgroup on; with one tile each -- C1: 63 tiles -- the synchronous
-        //  4-wave geometry is faster: 12.7 us against 16.4)
-        if (n_tiles_w <= ctx->n_cu / std::max(1, ((pl->nf + 3) / 4) * pl->n_kg)) pl->NLW = 0;
-        if (const char* e = getenv("SNMF_WSTATS_NL")) pl->NLW = (atoi(e) == 4 && pl->NLW == 4) ? 4 : 0;
-        size_t buf = buf_ld;
-        if (!pl->NLW && pl->NWB == 8) {  // the eight-consumer geometry exists with loader waves only
-            pl->NWB = 4;
-            pl->n_fg = (pl->nf + pl->NWB - 1) / pl->NWB;
-            buf = ((size_t)pl->TTW * pl->ldhw + (size_t)pl->TTW * 32 * pl->NWB) * 4;
-        }
-        // (the fixed-order sums at the end of the kernel use [4][rp] floats / one double per thread of the same memory)
-        // (+ ready/done slots + the extra row's V values [2][32] + the consumers' partial extra rows of the slab, NK <= 8)
-        const size_t gxs = pl->NKT <= 8 ? (size_t)pl->NWB * std::min(pl->rp, 256) * 4 : 0;
-        // a THIRD tile buffer where it fits (r <= 128 at F = 513, C2's geometry): the loader waves then stage two tiles ahead
-        // and the consumers stop waiting for `ready` (k_wstats; SNMF_WSTATS_NBUF=2 keeps two)
-        const size_t tail = (size_t)pl->rp * 4 + 512 + gxs;  // extra row of W, progress slots + the extra row's V values, gxs
-        pl->nbw = pl->NLW ? 2 : 1;
-        if (pl->NLW && 3 * buf_ld + tail <= lds_cap) pl->nbw = 3;
-        if (const char* e = getenv("SNMF_WSTATS_NBUF")) if (pl->NLW && atoi(e) == 2) pl->nbw = 2;
-        pl->lds_w = std::max<size_t>(std::max<size_t>((pl->NLW ? pl->nbw * buf_ld : buf) + tail,
-                                                      (size_t)std::max(4, pl->NWB) * pl->rp * 4),
-                                     (size_t)(pl->NWB + pl->NLW) * 64 * sizeof(double));
-    }
-    // Fewer row tiles than consumer waves (F = 64, a Mel spectrogram: two): the consumer waves form teams that take the chunk's
-    // tiles in turn (StepArgs::til) instead of leaving half the SIMDs without an MFMA wave.  Needs the loader geometry (the
-    // teams' partial statistics meet in the tile buffers at the end), one row group, one kappa-group, no extra row.
-    pl->til = 1;
-    if (pl->NLW && pl->TTW == 32 && !pl->xr && pl->n_fg == 1 && pl->n_kg == 1 && pl->upd_w && pl->NKT == 4 && pl->bm == BM_KL) {
-        int til = 1;
-        while (til * 2 * pl->nf <= pl->NWB) til *= 2;
-        const size_t per_wave = (size_t)(pl->NKT * 16 + 8) * 64 * 4;
-        while (til > 1 && (size_t)(til - 1) * (pl->NWB / til) * per_wave > pl->lds_w) til /= 2;
-        if (const char* e = getenv("SNMF_WSTATS_TIL")) if (atoi(e) == 1) til = 1;
-        pl->til = til;
-    }
-    // ... and the KL statistics of the same shapes (r <= 128) through k_wstats_sf; follows SNMF_WSTATS_NL (tests compare against
-    // the synchronously staging kernels); SNMF_WSTATS_SF=0 keeps k_wstats_teams
-    {
-        const char* e = getenv("SNMF_WSTATS_NL");
-        const char* e2 = getenv("SNMF_WSTATS_SF");
-        const int ncl = 8 / std::max(1, pl->nf);
-        pl->lds_wsf = ((size_t)(ncl - 1) * pl->nf * pl->nk * 1024 + (size_t)ncl * pl->rp) * 4 + 8 * sizeof(double) + 64;
-        pl->wsf = pl->bm == BM_KL && pl->upd_w && !pl->xr && pl->nf <= 2 && pl->nk <= 4 && pl->TTW == 32 && pl->n_kg == 1 && pl->n_fg == 1 &&
-                  pl->NLW && !pl->generic && pl->lds_wsf <= lds_cap && !(e && atoi(e) == 0) && !(e2 && atoi(e2) == 0);
-        if (pl->wsf) pl->til = 1;
-        const char* e4 = getenv("SNMF_HSTEP_SPLIT");
-        pl->wsf_share = pl->wsf && pl->nf == 2 && pl->nk >= 2 && !(pl->upd_h && pl->nk >= 3) && !(e4 && atoi(e4) == 0);  // (not the shapes of k_iter_sf: see sf_share)
-    }
-    // ... and, for FULL updates of those shapes, both half-steps in one launch (k_iter_sf; the run loop only: the step API keeps
-    // the two launches, between which a multi-rank caller sums nothing but could).  SNMF_ITER_SF=0 keeps two launches.
-    {
-        const char* e = getenv("SNMF_ITER_SF");
-        const int ncl = 4;  // SIMD pairs (H wave + W wave) per workgroup = chunk lanes of k_wstats_sf at two row tiles
-        // (images, 1 ./ dph and lambda, ncl + 1 hand-off buffers, 16 progress words, the H waves' fp64 objective sums and the W waves' row sums per lane)
-        const size_t body = ((size_t)pl->nf * pl->rp * 32 + (size_t)pl->nk * pl->Fq * 32 + 2 * (size_t)pl->rp + (size_t)(ncl + 1) * 32 * (32 * pl->nk + 4) + 16) * 4 + (size_t)ncl * 64 * 2 * sizeof(double) + (size_t)ncl * 64 * 4 * 4;
-        const size_t tail = ((size_t)ncl * pl->nf * pl->nk * 1024 + (size_t)ncl * pl->rp) * 4 + 2 * ncl * sizeof(double);
-        pl->lds_isf = std::max(body, tail) + 64;
-        pl->isf = pl->sf && pl->wsf && pl->nf == 2 && pl->nk >= 3 && pl->upd_h && pl->upd_w && pl->lds_isf <= lds_cap && !(e && atoi(e) == 0);
-        const char* e4 = getenv("SNMF_HSTEP_SPLIT");
-        pl->isf_share = pl->isf && !(e4 && atoi(e4) == 0);
-    }
-    // Small rank on tall spectrograms (r <= 32 on 3..16 row tiles; the reference's R = 20 / 10 / 30 at F = 513): a tile per workgroup
-    // cut by ROW TILES over its eight waves, every operand straight into the MFMA layouts (snmf_smallr.h).  Follow SNMF_HSTEP_RP /
-    // SNMF_WSTATS_NL like the other fast paths (tests compare against the plain kernels); SNMF_HSTEP_SR=0 / SNMF_WSTATS_SR=0 keep the role pipelines.
-    {
-        const char* e = getenv("SNMF_HSTEP_SR");
-        const char* e2 = getenv("SNMF_WSTATS_SR");
-        const char* e3 = getenv("SNMF_WSTATS_NL");
-        const bool shape = pl->bm == BM_KL && pl->nf >= 3 && pl->nf <= 16 && pl->nk == 1 && !pl->generic && pl->TTW == 32 && pl->TTH == 32;
-        pl->lds_sr = sr_hstep_lds_bytes(pl->nk, pl->Fq, pl->rp);
-        pl->sr = shape && pl->upd_h && pl->hstep_rp && pl->lds_sr <= lds_cap && !(e && atoi(e) == 0);
-        pl->sr_grid = std::max(1, std::min((T + 31) / 32, ctx->n_cu));
-        if (const char* e4 = getenv("SNMF_SR_STAG")) pl->sr_stagger = atoi(e4);
-        pl->lds_wsr = sr_wstats_lds_bytes(pl->rp);
-        pl->wsr = shape && pl->upd_w && pl->NLW && !(e2 && atoi(e2) == 0) && !(e3 && atoi(e3) == 0);
-        if (pl->wsr) {  // one workgroup per frame chunk carries every row tile: no row groups
-            pl->n_fg = 1;
-            pl->n_kg = 1;
-            pl->til = 1;
-        }
-    }
-    const int wg_w = pl->NLW ? 1 : pl->WPS;  // workgroups per CU
-    pl->n_chunks = std::max(1, std::min(n_tiles_w, ctx->n_cu * wg_w / std::max(1, pl->n_fg * pl->n_kg)));
-    // Two row groups, only group 0 carries the extra row: deal the workgroups out so that both finish together.
-    // Relative cost x of the extra row per tile: ~2.1 k cycles at rp = 256 against 21 k for the two MFMA loops (phase
-    // stamps; a sweep of the split point on C2 had its optimum where this x puts it: 131..135 chunks for group 0,
-    // k_wstats 0.2573 -> 0.2481 ms, profiles/r02_experiments.md).
-    pl->n_ch1 = 0;
-    if (pl->xr && pl->n_fg >= 2 && pl->n_kg == 1 && pl->NLW && pl->upd_w && n_tiles_w >= 4 * pl->n_chunks) {
-        const int tot = pl->n_fg * pl->n_chunks, ng1 = pl->n_fg - 1;  // group 0: n0 workgroups, every other group n1
-        // (the row is shared by the group's NWB waves.  Round 4 re-measured it with phase stamps at 513 x 72000, r = 100 -- a group-0
-        //  tile takes 12 % longer per wave -- and swept x over 0.065 .. 0.22: the split this model picks (x = 0.065 there) is within
-        //  0.5 % of the best one, larger x loses 4 % to the tile-count quantisation; SNMF_WSTATS_X overrides it for such sweeps)
-        double x = (600.0 + 6.0 * pl->rp) / (82.0 * (pl->rp / 2 + 16 * pl->nk)) * 4.0 / pl->NWB;
-        if (const char* e = getenv("SNMF_WSTATS_X")) x = atof(e);  // (experiment: relative cost of the extra row per tile)
-        auto n1_of = [&](int n0) { return (tot - n0) / ng1; };
-        auto cost = [&](int n0) {
-            return std::max(std::ceil((double)n_tiles_w / n0) * (1.0 + x), std::ceil((double)n_tiles_w / n1_of(n0)));
-        };
-        int best = pl->n_chunks;
-        for (int n0 = pl->n_chunks + 1; n0 <= pl->n_chunks + pl->n_chunks / 4 && n1_of(n0) >= 1; ++n0)
-            if (cost(n0) < cost(best) - 1e-9) best = n0;
-        if (best != pl->n_chunks) {
-            pl->n_ch1 = n1_of(best);
-            pl->n_chunks = best;
-        }
-    }
-    // start-up stagger (cycles) of the second half of each grid: about half a tile period when two
-    // workgroups share a CU.
-    {
-        const int mf_h = (pl->nf + pl->NWH - 1) / pl->NWH * pl->NT * (pl->rp / 2) +
-                         (pl->nk + pl->NWH - 1) / pl->NWH * pl->NT * (pl->Fq / 2);
-        pl->stagger_h = (pl->grid_h > ctx->n_cu) ? mf_h * 64 : 0;
-        const int mf_w = pl->rp / 2 + 16 * pl->NKT;
-        pl->stagger_w = 0;
-        if (const char* e = getenv("SNMF_WSTAG")) pl->stagger_w = atoi(e);  // (experiment: intra-workgroup stagger of k_wstats' second consumer wave per SIMD, cycles)
-        (void)mf_w;
-    }
-    if (pl->lds_w > lds_cap && pl->upd_w) pl->generic = true;  // r too large for k_wstats' H image
-    if (pl->bm == BM_EUC && pl->NKT == 16 && pl->TTW == 32 && pl->upd_w) {
-        // Q = V * H^T of the Euclidean W step needs no Lam', so nothing is recomputed when the statistics' columns are cut
-        // into 256-wide kappa-groups: the NK = 16 geometry (256 accumulator registers, no room for loader waves, 116
-        // spilled VGPRs) is replaced for this launch by <8,4,4,2> with double-buffered LDS-DMA staging
-        pl->kq_kg = (pl->nk + 7) / 8;
-        pl->kq_chunks = std::max(1, std::min(std::min(n_tiles_w, pl->n_chunks), ctx->n_cu / std::max(1, pl->n_fg * pl->kq_kg)));
-        pl->kq_lds = (size_t)2 * 32 * (260 + 32 * 4) * 4 + (size_t)pl->rp * 4 + 512 + (size_t)4 * 256 * 4;
-    }
-    // Euclidean full updates: P through the Gram matrix (launch_gram_p) wherever it is the cheaper form (2 r^2 T against
-    // 4 F T r; W-only solves take their objective from the P launch's Lam' and keep it)
-    // SNMF_GRAM_P=0 opts out: P = max(W*H, flr)*H' is then formed from the Lam' pass exactly as src/sparse_nmf.m:228-233 writes
-    // it (the two forms differ only where W*H sits below the 1e-9 floor, by at most flr * sum(h) per entry: include/snmf.h)
-    const char* gp_env = getenv("SNMF_GRAM_P");
-    if (pl->bm == BM_EUC && pl->upd_w && pl->upd_h && pl->TTW == 32 && r < 2 * F && !(gp_env && atoi(gp_env) == 0)) {
-        pl->gram_p = true;
-        const int nfg_g = (pl->rp / 32 + pl->NWB - 1) / pl->NWB;
-        pl->gram_chunks = pl->kq_kg ? pl->kq_chunks
-                                    : std::max(1, std::min(n_tiles_w, ctx->n_cu * (pl->NLW ? 1 : pl->WPS) / std::max(1, nfg_g)));
-    }
-    // k_wstats keeps the row sums of H (KL) and the extra row of the slab (F = 32n+1) in per-thread registers: 1024 columns
-    if (pl->rp > 4 * pl->NWB * 64 && pl->upd_w && (pl->bm == BM_KL || pl->xr)) pl->generic = true;
-
-    pl->lds_wfin = (size_t)9 * pl->n_mat * pl->Fp * sizeof(double);
-    pl->wfin = pl->upd_w && pl->lds_wfin + 12 * 1024 <= lds_cap;
-    // very few columns (r <= 32: the reference's R = 20 / 10 / 30): cut every column's rows into slices, a workgroup each (k_wfin,
-    // gridDim.y): r * S workgroups of at least eight 16-byte cells each.  Measured (513 x 72000): r = 10 W-only 13 824 -> 14 474 it/s,
-    // r = 20 7 615 -> 7 744; from r = 100 up the gather costs what the wider read saves (a11 17.3 -> 17.4 us, Mel 11.3 -> 12.5), so
-    // those keep one workgroup per column.  SNMF_WFIN_SPLIT=0: never split.
-    {
-        const char* e = getenv("SNMF_WFIN_SPLIT");
-        int S = r <= 32 ? std::max(1, std::min(8, ctx->n_cu / std::max(1, r))) : 1;
-        while (S > 1 && (pl->Fp / 4 + S - 1) / S < 8) --S;
-        pl->wfin_S = (pl->wfin && !(e && atoi(e) == 0)) ? S : 1;
-    }
-
-    // persistent single-launch path for the online shape (H-only, at most one 32-frame tile)
-    {
-        const size_t need = ((size_t)32 * (pl->ldh + pl->ldr) + ((pl->rp + 3) & ~3)) * 4 + 2 * 512 * sizeof(double);
-        pl->small_ok = pl->upd_h && !pl->upd_w && need <= lds_cap;   // shape admits the persistent kernel
-        // SNMF_NO_SMALL (tests): 1 = no persistent kernel at all (the plan loop), 2 = no register-resident frame kernel
-        const char* ns = getenv("SNMF_NO_SMALL");
-        const int no_small = ns ? atoi(ns) : 0;
-        pl->small = pl->small_ok && T <= 32 && no_small != 1;
-        pl->lds_small = need;
-        // one frame per solve: register-resident dictionary (k_hsolve_frame), F <= 64*FB + 1, r <= 8*KB
-        if (pl->small_ok && no_small == 0) {
-            static const int fbs[2] = {4, 8}, kbs[2] = {16, 25};
-            for (int fi = 0; fi < 2 && !pl->frame_fb; ++fi)
-                for (int ki = 0; ki < 2 && !pl->frame_fb; ++ki)
-                    if (F <= 64 * fbs[fi] + 1 && r <= 8 * kbs[ki]) {
-                        pl->frame_fb = fbs[fi];
-                        pl->frame_kb = kbs[ki];
-                    }
-            if (pl->frame_fb) {
-                const int Fm2 = 64 * pl->frame_fb, RB = 8 * pl->frame_kb, nv = pl->bm == BM_KL ? 1 : 2;
-                pl->lds_frame = (size_t)(40 + 4 * RB + 3 * (Fm2 + 4) + 8 * Fm2 + nv * 16 * (RB + 1)) * 4;
-                if (pl->lds_frame > lds_cap) pl->frame_fb = pl->frame_kb = 0;
-            }
-        }
-    }
-    if (pl->generic) {
-        // none of the fused geometries applies; contractions over the frames are split into chunks of kGChunkT frames,
-        // whose slabs k_reduce adds like the fast path's
-        pl->hstep_rp = pl->rh = false;
-        pl->rh_lxh = 0;
-        pl->rp_S = 0;
-        pl->kq_kg = 0;
-        pl->gram_p = false;
-        pl->n_ch1 = 0;
-        pl->small_ok = pl->small = false;
-        pl->frame_fb = pl->frame_kb = 0;
-        pl->wfin = false;
-        pl->n_fg = pl->n_kg = 1;
-        pl->n_chunks = (T + kGChunkT - 1) / kGChunkT;
-        pl->grid_h = pl->grid_mdi = kGBlocks;
-    }
+    for (int k = 0; k < r; ++k) pl->h_w_ind[k] = p->w_update_ind ? p->w_update_ind[k] != 0 : 1;
     // allocations
     const size_t nV = (size_t)pl->Fp * pl->Tp, nH = (size_t)pl->rp * pl->Tp, nW = (size_t)pl->Fp * pl->rp;
     const size_t nWt = (size_t)pl->Fm * pl->rp, nWk = (size_t)pl->Fq * pl->rp;
@@ -621,10 +248,6 @@ extern "C" int snmf_plan_create(snmf_ctx* ctx, const snmf_params* p, snmf_plan**
     A(palloc(&pl->colsum, (size_t)pl->rp));
     A(palloc(&pl->lamk, (size_t)pl->rp));
     if (p->sparsity_kind == SNMF_SPARSITY_FULL) A(palloc(&pl->S, nH));
-    {
-        const char* e = getenv("SNMF_HFOLD");
-        pl->fold_obj = pl->upd_h && !pl->upd_w && !pl->generic && !(e && atoi(e) == 0);
-    }
     if (pl->upd_w) {
         A(palloc(&pl->slabs, (size_t)pl->n_chunks * pl->n_mat * nW));
         A(palloc(&pl->spart, (size_t)pl->n_chunks * pl->rp));
@@ -711,40 +334,7 @@ extern "C" int64_t snmf_plan_stats_len(const snmf_plan* pl) {
 
 extern "C" int snmf_plan_describe(const snmf_plan* pl, char* buf, size_t n) {
     if (!pl || !buf) return fail(SNMF_ERR_INVALID, "NULL argument");
-    const bool kl_pipe = pl->NWH == 8 && pl->NLH == 4 && pl->bm == BM_KL && pl->upd_h && !pl->M && pl->hstep_rp;
-    char hs[256];
-    const bool rh_pipe = pl->rh && pl->upd_h && !pl->M;
-    const bool sf_pipe = pl->sf && !pl->M;
-    const bool sr_pipe = pl->sr && !pl->M;
-    if (sr_pipe)
-        snprintf(hs, sizeof hs, "k_hstep_sr (a tile per workgroup cut by row tiles over 8 waves, operands straight into the MFMA layouts, partial numerators meet in LDS; %d tiles, grid %d)", pl->rp_tiles, pl->sr_grid);
-    else if (sf_pipe && pl->isf && pl->wfin)
-        snprintf(hs, sizeof hs, "k_iter_sf (H step + W statistics of a full update in ONE launch, 4 SIMD pairs of an H wave and a W wave per workgroup%s; %d tiles, grid %d; step API: k_hstep_sf)", pl->isf_share ? ", a chunk's single remainder tile shared by the four pairs" : "", pl->rp_tiles, pl->n_chunks);
-    else if (sf_pipe)
-        snprintf(hs, sizeof hs, "k_hstep_sf (a tile per wave from first load to last store, 8 waves per workgroup; %d tiles, the last %d shared by four waves each, grid %d)", pl->rp_tiles, pl->sf_share, pl->sf_grid);
-    else if (rh_pipe)
-        snprintf(hs, sizeof hs, "k_hstep_rh (4 P1 + 4 P2 + 4 loader waves on half tiles%s; %d of %d tiles pipelined, last round split %d ways, grid %d)",
-                 pl->rh_lxh == 1 ? ", P2 cut four ways over the contraction + leftover columns as 4x4x1 MFMAs" : (pl->rh_lxh == 2 ? ", P2 in wave pairs cut over the contraction + leftover columns as 4x4x1 MFMAs" : ""), pl->rp_full, pl->rp_tiles, pl->rp_S, pl->rp_grid);
-    else if (kl_pipe && pl->hm && !pl->S)
-        snprintf(hs, sizeof hs, "k_hstep_m (merged roles: 4 waves, one per SIMD, each P1 + P2 of its own row / column tiles; %d tiles whole, grid %d)",
-                 pl->rp_tiles, pl->hm_grid);
-    else if (kl_pipe)
-        snprintf(hs, sizeof hs, "k_hstep_rp (4 P1 + 4 P2 + 4 loader waves%s; %d of %d tiles pipelined, last round split %d ways, grid %d)",
-                 pl->rp_cut == 2 ? ", P2 in wave pairs cut over the contraction" : pl->rp_cut ? ", P2 cut four ways over the contraction" : "", pl->rp_full, pl->rp_tiles, pl->rp_S, pl->rp_grid);
-    else
-        snprintf(hs, sizeof hs, "k_hstep");
-    if (pl->generic) {
-        snprintf(buf, n, "F=%d T=%d r=%d beta=%g | out-of-envelope path (intermediates in HBM: k_g_gemm / k_g_ratio / k_g_hupd, %d frame splits) | n_cu=%d",
-                 pl->p.F, pl->p.T, pl->p.r, pl->p.beta, pl->n_chunks, pl->ctx->n_cu);
-        return SNMF_OK;
-    }
-    snprintf(buf, n,
-             "F=%d T=%d r=%d beta=%g | Fm=%d(+%d VALU row) rp=%d Tp=%d | hstep: %s, tile=%d frames, grid=%d x %d thr, lds=%zu B | "
-             "wstats: NK=%d waves=%d+%d grid=(%d chunks,%d fgroups,%d kgroups; group-1 chunks %d) lds=%zu B%s | W finish (run loop): %s | n_cu=%d",
-             pl->p.F, pl->p.T, pl->p.r, pl->p.beta, pl->Fm, pl->xr, pl->rp, pl->Tp, hs, pl->TTH * pl->NT,
-             sr_pipe ? pl->sr_grid : sf_pipe ? pl->sf_grid : ((kl_pipe || rh_pipe) ? pl->rp_grid : pl->grid_h), (sr_pipe || sf_pipe) ? 512 : (rh_pipe ? 768 : (pl->NWH + pl->NLH) * 64),
-             sr_pipe ? pl->lds_sr : sf_pipe ? pl->lds_sf : (rh_pipe ? pl->lds_rh : pl->lds_h), pl->NKT, pl->NWB, pl->NLW, pl->n_chunks, pl->n_fg, pl->n_kg, pl->n_ch1 ? pl->n_ch1 : pl->n_chunks, pl->lds_w,
-             pl->gram_p ? ", P = W*(H*H') through the Gram matrix" : (pl->wsr ? ", k_wstats_sr: statistics rows per wave, operands straight into the MFMA layouts" : pl->wsf ? (pl->wsf_share ? ", k_wstats_sf: a tile per wave, a single remainder tile shared by the eight waves" : ", k_wstats_sf: a tile per wave") : (pl->til > 1 ? (pl->til == 2 ? ", 2 consumer teams take the tiles in turn" : ", 4+ consumer teams take the tiles in turn") : "")), pl->wfin ? "k_wfin" : (pl->upd_w ? "k_reduce + k_wapply" : (pl->fold_obj && !pl->M ? "none (objective fold + convergence test on the H step's last workgroup)" : "none (objective fold + convergence test: k_reduce)")), pl->ctx->n_cu);
+    describe_geometry(*pl, pl->p, pl->ctx->n_cu, pl->M != nullptr, buf, n);
     return SNMF_OK;
 }
 
@@ -1189,15 +779,16 @@ static int wstats_parts(const snmf_plan* pl) {
     if (pl->generic) return kGBlocks;
     return pl->n_ch1 ? pl->n_chunks + (pl->n_fg - 1) * pl->n_ch1 : pl->n_chunks * pl->n_fg;
 }
-static bool hupd_is_rp(const snmf_plan* pl) {
-    return !pl->M && (pl->rh || (pl->NWH == 8 && pl->NLH == 4 && pl->hstep_rp && pl->bm == BM_KL));
-}
 static int hupd_parts(const snmf_plan* pl) {
     if (pl->generic) return kGBlocks;
     if (pl->M) return pl->grid_mdi;
-    if (pl->sr) return pl->sr_grid;
-    if (pl->sf) return pl->sf_grid;
-    if (hupd_is_rp(pl)) return (pl->hm && !pl->rh && !pl->S) ? pl->hm_grid : pl->rp_grid;
+    switch (pl->hupd) {
+    case HUPD_SR: return pl->sr_grid;
+    case HUPD_SF: return pl->sf_grid;
+    case HUPD_RH:
+    case HUPD_RP: return pl->rp_grid;
+    case HUPD_PLAIN: break;
+    }
     return pl->grid_h;
 }
 
@@ -1367,7 +958,7 @@ extern "C" int snmf_plan_run(snmf_plan* pl, int32_t n_iters, int32_t* iters_done
     int since_poll = 0;
     bool stopped = false;
     while (pl->it_done < target) {
-        if (pl->isf && pl->wfin && !pl->M && pl->n_chunks == std::max(1, std::min((pl->p.T + 31) / 32, pl->ctx->n_cu))) {
+        if (pl->isf && !pl->M) {
             // F <= 64, r <= 128, full KL update: H step + W statistics in ONE launch (k_iter_sf), then the reduction + W update
             const int j = pl->it_done + 1;
             const bool obj = want_obj(pl, j);

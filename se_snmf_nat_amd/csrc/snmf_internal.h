@@ -1,7 +1,7 @@
 // snmf_internal.h -- what the translation units of libsnmf_hip.so share on the HOST side: error plumbing, the context
 // and plan structures, and the prototypes of the launch dispatchers.  The library is built from several .hip files
 // compiled in parallel (se_snmf_nat_amd/_lib.py): snmf_api.hip (context, plans, data movement, the iteration loop, the
-// front-end), snmf_tu_hstep*.hip / snmf_tu_wstats*.hip / snmf_tu_small.hip (the template instantiations of the three big
+// front-end), snmf_tu_geometry.hip (the kernels and launch geometry of a plan), snmf_tu_hstep*.hip / snmf_tu_wstats*.hip / snmf_tu_small.hip (the template instantiations of the three big
 // kernel families and their dispatch), snmf_tu_online.hip, snmf_tu_multi.hip, snmf_tu_dnmf.hip.  Nothing here is part of
 // the C ABI (include/snmf.h).
 #pragma once
@@ -97,92 +97,107 @@ struct ScopedTimer {
     }
 };
 
-// ---- plan --------------------------------------------------------------------------------------
-struct snmf_plan {
-    snmf_ctx* ctx = nullptr;
-    snmf_params p{};
-    // geometry
+// ---- plan geometry -----------------------------------------------------------------------------
+// Which kernels a plan launches and on what geometry: a pure function of snmf_params, the device's compute-unit count and
+// the plan-creation switches (plan_geometry in snmf_tu_geometry.hip; no device is touched, so snmf_plan_geometry_describe
+// answers without one).
+enum HUpd { HUPD_PLAIN = 0, HUPD_RP, HUPD_RH, HUPD_SF, HUPD_SR };  // kernel of the non-MDI H-update launches
+struct PlanGeometry {
+    int bm = BM_KL;
+    int n_mat = 1;
+    bool upd_h = true, upd_w = true;
     int Fp = 0, rp = 0, Tp = 0, nf = 0, nk = 0;
     int Fm = 0, Fq = 0, xr = 0;
+    int ldh = 0, ldr = 0, ldhw = 0;
     int NT = 1, NWH = 8, NLH = 0;  // k_hstep: frame tile = 32*NT, NWH consumer + NLH loader waves
     int TTH = 32, TTW = 32;        // frames per tile of k_hstep (NT == 1) / k_wstats; 16 = narrow tiles (images too big for 32 frames)
+    int grid_h = 1;
+    int stagger_h = 0;
+    size_t lds_h = 0;
+    HUpd hupd = HUPD_PLAIN;        // H-update launches without a mask: k_hstep_sr / _sf / _rh / _rp, or the k_hstep of the geometry above
     bool hstep_rp = true;          // KL update launches of the (8, 1, 4) geometry use the role pipeline k_hstep_rp (SNMF_HSTEP_RP=0: k_hstep)
     // k_hstep_rp launch geometry: tiles [0, rp_full) through the pipeline on rp_grid workgroups, the tiles of the last
     // partial round [rp_full, rp_tiles) cut into rp_S row parts, one workgroup each (rp_S = 0: no split)
     int rp_tiles = 0, rp_full = 0, rp_S = 0, rp_grid = 1;
-    int rp_cut = 0;                // k_hstep_rp<., CUT>: r <= 64, P2 cut over the contraction -- 1: four ways, every column tile; 2: wave pairs, a tile each (SNMF_RP_CUT=0: the column-tile deal)
-    bool hm = false;               // KL update launches run k_hstep_m (merged roles, one wave per SIMD: snmf_hstep_m.h); SNMF_HSTEP_M=0/1
-    int hm_grid = 1;
+    int rp_cut = 0;                // k_hstep_rp<., CUT>: r <= 64, P2 cut over the contraction -- 1: four ways, every column tile; 2: wave pairs, a tile each
     bool rh = false;               // KL update launches run k_hstep_rh (9..16 row tiles, e.g. F = 513: one ratio image, pipelined by half tiles)
     size_t lds_rh = 0;
-    float* part_buf = nullptr;     // partial numerators of the split tiles [rp_grid][32][rp]
-    unsigned* part_cnt = nullptr;  // arrivals per split tile (monotonic)
+    int rh_lxh = 0;  // k_hstep_rh: P2 cut over the contraction (1: r = 97..100 four ways; 2: r = 193..200 in pairs), leftover columns as 4x4x1 MFMAs
     int NKT = 8, NWB = 4, WPS = 2, NLW = 0;  // k_wstats template geometry (NLW loader waves)
     int nbw = 2;                             // k_wstats tile buffers in LDS with loader waves (3 where they fit)
     int n_fg = 1, n_kg = 1, n_chunks = 1;
+    static constexpr int stagger_w = 0;   // k_wstats: start-up stagger of the second consumer wave per SIMD (cycles)
     bool sf = false;      // KL H-update launches through k_hstep_sf (F <= 64, r <= 128: snmf_smallf.h)
     int sf_grid = 1;
     bool wsf = false;     // KL statistics through k_wstats_sf (F <= 64, r <= 128)
     size_t lds_wsf = 0;
     bool isf_share = false;  // k_iter_sf: a chunk's single remainder tile is shared by the four pairs (SNMF_HSTEP_SPLIT=0: whole)
     bool wsf_share = false;  // k_wstats_sf / k_iter_sf: a workgroup's single remainder tile is shared by its waves (SNMF_HSTEP_SPLIT=0: whole)
-    bool isf = false;     // full KL updates of those shapes: H step + W statistics in ONE launch (k_iter_sf); SNMF_ITER_SF=0 keeps two
+    bool isf = false;     // full KL updates of those shapes in snmf_plan_run: H step + W statistics in ONE launch (k_iter_sf); SNMF_ITER_SF=0 keeps two
     size_t lds_isf = 0;
-    int sf_stagger = 0;   // cycles by which the second wave of each SIMD starts late (k_hstep_sf)
+    static constexpr int sf_stagger = 8000;  // cycles by which the second wave of each SIMD starts late (k_hstep_sf)
     size_t lds_sf = 0;
     // k_hstep_sf: the tiles [sf_nfull, rp_tiles) -- one per workgroup, the partial wave level behind the whole ones -- are shared by the
     // four waves of that level (snmf_smallf.h, "the shared last tile"); 0 = every tile whole
     int sf_share = 0, sf_nfull = 0;
     // small rank on tall spectrograms (r <= 64, 3..16 row tiles: snmf_smallr.h): a tile per WORKGROUP cut by row tiles, operands straight
-    // into the MFMA layouts; KL H-update launches through k_hstep_sr, KL statistics through k_wstats_sr (SNMF_HSTEP_SR / SNMF_WSTATS_SR = 0: the role pipelines)
+    // into the MFMA layouts; KL H-update launches through k_hstep_sr, KL statistics through k_wstats_sr
     bool sr = false, wsr = false;
     int sr_grid = 1;
-    int sr_stagger = 1300;  // cycles by which the second wave of each SIMD starts late (k_hstep_sr / k_wstats_sr; SNMF_SR_STAG)
+    static constexpr int sr_stagger = 1300;  // cycles by which the second wave of each SIMD starts late (k_hstep_sr / k_wstats_sr)
     size_t lds_sr = 0, lds_wsr = 0;
     int til = 1;  // k_wstats: consumer teams that share a chunk's tiles (StepArgs::til)
     int n_ch1 = 0;  // k_wstats: chunks of row group 1 when the two row groups are split unevenly (else 0)
     // beta = 2, r > 256: the V*H^T launch (needs no Lam') runs the loader-wave geometry <8,4,4,2> once per 256-column
     // kappa-group, each staging only its own columns of H (kq_chunks frame chunks, kq_kg kappa-groups; 0 = off)
     int kq_chunks = 0, kq_kg = 0;
+    size_t kq_lds = 0;
+    size_t lds_w = 0;
     // snmf_plan_run: k_reduce + k_wapply as one launch (k_wfin) when a column's chunk-group sums fit the LDS
-    int rh_lxh = 0;  // k_hstep_rh: P2 cut over the contraction (1: r = 97..100 four ways; 2: r = 193..200 in pairs), leftover columns as 4x4x1 MFMAs
     bool wfin = false;
     int wfin_S = 1;             // k_wfin: row slices per column (few columns: r <= 128), gathered by the column's last arriver
-    double* qp_buf = nullptr;   // [r][n_mat * Fp]
-    unsigned* fin_cnt = nullptr;  // [r] arrivals per column (monotonic)
     size_t lds_wfin = 0;
     // H-only loop of snmf_plan_run: the objective fold + convergence test ride on the H step (obj_partial_out in snmf_kernels.h:
     // the last workgroup to arrive folds) instead of a k_reduce launch per iteration.  SNMF_HFOLD=0 keeps the launch.
     bool fold_obj = false;
-    FoldBlock fold_host{};         // what the FoldBlock behind *st holds (the source of the copy at plan creation)
-    int fold_now = 0;              // > 0 while snmf_plan_run issues the H step that carries the test of that iteration
-    // shapes beyond the fused kernels' LDS / register envelope: the same iteration with its intermediates in HBM
-    // (csrc/snmf_generic.h); Lam / ratio / denominator images [Tp][Fp], numerator / denominator of the H update [Tp][rp]
     // Euclidean W step, r > 256, full updates: P = max(W*H, flr) * H' is formed as W * (H*H') -- the r x r Gram matrix
     // costs 2 r^2 T flop instead of the P launch's 4 F T r (C5: 4.75 -> ~2.5 ms); see launch_gram_p
     bool gram_p = false;
     int gram_chunks = 0;
-    float *gram_slabs = nullptr, *gram32 = nullptr;
+    // shapes beyond the fused kernels' LDS / register envelope: the same iteration with its intermediates in HBM
+    // (csrc/snmf_generic.h); Lam / ratio / denominator images [Tp][Fp], numerator / denominator of the H update [Tp][rp]
     bool generic = false;
+    int frame_fb = 0, frame_kb = 0;  // register-block geometry of k_hsolve_frame (0: shape not admitted)
+    size_t lds_frame = 0;
+    size_t lds_mdi = 0;  // MDI pass: (NW=8, NT=1, NL=0)
+    int grid_mdi = 1;
+    bool small = false;       // T <= 32 H-only solve: one persistent single-workgroup launch
+    bool small_ok = false;
+    size_t lds_small = 0;
+};
+// Validates p as snmf_plan_create does and fills g; reads the plan-creation switches (SNMF_HSTEP_RP, ...) on every call.
+int plan_geometry(const snmf_params* p, int n_cu, PlanGeometry* g);
+// The text of snmf_plan_describe (mdi: a plan with an observed/missing mask).
+void describe_geometry(const PlanGeometry& g, const snmf_params& p, int n_cu, bool mdi, char* buf, size_t n);
+
+// ---- plan --------------------------------------------------------------------------------------
+struct snmf_plan : PlanGeometry {
+    snmf_ctx* ctx = nullptr;
+    snmf_params p{};
+    float* part_buf = nullptr;     // partial numerators of the split tiles [rp_grid][32][rp]
+    unsigned* part_cnt = nullptr;  // arrivals per split tile (monotonic)
+    double* qp_buf = nullptr;      // [r][n_mat * Fp]
+    unsigned* fin_cnt = nullptr;   // [r] arrivals per column (monotonic)
+    FoldBlock fold_host{};         // what the FoldBlock behind *st holds (the source of the copy at plan creation)
+    int fold_now = 0;              // > 0 while snmf_plan_run issues the H step that carries the test of that iteration
+    float *gram_slabs = nullptr, *gram32 = nullptr;
     float *gLam = nullptr, *gR = nullptr, *gD = nullptr, *gNum = nullptr, *gDen = nullptr;
-    size_t kq_lds = 0;
-    int grid_h = 1;
-    int ldh = 0, ldr = 0, ldhw = 0;
-    int stagger_h = 0, stagger_w = 0;
-    size_t lds_h = 0, lds_w = 0;
-    int bm = BM_KL;
-    int n_mat = 1;
-    bool upd_h = true, upd_w = true;
     // device buffers
     float *V = nullptr, *H[2] = {nullptr, nullptr}, *Wt4 = nullptr, *Wk4 = nullptr;
     double* Wc = nullptr;  // fp64 master copy of W (see k_wapply)
     float* Wcf = nullptr;  // fp32 rounding of Wc, column-major [rp][Fp] (k_hsolve_frame)
-    int frame_fb = 0, frame_kb = 0;  // register-block geometry of k_hsolve_frame (0: shape not admitted)
     float* M = nullptr;    // MDI: observed/missing mask in V's layout (src/snmf_mdi.m); non-null = MDI solve
     bool mdi_v_fresh = false, mdi_final = false;
-    size_t lds_mdi = 0;
-    int grid_mdi = 1;
-    size_t lds_frame = 0;
     float *dphv = nullptr, *colsum = nullptr, *lamk = nullptr, *S = nullptr, *wx = nullptr;
     float *slabs = nullptr, *spart = nullptr;
     double *part = nullptr, *stats = nullptr, *divh = nullptr, *costh = nullptr, *wn = nullptr;
@@ -209,9 +224,6 @@ struct snmf_plan {
     // state
     bool have_v = false, have_w = false, have_h = false, have_s = false, inited = false;
     bool w_dirty = true;      // W changed since its last normalisation (online: W stays, only V/H change)
-    bool small = false;       // T <= 32 H-only solve: one persistent single-workgroup launch
-    bool small_ok = false;
-    size_t lds_small = 0;
     bool small_done = false;
     int cur = 0;          // H[cur] holds the current iterate
     int it_done = 0;      // update iterations launched
@@ -278,7 +290,6 @@ int xfer_sync(snmf_ctx* c);
 int launch_hstep(snmf_plan* pl, bool obj, bool upd);
 int launch_hstep_rp(snmf_plan* pl, StepArgs a, bool obj);  // snmf_tu_hstep_rp.hip
 int launch_hstep_rh(snmf_plan* pl, StepArgs a, bool obj);  // snmf_tu_hstep_rh.hip
-int launch_hstep_m(snmf_plan* pl, StepArgs a, bool obj);   // snmf_tu_hstep_m.hip
 int launch_hstep_sf(snmf_plan* pl, StepArgs a, bool obj);  // snmf_tu_smallf.hip
 int launch_wstats_sf(snmf_plan* pl, const StepArgs& a, bool obj);  // snmf_tu_smallf.hip
 int launch_hstep_sr(snmf_plan* pl, StepArgs a, bool obj);            // snmf_tu_smallr.hip

@@ -47,16 +47,14 @@ int launch_hstep(snmf_plan* pl, bool obj, bool upd) {
         if (pl->bm == BM_EUC) return launch_hstep_mdi_b<BM_EUC>(pl, a, obj, upd);
         return launch_hstep_mdi_b<BM_GEN>(pl, a, obj, upd);
     }
-    if (pl->sr && upd) return launch_hstep_sr(pl, a, obj);  // KL update launches, r <= 64 on 3..16 row tiles: a tile per workgroup cut by row tiles (snmf_tu_smallr.hip)
-    if (pl->sf && upd) return launch_hstep_sf(pl, a, obj);  // KL update launches, F <= 64: a tile per wave (snmf_tu_smallf.hip)
-    if (pl->rh && upd) return launch_hstep_rh(pl, a, obj);  // KL update launches of the 9..16-row-tile geometry (snmf_tu_hstep_rh.hip)
-    if (pl->NWH == 8 && pl->NLH == 4) {
-#ifdef SNMF_EXPERIMENTS
-        if (pl->hm && pl->bm == BM_KL && upd && !a.S) return launch_hstep_m(pl, a, obj);  // merged roles, one wave per SIMD (experiments/snmf_tu_hstep_m.hip)
-#endif
-        if (pl->hstep_rp && pl->bm == BM_KL && upd) return launch_hstep_rp(pl, a, obj);  // KL update launches: the role pipeline (snmf_tu_hstep_rp.hip)
-        return launch_hstep_g<8, 1, 4>(pl, a, obj, upd);
-    }
+    if (upd) switch (pl->hupd) {  // (KL update launches of the fast paths; PLAIN: the k_hstep of the geometry below)
+        case HUPD_SR: return launch_hstep_sr(pl, a, obj);  // r <= 64 on 3..16 row tiles: a tile per workgroup cut by row tiles (snmf_tu_smallr.hip)
+        case HUPD_SF: return launch_hstep_sf(pl, a, obj);  // F <= 64: a tile per wave (snmf_tu_smallf.hip)
+        case HUPD_RH: return launch_hstep_rh(pl, a, obj);  // the 9..16-row-tile geometry (snmf_tu_hstep_rh.hip)
+        case HUPD_RP: return launch_hstep_rp(pl, a, obj);  // the role pipeline (snmf_tu_hstep_rp.hip)
+        case HUPD_PLAIN: break;
+        }
+    if (pl->NWH == 8 && pl->NLH == 4) return launch_hstep_g<8, 1, 4>(pl, a, obj, upd);
     if (pl->NWH == 4) return pl->NT == 2 ? launch_hstep_g<4, 2, 0>(pl, a, obj, upd) : launch_hstep_g<4, 1, 0>(pl, a, obj, upd);
     if (pl->TTH == 16) return launch_hstep_g<8, 1, 0, 16>(pl, a, obj, upd);
     return pl->NT == 2 ? launch_hstep_g<8, 2, 0>(pl, a, obj, upd) : launch_hstep_g<8, 1, 0>(pl, a, obj, upd);
