@@ -539,8 +539,9 @@ class Plan:
         _lib.check(self._lib.snmf_plan_set_h_random(self._h, int(seed)))
 
     def set_mask(self, m):
-        """Observed (1) / missing (0) mask, binary or soft: turns the plan into an MDI solve (src/snmf_mdi.m)."""
-        self._set("mask", np.asarray(m, dtype=np.float64) if not hasattr(m, "data_ptr") else m, self.F)
+        """Observed (1) / missing (0) mask, binary or soft: turns the plan into an MDI solve (src/snmf_mdi.m).  A float32 array
+        goes through snmf_plan_set_mask_f32, anything else (bool included) through the f64 entry."""
+        self._set("mask", m, self.F)
 
     def get_v_mdi(self, dtype=np.float64):
         """v_MDI of src/snmf_mdi.m:296-306."""

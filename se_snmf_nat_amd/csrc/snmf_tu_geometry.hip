@@ -408,12 +408,16 @@ void describe_geometry(const PlanGeometry& g, const snmf_params& p, int n_cu, bo
                  g.rp_cut == 2 ? ", P2 in wave pairs cut over the contraction" : g.rp_cut ? ", P2 cut four ways over the contraction" : "", g.rp_full, g.rp_tiles, g.rp_S, g.rp_grid);
         break;
     case HUPD_PLAIN:
-        snprintf(hs, sizeof hs, "k_hstep");
+        if (mdi)  // (launch_hstep_mdi_b: k_hstep<8, 1, 0, ., ., ., MDI = true> on every 32-frame tile of Tp, pad tiles included)
+            snprintf(hs, sizeof hs, "k_hstep (MDI pass: 8 waves on 32-frame tiles, synchronous staging, V re-imputed in place; %d tiles)", g.Tp / 32);
+        else
+            snprintf(hs, sizeof hs, "k_hstep");
         break;
     }
-    const int grid = h == HUPD_SR ? g.sr_grid : h == HUPD_SF ? g.sf_grid : (h == HUPD_RH || h == HUPD_RP) ? g.rp_grid : g.grid_h;
-    const int threads = (h == HUPD_SR || h == HUPD_SF) ? 512 : h == HUPD_RH ? 768 : (g.NWH + g.NLH) * 64;
-    const size_t lds = h == HUPD_SR ? g.lds_sr : h == HUPD_SF ? g.lds_sf : h == HUPD_RH ? g.lds_rh : g.lds_h;
+    // (a masked plan launches its own pass: grid_mdi workgroups of 512 threads with lds_mdi, whatever the geometry's k_hstep is)
+    const int grid = mdi ? g.grid_mdi : h == HUPD_SR ? g.sr_grid : h == HUPD_SF ? g.sf_grid : (h == HUPD_RH || h == HUPD_RP) ? g.rp_grid : g.grid_h;
+    const int threads = (mdi || h == HUPD_SR || h == HUPD_SF) ? 512 : h == HUPD_RH ? 768 : (g.NWH + g.NLH) * 64;
+    const size_t lds = mdi ? g.lds_mdi : h == HUPD_SR ? g.lds_sr : h == HUPD_SF ? g.lds_sf : h == HUPD_RH ? g.lds_rh : g.lds_h;
     const char* wkind = g.gram_p ? ", P = W*(H*H') through the Gram matrix"
                         : g.wsr  ? ", k_wstats_sr: statistics rows per wave, operands straight into the MFMA layouts"
                         : g.wsf  ? (g.wsf_share ? ", k_wstats_sf: a tile per wave, a single remainder tile shared by the eight waves" : ", k_wstats_sf: a tile per wave")
@@ -426,7 +430,7 @@ void describe_geometry(const PlanGeometry& g, const snmf_params& p, int n_cu, bo
     snprintf(buf, n,
              "F=%d T=%d r=%d beta=%g | Fm=%d(+%d VALU row) rp=%d Tp=%d | hstep: %s, tile=%d frames, grid=%d x %d thr, lds=%zu B | "
              "wstats: NK=%d waves=%d+%d grid=(%d chunks,%d fgroups,%d kgroups; group-1 chunks %d) lds=%zu B%s | W finish (run loop): %s | n_cu=%d",
-             p.F, p.T, p.r, p.beta, g.Fm, g.xr, g.rp, g.Tp, hs, g.TTH * g.NT, grid, threads, lds, g.NKT, g.NWB, g.NLW, g.n_chunks, g.n_fg,
+             p.F, p.T, p.r, p.beta, g.Fm, g.xr, g.rp, g.Tp, hs, mdi ? 32 : g.TTH * g.NT, grid, threads, lds, g.NKT, g.NWB, g.NLW, g.n_chunks, g.n_fg,
              g.n_kg, g.n_ch1 ? g.n_ch1 : g.n_chunks, g.lds_w, wkind, wfinish, n_cu);
 }
 

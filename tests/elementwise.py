@@ -42,6 +42,11 @@ multiplies a relative error of x by |p|.  V is the fp32 image the device holds (
 
   The bound needs every reference entry > 0 and every floor of :193 / :207 / :218 / :243 (on Lam, dph, dpw) at least 10x away
   from binding: compare() fails otherwise (the 1e-9 floor that :169 applies to V on upload is part of the input).
+
+  WITH A MASK (src/snmf_mdi.m; tests/mdi_elementwise.py derives it) V is no exact input any more: the solve re-imputes it every
+  iteration from its fp32 Lam, so after k imputations the device's V is within dV_k = (r + 2) u + 3 k u of the V the test tracks in
+  fp64 (0 where M = 1).  The numerators of the H step and the statistics G, Q of the W step are linear in V, so the bounds become
+  tau_H + dV_{k-1} and tau_W + 4 dV_{k-1}; ref_hstep / ref_wstep / cost_of take that tracked V as it is with exact_v=True.
 """
 from __future__ import annotations
 
@@ -64,16 +69,20 @@ def _sparsity_matrix(S, r, T):
     return sp
 
 
-def _floored_v(V32):
-    return np.fmax(np.asarray(V32, dtype=np.float32).astype(np.float64), FLR)  # the fp32 image, :169 on upload
+def _floored_v(V32, exact_v=False):
+    """The V of a step: the fp32 image of the input, floored (:169 on upload).  exact_v: V is taken as it is, in fp64 -- the
+    tracked state of a masked solve (tests/mdi_elementwise.py), which the re-imputation has moved off the fp32 grid."""
+    if exact_v:
+        return np.asarray(V32, dtype=np.float64)
+    return np.fmax(np.asarray(V32, dtype=np.float32).astype(np.float64), FLR)
 
 
-def ref_hstep(V32, W, H, beta, S=0.0, h_ind=None):
+def ref_hstep(V32, W, H, beta, S=0.0, h_ind=None, exact_v=False):
     """The H half of one iteration in fp64, src/sparse_nmf.m:189-207 (oracle/sparse_nmf_oracle.py:180-207).
 
     Returns (H_new, info): info holds the smallest unclamped Lam = W*H and dph, whose distance from the 1e-9 floor the bound
-    depends on.  Rows outside h_ind are returned unchanged (a partial h_ind is refused by the plan anyway)."""
-    V = _floored_v(V32)
+    depends on.  Rows outside h_ind are returned unchanged (a partial h_ind is refused by the plan anyway).  exact_v: _floored_v."""
+    V = _floored_v(V32, exact_v)
     W = np.asarray(W, dtype=np.float64)
     H = np.asarray(H, dtype=np.float64)
     F, T = V.shape
@@ -99,13 +108,13 @@ def ref_hstep(V32, W, H, beta, S=0.0, h_ind=None):
     return Hn, info
 
 
-def ref_wstep(V32, W, H, beta, w_ind=None, gram=False):
+def ref_wstep(V32, W, H, beta, w_ind=None, gram=False, exact_v=False):
     """The W half of one iteration in fp64, src/sparse_nmf.m:212-243 (oracle/sparse_nmf_oracle.py:210-233), with H the
     activations of THIS iteration.  All columns are normalised afterwards (:242).  gram=True forms P = W*(H*H') (what a plan
     reporting "through the Gram matrix" computes; equal to max(W*H, flr)*H' wherever the floor does not bind).
 
-    Returns (W_new, info): info holds the smallest unclamped Lam and dpw."""
-    V = _floored_v(V32)
+    Returns (W_new, info): info holds the smallest unclamped Lam and dpw.  exact_v: _floored_v."""
+    V = _floored_v(V32, exact_v)
     W = np.asarray(W, dtype=np.float64)
     H = np.asarray(H, dtype=np.float64)
     r = W.shape[1]
@@ -305,10 +314,10 @@ def rel(a, b):
     return float(np.linalg.norm(np.asarray(a, np.float64) - b) / max(np.linalg.norm(b), 1e-300))
 
 
-def cost_of(V32, W, H, beta, S):
-    """The objective of iterate (W, H) in fp64: divergence + sum(S .* H) (src/sparse_nmf.m:248-261)."""
+def cost_of(V32, W, H, beta, S, exact_v=False):
+    """The objective of iterate (W, H) in fp64: divergence + sum(S .* H) (src/sparse_nmf.m:248-261).  exact_v: _floored_v."""
     from oracle.sparse_nmf_oracle import divergence
-    V = _floored_v(V32)
+    V = _floored_v(V32, exact_v)
     W = np.asarray(W, np.float64)
     H = np.asarray(H, np.float64)
     lam = np.fmax(W @ H, FLR)
