@@ -398,6 +398,25 @@ int snmf_online_get_basis_f32(snmf_online* o, float* B_DFT_d, int64_t ld);
  * runs unbounded); copies the oldest min(cap, *n) of them in order, *n = frames held (= all frames for shorter runs). */
 int snmf_online_trace(snmf_online* o, snmf_online_frame* out, int64_t cap, int64_t* n);
 void snmf_online_destroy(snmf_online* o);
+/* Added within 5.  The fp64 mode of the separator.  The loop is a feedback system (activations -> adapted noise
+ * dictionary -> next activations) that amplifies a perturbation about tenfold per 100 frames, so the fp32 path leaves the
+ * fp64 reference's trajectory after a few hundred frames (docs/WIDENING.md, "Parity horizon").  A separator made here takes
+ * every input in fp64 and keeps every step from PCM to the fed-back state in fp64 (transforms, frame solve, post-filter
+ * state, adaptation solve, synthesis); it holds the reference's per-frame decisions over whole recordings.
+ * Scope: B_sep_mode 'DFT' and the supervised frame solve, every other field of snmf_online_params.  basis_update_N /
+ * basis_update_E here, and snmf_online_set_mel on such a separator, return SNMF_ERR_UNSUPPORTED; so does a geometry whose
+ * adaptation solve does not fit one cooperative launch (fftlength > 1024 or R_a > 64 with adapt_train_N set).
+ * snmf_online_process_f32 on it runs the fp64 path and rounds the float outputs; snmf_online_trace,
+ * snmf_online_get_basis_f32 and snmf_online_destroy work on both kinds. */
+int snmf_online_create_f64(snmf_ctx* ctx, const snmf_online_params* p, const double* B_DFT_x, const double* B_DFT_d,
+                           const double* H0, const double* Ad_blk0, const double* win_stft, const double* win_istft,
+                           snmf_online** out);
+/* Added within 5.  snmf_online_process_f32 with fp64 samples in and out (pcm: int16-valued doubles); the int16 stream is
+ * the fp64 value rounded half away from zero.  SNMF_ERR_STATE on a separator made by snmf_online_create. */
+int snmf_online_process_f64(snmf_online* o, const double* pcm, int64_t n, int flush, double* x_tilde_f64,
+                            int16_t* x_tilde_i16, double* x_hat_f64, double* d_hat_f64, int64_t cap, int64_t* n_out);
+/* Added within 5.  The fp64 master of the current B_DFT_d; both kinds of separator hold one. */
+int snmf_online_get_basis_f64(snmf_online* o, double* B_DFT_d, int64_t ld);
 
 /* ---- batched online separation: S independent streams per launch ------------------------
  * The reference's real workload enhances many recordings, each an independent chain of the per-frame function

@@ -14,6 +14,11 @@
 //   x_tilde_int16 = snmf_online_mex('process', h, pcm, flush)
 //   B_DFT_d = snmf_online_mex('basis', h, F, R_d)          g.B_DFT_d, saved to B_D_u.mat by src/NTF_sep_event_RT.m:138-140
 //   snmf_online_mex('destroy', h)
+// p.precision = 'fp64' selects the fp64 mode (snmf_online_create_f64 / _process_f64 / _get_basis_f64): MATLAB's doubles cross
+// unrounded and every step from PCM to the adapted dictionary runs in fp64 on the device, so the separator follows the
+// MATLAB trajectory over whole recordings (docs/WIDENING.md, "Parity horizon").  DFT mode, supervised frame solve.
+// In both precisions every array argument, pcm included, must be real double (fread(fid, n, 'int16') returns doubles; an
+// 'int16=>int16' read needs double(pcm) first).
 // H0 = rand(R_x+R_d,1) after rand('seed',p.random_seed) and Ad_blk0 = rand(p.R_a,p.m_a) are drawn by the
 // MATLAB wrapper with MATLAB's own generator (src/sparse_nmf.m:112-114,:133-134; src/init_buff.m:39).
 #include <cmath>
@@ -27,11 +32,13 @@
 
 static snmf_ctx* g_ctx = nullptr;
 static std::vector<snmf_online*> g_handles;
+static std::vector<char> g_is_f64;  // per handle: made by snmf_online_create_f64
 
 static void at_exit() {
     for (snmf_online* o : g_handles)
         if (o) snmf_online_destroy(o);
     g_handles.clear();
+    g_is_f64.clear();
     if (g_ctx) {
         snmf_ctx_destroy(g_ctx);
         g_ctx = nullptr;
@@ -56,6 +63,11 @@ static std::vector<float> to_f32(const mxArray* a, const char* what) {
     return out;
 }
 
+static const double* dbl(const mxArray* a, const char* what) {
+    if (!mxIsDouble(a) || mxIsComplex(a)) mexErrMsgIdAndTxt("snmf:type", "%s must be real double", what);
+    return mxGetDoubles(a);
+}
+
 static snmf_online* handle_of(const mxArray* a) {
     const size_t i = (size_t)mxGetScalar(a);
     if (i < 1 || i > g_handles.size() || !g_handles[i - 1]) mexErrMsgIdAndTxt("snmf:handle", "invalid separator handle");
@@ -77,7 +89,10 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         if (nrhs != 6) mexErrMsgIdAndTxt("snmf:usage", "create: B_DFT_x, B_DFT_d, H0, Ad_blk0, p");
         const mxArray* p = prhs[5];
         if (!mxIsStruct(p)) mexErrMsgIdAndTxt("snmf:type", "p must be a struct");
-        char mode[8] = "DFT", meth[8] = "MMSE", cf[8] = "kl";
+        char mode[8] = "DFT", meth[8] = "MMSE", cf[8] = "kl", prec[8] = "fp32";
+        if (const mxArray* f = mxGetField(p, 0, "precision")) mxGetString(f, prec, sizeof prec);
+        if (strcmp(prec, "fp32") && strcmp(prec, "fp64")) mexErrMsgIdAndTxt("snmf:precision", "p.precision must be 'fp32' or 'fp64'");
+        const bool f64 = !strcmp(prec, "fp64");
         if (const mxArray* f = mxGetField(p, 0, "B_sep_mode")) mxGetString(f, mode, sizeof mode);
         if (const mxArray* f = mxGetField(p, 0, "ENHANCE_METHOD")) mxGetString(f, meth, sizeof meth);
         if (const mxArray* f = mxGetField(p, 0, "cf")) mxGetString(f, cf, sizeof cf);
@@ -121,15 +136,23 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         q.class_outputs = 0;
         q.basis_update_N = fld(p, "basis_update_N", 0) != 0;
         q.basis_update_E = fld(p, "basis_update_E", 0) != 0;
-        const std::vector<float> Bx = to_f32(prhs[1], "B_DFT_x"), Bd = to_f32(prhs[2], "B_DFT_d"), H0 = to_f32(prhs[3], "H0"),
-                                 Ad = to_f32(prhs[4], "Ad_blk0");
         const mxArray *ws = mxGetField(p, 0, "win_STFT"), *wi = mxGetField(p, 0, "win_ISTFT");
         if (!ws || !wi) mexErrMsgIdAndTxt("snmf:field", "p.win_STFT / p.win_ISTFT missing");
-        const std::vector<float> w1 = to_f32(ws, "win_STFT"), w2 = to_f32(wi, "win_ISTFT");
         snmf_online* o = nullptr;
-        if (snmf_online_create(g_ctx, &q, Bx.data(), Bd.data(), H0.data(), Ad.data(), w1.data(), w2.data(), &o) != SNMF_OK)
-            mexErrMsgIdAndTxt("snmf:create", "%s", snmf_last_error());
+        if (f64) {
+            // MATLAB already holds doubles: nothing is rounded on the way in
+            if (snmf_online_create_f64(g_ctx, &q, dbl(prhs[1], "B_DFT_x"), dbl(prhs[2], "B_DFT_d"), dbl(prhs[3], "H0"), dbl(prhs[4], "Ad_blk0"),
+                                       dbl(ws, "win_STFT"), dbl(wi, "win_ISTFT"), &o) != SNMF_OK)
+                mexErrMsgIdAndTxt("snmf:create", "%s", snmf_last_error());
+        } else {
+            const std::vector<float> Bx = to_f32(prhs[1], "B_DFT_x"), Bd = to_f32(prhs[2], "B_DFT_d"), H0 = to_f32(prhs[3], "H0"),
+                                     Ad = to_f32(prhs[4], "Ad_blk0");
+            const std::vector<float> w1 = to_f32(ws, "win_STFT"), w2 = to_f32(wi, "win_ISTFT");
+            if (snmf_online_create(g_ctx, &q, Bx.data(), Bd.data(), H0.data(), Ad.data(), w1.data(), w2.data(), &o) != SNMF_OK)
+                mexErrMsgIdAndTxt("snmf:create", "%s", snmf_last_error());
+        }
         g_handles.push_back(o);
+        g_is_f64.push_back(f64 ? 1 : 0);
         plhs[0] = mxCreateDoubleScalar((double)g_handles.size());
     } else if (!strcmp(cmd, "set_mel")) {
         // snmf_online_mex('set_mel', h, melmat, B_Mel_x, B_Mel_d, MelConv): melmat = g.melmat (F_order x F), init_buff.m:46
@@ -146,24 +169,34 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     } else if (!strcmp(cmd, "process")) {
         if (nrhs != 4) mexErrMsgIdAndTxt("snmf:usage", "process: handle, pcm, flush");
         snmf_online* o = handle_of(prhs[1]);
-        const std::vector<float> pcm = to_f32(prhs[2], "pcm");
         const int flush = mxGetScalar(prhs[3]) != 0;
-        const int64_t cap = (int64_t)pcm.size() + 64 * 4096;
+        const int64_t np = (int64_t)mxGetNumberOfElements(prhs[2]);
+        const int64_t cap = np + 64 * 4096;
         std::vector<int16_t> out((size_t)cap);
         int64_t n = 0;
-        if (snmf_online_process_f32(o, pcm.data(), (int64_t)pcm.size(), flush, nullptr, out.data(), nullptr, nullptr, cap, &n) != SNMF_OK)
-            mexErrMsgIdAndTxt("snmf:process", "%s", snmf_last_error());
+        if (g_is_f64[(size_t)mxGetScalar(prhs[1]) - 1]) {
+            if (snmf_online_process_f64(o, dbl(prhs[2], "pcm"), np, flush, nullptr, out.data(), nullptr, nullptr, cap, &n) != SNMF_OK)
+                mexErrMsgIdAndTxt("snmf:process", "%s", snmf_last_error());
+        } else {
+            const std::vector<float> pcm = to_f32(prhs[2], "pcm");
+            if (snmf_online_process_f32(o, pcm.data(), np, flush, nullptr, out.data(), nullptr, nullptr, cap, &n) != SNMF_OK)
+                mexErrMsgIdAndTxt("snmf:process", "%s", snmf_last_error());
+        }
         plhs[0] = mxCreateNumericMatrix((mwSize)n, 1, mxINT16_CLASS, mxREAL);
         std::memcpy(mxGetInt16s(plhs[0]), out.data(), (size_t)n * 2);
     } else if (!strcmp(cmd, "basis")) {
         if (nrhs != 4) mexErrMsgIdAndTxt("snmf:usage", "basis: handle, F, R_d");
         snmf_online* o = handle_of(prhs[1]);
         const mwSize F = (mwSize)mxGetScalar(prhs[2]), Rd = (mwSize)mxGetScalar(prhs[3]);
-        std::vector<float> B((size_t)F * Rd);
-        if (snmf_online_get_basis_f32(o, B.data(), (int64_t)F) != SNMF_OK) mexErrMsgIdAndTxt("snmf:basis", "%s", snmf_last_error());
         plhs[0] = mxCreateDoubleMatrix(F, Rd, mxREAL);
         double* d = mxGetDoubles(plhs[0]);
-        for (size_t i = 0; i < B.size(); ++i) d[i] = (double)B[i];
+        if (g_is_f64[(size_t)mxGetScalar(prhs[1]) - 1]) {  // the fp64 master, unrounded
+            if (snmf_online_get_basis_f64(o, d, (int64_t)F) != SNMF_OK) mexErrMsgIdAndTxt("snmf:basis", "%s", snmf_last_error());
+        } else {
+            std::vector<float> B((size_t)F * Rd);
+            if (snmf_online_get_basis_f32(o, B.data(), (int64_t)F) != SNMF_OK) mexErrMsgIdAndTxt("snmf:basis", "%s", snmf_last_error());
+            for (size_t i = 0; i < B.size(); ++i) d[i] = (double)B[i];
+        }
     } else if (!strcmp(cmd, "destroy")) {
         if (nrhs != 2) mexErrMsgIdAndTxt("snmf:usage", "destroy: handle");
         const size_t i = (size_t)mxGetScalar(prhs[1]);

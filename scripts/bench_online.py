@@ -3,7 +3,8 @@
 src/bnmf_sep_event_RT_IS16.m, shipped settings, noise-dictionary adaptation on) over the committed 1.2 s
 audio fixture tiled to --seconds, shipped dictionaries.  Reports frames/s and the real-time factor
 (10 ms hop), whole file in one process() call and hop-by-hop calls (real-time use), next to the CPU
-oracle on a bounded sample.  One JSON line.  Usage: python scripts/bench_online.py [--seconds 12] [--cpu]"""
+oracle on a bounded sample.  One JSON line.  --precision fp64 runs the fp64 mode (OnlineSeparator(precision="fp64")).
+Usage: python scripts/bench_online.py [--seconds 12] [--cpu] [--no-adapt] [--precision fp32|fp64]"""
 import argparse
 import json
 import os
@@ -21,6 +22,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--seconds", type=float, default=12.0)
 ap.add_argument("--cpu", action="store_true")
 ap.add_argument("--no-adapt", action="store_true")
+ap.add_argument("--precision", choices=["fp32", "fp64"], default="fp32")
 a = ap.parse_args()
 
 G = os.path.join(ROOT, "tests", "golden")
@@ -36,10 +38,10 @@ ctx = Context(0)
 
 
 def run(chunk):
-    sep = OnlineSeparator(B[:, :100], B[:, 100:], p, H0=H0, Ad_blk0=Ad0, ctx=ctx)
+    sep = OnlineSeparator(B[:, :100], B[:, 100:], p, H0=H0, Ad_blk0=Ad0, ctx=ctx, precision=a.precision)
     sep.process(s[:1600])  # warm-up: kernels loaded, buffers sized
     sep.close()
-    sep = OnlineSeparator(B[:, :100], B[:, 100:], p, H0=H0, Ad_blk0=Ad0, ctx=ctx)
+    sep = OnlineSeparator(B[:, :100], B[:, 100:], p, H0=H0, Ad_blk0=Ad0, ctx=ctx, precision=a.precision)
     t = time.perf_counter()
     if chunk is None:
         sep.process(s, flush=True)
@@ -58,7 +60,7 @@ dt_hop, _ = run(160)
 nfr = len(tr)
 out = {"config": "C3 online separation end to end (bnmf_sep_event_RT_IS16, shipped settings%s), 513 bins, r=200, %d frames"
                  % (", adaptation off" if a.no_adapt else "", nfr),
-       "value": nfr / dt_file, "unit": "frames/s (whole file per call)", "realtime_factor": (nfr * 0.010) / dt_file,
+       "precision": a.precision, "value": nfr / dt_file, "unit": "frames/s (whole file per call)", "realtime_factor": (nfr * 0.010) / dt_file,
        "hop_by_hop_frames_per_s": nfr / dt_hop, "hop_by_hop_ms_per_frame": dt_hop / nfr * 1e3,
        "frame_solve_iters_mean": float(np.mean([t["n_iter"] for t in tr])),
        "adaptation_solves": int(sum(t["solved"] for t in tr)),

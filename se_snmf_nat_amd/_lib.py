@@ -28,7 +28,8 @@ _TU_HDRS = {
     "snmf_tu_wstats.hip": ["snmf_generic.h", "snmf_wstats_dispatch.h"],
     "snmf_tu_wstats4.hip": ["snmf_generic.h", "snmf_wstats_dispatch.h"],
     "snmf_tu_wstats8.hip": ["snmf_generic.h", "snmf_wstats_dispatch.h"],
-    "snmf_tu_online.hip": ["snmf_online.h"],
+    "snmf_tu_online.hip": ["snmf_online.h", "snmf_online_f64.h"],
+    "snmf_tu_online_f64.hip": ["snmf_online.h", "snmf_online_f64.h"],
     "snmf_tu_online_batch.hip": ["snmf_online.h", "snmf_online_batch.h"],
     "snmf_tu_multi.hip": ["snmf_multi.h"],
     "snmf_tu_dnmf.hip": ["snmf_frontend.h"],
@@ -56,7 +57,7 @@ SYMBOLS = [
     "snmf_stft_num_frames", "snmf_stft_features_f32", "snmf_plan_set_v_from_audio_f32", "snmf_mel_features_f32", "snmf_tf_dd_f32",
     "snmf_plan_set_mask_f64", "snmf_plan_set_mask_f32", "snmf_plan_get_v_mdi_f64", "snmf_plan_get_v_mdi_f32",
     "snmf_online_create", "snmf_online_set_mel", "snmf_online_get_mel_basis_f32", "snmf_online_process_f32", "snmf_online_get_basis_f32", "snmf_online_trace",
-    "snmf_online_destroy",
+    "snmf_online_destroy", "snmf_online_create_f64", "snmf_online_process_f64", "snmf_online_get_basis_f64",
     "snmf_online_batch_create", "snmf_online_batch_process_f32", "snmf_online_batch_get_basis_f32", "snmf_online_batch_trace",
     "snmf_online_batch_destroy", "snmf_online_batch_restart", "snmf_online_batch_get_basis_f64", "snmf_online_batch_set_mel",
     "snmf_online_batch_restart_mel", "snmf_online_batch_get_mel_basis_f32", "snmf_online_batch_get_mel_basis_f64",
@@ -254,6 +255,9 @@ def load():
     sig["snmf_online_get_basis_f32"] = (C.c_int, [vp, vp, i64])
     sig["snmf_online_trace"] = (C.c_int, [vp, vp, i64, C.POINTER(i64)])
     sig["snmf_online_destroy"] = (None, [vp])
+    sig["snmf_online_create_f64"] = (C.c_int, [vp, OP, vp, vp, vp, vp, vp, vp, C.POINTER(vp)])
+    sig["snmf_online_process_f64"] = (C.c_int, [vp, vp, i64, C.c_int, vp, vp, vp, vp, i64, C.POINTER(i64)])
+    sig["snmf_online_get_basis_f64"] = (C.c_int, [vp, vp, i64])
     sig["snmf_online_batch_create"] = (C.c_int, [vp, OP, i32, vp, vp, vp, vp, vp, vp, C.POINTER(vp)])
     sig["snmf_online_batch_process_f32"] = (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp])
     sig["snmf_online_batch_get_basis_f32"] = (C.c_int, [vp, i32, vp, i64])

@@ -1,0 +1,868 @@
+// snmf_online_f64.h -- the fp64 mode of the single-stream online separator (snmf_online_create_f64, include/snmf.h).
+// The online loop is a feedback system (activations -> adapted noise dictionary -> next activations) that amplifies a
+// perturbation about tenfold per 100 frames (docs/WIDENING.md, "Parity horizon"): a path that carries fp32-sized errors
+// leaves the fp64 reference's trajectory after a few hundred frames.  Here every step from PCM to the fed-back state is
+// double: the transforms, the frame solve, the post-filter state, the adaptation solve, the synthesis.  No float sits on
+// that path; float appears only in the diagnostic fields of the 32-byte status.
+//
+// The kernels are fp64 twins of the ones in snmf_online.h (same reference lines, same launch structure), except the
+// frame solve: an fp64 dictionary of 513 x 200 (820 KB) fits neither a CU's LDS nor its registers, so k_hsolve64 streams
+// the L2-resident normalised dictionary -- and a transposed image of it -- through the two matrix-vector products of an
+// iteration, with every vector in LDS.
+//
+// Host side (snmf_tu_online_f64.hip): an OnlineF64 object behind the snmf_online handle.
+#pragma once
+
+#ifndef SNMF_ONLINE_F64_HOST_API_ONLY
+#ifndef SNMF_ONLINE_NO_KERNELS
+#define SNMF_ONLINE_NO_KERNELS 1  // the device functions of snmf_online.h only (its kernels live in snmf_tu_online.hip)
+#endif
+#include "snmf_online.h"
+#endif
+#include "snmf.h"
+
+// ---- host interface between snmf_tu_online.hip (owner of the snmf_online handle) and snmf_tu_online_f64.hip -----------
+struct OnlineF64;
+int online_f64_create(snmf_ctx* ctx, const snmf_online_params* p, const double* Bx, const double* Bd, const double* H0,
+                      const double* Ad0, const double* win_stft, const double* win_istft, OnlineF64** out);
+void online_f64_destroy(OnlineF64* o);
+int online_f64_process(OnlineF64* o, const double* pcm, int64_t n, int flush, double* xt, int16_t* xt_i16, double* xh, double* dh,
+                       int64_t cap, int64_t* n_out);
+int online_f64_get_basis(OnlineF64* o, double* Bd, int64_t ld);
+int online_f64_trace(OnlineF64* o, snmf_online_frame* out, int64_t cap, int64_t* n);
+
+#ifndef SNMF_ONLINE_F64_HOST_API_ONLY
+namespace snmf {
+
+// radix-2 Stockham autosort FFT of N = 2^LOGN points held in LDS (fft_lds of snmf_online.h on double2)
+template <int LOGN>
+__device__ __forceinline__ double2* fft_lds_d(double2* x, double2* y, const double2* __restrict__ tw) {
+    constexpr int N = 1 << LOGN;
+    for (int l = N / 2, m = 1; l >= 1; l >>= 1, m <<= 1) {
+        const int tstep = N / (2 * l);
+        for (int idx = threadIdx.x; idx < N / 2; idx += blockDim.x) {
+            const int j = idx / m, k = idx - j * m;
+            const double2 c0 = x[k + j * m];
+            const double2 c1 = x[k + j * m + l * m];
+            const double2 w = tw[j * tstep];
+            const double2 d = make_double2(c0.x - c1.x, c0.y - c1.y);
+            y[k + 2 * j * m] = make_double2(c0.x + c1.x, c0.y + c1.y);
+            y[k + 2 * j * m + m] = make_double2(w.x * d.x - w.y * d.y, w.x * d.y + w.y * d.x);
+        }
+        __syncthreads();
+        double2* t = x;
+        x = y;
+        y = t;
+    }
+    return x;
+}
+
+struct OStft64Args {
+    const double* sig;  // [(sz - hop) history | n_frames * hop new samples]; frame i starts at i*hop
+    int sz, hop, dcbin;
+    double preemph;
+    const double* win;
+    const double2* tw;  // fp64 twiddles, computed by the host
+    double powv, floorv;
+    double* Ym;         // column i at Ym + i*ld
+    double2* Yph;       // unit phasor exp(i*angle(Y)) per bin, same layout
+    int64_t ld;
+    int n_frames;
+};
+
+// src/bnmf_sep_event_RT_IS16.m:65-81; dynamic LDS = 2 N double2
+template <int LOGN>
+__global__ __launch_bounds__(256) void k_ostft64(OStft64Args a) {
+    constexpr int N = 1 << LOGN;
+    extern __shared__ __attribute__((aligned(16))) double2 fbuf[];
+    double2* bufA = fbuf;
+    double2* bufB = fbuf + N;
+    const int t = blockIdx.x;
+    if (t >= a.n_frames) return;
+    const double* s = a.sig + (int64_t)t * a.hop;
+    double* om = a.Ym + (int64_t)t * a.ld;
+    double2* op = a.Yph + (int64_t)t * a.ld;
+    for (int n = threadIdx.x; n < N; n += 256) {
+        double x = 0.0;
+        if (n < a.sz) {
+            const double cur = s[n];
+            const double prev = n > 0 ? s[n - 1] : 0.0;  // filter([1 -preemph],1,y), zero state (:66)
+            x = (cur - a.preemph * prev) * a.win[n];      // :67
+        }
+        bufA[n] = make_double2(x, 0.0);
+    }
+    __syncthreads();
+    const double2* X = fft_lds_d<LOGN>(bufA, bufB, a.tw);
+    for (int f = threadIdx.x; f <= N / 2; f += 256) {
+        const double2 c = X[f];
+        const double mag = hypot(c.x, c.y);
+        double v;
+        if (a.powv == 2.0) v = mag * mag;
+        else if (a.powv == 1.0) v = mag;
+        else v = pow(mag, a.powv);
+        if (f < a.dcbin) v = 0.0;                        // :74
+        om[f] = v + a.floorv;                            // :77
+        op[f] = mag > 0.0 ? make_double2(c.x / mag, c.y / mag) : make_double2(1.0, 0.0);  // angle(0) = 0
+    }
+}
+
+__device__ __forceinline__ double block_max_d(double v, double* red) {
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_down(v, o, 64));  // (fmax skips NaN, as MATLAB's max)
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double s = red[0];
+    for (int i = 1; i < (int)(blockDim.x >> 6); ++i) s = fmax(s, red[i]);
+    return s;
+}
+
+// ---- dictionary images of the frame solve ---------------------------------------------------------------------------
+// src/sparse_nmf.m:157-159 for [B_DFT_x | B_DFT_d]: wn = sqrt(sum(w.^2)), w ./ wn column-major and transposed, and the
+// column sums of the normalised w (:192).  One workgroup per column; launched at creation and after every adaptation.
+__global__ __launch_bounds__(256) void k_wnorm64(const double* __restrict__ B, int F, int r, double* __restrict__ Wn,
+                                                 double* __restrict__ WnT, double* __restrict__ wn, double* __restrict__ csum) {
+    __shared__ double red[4];
+    const int k = blockIdx.x;
+    if (k >= r) return;
+    const double* b = B + (size_t)k * F;
+    double s2 = 0.0;
+    for (int f = threadIdx.x; f < F; f += 256) s2 += b[f] * b[f];
+    s2 = block_sum_d(s2, red);
+    const double nrm = sqrt(s2);
+    double s1 = 0.0;
+    for (int f = threadIdx.x; f < F; f += 256) {
+        const double w = b[f] / nrm;
+        Wn[(size_t)k * F + f] = w;
+        WnT[(size_t)f * r + k] = w;
+        s1 += w;
+    }
+    s1 = block_sum_d(s1, red);
+    if (threadIdx.x == 0) {
+        wn[k] = nrm;
+        csum[k] = s1;
+    }
+}
+
+// divergence of one element, src/sparse_nmf.m:248-258 (generic beta: the numerator; the caller divides the SUM by
+// beta*(beta-1), as the reference does)
+__device__ __forceinline__ double div_term_d(double v, double lam, double beta) {
+    if (beta == 1.0) return v * log(v / lam) - v + lam;
+    if (beta == 2.0) return (v - lam) * (v - lam);
+    if (beta == 0.0) {
+        const double q = v / lam;
+        return q - log(q) - 1.0;
+    }
+    return pow(v, beta) + (beta - 1.0) * pow(lam, beta) - beta * v * pow(lam, beta - 1.0);
+}
+__device__ __forceinline__ double div_scale_d(double s, double beta) {
+    return (beta == 1.0 || beta == 2.0 || beta == 0.0) ? s : s / (beta * (beta - 1.0));
+}
+
+struct HSolve64Args {
+    const double* Wn;    // [r][F]  normalised dictionary, column-major
+    const double* WnT;   // [F][r]  its transpose
+    const double* wn;    // [r]     column norms of the dictionary
+    const double* csum;  // [r]     column sums of Wn
+    const double* H0;    // [r]     init_h (the same vector every frame)
+    const double* V;     // [n][F]  Ym of the frames
+    double* A;           // [n][r]  activations
+    double* recon;       // [n][2][F]  B_x*A_x | B_d*A_d
+    int* n_iter;         // [n]
+    int F, r, Rx, max_iter, cost_check, n;
+    double beta, sparsity, conv_eps, flr;
+};
+
+// The whole H-only loop of src/sparse_nmf.m:157-286 for one frame per workgroup (h_update_ind all true, w_update_ind all
+// false), in the reference's sequence: h .* wn', Lam = max(w*h, flr); per iteration the H step, Lam again, the objective,
+// the stop test.  16 waves: a wave takes columns of W (lanes along the rows, coalesced in Wn) for the contractions over
+// rows, and rows of W (lanes along the columns, coalesced in WnT) for W*h.  Dynamic LDS = (4 F + 3 r + 32) doubles.
+__global__ __launch_bounds__(1024) void k_hsolve64(HSolve64Args a) {
+    extern __shared__ __attribute__((aligned(16))) double sm64[];
+    const int F = a.F, r = a.r, tid = threadIdx.x, nt = blockDim.x, lane = tid & 63, wv = tid >> 6, nwv = nt >> 6;
+    const int fr = blockIdx.x;
+    if (fr >= a.n) return;
+    double* vs = sm64;        // [F] max(v, flr)
+    double* lam = vs + F;     // [F]
+    double* p1 = lam + F;     // [F] numerator weights   v .* lam.^(beta-2)
+    double* p2 = p1 + F;      // [F] denominator weights lam.^(beta-1)
+    double* h = p2 + F;       // [r]
+    double* num = h + r;      // [r]
+    double* den = num + r;    // [r]
+    double* red = den + r;    // [32]
+    const double beta = a.beta;
+    const bool kl = beta == 1.0, ed = beta == 2.0;
+    const double* v = a.V + (size_t)fr * F;
+    for (int f = tid; f < F; f += nt) vs[f] = fmax(v[f], a.flr);          // :169
+    for (int k = tid; k < r; k += nt) h[k] = a.H0[k] * a.wn[k];           // :160
+    __syncthreads();
+    // Lam = max(w*h, flr) and, with it, the weights of the next H step
+    auto lam_pass = [&]() {
+        for (int f = wv; f < F; f += nwv) {
+            const double* wr = a.WnT + (size_t)f * r;
+            double s = 0.0;
+            for (int k = lane; k < r; k += 64) s = fma(wr[k], h[k], s);
+            s = wave_sum_d(s);
+            if (lane == 0) {
+                const double l = fmax(s, a.flr);
+                lam[f] = l;
+                if (kl) {
+                    p1[f] = vs[f] / l;
+                } else if (ed) {
+                    p1[f] = vs[f];
+                    p2[f] = l;
+                } else {
+                    p1[f] = vs[f] * pow(l, beta - 2.0);
+                    p2[f] = pow(l, beta - 1.0);
+                }
+            }
+        }
+        __syncthreads();
+    };
+    lam_pass();                                                           // :167
+    double last_cost = 0.0;
+    int n_iter = a.max_iter;
+    for (int it = 1; it <= a.max_iter; ++it) {
+        // ---- H step (:189-206) ----
+        for (int k = wv; k < r; k += nwv) {
+            const double* wc = a.Wn + (size_t)k * F;
+            double sn = 0.0, sd = 0.0;
+            if (kl) {
+                for (int f = lane; f < F; f += 64) sn = fma(wc[f], p1[f], sn);
+            } else {
+                for (int f = lane; f < F; f += 64) {
+                    const double w = wc[f];
+                    sn = fma(w, p1[f], sn);
+                    sd = fma(w, p2[f], sd);
+                }
+            }
+            sn = wave_sum_d(sn);
+            if (!kl) sd = wave_sum_d(sd);
+            if (lane == 0) {
+                num[k] = sn;
+                den[k] = fmax((kl ? a.csum[k] : sd) + a.sparsity, a.flr);  // :192-193 / :197-198 / :202-203
+            }
+        }
+        __syncthreads();
+        for (int k = tid; k < r; k += nt) h[k] = h[k] * num[k] / den[k];   // :195
+        __syncthreads();
+        lam_pass();                                                       // :207
+        // ---- objective (:248-261) and stop test (:273-284) ----
+        double d = 0.0;
+        for (int f = tid; f < F; f += nt) d += div_term_d(vs[f], lam[f], beta);
+        d = div_scale_d(block_sum_d(d, red), beta);
+        if (a.cost_check) {
+            double sh = 0.0;
+            for (int k = tid; k < r; k += nt) sh += a.sparsity * h[k];
+            const double cost = d + block_sum_d(sh, red);
+            if (it > 1 && a.conv_eps > 0.0 && fabs(cost - last_cost) / last_cost < a.conv_eps) {  // (NaN < eps is false, as MATLAB's)
+                n_iter = it;
+                break;
+            }
+            last_cost = cost;
+        }
+    }
+    __syncthreads();
+    // activations and the reconstructions B_x*A_x, B_d*A_d (src/bnmf_sep_event_RT_IS16.m:158-202): B = Wn * diag(wn)
+    for (int k = tid; k < r; k += nt) {
+        a.A[(size_t)fr * r + k] = h[k];
+        num[k] = h[k] * a.wn[k];
+    }
+    __syncthreads();
+    double* rx = a.recon + (size_t)fr * 2 * F;
+    for (int f = wv; f < F; f += nwv) {
+        const double* wr = a.WnT + (size_t)f * r;
+        double x = 0.0, dd = 0.0;
+        for (int k = lane; k < r; k += 64) {
+            const double t = wr[k] * num[k];
+            if (k < a.Rx) x += t;
+            else dd += t;
+        }
+        x = wave_sum_d(x);
+        dd = wave_sum_d(dd);
+        if (lane == 0) {
+            rx[f] = x;
+            rx[F + f] = dd;
+        }
+    }
+    if (tid == 0) a.n_iter[fr] = n_iter;
+}
+
+// ---- post-filter -----------------------------------------------------------------------------------------------------
+struct OPost64Args {
+    const double* A;       // [r] activations of this frame
+    const int* n_iter;     // the frame solve's iteration count
+    const double* recon;   // [2][F] B_x*A_x and B_d*A_d
+    const double* Ym;      // [F]
+    double* lambda_dav;    // [F] state
+    double* Xm_tilde;      // [F] state
+    double* r_blk;         // [Pl][F] ring of SNR_local columns
+    double* ldblk;         // [ma][F] ring  lambda_d_blk
+    double* adblk;         // [ma][Ra] ring Ad_blk
+    uint8_t* rup;          // [Ra]
+    OnlineDev* dev;
+    OnlineStatus* status;
+    double* Xt_out;        // [F] G .* Ym of this frame
+    double* Xh_out;        // [F] Xm_hat_sum (may be NULL)
+    double* Dh_out;        // [F] Dm_hat_sum (may be NULL)
+    int F, Rx, Rd, Ra, ma, Pl, Pk, dcbin, gap;
+    int l;                 // 1-based frame index
+    int blk_sparse, adapt, wiener, init_N_len, switch_at;
+    double alpha_p, alpha_eta, alpha_d, beta0, beta_max, Ar_up, flr;
+    int n;                 // frames handled by this launch, one after the other (> 1 only without adaptation)
+};
+
+// opost_frame of snmf_online.h in fp64, DFT mode: src/bnmf_sep_event_RT_IS16.m:158-292 for one frame.
+__device__ __forceinline__ void opost64_frame(const OPost64Args& a, double* sm, double* red) {
+    const int F = a.F, r = a.Rx + a.Rd;
+    double* sA = sm;
+    double* Xs = sA + r;
+    double* Ds = Xs + F;
+    double* Q = Ds + F;
+    double* rs1 = Q + F;
+    double* rs2 = rs1 + F;
+    double* Gs = rs2 + F;
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const int n_push0 = a.dev->n_push, sw0 = a.dev->update_switch;
+    for (int k = tid; k < r; k += nt) sA[k] = a.A[k];
+    for (int f = tid; f < F; f += nt) {
+        Xs[f] = a.recon[f];
+        Ds[f] = a.recon[F + f];
+    }
+    __syncthreads();
+    // A_x_mag, A_d_mag (:228-229)
+    double sx = 0.0, sd = 0.0;
+    for (int k = tid; k < r; k += nt) {
+        if (k < a.Rx) sx += sA[k];
+        else sd += sA[k];
+    }
+    sx = block_sum_d(sx, red);
+    sd = block_sum_d(sd, red);
+    const double A_x_mag = sx / a.Rx, A_d_mag = sd / a.Rd;
+    // ---- src/blk_sparse.m ----
+    if (a.blk_sparse) {
+        double mx = -INFINITY;
+        for (int f = tid; f < F; f += nt) {
+            const double s = Xs[f] / fmax(Ds[f], a.flr);  // :10
+            rs1[f] = s;
+            mx = fmax(mx, s);
+        }
+        mx = block_max_d(mx, red);
+        double* col = a.r_blk + (size_t)((a.l - 1) % a.Pl) * F;  // newest column of the ring (:14)
+        for (int f = tid; f < F; f += nt) {
+            col[f] = rs1[f] / mx;                                 // :12
+            Q[f] = f < a.dcbin ? 0.0 : 0.1;                       // :16
+        }
+        __syncthreads();
+        if (a.l > a.Pl) {
+            for (int f = tid; f < F; f += nt) {
+                double s1 = 0.0, s2 = 0.0;
+                for (int c = 0; c < a.Pl; ++c) {
+                    const double v = a.r_blk[(size_t)c * F + f];
+                    s1 += v;
+                    s2 = fma(v, v, s2);
+                }
+                rs1[f] = s1;
+                rs2[f] = s2;
+            }
+            __syncthreads();
+            const int k2 = a.Pk / 2, gN2 = (a.gap - 1) / 2;
+            const int kfirst = k2 + a.dcbin, klast = F - k2;  // 1-based, :20
+            const int nwin = klast >= kfirst ? (klast - kfirst) / a.gap + 1 : 0;
+            const double sqn = sqrt((double)a.Pl * (double)a.Pk);
+            for (int j = tid; j < nwin; j += nt) {
+                const int k = kfirst + j * a.gap;
+                double l1 = 0.0, l2 = 0.0;
+                for (int row = k - k2; row < k + k2; ++row) {  // 1-based rows k-k2+1 .. k+k2
+                    l1 += rs1[row];
+                    l2 += rs2[row];
+                }
+                Gs[j] = (sqn - l1 / sqrt(l2)) / (sqn - 1.0);   // :26
+            }
+            __syncthreads();
+            if (gN2 >= 1) {
+                // blk_gap >= 3: window k reads Q(k-1), which no other window writes, so the windows are independent
+                for (int j = tid; j < nwin; j += nt) {
+                    const int k = kfirst + j * a.gap;
+                    const double qprev = (k - 2) < a.dcbin ? 0.0 : 0.1;
+                    const double pv = a.alpha_p * qprev + (1.0 - a.alpha_p) * Gs[j];
+                    for (int i = k - gN2 - 1; i <= k + gN2 - 1; ++i) Q[i] = pv;  // :29-30
+                }
+            } else if (tid == 0) {
+                // blk_gap = 1: a genuine first-order recursion along frequency
+                for (int j = 0; j < nwin; ++j) {
+                    const int k = kfirst + j;
+                    Q[k - 1] = a.alpha_p * Q[k - 2] + (1.0 - a.alpha_p) * Gs[j];
+                }
+            }
+            __syncthreads();
+            const double qv = Q[a.Pk + a.dcbin - 1];
+            __syncthreads();
+            for (int f = tid; f < a.Pk - 1; f += nt) Q[f] = qv;  // :32
+            __syncthreads();
+        }
+        for (int f = tid; f < a.dcbin; f += nt) Q[f] = 0.0;      // :36
+    } else {
+        for (int f = tid; f < F; f += nt) Q[f] = 1.0;            // :217
+    }
+    __syncthreads();
+    double qs = 0.0;
+    for (int f = tid; f < F; f += nt) qs += Q[f];
+    qs = block_sum_d(qs, red);
+    const double meanQ = qs / F;
+    // ---- gain (:221-261) ----
+    double beta = 20.0 * log10(A_d_mag / A_x_mag) * a.beta0;  // :230-231
+    if (beta < a.beta0) beta = a.beta0;
+    else if (beta >= a.beta_max) beta = a.beta_max;
+    const bool init = a.l <= a.init_N_len;
+    for (int f = tid; f < F; f += nt) {
+        const double ym = a.Ym[f];
+        double ld = a.l == 1 ? ym : a.lambda_dav[f];                       // :223-225
+        ld = a.alpha_d * ld + (1.0 - a.alpha_d) * Ds[f] * beta;            // :241
+        a.lambda_dav[f] = ld;
+        double G;
+        if (a.wiener) {
+            G = Xs[f] / (Xs[f] + Ds[f]);                                   // :245
+        } else {
+            double eta = (a.alpha_eta * a.Xm_tilde[f] + (1.0 - a.alpha_eta) * Xs[f] * Q[f]) / fmax(ld, a.flr);  // :247
+            eta = fmax(0.0031, eta);                                       // :251
+            G = eta / (eta + 1.0);
+        }
+        G = fmin(G, 1.0);                                                  // :254 (min ignores NaN, as MATLAB's)
+        if (init) G = a.flr;                                               // :256-258
+        Gs[f] = G;
+        const double xt = G * ym;                                          // :260
+        a.Xm_tilde[f] = xt;
+        a.Xt_out[f] = xt;
+        if (a.Xh_out) a.Xh_out[f] = Xs[f];
+        if (a.Dh_out) a.Dh_out[f] = Ds[f];
+    }
+    const double A_x_eff = init ? a.flr : A_x_mag;                         // :258
+    const double Q_control = (1.0 - meanQ) * a.Ar_up;                      // :264
+    const bool trig = a.adapt && (Q_control * A_d_mag > A_x_eff);          // :266
+    int do_solve = 0, n_up = 0;
+    __syncthreads();
+    if (trig) {
+        const int head = n_push0 % a.ma;  // overwrites the oldest column == shift + append (:282,:285)
+        for (int f = tid; f < F; f += nt) {
+            const double ym = a.Ym[f];
+            const double mref = f < a.dcbin ? a.flr : 1.0 - Gs[f];         // :271-272
+            a.ldblk[(size_t)head * F + f] = init ? ym : ym * mref;         // :268-274
+        }
+        for (int k = tid; k < a.Ra; k += nt) a.adblk[(size_t)head * a.Ra + k] = sA[a.Rx + k];
+        __syncthreads();
+        int cnt = 0;
+        for (int k = tid; k < a.Ra; k += nt) {
+            double s = 0.0;
+            for (int c = 0; c < a.ma; ++c) s += a.adblk[(size_t)((head + 1 + c) % a.ma) * a.Ra + k];  // oldest first
+            const bool up = Q_control * (s / a.ma) > A_x_eff;               // :288
+            a.rup[k] = up ? 1 : 0;
+            cnt += up;
+        }
+        n_up = (int)(block_sum_d((double)cnt, red) + 0.5);
+        do_solve = sw0 == a.switch_at;                                     // :294
+        if (tid == 0) {
+            a.dev->n_push = n_push0 + 1;
+            a.dev->update_switch = do_solve ? 1 : sw0 + 1;                 // :343-345
+        }
+    }
+    if (tid == 0) {
+        OnlineStatus s;
+        s.trig = trig;
+        s.do_solve = do_solve;
+        s.n_up = n_up;
+        s.n_iter = *a.n_iter;
+        s.beta = (float)beta;  // (diagnostics)
+        s.A_x_mag = (float)A_x_eff;
+        s.A_d_mag = (float)A_d_mag;
+        s.Q_control = (float)Q_control;
+        *a.status = s;
+    }
+}
+
+// One workgroup; dynamic LDS = (r + 6 F) doubles.  Walks the n frames of a launch in order (k_opost).
+__global__ __launch_bounds__(1024) void k_opost64(OPost64Args a0, int a_stride) {
+    extern __shared__ __attribute__((aligned(16))) double sm64[];
+    __shared__ double red[16];
+    for (int i = 0; i < a0.n; ++i) {
+        OPost64Args a = a0;
+        a.A += (size_t)i * a_stride;
+        a.recon += (size_t)i * 2 * a0.F;
+        a.n_iter += i;
+        a.Ym += (size_t)i * a0.F;
+        a.Xt_out += (size_t)i * a0.F;
+        if (a.Xh_out) a.Xh_out += (size_t)i * a0.F;
+        if (a.Dh_out) a.Dh_out += (size_t)i * a0.F;
+        a.status += i;
+        a.l += i;
+        opost64_frame(a, sm64, red);
+        __threadfence_block();
+        __syncthreads();  // state written by this frame (global + LDS scratch) is visible to the next
+    }
+}
+
+// ---- adaptation ------------------------------------------------------------------------------------------------------
+// k_oprep in fp64: V = lambda_d_blk and H = Ad_blk in time order, rows of H not flagged by r_up zeroed, the update mask.
+__global__ void k_oprep64(const double* __restrict__ ldblk, const double* __restrict__ adblk, const uint8_t* __restrict__ rup,
+                          const OnlineDev* dev, int F, int Ra, int ma, double* __restrict__ Vad, double* __restrict__ Had,
+                          uint8_t* __restrict__ w_ind) {
+    const int oldest = dev->n_push % ma;
+    const size_t nv = (size_t)F * ma, nh = (size_t)Ra * ma;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv + nh + Ra; i += (size_t)gridDim.x * blockDim.x) {
+        if (i < nv) {
+            const int c = (int)(i / F), f = (int)(i - (size_t)c * F);
+            Vad[i] = ldblk[(size_t)((oldest + c) % ma) * F + f];
+        } else if (i < nv + nh) {
+            const size_t j = i - nv;
+            const int c = (int)(j / Ra), k = (int)(j - (size_t)c * Ra);
+            Had[j] = rup[k] ? adblk[(size_t)((oldest + c) % ma) * Ra + k] : 0.0;
+        } else {
+            const int k = (int)(i - nv - nh);
+            w_ind[k] = rup[k];
+        }
+    }
+}
+
+// k_oassemble without the fp32 mirror: B_DFT_d = [B_d_rem, B_d_tmp, B_d_fix] (:336).  One workgroup per column.
+// (k_oassemble itself is compiled into snmf_tu_online.hip only -- it sits behind SNMF_ONLINE_NO_KERNELS in snmf_online.h -- so
+// the column selection below exists TWICE: a fix to it belongs in both kernels.)
+__global__ void k_oassemble64(const double* __restrict__ Bd_old, const double* __restrict__ Wc, int Fp,
+                              const double* __restrict__ Bfix, const uint8_t* __restrict__ rup, int F, int Ra, int Rd,
+                              double* __restrict__ Bd_new) {
+    const int j = blockIdx.x;
+    if (j >= Rd) return;
+    const double* src;
+    if (j >= Ra) {
+        src = Bfix + (size_t)j * F;
+    } else {
+        int n_rem = 0;
+        for (int k = 0; k < Ra; ++k) n_rem += rup[k] ? 0 : 1;
+        const bool want_up = j >= n_rem;
+        int need = want_up ? j - n_rem : j, k = 0;
+        for (; k < Ra; ++k) {
+            if ((rup[k] != 0) == want_up) {
+                if (need == 0) break;
+                --need;
+            }
+        }
+        src = want_up ? Wc + (size_t)k * Fp : Bd_old + (size_t)k * F;
+    }
+    for (int f = threadIdx.x; f < F; f += blockDim.x) Bd_new[(size_t)j * F + f] = src[f];
+}
+
+struct WAdapt64Args {
+    const double* V;       // [ma][F]  lambda_d_blk in time order
+    const double* H;       // [ma][Ra] Ad_blk in time order, rows not in r_up zeroed
+    const double* W0;      // [Ra][F]  init_w (first R_a columns of B_DFT_d)
+    const uint8_t* w_ind;  // [Ra]     r_up
+    double* Wout;          // [Ra][F]  result
+    double* part1;         // [nwg][2 RP + 1]  colsum(Q.*W) | colsum(P.*W) | divergence partials
+    double* part2;         // [nwg][RP]        squared-norm partials
+    int* n_iter_out;
+    unsigned* bar;         // grid-barrier counter, zero at launch
+    int F, Ra, ma, max_iter, cost_check;
+    double beta, sparsity, flr, conv_eps;
+};
+
+constexpr int kWa64RB = 8, kWa64RP = 64, kWa64LPR = 32, kWa64NT = kWa64RB * kWa64LPR;
+// doubles of dynamic LDS
+__host__ __device__ constexpr size_t wadapt64_lds_doubles(int Ra, int ma) {
+    return (size_t)kWa64RB * kWa64RP * 3 + 2 * kWa64RP + 32 + 256 + 2 * kWa64RP + kWa64RP + 3 * (size_t)kWa64RB * ma + (size_t)Ra * ma +
+           (size_t)ma * (kWa64RP + 1) + kWa64RP;
+}
+
+// The whole W-only adaptation solve (src/bnmf_sep_event_RT_IS16.m:330-335 -> src/sparse_nmf.m:157-286 with h_update_ind all
+// false) in ONE cooperative launch, every beta: k_wadapt's design in fp64.  V and H never change, so a workgroup keeps H
+// (both orientations) and its 8 rows of V and W in LDS for the whole solve; an iteration is two small products per row
+// block and two grid barriers (the column sums of the update, then the column norms), through k_wadapt's bounded-spin
+// barrier and its sc1 exchanges.  The stop test runs identically in every workgroup on the same reduced numbers.
+// With P = lam.^(beta-1) * h', Q = (v .* lam.^(beta-2)) * h' the update of :215-239 is, for every beta,
+//   w .* (Q + colsum(P.*w) .* w) ./ max(P + colsum(Q.*w) .* w, flr)        (beta = 1: P = sum(h,2)', Q = (v./lam) * h').
+// Grid = ceil(F / 8) workgroups of 256 threads.
+__global__ __launch_bounds__(kWa64NT) void k_wadapt64(WAdapt64Args a) {
+    constexpr int RB = kWa64RB, RP = kWa64RP, NT = kWa64NT, NWV = kWa64NT / 64, LPR = kWa64LPR;
+    unsigned gen = 0;
+    bool bar_ok = true;
+    extern __shared__ __attribute__((aligned(16))) double sm64[];
+    const int F = a.F, Ra = a.Ra, ma = a.ma, tid = threadIdx.x, nwg = gridDim.x, wg = blockIdx.x;
+    const int f0 = wg * RB;
+    double* Wd = sm64;                     // [RB][RP]
+    double* Ps = Wd + RB * RP;             // [RB][RP]
+    double* Qs = Ps + RB * RP;             // [RB][RP]
+    double* cq = Qs + RB * RP;             // [2 RP] reduced column quantities
+    double* red = cq + 2 * RP;             // [32] (the last one holds the grid barrier's verdict)
+    int* oks = reinterpret_cast<int*>(red + 31);
+    double* scr = red + 32;                // [2][128] cross_sum scratch
+    double* tmp = scr + 256;               // [2 RP] reduced quantities of one exchange
+    double* sk = tmp + 2 * RP;             // [RP] rowsum(H)
+    double* Vs = sk + RP;                  // [RB][ma]
+    double* As = Vs + RB * ma;             // [RB][ma] lam.^(beta-1)
+    double* Bs = As + RB * ma;             // [RB][ma] v .* lam.^(beta-2)
+    double* Hs = Bs + RB * ma;             // [Ra][ma]
+    double* HT = Hs + Ra * ma;             // [ma][RP + 1]
+    int* act = reinterpret_cast<int*>(HT + ma * (RP + 1));  // [1 + RP] number and list of the flagged columns
+    const double beta = a.beta;
+    const bool kl = beta == 1.0, ed = beta == 2.0;
+    const int f = tid / LPR, l32 = tid % LPR;
+    const bool row_ok = f0 + f < F;
+
+    // ---- load + src/sparse_nmf.m:157-169 ----
+    for (int i = tid; i < RB * RP; i += NT) {
+        const int k = i / RB, ff = i - k * RB;
+        Wd[ff * RP + k] = (k < Ra && f0 + ff < F) ? a.W0[(size_t)k * F + f0 + ff] : 0.0;
+    }
+    for (int i = tid; i < RB * ma; i += NT) {
+        const int t = i / RB, ff = i - t * RB;
+        Vs[ff * ma + t] = (f0 + ff < F) ? fmax(a.V[(size_t)t * F + f0 + ff], a.flr) : 0.0;   // :169
+    }
+    for (int i = tid; i < Ra * ma; i += NT) {
+        const int t = i / Ra, k = i - t * Ra;
+        Hs[k * ma + t] = a.H[i];
+    }
+    if (tid == 0) {
+        int n = 0;
+        for (int k = 0; k < Ra; ++k)
+            if (a.w_ind[k]) act[1 + n++] = k;
+        act[0] = n;
+    }
+    __syncthreads();
+    const int nact = act[0];
+    if (tid < RP) {
+        double s2 = 0.0;
+        for (int ff = 0; ff < RB; ++ff) {
+            const double w = Wd[ff * RP + tid];
+            s2 += w * w;
+        }
+        xstore(a.part2 + (size_t)wg * RP + tid, s2);
+    }
+    bar_ok &= grid_bar(a.bar, (unsigned)nwg, gen, oks);
+    cross_sum(a.part2, RP, RP, nwg, scr, tmp);
+    if (tid < RP) cq[tid] = tid < Ra ? sqrt(tmp[tid]) : 1.0;  // wn
+    __syncthreads();
+    for (int i = tid; i < RB * RP; i += NT) {
+        const int k = i % RP;
+        Wd[i] = k < Ra ? Wd[i] / cq[k] : 0.0;                 // w = w ./ wn
+    }
+    for (int i = tid; i < Ra * ma; i += NT) Hs[i] = Hs[i] * cq[i / ma];   // h = h .* wn'  (:160)
+    __syncthreads();
+    for (int i = tid; i < ma * (RP + 1); i += NT) {
+        const int t = i / (RP + 1), k = i - t * (RP + 1);
+        HT[i] = k < Ra ? Hs[k * ma + t] : 0.0;
+    }
+    if (tid < RP) {
+        double s = 0.0;
+        if (tid < Ra)
+            for (int t = 0; t < ma; ++t) s += Hs[tid * ma + t];
+        sk[tid] = s;                                          // sum(h,2)
+    }
+    __syncthreads();
+    double sh_const = 0.0;                                    // sum(sum(sparsity .* h)) (:261), constant: H is fixed
+    for (int k = 0; k < Ra; ++k) sh_const += a.sparsity * sk[k];
+
+    double last_cost = 0.0;
+    int n_rec = 0;
+    bool stopped = false;
+    for (int j = 1; j <= a.max_iter + 1; ++j) {
+        if (j > a.max_iter && !a.cost_check) break;
+        // ---- Lam = max(w*h, flr) of iterate j-1, its divergence, the weights of the update ----
+        double dterm = 0.0;
+        for (int t = l32; t < ma; t += LPR) {
+            double acc = 0.0;
+            for (int q = 0; q < nact; ++q) {
+                const int k = act[1 + q];
+                acc = fma(Wd[f * RP + k], Hs[k * ma + t], acc);
+            }
+            const double lam = fmax(acc, a.flr), v = Vs[f * ma + t];
+            double pa, pb;
+            if (kl) {
+                pa = 1.0;
+                pb = v / lam;
+            } else if (ed) {
+                pa = lam;
+                pb = v;
+            } else {
+                pa = pow(lam, beta - 1.0);
+                pb = v * pow(lam, beta - 2.0);
+            }
+            As[f * ma + t] = row_ok ? pa : 0.0;
+            Bs[f * ma + t] = row_ok ? pb : 0.0;
+            if (row_ok) dterm += div_term_d(v, lam, beta);
+        }
+        __syncthreads();
+        // ---- P = lam.^(beta-1) * h', Q = (v .* lam.^(beta-2)) * h' on this block's rows ----
+        {
+            double gp[2] = {0.0, 0.0}, gq[2] = {0.0, 0.0};
+            const double* ar = As + f * ma;
+            const double* br = Bs + f * ma;
+            const double* hc = HT + l32;
+            if (kl) {
+                for (int t = 0; t < ma; ++t) {
+                    const double b = br[t];
+                    gq[0] = fma(b, hc[t * (RP + 1)], gq[0]);
+                    gq[1] = fma(b, hc[t * (RP + 1) + LPR], gq[1]);
+                }
+                gp[0] = row_ok ? sk[l32] : 0.0;
+                gp[1] = row_ok ? sk[l32 + LPR] : 0.0;
+            } else {
+                for (int t = 0; t < ma; ++t) {
+                    const double av = ar[t], b = br[t], h0 = hc[t * (RP + 1)], h1 = hc[t * (RP + 1) + LPR];
+                    gp[0] = fma(av, h0, gp[0]);
+                    gp[1] = fma(av, h1, gp[1]);
+                    gq[0] = fma(b, h0, gq[0]);
+                    gq[1] = fma(b, h1, gq[1]);
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                const int k = l32 + LPR * c;
+                Ps[f * RP + k] = k < Ra ? gp[c] : 0.0;
+                Qs[f * RP + k] = k < Ra ? gq[c] : 0.0;
+            }
+        }
+        const double dw = wave_sum_d(dterm);
+        if ((tid & 63) == 0) red[tid >> 6] = dw;
+        __syncthreads();
+        if (tid < 2 * RP) {
+            const int k = tid & (RP - 1);
+            const double* src = tid < RP ? Qs : Ps;
+            double s = 0.0;
+            for (int ff = 0; ff < RB; ++ff) s += src[ff * RP + k] * Wd[ff * RP + k];
+            xstore(a.part1 + (size_t)wg * (2 * RP + 1) + tid, s);   // colsum(Q .* w) | colsum(P .* w) partials
+        }
+        if (tid == 2 * RP) {
+            double dsum = 0.0;
+#pragma unroll
+            for (int q = 0; q < NWV; ++q) dsum += red[q];
+            xstore(a.part1 + (size_t)wg * (2 * RP + 1) + 2 * RP, dsum);
+        }
+        bar_ok &= grid_bar(a.bar, (unsigned)nwg, gen, oks);
+        const double dpart = tid < nwg ? xload(a.part1 + (size_t)tid * (2 * RP + 1) + 2 * RP) : 0.0;
+        cross_sum(a.part1, 2 * RP + 1, 2 * RP, nwg, scr, tmp);
+        const double div = div_scale_d(block_sum_d(dpart, red), beta);   // fixed order: the same number in every workgroup
+        if (tid < 2 * RP) cq[tid] = tmp[tid];
+        __syncthreads();
+        if (a.cost_check && j > 1) {                          // cost of iterate j-1 (:260-284)
+            const double cost = div + sh_const;
+            const int it = j - 1;
+            bool stopnow = false;
+            if (it > 1 && a.conv_eps > 0.0) stopnow = fabs(cost - last_cost) / last_cost < a.conv_eps;
+            n_rec = it;
+            last_cost = cost;
+            if (stopnow) {
+                stopped = true;
+                break;
+            }
+        }
+        if (j > a.max_iter) break;
+        // ---- W update (:215-239) on this block's rows, then the norms ----
+        for (int i = tid; i < RB * RP; i += NT) {
+            const int k = i % RP;
+            double wv = Wd[i];
+            if (k < Ra && a.w_ind[k]) {
+                const double dpw = fmax(Ps[i] + cq[k] * wv, a.flr);
+                const double dmw = Qs[i] + cq[RP + k] * wv;
+                wv = wv * dmw / dpw;
+            }
+            Wd[i] = wv;
+        }
+        __syncthreads();
+        if (tid < RP) {
+            double s2 = 0.0;
+            for (int ff = 0; ff < RB; ++ff) {
+                const double w = Wd[ff * RP + tid];
+                s2 += w * w;
+            }
+            xstore(a.part2 + (size_t)wg * RP + tid, s2);
+        }
+        bar_ok &= grid_bar(a.bar, (unsigned)nwg, gen, oks);
+        cross_sum(a.part2, RP, RP, nwg, scr, tmp);
+        if (tid < RP) cq[tid] = tid < Ra ? sqrt(tmp[tid]) : 1.0;
+        __syncthreads();
+        for (int i = tid; i < RB * RP; i += NT) {
+            const int k = i % RP;
+            Wd[i] = k < Ra ? Wd[i] / cq[k] : 0.0;             // :242, ALL columns
+        }
+        __syncthreads();
+    }
+    __syncthreads();
+    for (int i = tid; i < RB * RP; i += NT) {
+        const int k = i / RB, ff = i - k * RB;
+        if (k < Ra && f0 + ff < F) a.Wout[(size_t)k * F + f0 + ff] = Wd[ff * RP + k];
+    }
+    if (wg == 0 && tid == 0) *a.n_iter_out = !bar_ok ? -1 : (stopped ? n_rec : a.max_iter);
+}
+
+// ---- synthesis -------------------------------------------------------------------------------------------------------
+struct OIstft64Args {
+    const double* mag;   // column i at mag + i*ld  (magnitude^pow domain)
+    const double2* ph;
+    int64_t ld;
+    int n_frames, sz, dcb;
+    double powv, scale, preemph;  // scale = overlapscale / N
+    const double* win;
+    const double2* tw;
+    double* syn;         // frame i at syn + i*sz
+};
+
+// src/synth_ifft_buff.m:10-28 (+ the overlapscale of src/bnmf_sep_event_RT_IS16.m:363); dynamic LDS = 2 N double2
+template <int LOGN>
+__global__ __launch_bounds__(256) void k_oistft64(OIstft64Args a) {
+    constexpr int N = 1 << LOGN;
+    extern __shared__ __attribute__((aligned(16))) double2 fbuf[];
+    double2* bufA = fbuf;
+    double2* bufB = fbuf + N;
+    const int t = blockIdx.x;
+    if (t >= a.n_frames) return;
+    const double* mg = a.mag + (int64_t)t * a.ld;
+    const double2* ph = a.ph + (int64_t)t * a.ld;
+    double* o = a.syn + (int64_t)t * a.sz;
+    // real(ifft(X)) = real(fft(conj(X)))/N with X(N-k) = conj(X(k)) for k = 1..N/2-1 (:16-18)
+    for (int k = threadIdx.x; k < N; k += 256) {
+        const int kk = k <= N / 2 ? k : N - k;
+        double m = kk < a.dcb ? 0.0 : mg[kk];                   // :10
+        if (a.powv == 2.0) m = sqrt(m);                         // :11
+        else if (a.powv != 1.0) m = pow(m, 1.0 / a.powv);
+        const double2 p = ph[kk];
+        bufA[k] = make_double2(m * p.x, k <= N / 2 ? -m * p.y : m * p.y);
+    }
+    __syncthreads();
+    double2* X = fft_lds_d<LOGN>(bufA, bufB, a.tw);
+    if (a.preemph == 0.0) {
+        for (int n = threadIdx.x; n < a.sz; n += 256) o[n] = X[n].x * a.scale * a.win[n];  // :19-24
+    } else {
+        for (int n = threadIdx.x; n < a.sz; n += 256) X[n].y = X[n].x * a.scale * a.win[n];
+        __syncthreads();
+        if (threadIdx.x == 0) {  // filter(1, [1 -preemph], .) (:26)
+            double acc = 0.0;
+            for (int n = 0; n < a.sz; ++n) {
+                acc = X[n].y + a.preemph * acc;
+                o[n] = acc;
+            }
+        }
+    }
+}
+
+// k_oola in fp64: overlap-add of src/NTF_sep_event_RT.m:104-124 in closed form, oldest frame first; the int16 stream is
+// the fp64 value rounded half away from zero (fwrite(..,'int16')).
+__global__ void k_oola64(const double* __restrict__ syn, int n_new, int l0, int delay, int sz, int hop, int nov, int i_first,
+                         int n_out, double* __restrict__ outf, int16_t* __restrict__ out16) {
+    const size_t n = (size_t)n_out * hop;
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
+        const int j = (int)(e / hop), s = (int)(e - (size_t)j * hop);
+        const int i = i_first + j;  // index among the new frames; global frame l = l0 + i
+        double acc = 0.0;
+        for (int q = nov - 1; q >= 0; --q) {
+            const int lq = l0 + i - q, off = q * hop + s;
+            if (lq > delay && lq >= 1 && off < sz) acc += syn[(size_t)(i - q + nov - 1) * sz + off];
+        }
+        if (outf) outf[e] = acc;
+        if (out16) {
+            double rr = copysign(floor(fabs(acc) + 0.5), acc);  // round half away, saturate
+            rr = fmin(fmax(rr, -32768.0), 32767.0);
+            if (!(acc == acc)) rr = 0.0;  // NaN -> 0 as MATLAB's integer conversion
+            out16[e] = (int16_t)rr;
+        }
+    }
+}
+
+}  // namespace snmf
+#endif  // SNMF_ONLINE_F64_HOST_API_ONLY

@@ -6,11 +6,14 @@
 // host only sequences launches: per frame it reads one 32-byte status (did the adaptation condition
 // fire?) and, when it did, runs the W-only adaptation solve through the engine's ordinary plan.
 #include "snmf_online.h"
+#define SNMF_ONLINE_F64_HOST_API_ONLY 1  // the fp64 mode's host entry points (its kernels live in snmf_tu_online_f64.hip)
+#include "snmf_online_f64.h"
 
 constexpr size_t kTraceCap = 1u << 16;  // diagnostics ring: the newest 65536 frames (~11 min at 100 frames/s)
 struct snmf_online {
     snmf_ctx* ctx = nullptr;
     snmf_online_params p{};
+    OnlineF64* f64 = nullptr;  // non-null: an fp64 separator (snmf_online_create_f64); every field below p is then unused
     int F = 0, r = 0, N = 0, nov = 0;
     int Fs = 0;               // rows of the solves: F, or F_order in Mel mode
     int mel = 0, mel_conv = 0, n1 = 0;  // B_sep_mode = 'Mel' (snmf_online_set_mel)
@@ -77,6 +80,11 @@ static void online_free_call_buffers(snmf_online* o) {
 
 extern "C" void snmf_online_destroy(snmf_online* o) {
     if (!o) return;
+    if (o->f64) {
+        online_f64_destroy(o->f64);
+        delete o;
+        return;
+    }
     hipSetDevice(o->ctx->device);
     hipStreamSynchronize(o->ctx->stream);
 #ifdef SNMF_PROF_WA
@@ -281,6 +289,7 @@ extern "C" int snmf_online_create(snmf_ctx* ctx, const snmf_online_params* p, co
 extern "C" int snmf_online_set_mel(snmf_online* o, int32_t F_order, int32_t mel_conv, const float* melmat, const float* BMx,
                                    const float* BMd) {
     if (!o || !melmat || !BMx || !BMd) return fail(SNMF_ERR_INVALID, "NULL argument");
+    if (o->f64) return fail(SNMF_ERR_UNSUPPORTED, "fp64 online separator: B_sep_mode 'Mel' is not supported");
     if (o->l != 0 || !o->pending.empty()) return fail(SNMF_ERR_STATE, "snmf_online_set_mel must precede the first process call");
     if (F_order < 2 || F_order > o->F) return fail(SNMF_ERR_INVALID, "F_order must be in [2, fftlength/2+1]");
     HIP_TRY(hipSetDevice(o->ctx->device));
@@ -627,11 +636,32 @@ static int online_run_frames(snmf_online* o, const std::vector<float>& sig, int 
     return SNMF_OK;
 }
 
+// snmf_online_process_f32 on an fp64 separator: the fp64 path, float outputs rounded from its doubles
+static int online_f64_process_rounded(snmf_online* o, const float* pcm, int64_t n, int flush, float* xt_f32, int16_t* xt_i16,
+                                      float* xh_f32, float* dh_f32, int64_t cap, int64_t* n_out) {
+    std::vector<double> x(pcm, pcm + n);
+    // what this call can write at most (n hops, one left over from earlier calls, the flush frames), not the caller's cap
+    const int64_t hop = o->p.frameshift, most = (n / hop + 1 + (flush ? o->p.delay + 1 : 0)) * hop;
+    const size_t c = (size_t)std::max<int64_t>(std::min(cap, most), 0);
+    std::vector<double> xt(xt_f32 ? c : 0), xh(xh_f32 ? c : 0), dh(dh_f32 ? c : 0);
+    int64_t m = 0;
+    SN_TRY(online_f64_process(o->f64, x.data(), n, flush, xt_f32 ? xt.data() : nullptr, xt_i16, xh_f32 ? xh.data() : nullptr,
+                              dh_f32 ? dh.data() : nullptr, (int64_t)c, &m));
+    for (int64_t i = 0; i < m; ++i) {
+        if (xt_f32) xt_f32[i] = (float)xt[i];
+        if (xh_f32) xh_f32[i] = (float)xh[i];
+        if (dh_f32) dh_f32[i] = (float)dh[i];
+    }
+    if (n_out) *n_out = m;
+    return SNMF_OK;
+}
+
 extern "C" int snmf_online_process_f32(snmf_online* o, const float* pcm, int64_t n, int flush, float* xt_f32, int16_t* xt_i16,
                                        float* xh_f32, float* dh_f32, int64_t cap, int64_t* n_out) {
     if (!o) return fail(SNMF_ERR_INVALID, "online handle is NULL");
     if (n_out) *n_out = 0;
     if (n < 0 || (n > 0 && !pcm)) return fail(SNMF_ERR_INVALID, "pcm is NULL");
+    if (o->f64) return online_f64_process_rounded(o, pcm, n, flush, xt_f32, xt_i16, xh_f32, dh_f32, cap, n_out);
     if (o->finished) return fail(SNMF_ERR_STATE, "the stream was flushed; create a new separator");
     if (o->failed) return fail(SNMF_ERR_STATE, "an earlier call failed midway through a batch; the separator state is not reusable, create a new one");
     if ((xh_f32 || dh_f32) && !o->p.class_outputs) return fail(SNMF_ERR_STATE, "class outputs were not requested at creation");
@@ -682,6 +712,15 @@ extern "C" int snmf_online_process_f32(snmf_online* o, const float* pcm, int64_t
 
 extern "C" int snmf_online_get_basis_f32(snmf_online* o, float* Bd, int64_t ld) {
     if (!o || !Bd) return fail(SNMF_ERR_INVALID, "NULL argument");
+    if (o->f64) {
+        const int F = o->p.fftlength / 2 + 1;
+        if (ld < F) return fail(SNMF_ERR_INVALID, "ld < F");
+        std::vector<double> B((size_t)F * o->p.R_d);
+        SN_TRY(online_f64_get_basis(o->f64, B.data(), F));
+        for (int j = 0; j < o->p.R_d; ++j)
+            for (int f = 0; f < F; ++f) Bd[(size_t)j * ld + f] = (float)B[(size_t)j * F + f];
+        return SNMF_OK;
+    }
     if (ld < o->F) return fail(SNMF_ERR_INVALID, "ld < F");
     HIP_TRY(hipSetDevice(o->ctx->device));
     HIP_TRY(hipStreamSynchronize(o->ctx->stream));
@@ -692,7 +731,44 @@ extern "C" int snmf_online_get_basis_f32(snmf_online* o, float* Bd, int64_t ld) 
 
 extern "C" int snmf_online_trace(snmf_online* o, snmf_online_frame* out, int64_t cap, int64_t* n) {
     if (!o) return fail(SNMF_ERR_INVALID, "online handle is NULL");
+    if (o->f64) return online_f64_trace(o->f64, out, cap, n);
     if (n) *n = (int64_t)o->trace.size();
     if (out && cap > 0) std::copy_n(o->trace.begin(), (size_t)std::min<int64_t>(cap, (int64_t)o->trace.size()), out);
+    return SNMF_OK;
+}
+
+// ---- fp64 mode (snmf_online_f64.h): every input crosses in fp64 and every step from PCM to the fed-back state is fp64 ----
+extern "C" int snmf_online_create_f64(snmf_ctx* ctx, const snmf_online_params* p, const double* Bx, const double* Bd, const double* H0,
+                                      const double* Ad0, const double* win_stft, const double* win_istft, snmf_online** out) {
+    if (!ctx || !out || !Bx || !Bd || !H0 || !win_stft || !win_istft) return fail(SNMF_ERR_INVALID, "NULL argument");
+    *out = nullptr;
+    SN_TRY(online_validate(p));
+    if (p->adapt_train_N && !Ad0) return fail(SNMF_ERR_INVALID, "Ad_blk0 is required when adapt_train_N is set");
+    OnlineF64* f = nullptr;
+    SN_TRY(online_f64_create(ctx, p, Bx, Bd, H0, Ad0, win_stft, win_istft, &f));
+    snmf_online* o = new snmf_online();
+    o->ctx = ctx;
+    o->p = *p;
+    o->f64 = f;
+    *out = o;
+    return SNMF_OK;
+}
+
+extern "C" int snmf_online_process_f64(snmf_online* o, const double* pcm, int64_t n, int flush, double* xt_f64, int16_t* xt_i16,
+                                       double* xh_f64, double* dh_f64, int64_t cap, int64_t* n_out) {
+    if (!o) return fail(SNMF_ERR_INVALID, "online handle is NULL");
+    if (n_out) *n_out = 0;
+    if (!o->f64) return fail(SNMF_ERR_STATE, "snmf_online_process_f64 needs a separator made by snmf_online_create_f64");
+    return online_f64_process(o->f64, pcm, n, flush, xt_f64, xt_i16, xh_f64, dh_f64, cap, n_out);
+}
+
+extern "C" int snmf_online_get_basis_f64(snmf_online* o, double* Bd, int64_t ld) {
+    if (!o || !Bd) return fail(SNMF_ERR_INVALID, "NULL argument");
+    if (o->f64) return online_f64_get_basis(o->f64, Bd, ld);
+    if (ld < o->F) return fail(SNMF_ERR_INVALID, "ld < F");
+    HIP_TRY(hipSetDevice(o->ctx->device));
+    HIP_TRY(hipStreamSynchronize(o->ctx->stream));
+    HIP_TRY(hipMemcpy2D(Bd, (size_t)ld * 8, o->B + (size_t)o->F * o->p.R_x, (size_t)o->F * 8, (size_t)o->F * 8, (size_t)o->p.R_d,
+                        hipMemcpyDeviceToHost));
     return SNMF_OK;
 }

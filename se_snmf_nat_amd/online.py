@@ -14,6 +14,10 @@ Scope = the configuration the reference ships: blk_len_sep = 1, Splice = 0, one 
 (shipped) or 'Mel' (MelConv 0/1); supervised or semi-supervised frame solve.  Anything else raises.
 MATLAB's global-RNG draws (rand(r,1) per frame solve, rand(R_a, m_a) in init_buff) are explicit
 arguments `H0` / `Ad_blk0` (default: numpy RandomState(random_seed) stand-ins).
+
+`OnlineSeparator(..., precision="fp64")` is the fp64 mode (snmf_online_create_f64): every array crosses in float64 and every
+step from PCM to the fed-back dictionary runs in fp64 on the device, so the separator holds the fp64 reference's per-frame
+decisions over whole recordings (docs/WIDENING.md, "Parity horizon").  DFT mode and the supervised frame solve only.
 """
 from __future__ import annotations
 
@@ -82,10 +86,18 @@ def _online_params(p, R_x, R_d, adapt, R_a, m_a, method, class_outputs):
 class OnlineSeparator:
     """State `g` of src/init_buff.m + the per-frame function, resident on the GPU."""
 
-    def __init__(self, B_DFT_x, B_DFT_d, p, H0=None, Ad_blk0=None, ctx=None, class_outputs=False, B_Mel_x=None, B_Mel_d=None):
+    def __init__(self, B_DFT_x, B_DFT_d, p, H0=None, Ad_blk0=None, ctx=None, class_outputs=False, B_Mel_x=None, B_Mel_d=None,
+                 precision="fp32"):
+        if precision not in ("fp32", "fp64"):
+            raise ValueError("precision must be 'fp32' or 'fp64'")
+        self.precision = precision
+        dt = np.float64 if precision == "fp64" else np.float32  # what crosses the C ABI
+        self._dt = dt
         mode = p.get("B_sep_mode", "DFT")
         if mode not in ("DFT", "Mel") or p.get("Splice", 0) != 0 or p.get("blk_len_sep", 1) != 1:
             raise NotImplementedError("online path: only Splice=0, blk_len_sep=1 (the shipped settings), B_sep_mode 'DFT' or 'Mel'")
+        if mode == "Mel" and precision == "fp64":
+            raise SnmfError(8, "fp64 online separator: B_sep_mode 'Mel' is not supported")  # SNMF_ERR_UNSUPPORTED, as snmf_online_set_mel
         if mode == "Mel" and (B_Mel_x is None or B_Mel_d is None):
             raise ValueError("B_sep_mode='Mel' needs B_Mel_x and B_Mel_d")
         if "cost_check" not in p:
@@ -95,8 +107,8 @@ class OnlineSeparator:
             raise ValueError("ENHANCE_METHOD must be 'Wiener' or 'MMSE'")
         self._lib = _lib.load()
         self.ctx = ctx or default_context()
-        Bx = np.asfortranarray(B_DFT_x, dtype=np.float32)
-        Bd = np.asfortranarray(B_DFT_d, dtype=np.float32)
+        Bx = np.asfortranarray(B_DFT_x, dtype=dt)
+        Bd = np.asfortranarray(B_DFT_d, dtype=dt)
         F = p["fftlength"] // 2 + 1
         if Bx.shape[0] != F or Bd.shape[0] != F:
             raise ValueError(f"dictionaries must have fftlength/2+1 = {F} rows")
@@ -109,24 +121,24 @@ class OnlineSeparator:
         R_a, m_a = int(p.get("R_a", 1)), int(p.get("m_a", 1))
         if adapt and Ad_blk0 is None:
             Ad_blk0 = rs.random_sample((R_a, m_a))  # stand-in for rand(R_a, m_a), src/init_buff.m:39
-        H0 = np.ascontiguousarray(np.asarray(H0, dtype=np.float32).reshape(-1))
+        H0 = np.ascontiguousarray(np.asarray(H0, dtype=dt).reshape(-1))
         if H0.size != r:
             raise ValueError("H0 must have R_x + R_d entries")
         Ad = None
         if adapt:
-            Ad = np.asfortranarray(Ad_blk0, dtype=np.float32)
+            Ad = np.asfortranarray(Ad_blk0, dtype=dt)
             if Ad.shape != (R_a, m_a):
                 raise ValueError("Ad_blk0 must be R_a x m_a")
-        ws = np.ascontiguousarray(p["win_STFT"], dtype=np.float32)
-        wi = np.ascontiguousarray(p["win_ISTFT"], dtype=np.float32)
+        ws = np.ascontiguousarray(p["win_STFT"], dtype=dt)
+        wi = np.ascontiguousarray(p["win_ISTFT"], dtype=dt)
         q = _online_params(p, self.R_x, self.R_d, adapt, R_a, m_a, method, class_outputs)
         self._q = q
         self.class_outputs = bool(class_outputs)
         self.hop, self.delay = q.frameshift, q.delay
         h = C.c_void_p()
-        _lib.check(self._lib.snmf_online_create(self.ctx._h, C.byref(q), Bx.ctypes.data, Bd.ctypes.data, H0.ctypes.data,
-                                                Ad.ctypes.data if Ad is not None else None, ws.ctypes.data, wi.ctypes.data,
-                                                C.byref(h)))
+        create = self._lib.snmf_online_create_f64 if precision == "fp64" else self._lib.snmf_online_create
+        _lib.check(create(self.ctx._h, C.byref(q), Bx.ctypes.data, Bd.ctypes.data, H0.ctypes.data,
+                          Ad.ctypes.data if Ad is not None else None, ws.ctypes.data, wi.ctypes.data, C.byref(h)))
         self._h = h
         self.ctx._plans.add(self)  # destroyed before the context
         self.mel = mode == "Mel"
@@ -145,15 +157,18 @@ class OnlineSeparator:
     def process(self, pcm, flush=False):
         """Feed PCM (int16 or int16-valued floats).  Returns a dict with the hops the driver writes for the
         frames completed by this call: 'x_tilde' (int16, what fwrite(...,'int16') stores), 'x_tilde_f'
-        (float, before rounding) and with class_outputs 'x_hat' / 'd_hat'."""
-        x = np.ascontiguousarray(np.asarray(pcm).reshape(-1), dtype=np.float32)
+        (float, before rounding) and with class_outputs 'x_hat' / 'd_hat'.  The float arrays are float32, or float64
+        with precision="fp64"."""
+        dt = self._dt
+        x = np.ascontiguousarray(np.asarray(pcm).reshape(-1), dtype=dt)
         cap = (x.size // self.hop + self.delay + 3) * self.hop
-        of = np.zeros(cap, np.float32)
+        of = np.zeros(cap, dt)
         o16 = np.zeros(cap, np.int16)
-        xh = np.zeros(cap, np.float32) if self.class_outputs else None
-        dh = np.zeros(cap, np.float32) if self.class_outputs else None
+        xh = np.zeros(cap, dt) if self.class_outputs else None
+        dh = np.zeros(cap, dt) if self.class_outputs else None
         n = C.c_int64()
-        _lib.check(self._lib.snmf_online_process_f32(
+        process = self._lib.snmf_online_process_f64 if self.precision == "fp64" else self._lib.snmf_online_process_f32
+        _lib.check(process(
             self._h, x.ctypes.data if x.size else None, x.size, 1 if flush else 0, of.ctypes.data, o16.ctypes.data,
             xh.ctypes.data if xh is not None else None, dh.ctypes.data if dh is not None else None, cap, C.byref(n)))
         out = {"x_tilde": o16[:n.value], "x_tilde_f": of[:n.value]}
@@ -162,10 +177,19 @@ class OnlineSeparator:
         return out
 
     def basis(self):
-        """Current B_DFT_d (g.B_DFT_d; saved to B_D_u.mat by src/NTF_sep_event_RT.m:138-140)."""
+        """Current B_DFT_d (g.B_DFT_d; saved to B_D_u.mat by src/NTF_sep_event_RT.m:138-140); with precision="fp64" the
+        fp64 master."""
+        if self.precision == "fp64":
+            return self.basis_f64()
         B = np.zeros((self.F, self.R_d), dtype=np.float32, order="F")
         _lib.check(self._lib.snmf_online_get_basis_f32(self._h, B.ctypes.data, self.F))
         return B.astype(np.float64)
+
+    def basis_f64(self):
+        """The fp64 master of the current B_DFT_d (snmf_online_get_basis_f64; both precisions hold one)."""
+        B = np.zeros((self.F, self.R_d), dtype=np.float64, order="F")
+        _lib.check(self._lib.snmf_online_get_basis_f64(self._h, B.ctypes.data, self.F))
+        return B
 
     def mel_basis(self):
         """Current B_Mel_d (Mel mode: the dictionary the adaptation updates, :318)."""
@@ -194,11 +218,12 @@ class OnlineSeparator:
             pass
 
 
-def ntf_sep_event_rt(pcm, B_DFT_x, B_DFT_d, p, H0=None, Ad_blk0=None, ctx=None, chunk=None, B_Mel_x=None, B_Mel_d=None):
+def ntf_sep_event_rt(pcm, B_DFT_x, B_DFT_d, p, H0=None, Ad_blk0=None, ctx=None, chunk=None, B_Mel_x=None, B_Mel_d=None,
+                     precision="fp32"):
     """src/NTF_sep_event_RT.m for one channel with p.NMF_algorithm = 'SNMF': pcm = the int16 samples after the
     wav header.  Returns (denoised int16, denoised float, final B_DFT_d).  `chunk` (samples per process() call)
-    only changes how the stream is fed, not the result."""
-    sep = OnlineSeparator(B_DFT_x, B_DFT_d, p, H0=H0, Ad_blk0=Ad_blk0, ctx=ctx, B_Mel_x=B_Mel_x, B_Mel_d=B_Mel_d)
+    only changes how the stream is fed, not the result.  precision="fp64": the fp64 mode of OnlineSeparator."""
+    sep = OnlineSeparator(B_DFT_x, B_DFT_d, p, H0=H0, Ad_blk0=Ad_blk0, ctx=ctx, B_Mel_x=B_Mel_x, B_Mel_d=B_Mel_d, precision=precision)
     try:
         x = np.asarray(pcm).reshape(-1)
         if chunk is None:
