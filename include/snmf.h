@@ -417,6 +417,34 @@ int snmf_online_process_f64(snmf_online* o, const double* pcm, int64_t n, int fl
                             int16_t* x_tilde_i16, double* x_hat_f64, double* d_hat_f64, int64_t cap, int64_t* n_out);
 /* Added within 5.  The fp64 master of the current B_DFT_d; both kinds of separator hold one. */
 int snmf_online_get_basis_f64(snmf_online* o, double* B_DFT_d, int64_t ld);
+/* Added within 5.  The per-class estimates x_hat_i / d_hat_i, the first two results of
+ * [x_hat_i, d_hat_i, x_tilde, g] = bnmf_sep_event_RT_IS16(y, l, g, p): p.EVENT_NUM / p.EVENT_RANK / p.NOISE_NUM / p.NOISE_RANK
+ * (settings/initial_setting_SNMF_NAT.m:40-44) cut the two dictionaries into classes of consecutive columns.  Ranks are the
+ * reference's 1-based starts: event class i covers columns event_rank[i] .. event_rank[i+1]-1 of B_x, the last one up to R_x,
+ * and noise class i the same of B_d (src/bnmf_sep_event_RT_IS16.m:158-163, :180-185).  Per frame the class spectrum is
+ * B_DFT(:,R_i) * A(R_i) -- 'Mel' with MelConv = 1: melmat' * (B_Mel(:,R_i) * A(R_i)), :165-171, :187-195 -- from the frame's
+ * activations and the dictionary the frame solve saw (:141), before this frame's adaptation replaces it (:336); a
+ * semi-supervised solve's private W is not used.  The class signal is synth_ifft_buff of it times overlapscale (:350-361),
+ * overlap-added as x_hat / d_hat are (src/NTF_sep_event_RT.m:112-126): the gain does not touch it and no frame is gated.
+ * The sums over the classes are x_hat's and d_hat's spectra, so x_tilde, the adaptation and every decision stay as they are.
+ * Works on separators of both precisions; call after create, before or after snmf_online_set_mel, before the first sample.
+ *   SNMF_ERR_STATE        a separator created without class_outputs; samples were already fed
+ *   SNMF_ERR_INVALID      a count below 1, a rank below 1, ranks not strictly ascending, a last start above R_x / R_d
+ *   SNMF_ERR_UNSUPPORTED  a first rank above 1 (Xm_hat_sum, the sum over the classes, feeds the gain, :201: the reference would
+ *                         silently drop the leading columns from the filter); more than 32 classes on a side; 'Mel' with
+ *                         MelConv = 1 when (event_num + noise_num) * F_order floats exceed a workgroup's LDS */
+int snmf_online_set_classes(snmf_online* o, int32_t event_num, const int32_t* event_rank, int32_t noise_num,
+                            const int32_t* noise_rank);
+/* Added within 5.  snmf_online_process_f32 / _f64 plus the class signals: x_hat_i event_num x cap and d_hat_i noise_num x cap,
+ * class-major (class i at x_hat_i + i * cap), *n_out samples written per class.  Either may be NULL.  Without
+ * snmf_online_set_classes there is one class per side: x_hat_i = x_hat, d_hat_i = d_hat.  The plain process entries keep
+ * working on a separator that has classes; they do not return them. */
+int snmf_online_process_classes_f32(snmf_online* o, const float* pcm, int64_t n, int flush, float* x_tilde_f32,
+                                    int16_t* x_tilde_i16, float* x_hat_f32, float* d_hat_f32, float* x_hat_i_f32,
+                                    float* d_hat_i_f32, int64_t cap, int64_t* n_out);
+int snmf_online_process_classes_f64(snmf_online* o, const double* pcm, int64_t n, int flush, double* x_tilde_f64,
+                                    int16_t* x_tilde_i16, double* x_hat_f64, double* d_hat_f64, double* x_hat_i_f64,
+                                    double* d_hat_i_f64, int64_t cap, int64_t* n_out);
 
 /* ---- batched online separation: S independent streams per launch ------------------------
  * The reference's real workload enhances many recordings, each an independent chain of the per-frame function
@@ -476,6 +504,20 @@ int snmf_online_batch_restart_mel(snmf_online_batch* b, int32_t n, const int32_t
  * batch is not in Mel mode. */
 int snmf_online_batch_get_mel_basis_f32(snmf_online_batch* b, int32_t k, float* B_Mel_d, int64_t ld);
 int snmf_online_batch_get_mel_basis_f64(snmf_online_batch* b, int32_t k, double* B_Mel_d, int64_t ld);
+/* Added within 5.  snmf_online_set_classes for the batch: ONE partition for all streams (the settings are shared), same
+ * semantics and status codes.  Call after create, before or after snmf_online_batch_set_mel, before the first process call
+ * (after it: SNMF_ERR_STATE; so does a batch created without class_outputs).  snmf_online_batch_restart also resets the
+ * listed streams' class overlap-add tails, like those of x_hat / d_hat. */
+int snmf_online_batch_set_classes(snmf_online_batch* b, int32_t event_num, const int32_t* event_rank, int32_t noise_num,
+                                  const int32_t* noise_rank);
+/* Added within 5.  snmf_online_batch_process_f32 plus the class signals: x_hat_i_f32 / d_hat_i_f32 are arrays of S host
+ * pointers (each array and each entry may be NULL) to event_num x cap[k] / noise_num x cap[k] floats, class-major.  A
+ * stream's class signals do not depend on the other streams of the batch.  Without
+ * snmf_online_batch_set_classes there is one class per side (x_hat / d_hat). */
+int snmf_online_batch_process_classes_f32(snmf_online_batch* b, const float* const* pcm, const int64_t* n, const int32_t* flush,
+                                          float* const* x_tilde_f32, int16_t* const* x_tilde_i16, float* const* x_hat_f32,
+                                          float* const* d_hat_f32, float* const* x_hat_i_f32, float* const* d_hat_i_f32,
+                                          const int64_t* cap, int64_t* n_out);
 /* Diagnostics of stream k's most recent frames (the newest 65536 per stream), as snmf_online_trace. */
 int snmf_online_batch_trace(snmf_online_batch* b, int32_t k, snmf_online_frame* out, int64_t cap, int64_t* n);
 void snmf_online_batch_destroy(snmf_online_batch* b);

@@ -590,7 +590,95 @@ __global__ void k_oola(const float* __restrict__ syn, int n_new, int l0, int del
     }
 }
 
-#endif  // SNMF_ONLINE_NO_KERNELS (k_oola)
+// k_oistft over a class-major stack (snmf_online_set_classes): class c's frame t at mag + c*mag_cstride + t*ld, every class
+// with the frame's phase, into syn + c*syn_cstride + t*sz.  Grid (n_frames, classes): ONE launch for all class signals.
+template <int LOGN>
+__global__ __launch_bounds__(256) void k_oistft_cls(OIstftArgs a, int64_t mag_cstride, int64_t syn_cstride) {
+    constexpr int N = 1 << LOGN;
+    __shared__ float2 bufA[N];
+    __shared__ float2 bufB[N];
+    const int t = blockIdx.x, c = blockIdx.y;
+    if (t >= a.n_frames) return;
+    oistft_frame<LOGN>(a, a.mag + (int64_t)c * mag_cstride + (int64_t)t * a.ld, a.ph + (int64_t)t * a.ld,
+                       a.syn + (int64_t)c * syn_cstride + (int64_t)t * a.sz, bufA, bufB);
+}
+
+#endif  // SNMF_ONLINE_NO_KERNELS (k_oola, k_oistft_cls)
+
+// ---------------------------------------------------------------------------------------------
+// Per-class reconstructions (src/bnmf_sep_event_RT_IS16.m:158-202): p.EVENT_RANK / p.NOISE_RANK cut [B_x | B_d] into
+// classes of consecutive columns, class c = columns cls[c] .. cls[c+1]-1 (0-based over the r columns; event classes
+// first, cls[n_cls] = r).  Xm_hat(c) = B(:, R_c) * A(R_c) from the frame's activations and the dictionary the frame solve
+// saw, so the launch sits between the frame solve and the adaptation.  With p.pow = 2 the synthesis takes a square root
+// (src/synth_ifft_buff.m:11): the class signals cannot be had from the sums afterwards.
+// One thread per bin f (rows coalesced along f), the columns walked once in order for all classes; the class of column k
+// does not depend on the thread, so the boundaries are uniform branches and the activations scalar loads.  Each class
+// is one fma chain in fp64 over values of the output precision TO: a class of 30 columns out of 200 has none of the sum's
+// averaging, and the fp64 chain keeps its rounding to the one final conversion.  TB: how the dictionary is stored (the
+// batched separator keeps fp64 masters only; their fp32 rounding IS the single-stream separator's mirror).
+// ---------------------------------------------------------------------------------------------
+constexpr int kOClassMax = 32;  // classes per side (snmf_online_set_classes refuses more)
+
+template <typename TO, typename TB, typename TA>
+__device__ __forceinline__ void oclass_dft(const TB* __restrict__ B, const TA* __restrict__ A, const int* __restrict__ cls, int n_cls,
+                                           int F, TO* __restrict__ out, int64_t cstride) {
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= F) return;
+    for (int c = 0; c < n_cls; ++c) {
+        const int k1 = cls[c + 1];
+        double acc = 0.0;
+#pragma unroll 4
+        for (int k = cls[c]; k < k1; ++k) acc = fma((double)(TO)B[(size_t)k * F + f], (double)A[k], acc);
+        out[(size_t)c * cstride + f] = (TO)acc;
+    }
+}
+
+// 'Mel' with MelConv = 1 (:165-171, :187-195): melmat' * (B_Mel(:, R_c) * A(R_c)).  The n1 x n_cls Mel products first (P, LDS,
+// [n_cls][n1]; every workgroup of a frame forms them), then melmat' on them for this workgroup's bins.
+template <typename TB>
+__device__ __forceinline__ void oclass_mel(const TB* __restrict__ Bm, const float* __restrict__ A, const int* __restrict__ cls,
+                                           int n_cls, int n1, const float* __restrict__ melmat, int F, float* __restrict__ out,
+                                           int64_t cstride, float* P) {
+    for (int i = threadIdx.x; i < n_cls * n1; i += blockDim.x) {
+        const int c = i / n1, m = i - c * n1, k1 = cls[c + 1];
+        double acc = 0.0;
+        for (int k = cls[c]; k < k1; ++k) acc = fma((double)(float)Bm[(size_t)k * n1 + m], (double)A[k], acc);
+        P[i] = (float)acc;
+    }
+    __syncthreads();
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= F) return;
+    for (int c = 0; c < n_cls; ++c) {
+        double acc = 0.0;
+#pragma unroll 4
+        for (int m = 0; m < n1; ++m) acc = fma((double)melmat[(size_t)m * F + f], (double)P[c * n1 + m], acc);
+        out[(size_t)c * cstride + f] = (float)acc;
+    }
+}
+
+struct OClassArgs {
+    const float* B;       // [r][F] fp32 [B_DFT_x | B_DFT_d] (Bf); MelConv = 1: [r][n1] [B_Mel_x | B_Mel_d] (Bmf)
+    const float* A;       // activations of frame i at A + i*a_stride
+    const int* cls;       // [n_cls + 1] column ranges
+    const float* melmat;  // [n1][F] (MelConv = 1)
+    float* out;           // class c, frame i at out + c*cstride + i*F
+    int64_t cstride;
+    int n_cls, F, n1, mel_conv, n, a_stride;
+};
+
+#ifndef SNMF_ONLINE_NO_KERNELS
+// Grid (ceil(F / 256), n frames): one launch per frame step, or one for the n frames of a fixed-dictionary batch.
+// Dynamic LDS: n_cls * n1 floats with MelConv = 1, none otherwise.
+__global__ __launch_bounds__(256) void k_oclass(OClassArgs a) {
+    extern __shared__ float sm[];
+    const int i = blockIdx.y;
+    if (i >= a.n) return;
+    const float* A = a.A + (size_t)i * a.a_stride;
+    float* out = a.out + (size_t)i * a.F;
+    if (a.mel_conv) oclass_mel<float>(a.B, A, a.cls, a.n_cls, a.n1, a.melmat, a.F, out, a.cstride, sm);
+    else oclass_dft<float, float, float>(a.B, A, a.cls, a.n_cls, a.F, out, a.cstride);
+}
+#endif  // SNMF_ONLINE_NO_KERNELS (k_oclass)
 
 // ---------------------------------------------------------------------------------------------
 // k_wadapt: the whole W-only adaptation solve (src/bnmf_sep_event_RT_IS16.m:330-335 ->

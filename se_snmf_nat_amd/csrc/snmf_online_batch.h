@@ -5,6 +5,8 @@
 //   k_obmel       B_sep_mode = 'Mel': the normalised Mel features of every (frame, stream), the solve's input
 //   k_hsolve_frame<..., BATCH = true> (snmf_kernels.h) the frame solves, one workgroup per (frame, stream)
 //   k_obpost      the post-filter, one workgroup per stream walking its frames in order
+//   k_obclass     the per-class reconstructions of a frame step (snmf_online_batch_set_classes), behind the solves and
+//                 before the adaptation
 //   k_obprep_mel  Mel mode: melmat * lambda_d_blk of every stream whose adaptation is due (k_wadapt_batch's V)
 //   k_wadapt_batch the W-only adaptation solve of :296-336, one workgroup per stream, gated on the device
 //   k_obassemble / k_obrefresh  the re-assembly of :336 and the next frame solve's dictionary images, gated
@@ -131,6 +133,32 @@ __global__ __launch_bounds__(1024) void k_obpost(OPostArgs a0, OBatchPost b) {
         opost_frame(a, sm, red);
         __syncthreads();  // state written by this frame (global + LDS scratch) is visible to the next
     }
+}
+
+// k_oclass (snmf_online.h) for every stream of a frame step: Xm_hat(c) = B(:, R_c) * A(R_c) (src/bnmf_sep_event_RT_IS16.m:158-202;
+// MelConv = 1: melmat' * (B_Mel(:, R_c) * A(R_c))) from the stream's fp64 master, rounded to fp32 as the single-stream
+// separator's mirror is, so a stream's class spectra are that separator's.  Slot q's class c goes to out + c*cstride + q*F.
+struct OBatchClassArgs {
+    const double* B;      // [S][r][F] the masters [B_DFT_x | B_DFT_d]; MelConv = 1: [S][r][n1] the Mel masters
+    const float* A;       // activations of slot q at A + q*rp
+    const int* cls;       // [n_cls + 1] column ranges
+    const float* melmat;  // [n1][F] (MelConv = 1)
+    float* out;
+    int64_t cstride;
+    int n_cls, F, n1, mel_conv, rp, r;
+};
+
+// Grid (ceil(F / 256), S, frames): step >= 0: frame `step` of every stream that has it (grid z = 1); step < 0: frame
+// blockIdx.z.  Streams without that frame leave (nfr, as their neighbours).  Dynamic LDS: n_cls * n1 floats with MelConv = 1.
+__global__ __launch_bounds__(256) void k_obclass(OBatchClassArgs a, OBatchFrames fr, int step) {
+    extern __shared__ float sm[];
+    const int s = blockIdx.y, i = step >= 0 ? step : (int)blockIdx.z;
+    if (i >= fr.nfr[s]) return;  // (uniform over the workgroup)
+    const size_t slot = (size_t)i * fr.S + s;
+    const float* A = a.A + slot * a.rp;
+    float* out = a.out + slot * a.F;
+    if (a.mel_conv) oclass_mel<double>(a.B + (size_t)s * a.r * a.n1, A, a.cls, a.n_cls, a.n1, a.melmat, a.F, out, a.cstride, sm);
+    else oclass_dft<float, double, float>(a.B + (size_t)s * a.r * a.F, A, a.cls, a.n_cls, a.F, out, a.cstride);
 }
 
 // the adaptation of stream s is due at frame `step`: the post-filter said so (:294, sum(r_up) > 0)

@@ -26,8 +26,11 @@ struct OnlineF64;
 int online_f64_create(snmf_ctx* ctx, const snmf_online_params* p, const double* Bx, const double* Bd, const double* H0,
                       const double* Ad0, const double* win_stft, const double* win_istft, OnlineF64** out);
 void online_f64_destroy(OnlineF64* o);
+// xhi / dhi: the class signals (snmf_online_process_classes_f64), class-major at `cap`, or NULL
 int online_f64_process(OnlineF64* o, const double* pcm, int64_t n, int flush, double* xt, int16_t* xt_i16, double* xh, double* dh,
-                       int64_t cap, int64_t* n_out);
+                       double* xhi, double* dhi, int64_t cap, int64_t* n_out);
+int online_f64_set_classes(OnlineF64* o, int32_t event_num, const int32_t* event_rank, int32_t noise_num, const int32_t* noise_rank);
+void online_f64_class_counts(OnlineF64* o, int* n_event, int* n_noise);  // (1, 1) without a partition
 int online_f64_get_basis(OnlineF64* o, double* Bd, int64_t ld);
 int online_f64_trace(OnlineF64* o, snmf_online_frame* out, int64_t cap, int64_t* n);
 
@@ -789,6 +792,17 @@ __global__ __launch_bounds__(kWa64NT) void k_wadapt64(WAdapt64Args a) {
         if (k < Ra && f0 + ff < F) a.Wout[(size_t)k * F + f0 + ff] = Wd[ff * RP + k];
     }
     if (wg == 0 && tid == 0) *a.n_iter_out = !bar_ok ? -1 : (stopped ? n_rec : a.max_iter);
+}
+
+// ---- per-class reconstructions ---------------------------------------------------------------------------------------
+// k_oclass of snmf_online.h on the fp64 dictionary (DFT mode; this separator has no Mel mode): Xm_hat(c) = B(:, R_c) * A(R_c)
+// (src/bnmf_sep_event_RT_IS16.m:158-202) of frame i = blockIdx.y into out + c*cstride + i*F.  Grid (ceil(F / 256), n frames).
+__global__ __launch_bounds__(256) void k_oclass64(const double* __restrict__ B, const double* __restrict__ A, int a_stride,
+                                                  const int* __restrict__ cls, int n_cls, int F, int n, double* __restrict__ out,
+                                                  int64_t cstride) {
+    const int i = blockIdx.y;
+    if (i >= n) return;
+    oclass_dft<double, double, double>(B, A + (size_t)i * a_stride, cls, n_cls, F, out + (size_t)i * F, cstride);
 }
 
 // ---- synthesis -------------------------------------------------------------------------------------------------------

@@ -8,6 +8,7 @@
 #include "snmf_online.h"
 #define SNMF_ONLINE_F64_HOST_API_ONLY 1  // the fp64 mode's host entry points (its kernels live in snmf_tu_online_f64.hip)
 #include "snmf_online_f64.h"
+#include "snmf_online_classes.h"
 
 constexpr size_t kTraceCap = 1u << 16;  // diagnostics ring: the newest 65536 frames (~11 min at 100 frames/s)
 struct snmf_online {
@@ -51,6 +52,11 @@ struct snmf_online {
     float *sig = nullptr, *Ym = nullptr, *Xt = nullptr, *Xh = nullptr, *Dh = nullptr, *syn = nullptr, *outf = nullptr;
     float2* Yph = nullptr;
     int16_t* out16 = nullptr;
+    // per-class outputs (snmf_online_set_classes): n_ev event classes then n_cls - n_ev noise classes; n_cls = 0: none set
+    int n_ev = 0, n_cls = 0;
+    int* cls = nullptr;         // [n_cls + 1] column ranges over [B_x | B_d] (snmf_online_classes.h)
+    float* tail_c = nullptr;    // [n_cls][nov - 1 frames] one overlap-add tail per class
+    float *Xc = nullptr, *syn_c = nullptr, *out_c = nullptr;  // per call, class-major: spectra, synthesis frames, hops
     // host state of the driver loop
     std::vector<float> pending, hist;
     int64_t l = 0;  // frames processed
@@ -60,7 +66,9 @@ struct snmf_online {
 };
 
 static void online_free_call_buffers(snmf_online* o) {
-    void* ptrs[] = {o->sig, o->Ym, o->Xt, o->Xh, o->Dh, o->syn, o->outf, o->Yph, o->out16, o->bst, o->bdiv, o->bcost, o->bstatus, o->breco, o->Ymel};
+    void* ptrs[] = {o->sig, o->Ym, o->Xt, o->Xh, o->Dh, o->syn, o->outf, o->Yph, o->out16, o->bst, o->bdiv, o->bcost, o->bstatus, o->breco, o->Ymel,
+                    o->Xc, o->syn_c, o->out_c};
+    o->Xc = o->syn_c = o->out_c = nullptr;
     o->Ymel = nullptr;
     o->breco = nullptr;
     if (o->hb) {
@@ -107,7 +115,8 @@ extern "C" void snmf_online_destroy(snmf_online* o) {
     online_free_call_buffers(o);
     void* ptrs[] = {o->B,   o->Bfix, o->Btmp,  o->H0,    o->lambda_dav, o->Xm_tilde, o->r_blk, o->ldblk, o->adblk,  o->Vad,
                     o->Had, o->win_s, o->win_i, o->syn_tail, o->tw,       o->rup,      o->dev,   o->status, o->hst,   o->hdiv,
-                    o->hcost, o->syn_tail_x, o->syn_tail_d, o->Bf, o->recon1, o->wa_W, o->wa_p1, o->wa_p2, o->wa_cost, o->wa_nit, o->wa_bar, o->melmat, o->Bmf, o->Bm, o->Bmtmp};
+                    o->hcost, o->syn_tail_x, o->syn_tail_d, o->Bf, o->recon1, o->wa_W, o->wa_p1, o->wa_p2, o->wa_cost, o->wa_nit, o->wa_bar, o->melmat, o->Bmf, o->Bm, o->Bmtmp,
+                    o->cls, o->tail_c};
     for (void* q : ptrs)
         if (q) hipFree(q);
     if (o->h_status) hipHostFree(o->h_status);
@@ -292,6 +301,8 @@ extern "C" int snmf_online_set_mel(snmf_online* o, int32_t F_order, int32_t mel_
     if (o->f64) return fail(SNMF_ERR_UNSUPPORTED, "fp64 online separator: B_sep_mode 'Mel' is not supported");
     if (o->l != 0 || !o->pending.empty()) return fail(SNMF_ERR_STATE, "snmf_online_set_mel must precede the first process call");
     if (F_order < 2 || F_order > o->F) return fail(SNMF_ERR_INVALID, "F_order must be in [2, fftlength/2+1]");
+    if (mel_conv && (size_t)o->n_cls * F_order * 4 > o->ctx->lds_max)
+        return fail(SNMF_ERR_UNSUPPORTED, "MelConv = 1 with %d classes at F_order = %d: the class kernel's Mel products do not fit the LDS", o->n_cls, F_order);
     HIP_TRY(hipSetDevice(o->ctx->device));
     hipStream_t st = o->ctx->stream;
     const int n1 = F_order, r = o->r, F = o->F, Rx = o->p.R_x, Rd = o->p.R_d;
@@ -333,6 +344,39 @@ extern "C" int snmf_online_get_mel_basis_f32(snmf_online* o, float* BMd, int64_t
     return SNMF_OK;
 }
 
+/* p.EVENT_RANK / p.NOISE_RANK (settings/initial_setting_SNMF_NAT.m:40-44): the class partition of x_hat_i / d_hat_i
+ * (src/bnmf_sep_event_RT_IS16.m:158-202, :350-361). */
+extern "C" int snmf_online_set_classes(snmf_online* o, int32_t event_num, const int32_t* event_rank, int32_t noise_num,
+                                       const int32_t* noise_rank) {
+    if (!o) return fail(SNMF_ERR_INVALID, "online handle is NULL");
+    if (!o->p.class_outputs) return fail(SNMF_ERR_STATE, "class outputs were not requested at creation");
+    if (o->f64) return online_f64_set_classes(o->f64, event_num, event_rank, noise_num, noise_rank);
+    if (o->l != 0 || !o->pending.empty() || o->finished) return fail(SNMF_ERR_STATE, "snmf_online_set_classes must precede the first sample");
+    std::vector<int> cls;
+    SN_TRY(online_class_ranges(event_num, event_rank, noise_num, noise_rank, o->p.R_x, o->p.R_d, &cls));
+    const int nc = event_num + noise_num;
+    if (o->mel && o->mel_conv && (size_t)nc * o->n1 * 4 > o->ctx->lds_max)
+        return fail(SNMF_ERR_UNSUPPORTED, "MelConv = 1 with %d classes at F_order = %d: the class kernel's Mel products do not fit the LDS", nc, o->n1);
+    HIP_TRY(hipSetDevice(o->ctx->device));
+    hipStream_t st = o->ctx->stream;
+    HIP_TRY(hipStreamSynchronize(st));
+    online_free_call_buffers(o);  // the class-major call buffers depend on the class count
+    for (void** q : {(void**)&o->cls, (void**)&o->tail_c}) {
+        if (*q) hipFree(*q);
+        *q = nullptr;
+    }
+    o->n_ev = o->n_cls = 0;
+    const size_t ntail = (size_t)std::max(1, o->nov - 1) * o->p.framelength;
+    SN_TRY(dalloc(&o->cls, cls.size()));
+    SN_TRY(dalloc(&o->tail_c, (size_t)nc * ntail));
+    HIP_TRY(hipMemcpyAsync(o->cls, cls.data(), cls.size() * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(o->tail_c, 0, (size_t)nc * ntail * 4, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    o->n_ev = event_num;
+    o->n_cls = nc;
+    return SNMF_OK;
+}
+
 static int online_reserve(snmf_online* o, int n) {
     if (n <= o->cap_frames) return SNMF_OK;
     hipStreamSynchronize(o->ctx->stream);
@@ -351,6 +395,11 @@ static int online_reserve(snmf_online* o, int n) {
     SN_TRY(dalloc(&o->syn, (size_t)(cap + o->nov - 1) * sz));
     SN_TRY(dalloc(&o->outf, (size_t)cap * hop));
     SN_TRY(dalloc(&o->out16, (size_t)cap * hop));
+    if (o->n_cls) {
+        SN_TRY(dalloc(&o->Xc, (size_t)o->n_cls * F * cap));
+        SN_TRY(dalloc(&o->syn_c, (size_t)o->n_cls * (cap + o->nov - 1) * sz));
+        SN_TRY(dalloc(&o->out_c, (size_t)o->n_cls * cap * hop));
+    }
     if (!o->p.adapt_train_N && !o->hsemi && o->hp->small_ok) {
         snmf_params bp = o->hp->p;
         bp.T = cap;
@@ -434,6 +483,20 @@ static int online_solve_frame(snmf_online* o, const float* dV, const float** A_o
     return launch_small(pl, 1, 1, o->hdiv, o->hcost, o->hst, (o->mel && !o->mel_conv) ? nullptr : o->recon1, o->p.R_x);
 }
 
+// the class spectra of n frames from frame i0 of the call on (:158-202): activations A + i*a_stride, the dictionary as the
+// frame solve saw it -- so this is queued behind the solve and before anything of the adaptation (k_oclass, snmf_online.h)
+static int online_class_spectra(snmf_online* o, const float* A, int a_stride, int i0, int n) {
+    const bool mc = o->mel && o->mel_conv;
+    OClassArgs c{};
+    c.B = mc ? o->Bmf : o->Bf; c.A = A; c.cls = o->cls; c.melmat = o->melmat; c.out = o->Xc + (size_t)i0 * o->F;
+    c.cstride = (int64_t)o->cap_frames * o->F; c.n_cls = o->n_cls; c.F = o->F; c.n1 = o->n1; c.mel_conv = mc; c.n = n; c.a_stride = a_stride;
+    const size_t lds = mc ? (size_t)o->n_cls * o->n1 * 4 : 0;
+    if (lds) SN_TRY(ensure_dyn_lds(o->ctx->device, (const void*)k_oclass, lds));
+    hipLaunchKernelGGL(k_oclass, dim3((o->F + 255) / 256, n), dim3(256), lds, o->ctx->stream, c);
+    HIP_TRY(hipGetLastError());
+    return SNMF_OK;
+}
+
 // :296-336 once the status says the solve is due
 static int online_adapt(snmf_online* o, int32_t* iters) {
     const snmf_online_params& p = o->p;
@@ -499,7 +562,8 @@ static int online_adapt(snmf_online* o, int32_t* iters) {
 
 // n frames whose samples are sig = [history | n hops] (host); appends the hops the driver would write
 static int online_run_frames(snmf_online* o, const std::vector<float>& sig, int n, std::vector<float>* outf,
-                             std::vector<int16_t>* out16, std::vector<float>* xh, std::vector<float>* dh) {
+                             std::vector<int16_t>* out16, std::vector<float>* xh, std::vector<float>* dh,
+                             std::vector<std::vector<float>>* xc) {
     const snmf_online_params& p = o->p;
     const int F = o->F, sz = p.framelength, hop = p.frameshift, nov = o->nov;
     hipStream_t st = o->ctx->stream;
@@ -562,6 +626,7 @@ static int online_run_frames(snmf_online* o, const std::vector<float>& sig, int 
         a.recon = (pl->frame_fb && (!o->mel || o->mel_conv)) ? o->breco : nullptr;
         hipLaunchKernelGGL(k_opost, dim3(1), dim3(1024), lds_post, st, a);
         HIP_TRY(hipGetLastError());
+        if (o->n_cls) SN_TRY(online_class_spectra(o, pl->H[0], pl->rp, 0, n));
         std::vector<OnlineStatus> hst((size_t)n);
         HIP_TRY(hipMemcpyAsync(hst.data(), o->bstatus, (size_t)n * sizeof(OnlineStatus), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
@@ -579,6 +644,7 @@ static int online_run_frames(snmf_online* o, const std::vector<float>& sig, int 
             a.status = o->status;
             hipLaunchKernelGGL(k_opost, dim3(1), dim3(1024), lds_post, st, a);
             HIP_TRY(hipGetLastError());
+            if (o->n_cls) SN_TRY(online_class_spectra(o, a.A, 0, i, 1));
             HIP_TRY(hipMemcpyAsync(o->h_status, o->status, sizeof(OnlineStatus), hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
             const OnlineStatus hs = *o->h_status;
@@ -632,39 +698,75 @@ static int online_run_frames(snmf_online* o, const std::vector<float>& sig, int 
         SN_TRY(synth(o->Xh, xh, nullptr, true, o->syn_tail_x));
         SN_TRY(synth(o->Dh, dh, nullptr, true, o->syn_tail_d));
     }
+    if (o->n_cls) {
+        // x_hat_i / d_hat_i (:356-361): the class-major stack through ONE inverse-STFT launch, one overlap-add per class on
+        // its own tail, one synchronise for all of them
+        const int nc = o->n_cls;
+        const size_t ntl = (size_t)(nov - 1) * sz, syn_cs = (size_t)(o->cap_frames + nov - 1) * sz, out_cs = (size_t)o->cap_frames * hop;
+        if (nov > 1) HIP_TRY(hipMemcpy2DAsync(o->syn_c, syn_cs * 4, o->tail_c, ntl * 4, ntl * 4, (size_t)nc, hipMemcpyDeviceToDevice, st));
+        OIstftArgs ia{};
+        ia.mag = o->Xc; ia.ph = o->Yph; ia.ld = F; ia.n_frames = n; ia.sz = sz; ia.dcb = p.dcbin_back; ia.powv = (float)p.pow;
+        ia.scale = (float)(p.overlapscale / (double)o->N); ia.preemph = (float)p.preemph; ia.win = o->win_i; ia.tw = o->tw;
+        ia.syn = o->syn_c + ntl;
+        const int64_t mag_cs = (int64_t)o->cap_frames * F;
+        launch_by_logn([&](auto L) { hipLaunchKernelGGL(k_oistft_cls<decltype(L)::value>, dim3(n, nc), dim3(256), 0, st, ia, mag_cs, (int64_t)syn_cs); },
+                       o->N);
+        HIP_TRY(hipGetLastError());
+        for (int c = 0; c < nc && n_out > 0; ++c) {
+            hipLaunchKernelGGL(k_oola, dim3(grid_for((size_t)n_out * hop)), dim3(256), 0, st, (const float*)(o->syn_c + (size_t)c * syn_cs), n, l0,
+                               p.delay, sz, hop, nov, i_first, n_out, o->out_c + (size_t)c * out_cs, (int16_t*)nullptr);
+            HIP_TRY(hipGetLastError());
+            if (xc) {
+                std::vector<float>& v = (*xc)[c];
+                const size_t at = v.size();
+                v.resize(at + (size_t)n_out * hop);
+                HIP_TRY(hipMemcpyAsync(v.data() + at, o->out_c + (size_t)c * out_cs, (size_t)n_out * hop * 4, hipMemcpyDeviceToHost, st));
+            }
+        }
+        if (nov > 1)
+            HIP_TRY(hipMemcpy2DAsync(o->tail_c, ntl * 4, o->syn_c + (size_t)n * sz, syn_cs * 4, ntl * 4, (size_t)nc, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
     o->l += n;
     return SNMF_OK;
 }
 
 // snmf_online_process_f32 on an fp64 separator: the fp64 path, float outputs rounded from its doubles
 static int online_f64_process_rounded(snmf_online* o, const float* pcm, int64_t n, int flush, float* xt_f32, int16_t* xt_i16,
-                                      float* xh_f32, float* dh_f32, int64_t cap, int64_t* n_out) {
+                                      float* xh_f32, float* dh_f32, float* xhi_f32, float* dhi_f32, int64_t cap, int64_t* n_out) {
     std::vector<double> x(pcm, pcm + n);
     // what this call can write at most (n hops, one left over from earlier calls, the flush frames), not the caller's cap
     const int64_t hop = o->p.frameshift, most = (n / hop + 1 + (flush ? o->p.delay + 1 : 0)) * hop;
     const size_t c = (size_t)std::max<int64_t>(std::min(cap, most), 0);
-    std::vector<double> xt(xt_f32 ? c : 0), xh(xh_f32 ? c : 0), dh(dh_f32 ? c : 0);
+    int n_ev = 1, n_no = 1;
+    online_f64_class_counts(o->f64, &n_ev, &n_no);
+    std::vector<double> xt(xt_f32 ? c : 0), xh(xh_f32 ? c : 0), dh(dh_f32 ? c : 0), xhi(xhi_f32 ? c * n_ev : 0), dhi(dhi_f32 ? c * n_no : 0);
     int64_t m = 0;
     SN_TRY(online_f64_process(o->f64, x.data(), n, flush, xt_f32 ? xt.data() : nullptr, xt_i16, xh_f32 ? xh.data() : nullptr,
-                              dh_f32 ? dh.data() : nullptr, (int64_t)c, &m));
+                              dh_f32 ? dh.data() : nullptr, xhi_f32 ? xhi.data() : nullptr, dhi_f32 ? dhi.data() : nullptr, (int64_t)c, &m));
     for (int64_t i = 0; i < m; ++i) {
         if (xt_f32) xt_f32[i] = (float)xt[i];
         if (xh_f32) xh_f32[i] = (float)xh[i];
         if (dh_f32) dh_f32[i] = (float)dh[i];
     }
+    for (int k = 0; xhi_f32 && k < n_ev; ++k)  // (class-major at the caller's cap)
+        for (int64_t i = 0; i < m; ++i) xhi_f32[(size_t)k * cap + i] = (float)xhi[(size_t)k * c + i];
+    for (int k = 0; dhi_f32 && k < n_no; ++k)
+        for (int64_t i = 0; i < m; ++i) dhi_f32[(size_t)k * cap + i] = (float)dhi[(size_t)k * c + i];
     if (n_out) *n_out = m;
     return SNMF_OK;
 }
 
-extern "C" int snmf_online_process_f32(snmf_online* o, const float* pcm, int64_t n, int flush, float* xt_f32, int16_t* xt_i16,
-                                       float* xh_f32, float* dh_f32, int64_t cap, int64_t* n_out) {
+// snmf_online_process_f32 / snmf_online_process_classes_f32 (xhi_f32 / dhi_f32: the class signals, class-major at `cap`)
+static int online_process(snmf_online* o, const float* pcm, int64_t n, int flush, float* xt_f32, int16_t* xt_i16, float* xh_f32,
+                          float* dh_f32, float* xhi_f32, float* dhi_f32, int64_t cap, int64_t* n_out) {
     if (!o) return fail(SNMF_ERR_INVALID, "online handle is NULL");
     if (n_out) *n_out = 0;
     if (n < 0 || (n > 0 && !pcm)) return fail(SNMF_ERR_INVALID, "pcm is NULL");
-    if (o->f64) return online_f64_process_rounded(o, pcm, n, flush, xt_f32, xt_i16, xh_f32, dh_f32, cap, n_out);
+    if (o->f64) return online_f64_process_rounded(o, pcm, n, flush, xt_f32, xt_i16, xh_f32, dh_f32, xhi_f32, dhi_f32, cap, n_out);
     if (o->finished) return fail(SNMF_ERR_STATE, "the stream was flushed; create a new separator");
     if (o->failed) return fail(SNMF_ERR_STATE, "an earlier call failed midway through a batch; the separator state is not reusable, create a new one");
-    if ((xh_f32 || dh_f32) && !o->p.class_outputs) return fail(SNMF_ERR_STATE, "class outputs were not requested at creation");
+    if ((xh_f32 || dh_f32 || xhi_f32 || dhi_f32) && !o->p.class_outputs) return fail(SNMF_ERR_STATE, "class outputs were not requested at creation");
     (void)hipGetLastError();  // clean sticky error state, see PLAN_CHECK
     HIP_TRY(hipSetDevice(o->ctx->device));
     const int sz = o->p.framelength, hop = o->p.frameshift;
@@ -672,19 +774,24 @@ extern "C" int snmf_online_process_f32(snmf_online* o, const float* pcm, int64_t
     const int64_t nfr = (int64_t)(o->pending.size() / (size_t)hop);
     const int64_t tail_frames = flush ? o->p.delay + 1 : 0;
     const int64_t max_out = (nfr + tail_frames) * hop;
-    if ((xt_f32 || xt_i16 || xh_f32 || dh_f32) && cap < max_out) {
+    if ((xt_f32 || xt_i16 || xh_f32 || dh_f32 || xhi_f32 || dhi_f32) && cap < max_out) {
         o->pending.resize(o->pending.size() - (size_t)n);
         return fail(SNMF_ERR_INVALID, "output capacity %lld < %lld samples", (long long)cap, (long long)max_out);
     }
     std::vector<float> of, ox, od;
     std::vector<int16_t> o16;
-    const int64_t chunk = 4096;  // frames per device batch
+    // class signals: with a partition set they come from the class kernel; without one x_hat / d_hat are the one class per side
+    const bool cls_set = o->n_cls > 0, want_c = cls_set && (xhi_f32 || dhi_f32);
+    std::vector<std::vector<float>> oc(want_c ? o->n_cls : 0);
+    std::vector<float>* px = (xh_f32 || (xhi_f32 && !cls_set)) ? &ox : nullptr;
+    std::vector<float>* pd = (dh_f32 || (dhi_f32 && !cls_set)) ? &od : nullptr;
+    const int64_t chunk = cls_set ? std::max<int64_t>(64, 4096 / o->n_cls) : 4096;  // frames per device batch (class-major buffers grow with the classes)
     int64_t done = 0;
     while (done < nfr) {
         const int nb = (int)std::min(chunk, nfr - done);
         std::vector<float> sig(o->hist);
         sig.insert(sig.end(), o->pending.begin() + done * hop, o->pending.begin() + (done + nb) * hop);
-        if (int rc = online_run_frames(o, sig, nb, xt_f32 ? &of : nullptr, xt_i16 ? &o16 : nullptr, xh_f32 ? &ox : nullptr, dh_f32 ? &od : nullptr)) {
+        if (int rc = online_run_frames(o, sig, nb, xt_f32 ? &of : nullptr, xt_i16 ? &o16 : nullptr, px, pd, want_c ? &oc : nullptr)) {
             o->failed = true;  // frames of this call were consumed and the device state advanced: never retry on it
             return rc;
         }
@@ -695,7 +802,7 @@ extern "C" int snmf_online_process_f32(snmf_online* o, const float* pcm, int64_t
     if (flush) {
         // a partial hop is dropped and delay+1 all-zero frames follow (src/NTF_sep_event_RT.m:69-76)
         std::vector<float> sig((size_t)(sz - hop) + (size_t)tail_frames * hop, 0.f);
-        if (int rc = online_run_frames(o, sig, (int)tail_frames, xt_f32 ? &of : nullptr, xt_i16 ? &o16 : nullptr, xh_f32 ? &ox : nullptr, dh_f32 ? &od : nullptr)) {
+        if (int rc = online_run_frames(o, sig, (int)tail_frames, xt_f32 ? &of : nullptr, xt_i16 ? &o16 : nullptr, px, pd, want_c ? &oc : nullptr)) {
             o->failed = true;
             return rc;
         }
@@ -706,8 +813,29 @@ extern "C" int snmf_online_process_f32(snmf_online* o, const float* pcm, int64_t
     if (xt_i16) std::memcpy(xt_i16, o16.data(), o16.size() * 2);
     if (xh_f32) std::memcpy(xh_f32, ox.data(), ox.size() * 4);
     if (dh_f32) std::memcpy(dh_f32, od.data(), od.size() * 4);
-    if (n_out) *n_out = (int64_t)std::max(std::max(of.size(), o16.size()), std::max(ox.size(), od.size()));
+    size_t nc_out = 0;
+    if (cls_set) {
+        for (int c = 0; c < (int)oc.size(); ++c) {
+            float* dst = c < o->n_ev ? (xhi_f32 ? xhi_f32 + (size_t)c * cap : nullptr) : (dhi_f32 ? dhi_f32 + (size_t)(c - o->n_ev) * cap : nullptr);
+            if (dst) std::memcpy(dst, oc[c].data(), oc[c].size() * 4);
+            nc_out = std::max(nc_out, oc[c].size());
+        }
+    } else {
+        if (xhi_f32) std::memcpy(xhi_f32, ox.data(), ox.size() * 4);
+        if (dhi_f32) std::memcpy(dhi_f32, od.data(), od.size() * 4);
+    }
+    if (n_out) *n_out = (int64_t)std::max(std::max(std::max(of.size(), o16.size()), std::max(ox.size(), od.size())), nc_out);
     return SNMF_OK;
+}
+
+extern "C" int snmf_online_process_f32(snmf_online* o, const float* pcm, int64_t n, int flush, float* xt_f32, int16_t* xt_i16,
+                                       float* xh_f32, float* dh_f32, int64_t cap, int64_t* n_out) {
+    return online_process(o, pcm, n, flush, xt_f32, xt_i16, xh_f32, dh_f32, nullptr, nullptr, cap, n_out);
+}
+
+extern "C" int snmf_online_process_classes_f32(snmf_online* o, const float* pcm, int64_t n, int flush, float* xt_f32, int16_t* xt_i16,
+                                               float* xh_f32, float* dh_f32, float* xhi_f32, float* dhi_f32, int64_t cap, int64_t* n_out) {
+    return online_process(o, pcm, n, flush, xt_f32, xt_i16, xh_f32, dh_f32, xhi_f32, dhi_f32, cap, n_out);
 }
 
 extern "C" int snmf_online_get_basis_f32(snmf_online* o, float* Bd, int64_t ld) {
@@ -759,7 +887,16 @@ extern "C" int snmf_online_process_f64(snmf_online* o, const double* pcm, int64_
     if (!o) return fail(SNMF_ERR_INVALID, "online handle is NULL");
     if (n_out) *n_out = 0;
     if (!o->f64) return fail(SNMF_ERR_STATE, "snmf_online_process_f64 needs a separator made by snmf_online_create_f64");
-    return online_f64_process(o->f64, pcm, n, flush, xt_f64, xt_i16, xh_f64, dh_f64, cap, n_out);
+    return online_f64_process(o->f64, pcm, n, flush, xt_f64, xt_i16, xh_f64, dh_f64, nullptr, nullptr, cap, n_out);
+}
+
+extern "C" int snmf_online_process_classes_f64(snmf_online* o, const double* pcm, int64_t n, int flush, double* xt_f64, int16_t* xt_i16,
+                                               double* xh_f64, double* dh_f64, double* xhi_f64, double* dhi_f64, int64_t cap,
+                                               int64_t* n_out) {
+    if (!o) return fail(SNMF_ERR_INVALID, "online handle is NULL");
+    if (n_out) *n_out = 0;
+    if (!o->f64) return fail(SNMF_ERR_STATE, "snmf_online_process_classes_f64 needs a separator made by snmf_online_create_f64");
+    return online_f64_process(o->f64, pcm, n, flush, xt_f64, xt_i16, xh_f64, dh_f64, xhi_f64, dhi_f64, cap, n_out);
 }
 
 extern "C" int snmf_online_get_basis_f64(snmf_online* o, double* Bd, int64_t ld) {

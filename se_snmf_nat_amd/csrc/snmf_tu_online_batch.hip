@@ -2,6 +2,7 @@
 // snmf_online_batch.h.  A translation unit of its own, so that the single-stream kernels' code does not move.
 #include "snmf_internal.h"
 #include "snmf_online_batch.h"
+#include "snmf_online_classes.h"
 
 // Host side: per stream, the hop queue / history / flush logic of snmf_online_process_f32 (snmf_tu_online.hip); on the
 // device, one fixed sequence of launches per frame step for all streams (frame solve, post-filter, gated adaptation,
@@ -51,6 +52,11 @@ struct snmf_online_batch {
     double *divh = nullptr, *costh = nullptr;
     OnlineStatus* status = nullptr;
     int* iters = nullptr;
+    // per-class outputs (snmf_online_batch_set_classes): n_ev event classes then n_cls - n_ev noise classes; n_cls = 0: none set
+    int n_ev = 0, n_cls = 0;
+    int* cls = nullptr;           // [n_cls + 1] column ranges over [B_x | B_d] (snmf_online_classes.h)
+    float* tail_c = nullptr;      // [n_cls][S][ntail] one overlap-add tail per class and stream
+    float *Xc = nullptr, *out_c = nullptr;  // per chunk, class-major: spectra [n_cls][C * S][F], hops [n_cls][cap_out]
     int* meta_i = nullptr;        // [6][S] nfr, nreal, l0, i_first, n_out, (pad)
     int64_t* meta_l = nullptr;    // [3][S] off, zoff, out_off
     // host state, per stream
@@ -63,9 +69,10 @@ struct snmf_online_batch {
 
 static void ob_free_chunk(snmf_online_batch* o) {
     void* ptrs[] = {o->sig, o->Ym, o->Vp, o->Hout, o->reco, o->Xt, o->Xh, o->Dh, o->syn, o->outf, o->Yph, o->out16,
-                    o->st, o->divh, o->costh, o->status, o->iters, o->Ymel};
+                    o->st, o->divh, o->costh, o->status, o->iters, o->Ymel, o->Xc, o->out_c};
     for (void* q : ptrs)
         if (q) hipFree(q);
+    o->Xc = o->out_c = nullptr;
     o->sig = o->Ym = o->Vp = o->Hout = o->reco = o->Xt = o->Xh = o->Dh = o->syn = o->outf = o->Ymel = nullptr;
     o->Yph = nullptr;
     o->out16 = nullptr;
@@ -86,7 +93,7 @@ extern "C" void snmf_online_batch_destroy(snmf_online_batch* o) {
     void* ptrs[] = {o->B, o->Bfix, o->Btmp, o->wn, o->Wu, o->Wcf, o->wx, o->dphv, o->Hin, o->H0, o->Ad0, o->lambda_dav, o->Xm_tilde,
                     o->r_blk, o->ldblk, o->adblk, o->G, o->P, o->Vt, o->tail, o->tail_x, o->tail_d, o->rup, o->dev, o->win_s,
                     o->win_i, o->tw, o->Bxd, o->rs_slots, o->rs_B, o->rs_H, o->rs_A, o->meta_i, o->meta_l, o->melmat, o->Vm, o->Bdf,
-                    o->Bmx, o->Bm, o->rs_Bm};
+                    o->Bmx, o->Bm, o->rs_Bm, o->cls, o->tail_c};
     for (void* q : ptrs)
         if (q) hipFree(q);
     delete o;
@@ -146,6 +153,8 @@ static int ob_restart(snmf_online_batch* o, int n, const int32_t* slots, const d
     a.Bmx = o->Bmx; a.Bmd = Bmd ? o->rs_Bm : nullptr; a.Bm = o->Bm; a.Bdf = o->Bdf; a.n1 = o->n1;
     hipLaunchKernelGGL(k_obrestart, dim3(n, kRsN, kRsParts), dim3(256), 0, st, a);
     HIP_TRY(hipGetLastError());
+    for (int i = 0; i < n && o->tail_c; ++i)  // the class tails of the stream, like tail_x / tail_d: one strided fill over its classes
+        HIP_TRY(hipMemset2DAsync(o->tail_c + (size_t)slots[i] * o->ntail, (size_t)o->S * o->ntail * 4, 0, o->ntail * 4, (size_t)o->n_cls, st));
     // every column's dictionary images (set_w + the init mode of k_wapply) from the solve's dictionary (Mel: the Mel master)
     ORefreshArgs ra{};
     ra.slots = o->rs_slots; ra.S = o->S; ra.B = o->mel ? o->Bm : o->B; ra.Wcf = o->Wcf; ra.wx = o->wx; ra.dphv = o->dphv; ra.wn = o->wn;
@@ -278,6 +287,8 @@ extern "C" int snmf_online_batch_set_mel(snmf_online_batch* o, int32_t F_order, 
     if (o->failed) return fail(SNMF_ERR_STATE, "an earlier call failed midway through a chunk; the batch state is not reusable, create a new one");
     if (o->started) return fail(SNMF_ERR_STATE, "snmf_online_batch_set_mel must precede the first process call");
     if (F_order < 2 || F_order > o->F) return fail(SNMF_ERR_INVALID, "F_order must be in [2, fftlength/2+1]");
+    if (mel_conv && (size_t)o->n_cls * F_order * 4 > o->ctx->lds_max)
+        return fail(SNMF_ERR_UNSUPPORTED, "MelConv = 1 with %d classes at F_order = %d: the class kernel's Mel products do not fit the LDS", o->n_cls, F_order);
     (void)hipGetLastError();  // clean sticky error state, see PLAN_CHECK
     HIP_TRY(hipSetDevice(o->ctx->device));
     hipStream_t st = o->ctx->stream;
@@ -323,6 +334,39 @@ extern "C" int snmf_online_batch_set_mel(snmf_online_batch* o, int32_t F_order, 
     return SNMF_OK;
 }
 
+/* snmf_online_set_classes for the batch: one partition for all streams (src/bnmf_sep_event_RT_IS16.m:158-202, :350-361). */
+extern "C" int snmf_online_batch_set_classes(snmf_online_batch* o, int32_t event_num, const int32_t* event_rank, int32_t noise_num,
+                                             const int32_t* noise_rank) {
+    if (!o) return fail(SNMF_ERR_INVALID, "online batch handle is NULL");
+    if (o->failed) return fail(SNMF_ERR_STATE, "an earlier call failed midway through a chunk; the batch state is not reusable, create a new one");
+    if (!o->p.class_outputs) return fail(SNMF_ERR_STATE, "class outputs were not requested at creation");
+    if (o->started) return fail(SNMF_ERR_STATE, "snmf_online_batch_set_classes must precede the first process call");
+    std::vector<int> cls;
+    SN_TRY(online_class_ranges(event_num, event_rank, noise_num, noise_rank, o->p.R_x, o->p.R_d, &cls));
+    const int nc = event_num + noise_num;
+    if (o->mel && o->mel_conv && (size_t)nc * o->n1 * 4 > o->ctx->lds_max)
+        return fail(SNMF_ERR_UNSUPPORTED, "MelConv = 1 with %d classes at F_order = %d: the class kernel's Mel products do not fit the LDS", nc, o->n1);
+    (void)hipGetLastError();  // clean sticky error state, see PLAN_CHECK
+    HIP_TRY(hipSetDevice(o->ctx->device));
+    hipStream_t st = o->ctx->stream;
+    HIP_TRY(hipStreamSynchronize(st));
+    ob_free_chunk(o);  // the class-major chunk buffers depend on the class count
+    for (void** q : {(void**)&o->cls, (void**)&o->tail_c}) {
+        if (*q) hipFree(*q);
+        *q = nullptr;
+    }
+    o->n_ev = o->n_cls = 0;
+    const size_t nt = (size_t)nc * o->S * o->ntail;
+    SN_TRY(dalloc(&o->cls, cls.size()));
+    SN_TRY(dalloc(&o->tail_c, nt));
+    HIP_TRY(hipMemcpyAsync(o->cls, cls.data(), cls.size() * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(o->tail_c, 0, nt * 4, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    o->n_ev = event_num;
+    o->n_cls = nc;
+    return SNMF_OK;
+}
+
 // chunk buffers for C frames per stream and the given signal / output sizes
 static int ob_reserve(snmf_online_batch* o, int C, size_t n_sig, size_t n_out) {
     if (C <= o->C && n_sig <= o->cap_sig && n_out <= o->cap_out) return SNMF_OK;
@@ -348,6 +392,10 @@ static int ob_reserve(snmf_online_batch* o, int C, size_t n_sig, size_t n_out) {
     SN_TRY(dalloc(&o->syn, (size_t)o->S * (C + o->nov - 1) * sz));
     SN_TRY(dalloc(&o->outf, 3 * std::max<size_t>(n_out, 1)));  // x_tilde | x_hat | d_hat
     SN_TRY(dalloc(&o->out16, std::max<size_t>(n_out, 1)));
+    if (o->n_cls) {
+        SN_TRY(dalloc(&o->Xc, (size_t)o->n_cls * F * slots));
+        SN_TRY(dalloc(&o->out_c, (size_t)o->n_cls * std::max<size_t>(n_out, 1)));
+    }
     SN_TRY(dalloc(&o->st, slots));
     SN_TRY(dalloc(&o->divh, slots * o->p.max_iter));
     SN_TRY(dalloc(&o->costh, slots * o->p.max_iter));
@@ -420,6 +468,20 @@ static int ob_frame_solve(snmf_online_batch* o, int step, int nf) {
     return pl->frame_kb == 16 ? by_bm(I8{}, I16{}) : by_bm(I8{}, I25{});
 }
 
+// the class spectra (:158-202) of frame `step` of every stream (step < 0: all C frames of the chunk): behind the frame solves,
+// before the adaptation replaces the dictionaries (k_obclass)
+static int ob_class_spectra(snmf_online_batch* o, const OBatchFrames& fr, int step, int C) {
+    const bool mc = o->mel && o->mel_conv;
+    OBatchClassArgs c{};
+    c.B = mc ? o->Bm : o->B; c.A = o->Hout; c.cls = o->cls; c.melmat = o->melmat; c.out = o->Xc;
+    c.cstride = (int64_t)o->C * o->S * o->F; c.n_cls = o->n_cls; c.F = o->F; c.n1 = o->n1; c.mel_conv = mc; c.rp = o->hp->rp; c.r = o->r;
+    const size_t lds = mc ? (size_t)o->n_cls * o->n1 * 4 : 0;
+    if (lds) SN_TRY(ensure_dyn_lds(o->ctx->device, (const void*)k_obclass, lds));
+    hipLaunchKernelGGL(k_obclass, dim3((o->F + 255) / 256, o->S, step >= 0 ? 1 : C), dim3(256), lds, o->ctx->stream, c, fr, step);
+    HIP_TRY(hipGetLastError());
+    return SNMF_OK;
+}
+
 // adaptation (gated on the device) + re-assembly + dictionary refresh after frame `step` of every stream
 static int ob_adapt(snmf_online_batch* o, const OBatchFrames& fr, int step) {
     const snmf_online_params& p = o->p;
@@ -469,9 +531,11 @@ static int ob_adapt(snmf_online_batch* o, const OBatchFrames& fr, int step) {
 struct ObSink {
     std::vector<float> f, x, d;
     std::vector<int16_t> i16;
+    std::vector<std::vector<float>> c;  // [n_cls] the class signals
 };
 static int ob_run_chunk(snmf_online_batch* o, const std::vector<int>& nfr, const std::vector<int>& nreal,
-                        const std::vector<int64_t>& consumed, bool want_f, bool want_i16, bool want_cls, std::vector<ObSink>& sink) {
+                        const std::vector<int64_t>& consumed, bool want_f, bool want_i16, bool want_cls, bool want_ci,
+                        std::vector<ObSink>& sink) {
     const snmf_online_params& p = o->p;
     const int S = o->S, F = o->F, sz = p.framelength, hop = p.frameshift, nov = o->nov;
     hipStream_t st = o->ctx->stream;
@@ -554,12 +618,14 @@ static int ob_run_chunk(snmf_online_batch* o, const std::vector<int>& nfr, const
         bp.step = -1;
         hipLaunchKernelGGL(k_obpost, dim3(S), dim3(1024), lds_post, st, a, bp);
         HIP_TRY(hipGetLastError());
+        if (o->n_cls) SN_TRY(ob_class_spectra(o, fr, -1, C));
     } else {
         for (int i = 0; i < C; ++i) {  // one frame step of every stream: four launches, nothing decided on the host
             SN_TRY(ob_frame_solve(o, i, 1));
             bp.step = i;
             hipLaunchKernelGGL(k_obpost, dim3(S), dim3(1024), lds_post, st, a, bp);
             HIP_TRY(hipGetLastError());
+            if (o->n_cls) SN_TRY(ob_class_spectra(o, fr, i, 1));
             SN_TRY(ob_adapt(o, fr, i));
         }
     }
@@ -610,6 +676,13 @@ static int ob_run_chunk(snmf_online_batch* o, const std::vector<int>& nfr, const
             SN_TRY(fetch(hd, o->outf + 2 * n_out));
         }
     }
+    // x_hat_i / d_hat_i (:356-361): each class of the class-major stack through the same synthesis on its own tails
+    std::vector<std::vector<float>> hc(want_ci ? o->n_cls : 0);
+    for (int c = 0; c < o->n_cls; ++c) {
+        float* oc = o->out_c + (size_t)c * std::max<size_t>(o->cap_out, 1);
+        SN_TRY(synth(o->Xc + (size_t)c * o->C * S * F, o->tail_c + (size_t)c * S * o->ntail, oc, nullptr));
+        if (want_ci) SN_TRY(fetch(hc[c], oc));
+    }
     // statuses + adaptation verdicts of the chunk: one copy each
     std::vector<OnlineStatus> hs((size_t)C * S);
     std::vector<int> hit((size_t)C * S);
@@ -636,6 +709,10 @@ static int ob_run_chunk(snmf_online_batch* o, const std::vector<int>& nfr, const
             sink[s].x.insert(sink[s].x.end(), hx.begin() + a0, hx.begin() + a0 + n);
             sink[s].d.insert(sink[s].d.end(), hd.begin() + a0, hd.begin() + a0 + n);
         }
+        if (want_ci) {
+            sink[s].c.resize(hc.size());
+            for (size_t c = 0; c < hc.size(); ++c) sink[s].c[c].insert(sink[s].c[c].end(), hc[c].begin() + a0, hc[c].begin() + a0 + n);
+        }
         if (nreal[s] > 0) {  // history for the next chunk: the last sz - hop samples this stream framed
             const float* end = sig.data() + h_off[s] + (sz - hop) + (size_t)nreal[s] * hop;
             o->hist[s].assign(end - (sz - hop), end);
@@ -645,9 +722,10 @@ static int ob_run_chunk(snmf_online_batch* o, const std::vector<int>& nfr, const
     return SNMF_OK;
 }
 
-extern "C" int snmf_online_batch_process_f32(snmf_online_batch* o, const float* const* pcm, const int64_t* n, const int32_t* flush,
-                                             float* const* xt_f32, int16_t* const* xt_i16, float* const* xh_f32, float* const* dh_f32,
-                                             const int64_t* cap, int64_t* n_out) {
+// snmf_online_batch_process_f32 / snmf_online_batch_process_classes_f32 (xhi_f32 / dhi_f32: the class signals, class-major at cap[s])
+static int ob_process(snmf_online_batch* o, const float* const* pcm, const int64_t* n, const int32_t* flush, float* const* xt_f32,
+                      int16_t* const* xt_i16, float* const* xh_f32, float* const* dh_f32, float* const* xhi_f32, float* const* dhi_f32,
+                      const int64_t* cap, int64_t* n_out) {
     if (!o) return fail(SNMF_ERR_INVALID, "online batch handle is NULL");
     if (!n || !pcm) return fail(SNMF_ERR_INVALID, "pcm / n is NULL");
     const int S = o->S;
@@ -656,8 +734,8 @@ extern "C" int snmf_online_batch_process_f32(snmf_online_batch* o, const float* 
     if (n_out)
         for (int s = 0; s < S; ++s) n_out[s] = 0;
     if (o->failed) return fail(SNMF_ERR_STATE, "an earlier call failed midway through a chunk; the batch state is not reusable, create a new one");
-    if ((xh_f32 || dh_f32) && !p.class_outputs) return fail(SNMF_ERR_STATE, "class outputs were not requested at creation");
-    const bool any_out = xt_f32 || xt_i16 || xh_f32 || dh_f32;
+    if ((xh_f32 || dh_f32 || xhi_f32 || dhi_f32) && !p.class_outputs) return fail(SNMF_ERR_STATE, "class outputs were not requested at creation");
+    const bool any_out = xt_f32 || xt_i16 || xh_f32 || dh_f32 || xhi_f32 || dhi_f32;
     if (any_out && !cap) return fail(SNMF_ERR_INVALID, "cap is NULL");
     std::vector<int64_t> nfr_tot(S), tail(S);
     for (int s = 0; s < S; ++s) {
@@ -669,7 +747,7 @@ extern "C" int snmf_online_batch_process_f32(snmf_online_batch* o, const float* 
         const int64_t need = (nfr_tot[s] + tail[s]) * hop;
         auto short_cap = [&](const void* const* v) { return v && v[s] && cap[s] < need; };
         if (short_cap((const void* const*)xt_f32) || short_cap((const void* const*)xt_i16) || short_cap((const void* const*)xh_f32) ||
-            short_cap((const void* const*)dh_f32))
+            short_cap((const void* const*)dh_f32) || short_cap((const void* const*)xhi_f32) || short_cap((const void* const*)dhi_f32))
             return fail(SNMF_ERR_INVALID, "stream %d: output capacity %lld < %lld samples", s, (long long)cap[s], (long long)need);
     }
     o->started = true;
@@ -680,7 +758,9 @@ extern "C" int snmf_online_batch_process_f32(snmf_online_batch* o, const float* 
     const int C = (int)std::max<int64_t>(1, std::min<int64_t>(4096, kBChunkSlots / S));
     std::vector<int64_t> done(S, 0);
     std::vector<ObSink> sink(S);
-    const bool wf = xt_f32 != nullptr, wi = xt_i16 != nullptr, wc = xh_f32 || dh_f32;
+    // class signals: with a partition set they come from the class kernel; without one x_hat / d_hat are the one class per side
+    const bool cls_set = o->n_cls > 0, wci = cls_set && (xhi_f32 || dhi_f32);
+    const bool wf = xt_f32 != nullptr, wi = xt_i16 != nullptr, wc = xh_f32 || dh_f32 || (!cls_set && (xhi_f32 || dhi_f32));
     for (;;) {
         std::vector<int> nfr(S), nreal(S);
         bool any = false;
@@ -691,7 +771,7 @@ extern "C" int snmf_online_batch_process_f32(snmf_online_batch* o, const float* 
             any |= nfr[s] > 0;
         }
         if (!any) break;
-        if (int rc = ob_run_chunk(o, nfr, nreal, done, wf, wi, wc, sink)) {
+        if (int rc = ob_run_chunk(o, nfr, nreal, done, wf, wi, wc, wci, sink)) {
             o->failed = true;  // frames of this call were consumed and the device state advanced: never retry on it
             return rc;
         }
@@ -708,9 +788,34 @@ extern "C" int snmf_online_batch_process_f32(snmf_online_batch* o, const float* 
         if (wi && xt_i16[s]) std::memcpy(xt_i16[s], k.i16.data(), k.i16.size() * 2);
         if (xh_f32 && xh_f32[s]) std::memcpy(xh_f32[s], k.x.data(), k.x.size() * 4);
         if (dh_f32 && dh_f32[s]) std::memcpy(dh_f32[s], k.d.data(), k.d.size() * 4);
-        if (n_out) n_out[s] = (int64_t)std::max(std::max(k.f.size(), k.i16.size()), std::max(k.x.size(), k.d.size()));
+        size_t nc_out = 0;
+        if (cls_set) {
+            for (int c = 0; c < (int)k.c.size(); ++c) {
+                float* dst = c < o->n_ev ? ((xhi_f32 && xhi_f32[s]) ? xhi_f32[s] + (size_t)c * cap[s] : nullptr)
+                                         : ((dhi_f32 && dhi_f32[s]) ? dhi_f32[s] + (size_t)(c - o->n_ev) * cap[s] : nullptr);
+                if (dst) std::memcpy(dst, k.c[c].data(), k.c[c].size() * 4);
+                nc_out = std::max(nc_out, k.c[c].size());
+            }
+        } else {
+            if (xhi_f32 && xhi_f32[s]) std::memcpy(xhi_f32[s], k.x.data(), k.x.size() * 4);
+            if (dhi_f32 && dhi_f32[s]) std::memcpy(dhi_f32[s], k.d.data(), k.d.size() * 4);
+        }
+        if (n_out) n_out[s] = (int64_t)std::max(std::max(std::max(k.f.size(), k.i16.size()), std::max(k.x.size(), k.d.size())), nc_out);
     }
     return SNMF_OK;
+}
+
+extern "C" int snmf_online_batch_process_f32(snmf_online_batch* o, const float* const* pcm, const int64_t* n, const int32_t* flush,
+                                             float* const* xt_f32, int16_t* const* xt_i16, float* const* xh_f32, float* const* dh_f32,
+                                             const int64_t* cap, int64_t* n_out) {
+    return ob_process(o, pcm, n, flush, xt_f32, xt_i16, xh_f32, dh_f32, nullptr, nullptr, cap, n_out);
+}
+
+extern "C" int snmf_online_batch_process_classes_f32(snmf_online_batch* o, const float* const* pcm, const int64_t* n, const int32_t* flush,
+                                                     float* const* xt_f32, int16_t* const* xt_i16, float* const* xh_f32,
+                                                     float* const* dh_f32, float* const* xhi_f32, float* const* dhi_f32,
+                                                     const int64_t* cap, int64_t* n_out) {
+    return ob_process(o, pcm, n, flush, xt_f32, xt_i16, xh_f32, dh_f32, xhi_f32, dhi_f32, cap, n_out);
 }
 
 extern "C" int snmf_online_batch_get_basis_f32(snmf_online_batch* o, int32_t k, float* Bd, int64_t ld) {

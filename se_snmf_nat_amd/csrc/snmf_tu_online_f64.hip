@@ -3,6 +3,7 @@
 // kernels' code does not move.  The snmf_online handle lives in snmf_tu_online.hip; it holds an OnlineF64 and forwards.
 #include "snmf_internal.h"
 #include "snmf_online_f64.h"
+#include "snmf_online_classes.h"
 
 namespace {
 constexpr size_t kTraceCap64 = 1u << 16;  // the newest 65536 frames, as snmf_online_trace
@@ -37,6 +38,11 @@ struct OnlineF64 {
     int16_t* out16 = nullptr;
     int* nit = nullptr;
     OnlineStatus* status = nullptr;
+    // per-class outputs (online_f64_set_classes): n_ev event classes then n_cls - n_ev noise classes; n_cls = 0: none set
+    int n_ev = 0, n_cls = 0;
+    int* cls = nullptr;          // [n_cls + 1] column ranges over [B_x | B_d] (snmf_online_classes.h)
+    double* tail_c = nullptr;    // [n_cls][nov - 1 frames] one overlap-add tail per class
+    double *Xc = nullptr, *syn_c = nullptr, *out_c = nullptr;  // per call, class-major: spectra, synthesis frames, hops
     // host state of the driver loop
     std::vector<double> pending, hist;
     int64_t l = 0;  // frames processed
@@ -45,9 +51,11 @@ struct OnlineF64 {
 };
 
 static void f64_free_call_buffers(OnlineF64* o) {
-    void* ptrs[] = {o->sig, o->Ym, o->Xt, o->Xh, o->Dh, o->syn, o->outf, o->A, o->recon, o->Yph, o->out16, o->nit, o->status};
+    void* ptrs[] = {o->sig, o->Ym, o->Xt, o->Xh, o->Dh, o->syn, o->outf, o->A, o->recon, o->Yph, o->out16, o->nit, o->status,
+                    o->Xc, o->syn_c, o->out_c};
     for (void* q : ptrs)
         if (q) hipFree(q);
+    o->Xc = o->syn_c = o->out_c = nullptr;
     o->sig = o->Ym = o->Xt = o->Xh = o->Dh = o->syn = o->outf = o->A = o->recon = nullptr;
     o->Yph = nullptr;
     o->out16 = nullptr;
@@ -63,7 +71,7 @@ void online_f64_destroy(OnlineF64* o) {
     f64_free_call_buffers(o);
     void* ptrs[] = {o->B, o->Bfix, o->Btmp, o->Wn, o->WnT, o->wn, o->csum, o->H0, o->lambda_dav, o->Xm_tilde, o->r_blk, o->ldblk,
                     o->adblk, o->Vad, o->Had, o->win_s, o->win_i, o->tail, o->tail_x, o->tail_d, o->tw, o->rup, o->w_ind, o->dev,
-                    o->wa_W, o->wa_p1, o->wa_p2, o->wa_nit, o->wa_bar};
+                    o->wa_W, o->wa_p1, o->wa_p2, o->wa_nit, o->wa_bar, o->cls, o->tail_c};
     for (void* q : ptrs)
         if (q) hipFree(q);
     if (o->h_status) hipHostFree(o->h_status);
@@ -173,6 +181,37 @@ int online_f64_create(snmf_ctx* ctx, const snmf_online_params* p, const double* 
     return SNMF_OK;
 }
 
+// snmf_online_set_classes on an fp64 separator (the handle's owner has checked class_outputs)
+int online_f64_set_classes(OnlineF64* o, int32_t event_num, const int32_t* event_rank, int32_t noise_num, const int32_t* noise_rank) {
+    if (o->l != 0 || !o->pending.empty() || o->finished) return fail(SNMF_ERR_STATE, "snmf_online_set_classes must precede the first sample");
+    std::vector<int> cls;
+    SN_TRY(online_class_ranges(event_num, event_rank, noise_num, noise_rank, o->p.R_x, o->p.R_d, &cls));
+    const int nc = event_num + noise_num;
+    HIP_TRY(hipSetDevice(o->ctx->device));
+    hipStream_t st = o->ctx->stream;
+    HIP_TRY(hipStreamSynchronize(st));
+    f64_free_call_buffers(o);  // the class-major call buffers depend on the class count
+    for (void** q : {(void**)&o->cls, (void**)&o->tail_c}) {
+        if (*q) hipFree(*q);
+        *q = nullptr;
+    }
+    o->n_ev = o->n_cls = 0;
+    const size_t ntail = (size_t)std::max(1, o->nov - 1) * o->p.framelength;
+    SN_TRY(dalloc(&o->cls, cls.size()));
+    SN_TRY(dalloc(&o->tail_c, (size_t)nc * ntail));
+    HIP_TRY(hipMemcpyAsync(o->cls, cls.data(), cls.size() * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(o->tail_c, 0, (size_t)nc * ntail * 8, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    o->n_ev = event_num;
+    o->n_cls = nc;
+    return SNMF_OK;
+}
+
+void online_f64_class_counts(OnlineF64* o, int* n_event, int* n_noise) {
+    *n_event = o->n_cls ? o->n_ev : 1;
+    *n_noise = o->n_cls ? o->n_cls - o->n_ev : 1;
+}
+
 static int f64_reserve(OnlineF64* o, int n) {
     if (n <= o->cap_frames) return SNMF_OK;
     hipStreamSynchronize(o->ctx->stream);
@@ -194,6 +233,11 @@ static int f64_reserve(OnlineF64* o, int n) {
     SN_TRY(dalloc(&o->recon, (size_t)cap * 2 * F));
     SN_TRY(dalloc(&o->nit, (size_t)cap));
     SN_TRY(dalloc(&o->status, (size_t)cap));
+    if (o->n_cls) {
+        SN_TRY(dalloc(&o->Xc, (size_t)o->n_cls * F * cap));
+        SN_TRY(dalloc(&o->syn_c, (size_t)o->n_cls * (cap + o->nov - 1) * sz));
+        SN_TRY(dalloc(&o->out_c, (size_t)o->n_cls * cap * hop));
+    }
     o->cap_frames = cap;
     return SNMF_OK;
 }
@@ -243,7 +287,7 @@ static int f64_adapt(OnlineF64* o, int32_t* iters) {
 
 // n frames whose samples are sig = [history | n hops] (host); appends the hops the driver would write
 static int f64_run_frames(OnlineF64* o, const std::vector<double>& sig, int n, std::vector<double>* outf, std::vector<int16_t>* out16,
-                          std::vector<double>* xh, std::vector<double>* dh) {
+                          std::vector<double>* xh, std::vector<double>* dh, std::vector<std::vector<double>>* xc) {
     const snmf_online_params& p = o->p;
     const int F = o->F, r = o->r, sz = p.framelength, hop = p.frameshift, nov = o->nov;
     hipStream_t st = o->ctx->stream;
@@ -294,6 +338,13 @@ static int f64_run_frames(OnlineF64* o, const std::vector<double>& sig, int n, s
         tr.Q_control = hs.Q_control;
         return tr;
     };
+    // the class spectra of `cnt` frames from frame i on (:158-202), behind their solves and before the adaptation (k_oclass64)
+    auto class_spectra = [&](int i, int cnt) -> int {
+        hipLaunchKernelGGL(k_oclass64, dim3((F + 255) / 256, cnt), dim3(256), 0, st, (const double*)o->B, (const double*)(o->A + (size_t)i * r), r,
+                           (const int*)o->cls, o->n_cls, F, cnt, o->Xc + (size_t)i * F, (int64_t)o->cap_frames * F);
+        HIP_TRY(hipGetLastError());
+        return SNMF_OK;
+    };
     auto push = [&](const snmf_online_frame& tr) {
         o->trace.push_back(tr);
         if (o->trace.size() > kTraceCap64) o->trace.pop_front();
@@ -304,6 +355,7 @@ static int f64_run_frames(OnlineF64* o, const std::vector<double>& sig, int n, s
         HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(k_opost64, dim3(1), dim3(1024), lds_post, st, post_args(0, o->l + 1, n), r);
         HIP_TRY(hipGetLastError());
+        if (o->n_cls) SN_TRY(class_spectra(0, n));
         std::vector<OnlineStatus> hst((size_t)n);
         HIP_TRY(hipMemcpyAsync(hst.data(), o->status, (size_t)n * sizeof(OnlineStatus), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
@@ -314,6 +366,7 @@ static int f64_run_frames(OnlineF64* o, const std::vector<double>& sig, int n, s
             HIP_TRY(hipGetLastError());
             hipLaunchKernelGGL(k_opost64, dim3(1), dim3(1024), lds_post, st, post_args(i, o->l + 1 + i, 1), r);
             HIP_TRY(hipGetLastError());
+            if (o->n_cls) SN_TRY(class_spectra(i, 1));
             HIP_TRY(hipMemcpyAsync(o->h_status, o->status + i, sizeof(OnlineStatus), hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
             const OnlineStatus hs = *o->h_status;
@@ -368,17 +421,50 @@ static int f64_run_frames(OnlineF64* o, const std::vector<double>& sig, int n, s
         SN_TRY(synth(o->Xh, xh, nullptr, o->tail_x));
         SN_TRY(synth(o->Dh, dh, nullptr, o->tail_d));
     }
+    if (o->n_cls) {
+        // x_hat_i / d_hat_i (:356-361): the class-major stack, each class through the same inverse STFT and overlap-add on its
+        // own tail; the launches are queued back to back and synchronised once
+        const int nc = o->n_cls;
+        const size_t ntl = (size_t)(nov - 1) * sz, syn_cs = (size_t)(o->cap_frames + nov - 1) * sz, out_cs = (size_t)o->cap_frames * hop;
+        if (nov > 1) HIP_TRY(hipMemcpy2DAsync(o->syn_c, syn_cs * 8, o->tail_c, ntl * 8, ntl * 8, (size_t)nc, hipMemcpyDeviceToDevice, st));
+        for (int c = 0; c < nc; ++c) {
+            OIstft64Args ia{};
+            ia.mag = o->Xc + (size_t)c * o->cap_frames * F; ia.ph = o->Yph; ia.ld = F; ia.n_frames = n; ia.sz = sz; ia.dcb = p.dcbin_back;
+            ia.powv = p.pow; ia.scale = p.overlapscale / (double)o->N; ia.preemph = p.preemph; ia.win = o->win_i; ia.tw = o->tw;
+            ia.syn = o->syn_c + (size_t)c * syn_cs + ntl;
+            int s2 = SNMF_OK;
+            by_logn([&](auto L) {
+                s2 = ensure_dyn_lds(o->ctx->device, (const void*)k_oistft64<decltype(L)::value>, lds_fft);
+                if (s2 == SNMF_OK) hipLaunchKernelGGL(k_oistft64<decltype(L)::value>, dim3(n), dim3(256), lds_fft, st, ia);
+            }, o->N);
+            SN_TRY(s2);
+            HIP_TRY(hipGetLastError());
+            if (n_out <= 0) continue;
+            hipLaunchKernelGGL(k_oola64, dim3(grid_for((size_t)n_out * hop)), dim3(256), 0, st, (const double*)(o->syn_c + (size_t)c * syn_cs), n,
+                               l0, p.delay, sz, hop, nov, i_first, n_out, o->out_c + (size_t)c * out_cs, (int16_t*)nullptr);
+            HIP_TRY(hipGetLastError());
+            if (xc) {
+                std::vector<double>& v = (*xc)[c];
+                const size_t at = v.size();
+                v.resize(at + (size_t)n_out * hop);
+                HIP_TRY(hipMemcpyAsync(v.data() + at, o->out_c + (size_t)c * out_cs, (size_t)n_out * hop * 8, hipMemcpyDeviceToHost, st));
+            }
+        }
+        if (nov > 1)
+            HIP_TRY(hipMemcpy2DAsync(o->tail_c, ntl * 8, o->syn_c + (size_t)n * sz, syn_cs * 8, ntl * 8, (size_t)nc, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
     o->l += n;
     return SNMF_OK;
 }
 
 int online_f64_process(OnlineF64* o, const double* pcm, int64_t n, int flush, double* xt, int16_t* xt_i16, double* xh, double* dh,
-                       int64_t cap, int64_t* n_out) {
+                       double* xhi, double* dhi, int64_t cap, int64_t* n_out) {
     if (n_out) *n_out = 0;
     if (n < 0 || (n > 0 && !pcm)) return fail(SNMF_ERR_INVALID, "pcm is NULL");
     if (o->finished) return fail(SNMF_ERR_STATE, "the stream was flushed; create a new separator");
     if (o->failed) return fail(SNMF_ERR_STATE, "an earlier call failed midway through a batch; the separator state is not reusable, create a new one");
-    if ((xh || dh) && !o->p.class_outputs) return fail(SNMF_ERR_STATE, "class outputs were not requested at creation");
+    if ((xh || dh || xhi || dhi) && !o->p.class_outputs) return fail(SNMF_ERR_STATE, "class outputs were not requested at creation");
     (void)hipGetLastError();  // clean sticky error state, see PLAN_CHECK
     HIP_TRY(hipSetDevice(o->ctx->device));
     const int sz = o->p.framelength, hop = o->p.frameshift;
@@ -386,18 +472,24 @@ int online_f64_process(OnlineF64* o, const double* pcm, int64_t n, int flush, do
     const int64_t nfr = (int64_t)(o->pending.size() / (size_t)hop);
     const int64_t tail_frames = flush ? o->p.delay + 1 : 0;
     const int64_t max_out = (nfr + tail_frames) * hop;
-    if ((xt || xt_i16 || xh || dh) && cap < max_out) {
+    if ((xt || xt_i16 || xh || dh || xhi || dhi) && cap < max_out) {
         o->pending.resize(o->pending.size() - (size_t)n);
         return fail(SNMF_ERR_INVALID, "output capacity %lld < %lld samples", (long long)cap, (long long)max_out);
     }
     std::vector<double> of, ox, od;
     std::vector<int16_t> o16;
+    // class signals: with a partition set they come from the class kernel; without one x_hat / d_hat are the one class per side
+    const bool cls_set = o->n_cls > 0, want_c = cls_set && (xhi || dhi);
+    std::vector<std::vector<double>> oc(want_c ? o->n_cls : 0);
+    std::vector<double>* px = (xh || (xhi && !cls_set)) ? &ox : nullptr;
+    std::vector<double>* pd = (dh || (dhi && !cls_set)) ? &od : nullptr;
+    const int64_t chunk = cls_set ? std::max<int64_t>(64, kChunk64 / o->n_cls) : kChunk64;  // (class-major buffers grow with the classes)
     int64_t done = 0;
     while (done < nfr) {
-        const int nb = (int)std::min(kChunk64, nfr - done);
+        const int nb = (int)std::min(chunk, nfr - done);
         std::vector<double> sig(o->hist);
         sig.insert(sig.end(), o->pending.begin() + done * hop, o->pending.begin() + (done + nb) * hop);
-        if (int rc = f64_run_frames(o, sig, nb, xt ? &of : nullptr, xt_i16 ? &o16 : nullptr, xh ? &ox : nullptr, dh ? &od : nullptr)) {
+        if (int rc = f64_run_frames(o, sig, nb, xt ? &of : nullptr, xt_i16 ? &o16 : nullptr, px, pd, want_c ? &oc : nullptr)) {
             o->failed = true;  // frames of this call were consumed and the device state advanced: never retry on it
             return rc;
         }
@@ -408,7 +500,7 @@ int online_f64_process(OnlineF64* o, const double* pcm, int64_t n, int flush, do
     if (flush) {
         // a partial hop is dropped and delay+1 all-zero frames follow (src/NTF_sep_event_RT.m:69-76)
         std::vector<double> sig((size_t)(sz - hop) + (size_t)tail_frames * hop, 0.0);
-        if (int rc = f64_run_frames(o, sig, (int)tail_frames, xt ? &of : nullptr, xt_i16 ? &o16 : nullptr, xh ? &ox : nullptr, dh ? &od : nullptr)) {
+        if (int rc = f64_run_frames(o, sig, (int)tail_frames, xt ? &of : nullptr, xt_i16 ? &o16 : nullptr, px, pd, want_c ? &oc : nullptr)) {
             o->failed = true;
             return rc;
         }
@@ -419,7 +511,18 @@ int online_f64_process(OnlineF64* o, const double* pcm, int64_t n, int flush, do
     if (xt_i16) std::memcpy(xt_i16, o16.data(), o16.size() * 2);
     if (xh) std::memcpy(xh, ox.data(), ox.size() * 8);
     if (dh) std::memcpy(dh, od.data(), od.size() * 8);
-    if (n_out) *n_out = (int64_t)std::max(std::max(of.size(), o16.size()), std::max(ox.size(), od.size()));
+    size_t nc_out = 0;
+    if (cls_set) {
+        for (int c = 0; c < (int)oc.size(); ++c) {
+            double* dst = c < o->n_ev ? (xhi ? xhi + (size_t)c * cap : nullptr) : (dhi ? dhi + (size_t)(c - o->n_ev) * cap : nullptr);
+            if (dst) std::memcpy(dst, oc[c].data(), oc[c].size() * 8);
+            nc_out = std::max(nc_out, oc[c].size());
+        }
+    } else {
+        if (xhi) std::memcpy(xhi, ox.data(), ox.size() * 8);
+        if (dhi) std::memcpy(dhi, od.data(), od.size() * 8);
+    }
+    if (n_out) *n_out = (int64_t)std::max(std::max(std::max(of.size(), o16.size()), std::max(ox.size(), od.size())), nc_out);
     return SNMF_OK;
 }
 

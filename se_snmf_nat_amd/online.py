@@ -15,6 +15,11 @@ Scope = the configuration the reference ships: blk_len_sep = 1, Splice = 0, one 
 MATLAB's global-RNG draws (rand(r,1) per frame solve, rand(R_a, m_a) in init_buff) are explicit
 arguments `H0` / `Ad_blk0` (default: numpy RandomState(random_seed) stand-ins).
 
+Class outputs: `p.EVENT_RANK` / `p.NOISE_RANK` (optional `p.EVENT_NUM` / `p.NOISE_NUM`; settings/initial_setting_SNMF_NAT.m:40-44)
+cut the two dictionaries into classes of consecutive columns, and with `class_outputs=True` every separator here also
+returns the per-class estimates `x_hat_i` [E, n] / `d_hat_i` [N, n] (src/bnmf_sep_event_RT_IS16.m:158-202, :350-361).  The
+shipped partition -- one class per side -- is x_hat / d_hat themselves and runs nothing extra.
+
 `OnlineSeparator(..., precision="fp64")` is the fp64 mode (snmf_online_create_f64): every array crosses in float64 and every
 step from PCM to the fed-back dictionary runs in fp64 on the device, so the separator holds the fp64 reference's per-frame
 decisions over whole recordings (docs/WIDENING.md, "Parity horizon").  DFT mode and the supervised frame solve only.
@@ -51,6 +56,7 @@ def default_settings():
         blk_sparse=1, P_len_k=60, P_len_l=20, alpha_p=0.4, blk_gap=3,
         ENHANCE_METHOD="MMSE", alpha_eta=0.4, alpha_d=0.6, beta=1.0, beta_max=1000.0,
         cf="kl", sparsity=5, max_iter=100, conv_eps=1e-3, cost_check=1, random_seed=1,
+        EVENT_NUM=1, EVENT_RANK=[1], NOISE_NUM=1, NOISE_RANK=[1],  # :40-44: one class per side
     )
 
 
@@ -83,6 +89,37 @@ def _online_params(p, R_x, R_d, adapt, R_a, m_a, method, class_outputs):
     return q
 
 
+_MAX_CLASSES = 32  # per side (kOClassMax, csrc/snmf_online.h)
+
+
+def _class_partition(p, R_x, R_d):
+    """p.EVENT_RANK / p.NOISE_RANK (1-based class starts, src/bnmf_sep_event_RT_IS16.m:158-163, :180-185) and the optional
+    p.EVENT_NUM / p.NOISE_NUM, checked as snmf_online_set_classes checks them -- SnmfError(1) / (8) before anything reaches
+    the device.  Returns (event starts, noise starts) as int32 arrays, or None for one class per side (also: keys absent)."""
+    sides = []
+    for num_key, rank_key, R in (("EVENT_NUM", "EVENT_RANK", R_x), ("NOISE_NUM", "NOISE_RANK", R_d)):
+        raw = np.asarray(p.get(rank_key, [1])).reshape(-1)
+        if raw.size < 1 or not np.all(np.isfinite(raw.astype(np.float64))) or np.any(raw != np.round(raw)):
+            raise _invalid(f"{rank_key} must hold at least one integer rank")
+        rk = [int(v) for v in raw]
+        for i, v in enumerate(rk):
+            if not 1 <= v <= R:
+                raise _invalid(f"{rank_key}({i + 1}) = {v} outside [1, {R}]")
+            if i and v <= rk[i - 1]:
+                raise _invalid(f"{rank_key} must be strictly ascending")
+        if p.get(num_key) is not None and int(p[num_key]) != len(rk):
+            raise _invalid(f"{num_key} = {p[num_key]} but {rank_key} lists {len(rk)} classes")
+        sides.append(rk)
+    for rank_key, rk in zip(("EVENT_RANK", "NOISE_RANK"), sides):
+        if rk[0] != 1:  # the sum over the classes feeds the gain (:201)
+            raise SnmfError(8, f"{rank_key}(1) = {rk[0]}: the classes must cover the dictionary from column 1")
+        if len(rk) > _MAX_CLASSES:
+            raise SnmfError(8, f"{len(rk)} classes on a side, at most {_MAX_CLASSES}")
+    if len(sides[0]) == 1 and len(sides[1]) == 1:
+        return None
+    return np.array(sides[0], dtype=np.int32), np.array(sides[1], dtype=np.int32)
+
+
 class OnlineSeparator:
     """State `g` of src/init_buff.m + the per-frame function, resident on the GPU."""
 
@@ -105,6 +142,8 @@ class OnlineSeparator:
         method = p.get("ENHANCE_METHOD", "MMSE")
         if method not in ("Wiener", "MMSE"):
             raise ValueError("ENHANCE_METHOD must be 'Wiener' or 'MMSE'")
+        shx, shd = np.shape(B_DFT_x), np.shape(B_DFT_d)
+        self._classes = _class_partition(p, shx[1], shd[1]) if len(shx) == 2 and len(shd) == 2 else None
         self._lib = _lib.load()
         self.ctx = ctx or default_context()
         Bx = np.asfortranarray(B_DFT_x, dtype=dt)
@@ -153,12 +192,17 @@ class OnlineSeparator:
             self.n1 = n1
             _lib.check(self._lib.snmf_online_set_mel(self._h, n1, int(bool(p.get("MelConv", 1))), melmat.ctypes.data, BMx.ctypes.data,
                                                      BMd.ctypes.data))
+        if not self.class_outputs:
+            self._classes = None  # (checked all the same; nothing to return them through)
+        if self._classes is not None:
+            ev, nz = self._classes
+            _lib.check(self._lib.snmf_online_set_classes(self._h, ev.size, ev.ctypes.data, nz.size, nz.ctypes.data))
 
     def process(self, pcm, flush=False):
         """Feed PCM (int16 or int16-valued floats).  Returns a dict with the hops the driver writes for the
         frames completed by this call: 'x_tilde' (int16, what fwrite(...,'int16') stores), 'x_tilde_f'
-        (float, before rounding) and with class_outputs 'x_hat' / 'd_hat'.  The float arrays are float32, or float64
-        with precision="fp64"."""
+        (float, before rounding) and with class_outputs 'x_hat' / 'd_hat' and the per-class 'x_hat_i' [E, n] / 'd_hat_i'
+        [N, n] of p.EVENT_RANK / p.NOISE_RANK.  The float arrays are float32, or float64 with precision="fp64"."""
         dt = self._dt
         x = np.ascontiguousarray(np.asarray(pcm).reshape(-1), dtype=dt)
         cap = (x.size // self.hop + self.delay + 3) * self.hop
@@ -167,13 +211,23 @@ class OnlineSeparator:
         xh = np.zeros(cap, dt) if self.class_outputs else None
         dh = np.zeros(cap, dt) if self.class_outputs else None
         n = C.c_int64()
-        process = self._lib.snmf_online_process_f64 if self.precision == "fp64" else self._lib.snmf_online_process_f32
-        _lib.check(process(
-            self._h, x.ctypes.data if x.size else None, x.size, 1 if flush else 0, of.ctypes.data, o16.ctypes.data,
-            xh.ctypes.data if xh is not None else None, dh.ctypes.data if dh is not None else None, cap, C.byref(n)))
+        f64 = self.precision == "fp64"
+        head = (self._h, x.ctypes.data if x.size else None, x.size, 1 if flush else 0, of.ctypes.data, o16.ctypes.data,
+                xh.ctypes.data if xh is not None else None, dh.ctypes.data if dh is not None else None)
+        if self._classes is None:  # one class per side: exactly the call a separator without classes makes
+            process = self._lib.snmf_online_process_f64 if f64 else self._lib.snmf_online_process_f32
+            _lib.check(process(*head, cap, C.byref(n)))
+        else:
+            xhi, dhi = np.zeros((self._classes[0].size, cap), dt), np.zeros((self._classes[1].size, cap), dt)
+            process = self._lib.snmf_online_process_classes_f64 if f64 else self._lib.snmf_online_process_classes_f32
+            _lib.check(process(*head, xhi.ctypes.data, dhi.ctypes.data, cap, C.byref(n)))
         out = {"x_tilde": o16[:n.value], "x_tilde_f": of[:n.value]}
         if self.class_outputs:
             out["x_hat"], out["d_hat"] = xh[:n.value], dh[:n.value]
+            if self._classes is None:
+                out["x_hat_i"], out["d_hat_i"] = out["x_hat"][None], out["d_hat"][None]
+            else:
+                out["x_hat_i"], out["d_hat_i"] = xhi[:, :n.value], dhi[:, :n.value]
         return out
 
     def basis(self):
@@ -272,7 +326,8 @@ class OnlineBatchSeparator:
     a list of S arrays; `H0` / `Ad_blk0` are lists or arrays stacked along the last axis, by default drawn per stream
     from RandomState(random_seed + k).  B_sep_mode 'DFT', or 'Mel' with `B_Mel_x` (F_order x R_x, shared) and `B_Mel_d`
     (one F_order x R_d array or S of them, like B_DFT_d); the supervised frame solve only (SNMF_ERR_UNSUPPORTED otherwise).
-    In DFT mode the Mel arguments are ignored, as in OnlineSeparator."""
+    In DFT mode the Mel arguments are ignored, as in OnlineSeparator.  p.EVENT_RANK / p.NOISE_RANK: one class partition for
+    all streams (with class_outputs each stream's dict also holds 'x_hat_i' / 'd_hat_i')."""
 
     def __init__(self, B_DFT_x, B_DFT_d, p, n_streams, H0=None, Ad_blk0=None, ctx=None, class_outputs=False, B_Mel_x=None,
                  B_Mel_d=None):
@@ -327,6 +382,7 @@ class OnlineBatchSeparator:
                 raise _invalid(f"B_Mel_x is {BMx.shape}, expected {(n1, R_x)}")
             BMd = _per_stream(B_Mel_d, S, (n1, R_d), "B_Mel_d", "F")
             self.n1 = n1
+        self._classes = _class_partition(p, R_x, R_d)
         self._lib = _lib.load()
         self.ctx = ctx or default_context()
         self.F, self.R_x, self.R_d, self.S = F, R_x, R_d, S
@@ -348,6 +404,11 @@ class OnlineBatchSeparator:
             melmat = np.ascontiguousarray(mel_matrix(p["fs"], self.n1, p["fftlength"], 1.0, p["fs"] / 2).T, dtype=np.float32)  # init_buff.m:46
             _lib.check(self._lib.snmf_online_batch_set_mel(self._h, self.n1, int(bool(p.get("MelConv", 1))), melmat.ctypes.data,
                                                            BMx.ctypes.data, BMd.ctypes.data))
+        if not self.class_outputs:
+            self._classes = None  # (checked all the same; nothing to return them through)
+        if self._classes is not None:  # one partition for all streams
+            ev, nz = self._classes
+            _lib.check(self._lib.snmf_online_batch_set_classes(self._h, ev.size, ev.ctypes.data, nz.size, nz.ctypes.data))
 
     def process(self, pcms, flush=False):
         """Feed every stream: `pcms` is a list of S sample arrays (any may be empty); `flush` a bool for all or a list of
@@ -369,16 +430,25 @@ class OnlineBatchSeparator:
         n = np.array([x.size for x in xs], dtype=np.int64)
         f32 = np.array(fl, dtype=np.int32)
         n_out = np.zeros(S, dtype=np.int64)
-        _lib.check(self._lib.snmf_online_batch_process_f32(
-            self._h, ptrs(xs), n.ctypes.data, f32.ctypes.data, P(*[a.ctypes.data for a in of]), P(*[a.ctypes.data for a in o16]),
-            P(*[a.ctypes.data for a in xh]) if xh else None, P(*[a.ctypes.data for a in dh]) if dh else None, caps.ctypes.data,
-            n_out.ctypes.data))
+        head = (self._h, ptrs(xs), n.ctypes.data, f32.ctypes.data, P(*[a.ctypes.data for a in of]), P(*[a.ctypes.data for a in o16]),
+                P(*[a.ctypes.data for a in xh]) if xh else None, P(*[a.ctypes.data for a in dh]) if dh else None)
+        if self._classes is None:  # one class per side: exactly the call a batch without classes makes
+            _lib.check(self._lib.snmf_online_batch_process_f32(*head, caps.ctypes.data, n_out.ctypes.data))
+        else:
+            xhi = [np.zeros((self._classes[0].size, c), np.float32) for c in caps]
+            dhi = [np.zeros((self._classes[1].size, c), np.float32) for c in caps]
+            _lib.check(self._lib.snmf_online_batch_process_classes_f32(
+                *head, P(*[a.ctypes.data for a in xhi]), P(*[a.ctypes.data for a in dhi]), caps.ctypes.data, n_out.ctypes.data))
         outs = []
         for k in range(S):
             m = int(n_out[k])
             o = {"x_tilde": o16[k][:m], "x_tilde_f": of[k][:m]}
             if self.class_outputs:
                 o["x_hat"], o["d_hat"] = xh[k][:m], dh[k][:m]
+                if self._classes is None:
+                    o["x_hat_i"], o["d_hat_i"] = o["x_hat"][None], o["d_hat"][None]
+                else:
+                    o["x_hat_i"], o["d_hat_i"] = xhi[k][:, :m], dhi[k][:, :m]
             outs.append(o)
         return outs
 
