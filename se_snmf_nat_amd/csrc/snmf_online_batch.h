@@ -1,6 +1,6 @@
 // snmf_online_batch.h -- kernels of the batched online separator (include/snmf.h: snmf_online_batch_*): S independent
 // streams of src/bnmf_sep_event_RT_IS16.m, one set of settings, each stream with its own PCM, noise dictionary and
-// state g (src/init_buff.m:17-42).  The per-frame work is that of snmf_online.h; here every launch covers all streams:
+// state g (src/init_buff.m:17-42).  The per-frame arithmetic is that of snmf_online_common.h; here every launch covers all streams:
 //   k_obstft      framing + STFT of the S x n frames of a chunk (one workgroup per (frame, stream))
 //   k_obmel       B_sep_mode = 'Mel': the normalised Mel features of every (frame, stream), the solve's input
 //   k_hsolve_frame<..., BATCH = true> (snmf_kernels.h) the frame solves, one workgroup per (frame, stream)
@@ -17,9 +17,9 @@
 // the other streams of its batch.
 // In Mel mode (snmf_online_batch_set_mel) the frame solve, the adaptation and the re-assembly run at F_order rows on the
 // per-stream fp64 Mel master [B_Mel_x | B_Mel_d]; B_DFT_d is set on restart and never adapted (src/bnmf_sep_event_RT_IS16.m).
+// Included by snmf_tu_online_batch.hip only.
 #pragma once
-#define SNMF_ONLINE_NO_KERNELS 1  // the device functions of snmf_online.h only (its kernels live in snmf_tu_online.hip)
-#include "snmf_online.h"
+#include "snmf_online_common.h"
 
 namespace snmf {
 
@@ -45,7 +45,7 @@ __global__ __launch_bounds__(256) void k_obstft(OStftArgs a, OBatchFrames b, flo
     const float* src = a.sig + (i < b.nreal[s] ? b.off[s] + (int64_t)i * a.hop : b.zoff[s]);
     const size_t slot = (size_t)i * b.S + s;
     float* om = a.Ym + slot * a.ld;
-    ostft_frame<LOGN>(a, src, om, a.Yph + slot * a.ld, bufA, bufB);
+    ostft_frame<LOGN, float>(a, src, om, a.Yph + slot * a.ld, bufA, bufB);
     if (!PACK) return;
     __syncthreads();
     float* vp = Vp + slot * Fp;
@@ -55,41 +55,19 @@ __global__ __launch_bounds__(256) void k_obstft(OStftArgs a, OBatchFrames b, flo
     }
 }
 
-// :106-120 for every (frame, stream): Ym_Mel = melmat * Ym, normalised to unit norm (+1e-9) and scaled to ||Ym|| -- the
-// arithmetic of k_omel_frame (snmf_online.h), so a stream's features are the single-stream separator's bits -- into Ymel
+// :106-120 for every (frame, stream) (omel_features, so a stream's features are the single-stream separator's bits) into Ymel
 // (the post-filter's, MelConv = 1) and, floored, into the solve input Vp at the plan's Fp stride.  Grid (C, S), 256 threads.
 __global__ __launch_bounds__(256) void k_obmel(const float* __restrict__ Ym, const float* __restrict__ melmat, const int* nfr, int S,
                                                int F, int n1, float* __restrict__ Ymel, float* __restrict__ Vp, int Fp) {
     extern __shared__ float sm[];  // [n1]
     __shared__ float part[4];
-    const int i = blockIdx.x, s = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int i = blockIdx.x, s = blockIdx.y;
     if (i >= nfr[s]) return;
     const size_t slot = (size_t)i * S + s;
-    const float* y = Ym + slot * F;
-    float tn2 = 0.f;
-    for (int f = tid; f < F; f += 256) tn2 = fmaf(y[f], y[f], tn2);
-    tn2 = wave_sum_f(tn2);
-    if (lane == 0) part[w] = tn2;
-    for (int m = w; m < n1; m += 4) {
-        float v = 0.f;
-        for (int f = lane; f < F; f += 64) v = fmaf(melmat[(size_t)m * F + f], y[f], v);
-        v = wave_sum_f(v);
-        if (lane == 0) sm[m] = v;
-    }
-    __syncthreads();
-    const float tn = sqrtf(part[0] + part[1] + part[2] + part[3]);
-    float vn2 = 0.f;
-    for (int m = tid; m < n1; m += 256) vn2 = fmaf(sm[m], sm[m], vn2);
-    vn2 = wave_sum_f(vn2);
-    __syncthreads();
-    if (lane == 0) part[w] = vn2;
-    __syncthreads();
-    const float vn = sqrtf(part[0] + part[1] + part[2] + part[3]);
-    for (int m = tid; m < n1; m += 256) {
-        const float v = (sm[m] / vn + 1e-9f) * tn;
+    omel_features(Ym + slot * F, melmat, F, n1, sm, part, [&](int m, float v) {
         Ymel[slot * n1 + m] = v;
         Vp[slot * Fp + m] = v > kFlr ? v : kFlr;
-    }
+    });
 }
 
 // per-stream strides of the post-filter state (OPostArgs holds stream 0's pointers)
@@ -101,7 +79,7 @@ struct OBatchPost {
                         // come from the frame solve)
 };
 
-// One workgroup per stream: opost_frame (snmf_online.h) on that stream's state, its frames one after the other.
+// One workgroup per stream: opost_frame on that stream's state, its frames one after the other.
 __global__ __launch_bounds__(1024) void k_obpost(OPostArgs a0, OBatchPost b) {
     extern __shared__ float sm[];
     __shared__ double red[16];
@@ -130,12 +108,12 @@ __global__ __launch_bounds__(1024) void k_obpost(OPostArgs a0, OBatchPost b) {
         if (a.Dh_out) a.Dh_out = a0.Dh_out + slot * F;
         a.status = a0.status + slot;
         a.l = b.fr.l0[s] + i;
-        opost_frame(a, sm, red);
+        opost_frame<float>(a, sm, red);
         __syncthreads();  // state written by this frame (global + LDS scratch) is visible to the next
     }
 }
 
-// k_oclass (snmf_online.h) for every stream of a frame step: Xm_hat(c) = B(:, R_c) * A(R_c) (src/bnmf_sep_event_RT_IS16.m:158-202;
+// The class spectra (oclass_dft / oclass_mel, as k_oclass) for every stream of a frame step: Xm_hat(c) = B(:, R_c) * A(R_c) (src/bnmf_sep_event_RT_IS16.m:158-202;
 // MelConv = 1: melmat' * (B_Mel(:, R_c) * A(R_c))) from the stream's fp64 master, rounded to fp32 as the single-stream
 // separator's mirror is, so a stream's class spectra are that separator's.  Slot q's class c goes to out + c*cstride + q*F.
 struct OBatchClassArgs {
@@ -168,21 +146,14 @@ __device__ __forceinline__ bool ob_due(const OnlineStatus* status, const int* nf
     return st.do_solve && st.n_up > 0;
 }
 
-// Mel mode's V of the adaptation solve (:298-303): melmat * lambda_d_blk, column c of stream s's ring into column c of Vm
-// (ring order: k_wadapt_batch reads it as it reads the ring, at F_order rows) for every stream whose adaptation is due.
-// k_oprep_mel's arithmetic.  Grid (m_a, S), 256 threads.
+// Mel mode's V of the adaptation solve (:298-303): melmat * lambda_d_blk (omel_project), column c of stream s's ring into
+// column c of Vm (ring order: k_wadapt_batch reads it as it reads the ring, at F_order rows) for every stream whose
+// adaptation is due.  Grid (m_a, S), 256 threads.
 __global__ __launch_bounds__(256) void k_obprep_mel(const OnlineStatus* status, const int* nfr, int step, int S, const float* __restrict__ ldblk,
                                                     const float* __restrict__ melmat, int F, int n1, int ma, float* __restrict__ Vm) {
-    const int c = blockIdx.x, s = blockIdx.y, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int c = blockIdx.x, s = blockIdx.y;
     if (!ob_due(status, nfr, step, S, s)) return;
-    const float* col = ldblk + ((size_t)s * ma + c) * F;
-    float* out = Vm + ((size_t)s * ma + c) * n1;
-    for (int m = w; m < n1; m += 4) {
-        float v = 0.f;
-        for (int f = lane; f < F; f += 64) v = fmaf(melmat[(size_t)m * F + f], col[f], v);
-        v = wave_sum_f(v);
-        if (lane == 0) out[m] = v;
-    }
+    omel_project(ldblk + ((size_t)s * ma + c) * F, melmat, F, n1, Vm + ((size_t)s * ma + c) * n1);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -258,7 +229,7 @@ __global__ __launch_bounds__(kWbNT) void k_wadapt_batch(WBatchArgs a) {
     float* Vt = a.Vt + (size_t)s * Fb * ma;
     const int oldest = a.dev[s].n_push % ma;
 
-    // ---- load (k_oprep's inputs: rings in time order, rows not in r_up zeroed) + src/sparse_nmf.m:157-169 ----------
+    // ---- load (oprep_elem's inputs: rings in time order, rows not in r_up zeroed) + src/sparse_nmf.m:157-169 ----------
     for (int i = tid; i < Ra * ma; i += kWbNT) {
         const int k = i / ma, t = i - k * ma;
         Hs[i] = rup[k] ? ad[(size_t)((oldest + t) % ma) * Ra + k] : 0.f;
@@ -529,17 +500,9 @@ __global__ __launch_bounds__(256) void k_obassemble(const OnlineStatus* status, 
     if (j >= Ra) {
         src = Bfix + (size_t)s * sfix + (size_t)j * F;
     } else {
-        int n_rem = 0;
-        for (int k = 0; k < Ra; ++k) n_rem += rup[k] ? 0 : 1;
-        const bool want_up = j >= n_rem;
-        int need = want_up ? j - n_rem : j, k = 0;
-        for (; k < Ra; ++k) {
-            if ((rup[k] != 0) == want_up) {
-                if (need == 0) break;
-                --need;
-            }
-        }
-        src = want_up ? Wu + (size_t)s * Ra * F + (size_t)k * F : Bd_old + (size_t)k * F;
+        bool retrained;
+        const int k = oassemble_col(rup, Ra, j, &retrained);
+        src = retrained ? Wu + (size_t)s * Ra * F + (size_t)k * F : Bd_old + (size_t)k * F;
     }
     double* dst = Btmp + (size_t)s * Rd * F + (size_t)j * F;
     for (int f = threadIdx.x; f < F; f += blockDim.x) dst[f] = src[f];
@@ -718,7 +681,7 @@ __global__ __launch_bounds__(256) void k_obistft(OIstftArgs a, const int* nfr, i
     const int i = blockIdx.x, s = blockIdx.y;
     if (i >= nfr[s]) return;
     const size_t slot = (size_t)i * S + s;
-    oistft_frame<LOGN>(a, a.mag + slot * a.ld, a.ph + slot * a.ld, a.syn + (size_t)s * syn_stride + (size_t)(nov - 1 + i) * a.sz, bufA,
+    oistft_frame<LOGN, float>(a, a.mag + slot * a.ld, a.ph + slot * a.ld, a.syn + (size_t)s * syn_stride + (size_t)(nov - 1 + i) * a.sz, bufA,
                        bufB);
 }
 
@@ -734,7 +697,7 @@ __global__ __launch_bounds__(256) void k_obtail(float* syn, float* tail, const i
     }
 }
 
-// k_oola (snmf_online.h) per stream: grid (blocks, S); stream s writes its n_out[s] hops at out_off[s]
+// Overlap-add and int16 output (oola_sample) per stream: grid (blocks, S); stream s writes its n_out[s] hops at out_off[s]
 __global__ __launch_bounds__(256) void k_obola(const float* __restrict__ syn, int64_t syn_stride, OBatchFrames b, const int* i_first,
                                                const int* n_out, const int64_t* out_off, int delay, int sz, int hop, int nov,
                                                float* __restrict__ outf, int16_t* __restrict__ out16) {
@@ -744,20 +707,7 @@ __global__ __launch_bounds__(256) void k_obola(const float* __restrict__ syn, in
     const int l0 = b.l0[s], i0 = i_first[s];
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
         const int j = (int)(e / hop), q0 = (int)(e - (size_t)j * hop);
-        const int i = i0 + j;
-        float acc = 0.f;
-        for (int q = nov - 1; q >= 0; --q) {
-            const int lq = l0 + i - q, off = q * hop + q0;
-            if (lq > delay && lq >= 1 && off < sz) acc += sy[(size_t)(i - q + nov - 1) * sz + off];
-        }
-        const size_t o = (size_t)out_off[s] + e;
-        if (outf) outf[o] = acc;
-        if (out16) {
-            float rr = copysignf(floorf(fabsf(acc) + 0.5f), acc);  // fwrite(..,'int16'): round half away, saturate
-            rr = fminf(fmaxf(rr, -32768.f), 32767.f);
-            if (!(acc == acc)) rr = 0.f;
-            out16[o] = (int16_t)rr;
-        }
+        oola_sample<float>(sy, i0 + j, q0, l0, delay, sz, hop, nov, outf, out16, (size_t)out_off[s] + e);
     }
 }
 

@@ -1,9 +1,23 @@
-// snmf_online_classes.h -- the class partition of the online separators (snmf_online_set_classes /
-// snmf_online_batch_set_classes, include/snmf.h), host side: p.EVENT_NUM / p.EVENT_RANK / p.NOISE_NUM / p.NOISE_RANK of
-// settings/initial_setting_SNMF_NAT.m:40-44 -> the column ranges the class kernels walk (snmf_online.h: oclass_dft).
+// snmf_online_classes.h -- host-side helpers of the online separators: the FFT-size dispatch of their transform kernels, and
+// the class partition (snmf_online_set_classes / snmf_online_batch_set_classes, include/snmf.h): p.EVENT_NUM / p.EVENT_RANK / p.NOISE_NUM / p.NOISE_RANK of
+// settings/initial_setting_SNMF_NAT.m:40-44 -> the column ranges the class kernels walk (snmf_online_common.h: oclass_dft).
 // Shared by snmf_tu_online.hip, snmf_tu_online_f64.hip and snmf_tu_online_batch.hip.
 #pragma once
 #include "snmf_internal.h"
+
+// the transform kernels are templates on LOGN = log2(fftlength), 6 .. 12 (checked at creation): f(integral_constant<int, LOGN>)
+template <typename K>
+static inline void by_logn(K&& f, int N) {
+    switch (N) {
+        case 64: f(std::integral_constant<int, 6>{}); break;
+        case 128: f(std::integral_constant<int, 7>{}); break;
+        case 256: f(std::integral_constant<int, 8>{}); break;
+        case 512: f(std::integral_constant<int, 9>{}); break;
+        case 1024: f(std::integral_constant<int, 10>{}); break;
+        case 2048: f(std::integral_constant<int, 11>{}); break;
+        default: f(std::integral_constant<int, 12>{}); break;
+    }
+}
 
 // Ranks are 1-based starts (src/bnmf_sep_event_RT_IS16.m:158-163, :180-185): event class i covers columns
 // EVENT_RANK(i) .. EVENT_RANK(i+1)-1 of B_x, the last one up to R_x; noise class i the same of B_d.  On success cls holds

@@ -1,122 +1,33 @@
-// snmf_online_f64.h -- the fp64 mode of the single-stream online separator (snmf_online_create_f64, include/snmf.h).
+// snmf_online_f64.h -- the kernels of the fp64 mode of the single-stream online separator (snmf_online_create_f64,
+// include/snmf.h).
 // The online loop is a feedback system (activations -> adapted noise dictionary -> next activations) that amplifies a
 // perturbation about tenfold per 100 frames (docs/WIDENING.md, "Parity horizon"): a path that carries fp32-sized errors
 // leaves the fp64 reference's trajectory after a few hundred frames.  Here every step from PCM to the fed-back state is
 // double: the transforms, the frame solve, the post-filter state, the adaptation solve, the synthesis.  No float sits on
 // that path; float appears only in the diagnostic fields of the 32-byte status.
 //
-// The kernels are fp64 twins of the ones in snmf_online.h (same reference lines, same launch structure), except the
-// frame solve: an fp64 dictionary of 513 x 200 (820 KB) fits neither a CU's LDS nor its registers, so k_hsolve64 streams
-// the L2-resident normalised dictionary -- and a transposed image of it -- through the two matrix-vector products of an
-// iteration, with every vector in LDS.
+// The transforms, the post-filter, the ring preparation, the re-assembly and the overlap-add are the double instantiations
+// of the per-frame steps in snmf_online_common.h (same launch structure as the fp32 kernels of snmf_online.h).  The frame
+// solve is this mode's own: an fp64 dictionary of 513 x 200 (820 KB) fits neither a CU's LDS nor its registers, so k_hsolve64
+// streams the L2-resident normalised dictionary -- and a transposed image of it -- through the two matrix-vector products
+// of an iteration, with every vector in LDS.
 //
-// Host side (snmf_tu_online_f64.hip): an OnlineF64 object behind the snmf_online handle.
+// Host side (snmf_tu_online_f64.hip): an OnlineF64 object behind the snmf_online handle (snmf_online_f64_host.h).
+// Included by snmf_tu_online_f64.hip only.
 #pragma once
+#include "snmf_online_common.h"
 
-#ifndef SNMF_ONLINE_F64_HOST_API_ONLY
-#ifndef SNMF_ONLINE_NO_KERNELS
-#define SNMF_ONLINE_NO_KERNELS 1  // the device functions of snmf_online.h only (its kernels live in snmf_tu_online.hip)
-#endif
-#include "snmf_online.h"
-#endif
-#include "snmf.h"
-
-// ---- host interface between snmf_tu_online.hip (owner of the snmf_online handle) and snmf_tu_online_f64.hip -----------
-struct OnlineF64;
-int online_f64_create(snmf_ctx* ctx, const snmf_online_params* p, const double* Bx, const double* Bd, const double* H0,
-                      const double* Ad0, const double* win_stft, const double* win_istft, OnlineF64** out);
-void online_f64_destroy(OnlineF64* o);
-// xhi / dhi: the class signals (snmf_online_process_classes_f64), class-major at `cap`, or NULL
-int online_f64_process(OnlineF64* o, const double* pcm, int64_t n, int flush, double* xt, int16_t* xt_i16, double* xh, double* dh,
-                       double* xhi, double* dhi, int64_t cap, int64_t* n_out);
-int online_f64_set_classes(OnlineF64* o, int32_t event_num, const int32_t* event_rank, int32_t noise_num, const int32_t* noise_rank);
-void online_f64_class_counts(OnlineF64* o, int* n_event, int* n_noise);  // (1, 1) without a partition
-int online_f64_get_basis(OnlineF64* o, double* Bd, int64_t ld);
-int online_f64_trace(OnlineF64* o, snmf_online_frame* out, int64_t cap, int64_t* n);
-
-#ifndef SNMF_ONLINE_F64_HOST_API_ONLY
 namespace snmf {
 
-// radix-2 Stockham autosort FFT of N = 2^LOGN points held in LDS (fft_lds of snmf_online.h on double2)
+// src/bnmf_sep_event_RT_IS16.m:65-81.  fp64 transforms keep their two buffers in dynamic LDS = 2 N double2 behind
+// ensure_dyn_lds (deliberate: 128 KB at N = 4096 cannot be static)
 template <int LOGN>
-__device__ __forceinline__ double2* fft_lds_d(double2* x, double2* y, const double2* __restrict__ tw) {
-    constexpr int N = 1 << LOGN;
-    for (int l = N / 2, m = 1; l >= 1; l >>= 1, m <<= 1) {
-        const int tstep = N / (2 * l);
-        for (int idx = threadIdx.x; idx < N / 2; idx += blockDim.x) {
-            const int j = idx / m, k = idx - j * m;
-            const double2 c0 = x[k + j * m];
-            const double2 c1 = x[k + j * m + l * m];
-            const double2 w = tw[j * tstep];
-            const double2 d = make_double2(c0.x - c1.x, c0.y - c1.y);
-            y[k + 2 * j * m] = make_double2(c0.x + c1.x, c0.y + c1.y);
-            y[k + 2 * j * m + m] = make_double2(w.x * d.x - w.y * d.y, w.x * d.y + w.y * d.x);
-        }
-        __syncthreads();
-        double2* t = x;
-        x = y;
-        y = t;
-    }
-    return x;
-}
-
-struct OStft64Args {
-    const double* sig;  // [(sz - hop) history | n_frames * hop new samples]; frame i starts at i*hop
-    int sz, hop, dcbin;
-    double preemph;
-    const double* win;
-    const double2* tw;  // fp64 twiddles, computed by the host
-    double powv, floorv;
-    double* Ym;         // column i at Ym + i*ld
-    double2* Yph;       // unit phasor exp(i*angle(Y)) per bin, same layout
-    int64_t ld;
-    int n_frames;
-};
-
-// src/bnmf_sep_event_RT_IS16.m:65-81; dynamic LDS = 2 N double2
-template <int LOGN>
-__global__ __launch_bounds__(256) void k_ostft64(OStft64Args a) {
+__global__ __launch_bounds__(256) void k_ostft64(OStftArgsT<double> a) {
     constexpr int N = 1 << LOGN;
     extern __shared__ __attribute__((aligned(16))) double2 fbuf[];
-    double2* bufA = fbuf;
-    double2* bufB = fbuf + N;
     const int t = blockIdx.x;
     if (t >= a.n_frames) return;
-    const double* s = a.sig + (int64_t)t * a.hop;
-    double* om = a.Ym + (int64_t)t * a.ld;
-    double2* op = a.Yph + (int64_t)t * a.ld;
-    for (int n = threadIdx.x; n < N; n += 256) {
-        double x = 0.0;
-        if (n < a.sz) {
-            const double cur = s[n];
-            const double prev = n > 0 ? s[n - 1] : 0.0;  // filter([1 -preemph],1,y), zero state (:66)
-            x = (cur - a.preemph * prev) * a.win[n];      // :67
-        }
-        bufA[n] = make_double2(x, 0.0);
-    }
-    __syncthreads();
-    const double2* X = fft_lds_d<LOGN>(bufA, bufB, a.tw);
-    for (int f = threadIdx.x; f <= N / 2; f += 256) {
-        const double2 c = X[f];
-        const double mag = hypot(c.x, c.y);
-        double v;
-        if (a.powv == 2.0) v = mag * mag;
-        else if (a.powv == 1.0) v = mag;
-        else v = pow(mag, a.powv);
-        if (f < a.dcbin) v = 0.0;                        // :74
-        om[f] = v + a.floorv;                            // :77
-        op[f] = mag > 0.0 ? make_double2(c.x / mag, c.y / mag) : make_double2(1.0, 0.0);  // angle(0) = 0
-    }
-}
-
-__device__ __forceinline__ double block_max_d(double v, double* red) {
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_down(v, o, 64));  // (fmax skips NaN, as MATLAB's max)
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = red[0];
-    for (int i = 1; i < (int)(blockDim.x >> 6); ++i) s = fmax(s, red[i]);
-    return s;
+    ostft_frame<LOGN, double>(a, a.sig + (int64_t)t * a.hop, a.Ym + (int64_t)t * a.ld, a.Yph + (int64_t)t * a.ld, fbuf, fbuf + N);
 }
 
 // ---- dictionary images of the frame solve ---------------------------------------------------------------------------
@@ -291,243 +202,39 @@ __global__ __launch_bounds__(1024) void k_hsolve64(HSolve64Args a) {
 }
 
 // ---- post-filter -----------------------------------------------------------------------------------------------------
-struct OPost64Args {
-    const double* A;       // [r] activations of this frame
-    const int* n_iter;     // the frame solve's iteration count
-    const double* recon;   // [2][F] B_x*A_x and B_d*A_d
-    const double* Ym;      // [F]
-    double* lambda_dav;    // [F] state
-    double* Xm_tilde;      // [F] state
-    double* r_blk;         // [Pl][F] ring of SNR_local columns
-    double* ldblk;         // [ma][F] ring  lambda_d_blk
-    double* adblk;         // [ma][Ra] ring Ad_blk
-    uint8_t* rup;          // [Ra]
-    OnlineDev* dev;
-    OnlineStatus* status;
-    double* Xt_out;        // [F] G .* Ym of this frame
-    double* Xh_out;        // [F] Xm_hat_sum (may be NULL)
-    double* Dh_out;        // [F] Dm_hat_sum (may be NULL)
-    int F, Rx, Rd, Ra, ma, Pl, Pk, dcbin, gap;
-    int l;                 // 1-based frame index
-    int blk_sparse, adapt, wiener, init_N_len, switch_at;
-    double alpha_p, alpha_eta, alpha_d, beta0, beta_max, Ar_up, flr;
-    int n;                 // frames handled by this launch, one after the other (> 1 only without adaptation)
-};
-
-// opost_frame of snmf_online.h in fp64, DFT mode: src/bnmf_sep_event_RT_IS16.m:158-292 for one frame.
-__device__ __forceinline__ void opost64_frame(const OPost64Args& a, double* sm, double* red) {
-    const int F = a.F, r = a.Rx + a.Rd;
-    double* sA = sm;
-    double* Xs = sA + r;
-    double* Ds = Xs + F;
-    double* Q = Ds + F;
-    double* rs1 = Q + F;
-    double* rs2 = rs1 + F;
-    double* Gs = rs2 + F;
-    const int tid = threadIdx.x, nt = blockDim.x;
-    const int n_push0 = a.dev->n_push, sw0 = a.dev->update_switch;
-    for (int k = tid; k < r; k += nt) sA[k] = a.A[k];
-    for (int f = tid; f < F; f += nt) {
-        Xs[f] = a.recon[f];
-        Ds[f] = a.recon[F + f];
-    }
-    __syncthreads();
-    // A_x_mag, A_d_mag (:228-229)
-    double sx = 0.0, sd = 0.0;
-    for (int k = tid; k < r; k += nt) {
-        if (k < a.Rx) sx += sA[k];
-        else sd += sA[k];
-    }
-    sx = block_sum_d(sx, red);
-    sd = block_sum_d(sd, red);
-    const double A_x_mag = sx / a.Rx, A_d_mag = sd / a.Rd;
-    // ---- src/blk_sparse.m ----
-    if (a.blk_sparse) {
-        double mx = -INFINITY;
-        for (int f = tid; f < F; f += nt) {
-            const double s = Xs[f] / fmax(Ds[f], a.flr);  // :10
-            rs1[f] = s;
-            mx = fmax(mx, s);
-        }
-        mx = block_max_d(mx, red);
-        double* col = a.r_blk + (size_t)((a.l - 1) % a.Pl) * F;  // newest column of the ring (:14)
-        for (int f = tid; f < F; f += nt) {
-            col[f] = rs1[f] / mx;                                 // :12
-            Q[f] = f < a.dcbin ? 0.0 : 0.1;                       // :16
-        }
-        __syncthreads();
-        if (a.l > a.Pl) {
-            for (int f = tid; f < F; f += nt) {
-                double s1 = 0.0, s2 = 0.0;
-                for (int c = 0; c < a.Pl; ++c) {
-                    const double v = a.r_blk[(size_t)c * F + f];
-                    s1 += v;
-                    s2 = fma(v, v, s2);
-                }
-                rs1[f] = s1;
-                rs2[f] = s2;
-            }
-            __syncthreads();
-            const int k2 = a.Pk / 2, gN2 = (a.gap - 1) / 2;
-            const int kfirst = k2 + a.dcbin, klast = F - k2;  // 1-based, :20
-            const int nwin = klast >= kfirst ? (klast - kfirst) / a.gap + 1 : 0;
-            const double sqn = sqrt((double)a.Pl * (double)a.Pk);
-            for (int j = tid; j < nwin; j += nt) {
-                const int k = kfirst + j * a.gap;
-                double l1 = 0.0, l2 = 0.0;
-                for (int row = k - k2; row < k + k2; ++row) {  // 1-based rows k-k2+1 .. k+k2
-                    l1 += rs1[row];
-                    l2 += rs2[row];
-                }
-                Gs[j] = (sqn - l1 / sqrt(l2)) / (sqn - 1.0);   // :26
-            }
-            __syncthreads();
-            if (gN2 >= 1) {
-                // blk_gap >= 3: window k reads Q(k-1), which no other window writes, so the windows are independent
-                for (int j = tid; j < nwin; j += nt) {
-                    const int k = kfirst + j * a.gap;
-                    const double qprev = (k - 2) < a.dcbin ? 0.0 : 0.1;
-                    const double pv = a.alpha_p * qprev + (1.0 - a.alpha_p) * Gs[j];
-                    for (int i = k - gN2 - 1; i <= k + gN2 - 1; ++i) Q[i] = pv;  // :29-30
-                }
-            } else if (tid == 0) {
-                // blk_gap = 1: a genuine first-order recursion along frequency
-                for (int j = 0; j < nwin; ++j) {
-                    const int k = kfirst + j;
-                    Q[k - 1] = a.alpha_p * Q[k - 2] + (1.0 - a.alpha_p) * Gs[j];
-                }
-            }
-            __syncthreads();
-            const double qv = Q[a.Pk + a.dcbin - 1];
-            __syncthreads();
-            for (int f = tid; f < a.Pk - 1; f += nt) Q[f] = qv;  // :32
-            __syncthreads();
-        }
-        for (int f = tid; f < a.dcbin; f += nt) Q[f] = 0.0;      // :36
-    } else {
-        for (int f = tid; f < F; f += nt) Q[f] = 1.0;            // :217
-    }
-    __syncthreads();
-    double qs = 0.0;
-    for (int f = tid; f < F; f += nt) qs += Q[f];
-    qs = block_sum_d(qs, red);
-    const double meanQ = qs / F;
-    // ---- gain (:221-261) ----
-    double beta = 20.0 * log10(A_d_mag / A_x_mag) * a.beta0;  // :230-231
-    if (beta < a.beta0) beta = a.beta0;
-    else if (beta >= a.beta_max) beta = a.beta_max;
-    const bool init = a.l <= a.init_N_len;
-    for (int f = tid; f < F; f += nt) {
-        const double ym = a.Ym[f];
-        double ld = a.l == 1 ? ym : a.lambda_dav[f];                       // :223-225
-        ld = a.alpha_d * ld + (1.0 - a.alpha_d) * Ds[f] * beta;            // :241
-        a.lambda_dav[f] = ld;
-        double G;
-        if (a.wiener) {
-            G = Xs[f] / (Xs[f] + Ds[f]);                                   // :245
-        } else {
-            double eta = (a.alpha_eta * a.Xm_tilde[f] + (1.0 - a.alpha_eta) * Xs[f] * Q[f]) / fmax(ld, a.flr);  // :247
-            eta = fmax(0.0031, eta);                                       // :251
-            G = eta / (eta + 1.0);
-        }
-        G = fmin(G, 1.0);                                                  // :254 (min ignores NaN, as MATLAB's)
-        if (init) G = a.flr;                                               // :256-258
-        Gs[f] = G;
-        const double xt = G * ym;                                          // :260
-        a.Xm_tilde[f] = xt;
-        a.Xt_out[f] = xt;
-        if (a.Xh_out) a.Xh_out[f] = Xs[f];
-        if (a.Dh_out) a.Dh_out[f] = Ds[f];
-    }
-    const double A_x_eff = init ? a.flr : A_x_mag;                         // :258
-    const double Q_control = (1.0 - meanQ) * a.Ar_up;                      // :264
-    const bool trig = a.adapt && (Q_control * A_d_mag > A_x_eff);          // :266
-    int do_solve = 0, n_up = 0;
-    __syncthreads();
-    if (trig) {
-        const int head = n_push0 % a.ma;  // overwrites the oldest column == shift + append (:282,:285)
-        for (int f = tid; f < F; f += nt) {
-            const double ym = a.Ym[f];
-            const double mref = f < a.dcbin ? a.flr : 1.0 - Gs[f];         // :271-272
-            a.ldblk[(size_t)head * F + f] = init ? ym : ym * mref;         // :268-274
-        }
-        for (int k = tid; k < a.Ra; k += nt) a.adblk[(size_t)head * a.Ra + k] = sA[a.Rx + k];
-        __syncthreads();
-        int cnt = 0;
-        for (int k = tid; k < a.Ra; k += nt) {
-            double s = 0.0;
-            for (int c = 0; c < a.ma; ++c) s += a.adblk[(size_t)((head + 1 + c) % a.ma) * a.Ra + k];  // oldest first
-            const bool up = Q_control * (s / a.ma) > A_x_eff;               // :288
-            a.rup[k] = up ? 1 : 0;
-            cnt += up;
-        }
-        n_up = (int)(block_sum_d((double)cnt, red) + 0.5);
-        do_solve = sw0 == a.switch_at;                                     // :294
-        if (tid == 0) {
-            a.dev->n_push = n_push0 + 1;
-            a.dev->update_switch = do_solve ? 1 : sw0 + 1;                 // :343-345
-        }
-    }
-    if (tid == 0) {
-        OnlineStatus s;
-        s.trig = trig;
-        s.do_solve = do_solve;
-        s.n_up = n_up;
-        s.n_iter = *a.n_iter;
-        s.beta = (float)beta;  // (diagnostics)
-        s.A_x_mag = (float)A_x_eff;
-        s.A_d_mag = (float)A_d_mag;
-        s.Q_control = (float)Q_control;
-        *a.status = s;
-    }
-}
-
-// One workgroup; dynamic LDS = (r + 6 F) doubles.  Walks the n frames of a launch in order (k_opost).
-__global__ __launch_bounds__(1024) void k_opost64(OPost64Args a0, int a_stride) {
+// One workgroup; dynamic LDS = (r + 6 F) doubles.  Walks the n frames of a launch in order, as k_opost does.
+__global__ __launch_bounds__(1024) void k_opost64(OPostArgsT<double> a0) {
     extern __shared__ __attribute__((aligned(16))) double sm64[];
     __shared__ double red[16];
     for (int i = 0; i < a0.n; ++i) {
-        OPost64Args a = a0;
-        a.A += (size_t)i * a_stride;
-        a.recon += (size_t)i * 2 * a0.F;
-        a.n_iter += i;
+        OPostArgsT<double> a = a0;
+        a.A += (size_t)i * a0.a_stride;
+        a.recon += (size_t)i * 2 * a0.recon_len;
+        a.hst += i;
         a.Ym += (size_t)i * a0.F;
         a.Xt_out += (size_t)i * a0.F;
         if (a.Xh_out) a.Xh_out += (size_t)i * a0.F;
         if (a.Dh_out) a.Dh_out += (size_t)i * a0.F;
         a.status += i;
         a.l += i;
-        opost64_frame(a, sm64, red);
-        __threadfence_block();
+        opost_frame<double>(a, sm64, red);
+        __threadfence_block();  // (deliberate: this kernel has it, k_opost and k_obpost do not)
         __syncthreads();  // state written by this frame (global + LDS scratch) is visible to the next
     }
 }
 
 // ---- adaptation ------------------------------------------------------------------------------------------------------
-// k_oprep in fp64: V = lambda_d_blk and H = Ad_blk in time order, rows of H not flagged by r_up zeroed, the update mask.
+// The inputs of the adaptation solve (oprep_elem)
 __global__ void k_oprep64(const double* __restrict__ ldblk, const double* __restrict__ adblk, const uint8_t* __restrict__ rup,
                           const OnlineDev* dev, int F, int Ra, int ma, double* __restrict__ Vad, double* __restrict__ Had,
                           uint8_t* __restrict__ w_ind) {
     const int oldest = dev->n_push % ma;
-    const size_t nv = (size_t)F * ma, nh = (size_t)Ra * ma;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv + nh + Ra; i += (size_t)gridDim.x * blockDim.x) {
-        if (i < nv) {
-            const int c = (int)(i / F), f = (int)(i - (size_t)c * F);
-            Vad[i] = ldblk[(size_t)((oldest + c) % ma) * F + f];
-        } else if (i < nv + nh) {
-            const size_t j = i - nv;
-            const int c = (int)(j / Ra), k = (int)(j - (size_t)c * Ra);
-            Had[j] = rup[k] ? adblk[(size_t)((oldest + c) % ma) * Ra + k] : 0.0;
-        } else {
-            const int k = (int)(i - nv - nh);
-            w_ind[k] = rup[k];
-        }
-    }
+    const size_t n = (size_t)F * ma + (size_t)Ra * ma + Ra;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+        oprep_elem<double>(i, oldest, ldblk, adblk, rup, F, Ra, ma, Vad, Had, w_ind);
 }
 
-// k_oassemble without the fp32 mirror: B_DFT_d = [B_d_rem, B_d_tmp, B_d_fix] (:336).  One workgroup per column.
-// (k_oassemble itself is compiled into snmf_tu_online.hip only -- it sits behind SNMF_ONLINE_NO_KERNELS in snmf_online.h -- so
-// the column selection below exists TWICE: a fix to it belongs in both kernels.)
+// The re-assembly of :336 (oassemble_col); this separator keeps no fp32 mirror.  One workgroup per column.
 __global__ void k_oassemble64(const double* __restrict__ Bd_old, const double* __restrict__ Wc, int Fp,
                               const double* __restrict__ Bfix, const uint8_t* __restrict__ rup, int F, int Ra, int Rd,
                               double* __restrict__ Bd_new) {
@@ -537,17 +244,9 @@ __global__ void k_oassemble64(const double* __restrict__ Bd_old, const double* _
     if (j >= Ra) {
         src = Bfix + (size_t)j * F;
     } else {
-        int n_rem = 0;
-        for (int k = 0; k < Ra; ++k) n_rem += rup[k] ? 0 : 1;
-        const bool want_up = j >= n_rem;
-        int need = want_up ? j - n_rem : j, k = 0;
-        for (; k < Ra; ++k) {
-            if ((rup[k] != 0) == want_up) {
-                if (need == 0) break;
-                --need;
-            }
-        }
-        src = want_up ? Wc + (size_t)k * Fp : Bd_old + (size_t)k * F;
+        bool retrained;
+        const int k = oassemble_col(rup, Ra, j, &retrained);
+        src = retrained ? Wc + (size_t)k * Fp : Bd_old + (size_t)k * F;
     }
     for (int f = threadIdx.x; f < F; f += blockDim.x) Bd_new[(size_t)j * F + f] = src[f];
 }
@@ -806,77 +505,24 @@ __global__ __launch_bounds__(256) void k_oclass64(const double* __restrict__ B, 
 }
 
 // ---- synthesis -------------------------------------------------------------------------------------------------------
-struct OIstft64Args {
-    const double* mag;   // column i at mag + i*ld  (magnitude^pow domain)
-    const double2* ph;
-    int64_t ld;
-    int n_frames, sz, dcb;
-    double powv, scale, preemph;  // scale = overlapscale / N
-    const double* win;
-    const double2* tw;
-    double* syn;         // frame i at syn + i*sz
-};
-
 // src/synth_ifft_buff.m:10-28 (+ the overlapscale of src/bnmf_sep_event_RT_IS16.m:363); dynamic LDS = 2 N double2
 template <int LOGN>
-__global__ __launch_bounds__(256) void k_oistft64(OIstft64Args a) {
+__global__ __launch_bounds__(256) void k_oistft64(OIstftArgsT<double> a) {
     constexpr int N = 1 << LOGN;
     extern __shared__ __attribute__((aligned(16))) double2 fbuf[];
-    double2* bufA = fbuf;
-    double2* bufB = fbuf + N;
     const int t = blockIdx.x;
     if (t >= a.n_frames) return;
-    const double* mg = a.mag + (int64_t)t * a.ld;
-    const double2* ph = a.ph + (int64_t)t * a.ld;
-    double* o = a.syn + (int64_t)t * a.sz;
-    // real(ifft(X)) = real(fft(conj(X)))/N with X(N-k) = conj(X(k)) for k = 1..N/2-1 (:16-18)
-    for (int k = threadIdx.x; k < N; k += 256) {
-        const int kk = k <= N / 2 ? k : N - k;
-        double m = kk < a.dcb ? 0.0 : mg[kk];                   // :10
-        if (a.powv == 2.0) m = sqrt(m);                         // :11
-        else if (a.powv != 1.0) m = pow(m, 1.0 / a.powv);
-        const double2 p = ph[kk];
-        bufA[k] = make_double2(m * p.x, k <= N / 2 ? -m * p.y : m * p.y);
-    }
-    __syncthreads();
-    double2* X = fft_lds_d<LOGN>(bufA, bufB, a.tw);
-    if (a.preemph == 0.0) {
-        for (int n = threadIdx.x; n < a.sz; n += 256) o[n] = X[n].x * a.scale * a.win[n];  // :19-24
-    } else {
-        for (int n = threadIdx.x; n < a.sz; n += 256) X[n].y = X[n].x * a.scale * a.win[n];
-        __syncthreads();
-        if (threadIdx.x == 0) {  // filter(1, [1 -preemph], .) (:26)
-            double acc = 0.0;
-            for (int n = 0; n < a.sz; ++n) {
-                acc = X[n].y + a.preemph * acc;
-                o[n] = acc;
-            }
-        }
-    }
+    oistft_frame<LOGN, double>(a, a.mag + (int64_t)t * a.ld, a.ph + (int64_t)t * a.ld, a.syn + (int64_t)t * a.sz, fbuf, fbuf + N);
 }
 
-// k_oola in fp64: overlap-add of src/NTF_sep_event_RT.m:104-124 in closed form, oldest frame first; the int16 stream is
-// the fp64 value rounded half away from zero (fwrite(..,'int16')).
+// Overlap-add (oola_sample); the int16 stream is the fp64 value rounded
 __global__ void k_oola64(const double* __restrict__ syn, int n_new, int l0, int delay, int sz, int hop, int nov, int i_first,
                          int n_out, double* __restrict__ outf, int16_t* __restrict__ out16) {
     const size_t n = (size_t)n_out * hop;
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
         const int j = (int)(e / hop), s = (int)(e - (size_t)j * hop);
-        const int i = i_first + j;  // index among the new frames; global frame l = l0 + i
-        double acc = 0.0;
-        for (int q = nov - 1; q >= 0; --q) {
-            const int lq = l0 + i - q, off = q * hop + s;
-            if (lq > delay && lq >= 1 && off < sz) acc += syn[(size_t)(i - q + nov - 1) * sz + off];
-        }
-        if (outf) outf[e] = acc;
-        if (out16) {
-            double rr = copysign(floor(fabs(acc) + 0.5), acc);  // round half away, saturate
-            rr = fmin(fmax(rr, -32768.0), 32767.0);
-            if (!(acc == acc)) rr = 0.0;  // NaN -> 0 as MATLAB's integer conversion
-            out16[e] = (int16_t)rr;
-        }
+        oola_sample<double>(syn, i_first + j, s, l0, delay, sz, hop, nov, outf, out16, e);  // global frame l = l0 + i_first + j
     }
 }
 
 }  // namespace snmf
-#endif  // SNMF_ONLINE_F64_HOST_API_ONLY

@@ -1,4 +1,4 @@
-// snmf_tu_online.hip -- the online separation loop behind the C ABI (snmf_online_*), kernels in snmf_online.h (snmf_internal.h).
+// snmf_tu_online.hip -- the online separation loop behind the C ABI (snmf_online_*), kernels in snmf_online.h, the per-frame arithmetic in snmf_online_common.h.
 #include "snmf_internal.h"
 
 // ---- online separation loop (include/snmf.h: snmf_online_*) -------------------------------------
@@ -6,8 +6,7 @@
 // host only sequences launches: per frame it reads one 32-byte status (did the adaptation condition
 // fire?) and, when it did, runs the W-only adaptation solve through the engine's ordinary plan.
 #include "snmf_online.h"
-#define SNMF_ONLINE_F64_HOST_API_ONLY 1  // the fp64 mode's host entry points (its kernels live in snmf_tu_online_f64.hip)
-#include "snmf_online_f64.h"
+#include "snmf_online_f64_host.h"  // the fp64 mode's host entry points (its kernels live in snmf_tu_online_f64.hip)
 #include "snmf_online_classes.h"
 
 constexpr size_t kTraceCap = 1u << 16;  // diagnostics ring: the newest 65536 frames (~11 min at 100 frames/s)
@@ -418,19 +417,6 @@ static int online_reserve(snmf_online* o, int n) {
     return SNMF_OK;
 }
 
-template <typename K>
-static void launch_by_logn(K&& f, int N) {
-    switch (N) {
-        case 64: f(std::integral_constant<int, 6>{}); break;
-        case 128: f(std::integral_constant<int, 7>{}); break;
-        case 256: f(std::integral_constant<int, 8>{}); break;
-        case 512: f(std::integral_constant<int, 9>{}); break;
-        case 1024: f(std::integral_constant<int, 10>{}); break;
-        case 2048: f(std::integral_constant<int, 11>{}); break;
-        default: f(std::integral_constant<int, 12>{}); break;
-    }
-}
-
 // the frame solve (:148-154): V = Ym (device), W resident, H0 the fixed start; leaves A in hp->H[0]
 static int online_solve_frame(snmf_online* o, const float* dV, const float** A_out, const DevState** st_out, const float** recon_out) {
     hipStream_t st = o->ctx->stream;
@@ -572,7 +558,7 @@ static int online_run_frames(snmf_online* o, const std::vector<float>& sig, int 
     OStftArgs sa{};
     sa.sig = o->sig; sa.sz = sz; sa.hop = hop; sa.dcbin = p.dcbin; sa.preemph = (float)p.preemph; sa.win = o->win_s; sa.tw = o->tw;
     sa.powv = (float)p.pow; sa.floorv = (float)p.nonzerofloor; sa.Ym = o->Ym; sa.Yph = o->Yph; sa.ld = F; sa.n_frames = n;
-    launch_by_logn([&](auto L) { hipLaunchKernelGGL(k_ostft<decltype(L)::value>, dim3(n), dim3(256), 0, st, sa); }, o->N);
+    by_logn([&](auto L) { hipLaunchKernelGGL(k_ostft<decltype(L)::value>, dim3(n), dim3(256), 0, st, sa); }, o->N);
     HIP_TRY(hipGetLastError());
     if (o->mel) {
         hipLaunchKernelGGL(k_omel_frame, dim3(n), dim3(256), (size_t)(o->n1 + 2) * 4, st, (const float*)o->Ym, (const float*)o->melmat, F, o->n1, n,
@@ -671,7 +657,7 @@ static int online_run_frames(snmf_online* o, const std::vector<float>& sig, int 
         ia.mag = mag; ia.ph = o->Yph; ia.ld = F; ia.n_frames = n; ia.sz = sz; ia.dcb = p.dcbin_back; ia.powv = (float)p.pow;
         ia.scale = (float)(p.overlapscale / (double)o->N); ia.preemph = (float)p.preemph; ia.win = o->win_i; ia.tw = o->tw;
         ia.syn = o->syn + (size_t)(nov - 1) * sz;
-        launch_by_logn([&](auto L) { hipLaunchKernelGGL(k_oistft<decltype(L)::value>, dim3(n), dim3(256), 0, st, ia); }, o->N);
+        by_logn([&](auto L) { hipLaunchKernelGGL(k_oistft<decltype(L)::value>, dim3(n), dim3(256), 0, st, ia); }, o->N);
         HIP_TRY(hipGetLastError());
         if (n_out > 0) {
             hipLaunchKernelGGL(k_oola, dim3(grid_for((size_t)n_out * hop)), dim3(256), 0, st, (const float*)o->syn, n, l0, p.delay, sz, hop, nov,
@@ -709,7 +695,7 @@ static int online_run_frames(snmf_online* o, const std::vector<float>& sig, int 
         ia.scale = (float)(p.overlapscale / (double)o->N); ia.preemph = (float)p.preemph; ia.win = o->win_i; ia.tw = o->tw;
         ia.syn = o->syn_c + ntl;
         const int64_t mag_cs = (int64_t)o->cap_frames * F;
-        launch_by_logn([&](auto L) { hipLaunchKernelGGL(k_oistft_cls<decltype(L)::value>, dim3(n, nc), dim3(256), 0, st, ia, mag_cs, (int64_t)syn_cs); },
+        by_logn([&](auto L) { hipLaunchKernelGGL(k_oistft_cls<decltype(L)::value>, dim3(n, nc), dim3(256), 0, st, ia, mag_cs, (int64_t)syn_cs); },
                        o->N);
         HIP_TRY(hipGetLastError());
         for (int c = 0; c < nc && n_out > 0; ++c) {

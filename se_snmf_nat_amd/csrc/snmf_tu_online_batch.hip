@@ -407,19 +407,6 @@ static int ob_reserve(snmf_online_batch* o, int C, size_t n_sig, size_t n_out) {
     return SNMF_OK;
 }
 
-template <typename K>
-static void ob_by_logn(K&& f, int N) {
-    switch (N) {
-        case 64: f(std::integral_constant<int, 6>{}); break;
-        case 128: f(std::integral_constant<int, 7>{}); break;
-        case 256: f(std::integral_constant<int, 8>{}); break;
-        case 512: f(std::integral_constant<int, 9>{}); break;
-        case 1024: f(std::integral_constant<int, 10>{}); break;
-        case 2048: f(std::integral_constant<int, 11>{}); break;
-        default: f(std::integral_constant<int, 12>{}); break;
-    }
-}
-
 // the frame solves of `nf` frames per stream (slots [step * S, (step + nf) * S)), one workgroup per (frame, stream)
 static int ob_frame_solve(snmf_online_batch* o, int step, int nf) {
     snmf_plan* pl = o->hp;
@@ -581,10 +568,10 @@ static int ob_run_chunk(snmf_online_batch* o, const std::vector<int>& nfr, const
     sa.sig = o->sig; sa.sz = sz; sa.hop = hop; sa.dcbin = p.dcbin; sa.preemph = (float)p.preemph; sa.win = o->win_s; sa.tw = o->tw;
     sa.powv = (float)p.pow; sa.floorv = (float)p.nonzerofloor; sa.Ym = o->Ym; sa.Yph = o->Yph; sa.ld = F; sa.n_frames = C;
     if (!o->mel) {
-        ob_by_logn([&](auto L) { hipLaunchKernelGGL(k_obstft<decltype(L)::value>, dim3(C, S), dim3(256), 0, st, sa, fr, o->Vp, o->hp->Fp); }, o->N);
+        by_logn([&](auto L) { hipLaunchKernelGGL(k_obstft<decltype(L)::value>, dim3(C, S), dim3(256), 0, st, sa, fr, o->Vp, o->hp->Fp); }, o->N);
         HIP_TRY(hipGetLastError());
     } else {  // the solve input is the Mel features (:106-120)
-        ob_by_logn([&](auto L) { hipLaunchKernelGGL((k_obstft<decltype(L)::value, false>), dim3(C, S), dim3(256), 0, st, sa, fr, o->Vp, o->hp->Fp); },
+        by_logn([&](auto L) { hipLaunchKernelGGL((k_obstft<decltype(L)::value, false>), dim3(C, S), dim3(256), 0, st, sa, fr, o->Vp, o->hp->Fp); },
                    o->N);
         HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(k_obmel, dim3(C, S), dim3(256), (size_t)o->n1 * 4, st, (const float*)o->Ym, (const float*)o->melmat, fr.nfr, S, F,
@@ -639,7 +626,7 @@ static int ob_run_chunk(snmf_online_batch* o, const std::vector<int>& nfr, const
         OIstftArgs ia{};
         ia.mag = mag; ia.ph = o->Yph; ia.ld = F; ia.n_frames = C; ia.sz = sz; ia.dcb = p.dcbin_back; ia.powv = (float)p.pow;
         ia.scale = (float)(p.overlapscale / (double)o->N); ia.preemph = (float)p.preemph; ia.win = o->win_i; ia.tw = o->tw; ia.syn = o->syn;
-        ob_by_logn([&](auto L) { hipLaunchKernelGGL(k_obistft<decltype(L)::value>, dim3(C, S), dim3(256), 0, st, ia, fr.nfr, S, syn_stride, nov); },
+        by_logn([&](auto L) { hipLaunchKernelGGL(k_obistft<decltype(L)::value>, dim3(C, S), dim3(256), 0, st, ia, fr.nfr, S, syn_stride, nov); },
                    o->N);
         HIP_TRY(hipGetLastError());
         if (n_out > 0) {

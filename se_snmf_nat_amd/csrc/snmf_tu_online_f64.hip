@@ -3,6 +3,7 @@
 // kernels' code does not move.  The snmf_online handle lives in snmf_tu_online.hip; it holds an OnlineF64 and forwards.
 #include "snmf_internal.h"
 #include "snmf_online_f64.h"
+#include "snmf_online_f64_host.h"
 #include "snmf_online_classes.h"
 
 namespace {
@@ -242,19 +243,6 @@ static int f64_reserve(OnlineF64* o, int n) {
     return SNMF_OK;
 }
 
-template <typename K>
-static void by_logn(K&& f, int N) {
-    switch (N) {
-        case 64: f(std::integral_constant<int, 6>{}); break;
-        case 128: f(std::integral_constant<int, 7>{}); break;
-        case 256: f(std::integral_constant<int, 8>{}); break;
-        case 512: f(std::integral_constant<int, 9>{}); break;
-        case 1024: f(std::integral_constant<int, 10>{}); break;
-        case 2048: f(std::integral_constant<int, 11>{}); break;
-        default: f(std::integral_constant<int, 12>{}); break;
-    }
-}
-
 // :296-336 once the status says the solve is due
 static int f64_adapt(OnlineF64* o, int32_t* iters) {
     const snmf_online_params& p = o->p;
@@ -294,7 +282,7 @@ static int f64_run_frames(OnlineF64* o, const std::vector<double>& sig, int n, s
     SN_TRY(f64_reserve(o, n));
     HIP_TRY(hipMemcpyAsync(o->sig, sig.data(), sig.size() * 8, hipMemcpyHostToDevice, st));
     const size_t lds_fft = (size_t)2 * o->N * sizeof(double2);
-    OStft64Args sa{};
+    OStftArgsT<double> sa{};
     sa.sig = o->sig; sa.sz = sz; sa.hop = hop; sa.dcbin = p.dcbin; sa.preemph = p.preemph; sa.win = o->win_s; sa.tw = o->tw;
     sa.powv = p.pow; sa.floorv = p.nonzerofloor; sa.Ym = o->Ym; sa.Yph = o->Yph; sa.ld = F; sa.n_frames = n;
     int s = SNMF_OK;
@@ -316,8 +304,8 @@ static int f64_run_frames(OnlineF64* o, const std::vector<double>& sig, int n, s
         return h;
     };
     auto post_args = [&](int i, int64_t l, int cnt) {
-        OPost64Args a{};
-        a.A = o->A + (size_t)i * r; a.n_iter = o->nit + i; a.recon = o->recon + (size_t)i * 2 * F; a.Ym = o->Ym + (size_t)i * F;
+        OPostArgsT<double> a{};
+        a.A = o->A + (size_t)i * r; a.hst = o->nit + i; a.recon = o->recon + (size_t)i * 2 * F; a.Ym = o->Ym + (size_t)i * F;
         a.lambda_dav = o->lambda_dav; a.Xm_tilde = o->Xm_tilde; a.r_blk = o->r_blk; a.ldblk = o->ldblk; a.adblk = o->adblk;
         a.rup = o->rup; a.dev = o->dev; a.status = o->status + i;
         a.Xt_out = o->Xt + (size_t)i * F;
@@ -329,7 +317,7 @@ static int f64_run_frames(OnlineF64* o, const std::vector<double>& sig, int n, s
         a.switch_at = (int)std::floor(p.overlap_m_a * p.m_a);
         a.alpha_p = p.alpha_p; a.alpha_eta = p.alpha_eta; a.alpha_d = p.alpha_d; a.beta0 = p.beta; a.beta_max = p.beta_max; a.Ar_up = p.Ar_up;
         a.flr = p.nonzerofloor;
-        a.n = cnt;
+        a.n = cnt; a.a_stride = r; a.recon_len = F;
         return a;
     };
     auto record = [&](const OnlineStatus& hs) -> snmf_online_frame {
@@ -353,7 +341,7 @@ static int f64_run_frames(OnlineF64* o, const std::vector<double>& sig, int n, s
         // Fixed dictionary: the frame solves of the batch as one grid, then one k_opost64 launch walks the recurrences.
         hipLaunchKernelGGL(k_hsolve64, dim3(n), dim3(1024), lds_solve, st, solve_args(0, n));
         HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_opost64, dim3(1), dim3(1024), lds_post, st, post_args(0, o->l + 1, n), r);
+        hipLaunchKernelGGL(k_opost64, dim3(1), dim3(1024), lds_post, st, post_args(0, o->l + 1, n));
         HIP_TRY(hipGetLastError());
         if (o->n_cls) SN_TRY(class_spectra(0, n));
         std::vector<OnlineStatus> hst((size_t)n);
@@ -364,7 +352,7 @@ static int f64_run_frames(OnlineF64* o, const std::vector<double>& sig, int n, s
         for (int i = 0; i < n; ++i) {
             hipLaunchKernelGGL(k_hsolve64, dim3(1), dim3(1024), lds_solve, st, solve_args(i, 1));
             HIP_TRY(hipGetLastError());
-            hipLaunchKernelGGL(k_opost64, dim3(1), dim3(1024), lds_post, st, post_args(i, o->l + 1 + i, 1), r);
+            hipLaunchKernelGGL(k_opost64, dim3(1), dim3(1024), lds_post, st, post_args(i, o->l + 1 + i, 1));
             HIP_TRY(hipGetLastError());
             if (o->n_cls) SN_TRY(class_spectra(i, 1));
             HIP_TRY(hipMemcpyAsync(o->h_status, o->status + i, sizeof(OnlineStatus), hipMemcpyDeviceToHost, st));
@@ -386,7 +374,7 @@ static int f64_run_frames(OnlineF64* o, const std::vector<double>& sig, int n, s
     const int n_out = std::max(0, n - i_first);
     auto synth = [&](const double* mag, std::vector<double>* of, std::vector<int16_t>* o16, double* tail) -> int {
         if (nov > 1) HIP_TRY(hipMemcpyAsync(o->syn, tail, (size_t)(nov - 1) * sz * 8, hipMemcpyDeviceToDevice, st));
-        OIstft64Args ia{};
+        OIstftArgsT<double> ia{};
         ia.mag = mag; ia.ph = o->Yph; ia.ld = F; ia.n_frames = n; ia.sz = sz; ia.dcb = p.dcbin_back; ia.powv = p.pow;
         ia.scale = p.overlapscale / (double)o->N; ia.preemph = p.preemph; ia.win = o->win_i; ia.tw = o->tw;
         ia.syn = o->syn + (size_t)(nov - 1) * sz;
@@ -428,7 +416,7 @@ static int f64_run_frames(OnlineF64* o, const std::vector<double>& sig, int n, s
         const size_t ntl = (size_t)(nov - 1) * sz, syn_cs = (size_t)(o->cap_frames + nov - 1) * sz, out_cs = (size_t)o->cap_frames * hop;
         if (nov > 1) HIP_TRY(hipMemcpy2DAsync(o->syn_c, syn_cs * 8, o->tail_c, ntl * 8, ntl * 8, (size_t)nc, hipMemcpyDeviceToDevice, st));
         for (int c = 0; c < nc; ++c) {
-            OIstft64Args ia{};
+            OIstftArgsT<double> ia{};
             ia.mag = o->Xc + (size_t)c * o->cap_frames * F; ia.ph = o->Yph; ia.ld = F; ia.n_frames = n; ia.sz = sz; ia.dcb = p.dcbin_back;
             ia.powv = p.pow; ia.scale = p.overlapscale / (double)o->N; ia.preemph = p.preemph; ia.win = o->win_i; ia.tw = o->tw;
             ia.syn = o->syn_c + (size_t)c * syn_cs + ntl;
