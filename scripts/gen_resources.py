@@ -23,7 +23,8 @@ OUT = os.path.join(ROOT, "profiles", f"{TAG}_resources.csv")
 LAUNCHED = [
     ("snmf::k_hstep_rp<true, false>", "C2 257x100000 r=256 KL (headline): H step, iterations with the objective"),
     ("snmf::k_hstep_rp<false, false>", "C2: H step of iteration 1 / cost_check = 0"),
-    ("snmf::k_wstats<8, 4, 4, 2, 0, 1, false, 32, 0>", "C2: W statistics (full update: the objective rides on the H step)"),
+    ("snmf::k_wstats_xg<8, 4, 4, 2, 0, 1, false>", "C2: W statistics (full update: the objective rides on the H step; extra row behind P3's first W loads)"),
+    ("snmf::k_wstats<8, 4, 4, 2, 0, 1, false, 32, 0>", "C2 with SNMF_WSTATS_XG=0 / four row groups at 128 < r <= 256: W statistics, extra row at the tile top"),
     ("snmf::k_wfin<1>", "C2 / a11 / C4 W-only: chunk reduction + W update (snmf_plan_run)"),
     ("snmf::k_hstep_rh<true, 1>", "a11 513x72000 r=100 KL full (run_basis_train.m:88): H step"),
     ("snmf::k_wstats<4, 8, 4, 3, 0, 1, false, 32, 1>", "a11: W statistics"),

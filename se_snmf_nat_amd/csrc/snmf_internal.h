@@ -148,6 +148,8 @@ struct PlanGeometry {
     size_t lds_sr = 0, lds_wsr = 0;
     int til = 1;  // k_wstats: consumer teams that share a chunk's tiles (StepArgs::til)
     int n_ch1 = 0;  // k_wstats: chunks of row group 1 when the two row groups are split unevenly (else 0)
+    bool wxg_off = false;  // ... a plan of that shape with the switch off (describe() names it)
+    bool wxg = false;  // k_wstats_xg: the extra row (F = 32n+1) runs behind P3's first W-fragment loads (SNMF_WSTATS_XG=0: at the top of the tile)
     // beta = 2, r > 256: the V*H^T launch (needs no Lam') runs the loader-wave geometry <8,4,4,2> once per 256-column
     // kappa-group, each staging only its own columns of H (kq_chunks frame chunks, kq_kg kappa-groups; 0 = off)
     int kq_chunks = 0, kq_kg = 0;

@@ -1116,13 +1116,14 @@ __global__ __launch_bounds__((NW + NL) * 64, (NL > 0 ? 3 : 2)) void k_hstep(Step
 // MFMA waves of a SIMD share the pipe and therefore leave their loops together; if P2 of the next tile could only start
 // after the A team's whole epilogue (and the extra row), nobody would issue an MFMA through all of it.  Hence P2 in
 // phases: the first 4*NA k-blocks need only the ratio rows of the row tiles 0..NA-1, the rest every row tile, and only
-// the very last k-block the extra row, which the A team computes after everything else.
+// the FMAs in front of the epilogue (rp_p2_xrow; CUT and the split round's parts: the very last k-block) the extra row,
+// which the A team computes after everything else.
 // No workgroup barrier inside the tile loop: six signals, each four per-wave progress words in LDS, order the roles
 //     ready  (loaders)   "the H block of tile j is staged"           A waits (loop), and the loaders' extra-row pass
 //     vready (loaders)   "the V block of tile j is staged"           A waits (epilogues), and the extra-row pass
 //     p1a    (A team)    "ratio rows of the row tiles 0..NA-1 whole"  B waits (phase 1)
 //     p1b    (A team)    "every ratio row tile is whole"              B waits (phase 2)
-//     xdone  (A team)    "the extra row of the ratio image is done"   B waits (last k-block)
+//     xdone  (A team)    "the extra row of the ratio image is done"   B waits (in front of its epilogue; CUT: last k-block)
 //     p2done (B team)    "H_j is updated, its ratio dead"             loaders wait
 // (dependencies run strictly forward in the tile index, so the waits cannot form a cycle; every wait is a bounded spin
 // that raises DevState::fault instead of hanging).  Each wave owns TWO 32-row (A) / 32-column (B) output tiles whose
@@ -1321,6 +1322,22 @@ __device__ __forceinline__ void rp_p1_epilogue(const StepArgs& a, const f32x16& 
                                                float& dsum) {
     if (!OBJ || (phi * 32 + 32 <= a.F && t0 + 32 <= a.T)) rp_p1_epilogue_t<OBJ, false>(a, acc, Rs, phi, t0, lane, dsum);
     else rp_p1_epilogue_t<OBJ, true>(a, acc, Rs, phi, t0, lane, dsum);
+}
+
+// The extra row's (F = 32n+1) term of one 32-column tile of W^T*ratio, on the VALU: acc[4g+j] += W[Fm][32 kap + 8g + 4h + j] *
+// ratio[Fm][t].  As a k-block of the contraction the row was cell 0 of an 8-deep block whose other seven cells are zero: a
+// pipeline refill and 4 MFMAs per tile of which one multiplied a non-zero operand.  The f32 MFMA accumulates as an ordered fma
+// chain (k = lane half 0, then 1) and the row's block was the chain's last link, so one fmaf per accumulator here gives the same
+// bits (the other links added +0): tests/test_gpu_pipelined_vs_plain.py holds k_hstep_rp to k_hstep bit for bit.
+//   wx4: the extra row of W in LDS at this lane's first column (32 kap + 4 h; the same fp32 values k_wfin writes into the Wk4
+//   image), rx: the row's ratio for this lane's frame.
+__device__ __forceinline__ void rp_p2_xrow(f32x16& acc, const float* wx4, float rx) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const f32x4 wv = *reinterpret_cast<const f32x4*>(wx4 + 8 * g);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[4 * g + j] = __builtin_fmaf(wv[j], rx, acc[4 * g + j]);
+    }
 }
 
 // P2 epilogue of one 32-column tile of W^T*ratio: H <- H .* dmh ./ dph in LDS (src/sparse_nmf.m:192-195).
@@ -1739,7 +1756,7 @@ __global__ __launch_bounds__(768, 3) void k_hstep_rp(StepArgs a) {
     // p1a: "the ratio rows of the row tiles 0..NA-1 are whole" (each A wave after the epilogue of its FIRST row tile);
     // p1b: "every row tile is" (each A wave after its last epilogue); xdone: "the extra row is" (each A wave after its
     // share of it).  The B team starts P2 on the first 4*NA k-blocks (rows
-    // 0..32*NA-1) at p1a, needs p1b for the rest and xdone for the extra row's k-block only: in steady state both teams
+    // 0..32*NA-1) at p1a, needs p1b for the rest and xdone for the extra row's term only: in steady state both teams
     // leave their MFMA loops together (they share the pipe), and the A team's epilogue is then the one stretch with nobody
     // in a loop -- B waits for half of it only.  Every signal is four per-wave progress words (rp_post / rp_await), so
     // each has a single kind of producer and a wave that runs ahead cannot stand in for one that lags.
@@ -2236,7 +2253,7 @@ __global__ __launch_bounds__(768, 3) void k_hstep_rp(StepArgs a) {
             float shsum = 0.f;
             // k-blocks over the ratio rows of the row tiles 0..NA-1 (never the extra row's block) / the rest
             const int nq = a.Fq / 8, nq1 = 4 * (a.nf < NA ? a.nf : NA);
-            const int nqm = a.xr ? nq - 1 : nq;  // k-blocks over the ratio rows proper; the extra row's is a phase of its own, gated by xdone
+            const int nqm = a.xr ? nq - 1 : nq;  // k-blocks over the ratio rows proper; the extra row's term is added on the VALU behind xdone
             auto gate_p1b = [&]() { rp_await(p1b, (unsigned)(j + 1), a.stop); };
             auto gate_x = [&]() { rp_await(xdone, (unsigned)(j + 1), a.stop); };
             for (int kap = kb < 0 ? a.nk : kb; kap < a.nk; kap += 2 * kpair) {
@@ -2257,8 +2274,10 @@ __global__ __launch_bounds__(768, 3) void k_hstep_rp(StepArgs a) {
                             gate_p1b();
                         }
                         if (nq > nqm) {
-                            const int so3[2] = {so[0] + nqm * 1024, so[1] + nqm * 1024};
-                            contract_shared_buf<2>(acc, rsk, lane * 16, so3, sp + 8 * nqm, nq - nqm, gate_x);
+                            gate_x();
+                            const float rx = sp[a.Fm - 4 * h];  // ratio[Fm][t0 + fl]
+                            rp_p2_xrow(acc[0], wxs + kap * 32 + 4 * h, rx);
+                            rp_p2_xrow(acc[1], wxs + (kap + kpair) * 32 + 4 * h, rx);
                         }
                     }
                     SNMF_STAMP(9);
@@ -2279,8 +2298,8 @@ __global__ __launch_bounds__(768, 3) void k_hstep_rp(StepArgs a) {
                             gate_p1b();
                         }
                         if (nq > nqm) {
-                            const int so3[1] = {so[0] + nqm * 1024};
-                            contract_shared_buf<1>(acc, rsk, lane * 16, so3, sp + 8 * nqm, nq - nqm, gate_x);
+                            gate_x();
+                            rp_p2_xrow(acc[0], wxs + kap * 32 + 4 * h, sp[a.Fm - 4 * h]);
                         }
                     }
                     rp_p2_epilogue<OBJ>(a, acc[0], Hs, kap, t0, lane, dp0, shsum);
@@ -3313,9 +3332,11 @@ __global__ __launch_bounds__(512, 2) void k_hsolve_frame(StepArgs a, SmallArgs s
 // TIL: the consumer teams of StepArgs::til.  A compile-time switch, and a kernel of its own (k_wstats_teams): the eight-consumer
 // geometries of the F = 513 shapes sit at their 168-VGPR limit, and the team indices as run-time values in their tile loop cost them
 // 19 spilled VGPRs (the reference's 513 x 72000 r = 100 W step 0.1350 -> 0.1407 ms); profiles/r04_resources.csv is the check.
-template <int NK, int NWB, int NL, int WPS, int WM, int BM, bool OBJ, int TT, int LX, bool TIL>
+// XG: the extra row (F = 32n+1) runs behind P3's first W-fragment loads instead of at the top of the tile (k_wstats_xg; see xrow_tile).
+template <int NK, int NWB, int NL, int WPS, int WM, int BM, bool OBJ, int TT, int LX, bool TIL, bool XG = false>
 __device__ __forceinline__ void wstats_body(StepArgs a, int n_chunks, int mat_index, int n_mat) {
     static_assert(TT == 32 || (TT == 16 && NL == 0), "narrow tiles: 16 frames, synchronous staging");
+    static_assert(!XG || (WM != 3 && !TIL), "the extra row rides in P3's gate: needs a P3, every consumer on every tile");
     constexpr int NTHR = (NWB + NL) * 64;
     // Tile buffers: 1 without loader waves; with them 2, or 3 where the LDS has room (host: a.nbuf).  With two buffers the DMA
     // of tile i+1 can only be issued once the SLOWEST consumer has finished tile i-1 and must have landed before the fastest
@@ -3442,8 +3463,17 @@ __device__ __forceinline__ void wstats_body(StepArgs a, int n_chunks, int mat_in
     }
 
     // The extra row of one tile (row group 0 only): ratio_x[t] for this wave's CPW columns, then gx[k] += ratio_x[t] * H[k,t].
-    // It stays on the CONSUMER waves: moved to the loader waves -- which only get an instruction in where their SIMD's
-    // MFMA wave stalls -- it delayed the staging of the next tile (k_wstats 0.249 -> 0.277 ms on C2).
+    // It stays on the CONSUMER waves.  On the loader waves -- which only get an instruction in where their SIMD's MFMA wave
+    // stalls -- it delays the staging of the next tile: round 2, ~300 staging instructions per tile on two buffers, k_wstats
+    // 0.249 -> 0.277 ms on C2; round 7, ~17 LDS-DMA instructions per tile and three buffers, run once the wave had posted `ready`
+    // and seen all four `ready` words: the consumers of group 0 waited 118 k cycles per chunk for `ready` where the row had
+    // cost them 39 k, the iteration 0.459 -> 0.491 ms (profiles/r07_experiments.md).
+    // At the top of a tile it is ~135 instructions with nothing else in flight on the SIMD -- a chain of LDS reads -> FMAs ->
+    // DPP reduction -> rcp -> readlane -> LDS reads whose latency nobody hides: 1.61 k cycles per tile against 19.5 k for the
+    // rest, and with 24 tiles + rows against the other group's 25 tiles group 0 ended the launch 8 us late.  XG (k_wstats_xg,
+    // the NK = 8 / 4+4-wave KL statistics of full updates) calls it as the GATE of P3's contraction instead: behind the loop's
+    // first W-fragment loads, whose L2 round trip then runs under the row (1.15 k cycles per tile; group 0 ends 4 us earlier,
+    // the iteration 0.4574 -> 0.4528 ms).  Same code, same tile order: same bits.
     auto xrow_tile = [&](const float* xH, int xt0, int xw, const float* vxc) {
             // extra row: ratio_x[t] for this wave's CPW columns, then gx[k] += ratio_x[t] * H[k,t]
             float rxv[CPW];
@@ -3635,9 +3665,12 @@ __device__ __forceinline__ void wstats_body(StepArgs a, int n_chunks, int mat_in
                 }
             }
         }
-        if (do_x) xrow_tile(Hs, t0, w, vx + cb * 32);
+        if (!XG && do_x) xrow_tile(Hs, t0, w, vx + cb * 32);
         SNMF_STAMP(2);
         if (!active || (TIL && til > 1 && it % til != tph)) {  // (another team's tile: only the progress report)
+            if constexpr (XG) {  // a wave without a row tile (F = 33, 65, 97) has no P3 to run its share of the row under
+                if (do_x) xrow_tile(Hs, t0, w, vx + cb * 32);
+            }
             if (NL > 0) rp_post(done, w, (unsigned)(it + 1), lane);
             continue;
         }
@@ -3650,8 +3683,17 @@ __device__ __forceinline__ void wstats_body(StepArgs a, int n_chunks, int mat_in
             {
                 const __amdgpu_buffer_rsrc_t rsw = wimage_rsrc(a.Wt4, (size_t)a.nf * rp * 32);
                 const float* spl = Hs + (fl & (TT - 1)) * ldh + 4 * h;
-                if (a.nqk == 32) contract_p3_buf<true>(acc1[0], rsw, lane * 16, phi * rp * 128, spl, 32, NoGate());
-                else contract_p3_buf<false>(acc1[0], rsw, lane * 16, phi * rp * 128, spl, a.nqk, NoGate());
+                if constexpr (XG) {
+                    // the row's latency chain runs while the loop's first W fragments make their L2 round trip
+                    auto xgate = [&]() {
+                        if (do_x) xrow_tile(Hs, t0, w, vx + cb * 32);
+                    };
+                    if (a.nqk == 32) contract_p3_buf<true>(acc1[0], rsw, lane * 16, phi * rp * 128, spl, 32, xgate);
+                    else contract_p3_buf<false>(acc1[0], rsw, lane * 16, phi * rp * 128, spl, a.nqk, xgate);
+                } else {
+                    if (a.nqk == 32) contract_p3_buf<true>(acc1[0], rsw, lane * 16, phi * rp * 128, spl, 32, NoGate());
+                    else contract_p3_buf<false>(acc1[0], rsw, lane * 16, phi * rp * 128, spl, a.nqk, NoGate());
+                }
             }
             SNMF_STAMP(3);
             const f32x16 acc = acc1[0];
@@ -3911,6 +3953,11 @@ template <int NK, int NWB, int NL, int WPS, int WM, int BM, bool OBJ, int TT = 3
 __global__ __launch_bounds__((NWB + NL) * 64, WPS) void k_wstats(StepArgs a, int n_chunks, int mat_index,
                                                                  int n_mat) {
     wstats_body<NK, NWB, NL, WPS, WM, BM, OBJ, TT, LX, false>(a, n_chunks, mat_index, n_mat);
+}
+// the same with the extra row behind P3's first W-fragment loads (XG)
+template <int NK, int NWB, int NL, int WPS, int WM, int BM, bool OBJ>
+__global__ __launch_bounds__((NWB + NL) * 64, WPS) void k_wstats_xg(StepArgs a, int n_chunks, int mat_index, int n_mat) {
+    wstats_body<NK, NWB, NL, WPS, WM, BM, OBJ, 32, 0, false, true>(a, n_chunks, mat_index, n_mat);
 }
 // the same with consumer TEAMS (StepArgs::til): a kernel of its own, see the note on TIL above
 template <int NK, int NWB, int NL, int WPS, int WM, int BM, bool OBJ, int TT = 32, int LX = 0>

@@ -10,6 +10,7 @@ struct Switches {
     bool hstep_rp;     // SNMF_HSTEP_RP=0: the barrier-phased k_hstep instead of the role pipelines and k_hstep_sf / k_hstep_sr
     bool hstep_split;  // SNMF_HSTEP_SPLIT=0: every tile whole (no split last round, no shared last tiles)
     bool wstats_nl;    // SNMF_WSTATS_NL set to anything but 4: k_wstats without loader waves (so no k_wstats_sf / k_wstats_sr)
+    bool wstats_xg;    // SNMF_WSTATS_XG=0: k_wstats' extra row at the top of the tile instead of behind P3's first W loads (k_wstats_xg)
     bool iter_sf;      // SNMF_ITER_SF=0: two launches instead of k_iter_sf
     bool gram_p;       // SNMF_GRAM_P=0: the Euclidean P without the Gram matrix
     int no_small;      // SNMF_NO_SMALL: 1 = no persistent kernel at all (the plan loop), 2 = no register-resident frame kernel
@@ -24,6 +25,7 @@ Switches read_switches() {
     s.hstep_rp = env_int("SNMF_HSTEP_RP", 1) != 0;
     s.hstep_split = env_int("SNMF_HSTEP_SPLIT", 1) != 0;
     s.wstats_nl = env_int("SNMF_WSTATS_NL", 4) == 4;
+    s.wstats_xg = env_int("SNMF_WSTATS_XG", 1) != 0;
     s.iter_sf = env_int("SNMF_ITER_SF", 1) != 0;
     s.gram_p = env_int("SNMF_GRAM_P", 1) != 0;
     s.no_small = env_int("SNMF_NO_SMALL", 0);
@@ -269,6 +271,10 @@ int plan_geometry(const snmf_params* pp, int n_cu, PlanGeometry* g) {
     // Relative cost x of the extra row per tile: ~2.1 k cycles at rp = 256 against 21 k for the two MFMA loops (phase
     // stamps; a sweep of the split point on C2 had its optimum where this x puts it: 131..135 chunks for group 0,
     // k_wstats 0.2573 -> 0.2481 ms, profiles/r02_experiments.md).
+    // (Round 7 stamps on C2: 1.61 k of 21.2 k cycles per group-0 tile, x = 0.083; k_wstats_xg hides part of the row under P3's
+    //  first W loads -- 1.15 k, see below -- and keeps this x: at C2 131 : 125 is the optimum for every x > 0 (24 tiles + rows
+    //  against 25 tiles; any other deal gives a group 25 tiles + rows or 27 tiles), and a plan's deal decides its chunks' fp32
+    //  sums, which stay what they were.)
     g->n_ch1 = 0;
     if (g->xr && g->n_fg >= 2 && g->n_kg == 1 && g->NLW && g->upd_w && n_tiles_w >= 4 * g->n_chunks) {
         const int tot = g->n_fg * g->n_chunks, ng1 = g->n_fg - 1;  // group 0: n0 workgroups, every other group n1
@@ -287,6 +293,16 @@ int plan_geometry(const snmf_params* pp, int n_cu, PlanGeometry* g) {
             g->n_ch1 = n1_of(best);
             g->n_chunks = best;
         }
+    }
+    // The extra row of the KL statistics of FULL updates on the NK = 8, 4 + 4-wave loader geometry with at most two row groups (the
+    // headline) runs behind P3's first W-fragment loads (k_wstats_xg); four-group plans, the statistics launch of a W-only solve
+    // (it also sums the objective) and every other instantiation keep it at the top of the tile.  SNMF_WSTATS_XG=0: there as well
+    // -- describe() then says so; the default text is the one the recorded plans pin.
+    {
+        const bool shape = g->xr && g->bm == BM_KL && g->upd_w && g->upd_h && g->NKT == 8 && g->NWB == 4 && g->NLW == 4 && g->TTW == 32 &&
+                           g->n_fg <= 2 && g->n_kg == 1 && !g->wsr;
+        g->wxg = shape && sw.wstats_xg;
+        g->wxg_off = shape && !sw.wstats_xg;
     }
     // start-up stagger (cycles) of the second half of each grid: about half a tile period when two
     // workgroups share a CU.
@@ -360,6 +376,7 @@ int plan_geometry(const snmf_params* pp, int n_cu, PlanGeometry* g) {
         g->kq_kg = 0;
         g->gram_p = false;
         g->n_ch1 = 0;
+        g->wxg = g->wxg_off = false;
         g->small_ok = g->small = false;
         g->frame_fb = g->frame_kb = 0;
         g->wfin = false;
@@ -422,6 +439,7 @@ void describe_geometry(const PlanGeometry& g, const snmf_params& p, int n_cu, bo
                         : g.wsr  ? ", k_wstats_sr: statistics rows per wave, operands straight into the MFMA layouts"
                         : g.wsf  ? (g.wsf_share ? ", k_wstats_sf: a tile per wave, a single remainder tile shared by the eight waves" : ", k_wstats_sf: a tile per wave")
                         : g.til > 1 ? (g.til == 2 ? ", 2 consumer teams take the tiles in turn" : ", 4+ consumer teams take the tiles in turn")
+                        : g.wxg_off ? ", extra row at the top of the tile (SNMF_WSTATS_XG=0)"
                                     : "";
     const char* wfinish = g.wfin    ? "k_wfin"
                           : g.upd_w ? "k_reduce + k_wapply"

@@ -75,9 +75,29 @@ static int launch_gram_p(snmf_plan* pl, const StepArgs& a) {
     return g_gemm(pl, pl->Wcf, 1, pl->Fp, pl->gram32, 1, pl->rp, pl->slabs + nW, 1, pl->Fp, pl->p.F, pl->p.r, pl->p.r, kchunk,
                   nW * pl->n_mat);
 }
+// KL statistics with the extra row behind P3's first W loads (k_wstats_xg; plan->wxg: full updates on the NK = 8, 4 + 4-wave geometry)
+template <int NK, int NWB, int NL, int WPS>
+static int launch_wstats_xg(snmf_plan* pl, const StepArgs& a) {
+    StepArgs as = a;
+    const bool split = pl->n_ch1 > 0;
+    as.n_ch1 = split ? pl->n_ch1 : 0;
+    as.til = 1;
+    auto kern = k_wstats_xg<NK, NWB, NL, WPS, 0, BM_KL, false>;
+    SN_TRY(ensure_dyn_lds(pl->ctx->device, (const void*)kern, pl->lds_w));
+    dim3 g(split ? pl->n_chunks + (pl->n_fg - 1) * pl->n_ch1 : pl->n_chunks, split ? 1 : pl->n_fg, 1);
+    hipLaunchKernelGGL(kern, g, dim3((NWB + NL) * 64), pl->lds_w, pl->ctx->stream, as, pl->n_chunks, 0, pl->n_mat);
+    HIP_TRY(hipGetLastError());
+    return SNMF_OK;
+}
 template <int NK, int NWB, int NL, int WPS, int TT = 32>
 static int launch_wstats_geo(snmf_plan* pl, const StepArgs& a, bool obj) {
     if (pl->bm == BM_KL) {
+        if constexpr (NK == 8 && NWB == 4 && NL == 4 && TT == 32) {
+            if (pl->wxg) {
+                if (obj || pl->n_kg != 1) return fail(SNMF_ERR_INTERNAL, "k_wstats_xg: not the statistics of a full update");
+                return launch_wstats_xg<NK, NWB, NL, WPS>(pl, a);
+            }
+        }
         // statistics columns past the last full 32-column tile: up to 8 go through the VALU (k_wstats<..., LX>; loader
         // geometries only: r = 100 at the reference's settings)
         const int left = pl->p.r - 32 * (pl->nk - 1);
