@@ -109,6 +109,22 @@ int snmf_sparse_nmf_oop_f64(snmf_ctx* ctx, const snmf_params* p, const double* V
 int snmf_sparse_nmf_oop_f32(snmf_ctx* ctx, const snmf_params* p, const float* V, int64_t ldV, const float* W0,
                             const float* H0, const float* sparsity, float* W, float* H, double* div_out,
                             double* cost_out, int32_t* n_iter_out);
+/* The fp64 solve mode (added within ABI 5: a new entry only).  The four entries above only name the type of the HOST buffers:
+ * everything is narrowed on upload and the iteration runs on the fp32 MFMA (results ~1e-6 from the double-precision
+ * algorithm).  This entry computes src/sparse_nmf.m:157-286 in fp64 from end to end: storage is fp64 and the five products
+ * of an iteration (w*h, w'*R, w'*D, R*h', D*h'; :194-207, :215-243) run on the f64 MFMA (v_mfma_f64_16x16x4_f64), the
+ * element-wise passes, the F x r epilogue (:215-244), the initial scaling (:157-169), the objective (:248-261) and the
+ * stop test (:272-284, on the device) in fp64.  Every reduction has a fixed order: two calls on one input give the same bits.
+ * What it is for: a caller who passes doubles and wants the double-precision algorithm's results (within ~1e-12 of a host
+ * fp64 evaluation), and a judge of the fp32 path at the workload's own size.  What it costs: every intermediate lives in
+ * HBM (about 8 (3 F T + 3 r T) bytes; 1.5 GB at 257 x 100 000, r = 256), nothing is fused, and the f64 MFMA runs at half
+ * the f32 MFMA's rate -- measured 6 to 8 times fewer iterations per second than the fp32 entries.
+ * Same argument list and meaning as snmf_sparse_nmf_oop_f64; every field of snmf_params means what it means there
+ * (floor_v = 0: sparse_nmf_GPU.m; cost_check = 0: no objective, no stop; partial w_update_ind; the three sparsity forms;
+ * a partial h_update_ind is SNMF_ERR_DIM).  Any F, T, r the device memory holds; a failed allocation is SNMF_ERR_NOMEM. */
+int snmf_sparse_nmf_fp64(snmf_ctx* ctx, const snmf_params* p, const double* V, int64_t ldV, const double* W0,
+                         const double* H0, const double* sparsity, double* W, double* H, double* div_out,
+                         double* cost_out, int32_t* n_iter_out);
 
 /* ---- resident-plan API (benchmarks, on-device pipelines, multi-GPU sharding) -------------- */
 /* A plan owns fp32 device copies of V (F x T), W (F x r), H (r x T) in the engine's padded

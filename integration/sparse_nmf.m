@@ -67,6 +67,11 @@ if isfield(p, 'snmf_devices') && ~isempty(p.snmf_devices)
     % snmf_sparse_nmf_multi_f64): how run_basis_DNMF.m:40,47,53 / run_basis_train.m:88 reach the 8-GPU path unchanged
     opts.devices = double(p.snmf_devices(:)');
 end
+if isfield(p, 'snmf_precision') && ~isempty(p.snmf_precision)
+    % p.snmf_precision = 'fp64' -- the fp64 solve mode (snmf_sparse_nmf_fp64): fp64 storage and f64 MFMA contractions, the
+    % double-precision algorithm's results to ~1e-12, many times slower than the default 'fp32'; one device only
+    opts.precision = char(p.snmf_precision);
+end
 if gpu_variant
     opts.cost_check = 1;
 else

@@ -21,6 +21,8 @@
 //            w_update_ind (r x 1 logical), h_update_ind (r x 1 logical), device (0-based),
 //            devices (vector of 0-based device ordinals, optional): the frames are sharded over these GPUs inside
 //            this one MATLAB process (snmf_sparse_nmf_multi_f64: one exchange of the W statistics per iteration)
+//            precision ('fp32' default | 'fp64', optional): 'fp64' = the fp64 solve mode (snmf_sparse_nmf_fp64: fp64 storage,
+//            f64 MFMA contractions; one device only)
 #include <cstdint>
 #include <cstring>
 #include <vector>
@@ -129,12 +131,26 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
             for (size_t i = 0; i < mxGetNumberOfElements(dv); ++i) devices.push_back((int32_t)d[i]);
         }
     }
+    // opts.precision = 'fp64': the fp64 solve mode; any other string but 'fp32' is an error, as is a device list with it
+    bool fp64_mode = false;
+    if (const mxArray* pr = mxGetField(opts, 0, "precision")) {
+        if (!mxIsEmpty(pr)) {
+            char prec[16] = "";
+            if (!mxIsChar(pr) || mxGetString(pr, prec, sizeof prec) != 0) mexErrMsgIdAndTxt("snmf:type", "opts.precision must be 'fp32' or 'fp64'");
+            if (std::strcmp(prec, "fp64") == 0) fp64_mode = true;
+            else if (std::strcmp(prec, "fp32") != 0) mexErrMsgIdAndTxt("snmf:type", "opts.precision must be 'fp32' or 'fp64' (got '%s')", prec);
+        }
+    }
+    if (fp64_mode && !devices.empty()) mexErrMsgIdAndTxt("snmf:unsupported", "opts.precision = 'fp64' runs on one device (no opts.devices)");
     mxArray* hout = devices.empty() ? mxCreateDoubleMatrix((mwSize)r, (mwSize)T, mxREAL) : mxDuplicateArray(h0);
     plhs[0] = devices.empty() ? mxCreateDoubleMatrix((mwSize)F, (mwSize)r, mxREAL) : mxDuplicateArray(w0);
     mxArray* divv = mxCreateDoubleMatrix(1, p.max_iter > 0 ? p.max_iter : 1, mxREAL);
     mxArray* costv = mxCreateDoubleMatrix(1, p.max_iter > 0 ? p.max_iter : 1, mxREAL);
     int32_t n_iter = 0;
-    const int st = devices.empty()
+    const int st = fp64_mode
+        ? snmf_sparse_nmf_fp64(g_ctx, &p, mxGetDoubles(v), (int64_t)F, mxGetDoubles(w0), mxGetDoubles(h0), sparsity,
+                               mxGetDoubles(plhs[0]), mxGetDoubles(hout), mxGetDoubles(divv), mxGetDoubles(costv), &n_iter)
+        : devices.empty()
         ? snmf_sparse_nmf_oop_f64(g_ctx, &p, mxGetDoubles(v), (int64_t)F, mxGetDoubles(w0), mxGetDoubles(h0), sparsity,
                                   mxGetDoubles(plhs[0]), mxGetDoubles(hout), mxGetDoubles(divv), mxGetDoubles(costv), &n_iter)
         : snmf_sparse_nmf_multi_f64(devices.data(), (int32_t)devices.size(), &p, mxGetDoubles(v), (int64_t)F,

@@ -4,10 +4,13 @@
 // Bare loops on random operands, one or two waves per SIMD, operands either held in registers or re-read from LDS
 // with one ds_read_b128 per four MFMAs (the cadence of the solver's P1/P2/P3 loops).  Reports wall TFLOP/s and the
 // in-kernel clock (s_memtime over s_memrealtime, median over workgroups) -- MI355X_MICROARCH.md, DVFS give-back.
+// Also the f64 shape v_mfma_f64_16x16x4_f64 (k_loop64: 2048 flop per instruction): the denominator of "fraction of the
+// f64 MFMA rate" for the fp64 solve mode (csrc/snmf_solve64.h).  `mfma_shape_bench f64` runs only those lines.
 // Build + run:  hipcc -O3 --offload-arch=gfx950 -std=c++17 -o /tmp/mfma_shape_bench scripts/mfma_shape_bench.hip && /tmp/mfma_shape_bench
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdio>
+#include <cstring>
 #include <random>
 #include <vector>
 
@@ -85,6 +88,40 @@ __global__ __launch_bounds__(512) void k_loop(const float* __restrict__ src, flo
     }
 }
 
+// f64 16x16x4: 8 accumulators (64 VGPRs), 64 MFMAs per trip = 131072 flop per wave, operands held in registers
+__global__ __launch_bounds__(512) void k_loop64(const float* __restrict__ src, float* __restrict__ out, Stamp* st, int trips) {
+    typedef double f64x4 __attribute__((ext_vector_type(4)));
+    const int lane = threadIdx.x & 63;
+    double a[8], b[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        a[j] = (double)src[(threadIdx.x * 8 + j + blockIdx.x * 131) & 0xfffff];
+        b[j] = (double)src[(threadIdx.x * 8 + j + 7777 + blockIdx.x * 17) & 0xfffff];
+    }
+    unsigned long long c0 = 0, r0 = 0;
+    if (lane == 0) {
+        c0 = __builtin_amdgcn_s_memtime();
+        r0 = __builtin_amdgcn_s_memrealtime();
+    }
+    f64x4 acc[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) acc[c] = f64x4{0.0, 0.0, 0.0, 0.0};
+    for (int t = 0; t < trips; ++t) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+#pragma unroll
+            for (int c = 0; c < 8; ++c) acc[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[(j + c) & 7], b[j], acc[c], 0, 0, 0);
+    }
+    double s = 0.0;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) s += acc[c][0] + acc[c][1] + acc[c][2] + acc[c][3];
+    out[blockIdx.x * blockDim.x + threadIdx.x] = (float)s;
+    if (lane == 0) {
+        Stamp x{c0, __builtin_amdgcn_s_memtime(), r0, __builtin_amdgcn_s_memrealtime()};
+        st[blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)] = x;
+    }
+}
+
 template <typename K>
 static void run(K kern, const char* name, int threads, const float* src, float* out, Stamp* st, int trips) {
     const int grid = 256;
@@ -126,7 +163,8 @@ static void run(K kern, const char* name, int threads, const float* src, float* 
            hipGetErrorString(hipGetLastError()));
 }
 
-int main() {
+int main(int argc, char** argv) {
+    const bool f64_only = argc > 1 && std::strcmp(argv[1], "f64") == 0;
     std::mt19937 g(7);
     std::uniform_real_distribution<float> u(0.01f, 1.f);
     std::vector<float> h(1 << 20);
@@ -138,6 +176,10 @@ int main() {
     hipMalloc(&st, 256 * 8 * sizeof(Stamp));
     hipMemcpy(src, h.data(), h.size() * 4, hipMemcpyHostToDevice);
     const int trips = 4000;  // 4000 x 2048 issue cycles = 8.2 M cycles, ~4 ms per launch at one wave per SIMD
+    // (the "MFMA issue" column assumes 2048 cycles per trip, the f32 shapes' figure; the f64 lines' wave cycles say what it is there)
+    run(k_loop64, "f64 16x16x4  regs  1 wave/SIMD", 256, src, out, st, trips / 2);
+    run(k_loop64, "f64 16x16x4  regs  2 waves/SIMD", 512, src, out, st, trips / 4);
+    if (f64_only) return 0;
     run(k_loop<32, false>, "32x32x2  regs  1 wave/SIMD", 256, src, out, st, trips);
     run(k_loop<16, false>, "16x16x4  regs  1 wave/SIMD", 256, src, out, st, trips);
     run(k_loop<32, true>, "32x32x2  lds   1 wave/SIMD", 256, src, out, st, trips);

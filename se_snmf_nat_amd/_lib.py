@@ -37,6 +37,7 @@ _TU_HDRS = {
     "snmf_tu_itersf.hip": ["snmf_smallf.h"],
     "snmf_tu_smallr.hip": ["snmf_smallf.h", "snmf_smallr.h"],
     "snmf_tu_geometry.hip": ["snmf_generic.h"],
+    "snmf_tu_solve64.hip": ["snmf_solve64.h"],
 }
 HDRS = sorted(_glob.glob(os.path.join(_HERE, "csrc", "*.h"))) + [os.path.join(_ROOT, "include", "snmf.h")]
 
@@ -72,6 +73,7 @@ SYMBOLS = [
     "snmf_run_basis_train_audio_f64", "snmf_ctx_xfer_stats", "snmf_sparse_nmf_oop_f64", "snmf_sparse_nmf_oop_f32",
     "snmf_run_basis_dnmf_multi_f64", "snmf_run_basis_dnmf_multi_f32",
     "snmf_multi_release_cache", "snmf_multi_cached_teams",
+    "snmf_sparse_nmf_fp64",
     "snmf_rccl_available", "snmf_rccl_get_unique_id", "snmf_rccl_comm_create", "snmf_rccl_comm_destroy", "snmf_plan_run_sharded_rccl",
 ]
 ABI_VERSION = 5  # include/snmf.h: SNMF_ABI_VERSION this binding was written against
@@ -321,6 +323,7 @@ def load():
     sig["snmf_plan_run_sharded_rccl"] = (C.c_int, [vp, i32, vp, vp, i32, i32, C.POINTER(i32)])
     for ty in ("f64", "f32"):
         sig[f"snmf_sparse_nmf_oop_{ty}"] = (C.c_int, [vp, PP, vp, i64, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i32)])
+    sig["snmf_sparse_nmf_fp64"] = (C.c_int, [vp, PP, vp, i64, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i32)])
     lib.snmf_abi_version.restype = C.c_int
     if lib.snmf_abi_version() != ABI_VERSION:  # a stale library must not be driven through newer prototypes
         raise ImportError(f"{path} has ABI version {lib.snmf_abi_version()}, this binding needs {ABI_VERSION}: rebuild the library")

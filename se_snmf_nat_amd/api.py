@@ -142,11 +142,13 @@ def _colmajor(M, dt):
     return np.asfortranarray(M, dtype=dt)
 
 
-def _solve(v, p, *, gpu_variant, ctx, dtype, rng, devices=None):
+def _solve(v, p, *, gpu_variant, ctx, dtype, rng, devices=None, precision="fp32"):
     p = dict(p or {})
     dt = np.dtype(dtype)
     if dt not in (np.dtype(np.float64), np.dtype(np.float32)):
         raise SnmfError(1, "dtype must be float64 or float32")
+    if precision not in ("fp32", "fp64"):
+        raise ValueError(f"precision must be 'fp32' or 'fp64' (got {precision!r})")
     v = np.asarray(v)
     if v.ndim != 2:
         raise SnmfError(1, "v must be a 2-D matrix")
@@ -199,6 +201,12 @@ def _solve(v, p, *, gpu_variant, ctx, dtype, rng, devices=None):
             raise SnmfError(4, "Reference to non-existent field 'cost_check'.")
         cost_check = 1 if p["cost_check"] else 0
 
+    if precision == "fp64":  # (after the reference's own errors, before any device work)
+        if dt != np.dtype(np.float64):
+            raise SnmfError(1, "precision='fp64' needs dtype=np.float64 (the fp64 solve takes and returns doubles)")
+        if devices is not None:
+            raise SnmfError(8, "precision='fp64' runs on one device (no fp64 solve over a device list)")
+
     sp = _make_params(m, n, r, beta, max_iter, conv_eps, cost_check, not gpu_variant, kind, scalar, w_ind, h_ind)
     vv = _colmajor(v, dt)
     W = np.asfortranarray(w0, dtype=dt)
@@ -223,7 +231,10 @@ def _solve(v, p, *, gpu_variant, ctx, dtype, rng, devices=None):
         W0c, H0c = W, H
         W = np.empty((m, r), dtype=dt, order="F")
         H = np.empty((r, n), dtype=dt, order="F")
-        fn = lib.snmf_sparse_nmf_oop_f64 if dt == np.float64 else lib.snmf_sparse_nmf_oop_f32
+        if precision == "fp64":  # the fp64 solve mode: fp64 storage, contractions on the f64 MFMA (include/snmf.h)
+            fn = lib.snmf_sparse_nmf_fp64
+        else:
+            fn = lib.snmf_sparse_nmf_oop_f64 if dt == np.float64 else lib.snmf_sparse_nmf_oop_f32
         _lib.check(fn(ctx._h, C.byref(sp), _ptr(vv), ldv, _ptr(W0c), _ptr(H0c), _ptr(sarr) if sarr is not None else None,
                       _ptr(W), _ptr(H), _ptr(div), _ptr(cost), C.byref(n_iter)))
     ni = n_iter.value
@@ -270,20 +281,24 @@ def _display(beta, div, cost, n_iter, max_iter, cost_check, conv_eps, gpu_varian
     w("\\nMax Iteration reached, aborting iteration\\n\n")
 
 
-def sparse_nmf(v, p=None, *, ctx=None, dtype=np.float64, rng=None, devices=None):
+def sparse_nmf(v, p=None, *, ctx=None, dtype=np.float64, rng=None, devices=None, precision="fp32"):
     """[w, h, objective] = sparse_nmf(v, p) -- drop-in for src/sparse_nmf.m on the MI355X.
 
-    `dtype` selects the host-buffer type handed over the C ABI (the device arithmetic is fp32
-    MFMA + fp64 objective either way).  `devices`: list of device ordinals -> the frame axis is sharded over
+    `dtype` selects the host-buffer type handed over the C ABI; it does not choose the device arithmetic.
+    `precision` does: "fp32" (default) = fp32 MFMA + fp64 objective, results ~1e-6 from the double-precision
+    algorithm; "fp64" = the fp64 solve mode (snmf_sparse_nmf_fp64: fp64 storage, f64 MFMA contractions, results
+    within ~1e-14 of a host fp64 evaluation, bit-reproducible, 6-8x slower per iteration).  "fp64" needs dtype=np.float64
+    (SnmfError status 1 otherwise) and one device (status 8 with `devices`); any other string is a ValueError.
+    `devices`: list of device ordinals -> the frame axis is sharded over
     that many ranks inside this one process (snmf_sparse_nmf_multi_*), same results up to the fp64 summation order
     of the W statistics; the multi-device entry creates a context per rank itself, so `ctx` is not used then."""
-    return _solve(v, p, gpu_variant=False, ctx=ctx, dtype=dtype, rng=rng, devices=devices)
+    return _solve(v, p, gpu_variant=False, ctx=ctx, dtype=dtype, rng=rng, devices=devices, precision=precision)
 
 
-def sparse_nmf_GPU(v, p=None, *, ctx=None, dtype=np.float64, rng=None):
+def sparse_nmf_GPU(v, p=None, *, ctx=None, dtype=np.float64, rng=None, precision="fp32"):
     """Drop-in for src/sparse_nmf_GPU.m (its deltas: no V floor, objective vectors left zero,
-    cost_check ignored)."""
-    return _solve(v, p, gpu_variant=True, ctx=ctx, dtype=dtype, rng=rng)
+    cost_check ignored).  `precision`: as in sparse_nmf."""
+    return _solve(v, p, gpu_variant=True, ctx=ctx, dtype=dtype, rng=rng, precision=precision)
 
 
 def philox4x32_10(ctr, key0, key1):

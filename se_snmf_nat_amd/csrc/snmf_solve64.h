@@ -1,0 +1,313 @@
+// ============================================================================================
+// The fp64 solve mode (snmf_sparse_nmf_fp64): src/sparse_nmf.m:157-286 with fp64 storage and the contractions on the
+// f64 MFMA (v_mfma_f64_16x16x4_f64).  The structure is the out-of-envelope path's (snmf_generic.h): every intermediate
+// lives in HBM, one strided split-K GEMM kernel forms all five products of an iteration
+//     Lam = W*H,   num = W'*R,   den = W'*D,   Q = R*H',   P = D*H'
+// and a few element-wise passes do the rest.  Nothing is padded: V, Lam, R, D are F x T, H / num / den r x T, W / Q / P
+// F x r, all column-major and tight, every kernel checks its bounds, so no pad row or column can reach the objective
+// (0 * log 0 = NaN) or a sum.  Offsets are 64-bit throughout.
+// Every reduction has a fixed order -- the k-loop of a GEMM chunk, the chunk partials (added in chunk order by
+// k_s64_sumz), the workgroup trees of the objective and the column sums -- so two runs give the same bits.
+// Every per-iteration kernel returns at once when the device-side stop word is set: after a convergence stop
+// (src/sparse_nmf.m:272-282) W and H keep the values of the stop iteration without a host round trip.
+// ============================================================================================
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace snmf {
+
+typedef double f64x4 __attribute__((ext_vector_type(4)));
+
+constexpr int kS64Blocks = 1024;     // workgroups of the objective pass = its partial slots
+constexpr int kS64ChunkK = 2048;     // L: contraction indices per split of a GEMM (each split writes a partial of its own)
+constexpr int kS64RowChunk = 256;    // frames per split of the row sums of H
+constexpr double kS64Flr = 1e-9;     // src/sparse_nmf.m:166
+enum { S64_KL = 0, S64_ED = 1, S64_IS = 2, S64_GEN = 3 };
+
+struct Solve64State {
+    int stop;          // 1 once the convergence test of :273-282 has fired
+    int n_iter;        // the iteration it fired at
+    double last_cost;  // :168, :284
+};
+
+// C[z](m, n) = sum_{k in split z} A(m, k) * B(k, n); element (i, j) of X at X[i * rsX + j * csX]; split z covers
+// k in [z * kchunk, min(K, (z + 1) * kchunk)) and writes C + z * zC.  do_floor: C = max(C, 1e-9) (one split only).
+struct Gemm64Args {
+    const double* A;
+    const double* B;
+    double* C;
+    int M, N, K, kchunk;
+    long long rsA, csA, rsB, csB, rsC, csC, zC;
+    int do_floor;
+    const int* stop;
+};
+
+// 64 x 64 x 16 LDS tiles, four waves, a 32 x 32 quadrant each as 2 x 2 MFMA tiles of 16 x 16 x 4.  Operand map of the
+// f64 MFMA: lane l gives A[i = l & 15][k = l >> 4] and B[k = l >> 4][j = l & 15]; result register g of lane l is
+// D[row = (l >> 4) + 4 g][col = l & 15] -- NOT the f32 map.  The 16 lanes of a result register run along n, so the
+// stores are contiguous (128 bytes) when C's unit stride runs along n: the host hands a product whose C has its unit
+// stride along m over as C^T = B^T * A^T (gemm64 in snmf_tu_solve64.hip), a relabelling of the strides.
+// Workgroup b of a split takes row tile b % tiles_m and column tile b / tiles_m (x is the one grid dimension that
+// holds 2^31 tiles); blockIdx.y is the split.
+static __global__ __launch_bounds__(256) void k_s64_gemm(Gemm64Args g) {
+    if (*g.stop) return;
+    constexpr int BM = 64, BN = 64, BK = 16;
+    __shared__ double As[BK][BM + 2];
+    __shared__ double Bs[BK][BN + 2];
+    const int tid = threadIdx.x;
+    const int tiles_m = (g.M + BM - 1) / BM;
+    const int m0 = (int)(blockIdx.x % tiles_m) * BM, n0 = (int)(blockIdx.x / tiles_m) * BN;
+    const int k_lo = blockIdx.y * g.kchunk, k_hi = min(g.K, k_lo + g.kchunk);
+    const int w = tid >> 6, lane = tid & 63, l15 = lane & 15, q = lane >> 4;
+    const int wm = (w >> 1) * 32, wn = (w & 1) * 32;
+    f64x4 acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[i][j] = f64x4{0.0, 0.0, 0.0, 0.0};
+    // the faster-running index of each operand picks how a tile is read (coalesced along the unit stride)
+    const bool a_m_fast = g.rsA == 1, b_n_fast = g.csB == 1;
+    for (int k0 = k_lo; k0 < k_hi; k0 += BK) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int i = tid + 256 * e;  // 1024 elements of each tile
+            {
+                const int mm = a_m_fast ? (i & 63) : (i >> 4), kk = a_m_fast ? (i >> 6) : (i & 15);
+                const int m = m0 + mm, k = k0 + kk;
+                As[kk][mm] = (m < g.M && k < k_hi) ? g.A[(long long)m * g.rsA + (long long)k * g.csA] : 0.0;
+            }
+            {
+                const int nn = b_n_fast ? (i & 63) : (i >> 4), kk = b_n_fast ? (i >> 6) : (i & 15);
+                const int n = n0 + nn, k = k0 + kk;
+                Bs[kk][nn] = (n < g.N && k < k_hi) ? g.B[(long long)k * g.rsB + (long long)n * g.csB] : 0.0;
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int kk = 0; kk < BK; kk += 4) {
+            const double a0 = As[kk + q][wm + l15], a1 = As[kk + q][wm + 16 + l15];
+            const double b0 = Bs[kk + q][wn + l15], b1 = Bs[kk + q][wn + 16 + l15];
+            acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
+            acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
+            acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
+            acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
+        }
+        __syncthreads();
+    }
+    double* C = g.C + (long long)blockIdx.y * g.zC;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) {
+                // rows of D come from the first MFMA operand, columns from the second
+                const int m = m0 + wm + 16 * i + q + 4 * reg, n = n0 + wn + 16 * j + l15;
+                double v = acc[i][j][reg];
+                if (g.do_floor) v = fmax(v, kS64Flr);
+                if (m < g.M && n < g.N) C[(long long)m * g.rsC + (long long)n * g.csC] = v;
+            }
+}
+
+// C(m, n) = sum over the splits z, in split order, of part[z][m + M * n] (the partials are tight and column-major)
+static __global__ __launch_bounds__(256) void k_s64_sumz(const double* __restrict__ part, int nz, long long n, int M, double* __restrict__ C,
+                                                         long long rsC, long long csC, int do_floor, const int* stop) {
+    if (*stop) return;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        double s = 0.0;
+        for (int z = 0; z < nz; ++z) s += part[(long long)z * n + i];
+        if (do_floor) s = fmax(s, kS64Flr);
+        const long long col = i / M, row = i - col * M;
+        C[row * rsC + col * csC] = s;
+    }
+}
+
+// workgroup sum of one double per thread (256 threads), fixed tree; the result in every thread
+__device__ __forceinline__ double s64_block_sum(double v, double* red /*[256]*/) {
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    const double r = red[0];
+    __syncthreads();
+    return r;
+}
+
+// R = V .* Lam^(beta-2) (KL: V ./ Lam) and D = Lam^(beta-1) (src/sparse_nmf.m:194, :202-204, :217, :231-236); the
+// Euclidean case needs neither (R = V, D = Lam are used where they lie).
+template <int MODE>
+__global__ __launch_bounds__(256) void k_s64_ratio(const double* __restrict__ V, const double* __restrict__ Lam, double* __restrict__ R,
+                                                   double* __restrict__ D, long long n, double beta, const int* stop) {
+    if (*stop) return;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        const double v = V[i], lam = Lam[i];
+        if (MODE == S64_KL) {
+            R[i] = v / lam;
+        } else if (MODE == S64_IS) {
+            R[i] = v / (lam * lam);
+            D[i] = 1.0 / lam;
+        } else {
+            R[i] = v * pow(lam, beta - 2.0);
+            D[i] = pow(lam, beta - 1.0);
+        }
+    }
+}
+
+__device__ __forceinline__ double s64_sparsity(int kind, double scalar, const double* __restrict__ S, long long i, int k) {
+    return kind == 0 ? scalar : (kind == 1 ? S[k] : S[i]);
+}
+
+// H <- H .* num ./ max(den + sparsity, flr) (src/sparse_nmf.m:192-205); KL: den = colsum(W)
+template <bool KL>
+__global__ __launch_bounds__(256) void k_s64_hupd(double* __restrict__ H, const double* __restrict__ Num, const double* __restrict__ Den,
+                                                  const double* __restrict__ colsum, int kind, double scalar,
+                                                  const double* __restrict__ S, int r, long long n, const int* stop) {
+    if (*stop) return;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        const int k = (int)(i % r);
+        const double sp = s64_sparsity(kind, scalar, S, i, k);
+        const double den = fmax((KL ? colsum[k] : Den[i]) + sp, kS64Flr);
+        H[i] = H[i] * Num[i] / den;
+    }
+}
+
+// colsum[k] = sum_f W[f, k] (:192), one workgroup per column
+static __global__ __launch_bounds__(256) void k_s64_colsum(const double* __restrict__ W, int F, double* __restrict__ colsum, const int* stop) {
+    if (*stop) return;
+    __shared__ double red[256];
+    const double* col = W + (long long)blockIdx.x * F;
+    double s = 0.0;
+    for (int f = threadIdx.x; f < F; f += 256) s += col[f];
+    s = s64_block_sum(s, red);
+    if (threadIdx.x == 0) colsum[blockIdx.x] = s;
+}
+
+// spart[z][k] = sum over the frames of split z of H[k, t] (:215, the row sums of H; the splits are added by k_s64_sumz)
+static __global__ __launch_bounds__(256) void k_s64_rowsum(const double* __restrict__ H, int r, int T, int chunk, double* __restrict__ spart,
+                                                           const int* stop) {
+    if (*stop) return;
+    const int z = blockIdx.y, t_lo = z * chunk, t_hi = min(T, t_lo + chunk);
+    for (int k = blockIdx.x * 256 + threadIdx.x; k < r; k += gridDim.x * 256) {
+        double s = 0.0;
+        for (int t = t_lo; t < t_hi; ++t) s += H[(long long)t * r + k];
+        spart[(long long)z * r + k] = s;
+    }
+}
+
+// The F x r epilogue of the W step (src/sparse_nmf.m:215-244), one workgroup per column k:
+//   a = sum_f Q[f,k] w[f,k], b = sum_f P[f,k] w[f,k] (KL: P[f,k] = hsum[k] for every f)
+//   w <- w .* (Q + b w) ./ max(P + a w, flr)      for the columns of w_update_ind
+//   w <- w / sqrt(sum w^2)                         for ALL columns (:242)
+// UPD = false: only the normalisation, and wn[k] = the norm (the initial scaling of :157-160).
+template <bool KL, bool UPD>
+__global__ __launch_bounds__(256) void k_s64_wupd(double* __restrict__ W, const double* __restrict__ Q, const double* __restrict__ P,
+                                                  const double* __restrict__ hsum, const uint8_t* __restrict__ w_ind, int F,
+                                                  double* __restrict__ wn, const int* stop) {
+    if (UPD && *stop) return;
+    __shared__ double red[256];
+    const int k = blockIdx.x;
+    const long long o = (long long)k * F;
+    double* col = W + o;
+    if (UPD && w_ind[k]) {
+        const double hs = KL ? hsum[k] : 0.0;
+        double a = 0.0, b = 0.0;
+        for (int f = threadIdx.x; f < F; f += 256) {
+            const double w = col[f];
+            a += Q[o + f] * w;
+            b += (KL ? hs : P[o + f]) * w;
+        }
+        a = s64_block_sum(a, red);
+        b = s64_block_sum(b, red);
+        for (int f = threadIdx.x; f < F; f += 256) {
+            const double w = col[f];
+            const double dpw = fmax((KL ? hs : P[o + f]) + a * w, kS64Flr);
+            const double dmw = Q[o + f] + b * w;
+            col[f] = w * dmw / dpw;
+        }
+    }
+    double s = 0.0;
+    for (int f = threadIdx.x; f < F; f += 256) s += col[f] * col[f];  // (each thread re-reads what it wrote itself)
+    const double nrm = sqrt(s64_block_sum(s, red));
+    for (int f = threadIdx.x; f < F; f += 256) col[f] = col[f] / nrm;
+    if (!UPD && threadIdx.x == 0) wn[k] = nrm;
+}
+
+// h = bsxfun(@times, h, wn') (:160)
+static __global__ __launch_bounds__(256) void k_s64_hscale(double* __restrict__ H, const double* __restrict__ wn, int r, long long n) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) H[i] = H[i] * wn[i % r];
+}
+
+// v = max(v, flr) (:169)
+static __global__ __launch_bounds__(256) void k_s64_floor(double* __restrict__ X, long long n) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) X[i] = fmax(X[i], kS64Flr);
+}
+
+// The divergence terms of src/sparse_nmf.m:248-258 and sum(sparsity .* h) of :261: workgroup b sums its elements (a fixed
+// assignment: grid-stride from b) into part[2 b] and part[2 b + 1].
+template <int MODE>
+__global__ __launch_bounds__(256) void k_s64_obj(const double* __restrict__ V, const double* __restrict__ Lam, long long n_v, double beta,
+                                                 const double* __restrict__ H, int kind, double scalar, const double* __restrict__ S,
+                                                 int r, long long n_h, double* __restrict__ part, const int* stop) {
+    if (*stop) return;
+    __shared__ double red[256];
+    double d = 0.0, sh = 0.0;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n_v; i += (long long)gridDim.x * 256) {
+        const double v = V[i], lam = Lam[i];
+        if (MODE == S64_KL) {
+            d += v * log(v / lam) - v + lam;
+        } else if (MODE == S64_ED) {
+            d += (v - lam) * (v - lam);
+        } else if (MODE == S64_IS) {
+            const double qq = v / lam;
+            d += qq - log(qq) - 1.0;
+        } else {
+            d += pow(v, beta) + (beta - 1.0) * pow(lam, beta) - beta * v * pow(lam, beta - 1.0);
+        }
+    }
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n_h; i += (long long)gridDim.x * 256)
+        sh += s64_sparsity(kind, scalar, S, i, (int)(i % r)) * H[i];
+    d = s64_block_sum(d, red);
+    sh = s64_block_sum(sh, red);
+    if (threadIdx.x == 0) {
+        part[2 * blockIdx.x] = d;
+        part[2 * blockIdx.x + 1] = sh;
+    }
+}
+
+// One workgroup: div and cost of iteration `it` from the block partials (fixed order), the objective vectors (:263-264)
+// and the convergence test of :272-284 -- on the device, so that the host need not wait for every iteration.
+static __global__ __launch_bounds__(256) void k_s64_stop(const double* __restrict__ part, int n_part, int it, double conv_eps, double div_scale,
+                                                         double* __restrict__ divh, double* __restrict__ costh, Solve64State* st) {
+    if (st->stop) return;
+    __shared__ double red[256];
+    double d = 0.0, sh = 0.0;
+    for (int b = threadIdx.x; b < n_part; b += 256) {
+        d += part[2 * b];
+        sh += part[2 * b + 1];
+    }
+    d = s64_block_sum(d, red);
+    sh = s64_block_sum(sh, red);
+    if (threadIdx.x == 0) {
+        const double div = d / div_scale;  // beta (beta - 1) for the generic divergence (:257), else 1
+        const double cost = div + sh;
+        divh[it - 1] = div;
+        costh[it - 1] = cost;
+        bool fired = false;
+        if (it > 1 && conv_eps > 0.0) {
+            const double e = fabs(cost - st->last_cost) / st->last_cost;  // :274 (NaN compares false, as in MATLAB)
+            fired = e < conv_eps;
+        }
+        if (fired) {
+            st->n_iter = it;
+            st->stop = 1;
+        } else {
+            st->last_cost = cost;
+        }
+    }
+}
+
+}  // namespace snmf

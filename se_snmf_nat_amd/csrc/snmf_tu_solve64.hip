@@ -1,0 +1,264 @@
+// snmf_tu_solve64.hip -- the fp64 solve mode (snmf_sparse_nmf_fp64), kernels in snmf_solve64.h.  A translation unit of its
+// own: the fp32 plan, its kernels and its geometry are not touched, and compile to the code they compiled to before.
+#include "snmf_internal.h"
+#include "snmf_solve64.h"
+
+namespace {
+
+// every device block of one solve; freed on every way out (a failed allocation leaks nothing)
+struct Blocks64 {
+    std::vector<void*> ptrs;
+    hipStream_t st = nullptr;
+    ~Blocks64() {
+        if (st) hipStreamSynchronize(st);
+        for (void* q : ptrs) hipFree(q);
+    }
+    int get(double** p, size_t n) { return get_bytes((void**)p, std::max<size_t>(n, 1) * sizeof(double)); }
+    int get_bytes(void** p, size_t bytes) {
+        *p = nullptr;
+        hipError_t e = hipMalloc(p, bytes);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(SNMF_ERR_NOMEM, "hipMalloc(%zu bytes): %s", bytes, hipGetErrorString(e));
+        }
+        ptrs.push_back(*p);
+        return SNMF_OK;
+    }
+};
+
+inline int grid64(long long n) { return (int)std::max<long long>(1, std::min<long long>((n + 255) / 256, 8192)); }
+inline int n_splits(int K) { return (K + kS64ChunkK - 1) / kS64ChunkK; }
+
+struct Solve64 {
+    hipStream_t st = nullptr;
+    int* stop = nullptr;    // &state->stop
+    double* zbuf = nullptr; // split partials, tight column-major M x N each
+};
+
+// C = A * B with the contraction cut into splits of kS64ChunkK; one split stores straight into C, several go through
+// their partials and k_s64_sumz (chunk order).  The kernel's stores run along n: a C whose smaller stride runs along m
+// is formed as C^T = B^T * A^T, which only relabels the strides.
+int gemm64(const Solve64& s, const double* A, long long rsA, long long csA, const double* B, long long rsB, long long csB, double* C,
+           long long rsC, long long csC, int M, int N, int K, bool do_floor) {
+    const int nz = n_splits(K);
+    Gemm64Args g;
+    g.K = K, g.kchunk = kS64ChunkK, g.stop = s.stop;
+    const bool direct = nz == 1;
+    // the partials of a split product are tight and column-major (unit stride along m)
+    const long long rs = direct ? rsC : 1, cs = direct ? csC : M;
+    if (rs < cs) {  // transposed problem
+        g.A = B, g.rsA = csB, g.csA = rsB;
+        g.B = A, g.rsB = csA, g.csB = rsA;
+        g.M = N, g.N = M, g.rsC = cs, g.csC = rs;
+    } else {
+        g.A = A, g.rsA = rsA, g.csA = csA;
+        g.B = B, g.rsB = rsB, g.csB = csB;
+        g.M = M, g.N = N, g.rsC = rs, g.csC = cs;
+    }
+    g.C = direct ? C : s.zbuf;
+    g.zC = direct ? 0 : (long long)M * N;
+    g.do_floor = direct && do_floor;
+    const long long tiles = (long long)((g.M + 63) / 64) * ((g.N + 63) / 64);
+    if (tiles > 0x7fffffffLL || nz > 65535) return fail(SNMF_ERR_UNSUPPORTED, "fp64 solve: %lld tiles / %d splits exceed the launch grid", tiles, nz);
+    hipLaunchKernelGGL(k_s64_gemm, dim3((unsigned)tiles, nz), dim3(256), 0, s.st, g);
+    HIP_TRY(hipGetLastError());
+    if (!direct) {
+        const long long n = (long long)M * N;
+        hipLaunchKernelGGL(k_s64_sumz, dim3(grid64(n)), dim3(256), 0, s.st, s.zbuf, nz, n, M, C, rsC, csC, do_floor ? 1 : 0, s.stop);
+        HIP_TRY(hipGetLastError());
+    }
+    return SNMF_OK;
+}
+
+template <int MODE>
+int ratio64(const Solve64& s, const double* V, const double* Lam, double* R, double* D, long long n, double beta) {
+    hipLaunchKernelGGL(k_s64_ratio<MODE>, dim3(grid64(n)), dim3(256), 0, s.st, V, Lam, R, D, n, beta, s.stop);
+    HIP_TRY(hipGetLastError());
+    return SNMF_OK;
+}
+
+template <int MODE>
+int obj64(const Solve64& s, const double* V, const double* Lam, long long n_v, double beta, const double* H, int kind, double scalar,
+          const double* S, int r, long long n_h, double* part) {
+    hipLaunchKernelGGL(k_s64_obj<MODE>, dim3(kS64Blocks), dim3(256), 0, s.st, V, Lam, n_v, beta, H, kind, scalar, S, r, n_h, part, s.stop);
+    HIP_TRY(hipGetLastError());
+    return SNMF_OK;
+}
+
+}  // namespace
+
+extern "C" int snmf_sparse_nmf_fp64(snmf_ctx* ctx, const snmf_params* p, const double* V, int64_t ldV, const double* W0,
+                                    const double* H0, const double* sparsity, double* W, double* H, double* div_out,
+                                    double* cost_out, int32_t* n_iter_out) {
+    if (!ctx) return fail(SNMF_ERR_INVALID, "ctx is NULL");
+    if (!V || !W || !H || !W0 || !H0) return fail(SNMF_ERR_INVALID, "V, W and H must be non-NULL");
+    SN_TRY(validate_params(p));
+    const int F = p->F, T = p->T, r = p->r, max_iter = p->max_iter;
+    if (ldV < F) return fail(SNMF_ERR_INVALID, "ldV = %lld < F = %d", (long long)ldV, F);
+    const int kind = p->sparsity_kind;
+    if (kind != SNMF_SPARSITY_SCALAR && !sparsity) return fail(SNMF_ERR_INVALID, "sparsity array required for this sparsity_kind");
+    // masks (src/sparse_nmf.m:142-148, :176-179)
+    std::vector<uint8_t> w_ind(r);
+    int n_h = 0, n_w = 0;
+    for (int k = 0; k < r; ++k) {
+        n_h += p->h_update_ind ? p->h_update_ind[k] != 0 : 1;
+        w_ind[k] = p->w_update_ind ? p->w_update_ind[k] != 0 : 1;
+        n_w += w_ind[k];
+    }
+    if (n_h != 0 && n_h != r)
+        return fail(SNMF_ERR_DIM, "partial h_update_ind (%d of %d rows): dimension mismatch in src/sparse_nmf.m:192/197/202", n_h, r);
+    const bool upd_h = n_h > 0, upd_w = n_w > 0;
+    const double beta = p->beta;
+    const int mode = beta == 1.0 ? S64_KL : (beta == 2.0 ? S64_ED : (beta == 0.0 ? S64_IS : S64_GEN));
+    const bool kl = mode == S64_KL, ed = mode == S64_ED;
+
+    (void)hipGetLastError();
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    Blocks64 mem;
+    mem.st = st;
+    const long long nFT = (long long)F * T, nRT = (long long)r * T, nFR = (long long)F * r;
+    double *dV, *dW, *dH, *dLam, *dR = nullptr, *dD = nullptr, *dNum = nullptr, *dDen = nullptr, *dQ = nullptr, *dP = nullptr;
+    double *dS = nullptr, *dcs = nullptr, *dhs = nullptr, *dsp = nullptr, *dwn, *dpart, *ddiv, *dcost, *dz = nullptr;
+    uint8_t* dwi;
+    Solve64State* dst;
+    SN_TRY(mem.get(&dV, nFT));
+    SN_TRY(mem.get(&dW, nFR));
+    SN_TRY(mem.get(&dH, nRT));
+    SN_TRY(mem.get(&dLam, nFT));
+    if (!ed) SN_TRY(mem.get(&dR, nFT));
+    if (!ed && !kl) SN_TRY(mem.get(&dD, nFT));
+    if (upd_h) {
+        SN_TRY(mem.get(&dNum, nRT));
+        if (!kl) SN_TRY(mem.get(&dDen, nRT));
+        else SN_TRY(mem.get(&dcs, r));
+    }
+    const int n_rowz = (T + kS64RowChunk - 1) / kS64RowChunk;
+    if (upd_w) {
+        SN_TRY(mem.get(&dQ, nFR));
+        if (!kl) SN_TRY(mem.get(&dP, nFR));
+        else {
+            SN_TRY(mem.get(&dhs, r));
+            SN_TRY(mem.get(&dsp, (size_t)n_rowz * r));
+        }
+    }
+    // split partials: the largest nz * M * N over the products that are split at all
+    {
+        size_t need = 0;
+        auto want = [&](long long M, long long N, int K) {
+            const int nz = n_splits(K);
+            if (nz > 1) need = std::max(need, (size_t)nz * (size_t)M * (size_t)N);
+        };
+        want(F, T, r);              // Lam = W * H
+        if (upd_h) want(r, T, F);   // W' * R, W' * D
+        if (upd_w) want(F, r, T);   // R * H', D * H'
+        if (need) SN_TRY(mem.get(&dz, need));
+    }
+    const size_t n_s = kind == SNMF_SPARSITY_SCALAR ? 0 : (kind == SNMF_SPARSITY_RVEC ? (size_t)r : (size_t)nRT);
+    if (n_s) SN_TRY(mem.get(&dS, n_s));
+    SN_TRY(mem.get(&dwn, r));
+    SN_TRY(mem.get(&dpart, 2 * kS64Blocks));
+    SN_TRY(mem.get(&ddiv, std::max(max_iter, 1)));
+    SN_TRY(mem.get(&dcost, std::max(max_iter, 1)));
+    SN_TRY(mem.get_bytes((void**)&dwi, (size_t)r));
+    SN_TRY(mem.get_bytes((void**)&dst, sizeof(Solve64State)));
+
+    // upload (tight column-major on the device)
+    if (ldV == F || T == 1) HIP_TRY(hipMemcpyAsync(dV, V, (size_t)nFT * 8, hipMemcpyHostToDevice, st));
+    else HIP_TRY(hipMemcpy2DAsync(dV, (size_t)F * 8, V, (size_t)ldV * 8, (size_t)F * 8, (size_t)T, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dW, W0, (size_t)nFR * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dH, H0, (size_t)nRT * 8, hipMemcpyHostToDevice, st));
+    if (n_s) HIP_TRY(hipMemcpyAsync(dS, sparsity, n_s * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dwi, w_ind.data(), (size_t)r, hipMemcpyHostToDevice, st));
+    Solve64State h_state;
+    h_state.stop = 0, h_state.n_iter = 0, h_state.last_cost = INFINITY;  // :168
+    HIP_TRY(hipMemcpyAsync(dst, &h_state, sizeof(h_state), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(ddiv, 0, (size_t)std::max(max_iter, 1) * 8, st));   // :171-173
+    HIP_TRY(hipMemsetAsync(dcost, 0, (size_t)std::max(max_iter, 1) * 8, st));
+    HIP_TRY(hipStreamSynchronize(st));  // (the host arrays are pageable: the sources may be reused from here on)
+
+    Solve64 s;
+    s.st = st, s.stop = &dst->stop, s.zbuf = dz;
+    const double scalar = p->sparsity_scalar;
+
+    // ---- initial scaling (:157-169)
+    hipLaunchKernelGGL((k_s64_wupd<true, false>), dim3(r), dim3(256), 0, st, dW, nullptr, nullptr, nullptr, nullptr, F, dwn, s.stop);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_s64_hscale, dim3(grid64(nRT)), dim3(256), 0, st, dH, dwn, r, nRT);
+    HIP_TRY(hipGetLastError());
+    if (p->floor_v) {
+        hipLaunchKernelGGL(k_s64_floor, dim3(grid64(nFT)), dim3(256), 0, st, dV, nFT);
+        HIP_TRY(hipGetLastError());
+    }
+    auto lam = [&]() { return gemm64(s, dW, 1, F, dH, 1, r, dLam, 1, F, F, T, r, true); };  // lambda = max(w * h, flr)
+    auto ratio = [&]() -> int {
+        switch (mode) {
+            case S64_KL: return ratio64<S64_KL>(s, dV, dLam, dR, dD, nFT, beta);
+            case S64_IS: return ratio64<S64_IS>(s, dV, dLam, dR, dD, nFT, beta);
+            case S64_GEN: return ratio64<S64_GEN>(s, dV, dLam, dR, dD, nFT, beta);
+            default: return SNMF_OK;  // Euclidean: R = V, D = Lam
+        }
+    };
+    const double* Rm = ed ? dV : dR;
+    const double* Dm = ed ? dLam : dD;
+    SN_TRY(lam());
+
+    const bool polling = p->cost_check && p->conv_eps > 0.0;
+    const double div_scale = mode == S64_GEN ? beta * (beta - 1.0) : 1.0;
+    for (int it = 1; it <= max_iter; ++it) {
+        if (upd_h) {  // :189-208
+            SN_TRY(ratio());
+            SN_TRY(gemm64(s, dW, F, 1, Rm, 1, F, dNum, 1, r, r, T, F, false));  // W' * R
+            if (!kl) SN_TRY(gemm64(s, dW, F, 1, Dm, 1, F, dDen, 1, r, r, T, F, false));  // W' * D
+            else {
+                hipLaunchKernelGGL(k_s64_colsum, dim3(r), dim3(256), 0, st, dW, F, dcs, s.stop);
+                HIP_TRY(hipGetLastError());
+            }
+            if (kl) hipLaunchKernelGGL(k_s64_hupd<true>, dim3(grid64(nRT)), dim3(256), 0, st, dH, dNum, dDen, dcs, kind, scalar, dS, r, nRT, s.stop);
+            else hipLaunchKernelGGL(k_s64_hupd<false>, dim3(grid64(nRT)), dim3(256), 0, st, dH, dNum, dDen, dcs, kind, scalar, dS, r, nRT, s.stop);
+            HIP_TRY(hipGetLastError());
+            SN_TRY(lam());
+        }
+        if (upd_w) {  // :212-244
+            SN_TRY(ratio());
+            SN_TRY(gemm64(s, Rm, 1, F, dH, r, 1, dQ, 1, F, F, r, T, false));  // R * H'
+            if (!kl) SN_TRY(gemm64(s, Dm, 1, F, dH, r, 1, dP, 1, F, F, r, T, false));  // D * H'
+            else {
+                hipLaunchKernelGGL(k_s64_rowsum, dim3((r + 255) / 256, n_rowz), dim3(256), 0, st, dH, r, T, kS64RowChunk, dsp, s.stop);
+                HIP_TRY(hipGetLastError());
+                hipLaunchKernelGGL(k_s64_sumz, dim3(grid64(r)), dim3(256), 0, st, dsp, n_rowz, (long long)r, r, dhs, 1LL, 0LL, 0, s.stop);
+                HIP_TRY(hipGetLastError());
+            }
+            if (kl) hipLaunchKernelGGL((k_s64_wupd<true, true>), dim3(r), dim3(256), 0, st, dW, dQ, dP, dhs, dwi, F, dwn, s.stop);
+            else hipLaunchKernelGGL((k_s64_wupd<false, true>), dim3(r), dim3(256), 0, st, dW, dQ, dP, dhs, dwi, F, dwn, s.stop);
+            HIP_TRY(hipGetLastError());
+            SN_TRY(lam());
+        }
+        if (p->cost_check) {  // :248-284
+            switch (mode) {
+                case S64_KL: SN_TRY((obj64<S64_KL>(s, dV, dLam, nFT, beta, dH, kind, scalar, dS, r, nRT, dpart))); break;
+                case S64_ED: SN_TRY((obj64<S64_ED>(s, dV, dLam, nFT, beta, dH, kind, scalar, dS, r, nRT, dpart))); break;
+                case S64_IS: SN_TRY((obj64<S64_IS>(s, dV, dLam, nFT, beta, dH, kind, scalar, dS, r, nRT, dpart))); break;
+                default: SN_TRY((obj64<S64_GEN>(s, dV, dLam, nFT, beta, dH, kind, scalar, dS, r, nRT, dpart))); break;
+            }
+            hipLaunchKernelGGL(k_s64_stop, dim3(1), dim3(256), 0, st, dpart, kS64Blocks, it, p->conv_eps, div_scale, ddiv, dcost, dst);
+            HIP_TRY(hipGetLastError());
+            if (polling && (it % 8 == 0) && it < max_iter) {  // the host looks every 8 iterations; the kernels past a stop are no-ops
+                HIP_TRY(hipMemcpyAsync(&h_state, dst, sizeof(h_state), hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipStreamSynchronize(st));
+                if (h_state.stop) break;
+            }
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(&h_state, dst, sizeof(h_state), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(W, dW, (size_t)nFR * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(H, dH, (size_t)nRT * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    std::vector<double> hd(std::max(max_iter, 1)), hc(std::max(max_iter, 1));
+    HIP_TRY(hipMemcpy(hd.data(), ddiv, hd.size() * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(hc.data(), dcost, hc.size() * 8, hipMemcpyDeviceToHost));
+    if (div_out) std::copy(hd.begin(), hd.begin() + max_iter, div_out);
+    if (cost_out) std::copy(hc.begin(), hc.begin() + max_iter, cost_out);
+    if (n_iter_out) *n_iter_out = h_state.stop ? h_state.n_iter : max_iter;
+    return SNMF_OK;
+}
