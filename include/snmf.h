@@ -325,6 +325,43 @@ int snmf_run_basis_train_audio_f64(snmf_ctx* ctx, const snmf_params* p, const sn
                                    const int64_t* sample_idx, int32_t train_exemplar, const double* H0, uint64_t seed,
                                    double* B_DFT, double* A_DFT, double* B_Mel, double* A_Mel, int32_t* n_iter_out);
 
+/* ---- the fp64 mode of the front-end and of the training callers (added within 5) -----------------
+ * The entries above take float samples and compute in fp32 whatever the type of the host matrices.  These compute in double
+ * from the samples to the dictionaries, as snmf_sparse_nmf_fp64 does for one solve: samples, Mel table, features and factors
+ * are double, y = x + d is formed in double, the transform is a double FFT on host-computed double twiddles, every matrix
+ * lives in HBM tight and column-major, and every solve runs the kernels of snmf_sparse_nmf_fp64.  Every sum has a fixed order:
+ * two calls on one input give the same bits.  One device; there is no _multi_ form.
+ *
+ * Front-end: arguments and meaning of the _f32 namesakes (host or device buffers), all values double. */
+int snmf_stft_features_fp64(snmf_ctx* ctx, const snmf_stft_params* sp, const double* samples, int64_t n_samples,
+                            int samples_on_device, double* V_out, int64_t ld, int out_on_device, int32_t* n_frames_out);
+int snmf_mel_features_fp64(snmf_ctx* ctx, const double* mel, int32_t M, int32_t n, int32_t K, const double* V, int64_t ldv,
+                           int32_t T, double* out, int64_t ldo, int on_device);
+/* (the first column comes out as the input's, bit for bit) */
+int snmf_tf_dd_fp64(snmf_ctx* ctx, double alpha_eta, int32_t F, int32_t T, const double* X, int64_t ldx, double* out,
+                    int64_t ldo, int on_device);
+/* The 3-solve loop on formed features: arguments and meaning of snmf_run_basis_dnmf_f64.  Y, X, D are uploaded once each,
+ * A_hat never leaves HBM between the solves (solves 2 / 3 take copies of its row blocks as init_h: the solve rescales its
+ * init_h, src/sparse_nmf.m:157-159), only B_hat (and A_hat if asked for) comes back.  Bit-identical to three
+ * snmf_sparse_nmf_fp64 calls.  H0 == NULL: the Philox stream of snmf_plan_set_h_random written as doubles (its values hold
+ * 24 bits: the fp32 entries start from the same numbers).  A non-scalar p->sparsity_kind is SNMF_ERR_DIM. */
+int snmf_run_basis_dnmf_fp64(snmf_ctx* ctx, const snmf_params* p, int32_t R_x, int32_t R_d, const double* Y, int64_t ldY,
+                             const double* X, int64_t ldX, const double* D, int64_t ldD, const double* B, int64_t ldB,
+                             const double* H0, uint64_t seed, double* B_hat, int64_t ldBh, double* A_hat, int64_t ldA,
+                             int32_t* n_iter_out);
+/* As snmf_run_basis_dnmf_audio_f64 with x, d and mel as doubles (mel != NULL: run_basis_DNMF_Mel.m).  p->F / p->T that do
+ * not match the features are SNMF_ERR_DIM. */
+int snmf_run_basis_dnmf_audio_fp64(snmf_ctx* ctx, const snmf_params* p, const snmf_stft_params* sp, int32_t R_x, int32_t R_d,
+                                   const double* x, int64_t n_x, const double* d, int64_t n_d, const double* mel, int32_t mel_M,
+                                   const double* B, int64_t ldB, const double* H0, uint64_t seed, double* B_hat, int64_t ldBh,
+                                   double* A_hat, int64_t ldA, int32_t* n_iter_out);
+/* As snmf_run_basis_train_audio_f64 with s_full and mel as doubles: TF_DD, train_exemplar, both full-update solves (both
+ * start from the same H0) and the mel == NULL DFT-only form.  A sparsity vector or matrix is SNMF_ERR_UNSUPPORTED. */
+int snmf_run_basis_train_audio_fp64(snmf_ctx* ctx, const snmf_params* p, const snmf_stft_params* sp, double alpha_eta_dd,
+                                    const double* mel, int32_t mel_M, const double* s_full, int64_t n_samples,
+                                    const int64_t* sample_idx, int32_t train_exemplar, const double* H0, uint64_t seed,
+                                    double* B_DFT, double* A_DFT, double* B_Mel, double* A_Mel, int32_t* n_iter_out);
+
 /* ---- missing-data imputation variants --------------------------------
  * [v_MDI, h, objective] = snmf_mdi(v, Dm, p)     src/snmf_mdi.m:1      (binary observed mask)
  * [v_MDI, h, objective] = snmf_mdi_Sm(v, Sm, p)  src/snmf_mdi_Sm.m:1   (soft mask in [0,1])

@@ -11,6 +11,15 @@ function [B_hat] = run_basis_DNMF(x, d, B, p)
 %   first draw after the re-seed); the same two statements run below.  Set p.snmf_device_rng = 1 to let the engine draw
 %   them on the device instead (no r x n array crosses PCIe; the values then come from Philox, not from MATLAB's generator).
 if ~isfield(p, 'random_seed'), p.random_seed = 1; end
+if isfield(p, 'snmf_precision') && ~isempty(p.snmf_precision)
+    % p.snmf_precision = 'fp64' -- the fp64 mode (snmf_run_basis_dnmf_audio_fp64): the waveforms cross as doubles and
+    % y = x + d, the three feature sets and the three solves are computed in double on the device; 'fp32' is the default.  The MEX
+    % file refuses any other string, and 'fp64' together with a device list (p.snmf_devices).
+    p.snmf_precision = char(p.snmf_precision);
+end
+if isfield(p, 'snmf_precision') && strcmp(p.snmf_precision, 'fp64') && isfield(p, 'snmf_devices') && numel(p.snmf_devices) > 1
+    error('snmf:unsupported', 'p.snmf_precision = ''fp64'' runs on one device (no p.snmf_devices)');
+end
 n = snmf_dnmf_mex('nframes', min(length(x), length(d)), p);
 if isfield(p, 'snmf_device_rng') && p.snmf_device_rng
     H0 = [];

@@ -7,6 +7,12 @@ function [B_DFT_init, B_Mel_init, A_DFT_init, A_Mel_init] = snmf_basis_train_blo
 %   The draws stay in MATLAB, in the reference's order: rng(1); randsample(...) (:80-81), then what both sparse_nmf calls draw
 %   after re-seeding, rand('seed', p.random_seed); rand(r, n) (src/sparse_nmf.m:112-114,:133-134 -- the same matrix for both).
 if ~isfield(p, 'random_seed'), p.random_seed = 1; end
+if isfield(p, 'snmf_precision') && ~isempty(p.snmf_precision)
+    % p.snmf_precision = 'fp64' -- the fp64 mode (snmf_run_basis_train_audio_fp64): the waveforms cross as doubles and
+    % TF_mag, TF_DD, TF_Mel, the exemplar columns and both solves are computed in double on the device; 'fp32' is the default.  The MEX
+    % file refuses any other string.
+    p.snmf_precision = char(p.snmf_precision);
+end
 melmat = mel_matrix(p.fs, p.F_order, p.fftlength, 1, p.fs/2)';
 pp = p; pp.DCbin = DC_bin;
 m = snmf_dnmf_mex('nframes', length(s_full), pp);

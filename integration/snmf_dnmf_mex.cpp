@@ -1,5 +1,6 @@
 // snmf_dnmf_mex.cpp -- MATLAB MEX shim for the device-resident training callers of libsnmf_hip.so
-// (C ABI: include/snmf.h, snmf_run_basis_dnmf_audio_f64 / snmf_run_basis_train_audio_f64 / snmf_stft_num_frames).
+// (C ABI: include/snmf.h, snmf_run_basis_dnmf_audio_f64 / snmf_run_basis_train_audio_f64 / snmf_stft_num_frames, and their
+// fp64-mode twins snmf_run_basis_dnmf_audio_fp64 / snmf_run_basis_train_audio_fp64).
 //
 // Replaces whole reference FUNCTIONS rather than single sparse_nmf calls, so that the spectrograms and the activations of
 // solve 1 never come back to MATLAB between the solves:
@@ -15,6 +16,8 @@
 //       src/sparse_nmf.m:112-114,:133-134 would -- or [] to let the engine draw it on the device (snmf_plan_set_h_random).
 //   p : the settings struct (framelength, frameshift, fftlength, DCbin, win_STFT, preemph, pow, nonzerofloor, Splice, R_x, R_d,
 //       cf / beta, sparsity, max_iter, conv_eps, cost_check, random_seed, domain_DD, alpha_eta, train_Exemplar)
+//       p.snmf_precision = 'fp64': 'dnmf' and 'train' run in double from the samples on (waveforms, melmat, features and all
+//       solves; the *_fp64 entries); 'fp32' or absent: the default.  Any other string is an error, as is 'fp64' with 'dnmf_multi'.
 //
 // Written against the documented MEX C API; MATLAB is not available in the build container, so __graft_entry__.build() only
 // SYNTAX-CHECKS this file against integration/mex_stub/mex.h.  Build:
@@ -59,9 +62,24 @@ static std::vector<float> to_float(const mxArray* a, const char* what) {
     for (size_t i = 0; i < n; ++i) out[i] = (float)d[i];
     return out;
 }
-// melmat (F_order x n, column-major in MATLAB) -> ROW-major float for the C ABI
-static std::vector<float> mel_rows(const mxArray* m, int* M, int n_expect) {
-    std::vector<float> out;
+static const double* doubles_of(const mxArray* a, const char* what) {
+    if (!mxIsDouble(a) || mxIsComplex(a)) mexErrMsgIdAndTxt("snmf:type", "%s must be real double", what);
+    return mxGetDoubles(a);
+}
+// p.snmf_precision = 'fp64': the fp64 mode; any other string but 'fp32' is an error (as opts.precision of sparse_nmf_mex.cpp)
+static bool fp64_mode(const mxArray* p) {
+    const mxArray* pr = mxGetField(p, 0, "snmf_precision");
+    if (!pr || mxIsEmpty(pr)) return false;
+    char prec[16] = "";
+    if (!mxIsChar(pr) || mxGetString(pr, prec, sizeof prec) != 0) mexErrMsgIdAndTxt("snmf:type", "p.snmf_precision must be 'fp32' or 'fp64'");
+    if (std::strcmp(prec, "fp64") == 0) return true;
+    if (std::strcmp(prec, "fp32") != 0) mexErrMsgIdAndTxt("snmf:type", "p.snmf_precision must be 'fp32' or 'fp64' (got '%s')", prec);
+    return false;
+}
+// melmat (F_order x n, column-major in MATLAB) -> ROW-major float (double in the fp64 mode) for the C ABI
+template <typename T>
+static std::vector<T> mel_rows(const mxArray* m, int* M, int n_expect) {
+    std::vector<T> out;
     *M = 0;
     if (!m || mxIsEmpty(m)) return out;
     if (!mxIsDouble(m) || mxIsComplex(m) || (int)mxGetN(m) != n_expect) mexErrMsgIdAndTxt("snmf:dim", "melmat must be F_order x (fftlength/2+1) double");
@@ -69,7 +87,7 @@ static std::vector<float> mel_rows(const mxArray* m, int* M, int n_expect) {
     const double* d = mxGetDoubles(m);
     out.resize((size_t)*M * n_expect);
     for (int j = 0; j < *M; ++j)
-        for (int f = 0; f < n_expect; ++f) out[(size_t)j * n_expect + f] = (float)d[(size_t)f * *M + j];
+        for (int f = 0; f < n_expect; ++f) out[(size_t)j * n_expect + f] = (T)d[(size_t)f * *M + j];
     return out;
 }
 static void fill_stft(const mxArray* p, std::vector<double>& win, snmf_stft_params* sp, double dcbin) {
@@ -132,6 +150,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         if (nrhs != 8 || !mxIsStruct(prhs[6])) mexErrMsgIdAndTxt("snmf:nargin", "usage: [B_hat, n_iter] = snmf_dnmf_mex('dnmf_multi', Y, X, D, B, H0, p, devices)");
         const mxArray *Y = prhs[1], *X = prhs[2], *D = prhs[3], *B = prhs[4], *H0 = prhs[5], *p = prhs[6], *dv = prhs[7];
         const int R_x = (int)field(p, "R_x"), R_d = (int)field(p, "R_d");
+        if (fp64_mode(p)) mexErrMsgIdAndTxt("snmf:unsupported", "p.snmf_precision = 'fp64' runs on one device (no device list)");
         snmf_params q;
         fill_solver(p, &q);
         q.F = (int32_t)mxGetM(Y);
@@ -170,16 +189,23 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     if (!std::strcmp(cmd, "dnmf")) {
         if (nrhs != 7 || !mxIsStruct(prhs[5])) mexErrMsgIdAndTxt("snmf:nargin", "usage: [B_hat, n_iter] = snmf_dnmf_mex('dnmf', x, d, B, H0, p, melmat)");
         const mxArray *B = prhs[3], *H0 = prhs[4], *p = prhs[5];
-        const std::vector<float> x = to_float(prhs[1], "x"), d = to_float(prhs[2], "d");
+        const bool f64 = fp64_mode(p);
+        std::vector<float> x, d, mel;
+        std::vector<double> mel64;
+        const double *x64 = nullptr, *d64 = nullptr;
+        if (f64) x64 = doubles_of(prhs[1], "x"), d64 = doubles_of(prhs[2], "d");  // the fp64 mode reads MATLAB's doubles where they lie
+        else x = to_float(prhs[1], "x"), d = to_float(prhs[2], "d");
+        const size_t n_x = mxGetNumberOfElements(prhs[1]), n_d = mxGetNumberOfElements(prhs[2]);
         fill_stft(p, win, &sp, field(p, "DCbin"));
         int M = 0;
         const int nb = sp.fftlength / 2 + 1, K = 2 * sp.splice + 1;
-        const std::vector<float> mel = mel_rows(prhs[6], &M, nb);
+        if (f64) mel64 = mel_rows<double>(prhs[6], &M, nb);
+        else mel = mel_rows<float>(prhs[6], &M, nb);
         const int R_x = (int)field(p, "R_x"), R_d = (int)field(p, "R_d");
         snmf_params q;
         fill_solver(p, &q);
         q.F = M ? K * M : K * nb;
-        q.T = (int32_t)snmf_stft_num_frames(&sp, (int64_t)(x.size() < d.size() ? x.size() : d.size()));
+        q.T = (int32_t)snmf_stft_num_frames(&sp, (int64_t)(n_x < n_d ? n_x : n_d));
         q.r = R_x + R_d;
         if (!mxIsDouble(B) || mxIsComplex(B) || (int)mxGetM(B) != q.F || (int)mxGetN(B) != q.r)
             mexErrMsgIdAndTxt("snmf:dim", "B must be %d x (R_x + R_d = %d) double", q.F, q.r);
@@ -190,9 +216,11 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         }
         plhs[0] = mxCreateDoubleMatrix((mwSize)q.F, (mwSize)q.r, mxREAL);
         int32_t nit[3] = {0, 0, 0};
-        const int st = snmf_run_basis_dnmf_audio_f64(g_ctx, &q, &sp, R_x, R_d, x.data(), (int64_t)x.size(), d.data(), (int64_t)d.size(),
-                                                     M ? mel.data() : nullptr, M, mxGetDoubles(B), q.F, h0,
-                                                     device_seed(p, h0 != nullptr), mxGetDoubles(plhs[0]), q.F, nullptr, q.r, nit);
+        const uint64_t seed = device_seed(p, h0 != nullptr);
+        const int st = f64 ? snmf_run_basis_dnmf_audio_fp64(g_ctx, &q, &sp, R_x, R_d, x64, (int64_t)n_x, d64, (int64_t)n_d, M ? mel64.data() : nullptr, M,
+                                                            mxGetDoubles(B), q.F, h0, seed, mxGetDoubles(plhs[0]), q.F, nullptr, q.r, nit)
+                           : snmf_run_basis_dnmf_audio_f64(g_ctx, &q, &sp, R_x, R_d, x.data(), (int64_t)n_x, d.data(), (int64_t)n_d, M ? mel.data() : nullptr, M,
+                                                           mxGetDoubles(B), q.F, h0, seed, mxGetDoubles(plhs[0]), q.F, nullptr, q.r, nit);
         if (st != SNMF_OK) mexErrMsgIdAndTxt("snmf:solve", "%s", snmf_last_error());
         if (nlhs > 1) {
             plhs[1] = mxCreateDoubleMatrix(1, 3, mxREAL);
@@ -203,11 +231,18 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     if (!std::strcmp(cmd, "train")) {
         if (nrhs != 7 || !mxIsStruct(prhs[4])) mexErrMsgIdAndTxt("snmf:nargin", "usage: [B_DFT,B_Mel,A_DFT,A_Mel,n_iter] = snmf_dnmf_mex('train', s_full, sample_idx, H0, p, melmat, DC_bin)");
         const mxArray *idx = prhs[2], *H0 = prhs[3], *p = prhs[4];
-        const std::vector<float> s = to_float(prhs[1], "s_full");
+        const bool f64 = fp64_mode(p);
+        std::vector<float> s, mel;
+        std::vector<double> mel64;
+        const double* s64 = nullptr;
+        if (f64) s64 = doubles_of(prhs[1], "s_full");
+        else s = to_float(prhs[1], "s_full");
+        const size_t n_s = mxGetNumberOfElements(prhs[1]);
         fill_stft(p, win, &sp, mxGetScalar(prhs[6]));
         int M = 0;
         const int nb = sp.fftlength / 2 + 1, K = 2 * sp.splice + 1;
-        const std::vector<float> mel = mel_rows(prhs[5], &M, nb);
+        if (f64) mel64 = mel_rows<double>(prhs[5], &M, nb);
+        else mel = mel_rows<float>(prhs[5], &M, nb);
         if (!M) mexErrMsgIdAndTxt("snmf:dim", "melmat is required (run_basis_train.m:70-78 always forms TF_Mel)");
         snmf_params q;
         const bool exemplar = field_or(p, "train_Exemplar", 0) != 0.0;
@@ -220,7 +255,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
             fill_solver(p, &q);
         }
         q.F = K * nb;
-        q.T = (int32_t)snmf_stft_num_frames(&sp, (int64_t)s.size());
+        q.T = (int32_t)snmf_stft_num_frames(&sp, (int64_t)n_s);
         q.r = (int32_t)mxGetNumberOfElements(idx);
         if (!mxIsDouble(idx) || q.r < 1) mexErrMsgIdAndTxt("snmf:dim", "sample_idx must be a double vector of 1-based frame indices");
         std::vector<int64_t> i0((size_t)q.r);
@@ -236,9 +271,12 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         mxArray* AM = exemplar ? mxCreateDoubleScalar(0.0) : mxCreateDoubleMatrix((mwSize)q.r, (mwSize)q.T, mxREAL);
         int32_t nit[2] = {0, 0};
         const double dd = field_or(p, "domain_DD", 0) != 0.0 ? field(p, "alpha_eta") : -1.0;  // :64-67
-        const int st = snmf_run_basis_train_audio_f64(g_ctx, &q, &sp, dd, mel.data(), M, s.data(), (int64_t)s.size(), i0.data(), exemplar ? 1 : 0,
-                                                      h0, device_seed(p, h0 != nullptr || exemplar), mxGetDoubles(plhs[0]),
-                                                      exemplar ? nullptr : mxGetDoubles(AD), mxGetDoubles(BM), exemplar ? nullptr : mxGetDoubles(AM), nit);
+        const uint64_t seed = device_seed(p, h0 != nullptr || exemplar);
+        double *ad = exemplar ? nullptr : mxGetDoubles(AD), *am = exemplar ? nullptr : mxGetDoubles(AM);
+        const int st = f64 ? snmf_run_basis_train_audio_fp64(g_ctx, &q, &sp, dd, mel64.data(), M, s64, (int64_t)n_s, i0.data(), exemplar ? 1 : 0, h0, seed,
+                                                             mxGetDoubles(plhs[0]), ad, mxGetDoubles(BM), am, nit)
+                           : snmf_run_basis_train_audio_f64(g_ctx, &q, &sp, dd, mel.data(), M, s.data(), (int64_t)n_s, i0.data(), exemplar ? 1 : 0, h0, seed,
+                                                            mxGetDoubles(plhs[0]), ad, mxGetDoubles(BM), am, nit);
         if (st != SNMF_OK) {
             mxDestroyArray(BM);
             mxDestroyArray(AD);

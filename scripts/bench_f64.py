@@ -14,6 +14,14 @@ W'*R, R*H') and, with --f64-mfma-tflops X (the "f64 16x16x4" line of scripts/mfm
 that rate as a fraction of the measured f64 MFMA rate.
 
     python scripts/bench_f64.py [--shapes c2,a11] [--f64-mfma-tflops X] [--out profiles/solve_f64_bench.jsonl]
+
+--legs dnmf,mel: the resident fp64 DNMF loop (run_basis_dnmf(..., precision="fp64"): snmf_run_basis_dnmf_fp64) on BASELINE
+config 4 (513 x 100000, R_x = R_d = 100, KL, 3 solves x --dnmf-iters iterations) and on its 64-row Mel twin, each next to
+the three separate sparse_nmf(precision="fp64") calls it replaces (resident=False) and to the fp32 resident call.  Wall time
+of the whole call, transfers included (that is what the resident form saves), minimum over --reps; h0 is an array drawn
+outside the timed region.  One JSON line per leg is appended to profiles/train_f64_bench.jsonl.
+
+    python scripts/bench_f64.py --legs dnmf,mel [--dnmf-iters 50] [--reps 2]
 """
 import argparse
 import json
@@ -38,8 +46,44 @@ def timed(fn, reps):
     return best
 
 
+DNMF_LEGS = {"dnmf": (513, 100000, 100, 100), "mel": (64, 100000, 100, 100)}
+
+
+def dnmf_legs(a):
+    from se_snmf_nat_amd import Context, run_basis_dnmf
+    ctx = Context(0)
+    out = os.path.join(ROOT, "profiles", "train_f64_bench.jsonl") if a.out.endswith("solve_f64_bench.jsonl") else a.out
+    for name in a.legs.split(","):
+        F, T, Rx, Rd = DNMF_LEGS[name]
+        rd = np.random.default_rng(1)
+        X = np.asfortranarray(rd.gamma(0.5, 1.0, (F, Rx)) @ rd.gamma(0.3, 1.0, (Rx, T)))
+        D = np.asfortranarray(rd.gamma(0.5, 1.0, (F, Rd)) @ rd.gamma(0.3, 1.0, (Rd, T)))
+        Y = np.asfortranarray(X + D + 1e-9)
+        B = np.asfortranarray(np.random.default_rng(3).random((F, Rx + Rd)))
+        H0 = np.asfortranarray(np.random.RandomState(1).random_sample((Rx + Rd, T)))
+        p = dict(cf="kl", sparsity=5, max_iter=a.dnmf_iters, conv_eps=0, cost_check=1, random_seed=1)
+        modes = (("fp64_resident", dict(precision="fp64")), ("fp64_three_calls", dict(precision="fp64", resident=False)),
+                 ("fp32_resident", dict()))
+        line = dict(leg=name, F=F, T=T, R_x=Rx, R_d=Rd, cf="kl", sparsity=5, iters_per_solve=a.dnmf_iters, reps=a.reps)
+        res = {}
+        for mode, kw in modes:
+            run_basis_dnmf(Y[:, :4096], X[:, :4096], D[:, :4096], B, Rx, Rd, dict(p, max_iter=2), ctx=ctx, h0=H0[:, :4096].copy(order="F"), **kw)  # warm-up
+            t = timed(lambda: res.__setitem__(mode, run_basis_dnmf(Y, X, D, B, Rx, Rd, p, ctx=ctx, h0=H0, **kw)), a.reps)
+            line[mode + "_s"] = round(t, 4)
+            print(f"{name} {mode}: {t:.3f} s per call ({3 * a.dnmf_iters / t:.1f} solver iterations/s)", flush=True)
+        line["three_calls_over_resident"] = line["fp64_three_calls_s"] / line["fp64_resident_s"]
+        line["fp64_over_fp32_resident"] = line["fp64_resident_s"] / line["fp32_resident_s"]
+        line["resident_equals_three_calls_bitwise"] = bool(res["fp64_resident"][0].tobytes() == res["fp64_three_calls"][0].tobytes())
+        line["rel_fp32_vs_fp64_B_hat"] = float(np.linalg.norm(res["fp32_resident"][0] - res["fp64_resident"][0]) / np.linalg.norm(res["fp64_resident"][0]))
+        with open(out, "a") as f:
+            f.write(json.dumps(line) + "\n")
+        print(json.dumps(line), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--legs", default="", help="dnmf,mel: the resident fp64 DNMF loop instead of the one-shot shapes")
+    ap.add_argument("--dnmf-iters", type=int, default=50)
     ap.add_argument("--shapes", default="c2,a11")
     ap.add_argument("--n64", default="20,120", help="N1,N2 of the fp64 calls")
     ap.add_argument("--n32", default="20,220", help="N1,N2 of the fp32 calls")
@@ -47,6 +91,8 @@ def main():
     ap.add_argument("--f64-mfma-tflops", type=float, default=None)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "solve_f64_bench.jsonl"))
     a = ap.parse_args()
+    if a.legs:
+        return dnmf_legs(a)
     from bench import SPARSITY, make_problem
     from se_snmf_nat_amd import Context, sparse_nmf
     ctx = Context(0)

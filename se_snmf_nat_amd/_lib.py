@@ -32,12 +32,13 @@ _TU_HDRS = {
     "snmf_tu_online_f64.hip": ["snmf_online_common.h", "snmf_online_f64.h", "snmf_online_f64_host.h", "snmf_online_classes.h"],
     "snmf_tu_online_batch.hip": ["snmf_online_common.h", "snmf_online_batch.h", "snmf_online_classes.h"],
     "snmf_tu_multi.hip": ["snmf_multi.h"],
-    "snmf_tu_dnmf.hip": ["snmf_frontend.h"],
+    "snmf_tu_dnmf.hip": ["snmf_frontend.h", "snmf_philox.h"],
     "snmf_tu_smallf.hip": ["snmf_smallf.h"],
     "snmf_tu_itersf.hip": ["snmf_smallf.h"],
     "snmf_tu_smallr.hip": ["snmf_smallf.h", "snmf_smallr.h"],
     "snmf_tu_geometry.hip": ["snmf_generic.h"],
-    "snmf_tu_solve64.hip": ["snmf_solve64.h"],
+    "snmf_tu_solve64.hip": ["snmf_solve64.h", "snmf_solve64_core.h"],
+    "snmf_tu_train64.hip": ["snmf_online_common.h", "snmf_frontend64.h", "snmf_philox.h", "snmf_solve64_core.h"],
 }
 HDRS = sorted(_glob.glob(os.path.join(_HERE, "csrc", "*.h"))) + [os.path.join(_ROOT, "include", "snmf.h")]
 
@@ -74,6 +75,8 @@ SYMBOLS = [
     "snmf_run_basis_dnmf_multi_f64", "snmf_run_basis_dnmf_multi_f32",
     "snmf_multi_release_cache", "snmf_multi_cached_teams",
     "snmf_sparse_nmf_fp64",
+    "snmf_stft_features_fp64", "snmf_mel_features_fp64", "snmf_tf_dd_fp64",
+    "snmf_run_basis_dnmf_fp64", "snmf_run_basis_dnmf_audio_fp64", "snmf_run_basis_train_audio_fp64",
     "snmf_rccl_available", "snmf_rccl_get_unique_id", "snmf_rccl_comm_create", "snmf_rccl_comm_destroy", "snmf_plan_run_sharded_rccl",
 ]
 ABI_VERSION = 5  # include/snmf.h: SNMF_ABI_VERSION this binding was written against
@@ -324,6 +327,11 @@ def load():
     for ty in ("f64", "f32"):
         sig[f"snmf_sparse_nmf_oop_{ty}"] = (C.c_int, [vp, PP, vp, i64, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i32)])
     sig["snmf_sparse_nmf_fp64"] = (C.c_int, [vp, PP, vp, i64, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i32)])
+    # the fp64 mode of the front-end and of the training callers: the prototypes of the fp32 / f64 namesakes, doubles throughout
+    for nm in ("snmf_stft_features", "snmf_mel_features", "snmf_tf_dd"):
+        sig[nm + "_fp64"] = sig[nm + "_f32"]
+    for nm in ("snmf_run_basis_dnmf", "snmf_run_basis_dnmf_audio", "snmf_run_basis_train_audio"):
+        sig[nm + "_fp64"] = sig[nm + "_f64"]
     lib.snmf_abi_version.restype = C.c_int
     if lib.snmf_abi_version() != ABI_VERSION:  # a stale library must not be driven through newer prototypes
         raise ImportError(f"{path} has ABI version {lib.snmf_abi_version()}, this binding needs {ABI_VERSION}: rebuild the library")

@@ -341,7 +341,21 @@ def _solver_scalars(p):
     return _cf_to_beta(p), int(p.get("max_iter", 100)), float(p.get("conv_eps", 0)), 1 if p["cost_check"] else 0, float(sp.reshape(-1)[0])
 
 
-def run_basis_dnmf(Y, X, D, B, R_x, R_d, p, *, ctx=None, dtype=np.float64, devices=None, resident=None, h0="host"):
+def _check_precision(precision):
+    if precision not in ("fp32", "fp64"):
+        raise ValueError(f"precision must be 'fp32' or 'fp64' (got {precision!r})")
+
+
+def _fp64_rules(dtype, devices, what):
+    """What precision="fp64" refuses, as sparse_nmf does (after the reference's own errors, before any device work)."""
+    if dtype is not None and np.dtype(dtype) != np.dtype(np.float64):
+        raise SnmfError(1, f"precision='fp64' needs dtype=np.float64 ({what} takes and returns doubles)")
+    if devices is not None:
+        raise SnmfError(8, f"precision='fp64' runs on one device (no {what} over a device list)")
+
+
+def run_basis_dnmf(Y, X, D, B, R_x, R_d, p, *, ctx=None, dtype=np.float64, devices=None, resident=None, h0="host", precision="fp32",
+                   info=None):
     """The 3-solve discriminative re-training loop of run_basis_DNMF.m:36-55 on formed features.
 
     Y, X, D are the F x T features of mixture / clean / noise (run_basis_DNMF.m:13-34); B is the
@@ -351,13 +365,20 @@ def run_basis_dnmf(Y, X, D, B, R_x, R_d, p, *, ctx=None, dtype=np.float64, devic
     between the solves; False = three separate sparse_nmf calls (the same bits, three host round trips).
     h0: "host" = rand(r, n) of src/sparse_nmf.m:133-134 drawn here (the RandomState stand-in, as sparse_nmf does);
     "device" = drawn on the device (philox_uniform(random_seed, r, n): nothing but the features crosses PCIe); or the
-    r x n array itself (what integration/run_basis_DNMF.m passes: MATLAB's own draws)."""
+    r x n array itself (what integration/run_basis_DNMF.m passes: MATLAB's own draws).
+    precision: "fp32" (default) = the fp32 engine whatever `dtype`; "fp64" = the loop in double (snmf_run_basis_dnmf_fp64:
+    the kernels of the fp64 solve mode, bit-identical to resident=False, which then runs three sparse_nmf(precision="fp64")
+    calls).  "fp64" needs dtype=np.float64 (SnmfError status 1) and one device (status 8); any other string is a ValueError.
+    info: a dict that receives info["n_iter"], the iteration counts of the three solves."""
+    _check_precision(precision)
     p = dict(p)
     B = np.asarray(B, dtype=np.float64)
     if resident is None:
         resident = True
     if resident:  # (with a device list: snmf_run_basis_dnmf_multi_*, every rank's shard resident on its device)
-        return _run_basis_dnmf_resident(Y, X, D, B, int(R_x), int(R_d), p, ctx=ctx, dtype=dtype, h0=h0, devices=devices)
+        return _run_basis_dnmf_resident(Y, X, D, B, int(R_x), int(R_d), p, ctx=ctx, dtype=dtype, h0=h0, devices=devices,
+                                        precision=precision, info=info)
+    kw = dict(ctx=ctx, dtype=dtype, devices=devices, precision=precision)
     p["w_update_ind"] = np.zeros(R_x + R_d, bool)  # :37
     p["h_update_ind"] = np.ones(R_x + R_d, bool)  # :38
     p["init_w"] = B  # :39
@@ -367,21 +388,23 @@ def run_basis_dnmf(Y, X, D, B, R_x, R_d, p, *, ctx=None, dtype=np.float64, devic
     elif h0 == "device":
         seed = int(p.get("random_seed", 1))
         p["init_h"] = philox_uniform(seed, R_x + R_d, np.asarray(Y).shape[1]).astype(np.float64)
-    _, A_hat, _ = sparse_nmf(Y, p, ctx=ctx, dtype=dtype, devices=devices)  # :40
+    _, A_hat, o1 = sparse_nmf(Y, p, **kw)  # :40
     p["w_update_ind"] = np.ones(R_x, bool)  # :43
     p["h_update_ind"] = np.zeros(R_x, bool)  # :44
     p["init_w"] = B[:, :R_x]  # :45
     p["init_h"] = A_hat[:R_x, :]  # :46
-    B_hat_x, _, _ = sparse_nmf(X, p, ctx=ctx, dtype=dtype, devices=devices)  # :47
+    B_hat_x, _, o2 = sparse_nmf(X, p, **kw)  # :47
     p["w_update_ind"] = np.ones(R_d, bool)  # :49
     p["h_update_ind"] = np.zeros(R_d, bool)  # :50
     p["init_w"] = B[:, R_x:R_x + R_d]  # :51
     p["init_h"] = A_hat[R_x:R_x + R_d, :]  # :52
-    B_hat_d, _, _ = sparse_nmf(D, p, ctx=ctx, dtype=dtype, devices=devices)  # :53
+    B_hat_d, _, o3 = sparse_nmf(D, p, **kw)  # :53
+    if info is not None:
+        info["n_iter"] = [int(o["n_iter"]) for o in (o1, o2, o3)]
     return np.concatenate([B_hat_x, B_hat_d], axis=1), A_hat  # :55
 
 
-def _run_basis_dnmf_resident(Y, X, D, B, R_x, R_d, p, *, ctx, dtype, h0, want_a=True, devices=None):
+def _run_basis_dnmf_resident(Y, X, D, B, R_x, R_d, p, *, ctx, dtype, h0, want_a=True, devices=None, precision="fp32", info=None):
     dt = np.dtype(dtype)
     if dt not in (np.dtype(np.float64), np.dtype(np.float32)):
         raise SnmfError(1, "dtype must be float64 or float32")
@@ -394,6 +417,8 @@ def _run_basis_dnmf_resident(Y, X, D, B, R_x, R_d, p, *, ctx, dtype, h0, want_a=
         raise SnmfError(3, f"B is {B.shape}, expected ({F}, {r})")
     beta, max_iter, conv_eps, cost_check, lam = _solver_scalars(p)
     sp = _make_params(F, T, r, beta, max_iter, conv_eps, cost_check, True, 0, lam, None, None)
+    if precision == "fp64":
+        _fp64_rules(dt, devices, "the fp64 DNMF loop")
     seed = int(p.get("random_seed", 1))
     H0 = None
     if isinstance(h0, np.ndarray):
@@ -417,8 +442,13 @@ def _run_basis_dnmf_resident(Y, X, D, B, R_x, R_d, p, *, ctx, dtype, h0, want_a=
         _lib.check(fn(_ptr(dv), int(dv.size), *tail))
     else:
         ctx = ctx or default_context()
-        fn = lib.snmf_run_basis_dnmf_f64 if dt == np.float64 else lib.snmf_run_basis_dnmf_f32
+        if precision == "fp64":
+            fn = lib.snmf_run_basis_dnmf_fp64
+        else:
+            fn = lib.snmf_run_basis_dnmf_f64 if dt == np.float64 else lib.snmf_run_basis_dnmf_f32
         _lib.check(fn(ctx._h, *tail))
+    if info is not None:
+        info["n_iter"] = [int(x) for x in nit]
     return B_hat, A_hat
 
 

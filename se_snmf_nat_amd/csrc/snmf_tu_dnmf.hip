@@ -11,6 +11,7 @@
 // runs both solves without V ever crossing PCIe.
 #include "snmf_internal.h"
 #include "snmf_frontend.h"
+#include "snmf_philox.h"
 
 #include <thread>
 
@@ -22,16 +23,6 @@ namespace snmf {
 // gets Philox-4x32-10 (Salmon et al., SC'11) keyed by the seed, counter = the column-major element index / 4: r x n numbers
 // in (0, 1), reproducible on any host (se_snmf_nat_amd/api.py: philox_uniform restates it in NumPy for the tests), and 160 MB
 // that do not cross PCIe at BASELINE config 4.
-__device__ __host__ inline void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t out[4]) {
-    for (int round = 0; round < 10; ++round) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
 // H[t * rp + k] = u(k + r * (t_off + t)) for k < r, t < T; pads zero.  t_off: this plan's first column in the r x n matrix the draw
 // is defined on (a shard of the frames starts from ITS columns of the unsharded draw: dist.h0_columns, snmf_run_basis_dnmf_multi_*).
 // value = ((x >> 9) + 0.5) * 2^-23: every one of the 2^23 results is exactly representable and lies strictly inside (0, 1)

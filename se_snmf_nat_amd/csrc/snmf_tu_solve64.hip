@@ -1,7 +1,9 @@
-// snmf_tu_solve64.hip -- the fp64 solve mode (snmf_sparse_nmf_fp64), kernels in snmf_solve64.h.  A translation unit of its
-// own: the fp32 plan, its kernels and its geometry are not touched, and compile to the code they compiled to before.
+// snmf_tu_solve64.hip -- the fp64 solve mode, kernels in snmf_solve64.h: solve64_core runs one solve on device pointers
+// with a workspace of the caller's, snmf_sparse_nmf_fp64 is allocation, upload and download around it.  A translation
+// unit of its own: the fp32 plan, its kernels and its geometry are not touched, and compile to the code they compiled to before.
 #include "snmf_internal.h"
 #include "snmf_solve64.h"
+#include "snmf_solve64_core.h"
 
 namespace {
 
@@ -85,102 +87,132 @@ int obj64(const Solve64& s, const double* V, const double* Lam, long long n_v, d
     return SNMF_OK;
 }
 
-}  // namespace
+// the host's reading of the update masks (src/sparse_nmf.m:142-148, :176-179) and of beta
+struct Shape64 {
+    bool upd_h = true, upd_w = true;
+    int mode = S64_KL;
+    std::vector<uint8_t> w_ind;
+};
 
-extern "C" int snmf_sparse_nmf_fp64(snmf_ctx* ctx, const snmf_params* p, const double* V, int64_t ldV, const double* W0,
-                                    const double* H0, const double* sparsity, double* W, double* H, double* div_out,
-                                    double* cost_out, int32_t* n_iter_out) {
-    if (!ctx) return fail(SNMF_ERR_INVALID, "ctx is NULL");
-    if (!V || !W || !H || !W0 || !H0) return fail(SNMF_ERR_INVALID, "V, W and H must be non-NULL");
+int shape64(const snmf_params* p, Shape64* s) {
     SN_TRY(validate_params(p));
-    const int F = p->F, T = p->T, r = p->r, max_iter = p->max_iter;
-    if (ldV < F) return fail(SNMF_ERR_INVALID, "ldV = %lld < F = %d", (long long)ldV, F);
-    const int kind = p->sparsity_kind;
-    if (kind != SNMF_SPARSITY_SCALAR && !sparsity) return fail(SNMF_ERR_INVALID, "sparsity array required for this sparsity_kind");
-    // masks (src/sparse_nmf.m:142-148, :176-179)
-    std::vector<uint8_t> w_ind(r);
+    const int r = p->r;
+    s->w_ind.resize(r);
     int n_h = 0, n_w = 0;
     for (int k = 0; k < r; ++k) {
         n_h += p->h_update_ind ? p->h_update_ind[k] != 0 : 1;
-        w_ind[k] = p->w_update_ind ? p->w_update_ind[k] != 0 : 1;
-        n_w += w_ind[k];
+        s->w_ind[k] = p->w_update_ind ? p->w_update_ind[k] != 0 : 1;
+        n_w += s->w_ind[k];
     }
     if (n_h != 0 && n_h != r)
         return fail(SNMF_ERR_DIM, "partial h_update_ind (%d of %d rows): dimension mismatch in src/sparse_nmf.m:192/197/202", n_h, r);
-    const bool upd_h = n_h > 0, upd_w = n_w > 0;
+    s->upd_h = n_h > 0, s->upd_w = n_w > 0;
     const double beta = p->beta;
-    const int mode = beta == 1.0 ? S64_KL : (beta == 2.0 ? S64_ED : (beta == 0.0 ? S64_IS : S64_GEN));
-    const bool kl = mode == S64_KL, ed = mode == S64_ED;
+    s->mode = beta == 1.0 ? S64_KL : (beta == 2.0 ? S64_ED : (beta == 0.0 ? S64_IS : S64_GEN));
+    return SNMF_OK;
+}
 
-    (void)hipGetLastError();
-    HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    Blocks64 mem;
-    mem.st = st;
-    const long long nFT = (long long)F * T, nRT = (long long)r * T, nFR = (long long)F * r;
-    double *dV, *dW, *dH, *dLam, *dR = nullptr, *dD = nullptr, *dNum = nullptr, *dDen = nullptr, *dQ = nullptr, *dP = nullptr;
-    double *dS = nullptr, *dcs = nullptr, *dhs = nullptr, *dsp = nullptr, *dwn, *dpart, *ddiv, *dcost, *dz = nullptr;
-    uint8_t* dwi;
-    Solve64State* dst;
-    SN_TRY(mem.get(&dV, nFT));
-    SN_TRY(mem.get(&dW, nFR));
-    SN_TRY(mem.get(&dH, nRT));
-    SN_TRY(mem.get(&dLam, nFT));
-    if (!ed) SN_TRY(mem.get(&dR, nFT));
-    if (!ed && !kl) SN_TRY(mem.get(&dD, nFT));
-    if (upd_h) {
-        SN_TRY(mem.get(&dNum, nRT));
-        if (!kl) SN_TRY(mem.get(&dDen, nRT));
-        else SN_TRY(mem.get(&dcs, r));
+// The workspace of one solve, carved out of one block in a fixed order (256-byte aligned pieces).  base == nullptr only
+// measures: the same walk gives the size a caller has to provide.
+struct Carve64 {
+    char* base;
+    size_t off = 0;
+    explicit Carve64(void* b) : base((char*)b) {}
+    void* bytes(size_t n) {
+        void* q = base ? base + off : nullptr;
+        off += (std::max<size_t>(n, 1) + 255) & ~(size_t)255;
+        return q;
     }
-    const int n_rowz = (T + kS64RowChunk - 1) / kS64RowChunk;
-    if (upd_w) {
-        SN_TRY(mem.get(&dQ, nFR));
-        if (!kl) SN_TRY(mem.get(&dP, nFR));
+    double* f64(size_t n) { return (double*)bytes(n * sizeof(double)); }
+};
+
+struct Work64 {
+    double *Lam, *R = nullptr, *D = nullptr, *Num = nullptr, *Den = nullptr, *Q = nullptr, *P = nullptr;
+    double *cs = nullptr, *hs = nullptr, *sp = nullptr, *wn, *part, *div, *cost, *z = nullptr;
+    uint8_t* wi;
+    Solve64State* state;
+};
+
+size_t carve64(const snmf_params* p, const Shape64& sh, void* base, Work64* w) {
+    const int F = p->F, T = p->T, r = p->r;
+    const size_t nFT = (size_t)F * T, nRT = (size_t)r * T, nFR = (size_t)F * r;
+    const bool kl = sh.mode == S64_KL, ed = sh.mode == S64_ED;
+    Carve64 c(base);
+    w->Lam = c.f64(nFT);
+    if (!ed) w->R = c.f64(nFT);
+    if (!ed && !kl) w->D = c.f64(nFT);
+    if (sh.upd_h) {
+        w->Num = c.f64(nRT);
+        if (!kl) w->Den = c.f64(nRT);
+        else w->cs = c.f64(r);
+    }
+    if (sh.upd_w) {
+        w->Q = c.f64(nFR);
+        if (!kl) w->P = c.f64(nFR);
         else {
-            SN_TRY(mem.get(&dhs, r));
-            SN_TRY(mem.get(&dsp, (size_t)n_rowz * r));
+            w->hs = c.f64(r);
+            w->sp = c.f64((size_t)((T + kS64RowChunk - 1) / kS64RowChunk) * r);
         }
     }
     // split partials: the largest nz * M * N over the products that are split at all
-    {
-        size_t need = 0;
-        auto want = [&](long long M, long long N, int K) {
-            const int nz = n_splits(K);
-            if (nz > 1) need = std::max(need, (size_t)nz * (size_t)M * (size_t)N);
-        };
-        want(F, T, r);              // Lam = W * H
-        if (upd_h) want(r, T, F);   // W' * R, W' * D
-        if (upd_w) want(F, r, T);   // R * H', D * H'
-        if (need) SN_TRY(mem.get(&dz, need));
-    }
-    const size_t n_s = kind == SNMF_SPARSITY_SCALAR ? 0 : (kind == SNMF_SPARSITY_RVEC ? (size_t)r : (size_t)nRT);
-    if (n_s) SN_TRY(mem.get(&dS, n_s));
-    SN_TRY(mem.get(&dwn, r));
-    SN_TRY(mem.get(&dpart, 2 * kS64Blocks));
-    SN_TRY(mem.get(&ddiv, std::max(max_iter, 1)));
-    SN_TRY(mem.get(&dcost, std::max(max_iter, 1)));
-    SN_TRY(mem.get_bytes((void**)&dwi, (size_t)r));
-    SN_TRY(mem.get_bytes((void**)&dst, sizeof(Solve64State)));
+    size_t need = 0;
+    auto want = [&](long long M, long long N, int K) {
+        const int nz = n_splits(K);
+        if (nz > 1) need = std::max(need, (size_t)nz * (size_t)M * (size_t)N);
+    };
+    want(F, T, r);                 // Lam = W * H
+    if (sh.upd_h) want(r, T, F);   // W' * R, W' * D
+    if (sh.upd_w) want(F, r, T);   // R * H', D * H'
+    if (need) w->z = c.f64(need);
+    w->wn = c.f64(r);
+    w->part = c.f64(2 * kS64Blocks);
+    w->div = c.f64(std::max(p->max_iter, 1));
+    w->cost = c.f64(std::max(p->max_iter, 1));
+    w->wi = (uint8_t*)c.bytes((size_t)r);
+    w->state = (Solve64State*)c.bytes(sizeof(Solve64State));
+    return c.off;
+}
 
-    // upload (tight column-major on the device)
-    if (ldV == F || T == 1) HIP_TRY(hipMemcpyAsync(dV, V, (size_t)nFT * 8, hipMemcpyHostToDevice, st));
-    else HIP_TRY(hipMemcpy2DAsync(dV, (size_t)F * 8, V, (size_t)ldV * 8, (size_t)F * 8, (size_t)T, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(dW, W0, (size_t)nFR * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(dH, H0, (size_t)nRT * 8, hipMemcpyHostToDevice, st));
-    if (n_s) HIP_TRY(hipMemcpyAsync(dS, sparsity, n_s * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(dwi, w_ind.data(), (size_t)r, hipMemcpyHostToDevice, st));
+}  // namespace
+
+int solve64_ws_bytes(const snmf_params* p, size_t* bytes) {
+    Shape64 sh;
+    SN_TRY(shape64(p, &sh));
+    Work64 w;
+    *bytes = carve64(p, sh, nullptr, &w);
+    return SNMF_OK;
+}
+
+int solve64_core(snmf_ctx* ctx, const snmf_params* p, double* dV, double* dW, double* dH, const double* dS, void* ws, size_t ws_bytes,
+                 double* div_out, double* cost_out, int32_t* n_iter_out) {
+    Shape64 sh;
+    SN_TRY(shape64(p, &sh));
+    const int F = p->F, T = p->T, r = p->r, max_iter = p->max_iter, kind = p->sparsity_kind;
+    const bool upd_h = sh.upd_h, upd_w = sh.upd_w;
+    const double beta = p->beta;
+    const int mode = sh.mode;
+    const bool kl = mode == S64_KL, ed = mode == S64_ED;
+    Work64 w;
+    if (carve64(p, sh, ws, &w) > ws_bytes || !ws) return fail(SNMF_ERR_INTERNAL, "fp64 solve: workspace of %zu bytes is too small", ws_bytes);
+    hipStream_t st = ctx->stream;
+    const long long nFT = (long long)F * T, nRT = (long long)r * T;
+    const int n_rowz = (T + kS64RowChunk - 1) / kS64RowChunk;
+    double *dLam = w.Lam, *dR = w.R, *dD = w.D, *dNum = w.Num, *dDen = w.Den, *dQ = w.Q, *dP = w.P;
+    double *dcs = w.cs, *dhs = w.hs, *dsp = w.sp, *dwn = w.wn, *dpart = w.part, *ddiv = w.div, *dcost = w.cost;
+    uint8_t* dwi = w.wi;
+    Solve64State* dst = w.state;
+
+    HIP_TRY(hipMemcpyAsync(dwi, sh.w_ind.data(), (size_t)r, hipMemcpyHostToDevice, st));
     Solve64State h_state;
     h_state.stop = 0, h_state.n_iter = 0, h_state.last_cost = INFINITY;  // :168
     HIP_TRY(hipMemcpyAsync(dst, &h_state, sizeof(h_state), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(ddiv, 0, (size_t)std::max(max_iter, 1) * 8, st));   // :171-173
     HIP_TRY(hipMemsetAsync(dcost, 0, (size_t)std::max(max_iter, 1) * 8, st));
-    HIP_TRY(hipStreamSynchronize(st));  // (the host arrays are pageable: the sources may be reused from here on)
+    HIP_TRY(hipStreamSynchronize(st));  // (the host sources are pageable: they may be reused from here on)
 
     Solve64 s;
-    s.st = st, s.stop = &dst->stop, s.zbuf = dz;
+    s.st = st, s.stop = &dst->stop, s.zbuf = w.z;
     const double scalar = p->sparsity_scalar;
-
     // ---- initial scaling (:157-169)
     hipLaunchKernelGGL((k_s64_wupd<true, false>), dim3(r), dim3(256), 0, st, dW, nullptr, nullptr, nullptr, nullptr, F, dwn, s.stop);
     HIP_TRY(hipGetLastError());
@@ -251,8 +283,6 @@ extern "C" int snmf_sparse_nmf_fp64(snmf_ctx* ctx, const snmf_params* p, const d
         }
     }
     HIP_TRY(hipMemcpyAsync(&h_state, dst, sizeof(h_state), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(W, dW, (size_t)nFR * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(H, dH, (size_t)nRT * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     std::vector<double> hd(std::max(max_iter, 1)), hc(std::max(max_iter, 1));
     HIP_TRY(hipMemcpy(hd.data(), ddiv, hd.size() * 8, hipMemcpyDeviceToHost));
@@ -260,5 +290,46 @@ extern "C" int snmf_sparse_nmf_fp64(snmf_ctx* ctx, const snmf_params* p, const d
     if (div_out) std::copy(hd.begin(), hd.begin() + max_iter, div_out);
     if (cost_out) std::copy(hc.begin(), hc.begin() + max_iter, cost_out);
     if (n_iter_out) *n_iter_out = h_state.stop ? h_state.n_iter : max_iter;
+    return SNMF_OK;
+}
+
+// the one-shot entry: allocation, upload and download around solve64_core
+extern "C" int snmf_sparse_nmf_fp64(snmf_ctx* ctx, const snmf_params* p, const double* V, int64_t ldV, const double* W0,
+                                    const double* H0, const double* sparsity, double* W, double* H, double* div_out,
+                                    double* cost_out, int32_t* n_iter_out) {
+    if (!ctx) return fail(SNMF_ERR_INVALID, "ctx is NULL");
+    if (!V || !W || !H || !W0 || !H0) return fail(SNMF_ERR_INVALID, "V, W and H must be non-NULL");
+    size_t ws_bytes = 0;
+    SN_TRY(solve64_ws_bytes(p, &ws_bytes));
+    const int F = p->F, T = p->T, r = p->r;
+    if (ldV < F) return fail(SNMF_ERR_INVALID, "ldV = %lld < F = %d", (long long)ldV, F);
+    const int kind = p->sparsity_kind;
+    if (kind != SNMF_SPARSITY_SCALAR && !sparsity) return fail(SNMF_ERR_INVALID, "sparsity array required for this sparsity_kind");
+
+    (void)hipGetLastError();
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    Blocks64 mem;
+    mem.st = st;
+    const long long nFT = (long long)F * T, nRT = (long long)r * T, nFR = (long long)F * r;
+    double *dV, *dW, *dH, *dS = nullptr;
+    void* ws;
+    SN_TRY(mem.get(&dV, nFT));
+    SN_TRY(mem.get(&dW, nFR));
+    SN_TRY(mem.get(&dH, nRT));
+    const size_t n_s = kind == SNMF_SPARSITY_SCALAR ? 0 : (kind == SNMF_SPARSITY_RVEC ? (size_t)r : (size_t)nRT);
+    if (n_s) SN_TRY(mem.get(&dS, n_s));
+    SN_TRY(mem.get_bytes(&ws, ws_bytes));
+
+    // upload (tight column-major on the device)
+    if (ldV == F || T == 1) HIP_TRY(hipMemcpyAsync(dV, V, (size_t)nFT * 8, hipMemcpyHostToDevice, st));
+    else HIP_TRY(hipMemcpy2DAsync(dV, (size_t)F * 8, V, (size_t)ldV * 8, (size_t)F * 8, (size_t)T, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dW, W0, (size_t)nFR * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dH, H0, (size_t)nRT * 8, hipMemcpyHostToDevice, st));
+    if (n_s) HIP_TRY(hipMemcpyAsync(dS, sparsity, n_s * 8, hipMemcpyHostToDevice, st));
+    SN_TRY(solve64_core(ctx, p, dV, dW, dH, dS, ws, ws_bytes, div_out, cost_out, n_iter_out));
+    HIP_TRY(hipMemcpyAsync(W, dW, (size_t)nFR * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(H, dH, (size_t)nRT * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return SNMF_OK;
 }

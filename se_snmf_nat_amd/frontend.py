@@ -8,6 +8,9 @@
 
 `p` uses the reference's field names (framelength, frameshift, fftlength, DCbin, win_STFT, preemph,
 pow, nonzerofloor, Splice, fs, F_order).
+
+The three device functions take precision="fp32" (default: float32 in, fp32 arithmetic, float32 out) or "fp64" (the
+snmf_*_fp64 entries: float64 samples / matrices / Mel table, double arithmetic, float64 out); any other string is a ValueError.
 """
 from __future__ import annotations
 
@@ -17,7 +20,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import SnmfError, SnmfStftParams
-from .api import default_context
+from .api import _check_precision, default_context
 
 
 def default_params():
@@ -49,18 +52,26 @@ def num_frames(n_samples, p):
     return int(_lib.load().snmf_stft_num_frames(C.byref(sp), int(n_samples)))
 
 
-def stft_features(s, p, *, ctx=None):
-    """TF_mag = (|STFT(s)|.^pow + nonzerofloor) with splicing, F x n_frames float32 (Fortran order)."""
+def _prec(precision):
+    """(host type, entry suffix) of a precision."""
+    _check_precision(precision)
+    return (np.float64, "fp64") if precision == "fp64" else (np.float32, "f32")
+
+
+def stft_features(s, p, *, ctx=None, precision="fp32"):
+    """TF_mag = (|STFT(s)|.^pow + nonzerofloor) with splicing, F x n_frames float32 (Fortran order); float64, computed in
+    double, with precision="fp64"."""
+    dt, sfx = _prec(precision)
     ctx = ctx or default_context()
-    s = np.ascontiguousarray(np.asarray(s, dtype=np.float32).reshape(-1))
+    s = np.ascontiguousarray(np.asarray(s, dtype=dt).reshape(-1))
     sp, _win = _params(p)
     lib = _lib.load()
     nfr = int(lib.snmf_stft_num_frames(C.byref(sp), s.size))
     F = (2 * sp.splice + 1) * (sp.fftlength // 2 + 1)
-    out = np.zeros((F, max(nfr, 0)), dtype=np.float32, order="F")
+    out = np.zeros((F, max(nfr, 0)), dtype=dt, order="F")
     n_out = C.c_int32()
-    _lib.check(lib.snmf_stft_features_f32(ctx._h, C.byref(sp), C.c_void_p(s.ctypes.data), s.size, 0,
-                                          C.c_void_p(out.ctypes.data), F, 0, C.byref(n_out)))
+    _lib.check(getattr(lib, "snmf_stft_features_" + sfx)(ctx._h, C.byref(sp), C.c_void_p(s.ctypes.data), s.size, 0,
+                                                         C.c_void_p(out.ctypes.data), F, 0, C.byref(n_out)))
     return out
 
 
@@ -93,35 +104,38 @@ def mel_matrix(fs, NbCh, Nfft, warp=1.0, fhigh=None):
     return M[:Nfft // 2 + 1, :]
 
 
-def mel_features(TF_mag, p, *, ctx=None):
-    """run_basis_train.m:70-78 on the GPU: TF_Mel (F_order*(2*Splice+1) x T)."""
+def mel_features(TF_mag, p, *, ctx=None, precision="fp32"):
+    """run_basis_train.m:70-78 on the GPU: TF_Mel (F_order*(2*Splice+1) x T); precision: as in stft_features."""
+    dt, sfx = _prec(precision)
     ctx = ctx or default_context()
     n = int(p["fftlength"]) // 2 + 1
     K = 2 * int(p.get("Splice", 0)) + 1
     M = int(p["F_order"])
-    mel = np.ascontiguousarray(mel_matrix(p["fs"], M, p["fftlength"], 1.0, p["fs"] / 2).T, dtype=np.float32)
-    V = np.asfortranarray(TF_mag, dtype=np.float32)
+    mel = np.ascontiguousarray(mel_matrix(p["fs"], M, p["fftlength"], 1.0, p["fs"] / 2).T, dtype=dt)
+    V = np.asfortranarray(TF_mag, dtype=dt)
     if V.shape[0] != K * n:
         raise SnmfError(3, f"TF_mag has {V.shape[0]} rows, expected {K * n}")
     T = V.shape[1]
-    out = np.zeros((K * M, T), dtype=np.float32, order="F")
-    _lib.check(_lib.load().snmf_mel_features_f32(ctx._h, C.c_void_p(mel.ctypes.data), M, n, K, C.c_void_p(V.ctypes.data),
-                                                  K * n, T, C.c_void_p(out.ctypes.data), K * M, 0))
+    out = np.zeros((K * M, T), dtype=dt, order="F")
+    _lib.check(getattr(_lib.load(), "snmf_mel_features_" + sfx)(ctx._h, C.c_void_p(mel.ctypes.data), M, n, K, C.c_void_p(V.ctypes.data),
+                                                                K * n, T, C.c_void_p(out.ctypes.data), K * M, 0))
     return out
 
 
-def tf_dd(X, p, *, ctx=None):
-    """[X_DD] = TF_DD(X, p), src/TF_DD.m:1-9: X_DD(:,l) = p.alpha_eta * X_DD(:,l-1) + (1 - p.alpha_eta) * X(:,l), on the GPU."""
+def tf_dd(X, p, *, ctx=None, precision="fp32"):
+    """[X_DD] = TF_DD(X, p), src/TF_DD.m:1-9: X_DD(:,l) = p.alpha_eta * X_DD(:,l-1) + (1 - p.alpha_eta) * X(:,l), on the GPU;
+    precision: as in stft_features (in "fp64" the first column is the input's, bit for bit)."""
+    dt, sfx = _prec(precision)
     ctx = ctx or default_context()
     if "alpha_eta" not in p:
         raise SnmfError(4, "Reference to non-existent field 'alpha_eta'.")
-    X = np.asfortranarray(X, dtype=np.float32)
+    X = np.asfortranarray(X, dtype=dt)
     if X.ndim != 2:
         raise SnmfError(3, "TF_DD: X must be a matrix")
     F, T = X.shape
-    out = np.zeros((F, T), dtype=np.float32, order="F")
+    out = np.zeros((F, T), dtype=dt, order="F")
     if T == 0:
         return out
-    _lib.check(_lib.load().snmf_tf_dd_f32(ctx._h, float(p["alpha_eta"]), F, T, C.c_void_p(X.ctypes.data), F,
-                                           C.c_void_p(out.ctypes.data), F, 0))
+    _lib.check(getattr(_lib.load(), "snmf_tf_dd_" + sfx)(ctx._h, float(p["alpha_eta"]), F, T, C.c_void_p(X.ctypes.data), F,
+                                                         C.c_void_p(out.ctypes.data), F, 0))
     return out

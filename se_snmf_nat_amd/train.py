@@ -15,10 +15,10 @@ import ctypes as C
 import numpy as np
 
 from . import _lib, frontend
-from .api import SnmfError, _make_params, _solver_scalars, default_context
+from .api import SnmfError, _check_precision, _fp64_rules, _make_params, _solver_scalars, default_context
 
 
-def run_basis_train_signal(s_full, R, p, *, DC_bin=None, sample_idx=None, ctx=None, h0="host"):
+def run_basis_train_signal(s_full, R, p, *, DC_bin=None, sample_idx=None, ctx=None, h0="host", precision="fp32"):
     """run_basis_train.m:58-136.  `p`: the reference's settings fields (front-end fields of
     frontend.default_params() plus cf/sparsity/max_iter/conv_eps/cost_check, cluster_buff,
     train_Exemplar).  sample_idx: the exemplar columns (1-based like randsample, :81); default = a
@@ -28,7 +28,13 @@ def run_basis_train_signal(s_full, R, p, *, DC_bin=None, sample_idx=None, ctx=No
     ONE call across the C ABI (include/snmf.h: snmf_run_basis_train_audio_f64): TF_mag, TF_DD, TF_Mel, the exemplar columns and
     both solves stay in HBM -- only the audio goes in and the dictionaries (and activations) come out.
     h0: "host" = the rand(r, n) both sparse_nmf calls draw after re-seeding (src/sparse_nmf.m:112-114,:133-134; RandomState
-    stand-in) is drawn here and uploaded; "device" = drawn on the device (api.philox_uniform)."""
+    stand-in) is drawn here and uploaded; "device" = drawn on the device (api.philox_uniform).
+    precision: "fp32" (default) = float samples, fp32 features and solves; "fp64" = snmf_run_basis_train_audio_fp64: the signal
+    crosses as float64 and features, Mel projection, exemplars and both solves are computed in double.  Any other string is a
+    ValueError.  The returned arrays are float64 in both."""
+    _check_precision(precision)
+    f64 = precision == "fp64"
+    sdt = np.float64 if f64 else np.float32
     p = dict(p)
     cluster_buff = int(p.get("cluster_buff", 1))
     exemplar = bool(p.get("train_Exemplar", 0))
@@ -38,7 +44,7 @@ def run_basis_train_signal(s_full, R, p, *, DC_bin=None, sample_idx=None, ctx=No
     fp = dict(p)
     if DC_bin is not None:
         fp["DCbin"] = int(DC_bin)
-    s = np.ascontiguousarray(np.asarray(s_full, dtype=np.float32).reshape(-1))
+    s = np.ascontiguousarray(np.asarray(s_full, dtype=sdt).reshape(-1))
     sp, _win = frontend._params(fp)
     lib = _lib.load()
     T = int(lib.snmf_stft_num_frames(C.byref(sp), s.size))
@@ -61,7 +67,7 @@ def run_basis_train_signal(s_full, R, p, *, DC_bin=None, sample_idx=None, ctx=No
     H0 = None
     if h0 == "host" and not exemplar:
         H0 = np.asfortranarray(np.random.RandomState(seed if seed > 0 else None).random_sample((n_ex, T)))
-    mel = np.ascontiguousarray(frontend.mel_matrix(p["fs"], M, p["fftlength"], 1.0, p["fs"] / 2).T, dtype=np.float32)
+    mel = np.ascontiguousarray(frontend.mel_matrix(p["fs"], M, p["fftlength"], 1.0, p["fs"] / 2).T, dtype=sdt)
     B_DFT = np.empty((F, n_ex), order="F")
     B_Mel = np.empty((K * M, n_ex), order="F")
     A_DFT = A_Mel = 0  # :95-96
@@ -71,7 +77,8 @@ def run_basis_train_signal(s_full, R, p, *, DC_bin=None, sample_idx=None, ctx=No
     nit = np.zeros(2, np.int32)
     ptr = lambda a: C.c_void_p(a.ctypes.data) if isinstance(a, np.ndarray) else None
     ctx = ctx or default_context()
-    _lib.check(lib.snmf_run_basis_train_audio_f64(
+    fn = lib.snmf_run_basis_train_audio_fp64 if f64 else lib.snmf_run_basis_train_audio_f64
+    _lib.check(fn(
         ctx._h, C.byref(q), C.byref(sp), float(p["alpha_eta"]) if p.get("domain_DD", 0) else -1.0, ptr(mel), M, ptr(s), s.size,
         ptr(idx0), 1 if exemplar else 0, ptr(H0), seed, ptr(B_DFT), ptr(A_DFT), ptr(B_Mel), ptr(A_Mel), ptr(nit)))
     B_DFT = B_DFT / np.sqrt((B_DFT ** 2).sum(0)) + 1e-9  # :113-114
@@ -117,11 +124,13 @@ def _dnmf_features(x, d, p, ctx):
     return tuple(frontend.stft_features(sig, p, ctx=ctx) for sig in (y, x, d))  # :13-34
 
 
-def _run_basis_dnmf_audio(x, d, B, p, *, ctx, mel, h0, want_a=False):
-    """ONE call across the C ABI (snmf_run_basis_dnmf_audio_f64): the waveforms go in, B_hat comes out; features, A_hat and
-    all three V matrices stay in HBM."""
-    x = np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(-1))
-    d = np.ascontiguousarray(np.asarray(d, dtype=np.float32).reshape(-1))
+def _run_basis_dnmf_audio(x, d, B, p, *, ctx, mel, h0, want_a=False, precision="fp32", dtype=None):
+    """ONE call across the C ABI (snmf_run_basis_dnmf_audio_f64; precision="fp64": snmf_run_basis_dnmf_audio_fp64, waveforms and
+    Mel table as float64): the waveforms go in, B_hat comes out; features, A_hat and all three V matrices stay in HBM."""
+    f64 = precision == "fp64"
+    sdt = np.float64 if f64 else np.float32
+    x = np.ascontiguousarray(np.asarray(x, dtype=sdt).reshape(-1))
+    d = np.ascontiguousarray(np.asarray(d, dtype=sdt).reshape(-1))
     sp, _win = frontend._params(p)
     lib = _lib.load()
     R_x, R_d = int(p["R_x"]), int(p["R_d"])
@@ -137,18 +146,21 @@ def _run_basis_dnmf_audio(x, d, B, p, *, ctx, mel, h0, want_a=False):
         raise SnmfError(3, f"B is {B.shape}, expected ({F}, {r})")
     beta, max_iter, conv_eps, cost_check, lam = _solver_scalars(p)
     q = _make_params(F, T, r, beta, max_iter, conv_eps, cost_check, True, 0, lam, None, None)
+    if f64:  # (after the reference's own errors, before any device work)
+        _fp64_rules(dtype, None, "the fp64 DNMF caller")
     seed = int(p.get("random_seed", 1))
     H0 = None
     if h0 == "host":
         H0 = np.asfortranarray(np.random.RandomState(seed if seed > 0 else None).random_sample((r, T)))
-    melm = np.ascontiguousarray(frontend.mel_matrix(p["fs"], M, p["fftlength"], 1.0, p["fs"] / 2).T, dtype=np.float32) if mel else None
+    melm = np.ascontiguousarray(frontend.mel_matrix(p["fs"], M, p["fftlength"], 1.0, p["fs"] / 2).T, dtype=sdt) if mel else None
     B_hat = np.empty((F, r), order="F")
     A_hat = np.empty((r, T), order="F") if want_a else None
     nit = np.zeros(3, np.int32)
     ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None
     ctx = ctx or default_context()
-    _lib.check(lib.snmf_run_basis_dnmf_audio_f64(ctx._h, C.byref(q), C.byref(sp), R_x, R_d, ptr(x), x.size, ptr(d), d.size, ptr(melm), M,
-                                                 ptr(B), F, ptr(H0), seed, ptr(B_hat), F, ptr(A_hat), r, ptr(nit)))
+    fn = lib.snmf_run_basis_dnmf_audio_fp64 if f64 else lib.snmf_run_basis_dnmf_audio_f64
+    _lib.check(fn(ctx._h, C.byref(q), C.byref(sp), R_x, R_d, ptr(x), x.size, ptr(d), d.size, ptr(melm), M,
+                  ptr(B), F, ptr(H0), seed, ptr(B_hat), F, ptr(A_hat), r, ptr(nit)))
     return (B_hat, A_hat) if want_a else B_hat
 
 
@@ -160,15 +172,19 @@ def _check_dtype(dtype):
         raise SnmfError(1, "dtype must be float64 or float32")
 
 
-def run_basis_DNMF(x, d, B, p, *, ctx=None, h0="host", dtype=None):
+def run_basis_DNMF(x, d, B, p, *, ctx=None, h0="host", dtype=None, precision="fp32"):
     """B_hat = run_basis_DNMF(x, d, B, p) -- run_basis_DNMF.m:1: clean and noise waveforms, exemplar basis
-    B = [B_x, B_d] (F x (R_x+R_d)); p carries the front-end fields, R_x, R_d and the solver fields."""
+    B = [B_x, B_d] (F x (R_x+R_d)); p carries the front-end fields, R_x, R_d and the solver fields.
+    precision="fp64": the waveforms cross as float64 and y = x + d, the features and the three solves are computed in double
+    (dtype=np.float32 is then SnmfError status 1); any other string than "fp32" / "fp64" is a ValueError."""
+    _check_precision(precision)
     _check_dtype(dtype)
-    return _run_basis_dnmf_audio(x, d, B, p, ctx=ctx, mel=False, h0=h0)  # :1-55
+    return _run_basis_dnmf_audio(x, d, B, p, ctx=ctx, mel=False, h0=h0, precision=precision, dtype=dtype)  # :1-55
 
 
-def run_basis_DNMF_Mel(x, d, B, p, *, ctx=None, h0="host", dtype=None):
+def run_basis_DNMF_Mel(x, d, B, p, *, ctx=None, h0="host", dtype=None, precision="fp32"):
     """B_hat = run_basis_DNMF_Mel(x, d, B, p) -- run_basis_DNMF_Mel.m:1: the same loop on the Mel projections of
-    the three feature sets (:21-69); B is the Mel exemplar basis (F_order*(2*Splice+1) rows)."""
+    the three feature sets (:21-69); B is the Mel exemplar basis (F_order*(2*Splice+1) rows).  precision: as in run_basis_DNMF."""
+    _check_precision(precision)
     _check_dtype(dtype)
-    return _run_basis_dnmf_audio(x, d, B, p, ctx=ctx, mel=True, h0=h0)  # :1-95
+    return _run_basis_dnmf_audio(x, d, B, p, ctx=ctx, mel=True, h0=h0, precision=precision, dtype=dtype)  # :1-95
