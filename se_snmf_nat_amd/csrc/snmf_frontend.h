@@ -149,8 +149,10 @@ static __global__ __launch_bounds__(256) void k_tfdd_state(const float* __restri
         s = pow(a, (double)len) * s + c;
     }
 }
-static __global__ __launch_bounds__(256) void k_tfdd_apply(const float* __restrict__ X, int64_t ld, int F, int T, double a, const double* __restrict__ state,
-                                                    float* __restrict__ out, int64_t ldo) {
+// (X and out carry no __restrict__: out may alias X, snmf_tf_dd_f32 says so and the training caller runs it in place; every
+// element is read before it is written, by this thread)
+static __global__ __launch_bounds__(256) void k_tfdd_apply(const float* X, int64_t ld, int F, int T, double a, const double* __restrict__ state,
+                                                    float* out, int64_t ldo) {
     const int f = blockIdx.y * 256 + threadIdx.x, j = blockIdx.x;
     if (f >= F) return;
     const int t0 = j * kDdChunk, t1 = min(T, t0 + kDdChunk);
