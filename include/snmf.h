@@ -506,7 +506,8 @@ int snmf_online_process_classes_f64(snmf_online* o, const double* pcm, int64_t n
  * frame in shared launches, with no host round trip per frame: stream k has its own PCM, its own noise dictionary and
  * its own state g (src/init_buff.m:17-42), and its output equals what snmf_online_* produces for it alone.
  * Scope: B_sep_mode 'DFT', or 'Mel' through snmf_online_batch_set_mel; the supervised frame solve of the register-resident
- * frame kernel (F <= 513, R_x + R_d <= 200), R_a and m_a <= 128; anything else returns SNMF_ERR_UNSUPPORTED. */
+ * frame kernel (F <= 513, R_x + R_d <= 200), R_a and m_a <= 128; anything else returns SNMF_ERR_UNSUPPORTED.
+ * snmf_online_batch_create_f64 makes the same batch in fp64 (DFT mode; its own envelope is given there). */
 typedef struct snmf_online_batch snmf_online_batch;
 /* src/init_buff.m for S streams.  B_DFT_x: F x R_x, shared; B_DFT_d0: F x R_d x S, the initial noise dictionary of
  * every stream (e.g. each stream's B_D_u.mat, src/NTF_sep_event_RT.m:27-31); H0: r x S (rand(r,1) of
@@ -571,6 +572,34 @@ int snmf_online_batch_process_classes_f32(snmf_online_batch* b, const float* con
                                           float* const* x_tilde_f32, int16_t* const* x_tilde_i16, float* const* x_hat_f32,
                                           float* const* d_hat_f32, float* const* x_hat_i_f32, float* const* d_hat_i_f32,
                                           const int64_t* cap, int64_t* n_out);
+/* Added within 5.  The fp64 mode of the batch: snmf_online_create_f64 for S streams.  Every array crosses in fp64 (layouts as
+ * snmf_online_batch_create) and every step from PCM to each stream's fed-back dictionary runs in fp64 on the device, so every
+ * stream holds the fp64 reference's per-frame decisions over whole recordings and chains of recordings.  Same handle type,
+ * same destroy.  Scope: B_sep_mode 'DFT', the supervised frame solve, every beta_div, Wiener / MMSE, block sparsity,
+ * adaptation on or off, class outputs, restart.  SNMF_ERR_UNSUPPORTED: basis_update_N / basis_update_E; with adaptation
+ * R_a > 64, m_a > 128 or a ring whose LDS image exceeds a compute unit's (the message names the limit); a transform or
+ * dictionary whose frame solve does not fit the LDS.
+ * On such a batch snmf_online_batch_restart (H0 / Ad_blk0 widened from fp32), _get_basis_f64, _set_classes and _trace work as
+ * on an fp32 batch; snmf_online_batch_get_basis_f32 returns the fp64 dictionary rounded; snmf_online_batch_set_mel,
+ * _restart_mel and _get_mel_basis_* return SNMF_ERR_UNSUPPORTED; snmf_online_batch_process_f32 /
+ * _process_classes_f32 return SNMF_ERR_STATE with n_out zeroed, as the _f64 process entries do on an fp32 batch.  A refused
+ * call leaves the handle usable. */
+int snmf_online_batch_create_f64(snmf_ctx* ctx, const snmf_online_params* p, int32_t S, const double* B_DFT_x,
+                                 const double* B_DFT_d0, const double* H0, const double* Ad_blk0, const double* win_stft,
+                                 const double* win_istft, snmf_online_batch** out);
+/* Added within 5.  snmf_online_batch_process_f32 / _process_classes_f32 of an fp64 batch: fp64 PCM and outputs; the int16
+ * stream is the fp64 value rounded half away from zero. */
+int snmf_online_batch_process_f64(snmf_online_batch* b, const double* const* pcm, const int64_t* n, const int32_t* flush,
+                                  double* const* x_tilde_f64, int16_t* const* x_tilde_i16, double* const* x_hat_f64,
+                                  double* const* d_hat_f64, const int64_t* cap, int64_t* n_out);
+int snmf_online_batch_process_classes_f64(snmf_online_batch* b, const double* const* pcm, const int64_t* n, const int32_t* flush,
+                                          double* const* x_tilde_f64, int16_t* const* x_tilde_i16, double* const* x_hat_f64,
+                                          double* const* d_hat_f64, double* const* x_hat_i_f64, double* const* d_hat_i_f64,
+                                          const int64_t* cap, int64_t* n_out);
+/* Added within 5.  snmf_online_batch_restart of an fp64 batch with H0 (r x n) and Ad_blk0 (R_a x m_a x n) in fp64, so that a
+ * new recording starts from exactly the draws its fp64 reference run uses.  SNMF_ERR_STATE on an fp32 batch. */
+int snmf_online_batch_restart_f64(snmf_online_batch* b, int32_t n, const int32_t* slots, const double* B_DFT_d, const double* H0,
+                                  const double* Ad_blk0);
 /* Diagnostics of stream k's most recent frames (the newest 65536 per stream), as snmf_online_trace. */
 int snmf_online_batch_trace(snmf_online_batch* b, int32_t k, snmf_online_frame* out, int64_t cap, int64_t* n);
 void snmf_online_batch_destroy(snmf_online_batch* b);

@@ -29,8 +29,12 @@ _TU_HDRS = {
     "snmf_tu_wstats4.hip": ["snmf_generic.h", "snmf_wstats_dispatch.h"],
     "snmf_tu_wstats8.hip": ["snmf_generic.h", "snmf_wstats_dispatch.h"],
     "snmf_tu_online.hip": ["snmf_online_common.h", "snmf_online.h", "snmf_online_f64_host.h", "snmf_online_classes.h"],
-    "snmf_tu_online_f64.hip": ["snmf_online_common.h", "snmf_online_f64.h", "snmf_online_f64_host.h", "snmf_online_classes.h"],
-    "snmf_tu_online_batch.hip": ["snmf_online_common.h", "snmf_online_batch.h", "snmf_online_classes.h"],
+    "snmf_tu_online_f64.hip": ["snmf_online_common.h", "snmf_online_f64_core.h", "snmf_online_f64.h", "snmf_online_f64_host.h",
+                               "snmf_online_classes.h"],
+    "snmf_tu_online_batch.hip": ["snmf_online_common.h", "snmf_online_batch_common.h", "snmf_online_batch.h",
+                                 "snmf_online_batch_f64_host.h", "snmf_online_classes.h"],
+    "snmf_tu_online_batch_f64.hip": ["snmf_online_common.h", "snmf_online_batch_common.h", "snmf_online_f64_core.h",
+                                     "snmf_online_batch_f64.h", "snmf_online_batch_f64_host.h", "snmf_online_classes.h"],
     "snmf_tu_multi.hip": ["snmf_multi.h"],
     "snmf_tu_dnmf.hip": ["snmf_frontend.h", "snmf_philox.h"],
     "snmf_tu_smallf.hip": ["snmf_smallf.h"],
@@ -65,6 +69,8 @@ SYMBOLS = [
     "snmf_online_batch_restart_mel", "snmf_online_batch_get_mel_basis_f32", "snmf_online_batch_get_mel_basis_f64",
     "snmf_online_set_classes", "snmf_online_process_classes_f32", "snmf_online_process_classes_f64",
     "snmf_online_batch_set_classes", "snmf_online_batch_process_classes_f32",
+    "snmf_online_batch_create_f64", "snmf_online_batch_process_f64", "snmf_online_batch_process_classes_f64",
+    "snmf_online_batch_restart_f64",
     "snmf_multi_create", "snmf_multi_destroy", "snmf_multi_set_v_f64", "snmf_multi_set_v_f32", "snmf_multi_set_w_f64",
     "snmf_multi_set_w_f32", "snmf_multi_set_h_f64", "snmf_multi_set_h_f32", "snmf_multi_set_sparsity_f64",
     "snmf_multi_set_sparsity_f32", "snmf_multi_init", "snmf_multi_run", "snmf_multi_get_w_f64", "snmf_multi_get_w_f32",
@@ -281,6 +287,10 @@ def load():
     sig["snmf_online_process_classes_f64"] = (C.c_int, [vp, vp, i64, C.c_int, vp, vp, vp, vp, vp, vp, i64, C.POINTER(i64)])
     sig["snmf_online_batch_set_classes"] = (C.c_int, [vp, i32, vp, i32, vp])
     sig["snmf_online_batch_process_classes_f32"] = (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp])
+    sig["snmf_online_batch_create_f64"] = (C.c_int, [vp, OP, i32, vp, vp, vp, vp, vp, vp, C.POINTER(vp)])
+    sig["snmf_online_batch_process_f64"] = (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp])
+    sig["snmf_online_batch_process_classes_f64"] = (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp])
+    sig["snmf_online_batch_restart_f64"] = (C.c_int, [vp, i32, vp, vp, vp, vp])
     for ty in ("f64", "f32"):
         sig[f"snmf_plan_solve_frames_{ty}"] = (C.c_int, [vp, i32, vp, i64, i32, vp, vp, vp, vp])
     for nm in ("v", "w", "h", "mask"):

@@ -20,18 +20,9 @@
 // Included by snmf_tu_online_batch.hip only.
 #pragma once
 #include "snmf_online_common.h"
+#include "snmf_online_batch_common.h"
 
 namespace snmf {
-
-// per-stream, per-chunk framing (host-computed, uploaded once per chunk)
-struct OBatchFrames {
-    const int* nfr;        // [S] frames of stream s in this chunk
-    const int* nreal;      // [S] of which the first nreal come from PCM (the rest are the all-zero flush frames)
-    const int64_t* off;    // [S] sample offset of stream s's [history | hops] in the signal buffer
-    const int64_t* zoff;   // [S] offset of sz zero samples (the flush frames, src/NTF_sep_event_RT.m:69-76)
-    const int* l0;         // [S] 1-based index of stream s's first frame of the chunk
-    int S;
-};
 
 // src/bnmf_sep_event_RT_IS16.m:65-81 for every (frame, stream); PACK (DFT mode) also writes the floored solve input (k_pack's
 // floor) -- in Mel mode k_obmel writes it, at F_order rows
@@ -137,13 +128,6 @@ __global__ __launch_bounds__(256) void k_obclass(OBatchClassArgs a, OBatchFrames
     float* out = a.out + slot * a.F;
     if (a.mel_conv) oclass_mel<double>(a.B + (size_t)s * a.r * a.n1, A, a.cls, a.n_cls, a.n1, a.melmat, a.F, out, a.cstride, sm);
     else oclass_dft<float, double, float>(a.B + (size_t)s * a.r * a.F, A, a.cls, a.n_cls, a.F, out, a.cstride);
-}
-
-// the adaptation of stream s is due at frame `step`: the post-filter said so (:294, sum(r_up) > 0)
-__device__ __forceinline__ bool ob_due(const OnlineStatus* status, const int* nfr, int step, int S, int s) {
-    if (step >= nfr[s]) return false;
-    const OnlineStatus& st = status[(size_t)step * S + s];
-    return st.do_solve && st.n_up > 0;
 }
 
 // Mel mode's V of the adaptation solve (:298-303): melmat * lambda_d_blk (omel_project), column c of stream s's ring into

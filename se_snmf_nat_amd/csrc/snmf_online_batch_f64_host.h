@@ -1,0 +1,21 @@
+// snmf_online_batch_f64_host.h -- host interface between snmf_tu_online_batch.hip (owner of the snmf_online_batch handle) and
+// snmf_tu_online_batch_f64.hip (the fp64 batch behind it, kernels in snmf_online_batch_f64.h).  Declarations only.
+#pragma once
+#include "snmf.h"
+
+struct OnlineBatchF64;
+// `p` and S have passed snmf_tu_online_batch.hip's validation; the arrays are snmf_online_batch_create's, in fp64
+int online_batch_f64_create(snmf_ctx* ctx, const snmf_online_params* p, int32_t S, const double* Bx, const double* Bd0, const double* H0,
+                            const double* Ad0, const double* win_stft, const double* win_istft, OnlineBatchF64** out);
+void online_batch_f64_destroy(OnlineBatchF64* o);
+// xhi / dhi: the class signals (snmf_online_batch_process_classes_f64), class-major at cap[s], or NULL
+int online_batch_f64_process(OnlineBatchF64* o, const double* const* pcm, const int64_t* n, const int32_t* flush, double* const* xt,
+                             int16_t* const* xt_i16, double* const* xh, double* const* dh, double* const* xhi, double* const* dhi,
+                             const int64_t* cap, int64_t* n_out);
+int online_batch_f64_set_classes(OnlineBatchF64* o, int32_t event_num, const int32_t* event_rank, int32_t noise_num,
+                                 const int32_t* noise_rank);
+// Bd n x Rd x F or NULL (carry), H0 n x r or NULL, Ad n x Ra x ma or NULL
+int online_batch_f64_restart(OnlineBatchF64* o, int32_t n, const int32_t* slots, const double* Bd, const double* H0, const double* Ad);
+void online_batch_f64_dims(OnlineBatchF64* o, int* r, int* ra_ma);  // lengths of one stream's H0 and Ad_blk0
+int online_batch_f64_get_basis(OnlineBatchF64* o, int32_t k, double* Bd, int64_t ld);
+int online_batch_f64_trace(OnlineBatchF64* o, int32_t k, snmf_online_frame* out, int64_t cap, int64_t* n);

@@ -2,6 +2,7 @@
 // snmf_online_batch.h.  A translation unit of its own, so that the single-stream kernels' code does not move.
 #include "snmf_internal.h"
 #include "snmf_online_batch.h"
+#include "snmf_online_batch_f64_host.h"  // the fp64 mode's host entry points (its kernels live in snmf_tu_online_batch_f64.hip)
 #include "snmf_online_classes.h"
 
 // Host side: per stream, the hop queue / history / flush logic of snmf_online_process_f32 (snmf_tu_online.hip); on the
@@ -15,6 +16,7 @@ constexpr int64_t kBChunkSlots = 16384;  // (frame, stream) slots of one device 
 
 struct snmf_online_batch {
     snmf_ctx* ctx = nullptr;
+    OnlineBatchF64* f64 = nullptr;  // non-null: an fp64 batch (snmf_online_batch_create_f64); every field below S is then unused
     snmf_online_params p{};
     int S = 0, F = 0, r = 0, N = 0, nov = 0, Ra = 1, ma = 1, Pl = 1, RA2 = 64;
     int Fs = 0;                                // rows of the solves: F, or F_order in Mel mode
@@ -86,6 +88,11 @@ static void ob_free_chunk(snmf_online_batch* o) {
 
 extern "C" void snmf_online_batch_destroy(snmf_online_batch* o) {
     if (!o) return;
+    if (o->f64) {
+        online_batch_f64_destroy(o->f64);
+        delete o;
+        return;
+    }
     hipSetDevice(o->ctx->device);
     hipStreamSynchronize(o->ctx->stream);
     if (o->hp) snmf_plan_destroy(o->hp);
@@ -284,6 +291,7 @@ extern "C" int snmf_online_batch_create(snmf_ctx* ctx, const snmf_online_params*
 extern "C" int snmf_online_batch_set_mel(snmf_online_batch* o, int32_t F_order, int32_t mel_conv, const float* melmat, const float* BMx,
                                          const float* BMd) {
     if (!o || !melmat || !BMx || !BMd) return fail(SNMF_ERR_INVALID, "NULL argument");
+    if (o->f64) return fail(SNMF_ERR_UNSUPPORTED, "fp64 batched separator: B_sep_mode 'Mel' is not supported");
     if (o->failed) return fail(SNMF_ERR_STATE, "an earlier call failed midway through a chunk; the batch state is not reusable, create a new one");
     if (o->started) return fail(SNMF_ERR_STATE, "snmf_online_batch_set_mel must precede the first process call");
     if (F_order < 2 || F_order > o->F) return fail(SNMF_ERR_INVALID, "F_order must be in [2, fftlength/2+1]");
@@ -338,6 +346,7 @@ extern "C" int snmf_online_batch_set_mel(snmf_online_batch* o, int32_t F_order, 
 extern "C" int snmf_online_batch_set_classes(snmf_online_batch* o, int32_t event_num, const int32_t* event_rank, int32_t noise_num,
                                              const int32_t* noise_rank) {
     if (!o) return fail(SNMF_ERR_INVALID, "online batch handle is NULL");
+    if (o->f64) return online_batch_f64_set_classes(o->f64, event_num, event_rank, noise_num, noise_rank);
     if (o->failed) return fail(SNMF_ERR_STATE, "an earlier call failed midway through a chunk; the batch state is not reusable, create a new one");
     if (!o->p.class_outputs) return fail(SNMF_ERR_STATE, "class outputs were not requested at creation");
     if (o->started) return fail(SNMF_ERR_STATE, "snmf_online_batch_set_classes must precede the first process call");
@@ -720,6 +729,7 @@ static int ob_process(snmf_online_batch* o, const float* const* pcm, const int64
     const int hop = p.frameshift;
     if (n_out)
         for (int s = 0; s < S; ++s) n_out[s] = 0;
+    if (o->f64) return fail(SNMF_ERR_STATE, "snmf_online_batch_process_f32 on an fp64 batch: use snmf_online_batch_process_f64");
     if (o->failed) return fail(SNMF_ERR_STATE, "an earlier call failed midway through a chunk; the batch state is not reusable, create a new one");
     if ((xh_f32 || dh_f32 || xhi_f32 || dhi_f32) && !p.class_outputs) return fail(SNMF_ERR_STATE, "class outputs were not requested at creation");
     const bool any_out = xt_f32 || xt_i16 || xh_f32 || dh_f32 || xhi_f32 || dhi_f32;
@@ -809,11 +819,15 @@ extern "C" int snmf_online_batch_get_basis_f32(snmf_online_batch* o, int32_t k, 
     if (!o || !Bd) return fail(SNMF_ERR_INVALID, "NULL argument");
     if (k < 0 || k >= o->S) return fail(SNMF_ERR_INVALID, "stream %d out of range [0, %d)", k, o->S);
     if (ld < o->F) return fail(SNMF_ERR_INVALID, "ld < F");
-    HIP_TRY(hipSetDevice(o->ctx->device));
-    HIP_TRY(hipStreamSynchronize(o->ctx->stream));
     const size_t F = o->F, Rd = o->p.R_d;
     std::vector<double> h(F * Rd);
-    HIP_TRY(hipMemcpy(h.data(), o->B + (size_t)k * o->r * F + (size_t)o->p.R_x * F, h.size() * 8, hipMemcpyDeviceToHost));
+    if (o->f64) {  // the fp64 dictionary, rounded
+        SN_TRY(online_batch_f64_get_basis(o->f64, k, h.data(), (int64_t)F));
+    } else {
+        HIP_TRY(hipSetDevice(o->ctx->device));
+        HIP_TRY(hipStreamSynchronize(o->ctx->stream));
+        HIP_TRY(hipMemcpy(h.data(), o->B + (size_t)k * o->r * F + (size_t)o->p.R_x * F, h.size() * 8, hipMemcpyDeviceToHost));
+    }
     for (size_t j = 0; j < Rd; ++j)
         for (size_t f = 0; f < F; ++f) Bd[j * ld + f] = (float)h[j * F + f];  // the single-stream separator's fp32 mirror
     return SNMF_OK;
@@ -821,6 +835,7 @@ extern "C" int snmf_online_batch_get_basis_f32(snmf_online_batch* o, int32_t k, 
 
 extern "C" int snmf_online_batch_get_basis_f64(snmf_online_batch* o, int32_t k, double* Bd, int64_t ld) {
     if (!o || !Bd) return fail(SNMF_ERR_INVALID, "NULL argument");
+    if (o->f64) return online_batch_f64_get_basis(o->f64, k, Bd, ld);
     if (k < 0 || k >= o->S) return fail(SNMF_ERR_INVALID, "stream %d out of range [0, %d)", k, o->S);
     if (ld < o->F) return fail(SNMF_ERR_INVALID, "ld < F");
     HIP_TRY(hipSetDevice(o->ctx->device));
@@ -862,18 +877,28 @@ static int ob_restart_checked(snmf_online_batch* o, int32_t n, const int32_t* sl
 extern "C" int snmf_online_batch_restart(snmf_online_batch* o, int32_t n, const int32_t* slots, const double* Bd, const float* H0,
                                          const float* Ad) {
     if (!o) return fail(SNMF_ERR_INVALID, "online batch handle is NULL");
+    if (o->f64) {  // H0 / Ad_blk0 widened; snmf_online_batch_restart_f64 takes them in fp64
+        if (n < 0 || n > o->S) return fail(SNMF_ERR_INVALID, "restart of %d streams in a batch of %d", n, o->S);  // (before H0 / Ad_blk0 are read)
+        int r = 0, na = 0;
+        online_batch_f64_dims(o->f64, &r, &na);
+        const size_t m = (size_t)n;
+        std::vector<double> h(H0 ? H0 : nullptr, H0 ? H0 + m * r : nullptr), a(Ad ? Ad : nullptr, Ad ? Ad + m * na : nullptr);
+        return online_batch_f64_restart(o->f64, n, slots, Bd, H0 ? h.data() : nullptr, Ad ? a.data() : nullptr);
+    }
     return ob_restart_checked(o, n, slots, Bd, nullptr, H0, Ad);  // Mel mode: B_Mel_d carried
 }
 
 extern "C" int snmf_online_batch_restart_mel(snmf_online_batch* o, int32_t n, const int32_t* slots, const double* Bd, const double* Bmd,
                                              const float* H0, const float* Ad) {
     if (!o) return fail(SNMF_ERR_INVALID, "online batch handle is NULL");
+    if (o->f64) return fail(SNMF_ERR_UNSUPPORTED, "fp64 batched separator: B_sep_mode 'Mel' is not supported");
     if (Bmd && !o->mel) return fail(SNMF_ERR_STATE, "B_Mel_d given to a batch that is not in Mel mode");
     return ob_restart_checked(o, n, slots, Bd, Bmd, H0, Ad);
 }
 
 // stream k's B_Mel_d (the fp64 master), n1 x Rd
 static int ob_mel_basis(snmf_online_batch* o, int32_t k, int64_t ld, std::vector<double>& h) {
+    if (o->f64) return fail(SNMF_ERR_UNSUPPORTED, "fp64 batched separator: B_sep_mode 'Mel' is not supported");
     if (!o->mel) return fail(SNMF_ERR_STATE, "not in Mel mode");
     if (k < 0 || k >= o->S) return fail(SNMF_ERR_INVALID, "stream %d out of range [0, %d)", k, o->S);
     if (ld < o->n1) return fail(SNMF_ERR_INVALID, "ld < F_order");
@@ -906,9 +931,63 @@ extern "C" int snmf_online_batch_get_mel_basis_f64(snmf_online_batch* o, int32_t
 
 extern "C" int snmf_online_batch_trace(snmf_online_batch* o, int32_t k, snmf_online_frame* out, int64_t cap, int64_t* n) {
     if (!o) return fail(SNMF_ERR_INVALID, "online batch handle is NULL");
+    if (o->f64) return online_batch_f64_trace(o->f64, k, out, cap, n);
     if (k < 0 || k >= o->S) return fail(SNMF_ERR_INVALID, "stream %d out of range [0, %d)", k, o->S);
     const auto& tr = o->trace[k];
     if (n) *n = (int64_t)tr.size();
     if (out && cap > 0) std::copy_n(tr.begin(), (size_t)std::min<int64_t>(cap, (int64_t)tr.size()), out);
     return SNMF_OK;
+}
+
+// ---- fp64 mode (snmf_online_batch_f64.h): every input crosses in fp64 and every step from PCM to the fed-back state is fp64 ----
+extern "C" int snmf_online_batch_create_f64(snmf_ctx* ctx, const snmf_online_params* p, int32_t S, const double* Bx, const double* Bd0,
+                                            const double* H0, const double* Ad0, const double* win_stft, const double* win_istft,
+                                            snmf_online_batch** out) {
+    if (!ctx || !out || !Bx || !Bd0 || !H0 || !win_stft || !win_istft) return fail(SNMF_ERR_INVALID, "NULL argument");
+    *out = nullptr;
+    SN_TRY(ob_validate(p, S));  // (refuses basis_update_N / _E)
+    if (p->adapt_train_N && !Ad0) return fail(SNMF_ERR_INVALID, "Ad_blk0 is required when adapt_train_N is set");
+    (void)hipGetLastError();  // clean sticky error state, see PLAN_CHECK
+    OnlineBatchF64* f = nullptr;
+    SN_TRY(online_batch_f64_create(ctx, p, S, Bx, Bd0, H0, Ad0, win_stft, win_istft, &f));
+    snmf_online_batch* o = new snmf_online_batch();
+    o->ctx = ctx;
+    o->f64 = f;
+    o->p = *p;
+    o->S = S;
+    o->F = p->fftlength / 2 + 1;
+    *out = o;
+    return SNMF_OK;
+}
+
+static int ob_process_f64(snmf_online_batch* o, const double* const* pcm, const int64_t* n, const int32_t* flush, double* const* xt,
+                          int16_t* const* xt_i16, double* const* xh, double* const* dh, double* const* xhi, double* const* dhi,
+                          const int64_t* cap, int64_t* n_out) {
+    if (!o) return fail(SNMF_ERR_INVALID, "online batch handle is NULL");
+    if (!o->f64) {
+        if (n_out)
+            for (int s = 0; s < o->S; ++s) n_out[s] = 0;
+        return fail(SNMF_ERR_STATE, "snmf_online_batch_process_f64 needs a batch made by snmf_online_batch_create_f64");
+    }
+    return online_batch_f64_process(o->f64, pcm, n, flush, xt, xt_i16, xh, dh, xhi, dhi, cap, n_out);
+}
+
+extern "C" int snmf_online_batch_process_f64(snmf_online_batch* o, const double* const* pcm, const int64_t* n, const int32_t* flush,
+                                             double* const* xt_f64, int16_t* const* xt_i16, double* const* xh_f64, double* const* dh_f64,
+                                             const int64_t* cap, int64_t* n_out) {
+    return ob_process_f64(o, pcm, n, flush, xt_f64, xt_i16, xh_f64, dh_f64, nullptr, nullptr, cap, n_out);
+}
+
+extern "C" int snmf_online_batch_process_classes_f64(snmf_online_batch* o, const double* const* pcm, const int64_t* n, const int32_t* flush,
+                                                     double* const* xt_f64, int16_t* const* xt_i16, double* const* xh_f64,
+                                                     double* const* dh_f64, double* const* xhi_f64, double* const* dhi_f64,
+                                                     const int64_t* cap, int64_t* n_out) {
+    return ob_process_f64(o, pcm, n, flush, xt_f64, xt_i16, xh_f64, dh_f64, xhi_f64, dhi_f64, cap, n_out);
+}
+
+extern "C" int snmf_online_batch_restart_f64(snmf_online_batch* o, int32_t n, const int32_t* slots, const double* Bd, const double* H0,
+                                             const double* Ad) {
+    if (!o) return fail(SNMF_ERR_INVALID, "online batch handle is NULL");
+    if (!o->f64) return fail(SNMF_ERR_STATE, "snmf_online_batch_restart_f64 needs a batch made by snmf_online_batch_create_f64");
+    return online_batch_f64_restart(o->f64, n, slots, Bd, H0, Ad);
 }

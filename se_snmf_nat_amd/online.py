@@ -23,6 +23,13 @@ shipped partition -- one class per side -- is x_hat / d_hat themselves and runs 
 `OnlineSeparator(..., precision="fp64")` is the fp64 mode (snmf_online_create_f64): every array crosses in float64 and every
 step from PCM to the fed-back dictionary runs in fp64 on the device, so the separator holds the fp64 reference's per-frame
 decisions over whole recordings (docs/WIDENING.md, "Parity horizon").  DFT mode and the supervised frame solve only.
+
+`OnlineBatchSeparator(..., precision="fp64")`, `ntf_sep_event_rt_batch(..., precision="fp64")` and
+`ntf_sep_event_rt_chains(..., precision="fp64")` are the same mode for many streams (snmf_online_batch_create_f64): every
+stream holds its own fp64 reference run's decisions, also over a chain of files with the adapted dictionary carried.  It
+covers B_sep_mode 'DFT', the supervised frame solve, every cf / beta_div, Wiener / MMSE, block sparsity, adaptation on or
+off, class outputs, restart and chains; it refuses (SnmfError 8) B_sep_mode 'Mel', basis_update_N / basis_update_E and, with
+adaptation, a ring beyond R_a <= 64, m_a <= 128.
 """
 from __future__ import annotations
 
@@ -327,10 +334,17 @@ class OnlineBatchSeparator:
     from RandomState(random_seed + k).  B_sep_mode 'DFT', or 'Mel' with `B_Mel_x` (F_order x R_x, shared) and `B_Mel_d`
     (one F_order x R_d array or S of them, like B_DFT_d); the supervised frame solve only (SNMF_ERR_UNSUPPORTED otherwise).
     In DFT mode the Mel arguments are ignored, as in OnlineSeparator.  p.EVENT_RANK / p.NOISE_RANK: one class partition for
-    all streams (with class_outputs each stream's dict also holds 'x_hat_i' / 'd_hat_i')."""
+    all streams (with class_outputs each stream's dict also holds 'x_hat_i' / 'd_hat_i').
+    precision="fp64" is the fp64 mode (snmf_online_batch_create_f64): every array crosses in float64, the signals come back
+    as float64 and basis(k) is the fp64 dictionary; DFT mode only ('Mel' raises SnmfError(8) before any device call)."""
 
     def __init__(self, B_DFT_x, B_DFT_d, p, n_streams, H0=None, Ad_blk0=None, ctx=None, class_outputs=False, B_Mel_x=None,
-                 B_Mel_d=None):
+                 B_Mel_d=None, precision="fp32"):
+        if precision not in ("fp32", "fp64"):
+            raise ValueError("precision must be 'fp32' or 'fp64'")
+        self.precision = precision
+        dt = np.float64 if precision == "fp64" else np.float32  # what crosses the C ABI
+        self._dt = dt
         S = int(n_streams)
         if S < 1:
             raise _invalid("n_streams must be >= 1")
@@ -339,6 +353,8 @@ class OnlineBatchSeparator:
         mode = p.get("B_sep_mode", "DFT")
         if mode not in ("DFT", "Mel"):
             raise SnmfError(8, f"batched separator: B_sep_mode {mode!r} is not supported")  # SNMF_ERR_UNSUPPORTED
+        if mode == "Mel" and precision == "fp64":
+            raise SnmfError(8, "fp64 batched separator: B_sep_mode 'Mel' is not supported")  # as snmf_online_batch_set_mel
         if mode == "Mel" and (B_Mel_x is None or B_Mel_d is None):
             raise SnmfError(8, "batched separator: B_sep_mode 'Mel' needs B_Mel_x and B_Mel_d")
         if "cost_check" not in p:
@@ -347,7 +363,7 @@ class OnlineBatchSeparator:
         if method not in ("Wiener", "MMSE"):
             raise ValueError("ENHANCE_METHOD must be 'Wiener' or 'MMSE'")
         F = p["fftlength"] // 2 + 1
-        Bx = np.asfortranarray(B_DFT_x, dtype=np.float32)
+        Bx = np.asfortranarray(B_DFT_x, dtype=dt)
         if Bx.ndim != 2 or Bx.shape[0] != F:
             raise _invalid(f"B_DFT_x must have fftlength/2+1 = {F} rows")
         R_x = Bx.shape[1]
@@ -369,9 +385,9 @@ class OnlineBatchSeparator:
                     draws_a.append(rs.random_sample((R_a, m_a)))
             H0 = draws_h if H0 is None else H0
             Ad_blk0 = draws_a if (adapt and Ad_blk0 is None) else Ad_blk0
-        Bd = _per_stream(B_DFT_d, S, (F, R_d), "B_DFT_d", "F")
-        H = _per_stream(H0, S, (r,), "H0", "F")
-        Ad = _per_stream(Ad_blk0, S, (R_a, m_a), "Ad_blk0", "F") if adapt else None
+        Bd = _per_stream(B_DFT_d, S, (F, R_d), "B_DFT_d", "F", dt)
+        H = _per_stream(H0, S, (r,), "H0", "F", dt)
+        Ad = _per_stream(Ad_blk0, S, (R_a, m_a), "Ad_blk0", "F", dt) if adapt else None
         self.mel = mode == "Mel"
         if self.mel:
             n1 = int(p.get("F_order", 64))
@@ -387,16 +403,16 @@ class OnlineBatchSeparator:
         self.ctx = ctx or default_context()
         self.F, self.R_x, self.R_d, self.S = F, R_x, R_d, S
         self.adapt, self.R_a, self.m_a = adapt, R_a, m_a
-        ws = np.ascontiguousarray(p["win_STFT"], dtype=np.float32)
-        wi = np.ascontiguousarray(p["win_ISTFT"], dtype=np.float32)
+        ws = np.ascontiguousarray(p["win_STFT"], dtype=dt)
+        wi = np.ascontiguousarray(p["win_ISTFT"], dtype=dt)
         q = _online_params(p, R_x, R_d, adapt, R_a, m_a, method, class_outputs)
         self._q = q
         self.class_outputs = bool(class_outputs)
         self.hop, self.delay = q.frameshift, q.delay
         h = C.c_void_p()
-        _lib.check(self._lib.snmf_online_batch_create(self.ctx._h, C.byref(q), S, Bx.ctypes.data, Bd.ctypes.data, H.ctypes.data,
-                                                      Ad.ctypes.data if Ad is not None else None, ws.ctypes.data, wi.ctypes.data,
-                                                      C.byref(h)))
+        create = self._lib.snmf_online_batch_create_f64 if precision == "fp64" else self._lib.snmf_online_batch_create
+        _lib.check(create(self.ctx._h, C.byref(q), S, Bx.ctypes.data, Bd.ctypes.data, H.ctypes.data,
+                          Ad.ctypes.data if Ad is not None else None, ws.ctypes.data, wi.ctypes.data, C.byref(h)))
         self._h = h
         self.ctx._plans.add(self)  # destroyed before the context
         if self.mel:
@@ -412,19 +428,19 @@ class OnlineBatchSeparator:
 
     def process(self, pcms, flush=False):
         """Feed every stream: `pcms` is a list of S sample arrays (any may be empty); `flush` a bool for all or a list of
-        S bools.  Returns a list of S dicts, each as OnlineSeparator.process returns."""
-        S = self.S
+        S bools.  Returns a list of S dicts, each as OnlineSeparator.process returns (float64 signals with precision="fp64")."""
+        S, dt, f64 = self.S, self._dt, self.precision == "fp64"
         if len(pcms) != S:
             raise _invalid(f"{len(pcms)} PCM arrays for {S} streams")
         fl = [bool(flush)] * S if np.isscalar(flush) or flush is None else [bool(x) for x in flush]
         if len(fl) != S:
             raise _invalid(f"{len(fl)} flush flags for {S} streams")
-        xs = [np.ascontiguousarray(np.asarray(x).reshape(-1), dtype=np.float32) for x in pcms]
+        xs = [np.ascontiguousarray(np.asarray(x).reshape(-1), dtype=dt) for x in pcms]
         caps = np.array([(x.size // self.hop + self.delay + 3) * self.hop for x in xs], dtype=np.int64)
-        of = [np.zeros(c, np.float32) for c in caps]
+        of = [np.zeros(c, dt) for c in caps]
         o16 = [np.zeros(c, np.int16) for c in caps]
-        xh = [np.zeros(c, np.float32) for c in caps] if self.class_outputs else None
-        dh = [np.zeros(c, np.float32) for c in caps] if self.class_outputs else None
+        xh = [np.zeros(c, dt) for c in caps] if self.class_outputs else None
+        dh = [np.zeros(c, dt) for c in caps] if self.class_outputs else None
         P = C.c_void_p * S
         ptrs = lambda arrs: P(*[a.ctypes.data if a.size else None for a in arrs])  # noqa: E731
         n = np.array([x.size for x in xs], dtype=np.int64)
@@ -433,11 +449,13 @@ class OnlineBatchSeparator:
         head = (self._h, ptrs(xs), n.ctypes.data, f32.ctypes.data, P(*[a.ctypes.data for a in of]), P(*[a.ctypes.data for a in o16]),
                 P(*[a.ctypes.data for a in xh]) if xh else None, P(*[a.ctypes.data for a in dh]) if dh else None)
         if self._classes is None:  # one class per side: exactly the call a batch without classes makes
-            _lib.check(self._lib.snmf_online_batch_process_f32(*head, caps.ctypes.data, n_out.ctypes.data))
+            process = self._lib.snmf_online_batch_process_f64 if f64 else self._lib.snmf_online_batch_process_f32
+            _lib.check(process(*head, caps.ctypes.data, n_out.ctypes.data))
         else:
-            xhi = [np.zeros((self._classes[0].size, c), np.float32) for c in caps]
-            dhi = [np.zeros((self._classes[1].size, c), np.float32) for c in caps]
-            _lib.check(self._lib.snmf_online_batch_process_classes_f32(
+            xhi = [np.zeros((self._classes[0].size, c), dt) for c in caps]
+            dhi = [np.zeros((self._classes[1].size, c), dt) for c in caps]
+            process = self._lib.snmf_online_batch_process_classes_f64 if f64 else self._lib.snmf_online_batch_process_classes_f32
+            _lib.check(process(
                 *head, P(*[a.ctypes.data for a in xhi]), P(*[a.ctypes.data for a in dhi]), caps.ctypes.data, n_out.ctypes.data))
         outs = []
         for k in range(S):
@@ -467,8 +485,8 @@ class OnlineBatchSeparator:
         if len(set(ks)) != n:
             raise _invalid("a stream is listed twice")
         Bd = None if B_DFT_d is None else _per_stream(B_DFT_d, n, (self.F, self.R_d), "B_DFT_d", "F", np.float64)
-        H = None if H0 is None else _per_stream(H0, n, (self.R_x + self.R_d,), "H0", "F")
-        Ad = None if (Ad_blk0 is None or not self.adapt) else _per_stream(Ad_blk0, n, (self.R_a, self.m_a), "Ad_blk0", "F")
+        H = None if H0 is None else _per_stream(H0, n, (self.R_x + self.R_d,), "H0", "F", self._dt)
+        Ad = None if (Ad_blk0 is None or not self.adapt) else _per_stream(Ad_blk0, n, (self.R_a, self.m_a), "Ad_blk0", "F", self._dt)
         if B_Mel_d is not None and not self.mel:
             raise SnmfError(7, "B_Mel_d given to a batch that is not in Mel mode")  # SNMF_ERR_STATE, as the C entry
         Bm = None if B_Mel_d is None else _per_stream(B_Mel_d, n, (self.n1, self.R_d), "B_Mel_d", "F", np.float64)
@@ -478,11 +496,15 @@ class OnlineBatchSeparator:
         ptr = lambda a: a.ctypes.data if a is not None else None  # noqa: E731
         if self.mel:
             _lib.check(self._lib.snmf_online_batch_restart_mel(self._h, n, sl.ctypes.data, ptr(Bd), ptr(Bm), ptr(H), ptr(Ad)))
+        elif self.precision == "fp64":  # H0 / Ad_blk0 cross in fp64 too
+            _lib.check(self._lib.snmf_online_batch_restart_f64(self._h, n, sl.ctypes.data, ptr(Bd), ptr(H), ptr(Ad)))
         else:
             _lib.check(self._lib.snmf_online_batch_restart(self._h, n, sl.ctypes.data, ptr(Bd), ptr(H), ptr(Ad)))
 
     def basis(self, k):
-        """Current B_DFT_d of stream k."""
+        """Current B_DFT_d of stream k; with precision="fp64" the fp64 dictionary."""
+        if self.precision == "fp64":
+            return self.basis_f64(k)
         B = np.zeros((self.F, self.R_d), dtype=np.float32, order="F")
         _lib.check(self._lib.snmf_online_batch_get_basis_f32(self._h, int(k), B.ctypes.data, self.F))
         return B.astype(np.float64)
@@ -530,11 +552,13 @@ class OnlineBatchSeparator:
             pass
 
 
-def ntf_sep_event_rt_batch(pcms, B_DFT_x, B_DFT_d, p, H0=None, Ad_blk0=None, ctx=None, B_Mel_x=None, B_Mel_d=None):
+def ntf_sep_event_rt_batch(pcms, B_DFT_x, B_DFT_d, p, H0=None, Ad_blk0=None, ctx=None, B_Mel_x=None, B_Mel_d=None,
+                           precision="fp32"):
     """src/NTF_sep_event_RT.m for several recordings at once (the per-target loop of Do_MultiBatch_IS16_20160324.m:183-205
     as one batch): returns a list of the (int16, float, final B_DFT_d) triples ntf_sep_event_rt returns (Mel mode: the
-    final B_Mel_d)."""
-    sep = OnlineBatchSeparator(B_DFT_x, B_DFT_d, p, len(pcms), H0=H0, Ad_blk0=Ad_blk0, ctx=ctx, B_Mel_x=B_Mel_x, B_Mel_d=B_Mel_d)
+    final B_Mel_d).  precision="fp64": the fp64 mode of OnlineBatchSeparator."""
+    sep = OnlineBatchSeparator(B_DFT_x, B_DFT_d, p, len(pcms), H0=H0, Ad_blk0=Ad_blk0, ctx=ctx, B_Mel_x=B_Mel_x, B_Mel_d=B_Mel_d,
+                               precision=precision)
     try:
         outs = sep.process(list(pcms), flush=True)
         fin = sep.mel_basis if sep.mel else sep.basis
@@ -569,7 +593,7 @@ def _per_chain(x, n, shape, name, dtype):
 
 
 def ntf_sep_event_rt_chains(chains, B_DFT_x, B_DFT_d, p, n_streams=None, H0=None, Ad_blk0=None, ctx=None, chunk_hops=None,
-                            B_Mel_x=None, B_Mel_d=None):
+                            B_Mel_x=None, B_Mel_d=None, precision="fp32"):
     """Do_MultiBatch_IS16_20160324.m:183-205 + run_ntf_sep_RT.m:10-41 on one batch: `chains` is a list of chains, each a
     list of PCM arrays enhanced in turn by src/NTF_sep_event_RT.m.  Chain c starts from B_DFT_d (one array or one per
     chain; the delete('B_D_u.mat') of :187), and every later file starts from the dictionary its predecessor adapted,
@@ -582,7 +606,11 @@ def ntf_sep_event_rt_chains(chains, B_DFT_x, B_DFT_d, p, n_streams=None, H0=None
     default drawn from RandomState(random_seed + c), as OnlineBatchSeparator draws for stream k) for all its files, so
     its bits depend neither on its slot, `n_streams` or `chunk_hops` nor on the other chains.  Start dictionaries enter
     in fp32, as in ntf_sep_event_rt_batch.  In Mel mode (B_Mel_x, and B_Mel_d as one array or one per chain) a chain
-    carries both dictionaries (:137-139) and its triples hold the final B_Mel_d."""
+    carries both dictionaries (:137-139) and its triples hold the final B_Mel_d.
+    precision="fp64": the fp64 mode of OnlineBatchSeparator; start dictionaries, H0 and Ad_blk0 then enter as float64 (not
+    rounded to fp32 first), the float signals and final dictionaries are the fp64 ones, and the slot-independence above holds."""
+    if precision not in ("fp32", "fp64"):
+        raise ValueError("precision must be 'fp32' or 'fp64'")
     chains = [[np.asarray(x).reshape(-1) for x in c] for c in chains]
     nc = len(chains)
     if nc == 0:
@@ -601,8 +629,11 @@ def ntf_sep_event_rt_chains(chains, B_DFT_x, B_DFT_d, p, n_streams=None, H0=None
     r = R_x + R_d
     adapt = int(bool(p.get("adapt_train_N", 0)))
     R_a, m_a = int(p.get("R_a", 1)), int(p.get("m_a", 1))
-    Bds = _per_chain(B_DFT_d, nc, (F, R_d), "B_DFT_d", np.float32)  # (fp32 values, restarted with in fp64)
+    # (fp32 mode: fp32 values, restarted with in fp64; fp64 mode: the doubles as they are)
+    Bds = _per_chain(B_DFT_d, nc, (F, R_d), "B_DFT_d", np.float64 if precision == "fp64" else np.float32)
     mel = p.get("B_sep_mode", "DFT") == "Mel"
+    if mel and precision == "fp64":
+        raise SnmfError(8, "fp64 batched separator: B_sep_mode 'Mel' is not supported")
     Bms = None
     if mel:
         if B_Mel_x is None or B_Mel_d is None:
@@ -633,7 +664,7 @@ def ntf_sep_event_rt_chains(chains, B_DFT_x, B_DFT_d, p, n_streams=None, H0=None
     dr = {c: draws(c) for c in set(init)}
     sep = OnlineBatchSeparator(Bx, [Bds[c] for c in init], p, S, H0=[dr[c][0] for c in init],
                                Ad_blk0=[dr[c][1] for c in init] if adapt else None, ctx=ctx, B_Mel_x=B_Mel_x,
-                               B_Mel_d=[Bms[c] for c in init] if mel else None)
+                               B_Mel_d=[Bms[c] for c in init] if mel else None, precision=precision)
     fin = sep.mel_basis if mel else sep.basis
     hop = sep.hop
     step = int(chunk_hops) if chunk_hops else max(1, min(4096, _B_CHUNK_SLOTS // S))
@@ -652,7 +683,7 @@ def ntf_sep_event_rt_chains(chains, B_DFT_x, B_DFT_d, p, n_streams=None, H0=None
                 sep.restart(fresh, [Bds[c] for c in cs], [d[0] for d in ds], [d[1] for d in ds] if adapt else None,
                             B_Mel_d=[Bms[c] for c in cs] if mel else None)
             carry, fresh = [], []
-            pcms, flush = [np.zeros(0, np.float32)] * S, [False] * S
+            pcms, flush = [np.zeros(0, sep._dt)] * S, [False] * S
             for k, st in busy.items():
                 x = chains[st[0]][st[1]]
                 pcms[k] = x[st[2]:st[2] + step * hop]
