@@ -1,0 +1,414 @@
+// snmf_online_batch_host.h -- the host driver of the batched online separator, shared by its two precisions
+// (snmf_tu_online_batch.hip: fp32, handle snmf_online_batch; snmf_tu_online_batch_f64.hip: fp64, handle OnlineBatchF64).
+// Host code only: no kernel and no device function lives here.
+//
+// Per stream, the hop queue / history / flush logic of snmf_online_process_f32 (snmf_tu_online.hip); on the device, one fixed
+// sequence of launches per frame step for all streams (frame solve, post-filter, class spectra, gated adaptation) -- with
+// the dictionary fixed, one launch of each for the whole chunk.  A chunk synchronises ONCE: outputs, statuses and
+// adaptation verdicts are copied back together at its end.
+//
+// A mode's handle H derives from OBatchState<T> and defines, as overloads on H*, the steps that differ between the modes:
+//   int obm_chunk_frames(const H*)                               frames per stream of one device chunk
+//   int obm_reserve(H*, size_t slots), void obm_free_chunk(H*)   the mode's own chunk buffers (slots = C * S)
+//   int obm_begin_chunk(H*, fr, C)                               STFT of the chunk (fp32: with the Mel projection) and the chunk's post-filter arguments
+//   int obm_frame_solve(H*, fr, step, C)                         frame `step` of every stream; step < 0: all C frames
+//   int obm_post(H*, fr, step)                                   likewise
+//   int obm_class_spectra(H*, fr, step, C)                       likewise (only with a class partition set)
+//   int obm_adapt(H*, fr, step)                                  adaptation + re-assembly + dictionary refresh behind frame `step`
+//   int obm_tail(H*, tail, fr, syn_stride, store)                overlap-add tail into (0) / out of (1) the synthesis buffer
+//   int obm_istft(H*, mag, fr, C, syn_stride)                    inverse STFT of the kept frames
+//   int obm_ola(H*, gx, fr, syn_stride, d_if, d_no, d_oo, out, out16)   overlap-add to output hops
+// The calls are resolved at compile time (argument-dependent lookup on the handle type); nothing is dispatched at run time.
+#pragma once
+#include "snmf_internal.h"
+#include "snmf_online_batch_common.h"
+
+constexpr size_t kBTraceCap = 1u << 16;   // per stream: the newest 65536 frames, as snmf_online_trace
+constexpr int64_t kBChunkSlots = 16384;  // (frame, stream) slots of one device chunk
+
+// What the two modes' handles hold in common; T is the mode's element type (float / double).
+template <typename T>
+struct OBatchState {
+    using elem = T;
+    snmf_ctx* ctx = nullptr;
+    snmf_online_params p{};
+    int S = 0, F = 0, r = 0, N = 0, nov = 0, Ra = 1, ma = 1, Pl = 1;
+    bool started = false;  // a process call was made (set_mel / set_classes must come first)
+    bool failed = false;
+    size_t ntail = 0;
+    // per stream, device
+    T *tail = nullptr, *tail_x = nullptr, *tail_d = nullptr;
+    uint8_t* rup = nullptr;
+    OnlineDev* dev = nullptr;
+    int* rs_slots = nullptr;     // restart upload (sized for all S streams)
+    int* meta_i = nullptr;       // [6][S] nfr, nreal, l0, i_first, n_out, (pad)
+    int64_t* meta_l = nullptr;   // [3][S] off, zoff, out_off
+    // per-class outputs (set_classes): n_ev event classes then n_cls - n_ev noise classes; n_cls = 0: none set
+    int n_ev = 0, n_cls = 0;
+    int* cls = nullptr;          // [n_cls + 1] column ranges over [B_x | B_d] (snmf_online_classes.h)
+    T* tail_c = nullptr;         // [n_cls][S][ntail] one overlap-add tail per class and stream
+    // per chunk, device (grown on demand)
+    int C = 0;  // frames per stream per chunk
+    size_t cap_sig = 0, cap_out = 0;
+    T *sig = nullptr, *Ym = nullptr, *Xt = nullptr, *Xh = nullptr, *Dh = nullptr, *syn = nullptr, *outf = nullptr;
+    ocplx<T>* Yph = nullptr;
+    int16_t* out16 = nullptr;
+    T *Xc = nullptr, *out_c = nullptr;  // class-major: spectra [n_cls][C * S][F], hops [n_cls][cap_out]
+    OnlineStatus* status = nullptr;
+    int* iters = nullptr;
+    // host state, per stream
+    std::vector<std::vector<T>> pending, hist;
+    std::vector<int64_t> l;
+    std::vector<uint8_t> finished;
+    std::vector<std::deque<snmf_online_frame>> trace;
+};
+
+// one stream's output hops of a process call
+template <typename T>
+struct OBatchSink {
+    std::vector<T> f, x, d;
+    std::vector<int16_t> i16;
+    std::vector<std::vector<T>> c;  // [n_cls] the class signals
+};
+
+template <class H>
+void obatch_free_chunk(H* o) {
+    obm_free_chunk(o);
+    void* ptrs[] = {o->sig, o->Ym, o->Xt, o->Xh, o->Dh, o->syn, o->outf, o->Yph, o->out16, o->status, o->iters, o->Xc, o->out_c};
+    for (void* q : ptrs)
+        if (q) hipFree(q);
+    o->sig = o->Ym = o->Xt = o->Xh = o->Dh = o->syn = o->outf = o->Xc = o->out_c = nullptr;
+    o->Yph = nullptr;
+    o->out16 = nullptr;
+    o->status = nullptr;
+    o->iters = nullptr;
+    o->C = 0;
+    o->cap_sig = o->cap_out = 0;
+}
+
+// chunk buffers for C frames per stream and the given signal / output sizes
+template <class H>
+int obatch_reserve(H* o, int C, size_t n_sig, size_t n_out) {
+    if (C <= o->C && n_sig <= o->cap_sig && n_out <= o->cap_out) return SNMF_OK;
+    hipStreamSynchronize(o->ctx->stream);
+    C = std::max(C, o->C);
+    n_sig = std::max(n_sig, o->cap_sig);
+    n_out = std::max(n_out, o->cap_out);
+    obatch_free_chunk(o);
+    const size_t slots = (size_t)C * o->S, F = o->F, sz = o->p.framelength;
+    SN_TRY(dalloc(&o->sig, n_sig));
+    SN_TRY(dalloc(&o->Ym, F * slots));
+    SN_TRY(dalloc(&o->Yph, F * slots));
+    SN_TRY(dalloc(&o->Xt, F * slots));
+    if (o->p.class_outputs) {
+        SN_TRY(dalloc(&o->Xh, F * slots));
+        SN_TRY(dalloc(&o->Dh, F * slots));
+    }
+    SN_TRY(dalloc(&o->syn, (size_t)o->S * (C + o->nov - 1) * sz));
+    SN_TRY(dalloc(&o->outf, 3 * std::max<size_t>(n_out, 1)));  // x_tilde | x_hat | d_hat
+    SN_TRY(dalloc(&o->out16, std::max<size_t>(n_out, 1)));
+    if (o->n_cls) {
+        SN_TRY(dalloc(&o->Xc, (size_t)o->n_cls * F * slots));
+        SN_TRY(dalloc(&o->out_c, (size_t)o->n_cls * std::max<size_t>(n_out, 1)));
+    }
+    SN_TRY(dalloc(&o->status, slots));
+    SN_TRY(dalloc(&o->iters, slots));
+    SN_TRY(obm_reserve(o, slots));
+    o->C = C;
+    o->cap_sig = n_sig;
+    o->cap_out = n_out;
+    return SNMF_OK;
+}
+
+// set_classes behind the mode's own checks: the class table `cls` (online_class_ranges) of event_num + noise_num classes
+template <class H>
+int obatch_install_classes(H* o, const std::vector<int>& cls, int event_num, int nc) {
+    using T = typename H::elem;
+    (void)hipGetLastError();  // clean sticky error state, see PLAN_CHECK
+    HIP_TRY(hipSetDevice(o->ctx->device));
+    hipStream_t st = o->ctx->stream;
+    HIP_TRY(hipStreamSynchronize(st));
+    obatch_free_chunk(o);  // the class-major chunk buffers depend on the class count
+    for (void** q : {(void**)&o->cls, (void**)&o->tail_c}) {
+        if (*q) hipFree(*q);
+        *q = nullptr;
+    }
+    o->n_ev = o->n_cls = 0;
+    const size_t nt = (size_t)nc * o->S * o->ntail;
+    SN_TRY(dalloc(&o->cls, cls.size()));
+    SN_TRY(dalloc(&o->tail_c, nt));
+    HIP_TRY(hipMemcpyAsync(o->cls, cls.data(), cls.size() * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(o->tail_c, 0, nt * sizeof(T), st));
+    HIP_TRY(hipStreamSynchronize(st));
+    o->n_ev = event_num;
+    o->n_cls = nc;
+    return SNMF_OK;
+}
+
+// a restart's argument checks: the listed slots are valid, distinct and not in the middle of a recording
+template <class H>
+int obatch_restart_check(const H* o, int32_t n, const int32_t* slots) {
+    if (n < 0 || n > o->S) return fail(SNMF_ERR_INVALID, "restart of %d streams in a batch of %d", n, o->S);
+    if (n > 0 && !slots) return fail(SNMF_ERR_INVALID, "slots is NULL");
+    std::vector<uint8_t> seen(o->S, 0);
+    for (int i = 0; i < n; ++i) {
+        const int s = slots[i];
+        if (s < 0 || s >= o->S) return fail(SNMF_ERR_INVALID, "stream %d out of range [0, %d)", s, o->S);
+        if (seen[s]) return fail(SNMF_ERR_INVALID, "stream %d listed twice", s);
+        seen[s] = 1;
+    }
+    if (o->failed) return fail(SNMF_ERR_STATE, "an earlier call failed midway through a chunk; the batch state is not reusable, create a new one");
+    for (int i = 0; i < n; ++i) {
+        const int s = slots[i];
+        if (!o->finished[s] && (o->l[s] > 0 || !o->pending[s].empty()))
+            return fail(SNMF_ERR_STATE, "stream %d is in the middle of a recording; flush it before a restart", s);
+    }
+    return SNMF_OK;
+}
+
+// the host state of streams that start a new recording (src/init_buff.m)
+template <class H>
+void obatch_restart_host(H* o, int n, const int32_t* slots) {
+    const int sz = o->p.framelength, hop = o->p.frameshift;
+    for (int i = 0; i < n; ++i) {
+        const int s = slots[i];
+        o->pending[s].clear();
+        o->hist[s].assign((size_t)(sz - hop), typename H::elem(0));
+        o->l[s] = 0;
+        o->finished[s] = 0;
+        o->trace[s].clear();
+    }
+}
+
+template <class H>
+int obatch_trace(const H* o, int32_t k, snmf_online_frame* out, int64_t cap, int64_t* n) {
+    if (k < 0 || k >= o->S) return fail(SNMF_ERR_INVALID, "stream %d out of range [0, %d)", k, o->S);
+    const auto& tr = o->trace[k];
+    if (n) *n = (int64_t)tr.size();
+    if (out && cap > 0) std::copy_n(tr.begin(), (size_t)std::min<int64_t>(cap, (int64_t)tr.size()), out);
+    return SNMF_OK;
+}
+
+// One device chunk: stream s runs nfr[s] frames (its next nreal[s] PCM frames, then nfr - nreal flush frames).  Appends
+// every stream's output hops and trace records.
+template <class H>
+int obatch_run_chunk(H* o, const std::vector<int>& nfr, const std::vector<int>& nreal, const std::vector<int64_t>& consumed, bool want_f,
+                     bool want_i16, bool want_cls, bool want_ci, std::vector<OBatchSink<typename H::elem>>& sink) {
+    using T = typename H::elem;
+    const snmf_online_params& p = o->p;
+    const int S = o->S, F = o->F, sz = p.framelength, hop = p.frameshift, nov = o->nov;
+    hipStream_t st = o->ctx->stream;
+    const int C = *std::max_element(nfr.begin(), nfr.end());
+    if (C == 0) return SNMF_OK;
+    // host framing: stream s's samples = [history | its hops of this chunk], then sz zeros for its flush frames
+    std::vector<int> mi(6 * (size_t)S, 0);
+    std::vector<int64_t> ml(3 * (size_t)S, 0);
+    int* h_nfr = mi.data(); int* h_nreal = h_nfr + S; int* h_l0 = h_nreal + S; int* h_if = h_l0 + S; int* h_no = h_if + S;
+    int64_t* h_off = ml.data(); int64_t* h_zoff = h_off + S; int64_t* h_oo = h_zoff + S;
+    size_t n_sig = 0, n_out = 0;
+    for (int s = 0; s < S; ++s) {
+        h_nfr[s] = nfr[s];
+        h_nreal[s] = nreal[s];
+        h_l0[s] = (int)std::min<int64_t>(o->l[s] + 1, 1 << 30);
+        h_if[s] = (int)std::max<int64_t>(0, (int64_t)p.delay + 1 - h_l0[s]);
+        h_no[s] = std::max(0, nfr[s] - h_if[s]);
+        h_off[s] = (int64_t)n_sig;
+        if (nreal[s] > 0) n_sig += (size_t)(sz - hop) + (size_t)nreal[s] * hop;
+        h_zoff[s] = (int64_t)n_sig;
+        if (nfr[s] > nreal[s]) n_sig += (size_t)sz;
+        h_oo[s] = (int64_t)n_out;
+        n_out += (size_t)h_no[s] * hop;
+    }
+    std::vector<T> sig(std::max<size_t>(n_sig, 1), T(0));
+    for (int s = 0; s < S; ++s) {
+        if (nreal[s] <= 0) continue;
+        T* d = sig.data() + h_off[s];
+        std::copy(o->hist[s].begin(), o->hist[s].end(), d);
+        std::copy(o->pending[s].begin() + consumed[s] * hop, o->pending[s].begin() + (consumed[s] + nreal[s]) * hop, d + (sz - hop));
+    }
+    SN_TRY(obatch_reserve(o, C, sig.size(), n_out));
+    HIP_TRY(hipMemcpyAsync(o->sig, sig.data(), sig.size() * sizeof(T), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(o->meta_i, mi.data(), mi.size() * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(o->meta_l, ml.data(), ml.size() * 8, hipMemcpyHostToDevice, st));
+    OBatchFrames fr{};
+    fr.nfr = o->meta_i; fr.nreal = o->meta_i + S; fr.l0 = o->meta_i + 2 * S; fr.off = o->meta_l; fr.zoff = o->meta_l + S; fr.S = S;
+    const int* d_if = o->meta_i + 3 * S;
+    const int* d_no = o->meta_i + 4 * S;
+    const int64_t* d_oo = o->meta_l + 2 * S;
+    SN_TRY(obm_begin_chunk(o, fr, C));  // STFT of every frame of the chunk; the post-filter's arguments for its launches below
+    HIP_TRY(hipMemsetAsync(o->iters, 0, (size_t)C * S * 4, st));
+    if (!p.adapt_train_N) {
+        // fixed dictionaries: every frame solve of the chunk in one launch, then one post-filter launch walks the frames
+        SN_TRY(obm_frame_solve(o, fr, -1, C));
+        SN_TRY(obm_post(o, fr, -1));
+        if (o->n_cls) SN_TRY(obm_class_spectra(o, fr, -1, C));
+    } else {
+        for (int i = 0; i < C; ++i) {  // one frame step of every stream, nothing decided on the host
+            SN_TRY(obm_frame_solve(o, fr, i, C));
+            SN_TRY(obm_post(o, fr, i));
+            if (o->n_cls) SN_TRY(obm_class_spectra(o, fr, i, C));
+            SN_TRY(obm_adapt(o, fr, i));
+        }
+    }
+    // inverse STFT behind each stream's kept frames, overlap-add
+    const int64_t syn_stride = (int64_t)(C + nov - 1) * sz;
+    auto synth = [&](const T* mag, T* tail, T* of, int16_t* o16) -> int {
+        if (nov > 1) SN_TRY(obm_tail(o, tail, fr, syn_stride, 0));
+        SN_TRY(obm_istft(o, mag, fr, C, syn_stride));
+        if (n_out > 0) {
+            const int gx = std::max(1, std::min(64, (int)((size_t)C * hop / 256 + 1)));
+            SN_TRY(obm_ola(o, gx, fr, syn_stride, d_if, d_no, d_oo, of, o16));
+        }
+        if (nov > 1) SN_TRY(obm_tail(o, tail, fr, syn_stride, 1));
+        return SNMF_OK;
+    };
+    // the three signals go to the thirds of outf: x_tilde, x_hat, d_hat
+    std::vector<T> hf, hx, hd;
+    std::vector<int16_t> h16;
+    auto fetch = [&](std::vector<T>& v, const T* src) -> int {
+        v.resize(n_out);
+        if (n_out) HIP_TRY(hipMemcpyAsync(v.data(), src, n_out * sizeof(T), hipMemcpyDeviceToHost, st));
+        return SNMF_OK;
+    };
+    SN_TRY(synth(o->Xt, o->tail, o->outf, want_i16 ? o->out16 : nullptr));
+    if (want_f) SN_TRY(fetch(hf, o->outf));
+    if (want_i16) {
+        h16.resize(n_out);
+        if (n_out) HIP_TRY(hipMemcpyAsync(h16.data(), o->out16, n_out * 2, hipMemcpyDeviceToHost, st));
+    }
+    if (p.class_outputs) {  // x_hat / d_hat of :350-361, same synthesis
+        SN_TRY(synth(o->Xh, o->tail_x, o->outf + n_out, nullptr));
+        SN_TRY(synth(o->Dh, o->tail_d, o->outf + 2 * n_out, nullptr));
+        if (want_cls) {
+            SN_TRY(fetch(hx, o->outf + n_out));
+            SN_TRY(fetch(hd, o->outf + 2 * n_out));
+        }
+    }
+    // x_hat_i / d_hat_i (:356-361): each class of the class-major stack through the same synthesis on its own tails
+    std::vector<std::vector<T>> hc(want_ci ? o->n_cls : 0);
+    for (int c = 0; c < o->n_cls; ++c) {
+        T* oc = o->out_c + (size_t)c * std::max<size_t>(o->cap_out, 1);
+        SN_TRY(synth(o->Xc + (size_t)c * o->C * S * F, o->tail_c + (size_t)c * S * o->ntail, oc, nullptr));
+        if (want_ci) SN_TRY(fetch(hc[c], oc));
+    }
+    // statuses + adaptation verdicts of the chunk: one copy each
+    std::vector<OnlineStatus> hs((size_t)C * S);
+    std::vector<int> hit((size_t)C * S);
+    HIP_TRY(hipMemcpyAsync(hs.data(), o->status, hs.size() * sizeof(OnlineStatus), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(hit.data(), o->iters, hit.size() * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int s = 0; s < S; ++s) {
+        for (int i = 0; i < nfr[s]; ++i) {
+            const OnlineStatus& q = hs[(size_t)i * S + s];
+            snmf_online_frame tr{};
+            tr.n_iter = q.n_iter; tr.trig = q.trig; tr.n_up = q.n_up; tr.beta = q.beta; tr.A_x_mag = q.A_x_mag; tr.A_d_mag = q.A_d_mag;
+            tr.Q_control = q.Q_control;
+            if (p.adapt_train_N && q.do_solve && q.n_up > 0) {
+                tr.solved = 1;
+                tr.adapt_iters = hit[(size_t)i * S + s];
+            }
+            o->trace[s].push_back(tr);
+            if (o->trace[s].size() > kBTraceCap) o->trace[s].pop_front();
+        }
+        const size_t a0 = (size_t)h_oo[s], n = (size_t)h_no[s] * hop;
+        if (want_f) sink[s].f.insert(sink[s].f.end(), hf.begin() + a0, hf.begin() + a0 + n);
+        if (want_i16) sink[s].i16.insert(sink[s].i16.end(), h16.begin() + a0, h16.begin() + a0 + n);
+        if (want_cls) {
+            sink[s].x.insert(sink[s].x.end(), hx.begin() + a0, hx.begin() + a0 + n);
+            sink[s].d.insert(sink[s].d.end(), hd.begin() + a0, hd.begin() + a0 + n);
+        }
+        if (want_ci) {
+            sink[s].c.resize(hc.size());
+            for (size_t c = 0; c < hc.size(); ++c) sink[s].c[c].insert(sink[s].c[c].end(), hc[c].begin() + a0, hc[c].begin() + a0 + n);
+        }
+        if (nreal[s] > 0) {  // history for the next chunk: the last sz - hop samples this stream framed
+            const T* end = sig.data() + h_off[s] + (sz - hop) + (size_t)nreal[s] * hop;
+            o->hist[s].assign(end - (sz - hop), end);
+        }
+        o->l[s] += nfr[s];
+    }
+    return SNMF_OK;
+}
+
+// snmf_online_batch_process_* / _process_classes_* behind the handle checks (xhi / dhi: the class signals, class-major at cap[s])
+template <class H, typename T = typename H::elem>
+int obatch_process(H* o, const T* const* pcm, const int64_t* n, const int32_t* flush, T* const* xt, int16_t* const* xt_i16, T* const* xh,
+                   T* const* dh, T* const* xhi, T* const* dhi, const int64_t* cap, int64_t* n_out) {
+    if (!n || !pcm) return fail(SNMF_ERR_INVALID, "pcm / n is NULL");
+    const int S = o->S;
+    const snmf_online_params& p = o->p;
+    const int hop = p.frameshift;
+    if (n_out)
+        for (int s = 0; s < S; ++s) n_out[s] = 0;
+    if (o->failed) return fail(SNMF_ERR_STATE, "an earlier call failed midway through a chunk; the batch state is not reusable, create a new one");
+    if ((xh || dh || xhi || dhi) && !p.class_outputs) return fail(SNMF_ERR_STATE, "class outputs were not requested at creation");
+    const bool any_out = xt || xt_i16 || xh || dh || xhi || dhi;
+    if (any_out && !cap) return fail(SNMF_ERR_INVALID, "cap is NULL");
+    std::vector<int64_t> nfr_tot(S), tail(S);
+    for (int s = 0; s < S; ++s) {
+        if (n[s] < 0 || (n[s] > 0 && !pcm[s])) return fail(SNMF_ERR_INVALID, "stream %d: pcm is NULL", s);
+        if (o->finished[s] && (n[s] > 0 || (flush && flush[s])))
+            return fail(SNMF_ERR_STATE, "stream %d was flushed; restart it before feeding it", s);
+        nfr_tot[s] = ((int64_t)o->pending[s].size() + n[s]) / hop;
+        tail[s] = (flush && flush[s] && !o->finished[s]) ? p.delay + 1 : 0;
+        const int64_t need = (nfr_tot[s] + tail[s]) * hop;
+        auto short_cap = [&](const void* const* v) { return v && v[s] && cap[s] < need; };
+        if (short_cap((const void* const*)xt) || short_cap((const void* const*)xt_i16) || short_cap((const void* const*)xh) ||
+            short_cap((const void* const*)dh) || short_cap((const void* const*)xhi) || short_cap((const void* const*)dhi))
+            return fail(SNMF_ERR_INVALID, "stream %d: output capacity %lld < %lld samples", s, (long long)cap[s], (long long)need);
+    }
+    o->started = true;
+    (void)hipGetLastError();  // clean sticky error state, see PLAN_CHECK
+    HIP_TRY(hipSetDevice(o->ctx->device));
+    for (int s = 0; s < S; ++s)
+        if (n[s] > 0) o->pending[s].insert(o->pending[s].end(), pcm[s], pcm[s] + n[s]);
+    // chunks: up to C frames per stream, each stream's PCM frames first, then its flush frames
+    const int C = obm_chunk_frames(o);
+    std::vector<int64_t> done(S, 0);
+    std::vector<OBatchSink<T>> sink(S);
+    // class signals: with a partition set they come from the class kernel; without one x_hat / d_hat are the one class per side
+    const bool cls_set = o->n_cls > 0, wci = cls_set && (xhi || dhi);
+    const bool wf = xt != nullptr, wi = xt_i16 != nullptr, wc = xh || dh || (!cls_set && (xhi || dhi));
+    for (;;) {
+        std::vector<int> nfr(S), nreal(S);
+        bool any = false;
+        for (int s = 0; s < S; ++s) {
+            const int64_t left = nfr_tot[s] + tail[s] - done[s];
+            nfr[s] = (int)std::min<int64_t>(C, left);
+            nreal[s] = (int)std::max<int64_t>(0, std::min<int64_t>(nfr[s], nfr_tot[s] - done[s]));
+            any |= nfr[s] > 0;
+        }
+        if (!any) break;
+        if (int rc = obatch_run_chunk(o, nfr, nreal, done, wf, wi, wc, wci, sink)) {
+            o->failed = true;  // frames of this call were consumed and the device state advanced: never retry on it
+            return rc;
+        }
+        for (int s = 0; s < S; ++s) done[s] += nfr[s];
+    }
+    for (int s = 0; s < S; ++s) {
+        o->pending[s].erase(o->pending[s].begin(), o->pending[s].begin() + nfr_tot[s] * hop);
+        if (tail[s]) {
+            o->pending[s].clear();  // a partial hop is dropped (src/NTF_sep_event_RT.m:69-76)
+            o->finished[s] = 1;
+        }
+        const OBatchSink<T>& k = sink[s];
+        if (wf && xt[s]) std::memcpy(xt[s], k.f.data(), k.f.size() * sizeof(T));
+        if (wi && xt_i16[s]) std::memcpy(xt_i16[s], k.i16.data(), k.i16.size() * 2);
+        if (xh && xh[s]) std::memcpy(xh[s], k.x.data(), k.x.size() * sizeof(T));
+        if (dh && dh[s]) std::memcpy(dh[s], k.d.data(), k.d.size() * sizeof(T));
+        size_t nc_out = 0;
+        if (cls_set) {
+            for (int c = 0; c < (int)k.c.size(); ++c) {
+                T* dst = c < o->n_ev ? ((xhi && xhi[s]) ? xhi[s] + (size_t)c * cap[s] : nullptr)
+                                     : ((dhi && dhi[s]) ? dhi[s] + (size_t)(c - o->n_ev) * cap[s] : nullptr);
+                if (dst) std::memcpy(dst, k.c[c].data(), k.c[c].size() * sizeof(T));
+                nc_out = std::max(nc_out, k.c[c].size());
+            }
+        } else {
+            if (xhi && xhi[s]) std::memcpy(xhi[s], k.x.data(), k.x.size() * sizeof(T));
+            if (dhi && dhi[s]) std::memcpy(dhi[s], k.d.data(), k.d.size() * sizeof(T));
+        }
+        if (n_out) n_out[s] = (int64_t)std::max(std::max(std::max(k.f.size(), k.i16.size()), std::max(k.x.size(), k.d.size())), nc_out);
+    }
+    return SNMF_OK;
+}

@@ -1,36 +1,24 @@
 // snmf_tu_online_batch.hip -- the batched online separator behind the C ABI (snmf_online_batch_*), kernels in
 // snmf_online_batch.h.  A translation unit of its own, so that the single-stream kernels' code does not move.
+// The host driver (hop queues, chunk loop, framing, synthesis, trace) is snmf_online_batch_host.h, shared with the fp64 mode;
+// here are the handle, its creation / Mel conversion / restart, and the fp32 steps the driver calls (obm_*).
 #include "snmf_internal.h"
 #include "snmf_online_batch.h"
 #include "snmf_online_batch_f64_host.h"  // the fp64 mode's host entry points (its kernels live in snmf_tu_online_batch_f64.hip)
+#include "snmf_online_batch_host.h"
 #include "snmf_online_classes.h"
 
-// Host side: per stream, the hop queue / history / flush logic of snmf_online_process_f32 (snmf_tu_online.hip); on the
-// device, one fixed sequence of launches per frame step for all streams (frame solve, post-filter, gated adaptation,
-// gated re-assembly + dictionary refresh) -- with the dictionary fixed, one launch of each for the whole chunk.  A
-// chunk synchronises ONCE: outputs, statuses and adaptation verdicts are copied back together at its end.
-namespace {
-constexpr size_t kBTraceCap = 1u << 16;   // per stream: the newest 65536 frames, as snmf_online_trace
-constexpr int64_t kBChunkSlots = 16384;  // (frame, stream) slots of one device chunk
-}
-
-struct snmf_online_batch {
-    snmf_ctx* ctx = nullptr;
-    OnlineBatchF64* f64 = nullptr;  // non-null: an fp64 batch (snmf_online_batch_create_f64); every field below S is then unused
-    snmf_online_params p{};
-    int S = 0, F = 0, r = 0, N = 0, nov = 0, Ra = 1, ma = 1, Pl = 1, RA2 = 64;
+struct snmf_online_batch : OBatchState<float> {
+    OnlineBatchF64* f64 = nullptr;  // non-null: an fp64 batch (snmf_online_batch_create_f64); only ctx, p, S and F are then used
+    int RA2 = 64;
     int Fs = 0;                                // rows of the solves: F, or F_order in Mel mode
     int mel = 0, mel_conv = 0, n1 = 0;         // B_sep_mode = 'Mel' (snmf_online_batch_set_mel)
-    bool started = false;                      // a process call was made (set_mel must come first)
     snmf_plan* hp = nullptr;  // the frame solve's geometry, sparsity and beta (one plan serves every stream)
     // per stream, device
     double *B = nullptr, *Bfix = nullptr, *Btmp = nullptr, *wn = nullptr, *Wu = nullptr;
     float *Wcf = nullptr, *wx = nullptr, *dphv = nullptr, *Hin = nullptr, *H0 = nullptr, *Ad0 = nullptr;
     float *lambda_dav = nullptr, *Xm_tilde = nullptr, *r_blk = nullptr, *ldblk = nullptr, *adblk = nullptr;
     float *G = nullptr, *P = nullptr, *Vt = nullptr;
-    float *tail = nullptr, *tail_x = nullptr, *tail_d = nullptr;
-    uint8_t* rup = nullptr;
-    OnlineDev* dev = nullptr;
     float *win_s = nullptr, *win_i = nullptr;
     float2* tw = nullptr;
     double* Bxd = nullptr;  // B_DFT_x in fp64, shared
@@ -39,52 +27,41 @@ struct snmf_online_batch {
     float *melmat = nullptr, *Vm = nullptr, *Bdf = nullptr;
     double *Bmx = nullptr, *Bm = nullptr, *rs_Bm = nullptr;
     // restart uploads (sized for all S streams)
-    int* rs_slots = nullptr;
     double* rs_B = nullptr;
     float *rs_H = nullptr, *rs_A = nullptr;
-    size_t ntail = 0;
-    // per chunk, device (grown on demand)
-    int C = 0;  // frames per stream per chunk
-    size_t cap_sig = 0, cap_out = 0;
-    float *sig = nullptr, *Ym = nullptr, *Vp = nullptr, *Hout = nullptr, *reco = nullptr, *Xt = nullptr, *Xh = nullptr, *Dh = nullptr;
-    float *syn = nullptr, *outf = nullptr, *Ymel = nullptr;
-    float2* Yph = nullptr;
-    int16_t* out16 = nullptr;
+    // per chunk, device (obm_reserve): the solve's input, Mel features, activations, reconstructions (Fs rows), state and histories
+    float *Vp = nullptr, *Ymel = nullptr, *Hout = nullptr, *reco = nullptr;
     DevState* st = nullptr;
     double *divh = nullptr, *costh = nullptr;
-    OnlineStatus* status = nullptr;
-    int* iters = nullptr;
-    // per-class outputs (snmf_online_batch_set_classes): n_ev event classes then n_cls - n_ev noise classes; n_cls = 0: none set
-    int n_ev = 0, n_cls = 0;
-    int* cls = nullptr;           // [n_cls + 1] column ranges over [B_x | B_d] (snmf_online_classes.h)
-    float* tail_c = nullptr;      // [n_cls][S][ntail] one overlap-add tail per class and stream
-    float *Xc = nullptr, *out_c = nullptr;  // per chunk, class-major: spectra [n_cls][C * S][F], hops [n_cls][cap_out]
-    int* meta_i = nullptr;        // [6][S] nfr, nreal, l0, i_first, n_out, (pad)
-    int64_t* meta_l = nullptr;    // [3][S] off, zoff, out_off
-    // host state, per stream
-    std::vector<std::vector<float>> pending, hist;
-    std::vector<int64_t> l;
-    std::vector<uint8_t> finished;
-    std::vector<std::deque<snmf_online_frame>> trace;
-    bool failed = false;
+    // the post-filter's launch arguments of the current chunk (ob_post_args)
+    OPostArgs post_a{};
+    OBatchPost post_bp{};
+    size_t post_lds = 0;
 };
 
-static void ob_free_chunk(snmf_online_batch* o) {
-    void* ptrs[] = {o->sig, o->Ym, o->Vp, o->Hout, o->reco, o->Xt, o->Xh, o->Dh, o->syn, o->outf, o->Yph, o->out16,
-                    o->st, o->divh, o->costh, o->status, o->iters, o->Ymel, o->Xc, o->out_c};
+static void obm_free_chunk(snmf_online_batch* o) {
+    void* ptrs[] = {o->Vp, o->Ymel, o->Hout, o->reco, o->st, o->divh, o->costh};
     for (void* q : ptrs)
         if (q) hipFree(q);
-    o->Xc = o->out_c = nullptr;
-    o->sig = o->Ym = o->Vp = o->Hout = o->reco = o->Xt = o->Xh = o->Dh = o->syn = o->outf = o->Ymel = nullptr;
-    o->Yph = nullptr;
-    o->out16 = nullptr;
+    o->Vp = o->Ymel = o->Hout = o->reco = nullptr;
     o->st = nullptr;
     o->divh = o->costh = nullptr;
-    o->status = nullptr;
-    o->iters = nullptr;
-    o->C = 0;
-    o->cap_sig = o->cap_out = 0;
 }
+
+static int obm_reserve(snmf_online_batch* o, size_t slots) {
+    const snmf_plan* pl = o->hp;
+    SN_TRY(dalloc(&o->Vp, (size_t)pl->Fp * slots));
+    if (o->mel) SN_TRY(dalloc(&o->Ymel, (size_t)o->n1 * slots));
+    SN_TRY(dalloc(&o->Hout, (size_t)pl->rp * slots));
+    SN_TRY(dalloc(&o->reco, 2 * (size_t)o->Fs * slots));
+    SN_TRY(dalloc(&o->st, slots));
+    SN_TRY(dalloc(&o->divh, slots * o->p.max_iter));
+    SN_TRY(dalloc(&o->costh, slots * o->p.max_iter));
+    return SNMF_OK;
+}
+
+// as inherited: the slots bound the per-slot solve buffers; the class count does not enter, though Xc grows with it
+static int obm_chunk_frames(const snmf_online_batch* o) { return (int)std::max<int64_t>(1, std::min<int64_t>(4096, kBChunkSlots / o->S)); }
 
 extern "C" void snmf_online_batch_destroy(snmf_online_batch* o) {
     if (!o) return;
@@ -96,7 +73,7 @@ extern "C" void snmf_online_batch_destroy(snmf_online_batch* o) {
     hipSetDevice(o->ctx->device);
     hipStreamSynchronize(o->ctx->stream);
     if (o->hp) snmf_plan_destroy(o->hp);
-    ob_free_chunk(o);
+    obatch_free_chunk(o);
     void* ptrs[] = {o->B, o->Bfix, o->Btmp, o->wn, o->Wu, o->Wcf, o->wx, o->dphv, o->Hin, o->H0, o->Ad0, o->lambda_dav, o->Xm_tilde,
                     o->r_blk, o->ldblk, o->adblk, o->G, o->P, o->Vt, o->tail, o->tail_x, o->tail_d, o->rup, o->dev, o->win_s,
                     o->win_i, o->tw, o->Bxd, o->rs_slots, o->rs_B, o->rs_H, o->rs_A, o->meta_i, o->meta_l, o->melmat, o->Vm, o->Bdf,
@@ -169,15 +146,7 @@ static int ob_restart(snmf_online_batch* o, int n, const int32_t* slots, const d
     ra.xr = o->Fs > 64 * o->hp->frame_fb; ra.k0 = 0;
     hipLaunchKernelGGL(k_obrefresh, dim3(o->r, n), dim3(256), 0, st, ra);
     HIP_TRY(hipGetLastError());
-    const int sz = p.framelength, hop = p.frameshift;
-    for (int i = 0; i < n; ++i) {
-        const int s = slots[i];
-        o->pending[s].clear();
-        o->hist[s].assign((size_t)(sz - hop), 0.f);
-        o->l[s] = 0;
-        o->finished[s] = 0;
-        o->trace[s].clear();
-    }
+    obatch_restart_host(o, n, slots);
     return SNMF_OK;
 }
 
@@ -312,7 +281,7 @@ extern "C" int snmf_online_batch_set_mel(snmf_online_batch* o, int32_t F_order, 
     o->failed = true;
     snmf_plan_destroy(o->hp);
     o->hp = hp;
-    ob_free_chunk(o);  // Vp / Ymel / reco depend on the solve's rows
+    obatch_free_chunk(o);  // Vp / Ymel / reco depend on the solve's rows
     for (void** q : {(void**)&o->Wcf, (void**)&o->melmat, (void**)&o->Vm, (void**)&o->Bdf, (void**)&o->Bmx, (void**)&o->Bm, (void**)&o->rs_Bm}) {
         if (*q) hipFree(*q);
         *q = nullptr;
@@ -355,71 +324,15 @@ extern "C" int snmf_online_batch_set_classes(snmf_online_batch* o, int32_t event
     const int nc = event_num + noise_num;
     if (o->mel && o->mel_conv && (size_t)nc * o->n1 * 4 > o->ctx->lds_max)
         return fail(SNMF_ERR_UNSUPPORTED, "MelConv = 1 with %d classes at F_order = %d: the class kernel's Mel products do not fit the LDS", nc, o->n1);
-    (void)hipGetLastError();  // clean sticky error state, see PLAN_CHECK
-    HIP_TRY(hipSetDevice(o->ctx->device));
-    hipStream_t st = o->ctx->stream;
-    HIP_TRY(hipStreamSynchronize(st));
-    ob_free_chunk(o);  // the class-major chunk buffers depend on the class count
-    for (void** q : {(void**)&o->cls, (void**)&o->tail_c}) {
-        if (*q) hipFree(*q);
-        *q = nullptr;
-    }
-    o->n_ev = o->n_cls = 0;
-    const size_t nt = (size_t)nc * o->S * o->ntail;
-    SN_TRY(dalloc(&o->cls, cls.size()));
-    SN_TRY(dalloc(&o->tail_c, nt));
-    HIP_TRY(hipMemcpyAsync(o->cls, cls.data(), cls.size() * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(o->tail_c, 0, nt * 4, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    o->n_ev = event_num;
-    o->n_cls = nc;
-    return SNMF_OK;
+    return obatch_install_classes(o, cls, event_num, nc);
 }
 
-// chunk buffers for C frames per stream and the given signal / output sizes
-static int ob_reserve(snmf_online_batch* o, int C, size_t n_sig, size_t n_out) {
-    if (C <= o->C && n_sig <= o->cap_sig && n_out <= o->cap_out) return SNMF_OK;
-    hipStreamSynchronize(o->ctx->stream);
-    C = std::max(C, o->C);
-    n_sig = std::max(n_sig, o->cap_sig);
-    n_out = std::max(n_out, o->cap_out);
-    ob_free_chunk(o);
-    const size_t slots = (size_t)C * o->S, F = o->F, sz = o->p.framelength;
-    const snmf_plan* pl = o->hp;
-    SN_TRY(dalloc(&o->sig, n_sig));
-    SN_TRY(dalloc(&o->Ym, F * slots));
-    SN_TRY(dalloc(&o->Yph, F * slots));
-    SN_TRY(dalloc(&o->Vp, (size_t)pl->Fp * slots));
-    if (o->mel) SN_TRY(dalloc(&o->Ymel, (size_t)o->n1 * slots));
-    SN_TRY(dalloc(&o->Hout, (size_t)pl->rp * slots));
-    SN_TRY(dalloc(&o->reco, 2 * (size_t)o->Fs * slots));
-    SN_TRY(dalloc(&o->Xt, F * slots));
-    if (o->p.class_outputs) {
-        SN_TRY(dalloc(&o->Xh, F * slots));
-        SN_TRY(dalloc(&o->Dh, F * slots));
-    }
-    SN_TRY(dalloc(&o->syn, (size_t)o->S * (C + o->nov - 1) * sz));
-    SN_TRY(dalloc(&o->outf, 3 * std::max<size_t>(n_out, 1)));  // x_tilde | x_hat | d_hat
-    SN_TRY(dalloc(&o->out16, std::max<size_t>(n_out, 1)));
-    if (o->n_cls) {
-        SN_TRY(dalloc(&o->Xc, (size_t)o->n_cls * F * slots));
-        SN_TRY(dalloc(&o->out_c, (size_t)o->n_cls * std::max<size_t>(n_out, 1)));
-    }
-    SN_TRY(dalloc(&o->st, slots));
-    SN_TRY(dalloc(&o->divh, slots * o->p.max_iter));
-    SN_TRY(dalloc(&o->costh, slots * o->p.max_iter));
-    SN_TRY(dalloc(&o->status, slots));
-    SN_TRY(dalloc(&o->iters, slots));
-    o->C = C;
-    o->cap_sig = n_sig;
-    o->cap_out = n_out;
-    return SNMF_OK;
-}
-
-// the frame solves of `nf` frames per stream (slots [step * S, (step + nf) * S)), one workgroup per (frame, stream)
-static int ob_frame_solve(snmf_online_batch* o, int step, int nf) {
+// the frame solves of frame `step` of every stream (step < 0: all C frames of the chunk; slots [first * S, (first + nf) * S)),
+// one workgroup per (frame, stream)
+static int obm_frame_solve(snmf_online_batch* o, const OBatchFrames&, int step, int C) {
     snmf_plan* pl = o->hp;
-    const size_t off = (size_t)step * o->S;
+    const int first = step < 0 ? 0 : step, nf = step < 0 ? C : 1;
+    const size_t off = (size_t)first * o->S;
     StepArgs a = make_args(pl);
     a.V = o->Vp + off * pl->Fp;
     a.Hin = o->Hin;
@@ -466,7 +379,7 @@ static int ob_frame_solve(snmf_online_batch* o, int step, int nf) {
 
 // the class spectra (:158-202) of frame `step` of every stream (step < 0: all C frames of the chunk): behind the frame solves,
 // before the adaptation replaces the dictionaries (k_obclass)
-static int ob_class_spectra(snmf_online_batch* o, const OBatchFrames& fr, int step, int C) {
+static int obm_class_spectra(snmf_online_batch* o, const OBatchFrames& fr, int step, int C) {
     const bool mc = o->mel && o->mel_conv;
     OBatchClassArgs c{};
     c.B = mc ? o->Bm : o->B; c.A = o->Hout; c.cls = o->cls; c.melmat = o->melmat; c.out = o->Xc;
@@ -479,7 +392,7 @@ static int ob_class_spectra(snmf_online_batch* o, const OBatchFrames& fr, int st
 }
 
 // adaptation (gated on the device) + re-assembly + dictionary refresh after frame `step` of every stream
-static int ob_adapt(snmf_online_batch* o, const OBatchFrames& fr, int step) {
+static int obm_adapt(snmf_online_batch* o, const OBatchFrames& fr, int step) {
     const snmf_online_params& p = o->p;
     hipStream_t st = o->ctx->stream;
     snmf_plan* pl = o->hp;
@@ -522,64 +435,20 @@ static int ob_adapt(snmf_online_batch* o, const OBatchFrames& fr, int step) {
     return SNMF_OK;
 }
 
-// One device chunk: stream s runs nfr[s] frames (its next nreal[s] PCM frames, then nfr - nreal flush frames).  Appends
-// every stream's output hops and trace records.
-struct ObSink {
-    std::vector<float> f, x, d;
-    std::vector<int16_t> i16;
-    std::vector<std::vector<float>> c;  // [n_cls] the class signals
-};
-static int ob_run_chunk(snmf_online_batch* o, const std::vector<int>& nfr, const std::vector<int>& nreal,
-                        const std::vector<int64_t>& consumed, bool want_f, bool want_i16, bool want_cls, bool want_ci,
-                        std::vector<ObSink>& sink) {
+static void ob_post_args(snmf_online_batch* o);
+
+// STFT of every frame of the chunk (in Mel mode the solve input is the Mel features, :106-120), and the chunk's post-filter arguments
+static int obm_begin_chunk(snmf_online_batch* o, const OBatchFrames& fr, int C) {
     const snmf_online_params& p = o->p;
-    const int S = o->S, F = o->F, sz = p.framelength, hop = p.frameshift, nov = o->nov;
+    const int S = o->S, F = o->F;
     hipStream_t st = o->ctx->stream;
-    const int C = *std::max_element(nfr.begin(), nfr.end());
-    if (C == 0) return SNMF_OK;
-    // host framing: stream s's samples = [history | its hops of this chunk], then sz zeros for its flush frames
-    std::vector<int> mi(6 * (size_t)S, 0);
-    std::vector<int64_t> ml(3 * (size_t)S, 0);
-    int* h_nfr = mi.data(); int* h_nreal = h_nfr + S; int* h_l0 = h_nreal + S; int* h_if = h_l0 + S; int* h_no = h_if + S;
-    int64_t* h_off = ml.data(); int64_t* h_zoff = h_off + S; int64_t* h_oo = h_zoff + S;
-    size_t n_sig = 0, n_out = 0;
-    for (int s = 0; s < S; ++s) {
-        h_nfr[s] = nfr[s];
-        h_nreal[s] = nreal[s];
-        h_l0[s] = (int)std::min<int64_t>(o->l[s] + 1, 1 << 30);
-        h_if[s] = (int)std::max<int64_t>(0, (int64_t)p.delay + 1 - h_l0[s]);
-        h_no[s] = std::max(0, nfr[s] - h_if[s]);
-        h_off[s] = (int64_t)n_sig;
-        if (nreal[s] > 0) n_sig += (size_t)(sz - hop) + (size_t)nreal[s] * hop;
-        h_zoff[s] = (int64_t)n_sig;
-        if (nfr[s] > nreal[s]) n_sig += (size_t)sz;
-        h_oo[s] = (int64_t)n_out;
-        n_out += (size_t)h_no[s] * hop;
-    }
-    std::vector<float> sig(std::max<size_t>(n_sig, 1), 0.f);
-    for (int s = 0; s < S; ++s) {
-        if (nreal[s] <= 0) continue;
-        float* d = sig.data() + h_off[s];
-        std::copy(o->hist[s].begin(), o->hist[s].end(), d);
-        std::copy(o->pending[s].begin() + consumed[s] * hop, o->pending[s].begin() + (consumed[s] + nreal[s]) * hop, d + (sz - hop));
-    }
-    SN_TRY(ob_reserve(o, C, sig.size(), n_out));
-    HIP_TRY(hipMemcpyAsync(o->sig, sig.data(), sig.size() * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(o->meta_i, mi.data(), mi.size() * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(o->meta_l, ml.data(), ml.size() * 8, hipMemcpyHostToDevice, st));
-    OBatchFrames fr{};
-    fr.nfr = o->meta_i; fr.nreal = o->meta_i + S; fr.l0 = o->meta_i + 2 * S; fr.off = o->meta_l; fr.zoff = o->meta_l + S; fr.S = S;
-    const int* d_if = o->meta_i + 3 * S;
-    const int* d_no = o->meta_i + 4 * S;
-    const int64_t* d_oo = o->meta_l + 2 * S;
-    // STFT of every frame of the chunk
     OStftArgs sa{};
-    sa.sig = o->sig; sa.sz = sz; sa.hop = hop; sa.dcbin = p.dcbin; sa.preemph = (float)p.preemph; sa.win = o->win_s; sa.tw = o->tw;
-    sa.powv = (float)p.pow; sa.floorv = (float)p.nonzerofloor; sa.Ym = o->Ym; sa.Yph = o->Yph; sa.ld = F; sa.n_frames = C;
+    sa.sig = o->sig; sa.sz = p.framelength; sa.hop = p.frameshift; sa.dcbin = p.dcbin; sa.preemph = (float)p.preemph; sa.win = o->win_s;
+    sa.tw = o->tw; sa.powv = (float)p.pow; sa.floorv = (float)p.nonzerofloor; sa.Ym = o->Ym; sa.Yph = o->Yph; sa.ld = F; sa.n_frames = C;
     if (!o->mel) {
         by_logn([&](auto L) { hipLaunchKernelGGL(k_obstft<decltype(L)::value>, dim3(C, S), dim3(256), 0, st, sa, fr, o->Vp, o->hp->Fp); }, o->N);
         HIP_TRY(hipGetLastError());
-    } else {  // the solve input is the Mel features (:106-120)
+    } else {
         by_logn([&](auto L) { hipLaunchKernelGGL((k_obstft<decltype(L)::value, false>), dim3(C, S), dim3(256), 0, st, sa, fr, o->Vp, o->hp->Fp); },
                    o->N);
         HIP_TRY(hipGetLastError());
@@ -587,8 +456,15 @@ static int ob_run_chunk(snmf_online_batch* o, const std::vector<int>& nfr, const
                            o->n1, o->Ymel, o->Vp, o->hp->Fp);
         HIP_TRY(hipGetLastError());
     }
-    // post-filter arguments (stream 0's pointers; k_obpost re-bases them)
-    OPostArgs a{};
+    ob_post_args(o);
+    return SNMF_OK;
+}
+
+// post-filter arguments of a chunk (stream 0's pointers; k_obpost re-bases them)
+static void ob_post_args(snmf_online_batch* o) {
+    const snmf_online_params& p = o->p;
+    const int F = o->F;
+    OPostArgs& a = o->post_a;
     a.A = o->Hout; a.hst = o->st; a.B = nullptr; a.recon = o->reco; a.Ym = o->Ym; a.lambda_dav = o->lambda_dav; a.Xm_tilde = o->Xm_tilde;
     a.r_blk = o->r_blk; a.ldblk = o->ldblk; a.adblk = o->adblk; a.rup = o->rup; a.dev = o->dev; a.status = o->status;
     a.Xt_out = o->Xt; a.Xh_out = o->Xh; a.Dh_out = o->Dh;
@@ -599,122 +475,51 @@ static int ob_run_chunk(snmf_online_batch* o, const std::vector<int>& nfr, const
     a.beta_max = (float)p.beta_max; a.Ar_up = (float)p.Ar_up; a.flr = (float)p.nonzerofloor;
     a.mel = o->mel; a.mel_conv = o->mel_conv; a.n1 = o->n1; a.melmat = o->melmat; a.Ymel = o->mel ? o->Ymel : nullptr; a.Bmf = nullptr;
     a.recon_len = o->Fs; a.n = 1; a.a_stride = 0;
-    OBatchPost bp{};
-    bp.fr = fr; bp.rp = o->hp->rp; bp.sB = 0;
+    OBatchPost& bp = o->post_bp;
+    bp.rp = o->hp->rp; bp.sB = 0;
     if (o->mel && !o->mel_conv) {  // coupled dictionaries: the Mel activations on the stream's DFT bases (:158-202)
         a.recon = nullptr;
         a.B = o->Bdf;
         bp.sB = (int64_t)o->r * F;
     }
-    const size_t lds_post = (size_t)(o->r + 7 * F + 3 * o->n1) * 4;
-    HIP_TRY(hipMemsetAsync(o->iters, 0, (size_t)C * S * 4, st));
-    if (!p.adapt_train_N) {
-        // fixed dictionaries: every frame solve of the chunk in one launch, then one post-filter launch (snmf_tu_online.hip)
-        SN_TRY(ob_frame_solve(o, 0, C));
-        bp.step = -1;
-        hipLaunchKernelGGL(k_obpost, dim3(S), dim3(1024), lds_post, st, a, bp);
-        HIP_TRY(hipGetLastError());
-        if (o->n_cls) SN_TRY(ob_class_spectra(o, fr, -1, C));
-    } else {
-        for (int i = 0; i < C; ++i) {  // one frame step of every stream: four launches, nothing decided on the host
-            SN_TRY(ob_frame_solve(o, i, 1));
-            bp.step = i;
-            hipLaunchKernelGGL(k_obpost, dim3(S), dim3(1024), lds_post, st, a, bp);
-            HIP_TRY(hipGetLastError());
-            if (o->n_cls) SN_TRY(ob_class_spectra(o, fr, i, 1));
-            SN_TRY(ob_adapt(o, fr, i));
-        }
-    }
-    // inverse STFT behind each stream's kept frames, overlap-add
-    const int64_t syn_stride = (int64_t)(C + nov - 1) * sz;
-    auto synth = [&](const float* mag, float* tail, float* of, int16_t* o16) -> int {
-        if (nov > 1) {
-            hipLaunchKernelGGL(k_obtail, dim3(S), dim3(256), 0, st, o->syn, tail, fr.nfr, syn_stride, nov, sz, 0);
-            HIP_TRY(hipGetLastError());
-        }
-        OIstftArgs ia{};
-        ia.mag = mag; ia.ph = o->Yph; ia.ld = F; ia.n_frames = C; ia.sz = sz; ia.dcb = p.dcbin_back; ia.powv = (float)p.pow;
-        ia.scale = (float)(p.overlapscale / (double)o->N); ia.preemph = (float)p.preemph; ia.win = o->win_i; ia.tw = o->tw; ia.syn = o->syn;
-        by_logn([&](auto L) { hipLaunchKernelGGL(k_obistft<decltype(L)::value>, dim3(C, S), dim3(256), 0, st, ia, fr.nfr, S, syn_stride, nov); },
-                   o->N);
-        HIP_TRY(hipGetLastError());
-        if (n_out > 0) {
-            const int gx = std::max(1, std::min(64, (int)((size_t)C * hop / 256 + 1)));
-            hipLaunchKernelGGL(k_obola, dim3(gx, S), dim3(256), 0, st, (const float*)o->syn, syn_stride, fr, d_if, d_no, d_oo, p.delay, sz, hop,
-                               nov, of, o16);
-            HIP_TRY(hipGetLastError());
-        }
-        if (nov > 1) {
-            hipLaunchKernelGGL(k_obtail, dim3(S), dim3(256), 0, st, o->syn, tail, fr.nfr, syn_stride, nov, sz, 1);
-            HIP_TRY(hipGetLastError());
-        }
-        return SNMF_OK;
-    };
-    // the three signals go to the thirds of outf: x_tilde, x_hat, d_hat
-    std::vector<float> hf, hx, hd;
-    std::vector<int16_t> h16;
-    auto fetch = [&](std::vector<float>& v, const float* src) -> int {
-        v.resize(n_out);
-        if (n_out) HIP_TRY(hipMemcpyAsync(v.data(), src, n_out * 4, hipMemcpyDeviceToHost, st));
-        return SNMF_OK;
-    };
-    SN_TRY(synth(o->Xt, o->tail, o->outf, want_i16 ? o->out16 : nullptr));
-    if (want_f) SN_TRY(fetch(hf, o->outf));
-    if (want_i16) {
-        h16.resize(n_out);
-        if (n_out) HIP_TRY(hipMemcpyAsync(h16.data(), o->out16, n_out * 2, hipMemcpyDeviceToHost, st));
-    }
-    if (p.class_outputs) {  // x_hat / d_hat of :350-361, same synthesis
-        SN_TRY(synth(o->Xh, o->tail_x, o->outf + n_out, nullptr));
-        SN_TRY(synth(o->Dh, o->tail_d, o->outf + 2 * n_out, nullptr));
-        if (want_cls) {
-            SN_TRY(fetch(hx, o->outf + n_out));
-            SN_TRY(fetch(hd, o->outf + 2 * n_out));
-        }
-    }
-    // x_hat_i / d_hat_i (:356-361): each class of the class-major stack through the same synthesis on its own tails
-    std::vector<std::vector<float>> hc(want_ci ? o->n_cls : 0);
-    for (int c = 0; c < o->n_cls; ++c) {
-        float* oc = o->out_c + (size_t)c * std::max<size_t>(o->cap_out, 1);
-        SN_TRY(synth(o->Xc + (size_t)c * o->C * S * F, o->tail_c + (size_t)c * S * o->ntail, oc, nullptr));
-        if (want_ci) SN_TRY(fetch(hc[c], oc));
-    }
-    // statuses + adaptation verdicts of the chunk: one copy each
-    std::vector<OnlineStatus> hs((size_t)C * S);
-    std::vector<int> hit((size_t)C * S);
-    HIP_TRY(hipMemcpyAsync(hs.data(), o->status, hs.size() * sizeof(OnlineStatus), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(hit.data(), o->iters, hit.size() * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    for (int s = 0; s < S; ++s) {
-        for (int i = 0; i < nfr[s]; ++i) {
-            const OnlineStatus& q = hs[(size_t)i * S + s];
-            snmf_online_frame tr{};
-            tr.n_iter = q.n_iter; tr.trig = q.trig; tr.n_up = q.n_up; tr.beta = q.beta; tr.A_x_mag = q.A_x_mag; tr.A_d_mag = q.A_d_mag;
-            tr.Q_control = q.Q_control;
-            if (p.adapt_train_N && q.do_solve && q.n_up > 0) {
-                tr.solved = 1;
-                tr.adapt_iters = hit[(size_t)i * S + s];
-            }
-            o->trace[s].push_back(tr);
-            if (o->trace[s].size() > kBTraceCap) o->trace[s].pop_front();
-        }
-        const size_t a0 = (size_t)h_oo[s], n = (size_t)h_no[s] * hop;
-        if (want_f) sink[s].f.insert(sink[s].f.end(), hf.begin() + a0, hf.begin() + a0 + n);
-        if (want_i16) sink[s].i16.insert(sink[s].i16.end(), h16.begin() + a0, h16.begin() + a0 + n);
-        if (want_cls) {
-            sink[s].x.insert(sink[s].x.end(), hx.begin() + a0, hx.begin() + a0 + n);
-            sink[s].d.insert(sink[s].d.end(), hd.begin() + a0, hd.begin() + a0 + n);
-        }
-        if (want_ci) {
-            sink[s].c.resize(hc.size());
-            for (size_t c = 0; c < hc.size(); ++c) sink[s].c[c].insert(sink[s].c[c].end(), hc[c].begin() + a0, hc[c].begin() + a0 + n);
-        }
-        if (nreal[s] > 0) {  // history for the next chunk: the last sz - hop samples this stream framed
-            const float* end = sig.data() + h_off[s] + (sz - hop) + (size_t)nreal[s] * hop;
-            o->hist[s].assign(end - (sz - hop), end);
-        }
-        o->l[s] += nfr[s];
-    }
+    o->post_lds = (size_t)(o->r + 7 * F + 3 * o->n1) * 4;
+}
+
+static int obm_post(snmf_online_batch* o, const OBatchFrames& fr, int step) {
+    OBatchPost bp = o->post_bp;
+    bp.fr = fr;
+    bp.step = step;
+    hipLaunchKernelGGL(k_obpost, dim3(o->S), dim3(1024), o->post_lds, o->ctx->stream, o->post_a, bp);
+    HIP_TRY(hipGetLastError());
+    return SNMF_OK;
+}
+
+// the synthesis of one signal: k_obtail (store = 0: the stream's tail into the buffer's head; 1: back out), k_obistft, k_obola
+static int obm_tail(snmf_online_batch* o, float* tail, const OBatchFrames& fr, int64_t syn_stride, int store) {
+    hipLaunchKernelGGL(k_obtail, dim3(o->S), dim3(256), 0, o->ctx->stream, o->syn, tail, fr.nfr, syn_stride, o->nov, o->p.framelength, store);
+    HIP_TRY(hipGetLastError());
+    return SNMF_OK;
+}
+
+static int obm_istft(snmf_online_batch* o, const float* mag, const OBatchFrames& fr, int C, int64_t syn_stride) {
+    const snmf_online_params& p = o->p;
+    const int S = o->S, nov = o->nov;
+    hipStream_t st = o->ctx->stream;
+    OIstftArgs ia{};
+    ia.mag = mag; ia.ph = o->Yph; ia.ld = o->F; ia.n_frames = C; ia.sz = p.framelength; ia.dcb = p.dcbin_back; ia.powv = (float)p.pow;
+    ia.scale = (float)(p.overlapscale / (double)o->N); ia.preemph = (float)p.preemph; ia.win = o->win_i; ia.tw = o->tw; ia.syn = o->syn;
+    by_logn([&](auto L) { hipLaunchKernelGGL(k_obistft<decltype(L)::value>, dim3(C, S), dim3(256), 0, st, ia, fr.nfr, S, syn_stride, nov); },
+               o->N);
+    HIP_TRY(hipGetLastError());
+    return SNMF_OK;
+}
+
+static int obm_ola(snmf_online_batch* o, int gx, const OBatchFrames& fr, int64_t syn_stride, const int* d_if, const int* d_no,
+                   const int64_t* d_oo, float* of, int16_t* o16) {
+    const snmf_online_params& p = o->p;
+    hipLaunchKernelGGL(k_obola, dim3(gx, o->S), dim3(256), 0, o->ctx->stream, (const float*)o->syn, syn_stride, fr, d_if, d_no, d_oo, p.delay,
+                       p.framelength, p.frameshift, o->nov, of, o16);
+    HIP_TRY(hipGetLastError());
     return SNMF_OK;
 }
 
@@ -723,83 +528,13 @@ static int ob_process(snmf_online_batch* o, const float* const* pcm, const int64
                       int16_t* const* xt_i16, float* const* xh_f32, float* const* dh_f32, float* const* xhi_f32, float* const* dhi_f32,
                       const int64_t* cap, int64_t* n_out) {
     if (!o) return fail(SNMF_ERR_INVALID, "online batch handle is NULL");
-    if (!n || !pcm) return fail(SNMF_ERR_INVALID, "pcm / n is NULL");
-    const int S = o->S;
-    const snmf_online_params& p = o->p;
-    const int hop = p.frameshift;
-    if (n_out)
-        for (int s = 0; s < S; ++s) n_out[s] = 0;
-    if (o->f64) return fail(SNMF_ERR_STATE, "snmf_online_batch_process_f32 on an fp64 batch: use snmf_online_batch_process_f64");
-    if (o->failed) return fail(SNMF_ERR_STATE, "an earlier call failed midway through a chunk; the batch state is not reusable, create a new one");
-    if ((xh_f32 || dh_f32 || xhi_f32 || dhi_f32) && !p.class_outputs) return fail(SNMF_ERR_STATE, "class outputs were not requested at creation");
-    const bool any_out = xt_f32 || xt_i16 || xh_f32 || dh_f32 || xhi_f32 || dhi_f32;
-    if (any_out && !cap) return fail(SNMF_ERR_INVALID, "cap is NULL");
-    std::vector<int64_t> nfr_tot(S), tail(S);
-    for (int s = 0; s < S; ++s) {
-        if (n[s] < 0 || (n[s] > 0 && !pcm[s])) return fail(SNMF_ERR_INVALID, "stream %d: pcm is NULL", s);
-        if (o->finished[s] && (n[s] > 0 || (flush && flush[s])))
-            return fail(SNMF_ERR_STATE, "stream %d was flushed; restart it before feeding it", s);
-        nfr_tot[s] = ((int64_t)o->pending[s].size() + n[s]) / hop;
-        tail[s] = (flush && flush[s] && !o->finished[s]) ? p.delay + 1 : 0;
-        const int64_t need = (nfr_tot[s] + tail[s]) * hop;
-        auto short_cap = [&](const void* const* v) { return v && v[s] && cap[s] < need; };
-        if (short_cap((const void* const*)xt_f32) || short_cap((const void* const*)xt_i16) || short_cap((const void* const*)xh_f32) ||
-            short_cap((const void* const*)dh_f32) || short_cap((const void* const*)xhi_f32) || short_cap((const void* const*)dhi_f32))
-            return fail(SNMF_ERR_INVALID, "stream %d: output capacity %lld < %lld samples", s, (long long)cap[s], (long long)need);
+    if (o->f64) {  // (the order of obatch_process's first checks)
+        if (!n || !pcm) return fail(SNMF_ERR_INVALID, "pcm / n is NULL");
+        if (n_out)
+            for (int s = 0; s < o->S; ++s) n_out[s] = 0;
+        return fail(SNMF_ERR_STATE, "snmf_online_batch_process_f32 on an fp64 batch: use snmf_online_batch_process_f64");
     }
-    o->started = true;
-    (void)hipGetLastError();  // clean sticky error state, see PLAN_CHECK
-    HIP_TRY(hipSetDevice(o->ctx->device));
-    for (int s = 0; s < S; ++s) o->pending[s].insert(o->pending[s].end(), pcm[s] ? pcm[s] : nullptr, pcm[s] ? pcm[s] + n[s] : nullptr);
-    // chunks: up to C frames per stream, each stream's PCM frames first, then its flush frames
-    const int C = (int)std::max<int64_t>(1, std::min<int64_t>(4096, kBChunkSlots / S));
-    std::vector<int64_t> done(S, 0);
-    std::vector<ObSink> sink(S);
-    // class signals: with a partition set they come from the class kernel; without one x_hat / d_hat are the one class per side
-    const bool cls_set = o->n_cls > 0, wci = cls_set && (xhi_f32 || dhi_f32);
-    const bool wf = xt_f32 != nullptr, wi = xt_i16 != nullptr, wc = xh_f32 || dh_f32 || (!cls_set && (xhi_f32 || dhi_f32));
-    for (;;) {
-        std::vector<int> nfr(S), nreal(S);
-        bool any = false;
-        for (int s = 0; s < S; ++s) {
-            const int64_t left = nfr_tot[s] + tail[s] - done[s];
-            nfr[s] = (int)std::min<int64_t>(C, left);
-            nreal[s] = (int)std::max<int64_t>(0, std::min<int64_t>(nfr[s], nfr_tot[s] - done[s]));
-            any |= nfr[s] > 0;
-        }
-        if (!any) break;
-        if (int rc = ob_run_chunk(o, nfr, nreal, done, wf, wi, wc, wci, sink)) {
-            o->failed = true;  // frames of this call were consumed and the device state advanced: never retry on it
-            return rc;
-        }
-        for (int s = 0; s < S; ++s) done[s] += nfr[s];
-    }
-    for (int s = 0; s < S; ++s) {
-        o->pending[s].erase(o->pending[s].begin(), o->pending[s].begin() + nfr_tot[s] * hop);
-        if (tail[s]) {
-            o->pending[s].clear();  // a partial hop is dropped (src/NTF_sep_event_RT.m:69-76)
-            o->finished[s] = 1;
-        }
-        const ObSink& k = sink[s];
-        if (wf && xt_f32[s]) std::memcpy(xt_f32[s], k.f.data(), k.f.size() * 4);
-        if (wi && xt_i16[s]) std::memcpy(xt_i16[s], k.i16.data(), k.i16.size() * 2);
-        if (xh_f32 && xh_f32[s]) std::memcpy(xh_f32[s], k.x.data(), k.x.size() * 4);
-        if (dh_f32 && dh_f32[s]) std::memcpy(dh_f32[s], k.d.data(), k.d.size() * 4);
-        size_t nc_out = 0;
-        if (cls_set) {
-            for (int c = 0; c < (int)k.c.size(); ++c) {
-                float* dst = c < o->n_ev ? ((xhi_f32 && xhi_f32[s]) ? xhi_f32[s] + (size_t)c * cap[s] : nullptr)
-                                         : ((dhi_f32 && dhi_f32[s]) ? dhi_f32[s] + (size_t)(c - o->n_ev) * cap[s] : nullptr);
-                if (dst) std::memcpy(dst, k.c[c].data(), k.c[c].size() * 4);
-                nc_out = std::max(nc_out, k.c[c].size());
-            }
-        } else {
-            if (xhi_f32 && xhi_f32[s]) std::memcpy(xhi_f32[s], k.x.data(), k.x.size() * 4);
-            if (dhi_f32 && dhi_f32[s]) std::memcpy(dhi_f32[s], k.d.data(), k.d.size() * 4);
-        }
-        if (n_out) n_out[s] = (int64_t)std::max(std::max(std::max(k.f.size(), k.i16.size()), std::max(k.x.size(), k.d.size())), nc_out);
-    }
-    return SNMF_OK;
+    return obatch_process(o, pcm, n, flush, xt_f32, xt_i16, xh_f32, dh_f32, xhi_f32, dhi_f32, cap, n_out);
 }
 
 extern "C" int snmf_online_batch_process_f32(snmf_online_batch* o, const float* const* pcm, const int64_t* n, const int32_t* flush,
@@ -849,21 +584,7 @@ extern "C" int snmf_online_batch_get_basis_f64(snmf_online_batch* o, int32_t k, 
 
 static int ob_restart_checked(snmf_online_batch* o, int32_t n, const int32_t* slots, const double* Bd, const double* Bmd, const float* H0,
                               const float* Ad) {
-    if (n < 0 || n > o->S) return fail(SNMF_ERR_INVALID, "restart of %d streams in a batch of %d", n, o->S);
-    if (n > 0 && !slots) return fail(SNMF_ERR_INVALID, "slots is NULL");
-    std::vector<uint8_t> seen(o->S, 0);
-    for (int i = 0; i < n; ++i) {
-        const int s = slots[i];
-        if (s < 0 || s >= o->S) return fail(SNMF_ERR_INVALID, "stream %d out of range [0, %d)", s, o->S);
-        if (seen[s]) return fail(SNMF_ERR_INVALID, "stream %d listed twice", s);
-        seen[s] = 1;
-    }
-    if (o->failed) return fail(SNMF_ERR_STATE, "an earlier call failed midway through a chunk; the batch state is not reusable, create a new one");
-    for (int i = 0; i < n; ++i) {
-        const int s = slots[i];
-        if (!o->finished[s] && (o->l[s] > 0 || !o->pending[s].empty()))
-            return fail(SNMF_ERR_STATE, "stream %d is in the middle of a recording; flush it before a restart", s);
-    }
+    SN_TRY(obatch_restart_check(o, n, slots));
     if (n == 0) return SNMF_OK;
     (void)hipGetLastError();  // clean sticky error state, see PLAN_CHECK
     HIP_TRY(hipSetDevice(o->ctx->device));
@@ -932,11 +653,7 @@ extern "C" int snmf_online_batch_get_mel_basis_f64(snmf_online_batch* o, int32_t
 extern "C" int snmf_online_batch_trace(snmf_online_batch* o, int32_t k, snmf_online_frame* out, int64_t cap, int64_t* n) {
     if (!o) return fail(SNMF_ERR_INVALID, "online batch handle is NULL");
     if (o->f64) return online_batch_f64_trace(o->f64, k, out, cap, n);
-    if (k < 0 || k >= o->S) return fail(SNMF_ERR_INVALID, "stream %d out of range [0, %d)", k, o->S);
-    const auto& tr = o->trace[k];
-    if (n) *n = (int64_t)tr.size();
-    if (out && cap > 0) std::copy_n(tr.begin(), (size_t)std::min<int64_t>(cap, (int64_t)tr.size()), out);
-    return SNMF_OK;
+    return obatch_trace(o, k, out, cap, n);
 }
 
 // ---- fp64 mode (snmf_online_batch_f64.h): every input crosses in fp64 and every step from PCM to the fed-back state is fp64 ----

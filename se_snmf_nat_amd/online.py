@@ -567,7 +567,7 @@ def ntf_sep_event_rt_batch(pcms, B_DFT_x, B_DFT_d, p, H0=None, Ad_blk0=None, ctx
         sep.close()
 
 
-_B_CHUNK_SLOTS = 16384  # (frame, stream) slots of one device chunk (kBChunkSlots, snmf_tu_online_batch.hip)
+_B_CHUNK_SLOTS = 16384  # (frame, stream) slots of one device chunk (kBChunkSlots, csrc/snmf_online_batch_host.h)
 
 
 def _per_chain(x, n, shape, name, dtype):
