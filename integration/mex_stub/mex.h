@@ -1,9 +1,14 @@
-/* mex.h -- COMPILE-ONLY stub of the documented MathWorks MEX / matrix C API, limited to the entry points the two
- * shims in this directory use.  MATLAB is not installed in the build container, so the real mex.h / matrix.h are
- * absent; __graft_entry__.build() runs `g++ -fsyntax-only -Iintegration/mex_stub` over the *_mex.cpp shims so that
- * a typo or a wrong argument type in a shim cannot ship unnoticed.  Prototypes follow the public API reference
- * ("C Matrix API", "C MEX API", interleaved-complex / -R2018a names).  Nothing links against this file and it is not
- * a substitute for MATLAB's header: build the shims with `mex -R2018a` as INTEGRATION.md says. */
+/* mex.h -- stub of the documented MathWorks MEX / matrix C API, limited to the entry points the shims in the parent
+ * directory use.  MATLAB is not installed where this project is built and tested, so the real mex.h / matrix.h are
+ * absent.  Two things stand on this file:
+ *   - __graft_entry__.build() runs `g++ -fsyntax-only -Iintegration/mex_stub` over the *_mex.cpp shims, so that a typo
+ *     or a wrong argument type in a shim cannot ship unnoticed;
+ *   - tests/mexhost/mexhost.cpp implements exactly these prototypes (documented semantics, arrays between guard zones),
+ *     and tests/test_mexhost.py / tests/test_gpu_mex.py compile each shim with it and EXECUTE the shim: argument checks
+ *     without a device, every command on the device against the Python binding and the fp64 oracle.
+ * Prototypes follow the public API reference ("C Matrix API", "C MEX API", interleaved-complex / -R2018a names).  This is
+ * not a substitute for MATLAB's header: build the shims with `mex -R2018a` as INTEGRATION.md says.  The shims under real
+ * MATLAB, and the .m wrappers beyond the arity of their MEX calls, remain unverified. */
 #ifndef SNMF_MEX_STUB_H
 #define SNMF_MEX_STUB_H
 #include <stddef.h>

@@ -19,8 +19,10 @@
 //       p.snmf_precision = 'fp64': 'dnmf' and 'train' run in double from the samples on (waveforms, melmat, features and all
 //       solves; the *_fp64 entries); 'fp32' or absent: the default.  Any other string is an error, as is 'fp64' with 'dnmf_multi'.
 //
-// Written against the documented MEX C API; MATLAB is not available in the build container, so __graft_entry__.build() only
-// SYNTAX-CHECKS this file against integration/mex_stub/mex.h.  Build:
+// Written against the documented MEX C API.  MATLAB is not available where this project is built and tested:
+// __graft_entry__.build() syntax-checks this file against integration/mex_stub/mex.h, and the tests execute it under a test
+// host that implements that stub (tests/mexhost/, tests/test_mexhost.py, tests/test_gpu_mex.py).  Every argument is checked
+// before the device is touched.  Build:
 //     mex -R2018a -I<repo>/include integration/snmf_dnmf_mex.cpp -L<repo>/se_snmf_nat_amd -lsnmf_hip
 #include <cstdint>
 #include <cstring>
@@ -53,6 +55,15 @@ static double field(const mxArray* s, const char* name) {
 static double field_or(const mxArray* s, const char* name, double dflt) {
     const mxArray* f = mxGetField(s, 0, name);
     return (!f || mxIsEmpty(f)) ? dflt : mxGetScalar(f);
+}
+static double scalar_arg(const mxArray* a, const char* what) {
+    if (mxIsStruct(a) || mxGetNumberOfElements(a) != 1) mexErrMsgIdAndTxt("snmf:dim", "%s must be a scalar", what);
+    return mxGetScalar(a);
+}
+// a waveform: the C ABI reads numel(a) consecutive samples, which is the signal only if a is a vector
+static void check_vector(const mxArray* a, const char* what) {
+    if (!mxIsDouble(a) || mxIsComplex(a)) mexErrMsgIdAndTxt("snmf:type", "%s must be real double", what);
+    if (mxGetNumberOfDimensions(a) != 2 || (mxGetM(a) > 1 && mxGetN(a) > 1)) mexErrMsgIdAndTxt("snmf:dim", "%s must be a vector", what);
 }
 static std::vector<float> to_float(const mxArray* a, const char* what) {
     if (!mxIsDouble(a) || mxIsComplex(a)) mexErrMsgIdAndTxt("snmf:type", "%s must be real double", what);
@@ -143,7 +154,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     if (!std::strcmp(cmd, "nframes")) {
         if (nrhs != 3 || !mxIsStruct(prhs[2])) mexErrMsgIdAndTxt("snmf:nargin", "usage: n = snmf_dnmf_mex('nframes', n_samples, p)");
         fill_stft(prhs[2], win, &sp, field_or(prhs[2], "DCbin", 1));
-        plhs[0] = mxCreateDoubleScalar((double)snmf_stft_num_frames(&sp, (int64_t)mxGetScalar(prhs[1])));
+        plhs[0] = mxCreateDoubleScalar((double)snmf_stft_num_frames(&sp, (int64_t)scalar_arg(prhs[1], "n_samples")));
         return;
     }
     if (!std::strcmp(cmd, "dnmf_multi")) {  // (no context of this file's own: the library keeps one team of contexts per device list)
@@ -185,11 +196,12 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         }
         return;
     }
-    need_ctx();
     if (!std::strcmp(cmd, "dnmf")) {
         if (nrhs != 7 || !mxIsStruct(prhs[5])) mexErrMsgIdAndTxt("snmf:nargin", "usage: [B_hat, n_iter] = snmf_dnmf_mex('dnmf', x, d, B, H0, p, melmat)");
         const mxArray *B = prhs[3], *H0 = prhs[4], *p = prhs[5];
         const bool f64 = fp64_mode(p);
+        check_vector(prhs[1], "x");
+        check_vector(prhs[2], "d");
         std::vector<float> x, d, mel;
         std::vector<double> mel64;
         const double *x64 = nullptr, *d64 = nullptr;
@@ -214,9 +226,10 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
             if (!mxIsDouble(H0) || (int)mxGetM(H0) != q.r || (int)mxGetN(H0) != q.T) mexErrMsgIdAndTxt("snmf:dim", "H0 must be %d x %d double or []", q.r, q.T);
             h0 = mxGetDoubles(H0);
         }
+        const uint64_t seed = device_seed(p, h0 != nullptr);
+        need_ctx();
         plhs[0] = mxCreateDoubleMatrix((mwSize)q.F, (mwSize)q.r, mxREAL);
         int32_t nit[3] = {0, 0, 0};
-        const uint64_t seed = device_seed(p, h0 != nullptr);
         const int st = f64 ? snmf_run_basis_dnmf_audio_fp64(g_ctx, &q, &sp, R_x, R_d, x64, (int64_t)n_x, d64, (int64_t)n_d, M ? mel64.data() : nullptr, M,
                                                             mxGetDoubles(B), q.F, h0, seed, mxGetDoubles(plhs[0]), q.F, nullptr, q.r, nit)
                            : snmf_run_basis_dnmf_audio_f64(g_ctx, &q, &sp, R_x, R_d, x.data(), (int64_t)n_x, d.data(), (int64_t)n_d, M ? mel.data() : nullptr, M,
@@ -232,13 +245,14 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         if (nrhs != 7 || !mxIsStruct(prhs[4])) mexErrMsgIdAndTxt("snmf:nargin", "usage: [B_DFT,B_Mel,A_DFT,A_Mel,n_iter] = snmf_dnmf_mex('train', s_full, sample_idx, H0, p, melmat, DC_bin)");
         const mxArray *idx = prhs[2], *H0 = prhs[3], *p = prhs[4];
         const bool f64 = fp64_mode(p);
+        check_vector(prhs[1], "s_full");
         std::vector<float> s, mel;
         std::vector<double> mel64;
         const double* s64 = nullptr;
         if (f64) s64 = doubles_of(prhs[1], "s_full");
         else s = to_float(prhs[1], "s_full");
         const size_t n_s = mxGetNumberOfElements(prhs[1]);
-        fill_stft(p, win, &sp, mxGetScalar(prhs[6]));
+        fill_stft(p, win, &sp, scalar_arg(prhs[6], "DC_bin"));
         int M = 0;
         const int nb = sp.fftlength / 2 + 1, K = 2 * sp.splice + 1;
         if (f64) mel64 = mel_rows<double>(prhs[5], &M, nb);
@@ -259,19 +273,25 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         q.r = (int32_t)mxGetNumberOfElements(idx);
         if (!mxIsDouble(idx) || q.r < 1) mexErrMsgIdAndTxt("snmf:dim", "sample_idx must be a double vector of 1-based frame indices");
         std::vector<int64_t> i0((size_t)q.r);
-        for (int j = 0; j < q.r; ++j) i0[j] = (int64_t)mxGetDoubles(idx)[j] - 1;  // randsample is 1-based (:81)
+        for (int j = 0; j < q.r; ++j) {
+            const double v = mxGetDoubles(idx)[j];  // randsample is 1-based (:81)
+            if (!(v >= 1.0 && v <= (double)q.T) || v != (double)(int64_t)v)
+                mexErrMsgIdAndTxt("snmf:dim", "sample_idx(%d) = %g is not a frame index in 1..%d", j + 1, v, q.T);
+            i0[j] = (int64_t)v - 1;
+        }
         const double* h0 = nullptr;
         if (!mxIsEmpty(H0)) {
             if (!mxIsDouble(H0) || (int)mxGetM(H0) != q.r || (int)mxGetN(H0) != q.T) mexErrMsgIdAndTxt("snmf:dim", "H0 must be %d x %d double or []", q.r, q.T);
             h0 = mxGetDoubles(H0);
         }
+        const double dd = field_or(p, "domain_DD", 0) != 0.0 ? field(p, "alpha_eta") : -1.0;  // :64-67
+        const uint64_t seed = device_seed(p, h0 != nullptr || exemplar);
+        need_ctx();
         plhs[0] = mxCreateDoubleMatrix((mwSize)q.F, (mwSize)q.r, mxREAL);
         mxArray* BM = mxCreateDoubleMatrix((mwSize)(K * M), (mwSize)q.r, mxREAL);
         mxArray* AD = exemplar ? mxCreateDoubleScalar(0.0) : mxCreateDoubleMatrix((mwSize)q.r, (mwSize)q.T, mxREAL);  // :95-96
         mxArray* AM = exemplar ? mxCreateDoubleScalar(0.0) : mxCreateDoubleMatrix((mwSize)q.r, (mwSize)q.T, mxREAL);
         int32_t nit[2] = {0, 0};
-        const double dd = field_or(p, "domain_DD", 0) != 0.0 ? field(p, "alpha_eta") : -1.0;  // :64-67
-        const uint64_t seed = device_seed(p, h0 != nullptr || exemplar);
         double *ad = exemplar ? nullptr : mxGetDoubles(AD), *am = exemplar ? nullptr : mxGetDoubles(AM);
         const int st = f64 ? snmf_run_basis_train_audio_fp64(g_ctx, &q, &sp, dd, mel64.data(), M, s64, (int64_t)n_s, i0.data(), exemplar ? 1 : 0, h0, seed,
                                                              mxGetDoubles(plhs[0]), ad, mxGetDoubles(BM), am, nit)

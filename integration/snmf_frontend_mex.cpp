@@ -9,14 +9,16 @@
 //     TF_Mel(...) = melmat * TF_mag(...)                                                                     :70-78
 // (run_basis_DNMF.m:13-34 and run_basis_DNMF_Mel.m form Y, X, D the same way).
 //
-//     TF_mag = snmf_frontend_mex('stft', s, p, DC_bin)        s: samples (double or single vector), p: settings struct
+//     TF_mag = snmf_frontend_mex('stft', s, p, DC_bin)        s: samples (real double vector), p: settings struct
 //     TF_Mel = snmf_frontend_mex('mel', TF_mag, melmat, K)    melmat: F_order x (fftlength/2+1) (= mel_matrix(...)'), K = 2*Splice+1
 //     TF_Mel = snmf_frontend_mex('mel', TF_mag, melmat, K, precision)
 //   p.snmf_precision (resp. the fifth argument of 'mel') = 'fp64': computed in double from MATLAB's doubles (the *_fp64 entries);
 //   'fp32', empty or absent: the default.  Any other string is an error.
 //
-// Written against the documented MEX C API; MATLAB is not available in the build container, so
-// __graft_entry__.build() only SYNTAX-CHECKS this file against integration/mex_stub/mex.h.  Build:
+// Written against the documented MEX C API.  MATLAB is not available where this project is built and tested:
+// __graft_entry__.build() syntax-checks this file against integration/mex_stub/mex.h, and the tests execute it under a test
+// host that implements that stub (tests/mexhost/, tests/test_mexhost.py, tests/test_gpu_mex.py).  Every argument is checked
+// before the device is touched.  Build:
 //     mex -R2018a -I<repo>/include integration/snmf_frontend_mex.cpp -L<repo>/se_snmf_nat_amd -lsnmf_hip
 #include <cstdint>
 #include <cstring>
@@ -45,6 +47,10 @@ static double field(const mxArray* s, const char* name) {
     if (!f || mxIsEmpty(f)) mexErrMsgIdAndTxt("snmf:field", "Reference to non-existent field '%s'.", name);
     return mxGetScalar(f);
 }
+static double scalar_arg(const mxArray* a, const char* what) {
+    if (mxIsStruct(a) || mxGetNumberOfElements(a) != 1) mexErrMsgIdAndTxt("snmf:dim", "%s must be a scalar", what);
+    return mxGetScalar(a);
+}
 static std::vector<float> to_float(const mxArray* a, const char* what) {
     if (!mxIsDouble(a) || mxIsComplex(a)) mexErrMsgIdAndTxt("snmf:type", "%s must be real double", what);
     const size_t n = mxGetNumberOfElements(a);
@@ -70,7 +76,6 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     if (nlhs > 1) mexErrMsgIdAndTxt("snmf:nargout", "one output");
     char cmd[16];
     mxGetString(prhs[0], cmd, sizeof cmd);
-    need_ctx();
     if (std::string(cmd) == "stft") {
         if (nrhs != 4 || !mxIsStruct(prhs[2])) mexErrMsgIdAndTxt("snmf:nargin", "TF_mag = snmf_frontend_mex('stft', s, p, DC_bin)");
         const mxArray* p = prhs[2];
@@ -85,13 +90,15 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         sp.framelength = (int32_t)field(p, "framelength");
         sp.frameshift = (int32_t)field(p, "frameshift");
         sp.fftlength = (int32_t)field(p, "fftlength");
-        sp.dcbin = (int32_t)mxGetScalar(prhs[3]);
+        sp.dcbin = (int32_t)scalar_arg(prhs[3], "DC_bin");
         sp.splice = (int32_t)field(p, "Splice");
         sp.preemph = field(p, "preemph");
         sp.pow = field(p, "pow");
         sp.nonzerofloor = field(p, "nonzerofloor");
         if (mxGetNumberOfElements(win) != (size_t)sp.framelength) mexErrMsgIdAndTxt("snmf:dim", "win_STFT must have framelength entries");
+        if (mxGetM(prhs[1]) > 1 && mxGetN(prhs[1]) > 1) mexErrMsgIdAndTxt("snmf:dim", "s must be a vector");
         sp.window = mxGetDoubles(win);
+        need_ctx();
         const int64_t nfr = snmf_stft_num_frames(&sp, (int64_t)n_s);
         const size_t F = (size_t)(2 * sp.splice + 1) * (size_t)(sp.fftlength / 2 + 1);
         int32_t n_out = 0;
@@ -113,9 +120,16 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         const std::vector<float> V = f64 ? std::vector<float>() : to_float(prhs[1], "TF_mag");
         if (f64 && (!mxIsDouble(prhs[1]) || mxIsComplex(prhs[1]))) mexErrMsgIdAndTxt("snmf:type", "TF_mag must be real double");
         const size_t rows = mxGetM(prhs[1]), T = mxGetN(prhs[1]);
+        if (!mxIsDouble(prhs[2]) || mxIsComplex(prhs[2])) mexErrMsgIdAndTxt("snmf:type", "melmat must be real double");
         const size_t M = mxGetM(prhs[2]), n = mxGetN(prhs[2]);
-        const int K = (int)mxGetScalar(prhs[3]);
+        const int K = (int)scalar_arg(prhs[3], "K");
+        if (M < 1 || n < 1) mexErrMsgIdAndTxt("snmf:dim", "melmat must not be empty");
         if (K < 1 || rows != (size_t)K * n) mexErrMsgIdAndTxt("snmf:dim", "TF_mag must have K * size(melmat,2) rows");
+        if (T == 0) {  // no frames: nothing for the device to do
+            plhs[0] = mxCreateDoubleMatrix((size_t)K * M, 0, mxREAL);
+            return;
+        }
+        need_ctx();
         // the C ABI takes melmat row-major (M x n); MATLAB stores it column-major
         const double* mm = mxGetDoubles(prhs[2]);
         if (f64) {
@@ -123,7 +137,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
             for (size_t i = 0; i < M; ++i)
                 for (size_t j = 0; j < n; ++j) mel64[i * n + j] = mm[j * M + i];
             plhs[0] = mxCreateDoubleMatrix((size_t)K * M, T, mxREAL);
-            if (T > 0 && snmf_mel_features_fp64(g_ctx, mel64.data(), (int32_t)M, (int32_t)n, K, mxGetDoubles(prhs[1]), (int64_t)rows, (int32_t)T,
+            if (snmf_mel_features_fp64(g_ctx, mel64.data(), (int32_t)M, (int32_t)n, K, mxGetDoubles(prhs[1]), (int64_t)rows, (int32_t)T,
                                                 mxGetDoubles(plhs[0]), (int64_t)((size_t)K * M), 0) != SNMF_OK)
                 mexErrMsgIdAndTxt("snmf:mel", "%s", snmf_last_error());
             return;

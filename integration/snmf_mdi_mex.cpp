@@ -6,10 +6,13 @@
 //     [v_mdi, w, h, div, cost, n_iter] = snmf_mdi_mex(v, mask, w0, h0, sparsity, opts)
 //   v, mask  F x T double;  w0 F x r (init_w, :116-131);  h0 r x T (init_h, :133-140);  sparsity: scalar (p.sparsity_mdi)
 //   opts     struct: beta, max_iter, conv_eps (p.conv_eps_mdi), cost_check, w_update_ind, h_update_ind (r x 1), device
-// The MATLAB wrapper that shadows src/snmf_mdi.m applies the reference's defaults and draws the random factors with
-// MATLAB's own generator, exactly like integration/sparse_nmf.m does for the plain solver.
+// No MATLAB wrapper for this shim exists yet (integration/ holds none): the caller applies the defaults of
+// src/snmf_mdi.m:75-164 (sparsity_mdi, conv_eps_mdi, ...) and draws the random factors with MATLAB's own generator, as
+// integration/sparse_nmf.m does for the plain solver, and passes them in.
 //
-// Written against the documented MEX C API; only SYNTAX-CHECKED here (integration/mex_stub/mex.h), MATLAB being absent.
+// Written against the documented MEX C API.  MATLAB being absent, build() syntax-checks this file against
+// integration/mex_stub/mex.h, and the tests execute it under a test host that implements that stub (tests/mexhost/,
+// tests/test_mexhost.py, tests/test_gpu_mex.py).
 //     mex -R2018a -I<repo>/include integration/snmf_mdi_mex.cpp -L<repo>/se_snmf_nat_amd -lsnmf_hip
 #include <cstdint>
 #include <cstring>
@@ -45,6 +48,7 @@ static void fill_mask(const mxArray* opts, const char* name, size_t r, std::vect
         const mxLogical* p = mxGetLogicals(f);
         for (size_t i = 0; i < r; ++i) out[i] = p[i] ? 1 : 0;
     } else {
+        if (!mxIsDouble(f) || mxIsComplex(f)) mexErrMsgIdAndTxt("snmf:type", "%s must be logical or real double", name);
         const double* p = mxGetDoubles(f);
         for (size_t i = 0; i < r; ++i) out[i] = p[i] != 0.0;
     }
@@ -61,17 +65,11 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     check2d(w0, "init_w");
     check2d(h0, "init_h");
     if (!mxIsStruct(opts)) mexErrMsgIdAndTxt("snmf:type", "opts must be a struct");
+    if (!mxIsDouble(sp) || mxIsComplex(sp)) mexErrMsgIdAndTxt("snmf:type", "sparsity must be a real double scalar or []");
+    if (mxGetNumberOfElements(sp) > 1) mexErrMsgIdAndTxt("snmf:dim", "sparsity must be a scalar (p.sparsity_mdi) or []");
     const size_t F = mxGetM(v), T = mxGetN(v), r = mxGetN(w0);
     if (mxGetM(mk) != F || mxGetN(mk) != T) mexErrMsgIdAndTxt("snmf:dim", "mask must have the size of v");
     if (mxGetM(w0) != F || mxGetM(h0) != r || mxGetN(h0) != T) mexErrMsgIdAndTxt("snmf:dim", "init_w must be F x r and init_h r x T");
-    const int device = (int)opt_scalar(opts, "device", 0);
-    if (!g_ctx || g_device != device) {
-        at_exit();
-        if (snmf_ctx_create(&g_ctx, device) != SNMF_OK) mexErrMsgIdAndTxt("snmf:device", "%s", snmf_last_error());
-        g_device = device;
-        mexLock();
-        mexAtExit(at_exit);
-    }
     snmf_params p;
     std::memset(&p, 0, sizeof p);
     p.F = (int32_t)F;
@@ -90,6 +88,15 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     p.w_update_ind = wi.data();
     p.h_update_ind = hi.data();
 
+    // (every argument is checked before the device is touched)
+    const int device = (int)opt_scalar(opts, "device", 0);
+    if (!g_ctx || g_device != device) {
+        at_exit();
+        if (snmf_ctx_create(&g_ctx, device) != SNMF_OK) mexErrMsgIdAndTxt("snmf:device", "%s", snmf_last_error());
+        g_device = device;
+        mexLock();
+        mexAtExit(at_exit);
+    }
     snmf_plan* pl = nullptr;
     if (snmf_plan_create(g_ctx, &p, &pl) != SNMF_OK) mexErrMsgIdAndTxt("snmf:plan", "%s", snmf_last_error());
     int st = SNMF_OK;

@@ -2,10 +2,11 @@
 //
 // This is the binding a maintainer of lordet01/SE_SNMF_NAT adds to make src/sparse_nmf.m /
 // src/sparse_nmf_GPU.m run on an MI355X.  It is written against the documented MEX C API
-// (mex.h / matrix.h).  MATLAB is not available in the build container or on the GPU box, so
-// __graft_entry__.build() only SYNTAX-CHECKS this file against a stub of those prototypes
-// (integration/mex_stub/mex.h); the same C ABI is exercised by the Python ctypes binding
-// (se_snmf_nat_amd/_lib.py), which is what the tests drive.
+// (mex.h / matrix.h).  MATLAB is not available where this project is built and tested:
+// __graft_entry__.build() syntax-checks this file against a stub of those prototypes
+// (integration/mex_stub/mex.h), and the tests compile it with a test host that implements the stub
+// (tests/mexhost/) and execute it: tests/test_mexhost.py (argument checks), tests/test_gpu_mex.py (results,
+// bit for bit against the Python ctypes binding se_snmf_nat_amd/_lib.py, which makes the same C calls).
 //
 // Build (on a machine with MATLAB + ROCm):
 //     mex -R2018a -I<repo>/include integration/sparse_nmf_mex.cpp -L<repo>/se_snmf_nat_amd -lsnmf_hip
@@ -61,6 +62,7 @@ static void fill_mask(const mxArray* opts, const char* name, size_t r, std::vect
         const mxLogical* p = mxGetLogicals(f);
         for (size_t i = 0; i < r; ++i) out[i] = p[i] ? 1 : 0;
     } else {
+        if (!mxIsDouble(f) || mxIsComplex(f)) mexErrMsgIdAndTxt("snmf:type", "%s must be logical or real double", name);
         const double* p = mxGetDoubles(f);
         for (size_t i = 0; i < r; ++i) out[i] = p[i] != 0.0;
     }
@@ -81,15 +83,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     if (mxGetM(w0) != F) mexErrMsgIdAndTxt("snmf:dim", "init_w must have size(v,1) rows");
     if (mxGetM(h0) != r || mxGetN(h0) != T) mexErrMsgIdAndTxt("snmf:dim", "init_h must be r x size(v,2)");
 
-    const int device = (int)opt_scalar(opts, "device", 0);
-    if (!g_ctx || g_device != device) {
-        at_exit();
-        if (snmf_ctx_create(&g_ctx, device) != SNMF_OK) mexErrMsgIdAndTxt("snmf:device", "%s", snmf_last_error());
-        g_device = device;
-        mexLock();  // keep the context (device buffers, kernels) alive between calls
-        mexAtExit(at_exit);
-    }
-
+    // (every argument is checked before the device is touched: a wrong call costs no context)
     snmf_params p;
     std::memset(&p, 0, sizeof p);
     p.F = (int32_t)F;
@@ -142,6 +136,15 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         }
     }
     if (fp64_mode && !devices.empty()) mexErrMsgIdAndTxt("snmf:unsupported", "opts.precision = 'fp64' runs on one device (no opts.devices)");
+
+    const int device = (int)opt_scalar(opts, "device", 0);
+    if (!g_ctx || g_device != device) {
+        at_exit();
+        if (snmf_ctx_create(&g_ctx, device) != SNMF_OK) mexErrMsgIdAndTxt("snmf:device", "%s", snmf_last_error());
+        g_device = device;
+        mexLock();  // keep the context (device buffers, kernels) alive between calls
+        mexAtExit(at_exit);
+    }
     mxArray* hout = devices.empty() ? mxCreateDoubleMatrix((mwSize)r, (mwSize)T, mxREAL) : mxDuplicateArray(h0);
     plhs[0] = devices.empty() ? mxCreateDoubleMatrix((mwSize)F, (mwSize)r, mxREAL) : mxDuplicateArray(w0);
     mxArray* divv = mxCreateDoubleMatrix(1, p.max_iter > 0 ? p.max_iter : 1, mxREAL);
