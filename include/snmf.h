@@ -374,6 +374,28 @@ int snmf_plan_set_mask_f32(snmf_plan* plan, const float* M, int64_t ld, int on_d
 /* v_MDI (:296-306) after snmf_plan_run: F x T, observed entries kept, the rest Nt .* max(w*h, flr). */
 int snmf_plan_get_v_mdi_f64(snmf_plan* plan, double* V, int64_t ld, int on_device);
 int snmf_plan_get_v_mdi_f32(snmf_plan* plan, float* V, int64_t ld, int on_device);
+/* The fp64 mode of the missing-data solves (added within ABI 5: a new entry only): src/snmf_mdi.m:163-306 and
+ * src/snmf_mdi_Sm.m:163-309 in fp64 from end to end, a one-shot call like snmf_sparse_nmf_fp64 and with its kernels.  The
+ * iteration is that entry's (src/sparse_nmf.m:157-286 == src/snmf_mdi.m:163-295) plus three element-wise steps on the mask:
+ * the masked start v = max(v .* M, flr) (:175, in the place of the floor of v: p->floor_v is ignored), the re-imputation
+ * v = max(v .* M + max(w*h, flr) .* (1 - M), flr) after the W step of EVERY iteration (:251-254 / snmf_mdi_Sm.m:251-260;
+ * one pass that also forms the objective of the imputed v, :257-268; with cost_check = 0 the imputation alone), and the
+ * gain-matched final imputation (:296-306 / snmf_mdi_Sm.m:302-309): Nt = sum_f(v .* M) ./ max(sum_f(max(w*h, flr) .* M), flr)
+ * per frame, V_mdi = max(v .* M + Nt .* max(w*h, flr) .* (1 - M), flr).  A frame without an observed entry has Nt = 0: its
+ * entries come out as flr = 1e-9.  After a convergence stop (:281-292) v and w*h are those of the stop iteration.
+ *   V, M     F x T (ldV, ldM >= F), never modified; M: 1 = observed, 0 = missing, or a soft mask in [0, 1]
+ *   W0, H0   F x r and r x T, tight, read-only (init_w, init_h; :116-140)
+ *   sparsity as in snmf_sparse_nmf_fp64 and of all three forms: it carries p.sparsity_mdi, and p->conv_eps p.conv_eps_mdi (:87-93)
+ *   V_mdi    F x T (ldVm >= F);  H r x T;  W F x r or NULL;  div_out, cost_out (max_iter doubles each), n_iter_out: or NULL
+ * Unlike the fp32 missing-data plan (snmf_plan_set_mask_*) it takes any F, T, r the device memory holds, and a solve with
+ * neither factor updated, as the reference does: w*h stays the initial one, the imputation and the gain step run.  A partial
+ * w_update_ind works as in snmf_sparse_nmf_fp64; a partial h_update_ind is SNMF_ERR_DIM.  A NULL V, M, W0, H0, V_mdi or H and a
+ * leading dimension below F are SNMF_ERR_INVALID, a failed allocation is SNMF_ERR_NOMEM; every device block is freed on every
+ * way out and the context stays usable.  Every reduction has a fixed order: two calls on one input give the same bits, and
+ * M == 1 everywhere gives the W, H and objective of snmf_sparse_nmf_fp64 bit for bit. */
+int snmf_mdi_fp64(snmf_ctx* ctx, const snmf_params* p, const double* V, int64_t ldV, const double* M, int64_t ldM,
+                  const double* W0, const double* H0, const double* sparsity, double* V_mdi, int64_t ldVm, double* W,
+                  double* H, double* div_out, double* cost_out, int32_t* n_iter_out);
 
 /* ---- online separation loop (BASELINE config 3) -------------------
  * Device-resident replacement of the per-frame function

@@ -1,11 +1,14 @@
 // snmf_mdi_mex.cpp -- MATLAB MEX shim for the missing-data-imputation variants of the solver
 //     [v_MDI, h, objective] = snmf_mdi(v, Dm, p)       src/snmf_mdi.m:1      (binary mask, 1 = observed)
 //     [v_MDI, h, objective] = snmf_mdi_Sm(v, Sm, p)    src/snmf_mdi_Sm.m:1   (soft mask in [0,1])
-// over the plan API of libsnmf_hip.so (include/snmf.h: snmf_plan_set_mask_f64, snmf_plan_get_v_mdi_f64).
+// over the plan API of libsnmf_hip.so (include/snmf.h: snmf_plan_set_mask_f64, snmf_plan_get_v_mdi_f64), or, with
+// opts.precision = 'fp64', over the one-shot fp64 entry snmf_mdi_fp64.
 //
 //     [v_mdi, w, h, div, cost, n_iter] = snmf_mdi_mex(v, mask, w0, h0, sparsity, opts)
 //   v, mask  F x T double;  w0 F x r (init_w, :116-131);  h0 r x T (init_h, :133-140);  sparsity: scalar (p.sparsity_mdi)
-//   opts     struct: beta, max_iter, conv_eps (p.conv_eps_mdi), cost_check, w_update_ind, h_update_ind (r x 1), device
+//   opts     struct: beta, max_iter, conv_eps (p.conv_eps_mdi), cost_check, w_update_ind, h_update_ind (r x 1), device,
+//            precision ('fp32' default | 'fp64', optional): 'fp64' = the solve in double from end to end (snmf_mdi_fp64: the
+//            kernels of the fp64 solve mode; any F, T, r the device memory holds, also with neither factor updated)
 // No MATLAB wrapper for this shim exists yet (integration/ holds none): the caller applies the defaults of
 // src/snmf_mdi.m:75-164 (sparsity_mdi, conv_eps_mdi, ...) and draws the random factors with MATLAB's own generator, as
 // integration/sparse_nmf.m does for the plain solver, and passes them in.
@@ -54,6 +57,20 @@ static void fill_mask(const mxArray* opts, const char* name, size_t r, std::vect
     }
 }
 
+// the end of both paths: a failed solve destroys the five arrays and raises, else they go to the outputs that were asked for
+static void give(int nlhs, mxArray* plhs[], mxArray* outs[5], int st, int32_t n_iter) {
+    if (st != SNMF_OK) {
+        for (int i = 0; i < 5; ++i) mxDestroyArray(outs[i]);
+        mexErrMsgIdAndTxt("snmf:solve", "%s", snmf_last_error());
+    }
+    plhs[0] = outs[0];
+    for (int i = 1; i < 5; ++i) {
+        if (nlhs > i) plhs[i] = outs[i];
+        else mxDestroyArray(outs[i]);
+    }
+    if (nlhs > 5) plhs[5] = mxCreateDoubleScalar((double)n_iter);
+}
+
 void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     if (snmf_abi_version() != SNMF_ABI_VERSION)  // a stale libsnmf_hip.so must not be driven through newer prototypes
         mexErrMsgIdAndTxt("snmf:abi", "libsnmf_hip.so has ABI version %d, this MEX file was built against %d", snmf_abi_version(), SNMF_ABI_VERSION);
@@ -88,6 +105,17 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     p.w_update_ind = wi.data();
     p.h_update_ind = hi.data();
 
+    // opts.precision = 'fp64': the fp64 missing-data solve; any other string but 'fp32' is an error
+    bool fp64_mode = false;
+    if (const mxArray* pr = mxGetField(opts, 0, "precision")) {
+        if (!mxIsEmpty(pr)) {
+            char prec[16] = "";
+            if (!mxIsChar(pr) || mxGetString(pr, prec, sizeof prec) != 0) mexErrMsgIdAndTxt("snmf:type", "opts.precision must be 'fp32' or 'fp64'");
+            if (std::strcmp(prec, "fp64") == 0) fp64_mode = true;
+            else if (std::strcmp(prec, "fp32") != 0) mexErrMsgIdAndTxt("snmf:type", "opts.precision must be 'fp32' or 'fp64' (got '%s')", prec);
+        }
+    }
+
     // (every argument is checked before the device is touched)
     const int device = (int)opt_scalar(opts, "device", 0);
     if (!g_ctx || g_device != device) {
@@ -96,6 +124,20 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         g_device = device;
         mexLock();
         mexAtExit(at_exit);
+    }
+    if (fp64_mode) {  // one call: the outputs are written where they are returned
+        mxArray* vm = mxCreateDoubleMatrix(F, T, mxREAL);
+        mxArray* wout = mxCreateDoubleMatrix(F, r, mxREAL);
+        mxArray* hout = mxCreateDoubleMatrix(r, T, mxREAL);
+        mxArray* divv = mxCreateDoubleMatrix(1, p.max_iter > 0 ? p.max_iter : 1, mxREAL);
+        mxArray* costv = mxCreateDoubleMatrix(1, p.max_iter > 0 ? p.max_iter : 1, mxREAL);
+        int32_t n_iter = 0;
+        const int st = snmf_mdi_fp64(g_ctx, &p, mxGetDoubles(v), (int64_t)F, mxGetDoubles(mk), (int64_t)F, mxGetDoubles(w0), mxGetDoubles(h0),
+                                     nullptr, mxGetDoubles(vm), (int64_t)F, mxGetDoubles(wout), mxGetDoubles(hout), mxGetDoubles(divv),
+                                     mxGetDoubles(costv), &n_iter);
+        mxArray* outs[5] = {vm, wout, hout, divv, costv};
+        give(nlhs, plhs, outs, st, n_iter);
+        return;
     }
     snmf_plan* pl = nullptr;
     if (snmf_plan_create(g_ctx, &p, &pl) != SNMF_OK) mexErrMsgIdAndTxt("snmf:plan", "%s", snmf_last_error());
@@ -120,14 +162,5 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     STEP(snmf_plan_get_objective(pl, mxGetDoubles(divv), mxGetDoubles(costv), &n_iter));
     snmf_plan_destroy(pl);
     mxArray* outs[5] = {vm, wout, hout, divv, costv};
-    if (st != SNMF_OK) {
-        for (mxArray* a : outs) mxDestroyArray(a);
-        mexErrMsgIdAndTxt("snmf:solve", "%s", snmf_last_error());
-    }
-    plhs[0] = vm;
-    for (int i = 1; i < 5; ++i) {
-        if (nlhs > i) plhs[i] = outs[i];
-        else mxDestroyArray(outs[i]);
-    }
-    if (nlhs > 5) plhs[5] = mxCreateDoubleScalar((double)n_iter);
+    give(nlhs, plhs, outs, st, n_iter);
 }

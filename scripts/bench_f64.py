@@ -22,6 +22,13 @@ of the whole call, transfers included (that is what the resident form saves), mi
 outside the timed region.  One JSON line per leg is appended to profiles/train_f64_bench.jsonl.
 
     python scripts/bench_f64.py --legs dnmf,mel [--dnmf-iters 50] [--reps 2]
+
+--legs mdi: the fp64 missing-data solve (snmf_mdi(..., precision="fp64"): snmf_mdi_fp64) next to the plain fp64 solve at a11,
+binary mask with 30 % of the entries missing, by the same difference of two calls, each the minimum over --reps; the two
+solves alternate inside every repetition, so that another job on the machine falls on both.  One JSON line is appended to
+profiles/mdi_f64_bench.jsonl.
+
+    python scripts/bench_f64.py --legs mdi [--n64 20,120] [--reps 5]
 """
 import argparse
 import json
@@ -80,9 +87,43 @@ def dnmf_legs(a):
         print(json.dumps(line), flush=True)
 
 
+def mdi_leg(a):
+    from bench import SPARSITY, make_problem
+    from se_snmf_nat_amd import Context, snmf_mdi, sparse_nmf
+    ctx = Context(0)
+    out = os.path.join(ROOT, "profiles", "mdi_f64_bench.jsonl") if a.out.endswith("solve_f64_bench.jsonl") else a.out
+    F, T, r = SHAPES["a11"]
+    V, W0, H0 = make_problem(F, T, r)
+    V = np.asfortranarray(V.astype(np.float32).astype(np.float64))
+    H0 = H0.astype(np.float32).astype(np.float64)
+    M = np.asfortranarray(np.random.RandomState(0).rand(F, T) > 0.3, dtype=np.float64)
+    n1, n2 = (int(x) for x in a.n64.split(","))
+    base = dict(cf="kl", conv_eps=0, conv_eps_mdi=0, sparsity=SPARSITY, sparsity_mdi=SPARSITY, init_w=W0, init_h=H0, cost_check=1)
+    solves = {"plain": lambda n: sparse_nmf(V, dict(base, max_iter=n), ctx=ctx, precision="fp64"),
+              "mdi": lambda n: snmf_mdi(V, M, dict(base, max_iter=n), ctx=ctx, precision="fp64")}
+    for fn in solves.values():
+        fn(1)  # warm-up: allocations, code load
+    best = {}
+    for _ in range(a.reps):
+        for n in (n1, n2):
+            for k, fn in solves.items():
+                t0 = time.perf_counter()
+                fn(n)
+                best[k, n] = min(best.get((k, n), float("inf")), time.perf_counter() - t0)
+    line = dict(leg="mdi", F=F, T=T, r=r, cf="kl", sparsity=SPARSITY, missing=float(1 - M.mean()), n1=n1, n2=n2, reps=a.reps)
+    for k in solves:
+        spi = (best[k, n2] - best[k, n1]) / (n2 - n1)
+        line[k] = dict(t_n1_s=round(best[k, n1], 4), t_n2_s=round(best[k, n2], 4), s_per_iter=spi, iter_per_s=1.0 / spi)
+        print(f"a11 fp64 {k}: {1.0 / spi:.2f} iterations/s ({spi * 1e3:.2f} ms per iteration)", flush=True)
+    line["mdi_over_plain"] = line["mdi"]["iter_per_s"] / line["plain"]["iter_per_s"]
+    with open(out, "a") as f:
+        f.write(json.dumps(line) + "\n")
+    print(json.dumps(line), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--legs", default="", help="dnmf,mel: the resident fp64 DNMF loop instead of the one-shot shapes")
+    ap.add_argument("--legs", default="", help="dnmf,mel: the resident fp64 DNMF loop instead of the one-shot shapes; mdi: the fp64 missing-data solve")
     ap.add_argument("--dnmf-iters", type=int, default=50)
     ap.add_argument("--shapes", default="c2,a11")
     ap.add_argument("--n64", default="20,120", help="N1,N2 of the fp64 calls")
@@ -91,6 +132,8 @@ def main():
     ap.add_argument("--f64-mfma-tflops", type=float, default=None)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "solve_f64_bench.jsonl"))
     a = ap.parse_args()
+    if a.legs == "mdi":
+        return mdi_leg(a)
     if a.legs:
         return dnmf_legs(a)
     from bench import SPARSITY, make_problem

@@ -81,7 +81,7 @@ SYMBOLS = [
     "snmf_run_basis_train_audio_f64", "snmf_ctx_xfer_stats", "snmf_sparse_nmf_oop_f64", "snmf_sparse_nmf_oop_f32",
     "snmf_run_basis_dnmf_multi_f64", "snmf_run_basis_dnmf_multi_f32",
     "snmf_multi_release_cache", "snmf_multi_cached_teams",
-    "snmf_sparse_nmf_fp64",
+    "snmf_sparse_nmf_fp64", "snmf_mdi_fp64",
     "snmf_stft_features_fp64", "snmf_mel_features_fp64", "snmf_tf_dd_fp64",
     "snmf_run_basis_dnmf_fp64", "snmf_run_basis_dnmf_audio_fp64", "snmf_run_basis_train_audio_fp64",
     "snmf_rccl_available", "snmf_rccl_get_unique_id", "snmf_rccl_comm_create", "snmf_rccl_comm_destroy", "snmf_plan_run_sharded_rccl",
@@ -338,6 +338,7 @@ def load():
     for ty in ("f64", "f32"):
         sig[f"snmf_sparse_nmf_oop_{ty}"] = (C.c_int, [vp, PP, vp, i64, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i32)])
     sig["snmf_sparse_nmf_fp64"] = (C.c_int, [vp, PP, vp, i64, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i32)])
+    sig["snmf_mdi_fp64"] = (C.c_int, [vp, PP, vp, i64, vp, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp, C.POINTER(i32)])
     # the fp64 mode of the front-end and of the training callers: the prototypes of the fp32 / f64 namesakes, doubles throughout
     for nm in ("snmf_stft_features", "snmf_mel_features", "snmf_tf_dd"):
         sig[nm + "_fp64"] = sig[nm + "_f32"]

@@ -452,10 +452,13 @@ def _run_basis_dnmf_resident(Y, X, D, B, R_x, R_d, p, *, ctx, dtype, h0, want_a=
     return B_hat, A_hat
 
 
-def dnmf_adapt(Y, D, B, p, *, ctx=None, dtype=np.float64):
+def dnmf_adapt(Y, D, B, p, *, ctx=None, dtype=np.float64, precision="fp32"):
     """B_a = DNMF_adapt(Y, D, B, p) -- src/DNMF_adapt.m:1-20: activations of the mixture features Y on the fixed
     dictionary B = [B_x, B_d] (:4-7), then the noise columns re-trained on the noise features D with those
-    activations fixed (:16-20).  p carries R_x, R_d and the solver fields."""
+    activations fixed (:16-20).  p carries R_x, R_d and the solver fields.
+    precision: "fp32" (default) or "fp64" = both solves as sparse_nmf(..., precision="fp64"), under its rules (dtype=np.float64,
+    SnmfError status 1 otherwise); any other string is a ValueError."""
+    _check_precision(precision)
     p = dict(p)
     R_x, R_d = int(p["R_x"]), int(p["R_d"])
     B = np.asarray(B, dtype=np.float64)
@@ -463,12 +466,12 @@ def dnmf_adapt(Y, D, B, p, *, ctx=None, dtype=np.float64):
     p["h_update_ind"] = np.ones(R_x + R_d, bool)  # :5
     p["init_w"] = B  # :6
     p.pop("init_h", None)
-    _, A_hat, _ = sparse_nmf(Y, p, ctx=ctx, dtype=dtype)  # :7
+    _, A_hat, _ = sparse_nmf(Y, p, ctx=ctx, dtype=dtype, precision=precision)  # :7
     p["w_update_ind"] = np.ones(R_d, bool)  # :16
     p["h_update_ind"] = np.zeros(R_d, bool)  # :17
     p["init_w"] = B[:, R_x:R_x + R_d]  # :18
     p["init_h"] = A_hat[R_x:R_x + R_d, :]  # :19
-    B_a, _, _ = sparse_nmf(D, p, ctx=ctx, dtype=dtype)  # :20
+    B_a, _, _ = sparse_nmf(D, p, ctx=ctx, dtype=dtype, precision=precision)  # :20
     return B_a
 
 
@@ -731,7 +734,7 @@ class Plan:
             pass
 
 
-def _mdi(v, mask, p, *, ctx, dtype, rng):
+def _mdi(v, mask, p, *, ctx, dtype, rng, precision="fp32", info=None):
     """Shared body of snmf_mdi / snmf_mdi_Sm: src/snmf_mdi.m:71-312 (the two files differ only in how the
     mask argument is named and complemented; `.*~Dm` equals `.*(1-Sm)` for a 0/1 mask)."""
     p = dict(p or {})
@@ -772,6 +775,10 @@ def _mdi(v, mask, p, *, ctx, dtype, rng):
         if h0.shape != (r, n):
             raise SnmfError(3, "init_h must be r x n")
     w_ind, h_ind = _mask(p, "w_update_ind", r), _mask(p, "h_update_ind", r)
+    _check_precision(precision)  # (after the reference's own errors, before any device work)
+    if precision == "fp64":
+        _fp64_rules(dt, None, "the fp64 missing-data solve")
+        return _mdi_fp64(v, mask, p, w0, h0, w_ind, h_ind, beta, max_iter, ctx, info)
     plan = Plan(ctx or default_context(), m, n, r, beta=beta, max_iter=max_iter, conv_eps=float(p["conv_eps_mdi"]),
                 cost_check=bool(p["cost_check"]), floor_v=True, sparsity=p["sparsity_mdi"], w_update_ind=w_ind,
                 h_update_ind=h_ind)
@@ -786,17 +793,53 @@ def _mdi(v, mask, p, *, ctx, dtype, rng):
         h = plan.get_h(dtype=dt)
         div, cost, nn = plan.get_objective()
         stopped = plan.stopped()
+        if info is not None:
+            info["w"] = plan.get_w(dtype=dt)
     finally:
         plan.close()
     k = nn if stopped else max_iter  # :286-287 truncation on convergence only
     return v_mdi, h, {"div": div[:k], "cost": cost[:k], "n_iter": n_it}
 
 
-def snmf_mdi(v, Dm, p=None, *, ctx=None, dtype=np.float64, rng=None):
-    """[v_MDI, h, objective] = snmf_mdi(v, Dm, p)  -- src/snmf_mdi.m:1 (Dm: 1 = observed, 0 = missing)."""
-    return _mdi(v, np.asarray(Dm) != 0, p, ctx=ctx, dtype=dtype, rng=rng)
+def _mdi_fp64(v, mask, p, w0, h0, w_ind, h_ind, beta, max_iter, ctx, info):
+    """The fp64 mode of _mdi: one call of snmf_mdi_fp64 (include/snmf.h) on the factors and masks _mdi has prepared."""
+    dt = np.dtype(np.float64)
+    m, n = v.shape
+    if w0.ndim != 2 or w0.shape[0] != m:
+        raise SnmfError(3, f"init_w is {w0.shape}, v has {m} rows")
+    r = w0.shape[1]
+    kind, scalar, sarr = _sparsity_form(p["sparsity_mdi"], r, n, dt)
+    sp = _make_params(m, n, r, beta, max_iter, float(p["conv_eps_mdi"]), bool(p["cost_check"]), True, kind, scalar, w_ind, h_ind)
+    vv, mm = _colmajor(v, dt), _colmajor(mask, dt)
+    W0c, H0c = np.asfortranarray(w0, dtype=dt), np.asfortranarray(h0, dtype=dt)
+    v_mdi = np.empty((m, n), dtype=dt, order="F")
+    W = np.empty((m, r), dtype=dt, order="F")
+    H = np.empty((r, n), dtype=dt, order="F")
+    div, cost = np.zeros(max(max_iter, 1)), np.zeros(max(max_iter, 1))
+    n_iter = C.c_int32(0)
+    ld = lambda M: M.strides[1] // dt.itemsize if n > 1 else m
+    lib = _lib.load()
+    ctx = ctx or default_context()
+    _lib.check(lib.snmf_mdi_fp64(ctx._h, C.byref(sp), _ptr(vv), ld(vv), _ptr(mm), ld(mm), _ptr(W0c), _ptr(H0c),
+                                 _ptr(sarr) if sarr is not None else None, _ptr(v_mdi), m, _ptr(W), _ptr(H), _ptr(div), _ptr(cost),
+                                 C.byref(n_iter)))
+    ni = n_iter.value
+    if info is not None:
+        info["w"] = W
+    k = ni if ni < max_iter else max_iter  # :286-287 truncation on convergence only
+    return v_mdi, H, {"div": div[:k].copy(), "cost": cost[:k].copy(), "n_iter": ni}
 
 
-def snmf_mdi_Sm(v, Sm, p=None, *, ctx=None, dtype=np.float64, rng=None):
-    """[v_MDI, h, objective] = snmf_mdi_Sm(v, Sm, p)  -- src/snmf_mdi_Sm.m:1 (soft mask in [0,1])."""
-    return _mdi(v, Sm, p, ctx=ctx, dtype=dtype, rng=rng)
+def snmf_mdi(v, Dm, p=None, *, ctx=None, dtype=np.float64, rng=None, precision="fp32", info=None):
+    """[v_MDI, h, objective] = snmf_mdi(v, Dm, p)  -- src/snmf_mdi.m:1 (Dm: 1 = observed, 0 = missing).
+
+    precision: "fp32" (default) = the fused fp32 kernels (F, r within their 32-frame images; at least one factor updated);
+    "fp64" = snmf_mdi_fp64: the solve in double from end to end, within ~1e-14 of a host fp64 evaluation, bit-reproducible, any
+    F, T, r the device memory holds, also with neither factor updated.  "fp64" needs dtype=np.float64 (SnmfError status 1
+    otherwise); any other string is a ValueError.  info: a dict that receives info["w"], the dictionary of the solve."""
+    return _mdi(v, np.asarray(Dm) != 0, p, ctx=ctx, dtype=dtype, rng=rng, precision=precision, info=info)
+
+
+def snmf_mdi_Sm(v, Sm, p=None, *, ctx=None, dtype=np.float64, rng=None, precision="fp32", info=None):
+    """[v_MDI, h, objective] = snmf_mdi_Sm(v, Sm, p)  -- src/snmf_mdi_Sm.m:1 (soft mask in [0,1]).  precision, info: as in snmf_mdi."""
+    return _mdi(v, Sm, p, ctx=ctx, dtype=dtype, rng=rng, precision=precision, info=info)

@@ -246,6 +246,36 @@ static __global__ __launch_bounds__(256) void k_s64_floor(double* __restrict__ X
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) X[i] = fmax(X[i], kS64Flr);
 }
 
+// d + one element's divergence term (src/sparse_nmf.m:248-258); the one expression of k_s64_obj and k_s64_mdi_obj
+template <int MODE>
+__device__ __forceinline__ double s64_div_add(double d, double v, double lam, double beta) {
+    if (MODE == S64_KL) {
+        d += v * log(v / lam) - v + lam;
+    } else if (MODE == S64_ED) {
+        d += (v - lam) * (v - lam);
+    } else if (MODE == S64_IS) {
+        const double qq = v / lam;
+        d += qq - log(qq) - 1.0;
+    } else {
+        d += pow(v, beta) + (beta - 1.0) * pow(lam, beta) - beta * v * pow(lam, beta - 1.0);
+    }
+    return d;
+}
+
+// sum(sparsity .* h) of :261 over the elements of workgroup b, then both workgroup sums into part[2 b] and part[2 b + 1]
+__device__ __forceinline__ void s64_obj_tail(double d, const double* __restrict__ H, int kind, double scalar, const double* __restrict__ S,
+                                             int r, long long n_h, double* __restrict__ part, double* red) {
+    double sh = 0.0;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n_h; i += (long long)gridDim.x * 256)
+        sh += s64_sparsity(kind, scalar, S, i, (int)(i % r)) * H[i];
+    d = s64_block_sum(d, red);
+    sh = s64_block_sum(sh, red);
+    if (threadIdx.x == 0) {
+        part[2 * blockIdx.x] = d;
+        part[2 * blockIdx.x + 1] = sh;
+    }
+}
+
 // The divergence terms of src/sparse_nmf.m:248-258 and sum(sparsity .* h) of :261: workgroup b sums its elements (a fixed
 // assignment: grid-stride from b) into part[2 b] and part[2 b + 1].
 template <int MODE>
@@ -254,27 +284,73 @@ __global__ __launch_bounds__(256) void k_s64_obj(const double* __restrict__ V, c
                                                  int r, long long n_h, double* __restrict__ part, const int* stop) {
     if (*stop) return;
     __shared__ double red[256];
-    double d = 0.0, sh = 0.0;
+    double d = 0.0;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n_v; i += (long long)gridDim.x * 256)
+        d = s64_div_add<MODE>(d, V[i], Lam[i], beta);
+    s64_obj_tail(d, H, kind, scalar, S, r, n_h, part, red);
+}
+
+// ---- the missing-data steps (src/snmf_mdi.m / src/snmf_mdi_Sm.m; M is F x T, 1 = observed, soft masks lie in [0, 1]) ----
+// the masked start v = max(v .* M, flr) (src/snmf_mdi.m:175), in the place of k_s64_floor
+static __global__ __launch_bounds__(256) void k_s64_mdi_start(double* __restrict__ V, const double* __restrict__ M, long long n) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) V[i] = fmax(V[i] * M[i], kS64Flr);
+}
+
+// one element of the re-imputation v = max(v .* M + lam .* (1 - M), flr) (:251-254 / snmf_mdi_Sm.m:251-260); M = 1 gives v
+// and M = 0 gives lam, both exactly
+__device__ __forceinline__ double s64_impute(double v, double m, double lam) { return fmax(v * m + lam * (1.0 - m), kS64Flr); }
+
+// The re-imputation of every iteration fused with the objective of the imputed v (:257-268): V is read once and written
+// once, and the partials have the element assignment, the workgroup tree and the slots of k_s64_obj -- with M = 1 the
+// objective is the plain solve's bit for bit.  Lam is the max(w * h, flr) the last product left: the reference's v_est.
+template <int MODE>
+__global__ __launch_bounds__(256) void k_s64_mdi_obj(double* __restrict__ V, const double* __restrict__ M, const double* __restrict__ Lam,
+                                                     long long n_v, double beta, const double* __restrict__ H, int kind, double scalar,
+                                                     const double* __restrict__ S, int r, long long n_h, double* __restrict__ part,
+                                                     const int* stop) {
+    if (*stop) return;
+    __shared__ double red[256];
+    double d = 0.0;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n_v; i += (long long)gridDim.x * 256) {
-        const double v = V[i], lam = Lam[i];
-        if (MODE == S64_KL) {
-            d += v * log(v / lam) - v + lam;
-        } else if (MODE == S64_ED) {
-            d += (v - lam) * (v - lam);
-        } else if (MODE == S64_IS) {
-            const double qq = v / lam;
-            d += qq - log(qq) - 1.0;
-        } else {
-            d += pow(v, beta) + (beta - 1.0) * pow(lam, beta) - beta * v * pow(lam, beta - 1.0);
-        }
+        const double lam = Lam[i], v = s64_impute(V[i], M[i], lam);
+        V[i] = v;
+        d = s64_div_add<MODE>(d, v, lam, beta);
     }
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n_h; i += (long long)gridDim.x * 256)
-        sh += s64_sparsity(kind, scalar, S, i, (int)(i % r)) * H[i];
-    d = s64_block_sum(d, red);
-    sh = s64_block_sum(sh, red);
-    if (threadIdx.x == 0) {
-        part[2 * blockIdx.x] = d;
-        part[2 * blockIdx.x + 1] = sh;
+    s64_obj_tail(d, H, kind, scalar, S, r, n_h, part, red);
+}
+
+// cost_check = 0: the re-imputation alone
+static __global__ __launch_bounds__(256) void k_s64_mdi_impute(double* __restrict__ V, const double* __restrict__ M,
+                                                               const double* __restrict__ Lam, long long n, const int* stop) {
+    if (*stop) return;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) V[i] = s64_impute(V[i], M[i], Lam[i]);
+}
+
+// The gain-matched final imputation (:296-306 / snmf_mdi_Sm.m:302-309), one wave per frame t (four frames a workgroup):
+//   a = sum_f v .* M, b = sum_f lam .* M, Nt = a / max(b, flr),   v_mdi = max(v .* M + Nt .* lam .* (1 - M), flr)
+// Lane l sums the rows l, l + 64, ... in row order and the 64 lane sums meet in a fixed butterfly, so the result depends on
+// neither the grid nor the timing; the second pass finds the frame in the cache.  Runs after the loop: no stop test.
+// Vm may be V itself (every element is read and then written by the same lane).
+static __global__ __launch_bounds__(256) void k_s64_mdi_final(const double* V, const double* __restrict__ M, const double* __restrict__ Lam,
+                                                              int F, long long T, double* Vm) {
+    const int lane = threadIdx.x & 63;
+    for (long long t = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); t < T; t += (long long)gridDim.x * 4) {  // (wave-uniform)
+        const long long o = t * F;
+        double a = 0.0, b = 0.0;
+        for (int f = lane; f < F; f += 64) {
+            const double m = M[o + f];
+            a += V[o + f] * m;
+            b += Lam[o + f] * m;
+        }
+        for (int s = 32; s > 0; s >>= 1) {
+            a += __shfl_xor(a, s, 64);
+            b += __shfl_xor(b, s, 64);
+        }
+        const double nt = a / fmax(b, kS64Flr);
+        for (int f = lane; f < F; f += 64) {
+            const double m = M[o + f];
+            Vm[o + f] = fmax(V[o + f] * m + nt * Lam[o + f] * (1.0 - m), kS64Flr);
+        }
     }
 }
 

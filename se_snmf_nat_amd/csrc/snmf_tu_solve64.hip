@@ -1,5 +1,6 @@
 // snmf_tu_solve64.hip -- the fp64 solve mode, kernels in snmf_solve64.h: solve64_core runs one solve on device pointers
-// with a workspace of the caller's, snmf_sparse_nmf_fp64 is allocation, upload and download around it.  A translation
+// with a workspace of the caller's, snmf_sparse_nmf_fp64 is allocation, upload and download around it; solve64_mdi_core and
+// snmf_mdi_fp64 are the same two with a mask (the missing-data solve of src/snmf_mdi.m / src/snmf_mdi_Sm.m).  A translation
 // unit of its own: the fp32 plan, its kernels and its geometry are not touched, and compile to the code they compiled to before.
 #include "snmf_internal.h"
 #include "snmf_solve64.h"
@@ -83,6 +84,15 @@ template <int MODE>
 int obj64(const Solve64& s, const double* V, const double* Lam, long long n_v, double beta, const double* H, int kind, double scalar,
           const double* S, int r, long long n_h, double* part) {
     hipLaunchKernelGGL(k_s64_obj<MODE>, dim3(kS64Blocks), dim3(256), 0, s.st, V, Lam, n_v, beta, H, kind, scalar, S, r, n_h, part, s.stop);
+    HIP_TRY(hipGetLastError());
+    return SNMF_OK;
+}
+
+// the re-imputation of src/snmf_mdi.m:251-254 with the objective of :257-268 in the same pass
+template <int MODE>
+int mdi_obj64(const Solve64& s, double* V, const double* M, const double* Lam, long long n_v, double beta, const double* H, int kind,
+              double scalar, const double* S, int r, long long n_h, double* part) {
+    hipLaunchKernelGGL(k_s64_mdi_obj<MODE>, dim3(kS64Blocks), dim3(256), 0, s.st, V, M, Lam, n_v, beta, H, kind, scalar, S, r, n_h, part, s.stop);
     HIP_TRY(hipGetLastError());
     return SNMF_OK;
 }
@@ -183,8 +193,11 @@ int solve64_ws_bytes(const snmf_params* p, size_t* bytes) {
     return SNMF_OK;
 }
 
-int solve64_core(snmf_ctx* ctx, const snmf_params* p, double* dV, double* dW, double* dH, const double* dS, void* ws, size_t ws_bytes,
-                 double* div_out, double* cost_out, int32_t* n_iter_out) {
+namespace {
+
+// The one body of solve64_core (dM == nullptr: the launches of the plain solve, nothing else) and solve64_mdi_core.
+int solve64_run(snmf_ctx* ctx, const snmf_params* p, double* dV, const double* dM, double* dW, double* dH, const double* dS, void* ws,
+                size_t ws_bytes, double* dVm, double* div_out, double* cost_out, int32_t* n_iter_out) {
     Shape64 sh;
     SN_TRY(shape64(p, &sh));
     const int F = p->F, T = p->T, r = p->r, max_iter = p->max_iter, kind = p->sparsity_kind;
@@ -218,7 +231,10 @@ int solve64_core(snmf_ctx* ctx, const snmf_params* p, double* dV, double* dW, do
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_s64_hscale, dim3(grid64(nRT)), dim3(256), 0, st, dH, dwn, r, nRT);
     HIP_TRY(hipGetLastError());
-    if (p->floor_v) {
+    if (dM) {  // src/snmf_mdi.m:175, the masked start (it floors: floor_v has no meaning here)
+        hipLaunchKernelGGL(k_s64_mdi_start, dim3(grid64(nFT)), dim3(256), 0, st, dV, dM, nFT);
+        HIP_TRY(hipGetLastError());
+    } else if (p->floor_v) {
         hipLaunchKernelGGL(k_s64_floor, dim3(grid64(nFT)), dim3(256), 0, st, dV, nFT);
         HIP_TRY(hipGetLastError());
     }
@@ -266,12 +282,25 @@ int solve64_core(snmf_ctx* ctx, const snmf_params* p, double* dV, double* dW, do
             HIP_TRY(hipGetLastError());
             SN_TRY(lam());
         }
+        if (dM && !p->cost_check) {  // src/snmf_mdi.m:251-254: v is re-imputed in every iteration, objective or not
+            hipLaunchKernelGGL(k_s64_mdi_impute, dim3(grid64(nFT)), dim3(256), 0, st, dV, dM, dLam, nFT, s.stop);
+            HIP_TRY(hipGetLastError());
+        }
         if (p->cost_check) {  // :248-284
-            switch (mode) {
-                case S64_KL: SN_TRY((obj64<S64_KL>(s, dV, dLam, nFT, beta, dH, kind, scalar, dS, r, nRT, dpart))); break;
-                case S64_ED: SN_TRY((obj64<S64_ED>(s, dV, dLam, nFT, beta, dH, kind, scalar, dS, r, nRT, dpart))); break;
-                case S64_IS: SN_TRY((obj64<S64_IS>(s, dV, dLam, nFT, beta, dH, kind, scalar, dS, r, nRT, dpart))); break;
-                default: SN_TRY((obj64<S64_GEN>(s, dV, dLam, nFT, beta, dH, kind, scalar, dS, r, nRT, dpart))); break;
+            if (dM) {
+                switch (mode) {  // (the re-imputation and the objective of the imputed v in one pass)
+                    case S64_KL: SN_TRY((mdi_obj64<S64_KL>(s, dV, dM, dLam, nFT, beta, dH, kind, scalar, dS, r, nRT, dpart))); break;
+                    case S64_ED: SN_TRY((mdi_obj64<S64_ED>(s, dV, dM, dLam, nFT, beta, dH, kind, scalar, dS, r, nRT, dpart))); break;
+                    case S64_IS: SN_TRY((mdi_obj64<S64_IS>(s, dV, dM, dLam, nFT, beta, dH, kind, scalar, dS, r, nRT, dpart))); break;
+                    default: SN_TRY((mdi_obj64<S64_GEN>(s, dV, dM, dLam, nFT, beta, dH, kind, scalar, dS, r, nRT, dpart))); break;
+                }
+            } else {
+                switch (mode) {
+                    case S64_KL: SN_TRY((obj64<S64_KL>(s, dV, dLam, nFT, beta, dH, kind, scalar, dS, r, nRT, dpart))); break;
+                    case S64_ED: SN_TRY((obj64<S64_ED>(s, dV, dLam, nFT, beta, dH, kind, scalar, dS, r, nRT, dpart))); break;
+                    case S64_IS: SN_TRY((obj64<S64_IS>(s, dV, dLam, nFT, beta, dH, kind, scalar, dS, r, nRT, dpart))); break;
+                    default: SN_TRY((obj64<S64_GEN>(s, dV, dLam, nFT, beta, dH, kind, scalar, dS, r, nRT, dpart))); break;
+                }
             }
             hipLaunchKernelGGL(k_s64_stop, dim3(1), dim3(256), 0, st, dpart, kS64Blocks, it, p->conv_eps, div_scale, ddiv, dcost, dst);
             HIP_TRY(hipGetLastError());
@@ -282,6 +311,11 @@ int solve64_core(snmf_ctx* ctx, const snmf_params* p, double* dV, double* dW, do
             }
         }
     }
+    if (dM) {  // src/snmf_mdi.m:296-306: V and Lam are those of the last iteration that ran (the stop iteration after a stop)
+        const long long groups = ((long long)T + 3) / 4;  // a wave per frame
+        hipLaunchKernelGGL(k_s64_mdi_final, dim3((unsigned)std::min<long long>(groups, 65536)), dim3(256), 0, st, dV, dM, dLam, F, (long long)T, dVm);
+        HIP_TRY(hipGetLastError());
+    }
     HIP_TRY(hipMemcpyAsync(&h_state, dst, sizeof(h_state), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     std::vector<double> hd(std::max(max_iter, 1)), hc(std::max(max_iter, 1));
@@ -291,6 +325,19 @@ int solve64_core(snmf_ctx* ctx, const snmf_params* p, double* dV, double* dW, do
     if (cost_out) std::copy(hc.begin(), hc.begin() + max_iter, cost_out);
     if (n_iter_out) *n_iter_out = h_state.stop ? h_state.n_iter : max_iter;
     return SNMF_OK;
+}
+
+}  // namespace
+
+int solve64_core(snmf_ctx* ctx, const snmf_params* p, double* dV, double* dW, double* dH, const double* dS, void* ws, size_t ws_bytes,
+                 double* div_out, double* cost_out, int32_t* n_iter_out) {
+    return solve64_run(ctx, p, dV, nullptr, dW, dH, dS, ws, ws_bytes, nullptr, div_out, cost_out, n_iter_out);
+}
+
+int solve64_mdi_core(snmf_ctx* ctx, const snmf_params* p, double* dV, const double* dM, double* dW, double* dH, const double* dS, void* ws,
+                     size_t ws_bytes, double* dVm, double* div_out, double* cost_out, int32_t* n_iter_out) {
+    if (!dM || !dVm) return fail(SNMF_ERR_INTERNAL, "fp64 missing-data solve: no mask or no output");
+    return solve64_run(ctx, p, dV, dM, dW, dH, dS, ws, ws_bytes, dVm, div_out, cost_out, n_iter_out);
 }
 
 // the one-shot entry: allocation, upload and download around solve64_core
@@ -329,6 +376,56 @@ extern "C" int snmf_sparse_nmf_fp64(snmf_ctx* ctx, const snmf_params* p, const d
     if (n_s) HIP_TRY(hipMemcpyAsync(dS, sparsity, n_s * 8, hipMemcpyHostToDevice, st));
     SN_TRY(solve64_core(ctx, p, dV, dW, dH, dS, ws, ws_bytes, div_out, cost_out, n_iter_out));
     HIP_TRY(hipMemcpyAsync(W, dW, (size_t)nFR * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(H, dH, (size_t)nRT * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return SNMF_OK;
+}
+
+// the one-shot missing-data entry: allocation, upload and download around solve64_mdi_core
+extern "C" int snmf_mdi_fp64(snmf_ctx* ctx, const snmf_params* p, const double* V, int64_t ldV, const double* M, int64_t ldM,
+                             const double* W0, const double* H0, const double* sparsity, double* V_mdi, int64_t ldVm, double* W,
+                             double* H, double* div_out, double* cost_out, int32_t* n_iter_out) {
+    if (!ctx) return fail(SNMF_ERR_INVALID, "ctx is NULL");
+    if (!V || !M || !W0 || !H0 || !V_mdi || !H) return fail(SNMF_ERR_INVALID, "V, M, W0, H0, V_mdi and H must be non-NULL");
+    size_t ws_bytes = 0;
+    SN_TRY(solve64_ws_bytes(p, &ws_bytes));
+    const int F = p->F, T = p->T, r = p->r;
+    if (ldV < F || ldM < F || ldVm < F)
+        return fail(SNMF_ERR_INVALID, "ldV = %lld, ldM = %lld, ldVm = %lld: each must be at least F = %d", (long long)ldV, (long long)ldM, (long long)ldVm, F);
+    const int kind = p->sparsity_kind;
+    if (kind != SNMF_SPARSITY_SCALAR && !sparsity) return fail(SNMF_ERR_INVALID, "sparsity array required for this sparsity_kind");
+
+    (void)hipGetLastError();
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    Blocks64 mem;
+    mem.st = st;
+    const long long nFT = (long long)F * T, nRT = (long long)r * T, nFR = (long long)F * r;
+    double *dV, *dM, *dW, *dH, *dS = nullptr;
+    void* ws;
+    SN_TRY(mem.get(&dV, nFT));
+    SN_TRY(mem.get(&dM, nFT));
+    SN_TRY(mem.get(&dW, nFR));
+    SN_TRY(mem.get(&dH, nRT));
+    const size_t n_s = kind == SNMF_SPARSITY_SCALAR ? 0 : (kind == SNMF_SPARSITY_RVEC ? (size_t)r : (size_t)nRT);
+    if (n_s) SN_TRY(mem.get(&dS, n_s));
+    SN_TRY(mem.get_bytes(&ws, ws_bytes));
+
+    // upload (tight column-major on the device)
+    auto up = [&](double* d, const double* h, int64_t ld) {
+        if (ld == F || T == 1) return hipMemcpyAsync(d, h, (size_t)nFT * 8, hipMemcpyHostToDevice, st);
+        return hipMemcpy2DAsync(d, (size_t)F * 8, h, (size_t)ld * 8, (size_t)F * 8, (size_t)T, hipMemcpyHostToDevice, st);
+    };
+    HIP_TRY(up(dV, V, ldV));
+    HIP_TRY(up(dM, M, ldM));
+    HIP_TRY(hipMemcpyAsync(dW, W0, (size_t)nFR * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dH, H0, (size_t)nRT * 8, hipMemcpyHostToDevice, st));
+    if (n_s) HIP_TRY(hipMemcpyAsync(dS, sparsity, n_s * 8, hipMemcpyHostToDevice, st));
+    // (v_MDI takes the place of the imputed v: the last kernel reads and writes each element in one lane)
+    SN_TRY(solve64_mdi_core(ctx, p, dV, dM, dW, dH, dS, ws, ws_bytes, dV, div_out, cost_out, n_iter_out));
+    if (ldVm == F || T == 1) HIP_TRY(hipMemcpyAsync(V_mdi, dV, (size_t)nFT * 8, hipMemcpyDeviceToHost, st));
+    else HIP_TRY(hipMemcpy2DAsync(V_mdi, (size_t)ldVm * 8, dV, (size_t)F * 8, (size_t)F * 8, (size_t)T, hipMemcpyDeviceToHost, st));
+    if (W) HIP_TRY(hipMemcpyAsync(W, dW, (size_t)nFR * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(H, dH, (size_t)nRT * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return SNMF_OK;
