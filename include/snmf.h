@@ -707,6 +707,58 @@ int snmf_run_basis_dnmf_multi_f32(const int32_t* devices, int32_t n_dev, const s
                                   const float* B, int64_t ldB, const float* H0, uint64_t seed, float* B_hat, int64_t ldBh,
                                   float* A_hat, int64_t ldA, int32_t* n_iter_out);
 
+/* ---- batched offline solve: many independent factorizations in shared launches ----------- */
+/* Added within 5 (new entries only).  B independent problems V_b ~ W_b * H_b -- src/sparse_nmf.m:157-286 each -- advance in
+ * SHARED launches: per iteration one H step over every (problem, 32-frame tile), one W-statistics launch over every
+ * (problem, 256-frame chunk) and one finish launch over every (problem, column of W).  A solve of a few hundred to a few
+ * thousand frames fills a quarter of the device and is bound by its three launch boundaries per iteration; a batch of them
+ * is not ("Batched offline solve", has the measured table).  Shared by the batch: F, r and one snmf_params with
+ * the meaning its fields have in snmf_sparse_nmf_f64 (every beta; sparsity SCALAR or RVEC; max_iter, conv_eps, cost_check
+ * -- 0: no objective, no stop --, floor_v; w_update_ind full, partial or none; h_update_ind all or none, a partial one is
+ * SNMF_ERR_DIM).  Per problem: its frame count T_b >= 1, V_b, the initial factors, the results and the objective.
+ * Arithmetic: the fp32 solver's (f32 MFMA products, fp64 statistics and fp64 master copy of W, fp64 objective).
+ * Independent solves: problem b stops at the iteration where ITS test (:272-284) fires, with the factors, the div / cost
+ * vectors and the n_iter of a solve that ran alone; it is frozen on the device from then on.  The host does not synchronise
+ * per iteration: it polls a device counter of stopped problems every 8 iterations, and the run ends when all have stopped or
+ * at max_iter.  The bits of problem b depend on its own inputs and p only -- not on B, its slot, the other problems' sizes
+ * or stop indices, nor on the entry (one-shot or resident, one run or several): every sum has a fixed order per problem
+ * and no floating-point atomics are used.  They are NOT the bits of snmf_sparse_nmf_f64 on the same problem (other
+ * summation orders); both are within the same tolerances of the double-precision algorithm.
+ * Envelope: F <= 513, r <= 200, any T_b >= 1; B and the sum of T_b are limited by memory (and 2^26 tiles).  Outside it, and
+ * for SNMF_SPARSITY_FULL: SNMF_ERR_UNSUPPORTED, the message names the limit.  A failed allocation is SNMF_ERR_NOMEM, frees
+ * every block of the batch and leaves the context usable.  NULL arguments, an index outside [0, B), T_b < 1, ldV < F:
+ * SNMF_ERR_INVALID.
+ * Call order: create -> [set_sparsity for RVEC] -> set_problem for every k -> run -> get.  run before every problem (and
+ * an RVEC sparsity) is set, get before run, set_sparsity after run: SNMF_ERR_STATE.  snmf_batch_run(b, n): n more
+ * iterations (0: up to max_iter); a later call continues, and run(10) + run(0) gives the bits of one run(0).  A
+ * set_problem after a run starts a NEW batch on the handle: every problem is then set again.
+ *   snmf_batch_create       p->T is ignored; T: n_problems frame counts
+ *   snmf_batch_set_problem  V F x T_k (ldV >= F, floored at 1e-9 when p->floor_v), W0 F x r, H0 r x T_k (tight, read-only)
+ *   snmf_batch_get          W F x r, H r x T_k (tight), div_out / cost_out max_iter doubles (zero-filled, then the recorded
+ *                           values), n_iter_out; any of them may be NULL
+ *   snmf_batch_describe     the geometry (tiles, chunks, grids, LDS) as text */
+typedef struct snmf_batch snmf_batch;
+int snmf_batch_create(snmf_ctx* ctx, const snmf_params* p, int32_t n_problems, const int32_t* T, snmf_batch** out);
+int snmf_batch_set_problem_f64(snmf_batch* b, int32_t k, const double* V, int64_t ldV, const double* W0, const double* H0);
+int snmf_batch_set_problem_f32(snmf_batch* b, int32_t k, const float* V, int64_t ldV, const float* W0, const float* H0);
+int snmf_batch_set_sparsity_f64(snmf_batch* b, const double* sparsity /* r */);
+int snmf_batch_run(snmf_batch* b, int32_t n_iters);
+int snmf_batch_get_f64(snmf_batch* b, int32_t k, double* W, double* H, double* div_out, double* cost_out, int32_t* n_iter_out);
+int snmf_batch_get_f32(snmf_batch* b, int32_t k, float* W, float* H, double* div_out, double* cost_out, int32_t* n_iter_out);
+int snmf_batch_describe(const snmf_batch* b, char* buf, size_t buflen);
+void snmf_batch_destroy(snmf_batch* b);
+/* One-shot: create, set, run to the end, get, destroy; the arrays move through the context's chunked transfer pipeline.
+ * T, ldV: n entries; V, W0, H0, W, H: n pointers each (the layouts of set_problem / get); sparsity: NULL for SCALAR, r doubles
+ * for RVEC; div_out / cost_out: NULL or n pointers to max_iter doubles (single entries may be NULL); n_iter_out: NULL or n. */
+int snmf_sparse_nmf_batch_f64(snmf_ctx* ctx, const snmf_params* p, int32_t n_problems, const int32_t* T, const double* const* V,
+                              const int64_t* ldV, const double* const* W0, const double* const* H0, const double* sparsity,
+                              double* const* W, double* const* H, double* const* div_out, double* const* cost_out,
+                              int32_t* n_iter_out);
+int snmf_sparse_nmf_batch_f32(snmf_ctx* ctx, const snmf_params* p, int32_t n_problems, const int32_t* T, const float* const* V,
+                              const int64_t* ldV, const float* const* W0, const float* const* H0, const double* sparsity,
+                              float* const* W, float* const* H, double* const* div_out, double* const* cost_out,
+                              int32_t* n_iter_out);
+
 /* ---- instrumentation (bench.py: HIP-event timing on the engine's own stream) ------------ */
 /* Average device time in milliseconds per launch of the named kernel family over the launches
  * recorded since snmf_ctx_timing(ctx, 1) was switched on.  Families: "hstep", "wstats",

@@ -44,6 +44,7 @@ _TU_HDRS = {
     "snmf_tu_geometry.hip": ["snmf_generic.h"],
     "snmf_tu_solve64.hip": ["snmf_solve64.h", "snmf_solve64_core.h"],
     "snmf_tu_train64.hip": ["snmf_online_common.h", "snmf_frontend64.h", "snmf_philox.h", "snmf_solve64_core.h"],
+    "snmf_tu_batch.hip": ["snmf_batch.h"],
 }
 HDRS = sorted(_glob.glob(os.path.join(_HERE, "csrc", "*.h"))) + [os.path.join(_ROOT, "include", "snmf.h")]
 
@@ -84,6 +85,9 @@ SYMBOLS = [
     "snmf_sparse_nmf_fp64", "snmf_mdi_fp64",
     "snmf_stft_features_fp64", "snmf_mel_features_fp64", "snmf_tf_dd_fp64",
     "snmf_run_basis_dnmf_fp64", "snmf_run_basis_dnmf_audio_fp64", "snmf_run_basis_train_audio_fp64",
+    "snmf_batch_create", "snmf_batch_set_problem_f64", "snmf_batch_set_problem_f32", "snmf_batch_set_sparsity_f64", "snmf_batch_run",
+    "snmf_batch_get_f64", "snmf_batch_get_f32", "snmf_batch_describe", "snmf_batch_destroy",
+    "snmf_sparse_nmf_batch_f64", "snmf_sparse_nmf_batch_f32",
     "snmf_rccl_available", "snmf_rccl_get_unique_id", "snmf_rccl_comm_create", "snmf_rccl_comm_destroy", "snmf_plan_run_sharded_rccl",
 ]
 ABI_VERSION = 5  # include/snmf.h: SNMF_ABI_VERSION this binding was written against
@@ -344,6 +348,16 @@ def load():
         sig[nm + "_fp64"] = sig[nm + "_f32"]
     for nm in ("snmf_run_basis_dnmf", "snmf_run_basis_dnmf_audio", "snmf_run_basis_train_audio"):
         sig[nm + "_fp64"] = sig[nm + "_f64"]
+    # the batched offline solve (snmf_batch_*, snmf_sparse_nmf_batch_*)
+    sig["snmf_batch_create"] = (C.c_int, [vp, PP, i32, vp, C.POINTER(vp)])
+    sig["snmf_batch_set_sparsity_f64"] = (C.c_int, [vp, vp])
+    sig["snmf_batch_run"] = (C.c_int, [vp, i32])
+    sig["snmf_batch_describe"] = (C.c_int, [vp, C.c_char_p, C.c_size_t])
+    sig["snmf_batch_destroy"] = (None, [vp])
+    for ty in ("f64", "f32"):
+        sig[f"snmf_batch_set_problem_{ty}"] = (C.c_int, [vp, i32, vp, i64, vp, vp])
+        sig[f"snmf_batch_get_{ty}"] = (C.c_int, [vp, i32, vp, vp, vp, vp, C.POINTER(i32)])
+        sig[f"snmf_sparse_nmf_batch_{ty}"] = (C.c_int, [vp, PP, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp])
     lib.snmf_abi_version.restype = C.c_int
     if lib.snmf_abi_version() != ABI_VERSION:  # a stale library must not be driven through newer prototypes
         raise ImportError(f"{path} has ABI version {lib.snmf_abi_version()}, this binding needs {ABI_VERSION}: rebuild the library")

@@ -1,0 +1,245 @@
+"""Batched offline solve: many independent factorizations in shared launches (include/snmf.h: snmf_batch_*).
+
+    results = sparse_nmf_batch(vs, p)       a list of (w, h, objective), one per v in vs -- each what sparse_nmf(v, p) means
+    BatchPlan                               the resident handle: set_problem / run / get / describe / close
+
+The problems share the row count F, the rank r and the settings `p`; every problem has its own frame count, its own initial
+factors and its own stop index.  All arithmetic happens in libsnmf_hip.so on the GPU; this module does the reference's
+defaulting and its own errors (src/sparse_nmf.m:75-164, :260) on the host, before any device call.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import SnmfError
+from .api import _cf_to_beta, _colmajor, _display, _make_params, _mask, _ptr, default_context
+
+__all__ = ["sparse_nmf_batch", "BatchPlan"]
+
+
+def _check_batch_precision(precision):
+    if precision != "fp32":
+        raise ValueError(f"precision must be 'fp32' for the batched solve (got {precision!r})")
+
+
+def _batch_sparsity(sparsity, r):
+    """src/sparse_nmf.m:150-155 for a batch -> (kind, scalar, r-vector or None); a matrix has no batched form."""
+    sp = np.asarray(sparsity, dtype=np.float64)
+    if sp.size == 1:
+        return 0, float(sp.reshape(-1)[0]), None
+    if sp.ndim == 1 or (sp.ndim == 2 and sp.shape[1] == 1):
+        if sp.size != r:
+            raise SnmfError(3, f"sparsity column has {sp.size} rows, h has {r}")
+        return 1, 0.0, np.ascontiguousarray(sp.reshape(-1))
+    raise SnmfError(8, "the batched solve takes a scalar or an r-vector sparsity, not an r x n matrix")
+
+
+def _h_ind_all_or_none(p, r):
+    h_ind = _mask(p, "h_update_ind", r)
+    n_h = int(h_ind.sum())
+    if n_h not in (0, r):
+        raise SnmfError(3, f"partial h_update_ind ({n_h} of {r} rows): dimension mismatch in src/sparse_nmf.m:192/197/202")
+    return h_ind
+
+
+def _objective(div, cost, ni, max_iter, cost_check):
+    if cost_check:
+        n = ni if ni < max_iter else max_iter  # :279-280 truncate to 1:it on convergence
+        return {"div": div[:n].copy(), "cost": cost[:n].copy(), "n_iter": ni}
+    return {"div": np.zeros(max_iter), "cost": np.zeros(max_iter), "n_iter": ni}
+
+
+def sparse_nmf_batch(vs, p=None, *, ctx=None, dtype=np.float64, rng=None, precision="fp32"):
+    """[w, h, objective] = sparse_nmf(v, p) for every v in `vs`, solved together (snmf_sparse_nmf_batch_*).
+
+    vs: a list of F x T_b arrays (one F).  p: the reference's settings, shared; p["init_w"] is one F x r array (every
+    problem starts from it) or a list of len(vs) of them; p["init_h"] is a list of len(vs) arrays r x T_b, or absent (drawn
+    per problem as sparse_nmf draws it, from one generator in list order); p["sparsity"] is a scalar or an r-vector;
+    p["display"] prints each problem's lines after the solve.  Returns a list of (w, h, objective).
+    Every problem stops at its own iteration, with the results of a solve that ran alone; the results of a problem do not
+    depend on the batch around it.  `precision` accepts only "fp32" (ValueError otherwise)."""
+    _check_batch_precision(precision)
+    p = dict(p or {})
+    dt = np.dtype(dtype)
+    if dt not in (np.dtype(np.float64), np.dtype(np.float32)):
+        raise SnmfError(1, "dtype must be float64 or float32")
+    vs = [np.asarray(v) for v in vs]
+    B = len(vs)
+    if B == 0:
+        raise SnmfError(1, "the batch is empty: vs must hold at least one matrix")
+    for v in vs:
+        if v.ndim != 2 or v.shape[1] < 1:
+            raise SnmfError(1, "every v must be a 2-D matrix with at least one column")
+    m = vs[0].shape[0]  # :71
+    for k, v in enumerate(vs):
+        if v.shape[0] != m:
+            raise SnmfError(3, f"v of problem {k} has {v.shape[0]} rows, problem 0 has {m}: a batch shares the row count")
+    max_iter = int(p.get("max_iter", 100))  # :79-81
+    random_seed = p.get("random_seed", 1)  # :83-85
+    conv_eps = float(p.get("conv_eps", 0))  # :91-93
+    beta = _cf_to_beta(p)
+    if rng is None:  # :112-114
+        rng = np.random.RandomState(int(random_seed) if random_seed and random_seed > 0 else None)
+
+    # :116-131
+    iw = p.get("init_w", None)
+    if iw is None:
+        if p.get("r", None) is None:
+            raise SnmfError(2, "Number of components or initialization must be given")
+        r = int(p["r"])
+        iws = [None] * B
+    else:
+        if isinstance(iw, (list, tuple)):
+            if len(iw) != B:
+                raise SnmfError(3, f"init_w is a list of {len(iw)}, the batch has {B} problems")
+            iws = [np.asarray(x, dtype=np.float64) for x in iw]
+        else:
+            iws = [np.asarray(iw, dtype=np.float64)] * B
+        for x in iws:
+            if x.ndim != 2 or x.shape[0] != m:
+                raise SnmfError(3, f"init_w is {x.shape}, v has {m} rows")
+            if x.shape[1] != iws[0].shape[1]:
+                raise SnmfError(3, f"init_w is {x.shape}, problem 0 has {iws[0].shape[1]} columns: a batch shares the rank")
+        ri = iws[0].shape[1]
+        r = int(p["r"]) if (p.get("r", None) is not None and ri < int(p["r"])) else ri
+    ih = p.get("init_h", None)
+    if ih is not None:
+        if isinstance(ih, str) or not isinstance(ih, (list, tuple)) or len(ih) != B:
+            raise SnmfError(3, f"init_h must be a list of {B} arrays (r x T_b each), or absent")
+        ihs = [np.asarray(x, dtype=np.float64) for x in ih]
+        for v, x in zip(vs, ihs):
+            if x.shape != (r, v.shape[1]):
+                raise SnmfError(3, f"init_h is {x.shape}, expected ({r}, {v.shape[1]})")
+    w_ind = _mask(p, "w_update_ind", r)
+    h_ind = _h_ind_all_or_none(p, r)
+    kind, scalar, sarr = _batch_sparsity(p.get("sparsity", 0), r)
+    if "cost_check" not in p:  # src/sparse_nmf.m:260
+        raise SnmfError(4, "Reference to non-existent field 'cost_check'.")
+    cost_check = 1 if p["cost_check"] else 0
+
+    # the draws, in list order (:116-140)
+    w0s, h0s = [], []
+    for k, v in enumerate(vs):
+        n = v.shape[1]
+        if iws[k] is None:
+            w0 = rng.random_sample((m, r))
+        elif iws[k].shape[1] < r:
+            w0 = np.concatenate([iws[k], rng.random_sample((m, r - iws[k].shape[1]))], axis=1)
+        else:
+            w0 = iws[k]
+        h0 = rng.random_sample((r, n)) if ih is None else ihs[k]
+        w0s.append(np.asfortranarray(w0, dtype=dt))
+        h0s.append(np.asfortranarray(h0, dtype=dt))
+
+    sp = _make_params(m, 1, r, beta, max_iter, conv_eps, cost_check, True, kind, scalar, w_ind, h_ind)
+    lib = _lib.load()
+    ctx = ctx or default_context()
+    vv = [_colmajor(v, dt) for v in vs]
+    Ts = np.array([v.shape[1] for v in vs], np.int32)
+    ldv = np.array([(v.strides[1] // dt.itemsize) if v.shape[1] > 1 else m for v in vv], np.int64)
+    W = [np.empty((m, r), dtype=dt, order="F") for _ in vs]
+    H = [np.empty((r, v.shape[1]), dtype=dt, order="F") for v in vs]
+    nh = max(max_iter, 1)
+    div = [np.zeros(nh) for _ in vs]
+    cost = [np.zeros(nh) for _ in vs]
+    n_iter = np.zeros(B, np.int32)
+
+    def ptrs(arrs):
+        return (C.c_void_p * B)(*[a.ctypes.data for a in arrs])
+
+    fn = lib.snmf_sparse_nmf_batch_f64 if dt == np.float64 else lib.snmf_sparse_nmf_batch_f32
+    _lib.check(fn(ctx._h, C.byref(sp), B, _ptr(Ts), ptrs(vv), _ptr(ldv), ptrs(w0s), ptrs(h0s), _ptr(sarr) if sarr is not None else None,
+                  ptrs(W), ptrs(H), ptrs(div), ptrs(cost), _ptr(n_iter)))
+    out = []
+    for k in range(B):
+        ni = int(n_iter[k])
+        if p.get("display", 0) != 0:
+            _display(beta, div[k], cost[k], ni, max_iter, cost_check, conv_eps, False)
+        out.append((W[k], H[k], _objective(div[k], cost[k], ni, max_iter, cost_check)))
+    return out
+
+
+class BatchPlan:
+    """snmf_batch: B problems of one (F, r) and one settings struct resident in HBM.  Call order: set_problem for every
+    k -> run -> get; run(n) runs n more iterations (None: up to max_iter) and a later run continues."""
+
+    def __init__(self, ctx, F, r, Ts, *, beta=1.0, max_iter=100, conv_eps=0.0, cost_check=True, floor_v=True, sparsity=0.0,
+                 w_update_ind=None, h_update_ind=None, precision="fp32"):
+        _check_batch_precision(precision)
+        self.F, self.r, self.max_iter = int(F), int(r), int(max_iter)
+        self.Ts = np.ascontiguousarray(np.asarray(Ts, dtype=np.int32).reshape(-1))
+        self.B = int(self.Ts.size)
+        if self.B == 0:
+            raise SnmfError(1, "the batch is empty: Ts must hold at least one frame count")
+        self.cost_check = 1 if cost_check else 0
+        pd = dict(w_update_ind=w_update_ind, h_update_ind=h_update_ind)
+        self._w_ind = _mask(pd, "w_update_ind", self.r)
+        self._h_ind = _h_ind_all_or_none(pd, self.r)
+        kind, scalar, self._sarr = _batch_sparsity(sparsity, self.r)
+        sp = _make_params(F, 1, r, beta, max_iter, conv_eps, cost_check, floor_v, kind, scalar, self._w_ind, self._h_ind)
+        self._lib = _lib.load()
+        self.ctx = ctx or default_context()
+        h = C.c_void_p()
+        _lib.check(self._lib.snmf_batch_create(self.ctx._h, C.byref(sp), self.B, _ptr(self.Ts), C.byref(h)))
+        self._h = h
+        self.ctx._plans.add(self)
+        if self._sarr is not None:
+            _lib.check(self._lib.snmf_batch_set_sparsity_f64(self._h, _ptr(self._sarr)))
+
+    def set_problem(self, k, v, w0, h0):
+        k = int(k)
+        if not 0 <= k < self.B:
+            raise SnmfError(1, f"problem index {k} outside [0, {self.B})")
+        v = np.asarray(v)
+        dt = np.dtype(np.float32) if v.dtype == np.float32 else np.dtype(np.float64)
+        T = int(self.Ts[k])
+        if v.shape != (self.F, T):
+            raise SnmfError(3, f"v is {v.shape}, problem {k} is ({self.F}, {T})")
+        w0, h0 = np.asarray(w0), np.asarray(h0)
+        if w0.shape != (self.F, self.r):
+            raise SnmfError(3, f"init_w is {w0.shape}, v has {self.F} rows")
+        if h0.shape != (self.r, T):
+            raise SnmfError(3, f"init_h is {h0.shape}, expected ({self.r}, {T})")
+        vv = _colmajor(v, dt)
+        w0 = np.asfortranarray(w0, dtype=dt)
+        h0 = np.asfortranarray(h0, dtype=dt)
+        fn = self._lib.snmf_batch_set_problem_f64 if dt == np.float64 else self._lib.snmf_batch_set_problem_f32
+        _lib.check(fn(self._h, k, _ptr(vv), vv.strides[1] // dt.itemsize if T > 1 else self.F, _ptr(w0), _ptr(h0)))
+        self.ctx.sync()  # (the host arrays may go out of scope)
+
+    def run(self, n_iters=None):
+        _lib.check(self._lib.snmf_batch_run(self._h, 0 if n_iters is None else int(n_iters)))
+
+    def get(self, k, dtype=np.float64):
+        k = int(k)
+        if not 0 <= k < self.B:
+            raise SnmfError(1, f"problem index {k} outside [0, {self.B})")
+        dt = np.dtype(dtype)
+        W = np.empty((self.F, self.r), dtype=dt, order="F")
+        H = np.empty((self.r, int(self.Ts[k])), dtype=dt, order="F")
+        nh = max(self.max_iter, 1)
+        div, cost = np.zeros(nh), np.zeros(nh)
+        ni = C.c_int32()
+        fn = self._lib.snmf_batch_get_f64 if dt == np.float64 else self._lib.snmf_batch_get_f32
+        _lib.check(fn(self._h, k, _ptr(W), _ptr(H), _ptr(div), _ptr(cost), C.byref(ni)))
+        return W, H, _objective(div, cost, ni.value, self.max_iter, self.cost_check)
+
+    def describe(self):
+        buf = C.create_string_buffer(1024)
+        _lib.check(self._lib.snmf_batch_describe(self._h, buf, 1024))
+        return buf.value.decode()
+
+    def close(self):
+        if getattr(self, "_h", None):
+            if getattr(self.ctx, "_h", None):  # a destroyed context has already destroyed its plans
+                self._lib.snmf_batch_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
