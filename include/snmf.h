@@ -710,7 +710,7 @@ int snmf_run_basis_dnmf_multi_f32(const int32_t* devices, int32_t n_dev, const s
 /* ---- batched offline solve: many independent factorizations in shared launches ----------- */
 /* Added within 5 (new entries only).  B independent problems V_b ~ W_b * H_b -- src/sparse_nmf.m:157-286 each -- advance in
  * SHARED launches: per iteration one H step over every (problem, 32-frame tile), one W-statistics launch over every
- * (problem, 256-frame chunk) and one finish launch over every (problem, column of W).  A solve of a few hundred to a few
+ * (problem, 64-frame chunk) and one finish launch over every (problem, column of W).  A solve of a few hundred to a few
  * thousand frames fills a quarter of the device and is bound by its three launch boundaries per iteration; a batch of them
  * is not ("Batched offline solve", has the measured table).  Shared by the batch: F, r and one snmf_params with
  * the meaning its fields have in snmf_sparse_nmf_f64 (every beta; sparsity SCALAR or RVEC; max_iter, conv_eps, cost_check

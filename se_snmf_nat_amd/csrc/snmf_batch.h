@@ -28,7 +28,8 @@ namespace snmf {
 
 constexpr int kBW = 8;            // waves per workgroup of k_bh / k_bw
 constexpr int kBThr = 64 * kBW;
-constexpr int kBChunkTiles = 8;   // 32-frame tiles per W-statistics chunk (256 frames)
+constexpr int kBChunkTiles = 2;   // 32-frame tiles per W-statistics chunk (64 frames: the longest fp32 chain over frames; DESIGN.md, "How the
+                                  // batch kernels are judged", has why)
 constexpr int kBMaxF = 513;       // envelope: 16 row tiles (+ the extra row of F = 32n+1)
 constexpr int kBMaxR = 200;       //           7 column tiles
 

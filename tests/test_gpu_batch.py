@@ -68,6 +68,7 @@ RAGGED = [
     ("is_129", 129, (300, 45, 96), 24, dict(cf="is", sparsity=0.1, max_iter=15)),
     ("kl_513", 513, (100, 300, 63), 100, dict(cf="kl", sparsity=5, max_iter=10)),
     ("kl_mel_64", 64, (200, 90, 33), 100, dict(cf="kl", sparsity=5, max_iter=10)),
+    ("kl_513_r200", 513, (33, 257, 100), 200, dict(cf="kl", sparsity=5, max_iter=10)),
 ]
 
 
