@@ -759,6 +759,30 @@ int snmf_sparse_nmf_batch_f32(snmf_ctx* ctx, const snmf_params* p, int32_t n_pro
                               float* const* W, float* const* H, double* const* div_out, double* const* cost_out,
                               int32_t* n_iter_out);
 
+/* Added within 5.  The fp64 mode of the batch: snmf_sparse_nmf_fp64 for n_problems problems in shared launches (DESIGN.md,
+ * "Batched offline solve in the fp64 mode").  fp64 storage, every contraction on the f64 MFMA, every intermediate in HBM,
+ * tight and unpadded; one grouped GEMM kernel forms each product of an iteration for all problems from a device table of
+ * (problem, 64 x 64 tile, split of 2048), and every element-wise pass and reduction is the single fp64 solve's, with the
+ * problem as one more grid index.  THE CONTRACT: W, H, div, cost and n_iter of problem b are bit for bit those of
+ * snmf_sparse_nmf_fp64 run alone on V_b, W0_b, H0_b with the same settings -- whatever B, the slot, the other problems'
+ * sizes and stop indices, and the entry (one-shot or resident, one run or several).
+ * Envelope: no F or r limit of its own (the fp32 batch's F <= 513, r <= 200 do not apply); at most 65535 problems, 2^31 - 1
+ * tiles in one grouped product, 65535 row-sum chunks of 256 frames in one problem, and the device's free memory -- all checked
+ * before anything is allocated: SNMF_ERR_UNSUPPORTED, the message names the limit.  Refused as by snmf_batch_create: a
+ * partial h_update_ind (SNMF_ERR_DIM), SNMF_SPARSITY_FULL (SNMF_ERR_UNSUPPORTED), n_problems < 1, T_b < 1, NULL
+ * (SNMF_ERR_INVALID) -- before the device is touched.
+ * The handle is an snmf_batch and the call order is the one above: create_fp64 -> [set_sparsity for RVEC] -> set_problem for
+ * every k -> run -> get.  Every snmf_batch_* entry works on it: set_problem_f64, or _f32 (widened on the way in);
+ * set_sparsity_f64; run, with continuation (run(n) + run(0) gives the bits of one run(0)); a set_problem after a run starts a
+ * NEW batch; get_f64, or _f32 (the fp64 results rounded to nearest on the way out); describe (tables, grids, launches per
+ * iteration, bytes); destroy.  p->floor_v = 0 leaves V unfloored, as in the fp32 batch. */
+int snmf_batch_create_fp64(snmf_ctx* ctx, const snmf_params* p, int32_t n_problems, const int32_t* T, snmf_batch** out);
+/* One-shot in the fp64 mode: the argument list of snmf_sparse_nmf_batch_f64. */
+int snmf_sparse_nmf_batch_fp64(snmf_ctx* ctx, const snmf_params* p, int32_t n_problems, const int32_t* T, const double* const* V,
+                               const int64_t* ldV, const double* const* W0, const double* const* H0, const double* sparsity,
+                               double* const* W, double* const* H, double* const* div_out, double* const* cost_out,
+                               int32_t* n_iter_out);
+
 /* ---- instrumentation (bench.py: HIP-event timing on the engine's own stream) ------------ */
 /* Average device time in milliseconds per launch of the named kernel family over the launches
  * recorded since snmf_ctx_timing(ctx, 1) was switched on.  Families: "hstep", "wstats",

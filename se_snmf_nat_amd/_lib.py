@@ -44,7 +44,8 @@ _TU_HDRS = {
     "snmf_tu_geometry.hip": ["snmf_generic.h"],
     "snmf_tu_solve64.hip": ["snmf_solve64.h", "snmf_solve64_core.h"],
     "snmf_tu_train64.hip": ["snmf_online_common.h", "snmf_frontend64.h", "snmf_philox.h", "snmf_solve64_core.h"],
-    "snmf_tu_batch.hip": ["snmf_batch.h"],
+    "snmf_tu_batch.hip": ["snmf_batch.h", "snmf_batch64_host.h"],
+    "snmf_tu_batch64.hip": ["snmf_solve64.h", "snmf_batch64.h", "snmf_batch64_host.h"],
 }
 HDRS = sorted(_glob.glob(os.path.join(_HERE, "csrc", "*.h"))) + [os.path.join(_ROOT, "include", "snmf.h")]
 
@@ -88,6 +89,7 @@ SYMBOLS = [
     "snmf_batch_create", "snmf_batch_set_problem_f64", "snmf_batch_set_problem_f32", "snmf_batch_set_sparsity_f64", "snmf_batch_run",
     "snmf_batch_get_f64", "snmf_batch_get_f32", "snmf_batch_describe", "snmf_batch_destroy",
     "snmf_sparse_nmf_batch_f64", "snmf_sparse_nmf_batch_f32",
+    "snmf_batch_create_fp64", "snmf_sparse_nmf_batch_fp64",
     "snmf_rccl_available", "snmf_rccl_get_unique_id", "snmf_rccl_comm_create", "snmf_rccl_comm_destroy", "snmf_plan_run_sharded_rccl",
 ]
 ABI_VERSION = 5  # include/snmf.h: SNMF_ABI_VERSION this binding was written against
@@ -358,6 +360,9 @@ def load():
         sig[f"snmf_batch_set_problem_{ty}"] = (C.c_int, [vp, i32, vp, i64, vp, vp])
         sig[f"snmf_batch_get_{ty}"] = (C.c_int, [vp, i32, vp, vp, vp, vp, C.POINTER(i32)])
         sig[f"snmf_sparse_nmf_batch_{ty}"] = (C.c_int, [vp, PP, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp])
+    # its fp64 mode: the same handle type and the argument lists of the namesakes
+    sig["snmf_batch_create_fp64"] = sig["snmf_batch_create"]
+    sig["snmf_sparse_nmf_batch_fp64"] = sig["snmf_sparse_nmf_batch_f64"]
     lib.snmf_abi_version.restype = C.c_int
     if lib.snmf_abi_version() != ABI_VERSION:  # a stale library must not be driven through newer prototypes
         raise ImportError(f"{path} has ABI version {lib.snmf_abi_version()}, this binding needs {ABI_VERSION}: rebuild the library")

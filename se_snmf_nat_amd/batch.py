@@ -2,6 +2,8 @@
 
     results = sparse_nmf_batch(vs, p)       a list of (w, h, objective), one per v in vs -- each what sparse_nmf(v, p) means
     BatchPlan                               the resident handle: set_problem / run / get / describe / close
+    sparse_nmf_batch_fp64, BatchPlan64      the same two in the fp64 mode (snmf_batch_create_fp64): every problem's results are
+                                            bit for bit those of sparse_nmf(v, p, precision="fp64") run alone
 
 The problems share the row count F, the rank r and the settings `p`; every problem has its own frame count, its own initial
 factors and its own stop index.  All arithmetic happens in libsnmf_hip.so on the GPU; this module does the reference's
@@ -17,12 +19,13 @@ from . import _lib
 from ._lib import SnmfError
 from .api import _cf_to_beta, _colmajor, _display, _make_params, _mask, _ptr, default_context
 
-__all__ = ["sparse_nmf_batch", "BatchPlan"]
+__all__ = ["sparse_nmf_batch", "BatchPlan", "sparse_nmf_batch_fp64", "BatchPlan64"]
 
 
 def _check_batch_precision(precision):
     if precision != "fp32":
-        raise ValueError(f"precision must be 'fp32' for the batched solve (got {precision!r})")
+        raise ValueError(f"precision must be 'fp32' for the batched solve (got {precision!r}); "
+                         "the fp64 mode has names of its own: sparse_nmf_batch_fp64 and BatchPlan64")
 
 
 def _batch_sparsity(sparsity, r):
@@ -62,6 +65,19 @@ def sparse_nmf_batch(vs, p=None, *, ctx=None, dtype=np.float64, rng=None, precis
     Every problem stops at its own iteration, with the results of a solve that ran alone; the results of a problem do not
     depend on the batch around it.  `precision` accepts only "fp32" (ValueError otherwise)."""
     _check_batch_precision(precision)
+    return _solve_batch(vs, p, ctx, dtype, rng, "fp32")
+
+
+def sparse_nmf_batch_fp64(vs, p=None, *, ctx=None, rng=None):
+    """sparse_nmf_batch in the fp64 mode (snmf_sparse_nmf_batch_fp64): float64 arrays in and out, the same settings, defaulting,
+    draws in list order and errors.  Problem k's w, h, div, cost and n_iter are bit for bit those of
+    sparse_nmf(vs[k], p_k, precision="fp64") run alone on the same initial factors.  No F or r limit of its own."""
+    return _solve_batch(vs, p, ctx, np.float64, rng, "fp64")
+
+
+def _solve_batch(vs, p, ctx, dtype, rng, mode):
+    """The one host side of sparse_nmf_batch and sparse_nmf_batch_fp64: the reference's defaulting, its errors and the batch's
+    refusals, the draws, then one call of the C entry of `mode`."""
     p = dict(p or {})
     dt = np.dtype(dtype)
     if dt not in (np.dtype(np.float64), np.dtype(np.float32)):
@@ -150,7 +166,10 @@ def sparse_nmf_batch(vs, p=None, *, ctx=None, dtype=np.float64, rng=None, precis
     def ptrs(arrs):
         return (C.c_void_p * B)(*[a.ctypes.data for a in arrs])
 
-    fn = lib.snmf_sparse_nmf_batch_f64 if dt == np.float64 else lib.snmf_sparse_nmf_batch_f32
+    if mode == "fp64":
+        fn = lib.snmf_sparse_nmf_batch_fp64
+    else:
+        fn = lib.snmf_sparse_nmf_batch_f64 if dt == np.float64 else lib.snmf_sparse_nmf_batch_f32
     _lib.check(fn(ctx._h, C.byref(sp), B, _ptr(Ts), ptrs(vv), _ptr(ldv), ptrs(w0s), ptrs(h0s), _ptr(sarr) if sarr is not None else None,
                   ptrs(W), ptrs(H), ptrs(div), ptrs(cost), _ptr(n_iter)))
     out = []
@@ -166,9 +185,14 @@ class BatchPlan:
     """snmf_batch: B problems of one (F, r) and one settings struct resident in HBM.  Call order: set_problem for every
     k -> run -> get; run(n) runs n more iterations (None: up to max_iter) and a later run continues."""
 
+    _create = "snmf_batch_create"
+
     def __init__(self, ctx, F, r, Ts, *, beta=1.0, max_iter=100, conv_eps=0.0, cost_check=True, floor_v=True, sparsity=0.0,
                  w_update_ind=None, h_update_ind=None, precision="fp32"):
         _check_batch_precision(precision)
+        self._init(ctx, F, r, Ts, beta, max_iter, conv_eps, cost_check, floor_v, sparsity, w_update_ind, h_update_ind)
+
+    def _init(self, ctx, F, r, Ts, beta, max_iter, conv_eps, cost_check, floor_v, sparsity, w_update_ind, h_update_ind):
         self.F, self.r, self.max_iter = int(F), int(r), int(max_iter)
         self.Ts = np.ascontiguousarray(np.asarray(Ts, dtype=np.int32).reshape(-1))
         self.B = int(self.Ts.size)
@@ -183,7 +207,7 @@ class BatchPlan:
         self._lib = _lib.load()
         self.ctx = ctx or default_context()
         h = C.c_void_p()
-        _lib.check(self._lib.snmf_batch_create(self.ctx._h, C.byref(sp), self.B, _ptr(self.Ts), C.byref(h)))
+        _lib.check(getattr(self._lib, self._create)(self.ctx._h, C.byref(sp), self.B, _ptr(self.Ts), C.byref(h)))
         self._h = h
         self.ctx._plans.add(self)
         if self._sarr is not None:
@@ -243,3 +267,15 @@ class BatchPlan:
             self.close()
         except Exception:
             pass
+
+
+class BatchPlan64(BatchPlan):
+    """BatchPlan in the fp64 mode (snmf_batch_create_fp64): the same methods and call order; every problem's results are bit
+    for bit those of sparse_nmf(..., precision="fp64") on it alone.  float32 arrays given to set_problem are widened,
+    get(dtype=np.float32) rounds the fp64 results; describe() gives the tables, the grids, the launches per iteration and the bytes."""
+
+    _create = "snmf_batch_create_fp64"
+
+    def __init__(self, ctx, F, r, Ts, *, beta=1.0, max_iter=100, conv_eps=0.0, cost_check=True, floor_v=True, sparsity=0.0,
+                 w_update_ind=None, h_update_ind=None):
+        self._init(ctx, F, r, Ts, beta, max_iter, conv_eps, cost_check, floor_v, sparsity, w_update_ind, h_update_ind)

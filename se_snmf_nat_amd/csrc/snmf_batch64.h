@@ -1,0 +1,145 @@
+// ============================================================================================
+// The batched offline solve in the fp64 mode (snmf_batch_create_fp64): B independent problems of one (F, r) and one
+// settings struct, each the fp64 solve of snmf_solve64.h, in SHARED launches.  The arrays of a problem are the single
+// solve's -- tight, column-major, nothing padded, 64-bit offsets -- and the problems lie one behind the other along the
+// frames: V, Lam, R, D are F x sum(T_b), H, Num, Den r x sum(T_b), W, Q, P F x r per problem, and every problem has its
+// own column norms, column sums, row-sum partials, objective partials, objective history and Solve64State.
+// Every kernel here is a grid of the single solve's workgroups with one more index, the problem: it finds the problem's
+// arrays and calls the __device__ body the single solve's kernel calls (snmf_solve64.h), with the workgroup index and the
+// grid size that kernel would have had.  So every element, every partial sum and every tree is formed by the same
+// expression in the same order, and a problem's bits are those of snmf_sparse_nmf_fp64 on it alone.
+// A workgroup returns at once when its problem's stop word is set.
+// ============================================================================================
+#pragma once
+
+#include "snmf_solve64.h"
+
+namespace snmf {
+
+struct B64Prob {
+    int T;          // frames of this problem
+    int n_rowz;     // its row-sum chunks of kS64RowChunk frames
+    long long fr0;  // frames of the problems before it
+    long long rz0;  // row-sum chunks of the problems before it
+};
+
+// one workgroup of a grouped product: problem, 64 x 64 tile of that problem's product, split
+struct B64Tile {
+    int prob, tile, z;
+};
+
+// one split product (or one problem's row sums) whose partials k_b64_sumz adds in split order
+struct B64Sum {
+    const double* part;
+    double* C;
+    long long n, rsC, csC;
+    int nz, M, do_floor;
+    const int* stop;
+};
+
+struct B64Args {
+    int F, r, kind, max_iter;
+    double scalar, beta, conv_eps, div_scale;
+    const B64Prob* prob;
+    const double* S;  // r-vector sparsity (kind 1)
+    double *V, *Lam, *R, *D, *H, *Num, *Den, *W, *Q, *P;
+    double *cs, *hs, *sp, *wn, *part, *divh, *costh;
+    const uint8_t* w_ind;
+    Solve64State* st;
+    int* n_stopped;
+};
+
+// The grouped f64-MFMA GEMM: workgroup b takes entry b of a table built from the frame counts when the batch is made --
+// the problem, the 64 x 64 tile within that problem's product and the split -- and that problem's Gemm64Args, which are
+// the ones gemm64() makes for the problem alone (s64_gemm_plan).  Problems with one split (a direct store, floored there)
+// and problems with several (tight partials for k_b64_sumz) share the launch.
+static __global__ __launch_bounds__(256) void k_b64_gemm(const Gemm64Args* __restrict__ args, const B64Tile* __restrict__ tiles) {
+    const B64Tile t = tiles[blockIdx.x];
+    const Gemm64Args g = args[t.prob];
+    if (*g.stop) return;
+    __shared__ double As[16][64 + 2];
+    __shared__ double Bs[16][64 + 2];
+    s64_gemm_tile(g, (unsigned)t.tile, t.z, As, Bs);
+}
+
+// blockIdx.y: the entry; the elements of an entry are spread over gridDim.x workgroups (each sum is one thread's, in split order)
+static __global__ __launch_bounds__(256) void k_b64_sumz(const B64Sum* __restrict__ e) {
+    const B64Sum s = e[blockIdx.y];
+    if (*s.stop) return;
+    s64_sumz_span(s.part, s.nz, s.n, s.M, s.C, s.rsC, s.csC, s.do_floor, blockIdx.x, gridDim.x);
+}
+
+// ---- element-wise passes: grid (workgroups, problem); an element's value does not depend on the workgroup that forms it
+template <int MODE>
+__global__ __launch_bounds__(256) void k_b64_ratio(B64Args a) {
+    const int b = blockIdx.y;
+    if (a.st[b].stop) return;
+    const B64Prob p = a.prob[b];
+    const long long o = p.fr0 * a.F;
+    s64_ratio_span<MODE>(a.V + o, a.Lam + o, a.R ? a.R + o : nullptr, a.D ? a.D + o : nullptr, (long long)a.F * p.T, a.beta, blockIdx.x,
+                         gridDim.x);
+}
+
+template <bool KL>
+__global__ __launch_bounds__(256) void k_b64_hupd(B64Args a) {
+    const int b = blockIdx.y;
+    if (a.st[b].stop) return;
+    const B64Prob p = a.prob[b];
+    const long long o = p.fr0 * a.r;
+    s64_hupd_span<KL>(a.H + o, a.Num + o, KL ? nullptr : a.Den + o, KL ? a.cs + (long long)b * a.r : nullptr, a.kind, a.scalar, a.S, a.r,
+                      (long long)a.r * p.T, blockIdx.x, gridDim.x);
+}
+
+// ---- reductions: the single solve's partition per problem
+// grid (r, B): column sums of W_b
+static __global__ __launch_bounds__(256) void k_b64_colsum(B64Args a) {
+    const int b = blockIdx.y;
+    if (a.st[b].stop) return;
+    __shared__ double red[256];
+    s64_colsum_col(a.W + (long long)b * a.F * a.r, a.F, a.cs + (long long)b * a.r, (int)blockIdx.x, red);
+}
+
+// grid (ceil(r / 256), the largest chunk count, B): the row-sum partials of H_b; k_b64_sumz adds them
+static __global__ __launch_bounds__(256) void k_b64_rowsum(B64Args a) {
+    const int b = blockIdx.z;
+    if (a.st[b].stop) return;
+    const B64Prob p = a.prob[b];
+    if ((int)blockIdx.y >= p.n_rowz) return;
+    s64_rowsum_chunk(a.H + p.fr0 * a.r, a.r, p.T, kS64RowChunk, a.sp + p.rz0 * a.r, (int)blockIdx.y, blockIdx.x, gridDim.x);
+}
+
+// grid (r, B): the W epilogue of problem b, column k
+template <bool KL>
+__global__ __launch_bounds__(256) void k_b64_wupd(B64Args a) {
+    const int b = blockIdx.y;
+    if (a.st[b].stop) return;
+    __shared__ double red[256];
+    const long long o = (long long)b * a.F * a.r;
+    s64_wupd_col<KL, true>(a.W + o, a.Q + o, KL ? nullptr : a.P + o, KL ? a.hs + (long long)b * a.r : nullptr, a.w_ind, a.F, nullptr,
+                           (int)blockIdx.x, red);
+}
+
+// grid (kS64Blocks, B): the objective partials of problem b, the single solve's kS64Blocks slots and element assignment
+template <int MODE>
+__global__ __launch_bounds__(256) void k_b64_obj(B64Args a) {
+    const int b = blockIdx.y;
+    if (a.st[b].stop) return;
+    __shared__ double red[256];
+    const B64Prob p = a.prob[b];
+    const long long o = p.fr0 * a.F;
+    s64_obj_block<MODE>(a.V + o, a.Lam + o, (long long)a.F * p.T, a.beta, a.H + p.fr0 * a.r, a.kind, a.scalar, a.S, a.r,
+                        (long long)a.r * p.T, a.part + (long long)b * 2 * kS64Blocks, red, blockIdx.x, gridDim.x);
+}
+
+// grid (B): the fixed tree over problem b's partials, its objective vectors and its stop test (src/sparse_nmf.m:272-284);
+// a problem that stops counts itself in n_stopped, which is all the host polls
+static __global__ __launch_bounds__(256) void k_b64_stop(B64Args a, int it) {
+    const int b = blockIdx.x;
+    if (a.st[b].stop) return;
+    __shared__ double red[256];
+    const bool fired = s64_stop_test(a.part + (long long)b * 2 * kS64Blocks, kS64Blocks, it, a.conv_eps, a.div_scale,
+                                     a.divh + (long long)b * a.max_iter, a.costh + (long long)b * a.max_iter, a.st + b, red);
+    if (fired) atomicAdd(a.n_stopped, 1);
+}
+
+}  // namespace snmf

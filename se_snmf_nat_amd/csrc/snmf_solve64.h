@@ -48,18 +48,17 @@ struct Gemm64Args {
 // f64 MFMA: lane l gives A[i = l & 15][k = l >> 4] and B[k = l >> 4][j = l & 15]; result register g of lane l is
 // D[row = (l >> 4) + 4 g][col = l & 15] -- NOT the f32 map.  The 16 lanes of a result register run along n, so the
 // stores are contiguous (128 bytes) when C's unit stride runs along n: the host hands a product whose C has its unit
-// stride along m over as C^T = B^T * A^T (gemm64 in snmf_tu_solve64.hip), a relabelling of the strides.
-// Workgroup b of a split takes row tile b % tiles_m and column tile b / tiles_m (x is the one grid dimension that
-// holds 2^31 tiles); blockIdx.y is the split.
-static __global__ __launch_bounds__(256) void k_s64_gemm(Gemm64Args g) {
-    if (*g.stop) return;
+// stride along m over as C^T = B^T * A^T (s64_gemm_plan below), a relabelling of the strides.
+// Tile bx of a split takes row tile bx % tiles_m and column tile bx / tiles_m.
+// This is the tile body: k_s64_gemm (blockIdx.x = bx -- the one grid dimension that holds 2^31 tiles --, blockIdx.y = the
+// split z) and the grouped kernel of the batched solve (k_b64_gemm in snmf_batch64.h: bx and z from a table) both call it,
+// so a product has one summation order whichever kernel forms it.
+__device__ __forceinline__ void s64_gemm_tile(const Gemm64Args& g, unsigned bx, int z, double (*As)[64 + 2], double (*Bs)[64 + 2]) {
     constexpr int BM = 64, BN = 64, BK = 16;
-    __shared__ double As[BK][BM + 2];
-    __shared__ double Bs[BK][BN + 2];
     const int tid = threadIdx.x;
     const int tiles_m = (g.M + BM - 1) / BM;
-    const int m0 = (int)(blockIdx.x % tiles_m) * BM, n0 = (int)(blockIdx.x / tiles_m) * BN;
-    const int k_lo = blockIdx.y * g.kchunk, k_hi = min(g.K, k_lo + g.kchunk);
+    const int m0 = (int)(bx % tiles_m) * BM, n0 = (int)(bx / tiles_m) * BN;
+    const int k_lo = z * g.kchunk, k_hi = min(g.K, k_lo + g.kchunk);
     const int w = tid >> 6, lane = tid & 63, l15 = lane & 15, q = lane >> 4;
     const int wm = (w >> 1) * 32, wn = (w & 1) * 32;
     f64x4 acc[2][2];
@@ -96,7 +95,7 @@ static __global__ __launch_bounds__(256) void k_s64_gemm(Gemm64Args g) {
         }
         __syncthreads();
     }
-    double* C = g.C + (long long)blockIdx.y * g.zC;
+    double* C = g.C + (long long)z * g.zC;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -111,17 +110,60 @@ static __global__ __launch_bounds__(256) void k_s64_gemm(Gemm64Args g) {
             }
 }
 
+static __global__ __launch_bounds__(256) void k_s64_gemm(Gemm64Args g) {
+    if (*g.stop) return;
+    __shared__ double As[16][64 + 2];
+    __shared__ double Bs[16][64 + 2];
+    s64_gemm_tile(g, blockIdx.x, (int)blockIdx.y, As, Bs);
+}
+
+// Host side: the kernel arguments of C = A * B with the contraction cut into splits of kS64ChunkK.  One split stores straight
+// into C; several write tight column-major partials at zbuf, which k_s64_sumz adds in split order.  The kernel's stores run
+// along n: a C whose smaller stride runs along m is formed as C^T = B^T * A^T, which only relabels the strides.  Returns the
+// number of splits.  The single solve (gemm64 in snmf_tu_solve64.hip) and the batched solve's tables both come from here.
+inline int s64_gemm_plan(Gemm64Args* out, const double* A, long long rsA, long long csA, const double* B, long long rsB, long long csB,
+                         double* C, long long rsC, long long csC, int M, int N, int K, bool do_floor, double* zbuf, const int* stop) {
+    const int nz = (K + kS64ChunkK - 1) / kS64ChunkK;
+    Gemm64Args g;
+    g.K = K, g.kchunk = kS64ChunkK, g.stop = stop;
+    const bool direct = nz == 1;
+    // the partials of a split product are tight and column-major (unit stride along m)
+    const long long rs = direct ? rsC : 1, cs = direct ? csC : M;
+    if (rs < cs) {  // transposed problem
+        g.A = B, g.rsA = csB, g.csA = rsB;
+        g.B = A, g.rsB = csA, g.csB = rsA;
+        g.M = N, g.N = M, g.rsC = cs, g.csC = rs;
+    } else {
+        g.A = A, g.rsA = rsA, g.csA = csA;
+        g.B = B, g.rsB = rsB, g.csB = csB;
+        g.M = M, g.N = N, g.rsC = rs, g.csC = cs;
+    }
+    g.C = direct ? C : zbuf;
+    g.zC = direct ? 0 : (long long)M * N;
+    g.do_floor = direct && do_floor;
+    *out = g;
+    return nz;
+}
+inline long long s64_gemm_tiles(const Gemm64Args& g) { return (long long)((g.M + 63) / 64) * ((g.N + 63) / 64); }
+
 // C(m, n) = sum over the splits z, in split order, of part[z][m + M * n] (the partials are tight and column-major)
-static __global__ __launch_bounds__(256) void k_s64_sumz(const double* __restrict__ part, int nz, long long n, int M, double* __restrict__ C,
-                                                         long long rsC, long long csC, int do_floor, const int* stop) {
-    if (*stop) return;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+// (Every pass below is a __device__ body -- workgroup bx of gx, or one column -- and a kernel of the single solve around it;
+// the batched solve's grouped kernels in snmf_batch64.h call the same bodies, one problem per grid row, so an element has ONE
+// expression and one summation order in both and the compiler cannot contract the two differently.)
+__device__ __forceinline__ void s64_sumz_span(const double* __restrict__ part, int nz, long long n, int M, double* __restrict__ C,
+                                              long long rsC, long long csC, int do_floor, unsigned bx, unsigned gx) {
+    for (long long i = (long long)bx * 256 + threadIdx.x; i < n; i += (long long)gx * 256) {
         double s = 0.0;
         for (int z = 0; z < nz; ++z) s += part[(long long)z * n + i];
         if (do_floor) s = fmax(s, kS64Flr);
         const long long col = i / M, row = i - col * M;
         C[row * rsC + col * csC] = s;
     }
+}
+static __global__ __launch_bounds__(256) void k_s64_sumz(const double* __restrict__ part, int nz, long long n, int M, double* __restrict__ C,
+                                                         long long rsC, long long csC, int do_floor, const int* stop) {
+    if (*stop) return;
+    s64_sumz_span(part, nz, n, M, C, rsC, csC, do_floor, blockIdx.x, gridDim.x);
 }
 
 // workgroup sum of one double per thread (256 threads), fixed tree; the result in every thread
@@ -140,10 +182,9 @@ __device__ __forceinline__ double s64_block_sum(double v, double* red /*[256]*/)
 // R = V .* Lam^(beta-2) (KL: V ./ Lam) and D = Lam^(beta-1) (src/sparse_nmf.m:194, :202-204, :217, :231-236); the
 // Euclidean case needs neither (R = V, D = Lam are used where they lie).
 template <int MODE>
-__global__ __launch_bounds__(256) void k_s64_ratio(const double* __restrict__ V, const double* __restrict__ Lam, double* __restrict__ R,
-                                                   double* __restrict__ D, long long n, double beta, const int* stop) {
-    if (*stop) return;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+__device__ __forceinline__ void s64_ratio_span(const double* __restrict__ V, const double* __restrict__ Lam, double* __restrict__ R,
+                                               double* __restrict__ D, long long n, double beta, unsigned bx, unsigned gx) {
+    for (long long i = (long long)bx * 256 + threadIdx.x; i < n; i += (long long)gx * 256) {
         const double v = V[i], lam = Lam[i];
         if (MODE == S64_KL) {
             R[i] = v / lam;
@@ -156,6 +197,12 @@ __global__ __launch_bounds__(256) void k_s64_ratio(const double* __restrict__ V,
         }
     }
 }
+template <int MODE>
+__global__ __launch_bounds__(256) void k_s64_ratio(const double* __restrict__ V, const double* __restrict__ Lam, double* __restrict__ R,
+                                                   double* __restrict__ D, long long n, double beta, const int* stop) {
+    if (*stop) return;
+    s64_ratio_span<MODE>(V, Lam, R, D, n, beta, blockIdx.x, gridDim.x);
+}
 
 __device__ __forceinline__ double s64_sparsity(int kind, double scalar, const double* __restrict__ S, long long i, int k) {
     return kind == 0 ? scalar : (kind == 1 ? S[k] : S[i]);
@@ -163,39 +210,52 @@ __device__ __forceinline__ double s64_sparsity(int kind, double scalar, const do
 
 // H <- H .* num ./ max(den + sparsity, flr) (src/sparse_nmf.m:192-205); KL: den = colsum(W)
 template <bool KL>
-__global__ __launch_bounds__(256) void k_s64_hupd(double* __restrict__ H, const double* __restrict__ Num, const double* __restrict__ Den,
-                                                  const double* __restrict__ colsum, int kind, double scalar,
-                                                  const double* __restrict__ S, int r, long long n, const int* stop) {
-    if (*stop) return;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+__device__ __forceinline__ void s64_hupd_span(double* __restrict__ H, const double* __restrict__ Num, const double* __restrict__ Den,
+                                              const double* __restrict__ colsum, int kind, double scalar, const double* __restrict__ S,
+                                              int r, long long n, unsigned bx, unsigned gx) {
+    for (long long i = (long long)bx * 256 + threadIdx.x; i < n; i += (long long)gx * 256) {
         const int k = (int)(i % r);
         const double sp = s64_sparsity(kind, scalar, S, i, k);
         const double den = fmax((KL ? colsum[k] : Den[i]) + sp, kS64Flr);
         H[i] = H[i] * Num[i] / den;
     }
 }
+template <bool KL>
+__global__ __launch_bounds__(256) void k_s64_hupd(double* __restrict__ H, const double* __restrict__ Num, const double* __restrict__ Den,
+                                                  const double* __restrict__ colsum, int kind, double scalar,
+                                                  const double* __restrict__ S, int r, long long n, const int* stop) {
+    if (*stop) return;
+    s64_hupd_span<KL>(H, Num, Den, colsum, kind, scalar, S, r, n, blockIdx.x, gridDim.x);
+}
 
 // colsum[k] = sum_f W[f, k] (:192), one workgroup per column
-static __global__ __launch_bounds__(256) void k_s64_colsum(const double* __restrict__ W, int F, double* __restrict__ colsum, const int* stop) {
-    if (*stop) return;
-    __shared__ double red[256];
-    const double* col = W + (long long)blockIdx.x * F;
+__device__ __forceinline__ void s64_colsum_col(const double* __restrict__ W, int F, double* __restrict__ colsum, int k, double* red) {
+    const double* col = W + (long long)k * F;
     double s = 0.0;
     for (int f = threadIdx.x; f < F; f += 256) s += col[f];
     s = s64_block_sum(s, red);
-    if (threadIdx.x == 0) colsum[blockIdx.x] = s;
+    if (threadIdx.x == 0) colsum[k] = s;
+}
+static __global__ __launch_bounds__(256) void k_s64_colsum(const double* __restrict__ W, int F, double* __restrict__ colsum, const int* stop) {
+    if (*stop) return;
+    __shared__ double red[256];
+    s64_colsum_col(W, F, colsum, (int)blockIdx.x, red);
 }
 
 // spart[z][k] = sum over the frames of split z of H[k, t] (:215, the row sums of H; the splits are added by k_s64_sumz)
-static __global__ __launch_bounds__(256) void k_s64_rowsum(const double* __restrict__ H, int r, int T, int chunk, double* __restrict__ spart,
-                                                           const int* stop) {
-    if (*stop) return;
-    const int z = blockIdx.y, t_lo = z * chunk, t_hi = min(T, t_lo + chunk);
-    for (int k = blockIdx.x * 256 + threadIdx.x; k < r; k += gridDim.x * 256) {
+__device__ __forceinline__ void s64_rowsum_chunk(const double* __restrict__ H, int r, int T, int chunk, double* __restrict__ spart, int z,
+                                                 unsigned bx, unsigned gx) {
+    const int t_lo = z * chunk, t_hi = min(T, t_lo + chunk);
+    for (int k = bx * 256 + threadIdx.x; k < r; k += gx * 256) {
         double s = 0.0;
         for (int t = t_lo; t < t_hi; ++t) s += H[(long long)t * r + k];
         spart[(long long)z * r + k] = s;
     }
+}
+static __global__ __launch_bounds__(256) void k_s64_rowsum(const double* __restrict__ H, int r, int T, int chunk, double* __restrict__ spart,
+                                                           const int* stop) {
+    if (*stop) return;
+    s64_rowsum_chunk(H, r, T, chunk, spart, (int)blockIdx.y, blockIdx.x, gridDim.x);
 }
 
 // The F x r epilogue of the W step (src/sparse_nmf.m:215-244), one workgroup per column k:
@@ -204,12 +264,9 @@ static __global__ __launch_bounds__(256) void k_s64_rowsum(const double* __restr
 //   w <- w / sqrt(sum w^2)                         for ALL columns (:242)
 // UPD = false: only the normalisation, and wn[k] = the norm (the initial scaling of :157-160).
 template <bool KL, bool UPD>
-__global__ __launch_bounds__(256) void k_s64_wupd(double* __restrict__ W, const double* __restrict__ Q, const double* __restrict__ P,
-                                                  const double* __restrict__ hsum, const uint8_t* __restrict__ w_ind, int F,
-                                                  double* __restrict__ wn, const int* stop) {
-    if (UPD && *stop) return;
-    __shared__ double red[256];
-    const int k = blockIdx.x;
+__device__ __forceinline__ void s64_wupd_col(double* __restrict__ W, const double* __restrict__ Q, const double* __restrict__ P,
+                                             const double* __restrict__ hsum, const uint8_t* __restrict__ w_ind, int F,
+                                             double* __restrict__ wn, int k, double* red) {
     const long long o = (long long)k * F;
     double* col = W + o;
     if (UPD && w_ind[k]) {
@@ -235,11 +292,19 @@ __global__ __launch_bounds__(256) void k_s64_wupd(double* __restrict__ W, const 
     for (int f = threadIdx.x; f < F; f += 256) col[f] = col[f] / nrm;
     if (!UPD && threadIdx.x == 0) wn[k] = nrm;
 }
+template <bool KL, bool UPD>
+__global__ __launch_bounds__(256) void k_s64_wupd(double* __restrict__ W, const double* __restrict__ Q, const double* __restrict__ P,
+                                                  const double* __restrict__ hsum, const uint8_t* __restrict__ w_ind, int F,
+                                                  double* __restrict__ wn, const int* stop) {
+    if (UPD && *stop) return;
+    __shared__ double red[256];
+    s64_wupd_col<KL, UPD>(W, Q, P, hsum, w_ind, F, wn, (int)blockIdx.x, red);
+}
 
 // h = bsxfun(@times, h, wn') (:160)
 static __global__ __launch_bounds__(256) void k_s64_hscale(double* __restrict__ H, const double* __restrict__ wn, int r, long long n) {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) H[i] = H[i] * wn[i % r];
-}
+}  // (the batched solve launches this kernel and k_s64_floor as they are, once per problem when the problem is set)
 
 // v = max(v, flr) (:169)
 static __global__ __launch_bounds__(256) void k_s64_floor(double* __restrict__ X, long long n) {
@@ -264,30 +329,36 @@ __device__ __forceinline__ double s64_div_add(double d, double v, double lam, do
 
 // sum(sparsity .* h) of :261 over the elements of workgroup b, then both workgroup sums into part[2 b] and part[2 b + 1]
 __device__ __forceinline__ void s64_obj_tail(double d, const double* __restrict__ H, int kind, double scalar, const double* __restrict__ S,
-                                             int r, long long n_h, double* __restrict__ part, double* red) {
+                                             int r, long long n_h, double* __restrict__ part, double* red, unsigned bx, unsigned gx) {
     double sh = 0.0;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n_h; i += (long long)gridDim.x * 256)
+    for (long long i = (long long)bx * 256 + threadIdx.x; i < n_h; i += (long long)gx * 256)
         sh += s64_sparsity(kind, scalar, S, i, (int)(i % r)) * H[i];
     d = s64_block_sum(d, red);
     sh = s64_block_sum(sh, red);
     if (threadIdx.x == 0) {
-        part[2 * blockIdx.x] = d;
-        part[2 * blockIdx.x + 1] = sh;
+        part[2 * bx] = d;
+        part[2 * bx + 1] = sh;
     }
 }
 
 // The divergence terms of src/sparse_nmf.m:248-258 and sum(sparsity .* h) of :261: workgroup b sums its elements (a fixed
 // assignment: grid-stride from b) into part[2 b] and part[2 b + 1].
 template <int MODE>
+__device__ __forceinline__ void s64_obj_block(const double* __restrict__ V, const double* __restrict__ Lam, long long n_v, double beta,
+                                              const double* __restrict__ H, int kind, double scalar, const double* __restrict__ S, int r,
+                                              long long n_h, double* __restrict__ part, double* red, unsigned bx, unsigned gx) {
+    double d = 0.0;
+    for (long long i = (long long)bx * 256 + threadIdx.x; i < n_v; i += (long long)gx * 256)
+        d = s64_div_add<MODE>(d, V[i], Lam[i], beta);
+    s64_obj_tail(d, H, kind, scalar, S, r, n_h, part, red, bx, gx);
+}
+template <int MODE>
 __global__ __launch_bounds__(256) void k_s64_obj(const double* __restrict__ V, const double* __restrict__ Lam, long long n_v, double beta,
                                                  const double* __restrict__ H, int kind, double scalar, const double* __restrict__ S,
                                                  int r, long long n_h, double* __restrict__ part, const int* stop) {
     if (*stop) return;
     __shared__ double red[256];
-    double d = 0.0;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n_v; i += (long long)gridDim.x * 256)
-        d = s64_div_add<MODE>(d, V[i], Lam[i], beta);
-    s64_obj_tail(d, H, kind, scalar, S, r, n_h, part, red);
+    s64_obj_block<MODE>(V, Lam, n_v, beta, H, kind, scalar, S, r, n_h, part, red, blockIdx.x, gridDim.x);
 }
 
 // ---- the missing-data steps (src/snmf_mdi.m / src/snmf_mdi_Sm.m; M is F x T, 1 = observed, soft masks lie in [0, 1]) ----
@@ -316,7 +387,7 @@ __global__ __launch_bounds__(256) void k_s64_mdi_obj(double* __restrict__ V, con
         V[i] = v;
         d = s64_div_add<MODE>(d, v, lam, beta);
     }
-    s64_obj_tail(d, H, kind, scalar, S, r, n_h, part, red);
+    s64_obj_tail(d, H, kind, scalar, S, r, n_h, part, red, blockIdx.x, gridDim.x);
 }
 
 // cost_check = 0: the re-imputation alone
@@ -356,10 +427,9 @@ static __global__ __launch_bounds__(256) void k_s64_mdi_final(const double* V, c
 
 // One workgroup: div and cost of iteration `it` from the block partials (fixed order), the objective vectors (:263-264)
 // and the convergence test of :272-284 -- on the device, so that the host need not wait for every iteration.
-static __global__ __launch_bounds__(256) void k_s64_stop(const double* __restrict__ part, int n_part, int it, double conv_eps, double div_scale,
-                                                         double* __restrict__ divh, double* __restrict__ costh, Solve64State* st) {
-    if (st->stop) return;
-    __shared__ double red[256];
+// s64_stop_test returns true in thread 0 when the test fired.
+__device__ __forceinline__ bool s64_stop_test(const double* __restrict__ part, int n_part, int it, double conv_eps, double div_scale,
+                                              double* __restrict__ divh, double* __restrict__ costh, Solve64State* st, double* red) {
     double d = 0.0, sh = 0.0;
     for (int b = threadIdx.x; b < n_part; b += 256) {
         d += part[2 * b];
@@ -383,7 +453,15 @@ static __global__ __launch_bounds__(256) void k_s64_stop(const double* __restric
         } else {
             st->last_cost = cost;
         }
+        return fired;
     }
+    return false;
+}
+static __global__ __launch_bounds__(256) void k_s64_stop(const double* __restrict__ part, int n_part, int it, double conv_eps, double div_scale,
+                                                         double* __restrict__ divh, double* __restrict__ costh, Solve64State* st) {
+    if (st->stop) return;
+    __shared__ double red[256];
+    (void)s64_stop_test(part, n_part, it, conv_eps, div_scale, divh, costh, st, red);
 }
 
 }  // namespace snmf

@@ -3,14 +3,18 @@
 // advance in shared launches: per iteration one H step over every (problem, tile), one W-statistics launch over every
 // (problem, chunk) and one finish launch over every (problem, column); a problem whose stop test fired is frozen on the
 // device and the host only polls a counter of stopped problems every kPollEvery iterations.
+// A handle made by snmf_batch_create_fp64 carries the fp64 state of snmf_tu_batch64.hip instead (b->b64): every entry below
+// hands such a handle over at its top, and nothing else of the fp32 batch knows about it.
 #include "snmf_internal.h"
 #include "snmf_batch.h"
+#include "snmf_batch64_host.h"
 
 namespace {
 constexpr int kPollEvery = 8;
 }
 
 struct snmf_batch {
+    Batch64* b64 = nullptr;  // the fp64 mode: the whole state of the batch (only ctx is filled in here)
     snmf_ctx* ctx = nullptr;
     snmf_params p{};
     int B = 0, bm = BM_KL;
@@ -36,6 +40,7 @@ struct snmf_batch {
 };
 
 static void batch_free(snmf_batch* b) {
+    batch64_destroy(b->b64);
     for (void* q : b->blocks) hipFree(q);
     delete b;
 }
@@ -248,8 +253,21 @@ extern "C" int snmf_batch_create(snmf_ctx* ctx, const snmf_params* p_in, int32_t
     return SNMF_OK;
 }
 
+extern "C" int snmf_batch_create_fp64(snmf_ctx* ctx, const snmf_params* p, int32_t n_problems, const int32_t* T, snmf_batch** out) {
+    if (!ctx || !p || !T || !out) return fail(SNMF_ERR_INVALID, "snmf_batch_create_fp64: NULL argument");
+    *out = nullptr;
+    Batch64* b64 = nullptr;
+    SN_TRY(batch64_create(ctx, p, n_problems, T, &b64));
+    snmf_batch* b = new snmf_batch();
+    b->ctx = ctx;
+    b->b64 = b64;
+    *out = b;
+    return SNMF_OK;
+}
+
 extern "C" int snmf_batch_set_sparsity_f64(snmf_batch* b, const double* sparsity) {
     BATCH_CHECK(b);
+    if (b->b64) return batch64_set_sparsity(b->b64, sparsity);
     if (!sparsity) return fail(SNMF_ERR_INVALID, "sparsity is NULL");
     if (b->p.sparsity_kind != SNMF_SPARSITY_RVEC) return fail(SNMF_ERR_STATE, "the batch was not created with SNMF_SPARSITY_RVEC");
     if (b->ran) return fail(SNMF_ERR_STATE, "snmf_batch_set_sparsity_f64 after snmf_batch_run");
@@ -276,6 +294,7 @@ static int launch_fin_bm(snmf_batch* b, int b0, int nb, int init, int it, int fo
 template <typename TT>
 static int set_problem(snmf_batch* b, int32_t k, const TT* V, int64_t ldV, const TT* W0, const TT* H0) {
     BATCH_CHECK(b);
+    if (b->b64) return batch64_set_problem(b->b64, k, V, ldV, W0, H0);
     if (k < 0 || k >= b->B) return fail(SNMF_ERR_INVALID, "problem index %d outside [0, %d)", k, b->B);
     if (!V || !W0 || !H0) return fail(SNMF_ERR_INVALID, "snmf_batch_set_problem: V, W0 or H0 of problem %d is NULL", k);
     if (ldV < b->a.F) return fail(SNMF_ERR_INVALID, "ldV = %lld is below F = %d", (long long)ldV, b->a.F);
@@ -346,6 +365,7 @@ static int launch_fold(snmf_batch* b, int j, int cur) {
 
 extern "C" int snmf_batch_run(snmf_batch* b, int32_t n_iters) {
     BATCH_CHECK(b);
+    if (b->b64) return batch64_run(b->b64, n_iters);
     if (n_iters < 0) return fail(SNMF_ERR_INVALID, "n_iters must be >= 0 (0: up to max_iter)");
     if (b->n_have != b->B) return fail(SNMF_ERR_STATE, "snmf_batch_run: %d of %d problems are set", b->n_have, b->B);
     if (!b->have_s) return fail(SNMF_ERR_STATE, "snmf_batch_run: the sparsity vector is not set (snmf_batch_set_sparsity_f64)");
@@ -401,6 +421,7 @@ extern "C" int snmf_batch_run(snmf_batch* b, int32_t n_iters) {
 template <typename TT>
 static int get_problem(snmf_batch* b, int32_t k, TT* W, TT* H, double* div_out, double* cost_out, int32_t* n_iter_out) {
     BATCH_CHECK(b);
+    if (b->b64) return batch64_get(b->b64, k, W, H, div_out, cost_out, n_iter_out);
     if (k < 0 || k >= b->B) return fail(SNMF_ERR_INVALID, "problem index %d outside [0, %d)", k, b->B);
     if (!b->ran) return fail(SNMF_ERR_STATE, "snmf_batch_get before snmf_batch_run");
     const BatchArgs& a = b->a;
@@ -430,6 +451,7 @@ extern "C" int snmf_batch_get_f32(snmf_batch* b, int32_t k, float* W, float* H, 
 
 extern "C" int snmf_batch_describe(const snmf_batch* b, char* buf, size_t buflen) {
     if (!b || !buf || buflen == 0) return fail(SNMF_ERR_INVALID, "snmf_batch_describe: NULL argument");
+    if (b->b64) return batch64_describe(b->b64, buf, buflen);
     const BatchArgs& a = b->a;
     const char* bmn = b->bm == BM_KL ? "kl" : (b->bm == BM_EUC ? "ed" : "beta");
     snprintf(buf, buflen,
@@ -443,13 +465,13 @@ extern "C" int snmf_batch_describe(const snmf_batch* b, char* buf, size_t buflen
 template <typename TT>
 static int batch_oneshot(snmf_ctx* ctx, const snmf_params* p, int32_t n, const int32_t* T, const TT* const* V, const int64_t* ldV,
                          const TT* const* W0, const TT* const* H0, const double* sparsity, TT* const* W, TT* const* H,
-                         double* const* div_out, double* const* cost_out, int32_t* n_iter_out) {
+                         double* const* div_out, double* const* cost_out, int32_t* n_iter_out, bool fp64 = false) {
     if (!ctx || !p || !T || !V || !ldV || !W0 || !H0 || !W || !H) return fail(SNMF_ERR_INVALID, "snmf_sparse_nmf_batch: NULL argument");
     if (p->sparsity_kind == SNMF_SPARSITY_RVEC && !sparsity) return fail(SNMF_ERR_INVALID, "SNMF_SPARSITY_RVEC needs the sparsity vector");
     for (int i = 0; i < n; ++i)
         if (!V[i] || !W0[i] || !H0[i] || !W[i] || !H[i]) return fail(SNMF_ERR_INVALID, "snmf_sparse_nmf_batch: an array of problem %d is NULL", i);
     snmf_batch* b = nullptr;
-    SN_TRY(snmf_batch_create(ctx, p, n, T, &b));
+    SN_TRY(fp64 ? snmf_batch_create_fp64(ctx, p, n, T, &b) : snmf_batch_create(ctx, p, n, T, &b));
     int s = SNMF_OK;
     if (p->sparsity_kind == SNMF_SPARSITY_RVEC) SN_STEP(s, snmf_batch_set_sparsity_f64(b, sparsity));
     for (int i = 0; i < n; ++i) SN_STEP(s, set_problem<TT>(b, i, V[i], ldV[i], W0[i], H0[i]));
@@ -471,4 +493,10 @@ extern "C" int snmf_sparse_nmf_batch_f32(snmf_ctx* ctx, const snmf_params* p, in
                                          float* const* W, float* const* H, double* const* div_out, double* const* cost_out,
                                          int32_t* n_iter_out) {
     return batch_oneshot<float>(ctx, p, n, T, V, ldV, W0, H0, sparsity, W, H, div_out, cost_out, n_iter_out);
+}
+extern "C" int snmf_sparse_nmf_batch_fp64(snmf_ctx* ctx, const snmf_params* p, int32_t n, const int32_t* T, const double* const* V,
+                                          const int64_t* ldV, const double* const* W0, const double* const* H0, const double* sparsity,
+                                          double* const* W, double* const* H, double* const* div_out, double* const* cost_out,
+                                          int32_t* n_iter_out) {
+    return batch_oneshot<double>(ctx, p, n, T, V, ldV, W0, H0, sparsity, W, H, div_out, cost_out, n_iter_out, true);
 }

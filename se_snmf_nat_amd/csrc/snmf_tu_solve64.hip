@@ -39,29 +39,13 @@ struct Solve64 {
 };
 
 // C = A * B with the contraction cut into splits of kS64ChunkK; one split stores straight into C, several go through
-// their partials and k_s64_sumz (chunk order).  The kernel's stores run along n: a C whose smaller stride runs along m
-// is formed as C^T = B^T * A^T, which only relabels the strides.
+// their partials and k_s64_sumz (chunk order).  s64_gemm_plan (snmf_solve64.h) chooses the operands and strides.
 int gemm64(const Solve64& s, const double* A, long long rsA, long long csA, const double* B, long long rsB, long long csB, double* C,
            long long rsC, long long csC, int M, int N, int K, bool do_floor) {
-    const int nz = n_splits(K);
     Gemm64Args g;
-    g.K = K, g.kchunk = kS64ChunkK, g.stop = s.stop;
+    const int nz = s64_gemm_plan(&g, A, rsA, csA, B, rsB, csB, C, rsC, csC, M, N, K, do_floor, s.zbuf, s.stop);
     const bool direct = nz == 1;
-    // the partials of a split product are tight and column-major (unit stride along m)
-    const long long rs = direct ? rsC : 1, cs = direct ? csC : M;
-    if (rs < cs) {  // transposed problem
-        g.A = B, g.rsA = csB, g.csA = rsB;
-        g.B = A, g.rsB = csA, g.csB = rsA;
-        g.M = N, g.N = M, g.rsC = cs, g.csC = rs;
-    } else {
-        g.A = A, g.rsA = rsA, g.csA = csA;
-        g.B = B, g.rsB = rsB, g.csB = csB;
-        g.M = M, g.N = N, g.rsC = rs, g.csC = cs;
-    }
-    g.C = direct ? C : s.zbuf;
-    g.zC = direct ? 0 : (long long)M * N;
-    g.do_floor = direct && do_floor;
-    const long long tiles = (long long)((g.M + 63) / 64) * ((g.N + 63) / 64);
+    const long long tiles = s64_gemm_tiles(g);
     if (tiles > 0x7fffffffLL || nz > 65535) return fail(SNMF_ERR_UNSUPPORTED, "fp64 solve: %lld tiles / %d splits exceed the launch grid", tiles, nz);
     hipLaunchKernelGGL(k_s64_gemm, dim3((unsigned)tiles, nz), dim3(256), 0, s.st, g);
     HIP_TRY(hipGetLastError());
