@@ -42,10 +42,10 @@ _TU_HDRS = {
     "snmf_tu_itersf.hip": ["snmf_smallf.h"],
     "snmf_tu_smallr.hip": ["snmf_smallf.h", "snmf_smallr.h"],
     "snmf_tu_geometry.hip": ["snmf_generic.h"],
-    "snmf_tu_solve64.hip": ["snmf_solve64.h", "snmf_solve64_core.h"],
-    "snmf_tu_train64.hip": ["snmf_online_common.h", "snmf_frontend64.h", "snmf_philox.h", "snmf_solve64_core.h"],
-    "snmf_tu_batch.hip": ["snmf_batch.h", "snmf_batch64_host.h"],
-    "snmf_tu_batch64.hip": ["snmf_solve64.h", "snmf_batch64.h", "snmf_batch64_host.h"],
+    "snmf_tu_solve64.hip": ["snmf_solve64.h", "snmf_solve64_core.h", "snmf_host64.h"],
+    "snmf_tu_train64.hip": ["snmf_online_common.h", "snmf_frontend64.h", "snmf_philox.h", "snmf_solve64_core.h", "snmf_host64.h"],
+    "snmf_tu_batch.hip": ["snmf_batch.h", "snmf_batch_host.h"],
+    "snmf_tu_batch64.hip": ["snmf_solve64.h", "snmf_batch64.h", "snmf_batch_host.h", "snmf_host64.h"],
 }
 HDRS = sorted(_glob.glob(os.path.join(_HERE, "csrc", "*.h"))) + [os.path.join(_ROOT, "include", "snmf.h")]
 

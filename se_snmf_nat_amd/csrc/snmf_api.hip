@@ -182,6 +182,21 @@ int validate_params(const snmf_params* p) {
     return SNMF_OK;
 }
 
+int read_update_masks(const snmf_params* p, int* n_h, int* n_w, uint8_t* w_ind) {
+    const int r = p->r;
+    *n_h = *n_w = 0;
+    for (int k = 0; k < r; ++k) {
+        const int w = p->w_update_ind ? p->w_update_ind[k] != 0 : 1;
+        *n_h += p->h_update_ind ? p->h_update_ind[k] != 0 : 1;
+        *n_w += w;
+        if (w_ind) w_ind[k] = (uint8_t)w;
+    }
+    if (*n_h != 0 && *n_h != r)
+        // bsxfun(@plus, sum(w(:,h_ind))', p.sparsity) with sum(h_ind) ~= r rows: MATLAB size error
+        return fail(SNMF_ERR_DIM, "partial h_update_ind (%d of %d rows): dimension mismatch in src/sparse_nmf.m:192/197/202", *n_h, r);
+    return SNMF_OK;
+}
+
 #ifdef SNMF_PROF
 #include "snmf_prof.h"
 #endif

@@ -1,0 +1,178 @@
+// snmf_batch_host.h -- the host driver of the batched offline solve (include/snmf.h: snmf_batch_*), once for its two modes.
+// Host code only.  A handle is the common state below plus one engine: the fp32 engine (snmf_tu_batch.hip, the kernels of
+// snmf_batch.h) or the fp64 engine (snmf_tu_batch64.hip, the grouped kernels of snmf_batch64.h).  The kernels and the device
+// layouts of the two have nothing in common; the life of the handle -- what is validated when it is made, which call is
+// allowed when, how far a run goes, when the host looks at the stopped counter, what get() reports -- is the same and is
+// written here.  The modes are told apart where the handle is made (snmf_batch_create / snmf_batch_create_fp64) and nowhere else:
+// nothing in this file asks which engine it drives.
+#pragma once
+#include <memory>
+
+#include "snmf_internal.h"
+
+struct snmf_batch {
+    // ---- the common state of a batch
+    snmf_ctx* ctx = nullptr;
+    snmf_params p{};  // (its mask pointers are cleared: upd_h, upd_w and w_ind are their reading)
+    int B = 0;
+    bool upd_h = true, upd_w = true;
+    std::vector<uint8_t> w_ind;
+    std::vector<uint8_t> have;
+    int n_have = 0;
+    bool have_s = false, ran = false;
+    int it_done = 0;
+    std::vector<double> h_div, h_cost;  // the objective histories on the host, hist_len() entries per problem
+    int hist_len() const { return std::max(1, p.max_iter); }
+
+    // ---- the engine: what each mode does in its own way
+    virtual ~snmf_batch() {}  // frees the device memory
+    // the mode's limits on F and r (p is validated): they are refused before the frame counts are looked at
+    virtual int check_shape() const { return SNMF_OK; }
+    // checks the limits that depend on the frame counts, allocates and builds; the common state above is filled in, and a failure
+    // leaves what was allocated to the destructor
+    virtual int build(const int32_t* T) = 0;
+    virtual int reset() = 0;  // the device state of a batch that has not run
+    virtual int upload_sparsity(const double* sparsity) = 0;  // r entries; the caller's array may go on return
+    // problem k from host arrays, and its initial scaling (src/sparse_nmf.m:157-169)
+    virtual int load(int k, const double* V, int64_t ldV, const double* W0, const double* H0) = 0;
+    virtual int load(int k, const float* V, int64_t ldV, const float* W0, const float* H0) = 0;
+    virtual int iterate(int it) = 0;  // enqueues iteration it (it_done == it - 1)
+    virtual int close_run() = 0;      // enqueues what a run that ends at it_done still owes
+    struct Device {                   // what a run reads back: the stopped counter, the B states of the engine's own type, the histories
+        const int* n_stopped;
+        const void* states;
+        void* h_states;
+        size_t state_bytes;
+        const double *divh, *costh;
+    };
+    virtual Device device() = 0;
+    virtual bool stopped(int k, int* n_iter) const = 0;  // from the states read back last
+    virtual int n_recorded(int k) const = 0;             // valid history entries of problem k
+    virtual int fetch(int k, double* W, double* H) = 0;  // W and / or H of problem k to the host
+    virtual int fetch(int k, float* W, float* H) = 0;
+    virtual void describe(char* buf, size_t buflen) const = 0;
+};
+
+snmf_batch* batch64_new();  // snmf_tu_batch64.hip: an fp64 engine, not built yet
+
+#define BATCH_CHECK(b)                                          \
+    if (!(b)) return fail(SNMF_ERR_INVALID, "batch is NULL");   \
+    (void)hipGetLastError();                                    \
+    HIP_TRY(hipSetDevice((b)->ctx->device))
+
+// Takes the engine `b` over (a failure deletes it).  entry: the C entry's name, for the messages.  Every refusal here and the
+// engine's own limits come before the device is touched.
+inline int batch_create(const char* entry, snmf_batch* b, snmf_ctx* ctx, const snmf_params* p_in, int32_t n_problems, const int32_t* T,
+                        snmf_batch** out) {
+    std::unique_ptr<snmf_batch> own(b);
+    if (!ctx || !p_in || !T || !out) return fail(SNMF_ERR_INVALID, "%s: NULL argument", entry);
+    *out = nullptr;
+    if (n_problems < 1) return fail(SNMF_ERR_INVALID, "%s: n_problems must be at least 1 (got %d)", entry, n_problems);
+    b->p = *p_in;
+    b->p.T = 1;  // (ignored: every problem brings its own)
+    SN_TRY(validate_params(&b->p));
+    int n_h = 0, n_w = 0;
+    b->w_ind.resize(b->p.r);
+    SN_TRY(read_update_masks(&b->p, &n_h, &n_w, b->w_ind.data()));
+    if (b->p.sparsity_kind == SNMF_SPARSITY_FULL)
+        return fail(SNMF_ERR_UNSUPPORTED, "the batched solve takes a scalar or an r-vector sparsity, not an r x n matrix");
+    SN_TRY(b->check_shape());
+    for (int i = 0; i < n_problems; ++i)
+        if (T[i] < 1) return fail(SNMF_ERR_INVALID, "problem %d has T = %d frames (at least 1)", i, T[i]);
+    b->ctx = ctx;
+    b->p.w_update_ind = b->p.h_update_ind = nullptr;
+    b->B = n_problems;
+    b->upd_h = n_h > 0;
+    b->upd_w = n_w > 0;
+    b->have.assign(n_problems, 0);
+    b->have_s = b->p.sparsity_kind == SNMF_SPARSITY_SCALAR;
+    SN_TRY(b->build(T));
+    *out = own.release();
+    return SNMF_OK;
+}
+
+inline int batch_set_sparsity(snmf_batch* b, const double* sparsity) {
+    BATCH_CHECK(b);
+    if (!sparsity) return fail(SNMF_ERR_INVALID, "sparsity is NULL");
+    if (b->p.sparsity_kind != SNMF_SPARSITY_RVEC) return fail(SNMF_ERR_STATE, "the batch was not created with SNMF_SPARSITY_RVEC");
+    if (b->ran) return fail(SNMF_ERR_STATE, "snmf_batch_set_sparsity_f64 after snmf_batch_run");
+    SN_TRY(b->upload_sparsity(sparsity));
+    b->have_s = true;
+    return SNMF_OK;
+}
+
+template <typename TT>
+int batch_set_problem(snmf_batch* b, int32_t k, const TT* V, int64_t ldV, const TT* W0, const TT* H0) {
+    BATCH_CHECK(b);
+    if (k < 0 || k >= b->B) return fail(SNMF_ERR_INVALID, "problem index %d outside [0, %d)", k, b->B);
+    if (!V || !W0 || !H0) return fail(SNMF_ERR_INVALID, "snmf_batch_set_problem: V, W0 or H0 of problem %d is NULL", k);
+    if (ldV < b->p.F) return fail(SNMF_ERR_INVALID, "ldV = %lld is below F = %d", (long long)ldV, b->p.F);
+    if (b->ran) {  // a new batch on the same handle: every problem is set again
+        std::fill(b->have.begin(), b->have.end(), 0);
+        b->n_have = 0;
+        b->ran = false;
+        b->it_done = 0;
+        SN_TRY(b->reset());
+    }
+    SN_TRY(b->load(k, V, ldV, W0, H0));
+    if (!b->have[k]) {
+        b->have[k] = 1;
+        ++b->n_have;
+    }
+    return SNMF_OK;
+}
+
+inline int batch_run(snmf_batch* b, int32_t n_iters) {
+    BATCH_CHECK(b);
+    if (n_iters < 0) return fail(SNMF_ERR_INVALID, "n_iters must be >= 0 (0: up to max_iter)");
+    if (b->n_have != b->B) return fail(SNMF_ERR_STATE, "snmf_batch_run: %d of %d problems are set", b->n_have, b->B);
+    if (!b->have_s) return fail(SNMF_ERR_STATE, "snmf_batch_run: the sparsity vector is not set (snmf_batch_set_sparsity_f64)");
+    hipStream_t st = b->ctx->stream;
+    const int max_iter = b->p.max_iter;
+    const int target = n_iters == 0 ? max_iter : (int)std::min<long long>(max_iter, (long long)b->it_done + n_iters);
+    const bool cc = b->p.cost_check != 0, can_stop = cc && b->p.conv_eps > 0.0;
+    const snmf_batch::Device d = b->device();
+    b->ran = true;
+    // A stopped problem is frozen on the device (its workgroups return at once) and its n_iter comes from its device state, so
+    // when the host looks changes no result: it only ends the loop once every problem has stopped.
+    int stopped = 0;
+    auto poll = [&]() {
+        HIP_TRY(hipMemcpyAsync(&stopped, d.n_stopped, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return (int)SNMF_OK;
+    };
+    if (can_stop && b->it_done > 0) SN_TRY(poll());  // (a batch that has not run has a counter of zero)
+    for (int it = b->it_done + 1; it <= target && stopped < b->B; ++it) {
+        SN_TRY(b->iterate(it));
+        b->it_done = it;
+        if (can_stop && it % kPollEvery == 0 && it < max_iter) SN_TRY(poll());  // (at max_iter the closing synchronise follows anyway)
+    }
+    if (stopped < b->B) SN_TRY(b->close_run());
+    const size_t nB = (size_t)b->B, nh = nB * b->hist_len();
+    b->h_div.assign(nh, 0.0);
+    b->h_cost.assign(nh, 0.0);
+    HIP_TRY(hipMemcpyAsync(d.h_states, d.states, d.state_bytes * nB, hipMemcpyDeviceToHost, st));
+    if (cc) {
+        HIP_TRY(hipMemcpyAsync(b->h_div.data(), d.divh, sizeof(double) * nh, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(b->h_cost.data(), d.costh, sizeof(double) * nh, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    return SNMF_OK;
+}
+
+template <typename TT>
+int batch_get(snmf_batch* b, int32_t k, TT* W, TT* H, double* div_out, double* cost_out, int32_t* n_iter_out) {
+    BATCH_CHECK(b);
+    if (k < 0 || k >= b->B) return fail(SNMF_ERR_INVALID, "problem index %d outside [0, %d)", k, b->B);
+    if (!b->ran) return fail(SNMF_ERR_STATE, "snmf_batch_get before snmf_batch_run");
+    SN_TRY(b->fetch(k, W, H));
+    const int mi = b->p.max_iter, n_rec = b->n_recorded(k);
+    const size_t h0 = (size_t)k * b->hist_len();
+    for (int i = 0; i < mi; ++i) {
+        if (div_out) div_out[i] = i < n_rec ? b->h_div[h0 + i] : 0.0;
+        if (cost_out) cost_out[i] = i < n_rec ? b->h_cost[h0 + i] : 0.0;
+    }
+    int n_iter = 0;
+    if (n_iter_out) *n_iter_out = b->stopped(k, &n_iter) ? n_iter : b->it_done;
+    return SNMF_OK;
+}

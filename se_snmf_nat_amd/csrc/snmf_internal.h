@@ -254,6 +254,10 @@ static int dalloc(T** p, size_t n, snmf_ctx* cache_of = nullptr, size_t* bytes_o
 
 static inline int grid_for(size_t n) { return (int)std::min<size_t>((n + 255) / 256, 4096); }
 
+// A loop whose stop test runs on the device (the batched solves, the fp64 solve) reads the stop state back every kPollEvery
+// iterations: a stopped solve's kernels are no-ops, so a late look costs a few empty launches and changes no result.
+constexpr int kPollEvery = 8;
+
 // Every plan entry point starts from a clean HIP error state: hipGetLastError() is sticky per thread, so an error some
 // EARLIER, unrelated call left behind (a refused device ordinal, the caller's own HIP code, torch) would otherwise be
 // reported by the first kernel-launch check of this library as if the launch had failed.
@@ -264,6 +268,9 @@ static inline int grid_for(size_t n) { return (int)std::min<size_t>((n + 255) / 
 // ---- shared host functions ------------------------------------------------------------------------
 // snmf_api.hip
 int validate_params(const snmf_params* p);
+// The update masks of validated params (src/sparse_nmf.m:142-148, :176-179; a NULL mask is all true): the rows of h and the
+// columns of w that are updated, and w's mask as r bytes (w_ind, may be NULL).  Refuses an h mask that is neither all nor none.
+int read_update_masks(const snmf_params* p, int* n_h, int* n_w, uint8_t* w_ind);
 StepArgs make_args(snmf_plan* pl);
 int ensure_dyn_lds(int device, const void* kern, size_t lds);
 int g_gemm(snmf_plan* pl, const float* A, long long rsA, long long csA, const float* B, long long rsB, long long csB, float* C,

@@ -42,13 +42,7 @@ int plan_geometry(const snmf_params* pp, int n_cu, PlanGeometry* g) {
     const int F = p.F, T = p.T, r = p.r;
     // masks (src/sparse_nmf.m:142-148, :176-179)
     int n_h = 0, n_w = 0;
-    for (int k = 0; k < r; ++k) {
-        n_h += p.h_update_ind ? p.h_update_ind[k] != 0 : 1;
-        n_w += p.w_update_ind ? p.w_update_ind[k] != 0 : 1;
-    }
-    if (n_h != 0 && n_h != r)
-        // bsxfun(@plus, sum(w(:,h_ind))', p.sparsity) with sum(h_ind) ~= r rows: MATLAB size error
-        return fail(SNMF_ERR_DIM, "partial h_update_ind (%d of %d rows): dimension mismatch in src/sparse_nmf.m:192/197/202", n_h, r);
+    SN_TRY(read_update_masks(pp, &n_h, &n_w, nullptr));
     g->upd_h = n_h > 0;
     g->upd_w = n_w > 0;
     g->bm = (p.beta == 1.0) ? BM_KL : (p.beta == 2.0 ? BM_EUC : BM_GEN);

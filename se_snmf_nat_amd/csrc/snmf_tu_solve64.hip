@@ -5,6 +5,7 @@
 #include "snmf_internal.h"
 #include "snmf_solve64.h"
 #include "snmf_solve64_core.h"
+#include "snmf_host64.h"
 
 namespace {
 
@@ -28,9 +29,6 @@ struct Blocks64 {
         return SNMF_OK;
     }
 };
-
-inline int grid64(long long n) { return (int)std::max<long long>(1, std::min<long long>((n + 255) / 256, 8192)); }
-inline int n_splits(int K) { return (K + kS64ChunkK - 1) / kS64ChunkK; }
 
 struct Solve64 {
     hipStream_t st = nullptr;
@@ -90,36 +88,16 @@ struct Shape64 {
 
 int shape64(const snmf_params* p, Shape64* s) {
     SN_TRY(validate_params(p));
-    const int r = p->r;
-    s->w_ind.resize(r);
+    s->w_ind.resize(p->r);
     int n_h = 0, n_w = 0;
-    for (int k = 0; k < r; ++k) {
-        n_h += p->h_update_ind ? p->h_update_ind[k] != 0 : 1;
-        s->w_ind[k] = p->w_update_ind ? p->w_update_ind[k] != 0 : 1;
-        n_w += s->w_ind[k];
-    }
-    if (n_h != 0 && n_h != r)
-        return fail(SNMF_ERR_DIM, "partial h_update_ind (%d of %d rows): dimension mismatch in src/sparse_nmf.m:192/197/202", n_h, r);
+    SN_TRY(read_update_masks(p, &n_h, &n_w, s->w_ind.data()));
     s->upd_h = n_h > 0, s->upd_w = n_w > 0;
     const double beta = p->beta;
     s->mode = beta == 1.0 ? S64_KL : (beta == 2.0 ? S64_ED : (beta == 0.0 ? S64_IS : S64_GEN));
     return SNMF_OK;
 }
 
-// The workspace of one solve, carved out of one block in a fixed order (256-byte aligned pieces).  base == nullptr only
-// measures: the same walk gives the size a caller has to provide.
-struct Carve64 {
-    char* base;
-    size_t off = 0;
-    explicit Carve64(void* b) : base((char*)b) {}
-    void* bytes(size_t n) {
-        void* q = base ? base + off : nullptr;
-        off += (std::max<size_t>(n, 1) + 255) & ~(size_t)255;
-        return q;
-    }
-    double* f64(size_t n) { return (double*)bytes(n * sizeof(double)); }
-};
-
+// The workspace of one solve, carved out of one block in a fixed order (Carve64); the same walk measures it.
 struct Work64 {
     double *Lam, *R = nullptr, *D = nullptr, *Num = nullptr, *Den = nullptr, *Q = nullptr, *P = nullptr;
     double *cs = nullptr, *hs = nullptr, *sp = nullptr, *wn, *part, *div, *cost, *z = nullptr;
@@ -132,38 +110,32 @@ size_t carve64(const snmf_params* p, const Shape64& sh, void* base, Work64* w) {
     const size_t nFT = (size_t)F * T, nRT = (size_t)r * T, nFR = (size_t)F * r;
     const bool kl = sh.mode == S64_KL, ed = sh.mode == S64_ED;
     Carve64 c(base);
-    w->Lam = c.f64(nFT);
-    if (!ed) w->R = c.f64(nFT);
-    if (!ed && !kl) w->D = c.f64(nFT);
+    w->Lam = c.get<double>(nFT);
+    if (!ed) w->R = c.get<double>(nFT);
+    if (!ed && !kl) w->D = c.get<double>(nFT);
     if (sh.upd_h) {
-        w->Num = c.f64(nRT);
-        if (!kl) w->Den = c.f64(nRT);
-        else w->cs = c.f64(r);
+        w->Num = c.get<double>(nRT);
+        if (!kl) w->Den = c.get<double>(nRT);
+        else w->cs = c.get<double>(r);
     }
     if (sh.upd_w) {
-        w->Q = c.f64(nFR);
-        if (!kl) w->P = c.f64(nFR);
+        w->Q = c.get<double>(nFR);
+        if (!kl) w->P = c.get<double>(nFR);
         else {
-            w->hs = c.f64(r);
-            w->sp = c.f64((size_t)((T + kS64RowChunk - 1) / kS64RowChunk) * r);
+            w->hs = c.get<double>(r);
+            w->sp = c.get<double>((size_t)((T + kS64RowChunk - 1) / kS64RowChunk) * r);
         }
     }
-    // split partials: the largest nz * M * N over the products that are split at all
-    size_t need = 0;
-    auto want = [&](long long M, long long N, int K) {
-        const int nz = n_splits(K);
-        if (nz > 1) need = std::max(need, (size_t)nz * (size_t)M * (size_t)N);
-    };
-    want(F, T, r);                 // Lam = W * H
-    if (sh.upd_h) want(r, T, F);   // W' * R, W' * D
-    if (sh.upd_w) want(F, r, T);   // R * H', D * H'
-    if (need) w->z = c.f64(need);
-    w->wn = c.f64(r);
-    w->part = c.f64(2 * kS64Blocks);
-    w->div = c.f64(std::max(p->max_iter, 1));
-    w->cost = c.f64(std::max(p->max_iter, 1));
-    w->wi = (uint8_t*)c.bytes((size_t)r);
-    w->state = (Solve64State*)c.bytes(sizeof(Solve64State));
+    size_t need = split_partials(F, T, r, kS64ChunkK);                         // Lam = W * H
+    if (sh.upd_h) need = std::max(need, split_partials(r, T, F, kS64ChunkK));  // W' * R, W' * D
+    if (sh.upd_w) need = std::max(need, split_partials(F, r, T, kS64ChunkK));  // R * H', D * H'
+    if (need) w->z = c.get<double>(need);
+    w->wn = c.get<double>(r);
+    w->part = c.get<double>(2 * kS64Blocks);
+    w->div = c.get<double>(std::max(p->max_iter, 1));
+    w->cost = c.get<double>(std::max(p->max_iter, 1));
+    w->wi = c.get<uint8_t>(r);
+    w->state = c.get<Solve64State>(1);
     return c.off;
 }
 
@@ -288,7 +260,7 @@ int solve64_run(snmf_ctx* ctx, const snmf_params* p, double* dV, const double* d
             }
             hipLaunchKernelGGL(k_s64_stop, dim3(1), dim3(256), 0, st, dpart, kS64Blocks, it, p->conv_eps, div_scale, ddiv, dcost, dst);
             HIP_TRY(hipGetLastError());
-            if (polling && (it % 8 == 0) && it < max_iter) {  // the host looks every 8 iterations; the kernels past a stop are no-ops
+            if (polling && it % kPollEvery == 0 && it < max_iter) {  // the kernels past a stop are no-ops
                 HIP_TRY(hipMemcpyAsync(&h_state, dst, sizeof(h_state), hipMemcpyDeviceToHost, st));
                 HIP_TRY(hipStreamSynchronize(st));
                 if (h_state.stop) break;

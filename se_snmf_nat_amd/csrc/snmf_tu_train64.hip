@@ -12,6 +12,7 @@
 #include "snmf_internal.h"
 #include "snmf_frontend64.h"
 #include "snmf_solve64_core.h"
+#include "snmf_host64.h"
 
 namespace {
 
@@ -36,8 +37,6 @@ struct Dev64 {
         return SNMF_OK;
     }
 };
-
-inline int grid64(long long n) { return (int)std::max<long long>(1, std::min<long long>((n + 255) / 256, 8192)); }
 
 // a column-major rows x cols matrix between the host (leading dimension ld) and a tight device buffer
 int up2d(hipStream_t st, double* dst, const double* src, int64_t ld, int64_t rows, int64_t cols) {
