@@ -783,6 +783,36 @@ int snmf_sparse_nmf_batch_fp64(snmf_ctx* ctx, const snmf_params* p, int32_t n_pr
                                double* const* W, double* const* H, double* const* div_out, double* const* cost_out,
                                int32_t* n_iter_out);
 
+/* Added within 5.  The missing-data solves in the batch: snmf_mdi_fp64 (src/snmf_mdi.m / src/snmf_mdi_Sm.m) for n_problems
+ * problems, each with a mask of its own (M_b F x T_b, 1 = observed, soft masks in [0, 1]), in the shared launches of the fp64
+ * batch ("Batched missing-data solves").  fp64 only: the fused fp32 missing-data kernels have no batched form.
+ * THE CONTRACT: V_mdi, H, W, div, cost and n_iter of problem b are bit for bit those of snmf_mdi_fp64 run alone on V_b, M_b,
+ * W0_b, H0_b with the same settings -- whatever B, the slot, the other problems and the entry (one-shot or resident).
+ * snmf_batch_create_mdi_fp64 makes an fp64 batch whose problems carry masks: the validation, refusals and envelope of
+ * snmf_batch_create_fp64, checked before the device is touched; the masks take one more F x sum(T_b) block of doubles and
+ * reading v_MDI one of F x max(T_b), both counted in the free-memory check and in describe().  p->floor_v has no meaning
+ * (the masked start v = max(v .* M, 1e-9) floors, as in snmf_mdi_fp64).
+ * The call order is the batch's: create_mdi -> [set_sparsity for RVEC] -> set_problem_mdi for every k -> run -> get / get_v_mdi.
+ *   snmf_batch_set_problem_mdi_f64  V and M F x T_k (ldV, ldM >= F), W0 F x r, H0 r x T_k: a problem and its mask in one call.
+ *                                   On a batch made without masks: SNMF_ERR_STATE.  On a masked batch snmf_batch_set_problem_f64
+ *                                   / _f32 return SNMF_ERR_STATE.  Either refusal leaves the handle as it was.
+ *   snmf_batch_get_v_mdi_f64        the gain-matched final imputation (src/snmf_mdi.m:296-306) of problem k from the state the
+ *                                   last run left, F x T_k (ld >= F).  The problem's V, its estimate and its mask are not
+ *                                   written: a later run continues as if nothing had been read.  With max_iter = 0 it is the
+ *                                   imputation from the scaled initial factors, as in snmf_mdi_fp64.  Before the first run and on a
+ *                                   batch made without masks: SNMF_ERR_STATE.
+ * snmf_batch_set_sparsity_f64, _run, _get_f64 / _f32, _describe and _destroy are the entries above. */
+int snmf_batch_create_mdi_fp64(snmf_ctx* ctx, const snmf_params* p, int32_t n_problems, const int32_t* T, snmf_batch** out);
+int snmf_batch_set_problem_mdi_f64(snmf_batch* b, int32_t k, const double* V, int64_t ldV, const double* M, int64_t ldM,
+                                   const double* W0, const double* H0);
+int snmf_batch_get_v_mdi_f64(snmf_batch* b, int32_t k, double* V_mdi, int64_t ld);
+/* One-shot: the arguments of snmf_sparse_nmf_batch_fp64 plus M / ldM (n pointers, n leading dimensions) and the outputs V_mdi (n
+ * pointers, F x T_k each) with ldVm (n leading dimensions, or NULL: tight).  W may be NULL, and so may single entries of it. */
+int snmf_mdi_batch_fp64(snmf_ctx* ctx, const snmf_params* p, int32_t n_problems, const int32_t* T, const double* const* V,
+                        const int64_t* ldV, const double* const* M, const int64_t* ldM, const double* const* W0,
+                        const double* const* H0, const double* sparsity, double* const* V_mdi, const int64_t* ldVm,
+                        double* const* W, double* const* H, double* const* div_out, double* const* cost_out, int32_t* n_iter_out);
+
 /* ---- instrumentation (bench.py: HIP-event timing on the engine's own stream) ------------ */
 /* Average device time in milliseconds per launch of the named kernel family over the launches
  * recorded since snmf_ctx_timing(ctx, 1) was switched on.  Families: "hstep", "wstats",

@@ -90,6 +90,7 @@ SYMBOLS = [
     "snmf_batch_get_f64", "snmf_batch_get_f32", "snmf_batch_describe", "snmf_batch_destroy",
     "snmf_sparse_nmf_batch_f64", "snmf_sparse_nmf_batch_f32",
     "snmf_batch_create_fp64", "snmf_sparse_nmf_batch_fp64",
+    "snmf_batch_create_mdi_fp64", "snmf_batch_set_problem_mdi_f64", "snmf_batch_get_v_mdi_f64", "snmf_mdi_batch_fp64",
     "snmf_rccl_available", "snmf_rccl_get_unique_id", "snmf_rccl_comm_create", "snmf_rccl_comm_destroy", "snmf_plan_run_sharded_rccl",
 ]
 ABI_VERSION = 5  # include/snmf.h: SNMF_ABI_VERSION this binding was written against
@@ -363,6 +364,11 @@ def load():
     # its fp64 mode: the same handle type and the argument lists of the namesakes
     sig["snmf_batch_create_fp64"] = sig["snmf_batch_create"]
     sig["snmf_sparse_nmf_batch_fp64"] = sig["snmf_sparse_nmf_batch_f64"]
+    # the missing-data batch: a masked fp64 handle, a problem with its mask, v_MDI, and the one-shot
+    sig["snmf_batch_create_mdi_fp64"] = sig["snmf_batch_create"]
+    sig["snmf_batch_set_problem_mdi_f64"] = (C.c_int, [vp, i32, vp, i64, vp, i64, vp, vp])
+    sig["snmf_batch_get_v_mdi_f64"] = (C.c_int, [vp, i32, vp, i64])
+    sig["snmf_mdi_batch_fp64"] = (C.c_int, [vp, PP, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp])
     lib.snmf_abi_version.restype = C.c_int
     if lib.snmf_abi_version() != ABI_VERSION:  # a stale library must not be driven through newer prototypes
         raise ImportError(f"{path} has ABI version {lib.snmf_abi_version()}, this binding needs {ABI_VERSION}: rebuild the library")

@@ -4,6 +4,9 @@
     BatchPlan                               the resident handle: set_problem / run / get / describe / close
     sparse_nmf_batch_fp64, BatchPlan64      the same two in the fp64 mode (snmf_batch_create_fp64): every problem's results are
                                             bit for bit those of sparse_nmf(v, p, precision="fp64") run alone
+    snmf_mdi_batch, snmf_mdi_Sm_batch       the missing-data solves in the fp64 batch: a list of (v_mdi, h, objective), each bit
+                                            for bit snmf_mdi / snmf_mdi_Sm(v, mask, p, precision="fp64") run alone
+    BatchPlanMdi64                          their resident handle (snmf_batch_create_mdi_fp64): set_problem takes the mask too
 
 The problems share the row count F, the rank r and the settings `p`; every problem has its own frame count, its own initial
 factors and its own stop index.  All arithmetic happens in libsnmf_hip.so on the GPU; this module does the reference's
@@ -19,7 +22,8 @@ from . import _lib
 from ._lib import SnmfError
 from .api import _cf_to_beta, _colmajor, _display, _make_params, _mask, _ptr, default_context
 
-__all__ = ["sparse_nmf_batch", "BatchPlan", "sparse_nmf_batch_fp64", "BatchPlan64"]
+__all__ = ["sparse_nmf_batch", "BatchPlan", "sparse_nmf_batch_fp64", "BatchPlan64", "snmf_mdi_batch", "snmf_mdi_Sm_batch",
+           "BatchPlanMdi64"]
 
 
 def _check_batch_precision(precision):
@@ -53,6 +57,58 @@ def _objective(div, cost, ni, max_iter, cost_check):
         n = ni if ni < max_iter else max_iter  # :279-280 truncate to 1:it on convergence
         return {"div": div[:n].copy(), "cost": cost[:n].copy(), "n_iter": ni}
     return {"div": np.zeros(max_iter), "cost": np.zeros(max_iter), "n_iter": ni}
+
+
+def _batch_inits(p, vs, m):
+    """src/sparse_nmf.m:116-140 for a batch: the list forms of init_w / init_h -> (r, init_w per problem or None, init_h list or None)."""
+    B = len(vs)
+    iw = p.get("init_w", None)
+    if iw is None:
+        if p.get("r", None) is None:
+            raise SnmfError(2, "Number of components or initialization must be given")
+        r = int(p["r"])
+        iws = [None] * B
+    else:
+        if isinstance(iw, (list, tuple)):
+            if len(iw) != B:
+                raise SnmfError(3, f"init_w is a list of {len(iw)}, the batch has {B} problems")
+            iws = [np.asarray(x, dtype=np.float64) for x in iw]
+        else:
+            iws = [np.asarray(iw, dtype=np.float64)] * B
+        for x in iws:
+            if x.ndim != 2 or x.shape[0] != m:
+                raise SnmfError(3, f"init_w is {x.shape}, v has {m} rows")
+            if x.shape[1] != iws[0].shape[1]:
+                raise SnmfError(3, f"init_w is {x.shape}, problem 0 has {iws[0].shape[1]} columns: a batch shares the rank")
+        ri = iws[0].shape[1]
+        r = int(p["r"]) if (p.get("r", None) is not None and ri < int(p["r"])) else ri
+    ih = p.get("init_h", None)
+    ihs = None
+    if ih is not None:
+        if isinstance(ih, str) or not isinstance(ih, (list, tuple)) or len(ih) != B:
+            raise SnmfError(3, f"init_h must be a list of {B} arrays (r x T_b each), or absent")
+        ihs = [np.asarray(x, dtype=np.float64) for x in ih]
+        for v, x in zip(vs, ihs):
+            if x.shape != (r, v.shape[1]):
+                raise SnmfError(3, f"init_h is {x.shape}, expected ({r}, {v.shape[1]})")
+    return r, iws, ihs
+
+
+def _batch_draws(vs, m, r, iws, ihs, rng, dt):
+    """The initial factors of every problem, drawn in list order from one generator (w then h, as one solve draws them)."""
+    w0s, h0s = [], []
+    for k, v in enumerate(vs):
+        n = v.shape[1]
+        if iws[k] is None:
+            w0 = rng.random_sample((m, r))
+        elif iws[k].shape[1] < r:
+            w0 = np.concatenate([iws[k], rng.random_sample((m, r - iws[k].shape[1]))], axis=1)
+        else:
+            w0 = iws[k]
+        h0 = rng.random_sample((r, n)) if ihs is None else ihs[k]
+        w0s.append(np.asfortranarray(w0, dtype=dt))
+        h0s.append(np.asfortranarray(h0, dtype=dt))
+    return w0s, h0s
 
 
 def sparse_nmf_batch(vs, p=None, *, ctx=None, dtype=np.float64, rng=None, precision="fp32"):
@@ -100,35 +156,7 @@ def _solve_batch(vs, p, ctx, dtype, rng, mode):
     if rng is None:  # :112-114
         rng = np.random.RandomState(int(random_seed) if random_seed and random_seed > 0 else None)
 
-    # :116-131
-    iw = p.get("init_w", None)
-    if iw is None:
-        if p.get("r", None) is None:
-            raise SnmfError(2, "Number of components or initialization must be given")
-        r = int(p["r"])
-        iws = [None] * B
-    else:
-        if isinstance(iw, (list, tuple)):
-            if len(iw) != B:
-                raise SnmfError(3, f"init_w is a list of {len(iw)}, the batch has {B} problems")
-            iws = [np.asarray(x, dtype=np.float64) for x in iw]
-        else:
-            iws = [np.asarray(iw, dtype=np.float64)] * B
-        for x in iws:
-            if x.ndim != 2 or x.shape[0] != m:
-                raise SnmfError(3, f"init_w is {x.shape}, v has {m} rows")
-            if x.shape[1] != iws[0].shape[1]:
-                raise SnmfError(3, f"init_w is {x.shape}, problem 0 has {iws[0].shape[1]} columns: a batch shares the rank")
-        ri = iws[0].shape[1]
-        r = int(p["r"]) if (p.get("r", None) is not None and ri < int(p["r"])) else ri
-    ih = p.get("init_h", None)
-    if ih is not None:
-        if isinstance(ih, str) or not isinstance(ih, (list, tuple)) or len(ih) != B:
-            raise SnmfError(3, f"init_h must be a list of {B} arrays (r x T_b each), or absent")
-        ihs = [np.asarray(x, dtype=np.float64) for x in ih]
-        for v, x in zip(vs, ihs):
-            if x.shape != (r, v.shape[1]):
-                raise SnmfError(3, f"init_h is {x.shape}, expected ({r}, {v.shape[1]})")
+    r, iws, ihs = _batch_inits(p, vs, m)  # :116-131
     w_ind = _mask(p, "w_update_ind", r)
     h_ind = _h_ind_all_or_none(p, r)
     kind, scalar, sarr = _batch_sparsity(p.get("sparsity", 0), r)
@@ -136,19 +164,7 @@ def _solve_batch(vs, p, ctx, dtype, rng, mode):
         raise SnmfError(4, "Reference to non-existent field 'cost_check'.")
     cost_check = 1 if p["cost_check"] else 0
 
-    # the draws, in list order (:116-140)
-    w0s, h0s = [], []
-    for k, v in enumerate(vs):
-        n = v.shape[1]
-        if iws[k] is None:
-            w0 = rng.random_sample((m, r))
-        elif iws[k].shape[1] < r:
-            w0 = np.concatenate([iws[k], rng.random_sample((m, r - iws[k].shape[1]))], axis=1)
-        else:
-            w0 = iws[k]
-        h0 = rng.random_sample((r, n)) if ih is None else ihs[k]
-        w0s.append(np.asfortranarray(w0, dtype=dt))
-        h0s.append(np.asfortranarray(h0, dtype=dt))
+    w0s, h0s = _batch_draws(vs, m, r, iws, ihs, rng, dt)  # the draws, in list order (:116-140)
 
     sp = _make_params(m, 1, r, beta, max_iter, conv_eps, cost_check, True, kind, scalar, w_ind, h_ind)
     lib = _lib.load()
@@ -279,3 +295,130 @@ class BatchPlan64(BatchPlan):
     def __init__(self, ctx, F, r, Ts, *, beta=1.0, max_iter=100, conv_eps=0.0, cost_check=True, floor_v=True, sparsity=0.0,
                  w_update_ind=None, h_update_ind=None):
         self._init(ctx, F, r, Ts, beta, max_iter, conv_eps, cost_check, floor_v, sparsity, w_update_ind, h_update_ind)
+
+
+def snmf_mdi_batch(vs, Dms, p=None, *, ctx=None, rng=None, info=None):
+    """[v_MDI, h, objective] = snmf_mdi(v, Dm, p) for every (v, Dm) of the two lists, solved together in the fp64 batch
+    (snmf_mdi_batch_fp64).  Dm: 1 = observed, 0 = missing.  p: snmf_mdi's settings, shared (sparsity_mdi a scalar or an r-vector,
+    conv_eps_mdi, cost_check, ...), with init_w / init_h in the list forms of sparse_nmf_batch and the draws in list order.
+    Returns a list of (v_mdi, h, objective); info, when given, receives info["w"], the list of each problem's dictionary.
+    Problem k's results are bit for bit those of snmf_mdi(vs[k], Dms[k], p_k, precision="fp64") run alone."""
+    return _mdi_batch(vs, [np.asarray(d) != 0 for d in Dms], p, ctx, rng, info)
+
+
+def snmf_mdi_Sm_batch(vs, Sms, p=None, *, ctx=None, rng=None, info=None):
+    """snmf_mdi_batch for soft masks in [0, 1]: problem k is snmf_mdi_Sm(vs[k], Sms[k], p_k, precision="fp64") bit for bit."""
+    return _mdi_batch(vs, Sms, p, ctx, rng, info)
+
+
+def _mdi_batch(vs, masks, p, ctx, rng, info):
+    """The host side of the two entries above: api._mdi's defaulting and errors (src/snmf_mdi.m:83-93, :260) and the batch's
+    refusals, all before the library is loaded; then one call of snmf_mdi_batch_fp64."""
+    p = dict(p or {})
+    dt = np.dtype(np.float64)
+    vs = [np.asarray(v) for v in vs]
+    masks = [np.asarray(mk, dtype=np.float64) for mk in masks]
+    B = len(vs)
+    if B == 0:
+        raise SnmfError(1, "the batch is empty: vs must hold at least one matrix")
+    if len(masks) != B:
+        raise SnmfError(3, f"{len(masks)} masks for {B} problems")
+    for k, (v, mk) in enumerate(zip(vs, masks)):
+        if v.ndim != 2 or v.shape[1] < 1:
+            raise SnmfError(1, "every v must be a 2-D matrix with at least one column")
+        if mk.shape != v.shape:
+            raise SnmfError(3, f"the mask of problem {k} is {mk.shape}, its v is {v.shape}")
+    m = vs[0].shape[0]
+    for k, v in enumerate(vs):
+        if v.shape[0] != m:
+            raise SnmfError(3, f"v of problem {k} has {v.shape[0]} rows, problem 0 has {m}: a batch shares the row count")
+    max_iter = int(p.get("max_iter", 100))  # src/snmf_mdi.m:83-85
+    seed = p.get("random_seed", 1)
+    if "sparsity" not in p:  # :87-89 (the default is installed only when p.sparsity is ABSENT)
+        p.setdefault("sparsity_mdi", 0)
+    if "conv_eps" not in p:  # :91-93
+        p.setdefault("conv_eps_mdi", 0)
+    for fld in ("sparsity_mdi", "conv_eps_mdi", "cost_check"):
+        if fld not in p:
+            raise KeyError(f"Reference to non-existent field '{fld}'.")
+    beta = _cf_to_beta(p)
+    if rng is None:
+        rng = np.random.RandomState(int(seed) if seed and seed > 0 else None)
+    r, iws, ihs = _batch_inits(p, vs, m)
+    w_ind = _mask(p, "w_update_ind", r)
+    h_ind = _h_ind_all_or_none(p, r)
+    kind, scalar, sarr = _batch_sparsity(p["sparsity_mdi"], r)
+    cost_check = 1 if p["cost_check"] else 0
+    conv_eps = float(p["conv_eps_mdi"])
+    w0s, h0s = _batch_draws(vs, m, r, iws, ihs, rng, dt)
+
+    sp = _make_params(m, 1, r, beta, max_iter, conv_eps, cost_check, True, kind, scalar, w_ind, h_ind)
+    lib = _lib.load()
+    ctx = ctx or default_context()
+    vv = [_colmajor(v, dt) for v in vs]
+    mm = [_colmajor(mk, dt) for mk in masks]
+    Ts = np.array([v.shape[1] for v in vs], np.int32)
+    ld = lambda arrs: np.array([(a.strides[1] // dt.itemsize) if a.shape[1] > 1 else m for a in arrs], np.int64)  # noqa: E731
+    ldv, ldm = ld(vv), ld(mm)
+    Vm = [np.empty(v.shape, dtype=dt, order="F") for v in vs]
+    W = [np.empty((m, r), dtype=dt, order="F") for _ in vs]
+    H = [np.empty((r, v.shape[1]), dtype=dt, order="F") for v in vs]
+    nh = max(max_iter, 1)
+    div = [np.zeros(nh) for _ in vs]
+    cost = [np.zeros(nh) for _ in vs]
+    n_iter = np.zeros(B, np.int32)
+
+    def ptrs(arrs):
+        return (C.c_void_p * B)(*[a.ctypes.data for a in arrs])
+
+    _lib.check(lib.snmf_mdi_batch_fp64(ctx._h, C.byref(sp), B, _ptr(Ts), ptrs(vv), _ptr(ldv), ptrs(mm), _ptr(ldm), ptrs(w0s), ptrs(h0s),
+                                       _ptr(sarr) if sarr is not None else None, ptrs(Vm), None, ptrs(W), ptrs(H), ptrs(div), ptrs(cost),
+                                       _ptr(n_iter)))
+    if info is not None:
+        info["w"] = W
+    out = []
+    for k in range(B):
+        ni = int(n_iter[k])
+        n = ni if ni < max_iter else max_iter  # src/snmf_mdi.m:286-287: truncation on convergence only
+        out.append((Vm[k], H[k], {"div": div[k][:n].copy(), "cost": cost[k][:n].copy(), "n_iter": ni}))
+    return out
+
+
+class BatchPlanMdi64(BatchPlan64):
+    """BatchPlan64 for missing-data solves (snmf_batch_create_mdi_fp64): set_problem takes the problem's mask (1 = observed, soft
+    masks in [0, 1]) and get_v_mdi(k) reads the gain-matched final imputation of problem k from the state the last run left,
+    without writing it: run(n) + get_v_mdi + run() gives the bytes of one run().  Every problem's results are bit for bit those
+    of snmf_mdi / snmf_mdi_Sm(..., precision="fp64") on it alone.  floor_v has no meaning here (the masked start floors)."""
+
+    _create = "snmf_batch_create_mdi_fp64"
+
+    def set_problem(self, k, v, mask, w0, h0):
+        k = int(k)
+        if not 0 <= k < self.B:
+            raise SnmfError(1, f"problem index {k} outside [0, {self.B})")
+        dt = np.dtype(np.float64)
+        v, mask = np.asarray(v), np.asarray(mask, dtype=np.float64)
+        T = int(self.Ts[k])
+        if v.shape != (self.F, T):
+            raise SnmfError(3, f"v is {v.shape}, problem {k} is ({self.F}, {T})")
+        if mask.shape != v.shape:
+            raise SnmfError(3, f"the mask is {mask.shape}, v is {v.shape}")
+        w0, h0 = np.asarray(w0), np.asarray(h0)
+        if w0.shape != (self.F, self.r):
+            raise SnmfError(3, f"init_w is {w0.shape}, v has {self.F} rows")
+        if h0.shape != (self.r, T):
+            raise SnmfError(3, f"init_h is {h0.shape}, expected ({self.r}, {T})")
+        vv, mm = _colmajor(v, dt), _colmajor(mask, dt)
+        w0 = np.asfortranarray(w0, dtype=dt)
+        h0 = np.asfortranarray(h0, dtype=dt)
+        ld = lambda a: a.strides[1] // dt.itemsize if T > 1 else self.F  # noqa: E731
+        _lib.check(self._lib.snmf_batch_set_problem_mdi_f64(self._h, k, _ptr(vv), ld(vv), _ptr(mm), ld(mm), _ptr(w0), _ptr(h0)))
+        self.ctx.sync()  # (the host arrays may go out of scope)
+
+    def get_v_mdi(self, k):
+        k = int(k)
+        if not 0 <= k < self.B:
+            raise SnmfError(1, f"problem index {k} outside [0, {self.B})")
+        out = np.empty((self.F, int(self.Ts[k])), dtype=np.float64, order="F")
+        _lib.check(self._lib.snmf_batch_get_v_mdi_f64(self._h, k, _ptr(out), self.F))
+        return out

@@ -43,6 +43,7 @@ struct B64Args {
     const B64Prob* prob;
     const double* S;  // r-vector sparsity (kind 1)
     double *V, *Lam, *R, *D, *H, *Num, *Den, *W, *Q, *P;
+    const double* M;  // the masks of a missing-data batch (F x sum(T_b), at V's frame offsets); nullptr on a plain batch
     double *cs, *hs, *sp, *wn, *part, *divh, *costh;
     const uint8_t* w_ind;
     Solve64State* st;
@@ -129,6 +130,28 @@ __global__ __launch_bounds__(256) void k_b64_obj(B64Args a) {
     const long long o = p.fr0 * a.F;
     s64_obj_block<MODE>(a.V + o, a.Lam + o, (long long)a.F * p.T, a.beta, a.H + p.fr0 * a.r, a.kind, a.scalar, a.S, a.r,
                         (long long)a.r * p.T, a.part + (long long)b * 2 * kS64Blocks, red, blockIdx.x, gridDim.x);
+}
+
+// ---- the missing-data steps of a masked batch (snmf_batch_create_mdi_fp64): the bodies of k_s64_mdi_impute / k_s64_mdi_obj
+// grid (workgroups, B): the re-imputation alone (cost_check = 0).  V and Lam of a stopped problem stay those of its stop iterate.
+static __global__ __launch_bounds__(256) void k_b64_mdi_impute(B64Args a) {
+    const int b = blockIdx.y;
+    if (a.st[b].stop) return;
+    const B64Prob p = a.prob[b];
+    const long long o = p.fr0 * a.F;
+    s64_mdi_impute_span(a.V + o, a.M + o, a.Lam + o, (long long)a.F * p.T, blockIdx.x, gridDim.x);
+}
+
+// grid (kS64Blocks, B): the re-imputation fused with the objective of the imputed v, in the place of k_b64_obj
+template <int MODE>
+__global__ __launch_bounds__(256) void k_b64_mdi_obj(B64Args a) {
+    const int b = blockIdx.y;
+    if (a.st[b].stop) return;
+    __shared__ double red[256];
+    const B64Prob p = a.prob[b];
+    const long long o = p.fr0 * a.F;
+    s64_mdi_obj_block<MODE>(a.V + o, a.M + o, a.Lam + o, (long long)a.F * p.T, a.beta, a.H + p.fr0 * a.r, a.kind, a.scalar, a.S, a.r,
+                            (long long)a.r * p.T, a.part + (long long)b * 2 * kS64Blocks, red, blockIdx.x, gridDim.x);
 }
 
 // grid (B): the fixed tree over problem b's partials, its objective vectors and its stop test (src/sparse_nmf.m:272-284);

@@ -5,6 +5,9 @@
 // allowed when, how far a run goes, when the host looks at the stopped counter, what get() reports -- is the same and is
 // written here.  The modes are told apart where the handle is made (snmf_batch_create / snmf_batch_create_fp64) and nowhere else:
 // nothing in this file asks which engine it drives.
+// A handle made by snmf_batch_create_mdi_fp64 is a batch of missing-data solves (`masked`): its problems are set together with
+// their masks (batch_set_problem_mdi), and the imputed V of a problem can be read (batch_get_v_mdi); everything else -- run, get,
+// describe, destroy, the new batch on a used handle -- is the life below, unchanged.
 #pragma once
 #include <memory>
 
@@ -20,6 +23,7 @@ struct snmf_batch {
     std::vector<uint8_t> have;
     int n_have = 0;
     bool have_s = false, ran = false;
+    bool masked = false;  // a batch of missing-data solves: set by the engine that was made for one, before batch_create
     int it_done = 0;
     std::vector<double> h_div, h_cost;  // the objective histories on the host, hist_len() entries per problem
     int hist_len() const { return std::max(1, p.max_iter); }
@@ -36,6 +40,12 @@ struct snmf_batch {
     // problem k from host arrays, and its initial scaling (src/sparse_nmf.m:157-169)
     virtual int load(int k, const double* V, int64_t ldV, const double* W0, const double* H0) = 0;
     virtual int load(int k, const float* V, int64_t ldV, const float* W0, const float* H0) = 0;
+    // a masked batch: problem k with its mask (1 = observed), the initial scaling and the masked start (src/snmf_mdi.m:175)
+    virtual int load_mdi(int, const double*, int64_t, const double*, int64_t, const double*, const double*) {
+        return fail(SNMF_ERR_UNSUPPORTED, "this batch engine has no missing-data form");
+    }
+    // a masked batch: the gain-matched final imputation (:296-306) of problem k to the host; the problem's state is not written
+    virtual int fetch_v_mdi(int, double*, int64_t) { return fail(SNMF_ERR_UNSUPPORTED, "this batch engine has no missing-data form"); }
     virtual int iterate(int it) = 0;  // enqueues iteration it (it_done == it - 1)
     virtual int close_run() = 0;      // enqueues what a run that ends at it_done still owes
     struct Device {                   // what a run reads back: the stopped counter, the B states of the engine's own type, the histories
@@ -53,7 +63,7 @@ struct snmf_batch {
     virtual void describe(char* buf, size_t buflen) const = 0;
 };
 
-snmf_batch* batch64_new();  // snmf_tu_batch64.hip: an fp64 engine, not built yet
+snmf_batch* batch64_new(bool masked = false);  // snmf_tu_batch64.hip: an fp64 engine (masked: of missing-data solves), not built yet
 
 #define BATCH_CHECK(b)                                          \
     if (!(b)) return fail(SNMF_ERR_INVALID, "batch is NULL");   \
@@ -101,12 +111,9 @@ inline int batch_set_sparsity(snmf_batch* b, const double* sparsity) {
     return SNMF_OK;
 }
 
-template <typename TT>
-int batch_set_problem(snmf_batch* b, int32_t k, const TT* V, int64_t ldV, const TT* W0, const TT* H0) {
-    BATCH_CHECK(b);
+// what every set_problem entry does before it loads: the index, and the new batch a set after a run starts
+inline int batch_begin_set(snmf_batch* b, int32_t k) {
     if (k < 0 || k >= b->B) return fail(SNMF_ERR_INVALID, "problem index %d outside [0, %d)", k, b->B);
-    if (!V || !W0 || !H0) return fail(SNMF_ERR_INVALID, "snmf_batch_set_problem: V, W0 or H0 of problem %d is NULL", k);
-    if (ldV < b->p.F) return fail(SNMF_ERR_INVALID, "ldV = %lld is below F = %d", (long long)ldV, b->p.F);
     if (b->ran) {  // a new batch on the same handle: every problem is set again
         std::fill(b->have.begin(), b->have.end(), 0);
         b->n_have = 0;
@@ -114,11 +121,42 @@ int batch_set_problem(snmf_batch* b, int32_t k, const TT* V, int64_t ldV, const 
         b->it_done = 0;
         SN_TRY(b->reset());
     }
-    SN_TRY(b->load(k, V, ldV, W0, H0));
+    return SNMF_OK;
+}
+inline void batch_mark_set(snmf_batch* b, int32_t k) {
     if (!b->have[k]) {
         b->have[k] = 1;
         ++b->n_have;
     }
+}
+
+template <typename TT>
+int batch_set_problem(snmf_batch* b, int32_t k, const TT* V, int64_t ldV, const TT* W0, const TT* H0) {
+    BATCH_CHECK(b);
+    if (b->masked)  // (refused before anything changes: the handle stays as it was)
+        return fail(SNMF_ERR_STATE, "snmf_batch_set_problem on a missing-data batch: its problems are set by snmf_batch_set_problem_mdi_f64");
+    if (k < 0 || k >= b->B) return fail(SNMF_ERR_INVALID, "problem index %d outside [0, %d)", k, b->B);
+    if (!V || !W0 || !H0) return fail(SNMF_ERR_INVALID, "snmf_batch_set_problem: V, W0 or H0 of problem %d is NULL", k);
+    if (ldV < b->p.F) return fail(SNMF_ERR_INVALID, "ldV = %lld is below F = %d", (long long)ldV, b->p.F);
+    SN_TRY(batch_begin_set(b, k));
+    SN_TRY(b->load(k, V, ldV, W0, H0));
+    batch_mark_set(b, k);
+    return SNMF_OK;
+}
+
+// a problem of a masked batch and its mask in one call: a problem never exists without its mask
+inline int batch_set_problem_mdi(snmf_batch* b, int32_t k, const double* V, int64_t ldV, const double* M, int64_t ldM, const double* W0,
+                                 const double* H0) {
+    BATCH_CHECK(b);
+    if (!b->masked)
+        return fail(SNMF_ERR_STATE, "snmf_batch_set_problem_mdi_f64 on a batch that was not made by snmf_batch_create_mdi_fp64");
+    if (k < 0 || k >= b->B) return fail(SNMF_ERR_INVALID, "problem index %d outside [0, %d)", k, b->B);
+    if (!V || !M || !W0 || !H0) return fail(SNMF_ERR_INVALID, "snmf_batch_set_problem_mdi_f64: V, M, W0 or H0 of problem %d is NULL", k);
+    if (ldV < b->p.F || ldM < b->p.F)
+        return fail(SNMF_ERR_INVALID, "ldV = %lld, ldM = %lld: each must be at least F = %d", (long long)ldV, (long long)ldM, b->p.F);
+    SN_TRY(batch_begin_set(b, k));
+    SN_TRY(b->load_mdi(k, V, ldV, M, ldM, W0, H0));
+    batch_mark_set(b, k);
     return SNMF_OK;
 }
 
@@ -175,4 +213,15 @@ int batch_get(snmf_batch* b, int32_t k, TT* W, TT* H, double* div_out, double* c
     int n_iter = 0;
     if (n_iter_out) *n_iter_out = b->stopped(k, &n_iter) ? n_iter : b->it_done;
     return SNMF_OK;
+}
+
+// v_MDI of problem k from the state the last run left (after run(n): of the iterate reached); a later run continues unchanged
+inline int batch_get_v_mdi(snmf_batch* b, int32_t k, double* V_mdi, int64_t ld) {
+    BATCH_CHECK(b);
+    if (!b->masked) return fail(SNMF_ERR_STATE, "snmf_batch_get_v_mdi_f64 on a batch that was not made by snmf_batch_create_mdi_fp64");
+    if (k < 0 || k >= b->B) return fail(SNMF_ERR_INVALID, "problem index %d outside [0, %d)", k, b->B);
+    if (!V_mdi) return fail(SNMF_ERR_INVALID, "V_mdi is NULL");
+    if (ld < b->p.F) return fail(SNMF_ERR_INVALID, "ld = %lld is below F = %d", (long long)ld, b->p.F);
+    if (!b->ran) return fail(SNMF_ERR_STATE, "snmf_batch_get_v_mdi_f64 before snmf_batch_run");
+    return b->fetch_v_mdi(k, V_mdi, ld);
 }

@@ -374,6 +374,20 @@ __device__ __forceinline__ double s64_impute(double v, double m, double lam) { r
 // The re-imputation of every iteration fused with the objective of the imputed v (:257-268): V is read once and written
 // once, and the partials have the element assignment, the workgroup tree and the slots of k_s64_obj -- with M = 1 the
 // objective is the plain solve's bit for bit.  Lam is the max(w * h, flr) the last product left: the reference's v_est.
+// (The body of workgroup bx of gx, as every pass above: k_s64_mdi_obj and the batched solve's k_b64_mdi_obj call it.)
+template <int MODE>
+__device__ __forceinline__ void s64_mdi_obj_block(double* __restrict__ V, const double* __restrict__ M, const double* __restrict__ Lam,
+                                                  long long n_v, double beta, const double* __restrict__ H, int kind, double scalar,
+                                                  const double* __restrict__ S, int r, long long n_h, double* __restrict__ part,
+                                                  double* red, unsigned bx, unsigned gx) {
+    double d = 0.0;
+    for (long long i = (long long)bx * 256 + threadIdx.x; i < n_v; i += (long long)gx * 256) {
+        const double lam = Lam[i], v = s64_impute(V[i], M[i], lam);
+        V[i] = v;
+        d = s64_div_add<MODE>(d, v, lam, beta);
+    }
+    s64_obj_tail(d, H, kind, scalar, S, r, n_h, part, red, bx, gx);
+}
 template <int MODE>
 __global__ __launch_bounds__(256) void k_s64_mdi_obj(double* __restrict__ V, const double* __restrict__ M, const double* __restrict__ Lam,
                                                      long long n_v, double beta, const double* __restrict__ H, int kind, double scalar,
@@ -381,20 +395,18 @@ __global__ __launch_bounds__(256) void k_s64_mdi_obj(double* __restrict__ V, con
                                                      const int* stop) {
     if (*stop) return;
     __shared__ double red[256];
-    double d = 0.0;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n_v; i += (long long)gridDim.x * 256) {
-        const double lam = Lam[i], v = s64_impute(V[i], M[i], lam);
-        V[i] = v;
-        d = s64_div_add<MODE>(d, v, lam, beta);
-    }
-    s64_obj_tail(d, H, kind, scalar, S, r, n_h, part, red, blockIdx.x, gridDim.x);
+    s64_mdi_obj_block<MODE>(V, M, Lam, n_v, beta, H, kind, scalar, S, r, n_h, part, red, blockIdx.x, gridDim.x);
 }
 
 // cost_check = 0: the re-imputation alone
+__device__ __forceinline__ void s64_mdi_impute_span(double* __restrict__ V, const double* __restrict__ M, const double* __restrict__ Lam,
+                                                    long long n, unsigned bx, unsigned gx) {
+    for (long long i = (long long)bx * 256 + threadIdx.x; i < n; i += (long long)gx * 256) V[i] = s64_impute(V[i], M[i], Lam[i]);
+}
 static __global__ __launch_bounds__(256) void k_s64_mdi_impute(double* __restrict__ V, const double* __restrict__ M,
                                                                const double* __restrict__ Lam, long long n, const int* stop) {
     if (*stop) return;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) V[i] = s64_impute(V[i], M[i], Lam[i]);
+    s64_mdi_impute_span(V, M, Lam, n, blockIdx.x, gridDim.x);
 }
 
 // The gain-matched final imputation (:296-306 / snmf_mdi_Sm.m:302-309), one wave per frame t (four frames a workgroup):
@@ -402,6 +414,7 @@ static __global__ __launch_bounds__(256) void k_s64_mdi_impute(double* __restric
 // Lane l sums the rows l, l + 64, ... in row order and the 64 lane sums meet in a fixed butterfly, so the result depends on
 // neither the grid nor the timing; the second pass finds the frame in the cache.  Runs after the loop: no stop test.
 // Vm may be V itself (every element is read and then written by the same lane).
+// (The batched solve launches this kernel and k_s64_mdi_start as they are, on one problem's arrays.)
 static __global__ __launch_bounds__(256) void k_s64_mdi_final(const double* V, const double* __restrict__ M, const double* __restrict__ Lam,
                                                               int F, long long T, double* Vm) {
     const int lane = threadIdx.x & 63;

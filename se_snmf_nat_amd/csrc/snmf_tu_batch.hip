@@ -3,8 +3,9 @@
 // with its own frame count, advance in shared launches: per iteration one H step over every (problem, tile), one W-statistics
 // launch over every (problem, chunk) and one finish launch over every (problem, column); a problem whose stop test fired is
 // frozen on the device.  The life of the handle -- validation, call order, the run loop and its polls of the stopped counter,
-// what get() reports -- is snmf_batch_host.h's, shared with the fp64 engine of snmf_tu_batch64.hip; the two entries that make a
-// handle are the one place that chooses between the engines.
+// what get() reports -- is snmf_batch_host.h's, shared with the fp64 engine of snmf_tu_batch64.hip; the entries that make a
+// handle (snmf_batch_create, _create_fp64 and _create_mdi_fp64: the fp64 engine with masks) are the one place that chooses between
+// the engines.
 #include "snmf_internal.h"
 #include "snmf_batch.h"
 #include "snmf_batch_host.h"
@@ -336,6 +337,9 @@ extern "C" int snmf_batch_create(snmf_ctx* ctx, const snmf_params* p, int32_t n_
 extern "C" int snmf_batch_create_fp64(snmf_ctx* ctx, const snmf_params* p, int32_t n_problems, const int32_t* T, snmf_batch** out) {
     return batch_create("snmf_batch_create_fp64", batch64_new(), ctx, p, n_problems, T, out);
 }
+extern "C" int snmf_batch_create_mdi_fp64(snmf_ctx* ctx, const snmf_params* p, int32_t n_problems, const int32_t* T, snmf_batch** out) {
+    return batch_create("snmf_batch_create_mdi_fp64", batch64_new(true), ctx, p, n_problems, T, out);
+}
 extern "C" void snmf_batch_destroy(snmf_batch* b) {
     if (!b) return;
     hipSetDevice(b->ctx->device);
@@ -349,6 +353,11 @@ extern "C" int snmf_batch_set_problem_f64(snmf_batch* b, int32_t k, const double
 extern "C" int snmf_batch_set_problem_f32(snmf_batch* b, int32_t k, const float* V, int64_t ldV, const float* W0, const float* H0) {
     return batch_set_problem<float>(b, k, V, ldV, W0, H0);
 }
+extern "C" int snmf_batch_set_problem_mdi_f64(snmf_batch* b, int32_t k, const double* V, int64_t ldV, const double* M, int64_t ldM,
+                                              const double* W0, const double* H0) {
+    return batch_set_problem_mdi(b, k, V, ldV, M, ldM, W0, H0);
+}
+extern "C" int snmf_batch_get_v_mdi_f64(snmf_batch* b, int32_t k, double* V_mdi, int64_t ld) { return batch_get_v_mdi(b, k, V_mdi, ld); }
 extern "C" int snmf_batch_run(snmf_batch* b, int32_t n_iters) { return batch_run(b, n_iters); }
 extern "C" int snmf_batch_get_f64(snmf_batch* b, int32_t k, double* W, double* H, double* div_out, double* cost_out, int32_t* n_iter_out) {
     return batch_get<double>(b, k, W, H, div_out, cost_out, n_iter_out);
@@ -399,4 +408,30 @@ extern "C" int snmf_sparse_nmf_batch_fp64(snmf_ctx* ctx, const snmf_params* p, i
                                           double* const* W, double* const* H, double* const* div_out, double* const* cost_out,
                                           int32_t* n_iter_out) {
     return batch_oneshot<double>(ctx, p, n, T, V, ldV, W0, H0, sparsity, W, H, div_out, cost_out, n_iter_out, true);
+}
+
+// the missing-data one-shot: create_mdi, set every problem with its mask, run to the end, get, read v_MDI, destroy
+extern "C" int snmf_mdi_batch_fp64(snmf_ctx* ctx, const snmf_params* p, int32_t n, const int32_t* T, const double* const* V,
+                                   const int64_t* ldV, const double* const* M, const int64_t* ldM, const double* const* W0,
+                                   const double* const* H0, const double* sparsity, double* const* V_mdi, const int64_t* ldVm,
+                                   double* const* W, double* const* H, double* const* div_out, double* const* cost_out,
+                                   int32_t* n_iter_out) {
+    if (!ctx || !p || !T || !V || !ldV || !M || !ldM || !W0 || !H0 || !V_mdi || !H) return fail(SNMF_ERR_INVALID, "snmf_mdi_batch_fp64: NULL argument");
+    if (p->sparsity_kind == SNMF_SPARSITY_RVEC && !sparsity) return fail(SNMF_ERR_INVALID, "SNMF_SPARSITY_RVEC needs the sparsity vector");
+    for (int i = 0; i < n; ++i)
+        if (!V[i] || !M[i] || !W0[i] || !H0[i] || !V_mdi[i] || !H[i])
+            return fail(SNMF_ERR_INVALID, "snmf_mdi_batch_fp64: an array of problem %d is NULL", i);
+    snmf_batch* b = nullptr;
+    SN_TRY(snmf_batch_create_mdi_fp64(ctx, p, n, T, &b));
+    int s = SNMF_OK;
+    if (p->sparsity_kind == SNMF_SPARSITY_RVEC) SN_STEP(s, snmf_batch_set_sparsity_f64(b, sparsity));
+    for (int i = 0; i < n; ++i) SN_STEP(s, batch_set_problem_mdi(b, i, V[i], ldV[i], M[i], ldM[i], W0[i], H0[i]));
+    SN_STEP(s, snmf_batch_run(b, 0));
+    for (int i = 0; i < n; ++i) {
+        SN_STEP(s, batch_get<double>(b, i, W ? W[i] : nullptr, H[i], div_out ? div_out[i] : nullptr, cost_out ? cost_out[i] : nullptr,
+                                     n_iter_out ? n_iter_out + i : nullptr));
+        SN_STEP(s, batch_get_v_mdi(b, i, V_mdi[i], ldVm ? ldVm[i] : (int64_t)p->F));
+    }
+    snmf_batch_destroy(b);
+    return s;
 }

@@ -3,6 +3,10 @@
 // for launch, with every launch grouped over the problems; the tables that map a workgroup to (problem, tile, split) and the
 // per-problem GEMM arguments are built once, when the batch is made, from the frame counts and the addresses of the one device
 // block.  A translation unit of its own: the fp32 batch, its kernels and its geometry are not touched.
+// A masked engine (snmf_batch_create_mdi_fp64) is the same engine with solve64_run's missing-data steps: one more F x sum(T_b)
+// block for the masks, the masked start when a problem is set, the grouped re-imputation (fused with the objective when there is
+// one) at the end of an iteration, and the gain-matched final imputation into a scratch block when v_MDI is read.  Without masks
+// nothing of this is allocated or launched.
 #include "snmf_internal.h"
 #include "snmf_batch64.h"
 #include "snmf_batch_host.h"
@@ -36,6 +40,10 @@ struct Batch64 final : snmf_batch {
     B64Args a{};
     double* S = nullptr;
     double* zbuf = nullptr;
+    double* Mblk = nullptr;   // masked: the masks, F x sum(T_b) at V's frame offsets (a.M is the kernels' read-only view)
+    double* Vm = nullptr;     // masked: F x max T_b, where the final imputation of one problem is formed before it is copied out
+    size_t mask_bytes = 0;
+    bool lam_done = false;    // Lam = max(W * H, flr) of the scaled initial factors has been formed since the last reset
     B64Prob* dprob = nullptr;
     uint8_t* dwi = nullptr;
     Family fLam, fH, fW;
@@ -54,6 +62,10 @@ struct Batch64 final : snmf_batch {
     int upload_sparsity(const double* sparsity) override;
     int load(int k, const double* V, int64_t ldV, const double* W0, const double* H0) override { return load_t(k, V, ldV, W0, H0); }
     int load(int k, const float* V, int64_t ldV, const float* W0, const float* H0) override { return load_t(k, V, ldV, W0, H0); }
+    int load_mdi(int k, const double* V, int64_t ldV, const double* M, int64_t ldM, const double* W0, const double* H0) override {
+        return load_t(k, V, ldV, W0, H0, M, ldM);
+    }
+    int fetch_v_mdi(int k, double* V_mdi, int64_t ld) override;
     int iterate(int it) override;
     int close_run() override { return SNMF_OK; }  // (the objective and the stop test of an iteration run inside it)
     Device device() override { return Device{a.n_stopped, a.st, h_st.data(), sizeof(Solve64State), a.divh, a.costh}; }
@@ -67,7 +79,7 @@ struct Batch64 final : snmf_batch {
     void describe(char* buf, size_t buflen) const override;
 
     template <typename TT>
-    int load_t(int k, const TT* V, int64_t ldV, const TT* W0, const TT* H0);
+    int load_t(int k, const TT* V, int64_t ldV, const TT* W0, const TT* H0, const TT* M = nullptr, int64_t ldM = 0);
     template <typename TT>
     int fetch_t(int k, TT* W, TT* H);
 };
@@ -81,6 +93,12 @@ size_t carve(Batch64* s, void* base) {
     Carve64 c(base);
     a.V = c.get<double>(F * sT);
     a.Lam = c.get<double>(F * sT);
+    s->Mblk = s->Vm = nullptr;
+    if (s->masked) {
+        s->Mblk = c.get<double>(F * sT);
+        s->Vm = c.get<double>(F * (size_t)s->maxT);
+    }
+    a.M = s->Mblk;
     a.R = ed ? nullptr : c.get<double>(F * sT);
     a.D = (ed || kl) ? nullptr : c.get<double>(F * sT);
     a.H = c.get<double>(r * sT);
@@ -142,6 +160,7 @@ int Batch64::reset() {
     hipStream_t st = ctx->stream;
     const size_t nB = (size_t)B;
     h_st.assign(nB, Solve64State{0, 0, INFINITY});  // src/sparse_nmf.m:168
+    lam_done = false;
     HIP_TRY(hipMemcpyAsync(a.st, h_st.data(), sizeof(Solve64State) * nB, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(a.n_stopped, 0, sizeof(int), st));
     HIP_TRY(hipMemsetAsync(a.divh, 0, sizeof(double) * nB * a.max_iter, st));  // :171-173
@@ -197,6 +216,7 @@ int Batch64::build(const int32_t* T) {
     a.conv_eps = p.conv_eps;
     a.div_scale = mode == S64_GEN ? p.beta * (p.beta - 1.0) : 1.0;
     bytes = carve(this, nullptr);
+    mask_bytes = masked ? sizeof(double) * (size_t)F * (size_t)sumT : 0;
 
     // ---- the device
     (void)hipGetLastError();
@@ -303,6 +323,7 @@ int Batch64::build(const int32_t* T) {
         if (upd_h) n += ratio + prod(pNum) + (kl ? 1 : prod(pDen)) + 1 + lam;
         if (upd_w) n += ratio + prod(pQ) + (kl ? 2 : prod(pP)) + 1 + lam;
         if (p.cost_check) n += 2;
+        else if (masked) n += 1;  // the re-imputation runs objective or not (src/snmf_mdi.m:251-254)
         launches = n;
     }
     return SNMF_OK;
@@ -315,7 +336,7 @@ int Batch64::upload_sparsity(const double* sparsity) {
 }
 
 template <typename TT>
-int Batch64::load_t(int k, const TT* V, int64_t ldV, const TT* W0, const TT* H0) {
+int Batch64::load_t(int k, const TT* V, int64_t ldV, const TT* W0, const TT* H0, const TT* M, int64_t ldM) {
     const B64Prob& q = prob[k];
     const int F = a.F, r = a.r, T = q.T;
     const long long nFT = (long long)F * T, nRT = (long long)r * T;
@@ -323,6 +344,7 @@ int Batch64::load_t(int k, const TT* V, int64_t ldV, const TT* W0, const TT* H0)
     hipStream_t st = ctx->stream;
     // (tight on the device; fp32 arrays are widened on the way in)
     SN_TRY((xfer_pack_in<TT, double>(ctx, V, ldV, F, T, dV, F, T, false)));
+    if (masked) SN_TRY((xfer_pack_in<TT, double>(ctx, M, ldM, F, T, Mblk + q.fr0 * F, F, T, false)));
     SN_TRY((xfer_pack_in<TT, double>(ctx, H0, r, r, T, dH, r, T, false)));
     SN_TRY((xfer_pack_in<TT, double>(ctx, W0, F, F, r, dW, F, r, false)));
     // the initial scaling (:157-169) with the single solve's own kernels, on this problem's arrays
@@ -330,7 +352,10 @@ int Batch64::load_t(int k, const TT* V, int64_t ldV, const TT* W0, const TT* H0)
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_s64_hscale, dim3(grid64(nRT)), dim3(256), 0, st, dH, dwn, r, nRT);
     HIP_TRY(hipGetLastError());
-    if (p.floor_v) {
+    if (masked) {  // src/snmf_mdi.m:175, the masked start (it floors: floor_v has no meaning here)
+        hipLaunchKernelGGL(k_s64_mdi_start, dim3(grid64(nFT)), dim3(256), 0, st, dV, (const double*)(Mblk + q.fr0 * F), nFT);
+        HIP_TRY(hipGetLastError());
+    } else if (p.floor_v) {
         hipLaunchKernelGGL(k_s64_floor, dim3(grid64(nFT)), dim3(256), 0, st, dV, nFT);
         HIP_TRY(hipGetLastError());
     }
@@ -379,13 +404,27 @@ int objective(Batch64* s) {
     }
 }
 
+// the re-imputation and the objective of the imputed v in one pass, in the place of objective() on a masked batch
+int mdi_objective(Batch64* s) {
+    const dim3 g(kS64Blocks, s->B);
+    switch (s->mode) {
+        case S64_KL: return grouped(s, k_b64_mdi_obj<S64_KL>, g);
+        case S64_ED: return grouped(s, k_b64_mdi_obj<S64_ED>, g);
+        case S64_IS: return grouped(s, k_b64_mdi_obj<S64_IS>, g);
+        default: return grouped(s, k_b64_mdi_obj<S64_GEN>, g);
+    }
+}
+
 // One iteration, the launches of solve64_run grouped over the problems.
 int Batch64::iterate(int it) {
     hipStream_t st = ctx->stream;
     const int r = a.r;
     const bool kl = mode == S64_KL;
     auto lam = [&]() { return product(this, fLam, pLam); };  // lambda = max(w * h, flr)
-    if (it == 1) SN_TRY(lam());                              // of the scaled initial factors
+    if (it == 1) {                                           // of the scaled initial factors
+        SN_TRY(lam());
+        lam_done = true;
+    }
     const dim3 g_rt(elem_grid(this, r), B), g_col(r, B);
     if (upd_h) {  // :189-208
         SN_TRY(ratio(this));
@@ -407,8 +446,10 @@ int Batch64::iterate(int it) {
         SN_TRY(kl ? grouped(this, k_b64_wupd<true>, g_col) : grouped(this, k_b64_wupd<false>, g_col));
         SN_TRY(lam());
     }
+    if (masked && !p.cost_check)  // src/snmf_mdi.m:251-254: v is re-imputed in every iteration, objective or not
+        SN_TRY(grouped(this, k_b64_mdi_impute, dim3(elem_grid(this, a.F), B)));
     if (p.cost_check) {  // :248-284
-        SN_TRY(objective(this));
+        SN_TRY(masked ? mdi_objective(this) : objective(this));
         hipLaunchKernelGGL(k_b64_stop, dim3(B), dim3(256), 0, st, a, it);
         HIP_TRY(hipGetLastError());
     }
@@ -423,18 +464,41 @@ int Batch64::fetch_t(int k, TT* W, TT* H) {
     return SNMF_OK;
 }
 
+// src/snmf_mdi.m:296-306 for problem k with the single solve's own kernel, into the scratch block: V, Lam and the mask of the
+// problem are read only, so a later run continues as if nothing had been read.
+int Batch64::fetch_v_mdi(int k, double* V_mdi, int64_t ld) {
+    const B64Prob& q = prob[k];
+    const int F = a.F, T = q.T;
+    const long long o = q.fr0 * F, groups = ((long long)T + 3) / 4;  // a wave per frame
+    if (!lam_done) {  // max_iter = 0: no iteration ran, and the single solve imputes from Lam of the scaled initial factors
+        SN_TRY(product(this, fLam, pLam));
+        lam_done = true;
+    }
+    hipLaunchKernelGGL(k_s64_mdi_final, dim3((unsigned)std::min<long long>(groups, 65536)), dim3(256), 0, ctx->stream,
+                       (const double*)(a.V + o), (const double*)(Mblk + o), (const double*)(a.Lam + o), F, (long long)T, Vm);
+    HIP_TRY(hipGetLastError());
+    return xfer_unpack_out<double, double>(ctx, Vm, F, F, T, V_mdi, ld);
+}
+
 void Batch64::describe(char* buf, size_t buflen) const {
     const char* mn = mode == S64_KL ? "kl" : (mode == S64_ED ? "ed" : (mode == S64_IS ? "is" : "beta"));
     const int ge = elem_grid(this, a.F), gh = elem_grid(this, a.r);
-    snprintf(buf, buflen,
+    const int n = snprintf(buf, buflen,
              "batch fp64 B=%d F=%d r=%d %s upd_h=%d upd_w=%d frames=%lld | k_b64_gemm tables (problem, 64x64 tile, split of %d): "
              "lam=%lld h=%lld w=%lld x256 | k_b64_sumz entries lam=%d h=%d w=%d rows=%d | k_b64_ratio grid=(%d,%d) k_b64_hupd grid=(%d,%d) "
-             "k_b64_colsum/k_b64_wupd grid=(%d,%d) k_b64_rowsum grid=(%d,%d,%d) k_b64_obj grid=(%d,%d) k_b64_stop grid=%d | "
+             "k_b64_colsum/k_b64_wupd grid=(%d,%d) k_b64_rowsum grid=(%d,%d,%d) %s grid=(%d,%d) k_b64_stop grid=%d | "
              "launches_per_iter=%d bytes=%zu poll_every=%d",
              B, a.F, a.r, mn, (int)upd_h, (int)upd_w, sumT, kS64ChunkK, fLam.n, fH.n, fW.n, pLam.n_sums, pNum.n_sums, pQ.n_sums,
-             sRow ? B : 0, ge, B, gh, B, a.r, B, (a.r + 255) / 256, max_rowz, B, kS64Blocks, B, B, launches, bytes, kPollEvery);
+             sRow ? B : 0, ge, B, gh, B, a.r, B, (a.r + 255) / 256, max_rowz, B, masked ? "k_b64_mdi_obj" : "k_b64_obj", kS64Blocks, B, B, launches, bytes, kPollEvery);
+    if (masked && n > 0 && (size_t)n < buflen)  // (bytes above counts both blocks)
+        snprintf(buf + n, buflen - (size_t)n, " | mdi: k_b64_mdi_impute grid=(%d,%d) mask_bytes=%zu v_mdi_scratch_bytes=%zu", ge, B,
+                 mask_bytes, sizeof(double) * (size_t)a.F * (size_t)maxT);
 }
 
 }  // namespace
 
-snmf_batch* batch64_new() { return new Batch64(); }
+snmf_batch* batch64_new(bool masked) {
+    Batch64* b = new Batch64();
+    b->masked = masked;
+    return b;
+}
