@@ -9,7 +9,12 @@
  * ctypes (se_snmf_nat_amd/_lib.py).  Every entry point below names the reference lines it replaces.
  *
  * Conventions: all matrices are column-major (MATLAB layout) with explicit leading dimensions
- * where given; plain pointers and sizes only; every function returns an snmf_status and never
+ * where given (a rows x cols matrix with leading dimension ld >= rows holds (cols - 1) * ld + rows elements, the BLAS convention:
+ * nothing past the last column's last row is read or written, nor the rows between `rows` and ld of any column; a leading
+ * dimension below the row count is SNMF_ERR_INVALID and nothing is written; arguments without one are tight); a HOST matrix handed
+ * to snmf_plan_set_*, snmf_multi_set_* or snmf_batch_set_problem_* may be overwritten or freed as soon as the call returns (a
+ * device buffer is read later, on the context's stream);
+ * plain pointers and sizes only; every function returns an snmf_status and never
  * throws; snmf_last_error() returns a thread-local message for the last failure.
  * There is NO CPU fallback: without a usable HIP device every compute entry point fails with
  * SNMF_ERR_NO_DEVICE.

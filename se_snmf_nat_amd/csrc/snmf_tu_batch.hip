@@ -421,6 +421,12 @@ extern "C" int snmf_mdi_batch_fp64(snmf_ctx* ctx, const snmf_params* p, int32_t 
     for (int i = 0; i < n; ++i)
         if (!V[i] || !M[i] || !W0[i] || !H0[i] || !V_mdi[i] || !H[i])
             return fail(SNMF_ERR_INVALID, "snmf_mdi_batch_fp64: an array of problem %d is NULL", i);
+    // every leading dimension before anything runs: ldVm[i] is only looked at when problem i is read back, after the solve and
+    // after the results of the problems before it have been written
+    for (int i = 0; i < n; ++i)
+        if (ldV[i] < p->F || ldM[i] < p->F || (ldVm && ldVm[i] < p->F))
+            return fail(SNMF_ERR_INVALID, "snmf_mdi_batch_fp64: problem %d has ldV = %lld, ldM = %lld, ldVm = %lld: each must be at least F = %d", i,
+                        (long long)ldV[i], (long long)ldM[i], (long long)(ldVm ? ldVm[i] : p->F), p->F);
     snmf_batch* b = nullptr;
     SN_TRY(snmf_batch_create_mdi_fp64(ctx, p, n, T, &b));
     int s = SNMF_OK;
