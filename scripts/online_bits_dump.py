@@ -1,6 +1,17 @@
 #!/usr/bin/env python3
-"""Bits of the online separators on the 124-frame fixture (shipped settings, adaptation on), dumped to an .npz: the
-single-stream fp64 separator, and every path of the batched separator that runs through its host driver
+"""Bits of the online separators on the 124-frame fixture (shipped settings, adaptation on), dumped to an .npz: every path
+of the single-stream separator that runs through its host driver (csrc/snmf_online_host.h) in both modes --
+  single_f64                   the fp64 separator (the four arrays this script has always written)
+  one_f32 / one_f64            default settings
+  one_f32_fixed / one_f64_fixed  adapt_train_N = 0: all frame solves of a call in one launch
+  one_f32_semi                 basis_update_N = 1: the semi-supervised frame solve
+  one_f32_mel1 / one_f32_mel0  B_sep_mode 'Mel' with MelConv 1 and 0
+  one_f32_co                   class_outputs without a partition
+  one_f32_cls / one_f64_cls    class_outputs with the 2 + 2 class partition
+  one_f32_fed<n>               the partition run fed in 160- / 1000- / 57-sample pieces, the flush in a call of its own
+  one_f32_big                  R_x = R_d = 500 over 20 hops: the frame solve through the plan loop
+-- per group x_tilde_f, the int16 stream, with class_outputs x_hat, d_hat and the class signals, the final B_DFT_d (Mel: and
+B_Mel_d) and every field of the trace; and every path of the batched separator that runs through its host driver
 (csrc/snmf_online_batch_host.h) in both modes --
   batch_f32 / batch_f64        three heterogeneous streams (the fixture is stream 1), class_outputs, fp64 with a class partition
   batch_f32_cls                the fp32 batch with the class partition
@@ -53,6 +64,49 @@ o = sep.process(s, flush=True)
 out.update(single_f64_x_tilde_f=o["x_tilde_f"], single_f64_i16=o["x_tilde"], single_f64_basis=sep.basis_f64(),
            single_f64_adapt_iters=np.array([t["adapt_iters"] for t in sep.trace()]))
 sep.close()
+
+
+def one(tag, p=p, precision="fp32", pieces=None, x=s, dicts=(Bx, Bd), draws=(H0, Ad0), **kw):
+    """One single-stream separator on `x`: in one call with the flush, or in `pieces`-sample calls and the flush on its own."""
+    sep = OnlineSeparator(dicts[0], dicts[1], p, H0=draws[0], Ad_blk0=draws[1], ctx=ctx, precision=precision, **kw)
+    if pieces is None:
+        parts = [sep.process(x, flush=True)]
+    else:
+        parts = [sep.process(x[i:i + pieces]) for i in range(0, len(x), pieces)] + [sep.process(x[:0], flush=True)]
+    for key in parts[0]:
+        out["%s_%s" % (tag, key)] = np.concatenate([q[key] for q in parts], axis=-1)
+    out[tag + "_basis"] = sep.basis_f64()
+    if sep.mel:
+        out[tag + "_mel_basis"] = sep.mel_basis()
+    tr = sep.trace()
+    for key in tr[0]:
+        out["%s_tr_%s" % (tag, key)] = np.array([t[key] for t in tr])
+    sep.close()
+
+
+mm = mel_matrix(p["fs"], 64, p["fftlength"], 1.0, p["fs"] / 2).T
+BM = mm @ B
+BM = BM / np.sqrt((BM ** 2).sum(0)) + 1e-9  # the stored form of run_basis_train.m:115-116
+one("one_f32")
+one("one_f32_fixed", p=dict(p, adapt_train_N=0), class_outputs=True)
+one("one_f32_semi", p=dict(p, basis_update_N=1), class_outputs=True)
+for conv in (1, 0):
+    one("one_f32_mel%d" % conv, p=dict(p, B_sep_mode="Mel", MelConv=conv, F_order=64), class_outputs=True, B_Mel_x=BM[:, :100],
+        B_Mel_d=BM[:, 100:])
+one("one_f32_co", class_outputs=True)
+one("one_f32_cls", p=dict(p, **CLS), class_outputs=True)
+for n in (160, 1000, 57):
+    one("one_f32_fed%d" % n, p=dict(p, **CLS), class_outputs=True, pieces=n)
+rs = np.random.RandomState(1024)  # tests/test_online.py: the exemplar geometry's dictionaries
+Bbig = rs.gamma(0.6, 1.0, (513, 1000)) + 1e-3
+Bbig = Bbig / np.sqrt((Bbig ** 2).sum(0)) + 1e-9
+rs = np.random.RandomState(7)
+one("one_f32_big", x=s[:20 * 160], dicts=(Bbig[:, :500], Bbig[:, 500:]), draws=(rs.random_sample(1000), rs.random_sample((50, 100))))
+one("one_f64", precision="fp64")
+one("one_f64_fixed", p=dict(p, adapt_train_N=0), precision="fp64", class_outputs=True)
+one("one_f64_cls", p=dict(p, **CLS), precision="fp64", class_outputs=True)
+assert all(out["one_%s_tr_solved" % t].sum() > 0 for t in ("f32", "f32_mel1", "f32_mel0", "f32_cls", "f32_fed57", "f64", "f64_cls"))
+assert not out["one_f32_fixed_tr_solved"].any() and out["one_f32_cls_x_hat_i"].shape[0] == 2
 rs = np.random.RandomState(5)
 pcms = [np.round(s[1733:1733 + 40 * 160] * 0.75 + rs.randn(40 * 160) * 30.0), s, np.round(s[:30 * 160 + 57] * 0.5)]
 Bds = [Bd[:, rs.permutation(100)], Bd, Bd * (1.0 + 0.05 * rs.random_sample(Bd.shape))]
@@ -87,9 +141,6 @@ out.update(batch_f32_x_tilde_f=out["batch_f32_s1_x_tilde_f"], batch_f32_i16=out[
            batch_f32_adapt_iters=out["batch_f32_s1_adapt_iters"])  # (the names this script has always written)
 batch("batch_f32_cls", pcms, Bds, H0s, Ads, p=dict(p, **CLS))
 batch("batch_f64", pcms, Bds, H0s, Ads, p=dict(p, **CLS), precision="fp64")
-mm = mel_matrix(p["fs"], 64, p["fftlength"], 1.0, p["fs"] / 2).T
-BM = mm @ B
-BM = BM / np.sqrt((BM ** 2).sum(0)) + 1e-9  # the stored form of run_basis_train.m:115-116
 for conv in (0, 1):
     batch("mel%d" % conv, pcms, Bds, H0s, Ads, p=dict(p, B_sep_mode="Mel", MelConv=conv, F_order=64), B_Mel_x=BM[:, :100],
           B_Mel_d=[BM[:, 100:], BM[:, 100:] * 1.01, BM[:, 100:]])

@@ -28,14 +28,16 @@ _TU_HDRS = {
     "snmf_tu_wstats.hip": ["snmf_generic.h", "snmf_wstats_dispatch.h"],
     "snmf_tu_wstats4.hip": ["snmf_generic.h", "snmf_wstats_dispatch.h"],
     "snmf_tu_wstats8.hip": ["snmf_generic.h", "snmf_wstats_dispatch.h"],
-    "snmf_tu_online.hip": ["snmf_online_common.h", "snmf_online.h", "snmf_online_f64_host.h", "snmf_online_classes.h"],
+    "snmf_tu_online.hip": ["snmf_online_common.h", "snmf_online.h", "snmf_online_f64_host.h", "snmf_online_host.h",
+                           "snmf_online_classes.h"],
     "snmf_tu_online_f64.hip": ["snmf_online_common.h", "snmf_online_f64_core.h", "snmf_online_f64.h", "snmf_online_f64_host.h",
-                               "snmf_online_classes.h"],
+                               "snmf_online_host.h", "snmf_online_classes.h"],
     "snmf_tu_online_batch.hip": ["snmf_online_common.h", "snmf_online_batch_common.h", "snmf_online_batch.h",
-                                 "snmf_online_batch_f64_host.h", "snmf_online_batch_host.h", "snmf_online_classes.h"],
+                                 "snmf_online_batch_f64_host.h", "snmf_online_batch_host.h", "snmf_online_host.h",
+                                 "snmf_online_classes.h"],
     "snmf_tu_online_batch_f64.hip": ["snmf_online_common.h", "snmf_online_batch_common.h", "snmf_online_f64_core.h",
                                      "snmf_online_batch_f64.h", "snmf_online_batch_f64_host.h", "snmf_online_batch_host.h",
-                                     "snmf_online_classes.h"],
+                                     "snmf_online_host.h", "snmf_online_classes.h"],
     "snmf_tu_multi.hip": ["snmf_multi.h"],
     "snmf_tu_dnmf.hip": ["snmf_frontend.h", "snmf_philox.h"],
     "snmf_tu_smallf.hip": ["snmf_smallf.h"],

@@ -2,7 +2,7 @@
 // (snmf_tu_online_batch.hip: fp32, handle snmf_online_batch; snmf_tu_online_batch_f64.hip: fp64, handle OnlineBatchF64).
 // Host code only: no kernel and no device function lives here.
 //
-// Per stream, the hop queue / history / flush logic of snmf_online_process_f32 (snmf_tu_online.hip); on the device, one fixed
+// Per stream, the hop queue / history / flush logic of snmf_online_process_f32 (snmf_online_host.h); on the device, one fixed
 // sequence of launches per frame step for all streams (frame solve, post-filter, class spectra, gated adaptation) -- with
 // the dictionary fixed, one launch of each for the whole chunk.  A chunk synchronises ONCE: outputs, statuses and
 // adaptation verdicts are copied back together at its end.
@@ -22,6 +22,7 @@
 #pragma once
 #include "snmf_internal.h"
 #include "snmf_online_batch_common.h"
+#include "snmf_online_host.h"  // online_frame_record: a frame's status as the trace holds it
 
 constexpr size_t kBTraceCap = 1u << 16;   // per stream: the newest 65536 frames, as snmf_online_trace
 constexpr int64_t kBChunkSlots = 16384;  // (frame, stream) slots of one device chunk
@@ -300,9 +301,7 @@ int obatch_run_chunk(H* o, const std::vector<int>& nfr, const std::vector<int>& 
     for (int s = 0; s < S; ++s) {
         for (int i = 0; i < nfr[s]; ++i) {
             const OnlineStatus& q = hs[(size_t)i * S + s];
-            snmf_online_frame tr{};
-            tr.n_iter = q.n_iter; tr.trig = q.trig; tr.n_up = q.n_up; tr.beta = q.beta; tr.A_x_mag = q.A_x_mag; tr.A_d_mag = q.A_d_mag;
-            tr.Q_control = q.Q_control;
+            snmf_online_frame tr = online_frame_record(q);
             if (p.adapt_train_N && q.do_solve && q.n_up > 0) {
                 tr.solved = 1;
                 tr.adapt_iters = hit[(size_t)i * S + s];

@@ -5,17 +5,16 @@
 // Host side of src/bnmf_sep_event_RT_IS16.m + the frame loop of src/NTF_sep_event_RT.m:54-135.  The
 // host only sequences launches: per frame it reads one 32-byte status (did the adaptation condition
 // fire?) and, when it did, runs the W-only adaptation solve through the engine's ordinary plan.
+// The host driver is snmf_online_host.h, shared with the fp64 mode.  What is left here: the C entries and the snmf_online
+// handle's own members (the engine's plans, Mel mode, the fp32 mirrors of the dictionaries), validation and creation, and
+// the fp32 mode's steps of the driver (om_*).
 #include "snmf_online.h"
 #include "snmf_online_f64_host.h"  // the fp64 mode's host entry points (its kernels live in snmf_tu_online_f64.hip)
-#include "snmf_online_classes.h"
+#include "snmf_online_host.h"
 
-constexpr size_t kTraceCap = 1u << 16;  // diagnostics ring: the newest 65536 frames (~11 min at 100 frames/s)
-struct snmf_online {
-    snmf_ctx* ctx = nullptr;
-    snmf_online_params p{};
-    OnlineF64* f64 = nullptr;  // non-null: an fp64 separator (snmf_online_create_f64); every field below p is then unused
-    int F = 0, r = 0, N = 0, nov = 0;
-    int Fs = 0;               // rows of the solves: F, or F_order in Mel mode
+struct snmf_online : OnlineState<float> {
+    OnlineF64* f64 = nullptr;  // non-null: an fp64 separator (snmf_online_create_f64); only ctx and p are then used
+    int Fs = 0;                // rows of the solves: F, or F_order in Mel mode
     int mel = 0, mel_conv = 0, n1 = 0;  // B_sep_mode = 'Mel' (snmf_online_set_mel)
     float *melmat = nullptr, *Bmf = nullptr, *Ymel = nullptr;
     double *Bm = nullptr, *Bmtmp = nullptr;  // [n1 x r] Mel dictionaries [B_Mel_x | B_Mel_d], fp64 like B
@@ -26,63 +25,33 @@ struct snmf_online {
     DevState* bst = nullptr;
     double *bdiv = nullptr, *bcost = nullptr;
     OnlineStatus* bstatus = nullptr;
-    float *recon1 = nullptr, *breco = nullptr;
+    float *recon1 = nullptr, *breco = nullptr;  // B_x*A_x | B_d*A_d from the frame solve: one frame / a batch
     // cooperative single-launch adaptation solve (k_wadapt)
     bool wadapt = false;
     int wa_nwg = 0;
     size_t wa_lds = 0;
     double *wa_W = nullptr, *wa_p1 = nullptr, *wa_p2 = nullptr, *wa_cost = nullptr;
     int* wa_nit = nullptr;
-    unsigned* wa_bar = nullptr;  // B_x*A_x | B_d*A_d from the frame solve: one frame / a batch
-    double *B = nullptr, *Bfix = nullptr, *Btmp = nullptr;  // fp64 like the engine's W master copy (k_wapply)
-    float *Bf = nullptr;                                    // fp32 mirror of B for the reconstructions
-    float *H0 = nullptr, *lambda_dav = nullptr, *Xm_tilde = nullptr,
-          *r_blk = nullptr, *ldblk = nullptr, *adblk = nullptr, *Vad = nullptr, *Had = nullptr, *win_s = nullptr,
-          *win_i = nullptr, *syn_tail = nullptr, *syn_tail_x = nullptr, *syn_tail_d = nullptr;
-    float2* tw = nullptr;
-    uint8_t* rup = nullptr;
-    OnlineDev* dev = nullptr;
+    unsigned* wa_bar = nullptr;
+    float* Bf = nullptr;  // fp32 mirror of B (fp64 like the engine's W master copy, k_wapply) for the reconstructions
     OnlineStatus* status = nullptr;
     DevState* hst = nullptr;
     double *hdiv = nullptr, *hcost = nullptr;
-    OnlineStatus* h_status = nullptr;  // pinned
-    // per-call buffers (grown on demand)
-    int cap_frames = 0;
-    float *sig = nullptr, *Ym = nullptr, *Xt = nullptr, *Xh = nullptr, *Dh = nullptr, *syn = nullptr, *outf = nullptr;
-    float2* Yph = nullptr;
-    int16_t* out16 = nullptr;
-    // per-class outputs (snmf_online_set_classes): n_ev event classes then n_cls - n_ev noise classes; n_cls = 0: none set
-    int n_ev = 0, n_cls = 0;
-    int* cls = nullptr;         // [n_cls + 1] column ranges over [B_x | B_d] (snmf_online_classes.h)
-    float* tail_c = nullptr;    // [n_cls][nov - 1 frames] one overlap-add tail per class
-    float *Xc = nullptr, *syn_c = nullptr, *out_c = nullptr;  // per call, class-major: spectra, synthesis frames, hops
-    // host state of the driver loop
-    std::vector<float> pending, hist;
-    int64_t l = 0;  // frames processed
-    bool finished = false;
-    bool failed = false;  // a device batch failed midway: frame counter, history and rings are no longer consistent
-    std::deque<snmf_online_frame> trace;  // bounded: the newest kTraceCap frames (a real-time stream runs for days)
 };
 
-static void online_free_call_buffers(snmf_online* o) {
-    void* ptrs[] = {o->sig, o->Ym, o->Xt, o->Xh, o->Dh, o->syn, o->outf, o->Yph, o->out16, o->bst, o->bdiv, o->bcost, o->bstatus, o->breco, o->Ymel,
-                    o->Xc, o->syn_c, o->out_c};
-    o->Xc = o->syn_c = o->out_c = nullptr;
-    o->Ymel = nullptr;
-    o->breco = nullptr;
+// the one-launch frame solves' plan and buffers, and the Mel features: they depend on the solve geometry
+static void om_free_call(snmf_online* o) {
     if (o->hb) {
         snmf_plan_destroy(o->hb);
         o->hb = nullptr;
     }
+    void* ptrs[] = {o->bst, o->bdiv, o->bcost, o->bstatus, o->breco, o->Ymel};
+    for (void* q : ptrs)
+        if (q) hipFree(q);
     o->bst = nullptr;
     o->bdiv = o->bcost = nullptr;
     o->bstatus = nullptr;
-    for (void* q : ptrs)
-        if (q) hipFree(q);
-    o->sig = o->Ym = o->Xt = o->Xh = o->Dh = o->syn = o->outf = nullptr;
-    o->Yph = nullptr;
-    o->out16 = nullptr;
-    o->cap_frames = 0;
+    o->breco = o->Ymel = nullptr;
 }
 
 extern "C" void snmf_online_destroy(snmf_online* o) {
@@ -111,14 +80,11 @@ extern "C" void snmf_online_destroy(snmf_online* o) {
     if (o->hp) snmf_plan_destroy(o->hp);
     if (o->ap) snmf_plan_destroy(o->ap);
     if (o->hsemi) snmf_plan_destroy(o->hsemi);
-    online_free_call_buffers(o);
-    void* ptrs[] = {o->B,   o->Bfix, o->Btmp,  o->H0,    o->lambda_dav, o->Xm_tilde, o->r_blk, o->ldblk, o->adblk,  o->Vad,
-                    o->Had, o->win_s, o->win_i, o->syn_tail, o->tw,       o->rup,      o->dev,   o->status, o->hst,   o->hdiv,
-                    o->hcost, o->syn_tail_x, o->syn_tail_d, o->Bf, o->recon1, o->wa_W, o->wa_p1, o->wa_p2, o->wa_cost, o->wa_nit, o->wa_bar, o->melmat, o->Bmf, o->Bm, o->Bmtmp,
-                    o->cls, o->tail_c};
+    online_free_state(o);
+    void* ptrs[] = {o->status, o->hst, o->hdiv, o->hcost, o->Bf, o->recon1, o->wa_W, o->wa_p1, o->wa_p2, o->wa_cost, o->wa_nit, o->wa_bar,
+                    o->melmat, o->Bmf, o->Bm, o->Bmtmp};
     for (void* q : ptrs)
         if (q) hipFree(q);
-    if (o->h_status) hipHostFree(o->h_status);
     delete o;
 }
 
@@ -218,42 +184,20 @@ extern "C" int snmf_online_create(snmf_ctx* ctx, const snmf_online_params* p, co
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     snmf_online* o = new snmf_online();
-    o->ctx = ctx;
-    o->p = *p;
-    const int N = p->fftlength, F = N / 2 + 1, r = p->R_x + p->R_d, sz = p->framelength, hop = p->frameshift;
-    const int Ra = p->adapt_train_N ? p->R_a : 1, ma = p->adapt_train_N ? p->m_a : 1, Pl = p->blk_sparse ? p->P_len_l : 1;
-    o->F = F;
-    o->r = r;
-    o->N = N;
-    o->nov = (sz + hop - 1) / hop;
-    int s = SNMF_OK;
-    auto A = [&](int v) { if (s == SNMF_OK) s = v; };
+    int s = online_alloc_state(o, ctx, p);
+    const int F = o->F, r = o->r;
     o->Fs = F;
-    A(online_make_solvers(o));
+    if (s == SNMF_OK) s = online_make_solvers(o);
     auto D = [&](auto** ptr, size_t n) { if (s == SNMF_OK) s = dalloc(ptr, n); };
-    D(&o->B, (size_t)F * r); D(&o->Bfix, (size_t)F * p->R_d); D(&o->Btmp, (size_t)F * p->R_d); D(&o->H0, (size_t)r);
     D(&o->Bf, (size_t)F * r);
     D(&o->recon1, (size_t)2 * F);
-    D(&o->lambda_dav, (size_t)F); D(&o->Xm_tilde, (size_t)F); D(&o->r_blk, (size_t)F * Pl); D(&o->ldblk, (size_t)F * ma);
-    D(&o->adblk, (size_t)Ra * ma); D(&o->Vad, (size_t)F * ma); D(&o->Had, (size_t)Ra * ma); D(&o->win_s, (size_t)sz);
-    D(&o->win_i, (size_t)sz); D(&o->syn_tail, (size_t)std::max(1, o->nov - 1) * sz); D(&o->tw, (size_t)N / 2);
-    if (p->class_outputs) {
-        D(&o->syn_tail_x, (size_t)std::max(1, o->nov - 1) * sz);
-        D(&o->syn_tail_d, (size_t)std::max(1, o->nov - 1) * sz);
-    }
-    D(&o->rup, (size_t)Ra); D(&o->dev, (size_t)1); D(&o->status, (size_t)1); D(&o->hst, (size_t)1);
+    D(&o->status, (size_t)1); D(&o->hst, (size_t)1);
     D(&o->hdiv, (size_t)p->max_iter); D(&o->hcost, (size_t)p->max_iter);
-    if (s == SNMF_OK && hipHostMalloc((void**)&o->h_status, sizeof(OnlineStatus)) != hipSuccess) A(fail(SNMF_ERR_NOMEM, "hipHostMalloc"));
     if (s != SNMF_OK) {
         snmf_online_destroy(o);
         return s;
     }
-    std::vector<float2> htw(N / 2);
-    for (int q = 0; q < N / 2; ++q) {
-        const double ang = -2.0 * M_PI * (double)q / (double)N;
-        htw[q] = make_float2((float)cos(ang), (float)sin(ang));
-    }
-    OnlineDev d0{0, 1, 0, 0};  // update_switch = 1 (src/init_buff.m:42)
+    std::vector<float2> htw;
     std::vector<double> hB((size_t)F * r);
     for (size_t i = 0; i < (size_t)F * p->R_x; ++i) hB[i] = (double)Bx[i];
     for (size_t i = 0; i < (size_t)F * p->R_d; ++i) hB[(size_t)F * p->R_x + i] = (double)Bd[i];
@@ -261,34 +205,19 @@ extern "C" int snmf_online_create(snmf_ctx* ctx, const snmf_online_params* p, co
     hipMemcpyAsync(o->Bfix, hB.data() + (size_t)F * p->R_x, (size_t)F * p->R_d * 8, hipMemcpyHostToDevice, st);  // B_Mel_d in DFT mode (:328)
     hipMemcpyAsync(o->Bf, Bx, (size_t)F * p->R_x * 4, hipMemcpyHostToDevice, st);
     hipMemcpyAsync(o->Bf + (size_t)F * p->R_x, Bd, (size_t)F * p->R_d * 4, hipMemcpyHostToDevice, st);
-    hipMemcpyAsync(o->H0, H0, (size_t)r * 4, hipMemcpyHostToDevice, st);
-    hipMemcpyAsync(o->win_s, win_stft, (size_t)sz * 4, hipMemcpyHostToDevice, st);
-    hipMemcpyAsync(o->win_i, win_istft, (size_t)sz * 4, hipMemcpyHostToDevice, st);
-    hipMemcpyAsync(o->tw, htw.data(), htw.size() * 8, hipMemcpyHostToDevice, st);
-    hipMemcpyAsync(o->dev, &d0, sizeof d0, hipMemcpyHostToDevice, st);
-    hipMemsetAsync(o->lambda_dav, 0, (size_t)F * 4, st);
-    hipMemsetAsync(o->Xm_tilde, 0, (size_t)F * 4, st);
-    hipMemsetAsync(o->r_blk, 0, (size_t)F * Pl * 4, st);
-    hipMemsetAsync(o->ldblk, 0, (size_t)F * ma * 4, st);
-    hipMemsetAsync(o->adblk, 0, (size_t)Ra * ma * 4, st);
-    hipMemsetAsync(o->syn_tail, 0, (size_t)std::max(1, o->nov - 1) * sz * 4, st);
-    if (p->class_outputs) {
-        hipMemsetAsync(o->syn_tail_x, 0, (size_t)std::max(1, o->nov - 1) * sz * 4, st);
-        hipMemsetAsync(o->syn_tail_d, 0, (size_t)std::max(1, o->nov - 1) * sz * 4, st);
-    }
-    hipMemsetAsync(o->rup, 0, (size_t)Ra, st);
-    if (p->adapt_train_N) hipMemcpyAsync(o->adblk, Ad0, (size_t)Ra * ma * 4, hipMemcpyHostToDevice, st);  // column-major R_a x m_a
+    online_upload_state(o, H0, win_stft, win_istft, htw);
+    if (p->adapt_train_N) hipMemcpyAsync(o->adblk, Ad0, (size_t)o->Ra * o->ma * 4, hipMemcpyHostToDevice, st);  // column-major R_a x m_a
     hipError_t e = hipStreamSynchronize(st);
     if (e != hipSuccess) {
         snmf_online_destroy(o);
         return fail(SNMF_ERR_NO_DEVICE, "online create: %s", hipGetErrorString(e));
     }
-    A(set_w<double>(o->hp, o->B, F, 1));
+    s = set_w<double>(o->hp, o->B, F, 1);
     if (s != SNMF_OK) {
         snmf_online_destroy(o);
         return s;
     }
-    o->hist.assign((size_t)(sz - hop), 0.f);
+    o->hist.assign((size_t)(p->framelength - p->frameshift), 0.f);
     *out = o;
     return SNMF_OK;
 }
@@ -350,55 +279,16 @@ extern "C" int snmf_online_set_classes(snmf_online* o, int32_t event_num, const 
     if (!o) return fail(SNMF_ERR_INVALID, "online handle is NULL");
     if (!o->p.class_outputs) return fail(SNMF_ERR_STATE, "class outputs were not requested at creation");
     if (o->f64) return online_f64_set_classes(o->f64, event_num, event_rank, noise_num, noise_rank);
-    if (o->l != 0 || !o->pending.empty() || o->finished) return fail(SNMF_ERR_STATE, "snmf_online_set_classes must precede the first sample");
     std::vector<int> cls;
-    SN_TRY(online_class_ranges(event_num, event_rank, noise_num, noise_rank, o->p.R_x, o->p.R_d, &cls));
+    SN_TRY(online_class_table(o, event_num, event_rank, noise_num, noise_rank, &cls));
     const int nc = event_num + noise_num;
     if (o->mel && o->mel_conv && (size_t)nc * o->n1 * 4 > o->ctx->lds_max)
         return fail(SNMF_ERR_UNSUPPORTED, "MelConv = 1 with %d classes at F_order = %d: the class kernel's Mel products do not fit the LDS", nc, o->n1);
-    HIP_TRY(hipSetDevice(o->ctx->device));
-    hipStream_t st = o->ctx->stream;
-    HIP_TRY(hipStreamSynchronize(st));
-    online_free_call_buffers(o);  // the class-major call buffers depend on the class count
-    for (void** q : {(void**)&o->cls, (void**)&o->tail_c}) {
-        if (*q) hipFree(*q);
-        *q = nullptr;
-    }
-    o->n_ev = o->n_cls = 0;
-    const size_t ntail = (size_t)std::max(1, o->nov - 1) * o->p.framelength;
-    SN_TRY(dalloc(&o->cls, cls.size()));
-    SN_TRY(dalloc(&o->tail_c, (size_t)nc * ntail));
-    HIP_TRY(hipMemcpyAsync(o->cls, cls.data(), cls.size() * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(o->tail_c, 0, (size_t)nc * ntail * 4, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    o->n_ev = event_num;
-    o->n_cls = nc;
-    return SNMF_OK;
+    return online_install_classes(o, cls, event_num, nc);
 }
 
-static int online_reserve(snmf_online* o, int n) {
-    if (n <= o->cap_frames) return SNMF_OK;
-    hipStreamSynchronize(o->ctx->stream);
-    online_free_call_buffers(o);
-    const int cap = std::max(n, 64);
-    const size_t F = o->F, sz = o->p.framelength, hop = o->p.frameshift;
-    SN_TRY(dalloc(&o->sig, (sz - hop) + (size_t)cap * hop));
-    SN_TRY(dalloc(&o->Ym, F * cap));
-    SN_TRY(dalloc(&o->Yph, F * cap));
+static int om_reserve(snmf_online* o, int cap) {
     if (o->mel) SN_TRY(dalloc(&o->Ymel, (size_t)o->n1 * cap));
-    SN_TRY(dalloc(&o->Xt, F * cap));
-    if (o->p.class_outputs) {
-        SN_TRY(dalloc(&o->Xh, F * cap));
-        SN_TRY(dalloc(&o->Dh, F * cap));
-    }
-    SN_TRY(dalloc(&o->syn, (size_t)(cap + o->nov - 1) * sz));
-    SN_TRY(dalloc(&o->outf, (size_t)cap * hop));
-    SN_TRY(dalloc(&o->out16, (size_t)cap * hop));
-    if (o->n_cls) {
-        SN_TRY(dalloc(&o->Xc, (size_t)o->n_cls * F * cap));
-        SN_TRY(dalloc(&o->syn_c, (size_t)o->n_cls * (cap + o->nov - 1) * sz));
-        SN_TRY(dalloc(&o->out_c, (size_t)o->n_cls * cap * hop));
-    }
     if (!o->p.adapt_train_N && !o->hsemi && o->hp->small_ok) {
         snmf_params bp = o->hp->p;
         bp.T = cap;
@@ -413,7 +303,6 @@ static int online_reserve(snmf_online* o, int n) {
         SN_TRY(dalloc(&o->bstatus, (size_t)cap));
         SN_TRY(dalloc(&o->breco, (size_t)cap * 2 * o->Fs));
     }
-    o->cap_frames = cap;
     return SNMF_OK;
 }
 
@@ -484,7 +373,7 @@ static int online_class_spectra(snmf_online* o, const float* A, int a_stride, in
 }
 
 // :296-336 once the status says the solve is due
-static int online_adapt(snmf_online* o, int32_t* iters) {
+static int om_adapt(snmf_online* o, int32_t* iters) {
     const snmf_online_params& p = o->p;
     hipStream_t st = o->ctx->stream;
     snmf_plan* ap = o->ap;
@@ -546,180 +435,111 @@ static int online_adapt(snmf_online* o, int32_t* iters) {
     return SNMF_OK;  // `iters` is already on the host (both paths synchronised when they read it)
 }
 
-// n frames whose samples are sig = [history | n hops] (host); appends the hops the driver would write
-static int online_run_frames(snmf_online* o, const std::vector<float>& sig, int n, std::vector<float>* outf,
-                             std::vector<int16_t>* out16, std::vector<float>* xh, std::vector<float>* dh,
-                             std::vector<std::vector<float>>* xc) {
-    const snmf_online_params& p = o->p;
-    const int F = o->F, sz = p.framelength, hop = p.frameshift, nov = o->nov;
+// ---- the other steps of the shared driver (snmf_online_host.h) -------------------------------------------------------------
+static int om_stft(snmf_online* o, int n) {
     hipStream_t st = o->ctx->stream;
-    SN_TRY(online_reserve(o, n));
-    HIP_TRY(hipMemcpyAsync(o->sig, sig.data(), sig.size() * 4, hipMemcpyHostToDevice, st));
-    OStftArgs sa{};
-    sa.sig = o->sig; sa.sz = sz; sa.hop = hop; sa.dcbin = p.dcbin; sa.preemph = (float)p.preemph; sa.win = o->win_s; sa.tw = o->tw;
-    sa.powv = (float)p.pow; sa.floorv = (float)p.nonzerofloor; sa.Ym = o->Ym; sa.Yph = o->Yph; sa.ld = F; sa.n_frames = n;
+    const OStftArgs sa = online_stft_args(o, n);
     by_logn([&](auto L) { hipLaunchKernelGGL(k_ostft<decltype(L)::value>, dim3(n), dim3(256), 0, st, sa); }, o->N);
     HIP_TRY(hipGetLastError());
     if (o->mel) {
-        hipLaunchKernelGGL(k_omel_frame, dim3(n), dim3(256), (size_t)(o->n1 + 2) * 4, st, (const float*)o->Ym, (const float*)o->melmat, F, o->n1, n,
+        hipLaunchKernelGGL(k_omel_frame, dim3(n), dim3(256), (size_t)(o->n1 + 2) * 4, st, (const float*)o->Ym, (const float*)o->melmat, o->F, o->n1, n,
                            o->Ymel);
         HIP_TRY(hipGetLastError());
     }
-    const size_t lds_post = (size_t)(o->r + 7 * F + 3 * o->n1) * 4;
-    auto post_args = [&](int i, int64_t l) {
-        OPostArgs a{};
-        a.B = o->Bf; a.Ym = o->Ym + (size_t)i * F; a.lambda_dav = o->lambda_dav; a.Xm_tilde = o->Xm_tilde;
-        a.r_blk = o->r_blk; a.ldblk = o->ldblk; a.adblk = o->adblk; a.rup = o->rup; a.dev = o->dev;
-        a.Xt_out = o->Xt + (size_t)i * F;
-        a.Xh_out = o->Xh ? o->Xh + (size_t)i * F : nullptr;
-        a.Dh_out = o->Dh ? o->Dh + (size_t)i * F : nullptr;
-        a.F = F; a.Rx = p.R_x; a.Rd = p.R_d; a.Ra = p.adapt_train_N ? p.R_a : 1; a.ma = p.adapt_train_N ? p.m_a : 1;
-        a.Pl = p.blk_sparse ? p.P_len_l : 1; a.Pk = p.P_len_k; a.dcbin = p.dcbin; a.gap = p.blk_gap;
-        a.l = (int)std::min<int64_t>(l, 1 << 30);
-        a.blk_sparse = p.blk_sparse; a.adapt = p.adapt_train_N; a.wiener = p.enhance_method == 0; a.init_N_len = p.init_N_len;
-        a.switch_at = (int)std::floor(p.overlap_m_a * p.m_a);
-        a.alpha_p = (float)p.alpha_p; a.alpha_eta = (float)p.alpha_eta; a.alpha_d = (float)p.alpha_d; a.beta0 = (float)p.beta;
-        a.beta_max = (float)p.beta_max; a.Ar_up = (float)p.Ar_up; a.flr = (float)p.nonzerofloor;
-        a.n = 1;
-        a.a_stride = 0;
-        a.mel = o->mel; a.mel_conv = o->mel_conv; a.n1 = o->n1; a.melmat = o->melmat; a.Bmf = o->Bmf;
-        a.Ymel = o->mel ? o->Ymel + (size_t)i * o->n1 : nullptr;
-        a.recon_len = o->Fs;
-        return a;
-    };
-    if (!p.adapt_train_N && !o->hsemi && o->hb) {
-        // Fixed dictionary: nothing the host decides sits between frames.  All frame solves of the batch run
-        // in ONE launch (one workgroup per frame, W normalised once), then ONE k_opost launch walks the
-        // sequential post-filter recurrences.
-        snmf_plan* pl = o->hb;
-        const size_t nVp = (size_t)pl->Fp * pl->Tp;
-        hipLaunchKernelGGL(k_pack<float>, dim3(grid_for(nVp)), dim3(256), 0, st, (const float*)(o->mel ? o->Ymel : o->Ym), (int64_t)o->Fs, o->Fs, n,
-                           pl->V, pl->Fp, pl->Tp, kFlr, pl->p.floor_v ? 1 : 0);
-        HIP_TRY(hipGetLastError());
-        pl->have_v = true;
-        if (pl->w_dirty) SN_TRY(launch_wapply(pl, pl->stats, 0, false, true));
-        pl->w_dirty = false;
-        pl->cur = 0;
-        hipLaunchKernelGGL(k_tile_h0<float>, dim3(grid_for((size_t)n * pl->rp)), dim3(256), 0, st, (const float*)o->H0, pl->wn, o->r, pl->rp,
-                           1, n, pl->H[0]);
-        HIP_TRY(hipGetLastError());
-        pl->have_h = true;
-        pl->inited = false;
-        HIP_TRY(hipMemsetAsync(o->bst, 0, (size_t)n * sizeof(DevState), st));
-        SN_TRY(launch_small(pl, n, 1, o->bdiv, o->bcost, o->bst, (o->mel && !o->mel_conv) ? nullptr : o->breco, p.R_x));
-        OPostArgs a = post_args(0, o->l + 1);
-        a.A = pl->H[0]; a.hst = o->bst; a.status = o->bstatus; a.n = n; a.a_stride = pl->rp;
-        a.recon = (pl->frame_fb && (!o->mel || o->mel_conv)) ? o->breco : nullptr;
-        hipLaunchKernelGGL(k_opost, dim3(1), dim3(1024), lds_post, st, a);
-        HIP_TRY(hipGetLastError());
-        if (o->n_cls) SN_TRY(online_class_spectra(o, pl->H[0], pl->rp, 0, n));
-        std::vector<OnlineStatus> hst((size_t)n);
-        HIP_TRY(hipMemcpyAsync(hst.data(), o->bstatus, (size_t)n * sizeof(OnlineStatus), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        for (const OnlineStatus& hs : hst) {
-            snmf_online_frame tr{};
-            tr.n_iter = hs.n_iter; tr.trig = hs.trig; tr.n_up = hs.n_up; tr.beta = hs.beta; tr.A_x_mag = hs.A_x_mag; tr.A_d_mag = hs.A_d_mag;
-            tr.Q_control = hs.Q_control;
-            o->trace.push_back(tr);
-            if (o->trace.size() > kTraceCap) o->trace.pop_front();
-        }
-    } else {
-        for (int i = 0; i < n; ++i) {
-            OPostArgs a = post_args(i, o->l + 1 + i);
-            SN_TRY(online_solve_frame(o, o->mel ? o->Ymel + (size_t)i * o->n1 : o->Ym + (size_t)i * F, &a.A, &a.hst, &a.recon));
-            a.status = o->status;
-            hipLaunchKernelGGL(k_opost, dim3(1), dim3(1024), lds_post, st, a);
-            HIP_TRY(hipGetLastError());
-            if (o->n_cls) SN_TRY(online_class_spectra(o, a.A, 0, i, 1));
-            HIP_TRY(hipMemcpyAsync(o->h_status, o->status, sizeof(OnlineStatus), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            const OnlineStatus hs = *o->h_status;
-            snmf_online_frame tr{};
-            tr.n_iter = hs.n_iter; tr.trig = hs.trig; tr.n_up = hs.n_up; tr.beta = hs.beta; tr.A_x_mag = hs.A_x_mag; tr.A_d_mag = hs.A_d_mag;
-            tr.Q_control = hs.Q_control;
-            if (hs.do_solve && hs.n_up > 0) {
-                int32_t it = 0;
-                SN_TRY(online_adapt(o, &it));
-                tr.solved = 1;
-                tr.adapt_iters = it;
-            }
-            o->trace.push_back(tr);
-            if (o->trace.size() > kTraceCap) o->trace.pop_front();
-        }
-    }
-    // inverse STFT of the n frames behind the nov-1 frames kept from the previous call, overlap-add
-    const int l0 = (int)std::min<int64_t>(o->l + 1, 1 << 30);
-    const int i_first = (int)std::max<int64_t>(0, (int64_t)p.delay + 1 - l0);
-    const int n_out = std::max(0, n - i_first);
-    auto synth = [&](const float* mag, std::vector<float>* of, std::vector<int16_t>* o16, bool keep_tail, float* tail) -> int {
-        if (nov > 1) HIP_TRY(hipMemcpyAsync(o->syn, tail, (size_t)(nov - 1) * sz * 4, hipMemcpyDeviceToDevice, st));
-        OIstftArgs ia{};
-        ia.mag = mag; ia.ph = o->Yph; ia.ld = F; ia.n_frames = n; ia.sz = sz; ia.dcb = p.dcbin_back; ia.powv = (float)p.pow;
-        ia.scale = (float)(p.overlapscale / (double)o->N); ia.preemph = (float)p.preemph; ia.win = o->win_i; ia.tw = o->tw;
-        ia.syn = o->syn + (size_t)(nov - 1) * sz;
-        by_logn([&](auto L) { hipLaunchKernelGGL(k_oistft<decltype(L)::value>, dim3(n), dim3(256), 0, st, ia); }, o->N);
-        HIP_TRY(hipGetLastError());
-        if (n_out > 0) {
-            hipLaunchKernelGGL(k_oola, dim3(grid_for((size_t)n_out * hop)), dim3(256), 0, st, (const float*)o->syn, n, l0, p.delay, sz, hop, nov,
-                               i_first, n_out, o->outf, o16 ? o->out16 : nullptr);
-            HIP_TRY(hipGetLastError());
-            if (of) {
-                const size_t at = of->size();
-                of->resize(at + (size_t)n_out * hop);
-                HIP_TRY(hipMemcpyAsync(of->data() + at, o->outf, (size_t)n_out * hop * 4, hipMemcpyDeviceToHost, st));
-            }
-            if (o16) {
-                const size_t at = o16->size();
-                o16->resize(at + (size_t)n_out * hop);
-                HIP_TRY(hipMemcpyAsync(o16->data() + at, o->out16, (size_t)n_out * hop * 2, hipMemcpyDeviceToHost, st));
-            }
-        }
-        if (keep_tail && nov > 1)
-            HIP_TRY(hipMemcpyAsync(tail, o->syn + (size_t)n * sz, (size_t)(nov - 1) * sz * 4, hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        return SNMF_OK;
-    };
-    SN_TRY(synth(o->Xt, outf, out16, true, o->syn_tail));
-    if (o->p.class_outputs) {  // x_hat / d_hat of :350-361 (summed over the classes), same synthesis
-        SN_TRY(synth(o->Xh, xh, nullptr, true, o->syn_tail_x));
-        SN_TRY(synth(o->Dh, dh, nullptr, true, o->syn_tail_d));
-    }
-    if (o->n_cls) {
-        // x_hat_i / d_hat_i (:356-361): the class-major stack through ONE inverse-STFT launch, one overlap-add per class on
-        // its own tail, one synchronise for all of them
-        const int nc = o->n_cls;
-        const size_t ntl = (size_t)(nov - 1) * sz, syn_cs = (size_t)(o->cap_frames + nov - 1) * sz, out_cs = (size_t)o->cap_frames * hop;
-        if (nov > 1) HIP_TRY(hipMemcpy2DAsync(o->syn_c, syn_cs * 4, o->tail_c, ntl * 4, ntl * 4, (size_t)nc, hipMemcpyDeviceToDevice, st));
-        OIstftArgs ia{};
-        ia.mag = o->Xc; ia.ph = o->Yph; ia.ld = F; ia.n_frames = n; ia.sz = sz; ia.dcb = p.dcbin_back; ia.powv = (float)p.pow;
-        ia.scale = (float)(p.overlapscale / (double)o->N); ia.preemph = (float)p.preemph; ia.win = o->win_i; ia.tw = o->tw;
-        ia.syn = o->syn_c + ntl;
-        const int64_t mag_cs = (int64_t)o->cap_frames * F;
-        by_logn([&](auto L) { hipLaunchKernelGGL(k_oistft_cls<decltype(L)::value>, dim3(n, nc), dim3(256), 0, st, ia, mag_cs, (int64_t)syn_cs); },
-                       o->N);
-        HIP_TRY(hipGetLastError());
-        for (int c = 0; c < nc && n_out > 0; ++c) {
-            hipLaunchKernelGGL(k_oola, dim3(grid_for((size_t)n_out * hop)), dim3(256), 0, st, (const float*)(o->syn_c + (size_t)c * syn_cs), n, l0,
-                               p.delay, sz, hop, nov, i_first, n_out, o->out_c + (size_t)c * out_cs, (int16_t*)nullptr);
-            HIP_TRY(hipGetLastError());
-            if (xc) {
-                std::vector<float>& v = (*xc)[c];
-                const size_t at = v.size();
-                v.resize(at + (size_t)n_out * hop);
-                HIP_TRY(hipMemcpyAsync(v.data() + at, o->out_c + (size_t)c * out_cs, (size_t)n_out * hop * 4, hipMemcpyDeviceToHost, st));
-            }
-        }
-        if (nov > 1)
-            HIP_TRY(hipMemcpy2DAsync(o->tail_c, ntl * 4, o->syn_c + (size_t)n * sz, syn_cs * 4, ntl * 4, (size_t)nc, hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    o->l += n;
+    return SNMF_OK;
+}
+
+// the post-filter's launch for one frame (the one-launch path sets A, hst, recon, status, n and a_stride itself)
+static OPostArgs online_post_frame_args(const snmf_online* o, int i, int64_t l) {
+    OPostArgs a = online_post_args(o, i, l);
+    a.B = o->Bf;
+    a.n = 1;
+    a.a_stride = 0;
+    a.mel = o->mel; a.mel_conv = o->mel_conv; a.n1 = o->n1; a.melmat = o->melmat; a.Bmf = o->Bmf;
+    a.Ymel = o->mel ? o->Ymel + (size_t)i * o->n1 : nullptr;
+    a.recon_len = o->Fs;
+    return a;
+}
+
+static int online_launch_post(snmf_online* o, const OPostArgs& a) {
+    hipLaunchKernelGGL(k_opost, dim3(1), dim3(1024), (size_t)(o->r + 7 * o->F + 3 * o->n1) * 4, o->ctx->stream, a);
+    HIP_TRY(hipGetLastError());
+    return SNMF_OK;
+}
+
+static bool om_one_launch(const snmf_online* o) { return !o->p.adapt_train_N && !o->hsemi && o->hb; }
+
+// Fixed dictionary: all frame solves of the run in ONE launch (one workgroup per frame, W normalised once), then ONE k_opost
+// launch walks the sequential post-filter recurrences.
+static int om_solve_run(snmf_online* o, int n, const OnlineStatus** st_out) {
+    hipStream_t st = o->ctx->stream;
+    snmf_plan* pl = o->hb;
+    const size_t nVp = (size_t)pl->Fp * pl->Tp;
+    hipLaunchKernelGGL(k_pack<float>, dim3(grid_for(nVp)), dim3(256), 0, st, (const float*)(o->mel ? o->Ymel : o->Ym), (int64_t)o->Fs, o->Fs, n,
+                       pl->V, pl->Fp, pl->Tp, kFlr, pl->p.floor_v ? 1 : 0);
+    HIP_TRY(hipGetLastError());
+    pl->have_v = true;
+    if (pl->w_dirty) SN_TRY(launch_wapply(pl, pl->stats, 0, false, true));
+    pl->w_dirty = false;
+    pl->cur = 0;
+    hipLaunchKernelGGL(k_tile_h0<float>, dim3(grid_for((size_t)n * pl->rp)), dim3(256), 0, st, (const float*)o->H0, pl->wn, o->r, pl->rp,
+                       1, n, pl->H[0]);
+    HIP_TRY(hipGetLastError());
+    pl->have_h = true;
+    pl->inited = false;
+    HIP_TRY(hipMemsetAsync(o->bst, 0, (size_t)n * sizeof(DevState), st));
+    SN_TRY(launch_small(pl, n, 1, o->bdiv, o->bcost, o->bst, (o->mel && !o->mel_conv) ? nullptr : o->breco, o->p.R_x));
+    OPostArgs a = online_post_frame_args(o, 0, o->l + 1);
+    a.A = pl->H[0]; a.hst = o->bst; a.status = o->bstatus; a.n = n; a.a_stride = pl->rp;
+    a.recon = (pl->frame_fb && (!o->mel || o->mel_conv)) ? o->breco : nullptr;
+    SN_TRY(online_launch_post(o, a));
+    if (o->n_cls) SN_TRY(online_class_spectra(o, pl->H[0], pl->rp, 0, n));
+    *st_out = o->bstatus;
+    return SNMF_OK;
+}
+
+static int om_solve_frame(snmf_online* o, int i, const OnlineStatus** st_out) {
+    OPostArgs a = online_post_frame_args(o, i, o->l + 1 + i);
+    SN_TRY(online_solve_frame(o, o->mel ? o->Ymel + (size_t)i * o->n1 : o->Ym + (size_t)i * o->F, &a.A, &a.hst, &a.recon));
+    a.status = o->status;
+    SN_TRY(online_launch_post(o, a));
+    if (o->n_cls) SN_TRY(online_class_spectra(o, a.A, 0, i, 1));
+    *st_out = o->status;
+    return SNMF_OK;
+}
+
+static int om_istft(snmf_online* o, const float* mag, int n, float* syn) {
+    const OIstftArgs ia = online_istft_args(o, mag, n, syn);
+    by_logn([&](auto L) { hipLaunchKernelGGL(k_oistft<decltype(L)::value>, dim3(n), dim3(256), 0, o->ctx->stream, ia); }, o->N);
+    HIP_TRY(hipGetLastError());
+    return SNMF_OK;
+}
+
+// the whole class-major stack through ONE inverse-STFT launch, queued when the driver asks for the first class
+static int om_istft_class(snmf_online* o, int c, int n, size_t syn_cs) {
+    if (c) return SNMF_OK;
+    const OIstftArgs ia = online_istft_args(o, (const float*)o->Xc, n, o->syn_c + (size_t)(o->nov - 1) * o->p.framelength);
+    const int64_t mag_cs = (int64_t)o->cap_frames * o->F;
+    by_logn([&](auto L) {
+        hipLaunchKernelGGL(k_oistft_cls<decltype(L)::value>, dim3(n, o->n_cls), dim3(256), 0, o->ctx->stream, ia, mag_cs, (int64_t)syn_cs);
+    }, o->N);
+    HIP_TRY(hipGetLastError());
+    return SNMF_OK;
+}
+
+static int om_ola(snmf_online* o, const float* syn, int n, int l0, int i_first, int n_out, float* out, int16_t* out16) {
+    const snmf_online_params& p = o->p;
+    hipLaunchKernelGGL(k_oola, dim3(grid_for((size_t)n_out * p.frameshift)), dim3(256), 0, o->ctx->stream, syn, n, l0, p.delay, p.framelength,
+                       p.frameshift, o->nov, i_first, n_out, out, out16);
+    HIP_TRY(hipGetLastError());
     return SNMF_OK;
 }
 
 // snmf_online_process_f32 on an fp64 separator: the fp64 path, float outputs rounded from its doubles
 static int online_f64_process_rounded(snmf_online* o, const float* pcm, int64_t n, int flush, float* xt_f32, int16_t* xt_i16,
                                       float* xh_f32, float* dh_f32, float* xhi_f32, float* dhi_f32, int64_t cap, int64_t* n_out) {
+    if (n_out) *n_out = 0;
+    if (n < 0 || (n > 0 && !pcm)) return fail(SNMF_ERR_INVALID, "pcm is NULL");  // (before pcm is read here)
     std::vector<double> x(pcm, pcm + n);
     // what this call can write at most (n hops, one left over from earlier calls, the flush frames), not the caller's cap
     const int64_t hop = o->p.frameshift, most = (n / hop + 1 + (flush ? o->p.delay + 1 : 0)) * hop;
@@ -744,84 +564,21 @@ static int online_f64_process_rounded(snmf_online* o, const float* pcm, int64_t 
 }
 
 // snmf_online_process_f32 / snmf_online_process_classes_f32 (xhi_f32 / dhi_f32: the class signals, class-major at `cap`)
-static int online_process(snmf_online* o, const float* pcm, int64_t n, int flush, float* xt_f32, int16_t* xt_i16, float* xh_f32,
-                          float* dh_f32, float* xhi_f32, float* dhi_f32, int64_t cap, int64_t* n_out) {
+static int online_process_f32(snmf_online* o, const float* pcm, int64_t n, int flush, float* xt_f32, int16_t* xt_i16, float* xh_f32,
+                              float* dh_f32, float* xhi_f32, float* dhi_f32, int64_t cap, int64_t* n_out) {
     if (!o) return fail(SNMF_ERR_INVALID, "online handle is NULL");
-    if (n_out) *n_out = 0;
-    if (n < 0 || (n > 0 && !pcm)) return fail(SNMF_ERR_INVALID, "pcm is NULL");
     if (o->f64) return online_f64_process_rounded(o, pcm, n, flush, xt_f32, xt_i16, xh_f32, dh_f32, xhi_f32, dhi_f32, cap, n_out);
-    if (o->finished) return fail(SNMF_ERR_STATE, "the stream was flushed; create a new separator");
-    if (o->failed) return fail(SNMF_ERR_STATE, "an earlier call failed midway through a batch; the separator state is not reusable, create a new one");
-    if ((xh_f32 || dh_f32 || xhi_f32 || dhi_f32) && !o->p.class_outputs) return fail(SNMF_ERR_STATE, "class outputs were not requested at creation");
-    (void)hipGetLastError();  // clean sticky error state, see PLAN_CHECK
-    HIP_TRY(hipSetDevice(o->ctx->device));
-    const int sz = o->p.framelength, hop = o->p.frameshift;
-    o->pending.insert(o->pending.end(), pcm, pcm + n);
-    const int64_t nfr = (int64_t)(o->pending.size() / (size_t)hop);
-    const int64_t tail_frames = flush ? o->p.delay + 1 : 0;
-    const int64_t max_out = (nfr + tail_frames) * hop;
-    if ((xt_f32 || xt_i16 || xh_f32 || dh_f32 || xhi_f32 || dhi_f32) && cap < max_out) {
-        o->pending.resize(o->pending.size() - (size_t)n);
-        return fail(SNMF_ERR_INVALID, "output capacity %lld < %lld samples", (long long)cap, (long long)max_out);
-    }
-    std::vector<float> of, ox, od;
-    std::vector<int16_t> o16;
-    // class signals: with a partition set they come from the class kernel; without one x_hat / d_hat are the one class per side
-    const bool cls_set = o->n_cls > 0, want_c = cls_set && (xhi_f32 || dhi_f32);
-    std::vector<std::vector<float>> oc(want_c ? o->n_cls : 0);
-    std::vector<float>* px = (xh_f32 || (xhi_f32 && !cls_set)) ? &ox : nullptr;
-    std::vector<float>* pd = (dh_f32 || (dhi_f32 && !cls_set)) ? &od : nullptr;
-    const int64_t chunk = cls_set ? std::max<int64_t>(64, 4096 / o->n_cls) : 4096;  // frames per device batch (class-major buffers grow with the classes)
-    int64_t done = 0;
-    while (done < nfr) {
-        const int nb = (int)std::min(chunk, nfr - done);
-        std::vector<float> sig(o->hist);
-        sig.insert(sig.end(), o->pending.begin() + done * hop, o->pending.begin() + (done + nb) * hop);
-        if (int rc = online_run_frames(o, sig, nb, xt_f32 ? &of : nullptr, xt_i16 ? &o16 : nullptr, px, pd, want_c ? &oc : nullptr)) {
-            o->failed = true;  // frames of this call were consumed and the device state advanced: never retry on it
-            return rc;
-        }
-        o->hist.assign(sig.end() - (sz - hop), sig.end());
-        done += nb;
-    }
-    o->pending.erase(o->pending.begin(), o->pending.begin() + nfr * hop);
-    if (flush) {
-        // a partial hop is dropped and delay+1 all-zero frames follow (src/NTF_sep_event_RT.m:69-76)
-        std::vector<float> sig((size_t)(sz - hop) + (size_t)tail_frames * hop, 0.f);
-        if (int rc = online_run_frames(o, sig, (int)tail_frames, xt_f32 ? &of : nullptr, xt_i16 ? &o16 : nullptr, px, pd, want_c ? &oc : nullptr)) {
-            o->failed = true;
-            return rc;
-        }
-        o->pending.clear();
-        o->finished = true;
-    }
-    if (xt_f32) std::memcpy(xt_f32, of.data(), of.size() * 4);
-    if (xt_i16) std::memcpy(xt_i16, o16.data(), o16.size() * 2);
-    if (xh_f32) std::memcpy(xh_f32, ox.data(), ox.size() * 4);
-    if (dh_f32) std::memcpy(dh_f32, od.data(), od.size() * 4);
-    size_t nc_out = 0;
-    if (cls_set) {
-        for (int c = 0; c < (int)oc.size(); ++c) {
-            float* dst = c < o->n_ev ? (xhi_f32 ? xhi_f32 + (size_t)c * cap : nullptr) : (dhi_f32 ? dhi_f32 + (size_t)(c - o->n_ev) * cap : nullptr);
-            if (dst) std::memcpy(dst, oc[c].data(), oc[c].size() * 4);
-            nc_out = std::max(nc_out, oc[c].size());
-        }
-    } else {
-        if (xhi_f32) std::memcpy(xhi_f32, ox.data(), ox.size() * 4);
-        if (dhi_f32) std::memcpy(dhi_f32, od.data(), od.size() * 4);
-    }
-    if (n_out) *n_out = (int64_t)std::max(std::max(std::max(of.size(), o16.size()), std::max(ox.size(), od.size())), nc_out);
-    return SNMF_OK;
+    return online_process(o, pcm, n, flush, xt_f32, xt_i16, xh_f32, dh_f32, xhi_f32, dhi_f32, cap, n_out);
 }
 
 extern "C" int snmf_online_process_f32(snmf_online* o, const float* pcm, int64_t n, int flush, float* xt_f32, int16_t* xt_i16,
                                        float* xh_f32, float* dh_f32, int64_t cap, int64_t* n_out) {
-    return online_process(o, pcm, n, flush, xt_f32, xt_i16, xh_f32, dh_f32, nullptr, nullptr, cap, n_out);
+    return online_process_f32(o, pcm, n, flush, xt_f32, xt_i16, xh_f32, dh_f32, nullptr, nullptr, cap, n_out);
 }
 
 extern "C" int snmf_online_process_classes_f32(snmf_online* o, const float* pcm, int64_t n, int flush, float* xt_f32, int16_t* xt_i16,
                                                float* xh_f32, float* dh_f32, float* xhi_f32, float* dhi_f32, int64_t cap, int64_t* n_out) {
-    return online_process(o, pcm, n, flush, xt_f32, xt_i16, xh_f32, dh_f32, xhi_f32, dhi_f32, cap, n_out);
+    return online_process_f32(o, pcm, n, flush, xt_f32, xt_i16, xh_f32, dh_f32, xhi_f32, dhi_f32, cap, n_out);
 }
 
 extern "C" int snmf_online_get_basis_f32(snmf_online* o, float* Bd, int64_t ld) {
@@ -846,9 +603,7 @@ extern "C" int snmf_online_get_basis_f32(snmf_online* o, float* Bd, int64_t ld) 
 extern "C" int snmf_online_trace(snmf_online* o, snmf_online_frame* out, int64_t cap, int64_t* n) {
     if (!o) return fail(SNMF_ERR_INVALID, "online handle is NULL");
     if (o->f64) return online_f64_trace(o->f64, out, cap, n);
-    if (n) *n = (int64_t)o->trace.size();
-    if (out && cap > 0) std::copy_n(o->trace.begin(), (size_t)std::min<int64_t>(cap, (int64_t)o->trace.size()), out);
-    return SNMF_OK;
+    return online_trace_read(o, out, cap, n);
 }
 
 // ---- fp64 mode (snmf_online_f64.h): every input crosses in fp64 and every step from PCM to the fed-back state is fp64 ----
@@ -888,10 +643,5 @@ extern "C" int snmf_online_process_classes_f64(snmf_online* o, const double* pcm
 extern "C" int snmf_online_get_basis_f64(snmf_online* o, double* Bd, int64_t ld) {
     if (!o || !Bd) return fail(SNMF_ERR_INVALID, "NULL argument");
     if (o->f64) return online_f64_get_basis(o->f64, Bd, ld);
-    if (ld < o->F) return fail(SNMF_ERR_INVALID, "ld < F");
-    HIP_TRY(hipSetDevice(o->ctx->device));
-    HIP_TRY(hipStreamSynchronize(o->ctx->stream));
-    HIP_TRY(hipMemcpy2D(Bd, (size_t)ld * 8, o->B + (size_t)o->F * o->p.R_x, (size_t)o->F * 8, (size_t)o->F * 8, (size_t)o->p.R_d,
-                        hipMemcpyDeviceToHost));
-    return SNMF_OK;
+    return online_get_basis_f64(o, Bd, ld);
 }
