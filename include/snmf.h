@@ -818,6 +818,34 @@ int snmf_mdi_batch_fp64(snmf_ctx* ctx, const snmf_params* p, int32_t n_problems,
                         const double* const* H0, const double* sparsity, double* const* V_mdi, const int64_t* ldVm,
                         double* const* W, double* const* H, double* const* div_out, double* const* cost_out, int32_t* n_iter_out);
 
+/* Added within 5.  run_basis_DNMF (run_basis_DNMF.m:36-55) for n_problems problems at once, one per noise type or class as in the
+ * loop of Do_MultiBatch_IS16_20160324.m:139-148 ("Batched DNMF re-training").  The problems share F, R_x, R_d and
+ * the settings; problem k has its own frame count T[k], its own B_k and its own initial activations H0_k.  The three solves
+ * run as three batches on the engines above -- the mixtures (r = R_x + R_d, H only), the clean features (r = R_x, W only) and
+ * the noise features (r = R_d, W only) -- and A_hat passes from the first into the other two on the device; every problem
+ * stops each of its solves at its own iteration.  One-shot entries, no handle.
+ * Every matrix is tight and column-major: Y_k, X_k, D_k F x T[k]; B_k F x (R_x + R_d); H0_k (R_x + R_d) x T[k]; the outputs
+ * B_hat_k F x (R_x + R_d) and A_hat_k (R_x + R_d) x T[k].  Y, X, D, B, H0, B_hat: n_problems pointers each.  A_hat: NULL, or
+ * n_problems pointers of which single ones may be NULL (not wanted).  n_iter: NULL, or 3 per problem (solves 1, 2, 3).
+ * p->r = R_x + R_d; p->T is ignored; the masks of p are ignored (the loop sets its own).
+ *   _f64 / _f32  the fp32 engine (snmf_batch_create) from double / float host arrays.  THE CONTRACT: bit for bit three chained
+ *                snmf_sparse_nmf_batch_* calls with the loop's masks, init_w = B_k / its column blocks and init_h = H0_k /
+ *                the row blocks of A_hat_k.  Envelope: the fp32 batch's (F <= 513, R_x + R_d <= 200), SNMF_ERR_UNSUPPORTED.
+ *   _fp64        the fp64 engine (snmf_batch_create_fp64).  THE CONTRACT: B_hat_k, A_hat_k and the three counts are bit for bit
+ *                those of snmf_run_basis_dnmf_fp64 run alone on problem k.
+ * In both, the results of a problem depend on its own inputs and the settings only, not on the batch around it.
+ * Refused before the device is touched: NULL arguments, n_problems < 1, T[k] < 1 (SNMF_ERR_INVALID); R_x < 1, R_d < 1,
+ * p->r != R_x + R_d, a sparsity that is not SNMF_SPARSITY_SCALAR (SNMF_ERR_DIM, as snmf_run_basis_dnmf_*). */
+int snmf_run_basis_dnmf_batch_f64(snmf_ctx* ctx, const snmf_params* p, int32_t R_x, int32_t R_d, int32_t n_problems, const int32_t* T,
+                                  const double* const* Y, const double* const* X, const double* const* D, const double* const* B,
+                                  const double* const* H0, double* const* B_hat, double* const* A_hat, int32_t* n_iter);
+int snmf_run_basis_dnmf_batch_f32(snmf_ctx* ctx, const snmf_params* p, int32_t R_x, int32_t R_d, int32_t n_problems, const int32_t* T,
+                                  const float* const* Y, const float* const* X, const float* const* D, const float* const* B,
+                                  const float* const* H0, float* const* B_hat, float* const* A_hat, int32_t* n_iter);
+int snmf_run_basis_dnmf_batch_fp64(snmf_ctx* ctx, const snmf_params* p, int32_t R_x, int32_t R_d, int32_t n_problems, const int32_t* T,
+                                   const double* const* Y, const double* const* X, const double* const* D, const double* const* B,
+                                   const double* const* H0, double* const* B_hat, double* const* A_hat, int32_t* n_iter);
+
 /* ---- instrumentation (bench.py: HIP-event timing on the engine's own stream) ------------ */
 /* Average device time in milliseconds per launch of the named kernel family over the launches
  * recorded since snmf_ctx_timing(ctx, 1) was switched on.  Families: "hstep", "wstats",

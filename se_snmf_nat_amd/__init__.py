@@ -7,8 +7,8 @@ the host-side mirror of the reference interface.  There is no CPU fallback.
 """
 from .api import (Context, Plan, SnmfError, default_context, dnmf_adapt, run_basis_dnmf, snmf_mdi, snmf_mdi_Sm,  # noqa: F401
                   sparse_nmf, sparse_nmf_GPU)
-from .batch import (BatchPlan, BatchPlan64, BatchPlanMdi64, snmf_mdi_batch, snmf_mdi_Sm_batch, sparse_nmf_batch,  # noqa: F401
-                    sparse_nmf_batch_fp64)
+from .batch import (BatchPlan, BatchPlan64, BatchPlanMdi64, run_basis_dnmf_batch, snmf_mdi_batch, snmf_mdi_Sm_batch,  # noqa: F401
+                    sparse_nmf_batch, sparse_nmf_batch_fp64)
 
 
 

@@ -93,6 +93,7 @@ SYMBOLS = [
     "snmf_sparse_nmf_batch_f64", "snmf_sparse_nmf_batch_f32",
     "snmf_batch_create_fp64", "snmf_sparse_nmf_batch_fp64",
     "snmf_batch_create_mdi_fp64", "snmf_batch_set_problem_mdi_f64", "snmf_batch_get_v_mdi_f64", "snmf_mdi_batch_fp64",
+    "snmf_run_basis_dnmf_batch_f64", "snmf_run_basis_dnmf_batch_f32", "snmf_run_basis_dnmf_batch_fp64",
     "snmf_rccl_available", "snmf_rccl_get_unique_id", "snmf_rccl_comm_create", "snmf_rccl_comm_destroy", "snmf_plan_run_sharded_rccl",
 ]
 ABI_VERSION = 5  # include/snmf.h: SNMF_ABI_VERSION this binding was written against
@@ -371,6 +372,9 @@ def load():
     sig["snmf_batch_set_problem_mdi_f64"] = (C.c_int, [vp, i32, vp, i64, vp, i64, vp, vp])
     sig["snmf_batch_get_v_mdi_f64"] = (C.c_int, [vp, i32, vp, i64])
     sig["snmf_mdi_batch_fp64"] = (C.c_int, [vp, PP, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp])
+    # run_basis_DNMF for a batch: tight arrays only, so no leading dimensions
+    for ty in ("f64", "f32", "fp64"):
+        sig[f"snmf_run_basis_dnmf_batch_{ty}"] = (C.c_int, [vp, PP, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp])
     lib.snmf_abi_version.restype = C.c_int
     if lib.snmf_abi_version() != ABI_VERSION:  # a stale library must not be driven through newer prototypes
         raise ImportError(f"{path} has ABI version {lib.snmf_abi_version()}, this binding needs {ABI_VERSION}: rebuild the library")

@@ -7,6 +7,8 @@
     snmf_mdi_batch, snmf_mdi_Sm_batch       the missing-data solves in the fp64 batch: a list of (v_mdi, h, objective), each bit
                                             for bit snmf_mdi / snmf_mdi_Sm(v, mask, p, precision="fp64") run alone
     BatchPlanMdi64                          their resident handle (snmf_batch_create_mdi_fp64): set_problem takes the mask too
+    run_basis_dnmf_batch                    run_basis_dnmf for a list of (Y, X, D) problems: three batches, A_hat resident between
+                                            them; a list of (B_hat, A_hat)
 
 The problems share the row count F, the rank r and the settings `p`; every problem has its own frame count, its own initial
 factors and its own stop index.  All arithmetic happens in libsnmf_hip.so on the GPU; this module does the reference's
@@ -20,10 +22,10 @@ import numpy as np
 
 from . import _lib
 from ._lib import SnmfError
-from .api import _cf_to_beta, _colmajor, _display, _make_params, _mask, _ptr, default_context
+from .api import _cf_to_beta, _check_precision, _colmajor, _display, _make_params, _mask, _ptr, _solver_scalars, default_context
 
 __all__ = ["sparse_nmf_batch", "BatchPlan", "sparse_nmf_batch_fp64", "BatchPlan64", "snmf_mdi_batch", "snmf_mdi_Sm_batch",
-           "BatchPlanMdi64"]
+           "BatchPlanMdi64", "run_basis_dnmf_batch"]
 
 
 def _check_batch_precision(precision):
@@ -422,3 +424,87 @@ class BatchPlanMdi64(BatchPlan64):
         out = np.empty((self.F, int(self.Ts[k])), dtype=np.float64, order="F")
         _lib.check(self._lib.snmf_batch_get_v_mdi_f64(self._h, k, _ptr(out), self.F))
         return out
+
+
+def run_basis_dnmf_batch(Ys, Xs, Ds, B, R_x, R_d, p, *, ctx=None, dtype=np.float64, h0="host", precision="fp32", info=None):
+    """(B_hat, A_hat) = run_basis_dnmf(Y, X, D, B, R_x, R_d, p) for every problem of the three lists, solved together
+    (snmf_run_basis_dnmf_batch_*): the mixtures, the clean and the noise features are three batches, and A_hat stays on the
+    device between them.  Ys, Xs, Ds: lists of F x T_k arrays (one F; X_k and D_k of Y_k's shape).  B: one F x (R_x + R_d)
+    array for every problem, or a list of them.  h0: "host" = rand(r, T_k) of solve 1 drawn per problem, in list order, from one
+    RandomState(p["random_seed"]); or a list of r x T_k arrays.  p: the settings, shared; a scalar sparsity.
+    precision="fp32": the fp32 batch engine (F <= 513, R_x + R_d <= 200), bit for bit three chained sparse_nmf_batch calls.
+    precision="fp64" (dtype float64): problem k's results are bit for bit run_basis_dnmf(..., precision="fp64", h0=H0_k) alone.
+    Every problem stops each of its three solves at its own iteration; info["n_iter"] receives a list of [n1, n2, n3].
+    Returns a list of (B_hat, A_hat)."""
+    _check_precision(precision)
+    p = dict(p)
+    dt = np.dtype(dtype)
+    if dt not in (np.dtype(np.float64), np.dtype(np.float32)):
+        raise SnmfError(1, "dtype must be float64 or float32")
+    Ys, Xs, Ds = ([np.asarray(v) for v in vs] for vs in (Ys, Xs, Ds))
+    n = len(Ys)
+    if n == 0:
+        raise SnmfError(1, "the batch is empty: Ys must hold at least one matrix")
+    if len(Xs) != n or len(Ds) != n:
+        raise SnmfError(1, f"{n} mixtures, {len(Xs)} clean and {len(Ds)} noise feature sets: one of each per problem")
+    R_x, R_d = int(R_x), int(R_d)
+    r = R_x + R_d
+    for y in Ys:
+        if y.ndim != 2 or y.shape[1] < 1:
+            raise SnmfError(1, "every Y must be a 2-D matrix with at least one column")
+    F = Ys[0].shape[0]
+    for k, (y, x, d) in enumerate(zip(Ys, Xs, Ds)):
+        if y.shape[0] != F:
+            raise SnmfError(3, f"Y of problem {k} has {y.shape[0]} rows, problem 0 has {F}: a batch shares the row count")
+        if x.shape != y.shape or d.shape != y.shape:
+            raise SnmfError(3, f"problem {k}: Y, X and D must have one size (got {y.shape}, {x.shape}, {d.shape})")
+    if isinstance(B, (list, tuple)):
+        if len(B) != n:
+            raise SnmfError(3, f"B is a list of {len(B)}, the batch has {n} problems")
+        Bs = [np.asarray(b, dtype=np.float64) for b in B]
+    else:
+        Bs = [np.asarray(B, dtype=np.float64)] * n
+    for b in Bs:
+        if b.shape != (F, r):
+            raise SnmfError(3, f"B is {b.shape}, expected ({F}, {r})")
+    if isinstance(h0, str):
+        if h0 != "host":
+            raise SnmfError(3, f"h0 must be 'host' or a list of {n} arrays (r x T_k each)")
+        H0s = None
+    else:
+        if not isinstance(h0, (list, tuple)) or len(h0) != n:
+            raise SnmfError(3, f"h0 must be 'host' or a list of {n} arrays (r x T_k each)")
+        H0s = [np.asarray(h) for h in h0]
+        for h, y in zip(H0s, Ys):
+            if h.shape != (r, y.shape[1]):
+                raise SnmfError(3, f"init_h is {h.shape}, expected ({r}, {y.shape[1]})")
+    beta, max_iter, conv_eps, cost_check, lam = _solver_scalars(p)
+    if precision == "fp64" and dt != np.dtype(np.float64):
+        raise SnmfError(1, "precision='fp64' needs dtype=np.float64 (the fp64 DNMF batch takes and returns doubles)")
+    if H0s is None:  # what sparse_nmf draws for solve 1 of each problem (init_w is given, so h is its first draw)
+        seed = int(p.get("random_seed", 1))
+        rs = np.random.RandomState(seed if seed > 0 else None)
+        H0s = [rs.random_sample((r, y.shape[1])) for y in Ys]
+    sp = _make_params(F, 1, r, beta, max_iter, conv_eps, cost_check, True, 0, lam, None, None)
+
+    lib = _lib.load()
+    ctx = ctx or default_context()
+    tight = lambda arrs: [np.asfortranarray(a, dtype=dt) for a in arrs]  # noqa: E731
+    yy, xx, dd, bb, hh = tight(Ys), tight(Xs), tight(Ds), tight(Bs), tight(H0s)
+    Ts = np.array([y.shape[1] for y in Ys], np.int32)
+    B_hat = [np.empty((F, r), dtype=dt, order="F") for _ in Ys]
+    A_hat = [np.empty((r, y.shape[1]), dtype=dt, order="F") for y in Ys]
+    n_iter = np.zeros(3 * n, np.int32)
+
+    def ptrs(arrs):
+        return (C.c_void_p * n)(*[a.ctypes.data for a in arrs])
+
+    if precision == "fp64":
+        fn = lib.snmf_run_basis_dnmf_batch_fp64
+    else:
+        fn = lib.snmf_run_basis_dnmf_batch_f64 if dt == np.float64 else lib.snmf_run_basis_dnmf_batch_f32
+    _lib.check(fn(ctx._h, C.byref(sp), R_x, R_d, n, _ptr(Ts), ptrs(yy), ptrs(xx), ptrs(dd), ptrs(bb), ptrs(hh), ptrs(B_hat), ptrs(A_hat),
+                  _ptr(n_iter)))
+    if info is not None:
+        info["n_iter"] = [[int(v) for v in n_iter[3 * k:3 * k + 3]] for k in range(n)]
+    return list(zip(B_hat, A_hat))

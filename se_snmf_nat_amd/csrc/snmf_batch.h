@@ -11,6 +11,7 @@
 //             chunk slabs in chunk order in fp64, the F x r epilogue of :215-244 for its column (the update and the
 //             renormalisation are column-local), and the column's entries of the W images of the next H step
 //   k_bfold : the objective fold + stop test alone (loops that do not update W, and the last iterate of a run)
+//   k_btake_h : one (problem, tile): the initial H of this batch from rows of the result H of another batch (the batched DNMF loop)
 //
 // Layouts: the engine's (snmf_kernels.h, StepArgs): V [Ttot][Fp], H [Ttot][rp], Wt4 / Wk4 per problem; the frames of
 // problem b start at tile prob[b].tile0, so a tile never spans two problems.  A problem's last tile is partial when T_b is
@@ -575,6 +576,27 @@ static __global__ __launch_bounds__(256) void k_bscale(BatchArgs a, int b) {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
         const int k = (int)(i % a.rp);
         if (k < a.r) H[i] = (float)((double)H[i] * wn[k]);
+    }
+}
+
+// H0 of every problem of batch `a` from rows [row0, row0 + a.r) of the result H of another batch with the same frame counts (and
+// so the same tile table): grid = a's tiles, one (problem, 32-frame tile) each.  s0 / s1: the other batch's two H buffers,
+// [frame][srp]; sst: its states; scur: the buffer its unstopped problems ended in.  A problem's source is the buffer of its
+// stop iterate (BState::hsel) once it has stopped -- the choice the host makes when it reads H back.  Lanes run along k, the
+// contiguous direction on both sides.  Pad rows (k >= a.r) and pad frames (t >= T_b) are written as zeros.
+static __global__ __launch_bounds__(256) void k_btake_h(BatchArgs a, const float* __restrict__ s0, const float* __restrict__ s1,
+                                                        const BState* __restrict__ sst, int scur, int srp, int row0) {
+    const BTile tt = a.tiles[blockIdx.x];
+    const BProb pb = a.prob[tt.b];
+    const BState ss = sst[tt.b];
+    const float* __restrict__ S = (ss.stop ? ss.hsel : scur) ? s1 : s0;
+    const long long fr0 = 32LL * (pb.tile0 + tt.l);
+    const int Tl = min(32, pb.T - 32 * tt.l);
+    float* __restrict__ H = a.H[0];
+    for (int i = threadIdx.x; i < 32 * a.rp; i += 256) {
+        const int t = i / a.rp, k = i - t * a.rp;
+        const long long fr = fr0 + t;
+        H[fr * a.rp + k] = (k < a.r && t < Tl) ? S[fr * srp + row0 + k] : 0.f;
     }
 }
 

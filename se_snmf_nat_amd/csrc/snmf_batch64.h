@@ -81,6 +81,20 @@ __global__ __launch_bounds__(256) void k_b64_ratio(B64Args a) {
                          gridDim.x);
 }
 
+// grid (workgroups, B): H0 of problem b of batch `a` (tight a.r x T_b) from rows [row0, row0 + a.r) of the H of another batch with
+// the same frame counts (tight r_src x T_b at the same frame offset); consecutive lanes run along k within a frame
+static __global__ __launch_bounds__(256) void k_b64_take_h(B64Args a, const double* __restrict__ Hsrc, int r_src, int row0) {
+    const B64Prob p = a.prob[blockIdx.y];
+    const double* __restrict__ S = Hsrc + p.fr0 * r_src + row0;
+    double* __restrict__ H = a.H + p.fr0 * a.r;
+    const long long n = (long long)a.r * p.T;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        const long long t = i / a.r;
+        const int k = (int)(i - t * a.r);
+        H[i] = S[t * r_src + k];
+    }
+}
+
 template <bool KL>
 __global__ __launch_bounds__(256) void k_b64_hupd(B64Args a) {
     const int b = blockIdx.y;

@@ -37,9 +37,14 @@ struct snmf_batch {
     virtual int build(const int32_t* T) = 0;
     virtual int reset() = 0;  // the device state of a batch that has not run
     virtual int upload_sparsity(const double* sparsity) = 0;  // r entries; the caller's array may go on return
-    // problem k from host arrays, and its initial scaling (src/sparse_nmf.m:157-169)
+    // problem k from host arrays, and its initial scaling (src/sparse_nmf.m:157-169).  H0 == nullptr: V, W0 and the scaling of W
+    // only -- the problem's H0 is still to come, for every problem at once, through take_h0
     virtual int load(int k, const double* V, int64_t ldV, const double* W0, const double* H0) = 0;
     virtual int load(int k, const float* V, int64_t ldV, const float* W0, const float* H0) = 0;
+    // H0 of every problem from rows [row0, row0 + r) of the result H of `src` -- another engine of this kind with the same frame
+    // counts, whose run has ended -- then the initial scaling of H (:159-160) by the norms load() left: what load() does with
+    // a host H0, without H leaving the device.  Every problem must have been loaded with H0 == nullptr.
+    virtual int take_h0(snmf_batch& src, int row0) = 0;
     // a masked batch: problem k with its mask (1 = observed), the initial scaling and the masked start (src/snmf_mdi.m:175)
     virtual int load_mdi(int, const double*, int64_t, const double*, int64_t, const double*, const double*) {
         return fail(SNMF_ERR_UNSUPPORTED, "this batch engine has no missing-data form");
@@ -224,4 +229,70 @@ inline int batch_get_v_mdi(snmf_batch* b, int32_t k, double* V_mdi, int64_t ld) 
     if (ld < b->p.F) return fail(SNMF_ERR_INVALID, "ld = %lld is below F = %d", (long long)ld, b->p.F);
     if (!b->ran) return fail(SNMF_ERR_STATE, "snmf_batch_get_v_mdi_f64 before snmf_batch_run");
     return b->fetch_v_mdi(k, V_mdi, ld);
+}
+
+// ---- run_basis_DNMF.m:36-55 for a batch of (Y, X, D, B) problems (include/snmf.h: snmf_run_basis_dnmf_batch_*) -----------------
+// Three engines of one kind, made by `make`, over the same frame counts: the Y-batch (r = R_x + R_d, H only), the X-batch
+// (r = R_x, W only) and the D-batch (r = R_d, W only).  Each phase is one batch_run, so every problem stops each of its three
+// solves at its own iteration and the polling is the batch's; between the phases A_hat goes from the Y-engine into the other two
+// through take_h0 and never leaves the device.  Like the rest of this file, the driver does not ask which engine it drives.
+struct BatchOwner {  // an engine that dies with the call
+    snmf_batch* b = nullptr;
+    ~BatchOwner() {
+        if (!b) return;
+        hipSetDevice(b->ctx->device);
+        hipStreamSynchronize(b->ctx->stream);
+        delete b;
+    }
+};
+
+// Every matrix tight and column-major: Y_k, X_k, D_k F x T[k], B_k F x (R_x + R_d), H0_k (R_x + R_d) x T[k]; B_hat_k and A_hat_k
+// likewise (A_hat, or single entries of it, may be NULL); n_iter: NULL or 3 per problem.  The masks of p are ignored (the loop
+// sets its own, :37-38, :43-44, :49-50).  Every refusal comes before the device is touched.
+template <typename TT>
+int dnmf_batch(const char* entry, snmf_batch* (*make)(), snmf_ctx* ctx, const snmf_params* p, int32_t R_x, int32_t R_d, int32_t n,
+               const int32_t* T, const TT* const* Y, const TT* const* X, const TT* const* D, const TT* const* B, const TT* const* H0,
+               TT* const* B_hat, TT* const* A_hat, int32_t* n_iter) {
+    if (!ctx || !p || !T || !Y || !X || !D || !B || !H0 || !B_hat) return fail(SNMF_ERR_INVALID, "%s: NULL argument", entry);
+    if (n < 1) return fail(SNMF_ERR_INVALID, "%s: n_problems must be at least 1 (got %d)", entry, n);
+    for (int i = 0; i < n; ++i) {
+        if (!Y[i] || !X[i] || !D[i] || !B[i] || !H0[i] || !B_hat[i]) return fail(SNMF_ERR_INVALID, "%s: an array of problem %d is NULL", entry, i);
+        if (T[i] < 1) return fail(SNMF_ERR_INVALID, "problem %d has T = %d frames (at least 1)", i, T[i]);
+    }
+    // (as loop3_create of snmf_tu_dnmf.hip)
+    if (R_x < 1 || R_d < 1 || p->r != R_x + R_d) return fail(SNMF_ERR_DIM, "params->r = %d must equal R_x + R_d = %d + %d", p->r, R_x, R_d);
+    if (p->sparsity_kind != SNMF_SPARSITY_SCALAR)
+        return fail(SNMF_ERR_DIM, "run_basis_DNMF needs a scalar p.sparsity (its W-only solves have R_x / R_d rows)");
+    const int F = p->F;
+    const std::vector<uint8_t> on(p->r, 1), off(p->r, 0);
+    snmf_params q = *p;
+    BatchOwner e1, e2, e3;
+    q.w_update_ind = off.data(), q.h_update_ind = on.data();  // :37-38
+    SN_TRY(batch_create(entry, make(), ctx, &q, n, T, &e1.b));  // (its limits on F and r are the widest of the three)
+    q.w_update_ind = on.data(), q.h_update_ind = off.data();  // :43-44, :49-50
+    q.r = R_x;
+    SN_TRY(batch_create(entry, make(), ctx, &q, n, T, &e2.b));
+    q.r = R_d;
+    SN_TRY(batch_create(entry, make(), ctx, &q, n, T, &e3.b));
+
+    for (int i = 0; i < n; ++i) SN_TRY(batch_set_problem<TT>(e1.b, i, Y[i], F, B[i], H0[i]));  // p.init_w = B   (:39)
+    SN_TRY(batch_run(e1.b, 0));  // [~, A_hat] = sparse_nmf(Y, p)   (:40)
+    // a W-only phase: V and init_w = B(:, row0 + (1:r)) from the host, init_h = A_hat(row0 + (1:r), :) from the Y-engine
+    auto w_phase = [&](snmf_batch* e, const TT* const* V, int row0) -> int {
+        for (int i = 0; i < n; ++i) {
+            SN_TRY(e->load(i, V[i], (int64_t)F, B[i] + (size_t)F * row0, (const TT*)nullptr));
+            batch_mark_set(e, i);
+        }
+        SN_TRY(e->take_h0(*e1.b, row0));
+        return batch_run(e, 0);
+    };
+    SN_TRY(w_phase(e2.b, X, 0));    // :43-47
+    SN_TRY(w_phase(e3.b, D, R_x));  // :49-53
+    for (int i = 0; i < n; ++i) {
+        int32_t* ni = n_iter ? n_iter + 3 * (size_t)i : nullptr;
+        SN_TRY(batch_get<TT>(e1.b, i, (TT*)nullptr, A_hat ? A_hat[i] : (TT*)nullptr, nullptr, nullptr, ni));
+        SN_TRY(batch_get<TT>(e2.b, i, B_hat[i], (TT*)nullptr, nullptr, nullptr, ni ? ni + 1 : nullptr));  // B_hat = [B_hat_x, B_hat_d]   (:55)
+        SN_TRY(batch_get<TT>(e3.b, i, B_hat[i] + (size_t)F * R_x, (TT*)nullptr, nullptr, nullptr, ni ? ni + 2 : nullptr));
+    }
+    return SNMF_OK;
 }

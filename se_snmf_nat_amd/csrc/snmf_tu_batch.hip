@@ -5,7 +5,7 @@
 // frozen on the device.  The life of the handle -- validation, call order, the run loop and its polls of the stopped counter,
 // what get() reports -- is snmf_batch_host.h's, shared with the fp64 engine of snmf_tu_batch64.hip; the entries that make a
 // handle (snmf_batch_create, _create_fp64 and _create_mdi_fp64: the fp64 engine with masks) are the one place that chooses between
-// the engines.
+// the engines.  The batched DNMF loop (snmf_run_basis_dnmf_batch_*) is dnmf_batch of the same header on three engines of one kind.
 #include "snmf_internal.h"
 #include "snmf_batch.h"
 #include "snmf_batch_host.h"
@@ -38,6 +38,7 @@ struct Batch32 final : snmf_batch {
     int upload_sparsity(const double* sparsity) override;
     int load(int k, const double* V, int64_t ldV, const double* W0, const double* H0) override { return load_t(k, V, ldV, W0, H0); }
     int load(int k, const float* V, int64_t ldV, const float* W0, const float* H0) override { return load_t(k, V, ldV, W0, H0); }
+    int take_h0(snmf_batch& src, int row0) override;
     int iterate(int j) override;
     int close_run() override;
     Device device() override { return Device{a.n_stopped, a.st, h_st.data(), sizeof(BState), a.divh, a.costh}; }
@@ -52,6 +53,7 @@ struct Batch32 final : snmf_batch {
 
     template <typename TT>
     int load_t(int k, const TT* V, int64_t ldV, const TT* W0, const TT* H0);
+    int scale_h0(int k);
     template <typename TT>
     int fetch_t(int k, TT* W, TT* H);
 };
@@ -233,11 +235,33 @@ int Batch32::load_t(int k, const TT* V, int64_t ldV, const TT* W0, const TT* H0)
     const size_t fr0 = (size_t)q.tile0 * 32;
     const int Tp = q.n_tiles * 32;
     SN_TRY((xfer_pack_in<TT, float>(ctx, V, ldV, a.F, q.T, const_cast<float*>(a.V) + fr0 * a.Fp, a.Fp, Tp, p.floor_v != 0)));
-    SN_TRY((xfer_pack_in<TT, float>(ctx, H0, a.r, a.r, q.T, a.H[0] + fr0 * a.rp, a.rp, Tp, false)));
+    if (H0) SN_TRY((xfer_pack_in<TT, float>(ctx, H0, a.r, a.r, q.T, a.H[0] + fr0 * a.rp, a.rp, Tp, false)));
     SN_TRY((xfer_pack_in<TT, double>(ctx, W0, a.F, a.F, a.r, Wraw, a.Fp, a.rp, false)));
     SN_TRY(launch_fin_bm(this, k, 1, 1, 0, 0, 0));  // :157-158
-    hipLaunchKernelGGL(k_bscale, dim3(std::min(1024, grid_for((size_t)q.T * a.rp))), dim3(256), 0, ctx->stream, a, k);  // :159
+    return H0 ? scale_h0(k) : SNMF_OK;
+}
+
+int Batch32::scale_h0(int k) {  // :159
+    hipLaunchKernelGGL(k_bscale, dim3(std::min(1024, grid_for((size_t)prob[k].T * a.rp))), dim3(256), 0, ctx->stream, a, k);
     HIP_TRY(hipGetLastError());
+    return SNMF_OK;
+}
+
+// One launch over every (problem, tile) of this batch -- the tile table of the H step -- copies the rows from the buffer that holds
+// each problem's stop iterate in `src` (what its fetch_t reads); then the scaling load() does, problem by problem.
+int Batch32::take_h0(snmf_batch& src_, int row0) {
+    const Batch32* src = dynamic_cast<const Batch32*>(&src_);
+    if (!src || src == this) return fail(SNMF_ERR_INTERNAL, "take_h0: the source is not another fp32 batch engine");
+    if (!src->ran || src->ctx != ctx) return fail(SNMF_ERR_STATE, "take_h0: the source batch has not run on this context");
+    if (row0 < 0 || row0 + a.r > src->a.r) return fail(SNMF_ERR_DIM, "take_h0: rows [%d, %d) of an H of %d rows", row0, row0 + a.r, src->a.r);
+    if (src->B != B) return fail(SNMF_ERR_DIM, "take_h0: %d problems from a batch of %d", B, src->B);
+    for (int k = 0; k < B; ++k)  // (equal frame counts give equal tile tables)
+        if (src->prob[k].T != prob[k].T) return fail(SNMF_ERR_DIM, "take_h0: problem %d has %d frames, its source %d", k, prob[k].T, src->prob[k].T);
+    cur = 0;
+    hipLaunchKernelGGL(k_btake_h, dim3(n_tiles), dim3(256), 0, ctx->stream, a, (const float*)src->a.H[0], (const float*)src->a.H[1],
+                       (const BState*)src->a.st, src->cur, src->a.rp, row0);
+    HIP_TRY(hipGetLastError());
+    for (int k = 0; k < B; ++k) SN_TRY(scale_h0(k));
     return SNMF_OK;
 }
 
@@ -440,4 +464,26 @@ extern "C" int snmf_mdi_batch_fp64(snmf_ctx* ctx, const snmf_params* p, int32_t 
     }
     snmf_batch_destroy(b);
     return s;
+}
+
+// run_basis_DNMF for a batch: dnmf_batch of snmf_batch_host.h on three engines of the entry's kind
+static snmf_batch* make32() { return new Batch32(); }
+static snmf_batch* make64() { return batch64_new(); }
+extern "C" int snmf_run_basis_dnmf_batch_f64(snmf_ctx* ctx, const snmf_params* p, int32_t R_x, int32_t R_d, int32_t n_problems,
+                                             const int32_t* T, const double* const* Y, const double* const* X, const double* const* D,
+                                             const double* const* B, const double* const* H0, double* const* B_hat, double* const* A_hat,
+                                             int32_t* n_iter) {
+    return dnmf_batch<double>("snmf_run_basis_dnmf_batch_f64", make32, ctx, p, R_x, R_d, n_problems, T, Y, X, D, B, H0, B_hat, A_hat, n_iter);
+}
+extern "C" int snmf_run_basis_dnmf_batch_f32(snmf_ctx* ctx, const snmf_params* p, int32_t R_x, int32_t R_d, int32_t n_problems,
+                                             const int32_t* T, const float* const* Y, const float* const* X, const float* const* D,
+                                             const float* const* B, const float* const* H0, float* const* B_hat, float* const* A_hat,
+                                             int32_t* n_iter) {
+    return dnmf_batch<float>("snmf_run_basis_dnmf_batch_f32", make32, ctx, p, R_x, R_d, n_problems, T, Y, X, D, B, H0, B_hat, A_hat, n_iter);
+}
+extern "C" int snmf_run_basis_dnmf_batch_fp64(snmf_ctx* ctx, const snmf_params* p, int32_t R_x, int32_t R_d, int32_t n_problems,
+                                              const int32_t* T, const double* const* Y, const double* const* X, const double* const* D,
+                                              const double* const* B, const double* const* H0, double* const* B_hat, double* const* A_hat,
+                                              int32_t* n_iter) {
+    return dnmf_batch<double>("snmf_run_basis_dnmf_batch_fp64", make64, ctx, p, R_x, R_d, n_problems, T, Y, X, D, B, H0, B_hat, A_hat, n_iter);
 }

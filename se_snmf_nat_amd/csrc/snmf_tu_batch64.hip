@@ -65,6 +65,7 @@ struct Batch64 final : snmf_batch {
     int load_mdi(int k, const double* V, int64_t ldV, const double* M, int64_t ldM, const double* W0, const double* H0) override {
         return load_t(k, V, ldV, W0, H0, M, ldM);
     }
+    int take_h0(snmf_batch& src, int row0) override;
     int fetch_v_mdi(int k, double* V_mdi, int64_t ld) override;
     int iterate(int it) override;
     int close_run() override { return SNMF_OK; }  // (the objective and the stop test of an iteration run inside it)
@@ -80,6 +81,7 @@ struct Batch64 final : snmf_batch {
 
     template <typename TT>
     int load_t(int k, const TT* V, int64_t ldV, const TT* W0, const TT* H0, const TT* M = nullptr, int64_t ldM = 0);
+    int scale_h0(int k);
     template <typename TT>
     int fetch_t(int k, TT* W, TT* H);
 };
@@ -339,19 +341,18 @@ template <typename TT>
 int Batch64::load_t(int k, const TT* V, int64_t ldV, const TT* W0, const TT* H0, const TT* M, int64_t ldM) {
     const B64Prob& q = prob[k];
     const int F = a.F, r = a.r, T = q.T;
-    const long long nFT = (long long)F * T, nRT = (long long)r * T;
+    const long long nFT = (long long)F * T;
     double *dV = a.V + q.fr0 * F, *dH = a.H + q.fr0 * r, *dW = a.W + (long long)k * F * r, *dwn = a.wn + (long long)k * r;
     hipStream_t st = ctx->stream;
     // (tight on the device; fp32 arrays are widened on the way in)
     SN_TRY((xfer_pack_in<TT, double>(ctx, V, ldV, F, T, dV, F, T, false)));
     if (masked) SN_TRY((xfer_pack_in<TT, double>(ctx, M, ldM, F, T, Mblk + q.fr0 * F, F, T, false)));
-    SN_TRY((xfer_pack_in<TT, double>(ctx, H0, r, r, T, dH, r, T, false)));
+    if (H0) SN_TRY((xfer_pack_in<TT, double>(ctx, H0, r, r, T, dH, r, T, false)));
     SN_TRY((xfer_pack_in<TT, double>(ctx, W0, F, F, r, dW, F, r, false)));
     // the initial scaling (:157-169) with the single solve's own kernels, on this problem's arrays
     hipLaunchKernelGGL((k_s64_wupd<true, false>), dim3(r), dim3(256), 0, st, dW, nullptr, nullptr, nullptr, nullptr, F, dwn, &a.st[k].stop);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_s64_hscale, dim3(grid64(nRT)), dim3(256), 0, st, dH, dwn, r, nRT);
-    HIP_TRY(hipGetLastError());
+    if (H0) SN_TRY(scale_h0(k));
     if (masked) {  // src/snmf_mdi.m:175, the masked start (it floors: floor_v has no meaning here)
         hipLaunchKernelGGL(k_s64_mdi_start, dim3(grid64(nFT)), dim3(256), 0, st, dV, (const double*)(Mblk + q.fr0 * F), nFT);
         HIP_TRY(hipGetLastError());
@@ -359,6 +360,31 @@ int Batch64::load_t(int k, const TT* V, int64_t ldV, const TT* W0, const TT* H0,
         hipLaunchKernelGGL(k_s64_floor, dim3(grid64(nFT)), dim3(256), 0, st, dV, nFT);
         HIP_TRY(hipGetLastError());
     }
+    return SNMF_OK;
+}
+
+int Batch64::scale_h0(int k) {  // :159-160, with the single solve's own kernel
+    const long long nRT = (long long)a.r * prob[k].T;
+    hipLaunchKernelGGL(k_s64_hscale, dim3(grid64(nRT)), dim3(256), 0, ctx->stream, a.H + prob[k].fr0 * a.r, a.wn + (long long)k * a.r, a.r, nRT);
+    HIP_TRY(hipGetLastError());
+    return SNMF_OK;
+}
+
+int elem_grid(const Batch64* s, long long rows);
+
+// One launch with the problem as a grid index copies the rows (a stopped problem's H is its stop iterate: nothing writes it
+// after the test has fired); then the scaling load() does, problem by problem.
+int Batch64::take_h0(snmf_batch& src_, int row0) {
+    const Batch64* src = dynamic_cast<const Batch64*>(&src_);
+    if (!src || src == this) return fail(SNMF_ERR_INTERNAL, "take_h0: the source is not another fp64 batch engine");
+    if (!src->ran || src->ctx != ctx) return fail(SNMF_ERR_STATE, "take_h0: the source batch has not run on this context");
+    if (row0 < 0 || row0 + a.r > src->a.r) return fail(SNMF_ERR_DIM, "take_h0: rows [%d, %d) of an H of %d rows", row0, row0 + a.r, src->a.r);
+    if (src->B != B) return fail(SNMF_ERR_DIM, "take_h0: %d problems from a batch of %d", B, src->B);
+    for (int k = 0; k < B; ++k)  // (equal frame counts give equal frame offsets)
+        if (src->prob[k].T != prob[k].T) return fail(SNMF_ERR_DIM, "take_h0: problem %d has %d frames, its source %d", k, prob[k].T, src->prob[k].T);
+    hipLaunchKernelGGL(k_b64_take_h, dim3(elem_grid(this, a.r), B), dim3(256), 0, ctx->stream, a, (const double*)src->a.H, src->a.r, row0);
+    HIP_TRY(hipGetLastError());
+    for (int k = 0; k < B; ++k) SN_TRY(scale_h0(k));
     return SNMF_OK;
 }
 
