@@ -846,6 +846,52 @@ int snmf_run_basis_dnmf_batch_fp64(snmf_ctx* ctx, const snmf_params* p, int32_t 
                                    const double* const* Y, const double* const* X, const double* const* D, const double* const* B,
                                    const double* const* H0, double* const* B_hat, double* const* A_hat, int32_t* n_iter);
 
+/* Added within 5.  The spectrogram front-end for n_signals signals at once: what snmf_stft_features_f32 / _fp64 give for each
+ * signal alone (and, with mel != NULL -- row-major mel_M x (fftlength/2+1), as snmf_mel_features_* take it -- what
+ * snmf_mel_features_* make of that), bit for bit, from launches shared by all signals: their number does not depend on n_signals.
+ * Host arrays in and out; the samples go up as one slab.  samples, n_samples, V_out: n_signals entries each; V_out[k] is tight,
+ * rows x n_frames_out[k] with rows = (2 * splice + 1) * (fftlength/2+1), or (2 * splice + 1) * mel_M with mel (the matrices of a
+ * batch are tight, as in snmf_run_basis_dnmf_batch_*).  n_frames_out: NULL, or n_signals counts.  A signal shorter than one frame gives
+ * n_frames_out[k] = 0 and nothing of it is read or written, as in the single entry.  Refused before the device is touched: NULL
+ * arguments, n_signals < 1, mel_M < 1 with mel (SNMF_ERR_INVALID), the refusals of the single entry for sp. */
+int snmf_stft_features_batch_f32(snmf_ctx* ctx, const snmf_stft_params* sp, int32_t n_signals, const float* const* samples,
+                                 const int64_t* n_samples, const float* mel, int32_t mel_M, float* const* V_out, int32_t* n_frames_out);
+int snmf_stft_features_batch_fp64(snmf_ctx* ctx, const snmf_stft_params* sp, int32_t n_signals, const double* const* samples,
+                                  const int64_t* n_samples, const double* mel, int32_t mel_M, double* const* V_out,
+                                  int32_t* n_frames_out);
+
+/* Added within 5.  run_basis_DNMF (run_basis_DNMF.m:1-55; with mel its twin run_basis_DNMF_Mel.m) for n_problems pairs of
+ * WAVEFORMS at once: snmf_run_basis_dnmf_batch_* with the features formed on the device, as snmf_run_basis_dnmf_audio_* form them
+ * for one pair.  Problem k: x_k (n_x[k] samples) and d_k (n_d[k] samples) are cut to their common length (:5-9), y_k = x_k + d_k
+ * in the sample type (:10), T_k = snmf_stft_num_frames(sp, min(n_x[k], n_d[k])).  The waveforms cross as one slab; the three
+ * feature sets of all problems are written by shared launches straight into the three resident batches, and A_hat passes between
+ * them on the device.  p->F must be the feature rows, (2 * splice + 1) * (fftlength/2+1), or (2 * splice + 1) * mel_M with mel
+ * (SNMF_ERR_DIM); p->r = R_x + R_d; p->T and the masks of p are ignored.  Every matrix is tight and column-major, as in
+ * snmf_run_basis_dnmf_batch_*: B_k, B_hat_k F x (R_x + R_d); H0_k, A_hat_k (R_x + R_d) x T_k.  H0: NULL, or n_problems pointers of
+ * which single ones may be NULL: such a problem starts from the Philox draw of snmf_plan_set_h_random keyed by seed[k] (seed:
+ * n_problems entries, read only there).  A_hat: NULL, or pointers of which single ones may be NULL.  n_iter: NULL, or 3 per problem.
+ *   _f64   the fp32 engine, named after its host type like snmf_run_basis_dnmf_audio_f64: float samples and Mel table, fp32
+ *          features.  THE CONTRACT: bit for bit snmf_run_basis_dnmf_batch_f64 fed the outputs of snmf_stft_features_f32
+ *          (+ snmf_mel_features_f32) on y_k, x_k, d_k widened to double, B_k, and H0_k or the draw.  Envelope: the fp32 batch's
+ *          (F <= 513, R_x + R_d <= 200), SNMF_ERR_UNSUPPORTED.
+ *   _fp64  the fp64 engine: double samples and Mel table, everything in double, no limit on F or r of its own.  THE CONTRACT:
+ *          B_hat_k, A_hat_k and the three counts are bit for bit those of snmf_run_basis_dnmf_audio_fp64 run alone on
+ *          (x_k, d_k, B_k) with the same H0_k, or with H0 = NULL and the same seed.
+ * Refused before the device is touched: NULL arguments, n_problems < 1, a problem shorter than one analysis frame, mel_M < 1
+ * with mel, a problem without H0 when seed is NULL (SNMF_ERR_INVALID); the refusals of the single entry for sp; R_x < 1,
+ * R_d < 1, p->r != R_x + R_d, a sparsity that is not SNMF_SPARSITY_SCALAR (SNMF_ERR_DIM).  A failed allocation is
+ * SNMF_ERR_NOMEM; everything is freed and the context stays usable.  One-shot entries: no handle, no device list. */
+int snmf_run_basis_dnmf_audio_batch_f64(snmf_ctx* ctx, const snmf_params* p, const snmf_stft_params* sp, int32_t R_x, int32_t R_d,
+                                        int32_t n_problems, const float* const* x, const int64_t* n_x, const float* const* d,
+                                        const int64_t* n_d, const float* mel, int32_t mel_M, const double* const* B,
+                                        const double* const* H0, const uint64_t* seed, double* const* B_hat, double* const* A_hat,
+                                        int32_t* n_iter);
+int snmf_run_basis_dnmf_audio_batch_fp64(snmf_ctx* ctx, const snmf_params* p, const snmf_stft_params* sp, int32_t R_x, int32_t R_d,
+                                         int32_t n_problems, const double* const* x, const int64_t* n_x, const double* const* d,
+                                         const int64_t* n_d, const double* mel, int32_t mel_M, const double* const* B,
+                                         const double* const* H0, const uint64_t* seed, double* const* B_hat, double* const* A_hat,
+                                         int32_t* n_iter);
+
 /* ---- instrumentation (bench.py: HIP-event timing on the engine's own stream) ------------ */
 /* Average device time in milliseconds per launch of the named kernel family over the launches
  * recorded since snmf_ctx_timing(ctx, 1) was switched on.  Families: "hstep", "wstats",

@@ -46,8 +46,9 @@ _TU_HDRS = {
     "snmf_tu_geometry.hip": ["snmf_generic.h"],
     "snmf_tu_solve64.hip": ["snmf_solve64.h", "snmf_solve64_core.h", "snmf_host64.h"],
     "snmf_tu_train64.hip": ["snmf_online_common.h", "snmf_frontend64.h", "snmf_philox.h", "snmf_solve64_core.h", "snmf_host64.h"],
-    "snmf_tu_batch.hip": ["snmf_batch.h", "snmf_batch_host.h"],
-    "snmf_tu_batch64.hip": ["snmf_solve64.h", "snmf_batch64.h", "snmf_batch_host.h", "snmf_host64.h"],
+    "snmf_tu_batch.hip": ["snmf_batch.h", "snmf_batch_host.h", "snmf_philox.h"],
+    "snmf_tu_batch64.hip": ["snmf_solve64.h", "snmf_batch64.h", "snmf_batch_host.h", "snmf_host64.h", "snmf_philox.h"],
+    "snmf_tu_frontend_batch.hip": ["snmf_online_common.h", "snmf_frontend_batch.h", "snmf_batch_host.h"],
 }
 HDRS = sorted(_glob.glob(os.path.join(_HERE, "csrc", "*.h"))) + [os.path.join(_ROOT, "include", "snmf.h")]
 
@@ -94,6 +95,8 @@ SYMBOLS = [
     "snmf_batch_create_fp64", "snmf_sparse_nmf_batch_fp64",
     "snmf_batch_create_mdi_fp64", "snmf_batch_set_problem_mdi_f64", "snmf_batch_get_v_mdi_f64", "snmf_mdi_batch_fp64",
     "snmf_run_basis_dnmf_batch_f64", "snmf_run_basis_dnmf_batch_f32", "snmf_run_basis_dnmf_batch_fp64",
+    "snmf_stft_features_batch_f32", "snmf_stft_features_batch_fp64",
+    "snmf_run_basis_dnmf_audio_batch_f64", "snmf_run_basis_dnmf_audio_batch_fp64",
     "snmf_rccl_available", "snmf_rccl_get_unique_id", "snmf_rccl_comm_create", "snmf_rccl_comm_destroy", "snmf_plan_run_sharded_rccl",
 ]
 ABI_VERSION = 5  # include/snmf.h: SNMF_ABI_VERSION this binding was written against
@@ -375,6 +378,11 @@ def load():
     # run_basis_DNMF for a batch: tight arrays only, so no leading dimensions
     for ty in ("f64", "f32", "fp64"):
         sig[f"snmf_run_basis_dnmf_batch_{ty}"] = (C.c_int, [vp, PP, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp])
+    # the front-end and run_basis_DNMF for a batch of waveforms: arrays of pointers and of lengths, tight matrices
+    for ty in ("f32", "fp64"):
+        sig[f"snmf_stft_features_batch_{ty}"] = (C.c_int, [vp, SP, i32, vp, vp, vp, i32, vp, vp])
+    for ty in ("f64", "fp64"):
+        sig[f"snmf_run_basis_dnmf_audio_batch_{ty}"] = (C.c_int, [vp, PP, SP, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp])
     lib.snmf_abi_version.restype = C.c_int
     if lib.snmf_abi_version() != ABI_VERSION:  # a stale library must not be driven through newer prototypes
         raise ImportError(f"{path} has ABI version {lib.snmf_abi_version()}, this binding needs {ABI_VERSION}: rebuild the library")

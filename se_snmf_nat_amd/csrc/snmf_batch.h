@@ -12,6 +12,8 @@
 //             renormalisation are column-local), and the column's entries of the W images of the next H step
 //   k_bfold : the objective fold + stop test alone (loops that do not update W, and the last iterate of a run)
 //   k_btake_h : one (problem, tile): the initial H of this batch from rows of the result H of another batch (the batched DNMF loop)
+//   k_bfloor_v, k_brand_h : grid (workgroups, problem): the V floor on a V that was written on the device, and an initial H drawn
+//             on the device (the batched DNMF loop from waveforms)
 //
 // Layouts: the engine's (snmf_kernels.h, StepArgs): V [Ttot][Fp], H [Ttot][rp], Wt4 / Wk4 per problem; the frames of
 // problem b start at tile prob[b].tile0, so a tile never spans two problems.  A problem's last tile is partial when T_b is
@@ -24,6 +26,7 @@
 // A problem whose stop test fired is frozen: BState::stop is read at the top of every workgroup of that problem.
 #pragma once
 #include "snmf_kernels.h"
+#include "snmf_philox.h"
 
 namespace snmf {
 
@@ -597,6 +600,45 @@ static __global__ __launch_bounds__(256) void k_btake_h(BatchArgs a, const float
         const int t = i / a.rp, k = i - t * a.rp;
         const long long fr = fr0 + t;
         H[fr * a.rp + k] = (k < a.r && t < Tl) ? S[fr * srp + row0 + k] : 0.f;
+    }
+}
+
+// v = max(v, flr) (src/sparse_nmf.m:169) on the real F x T_b entries of problem blockIdx.y: what k_pack does on the way in, for a
+// V that the grouped front-end wrote into the [frame][Fp] layout.  Pad rows and pad frames are not touched (they hold zeros).
+static __global__ __launch_bounds__(256) void k_bfloor_v(BatchArgs a, float* __restrict__ V) {
+    const BProb pb = a.prob[blockIdx.y];
+    float* __restrict__ Vb = V + 32LL * pb.tile0 * a.Fp;
+    const long long n = (long long)pb.T * a.Fp;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        if ((int)(i % a.Fp) >= a.F) continue;
+        const float v = Vb[i];
+        Vb[i] = v > kFlr ? v : kFlr;
+    }
+}
+
+// H0 of problem blockIdx.y drawn on the device, in buffer 0: H[t][k] = u(k + r * t), the Philox stream of snmf_plan_set_h_random
+// (k_rand_h, snmf_tu_dnmf.hip) keyed by seed[b] -- element index in the column-major r x T_b matrix, counter = index / 4.  Every
+// entry of the problem's tiles is written: pad rows and pad frames as zeros.  draw[b] == 0: the problem's H0 came from the host.
+static __global__ __launch_bounds__(256) void k_brand_h(BatchArgs a, const uint64_t* __restrict__ seed, const uint8_t* __restrict__ draw) {
+    const int b = blockIdx.y;
+    if (!draw[b]) return;
+    const BProb pb = a.prob[b];
+    const uint64_t sd = seed[b];
+    float* __restrict__ H = a.H[0] + 32LL * pb.tile0 * a.rp;
+    const long long n = 32LL * pb.n_tiles * a.rp;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        const long long t = i / a.rp;
+        const int k = (int)(i - t * a.rp);
+        float v = 0.f;
+        if (k < a.r && t < pb.T) {
+            const uint64_t e = (uint64_t)k + (uint64_t)a.r * (uint64_t)t, q = e >> 2;
+            uint32_t o[4];
+            philox4x32_10((uint32_t)q, (uint32_t)(q >> 32), 0u, 0u, (uint32_t)sd, (uint32_t)(sd >> 32), o);
+            const int j = (int)(e & 3);
+            const uint32_t x = j == 0 ? o[0] : (j == 1 ? o[1] : (j == 2 ? o[2] : o[3]));  // (no indexed array: no scratch)
+            v = ((float)(x >> 9) + 0.5f) * (1.0f / 8388608.0f);
+        }
+        H[i] = v;
     }
 }
 

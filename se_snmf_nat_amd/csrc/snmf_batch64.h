@@ -12,6 +12,7 @@
 // ============================================================================================
 #pragma once
 
+#include "snmf_philox.h"
 #include "snmf_solve64.h"
 
 namespace snmf {
@@ -92,6 +93,25 @@ static __global__ __launch_bounds__(256) void k_b64_take_h(B64Args a, const doub
         const long long t = i / a.r;
         const int k = (int)(i - t * a.r);
         H[i] = S[t * r_src + k];
+    }
+}
+
+// grid (workgroups, B): H0 of problem b drawn on the device: H[e] = u(e), e the element index in the tight column-major a.r x T_b
+// matrix -- k_rand64 (snmf_frontend64.h) per problem, keyed by seed[b].  draw[b] == 0: the problem's H0 came from the host.
+static __global__ __launch_bounds__(256) void k_b64_rand_h(B64Args a, const uint64_t* __restrict__ seed, const uint8_t* __restrict__ draw) {
+    const int b = blockIdx.y;
+    if (!draw[b]) return;
+    const B64Prob p = a.prob[b];
+    const uint64_t sd = seed[b], n = (uint64_t)a.r * (uint64_t)p.T, n4 = (n + 3) / 4;
+    double* __restrict__ H = a.H + p.fr0 * a.r;
+    for (uint64_t q = (uint64_t)blockIdx.x * 256 + threadIdx.x; q < n4; q += (uint64_t)gridDim.x * 256) {
+        uint32_t o[4];
+        philox4x32_10((uint32_t)q, (uint32_t)(q >> 32), 0u, 0u, (uint32_t)sd, (uint32_t)(sd >> 32), o);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint64_t e = 4 * q + j;
+            if (e < n) H[e] = ((double)(o[j] >> 9) + 0.5) * (1.0 / 8388608.0);
+        }
     }
 }
 

@@ -9,6 +9,7 @@
 // their masks (batch_set_problem_mdi), and the imputed V of a problem can be read (batch_get_v_mdi); everything else -- run, get,
 // describe, destroy, the new batch on a used handle -- is the life below, unchanged.
 #pragma once
+#include <functional>
 #include <memory>
 
 #include "snmf_internal.h"
@@ -38,9 +39,25 @@ struct snmf_batch {
     virtual int reset() = 0;  // the device state of a batch that has not run
     virtual int upload_sparsity(const double* sparsity) = 0;  // r entries; the caller's array may go on return
     // problem k from host arrays, and its initial scaling (src/sparse_nmf.m:157-169).  H0 == nullptr: V, W0 and the scaling of W
-    // only -- the problem's H0 is still to come, for every problem at once, through take_h0
+    // only -- the problem's H0 is still to come, for every problem at once, through take_h0 or draw_h0.  V == nullptr: W0 (and H0)
+    // only -- V of every problem is written on the device, through v_blocks / v_written
     virtual int load(int k, const double* V, int64_t ldV, const double* W0, const double* H0) = 0;
     virtual int load(int k, const float* V, int64_t ldV, const float* W0, const float* H0) = 0;
+    // V of every problem from device memory instead of a host pointer.  v_blocks hands out where problem k's V lies -- column t at
+    // V + t * ld, F rows of v_elem() bytes -- after making everything around those entries what load() leaves there (the fp32
+    // engine: zeroed pad rows and pad frames); work on the context's stream then writes every entry of every block, and v_written
+    // runs what load() runs after its upload (the V floor of :169), so that the solve sees what load() would have left.
+    struct VBlock {
+        void* V;
+        int64_t ld;
+    };
+    virtual size_t v_elem() const = 0;
+    virtual int v_blocks(std::vector<VBlock>* out) = 0;
+    virtual int v_written() = 0;
+    // H0 of the problems with draw[k] != 0 on the device: the Philox stream of snmf_plan_set_h_random keyed by seed[k], element
+    // index in the column-major r x T_k matrix; then, for those problems, the initial scaling of H (:159-160) by the norms load()
+    // left.  Each of them must have been loaded with H0 == nullptr.
+    virtual int draw_h0(const uint64_t* seed, const uint8_t* draw) = 0;
     // H0 of every problem from rows [row0, row0 + r) of the result H of `src` -- another engine of this kind with the same frame
     // counts, whose run has ended -- then the initial scaling of H (:159-160) by the norms load() left: what load() does with
     // a host H0, without H leaving the device.  Every problem must have been loaded with H0 == nullptr.
@@ -69,6 +86,7 @@ struct snmf_batch {
 };
 
 snmf_batch* batch64_new(bool masked = false);  // snmf_tu_batch64.hip: an fp64 engine (masked: of missing-data solves), not built yet
+snmf_batch* batch32_new();                     // snmf_tu_batch.hip: an fp32 engine, not built yet
 
 #define BATCH_CHECK(b)                                          \
     if (!(b)) return fail(SNMF_ERR_INVALID, "batch is NULL");   \
@@ -236,6 +254,8 @@ inline int batch_get_v_mdi(snmf_batch* b, int32_t k, double* V_mdi, int64_t ld) 
 // (r = R_x, W only) and the D-batch (r = R_d, W only).  Each phase is one batch_run, so every problem stops each of its three
 // solves at its own iteration and the polling is the batch's; between the phases A_hat goes from the Y-engine into the other two
 // through take_h0 and never leaves the device.  Like the rest of this file, the driver does not ask which engine it drives.
+// The matrix form (dnmf_batch) and the audio form (snmf_run_basis_dnmf_audio_batch_*, snmf_tu_frontend_batch.hip) share it:
+// dnmf_batch_run has the three phases, DnmfInputs says where V and H0 come from.
 struct BatchOwner {  // an engine that dies with the call
     snmf_batch* b = nullptr;
     ~BatchOwner() {
@@ -246,19 +266,23 @@ struct BatchOwner {  // an engine that dies with the call
     }
 };
 
+// Where V of the three phases and H0 of solve 1 come from.  The matrix form: host arrays, through load().  The audio form
+// (snmf_tu_frontend_batch.hip): `device_v` writes the features of every problem of phase `kind` (0, 1, 2: the mixtures, the clean, the
+// noise signals) into the blocks the phase's engine hands out, and an H0_k that is not given is drawn on the device from seed[k].
+template <typename TT>
+struct DnmfInputs {
+    const TT* const* V[3] = {nullptr, nullptr, nullptr};  // Y, X, D: tight F x T[k] on the host, or all three nullptr
+    std::function<int(int kind, const std::vector<snmf_batch::VBlock>& blocks, size_t elem)> device_v;
+    const TT* const* H0 = nullptr;                          // the audio form: may be nullptr, or hold nullptr entries
+    const uint64_t* seed = nullptr;                         // n, read where H0_k is not given
+};
+
 // Every matrix tight and column-major: Y_k, X_k, D_k F x T[k], B_k F x (R_x + R_d), H0_k (R_x + R_d) x T[k]; B_hat_k and A_hat_k
 // likewise (A_hat, or single entries of it, may be NULL); n_iter: NULL or 3 per problem.  The masks of p are ignored (the loop
-// sets its own, :37-38, :43-44, :49-50).  Every refusal comes before the device is touched.
+// sets its own, :37-38, :43-44, :49-50).  Every refusal comes before the device is touched; the caller has checked `in`.
 template <typename TT>
-int dnmf_batch(const char* entry, snmf_batch* (*make)(), snmf_ctx* ctx, const snmf_params* p, int32_t R_x, int32_t R_d, int32_t n,
-               const int32_t* T, const TT* const* Y, const TT* const* X, const TT* const* D, const TT* const* B, const TT* const* H0,
-               TT* const* B_hat, TT* const* A_hat, int32_t* n_iter) {
-    if (!ctx || !p || !T || !Y || !X || !D || !B || !H0 || !B_hat) return fail(SNMF_ERR_INVALID, "%s: NULL argument", entry);
-    if (n < 1) return fail(SNMF_ERR_INVALID, "%s: n_problems must be at least 1 (got %d)", entry, n);
-    for (int i = 0; i < n; ++i) {
-        if (!Y[i] || !X[i] || !D[i] || !B[i] || !H0[i] || !B_hat[i]) return fail(SNMF_ERR_INVALID, "%s: an array of problem %d is NULL", entry, i);
-        if (T[i] < 1) return fail(SNMF_ERR_INVALID, "problem %d has T = %d frames (at least 1)", i, T[i]);
-    }
+int dnmf_batch_run(const char* entry, snmf_batch* (*make)(), snmf_ctx* ctx, const snmf_params* p, int32_t R_x, int32_t R_d, int32_t n,
+                   const int32_t* T, const DnmfInputs<TT>& in, const TT* const* B, TT* const* B_hat, TT* const* A_hat, int32_t* n_iter) {
     // (as loop3_create of snmf_tu_dnmf.hip)
     if (R_x < 1 || R_d < 1 || p->r != R_x + R_d) return fail(SNMF_ERR_DIM, "params->r = %d must equal R_x + R_d = %d + %d", p->r, R_x, R_d);
     if (p->sparsity_kind != SNMF_SPARSITY_SCALAR)
@@ -275,19 +299,34 @@ int dnmf_batch(const char* entry, snmf_batch* (*make)(), snmf_ctx* ctx, const sn
     q.r = R_d;
     SN_TRY(batch_create(entry, make(), ctx, &q, n, T, &e3.b));
 
-    for (int i = 0; i < n; ++i) SN_TRY(batch_set_problem<TT>(e1.b, i, Y[i], F, B[i], H0[i]));  // p.init_w = B   (:39)
-    SN_TRY(batch_run(e1.b, 0));  // [~, A_hat] = sparse_nmf(Y, p)   (:40)
-    // a W-only phase: V and init_w = B(:, row0 + (1:r)) from the host, init_h = A_hat(row0 + (1:r), :) from the Y-engine
-    auto w_phase = [&](snmf_batch* e, const TT* const* V, int row0) -> int {
+    // V and init_w = B(:, row0 + (1:r)) of every problem of a phase: from the host through load(), V from the device where it is formed there
+    auto set_phase = [&](snmf_batch* e, int kind, int row0, const TT* const* H0) -> int {
         for (int i = 0; i < n; ++i) {
-            SN_TRY(e->load(i, V[i], (int64_t)F, B[i] + (size_t)F * row0, (const TT*)nullptr));
+            SN_TRY(e->load(i, in.V[kind] ? in.V[kind][i] : (const TT*)nullptr, (int64_t)F, B[i] + (size_t)F * row0, H0 ? H0[i] : (const TT*)nullptr));
             batch_mark_set(e, i);
         }
+        if (in.V[kind]) return SNMF_OK;
+        std::vector<snmf_batch::VBlock> blocks;
+        SN_TRY(e->v_blocks(&blocks));
+        SN_TRY(in.device_v(kind, blocks, e->v_elem()));
+        return e->v_written();
+    };
+    SN_TRY(set_phase(e1.b, 0, 0, in.H0));  // p.init_w = B   (:39)
+    {
+        std::vector<uint8_t> draw(n, 0);
+        bool any = false;
+        for (int i = 0; i < n; ++i) any |= (draw[i] = (!in.H0 || !in.H0[i]) ? 1 : 0) != 0;
+        if (any) SN_TRY(e1.b->draw_h0(in.seed, draw.data()));
+    }
+    SN_TRY(batch_run(e1.b, 0));  // [~, A_hat] = sparse_nmf(Y, p)   (:40)
+    // a W-only phase: init_h = A_hat(row0 + (1:r), :) from the Y-engine
+    auto w_phase = [&](snmf_batch* e, int kind, int row0) -> int {
+        SN_TRY(set_phase(e, kind, row0, nullptr));
         SN_TRY(e->take_h0(*e1.b, row0));
         return batch_run(e, 0);
     };
-    SN_TRY(w_phase(e2.b, X, 0));    // :43-47
-    SN_TRY(w_phase(e3.b, D, R_x));  // :49-53
+    SN_TRY(w_phase(e2.b, 1, 0));    // :43-47
+    SN_TRY(w_phase(e3.b, 2, R_x));  // :49-53
     for (int i = 0; i < n; ++i) {
         int32_t* ni = n_iter ? n_iter + 3 * (size_t)i : nullptr;
         SN_TRY(batch_get<TT>(e1.b, i, (TT*)nullptr, A_hat ? A_hat[i] : (TT*)nullptr, nullptr, nullptr, ni));
@@ -295,4 +334,21 @@ int dnmf_batch(const char* entry, snmf_batch* (*make)(), snmf_ctx* ctx, const sn
         SN_TRY(batch_get<TT>(e3.b, i, B_hat[i] + (size_t)F * R_x, (TT*)nullptr, nullptr, nullptr, ni ? ni + 2 : nullptr));
     }
     return SNMF_OK;
+}
+
+// the matrix form (snmf_run_basis_dnmf_batch_*): its own refusals, then the loop on host arrays
+template <typename TT>
+int dnmf_batch(const char* entry, snmf_batch* (*make)(), snmf_ctx* ctx, const snmf_params* p, int32_t R_x, int32_t R_d, int32_t n,
+               const int32_t* T, const TT* const* Y, const TT* const* X, const TT* const* D, const TT* const* B, const TT* const* H0,
+               TT* const* B_hat, TT* const* A_hat, int32_t* n_iter) {
+    if (!ctx || !p || !T || !Y || !X || !D || !B || !H0 || !B_hat) return fail(SNMF_ERR_INVALID, "%s: NULL argument", entry);
+    if (n < 1) return fail(SNMF_ERR_INVALID, "%s: n_problems must be at least 1 (got %d)", entry, n);
+    for (int i = 0; i < n; ++i) {
+        if (!Y[i] || !X[i] || !D[i] || !B[i] || !H0[i] || !B_hat[i]) return fail(SNMF_ERR_INVALID, "%s: an array of problem %d is NULL", entry, i);
+        if (T[i] < 1) return fail(SNMF_ERR_INVALID, "problem %d has T = %d frames (at least 1)", i, T[i]);
+    }
+    DnmfInputs<TT> in;
+    in.V[0] = Y, in.V[1] = X, in.V[2] = D;
+    in.H0 = H0;
+    return dnmf_batch_run<TT>(entry, make, ctx, p, R_x, R_d, n, T, in, B, B_hat, A_hat, n_iter);
 }

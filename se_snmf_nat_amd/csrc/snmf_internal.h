@@ -2,7 +2,7 @@
 // and plan structures, and the prototypes of the launch dispatchers.  The library is built from several .hip files
 // compiled in parallel (se_snmf_nat_amd/_lib.py): snmf_api.hip (context, plans, data movement, the iteration loop, the
 // front-end), snmf_tu_geometry.hip (the kernels and launch geometry of a plan), snmf_tu_hstep*.hip / snmf_tu_wstats*.hip / snmf_tu_small.hip (the template instantiations of the three big
-// kernel families and their dispatch), snmf_tu_online.hip, snmf_tu_multi.hip, snmf_tu_dnmf.hip.  Nothing here is part of
+// kernel families and their dispatch), snmf_tu_online.hip, snmf_tu_multi.hip, snmf_tu_dnmf.hip, snmf_tu_frontend_batch.hip (the front-end grouped over a batch).  Nothing here is part of
 // the C ABI (include/snmf.h).
 #pragma once
 #include "snmf_kernels.h"
@@ -293,6 +293,9 @@ template <typename TIn, typename TDst>
 int xfer_pack_in(snmf_ctx* ctx, const TIn* src, int64_t ld, int rows, int cols, TDst* dst, int rowsP, int colsP, bool do_floor);
 template <typename TOut, typename TSrc>
 int xfer_unpack_out(snmf_ctx* ctx, const TSrc* src, int rowsP, int rows, int cols, TOut* dst, int64_t ld);
+// n host vectors (len[k] elements each) one behind the other into the tight device vector dst: one pipelined transfer
+template <typename T>
+int xfer_gather_in(snmf_ctx* ctx, int n, const T* const* src, const int64_t* len, T* dst);
 void xfer_destroy(snmf_ctx* c);
 int xfer_sync(snmf_ctx* c);
 // snmf_tu_hstep.hip / snmf_tu_wstats.hip / snmf_tu_small.hip

@@ -39,6 +39,10 @@ struct Batch32 final : snmf_batch {
     int load(int k, const double* V, int64_t ldV, const double* W0, const double* H0) override { return load_t(k, V, ldV, W0, H0); }
     int load(int k, const float* V, int64_t ldV, const float* W0, const float* H0) override { return load_t(k, V, ldV, W0, H0); }
     int take_h0(snmf_batch& src, int row0) override;
+    size_t v_elem() const override { return sizeof(float); }
+    int v_blocks(std::vector<VBlock>* out) override;
+    int v_written() override;
+    int draw_h0(const uint64_t* seed, const uint8_t* draw) override;
     int iterate(int j) override;
     int close_run() override;
     Device device() override { return Device{a.n_stopped, a.st, h_st.data(), sizeof(BState), a.divh, a.costh}; }
@@ -234,7 +238,7 @@ int Batch32::load_t(int k, const TT* V, int64_t ldV, const TT* W0, const TT* H0)
     const BProb& q = prob[k];
     const size_t fr0 = (size_t)q.tile0 * 32;
     const int Tp = q.n_tiles * 32;
-    SN_TRY((xfer_pack_in<TT, float>(ctx, V, ldV, a.F, q.T, const_cast<float*>(a.V) + fr0 * a.Fp, a.Fp, Tp, p.floor_v != 0)));
+    if (V) SN_TRY((xfer_pack_in<TT, float>(ctx, V, ldV, a.F, q.T, const_cast<float*>(a.V) + fr0 * a.Fp, a.Fp, Tp, p.floor_v != 0)));
     if (H0) SN_TRY((xfer_pack_in<TT, float>(ctx, H0, a.r, a.r, q.T, a.H[0] + fr0 * a.rp, a.rp, Tp, false)));
     SN_TRY((xfer_pack_in<TT, double>(ctx, W0, a.F, a.F, a.r, Wraw, a.Fp, a.rp, false)));
     SN_TRY(launch_fin_bm(this, k, 1, 1, 0, 0, 0));  // :157-158
@@ -262,6 +266,48 @@ int Batch32::take_h0(snmf_batch& src_, int row0) {
                        (const BState*)src->a.st, src->cur, src->a.rp, row0);
     HIP_TRY(hipGetLastError());
     for (int k = 0; k < B; ++k) SN_TRY(scale_h0(k));
+    return SNMF_OK;
+}
+
+// The whole V block is zeroed -- the pad rows and pad frames of every problem, as xfer_pack_in leaves them -- and problem k's
+// F x T_k entries lie at its first tile, a frame every Fp floats.
+int Batch32::v_blocks(std::vector<VBlock>* out) {
+    float* V = const_cast<float*>(a.V);
+    HIP_TRY(hipMemsetAsync(V, 0, sizeof(float) * (size_t)n_tiles * 32 * a.Fp, ctx->stream));
+    out->resize(B);
+    for (int k = 0; k < B; ++k) (*out)[k] = VBlock{V + (size_t)prob[k].tile0 * 32 * a.Fp, (int64_t)a.Fp};
+    return SNMF_OK;
+}
+
+int Batch32::v_written() {  // the floor k_pack applies on the way in (:169), one launch over every problem
+    if (!p.floor_v) return SNMF_OK;
+    int maxT = 1;
+    for (const BProb& q : prob) maxT = std::max(maxT, q.T);
+    hipLaunchKernelGGL(k_bfloor_v, dim3(std::min(1024, grid_for((size_t)maxT * a.Fp)), B), dim3(256), 0, ctx->stream, a, const_cast<float*>(a.V));
+    HIP_TRY(hipGetLastError());
+    return SNMF_OK;
+}
+
+int Batch32::draw_h0(const uint64_t* seed, const uint8_t* draw) {
+    if (!seed || !draw) return fail(SNMF_ERR_INVALID, "draw_h0: NULL argument");
+    uint64_t* d_seed = nullptr;
+    uint8_t* d_draw = nullptr;
+    SN_TRY(dalloc(&d_seed, (size_t)B));
+    blocks.push_back(d_seed);
+    SN_TRY(dalloc(&d_draw, (size_t)B));
+    blocks.push_back(d_draw);
+    hipStream_t st = ctx->stream;
+    HIP_TRY(hipMemcpyAsync(d_seed, seed, sizeof(uint64_t) * (size_t)B, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_draw, draw, (size_t)B, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));  // (the caller's arrays may go)
+    int max_tiles = 1;
+    for (const BProb& q : prob) max_tiles = std::max(max_tiles, q.n_tiles);
+    cur = 0;
+    hipLaunchKernelGGL(k_brand_h, dim3(std::min(1024, grid_for((size_t)max_tiles * 32 * a.rp)), B), dim3(256), 0, st, a, (const uint64_t*)d_seed,
+                       (const uint8_t*)d_draw);
+    HIP_TRY(hipGetLastError());
+    for (int k = 0; k < B; ++k)
+        if (draw[k]) SN_TRY(scale_h0(k));
     return SNMF_OK;
 }
 
@@ -467,7 +513,8 @@ extern "C" int snmf_mdi_batch_fp64(snmf_ctx* ctx, const snmf_params* p, int32_t 
 }
 
 // run_basis_DNMF for a batch: dnmf_batch of snmf_batch_host.h on three engines of the entry's kind
-static snmf_batch* make32() { return new Batch32(); }
+snmf_batch* batch32_new() { return new Batch32(); }
+static snmf_batch* make32() { return batch32_new(); }
 static snmf_batch* make64() { return batch64_new(); }
 extern "C" int snmf_run_basis_dnmf_batch_f64(snmf_ctx* ctx, const snmf_params* p, int32_t R_x, int32_t R_d, int32_t n_problems,
                                              const int32_t* T, const double* const* Y, const double* const* X, const double* const* D,

@@ -66,6 +66,10 @@ struct Batch64 final : snmf_batch {
         return load_t(k, V, ldV, W0, H0, M, ldM);
     }
     int take_h0(snmf_batch& src, int row0) override;
+    size_t v_elem() const override { return sizeof(double); }
+    int v_blocks(std::vector<VBlock>* out) override;
+    int v_written() override;
+    int draw_h0(const uint64_t* seed, const uint8_t* draw) override;
     int fetch_v_mdi(int k, double* V_mdi, int64_t ld) override;
     int iterate(int it) override;
     int close_run() override { return SNMF_OK; }  // (the objective and the stop test of an iteration run inside it)
@@ -345,7 +349,8 @@ int Batch64::load_t(int k, const TT* V, int64_t ldV, const TT* W0, const TT* H0,
     double *dV = a.V + q.fr0 * F, *dH = a.H + q.fr0 * r, *dW = a.W + (long long)k * F * r, *dwn = a.wn + (long long)k * r;
     hipStream_t st = ctx->stream;
     // (tight on the device; fp32 arrays are widened on the way in)
-    SN_TRY((xfer_pack_in<TT, double>(ctx, V, ldV, F, T, dV, F, T, false)));
+    if (!V && masked) return fail(SNMF_ERR_UNSUPPORTED, "a missing-data batch takes its V from the host");
+    if (V) SN_TRY((xfer_pack_in<TT, double>(ctx, V, ldV, F, T, dV, F, T, false)));
     if (masked) SN_TRY((xfer_pack_in<TT, double>(ctx, M, ldM, F, T, Mblk + q.fr0 * F, F, T, false)));
     if (H0) SN_TRY((xfer_pack_in<TT, double>(ctx, H0, r, r, T, dH, r, T, false)));
     SN_TRY((xfer_pack_in<TT, double>(ctx, W0, F, F, r, dW, F, r, false)));
@@ -356,7 +361,7 @@ int Batch64::load_t(int k, const TT* V, int64_t ldV, const TT* W0, const TT* H0,
     if (masked) {  // src/snmf_mdi.m:175, the masked start (it floors: floor_v has no meaning here)
         hipLaunchKernelGGL(k_s64_mdi_start, dim3(grid64(nFT)), dim3(256), 0, st, dV, (const double*)(Mblk + q.fr0 * F), nFT);
         HIP_TRY(hipGetLastError());
-    } else if (p.floor_v) {
+    } else if (p.floor_v && V) {  // (a V written on the device is floored by v_written)
         hipLaunchKernelGGL(k_s64_floor, dim3(grid64(nFT)), dim3(256), 0, st, dV, nFT);
         HIP_TRY(hipGetLastError());
     }
@@ -385,6 +390,52 @@ int Batch64::take_h0(snmf_batch& src_, int row0) {
     hipLaunchKernelGGL(k_b64_take_h, dim3(elem_grid(this, a.r), B), dim3(256), 0, ctx->stream, a, (const double*)src->a.H, src->a.r, row0);
     HIP_TRY(hipGetLastError());
     for (int k = 0; k < B; ++k) SN_TRY(scale_h0(k));
+    return SNMF_OK;
+}
+
+// The layout is tight: problem k's F x T_k matrix at its frame offset, nothing around it to prepare.
+int Batch64::v_blocks(std::vector<VBlock>* out) {
+    if (masked) return fail(SNMF_ERR_UNSUPPORTED, "a missing-data batch takes its V from the host");
+    out->resize(B);
+    for (int k = 0; k < B; ++k) (*out)[k] = VBlock{a.V + prob[k].fr0 * a.F, (int64_t)a.F};
+    return SNMF_OK;
+}
+
+int Batch64::v_written() {  // the floor load() applies (:169): element-wise, so one launch over the block of every problem
+    if (!p.floor_v) return SNMF_OK;
+    const long long n = (long long)a.F * sumT;
+    hipLaunchKernelGGL(k_s64_floor, dim3(grid64(n)), dim3(256), 0, ctx->stream, a.V, n);
+    HIP_TRY(hipGetLastError());
+    return SNMF_OK;
+}
+
+int Batch64::draw_h0(const uint64_t* seed, const uint8_t* draw) {
+    if (!seed || !draw) return fail(SNMF_ERR_INVALID, "draw_h0: NULL argument");
+    struct Tmp {  // (a table of this call alone: the device block is carved once, when the batch is made)
+        void* q = nullptr;
+        ~Tmp() {
+            if (q) hipFree(q);
+        }
+    } tmp;
+    const size_t nB = (size_t)B;
+    {
+        hipError_t e = hipMalloc(&tmp.q, nB * 9);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            tmp.q = nullptr;
+            return fail(SNMF_ERR_NOMEM, "hipMalloc(%zu bytes): %s", nB * 9, hipGetErrorString(e));
+        }
+    }
+    uint64_t* d_seed = (uint64_t*)tmp.q;
+    uint8_t* d_draw = (uint8_t*)tmp.q + nB * 8;
+    hipStream_t st = ctx->stream;
+    HIP_TRY(hipMemcpyAsync(d_seed, seed, 8 * nB, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_draw, draw, nB, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_b64_rand_h, dim3(elem_grid(this, (a.r + 3) / 4), B), dim3(256), 0, st, a, (const uint64_t*)d_seed, (const uint8_t*)d_draw);
+    HIP_TRY(hipGetLastError());
+    for (int k = 0; k < B; ++k)
+        if (draw[k]) SN_TRY(scale_h0(k));
+    HIP_TRY(hipStreamSynchronize(st));  // (the table is freed on return)
     return SNMF_OK;
 }
 

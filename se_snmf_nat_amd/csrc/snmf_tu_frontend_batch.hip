@@ -1,0 +1,353 @@
+// snmf_tu_frontend_batch.hip -- the front-end grouped over the signals of a batch (the kernels of snmf_frontend_batch.h) and the
+// two callers that need it:
+//
+//   snmf_stft_features_batch_f32 / _fp64             TF_mag (or TF_Mel) of n signals, tight host arrays in and out
+//   snmf_run_basis_dnmf_audio_batch_f64 / _fp64      run_basis_DNMF.m:1-55 (and its Mel twin) for n pairs of WAVEFORMS
+//
+// The DNMF entries are dnmf_batch_run of snmf_batch_host.h -- the three resident batches of snmf_run_basis_dnmf_batch_* -- with V
+// formed on the device: the truncated waveforms of every problem go up as ONE slab through the context's transfer pipeline
+// (x_0 .. x_{n-1}, d_0 .. d_{n-1}), one launch forms y = x + d behind them, and for each of the three phases the features of all
+// n signals are written by two to three launches straight into the blocks the phase's engine hands out.  A call launches the
+// front-end 1 + 3 * (1 + [Splice > 0] + [mel]) times, whatever n.  Only the samples, B and a given H0 cross to the device.
+// A translation unit of its own: nothing of the single front-ends or of the engines is touched.
+#include "snmf_internal.h"
+#include "snmf_frontend_batch.h"
+#include "snmf_batch_host.h"
+
+namespace {
+
+constexpr int kMaxSignals = 65535;        // a launch grid's second dimension: the element-wise passes put the signal there
+constexpr long long kMaxFrames = 0x7fffffffLL;  // a launch grid's first dimension: k_stft*_grp has a workgroup per frame
+constexpr int kElemGrid = 1024;           // workgroups per signal of an element-wise pass (grid-stride beyond)
+
+// every device block of one call; freed on every way out (a failed allocation leaks nothing)
+struct DevMem {
+    std::vector<void*> ptrs;
+    hipStream_t st = nullptr;
+    ~DevMem() {
+        if (st) hipStreamSynchronize(st);
+        for (void* q : ptrs) hipFree(q);
+    }
+    template <typename T>
+    int get(T** p, size_t n) {
+        *p = nullptr;
+        const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
+        hipError_t e = hipMalloc((void**)p, bytes);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            *p = nullptr;
+            return fail(SNMF_ERR_NOMEM, "hipMalloc(%zu bytes): %s", bytes, hipGetErrorString(e));
+        }
+        ptrs.push_back(*p);
+        return SNMF_OK;
+    }
+};
+
+template <typename S>
+struct Types;
+template <>
+struct Types<float> {
+    using C2 = float2;
+    using Args = StftGrpArgs;
+    static C2 make(double re, double im) { return make_float2((float)re, (float)im); }
+};
+template <>
+struct Types<double> {
+    using C2 = double2;
+    using Args = Stft64GrpArgs;
+    static C2 make(double re, double im) { return make_double2(re, im); }
+};
+
+template <int LOGN>
+int launch_stft(snmf_ctx* ctx, unsigned frames, const StftGrpArgs& a) {
+    hipLaunchKernelGGL(k_stft_grp<LOGN>, dim3(frames), dim3(256), 0, ctx->stream, a);
+    HIP_TRY(hipGetLastError());
+    return SNMF_OK;
+}
+template <int LOGN>
+int launch_stft(snmf_ctx* ctx, unsigned frames, const Stft64GrpArgs& a) {
+    const size_t lds = (size_t)2 * (1 << LOGN) * sizeof(double2);
+    SN_TRY(ensure_dyn_lds(ctx->device, (const void*)k_stft64_grp<LOGN>, lds));
+    hipLaunchKernelGGL(k_stft64_grp<LOGN>, dim3(frames), dim3(256), lds, ctx->stream, a);
+    HIP_TRY(hipGetLastError());
+    return SNMF_OK;
+}
+
+// The grouped front-end of one call in the sample type S: the sample slab, the window, twiddles and Mel table (as the single
+// front-end of that type makes them), the scratch of one run and the tables of every run.
+template <typename S>
+struct FeBatch {
+    using C2 = typename Types<S>::C2;
+    snmf_ctx* ctx = nullptr;
+    snmf_stft_params sp{};
+    int N = 0, nb = 0, Ks = 1, M = 0;  // FFT length, bins, spliced blocks, Mel channels (0: none)
+    int64_t cap_frames = 0;
+    int cap_sig = 0, cap_runs = 0, runs = 0;
+    DevMem mem;
+    S *slab = nullptr, *win = nullptr, *mel = nullptr, *tmp = nullptr, *scr = nullptr;
+    C2* tw = nullptr;
+    FeSig* tab = nullptr;
+    std::vector<S> h_win, h_mel;  // (sources of asynchronous copies: they live as long as the device blocks)
+    std::vector<C2> h_tw;
+    std::vector<FeSig> h_tab;
+    bool opened = false;
+
+    int rows_dft() const { return Ks * nb; }
+
+    // slab_elems samples; every run forms at most max_frames frames of at most max_sig signals.  With a Mel table the DFT-row
+    // scratch is one run's: the runs of a call use it in turn.
+    int open(snmf_ctx* c, const snmf_stft_params* sp_in, const S* mel_host, int mel_M, int64_t slab_elems, int64_t max_frames, int max_sig,
+             int n_runs) {
+        ctx = c;
+        sp = *sp_in;
+        N = sp.fftlength, nb = N / 2 + 1, Ks = 2 * sp.splice + 1, M = mel_host ? mel_M : 0;
+        cap_frames = max_frames, cap_sig = max_sig, cap_runs = n_runs;
+        mem.st = ctx->stream;
+        hipStream_t st = ctx->stream;
+        h_win.resize(sp.framelength);
+        for (int i = 0; i < sp.framelength; ++i) h_win[i] = (S)sp.window[i];
+        h_tw.resize(N / 2);
+        for (int q = 0; q < N / 2; ++q) {
+            const double ang = -2.0 * M_PI * (double)q / (double)N;
+            h_tw[q] = Types<S>::make(cos(ang), sin(ang));
+        }
+        SN_TRY(mem.get(&slab, (size_t)slab_elems));
+        SN_TRY(mem.get(&win, h_win.size()));
+        SN_TRY(mem.get(&tw, h_tw.size()));
+        if (sp.splice > 0) SN_TRY(mem.get(&tmp, (size_t)nb * (size_t)max_frames));
+        if (M) {
+            SN_TRY(mem.get(&scr, (size_t)rows_dft() * (size_t)max_frames));
+            h_mel.resize((size_t)M * nb);
+            if (sizeof(S) == 4) std::copy(mel_host, mel_host + h_mel.size(), h_mel.begin());  // k_mel reads the ABI's row-major M x n
+            else                                                                                 // k_mel64 reads it transposed
+                for (int m = 0; m < M; ++m)
+                    for (int f = 0; f < nb; ++f) h_mel[(size_t)f * M + m] = mel_host[(size_t)m * nb + f];
+            SN_TRY(mem.get(&mel, h_mel.size()));
+            HIP_TRY(hipMemcpyAsync(mel, h_mel.data(), h_mel.size() * sizeof(S), hipMemcpyHostToDevice, st));
+        }
+        SN_TRY(mem.get(&tab, (size_t)3 * max_sig * n_runs));
+        h_tab.resize((size_t)3 * max_sig * n_runs);
+        HIP_TRY(hipMemcpyAsync(win, h_win.data(), h_win.size() * sizeof(S), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(tw, h_tw.data(), h_tw.size() * sizeof(C2), hipMemcpyHostToDevice, st));
+        opened = true;
+        return SNMF_OK;
+    }
+
+    // features of n signals: signal k starts at sample s0[k] of the slab, has T[k] >= 1 frames and goes to dst[k]
+    int run(int n, const int64_t* s0, const int32_t* T, const snmf_batch::VBlock* dst) {
+        if (runs >= cap_runs || n > cap_sig || n < 1) return fail(SNMF_ERR_INTERNAL, "grouped front-end: run %d of %d with %d signals", runs, cap_runs, n);
+        hipStream_t st = ctx->stream;
+        const int S_ = sp.splice;
+        FeSig* h = h_tab.data() + (size_t)3 * cap_sig * runs;
+        FeSig* d = tab + (size_t)3 * cap_sig * runs;
+        FeSig *h_st = h, *h_sp = h + cap_sig, *h_ml = h + 2 * (size_t)cap_sig;
+        int64_t f0 = 0;
+        int maxT = 1;
+        for (int k = 0; k < n; ++k) {
+            const int64_t Tk = T[k];
+            maxT = std::max(maxT, T[k]);
+            S* out = (S*)dst[k].V;
+            S* t_k = tmp ? tmp + (size_t)nb * f0 : nullptr;
+            S* s_k = scr ? scr + (size_t)rows_dft() * f0 : nullptr;
+            // the STFT writes the unspliced magnitudes (a splicing pass follows), the DFT-row scratch (the Mel pass follows) or the result
+            FeSig a{};
+            a.s0 = s0[k], a.f0 = f0, a.T = T[k];
+            if (S_ > 0) a.dst = t_k, a.ld_dst = nb;
+            else if (M) a.dst = s_k, a.ld_dst = rows_dft();
+            else a.dst = out, a.ld_dst = dst[k].ld;
+            h_st[k] = a;
+            FeSig b{};
+            b.T = T[k], b.src = t_k, b.ld_src = nb;
+            if (M) b.dst = s_k, b.ld_dst = rows_dft();
+            else b.dst = out, b.ld_dst = dst[k].ld;
+            h_sp[k] = b;
+            FeSig m{};
+            m.T = T[k], m.src = s_k, m.ld_src = rows_dft(), m.dst = out, m.ld_dst = dst[k].ld;
+            h_ml[k] = m;
+            f0 += Tk;
+        }
+        if (f0 > cap_frames || f0 > kMaxFrames) return fail(SNMF_ERR_INTERNAL, "grouped front-end: %lld frames in a run sized for %lld", (long long)f0, (long long)cap_frames);
+        HIP_TRY(hipMemcpyAsync(d, h, sizeof(FeSig) * (size_t)3 * cap_sig, hipMemcpyHostToDevice, st));
+        ++runs;
+        typename Types<S>::Args a{};
+        a.slab = slab, a.sig = d, a.n_sig = n;
+        a.sz = sp.framelength, a.shift = sp.frameshift, a.dcbin = sp.dcbin;
+        a.preemph = (S)sp.preemph;
+        a.win = win, a.tw = tw;
+        a.powv = (S)sp.pow;
+        a.floorv = S_ == 0 ? (S)sp.nonzerofloor : (S)0;
+        const unsigned frames = (unsigned)f0;
+        switch (N) {
+            case 64: SN_TRY(launch_stft<6>(ctx, frames, a)); break;
+            case 128: SN_TRY(launch_stft<7>(ctx, frames, a)); break;
+            case 256: SN_TRY(launch_stft<8>(ctx, frames, a)); break;
+            case 512: SN_TRY(launch_stft<9>(ctx, frames, a)); break;
+            case 1024: SN_TRY(launch_stft<10>(ctx, frames, a)); break;
+            case 2048: SN_TRY(launch_stft<11>(ctx, frames, a)); break;
+            default: SN_TRY(launch_stft<12>(ctx, frames, a)); break;
+        }
+        auto grid = [&](int rows) { return dim3((unsigned)std::max<long long>(1, std::min<long long>(((long long)rows * maxT + 255) / 256, kElemGrid)), (unsigned)n); };
+        if (S_ > 0) {
+            hipLaunchKernelGGL(k_splice_grp<S>, grid(rows_dft()), dim3(256), 0, st, (const FeSig*)(d + cap_sig), nb, S_, (S)sp.nonzerofloor);
+            HIP_TRY(hipGetLastError());
+        }
+        if (M) {
+            hipLaunchKernelGGL(k_mel_grp<S>, grid(Ks * M), dim3(256), 0, st, (const FeSig*)(d + 2 * (size_t)cap_sig), (const S*)mel, M, nb, Ks);
+            HIP_TRY(hipGetLastError());
+        }
+        return SNMF_OK;
+    }
+};
+
+int check_batch_size(const char* entry, int32_t n, const char* what) {
+    if (n < 1) return fail(SNMF_ERR_INVALID, "%s: %s must be at least 1 (got %d)", entry, what, n);
+    if (n > kMaxSignals) return fail(SNMF_ERR_UNSUPPORTED, "%s: %d is above the limit of %d (a launch grid's second dimension)", entry, n, kMaxSignals);
+    return SNMF_OK;
+}
+
+// ---- TF_mag / TF_Mel of n signals ----------------------------------------------------------------------------------------------
+template <typename S>
+int features_batch(const char* entry, snmf_ctx* ctx, const snmf_stft_params* sp, int32_t n, const S* const* samples, const int64_t* n_samples,
+                   const S* mel, int32_t mel_M, S* const* V_out, int32_t* n_frames_out) {
+    if (!ctx || !samples || !n_samples || !V_out) return fail(SNMF_ERR_INVALID, "%s: NULL argument", entry);
+    SN_TRY(check_batch_size(entry, n, "n_signals"));
+    SN_TRY(validate_stft(sp));
+    if (mel && mel_M < 1) return fail(SNMF_ERR_INVALID, "%s: mel_M must be positive", entry);
+    const int nb = sp->fftlength / 2 + 1, Ks = 2 * sp->splice + 1;
+    const int64_t rows = mel ? (int64_t)Ks * mel_M : (int64_t)Ks * nb;
+    // the signals that have a frame: the others report 0 frames and nothing of theirs is read or written
+    std::vector<int> who;
+    std::vector<int32_t> T;
+    std::vector<int64_t> len(n, 0), s0;
+    int64_t sumT = 0, sumL = 0;
+    for (int k = 0; k < n; ++k) {
+        if (n_samples[k] < 0) return fail(SNMF_ERR_INVALID, "%s: signal %d has a negative length", entry, k);
+        const int64_t Tk = snmf_stft_num_frames(sp, n_samples[k]);
+        if (Tk > kMaxFrames) return fail(SNMF_ERR_UNSUPPORTED, "%s: signal %d has %lld frames", entry, k, (long long)Tk);
+        if (Tk <= 0) continue;
+        if (!samples[k] || !V_out[k]) return fail(SNMF_ERR_INVALID, "%s: an array of signal %d is NULL", entry, k);
+        who.push_back(k);
+        T.push_back((int32_t)Tk);
+        s0.push_back(sumL);
+        len[k] = n_samples[k];
+        sumT += Tk;
+        sumL += n_samples[k];
+    }
+    if (sumT > kMaxFrames) return fail(SNMF_ERR_UNSUPPORTED, "%s: %lld frames are above the launch grid's limit", entry, (long long)sumT);
+    if (rows > 0x7fffffffLL) return fail(SNMF_ERR_UNSUPPORTED, "%s: %lld feature rows", entry, (long long)rows);
+    if (n_frames_out) {
+        for (int k = 0; k < n; ++k) n_frames_out[k] = 0;
+        for (size_t j = 0; j < who.size(); ++j) n_frames_out[who[j]] = T[j];
+    }
+    if (who.empty()) return SNMF_OK;
+    (void)hipGetLastError();
+    HIP_TRY(hipSetDevice(ctx->device));
+    FeBatch<S> fe;
+    SN_TRY(fe.open(ctx, sp, mel, mel_M, sumL, sumT, (int)who.size(), 1));
+    SN_TRY(xfer_gather_in<S>(ctx, n, samples, len.data(), fe.slab));
+    S* out = nullptr;
+    SN_TRY(fe.mem.get(&out, (size_t)rows * (size_t)sumT));
+    std::vector<snmf_batch::VBlock> dst(who.size());
+    {
+        int64_t c0 = 0;
+        for (size_t j = 0; j < who.size(); ++j) {
+            dst[j] = snmf_batch::VBlock{out + (size_t)rows * c0, rows};
+            c0 += T[j];
+        }
+    }
+    SN_TRY(fe.run((int)who.size(), s0.data(), T.data(), dst.data()));
+    for (size_t j = 0; j < who.size(); ++j) {
+        const int k = who[j];
+        SN_TRY((xfer_unpack_out<S, S>(ctx, (const S*)dst[j].V, (int)rows, (int)rows, T[j], V_out[k], rows)));
+    }
+    return SNMF_OK;
+}
+
+// ---- run_basis_DNMF from the waveforms of n problems ------------------------------------------------------------------------------
+template <typename S>
+int dnmf_audio_batch(const char* entry, snmf_batch* (*make)(), snmf_ctx* ctx, const snmf_params* p, const snmf_stft_params* sp, int32_t R_x,
+                     int32_t R_d, int32_t n, const S* const* x, const int64_t* n_x, const S* const* d, const int64_t* n_d, const S* mel,
+                     int32_t mel_M, const double* const* B, const double* const* H0, const uint64_t* seed, double* const* B_hat,
+                     double* const* A_hat, int32_t* n_iter) {
+    if (!ctx || !p || !x || !n_x || !d || !n_d || !B || !B_hat) return fail(SNMF_ERR_INVALID, "%s: NULL argument", entry);
+    SN_TRY(check_batch_size(entry, n, "n_problems"));
+    SN_TRY(validate_stft(sp));
+    if (mel && mel_M < 1) return fail(SNMF_ERR_INVALID, "%s: mel_M must be positive", entry);
+    const int nb = sp->fftlength / 2 + 1, Ks = 2 * sp->splice + 1;
+    const int64_t F = mel ? (int64_t)Ks * mel_M : (int64_t)Ks * nb;
+    std::vector<int32_t> T(n);
+    std::vector<int64_t> len(2 * (size_t)n), off(n);
+    std::vector<const S*> src(2 * (size_t)n);
+    int64_t sumL = 0, sumT = 0;
+    for (int k = 0; k < n; ++k) {
+        if (!x[k] || !d[k] || !B[k] || !B_hat[k]) return fail(SNMF_ERR_INVALID, "%s: an array of problem %d is NULL", entry, k);
+        if ((!H0 || !H0[k]) && !seed) return fail(SNMF_ERR_INVALID, "%s: problem %d has no H0 and there are no seeds", entry, k);
+        const int64_t L = std::min(n_x[k], n_d[k]);  // run_basis_DNMF.m:5-9
+        const int64_t Tk = snmf_stft_num_frames(sp, L);
+        if (Tk < 1) return fail(SNMF_ERR_INVALID, "%s: the signals of problem %d are shorter than one analysis frame", entry, k);
+        if (Tk > kMaxFrames) return fail(SNMF_ERR_UNSUPPORTED, "%s: problem %d has %lld frames", entry, k, (long long)Tk);
+        T[k] = (int32_t)Tk;
+        off[k] = sumL;
+        src[k] = x[k], src[(size_t)n + k] = d[k];
+        len[k] = len[(size_t)n + k] = L;
+        sumL += L;
+        sumT += Tk;
+    }
+    if (sumT > kMaxFrames) return fail(SNMF_ERR_UNSUPPORTED, "%s: %lld frames are above the launch grid's limit", entry, (long long)sumT);
+    if (F != p->F) return fail(SNMF_ERR_DIM, "%s: the signals give %lld feature rows, params say %d", entry, (long long)F, p->F);
+    (void)hipGetLastError();
+
+    FeBatch<S> fe;  // (declared before the engines of dnmf_batch_run: it outlives them)
+    DnmfInputs<double> in;
+    in.H0 = H0;
+    in.seed = seed;
+    in.device_v = [&](int kind, const std::vector<snmf_batch::VBlock>& blocks, size_t elem) -> int {
+        if (elem != sizeof(S) || (int)blocks.size() != n) return fail(SNMF_ERR_INTERNAL, "%s: the engine's V is not of the sample type", entry);
+        hipStream_t st = ctx->stream;
+        if (!fe.opened) {  // the slab [x | d | y], once: the engines exist, every refusal has been made
+            SN_TRY(fe.open(ctx, sp, mel, mel_M, 3 * sumL, sumT, n, 3));
+            SN_TRY(xfer_gather_in<S>(ctx, 2 * n, src.data(), len.data(), fe.slab));
+            const unsigned g = (unsigned)std::max<int64_t>(1, std::min<int64_t>((sumL + 255) / 256, 8192));
+            hipLaunchKernelGGL(k_add_grp<S>, dim3(g), dim3(256), 0, st, (const S*)fe.slab, (const S*)(fe.slab + sumL), fe.slab + 2 * sumL, sumL);  // :10
+            HIP_TRY(hipGetLastError());
+        }
+        const int64_t base = kind == 0 ? 2 * sumL : (kind == 1 ? 0 : sumL);  // y, x, d
+        std::vector<int64_t> s0(n);
+        for (int k = 0; k < n; ++k) s0[k] = base + off[k];
+        return fe.run(n, s0.data(), T.data(), blocks.data());
+    };
+    return dnmf_batch_run<double>(entry, make, ctx, p, R_x, R_d, n, T.data(), in, B, B_hat, A_hat, n_iter);
+}
+
+snmf_batch* make32() { return batch32_new(); }
+snmf_batch* make64() { return batch64_new(); }
+
+}  // namespace
+
+extern "C" int snmf_stft_features_batch_f32(snmf_ctx* ctx, const snmf_stft_params* sp, int32_t n_signals, const float* const* samples,
+                                            const int64_t* n_samples, const float* mel, int32_t mel_M, float* const* V_out,
+                                            int32_t* n_frames_out) {
+    return features_batch<float>("snmf_stft_features_batch_f32", ctx, sp, n_signals, samples, n_samples, mel, mel_M, V_out, n_frames_out);
+}
+extern "C" int snmf_stft_features_batch_fp64(snmf_ctx* ctx, const snmf_stft_params* sp, int32_t n_signals, const double* const* samples,
+                                             const int64_t* n_samples, const double* mel, int32_t mel_M, double* const* V_out,
+                                             int32_t* n_frames_out) {
+    return features_batch<double>("snmf_stft_features_batch_fp64", ctx, sp, n_signals, samples, n_samples, mel, mel_M, V_out, n_frames_out);
+}
+
+extern "C" int snmf_run_basis_dnmf_audio_batch_f64(snmf_ctx* ctx, const snmf_params* p, const snmf_stft_params* sp, int32_t R_x, int32_t R_d,
+                                                   int32_t n_problems, const float* const* x, const int64_t* n_x, const float* const* d,
+                                                   const int64_t* n_d, const float* mel, int32_t mel_M, const double* const* B,
+                                                   const double* const* H0, const uint64_t* seed, double* const* B_hat,
+                                                   double* const* A_hat, int32_t* n_iter) {
+    return dnmf_audio_batch<float>("snmf_run_basis_dnmf_audio_batch_f64", make32, ctx, p, sp, R_x, R_d, n_problems, x, n_x, d, n_d, mel, mel_M, B,
+                                   H0, seed, B_hat, A_hat, n_iter);
+}
+extern "C" int snmf_run_basis_dnmf_audio_batch_fp64(snmf_ctx* ctx, const snmf_params* p, const snmf_stft_params* sp, int32_t R_x, int32_t R_d,
+                                                    int32_t n_problems, const double* const* x, const int64_t* n_x, const double* const* d,
+                                                    const int64_t* n_d, const double* mel, int32_t mel_M, const double* const* B,
+                                                    const double* const* H0, const uint64_t* seed, double* const* B_hat,
+                                                    double* const* A_hat, int32_t* n_iter) {
+    return dnmf_audio_batch<double>("snmf_run_basis_dnmf_audio_batch_fp64", make64, ctx, p, sp, R_x, R_d, n_problems, x, n_x, d, n_d, mel, mel_M, B,
+                                    H0, seed, B_hat, A_hat, n_iter);
+}

@@ -311,6 +311,55 @@ int xfer_unpack_out(snmf_ctx* ctx, const TSrc* src, int rowsP, int rows, int col
     return SNMF_OK;
 }
 
+// n host vectors, one behind the other, into one tight device vector: the concatenation moves as chunks through the pinned bounce
+// buffers and the copy stream, like a matrix, but lands where it belongs (the types are equal: no staging, no kernel).  One
+// transfer call however many vectors there are.  The call returns when the last chunk has left the callers' arrays; the
+// context's stream waits for every chunk.
+template <typename T>
+int xfer_gather_in(snmf_ctx* ctx, int n, const T* const* src, const int64_t* len, T* dst) {
+    HostXfer* x = nullptr;
+    SN_TRY(xfer_get(ctx, &x));
+    hipStream_t st = ctx->stream;
+    const double t0 = now_s();
+    double t_host = 0.0;
+    const size_t cap = kChunkBytes / sizeof(T);  // elements per chunk
+    size_t total = 0, done = 0;
+    for (int k = 0; k < n; ++k) total += (size_t)std::max<int64_t>(len[k], 0);
+    int k = 0, i = 0;
+    size_t at = 0;  // elements of vector k already taken
+    HIP_TRY(hipStreamSynchronize(st));  // (nothing queued on the context's stream may still read or write dst when the copy stream writes it)
+    for (; done < total; ++i) {
+        const int b = i % kNB;
+        if (x->dma_pending[b]) {  // the DMA that last read pinned buffer b
+            HIP_TRY(hipEventSynchronize(x->ev_dma[b]));
+            x->dma_pending[b] = false;
+        }
+        T* pin = (T*)x->pin[b];
+        size_t fill = 0;
+        const double th = now_s();
+        while (fill < cap && k < n) {
+            const size_t have = (size_t)std::max<int64_t>(len[k], 0) - at, take = std::min(have, cap - fill);
+            if (take) host_to_pinned<T, T>(src[k], 1, 1, at, take, pin + fill);
+            fill += take;
+            at += take;
+            if (at == (size_t)std::max<int64_t>(len[k], 0)) ++k, at = 0;
+        }
+        t_host += now_s() - th;
+        HIP_TRY(hipMemcpyAsync(dst + done, pin, fill * sizeof(T), hipMemcpyHostToDevice, x->cs));
+        HIP_TRY(hipEventRecord(x->ev_dma[b], x->cs));
+        x->dma_pending[b] = true;
+        HIP_TRY(hipStreamWaitEvent(st, x->ev_dma[b], 0));
+        done += fill;
+    }
+    ctx->xs.h2d_bytes += (double)total * sizeof(T);
+    ctx->xs.h2d_wall += now_s() - t0;
+    ctx->xs.h2d_host += t_host;
+    ctx->xs.h2d_calls += 1;
+    return SNMF_OK;
+}
+template int xfer_gather_in<float>(snmf_ctx*, int, const float* const*, const int64_t*, float*);
+template int xfer_gather_in<double>(snmf_ctx*, int, const double* const*, const int64_t*, double*);
+
 // the combinations the library uses
 #define XFER_IN(TI, TD) template int xfer_pack_in<TI, TD>(snmf_ctx*, const TI*, int64_t, int, int, TD*, int, int, bool)
 XFER_IN(double, float);

@@ -1,6 +1,7 @@
 """Host mirror of the reference's feature front-end, on top of the C ABI (include/snmf.h).
 
     stft_features(s, p)       <->  src/stft_fft.m + run_basis_train.m:60-63  (TF_mag, on the GPU)
+    stft_features_batch(signals, p)  the same (and, with mel=True, the Mel projection) for a list of signals in shared launches
     mel_features(TF_mag, p)   <->  run_basis_train.m:70-78                   (Mel projection, on the GPU)
     tf_dd(TF_mag, p)          <->  src/TF_DD.m (run_basis_train.m:64-67)     (recursive average along frames, on the GPU)
     mel_matrix(...)           <->  src/mel_matrix.m   (a parameter TABLE, built on the host like the window)
@@ -72,6 +73,48 @@ def stft_features(s, p, *, ctx=None, precision="fp32"):
     n_out = C.c_int32()
     _lib.check(getattr(lib, "snmf_stft_features_" + sfx)(ctx._h, C.byref(sp), C.c_void_p(s.ctypes.data), s.size, 0,
                                                          C.c_void_p(out.ctypes.data), F, 0, C.byref(n_out)))
+    return out
+
+
+def num_frames_host(n_samples, p):
+    """snmf_stft_num_frames restated (src/stft_fft.m:15, :21, :35: a frame starts wherever 1 + i * shift < L - fftlength), for
+    callers that size their arrays and raise their errors before the library is loaded."""
+    shift, lim = int(p["frameshift"]), int(n_samples) - int(p["fftlength"]) - 1
+    if shift <= 0 or lim <= 0:
+        return 0
+    return (lim + shift - 1) // shift
+
+
+def _mel_table(p, dt):
+    """The Mel table as the C ABI takes it: row-major F_order x (fftlength/2+1)."""
+    return np.ascontiguousarray(mel_matrix(p["fs"], int(p["F_order"]), p["fftlength"], 1.0, p["fs"] / 2).T, dtype=dt)
+
+
+def stft_features_batch(signals, p, *, mel=False, precision="fp32", ctx=None):
+    """[stft_features(s, p) for s in signals] -- with mel=True [mel_features(stft_features(s, p), p) ...] -- bit for bit, from
+    ONE call (snmf_stft_features_batch_*): the samples go up as one slab and every signal's frames are formed by launches shared
+    with all the others.  Returns a list of F x T_k arrays (Fortran order; T_k = 0 for a signal shorter than one frame)."""
+    dt, sfx = _prec(precision)
+    sigs = [np.ascontiguousarray(np.asarray(s, dtype=dt).reshape(-1)) for s in signals]
+    n = len(sigs)
+    if n == 0:
+        raise SnmfError(1, "the batch is empty: signals must hold at least one waveform")
+    sp, _win = _params(p)
+    K = 2 * sp.splice + 1
+    M = int(p["F_order"]) if mel else 0
+    F = K * M if mel else K * (sp.fftlength // 2 + 1)
+    Ts = [num_frames_host(s.size, p) for s in sigs]
+    melm = _mel_table(p, dt) if mel else None
+    out = [np.zeros((F, T), dtype=dt, order="F") for T in Ts]
+    lens = np.array([s.size for s in sigs], np.int64)
+    n_out = np.zeros(n, np.int32)
+    ctx = ctx or default_context()
+    ptrs = lambda arrs: (C.c_void_p * n)(*[a.ctypes.data for a in arrs])  # noqa: E731
+    _lib.check(getattr(_lib.load(), "snmf_stft_features_batch_" + sfx)(
+        ctx._h, C.byref(sp), n, ptrs(sigs), C.c_void_p(lens.ctypes.data), C.c_void_p(melm.ctypes.data) if mel else None, M,
+        ptrs(out), C.c_void_p(n_out.ctypes.data)))
+    if [int(v) for v in n_out] != Ts:
+        raise SnmfError(9, f"the library counts {n_out.tolist()} frames, the wrapper {Ts}")
     return out
 
 

@@ -7,6 +7,8 @@ sparse_nmf solves (api.py); this module only sequences them like the reference d
     save_basis_mat(path, out)                         # R_<R>.mat with the reference's variable names
     B_hat = run_basis_DNMF(x, d, B, p)                # run_basis_DNMF.m:1      (waveforms in, like the reference)
     B_hat = run_basis_DNMF_Mel(x, d, B, p)            # run_basis_DNMF_Mel.m:1
+    [(B_hat, A_hat)] = run_basis_DNMF_batch(xs, ds, B, p)      # the same for a list of waveform pairs, solved together
+    [(B_hat, A_hat)] = run_basis_DNMF_Mel_batch(xs, ds, B, p)
 """
 from __future__ import annotations
 
@@ -124,9 +126,10 @@ def _dnmf_features(x, d, p, ctx):
     return tuple(frontend.stft_features(sig, p, ctx=ctx) for sig in (y, x, d))  # :13-34
 
 
-def _run_basis_dnmf_audio(x, d, B, p, *, ctx, mel, h0, want_a=False, precision="fp32", dtype=None):
+def _run_basis_dnmf_audio(x, d, B, p, *, ctx, mel, h0, want_a=False, precision="fp32", dtype=None, info=None):
     """ONE call across the C ABI (snmf_run_basis_dnmf_audio_f64; precision="fp64": snmf_run_basis_dnmf_audio_fp64, waveforms and
-    Mel table as float64): the waveforms go in, B_hat comes out; features, A_hat and all three V matrices stay in HBM."""
+    Mel table as float64): the waveforms go in, B_hat comes out; features, A_hat and all three V matrices stay in HBM.
+    h0: "host", "device", or the r x T array itself; info["n_iter"] receives [n1, n2, n3]."""
     f64 = precision == "fp64"
     sdt = np.float64 if f64 else np.float32
     x = np.ascontiguousarray(np.asarray(x, dtype=sdt).reshape(-1))
@@ -150,7 +153,11 @@ def _run_basis_dnmf_audio(x, d, B, p, *, ctx, mel, h0, want_a=False, precision="
         _fp64_rules(dtype, None, "the fp64 DNMF caller")
     seed = int(p.get("random_seed", 1))
     H0 = None
-    if h0 == "host":
+    if not isinstance(h0, str):
+        H0 = np.asfortranarray(h0, dtype=np.float64)
+        if H0.shape != (r, T):
+            raise SnmfError(3, f"init_h is {H0.shape}, expected ({r}, {T})")
+    elif h0 == "host":
         H0 = np.asfortranarray(np.random.RandomState(seed if seed > 0 else None).random_sample((r, T)))
     melm = np.ascontiguousarray(frontend.mel_matrix(p["fs"], M, p["fftlength"], 1.0, p["fs"] / 2).T, dtype=sdt) if mel else None
     B_hat = np.empty((F, r), order="F")
@@ -161,6 +168,8 @@ def _run_basis_dnmf_audio(x, d, B, p, *, ctx, mel, h0, want_a=False, precision="
     fn = lib.snmf_run_basis_dnmf_audio_fp64 if f64 else lib.snmf_run_basis_dnmf_audio_f64
     _lib.check(fn(ctx._h, C.byref(q), C.byref(sp), R_x, R_d, ptr(x), x.size, ptr(d), d.size, ptr(melm), M,
                   ptr(B), F, ptr(H0), seed, ptr(B_hat), F, ptr(A_hat), r, ptr(nit)))
+    if info is not None:
+        info["n_iter"] = [int(v) for v in nit]
     return (B_hat, A_hat) if want_a else B_hat
 
 
@@ -188,3 +197,98 @@ def run_basis_DNMF_Mel(x, d, B, p, *, ctx=None, h0="host", dtype=None, precision
     _check_precision(precision)
     _check_dtype(dtype)
     return _run_basis_dnmf_audio(x, d, B, p, ctx=ctx, mel=True, h0=h0, precision=precision, dtype=dtype)  # :1-95
+
+
+def _run_basis_dnmf_audio_batch(xs, ds, B, p, *, ctx, mel, h0, precision, dtype, info):
+    """ONE call across the C ABI (snmf_run_basis_dnmf_audio_batch_f64; precision="fp64": _fp64) for every waveform pair: the
+    waveforms go up as one slab, the three feature sets of all problems are formed in HBM by shared launches, and the three
+    solves are three resident batches.  Every error that needs no device is raised before the library is loaded."""
+    _check_precision(precision)
+    _check_dtype(dtype)
+    f64 = precision == "fp64"
+    sdt = np.float64 if f64 else np.float32
+    p = dict(p)
+    xs = [np.ascontiguousarray(np.asarray(x, dtype=sdt).reshape(-1)) for x in xs]
+    ds = [np.ascontiguousarray(np.asarray(d, dtype=sdt).reshape(-1)) for d in ds]
+    n = len(xs)
+    if n == 0:
+        raise SnmfError(1, "the batch is empty: xs must hold at least one waveform")
+    if len(ds) != n:
+        raise SnmfError(1, f"{n} clean and {len(ds)} noise waveforms: one of each per problem")
+    R_x, R_d = int(p["R_x"]), int(p["R_d"])
+    r = R_x + R_d
+    K = 2 * int(p.get("Splice", 0)) + 1
+    M = int(p["F_order"]) if mel else 0
+    F = K * M if mel else K * (int(p["fftlength"]) // 2 + 1)
+    Ts = [frontend.num_frames_host(min(x.size, d.size), p) for x, d in zip(xs, ds)]  # run_basis_DNMF.m:5-9
+    for k, T in enumerate(Ts):
+        if T < 1:
+            raise SnmfError(3, f"the signals of problem {k} are shorter than one analysis frame")
+    if isinstance(B, (list, tuple)):
+        if len(B) != n:
+            raise SnmfError(3, f"B is a list of {len(B)}, the batch has {n} problems")
+        Bs = [np.asfortranarray(b, dtype=np.float64) for b in B]
+    else:
+        Bs = [np.asfortranarray(B, dtype=np.float64)] * n
+    for b in Bs:
+        if b.shape != (F, r):
+            raise SnmfError(3, f"B is {b.shape}, expected ({F}, {r})")
+    seed = int(p.get("random_seed", 1))
+    H0s = seeds = None
+    if isinstance(h0, str):
+        if h0 not in ("host", "device"):
+            raise SnmfError(3, f"h0 must be 'host', 'device' or a list of {n} arrays (r x T_k each)")
+    else:
+        if not isinstance(h0, (list, tuple)) or len(h0) != n:
+            raise SnmfError(3, f"h0 must be 'host', 'device' or a list of {n} arrays (r x T_k each)")
+        H0s = [np.asfortranarray(h, dtype=np.float64) for h in h0]
+        for h, T in zip(H0s, Ts):
+            if h.shape != (r, T):
+                raise SnmfError(3, f"init_h is {h.shape}, expected ({r}, {T})")
+    beta, max_iter, conv_eps, cost_check, lam = _solver_scalars(p)
+    if f64:  # (after the reference's own errors, before any device work)
+        _fp64_rules(dtype, None, "the fp64 DNMF batch")
+    if H0s is None and h0 == "host":  # what sparse_nmf draws for solve 1 of each problem, in list order from one generator
+        rs = np.random.RandomState(seed if seed > 0 else None)
+        H0s = [np.asfortranarray(rs.random_sample((r, T))) for T in Ts]
+    if H0s is None:
+        seeds = np.array([seed + k for k in range(n)], np.uint64)
+    q = _make_params(F, 1, r, beta, max_iter, conv_eps, cost_check, True, 0, lam, None, None)
+    melm = frontend._mel_table(p, sdt) if mel else None
+    sp, _win = frontend._params(p)
+
+    lib = _lib.load()
+    ctx = ctx or default_context()
+    B_hat = [np.empty((F, r), order="F") for _ in Ts]
+    A_hat = [np.empty((r, T), order="F") for T in Ts]
+    n_iter = np.zeros(3 * n, np.int32)
+    n_x, n_d = (np.array([a.size for a in v], np.int64) for v in (xs, ds))
+    ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None  # noqa: E731
+    ptrs = lambda arrs: (C.c_void_p * n)(*[a.ctypes.data for a in arrs]) if arrs is not None else None  # noqa: E731
+    fn = lib.snmf_run_basis_dnmf_audio_batch_fp64 if f64 else lib.snmf_run_basis_dnmf_audio_batch_f64
+    _lib.check(fn(ctx._h, C.byref(q), C.byref(sp), R_x, R_d, n, ptrs(xs), ptr(n_x), ptrs(ds), ptr(n_d), ptr(melm), M, ptrs(Bs),
+                  ptrs(H0s), ptr(seeds), ptrs(B_hat), ptrs(A_hat), ptr(n_iter)))
+    if info is not None:
+        info["n_iter"] = [[int(v) for v in n_iter[3 * k:3 * k + 3]] for k in range(n)]
+        info["T"] = list(Ts)
+    return list(zip(B_hat, A_hat))
+
+
+def run_basis_DNMF_batch(xs, ds, B, p, *, ctx=None, h0="host", precision="fp32", info=None, dtype=None):
+    """[(B_hat_k, A_hat_k)] = run_basis_DNMF(x_k, d_k, B_k, p) for every pair of the two lists of waveforms, solved together
+    (snmf_run_basis_dnmf_audio_batch_*).  B: one F x (R_x + R_d) array for every problem, or a list of them; p: as for
+    run_basis_DNMF, shared.  h0: "host" = rand(r, T_k) of solve 1 drawn per problem, in list order, from one
+    RandomState(p["random_seed"]) (as run_basis_dnmf_batch); "device" = drawn on the device, problem k from
+    philox_uniform(random_seed + k, r, T_k); or a list of r x T_k arrays.
+    precision="fp32": float waveforms, fp32 features, the fp32 batch engine (F <= 513, R_x + R_d <= 200): bit for bit
+    run_basis_dnmf_batch on the features stft_features gives for y_k = float32(x_k) + float32(d_k), x_k and d_k.
+    precision="fp64": everything in double; problem k is bit for bit run_basis_DNMF(x_k, d_k, B_k, p, precision="fp64") alone
+    with the same H0 (dtype=np.float32 is then SnmfError status 1).
+    info["n_iter"] receives a list of [n1, n2, n3], info["T"] the frame counts.  Returns a list of (B_hat, A_hat)."""
+    return _run_basis_dnmf_audio_batch(xs, ds, B, p, ctx=ctx, mel=False, h0=h0, precision=precision, dtype=dtype, info=info)
+
+
+def run_basis_DNMF_Mel_batch(xs, ds, B, p, *, ctx=None, h0="host", precision="fp32", info=None, dtype=None):
+    """run_basis_DNMF_batch on the Mel projections of the three feature sets (run_basis_DNMF_Mel.m:21-69); B: the Mel exemplar
+    bases (F_order * (2 * Splice + 1) rows)."""
+    return _run_basis_dnmf_audio_batch(xs, ds, B, p, ctx=ctx, mel=True, h0=h0, precision=precision, dtype=dtype, info=info)
