@@ -892,6 +892,44 @@ int snmf_run_basis_dnmf_audio_batch_fp64(snmf_ctx* ctx, const snmf_params* p, co
                                          const double* const* H0, const uint64_t* seed, double* const* B_hat, double* const* A_hat,
                                          int32_t* n_iter);
 
+/* Added within 5.  Basis training (run_basis_train.m:58-91) for the training signals of n_problems event classes or noise types
+ * at once -- the loop l = 1:length(DB_path_list) of the reference: snmf_run_basis_train_audio_* for every signal, with the
+ * features of all signals formed by the grouped front-end and the two solves of every problem run as two resident batches
+ * ("Batched basis training").  The problems share the settings; problem k has its own signal (n_samples[k] samples),
+ * frame count T_k = snmf_stft_num_frames(sp, n_samples[k]) and exemplar columns sample_idx[k] (p->r indices, 0-based).
+ * The samples cross as one slab.  TF_mag of every signal is written straight into the DFT batch, TF_DD (alpha_eta_dd >= 0; < 0:
+ * off) runs in place there, TF_Mel is projected from there into the Mel batch, each batch gathers init_w = V(:, sample_idx) from
+ * its own, still unfloored V on the device, and both solves of a problem start from the same H0.  mel (row-major mel_M x
+ * (fftlength/2+1)) and B_Mel go together; without them only the DFT solve runs.  p->F must be (2 * splice + 1) * (fftlength/2+1)
+ * (SNMF_ERR_DIM); p->r = cluster_buff * R; p->T and the masks of p are ignored (every row and column is updated, :85-86).
+ * Every matrix is tight and column-major: B_DFT_k F x r, B_Mel_k (2 * splice + 1) * mel_M x r, H0_k, A_DFT_k, A_Mel_k r x T_k.
+ * samples, n_samples, sample_idx, B_DFT (and B_Mel): n_problems entries each.  H0: NULL, or n_problems pointers of which single
+ * ones may be NULL: such a problem starts from the Philox draw of snmf_plan_set_h_random keyed by seed[k] (seed: n_problems
+ * entries, read only there).  A_DFT, A_Mel: NULL, or pointers of which single ones may be NULL.  n_iter: NULL, or 2 per problem
+ * (the DFT and the Mel solve).  train_exemplar != 0 (:84, :93-96): nothing is solved, B_DFT_k and B_Mel_k are the gathered
+ * exemplar columns, H0, seed, A_DFT and A_Mel are not looked at and n_iter is zeroed.
+ *   _f64   the fp32 engine, named after its host type like snmf_run_basis_train_audio_f64: float samples and Mel table, fp32
+ *          features.  THE CONTRACT: B_*_k, A_*_k and the counts are bit for bit those of snmf_sparse_nmf_batch_f64 on the features
+ *          snmf_stft_features_f32 (then snmf_tf_dd_f32, then snmf_mel_features_f32 on that) give for signal k, widened to double,
+ *          with init_w their columns sample_idx[k] and init_h = H0_k or the draw.  Envelope: the fp32 batch's (F <= 513,
+ *          r <= 200), SNMF_ERR_UNSUPPORTED.
+ *   _fp64  the fp64 engine: double samples and Mel table, everything in double.  THE CONTRACT: bit for bit
+ *          snmf_run_basis_train_audio_fp64 run alone on signal k with the same H0_k, or with H0 = NULL and the same seed.
+ * Refused before the device is touched: NULL arguments, n_problems < 1, a signal shorter than one analysis frame, mel without
+ * B_Mel or the reverse, mel_M < 1 with mel, a problem without H0 when seed is NULL (SNMF_ERR_INVALID); the refusals of the single
+ * entry for sp; p->F that is not the feature rows, an index outside [0, T_k) (SNMF_ERR_DIM); a sparsity that is not
+ * SNMF_SPARSITY_SCALAR and the fp32 envelope (SNMF_ERR_UNSUPPORTED).  One-shot entries: no handle, no device list. */
+int snmf_run_basis_train_audio_batch_f64(snmf_ctx* ctx, const snmf_params* p, const snmf_stft_params* sp, double alpha_eta_dd,
+                                         const float* mel, int32_t mel_M, int32_t n_problems, const float* const* samples,
+                                         const int64_t* n_samples, const int64_t* const* sample_idx, int32_t train_exemplar,
+                                         const double* const* H0, const uint64_t* seed, double* const* B_DFT, double* const* A_DFT,
+                                         double* const* B_Mel, double* const* A_Mel, int32_t* n_iter);
+int snmf_run_basis_train_audio_batch_fp64(snmf_ctx* ctx, const snmf_params* p, const snmf_stft_params* sp, double alpha_eta_dd,
+                                          const double* mel, int32_t mel_M, int32_t n_problems, const double* const* samples,
+                                          const int64_t* n_samples, const int64_t* const* sample_idx, int32_t train_exemplar,
+                                          const double* const* H0, const uint64_t* seed, double* const* B_DFT, double* const* A_DFT,
+                                          double* const* B_Mel, double* const* A_Mel, int32_t* n_iter);
+
 /* ---- instrumentation (bench.py: HIP-event timing on the engine's own stream) ------------ */
 /* Average device time in milliseconds per launch of the named kernel family over the launches
  * recorded since snmf_ctx_timing(ctx, 1) was switched on.  Families: "hstep", "wstats",

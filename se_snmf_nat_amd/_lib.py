@@ -97,6 +97,7 @@ SYMBOLS = [
     "snmf_run_basis_dnmf_batch_f64", "snmf_run_basis_dnmf_batch_f32", "snmf_run_basis_dnmf_batch_fp64",
     "snmf_stft_features_batch_f32", "snmf_stft_features_batch_fp64",
     "snmf_run_basis_dnmf_audio_batch_f64", "snmf_run_basis_dnmf_audio_batch_fp64",
+    "snmf_run_basis_train_audio_batch_f64", "snmf_run_basis_train_audio_batch_fp64",
     "snmf_rccl_available", "snmf_rccl_get_unique_id", "snmf_rccl_comm_create", "snmf_rccl_comm_destroy", "snmf_plan_run_sharded_rccl",
 ]
 ABI_VERSION = 5  # include/snmf.h: SNMF_ABI_VERSION this binding was written against
@@ -383,6 +384,9 @@ def load():
         sig[f"snmf_stft_features_batch_{ty}"] = (C.c_int, [vp, SP, i32, vp, vp, vp, i32, vp, vp])
     for ty in ("f64", "fp64"):
         sig[f"snmf_run_basis_dnmf_audio_batch_{ty}"] = (C.c_int, [vp, PP, SP, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp])
+    # basis training for a batch of signals: the single entry's settings, then arrays of pointers and of lengths
+    for ty in ("f64", "fp64"):
+        sig[f"snmf_run_basis_train_audio_batch_{ty}"] = (C.c_int, [vp, PP, SP, dbl, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp])
     lib.snmf_abi_version.restype = C.c_int
     if lib.snmf_abi_version() != ABI_VERSION:  # a stale library must not be driven through newer prototypes
         raise ImportError(f"{path} has ABI version {lib.snmf_abi_version()}, this binding needs {ABI_VERSION}: rebuild the library")

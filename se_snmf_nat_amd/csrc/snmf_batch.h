@@ -14,6 +14,7 @@
 //   k_btake_h : one (problem, tile): the initial H of this batch from rows of the result H of another batch (the batched DNMF loop)
 //   k_bfloor_v, k_brand_h : grid (workgroups, problem): the V floor on a V that was written on the device, and an initial H drawn
 //             on the device (the batched DNMF loop from waveforms)
+//   k_btake_w : grid (workgroups, problem): the initial W of every problem from columns of its own V (batched basis training)
 //
 // Layouts: the engine's (snmf_kernels.h, StepArgs): V [Ttot][Fp], H [Ttot][rp], Wt4 / Wk4 per problem; the frames of
 // problem b start at tile prob[b].tile0, so a tile never spans two problems.  A problem's last tile is partial when T_b is
@@ -600,6 +601,23 @@ static __global__ __launch_bounds__(256) void k_btake_h(BatchArgs a, const float
         const int t = i / a.rp, k = i - t * a.rp;
         const long long fr = fr0 + t;
         H[fr * a.rp + k] = (k < a.r && t < Tl) ? S[fr * srp + row0 + k] : 0.f;
+    }
+}
+
+// grid (workgroups, problems): init_w of problem b = V_b(:, idx[b * r + k]), k < r (run_basis_train.m:82-83) -- the columns of
+// the problem's own V block, widened into the fp64 [rp][Fp] layout k_bfin's init pass reads, at W + b * stride.  idx: 0-based,
+// on the device; an index outside [0, T_b) (the host refuses it) gives a zero column, never a read outside the block.  Lanes run
+// along f, the contiguous direction on both sides.  Pad rows and pad columns are not written.
+static __global__ __launch_bounds__(256) void k_btake_w(BatchArgs a, const int64_t* __restrict__ idx, double* __restrict__ W, long long stride) {
+    const int b = blockIdx.y;
+    const BProb pb = a.prob[b];
+    const float* __restrict__ Vb = a.V + 32LL * pb.tile0 * a.Fp;
+    double* __restrict__ Wb = W + (long long)b * stride;
+    const int n = a.F * a.r;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+        const int k = i / a.F, f = i - k * a.F;
+        const long long t = idx[(long long)b * a.r + k];
+        Wb[(long long)k * a.Fp + f] = (t >= 0 && t < pb.T) ? (double)Vb[t * a.Fp + f] : 0.0;
     }
 }
 

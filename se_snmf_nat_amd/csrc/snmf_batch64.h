@@ -96,6 +96,22 @@ static __global__ __launch_bounds__(256) void k_b64_take_h(B64Args a, const doub
     }
 }
 
+// grid (workgroups, B): init_w of problem b = V_b(:, idx[b * r + k]), k < r (run_basis_train.m:82-83; k_gather64 per problem):
+// columns of the problem's own tight V block into its tight F x r W.  idx: 0-based, on the device; an index outside [0, T_b)
+// (the host refuses it) gives a zero column, never a read outside the block.
+static __global__ __launch_bounds__(256) void k_b64_take_w(B64Args a, const int64_t* __restrict__ idx) {
+    const int b = blockIdx.y;
+    const B64Prob p = a.prob[b];
+    const double* __restrict__ V = a.V + p.fr0 * a.F;
+    double* __restrict__ W = a.W + (long long)b * a.F * a.r;
+    const long long n = (long long)a.F * a.r;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        const long long k = i / a.F, f = i - k * a.F;
+        const long long t = idx[(long long)b * a.r + k];
+        W[i] = (t >= 0 && t < p.T) ? V[t * a.F + f] : 0.0;
+    }
+}
+
 // grid (workgroups, B): H0 of problem b drawn on the device: H[e] = u(e), e the element index in the tight column-major a.r x T_b
 // matrix -- k_rand64 (snmf_frontend64.h) per problem, keyed by seed[b].  draw[b] == 0: the problem's H0 came from the host.
 static __global__ __launch_bounds__(256) void k_b64_rand_h(B64Args a, const uint64_t* __restrict__ seed, const uint8_t* __restrict__ draw) {

@@ -40,9 +40,16 @@ struct snmf_batch {
     virtual int upload_sparsity(const double* sparsity) = 0;  // r entries; the caller's array may go on return
     // problem k from host arrays, and its initial scaling (src/sparse_nmf.m:157-169).  H0 == nullptr: V, W0 and the scaling of W
     // only -- the problem's H0 is still to come, for every problem at once, through take_h0 or draw_h0.  V == nullptr: W0 (and H0)
-    // only -- V of every problem is written on the device, through v_blocks / v_written
+    // only -- V of every problem is written on the device, through v_blocks / v_written.  W0 == nullptr: W0 of every problem has
+    // been taken on the device, through take_w0, and H0 is scaled by the norms that left
     virtual int load(int k, const double* V, int64_t ldV, const double* W0, const double* H0) = 0;
     virtual int load(int k, const float* V, int64_t ldV, const float* W0, const float* H0) = 0;
+    // init_w of every problem = the columns idx[k * r .. k * r + r) (0-based, host) of the problem's own V block, as it lies there
+    // when the call is made (between v_blocks and v_written: the unfloored V), gathered by one launch over all problems; then,
+    // with unit_columns, the initial scaling load() runs after its W0 upload (:157-158), so that the state is that of
+    // load(k, nullptr, ld, W0, nullptr) with the same values.  Without unit_columns the gathered columns stay as they are and
+    // fetch(k, W, nullptr) reads them (run_basis_train.m:84: the exemplars are the dictionary): such a batch does not run.
+    virtual int take_w0(const int64_t* idx, bool unit_columns = true) = 0;
     // V of every problem from device memory instead of a host pointer.  v_blocks hands out where problem k's V lies -- column t at
     // V + t * ld, F rows of v_elem() bytes -- after making everything around those entries what load() leaves there (the fp32
     // engine: zeroed pad rows and pad frames); work on the context's stream then writes every entry of every block, and v_written
@@ -351,4 +358,78 @@ int dnmf_batch(const char* entry, snmf_batch* (*make)(), snmf_ctx* ctx, const sn
     in.V[0] = Y, in.V[1] = X, in.V[2] = D;
     in.H0 = H0;
     return dnmf_batch_run<TT>(entry, make, ctx, p, R_x, R_d, n, T, in, B, B_hat, A_hat, n_iter);
+}
+
+// ---- run_basis_train.m:58-91 for a batch of training signals (include/snmf.h: snmf_run_basis_train_audio_batch_*) -----------------
+// Two engines of one kind, made by `make`, over the same frame counts, both with every row and column updated (:85-86): the DFT
+// engine (p->F rows) and, with F_mel > 0, the Mel engine (F_mel rows), r = p->r = cluster_buff * R each.  `device_v` (the grouped
+// front-end of snmf_tu_frontend_batch.hip) writes TF_mag -- TF_DD applied where asked -- of every signal into the DFT engine's V
+// blocks and TF_Mel, projected from those blocks, into the Mel engine's; both engines then gather their exemplar columns from
+// the still unfloored V (the single entry's order, snmf_tu_dnmf.hip), run their floor, take the same H0 and solve.  Nothing
+// between the sample slab and the results crosses to the host.  The driver does not ask which engine it drives.
+template <typename TT>
+struct TrainInputs {
+    // the features of every signal into `dft` and, unless it is empty, `mel`: blocks of `elem`-byte entries
+    std::function<int(const std::vector<snmf_batch::VBlock>& dft, const std::vector<snmf_batch::VBlock>& mel, size_t elem)> device_v;
+    const int64_t* idx = nullptr;    // n * p->r exemplar columns, 0-based, checked by the caller
+    bool exemplar = false;           // train_Exemplar (:84, :93-96): the exemplars are the dictionaries and nothing is solved
+    const TT* const* H0 = nullptr;   // may be nullptr, or hold nullptr entries: drawn on the device from seed[k]
+    const uint64_t* seed = nullptr;
+};
+
+// B_DFT_k F x r, B_Mel_k F_mel x r, A_*_k r x T[k], tight and column-major (A_DFT, A_Mel, or single entries of them, may be NULL);
+// n_iter: NULL or 2 per problem.  The masks of p are ignored.  Every refusal comes before the device is touched; the caller has
+// checked `in` and the pointers.
+template <typename TT>
+int train_batch_run(const char* entry, snmf_batch* (*make)(), snmf_ctx* ctx, const snmf_params* p, int32_t F_mel, int32_t n, const int32_t* T,
+                    const TrainInputs<TT>& in, TT* const* B_DFT, TT* const* A_DFT, TT* const* B_Mel, TT* const* A_Mel, int32_t* n_iter) {
+    snmf_params q = *p;
+    q.w_update_ind = q.h_update_ind = nullptr;
+    if (F_mel > 0) {  // the Mel engine's limits before the DFT engine allocates
+        std::unique_ptr<snmf_batch> probe(make());
+        probe->p = q;
+        probe->p.F = F_mel;
+        SN_TRY(probe->check_shape());
+    }
+    BatchOwner ed, em;
+    SN_TRY(batch_create(entry, make(), ctx, &q, n, T, &ed.b));
+    if (F_mel > 0) {
+        q.F = F_mel;
+        SN_TRY(batch_create(entry, make(), ctx, &q, n, T, &em.b));
+    }
+    snmf_batch* const eng[2] = {ed.b, em.b};
+    const int n_eng = em.b ? 2 : 1;
+    std::vector<snmf_batch::VBlock> vd, vm;
+    SN_TRY(ed.b->v_blocks(&vd));
+    if (em.b) SN_TRY(em.b->v_blocks(&vm));
+    SN_TRY(in.device_v(vd, vm, ed.b->v_elem()));                                      // :60-78
+    for (int j = 0; j < n_eng; ++j) SN_TRY(eng[j]->take_w0(in.idx, !in.exemplar));  // B_*_init = TF_*(:, sample_idx)   (:82-83)
+    if (in.exemplar) {
+        for (int i = 0; i < n; ++i) {
+            SN_TRY(ed.b->fetch(i, B_DFT[i], (TT*)nullptr));
+            if (em.b) SN_TRY(em.b->fetch(i, B_Mel[i], (TT*)nullptr));
+            if (n_iter) n_iter[2 * (size_t)i] = n_iter[2 * (size_t)i + 1] = 0;
+        }
+        return SNMF_OK;
+    }
+    for (int j = 0; j < n_eng; ++j) SN_TRY(eng[j]->v_written());
+    std::vector<uint8_t> draw(n, 0);
+    bool any = false;
+    for (int i = 0; i < n; ++i) any |= (draw[i] = (!in.H0 || !in.H0[i]) ? 1 : 0) != 0;
+    for (int j = 0; j < n_eng; ++j) {  // the reference re-seeds inside every sparse_nmf call: both solves of a problem start from the same H0
+        snmf_batch* e = eng[j];
+        for (int i = 0; i < n; ++i) {
+            if (!draw[i]) SN_TRY(e->load(i, (const TT*)nullptr, (int64_t)e->p.F, (const TT*)nullptr, in.H0[i]));
+            batch_mark_set(e, i);
+        }
+        if (any) SN_TRY(e->draw_h0(in.seed, draw.data()));
+    }
+    for (int j = 0; j < n_eng; ++j) SN_TRY(batch_run(eng[j], 0));  // :88, :91
+    for (int i = 0; i < n; ++i) {
+        int32_t* ni = n_iter ? n_iter + 2 * (size_t)i : nullptr;
+        SN_TRY(batch_get<TT>(ed.b, i, B_DFT[i], A_DFT ? A_DFT[i] : (TT*)nullptr, nullptr, nullptr, ni));
+        if (em.b) SN_TRY(batch_get<TT>(em.b, i, B_Mel[i], A_Mel ? A_Mel[i] : (TT*)nullptr, nullptr, nullptr, ni ? ni + 1 : nullptr));
+        else if (ni) ni[1] = 0;
+    }
+    return SNMF_OK;
 }

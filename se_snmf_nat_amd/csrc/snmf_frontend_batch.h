@@ -1,8 +1,9 @@
 // snmf_frontend_batch.h -- the spectrogram front-end GROUPED over the signals of a batch, in float and in double
-// (snmf_tu_frontend_batch.hip: snmf_stft_features_batch_*, snmf_run_basis_dnmf_audio_batch_*).
+// (snmf_tu_frontend_batch.hip: snmf_stft_features_batch_*, snmf_run_basis_dnmf_audio_batch_*, snmf_run_basis_train_audio_batch_*).
 //   src/stft_fft.m:15-37        framing, pre-emphasis, window, zero-padded FFT, |.|, DC-bin value   k_stft_grp / k_stft64_grp
 //   run_basis_train.m:60-63     splice, .^pow + nonzerofloor                                        k_splice_grp
 //   run_basis_train.m:70-78     Mel projection                                                      k_mel_grp
+//   run_basis_train.m:64-67     TF_DD, in place                                                     k_tfdd_carry_grp / _state_grp / _apply_grp
 //   run_basis_DNMF.m:10         y = x + d, over the whole sample slab                               k_add_grp
 // The single front-end (snmf_frontend.h, snmf_frontend64.h) launches per signal and per matrix: k_stft<LOGN> runs one workgroup
 // per frame of ONE signal, k_splice / k_mel one matrix.  Here one launch covers every signal of the batch, so the number of
@@ -194,6 +195,68 @@ __global__ __launch_bounds__(256) void k_mel_grp(const FeSig* __restrict__ sig, 
             for (int f = 0; f < n; ++f) s = fma(mc[(int64_t)f * M], vc[f], s);
         }
         out[(int64_t)t * e.ld_dst + row] = s;
+    }
+}
+
+// ---- TF_DD (src/TF_DD.m, run_basis_train.m:64-67) of every signal of the batch, IN PLACE on the signal's feature block (FeSig::dst,
+// ld_dst): the chunked recursion of snmf_frontend.h (float: k_tfdd_carry / _state / _apply) and snmf_frontend64.h (double:
+// k_tfdd64_*) restated operation for operation -- fp64 state and coefficients, chunks of 256 frames, the same expressions in the
+// same order -- so every column is bit for bit what snmf_tf_dd_f32 / _fp64 give for that signal alone.  The two differ where
+// the single kernels differ: in double the recursion starts at column 2 from the state X(:,1), which is stored as it is; in
+// float column 1 goes through the recursion from the state X(:,1) like every other.
+// The table has one FeSig per signal with f0 = the CHUNKS of the signals before it, so fe_find maps a workgroup of the carry and
+// apply passes to (signal, chunk); the state pass has the signal in blockIdx.y.  carry: [chunks of the batch][F] doubles.
+constexpr int kDdGrpChunk = 256;  // kDdChunk and kDd64Chunk: the chunk length is part of the bits
+template <typename T>
+__device__ __forceinline__ int tfdd_grp_first(int j) {  // first column a chunk's recursion steps over
+    return (sizeof(T) == 8 && j == 0) ? 1 : j * kDdGrpChunk;
+}
+// grid (chunks of the batch, ceil(F / 256)): every (signal, chunk, row) runs its chunk from state 0 -> its carry
+template <typename T>
+__global__ __launch_bounds__(256) void k_tfdd_carry_grp(const FeSig* __restrict__ sig, int n_sig, int F, double a, double* __restrict__ carry) {
+    const FeSig e = fe_find(sig, n_sig, (int64_t)blockIdx.x);
+    const int f = blockIdx.y * 256 + threadIdx.x, j = (int)((int64_t)blockIdx.x - e.f0);
+    if (f >= F || (int64_t)j * kDdGrpChunk >= e.T) return;
+    const T* X = (const T*)e.dst;
+    const int64_t ld = e.ld_dst;
+    const int t1 = min(e.T, (j + 1) * kDdGrpChunk);
+    double s = 0.0;
+    for (int t = tfdd_grp_first<T>(j); t < t1; ++t) s = a * s + (1.0 - a) * (double)X[(int64_t)t * ld + f];
+    carry[(int64_t)blockIdx.x * F + f] = s;
+}
+// grid (ceil(F / 256), signals): per row, the states at the chunk starts, S_{j+1} = a^len_j S_j + c_j, sequential over the
+// signal's chunks; carry in, start states out
+template <typename T>
+__global__ __launch_bounds__(256) void k_tfdd_state_grp(const FeSig* __restrict__ sig, int F, double a, double* __restrict__ carry) {
+    const FeSig e = sig[blockIdx.y];
+    const int f = blockIdx.x * 256 + threadIdx.x;
+    if (f >= F) return;
+    const T* X = (const T*)e.dst;
+    double* c = carry + e.f0 * F;
+    const int nch = (e.T + kDdGrpChunk - 1) / kDdGrpChunk;
+    double s = (double)X[f];  // float: the state "before" column 1 (a x + (1-a) x); double: the state after column 1
+    for (int j = 0; j < nch; ++j) {
+        const int len = min(e.T, (j + 1) * kDdGrpChunk) - tfdd_grp_first<T>(j);
+        const double cj = c[(int64_t)j * F + f];
+        c[(int64_t)j * F + f] = s;
+        s = pow(a, (double)len) * s + cj;
+    }
+}
+// grid as the carry pass: every (signal, chunk, row) re-runs its chunk from the true start state and writes the result over its
+// input (every element is read before it is written, by this thread)
+template <typename T>
+__global__ __launch_bounds__(256) void k_tfdd_apply_grp(const FeSig* __restrict__ sig, int n_sig, int F, double a, const double* __restrict__ state) {
+    const FeSig e = fe_find(sig, n_sig, (int64_t)blockIdx.x);
+    const int f = blockIdx.y * 256 + threadIdx.x, j = (int)((int64_t)blockIdx.x - e.f0);
+    if (f >= F || (int64_t)j * kDdGrpChunk >= e.T) return;
+    T* X = (T*)e.dst;
+    const int64_t ld = e.ld_dst;
+    const int t1 = min(e.T, (j + 1) * kDdGrpChunk);
+    double s = state[(int64_t)blockIdx.x * F + f];
+    if (sizeof(T) == 8 && j == 0) X[f] = (T)s;  // X_DD(:,1) = X(:,1)
+    for (int t = tfdd_grp_first<T>(j); t < t1; ++t) {
+        s = a * s + (1.0 - a) * (double)X[(int64_t)t * ld + f];
+        X[(int64_t)t * ld + f] = (T)s;
     }
 }
 

@@ -39,6 +39,7 @@ struct Batch32 final : snmf_batch {
     int load(int k, const double* V, int64_t ldV, const double* W0, const double* H0) override { return load_t(k, V, ldV, W0, H0); }
     int load(int k, const float* V, int64_t ldV, const float* W0, const float* H0) override { return load_t(k, V, ldV, W0, H0); }
     int take_h0(snmf_batch& src, int row0) override;
+    int take_w0(const int64_t* idx, bool unit_columns) override;
     size_t v_elem() const override { return sizeof(float); }
     int v_blocks(std::vector<VBlock>* out) override;
     int v_written() override;
@@ -221,16 +222,19 @@ int Batch32::upload_sparsity(const double* sparsity) {
     return SNMF_OK;
 }
 
+// wraw: where the init pass reads the initial W (default: the upload buffer of load())
 template <int BM>
-int launch_fin(Batch32* b, int b0, int nb, int init, int it, int fold, int cur) {
-    hipLaunchKernelGGL((k_bfin<BM>), dim3(b->a.r, nb), dim3(256), 0, b->ctx->stream, b->a, b0, init, it, fold, cur);
+int launch_fin(Batch32* b, int b0, int nb, int init, int it, int fold, int cur, const double* wraw) {
+    BatchArgs q = b->a;
+    if (wraw) q.Wraw = wraw;
+    hipLaunchKernelGGL((k_bfin<BM>), dim3(b->a.r, nb), dim3(256), 0, b->ctx->stream, q, b0, init, it, fold, cur);
     HIP_TRY(hipGetLastError());
     return SNMF_OK;
 }
-int launch_fin_bm(Batch32* b, int b0, int nb, int init, int it, int fold, int cur) {
-    return b->bm == BM_KL ? launch_fin<BM_KL>(b, b0, nb, init, it, fold, cur)
-                          : (b->bm == BM_EUC ? launch_fin<BM_EUC>(b, b0, nb, init, it, fold, cur)
-                                             : launch_fin<BM_GEN>(b, b0, nb, init, it, fold, cur));
+int launch_fin_bm(Batch32* b, int b0, int nb, int init, int it, int fold, int cur, const double* wraw = nullptr) {
+    return b->bm == BM_KL ? launch_fin<BM_KL>(b, b0, nb, init, it, fold, cur, wraw)
+                          : (b->bm == BM_EUC ? launch_fin<BM_EUC>(b, b0, nb, init, it, fold, cur, wraw)
+                                             : launch_fin<BM_GEN>(b, b0, nb, init, it, fold, cur, wraw));
 }
 
 template <typename TT>
@@ -240,8 +244,10 @@ int Batch32::load_t(int k, const TT* V, int64_t ldV, const TT* W0, const TT* H0)
     const int Tp = q.n_tiles * 32;
     if (V) SN_TRY((xfer_pack_in<TT, float>(ctx, V, ldV, a.F, q.T, const_cast<float*>(a.V) + fr0 * a.Fp, a.Fp, Tp, p.floor_v != 0)));
     if (H0) SN_TRY((xfer_pack_in<TT, float>(ctx, H0, a.r, a.r, q.T, a.H[0] + fr0 * a.rp, a.rp, Tp, false)));
-    SN_TRY((xfer_pack_in<TT, double>(ctx, W0, a.F, a.F, a.r, Wraw, a.Fp, a.rp, false)));
-    SN_TRY(launch_fin_bm(this, k, 1, 1, 0, 0, 0));  // :157-158
+    if (W0) {
+        SN_TRY((xfer_pack_in<TT, double>(ctx, W0, a.F, a.F, a.r, Wraw, a.Fp, a.rp, false)));
+        SN_TRY(launch_fin_bm(this, k, 1, 1, 0, 0, 0));  // :157-158
+    }
     return H0 ? scale_h0(k) : SNMF_OK;
 }
 
@@ -266,6 +272,25 @@ int Batch32::take_h0(snmf_batch& src_, int row0) {
                        (const BState*)src->a.st, src->cur, src->a.rp, row0);
     HIP_TRY(hipGetLastError());
     for (int k = 0; k < B; ++k) SN_TRY(scale_h0(k));
+    return SNMF_OK;
+}
+
+// One launch over every (problem, element of F x r) gathers the columns, widened, straight into each problem's fp64 master copy,
+// which has the layout of load()'s upload buffer.  The initial scaling is then load()'s launch per problem, reading its column
+// where it writes it: a workgroup of k_bfin holds its whole column in registers before it stores the first entry.
+int Batch32::take_w0(const int64_t* idx, bool unit_columns) {
+    if (!idx) return fail(SNMF_ERR_INVALID, "take_w0: NULL argument");
+    int64_t* d_idx = nullptr;
+    SN_TRY(dalloc(&d_idx, (size_t)B * a.r));
+    blocks.push_back(d_idx);
+    hipStream_t st = ctx->stream;
+    HIP_TRY(hipMemcpyAsync(d_idx, idx, sizeof(int64_t) * (size_t)B * a.r, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));  // (the caller's array may go)
+    hipLaunchKernelGGL(k_btake_w, dim3(std::min(1024, grid_for((size_t)a.F * a.r)), B), dim3(256), 0, st, a, (const int64_t*)d_idx, a.Wc,
+                       a.sWc);
+    HIP_TRY(hipGetLastError());
+    if (!unit_columns) return SNMF_OK;
+    for (int k = 0; k < B; ++k) SN_TRY(launch_fin_bm(this, k, 1, 1, 0, 0, 0, a.Wc + (size_t)k * a.sWc));  // :157-158
     return SNMF_OK;
 }
 

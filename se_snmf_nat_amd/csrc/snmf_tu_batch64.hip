@@ -66,6 +66,7 @@ struct Batch64 final : snmf_batch {
         return load_t(k, V, ldV, W0, H0, M, ldM);
     }
     int take_h0(snmf_batch& src, int row0) override;
+    int take_w0(const int64_t* idx, bool unit_columns) override;
     size_t v_elem() const override { return sizeof(double); }
     int v_blocks(std::vector<VBlock>* out) override;
     int v_written() override;
@@ -353,10 +354,12 @@ int Batch64::load_t(int k, const TT* V, int64_t ldV, const TT* W0, const TT* H0,
     if (V) SN_TRY((xfer_pack_in<TT, double>(ctx, V, ldV, F, T, dV, F, T, false)));
     if (masked) SN_TRY((xfer_pack_in<TT, double>(ctx, M, ldM, F, T, Mblk + q.fr0 * F, F, T, false)));
     if (H0) SN_TRY((xfer_pack_in<TT, double>(ctx, H0, r, r, T, dH, r, T, false)));
-    SN_TRY((xfer_pack_in<TT, double>(ctx, W0, F, F, r, dW, F, r, false)));
     // the initial scaling (:157-169) with the single solve's own kernels, on this problem's arrays
-    hipLaunchKernelGGL((k_s64_wupd<true, false>), dim3(r), dim3(256), 0, st, dW, nullptr, nullptr, nullptr, nullptr, F, dwn, &a.st[k].stop);
-    HIP_TRY(hipGetLastError());
+    if (W0) {
+        SN_TRY((xfer_pack_in<TT, double>(ctx, W0, F, F, r, dW, F, r, false)));
+        hipLaunchKernelGGL((k_s64_wupd<true, false>), dim3(r), dim3(256), 0, st, dW, nullptr, nullptr, nullptr, nullptr, F, dwn, &a.st[k].stop);
+        HIP_TRY(hipGetLastError());
+    }
     if (H0) SN_TRY(scale_h0(k));
     if (masked) {  // src/snmf_mdi.m:175, the masked start (it floors: floor_v has no meaning here)
         hipLaunchKernelGGL(k_s64_mdi_start, dim3(grid64(nFT)), dim3(256), 0, st, dV, (const double*)(Mblk + q.fr0 * F), nFT);
@@ -390,6 +393,41 @@ int Batch64::take_h0(snmf_batch& src_, int row0) {
     hipLaunchKernelGGL(k_b64_take_h, dim3(elem_grid(this, a.r), B), dim3(256), 0, ctx->stream, a, (const double*)src->a.H, src->a.r, row0);
     HIP_TRY(hipGetLastError());
     for (int k = 0; k < B; ++k) SN_TRY(scale_h0(k));
+    return SNMF_OK;
+}
+
+// One launch with the problem as a grid index gathers the columns into each problem's W; then the scaling load() does after its
+// W0 upload, problem by problem.
+int Batch64::take_w0(const int64_t* idx, bool unit_columns) {
+    if (!idx) return fail(SNMF_ERR_INVALID, "take_w0: NULL argument");
+    if (masked) return fail(SNMF_ERR_UNSUPPORTED, "a missing-data batch takes its W0 from the host");
+    struct Tmp {  // (a table of this call alone: the device block is carved once, when the batch is made)
+        void* q = nullptr;
+        ~Tmp() {
+            if (q) hipFree(q);
+        }
+    } tmp;
+    const size_t bytes = sizeof(int64_t) * (size_t)B * a.r;
+    {
+        hipError_t e = hipMalloc(&tmp.q, bytes);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            tmp.q = nullptr;
+            return fail(SNMF_ERR_NOMEM, "hipMalloc(%zu bytes): %s", bytes, hipGetErrorString(e));
+        }
+    }
+    hipStream_t st = ctx->stream;
+    HIP_TRY(hipMemcpyAsync(tmp.q, idx, bytes, hipMemcpyHostToDevice, st));
+    const int g = (int)std::min<long long>(((long long)a.F * a.r + 255) / 256, kElemGridMax);
+    hipLaunchKernelGGL(k_b64_take_w, dim3(g, B), dim3(256), 0, st, a, (const int64_t*)tmp.q);
+    HIP_TRY(hipGetLastError());
+    if (unit_columns)
+        for (int k = 0; k < B; ++k) {  // :157-158
+            hipLaunchKernelGGL((k_s64_wupd<true, false>), dim3(a.r), dim3(256), 0, st, a.W + (long long)k * a.F * a.r, nullptr, nullptr, nullptr,
+                               nullptr, a.F, a.wn + (long long)k * a.r, &a.st[k].stop);
+            HIP_TRY(hipGetLastError());
+        }
+    HIP_TRY(hipStreamSynchronize(st));  // (the table is freed on return, and the caller's array may go)
     return SNMF_OK;
 }
 

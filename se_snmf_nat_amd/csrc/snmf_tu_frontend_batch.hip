@@ -1,8 +1,9 @@
 // snmf_tu_frontend_batch.hip -- the front-end grouped over the signals of a batch (the kernels of snmf_frontend_batch.h) and the
-// two callers that need it:
+// three callers that need it:
 //
 //   snmf_stft_features_batch_f32 / _fp64             TF_mag (or TF_Mel) of n signals, tight host arrays in and out
 //   snmf_run_basis_dnmf_audio_batch_f64 / _fp64      run_basis_DNMF.m:1-55 (and its Mel twin) for n pairs of WAVEFORMS
+//   snmf_run_basis_train_audio_batch_f64 / _fp64     run_basis_train.m:58-91 for the training signals of n classes
 //
 // The DNMF entries are dnmf_batch_run of snmf_batch_host.h -- the three resident batches of snmf_run_basis_dnmf_batch_* -- with V
 // formed on the device: the truncated waveforms of every problem go up as ONE slab through the context's transfer pipeline
@@ -19,6 +20,7 @@ namespace {
 constexpr int kMaxSignals = 65535;        // a launch grid's second dimension: the element-wise passes put the signal there
 constexpr long long kMaxFrames = 0x7fffffffLL;  // a launch grid's first dimension: k_stft*_grp has a workgroup per frame
 constexpr int kElemGrid = 1024;           // workgroups per signal of an element-wise pass (grid-stride beyond)
+constexpr int kTabs = 4;                  // FeSig tables of a run: STFT, splice, Mel, TF_DD
 
 // every device block of one call; freed on every way out (a failed allocation leaks nothing)
 struct DevMem {
@@ -85,6 +87,7 @@ struct FeBatch {
     int cap_sig = 0, cap_runs = 0, runs = 0;
     DevMem mem;
     S *slab = nullptr, *win = nullptr, *mel = nullptr, *tmp = nullptr, *scr = nullptr;
+    double* carry = nullptr;  // TF_DD: [chunks of a run][DFT rows]
     C2* tw = nullptr;
     FeSig* tab = nullptr;
     std::vector<S> h_win, h_mel;  // (sources of asynchronous copies: they live as long as the device blocks)
@@ -95,9 +98,10 @@ struct FeBatch {
     int rows_dft() const { return Ks * nb; }
 
     // slab_elems samples; every run forms at most max_frames frames of at most max_sig signals.  With a Mel table the DFT-row
-    // scratch is one run's: the runs of a call use it in turn.
+    // scratch is one run's: the runs of a call use it in turn; a caller whose runs all keep the DFT rows (run with dst_mel) asks
+    // for none.  tfdd: the runs may apply TF_DD.
     int open(snmf_ctx* c, const snmf_stft_params* sp_in, const S* mel_host, int mel_M, int64_t slab_elems, int64_t max_frames, int max_sig,
-             int n_runs) {
+             int n_runs, bool dft_scratch = true, bool tfdd = false) {
         ctx = c;
         sp = *sp_in;
         N = sp.fftlength, nb = N / 2 + 1, Ks = 2 * sp.splice + 1, M = mel_host ? mel_M : 0;
@@ -115,8 +119,9 @@ struct FeBatch {
         SN_TRY(mem.get(&win, h_win.size()));
         SN_TRY(mem.get(&tw, h_tw.size()));
         if (sp.splice > 0) SN_TRY(mem.get(&tmp, (size_t)nb * (size_t)max_frames));
+        if (tfdd) SN_TRY(mem.get(&carry, (size_t)rows_dft() * (size_t)(max_frames / kDdGrpChunk + max_sig)));
         if (M) {
-            SN_TRY(mem.get(&scr, (size_t)rows_dft() * (size_t)max_frames));
+            if (dft_scratch) SN_TRY(mem.get(&scr, (size_t)rows_dft() * (size_t)max_frames));
             h_mel.resize((size_t)M * nb);
             if (sizeof(S) == 4) std::copy(mel_host, mel_host + h_mel.size(), h_mel.begin());  // k_mel reads the ABI's row-major M x n
             else                                                                                 // k_mel64 reads it transposed
@@ -125,49 +130,61 @@ struct FeBatch {
             SN_TRY(mem.get(&mel, h_mel.size()));
             HIP_TRY(hipMemcpyAsync(mel, h_mel.data(), h_mel.size() * sizeof(S), hipMemcpyHostToDevice, st));
         }
-        SN_TRY(mem.get(&tab, (size_t)3 * max_sig * n_runs));
-        h_tab.resize((size_t)3 * max_sig * n_runs);
+        SN_TRY(mem.get(&tab, (size_t)kTabs * max_sig * n_runs));
+        h_tab.resize((size_t)kTabs * max_sig * n_runs);
         HIP_TRY(hipMemcpyAsync(win, h_win.data(), h_win.size() * sizeof(S), hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(tw, h_tw.data(), h_tw.size() * sizeof(C2), hipMemcpyHostToDevice, st));
         opened = true;
         return SNMF_OK;
     }
 
-    // features of n signals: signal k starts at sample s0[k] of the slab, has T[k] >= 1 frames and goes to dst[k]
-    int run(int n, const int64_t* s0, const int32_t* T, const snmf_batch::VBlock* dst) {
+    // features of n signals: signal k starts at sample s0[k] of the slab, has T[k] >= 1 frames and goes to dst[k].
+    // dst_mel == nullptr: dst receives the Mel rows when there is a Mel table (the DFT rows pass through the scratch), else the
+    // DFT rows.  dst_mel != nullptr (needs the table): BOTH feature sets stay -- the DFT rows are formed in dst, the Mel rows are
+    // projected from there into dst_mel, and no scratch is used.  alpha_dd >= 0: TF_DD runs in place on the DFT rows, wherever
+    // they are, before the Mel pass reads them (run_basis_train.m:64-78).
+    int run(int n, const int64_t* s0, const int32_t* T, const snmf_batch::VBlock* dst, const snmf_batch::VBlock* dst_mel = nullptr,
+            double alpha_dd = -1.0) {
+        const bool dd = alpha_dd >= 0.0;
         if (runs >= cap_runs || n > cap_sig || n < 1) return fail(SNMF_ERR_INTERNAL, "grouped front-end: run %d of %d with %d signals", runs, cap_runs, n);
+        if ((dst_mel && !M) || (M && !dst_mel && !scr) || (dd && !carry)) return fail(SNMF_ERR_INTERNAL, "grouped front-end: a run it was not opened for");
         hipStream_t st = ctx->stream;
         const int S_ = sp.splice;
-        FeSig* h = h_tab.data() + (size_t)3 * cap_sig * runs;
-        FeSig* d = tab + (size_t)3 * cap_sig * runs;
-        FeSig *h_st = h, *h_sp = h + cap_sig, *h_ml = h + 2 * (size_t)cap_sig;
-        int64_t f0 = 0;
+        FeSig* h = h_tab.data() + (size_t)kTabs * cap_sig * runs;
+        FeSig* d = tab + (size_t)kTabs * cap_sig * runs;
+        FeSig *h_st = h, *h_sp = h + cap_sig, *h_ml = h + 2 * (size_t)cap_sig, *h_dd = h + 3 * (size_t)cap_sig;
+        int64_t f0 = 0, c0 = 0;  // frames, TF_DD chunks of the signals before k
         int maxT = 1;
         for (int k = 0; k < n; ++k) {
             const int64_t Tk = T[k];
             maxT = std::max(maxT, T[k]);
-            S* out = (S*)dst[k].V;
             S* t_k = tmp ? tmp + (size_t)nb * f0 : nullptr;
-            S* s_k = scr ? scr + (size_t)rows_dft() * f0 : nullptr;
-            // the STFT writes the unspliced magnitudes (a splicing pass follows), the DFT-row scratch (the Mel pass follows) or the result
+            // where the DFT rows of the signal are formed, and where its result goes
+            const bool via_scr = M && !dst_mel;
+            S* dft = via_scr ? scr + (size_t)rows_dft() * f0 : (S*)dst[k].V;
+            const int64_t ld_dft = via_scr ? (int64_t)rows_dft() : dst[k].ld;
+            const snmf_batch::VBlock& mo = dst_mel ? dst_mel[k] : dst[k];
+            // the STFT writes the unspliced magnitudes (a splicing pass follows) or the DFT rows
             FeSig a{};
             a.s0 = s0[k], a.f0 = f0, a.T = T[k];
             if (S_ > 0) a.dst = t_k, a.ld_dst = nb;
-            else if (M) a.dst = s_k, a.ld_dst = rows_dft();
-            else a.dst = out, a.ld_dst = dst[k].ld;
+            else a.dst = dft, a.ld_dst = ld_dft;
             h_st[k] = a;
             FeSig b{};
-            b.T = T[k], b.src = t_k, b.ld_src = nb;
-            if (M) b.dst = s_k, b.ld_dst = rows_dft();
-            else b.dst = out, b.ld_dst = dst[k].ld;
+            b.T = T[k], b.src = t_k, b.ld_src = nb, b.dst = dft, b.ld_dst = ld_dft;
             h_sp[k] = b;
             FeSig m{};
-            m.T = T[k], m.src = s_k, m.ld_src = rows_dft(), m.dst = out, m.ld_dst = dst[k].ld;
+            m.T = T[k], m.src = dft, m.ld_src = ld_dft, m.dst = mo.V, m.ld_dst = mo.ld;
             h_ml[k] = m;
+            FeSig e{};
+            e.T = T[k], e.f0 = c0, e.dst = dft, e.ld_dst = ld_dft;
+            h_dd[k] = e;
             f0 += Tk;
+            c0 += (Tk + kDdGrpChunk - 1) / kDdGrpChunk;
         }
         if (f0 > cap_frames || f0 > kMaxFrames) return fail(SNMF_ERR_INTERNAL, "grouped front-end: %lld frames in a run sized for %lld", (long long)f0, (long long)cap_frames);
-        HIP_TRY(hipMemcpyAsync(d, h, sizeof(FeSig) * (size_t)3 * cap_sig, hipMemcpyHostToDevice, st));
+        if (dd && c0 > cap_frames / kDdGrpChunk + cap_sig) return fail(SNMF_ERR_INTERNAL, "grouped front-end: %lld TF_DD chunks", (long long)c0);
+        HIP_TRY(hipMemcpyAsync(d, h, sizeof(FeSig) * (size_t)kTabs * cap_sig, hipMemcpyHostToDevice, st));
         ++runs;
         typename Types<S>::Args a{};
         a.slab = slab, a.sig = d, a.n_sig = n;
@@ -189,6 +206,15 @@ struct FeBatch {
         auto grid = [&](int rows) { return dim3((unsigned)std::max<long long>(1, std::min<long long>(((long long)rows * maxT + 255) / 256, kElemGrid)), (unsigned)n); };
         if (S_ > 0) {
             hipLaunchKernelGGL(k_splice_grp<S>, grid(rows_dft()), dim3(256), 0, st, (const FeSig*)(d + cap_sig), nb, S_, (S)sp.nonzerofloor);
+            HIP_TRY(hipGetLastError());
+        }
+        if (dd) {  // the three passes of snmf_tf_dd_*, each one launch over every signal
+            const FeSig* dt = d + 3 * (size_t)cap_sig;
+            const int F = rows_dft();
+            const dim3 g((unsigned)c0, (unsigned)((F + 255) / 256));
+            hipLaunchKernelGGL(k_tfdd_carry_grp<S>, g, dim3(256), 0, st, dt, n, F, alpha_dd, carry);
+            hipLaunchKernelGGL(k_tfdd_state_grp<S>, dim3((unsigned)((F + 255) / 256), (unsigned)n), dim3(256), 0, st, dt, F, alpha_dd, carry);
+            hipLaunchKernelGGL(k_tfdd_apply_grp<S>, g, dim3(256), 0, st, dt, n, F, alpha_dd, (const double*)carry);
             HIP_TRY(hipGetLastError());
         }
         if (M) {
@@ -319,10 +345,93 @@ int dnmf_audio_batch(const char* entry, snmf_batch* (*make)(), snmf_ctx* ctx, co
     return dnmf_batch_run<double>(entry, make, ctx, p, R_x, R_d, n, T.data(), in, B, B_hat, A_hat, n_iter);
 }
 
+// ---- run_basis_train for the training signals of n classes -----------------------------------------------------------------------
+// train_batch_run of snmf_batch_host.h with the features formed by ONE run of the grouped front-end: STFT (+ splice) into the DFT
+// engine's blocks, TF_DD in place there, the Mel projection from those blocks into the Mel engine's.  The front-end launches
+// 1 + [Splice > 0] + 3 [TF_DD] + [mel] times and each engine gathers its exemplars in one launch, whatever n.
+template <typename S>
+int train_audio_batch(const char* entry, snmf_batch* (*make)(), snmf_ctx* ctx, const snmf_params* p, const snmf_stft_params* sp, double alpha_eta_dd,
+                      const S* mel, int32_t mel_M, int32_t n, const S* const* samples, const int64_t* n_samples,
+                      const int64_t* const* sample_idx, int32_t train_exemplar, const double* const* H0, const uint64_t* seed,
+                      double* const* B_DFT, double* const* A_DFT, double* const* B_Mel, double* const* A_Mel, int32_t* n_iter) {
+    if (!ctx || !p || !samples || !n_samples || !sample_idx || !B_DFT) return fail(SNMF_ERR_INVALID, "%s: NULL argument", entry);
+    SN_TRY(check_batch_size(entry, n, "n_problems"));
+    SN_TRY(validate_stft(sp));
+    {
+        snmf_params q = *p;
+        q.T = 1;  // (ignored: every problem brings its own)
+        SN_TRY(validate_params(&q));
+    }
+    if ((mel != nullptr) != (B_Mel != nullptr)) return fail(SNMF_ERR_INVALID, "%s: mel and B_Mel must be given together", entry);
+    if (mel && mel_M < 1) return fail(SNMF_ERR_INVALID, "%s: mel_M must be positive", entry);
+    if (p->sparsity_kind != SNMF_SPARSITY_SCALAR)
+        return fail(SNMF_ERR_UNSUPPORTED, "%s: a sparsity vector or matrix is not supported by the training entry (it takes the scalar of p)", entry);
+    const int nb = sp->fftlength / 2 + 1, Ks = 2 * sp->splice + 1, r = p->r;
+    const int64_t F = (int64_t)Ks * nb, Fm = mel ? (int64_t)Ks * mel_M : 0;
+    std::vector<int32_t> T(n);
+    std::vector<int64_t> len(n), s0(n), idx((size_t)n * r);
+    int64_t sumL = 0, sumT = 0;
+    for (int k = 0; k < n; ++k) {
+        if (!samples[k] || !sample_idx[k] || !B_DFT[k] || (mel && !B_Mel[k])) return fail(SNMF_ERR_INVALID, "%s: an array of problem %d is NULL", entry, k);
+        if (!train_exemplar && (!H0 || !H0[k]) && !seed) return fail(SNMF_ERR_INVALID, "%s: problem %d has no H0 and there are no seeds", entry, k);
+        const int64_t Tk = snmf_stft_num_frames(sp, n_samples[k]);
+        if (Tk < 1) return fail(SNMF_ERR_INVALID, "%s: the signal of problem %d is shorter than one analysis frame", entry, k);
+        if (Tk > kMaxFrames) return fail(SNMF_ERR_UNSUPPORTED, "%s: problem %d has %lld frames", entry, k, (long long)Tk);
+        T[k] = (int32_t)Tk;
+        len[k] = n_samples[k];
+        s0[k] = sumL;
+        sumL += n_samples[k];
+        sumT += Tk;
+    }
+    if (sumT > kMaxFrames) return fail(SNMF_ERR_UNSUPPORTED, "%s: %lld frames are above the launch grid's limit", entry, (long long)sumT);
+    if (F != p->F) return fail(SNMF_ERR_DIM, "%s: the signals give %lld feature rows, params say %d", entry, (long long)F, p->F);
+    if (Fm > 0x7fffffffLL) return fail(SNMF_ERR_UNSUPPORTED, "%s: %lld Mel feature rows", entry, (long long)Fm);
+    for (int k = 0; k < n; ++k)
+        for (int j = 0; j < r; ++j) {
+            const int64_t t = sample_idx[k][j];
+            if (t < 0 || t >= T[k])
+                return fail(SNMF_ERR_DIM, "%s: sample_idx[%d][%d] = %lld outside [0, %d)", entry, k, j, (long long)t, T[k]);
+            idx[(size_t)k * r + j] = t;
+        }
+    (void)hipGetLastError();
+
+    FeBatch<S> fe;  // (declared before the engines of train_batch_run: it outlives them)
+    TrainInputs<double> in;
+    in.idx = idx.data();
+    in.exemplar = train_exemplar != 0;
+    in.H0 = H0;
+    in.seed = seed;
+    in.device_v = [&](const std::vector<snmf_batch::VBlock>& dft, const std::vector<snmf_batch::VBlock>& melb, size_t elem) -> int {
+        if (elem != sizeof(S) || (int)dft.size() != n || (mel && (int)melb.size() != n))
+            return fail(SNMF_ERR_INTERNAL, "%s: the engine's V is not of the sample type", entry);
+        SN_TRY(fe.open(ctx, sp, mel, mel_M, sumL, sumT, n, 1, false, alpha_eta_dd >= 0.0));  // the engines exist, every refusal has been made
+        SN_TRY(xfer_gather_in<S>(ctx, n, samples, len.data(), fe.slab));
+        return fe.run(n, s0.data(), T.data(), dft.data(), mel ? melb.data() : nullptr, alpha_eta_dd);
+    };
+    return train_batch_run<double>(entry, make, ctx, p, (int32_t)Fm, n, T.data(), in, B_DFT, A_DFT, B_Mel, A_Mel, n_iter);
+}
+
 snmf_batch* make32() { return batch32_new(); }
 snmf_batch* make64() { return batch64_new(); }
 
 }  // namespace
+
+extern "C" int snmf_run_basis_train_audio_batch_f64(snmf_ctx* ctx, const snmf_params* p, const snmf_stft_params* sp, double alpha_eta_dd,
+                                                    const float* mel, int32_t mel_M, int32_t n_problems, const float* const* samples,
+                                                    const int64_t* n_samples, const int64_t* const* sample_idx, int32_t train_exemplar,
+                                                    const double* const* H0, const uint64_t* seed, double* const* B_DFT,
+                                                    double* const* A_DFT, double* const* B_Mel, double* const* A_Mel, int32_t* n_iter) {
+    return train_audio_batch<float>("snmf_run_basis_train_audio_batch_f64", make32, ctx, p, sp, alpha_eta_dd, mel, mel_M, n_problems, samples,
+                                    n_samples, sample_idx, train_exemplar, H0, seed, B_DFT, A_DFT, B_Mel, A_Mel, n_iter);
+}
+extern "C" int snmf_run_basis_train_audio_batch_fp64(snmf_ctx* ctx, const snmf_params* p, const snmf_stft_params* sp, double alpha_eta_dd,
+                                                     const double* mel, int32_t mel_M, int32_t n_problems, const double* const* samples,
+                                                     const int64_t* n_samples, const int64_t* const* sample_idx, int32_t train_exemplar,
+                                                     const double* const* H0, const uint64_t* seed, double* const* B_DFT,
+                                                     double* const* A_DFT, double* const* B_Mel, double* const* A_Mel, int32_t* n_iter) {
+    return train_audio_batch<double>("snmf_run_basis_train_audio_batch_fp64", make64, ctx, p, sp, alpha_eta_dd, mel, mel_M, n_problems, samples,
+                                     n_samples, sample_idx, train_exemplar, H0, seed, B_DFT, A_DFT, B_Mel, A_Mel, n_iter);
+}
 
 extern "C" int snmf_stft_features_batch_f32(snmf_ctx* ctx, const snmf_stft_params* sp, int32_t n_signals, const float* const* samples,
                                             const int64_t* n_samples, const float* mel, int32_t mel_M, float* const* V_out,

@@ -4,6 +4,7 @@ and stays with the caller).  Everything numeric runs on the GPU: features (front
 sparse_nmf solves (api.py); this module only sequences them like the reference does.
 
     out = run_basis_train_signal(s_full, R, p)        # B_DFT_sub, B_Mel_sub, A_DFT_sub, A_Mel_sub
+    [out_k] = run_basis_train_signal_batch(signals, R, p)      # the same for a list of signals (one per class), solved together
     save_basis_mat(path, out)                         # R_<R>.mat with the reference's variable names
     B_hat = run_basis_DNMF(x, d, B, p)                # run_basis_DNMF.m:1      (waveforms in, like the reference)
     B_hat = run_basis_DNMF_Mel(x, d, B, p)            # run_basis_DNMF_Mel.m:1
@@ -20,7 +21,7 @@ from . import _lib, frontend
 from .api import SnmfError, _check_precision, _fp64_rules, _make_params, _solver_scalars, default_context
 
 
-def run_basis_train_signal(s_full, R, p, *, DC_bin=None, sample_idx=None, ctx=None, h0="host", precision="fp32"):
+def run_basis_train_signal(s_full, R, p, *, DC_bin=None, sample_idx=None, ctx=None, h0="host", precision="fp32", info=None):
     """run_basis_train.m:58-136.  `p`: the reference's settings fields (front-end fields of
     frontend.default_params() plus cf/sparsity/max_iter/conv_eps/cost_check, cluster_buff,
     train_Exemplar).  sample_idx: the exemplar columns (1-based like randsample, :81); default = a
@@ -33,7 +34,7 @@ def run_basis_train_signal(s_full, R, p, *, DC_bin=None, sample_idx=None, ctx=No
     stand-in) is drawn here and uploaded; "device" = drawn on the device (api.philox_uniform).
     precision: "fp32" (default) = float samples, fp32 features and solves; "fp64" = snmf_run_basis_train_audio_fp64: the signal
     crosses as float64 and features, Mel projection, exemplars and both solves are computed in double.  Any other string is a
-    ValueError.  The returned arrays are float64 in both."""
+    ValueError.  The returned arrays are float64 in both.  info: a dict that receives info["n_iter"] = [n_dft, n_mel]."""
     _check_precision(precision)
     f64 = precision == "fp64"
     sdt = np.float64 if f64 else np.float32
@@ -83,12 +84,111 @@ def run_basis_train_signal(s_full, R, p, *, DC_bin=None, sample_idx=None, ctx=No
     _lib.check(fn(
         ctx._h, C.byref(q), C.byref(sp), float(p["alpha_eta"]) if p.get("domain_DD", 0) else -1.0, ptr(mel), M, ptr(s), s.size,
         ptr(idx0), 1 if exemplar else 0, ptr(H0), seed, ptr(B_DFT), ptr(A_DFT), ptr(B_Mel), ptr(A_Mel), ptr(nit)))
+    if info is not None:
+        info["n_iter"] = [int(v) for v in nit]
     B_DFT = B_DFT / np.sqrt((B_DFT ** 2).sum(0)) + 1e-9  # :113-114
     B_Mel = B_Mel / np.sqrt((B_Mel ** 2).sum(0)) + 1e-9  # :115-116
     if cluster_buff > 1:  # :118-127: keep one basis vector per cluster of the Mel dictionary (host logic, as in the reference)
         from .kmeans import reduce_rank
         B_Mel, B_DFT, A_DFT, A_Mel, _ = reduce_rank(B_Mel, B_DFT, A_DFT, A_Mel, int(R), seed=int(p.get("kmeans_seed", 1)))
     return {"B_DFT_sub": B_DFT, "B_Mel_sub": B_Mel, "A_DFT_sub": A_DFT, "A_Mel_sub": A_Mel}  # :130-134
+
+
+def run_basis_train_signal_batch(signals, R, p, *, DC_bin=None, sample_idx=None, ctx=None, h0="host", precision="fp32", info=None):
+    """[run_basis_train_signal(s_k, R, p, ...) for s_k in signals], solved together: the loop l = 1:length(DB_path_list) of
+    run_basis_train.m, one training signal per event class or noise type, in ONE call across the C ABI
+    (snmf_run_basis_train_audio_batch_f64; precision="fp64": _fp64).  The signals (any lengths) go up as one slab, TF_mag, TF_DD and
+    TF_Mel of all of them are formed in HBM by shared launches, the exemplar columns are gathered there, and the DFT and the Mel
+    solves are two resident batches.  R, p and DC_bin are shared.  Returns a list of the dicts run_basis_train_signal returns.
+
+    sample_idx: None = every problem gets the single call's own stand-in draw, RandomState(1).choice(T_k, cluster_buff*R,
+    replace=False) + 1 (the reference re-seeds per class, :80-81); else a list of 1-based index arrays, one per problem.
+    h0: "host" = every problem gets the draw the single call makes, RandomState(random_seed).random_sample((n_ex, T_k)) -- the same
+    seed for every problem, since the reference re-seeds inside every sparse_nmf call; "device" = drawn on the device from
+    random_seed, for every problem.  Both solves of a problem start from the same H0, as in the single call.
+    precision="fp64": problem k is bit for bit run_basis_train_signal(s_k, R, p, precision="fp64", ...) alone.
+    precision="fp32": the fp32 batch engine (F <= 513, cluster_buff*R <= 200): bit for bit sparse_nmf_batch(precision="fp32") on
+    the fp32 features stft_features (then tf_dd, then mel_features on that) give for s_k, with init_w their columns sample_idx_k.
+    Any other string is a ValueError.  info["T"] receives the frame counts, info["n_iter"] a list of [n_dft, n_mel].
+    Every argument error is raised before the library is loaded."""
+    _check_precision(precision)
+    f64 = precision == "fp64"
+    sdt = np.float64 if f64 else np.float32
+    p = dict(p)
+    cluster_buff = int(p.get("cluster_buff", 1))
+    exemplar = bool(p.get("train_Exemplar", 0))
+    if cluster_buff > 1 and exemplar:
+        raise SnmfError(3, "cluster_buff > 1 needs train_Exemplar = 0 (run_basis_train.m:125-126 index A_*_init, a scalar otherwise)")
+    fp = dict(p)
+    if DC_bin is not None:
+        fp["DCbin"] = int(DC_bin)
+    sigs = [np.ascontiguousarray(np.asarray(s, dtype=sdt).reshape(-1)) for s in signals]
+    n = len(sigs)
+    if n == 0:
+        raise SnmfError(1, "the batch is empty: signals must hold at least one waveform")
+    if not isinstance(h0, str) or h0 not in ("host", "device"):
+        raise SnmfError(3, "h0 must be 'host' or 'device'")
+    K = 2 * int(fp.get("Splice", 0)) + 1
+    F, M = K * (int(fp["fftlength"]) // 2 + 1), int(p["F_order"])
+    n_ex = cluster_buff * int(R)
+    Ts = [frontend.num_frames_host(s.size, fp) for s in sigs]
+    for k, T in enumerate(Ts):
+        if T < 1:
+            raise SnmfError(3, f"the training signal of problem {k} is shorter than one analysis frame")
+        if n_ex > T:
+            raise SnmfError(3, f"problem {k} has {T} frames, fewer than cluster_buff*R = {n_ex} exemplar columns")
+    if sample_idx is None:
+        sample_idx = [np.random.RandomState(1).choice(T, size=n_ex, replace=False) + 1 for T in Ts]  # :80-81 stand-in, per class
+    elif len(sample_idx) != n:
+        raise SnmfError(3, f"sample_idx is a list of {len(sample_idx)}, the batch has {n} problems")
+    idx0 = [np.ascontiguousarray(np.asarray(ix, dtype=np.int64).reshape(-1) - 1) for ix in sample_idx]
+    for k, (ix, T) in enumerate(zip(idx0, Ts)):
+        if ix.size != n_ex or ix.min() < 0 or ix.max() >= T:
+            raise SnmfError(3, f"sample_idx of problem {k} must hold cluster_buff*R valid 1-based column indices")
+    if exemplar:
+        beta, max_iter, conv_eps, cost_check, lam = 1.0, 1, 0.0, 0, 0.0
+    else:
+        beta, max_iter, conv_eps, cost_check, lam = _solver_scalars(p)
+    q = _make_params(F, 1, n_ex, beta, max_iter, conv_eps, cost_check, True, 0, lam, None, None)
+    seed = int(p.get("random_seed", 1))
+    H0s = seeds = None
+    if not exemplar:
+        if h0 == "host":
+            H0s = [np.asfortranarray(np.random.RandomState(seed if seed > 0 else None).random_sample((n_ex, T))) for T in Ts]
+        else:
+            seeds = np.full(n, seed, np.uint64)
+    mel = frontend._mel_table(p, sdt)
+    sp, _win = frontend._params(fp)
+
+    lib = _lib.load()
+    ctx = ctx or default_context()
+    B_DFT = [np.empty((F, n_ex), order="F") for _ in Ts]
+    B_Mel = [np.empty((K * M, n_ex), order="F") for _ in Ts]
+    A_DFT = A_Mel = None
+    if not exemplar:
+        A_DFT = [np.empty((n_ex, T), order="F") for T in Ts]
+        A_Mel = [np.empty((n_ex, T), order="F") for T in Ts]
+    n_iter = np.zeros(2 * n, np.int32)
+    lens = np.array([s.size for s in sigs], np.int64)
+    ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None  # noqa: E731
+    ptrs = lambda arrs: (C.c_void_p * n)(*[a.ctypes.data for a in arrs]) if arrs is not None else None  # noqa: E731
+    fn = lib.snmf_run_basis_train_audio_batch_fp64 if f64 else lib.snmf_run_basis_train_audio_batch_f64
+    _lib.check(fn(ctx._h, C.byref(q), C.byref(sp), float(p["alpha_eta"]) if p.get("domain_DD", 0) else -1.0, ptr(mel), M, n, ptrs(sigs),
+                  ptr(lens), ptrs(idx0), 1 if exemplar else 0, ptrs(H0s), ptr(seeds), ptrs(B_DFT), ptrs(A_DFT), ptrs(B_Mel), ptrs(A_Mel),
+                  ptr(n_iter)))
+    if info is not None:
+        info["T"] = list(Ts)
+        info["n_iter"] = [[int(v) for v in n_iter[2 * k:2 * k + 2]] for k in range(n)]
+    out = []
+    for k in range(n):  # the host epilogue of the single call, per problem
+        bd = B_DFT[k] / np.sqrt((B_DFT[k] ** 2).sum(0)) + 1e-9  # :113-114
+        bm = B_Mel[k] / np.sqrt((B_Mel[k] ** 2).sum(0)) + 1e-9  # :115-116
+        ad, am = (0, 0) if exemplar else (A_DFT[k], A_Mel[k])  # :95-96
+        if cluster_buff > 1:  # :118-127
+            from .kmeans import reduce_rank
+            bm, bd, ad, am, _ = reduce_rank(bm, bd, ad, am, int(R), seed=int(p.get("kmeans_seed", 1)))
+        out.append({"B_DFT_sub": bd, "B_Mel_sub": bm, "A_DFT_sub": ad, "A_Mel_sub": am})  # :130-134
+    return out
 
 
 def save_basis_mat(path, out, v73=True):
