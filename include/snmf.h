@@ -930,10 +930,72 @@ int snmf_run_basis_train_audio_batch_fp64(snmf_ctx* ctx, const snmf_params* p, c
                                           const double* const* H0, const uint64_t* seed, double* const* B_DFT, double* const* A_DFT,
                                           double* const* B_Mel, double* const* A_Mel, int32_t* n_iter);
 
+/* Added within 5.  The step before basis training, run_basis_train.m:16-57 with src/vadenergy_simple.m:1-32: the training signal
+ * s_full of n_classes classes assembled on the device from their clips ("Training signals from clips").  The clips
+ * cross as they come off disk -- int16 PCM (_i16: s = pcm / 32768 * 32767, :26-27) or doubles already scaled wavread(.) * 32767
+ * (_f64) -- and every s_full stays in HBM behind the handle, for snmf_run_basis_train_signals_batch_* below.  The caller shuffles
+ * and subsamples (:17, :21): class k consumes its n_clips[k] clips in the order given.  clips and clip_len run over all clips of
+ * all classes in class order; mode has one entry per class (VAD_set / p.train_ANOT):
+ *   mode 1  src/vadenergy_simple.m: bg_mean = mean(|s(1:bg_len)|); frames k = 1 .. floor(len / shift) - 1 of frame_len samples
+ *           from 1 + (k-1) * shift, shift = frame_len / 2; a frame is voiced when (mean|frame| - bg_mean) / mean|frame| > thr (a
+ *           0/0 or -inf compares false); a sample is voiced when a frame covering it is; the clip becomes nonzeros(s .* vad): exact
+ *           zeros inside voiced stretches are dropped too (:37).  file_len_max is not applied.
+ *   mode 2  the clip becomes s(v_start:v_end), range[2c], range[2c+1] of clip c (1-based, inclusive; range is read only for the
+ *           clips of mode-2 classes and may be NULL when there is none).  Zeros stay.
+ *   mode 0  the clip becomes s(1:file_len_max) when it is longer; file_len_max <= 0: no cut.  Zeros stay.
+ * Then s = s / sqrt(var(s)) (two passes, N - 1), s = s / max|s| * 30000 (:44-45), element by element in that order, and the clip
+ * is appended; when the length then EXCEEDS seq_len_max the signal is cut to exactly seq_len_max and the later clips are not
+ * used (:50-53; a length equal to the limit does not stop).  All arithmetic is fp64.  The sums are formed in a fixed tree order
+ * (not MATLAB's sequential one): the signals are the same bits from run to run and within a few ulp of the reference's.
+ * TWO DEVIATIONS, where the reference fails or produces NaN: a clip with no kept sample contributes nothing and counts as used
+ * (MATLAB appends an empty vector); a clip among the consumed ones whose
+ * variance, as computed, is not a positive finite number -- one kept sample, a constant clip -- makes the call fail with
+ * SNMF_ERR_INVALID, naming the class and the clip: no handle is returned and the context stays usable (MATLAB writes NaN into
+ * s_full and trains NaN dictionaries).
+ * Refused before the device is touched: NULL arguments, n_classes < 1, a class with no clip, a mode outside 0..2, a mode-2 class
+ * with range == NULL, frame_len odd or < 2, bg_len < 1, seq_len_max < 0 (SNMF_ERR_INVALID); a clip without a sample, a mode-1 clip
+ * shorter than bg_len (an index error in MATLAB), a range outside [1, len] or with v_start > v_end (SNMF_ERR_DIM).  A class whose
+ * assembled length is 0 or shorter than one analysis frame assembles fine: the training entry refuses it.
+ * snmf_train_signals_info: n_samples and clips_used receive one entry per class (any of the three may be NULL).
+ * snmf_train_signals_get_f64: s_full of class k (n_samples[k] doubles; run_basis_train.m:96 writes s_full ./ 32767 as the class's
+ * wav).  snmf_train_signals_destroy gives the slab back (it may follow the context's own destruction; every other entry needs the
+ * context alive). */
+typedef struct snmf_train_signals snmf_train_signals;
+typedef struct {
+    int32_t frame_len, bg_len; /* src/vadenergy_simple.m:19 (0.02 * fs), run_basis_train.m:32 (0.05 * fs) */
+    double thr;                /* run_basis_train.m:35 */
+    int64_t seq_len_max, file_len_max; /* p.train_seq_len_max, p.train_file_len_max (samples) */
+} snmf_assemble_params;
+int snmf_train_signals_assemble_i16(snmf_ctx* ctx, const snmf_assemble_params* ap, int32_t n_classes, const int32_t* n_clips,
+                                    const int16_t* const* clips, const int64_t* clip_len, const int32_t* mode, const int64_t* range,
+                                    snmf_train_signals** out);
+int snmf_train_signals_assemble_f64(snmf_ctx* ctx, const snmf_assemble_params* ap, int32_t n_classes, const int32_t* n_clips,
+                                    const double* const* clips, const int64_t* clip_len, const int32_t* mode, const int64_t* range,
+                                    snmf_train_signals** out);
+int snmf_train_signals_info(const snmf_train_signals* signals, int32_t* n_classes, int64_t* n_samples, int32_t* clips_used);
+int snmf_train_signals_get_f64(const snmf_train_signals* signals, int32_t k, double* s_full);
+int snmf_train_signals_destroy(snmf_train_signals* signals);
+/* Added within 5.  snmf_run_basis_train_audio_batch_* on the signals of a handle: n_problems and n_samples are the handle's, the
+ * sample slab of the grouped front-end is filled from the resident signals by one launch (a copy for the fp64 engine, round to
+ * nearest to float for the fp32 engine) and the rest is the same code.  THE CONTRACTS: _fp64 is bit for bit
+ * snmf_run_basis_train_audio_batch_fp64 on the signals snmf_train_signals_get_f64 returns, _f64 bit for bit
+ * snmf_run_basis_train_audio_batch_f64 on those signals rounded to float.  Every refusal of those entries carries over (a class
+ * shorter than one analysis frame included); a handle of another context is SNMF_ERR_INVALID. */
+int snmf_run_basis_train_signals_batch_f64(snmf_ctx* ctx, const snmf_params* p, const snmf_stft_params* sp, double alpha_eta_dd,
+                                           const float* mel, int32_t mel_M, const snmf_train_signals* signals,
+                                           const int64_t* const* sample_idx, int32_t train_exemplar, const double* const* H0,
+                                           const uint64_t* seed, double* const* B_DFT, double* const* A_DFT, double* const* B_Mel,
+                                           double* const* A_Mel, int32_t* n_iter);
+int snmf_run_basis_train_signals_batch_fp64(snmf_ctx* ctx, const snmf_params* p, const snmf_stft_params* sp, double alpha_eta_dd,
+                                            const double* mel, int32_t mel_M, const snmf_train_signals* signals,
+                                            const int64_t* const* sample_idx, int32_t train_exemplar, const double* const* H0,
+                                            const uint64_t* seed, double* const* B_DFT, double* const* A_DFT, double* const* B_Mel,
+                                            double* const* A_Mel, int32_t* n_iter);
+
 /* ---- instrumentation (bench.py: HIP-event timing on the engine's own stream) ------------ */
 /* Average device time in milliseconds per launch of the named kernel family over the launches
  * recorded since snmf_ctx_timing(ctx, 1) was switched on.  Families: "hstep", "wstats",
- * "wapply", "reduce".  Timing inserts hipEvents around each launch (off by default). */
+ * "wapply", "reduce", "wfin", and "assemble" (the ten launches of one snmf_train_signals_assemble_* call).  Timing inserts hipEvents around each launch (off by default). */
 int snmf_ctx_timing(snmf_ctx* ctx, int enable);
 /* Host <-> device transfer counters of a context since the last reset (host arrays move as a pipeline of column chunks through
  * pinned bounce buffers, csrc/snmf_tu_xfer.hip).  out8 = { host->device: bytes of the callers' arrays, wall seconds inside the

@@ -10,7 +10,8 @@ from .api import (Context, Plan, SnmfError, default_context, dnmf_adapt, run_bas
 from .batch import (BatchPlan, BatchPlan64, BatchPlanMdi64, run_basis_dnmf_batch, snmf_mdi_batch, snmf_mdi_Sm_batch,  # noqa: F401
                     sparse_nmf_batch, sparse_nmf_batch_fp64)
 from .frontend import stft_features_batch  # noqa: F401
-from .train import run_basis_DNMF_batch, run_basis_DNMF_Mel_batch, run_basis_train_signal_batch  # noqa: F401
+from .train import (TrainSignals, assemble_training_signals, run_basis_DNMF_batch, run_basis_DNMF_Mel_batch,  # noqa: F401
+                    run_basis_train_assembled_batch, run_basis_train_clips_batch, run_basis_train_signal_batch)
 
 
 def release_device_lists():

@@ -48,7 +48,8 @@ _TU_HDRS = {
     "snmf_tu_train64.hip": ["snmf_online_common.h", "snmf_frontend64.h", "snmf_philox.h", "snmf_solve64_core.h", "snmf_host64.h"],
     "snmf_tu_batch.hip": ["snmf_batch.h", "snmf_batch_host.h", "snmf_philox.h"],
     "snmf_tu_batch64.hip": ["snmf_solve64.h", "snmf_batch64.h", "snmf_batch_host.h", "snmf_host64.h", "snmf_philox.h"],
-    "snmf_tu_frontend_batch.hip": ["snmf_online_common.h", "snmf_frontend_batch.h", "snmf_batch_host.h"],
+    "snmf_tu_frontend_batch.hip": ["snmf_online_common.h", "snmf_frontend_batch.h", "snmf_batch_host.h", "snmf_assemble.h"],
+    "snmf_tu_assemble.hip": ["snmf_online_common.h", "snmf_assemble.h"],
 }
 HDRS = sorted(_glob.glob(os.path.join(_HERE, "csrc", "*.h"))) + [os.path.join(_ROOT, "include", "snmf.h")]
 
@@ -98,6 +99,8 @@ SYMBOLS = [
     "snmf_stft_features_batch_f32", "snmf_stft_features_batch_fp64",
     "snmf_run_basis_dnmf_audio_batch_f64", "snmf_run_basis_dnmf_audio_batch_fp64",
     "snmf_run_basis_train_audio_batch_f64", "snmf_run_basis_train_audio_batch_fp64",
+    "snmf_train_signals_assemble_i16", "snmf_train_signals_assemble_f64", "snmf_train_signals_info", "snmf_train_signals_get_f64",
+    "snmf_train_signals_destroy", "snmf_run_basis_train_signals_batch_f64", "snmf_run_basis_train_signals_batch_fp64",
     "snmf_rccl_available", "snmf_rccl_get_unique_id", "snmf_rccl_comm_create", "snmf_rccl_comm_destroy", "snmf_plan_run_sharded_rccl",
 ]
 ABI_VERSION = 5  # include/snmf.h: SNMF_ABI_VERSION this binding was written against
@@ -126,6 +129,10 @@ class SnmfStftParams(C.Structure):
         ("splice", C.c_int32), ("preemph", C.c_double), ("pow", C.c_double), ("nonzerofloor", C.c_double),
         ("window", C.c_void_p),
     ]
+
+
+class SnmfAssembleParams(C.Structure):
+    _fields_ = [("frame_len", C.c_int32), ("bg_len", C.c_int32), ("thr", C.c_double), ("seq_len_max", C.c_int64), ("file_len_max", C.c_int64)]
 
 
 class SnmfOnlineParams(C.Structure):
@@ -387,6 +394,15 @@ def load():
     # basis training for a batch of signals: the single entry's settings, then arrays of pointers and of lengths
     for ty in ("f64", "fp64"):
         sig[f"snmf_run_basis_train_audio_batch_{ty}"] = (C.c_int, [vp, PP, SP, dbl, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp])
+    # the training signals assembled on the device from clips, and basis training on them
+    AP = C.POINTER(SnmfAssembleParams)
+    for ty in ("i16", "f64"):
+        sig[f"snmf_train_signals_assemble_{ty}"] = (C.c_int, [vp, AP, i32, vp, vp, vp, vp, vp, C.POINTER(vp)])
+    sig["snmf_train_signals_info"] = (C.c_int, [vp, C.POINTER(i32), vp, vp])
+    sig["snmf_train_signals_get_f64"] = (C.c_int, [vp, i32, vp])
+    sig["snmf_train_signals_destroy"] = (C.c_int, [vp])
+    for ty in ("f64", "fp64"):
+        sig[f"snmf_run_basis_train_signals_batch_{ty}"] = (C.c_int, [vp, PP, SP, dbl, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp])
     lib.snmf_abi_version.restype = C.c_int
     if lib.snmf_abi_version() != ABI_VERSION:  # a stale library must not be driven through newer prototypes
         raise ImportError(f"{path} has ABI version {lib.snmf_abi_version()}, this binding needs {ABI_VERSION}: rebuild the library")

@@ -25,7 +25,7 @@ int fail(int code, const char* fmt, ...) {
 // ------------------------------------------------------------------------------------------
 // context
 // ------------------------------------------------------------------------------------------
-static const char* kFamNames[FAM_N] = {"hstep", "wstats", "wapply", "reduce", "wfin"};
+static const char* kFamNames[FAM_N] = {"hstep", "wstats", "wapply", "reduce", "wfin", "assemble"};
 
 static void drain_timers(snmf_ctx* c) {
     if (c->pending.empty()) return;

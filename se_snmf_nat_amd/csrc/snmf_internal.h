@@ -2,7 +2,7 @@
 // and plan structures, and the prototypes of the launch dispatchers.  The library is built from several .hip files
 // compiled in parallel (se_snmf_nat_amd/_lib.py): snmf_api.hip (context, plans, data movement, the iteration loop, the
 // front-end), snmf_tu_geometry.hip (the kernels and launch geometry of a plan), snmf_tu_hstep*.hip / snmf_tu_wstats*.hip / snmf_tu_small.hip (the template instantiations of the three big
-// kernel families and their dispatch), snmf_tu_online.hip, snmf_tu_multi.hip, snmf_tu_dnmf.hip, snmf_tu_frontend_batch.hip (the front-end grouped over a batch).  Nothing here is part of
+// kernel families and their dispatch), snmf_tu_online.hip, snmf_tu_multi.hip, snmf_tu_dnmf.hip, snmf_tu_frontend_batch.hip (the front-end grouped over a batch), snmf_tu_assemble.hip (training signals from clips).  Nothing here is part of
 // the C ABI (include/snmf.h).
 #pragma once
 #include "snmf_kernels.h"
@@ -48,7 +48,7 @@ struct TimerPair {
     hipEvent_t a, b;
     int fam;
 };
-enum { FAM_HSTEP = 0, FAM_WSTATS, FAM_WAPPLY, FAM_REDUCE, FAM_WFIN, FAM_N };
+enum { FAM_HSTEP = 0, FAM_WSTATS, FAM_WAPPLY, FAM_REDUCE, FAM_WFIN, FAM_ASSEMBLE, FAM_N };
 
 struct HostXfer;  // pinned bounce buffers + copy stream of the chunked host <-> device pipeline (snmf_tu_xfer.hip)
 struct XferStats {
@@ -63,8 +63,8 @@ struct snmf_ctx {
     size_t lds_max = 160 * 1024;
     bool timing = false;
     std::vector<TimerPair> pending;
-    double fam_ms[FAM_N] = {0, 0, 0, 0, 0};
-    int64_t fam_n[FAM_N] = {0, 0, 0, 0, 0};
+    double fam_ms[FAM_N] = {};
+    int64_t fam_n[FAM_N] = {};
     HostXfer* xf = nullptr;  // created by the first host-array transfer
     snmf_ctx* aux = nullptr; // a second stream + transfer pipeline on the same device (uploads under a running solve: snmf_tu_dnmf.hip)
     XferStats xs;
@@ -251,6 +251,30 @@ static int dalloc(T** p, size_t n, snmf_ctx* cache_of = nullptr, size_t* bytes_o
     if (e != hipSuccess) return fail(SNMF_ERR_NOMEM, "hipMalloc(%zu bytes): %s", n * sizeof(T), hipGetErrorString(e));
     return SNMF_OK;
 }
+
+// every device block of one call; freed on every way out (a failed allocation leaks nothing).  keep: the block outlives the call
+// and is the caller's to free.
+struct DevMem {
+    std::vector<void*> ptrs;
+    hipStream_t st = nullptr;
+    ~DevMem() {
+        if (st) hipStreamSynchronize(st);
+        for (void* q : ptrs) hipFree(q);
+    }
+    template <typename T>
+    int get(T** p, size_t n, bool keep = false) {
+        *p = nullptr;
+        const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
+        hipError_t e = hipMalloc((void**)p, bytes);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            *p = nullptr;
+            return fail(SNMF_ERR_NOMEM, "hipMalloc(%zu bytes): %s", bytes, hipGetErrorString(e));
+        }
+        if (!keep) ptrs.push_back(*p);
+        return SNMF_OK;
+    }
+};
 
 static inline int grid_for(size_t n) { return (int)std::min<size_t>((n + 255) / 256, 4096); }
 

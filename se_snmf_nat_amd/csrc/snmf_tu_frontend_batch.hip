@@ -4,6 +4,7 @@
 //   snmf_stft_features_batch_f32 / _fp64             TF_mag (or TF_Mel) of n signals, tight host arrays in and out
 //   snmf_run_basis_dnmf_audio_batch_f64 / _fp64      run_basis_DNMF.m:1-55 (and its Mel twin) for n pairs of WAVEFORMS
 //   snmf_run_basis_train_audio_batch_f64 / _fp64     run_basis_train.m:58-91 for the training signals of n classes
+//   snmf_run_basis_train_signals_batch_f64 / _fp64   the same on the signals a snmf_train_signals handle holds in HBM
 //
 // The DNMF entries are dnmf_batch_run of snmf_batch_host.h -- the three resident batches of snmf_run_basis_dnmf_batch_* -- with V
 // formed on the device: the truncated waveforms of every problem go up as ONE slab through the context's transfer pipeline
@@ -14,6 +15,7 @@
 #include "snmf_internal.h"
 #include "snmf_frontend_batch.h"
 #include "snmf_batch_host.h"
+#include "snmf_assemble.h"
 
 namespace {
 
@@ -21,29 +23,6 @@ constexpr int kMaxSignals = 65535;        // a launch grid's second dimension: t
 constexpr long long kMaxFrames = 0x7fffffffLL;  // a launch grid's first dimension: k_stft*_grp has a workgroup per frame
 constexpr int kElemGrid = 1024;           // workgroups per signal of an element-wise pass (grid-stride beyond)
 constexpr int kTabs = 4;                  // FeSig tables of a run: STFT, splice, Mel, TF_DD
-
-// every device block of one call; freed on every way out (a failed allocation leaks nothing)
-struct DevMem {
-    std::vector<void*> ptrs;
-    hipStream_t st = nullptr;
-    ~DevMem() {
-        if (st) hipStreamSynchronize(st);
-        for (void* q : ptrs) hipFree(q);
-    }
-    template <typename T>
-    int get(T** p, size_t n) {
-        *p = nullptr;
-        const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
-        hipError_t e = hipMalloc((void**)p, bytes);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            *p = nullptr;
-            return fail(SNMF_ERR_NOMEM, "hipMalloc(%zu bytes): %s", bytes, hipGetErrorString(e));
-        }
-        ptrs.push_back(*p);
-        return SNMF_OK;
-    }
-};
 
 template <typename S>
 struct Types;
@@ -349,12 +328,21 @@ int dnmf_audio_batch(const char* entry, snmf_batch* (*make)(), snmf_ctx* ctx, co
 // train_batch_run of snmf_batch_host.h with the features formed by ONE run of the grouped front-end: STFT (+ splice) into the DFT
 // engine's blocks, TF_DD in place there, the Mel projection from those blocks into the Mel engine's.  The front-end launches
 // 1 + [Splice > 0] + 3 [TF_DD] + [mel] times and each engine gathers its exemplars in one launch, whatever n.
+// ts != nullptr (snmf_run_basis_train_signals_batch_*): the signals are the handle's, resident in HBM as doubles; samples and
+// n_samples are not looked at, the lengths are the handle's and the sample slab is filled by one launch of k_sig_fill (a copy
+// for double, round to nearest for float) instead of the transfer.  Everything else is the same code.
 template <typename S>
 int train_audio_batch(const char* entry, snmf_batch* (*make)(), snmf_ctx* ctx, const snmf_params* p, const snmf_stft_params* sp, double alpha_eta_dd,
                       const S* mel, int32_t mel_M, int32_t n, const S* const* samples, const int64_t* n_samples,
                       const int64_t* const* sample_idx, int32_t train_exemplar, const double* const* H0, const uint64_t* seed,
-                      double* const* B_DFT, double* const* A_DFT, double* const* B_Mel, double* const* A_Mel, int32_t* n_iter) {
-    if (!ctx || !p || !samples || !n_samples || !sample_idx || !B_DFT) return fail(SNMF_ERR_INVALID, "%s: NULL argument", entry);
+                      double* const* B_DFT, double* const* A_DFT, double* const* B_Mel, double* const* A_Mel, int32_t* n_iter,
+                      const snmf_train_signals* ts = nullptr) {
+    if (!ctx || !p || (!ts && (!samples || !n_samples)) || !sample_idx || !B_DFT) return fail(SNMF_ERR_INVALID, "%s: NULL argument", entry);
+    if (ts) {
+        if (ts->ctx != ctx) return fail(SNMF_ERR_INVALID, "%s: the signals were assembled on another context", entry);
+        n = (int32_t)ts->len.size();
+        n_samples = ts->len.data();
+    }
     SN_TRY(check_batch_size(entry, n, "n_problems"));
     SN_TRY(validate_stft(sp));
     {
@@ -372,7 +360,7 @@ int train_audio_batch(const char* entry, snmf_batch* (*make)(), snmf_ctx* ctx, c
     std::vector<int64_t> len(n), s0(n), idx((size_t)n * r);
     int64_t sumL = 0, sumT = 0;
     for (int k = 0; k < n; ++k) {
-        if (!samples[k] || !sample_idx[k] || !B_DFT[k] || (mel && !B_Mel[k])) return fail(SNMF_ERR_INVALID, "%s: an array of problem %d is NULL", entry, k);
+        if ((!ts && !samples[k]) || !sample_idx[k] || !B_DFT[k] || (mel && !B_Mel[k])) return fail(SNMF_ERR_INVALID, "%s: an array of problem %d is NULL", entry, k);
         if (!train_exemplar && (!H0 || !H0[k]) && !seed) return fail(SNMF_ERR_INVALID, "%s: problem %d has no H0 and there are no seeds", entry, k);
         const int64_t Tk = snmf_stft_num_frames(sp, n_samples[k]);
         if (Tk < 1) return fail(SNMF_ERR_INVALID, "%s: the signal of problem %d is shorter than one analysis frame", entry, k);
@@ -395,6 +383,7 @@ int train_audio_batch(const char* entry, snmf_batch* (*make)(), snmf_ctx* ctx, c
         }
     (void)hipGetLastError();
 
+    std::vector<SigCopy> h_cp;  // (the source of an asynchronous copy: it lives as long as the front-end)
     FeBatch<S> fe;  // (declared before the engines of train_batch_run: it outlives them)
     TrainInputs<double> in;
     in.idx = idx.data();
@@ -405,7 +394,19 @@ int train_audio_batch(const char* entry, snmf_batch* (*make)(), snmf_ctx* ctx, c
         if (elem != sizeof(S) || (int)dft.size() != n || (mel && (int)melb.size() != n))
             return fail(SNMF_ERR_INTERNAL, "%s: the engine's V is not of the sample type", entry);
         SN_TRY(fe.open(ctx, sp, mel, mel_M, sumL, sumT, n, 1, false, alpha_eta_dd >= 0.0));  // the engines exist, every refusal has been made
-        SN_TRY(xfer_gather_in<S>(ctx, n, samples, len.data(), fe.slab));
+        if (ts) {
+            h_cp.resize(n);
+            int64_t maxL = 1;
+            for (int k = 0; k < n; ++k) h_cp[k] = SigCopy{ts->out0[k], s0[k], len[k]}, maxL = std::max(maxL, len[k]);
+            SigCopy* d_cp = nullptr;
+            SN_TRY(fe.mem.get(&d_cp, (size_t)n));
+            HIP_TRY(hipMemcpyAsync(d_cp, h_cp.data(), sizeof(SigCopy) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+            const dim3 g((unsigned)std::min<int64_t>((maxL + 255) / 256, 8192), (unsigned)n);
+            hipLaunchKernelGGL(k_sig_fill<S>, g, dim3(256), 0, ctx->stream, (const double*)ts->slab, (const SigCopy*)d_cp, fe.slab);
+            HIP_TRY(hipGetLastError());
+        } else {
+            SN_TRY(xfer_gather_in<S>(ctx, n, samples, len.data(), fe.slab));
+        }
         return fe.run(n, s0.data(), T.data(), dft.data(), mel ? melb.data() : nullptr, alpha_eta_dd);
     };
     return train_batch_run<double>(entry, make, ctx, p, (int32_t)Fm, n, T.data(), in, B_DFT, A_DFT, B_Mel, A_Mel, n_iter);
@@ -431,6 +432,27 @@ extern "C" int snmf_run_basis_train_audio_batch_fp64(snmf_ctx* ctx, const snmf_p
                                                      double* const* A_DFT, double* const* B_Mel, double* const* A_Mel, int32_t* n_iter) {
     return train_audio_batch<double>("snmf_run_basis_train_audio_batch_fp64", make64, ctx, p, sp, alpha_eta_dd, mel, mel_M, n_problems, samples,
                                      n_samples, sample_idx, train_exemplar, H0, seed, B_DFT, A_DFT, B_Mel, A_Mel, n_iter);
+}
+
+extern "C" int snmf_run_basis_train_signals_batch_f64(snmf_ctx* ctx, const snmf_params* p, const snmf_stft_params* sp, double alpha_eta_dd,
+                                                      const float* mel, int32_t mel_M, const snmf_train_signals* signals,
+                                                      const int64_t* const* sample_idx, int32_t train_exemplar, const double* const* H0,
+                                                      const uint64_t* seed, double* const* B_DFT, double* const* A_DFT,
+                                                      double* const* B_Mel, double* const* A_Mel, int32_t* n_iter) {
+    const char* entry = "snmf_run_basis_train_signals_batch_f64";
+    if (!signals) return fail(SNMF_ERR_INVALID, "%s: NULL argument", entry);
+    return train_audio_batch<float>(entry, make32, ctx, p, sp, alpha_eta_dd, mel, mel_M, 0, nullptr, nullptr, sample_idx, train_exemplar, H0, seed,
+                                    B_DFT, A_DFT, B_Mel, A_Mel, n_iter, signals);
+}
+extern "C" int snmf_run_basis_train_signals_batch_fp64(snmf_ctx* ctx, const snmf_params* p, const snmf_stft_params* sp, double alpha_eta_dd,
+                                                       const double* mel, int32_t mel_M, const snmf_train_signals* signals,
+                                                       const int64_t* const* sample_idx, int32_t train_exemplar, const double* const* H0,
+                                                       const uint64_t* seed, double* const* B_DFT, double* const* A_DFT,
+                                                       double* const* B_Mel, double* const* A_Mel, int32_t* n_iter) {
+    const char* entry = "snmf_run_basis_train_signals_batch_fp64";
+    if (!signals) return fail(SNMF_ERR_INVALID, "%s: NULL argument", entry);
+    return train_audio_batch<double>(entry, make64, ctx, p, sp, alpha_eta_dd, mel, mel_M, 0, nullptr, nullptr, sample_idx, train_exemplar, H0, seed,
+                                     B_DFT, A_DFT, B_Mel, A_Mel, n_iter, signals);
 }
 
 extern "C" int snmf_stft_features_batch_f32(snmf_ctx* ctx, const snmf_stft_params* sp, int32_t n_signals, const float* const* samples,

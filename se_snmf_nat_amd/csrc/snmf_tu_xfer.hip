@@ -359,6 +359,7 @@ int xfer_gather_in(snmf_ctx* ctx, int n, const T* const* src, const int64_t* len
 }
 template int xfer_gather_in<float>(snmf_ctx*, int, const float* const*, const int64_t*, float*);
 template int xfer_gather_in<double>(snmf_ctx*, int, const double* const*, const int64_t*, double*);
+template int xfer_gather_in<int16_t>(snmf_ctx*, int, const int16_t* const*, const int64_t*, int16_t*);  // PCM clips (snmf_tu_assemble.hip)
 
 // the combinations the library uses
 #define XFER_IN(TI, TD) template int xfer_pack_in<TI, TD>(snmf_ctx*, const TI*, int64_t, int, int, TD*, int, int, bool)

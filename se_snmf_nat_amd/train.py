@@ -1,10 +1,14 @@
 """Host mirror of the basis-training caller, run_basis_train.m:58-136, for ONE event class whose
-training signal has already been assembled (the wav shuffling / concatenation of :16-57 is file I/O
-and stays with the caller).  Everything numeric runs on the GPU: features (frontend.py), both
-sparse_nmf solves (api.py); this module only sequences them like the reference does.
+training signal has already been assembled, and of the assembly itself (:16-57) for the clips of many
+classes at once (reading and shuffling the wav files stays with the caller).  Everything numeric runs
+on the GPU: the assembly, features (frontend.py), both sparse_nmf solves (api.py); this module only
+sequences them like the reference does.
 
     out = run_basis_train_signal(s_full, R, p)        # B_DFT_sub, B_Mel_sub, A_DFT_sub, A_Mel_sub
     [out_k] = run_basis_train_signal_batch(signals, R, p)      # the same for a list of signals (one per class), solved together
+    ts = assemble_training_signals(classes, p, vad=...)        # run_basis_train.m:16-57: every class's s_full from its clips, in HBM
+    [out_k] = run_basis_train_assembled_batch(ts, R, p)        # run_basis_train_signal_batch on those resident signals
+    [out_k] = run_basis_train_clips_batch(classes, R, p)       # both steps: clips in, dictionaries out
     save_basis_mat(path, out)                         # R_<R>.mat with the reference's variable names
     B_hat = run_basis_DNMF(x, d, B, p)                # run_basis_DNMF.m:1      (waveforms in, like the reference)
     B_hat = run_basis_DNMF_Mel(x, d, B, p)            # run_basis_DNMF_Mel.m:1
@@ -111,6 +115,13 @@ def run_basis_train_signal_batch(signals, R, p, *, DC_bin=None, sample_idx=None,
     the fp32 features stft_features (then tf_dd, then mel_features on that) give for s_k, with init_w their columns sample_idx_k.
     Any other string is a ValueError.  info["T"] receives the frame counts, info["n_iter"] a list of [n_dft, n_mel].
     Every argument error is raised before the library is loaded."""
+    return _train_batch(signals, None, R, p, DC_bin=DC_bin, sample_idx=sample_idx, ctx=ctx, h0=h0, precision=precision, info=info)
+
+
+def _train_batch(signals, ts, R, p, *, DC_bin, sample_idx, ctx, h0, precision, info):
+    """run_basis_train_signal_batch (ts None: host signals through snmf_run_basis_train_audio_batch_*) and
+    run_basis_train_assembled_batch (ts: a TrainSignals, through snmf_run_basis_train_signals_batch_*): the same checks, draws,
+    call and host epilogue; only where the samples come from differs."""
     _check_precision(precision)
     f64 = precision == "fp64"
     sdt = np.float64 if f64 else np.float32
@@ -122,8 +133,12 @@ def run_basis_train_signal_batch(signals, R, p, *, DC_bin=None, sample_idx=None,
     fp = dict(p)
     if DC_bin is not None:
         fp["DCbin"] = int(DC_bin)
-    sigs = [np.ascontiguousarray(np.asarray(s, dtype=sdt).reshape(-1)) for s in signals]
-    n = len(sigs)
+    if ts is None:
+        sigs = [np.ascontiguousarray(np.asarray(s, dtype=sdt).reshape(-1)) for s in signals]
+        sizes = [s.size for s in sigs]
+    else:
+        sizes = [int(v) for v in ts.lengths]
+    n = len(sizes)
     if n == 0:
         raise SnmfError(1, "the batch is empty: signals must hold at least one waveform")
     if not isinstance(h0, str) or h0 not in ("host", "device"):
@@ -131,7 +146,7 @@ def run_basis_train_signal_batch(signals, R, p, *, DC_bin=None, sample_idx=None,
     K = 2 * int(fp.get("Splice", 0)) + 1
     F, M = K * (int(fp["fftlength"]) // 2 + 1), int(p["F_order"])
     n_ex = cluster_buff * int(R)
-    Ts = [frontend.num_frames_host(s.size, fp) for s in sigs]
+    Ts = [frontend.num_frames_host(size, fp) for size in sizes]
     for k, T in enumerate(Ts):
         if T < 1:
             raise SnmfError(3, f"the training signal of problem {k} is shorter than one analysis frame")
@@ -161,7 +176,7 @@ def run_basis_train_signal_batch(signals, R, p, *, DC_bin=None, sample_idx=None,
     sp, _win = frontend._params(fp)
 
     lib = _lib.load()
-    ctx = ctx or default_context()
+    ctx = ts._ctx if ts is not None else (ctx or default_context())
     B_DFT = [np.empty((F, n_ex), order="F") for _ in Ts]
     B_Mel = [np.empty((K * M, n_ex), order="F") for _ in Ts]
     A_DFT = A_Mel = None
@@ -169,13 +184,17 @@ def run_basis_train_signal_batch(signals, R, p, *, DC_bin=None, sample_idx=None,
         A_DFT = [np.empty((n_ex, T), order="F") for T in Ts]
         A_Mel = [np.empty((n_ex, T), order="F") for T in Ts]
     n_iter = np.zeros(2 * n, np.int32)
-    lens = np.array([s.size for s in sigs], np.int64)
     ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None  # noqa: E731
     ptrs = lambda arrs: (C.c_void_p * n)(*[a.ctypes.data for a in arrs]) if arrs is not None else None  # noqa: E731
-    fn = lib.snmf_run_basis_train_audio_batch_fp64 if f64 else lib.snmf_run_basis_train_audio_batch_f64
-    _lib.check(fn(ctx._h, C.byref(q), C.byref(sp), float(p["alpha_eta"]) if p.get("domain_DD", 0) else -1.0, ptr(mel), M, n, ptrs(sigs),
-                  ptr(lens), ptrs(idx0), 1 if exemplar else 0, ptrs(H0s), ptr(seeds), ptrs(B_DFT), ptrs(A_DFT), ptrs(B_Mel), ptrs(A_Mel),
-                  ptr(n_iter)))
+    alpha = float(p["alpha_eta"]) if p.get("domain_DD", 0) else -1.0
+    tail = (ptrs(idx0), 1 if exemplar else 0, ptrs(H0s), ptr(seeds), ptrs(B_DFT), ptrs(A_DFT), ptrs(B_Mel), ptrs(A_Mel), ptr(n_iter))
+    if ts is None:
+        lens = np.array(sizes, np.int64)
+        fn = lib.snmf_run_basis_train_audio_batch_fp64 if f64 else lib.snmf_run_basis_train_audio_batch_f64
+        _lib.check(fn(ctx._h, C.byref(q), C.byref(sp), alpha, ptr(mel), M, n, ptrs(sigs), ptr(lens), *tail))
+    else:
+        fn = lib.snmf_run_basis_train_signals_batch_fp64 if f64 else lib.snmf_run_basis_train_signals_batch_f64
+        _lib.check(fn(ctx._h, C.byref(q), C.byref(sp), alpha, ptr(mel), M, ts._handle(), *tail))
     if info is not None:
         info["T"] = list(Ts)
         info["n_iter"] = [[int(v) for v in n_iter[2 * k:2 * k + 2]] for k in range(n)]
@@ -189,6 +208,164 @@ def run_basis_train_signal_batch(signals, R, p, *, DC_bin=None, sample_idx=None,
             bm, bd, ad, am, _ = reduce_rank(bm, bd, ad, am, int(R), seed=int(p.get("kmeans_seed", 1)))
         out.append({"B_DFT_sub": bd, "B_Mel_sub": bm, "A_DFT_sub": ad, "A_Mel_sub": am})  # :130-134
     return out
+
+
+class TrainSignals:
+    """The training signals of every class, assembled and resident on the device (snmf_train_signals of include/snmf.h).
+    .lengths / .clips_used: per class, samples of s_full and clips consumed (run_basis_train.m:46-57); .signal(k): s_full of class
+    k as float64 (:96 writes it ./ 32767 as the class's wav); .close() gives the device memory back (also a context manager)."""
+
+    def __init__(self, handle, ctx, lengths, clips_used):
+        self._h, self._ctx = handle, ctx
+        self.lengths, self.clips_used = list(lengths), list(clips_used)
+
+    def _handle(self):
+        if self._h is None:
+            raise SnmfError(7, "the training signals have been closed")
+        return self._h
+
+    def signal(self, k):
+        k = int(k)
+        if not 0 <= k < len(self.lengths):
+            raise SnmfError(3, f"class {k} of {len(self.lengths)}")
+        s = np.empty(self.lengths[k], np.float64)
+        _lib.check(_lib.load().snmf_train_signals_get_f64(self._handle(), k, C.c_void_p(s.ctypes.data)))
+        return s
+
+    def close(self):
+        if self._h is not None:
+            h, self._h = self._h, None
+            _lib.load().snmf_train_signals_destroy(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _whole(x, what):
+    """An integer-valued setting (0.05 * fs samples): the integer, or SnmfError."""
+    r = round(float(x))
+    if abs(float(x) - r) > 1e-9 * max(1.0, abs(float(x))):
+        raise SnmfError(1, f"{what} = {x} is not a whole number of samples")
+    return int(r)
+
+
+def assemble_training_signals(classes, p, *, vad=None, ranges=None, ctx=None):
+    """run_basis_train.m:16-57 for every class at once, on the device (snmf_train_signals_assemble_*): -> TrainSignals.
+    classes: a list (one entry per event class or noise type) of lists of 1-D arrays, the clips in the order they are consumed --
+    the caller applies randperm and clip_subsample (:17, :21).  int16 clips are PCM (s = pcm / 32768 * 32767, what wavread(.) *
+    32767 gives, :26-27) and cross as 2 bytes per sample; any other dtype is taken as doubles already scaled like that (a mix
+    crosses as doubles).  p: fs, train_seq_len_max, train_file_len_max (samples; <= 0: no cut).
+    vad: one bool per class (VAD_set, default all False): silence is removed by vadenergy_simple with bg_len = 0.05 * fs,
+    frame_len = 0.02 * fs, thr = 0.7 (:32-36) and nonzeros(s .* vad) (:37).  ranges: per class None, or one (v_start, v_end) per
+    clip (1-based, inclusive, what load_anot returns for p.train_ANOT, :38-40; v_start = 0 becomes 1 and v_end is clamped to the
+    clip, src/load_anot.m:9-15).  A class with neither is cut to train_file_len_max per clip (:41-43).
+    Every clip is then scaled to unit variance and a peak of 30000 (:44-45) and appended until the length exceeds
+    train_seq_len_max (:46-57).  Where the reference would produce NaN -- a consumed clip with one kept sample or no variance --
+    the call fails (SnmfError status 1, naming class and clip).  Every argument error is raised before the library is loaded."""
+    p = dict(p)
+    if not isinstance(classes, (list, tuple)) or len(classes) == 0:
+        raise SnmfError(1, "classes must be a list with at least one class")
+    n = len(classes)
+    fs = float(p["fs"])
+    bg_len, frame_len = _whole(0.05 * fs, "bg_len = 0.05 * fs"), _whole(0.02 * fs, "frame_len = 0.02 * fs")
+    if frame_len < 2 or frame_len % 2:
+        raise SnmfError(1, f"frame_len = 0.02 * fs = {frame_len} must be even and at least 2 (frame_shift = frame_len / 2)")
+    if bg_len < 1:
+        raise SnmfError(1, f"bg_len = 0.05 * fs = {bg_len} must be at least 1")
+    seq_max, file_max = int(p["train_seq_len_max"]), int(p["train_file_len_max"])
+    if seq_max < 0:
+        raise SnmfError(1, "train_seq_len_max is negative")
+    vad = [False] * n if vad is None else [bool(v) for v in vad]
+    if len(vad) != n:
+        raise SnmfError(1, f"vad has {len(vad)} entries, there are {n} classes")
+    ranges = [None] * n if ranges is None else list(ranges)
+    if len(ranges) != n:
+        raise SnmfError(1, f"ranges has {len(ranges)} entries, there are {n} classes")
+    clips, modes, rng = [], [], []
+    for k, cl in enumerate(classes):
+        if not isinstance(cl, (list, tuple)) or len(cl) == 0:
+            raise SnmfError(1, f"class {k} has no clip")
+        mode = 1 if vad[k] else (2 if ranges[k] is not None else 0)
+        if mode == 2 and len(ranges[k]) != len(cl):
+            raise SnmfError(1, f"class {k} has {len(cl)} clips and {len(ranges[k])} ranges")
+        modes.append(mode)
+        for i, c in enumerate(cl):
+            c = np.asarray(c)
+            if c.ndim != 1:
+                raise SnmfError(3, f"clip {i} of class {k} is not a vector")
+            if c.size < 1:
+                raise SnmfError(3, f"clip {i} of class {k} has no sample")
+            if mode == 1 and c.size < bg_len:
+                raise SnmfError(3, f"clip {i} of class {k} has {c.size} samples, fewer than bg_len = {bg_len}")
+            a, b = 1, c.size
+            if mode == 2:
+                a, b = (int(v) for v in ranges[k][i])
+                a, b = (1 if a == 0 else a), min(b, c.size)  # src/load_anot.m:9-15
+                if a < 1 or a > b:
+                    raise SnmfError(3, f"the range {tuple(ranges[k][i])} of clip {i} of class {k} is not inside [1, {c.size}]")
+            clips.append(c)
+            rng += [a, b]
+    pcm = all(c.dtype == np.int16 for c in clips)
+    if pcm:
+        clips = [np.ascontiguousarray(c) for c in clips]
+    else:  # (an int16 clip among doubles: its exact double values)
+        clips = [np.ascontiguousarray(c.astype(np.float64) / 32768 * 32767 if c.dtype == np.int16 else np.asarray(c, dtype=np.float64))
+                 for c in clips]
+    ap = _lib.SnmfAssembleParams(frame_len, bg_len, 0.7, seq_max, file_max)
+    n_clips = np.array([len(cl) for cl in classes], np.int32)
+    lens = np.array([c.size for c in clips], np.int64)
+    modes = np.array(modes, np.int32)
+    rng = np.array(rng, np.int64)
+
+    lib = _lib.load()
+    ctx = ctx or default_context()
+    h = C.c_void_p()
+    cp = (C.c_void_p * len(clips))(*[c.ctypes.data for c in clips])
+    fn = lib.snmf_train_signals_assemble_i16 if pcm else lib.snmf_train_signals_assemble_f64
+    vp = lambda a: C.c_void_p(a.ctypes.data)  # noqa: E731
+    _lib.check(fn(ctx._h, C.byref(ap), n, vp(n_clips), cp, vp(lens), vp(modes), vp(rng), C.byref(h)))
+    length, used = np.zeros(n, np.int64), np.zeros(n, np.int32)
+    _lib.check(lib.snmf_train_signals_info(h, None, vp(length), vp(used)))
+    return TrainSignals(h, ctx, [int(v) for v in length], [int(v) for v in used])
+
+
+def run_basis_train_assembled_batch(ts, R, p, *, DC_bin=None, sample_idx=None, h0="host", precision="fp32", info=None):
+    """run_basis_train_signal_batch([ts.signal(k) for k ...], R, p, ...) without the signals leaving the device
+    (snmf_run_basis_train_signals_batch_*): same arguments, same draws (T_k comes from ts.lengths, so the default sample_idx and the
+    host H0 are that call's own), same returned list, bit for bit -- in fp32 the resident doubles are rounded to float on the
+    device as np.float32 rounds them.  It runs on the context the signals were assembled on."""
+    if not isinstance(ts, TrainSignals):
+        raise SnmfError(1, "ts must be the TrainSignals assemble_training_signals returns")
+    ts._handle()
+    return _train_batch(None, ts, R, p, DC_bin=DC_bin, sample_idx=sample_idx, ctx=None, h0=h0, precision=precision, info=info)
+
+
+def run_basis_train_clips_batch(classes, R, p, *, vad=None, ranges=None, DC_bin=None, sample_idx=None, ctx=None, h0="host", precision="fp32",
+                                info=None):
+    """assemble_training_signals, run_basis_train_assembled_batch, close: the clips of every class in, the dictionaries out.
+    info also receives info["lengths"] and info["clips_used"].  The argument errors of either step that do not need the assembled
+    lengths are raised before the library is loaded; those that do (sample_idx, R against T_k) after the assembly."""
+    _check_precision(precision)
+    if not isinstance(h0, str) or h0 not in ("host", "device"):
+        raise SnmfError(3, "h0 must be 'host' or 'device'")
+    if int(p.get("cluster_buff", 1)) > 1 and p.get("train_Exemplar", 0):
+        raise SnmfError(3, "cluster_buff > 1 needs train_Exemplar = 0 (run_basis_train.m:125-126 index A_*_init, a scalar otherwise)")
+    if not p.get("train_Exemplar", 0):
+        _solver_scalars(p)
+    frontend._params(p if DC_bin is None else dict(p, DCbin=int(DC_bin)))
+    with assemble_training_signals(classes, p, vad=vad, ranges=ranges, ctx=ctx) as ts:
+        if info is not None:
+            info["lengths"], info["clips_used"] = list(ts.lengths), list(ts.clips_used)
+        return run_basis_train_assembled_batch(ts, R, p, DC_bin=DC_bin, sample_idx=sample_idx, h0=h0, precision=precision, info=info)
 
 
 def save_basis_mat(path, out, v73=True):
