@@ -788,6 +788,21 @@ int snmf_sparse_nmf_batch_fp64(snmf_ctx* ctx, const snmf_params* p, int32_t n_pr
                                double* const* W, double* const* H, double* const* div_out, double* const* cost_out,
                                int32_t* n_iter_out);
 
+/* Added within 5.  A rank of its own for every problem of an fp64 batch: r holds n_problems ranks, problem k factorizes V_k
+ * (F x T_k) into W_k (F x r[k]) and H_k (r[k] x T_k).  F and the settings stay shared.  p->r must be the largest r[k]
+ * (SNMF_ERR_DIM otherwise).  THE CONTRACT is that of snmf_batch_create_fp64: W, H, div, cost and n_iter of problem k are bit for
+ * bit those of snmf_sparse_nmf_fp64 run alone on V_k, W0_k, H0_k with p->r = r[k] -- whatever the ranks, frame counts and order
+ * of the problems around it -- and n_problems equal ranks give the bits of snmf_batch_create_fp64 with that rank.  The same
+ * kernels run: each finds its problem's rank and offsets in the device table of problems.
+ * The handle is an snmf_batch: snmf_batch_set_problem_f64 / _f32 (W0 F x r[k], H0 r[k] x T_k, tight), _run, _get_f64 / _f32
+ * (W F x r[k], H r[k] x T_k, tight), _describe (which also reports the smallest, the largest and the sum of the ranks) and
+ * _destroy work on it as on any other.  Refused before the device is touched: NULL r, r[k] < 1 (SNMF_ERR_INVALID);
+ * a sparsity that is not SNMF_SPARSITY_SCALAR, a w_update_ind or h_update_ind that is neither all ones nor all zeros
+ * (SNMF_ERR_UNSUPPORTED: an r-vector has no meaning across ranks); and what snmf_batch_create_fp64 refuses.  Uniform-only, as
+ * before: the fp32 engine (snmf_batch_create), missing-data batches (snmf_batch_create_mdi_fp64) and the DNMF batches. */
+int snmf_batch_create_ranks_fp64(snmf_ctx* ctx, const snmf_params* p, int32_t n_problems, const int32_t* T, const int32_t* r,
+                                 snmf_batch** out);
+
 /* Added within 5.  The missing-data solves in the batch: snmf_mdi_fp64 (src/snmf_mdi.m / src/snmf_mdi_Sm.m) for n_problems
  * problems, each with a mask of its own (M_b F x T_b, 1 = observed, soft masks in [0, 1]), in the shared launches of the fp64
  * batch ("Batched missing-data solves").  fp64 only: the fused fp32 missing-data kernels have no batched form.
@@ -991,6 +1006,25 @@ int snmf_run_basis_train_signals_batch_fp64(snmf_ctx* ctx, const snmf_params* p,
                                             const int64_t* const* sample_idx, int32_t train_exemplar, const double* const* H0,
                                             const uint64_t* seed, double* const* B_DFT, double* const* A_DFT, double* const* B_Mel,
                                             double* const* A_Mel, int32_t* n_iter);
+
+/* Added within 5.  snmf_run_basis_train_audio_batch_fp64 and snmf_run_basis_train_signals_batch_fp64 with a dictionary size per
+ * problem: n_atoms holds n_problems counts (cluster_buff * R_k), and p->r must be the largest (SNMF_ERR_DIM otherwise; an entry
+ * < 1 or a NULL n_atoms is SNMF_ERR_INVALID).  sample_idx[k] holds n_atoms[k] indices; H0_k, A_DFT_k and A_Mel_k are
+ * n_atoms[k] x T_k; B_DFT_k and B_Mel_k have n_atoms[k] columns.  Everything else -- arguments, refusals, the front-end, the two
+ * resident batches (made by snmf_batch_create_ranks_fp64's code) -- is the namesake's.  THE CONTRACT: problem k is bit for bit
+ * snmf_run_basis_train_audio_fp64 run alone on signal k with p->r = n_atoms[k] and the same H0_k, or with H0 = NULL and the same
+ * seed.  There is no fp32 form: the fp32 batch engine has one rank for all problems. */
+int snmf_run_basis_train_audio_batch_ranks_fp64(snmf_ctx* ctx, const snmf_params* p, const snmf_stft_params* sp, double alpha_eta_dd,
+                                                const double* mel, int32_t mel_M, int32_t n_problems, const double* const* samples,
+                                                const int64_t* n_samples, const int32_t* n_atoms, const int64_t* const* sample_idx,
+                                                int32_t train_exemplar, const double* const* H0, const uint64_t* seed,
+                                                double* const* B_DFT, double* const* A_DFT, double* const* B_Mel, double* const* A_Mel,
+                                                int32_t* n_iter);
+int snmf_run_basis_train_signals_batch_ranks_fp64(snmf_ctx* ctx, const snmf_params* p, const snmf_stft_params* sp, double alpha_eta_dd,
+                                                  const double* mel, int32_t mel_M, const snmf_train_signals* signals,
+                                                  const int32_t* n_atoms, const int64_t* const* sample_idx, int32_t train_exemplar,
+                                                  const double* const* H0, const uint64_t* seed, double* const* B_DFT,
+                                                  double* const* A_DFT, double* const* B_Mel, double* const* A_Mel, int32_t* n_iter);
 
 /* ---- instrumentation (bench.py: HIP-event timing on the engine's own stream) ------------ */
 /* Average device time in milliseconds per launch of the named kernel family over the launches

@@ -10,9 +10,11 @@
     run_basis_dnmf_batch                    run_basis_dnmf for a list of (Y, X, D) problems: three batches, A_hat resident between
                                             them; a list of (B_hat, A_hat)
 
-The problems share the row count F, the rank r and the settings `p`; every problem has its own frame count, its own initial
-factors and its own stop index.  All arithmetic happens in libsnmf_hip.so on the GPU; this module does the reference's
-defaulting and its own errors (src/sparse_nmf.m:75-164, :260) on the host, before any device call.
+The problems share the row count F and the settings `p`; every problem has its own frame count, its own initial factors and
+its own stop index.  The rank r is shared too, except in the fp64 batch (sparse_nmf_batch_fp64, BatchPlan64), where every
+problem may have a rank of its own (snmf_batch_create_ranks_fp64): a list for r, or init_w arrays of different widths.  The fp32
+engine, the missing-data batches and the DNMF batches stay at one rank.  All arithmetic happens in libsnmf_hip.so on the GPU;
+this module does the reference's defaulting and its own errors (src/sparse_nmf.m:75-164, :260) on the host, before any device call.
 """
 from __future__ import annotations
 
@@ -54,6 +56,36 @@ def _h_ind_all_or_none(p, r):
     return h_ind
 
 
+def _rank_list(r, B):
+    """A rank per problem given as a sequence -> a list of B ints (its own errors); anything else -> None."""
+    if isinstance(r, (str, bytes)) or not isinstance(r, (list, tuple, np.ndarray)) or (isinstance(r, np.ndarray) and r.ndim == 0):
+        return None
+    rs = [int(x) for x in np.asarray(r).reshape(-1)]
+    if len(rs) != B:
+        raise SnmfError(3, f"r is a list of {len(rs)}, the batch has {B} problems")
+    for k, x in enumerate(rs):
+        if x < 1:
+            raise SnmfError(1, f"problem {k} has rank {x} (at least 1)")
+    return rs
+
+
+def _mixed_rank_rules(sparsity, masks):
+    """What a batch with differing ranks takes: a scalar sparsity, and masks that are absent, all ones or all zeros (an r-vector
+    has no meaning across ranks) -> (scalar, {key: 0 or 1}); SnmfError status 8 otherwise."""
+    sp = np.asarray(sparsity, dtype=np.float64)
+    if sp.size != 1:
+        raise SnmfError(8, "a batch with differing ranks takes a scalar sparsity, not a vector or a matrix")
+    on = {}
+    for key, m in masks.items():
+        on[key] = 1
+        if m is not None:
+            m = np.asarray(m).reshape(-1) != 0
+            if m.size == 0 or (m.any() and not m.all()):
+                raise SnmfError(8, f"a batch with differing ranks takes a {key} of all ones or all zeros")
+            on[key] = int(m.all())
+    return float(sp.reshape(-1)[0]), on
+
+
 def _objective(div, cost, ni, max_iter, cost_check):
     if cost_check:
         n = ni if ni < max_iter else max_iter  # :279-280 truncate to 1:it on convergence
@@ -61,10 +93,38 @@ def _objective(div, cost, ni, max_iter, cost_check):
     return {"div": np.zeros(max_iter), "cost": np.zeros(max_iter), "n_iter": ni}
 
 
-def _batch_inits(p, vs, m):
-    """src/sparse_nmf.m:116-140 for a batch: the list forms of init_w / init_h -> (r, init_w per problem or None, init_h list or None)."""
+def _batch_inits(p, vs, m, per_problem=False):
+    """src/sparse_nmf.m:116-140 for a batch: the list forms of init_w / init_h -> (r, init_w per problem or None, init_h list or None).
+    per_problem (the fp64 batch): p["r"] may be a list and the init_w arrays may differ in width; :116-131 is then applied to
+    every problem on its own and r is the list of the problems' ranks.  Otherwise one rank, as an int, and differing ranks are
+    SnmfError status 3."""
     B = len(vs)
     iw = p.get("init_w", None)
+    prs = _rank_list(p.get("r", None), B)
+    if prs is not None and not per_problem:
+        if len(set(prs)) > 1:
+            raise SnmfError(3, f"r is {prs}: a batch shares the rank")
+        p = dict(p, r=prs[0])
+    if per_problem:
+        if prs is None and p.get("r", None) is not None:
+            prs = [int(p["r"])] * B
+        if iw is None:
+            if prs is None:
+                raise SnmfError(2, "Number of components or initialization must be given")
+            iws = [None] * B
+            rs = list(prs)
+        else:
+            if isinstance(iw, (list, tuple)):
+                if len(iw) != B:
+                    raise SnmfError(3, f"init_w is a list of {len(iw)}, the batch has {B} problems")
+                iws = [np.asarray(x, dtype=np.float64) for x in iw]
+            else:
+                iws = [np.asarray(iw, dtype=np.float64)] * B
+            for x in iws:
+                if x.ndim != 2 or x.shape[0] != m or x.shape[1] < 1:
+                    raise SnmfError(3, f"init_w is {x.shape}, v has {m} rows")
+            rs = [prs[k] if (prs is not None and x.shape[1] < prs[k]) else x.shape[1] for k, x in enumerate(iws)]  # :123-130
+        return rs, iws, _batch_init_h(p, vs, rs)
     if iw is None:
         if p.get("r", None) is None:
             raise SnmfError(2, "Number of components or initialization must be given")
@@ -84,23 +144,31 @@ def _batch_inits(p, vs, m):
                 raise SnmfError(3, f"init_w is {x.shape}, problem 0 has {iws[0].shape[1]} columns: a batch shares the rank")
         ri = iws[0].shape[1]
         r = int(p["r"]) if (p.get("r", None) is not None and ri < int(p["r"])) else ri
+    return r, iws, _batch_init_h(p, vs, [r] * B)
+
+
+def _batch_init_h(p, vs, rs):
+    """The list form of init_h (src/sparse_nmf.m:133-140): r_k x T_k arrays, or None when it is absent."""
+    B = len(vs)
     ih = p.get("init_h", None)
     ihs = None
     if ih is not None:
         if isinstance(ih, str) or not isinstance(ih, (list, tuple)) or len(ih) != B:
             raise SnmfError(3, f"init_h must be a list of {B} arrays (r x T_b each), or absent")
         ihs = [np.asarray(x, dtype=np.float64) for x in ih]
-        for v, x in zip(vs, ihs):
+        for v, x, r in zip(vs, ihs, rs):
             if x.shape != (r, v.shape[1]):
                 raise SnmfError(3, f"init_h is {x.shape}, expected ({r}, {v.shape[1]})")
-    return r, iws, ihs
+    return ihs
 
 
 def _batch_draws(vs, m, r, iws, ihs, rng, dt):
-    """The initial factors of every problem, drawn in list order from one generator (w then h, as one solve draws them)."""
+    """The initial factors of every problem, drawn in list order from one generator (w then h, as one solve draws them, each of
+    its own shape).  r: the shared rank, or a list with one per problem."""
     w0s, h0s = [], []
+    rs = r if isinstance(r, list) else [r] * len(vs)
     for k, v in enumerate(vs):
-        n = v.shape[1]
+        n, r = v.shape[1], rs[k]
         if iws[k] is None:
             w0 = rng.random_sample((m, r))
         elif iws[k].shape[1] < r:
@@ -116,7 +184,8 @@ def _batch_draws(vs, m, r, iws, ihs, rng, dt):
 def sparse_nmf_batch(vs, p=None, *, ctx=None, dtype=np.float64, rng=None, precision="fp32"):
     """[w, h, objective] = sparse_nmf(v, p) for every v in `vs`, solved together (snmf_sparse_nmf_batch_*).
 
-    vs: a list of F x T_b arrays (one F).  p: the reference's settings, shared; p["init_w"] is one F x r array (every
+    vs: a list of F x T_b arrays (one F).  p: the reference's settings, shared; p["r"] is the rank (a list of len(vs) equal
+    ranks is the same; differing ranks are SnmfError status 3 here); p["init_w"] is one F x r array (every
     problem starts from it) or a list of len(vs) of them; p["init_h"] is a list of len(vs) arrays r x T_b, or absent (drawn
     per problem as sparse_nmf draws it, from one generator in list order); p["sparsity"] is a scalar or an r-vector;
     p["display"] prints each problem's lines after the solve.  Returns a list of (w, h, objective).
@@ -129,7 +198,12 @@ def sparse_nmf_batch(vs, p=None, *, ctx=None, dtype=np.float64, rng=None, precis
 def sparse_nmf_batch_fp64(vs, p=None, *, ctx=None, rng=None):
     """sparse_nmf_batch in the fp64 mode (snmf_sparse_nmf_batch_fp64): float64 arrays in and out, the same settings, defaulting,
     draws in list order and errors.  Problem k's w, h, div, cost and n_iter are bit for bit those of
-    sparse_nmf(vs[k], p_k, precision="fp64") run alone on the same initial factors.  No F or r limit of its own."""
+    sparse_nmf(vs[k], p_k, precision="fp64") run alone on the same initial factors.  No F or r limit of its own.
+    A rank per problem: p["r"] may be a list of len(vs) ranks and the arrays of an init_w list may differ in width; problem k's
+    rank then follows src/sparse_nmf.m:116-131 on its own (init_w_k's width, or p["r"][k] when that is larger: the missing
+    columns are drawn), init_h[k] is r_k x T_k, and the draws stay in list order, w then h per problem, each of its own shape.
+    With differing ranks the sparsity must be a scalar and the masks absent, all ones or all zeros (SnmfError status 8
+    otherwise), and the solve goes through the resident handle (snmf_batch_create_ranks_fp64); equal ranks are the call above."""
     return _solve_batch(vs, p, ctx, np.float64, rng, "fp64")
 
 
@@ -158,7 +232,11 @@ def _solve_batch(vs, p, ctx, dtype, rng, mode):
     if rng is None:  # :112-114
         rng = np.random.RandomState(int(random_seed) if random_seed and random_seed > 0 else None)
 
-    r, iws, ihs = _batch_inits(p, vs, m)  # :116-131
+    r, iws, ihs = _batch_inits(p, vs, m, per_problem=mode == "fp64")  # :116-131
+    if isinstance(r, list) and len(set(r)) == 1:
+        r = r[0]
+    if isinstance(r, list):  # differing ranks: the resident handle, no one-shot entry
+        return _solve_batch_ranks(vs, p, ctx, rng, m, r, iws, ihs, beta, max_iter, conv_eps)
     w_ind = _mask(p, "w_update_ind", r)
     h_ind = _h_ind_all_or_none(p, r)
     kind, scalar, sarr = _batch_sparsity(p.get("sparsity", 0), r)
@@ -199,11 +277,39 @@ def _solve_batch(vs, p, ctx, dtype, rng, mode):
     return out
 
 
+def _solve_batch_ranks(vs, p, ctx, rng, m, rs, iws, ihs, beta, max_iter, conv_eps):
+    """sparse_nmf_batch_fp64 with differing ranks: the remaining checks and the draws, all before the library is loaded, then
+    BatchPlan64 with the ranks -- set every problem, run to the end, get."""
+    scalar, on = _mixed_rank_rules(p.get("sparsity", 0), {k: p.get(k, None) for k in ("w_update_ind", "h_update_ind")})
+    if "cost_check" not in p:  # src/sparse_nmf.m:260
+        raise SnmfError(4, "Reference to non-existent field 'cost_check'.")
+    cost_check = 1 if p["cost_check"] else 0
+    dt = np.dtype(np.float64)
+    w0s, h0s = _batch_draws(vs, m, rs, iws, ihs, rng, dt)  # the draws, in list order (:116-140)
+    plan = BatchPlan64(ctx, m, rs, [v.shape[1] for v in vs], beta=beta, max_iter=max_iter, conv_eps=conv_eps, cost_check=cost_check,
+                       sparsity=scalar, w_update_ind=bool(on["w_update_ind"]), h_update_ind=bool(on["h_update_ind"]))
+    try:
+        for k, v in enumerate(vs):
+            plan.set_problem(k, np.asarray(v, dtype=dt), w0s[k], h0s[k])
+        plan.run()
+        raw = [plan._get(k, dt) for k in range(len(vs))]
+    finally:
+        plan.close()
+    out = []
+    for W, H, div, cost, ni in raw:
+        if p.get("display", 0) != 0:
+            _display(beta, div, cost, ni, max_iter, cost_check, conv_eps, False)
+        out.append((W, H, _objective(div, cost, ni, max_iter, cost_check)))
+    return out
+
+
 class BatchPlan:
     """snmf_batch: B problems of one (F, r) and one settings struct resident in HBM.  Call order: set_problem for every
     k -> run -> get; run(n) runs n more iterations (None: up to max_iter) and a later run continues."""
 
     _create = "snmf_batch_create"
+    _create_ranks = None  # the entry that takes a rank per problem, where the engine has one
+    _rank_status = 3      # what differing ranks are where it has none
 
     def __init__(self, ctx, F, r, Ts, *, beta=1.0, max_iter=100, conv_eps=0.0, cost_check=True, floor_v=True, sparsity=0.0,
                  w_update_ind=None, h_update_ind=None, precision="fp32"):
@@ -211,12 +317,18 @@ class BatchPlan:
         self._init(ctx, F, r, Ts, beta, max_iter, conv_eps, cost_check, floor_v, sparsity, w_update_ind, h_update_ind)
 
     def _init(self, ctx, F, r, Ts, beta, max_iter, conv_eps, cost_check, floor_v, sparsity, w_update_ind, h_update_ind):
-        self.F, self.r, self.max_iter = int(F), int(r), int(max_iter)
         self.Ts = np.ascontiguousarray(np.asarray(Ts, dtype=np.int32).reshape(-1))
         self.B = int(self.Ts.size)
         if self.B == 0:
             raise SnmfError(1, "the batch is empty: Ts must hold at least one frame count")
+        self.ranks = None  # a rank per problem (BatchPlan64 with a sequence for r); None: self.r for every problem
+        rs = _rank_list(r, self.B)
+        if rs is not None:
+            r = self._take_ranks(rs, sparsity, w_update_ind, h_update_ind)
+        self.F, self.r, self.max_iter = int(F), int(r), int(max_iter)
         self.cost_check = 1 if cost_check else 0
+        if self.ranks is not None:
+            return self._init_ranks(ctx, beta, conv_eps, floor_v, sparsity, w_update_ind, h_update_ind)
         pd = dict(w_update_ind=w_update_ind, h_update_ind=h_update_ind)
         self._w_ind = _mask(pd, "w_update_ind", self.r)
         self._h_ind = _h_ind_all_or_none(pd, self.r)
@@ -231,20 +343,56 @@ class BatchPlan:
         if self._sarr is not None:
             _lib.check(self._lib.snmf_batch_set_sparsity_f64(self._h, _ptr(self._sarr)))
 
+    def _take_ranks(self, rs, sparsity, w_update_ind, h_update_ind):
+        """r given as a sequence -> the rank the handle is made with.  Where the engine takes a rank per problem and the settings
+        allow it, self.ranks is set (and the largest returned); equal ranks are otherwise that rank; differing ones are refused."""
+        equal = len(set(rs)) == 1
+        if self._create_ranks is None:
+            if not equal:
+                raise SnmfError(self._rank_status, f"r is {rs}: this batch shares the rank (a rank per problem: BatchPlan64)")
+            return rs[0]
+        try:
+            _mixed_rank_rules(sparsity, dict(w_update_ind=w_update_ind, h_update_ind=h_update_ind))
+        except SnmfError:
+            if not equal:
+                raise
+            return rs[0]  # equal ranks with an r-vector: the int form
+        self.ranks = rs
+        return max(rs)
+
+    def _init_ranks(self, ctx, beta, conv_eps, floor_v, sparsity, w_update_ind, h_update_ind):
+        scalar, on = _mixed_rank_rules(sparsity, dict(w_update_ind=w_update_ind, h_update_ind=h_update_ind))
+        self._sarr = None
+        self._w_ind = np.full(self.r, on["w_update_ind"], np.uint8)
+        self._h_ind = np.full(self.r, on["h_update_ind"], np.uint8)
+        sp = _make_params(self.F, 1, self.r, beta, self.max_iter, conv_eps, self.cost_check, floor_v, 0, scalar, self._w_ind, self._h_ind)
+        self._rk = np.array(self.ranks, np.int32)
+        self._lib = _lib.load()
+        self.ctx = ctx or default_context()
+        h = C.c_void_p()
+        _lib.check(getattr(self._lib, self._create_ranks)(self.ctx._h, C.byref(sp), self.B, _ptr(self.Ts), _ptr(self._rk), C.byref(h)))
+        self._h = h
+        self.ctx._plans.add(self)
+
+    def rank(self, k):
+        """The rank of problem k."""
+        return self.r if self.ranks is None else self.ranks[k]
+
     def set_problem(self, k, v, w0, h0):
         k = int(k)
         if not 0 <= k < self.B:
             raise SnmfError(1, f"problem index {k} outside [0, {self.B})")
         v = np.asarray(v)
         dt = np.dtype(np.float32) if v.dtype == np.float32 else np.dtype(np.float64)
-        T = int(self.Ts[k])
+        T, r = int(self.Ts[k]), self.rank(k)
         if v.shape != (self.F, T):
             raise SnmfError(3, f"v is {v.shape}, problem {k} is ({self.F}, {T})")
         w0, h0 = np.asarray(w0), np.asarray(h0)
-        if w0.shape != (self.F, self.r):
-            raise SnmfError(3, f"init_w is {w0.shape}, v has {self.F} rows")
-        if h0.shape != (self.r, T):
-            raise SnmfError(3, f"init_h is {h0.shape}, expected ({self.r}, {T})")
+        if w0.shape != (self.F, r):
+            raise SnmfError(3, f"init_w is {w0.shape}, problem {k} is ({self.F}, {r})" if self.ranks is not None
+                            else f"init_w is {w0.shape}, v has {self.F} rows")
+        if h0.shape != (r, T):
+            raise SnmfError(3, f"init_h is {h0.shape}, expected ({r}, {T})")
         vv = _colmajor(v, dt)
         w0 = np.asfortranarray(w0, dtype=dt)
         h0 = np.asfortranarray(h0, dtype=dt)
@@ -256,18 +404,21 @@ class BatchPlan:
         _lib.check(self._lib.snmf_batch_run(self._h, 0 if n_iters is None else int(n_iters)))
 
     def get(self, k, dtype=np.float64):
+        W, H, div, cost, ni = self._get(k, np.dtype(dtype))
+        return W, H, _objective(div, cost, ni, self.max_iter, self.cost_check)
+
+    def _get(self, k, dt):
         k = int(k)
         if not 0 <= k < self.B:
             raise SnmfError(1, f"problem index {k} outside [0, {self.B})")
-        dt = np.dtype(dtype)
-        W = np.empty((self.F, self.r), dtype=dt, order="F")
-        H = np.empty((self.r, int(self.Ts[k])), dtype=dt, order="F")
+        W = np.empty((self.F, self.rank(k)), dtype=dt, order="F")
+        H = np.empty((self.rank(k), int(self.Ts[k])), dtype=dt, order="F")
         nh = max(self.max_iter, 1)
         div, cost = np.zeros(nh), np.zeros(nh)
         ni = C.c_int32()
         fn = self._lib.snmf_batch_get_f64 if dt == np.float64 else self._lib.snmf_batch_get_f32
         _lib.check(fn(self._h, k, _ptr(W), _ptr(H), _ptr(div), _ptr(cost), C.byref(ni)))
-        return W, H, _objective(div, cost, ni.value, self.max_iter, self.cost_check)
+        return W, H, div, cost, ni.value
 
     def describe(self):
         buf = C.create_string_buffer(1024)
@@ -290,9 +441,15 @@ class BatchPlan:
 class BatchPlan64(BatchPlan):
     """BatchPlan in the fp64 mode (snmf_batch_create_fp64): the same methods and call order; every problem's results are bit
     for bit those of sparse_nmf(..., precision="fp64") on it alone.  float32 arrays given to set_problem are widened,
-    get(dtype=np.float32) rounds the fp64 results; describe() gives the tables, the grids, the launches per iteration and the bytes."""
+    get(dtype=np.float32) rounds the fp64 results; describe() gives the tables, the grids, the launches per iteration and the bytes.
+    r may be a sequence of len(Ts): a rank per problem (snmf_batch_create_ranks_fp64).  set_problem(k, ...) then takes init_w
+    F x r[k] and init_h r[k] x Ts[k], get(k) returns those shapes, .ranks holds the list (.r its largest entry) and describe()
+    names the ranks.  Such a batch takes a scalar sparsity and masks that are absent, a bool, all ones or all zeros; with
+    differing ranks anything else is SnmfError status 8, while a sequence of equal ranks with a vector sparsity or a partial
+    mask is the int form.  An int for r is snmf_batch_create_fp64, as before."""
 
     _create = "snmf_batch_create_fp64"
+    _create_ranks = "snmf_batch_create_ranks_fp64"
 
     def __init__(self, ctx, F, r, Ts, *, beta=1.0, max_iter=100, conv_eps=0.0, cost_check=True, floor_v=True, sparsity=0.0,
                  w_update_ind=None, h_update_ind=None):
@@ -393,6 +550,8 @@ class BatchPlanMdi64(BatchPlan64):
     of snmf_mdi / snmf_mdi_Sm(..., precision="fp64") on it alone.  floor_v has no meaning here (the masked start floors)."""
 
     _create = "snmf_batch_create_mdi_fp64"
+    _create_ranks = None  # a missing-data batch shares the rank
+    _rank_status = 8
 
     def set_problem(self, k, v, mask, w0, h0):
         k = int(k)

@@ -1,9 +1,11 @@
 // ============================================================================================
-// The batched offline solve in the fp64 mode (snmf_batch_create_fp64): B independent problems of one (F, r) and one
-// settings struct, each the fp64 solve of snmf_solve64.h, in SHARED launches.  The arrays of a problem are the single
-// solve's -- tight, column-major, nothing padded, 64-bit offsets -- and the problems lie one behind the other along the
-// frames: V, Lam, R, D are F x sum(T_b), H, Num, Den r x sum(T_b), W, Q, P F x r per problem, and every problem has its
-// own column norms, column sums, row-sum partials, objective partials, objective history and Solve64State.
+// The batched offline solve in the fp64 mode (snmf_batch_create_fp64, snmf_batch_create_ranks_fp64): B independent problems of
+// one F and one settings struct, each with a frame count T_b and a rank r_b of its own (one r for all on a handle made without
+// ranks), each the fp64 solve of snmf_solve64.h, in SHARED launches.  The arrays of a problem are the single solve's -- tight,
+// column-major, nothing padded, 64-bit offsets -- and the problems lie one behind the other: V, Lam, R, D are F x sum(T_b);
+// H, Num, Den are the r_b x T_b matrices packed at sum(r_j T_j); W, Q, P the F x r_b matrices packed at F sum(r_j); the column
+// norms, column sums and row sums r_b entries at sum(r_j); and every problem has its own row-sum partials, objective partials,
+// objective history and Solve64State.  The offsets are prefix sums kept per problem (B64Prob): no kernel multiplies by "the" r.
 // Every kernel here is a grid of the single solve's workgroups with one more index, the problem: it finds the problem's
 // arrays and calls the __device__ body the single solve's kernel calls (snmf_solve64.h), with the workgroup index and the
 // grid size that kernel would have had.  So every element, every partial sum and every tree is formed by the same
@@ -20,8 +22,12 @@ namespace snmf {
 struct B64Prob {
     int T;          // frames of this problem
     int n_rowz;     // its row-sum chunks of kS64RowChunk frames
+    int r;          // its rank
     long long fr0;  // frames of the problems before it
     long long rz0;  // row-sum chunks of the problems before it
+    long long h0;   // H elements of the problems before it: sum r_j T_j
+    long long w0;   // W columns of the problems before it: sum r_j
+    long long sp0;  // row-sum partials of the problems before it: sum r_j n_rowz_j
 };
 
 // one workgroup of a grouped product: problem, 64 x 64 tile of that problem's product, split
@@ -39,7 +45,7 @@ struct B64Sum {
 };
 
 struct B64Args {
-    int F, r, kind, max_iter;
+    int F, r, kind, max_iter;  // r: the largest rank (the rank, on a uniform batch)
     double scalar, beta, conv_eps, div_scale;
     const B64Prob* prob;
     const double* S;  // r-vector sparsity (kind 1)
@@ -83,7 +89,8 @@ __global__ __launch_bounds__(256) void k_b64_ratio(B64Args a) {
 }
 
 // grid (workgroups, B): H0 of problem b of batch `a` (tight a.r x T_b) from rows [row0, row0 + a.r) of the H of another batch with
-// the same frame counts (tight r_src x T_b at the same frame offset); consecutive lanes run along k within a frame
+// the same frame counts (tight r_src x T_b at the same frame offset); consecutive lanes run along k within a frame.  Both batches
+// have one rank for all problems (the host refuses the call on a batch with ranks), so h0 = fr0 * r in each.
 static __global__ __launch_bounds__(256) void k_b64_take_h(B64Args a, const double* __restrict__ Hsrc, int r_src, int row0) {
     const B64Prob p = a.prob[blockIdx.y];
     const double* __restrict__ S = Hsrc + p.fr0 * r_src + row0;
@@ -96,30 +103,30 @@ static __global__ __launch_bounds__(256) void k_b64_take_h(B64Args a, const doub
     }
 }
 
-// grid (workgroups, B): init_w of problem b = V_b(:, idx[b * r + k]), k < r (run_basis_train.m:82-83; k_gather64 per problem):
-// columns of the problem's own tight V block into its tight F x r W.  idx: 0-based, on the device; an index outside [0, T_b)
-// (the host refuses it) gives a zero column, never a read outside the block.
+// grid (workgroups, B): init_w of problem b = V_b(:, idx[w0_b + k]), k < r_b (run_basis_train.m:82-83; k_gather64 per problem):
+// columns of the problem's own tight V block into its tight F x r_b W.  idx: 0-based, on the device, the problems' r_b entries
+// packed one behind the other; an index outside [0, T_b) (the host refuses it) gives a zero column, never a read outside the block.
 static __global__ __launch_bounds__(256) void k_b64_take_w(B64Args a, const int64_t* __restrict__ idx) {
     const int b = blockIdx.y;
     const B64Prob p = a.prob[b];
     const double* __restrict__ V = a.V + p.fr0 * a.F;
-    double* __restrict__ W = a.W + (long long)b * a.F * a.r;
-    const long long n = (long long)a.F * a.r;
+    double* __restrict__ W = a.W + p.w0 * a.F;
+    const long long n = (long long)a.F * p.r;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
         const long long k = i / a.F, f = i - k * a.F;
-        const long long t = idx[(long long)b * a.r + k];
+        const long long t = idx[p.w0 + k];
         W[i] = (t >= 0 && t < p.T) ? V[t * a.F + f] : 0.0;
     }
 }
 
-// grid (workgroups, B): H0 of problem b drawn on the device: H[e] = u(e), e the element index in the tight column-major a.r x T_b
+// grid (workgroups, B): H0 of problem b drawn on the device: H[e] = u(e), e the element index in the tight column-major r_b x T_b
 // matrix -- k_rand64 (snmf_frontend64.h) per problem, keyed by seed[b].  draw[b] == 0: the problem's H0 came from the host.
 static __global__ __launch_bounds__(256) void k_b64_rand_h(B64Args a, const uint64_t* __restrict__ seed, const uint8_t* __restrict__ draw) {
     const int b = blockIdx.y;
     if (!draw[b]) return;
     const B64Prob p = a.prob[b];
-    const uint64_t sd = seed[b], n = (uint64_t)a.r * (uint64_t)p.T, n4 = (n + 3) / 4;
-    double* __restrict__ H = a.H + p.fr0 * a.r;
+    const uint64_t sd = seed[b], n = (uint64_t)p.r * (uint64_t)p.T, n4 = (n + 3) / 4;
+    double* __restrict__ H = a.H + p.h0;
     for (uint64_t q = (uint64_t)blockIdx.x * 256 + threadIdx.x; q < n4; q += (uint64_t)gridDim.x * 256) {
         uint32_t o[4];
         philox4x32_10((uint32_t)q, (uint32_t)(q >> 32), 0u, 0u, (uint32_t)sd, (uint32_t)(sd >> 32), o);
@@ -136,37 +143,41 @@ __global__ __launch_bounds__(256) void k_b64_hupd(B64Args a) {
     const int b = blockIdx.y;
     if (a.st[b].stop) return;
     const B64Prob p = a.prob[b];
-    const long long o = p.fr0 * a.r;
-    s64_hupd_span<KL>(a.H + o, a.Num + o, KL ? nullptr : a.Den + o, KL ? a.cs + (long long)b * a.r : nullptr, a.kind, a.scalar, a.S, a.r,
-                      (long long)a.r * p.T, blockIdx.x, gridDim.x);
+    const long long o = p.h0;
+    s64_hupd_span<KL>(a.H + o, a.Num + o, KL ? nullptr : a.Den + o, KL ? a.cs + p.w0 : nullptr, a.kind, a.scalar, a.S, p.r,
+                      (long long)p.r * p.T, blockIdx.x, gridDim.x);
 }
 
 // ---- reductions: the single solve's partition per problem
-// grid (r, B): column sums of W_b
+// grid (the largest r, B): column sums of W_b; the workgroups past the problem's own r_b columns return
 static __global__ __launch_bounds__(256) void k_b64_colsum(B64Args a) {
     const int b = blockIdx.y;
     if (a.st[b].stop) return;
+    const B64Prob p = a.prob[b];
+    if ((int)blockIdx.x >= p.r) return;
     __shared__ double red[256];
-    s64_colsum_col(a.W + (long long)b * a.F * a.r, a.F, a.cs + (long long)b * a.r, (int)blockIdx.x, red);
+    s64_colsum_col(a.W + p.w0 * a.F, a.F, a.cs + p.w0, (int)blockIdx.x, red);
 }
 
-// grid (ceil(r / 256), the largest chunk count, B): the row-sum partials of H_b; k_b64_sumz adds them
+// grid (ceil(the largest r / 256), the largest chunk count, B): the row-sum partials of H_b; k_b64_sumz adds them
 static __global__ __launch_bounds__(256) void k_b64_rowsum(B64Args a) {
     const int b = blockIdx.z;
     if (a.st[b].stop) return;
     const B64Prob p = a.prob[b];
     if ((int)blockIdx.y >= p.n_rowz) return;
-    s64_rowsum_chunk(a.H + p.fr0 * a.r, a.r, p.T, kS64RowChunk, a.sp + p.rz0 * a.r, (int)blockIdx.y, blockIdx.x, gridDim.x);
+    s64_rowsum_chunk(a.H + p.h0, p.r, p.T, kS64RowChunk, a.sp + p.sp0, (int)blockIdx.y, blockIdx.x, gridDim.x);
 }
 
-// grid (r, B): the W epilogue of problem b, column k
+// grid (the largest r, B): the W epilogue of problem b, column k < r_b (w_ind: one mask for all problems; with ranks it is uniform)
 template <bool KL>
 __global__ __launch_bounds__(256) void k_b64_wupd(B64Args a) {
     const int b = blockIdx.y;
     if (a.st[b].stop) return;
+    const B64Prob p = a.prob[b];
+    if ((int)blockIdx.x >= p.r) return;
     __shared__ double red[256];
-    const long long o = (long long)b * a.F * a.r;
-    s64_wupd_col<KL, true>(a.W + o, a.Q + o, KL ? nullptr : a.P + o, KL ? a.hs + (long long)b * a.r : nullptr, a.w_ind, a.F, nullptr,
+    const long long o = p.w0 * a.F;
+    s64_wupd_col<KL, true>(a.W + o, a.Q + o, KL ? nullptr : a.P + o, KL ? a.hs + p.w0 : nullptr, a.w_ind, a.F, nullptr,
                            (int)blockIdx.x, red);
 }
 
@@ -178,8 +189,8 @@ __global__ __launch_bounds__(256) void k_b64_obj(B64Args a) {
     __shared__ double red[256];
     const B64Prob p = a.prob[b];
     const long long o = p.fr0 * a.F;
-    s64_obj_block<MODE>(a.V + o, a.Lam + o, (long long)a.F * p.T, a.beta, a.H + p.fr0 * a.r, a.kind, a.scalar, a.S, a.r,
-                        (long long)a.r * p.T, a.part + (long long)b * 2 * kS64Blocks, red, blockIdx.x, gridDim.x);
+    s64_obj_block<MODE>(a.V + o, a.Lam + o, (long long)a.F * p.T, a.beta, a.H + p.h0, a.kind, a.scalar, a.S, p.r,
+                        (long long)p.r * p.T, a.part + (long long)b * 2 * kS64Blocks, red, blockIdx.x, gridDim.x);
 }
 
 // ---- the missing-data steps of a masked batch (snmf_batch_create_mdi_fp64): the bodies of k_s64_mdi_impute / k_s64_mdi_obj
@@ -200,8 +211,8 @@ __global__ __launch_bounds__(256) void k_b64_mdi_obj(B64Args a) {
     __shared__ double red[256];
     const B64Prob p = a.prob[b];
     const long long o = p.fr0 * a.F;
-    s64_mdi_obj_block<MODE>(a.V + o, a.M + o, a.Lam + o, (long long)a.F * p.T, a.beta, a.H + p.fr0 * a.r, a.kind, a.scalar, a.S, a.r,
-                            (long long)a.r * p.T, a.part + (long long)b * 2 * kS64Blocks, red, blockIdx.x, gridDim.x);
+    s64_mdi_obj_block<MODE>(a.V + o, a.M + o, a.Lam + o, (long long)a.F * p.T, a.beta, a.H + p.h0, a.kind, a.scalar, a.S, p.r,
+                            (long long)p.r * p.T, a.part + (long long)b * 2 * kS64Blocks, red, blockIdx.x, gridDim.x);
 }
 
 // grid (B): the fixed tree over problem b's partials, its objective vectors and its stop test (src/sparse_nmf.m:272-284);

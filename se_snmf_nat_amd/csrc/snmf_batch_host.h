@@ -8,6 +8,9 @@
 // A handle made by snmf_batch_create_mdi_fp64 is a batch of missing-data solves (`masked`): its problems are set together with
 // their masks (batch_set_problem_mdi), and the imputed V of a problem can be read (batch_get_v_mdi); everything else -- run, get,
 // describe, destroy, the new batch on a used handle -- is the life below, unchanged.
+// A handle made by snmf_batch_create_ranks_fp64 carries a rank per problem (`ranks`): problem k's W is F x ranks[k] and its H
+// ranks[k] x T_k wherever a call below says r; p.r is the largest of them.  The life is the same; what such a handle refuses
+// (batch_create, take_h0) it refuses before any device work.
 #pragma once
 #include <functional>
 #include <memory>
@@ -19,6 +22,8 @@ struct snmf_batch {
     snmf_ctx* ctx = nullptr;
     snmf_params p{};  // (its mask pointers are cleared: upd_h, upd_w and w_ind are their reading)
     int B = 0;
+    std::vector<int32_t> ranks;  // one rank per problem; empty: every problem has p.r
+    int rank_of(int k) const { return ranks.empty() ? p.r : ranks[k]; }
     bool upd_h = true, upd_w = true;
     std::vector<uint8_t> w_ind;
     std::vector<uint8_t> have;
@@ -44,7 +49,8 @@ struct snmf_batch {
     // been taken on the device, through take_w0, and H0 is scaled by the norms that left
     virtual int load(int k, const double* V, int64_t ldV, const double* W0, const double* H0) = 0;
     virtual int load(int k, const float* V, int64_t ldV, const float* W0, const float* H0) = 0;
-    // init_w of every problem = the columns idx[k * r .. k * r + r) (0-based, host) of the problem's own V block, as it lies there
+    // init_w of every problem = its rank_of(k) columns of idx (0-based, host; the problems' entries packed one behind the other,
+    // k * r .. k * r + r on a uniform batch) of the problem's own V block, as it lies there
     // when the call is made (between v_blocks and v_written: the unfloored V), gathered by one launch over all problems; then,
     // with unit_columns, the initial scaling load() runs after its W0 upload (:157-158), so that the state is that of
     // load(k, nullptr, ld, W0, nullptr) with the same values.  Without unit_columns the gathered columns stay as they are and
@@ -101,16 +107,37 @@ snmf_batch* batch32_new();                     // snmf_tu_batch.hip: an fp32 eng
     HIP_TRY(hipSetDevice((b)->ctx->device))
 
 // Takes the engine `b` over (a failure deletes it).  entry: the C entry's name, for the messages.  Every refusal here and the
-// engine's own limits come before the device is touched.
+// engine's own limits come before the device is touched.  with_ranks: r holds a rank per problem (p_in->r is the largest); such a
+// batch takes a scalar sparsity and masks that are all ones or all zeros, and has no missing-data form.
 inline int batch_create(const char* entry, snmf_batch* b, snmf_ctx* ctx, const snmf_params* p_in, int32_t n_problems, const int32_t* T,
-                        snmf_batch** out) {
+                        snmf_batch** out, bool with_ranks = false, const int32_t* r = nullptr) {
     std::unique_ptr<snmf_batch> own(b);
-    if (!ctx || !p_in || !T || !out) return fail(SNMF_ERR_INVALID, "%s: NULL argument", entry);
+    if (!ctx || !p_in || !T || !out || (with_ranks && !r)) return fail(SNMF_ERR_INVALID, "%s: NULL argument", entry);
     *out = nullptr;
     if (n_problems < 1) return fail(SNMF_ERR_INVALID, "%s: n_problems must be at least 1 (got %d)", entry, n_problems);
     b->p = *p_in;
     b->p.T = 1;  // (ignored: every problem brings its own)
     SN_TRY(validate_params(&b->p));
+    if (with_ranks) {
+        int r_max = 0;
+        for (int i = 0; i < n_problems; ++i) {
+            if (r[i] < 1) return fail(SNMF_ERR_INVALID, "%s: problem %d has rank %d (at least 1)", entry, i, r[i]);
+            r_max = std::max(r_max, (int)r[i]);
+        }
+        if (b->p.r != r_max) return fail(SNMF_ERR_DIM, "%s: params->r = %d must be the largest rank, %d", entry, b->p.r, r_max);
+        if (b->masked) return fail(SNMF_ERR_UNSUPPORTED, "%s: a missing-data batch has one rank for all problems", entry);
+        if (b->p.sparsity_kind != SNMF_SPARSITY_SCALAR)
+            return fail(SNMF_ERR_UNSUPPORTED, "%s: a batch with a rank per problem takes a scalar sparsity", entry);
+        for (int m = 0; m < 2; ++m) {
+            const uint8_t* ind = m ? b->p.h_update_ind : b->p.w_update_ind;
+            int n_on = 0;
+            for (int k = 0; ind && k < r_max; ++k) n_on += ind[k] != 0;
+            if (ind && n_on != 0 && n_on != r_max)
+                return fail(SNMF_ERR_UNSUPPORTED, "%s: a batch with a rank per problem takes a %s_update_ind of all ones or all zeros (%d of %d are set)",
+                            entry, m ? "h" : "w", n_on, r_max);
+        }
+        b->ranks.assign(r, r + n_problems);
+    }
     int n_h = 0, n_w = 0;
     b->w_ind.resize(b->p.r);
     SN_TRY(read_update_masks(&b->p, &n_h, &n_w, b->w_ind.data()));
@@ -362,7 +389,8 @@ int dnmf_batch(const char* entry, snmf_batch* (*make)(), snmf_ctx* ctx, const sn
 
 // ---- run_basis_train.m:58-91 for a batch of training signals (include/snmf.h: snmf_run_basis_train_audio_batch_*) -----------------
 // Two engines of one kind, made by `make`, over the same frame counts, both with every row and column updated (:85-86): the DFT
-// engine (p->F rows) and, with F_mel > 0, the Mel engine (F_mel rows), r = p->r = cluster_buff * R each.  `device_v` (the grouped
+// engine (p->F rows) and, with F_mel > 0, the Mel engine (F_mel rows), r = p->r = cluster_buff * R each -- or, with `ranks`, problem
+// k at ranks[k] = cluster_buff * R_k in both (p->r the largest).  `device_v` (the grouped
 // front-end of snmf_tu_frontend_batch.hip) writes TF_mag -- TF_DD applied where asked -- of every signal into the DFT engine's V
 // blocks and TF_Mel, projected from those blocks, into the Mel engine's; both engines then gather their exemplar columns from
 // the still unfloored V (the single entry's order, snmf_tu_dnmf.hip), run their floor, take the same H0 and solve.  Nothing
@@ -371,18 +399,19 @@ template <typename TT>
 struct TrainInputs {
     // the features of every signal into `dft` and, unless it is empty, `mel`: blocks of `elem`-byte entries
     std::function<int(const std::vector<snmf_batch::VBlock>& dft, const std::vector<snmf_batch::VBlock>& mel, size_t elem)> device_v;
-    const int64_t* idx = nullptr;    // n * p->r exemplar columns, 0-based, checked by the caller
+    const int64_t* idx = nullptr;    // the exemplar columns of every problem, packed (n * p->r without ranks), 0-based, checked by the caller
     bool exemplar = false;           // train_Exemplar (:84, :93-96): the exemplars are the dictionaries and nothing is solved
     const TT* const* H0 = nullptr;   // may be nullptr, or hold nullptr entries: drawn on the device from seed[k]
     const uint64_t* seed = nullptr;
 };
 
-// B_DFT_k F x r, B_Mel_k F_mel x r, A_*_k r x T[k], tight and column-major (A_DFT, A_Mel, or single entries of them, may be NULL);
+// B_DFT_k F x r, B_Mel_k F_mel x r, A_*_k r x T[k] (r: the problem's own with ranks), tight and column-major (A_DFT, A_Mel, or single entries of them, may be NULL);
 // n_iter: NULL or 2 per problem.  The masks of p are ignored.  Every refusal comes before the device is touched; the caller has
 // checked `in` and the pointers.
 template <typename TT>
 int train_batch_run(const char* entry, snmf_batch* (*make)(), snmf_ctx* ctx, const snmf_params* p, int32_t F_mel, int32_t n, const int32_t* T,
-                    const TrainInputs<TT>& in, TT* const* B_DFT, TT* const* A_DFT, TT* const* B_Mel, TT* const* A_Mel, int32_t* n_iter) {
+                    const TrainInputs<TT>& in, TT* const* B_DFT, TT* const* A_DFT, TT* const* B_Mel, TT* const* A_Mel, int32_t* n_iter,
+                    const int32_t* ranks = nullptr) {
     snmf_params q = *p;
     q.w_update_ind = q.h_update_ind = nullptr;
     if (F_mel > 0) {  // the Mel engine's limits before the DFT engine allocates
@@ -392,10 +421,10 @@ int train_batch_run(const char* entry, snmf_batch* (*make)(), snmf_ctx* ctx, con
         SN_TRY(probe->check_shape());
     }
     BatchOwner ed, em;
-    SN_TRY(batch_create(entry, make(), ctx, &q, n, T, &ed.b));
+    SN_TRY(batch_create(entry, make(), ctx, &q, n, T, &ed.b, ranks != nullptr, ranks));
     if (F_mel > 0) {
         q.F = F_mel;
-        SN_TRY(batch_create(entry, make(), ctx, &q, n, T, &em.b));
+        SN_TRY(batch_create(entry, make(), ctx, &q, n, T, &em.b, ranks != nullptr, ranks));
     }
     snmf_batch* const eng[2] = {ed.b, em.b};
     const int n_eng = em.b ? 2 : 1;

@@ -76,6 +76,8 @@ int Batch32::reset() {
 
 int Batch32::build(const int32_t* T) {
     const int F = p.F, r = p.r, n_problems = B;
+    if (!ranks.empty())  // (the LDS geometry nk, nqk, S, nkg of this engine is one per launch; no entry leads here)
+        return fail(SNMF_ERR_UNSUPPORTED, "the fp32 batch engine has one rank for all problems (a rank per problem: snmf_batch_create_ranks_fp64)");
     long long tiles = 0, chunks = 0;
     for (int i = 0; i < n_problems; ++i) {
         const long long nt = (T[i] + 31) / 32;
@@ -431,6 +433,10 @@ extern "C" int snmf_batch_create(snmf_ctx* ctx, const snmf_params* p, int32_t n_
 }
 extern "C" int snmf_batch_create_fp64(snmf_ctx* ctx, const snmf_params* p, int32_t n_problems, const int32_t* T, snmf_batch** out) {
     return batch_create("snmf_batch_create_fp64", batch64_new(), ctx, p, n_problems, T, out);
+}
+extern "C" int snmf_batch_create_ranks_fp64(snmf_ctx* ctx, const snmf_params* p, int32_t n_problems, const int32_t* T, const int32_t* r,
+                                            snmf_batch** out) {
+    return batch_create("snmf_batch_create_ranks_fp64", batch64_new(), ctx, p, n_problems, T, out, true, r);
 }
 extern "C" int snmf_batch_create_mdi_fp64(snmf_ctx* ctx, const snmf_params* p, int32_t n_problems, const int32_t* T, snmf_batch** out) {
     return batch_create("snmf_batch_create_mdi_fp64", batch64_new(true), ctx, p, n_problems, T, out);

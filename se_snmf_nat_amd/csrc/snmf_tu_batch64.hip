@@ -7,6 +7,9 @@
 // block for the masks, the masked start when a problem is set, the grouped re-imputation (fused with the objective when there is
 // one) at the end of an iteration, and the gain-matched final imputation into a scratch block when v_MDI is read.  Without masks
 // nothing of this is allocated or launched.
+// With a rank per problem (snmf_batch_create_ranks_fp64) nothing else is launched either: the tables are built from r_i where they
+// were built from r, the packed arrays are sized by the sums of r_i and r_i T_i, and the grids that count columns or rows of a
+// rank-sized matrix are sized for the largest rank.
 #include "snmf_internal.h"
 #include "snmf_batch64.h"
 #include "snmf_batch_host.h"
@@ -36,7 +39,8 @@ struct Batch64 final : snmf_batch {
     std::vector<B64Prob> prob;
     std::vector<long long> z0;  // first double of each problem's split partials
     long long sumT = 0, sumRz = 0, sumZ = 0;
-    int maxT = 0, max_rowz = 0;
+    long long sumR = 0, sumRT = 0, sumSp = 0;  // columns of W, elements of H, row-sum partials of all problems
+    int maxT = 0, max_rowz = 0, min_r = 0;
     B64Args a{};
     double* S = nullptr;
     double* zbuf = nullptr;
@@ -94,7 +98,7 @@ struct Batch64 final : snmf_batch {
 // the walk over the device block (the same for measuring and for carving)
 size_t carve(Batch64* s, void* base) {
     const snmf_params& p = s->p;
-    const size_t F = p.F, r = p.r, nB = s->B, sT = (size_t)s->sumT;
+    const size_t F = p.F, r = p.r, nB = s->B, sT = (size_t)s->sumT, sR = (size_t)s->sumR, sRT = (size_t)s->sumRT;
     const bool kl = s->mode == S64_KL, ed = s->mode == S64_ED;
     B64Args& a = s->a;
     Carve64 c(base);
@@ -108,24 +112,24 @@ size_t carve(Batch64* s, void* base) {
     a.M = s->Mblk;
     a.R = ed ? nullptr : c.get<double>(F * sT);
     a.D = (ed || kl) ? nullptr : c.get<double>(F * sT);
-    a.H = c.get<double>(r * sT);
-    a.W = c.get<double>(nB * F * r);
+    a.H = c.get<double>(sRT);
+    a.W = c.get<double>(F * sR);
     a.Num = a.Den = a.cs = a.Q = a.P = a.hs = a.sp = nullptr;
     if (s->upd_h) {
-        a.Num = c.get<double>(r * sT);
-        if (!kl) a.Den = c.get<double>(r * sT);
-        else a.cs = c.get<double>(nB * r);
+        a.Num = c.get<double>(sRT);
+        if (!kl) a.Den = c.get<double>(sRT);
+        else a.cs = c.get<double>(sR);
     }
     if (s->upd_w) {
-        a.Q = c.get<double>(nB * F * r);
-        if (!kl) a.P = c.get<double>(nB * F * r);
+        a.Q = c.get<double>(F * sR);
+        if (!kl) a.P = c.get<double>(F * sR);
         else {
-            a.hs = c.get<double>(nB * r);
-            a.sp = c.get<double>((size_t)s->sumRz * r);
+            a.hs = c.get<double>(sR);
+            a.sp = c.get<double>((size_t)s->sumSp);
         }
     }
     s->zbuf = s->sumZ ? c.get<double>((size_t)s->sumZ) : nullptr;
-    a.wn = c.get<double>(nB * r);
+    a.wn = c.get<double>(sR);
     a.part = c.get<double>(nB * 2 * kS64Blocks);
     a.divh = c.get<double>(nB * a.max_iter);
     a.costh = c.get<double>(nB * a.max_iter);
@@ -178,24 +182,34 @@ int Batch64::reset() {
 
 // Checks the grid and memory limits before anything is allocated, then allocates and builds the tables.
 int Batch64::build(const int32_t* T) {
-    const int F = p.F, r = p.r, n_problems = B;
+    const int F = p.F, n_problems = B;
     if (n_problems > kGridYMax)
         return fail(SNMF_ERR_UNSUPPORTED, "%d problems are above the fp64 batch's limit of %d (a launch grid's second dimension)", n_problems,
                     kGridYMax);
     mode = p.beta == 1.0 ? S64_KL : (p.beta == 2.0 ? S64_ED : (p.beta == 0.0 ? S64_IS : S64_GEN));
     const bool kl = mode == S64_KL, ed = mode == S64_ED;
 
-    // ---- sizes, from the frame counts alone
+    // ---- sizes, from the frame counts and the ranks alone
     prob.resize(n_problems);
     z0.resize(n_problems);
+    min_r = rank_of(0);
     for (int i = 0; i < n_problems; ++i) {
         B64Prob& q = prob[i];
+        const int r = rank_of(i);
         q.T = T[i];
         q.n_rowz = (T[i] + kS64RowChunk - 1) / kS64RowChunk;
+        q.r = r;
         q.fr0 = sumT;
         q.rz0 = sumRz;
+        q.h0 = sumRT;
+        q.w0 = sumR;
+        q.sp0 = sumSp;
         sumT += T[i];
         sumRz += q.n_rowz;
+        sumRT += (long long)r * T[i];
+        sumR += r;
+        sumSp += (long long)r * q.n_rowz;
+        min_r = std::min(min_r, r);
         maxT = std::max(maxT, T[i]);
         max_rowz = std::max(max_rowz, q.n_rowz);
         fLam.n += tiles_of(F, T[i]) * n_splits(r, kS64ChunkK);
@@ -215,7 +229,7 @@ int Batch64::build(const int32_t* T) {
     if (max_rowz > kGridYMax)
         return fail(SNMF_ERR_UNSUPPORTED, "T = %d frames give %d row-sum chunks, above the launch grid's limit of %d", maxT, max_rowz,
                     kGridYMax);
-    a.F = F, a.r = r;
+    a.F = F, a.r = p.r;
     a.kind = p.sparsity_kind;
     a.max_iter = std::max(1, p.max_iter);
     a.scalar = p.sparsity_scalar;
@@ -263,8 +277,8 @@ int Batch64::build(const int32_t* T) {
     size_t atLam = 0, atH = 0, atW = 0;
     for (int i = 0; i < n_problems; ++i) {
         const B64Prob& q = prob[i];
-        const int Ti = q.T;
-        const long long oFT = q.fr0 * F, oRT = q.fr0 * r, oFR = (long long)i * F * r;
+        const int Ti = q.T, r = q.r;
+        const long long oFT = q.fr0 * F, oRT = q.h0, oFR = q.w0 * F;
         double* zb = zbuf ? zbuf + z0[i] : nullptr;
         const int* stop = &a.st[i].stop;
         double *W = a.W + oFR, *H = a.H + oRT;
@@ -290,7 +304,7 @@ int Batch64::build(const int32_t* T) {
                 s64_gemm_plan(&gP[i], Dm + oFT, 1, F, H, r, 1, a.P + oFR, 1, F, F, r, Ti, false, zb, stop);
                 split_entry(uP, pP, zb, nz, a.P + oFR, 1, F, F, r, false, stop);
             } else {  // the row sums of H: k_s64_sumz(dsp, n_rowz, r, r, dhs, 1, 0, 0) of the single solve
-                uRow.push_back(B64Sum{a.sp + q.rz0 * r, a.hs + (long long)i * r, (long long)r, 1, 0, q.n_rowz, r, 0, stop});
+                uRow.push_back(B64Sum{a.sp + q.sp0, a.hs + q.w0, (long long)r, 1, 0, q.n_rowz, r, 0, stop});
             }
         }
     }
@@ -309,7 +323,7 @@ int Batch64::build(const int32_t* T) {
         up(pr.sums, u.data(), sizeof(B64Sum) * u.size());
     };
     up(dprob, prob.data(), sizeof(B64Prob) * (size_t)n_problems);
-    up(dwi, w_ind.data(), (size_t)r);
+    up(dwi, w_ind.data(), (size_t)p.r);
     up(fLam.tiles, tLam.data(), sizeof(B64Tile) * tLam.size());
     if (fH.tiles) up(fH.tiles, tH.data(), sizeof(B64Tile) * tH.size());
     if (fW.tiles) up(fW.tiles, tW.data(), sizeof(B64Tile) * tW.size());
@@ -345,9 +359,9 @@ int Batch64::upload_sparsity(const double* sparsity) {
 template <typename TT>
 int Batch64::load_t(int k, const TT* V, int64_t ldV, const TT* W0, const TT* H0, const TT* M, int64_t ldM) {
     const B64Prob& q = prob[k];
-    const int F = a.F, r = a.r, T = q.T;
+    const int F = a.F, r = q.r, T = q.T;
     const long long nFT = (long long)F * T;
-    double *dV = a.V + q.fr0 * F, *dH = a.H + q.fr0 * r, *dW = a.W + (long long)k * F * r, *dwn = a.wn + (long long)k * r;
+    double *dV = a.V + q.fr0 * F, *dH = a.H + q.h0, *dW = a.W + q.w0 * F, *dwn = a.wn + q.w0;
     hipStream_t st = ctx->stream;
     // (tight on the device; fp32 arrays are widened on the way in)
     if (!V && masked) return fail(SNMF_ERR_UNSUPPORTED, "a missing-data batch takes its V from the host");
@@ -372,8 +386,9 @@ int Batch64::load_t(int k, const TT* V, int64_t ldV, const TT* W0, const TT* H0,
 }
 
 int Batch64::scale_h0(int k) {  // :159-160, with the single solve's own kernel
-    const long long nRT = (long long)a.r * prob[k].T;
-    hipLaunchKernelGGL(k_s64_hscale, dim3(grid64(nRT)), dim3(256), 0, ctx->stream, a.H + prob[k].fr0 * a.r, a.wn + (long long)k * a.r, a.r, nRT);
+    const B64Prob& q = prob[k];
+    const long long nRT = (long long)q.r * q.T;
+    hipLaunchKernelGGL(k_s64_hscale, dim3(grid64(nRT)), dim3(256), 0, ctx->stream, a.H + q.h0, a.wn + q.w0, q.r, nRT);
     HIP_TRY(hipGetLastError());
     return SNMF_OK;
 }
@@ -385,6 +400,8 @@ int elem_grid(const Batch64* s, long long rows);
 int Batch64::take_h0(snmf_batch& src_, int row0) {
     const Batch64* src = dynamic_cast<const Batch64*>(&src_);
     if (!src || src == this) return fail(SNMF_ERR_INTERNAL, "take_h0: the source is not another fp64 batch engine");
+    if (!ranks.empty() || !src->ranks.empty())
+        return fail(SNMF_ERR_UNSUPPORTED, "take_h0: a batch with a rank per problem hands no activations over (the DNMF batches share their ranks)");
     if (!src->ran || src->ctx != ctx) return fail(SNMF_ERR_STATE, "take_h0: the source batch has not run on this context");
     if (row0 < 0 || row0 + a.r > src->a.r) return fail(SNMF_ERR_DIM, "take_h0: rows [%d, %d) of an H of %d rows", row0, row0 + a.r, src->a.r);
     if (src->B != B) return fail(SNMF_ERR_DIM, "take_h0: %d problems from a batch of %d", B, src->B);
@@ -407,7 +424,7 @@ int Batch64::take_w0(const int64_t* idx, bool unit_columns) {
             if (q) hipFree(q);
         }
     } tmp;
-    const size_t bytes = sizeof(int64_t) * (size_t)B * a.r;
+    const size_t bytes = sizeof(int64_t) * (size_t)sumR;
     {
         hipError_t e = hipMalloc(&tmp.q, bytes);
         if (e != hipSuccess) {
@@ -423,8 +440,8 @@ int Batch64::take_w0(const int64_t* idx, bool unit_columns) {
     HIP_TRY(hipGetLastError());
     if (unit_columns)
         for (int k = 0; k < B; ++k) {  // :157-158
-            hipLaunchKernelGGL((k_s64_wupd<true, false>), dim3(a.r), dim3(256), 0, st, a.W + (long long)k * a.F * a.r, nullptr, nullptr, nullptr,
-                               nullptr, a.F, a.wn + (long long)k * a.r, &a.st[k].stop);
+            hipLaunchKernelGGL((k_s64_wupd<true, false>), dim3(prob[k].r), dim3(256), 0, st, a.W + prob[k].w0 * a.F, nullptr, nullptr, nullptr,
+                               nullptr, a.F, a.wn + prob[k].w0, &a.st[k].stop);
             HIP_TRY(hipGetLastError());
         }
     HIP_TRY(hipStreamSynchronize(st));  // (the table is freed on return, and the caller's array may go)
@@ -574,8 +591,9 @@ int Batch64::iterate(int it) {
 template <typename TT>
 int Batch64::fetch_t(int k, TT* W, TT* H) {
     // (fp32 arrays receive the fp64 results rounded to nearest)
-    if (W) SN_TRY((xfer_unpack_out<TT, double>(ctx, a.W + (long long)k * a.F * a.r, a.F, a.F, a.r, W, a.F)));
-    if (H) SN_TRY((xfer_unpack_out<TT, double>(ctx, a.H + prob[k].fr0 * a.r, a.r, a.r, prob[k].T, H, a.r)));
+    const B64Prob& q = prob[k];
+    if (W) SN_TRY((xfer_unpack_out<TT, double>(ctx, a.W + q.w0 * a.F, a.F, a.F, q.r, W, a.F)));
+    if (H) SN_TRY((xfer_unpack_out<TT, double>(ctx, a.H + q.h0, q.r, q.r, q.T, H, q.r)));
     return SNMF_OK;
 }
 
@@ -605,6 +623,8 @@ void Batch64::describe(char* buf, size_t buflen) const {
              "launches_per_iter=%d bytes=%zu poll_every=%d",
              B, a.F, a.r, mn, (int)upd_h, (int)upd_w, sumT, kS64ChunkK, fLam.n, fH.n, fW.n, pLam.n_sums, pNum.n_sums, pQ.n_sums,
              sRow ? B : 0, ge, B, gh, B, a.r, B, (a.r + 255) / 256, max_rowz, B, masked ? "k_b64_mdi_obj" : "k_b64_obj", kS64Blocks, B, B, launches, bytes, kPollEvery);
+    if (!ranks.empty() && n > 0 && (size_t)n < buflen)  // (r above is the largest)
+        snprintf(buf + n, buflen - (size_t)n, " | ranks: min=%d max=%d sum=%lld h_elems=%lld", min_r, a.r, sumR, sumRT);
     if (masked && n > 0 && (size_t)n < buflen)  // (bytes above counts both blocks)
         snprintf(buf + n, buflen - (size_t)n, " | mdi: k_b64_mdi_impute grid=(%d,%d) mask_bytes=%zu v_mdi_scratch_bytes=%zu", ge, B,
                  mask_bytes, sizeof(double) * (size_t)a.F * (size_t)maxT);

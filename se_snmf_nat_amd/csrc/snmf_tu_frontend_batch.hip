@@ -5,6 +5,8 @@
 //   snmf_run_basis_dnmf_audio_batch_f64 / _fp64      run_basis_DNMF.m:1-55 (and its Mel twin) for n pairs of WAVEFORMS
 //   snmf_run_basis_train_audio_batch_f64 / _fp64     run_basis_train.m:58-91 for the training signals of n classes
 //   snmf_run_basis_train_signals_batch_f64 / _fp64   the same on the signals a snmf_train_signals handle holds in HBM
+//   snmf_run_basis_train_audio_batch_ranks_fp64, snmf_run_basis_train_signals_batch_ranks_fp64
+//                                                    the two fp64 training entries with a dictionary size per problem
 //
 // The DNMF entries are dnmf_batch_run of snmf_batch_host.h -- the three resident batches of snmf_run_basis_dnmf_batch_* -- with V
 // formed on the device: the truncated waveforms of every problem go up as ONE slab through the context's transfer pipeline
@@ -331,12 +333,14 @@ int dnmf_audio_batch(const char* entry, snmf_batch* (*make)(), snmf_ctx* ctx, co
 // ts != nullptr (snmf_run_basis_train_signals_batch_*): the signals are the handle's, resident in HBM as doubles; samples and
 // n_samples are not looked at, the lengths are the handle's and the sample slab is filled by one launch of k_sig_fill (a copy
 // for double, round to nearest for float) instead of the transfer.  Everything else is the same code.
+// n_atoms != nullptr (the _ranks_fp64 entries): problem k trains n_atoms[k] atoms -- sample_idx[k] holds that many indices, its
+// outputs have that many columns / rows -- and p->r is the largest; nullptr: p->r for every problem.
 template <typename S>
 int train_audio_batch(const char* entry, snmf_batch* (*make)(), snmf_ctx* ctx, const snmf_params* p, const snmf_stft_params* sp, double alpha_eta_dd,
                       const S* mel, int32_t mel_M, int32_t n, const S* const* samples, const int64_t* n_samples,
                       const int64_t* const* sample_idx, int32_t train_exemplar, const double* const* H0, const uint64_t* seed,
                       double* const* B_DFT, double* const* A_DFT, double* const* B_Mel, double* const* A_Mel, int32_t* n_iter,
-                      const snmf_train_signals* ts = nullptr) {
+                      const snmf_train_signals* ts = nullptr, const int32_t* n_atoms = nullptr) {
     if (!ctx || !p || (!ts && (!samples || !n_samples)) || !sample_idx || !B_DFT) return fail(SNMF_ERR_INVALID, "%s: NULL argument", entry);
     if (ts) {
         if (ts->ctx != ctx) return fail(SNMF_ERR_INVALID, "%s: the signals were assembled on another context", entry);
@@ -345,6 +349,14 @@ int train_audio_batch(const char* entry, snmf_batch* (*make)(), snmf_ctx* ctx, c
     }
     SN_TRY(check_batch_size(entry, n, "n_problems"));
     SN_TRY(validate_stft(sp));
+    if (n_atoms) {
+        int r_max = 0;
+        for (int k = 0; k < n; ++k) {
+            if (n_atoms[k] < 1) return fail(SNMF_ERR_INVALID, "%s: problem %d has n_atoms = %d (at least 1)", entry, k, n_atoms[k]);
+            r_max = std::max(r_max, (int)n_atoms[k]);
+        }
+        if (p->r != r_max) return fail(SNMF_ERR_DIM, "%s: params->r = %d must be the largest n_atoms, %d", entry, p->r, r_max);
+    }
     {
         snmf_params q = *p;
         q.T = 1;  // (ignored: every problem brings its own)
@@ -354,10 +366,10 @@ int train_audio_batch(const char* entry, snmf_batch* (*make)(), snmf_ctx* ctx, c
     if (mel && mel_M < 1) return fail(SNMF_ERR_INVALID, "%s: mel_M must be positive", entry);
     if (p->sparsity_kind != SNMF_SPARSITY_SCALAR)
         return fail(SNMF_ERR_UNSUPPORTED, "%s: a sparsity vector or matrix is not supported by the training entry (it takes the scalar of p)", entry);
-    const int nb = sp->fftlength / 2 + 1, Ks = 2 * sp->splice + 1, r = p->r;
+    const int nb = sp->fftlength / 2 + 1, Ks = 2 * sp->splice + 1;
     const int64_t F = (int64_t)Ks * nb, Fm = mel ? (int64_t)Ks * mel_M : 0;
     std::vector<int32_t> T(n);
-    std::vector<int64_t> len(n), s0(n), idx((size_t)n * r);
+    std::vector<int64_t> len(n), s0(n), idx;
     int64_t sumL = 0, sumT = 0;
     for (int k = 0; k < n; ++k) {
         if ((!ts && !samples[k]) || !sample_idx[k] || !B_DFT[k] || (mel && !B_Mel[k])) return fail(SNMF_ERR_INVALID, "%s: an array of problem %d is NULL", entry, k);
@@ -374,13 +386,15 @@ int train_audio_batch(const char* entry, snmf_batch* (*make)(), snmf_ctx* ctx, c
     if (sumT > kMaxFrames) return fail(SNMF_ERR_UNSUPPORTED, "%s: %lld frames are above the launch grid's limit", entry, (long long)sumT);
     if (F != p->F) return fail(SNMF_ERR_DIM, "%s: the signals give %lld feature rows, params say %d", entry, (long long)F, p->F);
     if (Fm > 0x7fffffffLL) return fail(SNMF_ERR_UNSUPPORTED, "%s: %lld Mel feature rows", entry, (long long)Fm);
-    for (int k = 0; k < n; ++k)
+    for (int k = 0; k < n; ++k) {  // (packed: problem k's entries behind those of the problems before it)
+        const int r = n_atoms ? n_atoms[k] : p->r;
         for (int j = 0; j < r; ++j) {
             const int64_t t = sample_idx[k][j];
             if (t < 0 || t >= T[k])
                 return fail(SNMF_ERR_DIM, "%s: sample_idx[%d][%d] = %lld outside [0, %d)", entry, k, j, (long long)t, T[k]);
-            idx[(size_t)k * r + j] = t;
+            idx.push_back(t);
         }
+    }
     (void)hipGetLastError();
 
     std::vector<SigCopy> h_cp;  // (the source of an asynchronous copy: it lives as long as the front-end)
@@ -409,7 +423,7 @@ int train_audio_batch(const char* entry, snmf_batch* (*make)(), snmf_ctx* ctx, c
         }
         return fe.run(n, s0.data(), T.data(), dft.data(), mel ? melb.data() : nullptr, alpha_eta_dd);
     };
-    return train_batch_run<double>(entry, make, ctx, p, (int32_t)Fm, n, T.data(), in, B_DFT, A_DFT, B_Mel, A_Mel, n_iter);
+    return train_batch_run<double>(entry, make, ctx, p, (int32_t)Fm, n, T.data(), in, B_DFT, A_DFT, B_Mel, A_Mel, n_iter, n_atoms);
 }
 
 snmf_batch* make32() { return batch32_new(); }
@@ -453,6 +467,29 @@ extern "C" int snmf_run_basis_train_signals_batch_fp64(snmf_ctx* ctx, const snmf
     if (!signals) return fail(SNMF_ERR_INVALID, "%s: NULL argument", entry);
     return train_audio_batch<double>(entry, make64, ctx, p, sp, alpha_eta_dd, mel, mel_M, 0, nullptr, nullptr, sample_idx, train_exemplar, H0, seed,
                                      B_DFT, A_DFT, B_Mel, A_Mel, n_iter, signals);
+}
+
+extern "C" int snmf_run_basis_train_audio_batch_ranks_fp64(snmf_ctx* ctx, const snmf_params* p, const snmf_stft_params* sp, double alpha_eta_dd,
+                                                           const double* mel, int32_t mel_M, int32_t n_problems, const double* const* samples,
+                                                           const int64_t* n_samples, const int32_t* n_atoms, const int64_t* const* sample_idx,
+                                                           int32_t train_exemplar, const double* const* H0, const uint64_t* seed,
+                                                           double* const* B_DFT, double* const* A_DFT, double* const* B_Mel,
+                                                           double* const* A_Mel, int32_t* n_iter) {
+    const char* entry = "snmf_run_basis_train_audio_batch_ranks_fp64";
+    if (!n_atoms) return fail(SNMF_ERR_INVALID, "%s: NULL argument", entry);
+    return train_audio_batch<double>(entry, make64, ctx, p, sp, alpha_eta_dd, mel, mel_M, n_problems, samples, n_samples, sample_idx,
+                                     train_exemplar, H0, seed, B_DFT, A_DFT, B_Mel, A_Mel, n_iter, nullptr, n_atoms);
+}
+extern "C" int snmf_run_basis_train_signals_batch_ranks_fp64(snmf_ctx* ctx, const snmf_params* p, const snmf_stft_params* sp, double alpha_eta_dd,
+                                                             const double* mel, int32_t mel_M, const snmf_train_signals* signals,
+                                                             const int32_t* n_atoms, const int64_t* const* sample_idx, int32_t train_exemplar,
+                                                             const double* const* H0, const uint64_t* seed, double* const* B_DFT,
+                                                             double* const* A_DFT, double* const* B_Mel, double* const* A_Mel,
+                                                             int32_t* n_iter) {
+    const char* entry = "snmf_run_basis_train_signals_batch_ranks_fp64";
+    if (!signals || !n_atoms) return fail(SNMF_ERR_INVALID, "%s: NULL argument", entry);
+    return train_audio_batch<double>(entry, make64, ctx, p, sp, alpha_eta_dd, mel, mel_M, 0, nullptr, nullptr, sample_idx, train_exemplar, H0, seed,
+                                     B_DFT, A_DFT, B_Mel, A_Mel, n_iter, signals, n_atoms);
 }
 
 extern "C" int snmf_stft_features_batch_f32(snmf_ctx* ctx, const snmf_stft_params* sp, int32_t n_signals, const float* const* samples,

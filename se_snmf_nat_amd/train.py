@@ -103,19 +103,43 @@ def run_basis_train_signal_batch(signals, R, p, *, DC_bin=None, sample_idx=None,
     run_basis_train.m, one training signal per event class or noise type, in ONE call across the C ABI
     (snmf_run_basis_train_audio_batch_f64; precision="fp64": _fp64).  The signals (any lengths) go up as one slab, TF_mag, TF_DD and
     TF_Mel of all of them are formed in HBM by shared launches, the exemplar columns are gathered there, and the DFT and the Mel
-    solves are two resident batches.  R, p and DC_bin are shared.  Returns a list of the dicts run_basis_train_signal returns.
+    solves are two resident batches.  p and DC_bin are shared.  Returns a list of the dicts run_basis_train_signal returns.
+    R: one dictionary size for every problem, or a sequence with one per problem (the reference trains events with R_x and noise
+    with R_d, Do_MultiBatch_IS16_20160324.m:107,135).  Equal entries are the scalar call in both precisions; differing ones need
+    precision="fp64" (snmf_run_basis_train_audio_batch_ranks_fp64; SnmfError status 8 in fp32).  Problem k then has
+    n_ex_k = cluster_buff * R_k exemplar columns in its default sample_idx, its H0 and its results, and the host epilogue
+    (renormalise + 1e-9, reduce_rank to R_k when cluster_buff > 1) runs with its own R_k.
 
     sample_idx: None = every problem gets the single call's own stand-in draw, RandomState(1).choice(T_k, cluster_buff*R,
     replace=False) + 1 (the reference re-seeds per class, :80-81); else a list of 1-based index arrays, one per problem.
     h0: "host" = every problem gets the draw the single call makes, RandomState(random_seed).random_sample((n_ex, T_k)) -- the same
     seed for every problem, since the reference re-seeds inside every sparse_nmf call; "device" = drawn on the device from
     random_seed, for every problem.  Both solves of a problem start from the same H0, as in the single call.
-    precision="fp64": problem k is bit for bit run_basis_train_signal(s_k, R, p, precision="fp64", ...) alone.
+    precision="fp64": problem k is bit for bit run_basis_train_signal(s_k, R_k, p, precision="fp64", ...) alone.
     precision="fp32": the fp32 batch engine (F <= 513, cluster_buff*R <= 200): bit for bit sparse_nmf_batch(precision="fp32") on
     the fp32 features stft_features (then tf_dd, then mel_features on that) give for s_k, with init_w their columns sample_idx_k.
     Any other string is a ValueError.  info["T"] receives the frame counts, info["n_iter"] a list of [n_dft, n_mel].
     Every argument error is raised before the library is loaded."""
     return _train_batch(signals, None, R, p, DC_bin=DC_bin, sample_idx=sample_idx, ctx=ctx, h0=h0, precision=precision, info=info)
+
+
+def _train_ranks(R, n, precision):
+    """R of the batched training calls: an int (one dictionary size for every problem) -> None; a sequence with one entry per
+    problem -> the list when the entries differ (fp64 only: SnmfError status 8 in fp32), None when they are equal (the scalar
+    call).  Its own errors: a length that is not n (3), an entry below 1 (1)."""
+    if not isinstance(R, (list, tuple, np.ndarray)) or (isinstance(R, np.ndarray) and R.ndim == 0):
+        return None
+    Rs = [int(x) for x in np.asarray(R).reshape(-1)]
+    if len(Rs) != n:
+        raise SnmfError(3, f"R is a list of {len(Rs)}, the batch has {n} problems")
+    for k, x in enumerate(Rs):
+        if x < 1:
+            raise SnmfError(1, f"R of problem {k} is {x} (at least 1)")
+    if len(set(Rs)) == 1:
+        return None
+    if precision != "fp64":
+        raise SnmfError(8, "differing R need precision='fp64': the fp32 batch engine has one rank for all problems")
+    return Rs
 
 
 def _train_batch(signals, ts, R, p, *, DC_bin, sample_idx, ctx, h0, precision, info):
@@ -145,31 +169,33 @@ def _train_batch(signals, ts, R, p, *, DC_bin, sample_idx, ctx, h0, precision, i
         raise SnmfError(3, "h0 must be 'host' or 'device'")
     K = 2 * int(fp.get("Splice", 0)) + 1
     F, M = K * (int(fp["fftlength"]) // 2 + 1), int(p["F_order"])
-    n_ex = cluster_buff * int(R)
+    Rk = _train_ranks(R, n, precision)  # a list only when the problems' R differ
+    Rs = Rk if Rk is not None else [int(np.asarray(R).reshape(-1)[0])] * n
+    n_exs = [cluster_buff * r for r in Rs]
     Ts = [frontend.num_frames_host(size, fp) for size in sizes]
-    for k, T in enumerate(Ts):
+    for k, (T, n_ex) in enumerate(zip(Ts, n_exs)):
         if T < 1:
             raise SnmfError(3, f"the training signal of problem {k} is shorter than one analysis frame")
         if n_ex > T:
             raise SnmfError(3, f"problem {k} has {T} frames, fewer than cluster_buff*R = {n_ex} exemplar columns")
-    if sample_idx is None:
-        sample_idx = [np.random.RandomState(1).choice(T, size=n_ex, replace=False) + 1 for T in Ts]  # :80-81 stand-in, per class
+    if sample_idx is None:  # :80-81 stand-in, per class
+        sample_idx = [np.random.RandomState(1).choice(T, size=n_ex, replace=False) + 1 for T, n_ex in zip(Ts, n_exs)]
     elif len(sample_idx) != n:
         raise SnmfError(3, f"sample_idx is a list of {len(sample_idx)}, the batch has {n} problems")
     idx0 = [np.ascontiguousarray(np.asarray(ix, dtype=np.int64).reshape(-1) - 1) for ix in sample_idx]
     for k, (ix, T) in enumerate(zip(idx0, Ts)):
-        if ix.size != n_ex or ix.min() < 0 or ix.max() >= T:
+        if ix.size != n_exs[k] or ix.min() < 0 or ix.max() >= T:
             raise SnmfError(3, f"sample_idx of problem {k} must hold cluster_buff*R valid 1-based column indices")
     if exemplar:
         beta, max_iter, conv_eps, cost_check, lam = 1.0, 1, 0.0, 0, 0.0
     else:
         beta, max_iter, conv_eps, cost_check, lam = _solver_scalars(p)
-    q = _make_params(F, 1, n_ex, beta, max_iter, conv_eps, cost_check, True, 0, lam, None, None)
+    q = _make_params(F, 1, max(n_exs), beta, max_iter, conv_eps, cost_check, True, 0, lam, None, None)
     seed = int(p.get("random_seed", 1))
     H0s = seeds = None
     if not exemplar:
         if h0 == "host":
-            H0s = [np.asfortranarray(np.random.RandomState(seed if seed > 0 else None).random_sample((n_ex, T))) for T in Ts]
+            H0s = [np.asfortranarray(np.random.RandomState(seed if seed > 0 else None).random_sample((n_ex, T))) for T, n_ex in zip(Ts, n_exs)]
         else:
             seeds = np.full(n, seed, np.uint64)
     mel = frontend._mel_table(p, sdt)
@@ -177,21 +203,29 @@ def _train_batch(signals, ts, R, p, *, DC_bin, sample_idx, ctx, h0, precision, i
 
     lib = _lib.load()
     ctx = ts._ctx if ts is not None else (ctx or default_context())
-    B_DFT = [np.empty((F, n_ex), order="F") for _ in Ts]
-    B_Mel = [np.empty((K * M, n_ex), order="F") for _ in Ts]
+    B_DFT = [np.empty((F, n_ex), order="F") for n_ex in n_exs]
+    B_Mel = [np.empty((K * M, n_ex), order="F") for n_ex in n_exs]
     A_DFT = A_Mel = None
     if not exemplar:
-        A_DFT = [np.empty((n_ex, T), order="F") for T in Ts]
-        A_Mel = [np.empty((n_ex, T), order="F") for T in Ts]
+        A_DFT = [np.empty((n_ex, T), order="F") for T, n_ex in zip(Ts, n_exs)]
+        A_Mel = [np.empty((n_ex, T), order="F") for T, n_ex in zip(Ts, n_exs)]
     n_iter = np.zeros(2 * n, np.int32)
     ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None  # noqa: E731
     ptrs = lambda arrs: (C.c_void_p * n)(*[a.ctypes.data for a in arrs]) if arrs is not None else None  # noqa: E731
     alpha = float(p["alpha_eta"]) if p.get("domain_DD", 0) else -1.0
+    atoms = np.array(n_exs, np.int32)
     tail = (ptrs(idx0), 1 if exemplar else 0, ptrs(H0s), ptr(seeds), ptrs(B_DFT), ptrs(A_DFT), ptrs(B_Mel), ptrs(A_Mel), ptr(n_iter))
     if ts is None:
         lens = np.array(sizes, np.int64)
-        fn = lib.snmf_run_basis_train_audio_batch_fp64 if f64 else lib.snmf_run_basis_train_audio_batch_f64
-        _lib.check(fn(ctx._h, C.byref(q), C.byref(sp), alpha, ptr(mel), M, n, ptrs(sigs), ptr(lens), *tail))
+        if Rk is not None:
+            _lib.check(lib.snmf_run_basis_train_audio_batch_ranks_fp64(ctx._h, C.byref(q), C.byref(sp), alpha, ptr(mel), M, n, ptrs(sigs),
+                                                                       ptr(lens), ptr(atoms), *tail))
+        else:
+            fn = lib.snmf_run_basis_train_audio_batch_fp64 if f64 else lib.snmf_run_basis_train_audio_batch_f64
+            _lib.check(fn(ctx._h, C.byref(q), C.byref(sp), alpha, ptr(mel), M, n, ptrs(sigs), ptr(lens), *tail))
+    elif Rk is not None:
+        _lib.check(lib.snmf_run_basis_train_signals_batch_ranks_fp64(ctx._h, C.byref(q), C.byref(sp), alpha, ptr(mel), M, ts._handle(),
+                                                                     ptr(atoms), *tail))
     else:
         fn = lib.snmf_run_basis_train_signals_batch_fp64 if f64 else lib.snmf_run_basis_train_signals_batch_f64
         _lib.check(fn(ctx._h, C.byref(q), C.byref(sp), alpha, ptr(mel), M, ts._handle(), *tail))
@@ -205,7 +239,7 @@ def _train_batch(signals, ts, R, p, *, DC_bin, sample_idx, ctx, h0, precision, i
         ad, am = (0, 0) if exemplar else (A_DFT[k], A_Mel[k])  # :95-96
         if cluster_buff > 1:  # :118-127
             from .kmeans import reduce_rank
-            bm, bd, ad, am, _ = reduce_rank(bm, bd, ad, am, int(R), seed=int(p.get("kmeans_seed", 1)))
+            bm, bd, ad, am, _ = reduce_rank(bm, bd, ad, am, Rs[k], seed=int(p.get("kmeans_seed", 1)))
         out.append({"B_DFT_sub": bd, "B_Mel_sub": bm, "A_DFT_sub": ad, "A_Mel_sub": am})  # :130-134
     return out
 
@@ -361,6 +395,8 @@ def run_basis_train_clips_batch(classes, R, p, *, vad=None, ranges=None, DC_bin=
         raise SnmfError(3, "cluster_buff > 1 needs train_Exemplar = 0 (run_basis_train.m:125-126 index A_*_init, a scalar otherwise)")
     if not p.get("train_Exemplar", 0):
         _solver_scalars(p)
+    if isinstance(classes, (list, tuple)):
+        _train_ranks(R, len(classes), precision)
     frontend._params(p if DC_bin is None else dict(p, DCbin=int(DC_bin)))
     with assemble_training_signals(classes, p, vad=vad, ranges=ranges, ctx=ctx) as ts:
         if info is not None:
