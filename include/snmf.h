@@ -803,6 +803,35 @@ int snmf_sparse_nmf_batch_fp64(snmf_ctx* ctx, const snmf_params* p, int32_t n_pr
 int snmf_batch_create_ranks_fp64(snmf_ctx* ctx, const snmf_params* p, int32_t n_problems, const int32_t* T, const int32_t* r,
                                  snmf_batch** out);
 
+/* Added within 5.  Settings of its own for every problem of an fp64 batch: the divergence, the sparsity weight, the stop
+ * threshold and the iteration limit, so that a sweep over them is one batch.  s holds n_problems entries.  p gives F, cost_check,
+ * floor_v and the masks, which stay shared; p->beta, p->sparsity_scalar and p->conv_eps are ignored; p->max_iter must be the
+ * largest s[k].max_iter (SNMF_ERR_DIM otherwise), as p->r is the largest rank on snmf_batch_create_ranks_fp64.  r: a rank per
+ * problem under the rules of that entry, or NULL for p->r in every problem.
+ * THE CONTRACT: W, H, div, cost and n_iter of problem k are bit for bit those of snmf_sparse_nmf_fp64 run alone on it with s[k]
+ * in the place of the four fields -- whatever the settings, ranks, sizes and order of the problems around it.  A problem whose
+ * stop test never fires ends after exactly s[k].max_iter iterations with n_iter = s[k].max_iter, with cost_check = 0 too;
+ * n_problems equal settings give the bits of snmf_batch_create_fp64 / _ranks_fp64 with those settings in p; run(n) + run(0)
+ * gives the bits of run(0), also where a problem's own max_iter falls inside the first run.
+ * The handle is an snmf_batch: set_problem_f64 / _f32, run, get_f64 / _f32 (p->max_iter entries of div and cost, zero past the
+ * problem's own count), describe (which also reports the number of distinct modes and the smallest and largest max_iter) and
+ * destroy work on it as on any other.  The kernels find a problem's settings in the device table of problems; the passes that
+ * are compiled per divergence are launched once per divergence present.
+ * Refused before the device is touched: NULL s, a non-zero reserved (SNMF_ERR_INVALID); a field of s[k] that snmf_params would
+ * be refused for (that status, the message names the problem); a sparsity kind other than SNMF_SPARSITY_SCALAR
+ * (SNMF_ERR_UNSUPPORTED); and what snmf_batch_create_fp64 / _ranks_fp64 refuse.  There is no fp32 form, no DNMF form and no
+ * missing-data form (a masked handle with settings is SNMF_ERR_UNSUPPORTED). */
+typedef struct snmf_problem_settings {
+    double beta;        /* divergence order: 1 kl, 2 ed, 0 is, else generic */
+    double sparsity;    /* scalar */
+    double conv_eps;    /* 0: no stop test */
+    int32_t max_iter;
+    int32_t reserved;   /* 0 */
+} snmf_problem_settings;
+
+int snmf_batch_create_settings_fp64(snmf_ctx* ctx, const snmf_params* p, int32_t n_problems, const int32_t* T, const int32_t* r,
+                                    const snmf_problem_settings* s, snmf_batch** out);
+
 /* Added within 5.  The missing-data solves in the batch: snmf_mdi_fp64 (src/snmf_mdi.m / src/snmf_mdi_Sm.m) for n_problems
  * problems, each with a mask of its own (M_b F x T_b, 1 = observed, soft masks in [0, 1]), in the shared launches of the fp64
  * batch ("Batched missing-data solves").  fp64 only: the fused fp32 missing-data kernels have no batched form.
@@ -1025,6 +1054,25 @@ int snmf_run_basis_train_signals_batch_ranks_fp64(snmf_ctx* ctx, const snmf_para
                                                   const int32_t* n_atoms, const int64_t* const* sample_idx, int32_t train_exemplar,
                                                   const double* const* H0, const uint64_t* seed, double* const* B_DFT,
                                                   double* const* A_DFT, double* const* B_Mel, double* const* A_Mel, int32_t* n_iter);
+
+/* Added within 5.  The two entries above with settings per problem (snmf_problem_settings, as on
+ * snmf_batch_create_settings_fp64): the argument lists of the _ranks_fp64 namesakes plus s, n_problems entries.  n_atoms may be
+ * NULL: p->r atoms for every problem.  Both resident batches, DFT and Mel, are made with the settings; p->beta,
+ * p->sparsity_scalar and p->conv_eps are ignored and p->max_iter must be the largest s[k].max_iter.  THE CONTRACT: signal k is
+ * bit for bit snmf_run_basis_train_audio_fp64 run alone with s[k] in the place of the four fields.  NULL s: SNMF_ERR_INVALID;
+ * everything else is refused as by the namesakes and by snmf_batch_create_settings_fp64, before the device is touched. */
+int snmf_run_basis_train_audio_batch_settings_fp64(snmf_ctx* ctx, const snmf_params* p, const snmf_stft_params* sp, double alpha_eta_dd,
+                                                   const double* mel, int32_t mel_M, int32_t n_problems, const double* const* samples,
+                                                   const int64_t* n_samples, const int32_t* n_atoms, const int64_t* const* sample_idx,
+                                                   int32_t train_exemplar, const double* const* H0, const uint64_t* seed,
+                                                   double* const* B_DFT, double* const* A_DFT, double* const* B_Mel, double* const* A_Mel,
+                                                   int32_t* n_iter, const snmf_problem_settings* s);
+int snmf_run_basis_train_signals_batch_settings_fp64(snmf_ctx* ctx, const snmf_params* p, const snmf_stft_params* sp, double alpha_eta_dd,
+                                                     const double* mel, int32_t mel_M, const snmf_train_signals* signals,
+                                                     const int32_t* n_atoms, const int64_t* const* sample_idx, int32_t train_exemplar,
+                                                     const double* const* H0, const uint64_t* seed, double* const* B_DFT,
+                                                     double* const* A_DFT, double* const* B_Mel, double* const* A_Mel, int32_t* n_iter,
+                                                     const snmf_problem_settings* s);
 
 /* ---- instrumentation (bench.py: HIP-event timing on the engine's own stream) ------------ */
 /* Average device time in milliseconds per launch of the named kernel family over the launches

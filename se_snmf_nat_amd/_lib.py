@@ -102,6 +102,7 @@ SYMBOLS = [
     "snmf_train_signals_assemble_i16", "snmf_train_signals_assemble_f64", "snmf_train_signals_info", "snmf_train_signals_get_f64",
     "snmf_train_signals_destroy", "snmf_run_basis_train_signals_batch_f64", "snmf_run_basis_train_signals_batch_fp64",
     "snmf_batch_create_ranks_fp64", "snmf_run_basis_train_audio_batch_ranks_fp64", "snmf_run_basis_train_signals_batch_ranks_fp64",
+    "snmf_batch_create_settings_fp64", "snmf_run_basis_train_audio_batch_settings_fp64", "snmf_run_basis_train_signals_batch_settings_fp64",
     "snmf_rccl_available", "snmf_rccl_get_unique_id", "snmf_rccl_comm_create", "snmf_rccl_comm_destroy", "snmf_plan_run_sharded_rccl",
 ]
 ABI_VERSION = 5  # include/snmf.h: SNMF_ABI_VERSION this binding was written against
@@ -112,6 +113,11 @@ STATUS_NAMES = {
     0: "SNMF_OK", 1: "SNMF_ERR_INVALID", 2: "SNMF_ERR_NO_INIT", 3: "SNMF_ERR_DIM", 4: "SNMF_ERR_NO_FIELD",
     5: "SNMF_ERR_NO_DEVICE", 6: "SNMF_ERR_NOMEM", 7: "SNMF_ERR_STATE", 8: "SNMF_ERR_UNSUPPORTED", 9: "SNMF_ERR_INTERNAL",
 }
+
+
+class SnmfProblemSettings(C.Structure):
+    """include/snmf.h: snmf_problem_settings, the settings of one problem of an fp64 batch with settings per problem."""
+    _fields_ = [("beta", C.c_double), ("sparsity", C.c_double), ("conv_eps", C.c_double), ("max_iter", C.c_int32), ("reserved", C.c_int32)]
 
 
 class SnmfParams(C.Structure):
@@ -408,6 +414,11 @@ def load():
     sig["snmf_batch_create_ranks_fp64"] = (C.c_int, [vp, PP, i32, vp, vp, C.POINTER(vp)])
     sig["snmf_run_basis_train_audio_batch_ranks_fp64"] = (C.c_int, [vp, PP, SP, dbl, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp])
     sig["snmf_run_basis_train_signals_batch_ranks_fp64"] = (C.c_int, [vp, PP, SP, dbl, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp])
+    # settings per problem in the fp64 batch: the ranks (may be NULL) and the settings after T / the settings at the end
+    sig["snmf_batch_create_settings_fp64"] = (C.c_int, [vp, PP, i32, vp, vp, vp, C.POINTER(vp)])
+    sig["snmf_run_basis_train_audio_batch_settings_fp64"] = (C.c_int, [vp, PP, SP, dbl, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp,
+                                                                      vp])
+    sig["snmf_run_basis_train_signals_batch_settings_fp64"] = (C.c_int, [vp, PP, SP, dbl, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp])
     lib.snmf_abi_version.restype = C.c_int
     if lib.snmf_abi_version() != ABI_VERSION:  # a stale library must not be driven through newer prototypes
         raise ImportError(f"{path} has ABI version {lib.snmf_abi_version()}, this binding needs {ABI_VERSION}: rebuild the library")

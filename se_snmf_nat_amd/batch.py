@@ -13,7 +13,10 @@
 The problems share the row count F and the settings `p`; every problem has its own frame count, its own initial factors and
 its own stop index.  The rank r is shared too, except in the fp64 batch (sparse_nmf_batch_fp64, BatchPlan64), where every
 problem may have a rank of its own (snmf_batch_create_ranks_fp64): a list for r, or init_w arrays of different widths.  The fp32
-engine, the missing-data batches and the DNMF batches stay at one rank.  All arithmetic happens in libsnmf_hip.so on the GPU;
+engine, the missing-data batches and the DNMF batches stay at one rank.  In the fp64 batch the settings may differ per problem
+as well (snmf_batch_create_settings_fp64): a list of settings dicts for sparse_nmf_batch_fp64, settings=[...] for BatchPlan64 --
+divergence, sparsity weight, max_iter and conv_eps of its own for every problem, so that a sweep over them is one batch;
+cost_check, floor_v and the masks stay shared.  All arithmetic happens in libsnmf_hip.so on the GPU;
 this module does the reference's defaulting and its own errors (src/sparse_nmf.m:75-164, :260) on the host, before any device call.
 """
 from __future__ import annotations
@@ -84,6 +87,49 @@ def _mixed_rank_rules(sparsity, masks):
                 raise SnmfError(8, f"a batch with differing ranks takes a {key} of all ones or all zeros")
             on[key] = int(m.all())
     return float(sp.reshape(-1)[0]), on
+
+
+_SETTING_KEYS = ("cf", "beta", "sparsity", "max_iter", "conv_eps")
+
+
+def _problem_settings(settings, B, shared):
+    """Settings per problem (BatchPlan64, the batched training calls): a list of B dicts with keys among cf, beta, sparsity,
+    max_iter, conv_eps -> a list of B tuples (beta, sparsity, max_iter, conv_eps); a missing key takes the value of `shared`
+    (a dict with those four).  Its own errors, all before the library is loaded: a list of another length (3), an entry that is
+    no dict or has an unknown key (1), a sparsity that is not a scalar (8), a max_iter below 0 (1)."""
+    if isinstance(settings, dict) or not isinstance(settings, (list, tuple)):
+        raise SnmfError(3, f"settings must be a list of {B} dicts, one per problem")
+    if len(settings) != B:
+        raise SnmfError(3, f"settings is a list of {len(settings)}, the batch has {B} problems")
+    out = []
+    for k, s in enumerate(settings):
+        if not isinstance(s, dict):
+            raise SnmfError(1, f"settings of problem {k} must be a dict with keys among {_SETTING_KEYS}")
+        unknown = sorted(set(s) - set(_SETTING_KEYS))
+        if unknown:
+            raise SnmfError(1, f"settings of problem {k} have unknown keys {unknown} (known: {_SETTING_KEYS})")
+        if "cf" in s:
+            beta = _cf_to_beta(s)  # src/sparse_nmf.m:95-110
+        elif "beta" in s:
+            beta = float(s["beta"])
+        else:
+            beta = float(shared["beta"])
+        sp = np.asarray(s.get("sparsity", shared["sparsity"]), dtype=np.float64)
+        if sp.size != 1:
+            raise SnmfError(8, f"settings of problem {k}: a batch with settings per problem takes a scalar sparsity, not a vector or a matrix")
+        mi = int(s.get("max_iter", shared["max_iter"]))
+        if mi < 0:
+            raise SnmfError(1, f"settings of problem {k}: max_iter must be >= 0")
+        out.append((beta, float(sp.reshape(-1)[0]), mi, float(s.get("conv_eps", shared["conv_eps"]))))
+    return out
+
+
+def _settings_array(resolved):
+    """The tuples of _problem_settings as the C array of snmf_problem_settings."""
+    arr = (_lib.SnmfProblemSettings * len(resolved))()
+    for a, (beta, sparsity, mi, eps) in zip(arr, resolved):
+        a.beta, a.sparsity, a.conv_eps, a.max_iter, a.reserved = beta, sparsity, eps, mi, 0
+    return arr
 
 
 def _objective(div, cost, ni, max_iter, cost_check):
@@ -192,6 +238,8 @@ def sparse_nmf_batch(vs, p=None, *, ctx=None, dtype=np.float64, rng=None, precis
     Every problem stops at its own iteration, with the results of a solve that ran alone; the results of a problem do not
     depend on the batch around it.  `precision` accepts only "fp32" (ValueError otherwise)."""
     _check_batch_precision(precision)
+    if isinstance(p, (list, tuple)):
+        raise SnmfError(8, "settings per problem need the fp64 batch: sparse_nmf_batch_fp64(vs, [p_0, ...])")
     return _solve_batch(vs, p, ctx, dtype, rng, "fp32")
 
 
@@ -203,7 +251,15 @@ def sparse_nmf_batch_fp64(vs, p=None, *, ctx=None, rng=None):
     rank then follows src/sparse_nmf.m:116-131 on its own (init_w_k's width, or p["r"][k] when that is larger: the missing
     columns are drawn), init_h[k] is r_k x T_k, and the draws stay in list order, w then h per problem, each of its own shape.
     With differing ranks the sparsity must be a scalar and the masks absent, all ones or all zeros (SnmfError status 8
-    otherwise), and the solve goes through the resident handle (snmf_batch_create_ranks_fp64); equal ranks are the call above."""
+    otherwise), and the solve goes through the resident handle (snmf_batch_create_ranks_fp64); equal ranks are the call above.
+    Settings per problem: p may be a list of len(vs) dicts, one per problem (snmf_batch_create_settings_fp64) -- a sweep over
+    divergence, sparsity, max_iter or conv_eps in one batch.  Per problem: cf, beta, sparsity (a scalar; a vector is status 8),
+    max_iter, conv_eps, r, init_w, init_h and display (differing ranks under the rules above).  Shared, and equal in every dict
+    (status 3 otherwise): cost_check (status 4 where absent), the masks and random_seed.  The draws are the dict call's: one
+    generator, list order, w then h.  Problem k is bit for bit sparse_nmf(vs[k], p[k], precision="fp64") alone on the same
+    initial factors, and its objective vectors have the single call's length; a list of equal dicts gives the dict call's bits."""
+    if isinstance(p, (list, tuple)):
+        return _solve_batch_settings(vs, list(p), ctx, rng)
     return _solve_batch(vs, p, ctx, np.float64, rng, "fp64")
 
 
@@ -303,6 +359,116 @@ def _solve_batch_ranks(vs, p, ctx, rng, m, rs, iws, ihs, beta, max_iter, conv_ep
     return out
 
 
+def _mask_key(m):
+    return None if m is None else tuple(bool(x) for x in np.asarray(m).reshape(-1) != 0)
+
+
+def _solve_batch_settings(vs, ps, ctx, rng):
+    """sparse_nmf_batch_fp64 with a list of settings dicts: the reference's defaulting and errors per problem, the batch's
+    refusals and the draws, all before the library is loaded; then BatchPlan64 with the settings (and the ranks, where they
+    differ) -- set every problem, run to the end, get."""
+    dt = np.dtype(np.float64)
+    vs = [np.asarray(v) for v in vs]
+    B = len(vs)
+    if B == 0:
+        raise SnmfError(1, "the batch is empty: vs must hold at least one matrix")
+    if len(ps) != B:
+        raise SnmfError(3, f"p is a list of {len(ps)} settings, the batch has {B} problems")
+    for v in vs:
+        if v.ndim != 2 or v.shape[1] < 1:
+            raise SnmfError(1, "every v must be a 2-D matrix with at least one column")
+    m = vs[0].shape[0]  # :71
+    for k, v in enumerate(vs):
+        if v.shape[0] != m:
+            raise SnmfError(3, f"v of problem {k} has {v.shape[0]} rows, problem 0 has {m}: a batch shares the row count")
+    ps = [dict(q or {}) for q in ps]
+    # ---- per problem: the settings (:79-110, :150-155) and the rank with its initial factors (:116-140)
+    resolved, rs, iws, ihs = [], [], [], []
+    for k, (q, v) in enumerate(zip(ps, vs)):
+        sp = np.asarray(q.get("sparsity", 0), dtype=np.float64)
+        if sp.size != 1:
+            raise SnmfError(8, f"problem {k}: a batch with settings per problem takes a scalar sparsity, not a vector or a matrix")
+        mi = int(q.get("max_iter", 100))
+        if mi < 0:
+            raise SnmfError(1, f"problem {k}: max_iter must be >= 0")
+        resolved.append((_cf_to_beta(q), float(sp.reshape(-1)[0]), mi, float(q.get("conv_eps", 0))))
+        iw, rk = q.get("init_w", None), q.get("r", None)
+        if iw is None:
+            if rk is None:
+                raise SnmfError(2, "Number of components or initialization must be given")
+            r = int(rk)
+            if r < 1:
+                raise SnmfError(1, f"problem {k} has rank {r} (at least 1)")
+        else:
+            iw = np.asarray(iw, dtype=np.float64)
+            if iw.ndim != 2 or iw.shape[0] != m or iw.shape[1] < 1:
+                raise SnmfError(3, f"init_w is {iw.shape}, v has {m} rows")
+            r = int(rk) if (rk is not None and iw.shape[1] < int(rk)) else iw.shape[1]  # :123-130
+        ih = q.get("init_h", None)
+        if ih is not None:
+            ih = np.asarray(ih, dtype=np.float64)
+            if ih.shape != (r, v.shape[1]):
+                raise SnmfError(3, f"init_h is {ih.shape}, expected ({r}, {v.shape[1]})")
+        rs.append(r)
+        iws.append(iw)
+        ihs.append(ih)
+    # ---- shared: cost_check, the masks, random_seed
+    for q in ps:
+        if "cost_check" not in q:  # src/sparse_nmf.m:260
+            raise SnmfError(4, "Reference to non-existent field 'cost_check'.")
+    cost_check = 1 if ps[0]["cost_check"] else 0
+    seed = ps[0].get("random_seed", 1)
+    mixed = len(set(rs)) > 1
+    masks = {}
+    for key in ("w_update_ind", "h_update_ind"):
+        if mixed:  # the classes of the ranks rules: absent or all ones, all zeros
+            cls = [_mixed_rank_rules(0.0, {key: q.get(key, None)})[1][key] for q in ps]
+        else:
+            cls = [_mask_key(_mask(q, key, rs[0])) for q in ps]
+        if any(c != cls[0] for c in cls):
+            raise SnmfError(3, f"{key} differs between the problems: a batch shares the masks")
+        masks[key] = bool(cls[0]) if mixed else np.array(cls[0], np.uint8)
+    for k, q in enumerate(ps):
+        if (1 if q["cost_check"] else 0) != cost_check:
+            raise SnmfError(3, f"cost_check of problem {k} differs from problem 0: a batch shares it")
+        if q.get("random_seed", 1) != seed:
+            raise SnmfError(3, f"random_seed of problem {k} differs from problem 0: a batch shares it")
+    if not mixed:
+        _h_ind_all_or_none(dict(h_update_ind=masks["h_update_ind"]), rs[0])
+    if rng is None:  # :112-114
+        rng = np.random.RandomState(int(seed) if seed and seed > 0 else None)
+    w0s, h0s = [], []
+    for k, v in enumerate(vs):  # the draws, in list order, w then h (:116-140)
+        n, r = v.shape[1], rs[k]
+        if iws[k] is None:
+            w0 = rng.random_sample((m, r))
+        elif iws[k].shape[1] < r:
+            w0 = np.concatenate([iws[k], rng.random_sample((m, r - iws[k].shape[1]))], axis=1)
+        else:
+            w0 = iws[k]
+        h0 = rng.random_sample((r, n)) if ihs[k] is None else ihs[k]
+        w0s.append(np.asfortranarray(w0, dtype=dt))
+        h0s.append(np.asfortranarray(h0, dtype=dt))
+    plan = BatchPlan64(ctx, m, rs if mixed else rs[0], [v.shape[1] for v in vs], cost_check=cost_check,
+                       w_update_ind=masks["w_update_ind"], h_update_ind=masks["h_update_ind"],
+                       settings=[dict(beta=b, sparsity=s, max_iter=mi, conv_eps=e) for b, s, mi, e in resolved])
+    try:
+        for k, v in enumerate(vs):
+            plan.set_problem(k, np.asarray(v, dtype=dt), w0s[k], h0s[k])
+        plan.run()
+        raw = [plan._get(k, dt) for k in range(B)]
+    finally:
+        plan.close()
+    out = []
+    for k, (W, H, div, cost, ni) in enumerate(raw):
+        beta, _, mi, eps = resolved[k]
+        div, cost = div[:max(mi, 1)], cost[:max(mi, 1)]
+        if ps[k].get("display", 0) != 0:
+            _display(beta, div, cost, ni, mi, cost_check, eps, False)
+        out.append((W, H, _objective(div, cost, ni, mi, cost_check)))
+    return out
+
+
 class BatchPlan:
     """snmf_batch: B problems of one (F, r) and one settings struct resident in HBM.  Call order: set_problem for every
     k -> run -> get; run(n) runs n more iterations (None: up to max_iter) and a later run continues."""
@@ -310,23 +476,33 @@ class BatchPlan:
     _create = "snmf_batch_create"
     _create_ranks = None  # the entry that takes a rank per problem, where the engine has one
     _rank_status = 3      # what differing ranks are where it has none
+    _create_settings = None  # the entry that takes settings per problem, where the engine has one (status 8 where it has none)
 
     def __init__(self, ctx, F, r, Ts, *, beta=1.0, max_iter=100, conv_eps=0.0, cost_check=True, floor_v=True, sparsity=0.0,
-                 w_update_ind=None, h_update_ind=None, precision="fp32"):
+                 w_update_ind=None, h_update_ind=None, precision="fp32", settings=None):
         _check_batch_precision(precision)
-        self._init(ctx, F, r, Ts, beta, max_iter, conv_eps, cost_check, floor_v, sparsity, w_update_ind, h_update_ind)
+        self._init(ctx, F, r, Ts, beta, max_iter, conv_eps, cost_check, floor_v, sparsity, w_update_ind, h_update_ind, settings)
 
-    def _init(self, ctx, F, r, Ts, beta, max_iter, conv_eps, cost_check, floor_v, sparsity, w_update_ind, h_update_ind):
+    def _init(self, ctx, F, r, Ts, beta, max_iter, conv_eps, cost_check, floor_v, sparsity, w_update_ind, h_update_ind, settings=None):
         self.Ts = np.ascontiguousarray(np.asarray(Ts, dtype=np.int32).reshape(-1))
         self.B = int(self.Ts.size)
         if self.B == 0:
             raise SnmfError(1, "the batch is empty: Ts must hold at least one frame count")
+        self.settings = None  # settings per problem (BatchPlan64): a list of (beta, sparsity, max_iter, conv_eps); None: shared
+        if settings is not None:
+            if self._create_settings is None:
+                raise SnmfError(8, "this batch has one settings struct for all problems (settings per problem: BatchPlan64)")
+            self.settings = _problem_settings(settings, self.B, dict(beta=beta, sparsity=sparsity, max_iter=max_iter, conv_eps=conv_eps))
+            max_iter = max(s[2] for s in self.settings)  # the handle's: the largest
+            sparsity = 0.0  # (every problem has its own)
         self.ranks = None  # a rank per problem (BatchPlan64 with a sequence for r); None: self.r for every problem
         rs = _rank_list(r, self.B)
         if rs is not None:
             r = self._take_ranks(rs, sparsity, w_update_ind, h_update_ind)
         self.F, self.r, self.max_iter = int(F), int(r), int(max_iter)
         self.cost_check = 1 if cost_check else 0
+        if self.settings is not None:
+            return self._init_settings(ctx, floor_v, w_update_ind, h_update_ind)
         if self.ranks is not None:
             return self._init_ranks(ctx, beta, conv_eps, floor_v, sparsity, w_update_ind, h_update_ind)
         pd = dict(w_update_ind=w_update_ind, h_update_ind=h_update_ind)
@@ -374,9 +550,37 @@ class BatchPlan:
         self._h = h
         self.ctx._plans.add(self)
 
+    def _init_settings(self, ctx, floor_v, w_update_ind, h_update_ind):
+        """The handle with settings per problem (and ranks, where self.ranks is set): the masks under the rules of the form."""
+        masks = dict(w_update_ind=w_update_ind, h_update_ind=h_update_ind)
+        if self.ranks is not None:
+            _, on = _mixed_rank_rules(0.0, masks)
+            self._w_ind = np.full(self.r, on["w_update_ind"], np.uint8)
+            self._h_ind = np.full(self.r, on["h_update_ind"], np.uint8)
+        else:
+            pd = {k: (np.full(self.r, m, np.uint8) if isinstance(m, (bool, np.bool_)) else m) for k, m in masks.items()}
+            self._w_ind = _mask(pd, "w_update_ind", self.r)
+            self._h_ind = _h_ind_all_or_none(pd, self.r)
+        self._sarr = None
+        beta, scalar, _, eps = self.settings[0]  # (the handle ignores these three fields of its params)
+        sp = _make_params(self.F, 1, self.r, beta, self.max_iter, eps, self.cost_check, floor_v, 0, scalar, self._w_ind, self._h_ind)
+        self._rk = np.array(self.ranks, np.int32) if self.ranks is not None else None
+        self._st = _settings_array(self.settings)
+        self._lib = _lib.load()
+        self.ctx = ctx or default_context()
+        h = C.c_void_p()
+        _lib.check(getattr(self._lib, self._create_settings)(self.ctx._h, C.byref(sp), self.B, _ptr(self.Ts),
+                                                             _ptr(self._rk) if self._rk is not None else None, self._st, C.byref(h)))
+        self._h = h
+        self.ctx._plans.add(self)
+
     def rank(self, k):
         """The rank of problem k."""
         return self.r if self.ranks is None else self.ranks[k]
+
+    def max_iter_of(self, k):
+        """The iteration limit of problem k."""
+        return self.max_iter if self.settings is None else self.settings[k][2]
 
     def set_problem(self, k, v, w0, h0):
         k = int(k)
@@ -405,7 +609,8 @@ class BatchPlan:
 
     def get(self, k, dtype=np.float64):
         W, H, div, cost, ni = self._get(k, np.dtype(dtype))
-        return W, H, _objective(div, cost, ni, self.max_iter, self.cost_check)
+        mi = self.max_iter_of(k)  # (the objective vectors of the single solve with the problem's own limit)
+        return W, H, _objective(div[:max(mi, 1)], cost[:max(mi, 1)], ni, mi, self.cost_check)
 
     def _get(self, k, dt):
         k = int(k)
@@ -446,14 +651,21 @@ class BatchPlan64(BatchPlan):
     F x r[k] and init_h r[k] x Ts[k], get(k) returns those shapes, .ranks holds the list (.r its largest entry) and describe()
     names the ranks.  Such a batch takes a scalar sparsity and masks that are absent, a bool, all ones or all zeros; with
     differing ranks anything else is SnmfError status 8, while a sequence of equal ranks with a vector sparsity or a partial
-    mask is the int form.  An int for r is snmf_batch_create_fp64, as before."""
+    mask is the int form.  An int for r is snmf_batch_create_fp64, as before.
+    settings: None, or a list of len(Ts) dicts with keys among cf, beta, sparsity, max_iter, conv_eps -- settings per problem
+    (snmf_batch_create_settings_fp64); a missing key takes the plan's shared value, an unknown key is SnmfError status 1, a list
+    of another length status 3, a vector sparsity status 8.  .settings then holds (beta, sparsity, max_iter, conv_eps) per
+    problem, .max_iter the largest limit, max_iter_of(k) problem k's own; get(k) returns the objective vectors of the single
+    solve with problem k's settings, and describe() names the modes and the limits.  cost_check, floor_v and the masks stay
+    shared.  BatchPlan and BatchPlanMdi64 refuse settings (status 8)."""
 
     _create = "snmf_batch_create_fp64"
     _create_ranks = "snmf_batch_create_ranks_fp64"
+    _create_settings = "snmf_batch_create_settings_fp64"
 
     def __init__(self, ctx, F, r, Ts, *, beta=1.0, max_iter=100, conv_eps=0.0, cost_check=True, floor_v=True, sparsity=0.0,
-                 w_update_ind=None, h_update_ind=None):
-        self._init(ctx, F, r, Ts, beta, max_iter, conv_eps, cost_check, floor_v, sparsity, w_update_ind, h_update_ind)
+                 w_update_ind=None, h_update_ind=None, settings=None):
+        self._init(ctx, F, r, Ts, beta, max_iter, conv_eps, cost_check, floor_v, sparsity, w_update_ind, h_update_ind, settings)
 
 
 def snmf_mdi_batch(vs, Dms, p=None, *, ctx=None, rng=None, info=None):
@@ -552,6 +764,7 @@ class BatchPlanMdi64(BatchPlan64):
     _create = "snmf_batch_create_mdi_fp64"
     _create_ranks = None  # a missing-data batch shares the rank
     _rank_status = 8
+    _create_settings = None  # and the settings
 
     def set_problem(self, k, v, mask, w0, h0):
         k = int(k)

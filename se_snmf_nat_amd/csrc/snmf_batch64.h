@@ -1,6 +1,6 @@
 // ============================================================================================
 // The batched offline solve in the fp64 mode (snmf_batch_create_fp64, snmf_batch_create_ranks_fp64): B independent problems of
-// one F and one settings struct, each with a frame count T_b and a rank r_b of its own (one r for all on a handle made without
+// one F, each with a frame count T_b and a rank r_b of its own (one r for all on a handle made without
 // ranks), each the fp64 solve of snmf_solve64.h, in SHARED launches.  The arrays of a problem are the single solve's -- tight,
 // column-major, nothing padded, 64-bit offsets -- and the problems lie one behind the other: V, Lam, R, D are F x sum(T_b);
 // H, Num, Den are the r_b x T_b matrices packed at sum(r_j T_j); W, Q, P the F x r_b matrices packed at F sum(r_j); the column
@@ -11,6 +11,10 @@
 // grid size that kernel would have had.  So every element, every partial sum and every tree is formed by the same
 // expression in the same order, and a problem's bits are those of snmf_sparse_nmf_fp64 on it alone.
 // A workgroup returns at once when its problem's stop word is set.
+// The settings of a solve -- divergence, sparsity weight, stop threshold, iteration limit -- are entries of B64Prob too
+// (snmf_batch_create_settings_fp64 gives every problem its own; otherwise they are filled from the one settings struct, and the
+// expressions and operands are the same).  A pass that is compiled per divergence is launched once per divergence present, and
+// a workgroup returns at once when its problem's mode is not the launch's: the pattern of the stop word.
 // ============================================================================================
 #pragma once
 
@@ -28,6 +32,10 @@ struct B64Prob {
     long long h0;   // H elements of the problems before it: sum r_j T_j
     long long w0;   // W columns of the problems before it: sum r_j
     long long sp0;  // row-sum partials of the problems before it: sum r_j n_rowz_j
+    // its settings (those of the one settings struct on a handle made without settings per problem)
+    int mode;          // S64_KL / S64_ED / S64_IS / S64_GEN: a pass compiled per mode is launched once per mode present
+    int max_iter;      // its iteration limit (B64Args.max_iter is the largest: the stride of the histories)
+    double beta, div_scale, sparsity, conv_eps;
 };
 
 // one workgroup of a grouped product: problem, 64 x 64 tile of that problem's product, split
@@ -45,8 +53,8 @@ struct B64Sum {
 };
 
 struct B64Args {
-    int F, r, kind, max_iter;  // r: the largest rank (the rank, on a uniform batch)
-    double scalar, beta, conv_eps, div_scale;
+    int F, r, kind, max_iter;  // r: the largest rank (the rank, on a uniform batch); max_iter: the largest limit
+    int own_limit;             // settings per problem: a problem is stopped and counted when it reaches its own max_iter
     const B64Prob* prob;
     const double* S;  // r-vector sparsity (kind 1)
     double *V, *Lam, *R, *D, *H, *Num, *Den, *W, *Q, *P;
@@ -83,8 +91,9 @@ __global__ __launch_bounds__(256) void k_b64_ratio(B64Args a) {
     const int b = blockIdx.y;
     if (a.st[b].stop) return;
     const B64Prob p = a.prob[b];
+    if (p.mode != MODE) return;  // (another launch's problem)
     const long long o = p.fr0 * a.F;
-    s64_ratio_span<MODE>(a.V + o, a.Lam + o, a.R ? a.R + o : nullptr, a.D ? a.D + o : nullptr, (long long)a.F * p.T, a.beta, blockIdx.x,
+    s64_ratio_span<MODE>(a.V + o, a.Lam + o, a.R ? a.R + o : nullptr, a.D ? a.D + o : nullptr, (long long)a.F * p.T, p.beta, blockIdx.x,
                          gridDim.x);
 }
 
@@ -143,8 +152,9 @@ __global__ __launch_bounds__(256) void k_b64_hupd(B64Args a) {
     const int b = blockIdx.y;
     if (a.st[b].stop) return;
     const B64Prob p = a.prob[b];
+    if ((p.mode == S64_KL) != KL) return;
     const long long o = p.h0;
-    s64_hupd_span<KL>(a.H + o, a.Num + o, KL ? nullptr : a.Den + o, KL ? a.cs + p.w0 : nullptr, a.kind, a.scalar, a.S, p.r,
+    s64_hupd_span<KL>(a.H + o, a.Num + o, KL ? nullptr : a.Den + o, KL ? a.cs + p.w0 : nullptr, a.kind, p.sparsity, a.S, p.r,
                       (long long)p.r * p.T, blockIdx.x, gridDim.x);
 }
 
@@ -154,7 +164,7 @@ static __global__ __launch_bounds__(256) void k_b64_colsum(B64Args a) {
     const int b = blockIdx.y;
     if (a.st[b].stop) return;
     const B64Prob p = a.prob[b];
-    if ((int)blockIdx.x >= p.r) return;
+    if (p.mode != S64_KL || (int)blockIdx.x >= p.r) return;
     __shared__ double red[256];
     s64_colsum_col(a.W + p.w0 * a.F, a.F, a.cs + p.w0, (int)blockIdx.x, red);
 }
@@ -164,7 +174,7 @@ static __global__ __launch_bounds__(256) void k_b64_rowsum(B64Args a) {
     const int b = blockIdx.z;
     if (a.st[b].stop) return;
     const B64Prob p = a.prob[b];
-    if ((int)blockIdx.y >= p.n_rowz) return;
+    if (p.mode != S64_KL || (int)blockIdx.y >= p.n_rowz) return;
     s64_rowsum_chunk(a.H + p.h0, p.r, p.T, kS64RowChunk, a.sp + p.sp0, (int)blockIdx.y, blockIdx.x, gridDim.x);
 }
 
@@ -174,7 +184,7 @@ __global__ __launch_bounds__(256) void k_b64_wupd(B64Args a) {
     const int b = blockIdx.y;
     if (a.st[b].stop) return;
     const B64Prob p = a.prob[b];
-    if ((int)blockIdx.x >= p.r) return;
+    if ((p.mode == S64_KL) != KL || (int)blockIdx.x >= p.r) return;
     __shared__ double red[256];
     const long long o = p.w0 * a.F;
     s64_wupd_col<KL, true>(a.W + o, a.Q + o, KL ? nullptr : a.P + o, KL ? a.hs + p.w0 : nullptr, a.w_ind, a.F, nullptr,
@@ -188,8 +198,9 @@ __global__ __launch_bounds__(256) void k_b64_obj(B64Args a) {
     if (a.st[b].stop) return;
     __shared__ double red[256];
     const B64Prob p = a.prob[b];
+    if (p.mode != MODE) return;  // (uniform over the workgroup, before any barrier)
     const long long o = p.fr0 * a.F;
-    s64_obj_block<MODE>(a.V + o, a.Lam + o, (long long)a.F * p.T, a.beta, a.H + p.h0, a.kind, a.scalar, a.S, p.r,
+    s64_obj_block<MODE>(a.V + o, a.Lam + o, (long long)a.F * p.T, p.beta, a.H + p.h0, a.kind, p.sparsity, a.S, p.r,
                         (long long)p.r * p.T, a.part + (long long)b * 2 * kS64Blocks, red, blockIdx.x, gridDim.x);
 }
 
@@ -210,20 +221,39 @@ __global__ __launch_bounds__(256) void k_b64_mdi_obj(B64Args a) {
     if (a.st[b].stop) return;
     __shared__ double red[256];
     const B64Prob p = a.prob[b];
+    if (p.mode != MODE) return;
     const long long o = p.fr0 * a.F;
-    s64_mdi_obj_block<MODE>(a.V + o, a.M + o, a.Lam + o, (long long)a.F * p.T, a.beta, a.H + p.h0, a.kind, a.scalar, a.S, p.r,
+    s64_mdi_obj_block<MODE>(a.V + o, a.M + o, a.Lam + o, (long long)a.F * p.T, p.beta, a.H + p.h0, a.kind, p.sparsity, a.S, p.r,
                             (long long)p.r * p.T, a.part + (long long)b * 2 * kS64Blocks, red, blockIdx.x, gridDim.x);
 }
 
 // grid (B): the fixed tree over problem b's partials, its objective vectors and its stop test (src/sparse_nmf.m:272-284);
-// a problem that stops counts itself in n_stopped, which is all the host polls
+// a problem that stops counts itself in n_stopped, which is all the host polls.  With settings per problem (own_limit) a problem
+// whose test has not fired at its own max_iter is stopped there too, after its objective is recorded: n_iter = max_iter_b, the
+// value the single solve reports at the end of its loop.  (Thread 0 alone holds `fired` and writes the state.)
 static __global__ __launch_bounds__(256) void k_b64_stop(B64Args a, int it) {
     const int b = blockIdx.x;
     if (a.st[b].stop) return;
     __shared__ double red[256];
-    const bool fired = s64_stop_test(a.part + (long long)b * 2 * kS64Blocks, kS64Blocks, it, a.conv_eps, a.div_scale,
-                                     a.divh + (long long)b * a.max_iter, a.costh + (long long)b * a.max_iter, a.st + b, red);
+    const B64Prob p = a.prob[b];
+    bool fired = s64_stop_test(a.part + (long long)b * 2 * kS64Blocks, kS64Blocks, it, p.conv_eps, p.div_scale,
+                               a.divh + (long long)b * a.max_iter, a.costh + (long long)b * a.max_iter, a.st + b, red);
+    if (threadIdx.x == 0 && !fired && a.own_limit && it == p.max_iter) {
+        a.st[b].n_iter = it;
+        a.st[b].stop = 1;
+        fired = true;
+    }
     if (fired) atomicAdd(a.n_stopped, 1);
+}
+
+// grid (ceil(B / 256)): the iteration limit of its own without the objective (cost_check = 0, settings per problem): thread b
+// stops problem b after iteration it == max_iter_b and counts it.  An integer counter, and nobody waits on anybody.
+static __global__ __launch_bounds__(256) void k_b64_limit(B64Args a, int n_problems, int it) {
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= n_problems || a.st[b].stop || a.prob[b].max_iter != it) return;
+    a.st[b].n_iter = it;
+    a.st[b].stop = 1;
+    atomicAdd(a.n_stopped, 1);
 }
 
 }  // namespace snmf

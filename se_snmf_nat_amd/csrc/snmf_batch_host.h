@@ -11,6 +11,10 @@
 // A handle made by snmf_batch_create_ranks_fp64 carries a rank per problem (`ranks`): problem k's W is F x ranks[k] and its H
 // ranks[k] x T_k wherever a call below says r; p.r is the largest of them.  The life is the same; what such a handle refuses
 // (batch_create, take_h0) it refuses before any device work.
+// A handle made by snmf_batch_create_settings_fp64 carries settings per problem (`settings`): problem k's divergence, sparsity
+// weight, stop threshold and iteration limit wherever a call below says p.beta, p.sparsity_scalar, p.conv_eps or p.max_iter;
+// p.max_iter is the largest of the limits.  A run goes to that, the engine freezes a problem at its own limit and counts it in
+// the stopped counter, and get() reports the problem's own n_iter.  An engine that has no such form refuses in build().
 #pragma once
 #include <functional>
 #include <memory>
@@ -24,6 +28,12 @@ struct snmf_batch {
     int B = 0;
     std::vector<int32_t> ranks;  // one rank per problem; empty: every problem has p.r
     int rank_of(int k) const { return ranks.empty() ? p.r : ranks[k]; }
+    std::vector<snmf_problem_settings> settings;  // settings per problem; empty: every problem has those of p
+    snmf_problem_settings settings_of(int k) const {
+        return settings.empty() ? snmf_problem_settings{p.beta, p.sparsity_scalar, p.conv_eps, p.max_iter, 0} : settings[k];
+    }
+    bool any_can_stop = false;  // the stop test of some problem can fire (a conv_eps > 0 with the objective computed)
+    bool own_max_iter = false;  // some problem ends at a max_iter of its own, below p.max_iter
     bool upd_h = true, upd_w = true;
     std::vector<uint8_t> w_ind;
     std::vector<uint8_t> have;
@@ -106,17 +116,52 @@ snmf_batch* batch32_new();                     // snmf_tu_batch.hip: an fp32 eng
     (void)hipGetLastError();                                    \
     HIP_TRY(hipSetDevice((b)->ctx->device))
 
+// The settings per problem of a batch, checked without a device: the shared fields of p, then every s[k] as the four fields of an
+// snmf_params (a refusal names the problem), the scalar sparsity and p->max_iter = the largest limit.  q_out (may be nullptr)
+// receives p with T = 1 and the four fields of s[0] in the place of the ones the entry ignores.
+inline int batch_check_settings(const char* entry, const snmf_params* p, int32_t n, const snmf_problem_settings* s, snmf_params* q_out) {
+    if (!p || !s) return fail(SNMF_ERR_INVALID, "%s: NULL argument", entry);
+    snmf_params q = *p;
+    q.T = 1;  // (ignored: every problem brings its own)
+    q.beta = 1.0, q.sparsity_scalar = 0.0, q.conv_eps = 0.0, q.max_iter = 0;
+    SN_TRY(validate_params(&q));
+    int mi_max = 0;
+    for (int k = n - 1; k >= 0; --k) {  // (downwards: q ends with the fields of s[0])
+        if (s[k].reserved != 0) return fail(SNMF_ERR_INVALID, "%s: problem %d: reserved must be 0 (got %d)", entry, k, s[k].reserved);
+        q.beta = s[k].beta, q.sparsity_scalar = s[k].sparsity, q.conv_eps = s[k].conv_eps, q.max_iter = s[k].max_iter;
+        const int rc = validate_params(&q);
+        if (rc != SNMF_OK) {
+            const std::string why = snmf_last_error();
+            return fail(rc, "%s: problem %d: %s", entry, k, why.c_str());
+        }
+        mi_max = std::max(mi_max, (int)s[k].max_iter);
+    }
+    if (p->sparsity_kind != SNMF_SPARSITY_SCALAR)
+        return fail(SNMF_ERR_UNSUPPORTED, "%s: a batch with settings per problem takes a scalar sparsity", entry);
+    if (p->max_iter != mi_max) return fail(SNMF_ERR_DIM, "%s: params->max_iter = %d must be the largest max_iter, %d", entry, p->max_iter, mi_max);
+    q.max_iter = mi_max;
+    if (q_out) *q_out = q;
+    return SNMF_OK;
+}
+
 // Takes the engine `b` over (a failure deletes it).  entry: the C entry's name, for the messages.  Every refusal here and the
 // engine's own limits come before the device is touched.  with_ranks: r holds a rank per problem (p_in->r is the largest); such a
-// batch takes a scalar sparsity and masks that are all ones or all zeros, and has no missing-data form.
+// batch takes a scalar sparsity and masks that are all ones or all zeros, and has no missing-data form.  with_settings: s holds
+// settings per problem (batch_check_settings); such a batch takes a scalar sparsity and has no missing-data form.
 inline int batch_create(const char* entry, snmf_batch* b, snmf_ctx* ctx, const snmf_params* p_in, int32_t n_problems, const int32_t* T,
-                        snmf_batch** out, bool with_ranks = false, const int32_t* r = nullptr) {
+                        snmf_batch** out, bool with_ranks = false, const int32_t* r = nullptr, bool with_settings = false,
+                        const snmf_problem_settings* s = nullptr) {
     std::unique_ptr<snmf_batch> own(b);
-    if (!ctx || !p_in || !T || !out || (with_ranks && !r)) return fail(SNMF_ERR_INVALID, "%s: NULL argument", entry);
+    if (!ctx || !p_in || !T || !out || (with_ranks && !r) || (with_settings && !s)) return fail(SNMF_ERR_INVALID, "%s: NULL argument", entry);
     *out = nullptr;
     if (n_problems < 1) return fail(SNMF_ERR_INVALID, "%s: n_problems must be at least 1 (got %d)", entry, n_problems);
     b->p = *p_in;
     b->p.T = 1;  // (ignored: every problem brings its own)
+    if (with_settings) {
+        SN_TRY(batch_check_settings(entry, p_in, n_problems, s, &b->p));
+        if (b->masked) return fail(SNMF_ERR_UNSUPPORTED, "%s: a missing-data batch has one settings struct for all problems", entry);
+        b->settings.assign(s, s + n_problems);
+    }
     SN_TRY(validate_params(&b->p));
     if (with_ranks) {
         int r_max = 0;
@@ -153,6 +198,11 @@ inline int batch_create(const char* entry, snmf_batch* b, snmf_ctx* ctx, const s
     b->upd_w = n_w > 0;
     b->have.assign(n_problems, 0);
     b->have_s = b->p.sparsity_kind == SNMF_SPARSITY_SCALAR;
+    for (int i = 0; i < n_problems; ++i) {
+        const snmf_problem_settings si = b->settings_of(i);
+        b->any_can_stop |= b->p.cost_check != 0 && si.conv_eps > 0.0;
+        b->own_max_iter |= si.max_iter != b->p.max_iter;
+    }
     SN_TRY(b->build(T));
     *out = own.release();
     return SNMF_OK;
@@ -225,7 +275,8 @@ inline int batch_run(snmf_batch* b, int32_t n_iters) {
     hipStream_t st = b->ctx->stream;
     const int max_iter = b->p.max_iter;
     const int target = n_iters == 0 ? max_iter : (int)std::min<long long>(max_iter, (long long)b->it_done + n_iters);
-    const bool cc = b->p.cost_check != 0, can_stop = cc && b->p.conv_eps > 0.0;
+    // (some problem can stop before the run's end: by its stop test, or at an iteration limit of its own)
+    const bool cc = b->p.cost_check != 0, can_stop = b->any_can_stop || b->own_max_iter;
     const snmf_batch::Device d = b->device();
     b->ran = true;
     // A stopped problem is frozen on the device (its workgroups return at once) and its n_iter comes from its device state, so
@@ -390,7 +441,7 @@ int dnmf_batch(const char* entry, snmf_batch* (*make)(), snmf_ctx* ctx, const sn
 // ---- run_basis_train.m:58-91 for a batch of training signals (include/snmf.h: snmf_run_basis_train_audio_batch_*) -----------------
 // Two engines of one kind, made by `make`, over the same frame counts, both with every row and column updated (:85-86): the DFT
 // engine (p->F rows) and, with F_mel > 0, the Mel engine (F_mel rows), r = p->r = cluster_buff * R each -- or, with `ranks`, problem
-// k at ranks[k] = cluster_buff * R_k in both (p->r the largest).  `device_v` (the grouped
+// k at ranks[k] = cluster_buff * R_k in both (p->r the largest); with `s`, problem k with the settings s[k] in both.  `device_v` (the grouped
 // front-end of snmf_tu_frontend_batch.hip) writes TF_mag -- TF_DD applied where asked -- of every signal into the DFT engine's V
 // blocks and TF_Mel, projected from those blocks, into the Mel engine's; both engines then gather their exemplar columns from
 // the still unfloored V (the single entry's order, snmf_tu_dnmf.hip), run their floor, take the same H0 and solve.  Nothing
@@ -411,7 +462,7 @@ struct TrainInputs {
 template <typename TT>
 int train_batch_run(const char* entry, snmf_batch* (*make)(), snmf_ctx* ctx, const snmf_params* p, int32_t F_mel, int32_t n, const int32_t* T,
                     const TrainInputs<TT>& in, TT* const* B_DFT, TT* const* A_DFT, TT* const* B_Mel, TT* const* A_Mel, int32_t* n_iter,
-                    const int32_t* ranks = nullptr) {
+                    const int32_t* ranks = nullptr, const snmf_problem_settings* s = nullptr) {
     snmf_params q = *p;
     q.w_update_ind = q.h_update_ind = nullptr;
     if (F_mel > 0) {  // the Mel engine's limits before the DFT engine allocates
@@ -421,10 +472,10 @@ int train_batch_run(const char* entry, snmf_batch* (*make)(), snmf_ctx* ctx, con
         SN_TRY(probe->check_shape());
     }
     BatchOwner ed, em;
-    SN_TRY(batch_create(entry, make(), ctx, &q, n, T, &ed.b, ranks != nullptr, ranks));
+    SN_TRY(batch_create(entry, make(), ctx, &q, n, T, &ed.b, ranks != nullptr, ranks, s != nullptr, s));
     if (F_mel > 0) {
         q.F = F_mel;
-        SN_TRY(batch_create(entry, make(), ctx, &q, n, T, &em.b, ranks != nullptr, ranks));
+        SN_TRY(batch_create(entry, make(), ctx, &q, n, T, &em.b, ranks != nullptr, ranks, s != nullptr, s));
     }
     snmf_batch* const eng[2] = {ed.b, em.b};
     const int n_eng = em.b ? 2 : 1;

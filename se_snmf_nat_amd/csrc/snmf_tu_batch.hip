@@ -78,6 +78,8 @@ int Batch32::build(const int32_t* T) {
     const int F = p.F, r = p.r, n_problems = B;
     if (!ranks.empty())  // (the LDS geometry nk, nqk, S, nkg of this engine is one per launch; no entry leads here)
         return fail(SNMF_ERR_UNSUPPORTED, "the fp32 batch engine has one rank for all problems (a rank per problem: snmf_batch_create_ranks_fp64)");
+    if (!settings.empty())  // (the divergence is a template argument of every launch of this engine; no entry leads here)
+        return fail(SNMF_ERR_UNSUPPORTED, "the fp32 batch engine has one settings struct for all problems (settings per problem: snmf_batch_create_settings_fp64)");
     long long tiles = 0, chunks = 0;
     for (int i = 0; i < n_problems; ++i) {
         const long long nt = (T[i] + 31) / 32;
@@ -437,6 +439,12 @@ extern "C" int snmf_batch_create_fp64(snmf_ctx* ctx, const snmf_params* p, int32
 extern "C" int snmf_batch_create_ranks_fp64(snmf_ctx* ctx, const snmf_params* p, int32_t n_problems, const int32_t* T, const int32_t* r,
                                             snmf_batch** out) {
     return batch_create("snmf_batch_create_ranks_fp64", batch64_new(), ctx, p, n_problems, T, out, true, r);
+}
+extern "C" int snmf_batch_create_settings_fp64(snmf_ctx* ctx, const snmf_params* p, int32_t n_problems, const int32_t* T, const int32_t* r,
+                                               const snmf_problem_settings* s, snmf_batch** out) {
+    const char* entry = "snmf_batch_create_settings_fp64";
+    if (!s) return fail(SNMF_ERR_INVALID, "%s: NULL argument", entry);
+    return batch_create(entry, batch64_new(), ctx, p, n_problems, T, out, r != nullptr, r, true, s);
 }
 extern "C" int snmf_batch_create_mdi_fp64(snmf_ctx* ctx, const snmf_params* p, int32_t n_problems, const int32_t* T, snmf_batch** out) {
     return batch_create("snmf_batch_create_mdi_fp64", batch64_new(true), ctx, p, n_problems, T, out);

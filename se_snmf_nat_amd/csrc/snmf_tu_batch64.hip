@@ -10,6 +10,10 @@
 // With a rank per problem (snmf_batch_create_ranks_fp64) nothing else is launched either: the tables are built from r_i where they
 // were built from r, the packed arrays are sized by the sums of r_i and r_i T_i, and the grids that count columns or rows of a
 // rank-sized matrix are sized for the largest rank.
+// With settings per problem (snmf_batch_create_settings_fp64) the problems may differ in divergence: the passes compiled per
+// divergence are launched once per divergence present, the second H and W products (the denominators) have tile and sum tables
+// over the problems that are not KL, the column and row sums cover the KL problems, and a Euclidean problem's products read V
+// and Lam where the others read R and D.  With one divergence present the launches of an iteration are what they were.
 #include "snmf_internal.h"
 #include "snmf_batch64.h"
 #include "snmf_batch_host.h"
@@ -35,7 +39,10 @@ struct Product {  // one product of a family: every problem's arguments, and the
 };
 
 struct Batch64 final : snmf_batch {
-    int mode = S64_KL;
+    bool has[4] = {false, false, false, false};  // the modes (S64_*) present among the problems
+    int n_modes = 0, min_mi = 0;                 // distinct modes; the smallest iteration limit (a.max_iter is the largest)
+    bool any_kl = false, any_nonkl = false;
+    std::vector<uint8_t> limit_at;               // cost_check = 0 with settings: some problem's own limit is iteration it
     std::vector<B64Prob> prob;
     std::vector<long long> z0;  // first double of each problem's split partials
     long long sumT = 0, sumRz = 0, sumZ = 0;
@@ -50,9 +57,10 @@ struct Batch64 final : snmf_batch {
     bool lam_done = false;    // Lam = max(W * H, flr) of the scaled initial factors has been formed since the last reset
     B64Prob* dprob = nullptr;
     uint8_t* dwi = nullptr;
-    Family fLam, fH, fW;
+    Family fLam, fH, fW, fHd, fWd;  // fHd, fWd: the H and W families over the problems that are not KL (pDen, pP)
     Product pLam, pNum, pDen, pQ, pP;
-    B64Sum* sRow = nullptr;
+    B64Sum* sRow = nullptr;  // the row sums of H of the KL problems, n_row entries
+    int n_row = 0;
     void* block = nullptr;
     size_t bytes = 0;
     int launches = 0;  // per iteration
@@ -99,7 +107,9 @@ struct Batch64 final : snmf_batch {
 size_t carve(Batch64* s, void* base) {
     const snmf_params& p = s->p;
     const size_t F = p.F, r = p.r, nB = s->B, sT = (size_t)s->sumT, sR = (size_t)s->sumR, sRT = (size_t)s->sumRT;
-    const bool kl = s->mode == S64_KL, ed = s->mode == S64_ED;
+    // kl / ed: every problem is; a mixed batch has the arrays of every mode present, each sized for all problems
+    const bool kl = !s->any_nonkl, ed = !s->has[S64_KL] && !s->has[S64_IS] && !s->has[S64_GEN];
+    const bool need_d = s->has[S64_IS] || s->has[S64_GEN], need_kl = s->any_kl;
     B64Args& a = s->a;
     Carve64 c(base);
     a.V = c.get<double>(F * sT);
@@ -111,19 +121,19 @@ size_t carve(Batch64* s, void* base) {
     }
     a.M = s->Mblk;
     a.R = ed ? nullptr : c.get<double>(F * sT);
-    a.D = (ed || kl) ? nullptr : c.get<double>(F * sT);
+    a.D = need_d ? c.get<double>(F * sT) : nullptr;
     a.H = c.get<double>(sRT);
     a.W = c.get<double>(F * sR);
     a.Num = a.Den = a.cs = a.Q = a.P = a.hs = a.sp = nullptr;
     if (s->upd_h) {
         a.Num = c.get<double>(sRT);
         if (!kl) a.Den = c.get<double>(sRT);
-        else a.cs = c.get<double>(sR);
+        if (need_kl) a.cs = c.get<double>(sR);
     }
     if (s->upd_w) {
         a.Q = c.get<double>(F * sR);
         if (!kl) a.P = c.get<double>(F * sR);
-        else {
+        if (need_kl) {
             a.hs = c.get<double>(sR);
             a.sp = c.get<double>((size_t)s->sumSp);
         }
@@ -146,6 +156,7 @@ size_t carve(Batch64* s, void* base) {
         s->pNum.args = c.get<Gemm64Args>(nB);
         s->pNum.sums = c.get<B64Sum>(nB);
         if (!kl) {
+            s->fHd.tiles = c.get<B64Tile>((size_t)s->fHd.n);
             s->pDen.args = c.get<Gemm64Args>(nB);
             s->pDen.sums = c.get<B64Sum>(nB);
         }
@@ -155,11 +166,11 @@ size_t carve(Batch64* s, void* base) {
         s->pQ.args = c.get<Gemm64Args>(nB);
         s->pQ.sums = c.get<B64Sum>(nB);
         if (!kl) {
+            s->fWd.tiles = c.get<B64Tile>((size_t)s->fWd.n);
             s->pP.args = c.get<Gemm64Args>(nB);
             s->pP.sums = c.get<B64Sum>(nB);
-        } else {
-            s->sRow = c.get<B64Sum>(nB);
         }
+        if (need_kl) s->sRow = c.get<B64Sum>(nB);
     }
     a.S = s->S;
     a.w_ind = s->dwi;
@@ -172,8 +183,13 @@ int Batch64::reset() {
     const size_t nB = (size_t)B;
     h_st.assign(nB, Solve64State{0, 0, INFINITY});  // src/sparse_nmf.m:168
     lam_done = false;
+    int n0 = 0;  // settings per problem: a problem with max_iter = 0 beside others is stopped before the first iteration
+    if (a.own_limit)
+        for (size_t k = 0; k < nB; ++k)
+            if (prob[k].max_iter == 0) h_st[k].stop = 1, ++n0;
     HIP_TRY(hipMemcpyAsync(a.st, h_st.data(), sizeof(Solve64State) * nB, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(a.n_stopped, 0, sizeof(int), st));
+    if (n0) HIP_TRY(hipMemcpyAsync(a.n_stopped, &n0, sizeof(int), hipMemcpyHostToDevice, st));  // (the synchronise below keeps n0 alive)
+    else HIP_TRY(hipMemsetAsync(a.n_stopped, 0, sizeof(int), st));
     HIP_TRY(hipMemsetAsync(a.divh, 0, sizeof(double) * nB * a.max_iter, st));  // :171-173
     HIP_TRY(hipMemsetAsync(a.costh, 0, sizeof(double) * nB * a.max_iter, st));
     HIP_TRY(hipStreamSynchronize(st));  // (h_st is a pageable source, and the next run reads the states back into it)
@@ -186,16 +202,24 @@ int Batch64::build(const int32_t* T) {
     if (n_problems > kGridYMax)
         return fail(SNMF_ERR_UNSUPPORTED, "%d problems are above the fp64 batch's limit of %d (a launch grid's second dimension)", n_problems,
                     kGridYMax);
-    mode = p.beta == 1.0 ? S64_KL : (p.beta == 2.0 ? S64_ED : (p.beta == 0.0 ? S64_IS : S64_GEN));
-    const bool kl = mode == S64_KL, ed = mode == S64_ED;
 
-    // ---- sizes, from the frame counts and the ranks alone
+    // ---- sizes, from the frame counts, the ranks and the modes alone
     prob.resize(n_problems);
     z0.resize(n_problems);
     min_r = rank_of(0);
+    min_mi = settings_of(0).max_iter;
     for (int i = 0; i < n_problems; ++i) {
         B64Prob& q = prob[i];
         const int r = rank_of(i);
+        const snmf_problem_settings si = settings_of(i);  // (the one settings struct on a handle made without settings per problem)
+        q.mode = si.beta == 1.0 ? S64_KL : (si.beta == 2.0 ? S64_ED : (si.beta == 0.0 ? S64_IS : S64_GEN));
+        q.max_iter = si.max_iter;
+        q.beta = si.beta;
+        q.div_scale = q.mode == S64_GEN ? si.beta * (si.beta - 1.0) : 1.0;
+        q.sparsity = si.sparsity;
+        q.conv_eps = si.conv_eps;
+        has[q.mode] = true;
+        min_mi = std::min(min_mi, (int)si.max_iter);
         q.T = T[i];
         q.n_rowz = (T[i] + kS64RowChunk - 1) / kS64RowChunk;
         q.r = r;
@@ -215,6 +239,10 @@ int Batch64::build(const int32_t* T) {
         fLam.n += tiles_of(F, T[i]) * n_splits(r, kS64ChunkK);
         if (upd_h) fH.n += tiles_of(r, T[i]) * n_splits(F, kS64ChunkK);
         if (upd_w) fW.n += tiles_of(F, r) * n_splits(T[i], kS64ChunkK);
+        if (q.mode != S64_KL) {  // the denominators W' * D and D * H'
+            if (upd_h) fHd.n += tiles_of(r, T[i]) * n_splits(F, kS64ChunkK);
+            if (upd_w) fWd.n += tiles_of(F, r) * n_splits(T[i], kS64ChunkK);
+        }
         // split partials: the largest over this problem's products (carve64 of the single solve)
         size_t need = split_partials(F, T[i], r, kS64ChunkK);
         if (upd_h) need = std::max(need, split_partials(r, T[i], F, kS64ChunkK));
@@ -232,10 +260,15 @@ int Batch64::build(const int32_t* T) {
     a.F = F, a.r = p.r;
     a.kind = p.sparsity_kind;
     a.max_iter = std::max(1, p.max_iter);
-    a.scalar = p.sparsity_scalar;
-    a.beta = p.beta;
-    a.conv_eps = p.conv_eps;
-    a.div_scale = mode == S64_GEN ? p.beta * (p.beta - 1.0) : 1.0;
+    a.own_limit = settings.empty() ? 0 : 1;
+    n_modes = (int)has[0] + (int)has[1] + (int)has[2] + (int)has[3];
+    any_kl = has[S64_KL];
+    any_nonkl = n_modes > (any_kl ? 1 : 0);
+    const bool kl = !any_nonkl;
+    if (a.own_limit && !p.cost_check) {  // the iterations after which k_b64_limit has a problem to stop
+        limit_at.assign((size_t)p.max_iter + 1, 0);
+        for (const B64Prob& q : prob) limit_at[q.max_iter] = 1;
+    }
     bytes = carve(this, nullptr);
     mask_bytes = masked ? sizeof(double) * (size_t)F * (size_t)sumT : 0;
 
@@ -257,9 +290,7 @@ int Batch64::build(const int32_t* T) {
     if (carve(this, block) != bytes) return fail(SNMF_ERR_INTERNAL, "fp64 batch: the two walks over the device block differ");
 
     // ---- tables: per problem the arguments gemm64() makes for it alone, then (split, tile) in the single launch's order
-    const double* Rm = ed ? a.V : a.R;
-    const double* Dm = ed ? a.Lam : a.D;
-    std::vector<B64Tile> tLam((size_t)fLam.n), tH((size_t)fH.n), tW((size_t)fW.n);
+    std::vector<B64Tile> tLam((size_t)fLam.n), tH((size_t)fH.n), tW((size_t)fW.n), tHd((size_t)fHd.n), tWd((size_t)fWd.n);
     std::vector<Gemm64Args> gLam(n_problems), gNum(n_problems), gDen(n_problems), gQ(n_problems), gP(n_problems);
     std::vector<B64Sum> uLam, uNum, uDen, uQ, uP, uRow;
     auto split_entry = [&](std::vector<B64Sum>& u, Product& pr, double* zb, int nz, double* C, long long rsC, long long csC, int M, int N,
@@ -274,10 +305,13 @@ int Batch64::build(const int32_t* T) {
         for (int z = 0; z < nz; ++z)
             for (int l = 0; l < nt; ++l) t[at++] = B64Tile{i, l, z};
     };
-    size_t atLam = 0, atH = 0, atW = 0;
+    size_t atLam = 0, atH = 0, atW = 0, atHd = 0, atWd = 0;
     for (int i = 0; i < n_problems; ++i) {
         const B64Prob& q = prob[i];
         const int Ti = q.T, r = q.r;
+        const bool kl_i = q.mode == S64_KL, ed_i = q.mode == S64_ED;
+        const double* Rm = ed_i ? a.V : a.R;  // Euclidean: R = V, D = Lam are used where they lie
+        const double* Dm = ed_i ? a.Lam : a.D;
         const long long oFT = q.fr0 * F, oRT = q.h0, oFR = q.w0 * F;
         double* zb = zbuf ? zbuf + z0[i] : nullptr;
         const int* stop = &a.st[i].stop;
@@ -291,8 +325,9 @@ int Batch64::build(const int32_t* T) {
             const int nz = s64_gemm_plan(&gNum[i], W, F, 1, Rm + oFT, 1, F, a.Num + oRT, 1, r, r, Ti, F, false, zb, stop);
             add_tiles(tH, atH, i, gNum[i], nz);
             split_entry(uNum, pNum, zb, nz, a.Num + oRT, 1, r, r, Ti, false, stop);
-            if (!kl) {
+            if (!kl_i) {
                 s64_gemm_plan(&gDen[i], W, F, 1, Dm + oFT, 1, F, a.Den + oRT, 1, r, r, Ti, F, false, zb, stop);
+                add_tiles(tHd, atHd, i, gDen[i], nz);
                 split_entry(uDen, pDen, zb, nz, a.Den + oRT, 1, r, r, Ti, false, stop);
             }
         }
@@ -300,15 +335,16 @@ int Batch64::build(const int32_t* T) {
             const int nz = s64_gemm_plan(&gQ[i], Rm + oFT, 1, F, H, r, 1, a.Q + oFR, 1, F, F, r, Ti, false, zb, stop);
             add_tiles(tW, atW, i, gQ[i], nz);
             split_entry(uQ, pQ, zb, nz, a.Q + oFR, 1, F, F, r, false, stop);
-            if (!kl) {
+            if (!kl_i) {
                 s64_gemm_plan(&gP[i], Dm + oFT, 1, F, H, r, 1, a.P + oFR, 1, F, F, r, Ti, false, zb, stop);
+                add_tiles(tWd, atWd, i, gP[i], nz);
                 split_entry(uP, pP, zb, nz, a.P + oFR, 1, F, F, r, false, stop);
             } else {  // the row sums of H: k_s64_sumz(dsp, n_rowz, r, r, dhs, 1, 0, 0) of the single solve
                 uRow.push_back(B64Sum{a.sp + q.sp0, a.hs + q.w0, (long long)r, 1, 0, q.n_rowz, r, 0, stop});
             }
         }
     }
-    if ((long long)atLam != fLam.n || (long long)atH != fH.n || (long long)atW != fW.n)
+    if ((long long)atLam != fLam.n || (long long)atH != fH.n || (long long)atW != fW.n || (long long)atHd != fHd.n || (long long)atWd != fWd.n)
         return fail(SNMF_ERR_INTERNAL, "fp64 batch: a tile table does not have the size it was measured at");
     hipStream_t st = ctx->stream;
     int rc = SNMF_OK;
@@ -327,11 +363,14 @@ int Batch64::build(const int32_t* T) {
     up(fLam.tiles, tLam.data(), sizeof(B64Tile) * tLam.size());
     if (fH.tiles) up(fH.tiles, tH.data(), sizeof(B64Tile) * tH.size());
     if (fW.tiles) up(fW.tiles, tW.data(), sizeof(B64Tile) * tW.size());
+    if (fHd.tiles) up(fHd.tiles, tHd.data(), sizeof(B64Tile) * tHd.size());
+    if (fWd.tiles) up(fWd.tiles, tWd.data(), sizeof(B64Tile) * tWd.size());
     up_product(pLam, gLam, uLam);
     up_product(pNum, gNum, uNum);
     up_product(pDen, gDen, uDen);
     up_product(pQ, gQ, uQ);
     up_product(pP, gP, uP);
+    n_row = (int)uRow.size();
     if (sRow) up(sRow, uRow.data(), sizeof(B64Sum) * uRow.size());
     if (rc == SNMF_OK && hipStreamSynchronize(st) != hipSuccess) rc = fail(SNMF_ERR_NO_DEVICE, "hipStreamSynchronize failed");
     if (rc != SNMF_OK) return rc;
@@ -340,10 +379,10 @@ int Batch64::build(const int32_t* T) {
     {
         auto prod = [](const Product& pr) { return pr.args ? 1 + (pr.n_sums ? 1 : 0) : 0; };
         int n = 0;
-        const int lam = prod(pLam), ratio = ed ? 0 : 1;
-        if (upd_h) n += ratio + prod(pNum) + (kl ? 1 : prod(pDen)) + 1 + lam;
-        if (upd_w) n += ratio + prod(pQ) + (kl ? 2 : prod(pP)) + 1 + lam;
-        if (p.cost_check) n += 2;
+        const int lam = prod(pLam), ratio = n_modes - (has[S64_ED] ? 1 : 0), upd = (any_kl ? 1 : 0) + (any_nonkl ? 1 : 0);
+        if (upd_h) n += ratio + prod(pNum) + (any_kl ? 1 : 0) + (kl ? 0 : prod(pDen)) + upd + lam;
+        if (upd_w) n += ratio + prod(pQ) + (any_kl ? 2 : 0) + (kl ? 0 : prod(pP)) + upd + lam;
+        if (p.cost_check) n += n_modes + 1;
         else if (masked) n += 1;  // the re-imputation runs objective or not (src/snmf_mdi.m:251-254)
         launches = n;
     }
@@ -516,42 +555,38 @@ int elem_grid(const Batch64* s, long long rows) {
     return (int)std::max<long long>(1, std::min<long long>((rows * s->maxT + 255) / 256, kElemGridMax));
 }
 
+// (the passes compiled per mode: one launch per mode present, whose workgroups return at once on a problem of another mode)
 int ratio(Batch64* s) {
     const dim3 g(elem_grid(s, s->a.F), s->B);
-    switch (s->mode) {
-        case S64_KL: return grouped(s, k_b64_ratio<S64_KL>, g);
-        case S64_IS: return grouped(s, k_b64_ratio<S64_IS>, g);
-        case S64_GEN: return grouped(s, k_b64_ratio<S64_GEN>, g);
-        default: return SNMF_OK;  // Euclidean: R = V, D = Lam
-    }
+    if (s->has[S64_KL]) SN_TRY(grouped(s, k_b64_ratio<S64_KL>, g));
+    if (s->has[S64_IS]) SN_TRY(grouped(s, k_b64_ratio<S64_IS>, g));
+    if (s->has[S64_GEN]) SN_TRY(grouped(s, k_b64_ratio<S64_GEN>, g));
+    return SNMF_OK;  // Euclidean: R = V, D = Lam
 }
 
 int objective(Batch64* s) {
     const dim3 g(kS64Blocks, s->B);
-    switch (s->mode) {
-        case S64_KL: return grouped(s, k_b64_obj<S64_KL>, g);
-        case S64_ED: return grouped(s, k_b64_obj<S64_ED>, g);
-        case S64_IS: return grouped(s, k_b64_obj<S64_IS>, g);
-        default: return grouped(s, k_b64_obj<S64_GEN>, g);
-    }
+    if (s->has[S64_KL]) SN_TRY(grouped(s, k_b64_obj<S64_KL>, g));
+    if (s->has[S64_ED]) SN_TRY(grouped(s, k_b64_obj<S64_ED>, g));
+    if (s->has[S64_IS]) SN_TRY(grouped(s, k_b64_obj<S64_IS>, g));
+    if (s->has[S64_GEN]) SN_TRY(grouped(s, k_b64_obj<S64_GEN>, g));
+    return SNMF_OK;
 }
 
 // the re-imputation and the objective of the imputed v in one pass, in the place of objective() on a masked batch
 int mdi_objective(Batch64* s) {
     const dim3 g(kS64Blocks, s->B);
-    switch (s->mode) {
-        case S64_KL: return grouped(s, k_b64_mdi_obj<S64_KL>, g);
-        case S64_ED: return grouped(s, k_b64_mdi_obj<S64_ED>, g);
-        case S64_IS: return grouped(s, k_b64_mdi_obj<S64_IS>, g);
-        default: return grouped(s, k_b64_mdi_obj<S64_GEN>, g);
-    }
+    if (s->has[S64_KL]) SN_TRY(grouped(s, k_b64_mdi_obj<S64_KL>, g));
+    if (s->has[S64_ED]) SN_TRY(grouped(s, k_b64_mdi_obj<S64_ED>, g));
+    if (s->has[S64_IS]) SN_TRY(grouped(s, k_b64_mdi_obj<S64_IS>, g));
+    if (s->has[S64_GEN]) SN_TRY(grouped(s, k_b64_mdi_obj<S64_GEN>, g));
+    return SNMF_OK;
 }
 
 // One iteration, the launches of solve64_run grouped over the problems.
 int Batch64::iterate(int it) {
     hipStream_t st = ctx->stream;
     const int r = a.r;
-    const bool kl = mode == S64_KL;
     auto lam = [&]() { return product(this, fLam, pLam); };  // lambda = max(w * h, flr)
     if (it == 1) {                                           // of the scaled initial factors
         SN_TRY(lam());
@@ -561,21 +596,25 @@ int Batch64::iterate(int it) {
     if (upd_h) {  // :189-208
         SN_TRY(ratio(this));
         SN_TRY(product(this, fH, pNum));
-        if (!kl) SN_TRY(product(this, fH, pDen));
-        else SN_TRY(grouped(this, k_b64_colsum, g_col));
-        SN_TRY(kl ? grouped(this, k_b64_hupd<true>, g_rt) : grouped(this, k_b64_hupd<false>, g_rt));
+        if (any_nonkl) SN_TRY(product(this, fHd, pDen));
+        if (any_kl) {
+            SN_TRY(grouped(this, k_b64_colsum, g_col));
+            SN_TRY(grouped(this, k_b64_hupd<true>, g_rt));
+        }
+        if (any_nonkl) SN_TRY(grouped(this, k_b64_hupd<false>, g_rt));
         SN_TRY(lam());
     }
     if (upd_w) {  // :212-244
         SN_TRY(ratio(this));
         SN_TRY(product(this, fW, pQ));
-        if (!kl) SN_TRY(product(this, fW, pP));
-        else {
+        if (any_nonkl) SN_TRY(product(this, fWd, pP));
+        if (any_kl) {
             SN_TRY(grouped(this, k_b64_rowsum, dim3((r + 255) / 256, max_rowz, B)));
-            hipLaunchKernelGGL(k_b64_sumz, dim3(grid64(r), B), dim3(256), 0, st, (const B64Sum*)sRow);
+            hipLaunchKernelGGL(k_b64_sumz, dim3(grid64(r), n_row), dim3(256), 0, st, (const B64Sum*)sRow);
             HIP_TRY(hipGetLastError());
+            SN_TRY(grouped(this, k_b64_wupd<true>, g_col));
         }
-        SN_TRY(kl ? grouped(this, k_b64_wupd<true>, g_col) : grouped(this, k_b64_wupd<false>, g_col));
+        if (any_nonkl) SN_TRY(grouped(this, k_b64_wupd<false>, g_col));
         SN_TRY(lam());
     }
     if (masked && !p.cost_check)  // src/snmf_mdi.m:251-254: v is re-imputed in every iteration, objective or not
@@ -583,6 +622,9 @@ int Batch64::iterate(int it) {
     if (p.cost_check) {  // :248-284
         SN_TRY(masked ? mdi_objective(this) : objective(this));
         hipLaunchKernelGGL(k_b64_stop, dim3(B), dim3(256), 0, st, a, it);
+        HIP_TRY(hipGetLastError());
+    } else if (!limit_at.empty() && it < p.max_iter && limit_at[it]) {  // settings per problem: the limits below the largest
+        hipLaunchKernelGGL(k_b64_limit, dim3((B + 255) / 256), dim3(256), 0, st, a, B, it);
         HIP_TRY(hipGetLastError());
     }
     return SNMF_OK;
@@ -614,17 +656,20 @@ int Batch64::fetch_v_mdi(int k, double* V_mdi, int64_t ld) {
 }
 
 void Batch64::describe(char* buf, size_t buflen) const {
-    const char* mn = mode == S64_KL ? "kl" : (mode == S64_ED ? "ed" : (mode == S64_IS ? "is" : "beta"));
+    const char* mn = n_modes > 1 ? "mixed" : (has[S64_KL] ? "kl" : (has[S64_ED] ? "ed" : (has[S64_IS] ? "is" : "beta")));
     const int ge = elem_grid(this, a.F), gh = elem_grid(this, a.r);
-    const int n = snprintf(buf, buflen,
+    int n = snprintf(buf, buflen,
              "batch fp64 B=%d F=%d r=%d %s upd_h=%d upd_w=%d frames=%lld | k_b64_gemm tables (problem, 64x64 tile, split of %d): "
              "lam=%lld h=%lld w=%lld x256 | k_b64_sumz entries lam=%d h=%d w=%d rows=%d | k_b64_ratio grid=(%d,%d) k_b64_hupd grid=(%d,%d) "
              "k_b64_colsum/k_b64_wupd grid=(%d,%d) k_b64_rowsum grid=(%d,%d,%d) %s grid=(%d,%d) k_b64_stop grid=%d | "
              "launches_per_iter=%d bytes=%zu poll_every=%d",
              B, a.F, a.r, mn, (int)upd_h, (int)upd_w, sumT, kS64ChunkK, fLam.n, fH.n, fW.n, pLam.n_sums, pNum.n_sums, pQ.n_sums,
-             sRow ? B : 0, ge, B, gh, B, a.r, B, (a.r + 255) / 256, max_rowz, B, masked ? "k_b64_mdi_obj" : "k_b64_obj", kS64Blocks, B, B, launches, bytes, kPollEvery);
+             n_row, ge, B, gh, B, a.r, B, (a.r + 255) / 256, max_rowz, B, masked ? "k_b64_mdi_obj" : "k_b64_obj", kS64Blocks, B, B, launches, bytes, kPollEvery);
     if (!ranks.empty() && n > 0 && (size_t)n < buflen)  // (r above is the largest)
-        snprintf(buf + n, buflen - (size_t)n, " | ranks: min=%d max=%d sum=%lld h_elems=%lld", min_r, a.r, sumR, sumRT);
+        n += snprintf(buf + n, buflen - (size_t)n, " | ranks: min=%d max=%d sum=%lld h_elems=%lld", min_r, a.r, sumR, sumRT);
+    if (!settings.empty() && n > 0 && (size_t)n < buflen)
+        n += snprintf(buf + n, buflen - (size_t)n, " | settings: modes=%d max_iter min=%d max=%d h_den_tiles=%lld w_den_tiles=%lld", n_modes, min_mi,
+                      p.max_iter, fHd.n, fWd.n);
     if (masked && n > 0 && (size_t)n < buflen)  // (bytes above counts both blocks)
         snprintf(buf + n, buflen - (size_t)n, " | mdi: k_b64_mdi_impute grid=(%d,%d) mask_bytes=%zu v_mdi_scratch_bytes=%zu", ge, B,
                  mask_bytes, sizeof(double) * (size_t)a.F * (size_t)maxT);

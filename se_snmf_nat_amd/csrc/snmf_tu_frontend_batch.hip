@@ -335,12 +335,13 @@ int dnmf_audio_batch(const char* entry, snmf_batch* (*make)(), snmf_ctx* ctx, co
 // for double, round to nearest for float) instead of the transfer.  Everything else is the same code.
 // n_atoms != nullptr (the _ranks_fp64 entries): problem k trains n_atoms[k] atoms -- sample_idx[k] holds that many indices, its
 // outputs have that many columns / rows -- and p->r is the largest; nullptr: p->r for every problem.
+// st != nullptr (the _settings_fp64 entries): problem k is solved with the settings st[k] in both engines.
 template <typename S>
 int train_audio_batch(const char* entry, snmf_batch* (*make)(), snmf_ctx* ctx, const snmf_params* p, const snmf_stft_params* sp, double alpha_eta_dd,
                       const S* mel, int32_t mel_M, int32_t n, const S* const* samples, const int64_t* n_samples,
                       const int64_t* const* sample_idx, int32_t train_exemplar, const double* const* H0, const uint64_t* seed,
                       double* const* B_DFT, double* const* A_DFT, double* const* B_Mel, double* const* A_Mel, int32_t* n_iter,
-                      const snmf_train_signals* ts = nullptr, const int32_t* n_atoms = nullptr) {
+                      const snmf_train_signals* ts = nullptr, const int32_t* n_atoms = nullptr, const snmf_problem_settings* st = nullptr) {
     if (!ctx || !p || (!ts && (!samples || !n_samples)) || !sample_idx || !B_DFT) return fail(SNMF_ERR_INVALID, "%s: NULL argument", entry);
     if (ts) {
         if (ts->ctx != ctx) return fail(SNMF_ERR_INVALID, "%s: the signals were assembled on another context", entry);
@@ -357,7 +358,9 @@ int train_audio_batch(const char* entry, snmf_batch* (*make)(), snmf_ctx* ctx, c
         }
         if (p->r != r_max) return fail(SNMF_ERR_DIM, "%s: params->r = %d must be the largest n_atoms, %d", entry, p->r, r_max);
     }
-    {
+    if (st) {  // (the four fields of p are ignored: every s[k] is checked in their place)
+        SN_TRY(batch_check_settings(entry, p, n, st, nullptr));
+    } else {
         snmf_params q = *p;
         q.T = 1;  // (ignored: every problem brings its own)
         SN_TRY(validate_params(&q));
@@ -423,7 +426,7 @@ int train_audio_batch(const char* entry, snmf_batch* (*make)(), snmf_ctx* ctx, c
         }
         return fe.run(n, s0.data(), T.data(), dft.data(), mel ? melb.data() : nullptr, alpha_eta_dd);
     };
-    return train_batch_run<double>(entry, make, ctx, p, (int32_t)Fm, n, T.data(), in, B_DFT, A_DFT, B_Mel, A_Mel, n_iter, n_atoms);
+    return train_batch_run<double>(entry, make, ctx, p, (int32_t)Fm, n, T.data(), in, B_DFT, A_DFT, B_Mel, A_Mel, n_iter, n_atoms, st);
 }
 
 snmf_batch* make32() { return batch32_new(); }
@@ -490,6 +493,30 @@ extern "C" int snmf_run_basis_train_signals_batch_ranks_fp64(snmf_ctx* ctx, cons
     if (!signals || !n_atoms) return fail(SNMF_ERR_INVALID, "%s: NULL argument", entry);
     return train_audio_batch<double>(entry, make64, ctx, p, sp, alpha_eta_dd, mel, mel_M, 0, nullptr, nullptr, sample_idx, train_exemplar, H0, seed,
                                      B_DFT, A_DFT, B_Mel, A_Mel, n_iter, signals, n_atoms);
+}
+
+extern "C" int snmf_run_basis_train_audio_batch_settings_fp64(snmf_ctx* ctx, const snmf_params* p, const snmf_stft_params* sp, double alpha_eta_dd,
+                                                              const double* mel, int32_t mel_M, int32_t n_problems, const double* const* samples,
+                                                              const int64_t* n_samples, const int32_t* n_atoms, const int64_t* const* sample_idx,
+                                                              int32_t train_exemplar, const double* const* H0, const uint64_t* seed,
+                                                              double* const* B_DFT, double* const* A_DFT, double* const* B_Mel,
+                                                              double* const* A_Mel, int32_t* n_iter, const snmf_problem_settings* s) {
+    const char* entry = "snmf_run_basis_train_audio_batch_settings_fp64";
+    if (!s) return fail(SNMF_ERR_INVALID, "%s: NULL argument", entry);
+    return train_audio_batch<double>(entry, make64, ctx, p, sp, alpha_eta_dd, mel, mel_M, n_problems, samples, n_samples, sample_idx,
+                                     train_exemplar, H0, seed, B_DFT, A_DFT, B_Mel, A_Mel, n_iter, nullptr, n_atoms, s);
+}
+extern "C" int snmf_run_basis_train_signals_batch_settings_fp64(snmf_ctx* ctx, const snmf_params* p, const snmf_stft_params* sp,
+                                                                double alpha_eta_dd, const double* mel, int32_t mel_M,
+                                                                const snmf_train_signals* signals, const int32_t* n_atoms,
+                                                                const int64_t* const* sample_idx, int32_t train_exemplar,
+                                                                const double* const* H0, const uint64_t* seed, double* const* B_DFT,
+                                                                double* const* A_DFT, double* const* B_Mel, double* const* A_Mel,
+                                                                int32_t* n_iter, const snmf_problem_settings* s) {
+    const char* entry = "snmf_run_basis_train_signals_batch_settings_fp64";
+    if (!signals || !s) return fail(SNMF_ERR_INVALID, "%s: NULL argument", entry);
+    return train_audio_batch<double>(entry, make64, ctx, p, sp, alpha_eta_dd, mel, mel_M, 0, nullptr, nullptr, sample_idx, train_exemplar, H0, seed,
+                                     B_DFT, A_DFT, B_Mel, A_Mel, n_iter, signals, n_atoms, s);
 }
 
 extern "C" int snmf_stft_features_batch_f32(snmf_ctx* ctx, const snmf_stft_params* sp, int32_t n_signals, const float* const* samples,

@@ -98,7 +98,8 @@ def run_basis_train_signal(s_full, R, p, *, DC_bin=None, sample_idx=None, ctx=No
     return {"B_DFT_sub": B_DFT, "B_Mel_sub": B_Mel, "A_DFT_sub": A_DFT, "A_Mel_sub": A_Mel}  # :130-134
 
 
-def run_basis_train_signal_batch(signals, R, p, *, DC_bin=None, sample_idx=None, ctx=None, h0="host", precision="fp32", info=None):
+def run_basis_train_signal_batch(signals, R, p, *, DC_bin=None, sample_idx=None, ctx=None, h0="host", precision="fp32", info=None,
+                                 settings=None):
     """[run_basis_train_signal(s_k, R, p, ...) for s_k in signals], solved together: the loop l = 1:length(DB_path_list) of
     run_basis_train.m, one training signal per event class or noise type, in ONE call across the C ABI
     (snmf_run_basis_train_audio_batch_f64; precision="fp64": _fp64).  The signals (any lengths) go up as one slab, TF_mag, TF_DD and
@@ -109,6 +110,10 @@ def run_basis_train_signal_batch(signals, R, p, *, DC_bin=None, sample_idx=None,
     precision="fp64" (snmf_run_basis_train_audio_batch_ranks_fp64; SnmfError status 8 in fp32).  Problem k then has
     n_ex_k = cluster_buff * R_k exemplar columns in its default sample_idx, its H0 and its results, and the host epilogue
     (renormalise + 1e-9, reduce_rank to R_k when cluster_buff > 1) runs with its own R_k.
+    settings: None, or a list with one dict per problem with keys among cf, beta, sparsity, max_iter, conv_eps (a missing key takes
+    p's value): both solves of problem k run with its own settings (snmf_run_basis_train_audio_batch_settings_fp64), bit for bit
+    run_basis_train_signal(s_k, R_k, dict(p, **settings[k]), precision="fp64") alone.  precision="fp64" only (status 8 in fp32);
+    a list of another length is status 3, an unknown key status 1, a vector sparsity status 8.  The host epilogue is unchanged.
 
     sample_idx: None = every problem gets the single call's own stand-in draw, RandomState(1).choice(T_k, cluster_buff*R,
     replace=False) + 1 (the reference re-seeds per class, :80-81); else a list of 1-based index arrays, one per problem.
@@ -120,7 +125,20 @@ def run_basis_train_signal_batch(signals, R, p, *, DC_bin=None, sample_idx=None,
     the fp32 features stft_features (then tf_dd, then mel_features on that) give for s_k, with init_w their columns sample_idx_k.
     Any other string is a ValueError.  info["T"] receives the frame counts, info["n_iter"] a list of [n_dft, n_mel].
     Every argument error is raised before the library is loaded."""
-    return _train_batch(signals, None, R, p, DC_bin=DC_bin, sample_idx=sample_idx, ctx=ctx, h0=h0, precision=precision, info=info)
+    return _train_batch(signals, None, R, p, DC_bin=DC_bin, sample_idx=sample_idx, ctx=ctx, h0=h0, precision=precision, info=info,
+                        settings=settings)
+
+
+def _train_settings(settings, n, p, precision):
+    """settings of the batched training calls -> None, or the list of (beta, sparsity, max_iter, conv_eps) per problem
+    (batch._problem_settings with p's values as the shared ones).  fp64 only: SnmfError status 8 in fp32."""
+    if settings is None:
+        return None
+    if precision != "fp64":
+        raise SnmfError(8, "settings per problem need precision='fp64': the fp32 batch engine has one settings struct for all problems")
+    from .batch import _problem_settings
+    beta, max_iter, conv_eps, _cc, lam = _solver_scalars(p)
+    return _problem_settings(settings, n, dict(beta=beta, sparsity=lam, max_iter=max_iter, conv_eps=conv_eps))
 
 
 def _train_ranks(R, n, precision):
@@ -142,7 +160,7 @@ def _train_ranks(R, n, precision):
     return Rs
 
 
-def _train_batch(signals, ts, R, p, *, DC_bin, sample_idx, ctx, h0, precision, info):
+def _train_batch(signals, ts, R, p, *, DC_bin, sample_idx, ctx, h0, precision, info, settings=None):
     """run_basis_train_signal_batch (ts None: host signals through snmf_run_basis_train_audio_batch_*) and
     run_basis_train_assembled_batch (ts: a TrainSignals, through snmf_run_basis_train_signals_batch_*): the same checks, draws,
     call and host epilogue; only where the samples come from differs."""
@@ -170,6 +188,7 @@ def _train_batch(signals, ts, R, p, *, DC_bin, sample_idx, ctx, h0, precision, i
     K = 2 * int(fp.get("Splice", 0)) + 1
     F, M = K * (int(fp["fftlength"]) // 2 + 1), int(p["F_order"])
     Rk = _train_ranks(R, n, precision)  # a list only when the problems' R differ
+    st = None if exemplar else _train_settings(settings, n, p, precision)  # (the exemplars are the dictionaries: nothing is solved)
     Rs = Rk if Rk is not None else [int(np.asarray(R).reshape(-1)[0])] * n
     n_exs = [cluster_buff * r for r in Rs]
     Ts = [frontend.num_frames_host(size, fp) for size in sizes]
@@ -190,6 +209,8 @@ def _train_batch(signals, ts, R, p, *, DC_bin, sample_idx, ctx, h0, precision, i
         beta, max_iter, conv_eps, cost_check, lam = 1.0, 1, 0.0, 0, 0.0
     else:
         beta, max_iter, conv_eps, cost_check, lam = _solver_scalars(p)
+    if st is not None:
+        max_iter = max(s[2] for s in st)  # the handles': the largest
     q = _make_params(F, 1, max(n_exs), beta, max_iter, conv_eps, cost_check, True, 0, lam, None, None)
     seed = int(p.get("random_seed", 1))
     H0s = seeds = None
@@ -215,7 +236,18 @@ def _train_batch(signals, ts, R, p, *, DC_bin, sample_idx, ctx, h0, precision, i
     alpha = float(p["alpha_eta"]) if p.get("domain_DD", 0) else -1.0
     atoms = np.array(n_exs, np.int32)
     tail = (ptrs(idx0), 1 if exemplar else 0, ptrs(H0s), ptr(seeds), ptrs(B_DFT), ptrs(A_DFT), ptrs(B_Mel), ptrs(A_Mel), ptr(n_iter))
-    if ts is None:
+    if st is not None:  # settings per problem: the _ranks_fp64 lists (n_atoms NULL for one size) plus the settings
+        from .batch import _settings_array
+        sarr = _settings_array(st)
+        at = ptr(atoms) if Rk is not None else None
+        if ts is None:
+            lens = np.array(sizes, np.int64)
+            _lib.check(lib.snmf_run_basis_train_audio_batch_settings_fp64(ctx._h, C.byref(q), C.byref(sp), alpha, ptr(mel), M, n, ptrs(sigs),
+                                                                          ptr(lens), at, *tail, sarr))
+        else:
+            _lib.check(lib.snmf_run_basis_train_signals_batch_settings_fp64(ctx._h, C.byref(q), C.byref(sp), alpha, ptr(mel), M, ts._handle(),
+                                                                            at, *tail, sarr))
+    elif ts is None:
         lens = np.array(sizes, np.int64)
         if Rk is not None:
             _lib.check(lib.snmf_run_basis_train_audio_batch_ranks_fp64(ctx._h, C.byref(q), C.byref(sp), alpha, ptr(mel), M, n, ptrs(sigs),
@@ -372,22 +404,25 @@ def assemble_training_signals(classes, p, *, vad=None, ranges=None, ctx=None):
     return TrainSignals(h, ctx, [int(v) for v in length], [int(v) for v in used])
 
 
-def run_basis_train_assembled_batch(ts, R, p, *, DC_bin=None, sample_idx=None, h0="host", precision="fp32", info=None):
+def run_basis_train_assembled_batch(ts, R, p, *, DC_bin=None, sample_idx=None, h0="host", precision="fp32", info=None, settings=None):
     """run_basis_train_signal_batch([ts.signal(k) for k ...], R, p, ...) without the signals leaving the device
     (snmf_run_basis_train_signals_batch_*): same arguments, same draws (T_k comes from ts.lengths, so the default sample_idx and the
     host H0 are that call's own), same returned list, bit for bit -- in fp32 the resident doubles are rounded to float on the
-    device as np.float32 rounds them.  It runs on the context the signals were assembled on."""
+    device as np.float32 rounds them.  It runs on the context the signals were assembled on.  settings: as in that call
+    (snmf_run_basis_train_signals_batch_settings_fp64)."""
     if not isinstance(ts, TrainSignals):
         raise SnmfError(1, "ts must be the TrainSignals assemble_training_signals returns")
     ts._handle()
-    return _train_batch(None, ts, R, p, DC_bin=DC_bin, sample_idx=sample_idx, ctx=None, h0=h0, precision=precision, info=info)
+    return _train_batch(None, ts, R, p, DC_bin=DC_bin, sample_idx=sample_idx, ctx=None, h0=h0, precision=precision, info=info,
+                        settings=settings)
 
 
 def run_basis_train_clips_batch(classes, R, p, *, vad=None, ranges=None, DC_bin=None, sample_idx=None, ctx=None, h0="host", precision="fp32",
-                                info=None):
+                                info=None, settings=None):
     """assemble_training_signals, run_basis_train_assembled_batch, close: the clips of every class in, the dictionaries out.
     info also receives info["lengths"] and info["clips_used"].  The argument errors of either step that do not need the assembled
-    lengths are raised before the library is loaded; those that do (sample_idx, R against T_k) after the assembly."""
+    lengths are raised before the library is loaded; those that do (sample_idx, R against T_k) after the assembly.
+    settings: as in run_basis_train_signal_batch."""
     _check_precision(precision)
     if not isinstance(h0, str) or h0 not in ("host", "device"):
         raise SnmfError(3, "h0 must be 'host' or 'device'")
@@ -397,11 +432,14 @@ def run_basis_train_clips_batch(classes, R, p, *, vad=None, ranges=None, DC_bin=
         _solver_scalars(p)
     if isinstance(classes, (list, tuple)):
         _train_ranks(R, len(classes), precision)
+        if not p.get("train_Exemplar", 0):
+            _train_settings(settings, len(classes), p, precision)
     frontend._params(p if DC_bin is None else dict(p, DCbin=int(DC_bin)))
     with assemble_training_signals(classes, p, vad=vad, ranges=ranges, ctx=ctx) as ts:
         if info is not None:
             info["lengths"], info["clips_used"] = list(ts.lengths), list(ts.clips_used)
-        return run_basis_train_assembled_batch(ts, R, p, DC_bin=DC_bin, sample_idx=sample_idx, h0=h0, precision=precision, info=info)
+        return run_basis_train_assembled_batch(ts, R, p, DC_bin=DC_bin, sample_idx=sample_idx, h0=h0, precision=precision, info=info,
+                                               settings=settings)
 
 
 def save_basis_mat(path, out, v73=True):
