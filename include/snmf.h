@@ -799,7 +799,8 @@ int snmf_sparse_nmf_batch_fp64(snmf_ctx* ctx, const snmf_params* p, int32_t n_pr
  * _destroy work on it as on any other.  Refused before the device is touched: NULL r, r[k] < 1 (SNMF_ERR_INVALID);
  * a sparsity that is not SNMF_SPARSITY_SCALAR, a w_update_ind or h_update_ind that is neither all ones nor all zeros
  * (SNMF_ERR_UNSUPPORTED: an r-vector has no meaning across ranks); and what snmf_batch_create_fp64 refuses.  Uniform-only, as
- * before: the fp32 engine (snmf_batch_create), missing-data batches (snmf_batch_create_mdi_fp64) and the DNMF batches. */
+ * before: the fp32 engine (snmf_batch_create) and missing-data batches (snmf_batch_create_mdi_fp64).  The DNMF batches with a
+ * rank pair per problem are snmf_run_basis_dnmf_batch_ranks_fp64 and snmf_run_basis_dnmf_audio_batch_ranks_fp64. */
 int snmf_batch_create_ranks_fp64(snmf_ctx* ctx, const snmf_params* p, int32_t n_problems, const int32_t* T, const int32_t* r,
                                  snmf_batch** out);
 
@@ -819,8 +820,9 @@ int snmf_batch_create_ranks_fp64(snmf_ctx* ctx, const snmf_params* p, int32_t n_
  * are compiled per divergence are launched once per divergence present.
  * Refused before the device is touched: NULL s, a non-zero reserved (SNMF_ERR_INVALID); a field of s[k] that snmf_params would
  * be refused for (that status, the message names the problem); a sparsity kind other than SNMF_SPARSITY_SCALAR
- * (SNMF_ERR_UNSUPPORTED); and what snmf_batch_create_fp64 / _ranks_fp64 refuse.  There is no fp32 form, no DNMF form and no
- * missing-data form (a masked handle with settings is SNMF_ERR_UNSUPPORTED). */
+ * (SNMF_ERR_UNSUPPORTED); and what snmf_batch_create_fp64 / _ranks_fp64 refuse.  There is no fp32 form and no missing-data form
+ * (a masked handle with settings is SNMF_ERR_UNSUPPORTED); the DNMF batches take settings per problem through
+ * snmf_run_basis_dnmf_batch_ranks_fp64 and snmf_run_basis_dnmf_audio_batch_ranks_fp64. */
 typedef struct snmf_problem_settings {
     double beta;        /* divergence order: 1 kl, 2 ed, 0 is, else generic */
     double sparsity;    /* scalar */
@@ -935,6 +937,34 @@ int snmf_run_basis_dnmf_audio_batch_fp64(snmf_ctx* ctx, const snmf_params* p, co
                                          const int64_t* n_d, const double* mel, int32_t mel_M, const double* const* B,
                                          const double* const* H0, const uint64_t* seed, double* const* B_hat, double* const* A_hat,
                                          int32_t* n_iter);
+
+/* Added within 5.  snmf_run_basis_dnmf_batch_fp64 and snmf_run_basis_dnmf_audio_batch_fp64 with a rank pair and, optionally,
+ * settings per problem: the sweep over R_x / R_d, max_iter and the sparsity weight of the reference's settings files as one call.
+ * R_x and R_d hold n_problems ranks each; s: NULL (the four fields of p for every problem), or n_problems entries
+ * (snmf_problem_settings, as on snmf_batch_create_settings_fp64) of which s[k] is used in all three solves of problem k, as the
+ * reference passes one p through them (run_basis_DNMF.m:37-53).  The other arguments keep the order of the namesakes.
+ * p->r must be the largest R_x[k] + R_d[k]; with s, p->max_iter must be the largest s[k].max_iter and p->beta,
+ * p->sparsity_scalar and p->conv_eps are ignored (SNMF_ERR_DIM otherwise: the rules of snmf_batch_create_ranks_fp64 /
+ * _settings_fp64, whose code makes the three resident batches -- ranks R_x[k] + R_d[k], R_x[k] and R_d[k]).  Every matrix is
+ * tight: B_k, B_hat_k F x (R_x[k] + R_d[k]), B_hat_k = [B_hat_x, B_hat_d] with the noise part at column R_x[k]; H0_k, A_hat_k
+ * (R_x[k] + R_d[k]) x T_k.  In the audio form an H0_k that is not given is the Philox draw keyed by seed[k] with R_x[k] + R_d[k] rows.
+ * THE CONTRACT: B_hat_k, A_hat_k and the three counts are bit for bit those of snmf_run_basis_dnmf_fp64 (the matrix form) or
+ * snmf_run_basis_dnmf_audio_fp64 (the audio form) run alone on problem k with R_x[k], R_d[k] and s[k] in the place of the four
+ * fields -- whatever the ranks, settings, sizes and order of the problems around it; n_problems equal pairs with s = NULL give
+ * the bits of the namesake.  A_hat passes between the batches on the device, problem k's rows at problem k's own offsets.
+ * Refused before the device is touched: NULL R_x or R_d, R_x[k] < 1, R_d[k] < 1, a sparsity that is not SNMF_SPARSITY_SCALAR
+ * (SNMF_ERR_DIM, as the namesakes refuse a bad scalar); a non-zero reserved (SNMF_ERR_INVALID) or a field of s[k] that
+ * snmf_params would be refused for (that status; the message names the problem); and what the namesakes and the two create
+ * entries refuse.  There is no fp32 form: the fp32 batch engine has one rank and one settings struct for all problems. */
+int snmf_run_basis_dnmf_batch_ranks_fp64(snmf_ctx* ctx, const snmf_params* p, const int32_t* R_x, const int32_t* R_d,
+                                         const snmf_problem_settings* s, int32_t n_problems, const int32_t* T, const double* const* Y,
+                                         const double* const* X, const double* const* D, const double* const* B,
+                                         const double* const* H0, double* const* B_hat, double* const* A_hat, int32_t* n_iter);
+int snmf_run_basis_dnmf_audio_batch_ranks_fp64(snmf_ctx* ctx, const snmf_params* p, const snmf_stft_params* sp, const int32_t* R_x,
+                                               const int32_t* R_d, const snmf_problem_settings* s, int32_t n_problems,
+                                               const double* const* x, const int64_t* n_x, const double* const* d, const int64_t* n_d,
+                                               const double* mel, int32_t mel_M, const double* const* B, const double* const* H0,
+                                               const uint64_t* seed, double* const* B_hat, double* const* A_hat, int32_t* n_iter);
 
 /* Added within 5.  Basis training (run_basis_train.m:58-91) for the training signals of n_problems event classes or noise types
  * at once -- the loop l = 1:length(DB_path_list) of the reference: snmf_run_basis_train_audio_* for every signal, with the

@@ -103,6 +103,7 @@ SYMBOLS = [
     "snmf_train_signals_destroy", "snmf_run_basis_train_signals_batch_f64", "snmf_run_basis_train_signals_batch_fp64",
     "snmf_batch_create_ranks_fp64", "snmf_run_basis_train_audio_batch_ranks_fp64", "snmf_run_basis_train_signals_batch_ranks_fp64",
     "snmf_batch_create_settings_fp64", "snmf_run_basis_train_audio_batch_settings_fp64", "snmf_run_basis_train_signals_batch_settings_fp64",
+    "snmf_run_basis_dnmf_batch_ranks_fp64", "snmf_run_basis_dnmf_audio_batch_ranks_fp64",
     "snmf_rccl_available", "snmf_rccl_get_unique_id", "snmf_rccl_comm_create", "snmf_rccl_comm_destroy", "snmf_plan_run_sharded_rccl",
 ]
 ABI_VERSION = 5  # include/snmf.h: SNMF_ABI_VERSION this binding was written against
@@ -419,6 +420,9 @@ def load():
     sig["snmf_run_basis_train_audio_batch_settings_fp64"] = (C.c_int, [vp, PP, SP, dbl, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp,
                                                                       vp])
     sig["snmf_run_basis_train_signals_batch_settings_fp64"] = (C.c_int, [vp, PP, SP, dbl, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp])
+    # a rank pair and settings per problem in the fp64 DNMF batches: the namesakes' lists with R_x, R_d as arrays and the settings behind them
+    sig["snmf_run_basis_dnmf_batch_ranks_fp64"] = (C.c_int, [vp, PP, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp])
+    sig["snmf_run_basis_dnmf_audio_batch_ranks_fp64"] = (C.c_int, [vp, PP, SP, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp])
     lib.snmf_abi_version.restype = C.c_int
     if lib.snmf_abi_version() != ABI_VERSION:  # a stale library must not be driven through newer prototypes
         raise ImportError(f"{path} has ABI version {lib.snmf_abi_version()}, this binding needs {ABI_VERSION}: rebuild the library")

@@ -798,7 +798,106 @@ class BatchPlanMdi64(BatchPlan64):
         return out
 
 
-def run_basis_dnmf_batch(Ys, Xs, Ds, B, R_x, R_d, p, *, ctx=None, dtype=np.float64, h0="host", precision="fp32", info=None):
+def _is_seq(x):
+    return isinstance(x, (list, tuple)) or (isinstance(x, np.ndarray) and x.ndim > 0)
+
+
+def _dnmf_rank_pairs(R_x, R_d, n, settings, precision):
+    """R_x, R_d and settings of the batched DNMF calls -> None for two scalars without settings (the uniform entries), else the
+    two lists of n ranks (a scalar beside a sequence counts for every problem).  A rank pair or settings per problem are the fp64
+    engine's: SnmfError status 8 in fp32.  Its own errors: a length that is not n (3), a rank below 1 (1)."""
+    if not _is_seq(R_x) and not _is_seq(R_d) and settings is None:
+        return None
+    if precision != "fp64":
+        raise SnmfError(8, "a rank pair or settings per problem need precision='fp64': the fp32 batch engine has one rank and one "
+                           "settings struct for all problems")
+    out = []
+    for name, R in (("R_x", R_x), ("R_d", R_d)):
+        Rs = [int(x) for x in np.asarray(R).reshape(-1)] if _is_seq(R) else [int(R)] * n
+        if len(Rs) != n:
+            raise SnmfError(3, f"{name} is a list of {len(Rs)}, the batch has {n} problems")
+        for k, x in enumerate(Rs):
+            if x < 1:
+                raise SnmfError(1, f"{name} of problem {k} is {x} (at least 1)")
+        out.append(Rs)
+    return out
+
+
+def _dnmf_rank_inputs(B, h0, rs, F, Ts, modes, seed):
+    """B and h0 of a DNMF batch with ranks rs[k] = R_x[k] + R_d[k] -> (Bs, H0s): B a list of F x rs[k] arrays, or one array when
+    every pair is the same; h0 one of the strings in `modes`, or a list of rs[k] x T_k arrays.  "host": rand(rs[k], T_k) per
+    problem, in list order, from one RandomState(seed) -- with equal ranks the uniform call's draw; another string: H0s is None.
+    All errors are SnmfError status 3."""
+    n = len(Ts)
+    if isinstance(B, (list, tuple)):
+        if len(B) != n:
+            raise SnmfError(3, f"B is a list of {len(B)}, the batch has {n} problems")
+        Bs = [np.asfortranarray(b, dtype=np.float64) for b in B]
+    else:
+        if len(set(rs)) > 1:
+            raise SnmfError(3, f"one B for problems of different ranks {rs}: B must be a list of F x (R_x[k] + R_d[k]) arrays")
+        Bs = [np.asfortranarray(B, dtype=np.float64)] * n
+    for k, b in enumerate(Bs):
+        if b.shape != (F, rs[k]):
+            raise SnmfError(3, f"B of problem {k} is {b.shape}, expected ({F}, {rs[k]})")
+    what = f"h0 must be {', '.join(repr(m) for m in modes)} or a list of {n} arrays ((R_x[k] + R_d[k]) x T_k each)"
+    if isinstance(h0, str):
+        if h0 not in modes:
+            raise SnmfError(3, what)
+        if h0 != "host":
+            return Bs, None
+        rng = np.random.RandomState(seed if seed > 0 else None)
+        return Bs, [np.asfortranarray(rng.random_sample((r, T))) for r, T in zip(rs, Ts)]
+    if not isinstance(h0, (list, tuple)) or len(h0) != n:
+        raise SnmfError(3, what)
+    H0s = [np.asfortranarray(h, dtype=np.float64) for h in h0]
+    for k, (h, r, T) in enumerate(zip(H0s, rs, Ts)):
+        if h.shape != (r, T):
+            raise SnmfError(3, f"init_h of problem {k} is {h.shape}, expected ({r}, {T})")
+    return Bs, H0s
+
+
+def _dnmf_rank_params(p, settings, n, F, r_max):
+    """(snmf_params, the C array of settings or None) of a DNMF batch with ranks: p's own errors (_solver_scalars), then the
+    settings per problem resolved by _problem_settings with p's values as the shared ones; params.max_iter is the largest limit."""
+    beta, max_iter, conv_eps, cost_check, lam = _solver_scalars(p)
+    sarr = None
+    if settings is not None:
+        st = _problem_settings(settings, n, dict(beta=beta, sparsity=lam, max_iter=max_iter, conv_eps=conv_eps))
+        max_iter = max(s[2] for s in st)
+        sarr = _settings_array(st)
+    return _make_params(F, 1, r_max, beta, max_iter, conv_eps, cost_check, True, 0, lam, None, None), sarr
+
+
+def _dnmf_batch_ranks(Ys, Xs, Ds, B, Rxs, Rds, p, ctx, dt, h0, info, settings):
+    """run_basis_dnmf_batch with a rank pair per problem (snmf_run_basis_dnmf_batch_ranks_fp64); the feature lists are checked."""
+    n, F = len(Ys), Ys[0].shape[0]
+    rs = [a + b for a, b in zip(Rxs, Rds)]
+    Ts = [y.shape[1] for y in Ys]
+    Bs, H0s = _dnmf_rank_inputs(B, h0, rs, F, Ts, ("host",), int(p.get("random_seed", 1)))
+    sp, sarr = _dnmf_rank_params(p, settings, n, F, max(rs))
+    if dt != np.dtype(np.float64):
+        raise SnmfError(1, "precision='fp64' needs dtype=np.float64 (the fp64 DNMF batch takes and returns doubles)")
+
+    lib = _lib.load()
+    ctx = ctx or default_context()
+    yy, xx, dd = ([np.asfortranarray(a, dtype=np.float64) for a in arrs] for arrs in (Ys, Xs, Ds))
+    B_hat = [np.empty((F, r), order="F") for r in rs]
+    A_hat = [np.empty((r, T), order="F") for r, T in zip(rs, Ts)]
+    n_iter = np.zeros(3 * n, np.int32)
+    Tv, rx, rd = np.array(Ts, np.int32), np.array(Rxs, np.int32), np.array(Rds, np.int32)
+
+    def ptrs(arrs):
+        return (C.c_void_p * n)(*[a.ctypes.data for a in arrs])
+
+    _lib.check(lib.snmf_run_basis_dnmf_batch_ranks_fp64(ctx._h, C.byref(sp), _ptr(rx), _ptr(rd), sarr, n, _ptr(Tv), ptrs(yy), ptrs(xx),
+                                                        ptrs(dd), ptrs(Bs), ptrs(H0s), ptrs(B_hat), ptrs(A_hat), _ptr(n_iter)))
+    if info is not None:
+        info["n_iter"] = [[int(v) for v in n_iter[3 * k:3 * k + 3]] for k in range(n)]
+    return list(zip(B_hat, A_hat))
+
+
+def run_basis_dnmf_batch(Ys, Xs, Ds, B, R_x, R_d, p, *, ctx=None, dtype=np.float64, h0="host", precision="fp32", info=None, settings=None):
     """(B_hat, A_hat) = run_basis_dnmf(Y, X, D, B, R_x, R_d, p) for every problem of the three lists, solved together
     (snmf_run_basis_dnmf_batch_*): the mixtures, the clean and the noise features are three batches, and A_hat stays on the
     device between them.  Ys, Xs, Ds: lists of F x T_k arrays (one F; X_k and D_k of Y_k's shape).  B: one F x (R_x + R_d)
@@ -807,6 +906,14 @@ def run_basis_dnmf_batch(Ys, Xs, Ds, B, R_x, R_d, p, *, ctx=None, dtype=np.float
     precision="fp32": the fp32 batch engine (F <= 513, R_x + R_d <= 200), bit for bit three chained sparse_nmf_batch calls.
     precision="fp64" (dtype float64): problem k's results are bit for bit run_basis_dnmf(..., precision="fp64", h0=H0_k) alone.
     Every problem stops each of its three solves at its own iteration; info["n_iter"] receives a list of [n1, n2, n3].
+    A rank pair per problem (precision="fp64" only, snmf_run_basis_dnmf_batch_ranks_fp64): R_x and R_d may each be a sequence of
+    len(Ys) ints (a scalar beside a sequence counts for every problem).  B is then a list of F x (R_x[k] + R_d[k]) arrays (one
+    array only when every pair is the same), h0 a list of (R_x[k] + R_d[k]) x T_k arrays or "host", which draws
+    rand(R_x[k] + R_d[k], T_k) per problem in list order from the one RandomState: with equal ranks the draw above.
+    settings: one dict per problem with keys among cf, beta, sparsity, max_iter, conv_eps (the rules of
+    sparse_nmf_batch_fp64(vs, [p_0, ...]); a missing key takes p's value); problem k's settings hold in all three of its solves.
+    Problem k stays bit for bit run_basis_dnmf(Y_k, X_k, D_k, B_k, R_x[k], R_d[k], p_k, precision="fp64", h0=H0_k) alone.  A
+    sequence or settings with precision="fp32" is SnmfError status 8.
     Returns a list of (B_hat, A_hat)."""
     _check_precision(precision)
     p = dict(p)
@@ -819,8 +926,10 @@ def run_basis_dnmf_batch(Ys, Xs, Ds, B, R_x, R_d, p, *, ctx=None, dtype=np.float
         raise SnmfError(1, "the batch is empty: Ys must hold at least one matrix")
     if len(Xs) != n or len(Ds) != n:
         raise SnmfError(1, f"{n} mixtures, {len(Xs)} clean and {len(Ds)} noise feature sets: one of each per problem")
-    R_x, R_d = int(R_x), int(R_d)
-    r = R_x + R_d
+    pairs = _dnmf_rank_pairs(R_x, R_d, n, settings, precision)
+    if pairs is None:
+        R_x, R_d = int(R_x), int(R_d)
+        r = R_x + R_d
     for y in Ys:
         if y.ndim != 2 or y.shape[1] < 1:
             raise SnmfError(1, "every Y must be a 2-D matrix with at least one column")
@@ -830,6 +939,8 @@ def run_basis_dnmf_batch(Ys, Xs, Ds, B, R_x, R_d, p, *, ctx=None, dtype=np.float
             raise SnmfError(3, f"Y of problem {k} has {y.shape[0]} rows, problem 0 has {F}: a batch shares the row count")
         if x.shape != y.shape or d.shape != y.shape:
             raise SnmfError(3, f"problem {k}: Y, X and D must have one size (got {y.shape}, {x.shape}, {d.shape})")
+    if pairs is not None:
+        return _dnmf_batch_ranks(Ys, Xs, Ds, B, pairs[0], pairs[1], p, ctx, dt, h0, info, settings)
     if isinstance(B, (list, tuple)):
         if len(B) != n:
             raise SnmfError(3, f"B is a list of {len(B)}, the batch has {n} problems")

@@ -112,6 +112,28 @@ static __global__ __launch_bounds__(256) void k_b64_take_h(B64Args a, const doub
     }
 }
 
+// grid (workgroups, B): the same hand-over between two batches whose problems have ranks of their own.  H0 of problem b of batch
+// `a` (tight r_b x T_b at its own B64Prob::h0) from rows [row0[b], row0[b] + r_b) of problem b's H in the source batch (tight
+// rs_b x T_b at the source's own h0): `src` is the source's table of problems, Hsrc its H, row0 a device array with one entry per
+// problem.  A flat index over the r_b T_b elements, consecutive lanes along k within a frame, so that a problem of rank one
+// keeps every lane busy.  The host has checked equal frame counts and 0 <= row0[b], row0[b] + r_b <= rs_b.  A copy: no
+// arithmetic, nothing shared between workgroups.
+static __global__ __launch_bounds__(256) void k_b64_take_h_rows(B64Args a, const B64Prob* __restrict__ src, const double* __restrict__ Hsrc,
+                                                                const int32_t* __restrict__ row0) {
+    const int b = blockIdx.y;
+    const B64Prob p = a.prob[b];
+    const B64Prob q = src[b];
+    const int r = p.r, rs = q.r;
+    const double* __restrict__ S = Hsrc + q.h0 + row0[b];
+    double* __restrict__ H = a.H + p.h0;
+    const long long n = (long long)r * p.T;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        const long long t = i / r;
+        const int k = (int)(i - t * r);
+        H[i] = S[t * rs + k];
+    }
+}
+
 // grid (workgroups, B): init_w of problem b = V_b(:, idx[w0_b + k]), k < r_b (run_basis_train.m:82-83; k_gather64 per problem):
 // columns of the problem's own tight V block into its tight F x r_b W.  idx: 0-based, on the device, the problems' r_b entries
 // packed one behind the other; an index outside [0, T_b) (the host refuses it) gives a zero column, never a read outside the block.

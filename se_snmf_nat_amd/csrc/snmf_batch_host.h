@@ -10,7 +10,7 @@
 // describe, destroy, the new batch on a used handle -- is the life below, unchanged.
 // A handle made by snmf_batch_create_ranks_fp64 carries a rank per problem (`ranks`): problem k's W is F x ranks[k] and its H
 // ranks[k] x T_k wherever a call below says r; p.r is the largest of them.  The life is the same; what such a handle refuses
-// (batch_create, take_h0) it refuses before any device work.
+// (batch_create, take_h0) it refuses before any device work; its activations go over through take_h0_rows.
 // A handle made by snmf_batch_create_settings_fp64 carries settings per problem (`settings`): problem k's divergence, sparsity
 // weight, stop threshold and iteration limit wherever a call below says p.beta, p.sparsity_scalar, p.conv_eps or p.max_iter;
 // p.max_iter is the largest of the limits.  A run goes to that, the engine freezes a problem at its own limit and counts it in
@@ -85,6 +85,12 @@ struct snmf_batch {
     // counts, whose run has ended -- then the initial scaling of H (:159-160) by the norms load() left: what load() does with
     // a host H0, without H leaving the device.  Every problem must have been loaded with H0 == nullptr.
     virtual int take_h0(snmf_batch& src, int row0) = 0;
+    // take_h0 between batches whose problems have ranks of their own: problem k takes rows [row0[k], row0[k] + rank_of(k)) of its
+    // source's H (row0: host, B entries; row0[k] + rank_of(k) <= the source's rank of k), then the same scaling.  Either batch may
+    // be one with or without ranks or settings.  An engine that has no rank per problem refuses.
+    virtual int take_h0_rows(snmf_batch&, const int32_t*) {
+        return fail(SNMF_ERR_UNSUPPORTED, "this batch engine hands no activations over between batches with a rank per problem");
+    }
     // a masked batch: problem k with its mask (1 = observed), the initial scaling and the masked start (src/snmf_mdi.m:175)
     virtual int load_mdi(int, const double*, int64_t, const double*, int64_t, const double*, const double*) {
         return fail(SNMF_ERR_UNSUPPORTED, "this batch engine has no missing-data form");
@@ -340,7 +346,9 @@ inline int batch_get_v_mdi(snmf_batch* b, int32_t k, double* V_mdi, int64_t ld) 
 // solves at its own iteration and the polling is the batch's; between the phases A_hat goes from the Y-engine into the other two
 // through take_h0 and never leaves the device.  Like the rest of this file, the driver does not ask which engine it drives.
 // The matrix form (dnmf_batch) and the audio form (snmf_run_basis_dnmf_audio_batch_*, snmf_tu_frontend_batch.hip) share it:
-// dnmf_batch_run has the three phases, DnmfInputs says where V and H0 come from.
+// dnmf_batch_phases has the three phases, DnmfInputs says where V and H0 come from.  Two drivers make the engines and say how A_hat
+// goes over: dnmf_batch_run (one R_x, one R_d, one settings struct: take_h0) and dnmf_batch_run_ranks (a rank pair and settings per
+// problem, the fp64 engine: take_h0_rows).
 struct BatchOwner {  // an engine that dies with the call
     snmf_batch* b = nullptr;
     ~BatchOwner() {
@@ -362,6 +370,50 @@ struct DnmfInputs {
     const uint64_t* seed = nullptr;                         // n, read where H0_k is not given
 };
 
+// The three phases on engines that have been made: e1 the Y-batch, e2 the X-batch, e3 the D-batch.  rx_of(k): the columns of B_k
+// (and of B_hat_k) in front of the noise part, R_x of problem k.  hand_over(e, noise): init_h of every problem of e from A_hat in
+// e1 -- the first R_x rows, or with `noise` the rows behind them.
+template <typename TT, typename RxOf, typename HandOver>
+int dnmf_batch_phases(snmf_batch* e1, snmf_batch* e2, snmf_batch* e3, int32_t n, int F, const DnmfInputs<TT>& in, const TT* const* B,
+                      TT* const* B_hat, TT* const* A_hat, int32_t* n_iter, RxOf rx_of, HandOver hand_over) {
+    // V and init_w = B(:, col0 + (1:r)) of every problem of a phase: from the host through load(), V from the device where it is formed there
+    auto set_phase = [&](snmf_batch* e, int kind, bool noise, const TT* const* H0) -> int {
+        for (int i = 0; i < n; ++i) {
+            const size_t col0 = noise ? (size_t)rx_of(i) : 0;
+            SN_TRY(e->load(i, in.V[kind] ? in.V[kind][i] : (const TT*)nullptr, (int64_t)F, B[i] + (size_t)F * col0, H0 ? H0[i] : (const TT*)nullptr));
+            batch_mark_set(e, i);
+        }
+        if (in.V[kind]) return SNMF_OK;
+        std::vector<snmf_batch::VBlock> blocks;
+        SN_TRY(e->v_blocks(&blocks));
+        SN_TRY(in.device_v(kind, blocks, e->v_elem()));
+        return e->v_written();
+    };
+    SN_TRY(set_phase(e1, 0, false, in.H0));  // p.init_w = B   (:39)
+    {
+        std::vector<uint8_t> draw(n, 0);
+        bool any = false;
+        for (int i = 0; i < n; ++i) any |= (draw[i] = (!in.H0 || !in.H0[i]) ? 1 : 0) != 0;
+        if (any) SN_TRY(e1->draw_h0(in.seed, draw.data()));
+    }
+    SN_TRY(batch_run(e1, 0));  // [~, A_hat] = sparse_nmf(Y, p)   (:40)
+    // a W-only phase: init_h = A_hat(row0 + (1:r), :) from the Y-engine
+    auto w_phase = [&](snmf_batch* e, int kind, bool noise) -> int {
+        SN_TRY(set_phase(e, kind, noise, nullptr));
+        SN_TRY(hand_over(e, noise));
+        return batch_run(e, 0);
+    };
+    SN_TRY(w_phase(e2, 1, false));  // :43-47
+    SN_TRY(w_phase(e3, 2, true));   // :49-53
+    for (int i = 0; i < n; ++i) {
+        int32_t* ni = n_iter ? n_iter + 3 * (size_t)i : nullptr;
+        SN_TRY(batch_get<TT>(e1, i, (TT*)nullptr, A_hat ? A_hat[i] : (TT*)nullptr, nullptr, nullptr, ni));
+        SN_TRY(batch_get<TT>(e2, i, B_hat[i], (TT*)nullptr, nullptr, nullptr, ni ? ni + 1 : nullptr));  // B_hat = [B_hat_x, B_hat_d]   (:55)
+        SN_TRY(batch_get<TT>(e3, i, B_hat[i] + (size_t)F * rx_of(i), (TT*)nullptr, nullptr, nullptr, ni ? ni + 2 : nullptr));
+    }
+    return SNMF_OK;
+}
+
 // Every matrix tight and column-major: Y_k, X_k, D_k F x T[k], B_k F x (R_x + R_d), H0_k (R_x + R_d) x T[k]; B_hat_k and A_hat_k
 // likewise (A_hat, or single entries of it, may be NULL); n_iter: NULL or 3 per problem.  The masks of p are ignored (the loop
 // sets its own, :37-38, :43-44, :49-50).  Every refusal comes before the device is touched; the caller has checked `in`.
@@ -372,7 +424,6 @@ int dnmf_batch_run(const char* entry, snmf_batch* (*make)(), snmf_ctx* ctx, cons
     if (R_x < 1 || R_d < 1 || p->r != R_x + R_d) return fail(SNMF_ERR_DIM, "params->r = %d must equal R_x + R_d = %d + %d", p->r, R_x, R_d);
     if (p->sparsity_kind != SNMF_SPARSITY_SCALAR)
         return fail(SNMF_ERR_DIM, "run_basis_DNMF needs a scalar p.sparsity (its W-only solves have R_x / R_d rows)");
-    const int F = p->F;
     const std::vector<uint8_t> on(p->r, 1), off(p->r, 0);
     snmf_params q = *p;
     BatchOwner e1, e2, e3;
@@ -383,59 +434,77 @@ int dnmf_batch_run(const char* entry, snmf_batch* (*make)(), snmf_ctx* ctx, cons
     SN_TRY(batch_create(entry, make(), ctx, &q, n, T, &e2.b));
     q.r = R_d;
     SN_TRY(batch_create(entry, make(), ctx, &q, n, T, &e3.b));
-
-    // V and init_w = B(:, row0 + (1:r)) of every problem of a phase: from the host through load(), V from the device where it is formed there
-    auto set_phase = [&](snmf_batch* e, int kind, int row0, const TT* const* H0) -> int {
-        for (int i = 0; i < n; ++i) {
-            SN_TRY(e->load(i, in.V[kind] ? in.V[kind][i] : (const TT*)nullptr, (int64_t)F, B[i] + (size_t)F * row0, H0 ? H0[i] : (const TT*)nullptr));
-            batch_mark_set(e, i);
-        }
-        if (in.V[kind]) return SNMF_OK;
-        std::vector<snmf_batch::VBlock> blocks;
-        SN_TRY(e->v_blocks(&blocks));
-        SN_TRY(in.device_v(kind, blocks, e->v_elem()));
-        return e->v_written();
-    };
-    SN_TRY(set_phase(e1.b, 0, 0, in.H0));  // p.init_w = B   (:39)
-    {
-        std::vector<uint8_t> draw(n, 0);
-        bool any = false;
-        for (int i = 0; i < n; ++i) any |= (draw[i] = (!in.H0 || !in.H0[i]) ? 1 : 0) != 0;
-        if (any) SN_TRY(e1.b->draw_h0(in.seed, draw.data()));
-    }
-    SN_TRY(batch_run(e1.b, 0));  // [~, A_hat] = sparse_nmf(Y, p)   (:40)
-    // a W-only phase: init_h = A_hat(row0 + (1:r), :) from the Y-engine
-    auto w_phase = [&](snmf_batch* e, int kind, int row0) -> int {
-        SN_TRY(set_phase(e, kind, row0, nullptr));
-        SN_TRY(e->take_h0(*e1.b, row0));
-        return batch_run(e, 0);
-    };
-    SN_TRY(w_phase(e2.b, 1, 0));    // :43-47
-    SN_TRY(w_phase(e3.b, 2, R_x));  // :49-53
-    for (int i = 0; i < n; ++i) {
-        int32_t* ni = n_iter ? n_iter + 3 * (size_t)i : nullptr;
-        SN_TRY(batch_get<TT>(e1.b, i, (TT*)nullptr, A_hat ? A_hat[i] : (TT*)nullptr, nullptr, nullptr, ni));
-        SN_TRY(batch_get<TT>(e2.b, i, B_hat[i], (TT*)nullptr, nullptr, nullptr, ni ? ni + 1 : nullptr));  // B_hat = [B_hat_x, B_hat_d]   (:55)
-        SN_TRY(batch_get<TT>(e3.b, i, B_hat[i] + (size_t)F * R_x, (TT*)nullptr, nullptr, nullptr, ni ? ni + 2 : nullptr));
-    }
-    return SNMF_OK;
+    return dnmf_batch_phases<TT>(e1.b, e2.b, e3.b, n, p->F, in, B, B_hat, A_hat, n_iter, [&](int) { return R_x; },
+                                 [&](snmf_batch* e, bool noise) { return e->take_h0(*e1.b, noise ? R_x : 0); });
 }
 
-// the matrix form (snmf_run_basis_dnmf_batch_*): its own refusals, then the loop on host arrays
+// The same loop with a rank pair (R_x[k], R_d[k]) per problem and, with s, settings per problem (the fp64 engine only: the
+// engines are made through the code behind snmf_batch_create_ranks_fp64 / _settings_fp64, which an engine without such a form
+// refuses).  The Y-batch has the ranks R_x[k] + R_d[k], the X-batch R_x[k], the D-batch R_d[k]; problem k has the same s[k] in
+// all three solves, as the reference passes one p through them (:37-53).  B_k, B_hat_k are F x (R_x[k] + R_d[k]), H0_k, A_hat_k
+// (R_x[k] + R_d[k]) x T[k]; p->r must be the largest sum and, with s, p->max_iter the largest limit.  A_hat goes over through
+// take_h0_rows.  The uniform driver above launches what it did: this one shares the phases with it and nothing else.
 template <typename TT>
-int dnmf_batch(const char* entry, snmf_batch* (*make)(), snmf_ctx* ctx, const snmf_params* p, int32_t R_x, int32_t R_d, int32_t n,
-               const int32_t* T, const TT* const* Y, const TT* const* X, const TT* const* D, const TT* const* B, const TT* const* H0,
-               TT* const* B_hat, TT* const* A_hat, int32_t* n_iter) {
+int dnmf_batch_run_ranks(const char* entry, snmf_batch* (*make)(), snmf_ctx* ctx, const snmf_params* p, const int32_t* R_x, const int32_t* R_d,
+                         const snmf_problem_settings* s, int32_t n, const int32_t* T, const DnmfInputs<TT>& in, const TT* const* B,
+                         TT* const* B_hat, TT* const* A_hat, int32_t* n_iter) {
+    if (!R_x || !R_d) return fail(SNMF_ERR_DIM, "%s: R_x and R_d hold a rank per problem (got NULL)", entry);
+    std::vector<int32_t> r1(n), rx0(n, 0), rx(R_x, R_x + n);
+    int mx = 0, md = 0;
+    for (int i = 0; i < n; ++i) {
+        if (R_x[i] < 1 || R_d[i] < 1) return fail(SNMF_ERR_DIM, "%s: problem %d has R_x = %d, R_d = %d (at least 1 each)", entry, i, R_x[i], R_d[i]);
+        if ((long long)R_x[i] + R_d[i] > 0x7fffffffLL) return fail(SNMF_ERR_DIM, "%s: problem %d: R_x + R_d overflows", entry, i);
+        r1[i] = R_x[i] + R_d[i];
+        mx = std::max(mx, (int)R_x[i]), md = std::max(md, (int)R_d[i]);
+    }
+    if (p->sparsity_kind != SNMF_SPARSITY_SCALAR)
+        return fail(SNMF_ERR_DIM, "run_basis_DNMF needs a scalar p.sparsity (its W-only solves have R_x / R_d rows)");
+    const int m1 = *std::max_element(r1.begin(), r1.end());
+    if (p->r != m1) return fail(SNMF_ERR_DIM, "%s: params->r = %d must be the largest R_x + R_d, %d", entry, p->r, m1);
+    const std::vector<uint8_t> on(m1, 1), off(m1, 0);
+    snmf_params q = *p;
+    BatchOwner e1, e2, e3;
+    q.w_update_ind = off.data(), q.h_update_ind = on.data();  // :37-38
+    SN_TRY(batch_create(entry, make(), ctx, &q, n, T, &e1.b, true, r1.data(), s != nullptr, s));  // (p->r is the largest sum, or refused)
+    q.w_update_ind = on.data(), q.h_update_ind = off.data();  // :43-44, :49-50
+    q.r = mx;
+    SN_TRY(batch_create(entry, make(), ctx, &q, n, T, &e2.b, true, R_x, s != nullptr, s));
+    q.r = md;
+    SN_TRY(batch_create(entry, make(), ctx, &q, n, T, &e3.b, true, R_d, s != nullptr, s));
+    return dnmf_batch_phases<TT>(e1.b, e2.b, e3.b, n, p->F, in, B, B_hat, A_hat, n_iter, [&](int i) { return (int)rx[i]; },
+                                 [&](snmf_batch* e, bool noise) { return e->take_h0_rows(*e1.b, noise ? rx.data() : rx0.data()); });
+}
+
+// the matrix form (snmf_run_basis_dnmf_batch_*, _ranks_fp64): its own refusals and where V and H0 come from, then the loop on host arrays
+template <typename TT>
+int dnmf_batch_inputs(const char* entry, snmf_ctx* ctx, const snmf_params* p, int32_t n, const int32_t* T, const TT* const* Y, const TT* const* X,
+                      const TT* const* D, const TT* const* B, const TT* const* H0, TT* const* B_hat, DnmfInputs<TT>* in) {
     if (!ctx || !p || !T || !Y || !X || !D || !B || !H0 || !B_hat) return fail(SNMF_ERR_INVALID, "%s: NULL argument", entry);
     if (n < 1) return fail(SNMF_ERR_INVALID, "%s: n_problems must be at least 1 (got %d)", entry, n);
     for (int i = 0; i < n; ++i) {
         if (!Y[i] || !X[i] || !D[i] || !B[i] || !H0[i] || !B_hat[i]) return fail(SNMF_ERR_INVALID, "%s: an array of problem %d is NULL", entry, i);
         if (T[i] < 1) return fail(SNMF_ERR_INVALID, "problem %d has T = %d frames (at least 1)", i, T[i]);
     }
+    in->V[0] = Y, in->V[1] = X, in->V[2] = D;
+    in->H0 = H0;
+    return SNMF_OK;
+}
+template <typename TT>
+int dnmf_batch(const char* entry, snmf_batch* (*make)(), snmf_ctx* ctx, const snmf_params* p, int32_t R_x, int32_t R_d, int32_t n,
+               const int32_t* T, const TT* const* Y, const TT* const* X, const TT* const* D, const TT* const* B, const TT* const* H0,
+               TT* const* B_hat, TT* const* A_hat, int32_t* n_iter) {
     DnmfInputs<TT> in;
-    in.V[0] = Y, in.V[1] = X, in.V[2] = D;
-    in.H0 = H0;
+    SN_TRY(dnmf_batch_inputs<TT>(entry, ctx, p, n, T, Y, X, D, B, H0, B_hat, &in));
     return dnmf_batch_run<TT>(entry, make, ctx, p, R_x, R_d, n, T, in, B, B_hat, A_hat, n_iter);
+}
+// with a rank pair and (s != nullptr) settings per problem
+template <typename TT>
+int dnmf_batch_ranks(const char* entry, snmf_batch* (*make)(), snmf_ctx* ctx, const snmf_params* p, const int32_t* R_x, const int32_t* R_d,
+                     const snmf_problem_settings* s, int32_t n, const int32_t* T, const TT* const* Y, const TT* const* X, const TT* const* D,
+                     const TT* const* B, const TT* const* H0, TT* const* B_hat, TT* const* A_hat, int32_t* n_iter) {
+    DnmfInputs<TT> in;
+    SN_TRY(dnmf_batch_inputs<TT>(entry, ctx, p, n, T, Y, X, D, B, H0, B_hat, &in));
+    return dnmf_batch_run_ranks<TT>(entry, make, ctx, p, R_x, R_d, s, n, T, in, B, B_hat, A_hat, n_iter);
 }
 
 // ---- run_basis_train.m:58-91 for a batch of training signals (include/snmf.h: snmf_run_basis_train_audio_batch_*) -----------------

@@ -573,3 +573,11 @@ extern "C" int snmf_run_basis_dnmf_batch_fp64(snmf_ctx* ctx, const snmf_params* 
                                               int32_t* n_iter) {
     return dnmf_batch<double>("snmf_run_basis_dnmf_batch_fp64", make64, ctx, p, R_x, R_d, n_problems, T, Y, X, D, B, H0, B_hat, A_hat, n_iter);
 }
+extern "C" int snmf_run_basis_dnmf_batch_ranks_fp64(snmf_ctx* ctx, const snmf_params* p, const int32_t* R_x, const int32_t* R_d,
+                                                    const snmf_problem_settings* s, int32_t n_problems, const int32_t* T,
+                                                    const double* const* Y, const double* const* X, const double* const* D,
+                                                    const double* const* B, const double* const* H0, double* const* B_hat,
+                                                    double* const* A_hat, int32_t* n_iter) {
+    return dnmf_batch_ranks<double>("snmf_run_basis_dnmf_batch_ranks_fp64", make64, ctx, p, R_x, R_d, s, n_problems, T, Y, X, D, B, H0, B_hat,
+                                    A_hat, n_iter);
+}

@@ -78,6 +78,7 @@ struct Batch64 final : snmf_batch {
         return load_t(k, V, ldV, W0, H0, M, ldM);
     }
     int take_h0(snmf_batch& src, int row0) override;
+    int take_h0_rows(snmf_batch& src, const int32_t* row0) override;
     int take_w0(const int64_t* idx, bool unit_columns) override;
     size_t v_elem() const override { return sizeof(double); }
     int v_blocks(std::vector<VBlock>* out) override;
@@ -449,6 +450,46 @@ int Batch64::take_h0(snmf_batch& src_, int row0) {
     hipLaunchKernelGGL(k_b64_take_h, dim3(elem_grid(this, a.r), B), dim3(256), 0, ctx->stream, a, (const double*)src->a.H, src->a.r, row0);
     HIP_TRY(hipGetLastError());
     for (int k = 0; k < B; ++k) SN_TRY(scale_h0(k));
+    return SNMF_OK;
+}
+
+// take_h0 for any two fp64 batches, with or without ranks and settings: problem k takes rows [row0[k], row0[k] + r_k) of its
+// source's H, both at their own prefix offsets.  One launch reads both tables of problems and the row offsets from the device.
+int Batch64::take_h0_rows(snmf_batch& src_, const int32_t* row0) {
+    const Batch64* src = dynamic_cast<const Batch64*>(&src_);
+    if (!src || src == this) return fail(SNMF_ERR_INTERNAL, "take_h0_rows: the source is not another fp64 batch engine");
+    if (!row0) return fail(SNMF_ERR_INVALID, "take_h0_rows: NULL argument");
+    if (!src->ran || src->ctx != ctx) return fail(SNMF_ERR_STATE, "take_h0_rows: the source batch has not run on this context");
+    if (src->B != B) return fail(SNMF_ERR_DIM, "take_h0_rows: %d problems from a batch of %d", B, src->B);
+    for (int k = 0; k < B; ++k) {
+        if (src->prob[k].T != prob[k].T)
+            return fail(SNMF_ERR_DIM, "take_h0_rows: problem %d has %d frames, its source %d", k, prob[k].T, src->prob[k].T);
+        if (row0[k] < 0 || (long long)row0[k] + prob[k].r > src->prob[k].r)
+            return fail(SNMF_ERR_DIM, "take_h0_rows: problem %d: rows [%d, %lld) of an H of %d rows", k, row0[k], (long long)row0[k] + prob[k].r,
+                        src->prob[k].r);
+    }
+    struct Tmp {  // (a table of this call alone: the device block is carved once, when the batch is made)
+        void* q = nullptr;
+        ~Tmp() {
+            if (q) hipFree(q);
+        }
+    } tmp;
+    const size_t bytes = sizeof(int32_t) * (size_t)B;
+    {
+        hipError_t e = hipMalloc(&tmp.q, bytes);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            tmp.q = nullptr;
+            return fail(SNMF_ERR_NOMEM, "hipMalloc(%zu bytes): %s", bytes, hipGetErrorString(e));
+        }
+    }
+    hipStream_t st = ctx->stream;
+    HIP_TRY(hipMemcpyAsync(tmp.q, row0, bytes, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_b64_take_h_rows, dim3(elem_grid(this, a.r), B), dim3(256), 0, st, a, (const B64Prob*)src->dprob, (const double*)src->a.H,
+                       (const int32_t*)tmp.q);
+    HIP_TRY(hipGetLastError());
+    for (int k = 0; k < B; ++k) SN_TRY(scale_h0(k));
+    HIP_TRY(hipStreamSynchronize(st));  // (the table is freed on return, and the caller's array may go)
     return SNMF_OK;
 }
 

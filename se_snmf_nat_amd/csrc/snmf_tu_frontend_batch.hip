@@ -3,6 +3,7 @@
 //
 //   snmf_stft_features_batch_f32 / _fp64             TF_mag (or TF_Mel) of n signals, tight host arrays in and out
 //   snmf_run_basis_dnmf_audio_batch_f64 / _fp64      run_basis_DNMF.m:1-55 (and its Mel twin) for n pairs of WAVEFORMS
+//   snmf_run_basis_dnmf_audio_batch_ranks_fp64       the fp64 entry with a rank pair and settings per problem
 //   snmf_run_basis_train_audio_batch_f64 / _fp64     run_basis_train.m:58-91 for the training signals of n classes
 //   snmf_run_basis_train_signals_batch_f64 / _fp64   the same on the signals a snmf_train_signals handle holds in HBM
 //   snmf_run_basis_train_audio_batch_ranks_fp64, snmf_run_basis_train_signals_batch_ranks_fp64
@@ -271,11 +272,14 @@ int features_batch(const char* entry, snmf_ctx* ctx, const snmf_stft_params* sp,
 }
 
 // ---- run_basis_DNMF from the waveforms of n problems ------------------------------------------------------------------------------
+// per_problem (snmf_run_basis_dnmf_audio_batch_ranks_fp64): problem k has the rank pair (R_xs[k], R_ds[k]) and, with st, the settings
+// st[k]; R_x and R_d are not looked at.  The front-end does not know the ranks: the same slab and the same launches.
 template <typename S>
 int dnmf_audio_batch(const char* entry, snmf_batch* (*make)(), snmf_ctx* ctx, const snmf_params* p, const snmf_stft_params* sp, int32_t R_x,
                      int32_t R_d, int32_t n, const S* const* x, const int64_t* n_x, const S* const* d, const int64_t* n_d, const S* mel,
                      int32_t mel_M, const double* const* B, const double* const* H0, const uint64_t* seed, double* const* B_hat,
-                     double* const* A_hat, int32_t* n_iter) {
+                     double* const* A_hat, int32_t* n_iter, bool per_problem = false, const int32_t* R_xs = nullptr,
+                     const int32_t* R_ds = nullptr, const snmf_problem_settings* st = nullptr) {
     if (!ctx || !p || !x || !n_x || !d || !n_d || !B || !B_hat) return fail(SNMF_ERR_INVALID, "%s: NULL argument", entry);
     SN_TRY(check_batch_size(entry, n, "n_problems"));
     SN_TRY(validate_stft(sp));
@@ -323,6 +327,7 @@ int dnmf_audio_batch(const char* entry, snmf_batch* (*make)(), snmf_ctx* ctx, co
         for (int k = 0; k < n; ++k) s0[k] = base + off[k];
         return fe.run(n, s0.data(), T.data(), blocks.data());
     };
+    if (per_problem) return dnmf_batch_run_ranks<double>(entry, make, ctx, p, R_xs, R_ds, st, n, T.data(), in, B, B_hat, A_hat, n_iter);
     return dnmf_batch_run<double>(entry, make, ctx, p, R_x, R_d, n, T.data(), in, B, B_hat, A_hat, n_iter);
 }
 
@@ -545,4 +550,14 @@ extern "C" int snmf_run_basis_dnmf_audio_batch_fp64(snmf_ctx* ctx, const snmf_pa
                                                     double* const* A_hat, int32_t* n_iter) {
     return dnmf_audio_batch<double>("snmf_run_basis_dnmf_audio_batch_fp64", make64, ctx, p, sp, R_x, R_d, n_problems, x, n_x, d, n_d, mel, mel_M, B,
                                     H0, seed, B_hat, A_hat, n_iter);
+}
+
+extern "C" int snmf_run_basis_dnmf_audio_batch_ranks_fp64(snmf_ctx* ctx, const snmf_params* p, const snmf_stft_params* sp, const int32_t* R_x,
+                                                          const int32_t* R_d, const snmf_problem_settings* s, int32_t n_problems,
+                                                          const double* const* x, const int64_t* n_x, const double* const* d,
+                                                          const int64_t* n_d, const double* mel, int32_t mel_M, const double* const* B,
+                                                          const double* const* H0, const uint64_t* seed, double* const* B_hat,
+                                                          double* const* A_hat, int32_t* n_iter) {
+    return dnmf_audio_batch<double>("snmf_run_basis_dnmf_audio_batch_ranks_fp64", make64, ctx, p, sp, 0, 0, n_problems, x, n_x, d, n_d, mel, mel_M,
+                                    B, H0, seed, B_hat, A_hat, n_iter, true, R_x, R_d, s);
 }

@@ -550,10 +550,11 @@ def run_basis_DNMF_Mel(x, d, B, p, *, ctx=None, h0="host", dtype=None, precision
     return _run_basis_dnmf_audio(x, d, B, p, ctx=ctx, mel=True, h0=h0, precision=precision, dtype=dtype)  # :1-95
 
 
-def _run_basis_dnmf_audio_batch(xs, ds, B, p, *, ctx, mel, h0, precision, dtype, info):
+def _run_basis_dnmf_audio_batch(xs, ds, B, p, *, ctx, mel, h0, precision, dtype, info, settings=None):
     """ONE call across the C ABI (snmf_run_basis_dnmf_audio_batch_f64; precision="fp64": _fp64) for every waveform pair: the
     waveforms go up as one slab, the three feature sets of all problems are formed in HBM by shared launches, and the three
-    solves are three resident batches.  Every error that needs no device is raised before the library is loaded."""
+    solves are three resident batches.  Every error that needs no device is raised before the library is loaded.
+    A sequence for p["R_x"] / p["R_d"] or settings per problem: snmf_run_basis_dnmf_audio_batch_ranks_fp64 (fp64 only)."""
     _check_precision(precision)
     _check_dtype(dtype)
     f64 = precision == "fp64"
@@ -566,8 +567,11 @@ def _run_basis_dnmf_audio_batch(xs, ds, B, p, *, ctx, mel, h0, precision, dtype,
         raise SnmfError(1, "the batch is empty: xs must hold at least one waveform")
     if len(ds) != n:
         raise SnmfError(1, f"{n} clean and {len(ds)} noise waveforms: one of each per problem")
-    R_x, R_d = int(p["R_x"]), int(p["R_d"])
-    r = R_x + R_d
+    from .batch import _dnmf_rank_pairs
+    pairs = _dnmf_rank_pairs(p["R_x"], p["R_d"], n, settings, precision)
+    if pairs is None:
+        R_x, R_d = int(p["R_x"]), int(p["R_d"])
+        r = R_x + R_d
     K = 2 * int(p.get("Splice", 0)) + 1
     M = int(p["F_order"]) if mel else 0
     F = K * M if mel else K * (int(p["fftlength"]) // 2 + 1)
@@ -575,6 +579,8 @@ def _run_basis_dnmf_audio_batch(xs, ds, B, p, *, ctx, mel, h0, precision, dtype,
     for k, T in enumerate(Ts):
         if T < 1:
             raise SnmfError(3, f"the signals of problem {k} are shorter than one analysis frame")
+    if pairs is not None:
+        return _dnmf_audio_batch_ranks(xs, ds, B, p, pairs, settings, F, M, Ts, ctx=ctx, mel=mel, h0=h0, dtype=dtype, info=info)
     if isinstance(B, (list, tuple)):
         if len(B) != n:
             raise SnmfError(3, f"B is a list of {len(B)}, the batch has {n} problems")
@@ -625,7 +631,41 @@ def _run_basis_dnmf_audio_batch(xs, ds, B, p, *, ctx, mel, h0, precision, dtype,
     return list(zip(B_hat, A_hat))
 
 
-def run_basis_DNMF_batch(xs, ds, B, p, *, ctx=None, h0="host", precision="fp32", info=None, dtype=None):
+def _dnmf_audio_batch_ranks(xs, ds, B, p, pairs, settings, F, M, Ts, *, ctx, mel, h0, dtype, info):
+    """_run_basis_dnmf_audio_batch with a rank pair per problem, fp64 (snmf_run_basis_dnmf_audio_batch_ranks_fp64): the waveforms
+    and the frame counts are checked.  The host draw is rand(r_k, T_k) per problem in list order from one generator; the device
+    draw of problem k is philox_uniform(random_seed + k, r_k, T_k)."""
+    from .batch import _dnmf_rank_inputs, _dnmf_rank_params
+    n = len(xs)
+    Rxs, Rds = pairs
+    rs = [a + b for a, b in zip(Rxs, Rds)]
+    seed = int(p.get("random_seed", 1))
+    Bs, H0s = _dnmf_rank_inputs(B, h0, rs, F, Ts, ("host", "device"), seed)
+    q, sarr = _dnmf_rank_params(p, settings, n, F, max(rs))
+    _fp64_rules(dtype, None, "the fp64 DNMF batch")
+    seeds = np.array([seed + k for k in range(n)], np.uint64) if H0s is None else None
+    melm = frontend._mel_table(p, np.float64) if mel else None
+    sp, _win = frontend._params(p)
+
+    lib = _lib.load()
+    ctx = ctx or default_context()
+    B_hat = [np.empty((F, r), order="F") for r in rs]
+    A_hat = [np.empty((r, T), order="F") for r, T in zip(rs, Ts)]
+    n_iter = np.zeros(3 * n, np.int32)
+    n_x, n_d = (np.array([a.size for a in v], np.int64) for v in (xs, ds))
+    rx, rd = np.array(Rxs, np.int32), np.array(Rds, np.int32)
+    ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None  # noqa: E731
+    ptrs = lambda arrs: (C.c_void_p * n)(*[a.ctypes.data for a in arrs]) if arrs is not None else None  # noqa: E731
+    _lib.check(lib.snmf_run_basis_dnmf_audio_batch_ranks_fp64(ctx._h, C.byref(q), C.byref(sp), ptr(rx), ptr(rd), sarr, n, ptrs(xs), ptr(n_x),
+                                                              ptrs(ds), ptr(n_d), ptr(melm), M, ptrs(Bs), ptrs(H0s), ptr(seeds), ptrs(B_hat),
+                                                              ptrs(A_hat), ptr(n_iter)))
+    if info is not None:
+        info["n_iter"] = [[int(v) for v in n_iter[3 * k:3 * k + 3]] for k in range(n)]
+        info["T"] = list(Ts)
+    return list(zip(B_hat, A_hat))
+
+
+def run_basis_DNMF_batch(xs, ds, B, p, *, ctx=None, h0="host", precision="fp32", info=None, dtype=None, settings=None):
     """[(B_hat_k, A_hat_k)] = run_basis_DNMF(x_k, d_k, B_k, p) for every pair of the two lists of waveforms, solved together
     (snmf_run_basis_dnmf_audio_batch_*).  B: one F x (R_x + R_d) array for every problem, or a list of them; p: as for
     run_basis_DNMF, shared.  h0: "host" = rand(r, T_k) of solve 1 drawn per problem, in list order, from one
@@ -635,11 +675,20 @@ def run_basis_DNMF_batch(xs, ds, B, p, *, ctx=None, h0="host", precision="fp32",
     run_basis_dnmf_batch on the features stft_features gives for y_k = float32(x_k) + float32(d_k), x_k and d_k.
     precision="fp64": everything in double; problem k is bit for bit run_basis_DNMF(x_k, d_k, B_k, p, precision="fp64") alone
     with the same H0 (dtype=np.float32 is then SnmfError status 1).
+    A rank pair per problem (precision="fp64" only, snmf_run_basis_dnmf_audio_batch_ranks_fp64): p["R_x"] and p["R_d"] may each be
+    a sequence of len(xs) ints, as p["r"] may be for sparse_nmf_batch_fp64.  B is then a list of F x (R_x[k] + R_d[k]) arrays (one
+    array only when every pair is the same); with r_k = R_x[k] + R_d[k], h0="host" draws rand(r_k, T_k) per problem in list order
+    from the one RandomState, h0="device" draws problem k from philox_uniform(random_seed + k, r_k, T_k), and a list holds
+    r_k x T_k arrays.  settings: one dict per problem with keys among cf, beta, sparsity, max_iter, conv_eps (a missing key takes
+    p's value), held in all three solves of the problem.  Problem k stays bit for bit run_basis_DNMF alone with its own ranks and
+    settings.  A sequence or settings with precision="fp32" is SnmfError status 8.
     info["n_iter"] receives a list of [n1, n2, n3], info["T"] the frame counts.  Returns a list of (B_hat, A_hat)."""
-    return _run_basis_dnmf_audio_batch(xs, ds, B, p, ctx=ctx, mel=False, h0=h0, precision=precision, dtype=dtype, info=info)
+    return _run_basis_dnmf_audio_batch(xs, ds, B, p, ctx=ctx, mel=False, h0=h0, precision=precision, dtype=dtype, info=info,
+                                       settings=settings)
 
 
-def run_basis_DNMF_Mel_batch(xs, ds, B, p, *, ctx=None, h0="host", precision="fp32", info=None, dtype=None):
+def run_basis_DNMF_Mel_batch(xs, ds, B, p, *, ctx=None, h0="host", precision="fp32", info=None, dtype=None, settings=None):
     """run_basis_DNMF_batch on the Mel projections of the three feature sets (run_basis_DNMF_Mel.m:21-69); B: the Mel exemplar
     bases (F_order * (2 * Splice + 1) rows)."""
-    return _run_basis_dnmf_audio_batch(xs, ds, B, p, ctx=ctx, mel=True, h0=h0, precision=precision, dtype=dtype, info=info)
+    return _run_basis_dnmf_audio_batch(xs, ds, B, p, ctx=ctx, mel=True, h0=h0, precision=precision, dtype=dtype, info=info,
+                                       settings=settings)
