@@ -627,6 +627,43 @@ int snmf_online_batch_process_classes_f64(snmf_online_batch* b, const double* co
  * new recording starts from exactly the draws its fp64 reference run uses.  SNMF_ERR_STATE on an fp32 batch. */
 int snmf_online_batch_restart_f64(snmf_online_batch* b, int32_t n, const int32_t* slots, const double* B_DFT_d, const double* H0,
                                   const double* Ad_blk0);
+/* Added within 5.  Settings and an event dictionary of its own for every stream of an fp64 batch: the consumer of the pairs
+ * (B_x, B_d) that snmf_run_basis_dnmf_batch_fp64 re-trains per noise type, and of the reference's comparison runs, which
+ * enhance one corpus under several settings files (adapt_train_N, sparsity, max_iter, Wiener / MMSE, alpha_eta, alpha_d, beta).
+ * snmf_online_stream_settings holds, in the units of snmf_online_params, the fields a stream may have of its own; everything
+ * else of snmf_online_params is the batch's geometry and stays shared: the transform and windows, delay, DCbin(_back), preemph,
+ * pow, nonzerofloor, R_x, R_d, R_a, m_a, P_len_l, cost_check, class_outputs and the class partition. */
+typedef struct snmf_online_stream_settings {
+    double beta_div, sparsity, conv_eps;
+    int32_t max_iter;
+    int32_t enhance_method, init_N_len;
+    double alpha_eta, alpha_d, beta, beta_max;
+    int32_t blk_sparse, P_len_k, blk_gap;
+    double alpha_p;
+    int32_t adapt_train_N;
+    double overlap_m_a, Ar_up;
+} snmf_online_stream_settings;
+/* snmf_online_batch_create_f64 with B_DFT_x F x R_x x S (stream k's event dictionary at k * F * R_x) and settings[S]
+ * (NULL: p's for every stream; p's own values of these fields are then the only ones used).  Every entry is checked like p
+ * itself, on the shared geometry, with the same status codes.  The rings exist when any stream needs them (P_len_l columns
+ * with a block-sparse stream, R_a x m_a with an adapting one); Ad_blk0 (R_a x m_a x S) is required when any stream adapts, and
+ * the entries of streams that do not are not used.  The ring envelope of snmf_online_batch_create_f64 is checked for every
+ * divergence (beta_div 1, 2, other) that an adapting stream uses.  Stream k's outputs, trace and dictionary are bit for bit
+ * those of a batch of one created by snmf_online_batch_create_f64 with its dictionary pair and its settings in p. */
+int snmf_online_batch_create_streams_f64(snmf_ctx* ctx, const snmf_online_params* p, int32_t S, const double* B_DFT_x,
+                                         const double* B_DFT_d0, const double* H0, const double* Ad_blk0,
+                                         const snmf_online_stream_settings* settings, const double* win_stft,
+                                         const double* win_istft, snmf_online_batch** out);
+/* snmf_online_batch_restart_f64 that may also give the listed streams another event dictionary (B_DFT_x F x R_x x n, NULL:
+ * each keeps its own) and other settings (settings[n], NULL: each keeps its own).  A stream that adapts after the call needs
+ * an Ad_blk0, here or from an earlier call (SNMF_ERR_INVALID otherwise).  A refused call leaves the batch as it was.
+ * SNMF_ERR_STATE on an fp32 batch. */
+int snmf_online_batch_restart_streams_f64(snmf_online_batch* b, int32_t n, const int32_t* slots, const double* B_DFT_x,
+                                          const double* B_DFT_d, const double* H0, const double* Ad_blk0,
+                                          const snmf_online_stream_settings* settings);
+/* Stream k's settings as they were last given (p's for a batch made by snmf_online_batch_create_f64).  SNMF_ERR_STATE on an
+ * fp32 batch. */
+int snmf_online_batch_get_settings(snmf_online_batch* b, int32_t k, snmf_online_stream_settings* out);
 /* Diagnostics of stream k's most recent frames (the newest 65536 per stream), as snmf_online_trace. */
 int snmf_online_batch_trace(snmf_online_batch* b, int32_t k, snmf_online_frame* out, int64_t cap, int64_t* n);
 void snmf_online_batch_destroy(snmf_online_batch* b);

@@ -78,6 +78,7 @@ SYMBOLS = [
     "snmf_online_batch_set_classes", "snmf_online_batch_process_classes_f32",
     "snmf_online_batch_create_f64", "snmf_online_batch_process_f64", "snmf_online_batch_process_classes_f64",
     "snmf_online_batch_restart_f64",
+    "snmf_online_batch_create_streams_f64", "snmf_online_batch_restart_streams_f64", "snmf_online_batch_get_settings",
     "snmf_multi_create", "snmf_multi_destroy", "snmf_multi_set_v_f64", "snmf_multi_set_v_f32", "snmf_multi_set_w_f64",
     "snmf_multi_set_w_f32", "snmf_multi_set_h_f64", "snmf_multi_set_h_f32", "snmf_multi_set_sparsity_f64",
     "snmf_multi_set_sparsity_f32", "snmf_multi_init", "snmf_multi_run", "snmf_multi_get_w_f64", "snmf_multi_get_w_f32",
@@ -158,6 +159,19 @@ class SnmfOnlineParams(C.Structure):
         ("adapt_train_N", C.c_int32), ("R_a", C.c_int32), ("m_a", C.c_int32),
         ("overlap_m_a", C.c_double), ("Ar_up", C.c_double),
         ("class_outputs", C.c_int32), ("basis_update_N", C.c_int32), ("basis_update_E", C.c_int32),
+    ]
+
+
+class SnmfOnlineStreamSettings(C.Structure):
+    """snmf_online_stream_settings: the fields of snmf_online_params a stream of an fp64 batch may have of its own."""
+    _fields_ = [
+        ("beta_div", C.c_double), ("sparsity", C.c_double), ("conv_eps", C.c_double), ("max_iter", C.c_int32),
+        ("enhance_method", C.c_int32), ("init_N_len", C.c_int32),
+        ("alpha_eta", C.c_double), ("alpha_d", C.c_double), ("beta", C.c_double), ("beta_max", C.c_double),
+        ("blk_sparse", C.c_int32), ("P_len_k", C.c_int32), ("blk_gap", C.c_int32),
+        ("alpha_p", C.c_double),
+        ("adapt_train_N", C.c_int32),
+        ("overlap_m_a", C.c_double), ("Ar_up", C.c_double),
     ]
 
 
@@ -321,6 +335,9 @@ def load():
     sig["snmf_online_batch_process_f64"] = (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp])
     sig["snmf_online_batch_process_classes_f64"] = (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp])
     sig["snmf_online_batch_restart_f64"] = (C.c_int, [vp, i32, vp, vp, vp, vp])
+    sig["snmf_online_batch_create_streams_f64"] = (C.c_int, [vp, OP, i32, vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp)])
+    sig["snmf_online_batch_restart_streams_f64"] = (C.c_int, [vp, i32, vp, vp, vp, vp, vp, vp])
+    sig["snmf_online_batch_get_settings"] = (C.c_int, [vp, i32, C.POINTER(SnmfOnlineStreamSettings)])
     for ty in ("f64", "f32"):
         sig[f"snmf_plan_solve_frames_{ty}"] = (C.c_int, [vp, i32, vp, i64, i32, vp, vp, vp, vp])
     for nm in ("v", "w", "h", "mask"):

@@ -12,14 +12,28 @@
 //   k_wadapt_batch64  the W-only adaptation solve of :296-336, ONE workgroup per due stream, gated on the device
 //   k_obassemble64 / k_obrefresh64  the re-assembly of :336 and the next frame solve's dictionary images, gated
 //   k_obistft64 / k_obtail64 / k_obola64  inverse STFT and overlap-add of src/NTF_sep_event_RT.m:104-124
-//   k_obrestart64  the state of the listed streams back to init_buff
-// DFT mode and the supervised frame solve only, as the single-stream fp64 mode.
+//   k_obrestart64  the state of the listed streams back to init_buff, each from its own event dictionary
+// Every stream has its own settings (OStreamSettings, a device table indexed by the stream) and its own B_DFT_x; the
+// geometry is the batch's.  DFT mode and the supervised frame solve only, as the single-stream fp64 mode.
 // Included by snmf_tu_online_batch_f64.hip only.
 #pragma once
 #include "snmf_online_batch_common.h"
 #include "snmf_online_f64_core.h"
 
 namespace snmf {
+
+// Entry s of the per-stream settings table (device, [S], next to the per-stream state): what the frame solve, the
+// post-filter, the adaptation and the restart read per stream instead of per launch.  The geometry (transform, windows,
+// ranks, ring sizes, cost_check, class partition) stays in the launch arguments: it is the batch's.  Written by the host
+// with hipMemcpyAsync from its mirror, read with ordinary loads; s is uniform over a workgroup, so the loads are scalar.
+struct OStreamSettings {
+    double beta_div, sparsity, conv_eps;               // the frame and adaptation solves (src/sparse_nmf.m)
+    double alpha_eta, alpha_d, beta, beta_max;         // the enhancement filter (:221-261)
+    double alpha_p, Ar_up;                             // src/blk_sparse.m:28, :264
+    int max_iter, enhance_method, init_N_len;
+    int blk_sparse, P_len_k, blk_gap;
+    int adapt_train_N, switch_at;                      // switch_at = floor(overlap_m_a * m_a) (:294)
+};
 
 // src/bnmf_sep_event_RT_IS16.m:65-81 for every (frame, stream); dynamic LDS = 2 N double2 (as k_ostft64)
 template <int LOGN>
@@ -34,11 +48,17 @@ __global__ __launch_bounds__(256) void k_obstft64(OStftArgsT<double> a, OBatchFr
 }
 
 // The frame solves: `a` holds stream 0's images and H0 and the chunk's slot-indexed buffers; grid (frames, S).  step >= 0:
-// frame `step` of every stream that has it (grid x = 1); step < 0: frame blockIdx.x.  Dynamic LDS as k_hsolve64.
-__global__ __launch_bounds__(1024) void k_obhsolve64(HSolve64Args a, OBatchFrames fr, int step) {
+// frame `step` of every stream that has it (grid x = 1); step < 0: frame blockIdx.x.  Dynamic LDS as k_hsolve64.  The
+// divergence, the sparsity weight and the stop rule are entry s of `set`.
+__global__ __launch_bounds__(1024) void k_obhsolve64(HSolve64Args a, const OStreamSettings* __restrict__ set, OBatchFrames fr, int step) {
     extern __shared__ __attribute__((aligned(16))) double sm64[];
     const int s = blockIdx.y, i = step >= 0 ? step : (int)blockIdx.x;
     if (i >= fr.nfr[s]) return;  // (uniform over the workgroup)
+    const OStreamSettings& q = set[s];
+    a.beta = q.beta_div;
+    a.sparsity = q.sparsity;
+    a.conv_eps = q.conv_eps;
+    a.max_iter = q.max_iter;
     const size_t img = (size_t)a.F * a.r;
     a.Wn += (size_t)s * img;
     a.WnT += (size_t)s * img;
@@ -50,8 +70,8 @@ __global__ __launch_bounds__(1024) void k_obhsolve64(HSolve64Args a, OBatchFrame
 
 // One workgroup per stream: opost_frame<double> on that stream's state, its frames one after the other (k_obpost's
 // indexing).  step >= 0: frame `step` of every stream that has it; < 0: all frames of the chunk in order.  Dynamic LDS =
-// (r + 6 F) doubles.
-__global__ __launch_bounds__(1024) void k_obpost64(OPostArgsT<double> a0, OBatchFrames fr, int step) {
+// (r + 6 F) doubles.  The filter's and the trigger's settings are re-based like the pointers: entry s of `set`.
+__global__ __launch_bounds__(1024) void k_obpost64(OPostArgsT<double> a0, const OStreamSettings* __restrict__ set, OBatchFrames fr, int step) {
     extern __shared__ __attribute__((aligned(16))) double sm64[];
     __shared__ double red[16];
     const int s = blockIdx.x, S = fr.S, n = fr.nfr[s];
@@ -64,6 +84,13 @@ __global__ __launch_bounds__(1024) void k_obpost64(OPostArgsT<double> a0, OBatch
     as.adblk += (size_t)s * a0.Ra * a0.ma;
     as.rup += (size_t)s * a0.Ra;
     as.dev += s;
+    {
+        const OStreamSettings& q = set[s];
+        as.blk_sparse = q.blk_sparse; as.Pk = q.P_len_k; as.gap = q.blk_gap; as.alpha_p = q.alpha_p;
+        as.adapt = q.adapt_train_N; as.switch_at = q.switch_at; as.Ar_up = q.Ar_up;
+        as.wiener = q.enhance_method == 0; as.init_N_len = q.init_N_len;
+        as.alpha_eta = q.alpha_eta; as.alpha_d = q.alpha_d; as.beta0 = q.beta; as.beta_max = q.beta_max;
+    }
     const int i0 = step >= 0 ? step : 0, i1 = step >= 0 ? step + 1 : n;
     for (int i = i0; i < i1 && i < n; ++i) {
         const size_t slot = (size_t)i * S + s;
@@ -128,8 +155,9 @@ struct WBatch64Args {
     double* P;             // [S][Fb][RP] denominator statistics (beta != 1)
     double* Vt;            // [S][Fb / 4][ma][4] V in time order, floored
     int* iters;            // [chunk slots] iterations of the solve
-    int F, r, Rx, Ra, ma, max_iter, cost_check;
-    double beta, sparsity, flr, conv_eps;
+    const OStreamSettings* set;  // [S] beta_div, sparsity, max_iter, conv_eps, adapt_train_N of each stream
+    int F, r, Rx, Ra, ma, cost_check;
+    double flr;
 };
 
 // dynamic LDS of k_wadapt_batch64 in bytes (kl: beta == 1 keeps no denominator image).  R_a <= 64 and m_a <= 128 fit the
@@ -142,13 +170,22 @@ __host__ __device__ inline size_t wbatch64_lds(int Ra, int ma, int kl) {
 }
 
 enum : int { kWb64KL = 0, kWb64ED = 1, kWb64GEN = 2 };
+// the instantiation of k_wadapt_batch64 that serves a divergence
+__host__ __device__ inline int wbatch64_class(double beta_div) { return beta_div == 1.0 ? kWb64KL : beta_div == 2.0 ? kWb64ED : kWb64GEN; }
 
+// One launch per divergence class present among the adapting streams, each over all S streams with its own dynamic LDS: a
+// workgroup whose stream does not adapt, or whose divergence is another instantiation's, returns before it touches LDS or
+// scratch.
 template <int BM>
 __global__ __launch_bounds__(kWb64NT) void k_wadapt_batch64(WBatch64Args a) {
     constexpr int NW = kWb64NW, RB = kWb64RB, RP = kWb64RP, NT = kWb64NT;
     constexpr bool KL = BM == kWb64KL;
     const int s = blockIdx.x;
-    if (!ob_due(a.status, a.nfr, a.step, a.S, s)) return;  // (uniform over the workgroup)
+    const OStreamSettings& set = a.set[s];
+    if (!set.adapt_train_N || wbatch64_class(set.beta_div) != BM) return;  // (uniform over the workgroup)
+    if (!ob_due(a.status, a.nfr, a.step, a.S, s)) return;
+    const int max_iter = set.max_iter;
+    const double sparsity = set.sparsity, conv_eps = set.conv_eps;
     extern __shared__ __attribute__((aligned(16))) double wsm[];
     const int F = a.F, Ra = a.Ra, ma = a.ma, ma1 = ma | 1, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int Fb = (F + RB - 1) / RB * RB, nblk = Fb / RB;
@@ -177,7 +214,7 @@ __global__ __launch_bounds__(kWb64NT) void k_wadapt_batch64(WBatch64Args a) {
     double* P = KL ? nullptr : a.P + (size_t)s * Fb * RP;  // (beta = 1 keeps no denominator statistics)
     double* Vt = a.Vt + (size_t)s * Fb * ma;
     const int oldest = a.dev[s].n_push % ma;
-    const double beta = a.beta;
+    const double beta = set.beta_div;
     const bool kact = lane < Ra;           // this lane owns column `lane`
     const bool up = kact && rup[kact ? lane : 0] != 0;
 
@@ -255,15 +292,15 @@ __global__ __launch_bounds__(kWb64NT) void k_wadapt_batch64(WBatch64Args a) {
     __syncthreads();
     const int nact = act[0];
     double sh_const = 0.0;                                     // sum(sum(sparsity .* h)) (:261), constant: H is fixed
-    for (int k = 0; k < Ra; ++k) sh_const += a.sparsity * sk[k];
+    for (int k = 0; k < Ra; ++k) sh_const += sparsity * sk[k];
 
     double last_cost = 0.0;
     int n_rec = 0;
     bool stopped = false;
     const bool t1 = lane + 64 < ma;
     const double* hk = Hs + (size_t)(kact ? lane : 0) * ma1;   // this lane's row of H (column k of the statistics)
-    for (int j = 1; j <= a.max_iter + 1; ++j) {
-        if (j > a.max_iter && !a.cost_check) break;
+    for (int j = 1; j <= max_iter + 1; ++j) {
+        if (j > max_iter && !a.cost_check) break;
         // ---- Lam = max(w*h, flr) of iterate j-1, its divergence, the weights; P and Q on this wave's row blocks --------
         double q0 = 0.0, q1 = 0.0, dterm = 0.0;
         for (int b = w; b < nblk; b += NW) {
@@ -369,7 +406,7 @@ __global__ __launch_bounds__(kWb64NT) void k_wadapt_batch64(WBatch64Args a) {
             const double cost = div + sh_const;
             const int it = j - 1;
             bool stopnow = false;
-            if (it > 1 && a.conv_eps > 0.0) stopnow = fabs(cost - last_cost) / last_cost < a.conv_eps;
+            if (it > 1 && conv_eps > 0.0) stopnow = fabs(cost - last_cost) / last_cost < conv_eps;
             n_rec = it;
             last_cost = cost;
             if (stopnow) {
@@ -377,7 +414,7 @@ __global__ __launch_bounds__(kWb64NT) void k_wadapt_batch64(WBatch64Args a) {
                 break;
             }
         }
-        if (j > a.max_iter) break;
+        if (j > max_iter) break;
         // ---- W update (:215-239) on this thread's entries, then the norms ------------------------------------------------
         s2 = 0.0;
         if (kact) {
@@ -414,7 +451,7 @@ __global__ __launch_bounds__(kWb64NT) void k_wadapt_batch64(WBatch64Args a) {
                 const int f = b * RB + jj;
                 if (f < F) Wu[(size_t)lane * F + f] = Wm[(size_t)f * RP + lane];
             }
-    if (tid == 0) a.iters[(size_t)a.step * a.S + s] = stopped ? n_rec : a.max_iter;
+    if (tid == 0) a.iters[(size_t)a.step * a.S + s] = stopped ? n_rec : max_iter;
 }
 
 // B_DFT_d = [B_d_rem, B_d_tmp, B_d_fix] (:336) of every stream whose adaptation ran (k_obassemble's form): one workgroup per
@@ -475,7 +512,8 @@ constexpr int kRs64Parts = 8;  // workgroups per (stream, array)
 
 struct ORestart64Args {
     const int* slots;       // [n] the streams to restart (distinct, in range: checked on the host)
-    const double* Bx;       // [Rx][F] the shared speech dictionary
+    const double* Bx;       // [S][Rx][F] every stream's own event dictionary
+    const OStreamSettings* set;  // [S] (adapt_train_N of the stream decides its Ad_blk)
     const double* Bd;       // [n][Rd][F] new noise dictionaries, or NULL = keep each stream's (carry; Bfix untouched)
     const double* H0n;      // [n][r] or NULL = keep
     const double* Adn;      // [n][Ra][ma] or NULL = the values the stream last started with (Ad0)
@@ -483,7 +521,7 @@ struct ORestart64Args {
     double *H0, *Ad0, *adblk, *ldblk, *lambda_dav, *Xm_tilde, *r_blk, *tail, *tail_x, *tail_d;
     uint8_t* rup;
     OnlineDev* dev;
-    int F, r, Rx, Rd, Ra, ma, Pl, adapt;
+    int F, r, Rx, Rd, Ra, ma, Pl;
     int64_t ntail;
 };
 
@@ -498,7 +536,7 @@ __global__ __launch_bounds__(256) void k_obrestart64(ORestart64Args a) {
     };
     const size_t nA = (size_t)a.Ra * a.ma;
     switch (arr) {
-        case kRs64Bx: copy(a.B + (size_t)s * a.r * F, a.Bx, (size_t)a.Rx * F); break;
+        case kRs64Bx: copy(a.B + (size_t)s * a.r * F, a.Bx + (size_t)s * a.Rx * F, (size_t)a.Rx * F); break;
         case kRs64Bd:
             if (a.Bd) copy(a.B + (size_t)s * a.r * F + (size_t)a.Rx * F, a.Bd + (size_t)i * a.Rd * F, (size_t)a.Rd * F);
             break;
@@ -512,7 +550,7 @@ __global__ __launch_bounds__(256) void k_obrestart64(ORestart64Args a) {
             if (a.Adn) copy(a.Ad0 + s * nA, a.Adn + i * nA, nA);
             break;
         case kRs64Adblk:  // rand(R_a, m_a) (src/init_buff.m:39); zeros without adaptation
-            if (!a.adapt) fill(a.adblk + s * nA, 0.0, nA);
+            if (!a.set[s].adapt_train_N) fill(a.adblk + s * nA, 0.0, nA);
             else copy(a.adblk + s * nA, a.Adn ? a.Adn + i * nA : a.Ad0 + s * nA, nA);
             break;
         case kRs64Ldblk: fill(a.ldblk + (size_t)s * F * a.ma, 0.0, F * a.ma); break;

@@ -62,7 +62,20 @@ struct OBatchState {
     std::vector<int64_t> l;
     std::vector<uint8_t> finished;
     std::vector<std::deque<snmf_online_frame>> trace;
+    // a mode with settings per stream lists here which streams adapt; empty: p.adapt_train_N holds for every stream
+    std::vector<uint8_t> adapt_s;
 };
+
+// stream s runs the noise-dictionary adaptation / any stream does (the launch structure of a chunk follows the latter)
+template <class H>
+bool obatch_adapts(const H* o, int s) {
+    return o->adapt_s.empty() ? o->p.adapt_train_N != 0 : o->adapt_s[s] != 0;
+}
+template <class H>
+bool obatch_any_adapts(const H* o) {
+    if (o->adapt_s.empty()) return o->p.adapt_train_N != 0;
+    return std::any_of(o->adapt_s.begin(), o->adapt_s.end(), [](uint8_t v) { return v != 0; });
+}
 
 // one stream's output hops of a process call
 template <typename T>
@@ -238,7 +251,7 @@ int obatch_run_chunk(H* o, const std::vector<int>& nfr, const std::vector<int>& 
     const int64_t* d_oo = o->meta_l + 2 * S;
     SN_TRY(obm_begin_chunk(o, fr, C));  // STFT of every frame of the chunk; the post-filter's arguments for its launches below
     HIP_TRY(hipMemsetAsync(o->iters, 0, (size_t)C * S * 4, st));
-    if (!p.adapt_train_N) {
+    if (!obatch_any_adapts(o)) {
         // fixed dictionaries: every frame solve of the chunk in one launch, then one post-filter launch walks the frames
         SN_TRY(obm_frame_solve(o, fr, -1, C));
         SN_TRY(obm_post(o, fr, -1));
@@ -302,7 +315,7 @@ int obatch_run_chunk(H* o, const std::vector<int>& nfr, const std::vector<int>& 
         for (int i = 0; i < nfr[s]; ++i) {
             const OnlineStatus& q = hs[(size_t)i * S + s];
             snmf_online_frame tr = online_frame_record(q);
-            if (p.adapt_train_N && q.do_solve && q.n_up > 0) {
+            if (obatch_adapts(o, s) && q.do_solve && q.n_up > 0) {
                 tr.solved = 1;
                 tr.adapt_iters = hit[(size_t)i * S + s];
             }

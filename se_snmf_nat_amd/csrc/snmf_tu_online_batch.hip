@@ -604,7 +604,7 @@ extern "C" int snmf_online_batch_restart(snmf_online_batch* o, int32_t n, const 
         online_batch_f64_dims(o->f64, &r, &na);
         const size_t m = (size_t)n;
         std::vector<double> h(H0 ? H0 : nullptr, H0 ? H0 + m * r : nullptr), a(Ad ? Ad : nullptr, Ad ? Ad + m * na : nullptr);
-        return online_batch_f64_restart(o->f64, n, slots, Bd, H0 ? h.data() : nullptr, Ad ? a.data() : nullptr);
+        return online_batch_f64_restart(o->f64, n, slots, nullptr, Bd, H0 ? h.data() : nullptr, Ad ? a.data() : nullptr, nullptr);
     }
     return ob_restart_checked(o, n, slots, Bd, nullptr, H0, Ad);  // Mel mode: B_Mel_d carried
 }
@@ -657,6 +657,18 @@ extern "C" int snmf_online_batch_trace(snmf_online_batch* o, int32_t k, snmf_onl
 }
 
 // ---- fp64 mode (snmf_online_batch_f64.h): every input crosses in fp64 and every step from PCM to the fed-back state is fp64 ----
+// the handle around a created fp64 batch
+static int ob_wrap_f64(snmf_ctx* ctx, const snmf_online_params* p, int32_t S, OnlineBatchF64* f, snmf_online_batch** out) {
+    snmf_online_batch* o = new snmf_online_batch();
+    o->ctx = ctx;
+    o->f64 = f;
+    o->p = *p;
+    o->S = S;
+    o->F = p->fftlength / 2 + 1;
+    *out = o;
+    return SNMF_OK;
+}
+
 extern "C" int snmf_online_batch_create_f64(snmf_ctx* ctx, const snmf_online_params* p, int32_t S, const double* Bx, const double* Bd0,
                                             const double* H0, const double* Ad0, const double* win_stft, const double* win_istft,
                                             snmf_online_batch** out) {
@@ -666,15 +678,56 @@ extern "C" int snmf_online_batch_create_f64(snmf_ctx* ctx, const snmf_online_par
     if (p->adapt_train_N && !Ad0) return fail(SNMF_ERR_INVALID, "Ad_blk0 is required when adapt_train_N is set");
     (void)hipGetLastError();  // clean sticky error state, see PLAN_CHECK
     OnlineBatchF64* f = nullptr;
-    SN_TRY(online_batch_f64_create(ctx, p, S, Bx, Bd0, H0, Ad0, win_stft, win_istft, &f));
-    snmf_online_batch* o = new snmf_online_batch();
-    o->ctx = ctx;
-    o->f64 = f;
-    o->p = *p;
-    o->S = S;
-    o->F = p->fftlength / 2 + 1;
-    *out = o;
-    return SNMF_OK;
+    SN_TRY(online_batch_f64_create(ctx, p, S, Bx, 0, Bd0, H0, Ad0, nullptr, win_stft, win_istft, &f));
+    return ob_wrap_f64(ctx, p, S, f, out);
+}
+
+// `p` with one stream's settings in the place of its own: what ob_validate checks for that stream
+static snmf_online_params ob_with_settings(const snmf_online_params& p, const snmf_online_stream_settings& q) {
+    snmf_online_params m = p;
+    m.beta_div = q.beta_div; m.sparsity = q.sparsity; m.conv_eps = q.conv_eps; m.max_iter = q.max_iter;
+    m.enhance_method = q.enhance_method; m.init_N_len = q.init_N_len;
+    m.alpha_eta = q.alpha_eta; m.alpha_d = q.alpha_d; m.beta = q.beta; m.beta_max = q.beta_max;
+    m.blk_sparse = q.blk_sparse; m.P_len_k = q.P_len_k; m.blk_gap = q.blk_gap; m.alpha_p = q.alpha_p;
+    m.adapt_train_N = q.adapt_train_N; m.overlap_m_a = q.overlap_m_a; m.Ar_up = q.Ar_up;
+    return m;
+}
+
+extern "C" int snmf_online_batch_create_streams_f64(snmf_ctx* ctx, const snmf_online_params* p, int32_t S, const double* Bx, const double* Bd0,
+                                                    const double* H0, const double* Ad0, const snmf_online_stream_settings* settings,
+                                                    const double* win_stft, const double* win_istft, snmf_online_batch** out) {
+    if (!ctx || !out || !Bx || !Bd0 || !H0 || !win_stft || !win_istft) return fail(SNMF_ERR_INVALID, "NULL argument");
+    *out = nullptr;
+    SN_TRY(ob_validate(p, S));
+    bool adapts = settings ? false : p->adapt_train_N != 0;
+    for (int k = 0; k < S && settings; ++k) {  // every stream's settings on the shared geometry
+        const snmf_online_params m = ob_with_settings(*p, settings[k]);
+        SN_TRY(ob_validate(&m, S));
+        adapts |= m.adapt_train_N != 0;
+    }
+    if (adapts && !Ad0) return fail(SNMF_ERR_INVALID, "Ad_blk0 is required when adapt_train_N is set");
+    (void)hipGetLastError();  // clean sticky error state, see PLAN_CHECK
+    OnlineBatchF64* f = nullptr;
+    SN_TRY(online_batch_f64_create(ctx, p, S, Bx, 1, Bd0, H0, Ad0, settings, win_stft, win_istft, &f));
+    return ob_wrap_f64(ctx, p, S, f, out);
+}
+
+extern "C" int snmf_online_batch_restart_streams_f64(snmf_online_batch* o, int32_t n, const int32_t* slots, const double* Bx, const double* Bd,
+                                                     const double* H0, const double* Ad, const snmf_online_stream_settings* settings) {
+    if (!o) return fail(SNMF_ERR_INVALID, "online batch handle is NULL");
+    if (!o->f64) return fail(SNMF_ERR_STATE, "snmf_online_batch_restart_streams_f64 needs a batch made by snmf_online_batch_create_f64 / _create_streams_f64");
+    if (n < 0 || n > o->S) return fail(SNMF_ERR_INVALID, "restart of %d streams in a batch of %d", n, o->S);  // (before settings are read)
+    for (int i = 0; i < n && settings; ++i) {
+        const snmf_online_params m = ob_with_settings(o->p, settings[i]);
+        SN_TRY(ob_validate(&m, o->S));
+    }
+    return online_batch_f64_restart(o->f64, n, slots, Bx, Bd, H0, Ad, settings);
+}
+
+extern "C" int snmf_online_batch_get_settings(snmf_online_batch* o, int32_t k, snmf_online_stream_settings* out) {
+    if (!o || !out) return fail(SNMF_ERR_INVALID, "NULL argument");
+    if (!o->f64) return fail(SNMF_ERR_STATE, "snmf_online_batch_get_settings needs a batch made by snmf_online_batch_create_f64 / _create_streams_f64");
+    return online_batch_f64_get_settings(o->f64, k, out);
 }
 
 static int ob_process_f64(snmf_online_batch* o, const double* const* pcm, const int64_t* n, const int32_t* flush, double* const* xt,
@@ -706,5 +759,5 @@ extern "C" int snmf_online_batch_restart_f64(snmf_online_batch* o, int32_t n, co
                                              const double* Ad) {
     if (!o) return fail(SNMF_ERR_INVALID, "online batch handle is NULL");
     if (!o->f64) return fail(SNMF_ERR_STATE, "snmf_online_batch_restart_f64 needs a batch made by snmf_online_batch_create_f64");
-    return online_batch_f64_restart(o->f64, n, slots, Bd, H0, Ad);
+    return online_batch_f64_restart(o->f64, n, slots, nullptr, Bd, H0, Ad, nullptr);
 }

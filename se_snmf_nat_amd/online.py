@@ -30,6 +30,13 @@ stream holds its own fp64 reference run's decisions, also over a chain of files 
 covers B_sep_mode 'DFT', the supervised frame solve, every cf / beta_div, Wiener / MMSE, block sparsity, adaptation on or
 off, class outputs, restart and chains; it refuses (SnmfError 8) B_sep_mode 'Mel', basis_update_N / basis_update_E and, with
 adaptation, a ring beyond R_a <= 64, m_a <= 128.
+
+Settings per stream (fp64 batch only): `OnlineBatchSeparator(..., precision="fp64", settings=[...])` takes a list of S dicts of
+overrides on `p`, and `B_DFT_x` as a list of S event dictionaries, so that one batch enhances a corpus under several settings
+files, or with the (B_x, B_d) pairs run_basis_dnmf_batch re-trained per noise type.  A stream may have its own cf / beta_div,
+sparsity, conv_eps, max_iter, ENHANCE_METHOD, init_N_len, alpha_eta, alpha_d, beta, beta_max, blk_sparse, P_len_k, blk_gap,
+alpha_p, adapt_train_N, overlap_m_a and Ar_up; every other key is the batch's geometry and an entry that changes one raises
+SnmfError(1) naming it.  Each stream's bits are those of a batch of one with its pair and its settings.
 """
 from __future__ import annotations
 
@@ -38,7 +45,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import SnmfError, SnmfOnlineFrame, SnmfOnlineParams
+from ._lib import SnmfError, SnmfOnlineFrame, SnmfOnlineParams, SnmfOnlineStreamSettings
 from .api import default_context
 
 __all__ = ["default_settings", "OnlineSeparator", "ntf_sep_event_rt", "OnlineBatchSeparator", "ntf_sep_event_rt_batch",
@@ -94,6 +101,55 @@ def _online_params(p, R_x, R_d, adapt, R_a, m_a, method, class_outputs):
     q.class_outputs = int(bool(class_outputs))
     q.basis_update_N, q.basis_update_E = int(bool(p.get("basis_update_N", 0))), int(bool(p.get("basis_update_E", 0)))
     return q
+
+
+# the keys of p a stream of an fp64 batch may have of its own (snmf_online_stream_settings); every other key is shared
+_STREAM_KEYS = ("cf", "beta_div", "sparsity", "conv_eps", "max_iter", "ENHANCE_METHOD", "init_N_len", "alpha_eta", "alpha_d", "beta",
+                "beta_max", "blk_sparse", "P_len_k", "blk_gap", "alpha_p", "adapt_train_N", "overlap_m_a", "Ar_up")
+_STREAM_FIELDS = tuple(f for f, _ in SnmfOnlineStreamSettings._fields_)
+
+
+def _stream_settings(p, settings, n, what="stream"):
+    """`settings` (None, one dict for all, or a list of n dicts of overrides on `p`) -> n merged settings dicts.  Raised here,
+    before the library is loaded: SnmfError(8) for an entry that asks for what the fp64 batch does not run, SnmfError(1) for
+    one that changes a key the streams share (the message names it)."""
+    if settings is None:
+        entries = [{}] * n
+    elif isinstance(settings, dict):
+        entries = [settings] * n
+    else:
+        entries = list(settings)
+        if len(entries) != n:
+            raise _invalid(f"settings: {len(entries)} entries for {n} {what}s")
+    out = []
+    for k, e in enumerate(entries):
+        if not isinstance(e, dict):
+            raise _invalid(f"settings of {what} {k} is not a dict")
+        for key in ("basis_update_N", "basis_update_E"):
+            if e.get(key, 0):
+                raise SnmfError(8, f"settings of {what} {k}: semi-supervised frame solves ({key}) are not supported")
+        if e.get("B_sep_mode", "DFT") == "Mel":
+            raise SnmfError(8, f"settings of {what} {k}: B_sep_mode 'Mel' is not supported")
+        for key, v in e.items():
+            if key in _STREAM_KEYS:
+                continue
+            if key not in p or not np.array_equal(np.asarray(v), np.asarray(p[key])):
+                raise _invalid(f"settings of {what} {k} change the shared key {key!r}")
+        m = dict(p)
+        m.update(e)
+        if m.get("ENHANCE_METHOD", "MMSE") not in ("Wiener", "MMSE"):
+            raise ValueError("ENHANCE_METHOD must be 'Wiener' or 'MMSE'")
+        out.append(m)
+    return out
+
+
+def _settings_struct(m, q):
+    """One merged settings dict -> snmf_online_stream_settings, through the conversions of _online_params (q: the batch's)."""
+    qk = _online_params(m, q.R_x, q.R_d, int(bool(m.get("adapt_train_N", 0))), q.R_a, q.m_a, m.get("ENHANCE_METHOD", "MMSE"), q.class_outputs)
+    st = SnmfOnlineStreamSettings()
+    for f in _STREAM_FIELDS:
+        setattr(st, f, getattr(qk, f))
+    return st
 
 
 _MAX_CLASSES = 32  # per side (kOClassMax, csrc/snmf_online.h)
@@ -336,12 +392,20 @@ class OnlineBatchSeparator:
     In DFT mode the Mel arguments are ignored, as in OnlineSeparator.  p.EVENT_RANK / p.NOISE_RANK: one class partition for
     all streams (with class_outputs each stream's dict also holds 'x_hat_i' / 'd_hat_i').
     precision="fp64" is the fp64 mode (snmf_online_batch_create_f64): every array crosses in float64, the signals come back
-    as float64 and basis(k) is the fp64 dictionary; DFT mode only ('Mel' raises SnmfError(8) before any device call)."""
+    as float64 and basis(k) is the fp64 dictionary; DFT mode only ('Mel' raises SnmfError(8) before any device call).
+    In that mode `settings` (a list of S dicts of overrides on `p`, the keys of _STREAM_KEYS) and `B_DFT_x` as a list of S
+    arrays give every stream its own settings and event dictionary (snmf_online_batch_create_streams_f64); stream k's output
+    is then what a batch of one with its dictionaries and `dict(p, **settings[k])` produces.  `Ad_blk0` is needed when any
+    stream adapts and holds an entry for every stream.  Without either, the call is the uniform one, unchanged."""
 
     def __init__(self, B_DFT_x, B_DFT_d, p, n_streams, H0=None, Ad_blk0=None, ctx=None, class_outputs=False, B_Mel_x=None,
-                 B_Mel_d=None, precision="fp32"):
+                 B_Mel_d=None, precision="fp32", settings=None):
         if precision not in ("fp32", "fp64"):
             raise ValueError("precision must be 'fp32' or 'fp64'")
+        Bx_list = list(B_DFT_x) if isinstance(B_DFT_x, (list, tuple)) else None
+        per_stream = settings is not None or Bx_list is not None
+        if per_stream and precision != "fp64":
+            raise SnmfError(8, "batched separator: settings and B_DFT_x per stream need precision='fp64'")
         self.precision = precision
         dt = np.float64 if precision == "fp64" else np.float32  # what crosses the C ABI
         self._dt = dt
@@ -363,7 +427,9 @@ class OnlineBatchSeparator:
         if method not in ("Wiener", "MMSE"):
             raise ValueError("ENHANCE_METHOD must be 'Wiener' or 'MMSE'")
         F = p["fftlength"] // 2 + 1
-        Bx = np.asfortranarray(B_DFT_x, dtype=dt)
+        if Bx_list is not None and len(Bx_list) != S:
+            raise _invalid(f"B_DFT_x: {len(Bx_list)} entries for {S} streams")
+        Bx = np.asfortranarray(Bx_list[0] if Bx_list is not None else B_DFT_x, dtype=dt)
         if Bx.ndim != 2 or Bx.shape[0] != F:
             raise _invalid(f"B_DFT_x must have fftlength/2+1 = {F} rows")
         R_x = Bx.shape[1]
@@ -374,6 +440,11 @@ class OnlineBatchSeparator:
         R_d = Bd_first.shape[1]
         r = R_x + R_d
         adapt = int(bool(p.get("adapt_train_N", 0)))
+        self._p, self._stream_p = dict(p), None
+        if per_stream:  # the rings exist when any stream adapts; Ad_blk0 then holds an entry for every stream
+            self._stream_p = _stream_settings(p, settings, S)
+            adapt = int(any(bool(m.get("adapt_train_N", 0)) for m in self._stream_p))
+            Bx = _per_stream(Bx_list if Bx_list is not None else B_DFT_x, S, (F, R_x), "B_DFT_x", "F", dt)
         R_a, m_a = int(p.get("R_a", 1)), int(p.get("m_a", 1))
         seed = int(p.get("random_seed", 1))
         if H0 is None or (adapt and Ad_blk0 is None):
@@ -410,9 +481,15 @@ class OnlineBatchSeparator:
         self.class_outputs = bool(class_outputs)
         self.hop, self.delay = q.frameshift, q.delay
         h = C.c_void_p()
-        create = self._lib.snmf_online_batch_create_f64 if precision == "fp64" else self._lib.snmf_online_batch_create
-        _lib.check(create(self.ctx._h, C.byref(q), S, Bx.ctypes.data, Bd.ctypes.data, H.ctypes.data,
-                          Ad.ctypes.data if Ad is not None else None, ws.ctypes.data, wi.ctypes.data, C.byref(h)))
+        if per_stream:
+            sts = (SnmfOnlineStreamSettings * S)(*[_settings_struct(m, q) for m in self._stream_p])
+            _lib.check(self._lib.snmf_online_batch_create_streams_f64(
+                self.ctx._h, C.byref(q), S, Bx.ctypes.data, Bd.ctypes.data, H.ctypes.data, Ad.ctypes.data if Ad is not None else None,
+                C.cast(sts, C.c_void_p), ws.ctypes.data, wi.ctypes.data, C.byref(h)))
+        else:
+            create = self._lib.snmf_online_batch_create_f64 if precision == "fp64" else self._lib.snmf_online_batch_create
+            _lib.check(create(self.ctx._h, C.byref(q), S, Bx.ctypes.data, Bd.ctypes.data, H.ctypes.data,
+                              Ad.ctypes.data if Ad is not None else None, ws.ctypes.data, wi.ctypes.data, C.byref(h)))
         self._h = h
         self.ctx._plans.add(self)  # destroyed before the context
         if self.mel:
@@ -470,13 +547,16 @@ class OnlineBatchSeparator:
             outs.append(o)
         return outs
 
-    def restart(self, streams, B_DFT_d=None, H0=None, Ad_blk0=None, B_Mel_d=None):
+    def restart(self, streams, B_DFT_d=None, H0=None, Ad_blk0=None, B_Mel_d=None, B_DFT_x=None, settings=None):
         """Streams `streams` (an index or a list of distinct indices) start a new recording: src/NTF_sep_event_RT.m:27-38
         + init_buff, every piece of their state as a new separator gives it, the other streams untouched.  Each of
         `B_DFT_d` (F x R_d, fp64), `B_Mel_d` (Mel mode: F_order x R_d, fp64), `H0` and `Ad_blk0` is None, one array for all
         listed streams or one per stream.  None keeps the stream's current, adapted dictionary at full fp64 precision
         (load('B_D_u.mat'), :27-38 load both) and the H0 / Ad_blk0 it last started with.  A stream that has consumed
-        samples and was not flushed raises SnmfError(7), and so does a B_Mel_d outside Mel mode."""
+        samples and was not flushed raises SnmfError(7), and so does a B_Mel_d outside Mel mode.
+        fp64 batch: `B_DFT_x` (F x R_x, one array or one per listed stream) and `settings` (one dict of overrides on `p` or
+        one per listed stream) also replace the streams' event dictionaries and settings (snmf_online_batch_restart_streams_f64);
+        None keeps each stream's own.  A stream that adapts from now on needs an `Ad_blk0`, here or from an earlier call."""
         ks = [int(streams)] if np.isscalar(streams) else [int(k) for k in streams]
         n = len(ks)
         bad = [k for k in ks if not 0 <= k < self.S]
@@ -484,6 +564,13 @@ class OnlineBatchSeparator:
             raise _invalid(f"stream {bad[0]} out of range [0, {self.S})")
         if len(set(ks)) != n:
             raise _invalid("a stream is listed twice")
+        per_stream = B_DFT_x is not None or settings is not None
+        if per_stream and (self.precision != "fp64" or self.mel):
+            raise SnmfError(8, "batched separator: settings and B_DFT_x per stream need precision='fp64'")
+        new_p = _stream_settings(self._p, settings, n, "listed stream") if settings is not None else None
+        Bxn = None if B_DFT_x is None else _per_stream(B_DFT_x, n, (self.F, self.R_x), "B_DFT_x", "F", np.float64)
+        if new_p is not None and any(bool(m.get("adapt_train_N", 0)) for m in new_p):
+            self.adapt = 1
         Bd = None if B_DFT_d is None else _per_stream(B_DFT_d, n, (self.F, self.R_d), "B_DFT_d", "F", np.float64)
         H = None if H0 is None else _per_stream(H0, n, (self.R_x + self.R_d,), "H0", "F", self._dt)
         Ad = None if (Ad_blk0 is None or not self.adapt) else _per_stream(Ad_blk0, n, (self.R_a, self.m_a), "Ad_blk0", "F", self._dt)
@@ -494,7 +581,16 @@ class OnlineBatchSeparator:
             return
         sl = np.array(ks, dtype=np.int32)
         ptr = lambda a: a.ctypes.data if a is not None else None  # noqa: E731
-        if self.mel:
+        if per_stream:
+            sts = None if new_p is None else (SnmfOnlineStreamSettings * n)(*[_settings_struct(m, self._q) for m in new_p])
+            _lib.check(self._lib.snmf_online_batch_restart_streams_f64(self._h, n, sl.ctypes.data, ptr(Bxn), ptr(Bd), ptr(H), ptr(Ad),
+                                                                       C.cast(sts, C.c_void_p) if sts is not None else None))
+            if new_p is not None:
+                if self._stream_p is None:
+                    self._stream_p = [dict(self._p) for _ in range(self.S)]
+                for k, m in zip(ks, new_p):
+                    self._stream_p[k] = m
+        elif self.mel:
             _lib.check(self._lib.snmf_online_batch_restart_mel(self._h, n, sl.ctypes.data, ptr(Bd), ptr(Bm), ptr(H), ptr(Ad)))
         elif self.precision == "fp64":  # H0 / Ad_blk0 cross in fp64 too
             _lib.check(self._lib.snmf_online_batch_restart_f64(self._h, n, sl.ctypes.data, ptr(Bd), ptr(H), ptr(Ad)))
@@ -531,6 +627,13 @@ class OnlineBatchSeparator:
         _lib.check(self._lib.snmf_online_batch_get_mel_basis_f64(self._h, int(k), B.ctypes.data, self.n1))
         return B
 
+    def settings(self, k):
+        """Stream k's settings as the batch holds them (snmf_online_batch_get_settings; fp64 batch): a dict of the fields
+        of snmf_online_stream_settings."""
+        st = SnmfOnlineStreamSettings()
+        _lib.check(self._lib.snmf_online_batch_get_settings(self._h, int(k), C.byref(st)))
+        return {f: getattr(st, f) for f in _STREAM_FIELDS}
+
     def trace(self, k):
         """Per-frame diagnostics of stream k, as OnlineSeparator.trace."""
         n = C.c_int64()
@@ -553,12 +656,13 @@ class OnlineBatchSeparator:
 
 
 def ntf_sep_event_rt_batch(pcms, B_DFT_x, B_DFT_d, p, H0=None, Ad_blk0=None, ctx=None, B_Mel_x=None, B_Mel_d=None,
-                           precision="fp32"):
+                           precision="fp32", settings=None):
     """src/NTF_sep_event_RT.m for several recordings at once (the per-target loop of Do_MultiBatch_IS16_20160324.m:183-205
     as one batch): returns a list of the (int16, float, final B_DFT_d) triples ntf_sep_event_rt returns (Mel mode: the
-    final B_Mel_d).  precision="fp64": the fp64 mode of OnlineBatchSeparator."""
+    final B_Mel_d).  precision="fp64": the fp64 mode of OnlineBatchSeparator, which also takes `settings` (one dict of
+    overrides on `p` per recording) and `B_DFT_x` as a list (one event dictionary per recording)."""
     sep = OnlineBatchSeparator(B_DFT_x, B_DFT_d, p, len(pcms), H0=H0, Ad_blk0=Ad_blk0, ctx=ctx, B_Mel_x=B_Mel_x, B_Mel_d=B_Mel_d,
-                               precision=precision)
+                               precision=precision, settings=settings)
     try:
         outs = sep.process(list(pcms), flush=True)
         fin = sep.mel_basis if sep.mel else sep.basis
@@ -593,7 +697,7 @@ def _per_chain(x, n, shape, name, dtype):
 
 
 def ntf_sep_event_rt_chains(chains, B_DFT_x, B_DFT_d, p, n_streams=None, H0=None, Ad_blk0=None, ctx=None, chunk_hops=None,
-                            B_Mel_x=None, B_Mel_d=None, precision="fp32"):
+                            B_Mel_x=None, B_Mel_d=None, precision="fp32", settings=None):
     """Do_MultiBatch_IS16_20160324.m:183-205 + run_ntf_sep_RT.m:10-41 on one batch: `chains` is a list of chains, each a
     list of PCM arrays enhanced in turn by src/NTF_sep_event_RT.m.  Chain c starts from B_DFT_d (one array or one per
     chain; the delete('B_D_u.mat') of :187), and every later file starts from the dictionary its predecessor adapted,
@@ -608,9 +712,15 @@ def ntf_sep_event_rt_chains(chains, B_DFT_x, B_DFT_d, p, n_streams=None, H0=None
     in fp32, as in ntf_sep_event_rt_batch.  In Mel mode (B_Mel_x, and B_Mel_d as one array or one per chain) a chain
     carries both dictionaries (:137-139) and its triples hold the final B_Mel_d.
     precision="fp64": the fp64 mode of OnlineBatchSeparator; start dictionaries, H0 and Ad_blk0 then enter as float64 (not
-    rounded to fp32 first), the float signals and final dictionaries are the fp64 ones, and the slot-independence above holds."""
+    rounded to fp32 first), the float signals and final dictionaries are the fp64 ones, and the slot-independence above holds.
+    In that mode `B_DFT_x` may be a list with one event dictionary per chain and `settings` a list with one dict of overrides
+    on `p` per chain: a slot takes its chain's pair and settings when the chain starts on it, and the independence holds."""
     if precision not in ("fp32", "fp64"):
         raise ValueError("precision must be 'fp32' or 'fp64'")
+    Bx_list = list(B_DFT_x) if isinstance(B_DFT_x, (list, tuple)) else None
+    per_chain = settings is not None or Bx_list is not None
+    if per_chain and precision != "fp64":
+        raise SnmfError(8, "batched separator: settings and B_DFT_x per chain need precision='fp64'")
     chains = [[np.asarray(x).reshape(-1) for x in c] for c in chains]
     nc = len(chains)
     if nc == 0:
@@ -619,7 +729,9 @@ def ntf_sep_event_rt_chains(chains, B_DFT_x, B_DFT_d, p, n_streams=None, H0=None
     if S < 1:
         raise _invalid("n_streams must be >= 1")
     F = p["fftlength"] // 2 + 1
-    Bx = np.asarray(B_DFT_x)
+    if Bx_list is not None and len(Bx_list) != nc:
+        raise _invalid(f"B_DFT_x: {len(Bx_list)} entries for {nc} chains")
+    Bx = np.asarray(Bx_list[0] if Bx_list is not None else B_DFT_x)
     if Bx.ndim != 2 or Bx.shape[0] != F:
         raise _invalid(f"B_DFT_x must have fftlength/2+1 = {F} rows")
     Bd_first = np.asarray(B_DFT_d[0] if isinstance(B_DFT_d, (list, tuple)) and len(B_DFT_d) else B_DFT_d)
@@ -628,6 +740,11 @@ def ntf_sep_event_rt_chains(chains, B_DFT_x, B_DFT_d, p, n_streams=None, H0=None
     R_x, R_d = Bx.shape[1], Bd_first.shape[1]
     r = R_x + R_d
     adapt = int(bool(p.get("adapt_train_N", 0)))
+    sets = Bxs = None
+    if per_chain:  # checked here, before the library is loaded; the draws follow "any chain adapts"
+        sets = [{k: m[k] for k in m if k in _STREAM_KEYS} for m in _stream_settings(p, settings, nc, "chain")]
+        adapt = int(any(bool(m.get("adapt_train_N", p.get("adapt_train_N", 0))) for m in sets))
+        Bxs = _per_chain(Bx_list if Bx_list is not None else B_DFT_x, nc, (F, R_x), "B_DFT_x", np.float64)
     R_a, m_a = int(p.get("R_a", 1)), int(p.get("m_a", 1))
     # (fp32 mode: fp32 values, restarted with in fp64; fp64 mode: the doubles as they are)
     Bds = _per_chain(B_DFT_d, nc, (F, R_d), "B_DFT_d", np.float64 if precision == "fp64" else np.float32)
@@ -662,9 +779,10 @@ def ntf_sep_event_rt_chains(chains, B_DFT_x, B_DFT_d, p, n_streams=None, H0=None
     first = [queue.pop() for _ in range(min(S, len(queue)))]
     init = [first[k] if k < len(first) else first[0] for k in range(S)]
     dr = {c: draws(c) for c in set(init)}
-    sep = OnlineBatchSeparator(Bx, [Bds[c] for c in init], p, S, H0=[dr[c][0] for c in init],
+    sep = OnlineBatchSeparator([Bxs[c] for c in init] if per_chain else Bx, [Bds[c] for c in init], p, S, H0=[dr[c][0] for c in init],
                                Ad_blk0=[dr[c][1] for c in init] if adapt else None, ctx=ctx, B_Mel_x=B_Mel_x,
-                               B_Mel_d=[Bms[c] for c in init] if mel else None, precision=precision)
+                               B_Mel_d=[Bms[c] for c in init] if mel else None, precision=precision,
+                               settings=[sets[c] for c in init] if per_chain else None)
     fin = sep.mel_basis if mel else sep.basis
     hop = sep.hop
     step = int(chunk_hops) if chunk_hops else max(1, min(4096, _B_CHUNK_SLOTS // S))
@@ -681,7 +799,8 @@ def ntf_sep_event_rt_chains(chains, B_DFT_x, B_DFT_d, p, n_streams=None, H0=None
                 cs = [busy[k][0] for k in fresh]
                 ds = [draws(c) for c in cs]
                 sep.restart(fresh, [Bds[c] for c in cs], [d[0] for d in ds], [d[1] for d in ds] if adapt else None,
-                            B_Mel_d=[Bms[c] for c in cs] if mel else None)
+                            B_Mel_d=[Bms[c] for c in cs] if mel else None, B_DFT_x=[Bxs[c] for c in cs] if per_chain else None,
+                            settings=[sets[c] for c in cs] if per_chain else None)
             carry, fresh = [], []
             pcms, flush = [np.zeros(0, sep._dt)] * S, [False] * S
             for k, st in busy.items():
