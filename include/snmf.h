@@ -664,6 +664,76 @@ int snmf_online_batch_restart_streams_f64(snmf_online_batch* b, int32_t n, const
 /* Stream k's settings as they were last given (p's for a batch made by snmf_online_batch_create_f64).  SNMF_ERR_STATE on an
  * fp32 batch. */
 int snmf_online_batch_get_settings(snmf_online_batch* b, int32_t k, snmf_online_stream_settings* out);
+/* Added within 5.  A stream's state g as a value the caller holds: the fourth result of
+ * [x_hat_i, d_hat_i, x_tilde, g] = bnmf_sep_event_RT_IS16(y, l, g, p) (src/init_buff.m:17-47,
+ * src/bnmf_sep_event_RT_IS16.m:385-420) together with the driver's variables around it (the frame buffer, the samples not
+ * yet framed, the overlap-add tails).  One stream's state is one RECORD of info.bytes bytes: a header (magic, layout
+ * version, the snmf_online_state_info it was taken under, so that a record on disk describes itself) and the fields of
+ * snmf_online_state_field_id behind it, each at the offset snmf_online_state_field reports.  Float fields have the batch's
+ * element type (float on an fp32 batch, double on an fp64 batch); the dictionary masters are double on both.  Matrices
+ * are column-major and tight.  Rings stand in the reference's order, oldest column first, as lambda_d_blk and Ad_blk stand
+ * after the shift-and-append of :282, :285 and r_blk as src/blk_sparse.m returns it; the device keeps column c of a ring in
+ * slot (n_push + c) % m_a (r_blk: (l - 1 + c) % P_len_l), and a restored stream has its columns in the slots they had.
+ * Not state: B_DFT_x, the per-stream settings, the class partition and the windows (configuration: the target slot has
+ * them already, from create or restart); the trace; r_up and every derived dictionary image (rebuilt from the masters). */
+#define SNMF_ONLINE_STATE_MAGIC 0x47534E4Fu /* "ONSG" */
+#define SNMF_ONLINE_STATE_VERSION 1
+typedef struct snmf_online_state_info {
+    int32_t elem_size;     /* 4: fp32 batch, 8: fp64 batch */
+    int32_t mel, mel_conv; /* B_sep_mode 'Mel', MelConv */
+    int32_t F, F_order;    /* F_order: 0 outside Mel mode */
+    int32_t R_x, R_d, R_a, m_a, P_len_l; /* R_a, m_a, P_len_l: the rings as the batch holds them (1 where unused) */
+    int32_t framelength, frameshift, ntail;
+    int32_t class_outputs, n_classes;
+    int32_t reserved;
+    int64_t bytes;         /* of one record */
+} snmf_online_state_info;
+typedef enum snmf_online_state_field_id {
+    SNMF_STATE_XM_TILDE = 0,  /* F                       g.Xm_tilde */
+    SNMF_STATE_LAMBDA_DAV,    /* F                       g.lambda_dav */
+    SNMF_STATE_R_BLK,         /* F x P_len_l             g.r_blk */
+    SNMF_STATE_LAMBDA_D_BLK,  /* F x m_a                 g.lambda_d_blk, time order */
+    SNMF_STATE_AD_BLK,        /* R_a x m_a               g.Ad_blk, time order */
+    SNMF_STATE_N_PUSH,        /* int32                   pushes into the two rings so far */
+    SNMF_STATE_UPDATE_SWITCH, /* int32                   g.update_switch */
+    SNMF_STATE_B_DFT_D,       /* F x R_d double          the fp64 master */
+    SNMF_STATE_B_FIX,         /* F x R_d double          the fixed columns of :328 */
+    SNMF_STATE_B_MEL_D,       /* F_order x R_d double    Mel mode: the adapted master (count 0 otherwise) */
+    SNMF_STATE_H0,            /* R_x + R_d               the stream's draw */
+    SNMF_STATE_AD_BLK0,       /* R_a x m_a               the stream's draw (a later carry-restart reuses it) */
+    SNMF_STATE_L,             /* int64                   1-based index of the next frame */
+    SNMF_STATE_Y_HIST,        /* framelength - frameshift   the driver's frame buffer behind the last hop */
+    SNMF_STATE_PENDING,       /* frameshift (capacity)   samples fed but not yet framed; the first PENDING_COUNT hold */
+    SNMF_STATE_PENDING_COUNT, /* int32                   < frameshift */
+    SNMF_STATE_X_TILDE_TAIL,  /* ntail                   the overlap-add tail: the last nov - 1 synthesised frames (framelength
+                                                          each, oldest first; nov = ceil(framelength / frameshift)), which the
+                                                          overlap-add of src/NTF_sep_event_RT.m:121-124 sums */
+    SNMF_STATE_X_HAT_TAIL,    /* ntail                   with class_outputs (count 0 otherwise) */
+    SNMF_STATE_D_HAT_TAIL,    /* ntail                   with class_outputs */
+    SNMF_STATE_CLASS_TAILS,   /* ntail x n_classes       with a partition set */
+    SNMF_STATE_FIELD_COUNT
+} snmf_online_state_field_id;
+typedef enum snmf_online_state_type { SNMF_STATE_F32 = 0, SNMF_STATE_F64 = 1, SNMF_STATE_I32 = 2, SNMF_STATE_I64 = 3 } snmf_online_state_type;
+/* The geometry and record size of the batch's streams, as they are now (snmf_online_batch_set_mel / _set_classes and, on an
+ * fp64 batch, a restart that makes the rings grow change them). */
+int snmf_online_batch_state_info(snmf_online_batch* b, snmf_online_state_info* out);
+/* Where `field` (an snmf_online_state_field_id) lies in a record taken under `info`: byte offset, element count and element type.  A pure host function:
+ * it reads nothing but `info` (its `bytes` included: it is recomputed, and returned through info only by
+ * snmf_online_batch_state_info).  Any of offset / count / type may be NULL.  An unknown field or a nonsensical info:
+ * SNMF_ERR_INVALID. */
+int snmf_online_state_field(const snmf_online_state_info* info, int32_t field, int64_t* offset, int64_t* count, int32_t* type);
+/* The records of the streams slots[0..n) (distinct), consecutive, info.bytes each, into `records` (cap bytes).  Allowed
+ * between process calls on a stream that was not flushed; a flushed stream returns SNMF_ERR_STATE (what survives it is the
+ * dictionary, snmf_online_batch_get_basis_f64).  The streams are not disturbed.  One gather launch and one copy, whatever n. */
+int snmf_online_batch_get_state(snmf_online_batch* b, int32_t n, const int32_t* slots, void* records, int64_t cap);
+/* Streams slots[0..n) (distinct) take the n consecutive records in `records` (bytes in all).  Allowed on any slot, fresh,
+ * running or finished; the slot is then a running stream at frame l with an empty trace (the batch counts as started:
+ * snmf_online_batch_set_mel / _set_classes come before, as before the first process call).  The headers are checked against
+ * the handle before the device is touched: bad magic or version, or too few bytes: SNMF_ERR_INVALID; another element size,
+ * mode, geometry or class count: SNMF_ERR_DIM (the message names the field); n_push < 0, update_switch < 1, l < 1 or a
+ * pending count >= frameshift: SNMF_ERR_INVALID.  A refused call changes nothing.  One upload, one scatter launch and the
+ * dictionary refresh of a restart, whatever n; the stream's next frames have the bits of the stream the record came from. */
+int snmf_online_batch_set_state(snmf_online_batch* b, int32_t n, const int32_t* slots, const void* records, int64_t bytes);
 /* Diagnostics of stream k's most recent frames (the newest 65536 per stream), as snmf_online_trace. */
 int snmf_online_batch_trace(snmf_online_batch* b, int32_t k, snmf_online_frame* out, int64_t cap, int64_t* n);
 void snmf_online_batch_destroy(snmf_online_batch* b);

@@ -79,6 +79,7 @@ SYMBOLS = [
     "snmf_online_batch_create_f64", "snmf_online_batch_process_f64", "snmf_online_batch_process_classes_f64",
     "snmf_online_batch_restart_f64",
     "snmf_online_batch_create_streams_f64", "snmf_online_batch_restart_streams_f64", "snmf_online_batch_get_settings",
+    "snmf_online_batch_state_info", "snmf_online_state_field", "snmf_online_batch_get_state", "snmf_online_batch_set_state",
     "snmf_multi_create", "snmf_multi_destroy", "snmf_multi_set_v_f64", "snmf_multi_set_v_f32", "snmf_multi_set_w_f64",
     "snmf_multi_set_w_f32", "snmf_multi_set_h_f64", "snmf_multi_set_h_f32", "snmf_multi_set_sparsity_f64",
     "snmf_multi_set_sparsity_f32", "snmf_multi_init", "snmf_multi_run", "snmf_multi_get_w_f64", "snmf_multi_get_w_f32",
@@ -173,6 +174,23 @@ class SnmfOnlineStreamSettings(C.Structure):
         ("adapt_train_N", C.c_int32),
         ("overlap_m_a", C.c_double), ("Ar_up", C.c_double),
     ]
+
+
+class SnmfOnlineStateInfo(C.Structure):
+    """snmf_online_state_info: what a stream-state record of the batched online separator was taken under."""
+    _fields_ = [
+        ("elem_size", C.c_int32), ("mel", C.c_int32), ("mel_conv", C.c_int32), ("F", C.c_int32), ("F_order", C.c_int32),
+        ("R_x", C.c_int32), ("R_d", C.c_int32), ("R_a", C.c_int32), ("m_a", C.c_int32), ("P_len_l", C.c_int32),
+        ("framelength", C.c_int32), ("frameshift", C.c_int32), ("ntail", C.c_int32),
+        ("class_outputs", C.c_int32), ("n_classes", C.c_int32), ("reserved", C.c_int32), ("bytes", C.c_int64),
+    ]
+
+
+# snmf_online_state_field_id, in the header's order, and snmf_online_state_type
+STATE_FIELDS = ("Xm_tilde", "lambda_dav", "r_blk", "lambda_d_blk", "Ad_blk", "n_push", "update_switch", "B_DFT_d", "B_fix", "B_Mel_d",
+                "H0", "Ad_blk0", "l", "y_hist", "pending", "pending_count", "x_tilde_tail", "x_hat_tail", "d_hat_tail", "class_tails")
+STATE_TYPES = ("<f4", "<f8", "<i4", "<i8")
+STATE_MAGIC, STATE_VERSION, STATE_HEADER_BYTES = 0x47534E4F, 1, 80
 
 
 class SnmfOnlineFrame(C.Structure):
@@ -338,6 +356,10 @@ def load():
     sig["snmf_online_batch_create_streams_f64"] = (C.c_int, [vp, OP, i32, vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp)])
     sig["snmf_online_batch_restart_streams_f64"] = (C.c_int, [vp, i32, vp, vp, vp, vp, vp, vp])
     sig["snmf_online_batch_get_settings"] = (C.c_int, [vp, i32, C.POINTER(SnmfOnlineStreamSettings)])
+    sig["snmf_online_batch_state_info"] = (C.c_int, [vp, C.POINTER(SnmfOnlineStateInfo)])
+    sig["snmf_online_state_field"] = (C.c_int, [C.POINTER(SnmfOnlineStateInfo), i32, C.POINTER(i64), C.POINTER(i64), C.POINTER(i32)])
+    sig["snmf_online_batch_get_state"] = (C.c_int, [vp, i32, vp, vp, i64])
+    sig["snmf_online_batch_set_state"] = (C.c_int, [vp, i32, vp, vp, i64])
     for ty in ("f64", "f32"):
         sig[f"snmf_plan_solve_frames_{ty}"] = (C.c_int, [vp, i32, vp, i64, i32, vp, vp, vp, vp])
     for nm in ("v", "w", "h", "mask"):

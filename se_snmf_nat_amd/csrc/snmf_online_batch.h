@@ -656,6 +656,11 @@ __global__ __launch_bounds__(256) void k_obrefresh(ORefreshArgs a) {
     }
 }
 
+// The listed streams' state g into (k_obstate_get) / out of (k_obstate_put) a slab of records (ostate_xfer,
+// snmf_online_batch_common.h); grid (listed stream, kStN, kStParts).  k_obrefresh (slot list form) follows a put.
+__global__ __launch_bounds__(256) void k_obstate_get(OStateArgs<float> a) { ostate_xfer<float, false>(a); }
+__global__ __launch_bounds__(256) void k_obstate_put(OStateArgs<float> a) { ostate_xfer<float, true>(a); }
+
 // inverse STFT of every (frame, stream): stream s's frames go behind the nov-1 frames kept from its previous chunk
 template <int LOGN>
 __global__ __launch_bounds__(256) void k_obistft(OIstftArgs a, const int* nfr, int S, int64_t syn_stride, int nov) {

@@ -570,6 +570,11 @@ __global__ __launch_bounds__(256) void k_obrestart64(ORestart64Args a) {
     }
 }
 
+// The listed streams' state g into (k_obstate_get64) / out of (k_obstate_put64) a slab of records (ostate_xfer,
+// snmf_online_batch_common.h); grid (listed stream, kStN, kStParts).  k_obrefresh64 (slot list form) follows a put.
+__global__ __launch_bounds__(256) void k_obstate_get64(OStateArgs<double> a) { ostate_xfer<double, false>(a); }
+__global__ __launch_bounds__(256) void k_obstate_put64(OStateArgs<double> a) { ostate_xfer<double, true>(a); }
+
 // inverse STFT of every (frame, stream): stream s's frames go behind the nov-1 frames kept from its previous chunk;
 // dynamic LDS = 2 N double2
 template <int LOGN>

@@ -24,3 +24,7 @@ int online_batch_f64_get_settings(OnlineBatchF64* o, int32_t k, snmf_online_stre
 void online_batch_f64_dims(OnlineBatchF64* o, int* r, int* ra_ma);  // lengths of one stream's H0 and Ad_blk0
 int online_batch_f64_get_basis(OnlineBatchF64* o, int32_t k, double* Bd, int64_t ld);
 int online_batch_f64_trace(OnlineBatchF64* o, int32_t k, snmf_online_frame* out, int64_t cap, int64_t* n);
+// get-state / set-state (snmf_online_batch_state_info / _get_state / _set_state) of the fp64 batch
+void online_batch_f64_state_info(OnlineBatchF64* o, snmf_online_state_info* out);
+int online_batch_f64_get_state(OnlineBatchF64* o, int32_t n, const int32_t* slots, void* records, int64_t cap);
+int online_batch_f64_set_state(OnlineBatchF64* o, int32_t n, const int32_t* slots, const void* records, int64_t bytes);

@@ -77,7 +77,7 @@ extern "C" void snmf_online_batch_destroy(snmf_online_batch* o) {
     void* ptrs[] = {o->B, o->Bfix, o->Btmp, o->wn, o->Wu, o->Wcf, o->wx, o->dphv, o->Hin, o->H0, o->Ad0, o->lambda_dav, o->Xm_tilde,
                     o->r_blk, o->ldblk, o->adblk, o->G, o->P, o->Vt, o->tail, o->tail_x, o->tail_d, o->rup, o->dev, o->win_s,
                     o->win_i, o->tw, o->Bxd, o->rs_slots, o->rs_B, o->rs_H, o->rs_A, o->meta_i, o->meta_l, o->melmat, o->Vm, o->Bdf,
-                    o->Bmx, o->Bm, o->rs_Bm, o->cls, o->tail_c};
+                    o->Bmx, o->Bm, o->rs_Bm, o->cls, o->tail_c, o->st_slab};
     for (void* q : ptrs)
         if (q) hipFree(q);
     delete o;
@@ -112,6 +112,19 @@ static int ob_validate(const snmf_online_params* p, int32_t S) {
     return SNMF_OK;
 }
 
+// Every column's dictionary images (set_w + the init mode of k_wapply) of the streams in rs_slots, from the solve's dictionary
+// (Mel: the Mel master): the launch that ends a restart and follows a set-state (the driver's obm_state_refresh).
+static int obm_state_refresh(snmf_online_batch* o, int n) {
+    const snmf_online_params& p = o->p;
+    ORefreshArgs ra{};
+    ra.slots = o->rs_slots; ra.S = o->S; ra.B = o->mel ? o->Bm : o->B; ra.Wcf = o->Wcf; ra.wx = o->wx; ra.dphv = o->dphv; ra.wn = o->wn;
+    ra.Hin = o->Hin; ra.H0 = o->H0; ra.lamk = o->hp->lamk; ra.F = o->Fs; ra.r = o->r; ra.Rx = p.R_x; ra.rp = o->hp->rp; ra.Fp = o->hp->Fp;
+    ra.xr = o->Fs > 64 * o->hp->frame_fb; ra.k0 = 0;
+    hipLaunchKernelGGL(k_obrefresh, dim3(o->r, n), dim3(256), 0, o->ctx->stream, ra);
+    HIP_TRY(hipGetLastError());
+    return SNMF_OK;
+}
+
 // The streams slots[0..n) start a new recording (src/NTF_sep_event_RT.m:27-38 + src/init_buff.m): the uploads, one
 // k_obrestart, one k_obrefresh over their columns, and their host state.  Arguments are checked by the caller; Bd is
 // n x Rd x F fp64 or NULL (carry), Bmd (Mel mode) n x Rd x n1 fp64 or NULL (carry), H0 n x r or NULL, Ad n x Ra x ma or
@@ -139,13 +152,7 @@ static int ob_restart(snmf_online_batch* o, int n, const int32_t* slots, const d
     HIP_TRY(hipGetLastError());
     for (int i = 0; i < n && o->tail_c; ++i)  // the class tails of the stream, like tail_x / tail_d: one strided fill over its classes
         HIP_TRY(hipMemset2DAsync(o->tail_c + (size_t)slots[i] * o->ntail, (size_t)o->S * o->ntail * 4, 0, o->ntail * 4, (size_t)o->n_cls, st));
-    // every column's dictionary images (set_w + the init mode of k_wapply) from the solve's dictionary (Mel: the Mel master)
-    ORefreshArgs ra{};
-    ra.slots = o->rs_slots; ra.S = o->S; ra.B = o->mel ? o->Bm : o->B; ra.Wcf = o->Wcf; ra.wx = o->wx; ra.dphv = o->dphv; ra.wn = o->wn;
-    ra.Hin = o->Hin; ra.H0 = o->H0; ra.lamk = o->hp->lamk; ra.F = o->Fs; ra.r = o->r; ra.Rx = p.R_x; ra.rp = o->hp->rp; ra.Fp = o->hp->Fp;
-    ra.xr = o->Fs > 64 * o->hp->frame_fb; ra.k0 = 0;
-    hipLaunchKernelGGL(k_obrefresh, dim3(o->r, n), dim3(256), 0, st, ra);
-    HIP_TRY(hipGetLastError());
+    SN_TRY(obm_state_refresh(o, n));
     obatch_restart_host(o, n, slots);
     return SNMF_OK;
 }
@@ -654,6 +661,59 @@ extern "C" int snmf_online_batch_trace(snmf_online_batch* o, int32_t k, snmf_onl
     if (!o) return fail(SNMF_ERR_INVALID, "online batch handle is NULL");
     if (o->f64) return online_batch_f64_trace(o->f64, k, out, cap, n);
     return obatch_trace(o, k, out, cap, n);
+}
+
+// ---- get-state / set-state (the driver's section in snmf_online_batch_host.h; kernels k_obstate_get / k_obstate_put) ----
+static void obm_state_mode(const snmf_online_batch* o, int* mel, int* mel_conv, int* n1) {
+    *mel = o->mel;
+    *mel_conv = o->mel_conv;
+    *n1 = o->n1;
+}
+
+static void obm_state_arrays(snmf_online_batch* o, OStateArgs<float>& a) {
+    a.Bm = o->mel ? o->Bm : nullptr;
+    a.Bdf = o->Bdf;  // (allocated only in Mel mode with MelConv = 0)
+    a.n1 = o->n1;
+}
+
+static int obm_state_launch(snmf_online_batch* o, const OStateArgs<float>& a, int n, bool put) {
+    if (put) hipLaunchKernelGGL(k_obstate_put, dim3(n, kStN, kStParts), dim3(256), 0, o->ctx->stream, a);
+    else hipLaunchKernelGGL(k_obstate_get, dim3(n, kStN, kStParts), dim3(256), 0, o->ctx->stream, a);
+    HIP_TRY(hipGetLastError());
+    return SNMF_OK;
+}
+
+static void obm_state_installed(snmf_online_batch*, int, const int32_t*) {}
+
+extern "C" int snmf_online_state_field(const snmf_online_state_info* info, int32_t field, int64_t* offset, int64_t* count, int32_t* type) {
+    if (!info) return fail(SNMF_ERR_INVALID, "info is NULL");
+    if (field < 0 || field >= SNMF_STATE_FIELD_COUNT) return fail(SNMF_ERR_INVALID, "no state field %d", field);
+    int64_t off[SNMF_STATE_FIELD_COUNT], cnt[SNMF_STATE_FIELD_COUNT];
+    int32_t typ[SNMF_STATE_FIELD_COUNT];
+    if (ostate_layout(*info, off, cnt, typ) < 0) return fail(SNMF_ERR_INVALID, "not the state info of a batch");
+    if (offset) *offset = off[field];
+    if (count) *count = cnt[field];
+    if (type) *type = typ[field];
+    return SNMF_OK;
+}
+
+extern "C" int snmf_online_batch_state_info(snmf_online_batch* o, snmf_online_state_info* out) {
+    if (!o || !out) return fail(SNMF_ERR_INVALID, "NULL argument");
+    if (o->f64) online_batch_f64_state_info(o->f64, out);
+    else obatch_state_info(o, out);
+    return SNMF_OK;
+}
+
+extern "C" int snmf_online_batch_get_state(snmf_online_batch* o, int32_t n, const int32_t* slots, void* records, int64_t cap) {
+    if (!o) return fail(SNMF_ERR_INVALID, "online batch handle is NULL");
+    if (o->f64) return online_batch_f64_get_state(o->f64, n, slots, records, cap);
+    return obatch_get_state(o, n, slots, records, cap);
+}
+
+extern "C" int snmf_online_batch_set_state(snmf_online_batch* o, int32_t n, const int32_t* slots, const void* records, int64_t bytes) {
+    if (!o) return fail(SNMF_ERR_INVALID, "online batch handle is NULL");
+    if (o->f64) return online_batch_f64_set_state(o->f64, n, slots, records, bytes);
+    return obatch_set_state(o, n, slots, records, bytes);
 }
 
 // ---- fp64 mode (snmf_online_batch_f64.h): every input crosses in fp64 and every step from PCM to the fed-back state is fp64 ----

@@ -167,10 +167,21 @@ void online_batch_f64_destroy(OnlineBatchF64* o) {
     obatch_free_chunk(o);
     void* ptrs[] = {o->B, o->Bfix, o->Btmp, o->Wn, o->WnT, o->wn, o->csum, o->H0, o->Ad0, o->lambda_dav, o->Xm_tilde, o->r_blk, o->ldblk,
                     o->adblk, o->Wu, o->Wm, o->Q, o->P, o->Vt, o->tail, o->tail_x, o->tail_d, o->rup, o->dev, o->win_s, o->win_i, o->Bxd,
-                    o->tw, o->rs_slots, o->rs_B, o->rs_H, o->rs_A, o->cls, o->tail_c, o->meta_i, o->meta_l, o->set};
+                    o->tw, o->rs_slots, o->rs_B, o->rs_H, o->rs_A, o->cls, o->tail_c, o->meta_i, o->meta_l, o->set, o->st_slab};
     for (void* q : ptrs)
         if (q) hipFree(q);
     delete o;
+}
+
+// Every column's dictionary images of the streams in rs_slots: the launch that ends a restart and follows a set-state (the
+// driver's obm_state_refresh).
+static int obm_state_refresh(OnlineBatchF64* o, int n) {
+    ORefresh64Args ra{};
+    ra.slots = o->rs_slots; ra.S = o->S; ra.B = o->B; ra.Wn = o->Wn; ra.WnT = o->WnT; ra.wn = o->wn; ra.csum = o->csum;
+    ra.F = o->F; ra.r = o->r; ra.Rx = o->p.R_x; ra.k0 = 0;
+    hipLaunchKernelGGL(k_obrefresh64, dim3(o->r, n), dim3(256), 0, o->ctx->stream, ra);
+    HIP_TRY(hipGetLastError());
+    return SNMF_OK;
 }
 
 // The streams slots[0..n) start a new recording (ob_restart of snmf_tu_online_batch.hip): the uploads, one k_obrestart64, one
@@ -203,11 +214,7 @@ static int b64_restart(OnlineBatchF64* o, int n, const int32_t* slots, const dou
     HIP_TRY(hipGetLastError());
     for (int i = 0; i < n && o->tail_c; ++i)  // the class tails of the stream, like tail_x / tail_d: one strided fill over its classes
         HIP_TRY(hipMemset2DAsync(o->tail_c + (size_t)slots[i] * o->ntail, (size_t)o->S * o->ntail * 8, 0, o->ntail * 8, (size_t)o->n_cls, st));
-    ORefresh64Args ra{};
-    ra.slots = o->rs_slots; ra.S = o->S; ra.B = o->B; ra.Wn = o->Wn; ra.WnT = o->WnT; ra.wn = o->wn; ra.csum = o->csum;
-    ra.F = o->F; ra.r = o->r; ra.Rx = p.R_x; ra.k0 = 0;
-    hipLaunchKernelGGL(k_obrefresh64, dim3(o->r, n), dim3(256), 0, st, ra);
-    HIP_TRY(hipGetLastError());
+    SN_TRY(obm_state_refresh(o, n));
     obatch_restart_host(o, n, slots);
     return SNMF_OK;
 }
@@ -482,3 +489,34 @@ int online_batch_f64_get_basis(OnlineBatchF64* o, int32_t k, double* Bd, int64_t
 }
 
 int online_batch_f64_trace(OnlineBatchF64* o, int32_t k, snmf_online_frame* out, int64_t cap, int64_t* n) { return obatch_trace(o, k, out, cap, n); }
+
+// ---- get-state / set-state (the driver's section in snmf_online_batch_host.h; kernels k_obstate_get64 / k_obstate_put64) ----
+static void obm_state_mode(const OnlineBatchF64*, int* mel, int* mel_conv, int* n1) { *mel = *mel_conv = *n1 = 0; }  // DFT mode only
+
+static void obm_state_arrays(OnlineBatchF64*, OStateArgs<double>& a) {
+    a.Bm = nullptr;
+    a.Bdf = nullptr;
+    a.n1 = 0;
+}
+
+static int obm_state_launch(OnlineBatchF64* o, const OStateArgs<double>& a, int n, bool put) {
+    if (put) hipLaunchKernelGGL(k_obstate_put64, dim3(n, kStN, kStParts), dim3(256), 0, o->ctx->stream, a);
+    else hipLaunchKernelGGL(k_obstate_get64, dim3(n, kStN, kStParts), dim3(256), 0, o->ctx->stream, a);
+    HIP_TRY(hipGetLastError());
+    return SNMF_OK;
+}
+
+// Ad0 now holds the record's Ad_blk0 (a ring that grows later forgets it, as b64_fit_rings does for every stream)
+static void obm_state_installed(OnlineBatchF64* o, int n, const int32_t* slots) {
+    for (int i = 0; i < n; ++i) o->has_ad0[slots[i]] = 1;
+}
+
+void online_batch_f64_state_info(OnlineBatchF64* o, snmf_online_state_info* out) { obatch_state_info(o, out); }
+
+int online_batch_f64_get_state(OnlineBatchF64* o, int32_t n, const int32_t* slots, void* records, int64_t cap) {
+    return obatch_get_state(o, n, slots, records, cap);
+}
+
+int online_batch_f64_set_state(OnlineBatchF64* o, int32_t n, const int32_t* slots, const void* records, int64_t bytes) {
+    return obatch_set_state(o, n, slots, records, bytes);
+}

@@ -445,6 +445,8 @@ class OnlineBatchSeparator:
             self._stream_p = _stream_settings(p, settings, S)
             adapt = int(any(bool(m.get("adapt_train_N", 0)) for m in self._stream_p))
             Bx = _per_stream(Bx_list if Bx_list is not None else B_DFT_x, S, (F, R_x), "B_DFT_x", "F", dt)
+        # the r_blk ring exists at P_len_l columns once any stream is block-sparse (the rings only grow)
+        self._blk_ring = any(bool(m.get("blk_sparse", 0)) for m in (self._stream_p or [p]))
         R_a, m_a = int(p.get("R_a", 1)), int(p.get("m_a", 1))
         seed = int(p.get("random_seed", 1))
         if H0 is None or (adapt and Ad_blk0 is None):
@@ -571,6 +573,8 @@ class OnlineBatchSeparator:
         Bxn = None if B_DFT_x is None else _per_stream(B_DFT_x, n, (self.F, self.R_x), "B_DFT_x", "F", np.float64)
         if new_p is not None and any(bool(m.get("adapt_train_N", 0)) for m in new_p):
             self.adapt = 1
+        if new_p is not None and any(bool(m.get("blk_sparse", 0)) for m in new_p):
+            self._blk_ring = True
         Bd = None if B_DFT_d is None else _per_stream(B_DFT_d, n, (self.F, self.R_d), "B_DFT_d", "F", np.float64)
         H = None if H0 is None else _per_stream(H0, n, (self.R_x + self.R_d,), "H0", "F", self._dt)
         Ad = None if (Ad_blk0 is None or not self.adapt) else _per_stream(Ad_blk0, n, (self.R_a, self.m_a), "Ad_blk0", "F", self._dt)
@@ -633,6 +637,172 @@ class OnlineBatchSeparator:
         st = SnmfOnlineStreamSettings()
         _lib.check(self._lib.snmf_online_batch_get_settings(self._h, int(k), C.byref(st)))
         return {f: getattr(st, f) for f in _STREAM_FIELDS}
+
+    # ---- a stream's state g as a value (snmf_online_batch_get_state / _set_state) ----
+    def _state_shapes(self):
+        """Field name -> (shape, dtype) of one stream's state as this batch holds it: the rows of include/snmf.h's
+        snmf_online_state_field_id that exist in its mode.  Computed from the constructor's arguments alone."""
+        q, dt = self._q, np.dtype(self._dt)
+        F, Rd, r = self.F, self.R_d, self.R_x + self.R_d
+        Ra, ma = (self.R_a, self.m_a) if self.adapt else (1, 1)
+        Pl = int(q.P_len_l) if self._blk_ring else 1
+        sz, hop = int(q.framelength), int(q.frameshift)
+        ntail = max(1, (sz + hop - 1) // hop - 1) * sz
+        f8, i4, i8 = np.dtype(np.float64), np.dtype(np.int32), np.dtype(np.int64)
+        sh = {"Xm_tilde": ((F,), dt), "lambda_dav": ((F,), dt), "r_blk": ((F, Pl), dt), "lambda_d_blk": ((F, ma), dt),
+              "Ad_blk": ((Ra, ma), dt), "n_push": ((), i4), "update_switch": ((), i4), "B_DFT_d": ((F, Rd), f8), "B_fix": ((F, Rd), f8)}
+        if self.mel:
+            sh["B_Mel_d"] = ((self.n1, Rd), f8)
+        sh.update({"H0": ((r,), dt), "Ad_blk0": ((Ra, ma), dt), "l": ((), i8), "y_hist": ((sz - hop,), dt), "pending": (None, dt),
+                   "x_tilde_tail": ((ntail,), dt)})
+        if self.class_outputs:
+            sh["x_hat_tail"], sh["d_hat_tail"] = ((ntail,), dt), ((ntail,), dt)
+        if self._classes is not None:
+            sh["class_tails"] = ((self._classes[0].size + self._classes[1].size, ntail), dt)
+        return sh
+
+    def _stream_list(self, streams):
+        ks = [int(streams)] if np.isscalar(streams) else [int(k) for k in streams]
+        bad = [k for k in ks if not 0 <= k < self.S]
+        if bad:
+            raise _invalid(f"stream {bad[0]} out of range [0, {self.S})")
+        if len(set(ks)) != len(ks):
+            raise _invalid("a stream is listed twice")
+        return ks
+
+    def _state_layout(self, lib):
+        """The batch's snmf_online_state_info and {field: (offset, count, numpy dtype)} of a record under it."""
+        info = _lib.SnmfOnlineStateInfo()
+        _lib.check(lib.snmf_online_batch_state_info(self._h, C.byref(info)))
+        lay = {}
+        for f, name in enumerate(_lib.STATE_FIELDS):
+            off, cnt, typ = C.c_int64(), C.c_int64(), C.c_int32()
+            _lib.check(lib.snmf_online_state_field(C.byref(info), f, C.byref(off), C.byref(cnt), C.byref(typ)))
+            lay[name] = (off.value, cnt.value, np.dtype(_lib.STATE_TYPES[typ.value]))
+        return info, lay
+
+    def get_state(self, streams):
+        """The state g of stream `streams` (an index: one dict; a list of distinct indices: a list of dicts), as the fourth
+        result of bnmf_sep_event_RT_IS16 with the driver's variables around it: the fields of snmf_online_state_field_id under
+        their names there ('Xm_tilde', 'lambda_dav', 'r_blk', 'lambda_d_blk', 'Ad_blk', 'n_push', 'update_switch', 'B_DFT_d',
+        'B_fix', 'B_Mel_d', 'H0', 'Ad_blk0', 'l', 'y_hist', 'pending', 'x_tilde_tail', 'x_hat_tail', 'd_hat_tail',
+        'class_tails'), matrices as F-ordered arrays with the rings in time order (oldest column first), plus 'record', the raw
+        bytes (self-describing; what set_state and a file take).  Allowed between process calls on a stream that was not
+        flushed (a flushed one raises SnmfError(7)); the stream is not disturbed."""
+        one = np.isscalar(streams)
+        ks = self._stream_list(streams)
+        shapes = self._state_shapes()
+        lib = _lib.load()
+        info, lay = self._state_layout(lib)
+        n, rb = len(ks), int(info.bytes)
+        buf = np.zeros(max(1, n * rb), dtype=np.uint8)
+        sl = np.array(ks, dtype=np.int32)
+        if n:
+            _lib.check(lib.snmf_online_batch_get_state(self._h, n, sl.ctypes.data, buf.ctypes.data, buf.size))
+        out = []
+        for i in range(n):
+            rec = buf[i * rb:(i + 1) * rb]
+            st = {}
+            cnt_p = int(rec[lay["pending_count"][0]:lay["pending_count"][0] + 4].view("<i4")[0])
+            for name in shapes:
+                off, cnt, dt = lay[name]
+                a = rec[off:off + cnt * dt.itemsize].view(dt).copy()
+                if name == "pending":
+                    st[name] = a[:cnt_p]
+                elif name == "class_tails":  # one tail per class, class-major in the record
+                    st[name] = a.reshape(-1, int(info.ntail))
+                elif name in ("n_push", "update_switch", "l"):
+                    st[name] = int(a[0])
+                else:
+                    dims = {"r_blk": (info.F, info.P_len_l), "lambda_d_blk": (info.F, info.m_a), "Ad_blk": (info.R_a, info.m_a),
+                            "Ad_blk0": (info.R_a, info.m_a), "B_DFT_d": (info.F, info.R_d), "B_fix": (info.F, info.R_d),
+                            "B_Mel_d": (info.F_order, info.R_d)}.get(name)
+                    st[name] = a.reshape(dims, order="F") if dims else a
+            st["record"] = rec.tobytes()
+            out.append(st)
+        return out[0] if one else out
+
+    def set_state(self, streams, states):
+        """Streams `streams` (an index or a list of distinct indices; any slot, fresh, running or finished) take the given
+        states and are then running streams at frame l with an empty trace: the next frames have the bits of the stream
+        the state came from.  A state is what get_state returns (a dict; with `streams` a list, a list of them), or the raw
+        bytes of a record.  In a dict the field arrays override its 'record', so a hand-built g works: without a 'record'
+        every field of the batch's mode must be there.  Unknown or missing keys raise SnmfError(1) and wrong shapes
+        SnmfError(3), naming the field, before the library is reached; a record of another precision, mode, geometry or
+        class count is refused by the library with SnmfError(3) and changes nothing.  B_DFT_x, the settings and the class
+        partition are configuration: the slot has them from create or restart."""
+        ks = self._stream_list(streams)
+        sts = [states] if (np.isscalar(streams) or isinstance(states, (dict, bytes, bytearray, memoryview))) else list(states)
+        if len(sts) != len(ks):
+            raise _invalid(f"{len(sts)} states for {len(ks)} streams")
+        shapes = self._state_shapes()
+        hop = int(self._q.frameshift)
+        parsed = []
+        for k, st in zip(ks, sts):
+            if isinstance(st, (bytes, bytearray, memoryview)):
+                parsed.append((bytes(st), {}))
+                continue
+            if not isinstance(st, dict):
+                raise _invalid(f"state of stream {k}: a dict or the bytes of a record, not {type(st).__name__}")
+            unknown = [key for key in st if key != "record" and key not in shapes]
+            if unknown:
+                raise _invalid(f"state of stream {k}: no field {unknown[0]!r} in this batch's mode")
+            if st.get("record") is None:
+                missing = [key for key in shapes if key not in st]
+                if missing:
+                    raise _invalid(f"state of stream {k}: field {missing[0]!r} is missing (and there is no 'record')")
+            fields = {}
+            for key, (shape, dt) in shapes.items():
+                if key not in st:
+                    continue
+                a = np.asarray(st[key])
+                if key == "pending":
+                    a = a.reshape(-1)
+                    if a.size >= hop:
+                        raise _invalid(f"state of stream {k}: 'pending' holds {a.size} samples, frameshift is {hop}")
+                elif a.size == int(np.prod(shape)) and len(shape) <= 1:
+                    a = a.reshape(shape)
+                if key != "pending" and a.shape != tuple(shape):
+                    raise SnmfError(3, f"state of stream {k}: {key!r} is {a.shape}, expected {tuple(shape)}")  # SNMF_ERR_DIM
+                fields[key] = np.asarray(a, dtype=dt).ravel(order="C" if key == "class_tails" else "F")
+            for key, lo in (("n_push", 0), ("update_switch", 1), ("l", 1)):
+                if key in fields and int(fields[key][0]) < lo:
+                    raise _invalid(f"state of stream {k}: {key!r} = {int(fields[key][0])}")
+            parsed.append((bytes(st["record"]) if st.get("record") is not None else None, fields))
+        lib = _lib.load()
+        info, lay = self._state_layout(lib)
+        n, rb = len(ks), int(info.bytes)
+        if n == 0:
+            return
+        buf = np.zeros(n * rb, dtype=np.uint8)
+        at = 0
+        for rec, fields in parsed:
+            if rec is None:  # a hand-built state: the header of this batch
+                head = np.zeros(_lib.STATE_HEADER_BYTES, dtype=np.uint8)
+                head[:8].view("<u4")[:] = (_lib.STATE_MAGIC, _lib.STATE_VERSION)
+                head[8:] = np.frombuffer(bytes(info), dtype=np.uint8)
+                rec = head.tobytes()
+            if not fields:  # raw bytes go as they are: the library judges them
+                if at + len(rec) > buf.size:
+                    buf = np.concatenate([buf, np.zeros(at + len(rec) - buf.size, dtype=np.uint8)])
+                buf[at:at + len(rec)] = np.frombuffer(rec, dtype=np.uint8)
+                at += len(rec)
+                continue
+            m = min(len(rec), rb)
+            row = buf[at:at + rb]
+            row[:m] = np.frombuffer(rec, dtype=np.uint8)[:m]
+            for key, a in fields.items():
+                off, cnt, dt = lay[key]
+                if key == "pending":
+                    o2 = lay["pending_count"][0]
+                    row[o2:o2 + 4].view("<i4")[0] = a.size
+                    row[off:off + cnt * dt.itemsize] = 0
+                elif a.size != cnt:
+                    raise SnmfError(3, f"state: {key!r} holds {a.size} elements, the batch's record {cnt}")
+                row[off:off + a.size * dt.itemsize] = np.ascontiguousarray(a, dtype=dt).view(np.uint8).reshape(-1)
+            at += rb
+        sl = np.array(ks, dtype=np.int32)
+        _lib.check(lib.snmf_online_batch_set_state(self._h, n, sl.ctypes.data, buf.ctypes.data, at))
 
     def trace(self, k):
         """Per-frame diagnostics of stream k, as OnlineSeparator.trace."""
