@@ -19,6 +19,10 @@ B_Mel_d) and every field of the trace; and every path of the batched separator t
   chains_f32 / chains_f64      ntf_sep_event_rt_chains: 3 chains on 2 slots (restarts on used slots), one carry, one empty file
   fed_f32 / fed_f64            the three streams fed in 160- / 1000- / 57-sample pieces, the flush in a call of its own
   cross_f32 / cross_f64        one call across device chunks (tests/test_online_batch_chunks.py): S = 140, and S = 34 with 4 classes
+  set_f64                      the fp64 batch with settings per stream: beta_div 1, 2 and 0.5, all three adapting
+  rs_f32 / rs_f64              restarts onto used slots: stream 0 with a new B_DFT_d / H0 / Ad_blk0, stream 2 as a carry
+  rs_mel                       the Mel batch (MelConv 0): stream 0 restarts with a new B_Mel_d, stream 2 as a carry
+  state_f32 / state_f64        the raw bytes of get_state for stream 1 after 557 samples (tests/test_gpu_online_batch_state.py)
 -- per stream x_tilde_f, the int16 stream, x_hat, d_hat, the class signals, the final B_DFT_d (Mel: and B_Mel_d) and the
 trace's adapt_iters / n_iter / trig; the chains groups hold per file what ntf_sep_event_rt_chains returns (the int16 stream,
 x_tilde_f and the final B_DFT_d: it hands out no trace, x_hat or d_hat).
@@ -114,16 +118,24 @@ H0s, Ads = [rs.random_sample(200), H0, rs.random_sample(200)], [rs.random_sample
 short = (np.round(s[1733:1733 + 5 * 160] * 0.75), Bd, rs.random_sample(200), rs.random_sample((50, 100)))
 
 
-def batch(tag, pcms, Bds, H0s, Ads, p=p, precision="fp32", feed=None, keep=None, **kw):
+def batch(tag, pcms, Bds, H0s, Ads, p=p, precision="fp32", feed=None, keep=None, then=None, **kw):
     """One batch: `feed` is a list of (pcm list, flush) calls (default: everything in one call, with the flush); dumps the
-    streams `keep` (default: all) as <tag>_s<k>_<array>."""
+    streams `keep` (default: all) as <tag>_s<k>_<array>.  `then(sep)` runs behind the feed and returns a second feed, whose
+    outputs are dumped in the place of the first one's."""
     S = len(pcms)
     sep = OnlineBatchSeparator(Bx, Bds, p, S, H0=H0s, Ad_blk0=Ads, ctx=ctx, class_outputs=True, precision=precision, **kw)
-    parts = [{} for _ in range(S)]
-    for xs, fl in (feed or [(pcms, True)]):
-        for k, o in enumerate(sep.process(xs, flush=fl)):
-            for key, v in o.items():
-                parts[k].setdefault(key, []).append(v)
+
+    def run(calls):
+        parts = [{} for _ in range(S)]
+        for xs, fl in calls:
+            for k, o in enumerate(sep.process(xs, flush=fl)):
+                for key, v in o.items():
+                    parts[k].setdefault(key, []).append(v)
+        return parts
+
+    parts = run(feed or [(pcms, True)])
+    if then is not None:
+        parts = run(then(sep))
     for k in (range(S) if keep is None else keep):
         for key, v in parts[k].items():
             out["%s_s%d_%s" % (tag, k, key)] = np.concatenate(v, axis=-1)
@@ -174,6 +186,34 @@ for tag, prec, S, slots, q in (("cross_f32", "fp32", 140, (0, 69, 139), p), ("cr
     pick = lambda long_ones, the_short: [long_ones[where[k]] if k in where else the_short for k in range(S)]  # noqa: E731
     batch(tag, pick([s] * 3, short[0]), pick(Bds, short[1]), pick(H0s, short[2]), pick(Ads, short[3]), p=q, precision=prec,
           keep=list(slots) + [1, S - 2])
+# settings per stream: every instantiation of the fp64 adaptation kernel, and the restart's per-stream "this stream adapts"
+batch("set_f64", pcms, Bds, H0s, Ads, precision="fp64", settings=[dict(cf="kl"), dict(cf="ed"), dict(cf="beta", beta_div=0.5)])
+# restarts onto used slots behind a whole recording: stream 0 with new arrays, stream 2 as a carry (all None), stream 1 left
+# flushed; the two then run each other's recording
+rs_new = np.random.RandomState(11)
+newB, newH, newA = Bds[2][:, rs_new.permutation(100)], rs_new.random_sample(200), rs_new.random_sample((50, 100))
+none = pcms[0][:0]
+
+
+def restarts(mel_d=None):
+    def then(sep):
+        sep.restart(0, B_DFT_d=None if mel_d is not None else newB, H0=newH, Ad_blk0=newA, B_Mel_d=mel_d)
+        sep.restart(2)
+        return [([pcms[2], none, pcms[0]], [True, False, True])]
+    return then
+
+
+batch("rs_f32", pcms, Bds, H0s, Ads, then=restarts(), keep=(0, 2))
+batch("rs_f64", pcms, Bds, H0s, Ads, precision="fp64", then=restarts(), keep=(0, 2))
+batch("rs_mel", pcms, Bds, H0s, Ads, p=dict(p, B_sep_mode="Mel", MelConv=0, F_order=64), B_Mel_x=BM[:, :100],
+      B_Mel_d=[BM[:, 100:], BM[:, 100:] * 1.01, BM[:, 100:]], then=restarts(BM[:, 100:][:, rs_new.permutation(100)]), keep=(0, 2))
+# a stream's state g as raw bytes, mid-recording and mid-hop
+for prec in ("fp32", "fp64"):
+    sep = OnlineBatchSeparator(Bx, Bds, dict(p, **CLS), 3, H0=H0s, Ad_blk0=Ads, ctx=ctx, class_outputs=True, precision=prec)
+    sep.process([x[:557] for x in pcms])
+    out["state_f%s_record" % prec[2:]] = np.frombuffer(sep.get_state(1)["record"], dtype=np.uint8)
+    sep.close()
+assert all(out["%s_s%d_adapt_iters" % (t, k)].max() > 0 for t in ("set_f64", "rs_f32", "rs_f64", "rs_mel") for k in (0, 2))
 assert out["single_f64_adapt_iters"].max() > 0 and out["batch_f32_adapt_iters"].max() > 0  # the adaptation ran
 assert all(out["%s_s1_adapt_iters" % t].max() > 0 for t in ("batch_f64", "batch_f32_cls", "mel0", "mel1", "fed_f32", "fed_f64"))
 np.savez(sys.argv[1], **out)

@@ -10,8 +10,10 @@
 //   k_obprep_mel  Mel mode: melmat * lambda_d_blk of every stream whose adaptation is due (k_wadapt_batch's V)
 //   k_wadapt_batch the W-only adaptation solve of :296-336, one workgroup per stream, gated on the device
 //   k_obassemble / k_obrefresh  the re-assembly of :336 and the next frame solve's dictionary images, gated
-//   k_obistft / k_obtail / k_obola  inverse STFT and overlap-add of src/NTF_sep_event_RT.m:104-124
+//   k_obistft<LOGN, float> / k_obtail<float> / k_obola<float>  inverse STFT and overlap-add of src/NTF_sep_event_RT.m:104-124
 //   k_obrestart   the state of the listed streams back to init_buff (a new recording; creation restarts all streams)
+// The synthesis kernels and the restart of the arrays both modes hold are written once over the element type in
+// snmf_online_batch_common.h, and this unit instantiates them with float; the re-assembly's body (all doubles) is there too.
 // Frame-indexed buffers are frame-major: the slot of frame i of stream s is i * S + s.  A stream's own state sits at a
 // fixed stride per stream.  Nothing is shared between the streams' workgroups, so a stream's bits do not depend on
 // the other streams of its batch.
@@ -470,50 +472,22 @@ __global__ __launch_bounds__(kWbNT) void k_wadapt_batch(WBatchArgs a) {
     if (tid == 0) a.iters[(size_t)a.step * a.S + s] = stopped ? n_rec : a.max_iter;
 }
 
-// B_DFT_d = [B_d_rem, B_d_tmp, B_d_fix] (:336), resp. B_Mel_d (:318), of every stream whose adaptation ran: one workgroup per
-// (column, stream), into Btmp (the kept columns are read from the dictionary the next launch overwrites).  Stream s's fixed
-// columns are at Bfix + s * sfix (DFT: the dictionary it started with, :328; Mel: its own B_Mel_d, :309).
+// the re-assembly of every stream whose adaptation ran (oassemble_cols, snmf_online_batch_common.h); grid (Rd, S)
 __global__ __launch_bounds__(256) void k_obassemble(const OnlineStatus* status, const int* nfr, int step, int S, const double* B,
                                                     const double* Wu, const double* Bfix, int64_t sfix, const uint8_t* rupa, int F,
                                                     int r, int Rx, int Ra, int Rd, double* Btmp) {
-    const int j = blockIdx.x, s = blockIdx.y;
-    if (j >= Rd || !ob_due(status, nfr, step, S, s)) return;
-    const double* Bd_old = B + (size_t)s * r * F + (size_t)Rx * F;
-    const uint8_t* rup = rupa + (size_t)s * Ra;
-    const double* src;
-    if (j >= Ra) {
-        src = Bfix + (size_t)s * sfix + (size_t)j * F;
-    } else {
-        bool retrained;
-        const int k = oassemble_col(rup, Ra, j, &retrained);
-        src = retrained ? Wu + (size_t)s * Ra * F + (size_t)k * F : Bd_old + (size_t)k * F;
-    }
-    double* dst = Btmp + (size_t)s * Rd * F + (size_t)j * F;
-    for (int f = threadIdx.x; f < F; f += blockDim.x) dst[f] = src[f];
+    oassemble_cols(status, nfr, step, S, B, Wu, Bfix, sfix, rupa, F, r, Rx, Ra, Rd, Btmp);
 }
 
 // ---------------------------------------------------------------------------------------------
-// k_obrestart: src/NTF_sep_event_RT.m:27-38 + src/init_buff.m:17-42 for the listed streams -- the one initialisation path
-// (snmf_online_batch_create restarts every stream through it).  Grid (listed stream, array, part): each workgroup resets
-// one part of one per-stream array of one listed stream.  No array is both read and written by the launch except
-// through disjoint (stream, array) pairs, so the workgroups are independent.  k_obrefresh (slot list form) follows.
+// k_obrestart: the restart of the listed streams (snmf_online_batch_common.h: grid (listed stream, array, part), the shared
+// arrays through orestart_common) with the fp32 mode's own arrays behind the shared ones: the frame solve's images and, in
+// Mel mode, the Mel masters and the fp32 DFT dictionary.  k_obrefresh (slot list form) follows.
 // ---------------------------------------------------------------------------------------------
-enum : int {
-    kRsBx, kRsBd, kRsBfix, kRsH0, kRsAd0, kRsAdblk, kRsLdblk, kRsRup, kRsLam, kRsXm, kRsRblk, kRsTail, kRsTailX, kRsTailD,
-    kRsDev, kRsWcf, kRsBmx, kRsBmd, kRsBdf, kRsImg, kRsN
-};
-constexpr int kRsParts = 8;  // workgroups per (stream, array)
+enum : int { kRsWcf = kRsShared, kRsBmx, kRsBmd, kRsBdf, kRsImg, kRsN };
 
 struct ORestartArgs {
-    const int* slots;       // [n] the streams to restart (distinct, in range: checked on the host)
-    const double* Bx;       // [Rx][F] the shared speech dictionary
-    const double* Bd;       // [n][Rd][F] new noise dictionaries, or NULL = keep each stream's (carry; Bfix untouched)
-    const float* H0n;       // [n][r] or NULL = keep
-    const float* Adn;       // [n][Ra][ma] or NULL = the values the stream last started with (Ad0)
-    double *B, *Bfix;       // [S][r][F], [S][Rd][F]
-    float *H0, *Ad0, *adblk, *ldblk, *lambda_dav, *Xm_tilde, *r_blk, *tail, *tail_x, *tail_d;
-    uint8_t* rup;
-    OnlineDev* dev;
+    ORestartCommon<float> c;
     float *Wcf, *wx, *dphv, *Hin;
     double* wn;
     // Mel mode (NULL otherwise)
@@ -521,75 +495,35 @@ struct ORestartArgs {
     const double* Bmd;      // [n][Rd][n1] new B_Mel_d, or NULL = keep each stream's (carry)
     double* Bm;             // [S][r][n1] the fp64 Mel masters [B_Mel_x | B_Mel_d]: the solve's dictionary
     float* Bdf;             // [S][r][F] fp32 [B_DFT_x | B_DFT_d] (MelConv = 0: the post-filter's DFT bases)
-    int F, r, Rx, Rd, Ra, ma, Pl, rp, Fp, adapt, n1;
-    int64_t ntail;
+    int rp, Fp, adapt, n1;
 };
 
 __global__ __launch_bounds__(256) void k_obrestart(ORestartArgs a) {
-    const int i = blockIdx.x, arr = blockIdx.y, s = a.slots[i];
-    const size_t F = a.F, q0 = (size_t)blockIdx.z * 256 + threadIdx.x, qs = (size_t)kRsParts * 256;
-    auto copy = [&](auto* dst, const auto* src, size_t n) {
-        for (size_t e = q0; e < n; e += qs) dst[e] = src[e];
-    };
-    auto fill = [&](auto* dst, auto v, size_t n) {
-        for (size_t e = q0; e < n; e += qs) dst[e] = v;
-    };
-    const size_t nA = (size_t)a.Ra * a.ma;
+    const int i = blockIdx.x, arr = blockIdx.y, s = a.c.slots[i];
+    if (arr < kRsShared) return orestart_common(a.c, arr, a.adapt != 0);
+    const size_t F = a.c.F, nX = (size_t)a.c.Rx, nD = (size_t)a.c.Rd, r = a.c.r;
     switch (arr) {
-        case kRsBx: copy(a.B + (size_t)s * a.r * F, a.Bx, (size_t)a.Rx * F); break;
-        case kRsBd:
-            if (a.Bd) copy(a.B + (size_t)s * a.r * F + (size_t)a.Rx * F, a.Bd + (size_t)i * a.Rd * F, (size_t)a.Rd * F);
-            break;
-        case kRsBfix:  // B_Mel_d in DFT mode (:328): set with a new dictionary, never adapted (:392)
-            if (a.Bd) copy(a.Bfix + (size_t)s * a.Rd * F, a.Bd + (size_t)i * a.Rd * F, (size_t)a.Rd * F);
-            break;
-        case kRsH0:
-            if (a.H0n) copy(a.H0 + (size_t)s * a.r, a.H0n + (size_t)i * a.r, (size_t)a.r);
-            break;
-        case kRsAd0:
-            if (a.Adn) copy(a.Ad0 + s * nA, a.Adn + i * nA, nA);
-            break;
-        case kRsAdblk:  // rand(R_a, m_a) (src/init_buff.m:39); zeros without adaptation
-            if (!a.adapt) fill(a.adblk + s * nA, 0.f, nA);
-            else copy(a.adblk + s * nA, a.Adn ? a.Adn + i * nA : a.Ad0 + s * nA, nA);
-            break;
-        case kRsLdblk: fill(a.ldblk + (size_t)s * F * a.ma, 0.f, F * a.ma); break;
-        case kRsRup: fill(a.rup + (size_t)s * a.Ra, (uint8_t)0, (size_t)a.Ra); break;
-        case kRsLam: fill(a.lambda_dav + s * F, 0.f, F); break;
-        case kRsXm: fill(a.Xm_tilde + s * F, 0.f, F); break;
-        case kRsRblk: fill(a.r_blk + s * F * a.Pl, 0.f, F * a.Pl); break;
-        case kRsTail: fill(a.tail + s * a.ntail, 0.f, (size_t)a.ntail); break;
-        case kRsTailX:
-            if (a.tail_x) fill(a.tail_x + s * a.ntail, 0.f, (size_t)a.ntail);
-            break;
-        case kRsTailD:
-            if (a.tail_d) fill(a.tail_d + s * a.ntail, 0.f, (size_t)a.ntail);
-            break;
-        case kRsDev:
-            if (q0 == 0) a.dev[s] = OnlineDev{0, 1, 0, 0};  // update_switch = 1 (src/init_buff.m:42)
-            break;
-        case kRsWcf: fill(a.Wcf + (size_t)s * a.rp * a.Fp, 0.f, (size_t)a.rp * a.Fp); break;  // rows >= F stay zero
+        case kRsWcf: ors_fill(a.Wcf + (size_t)s * a.rp * a.Fp, 0.f, (size_t)a.rp * a.Fp); break;  // rows >= F stay zero
         case kRsBmx:
-            if (a.Bm) copy(a.Bm + (size_t)s * a.r * a.n1, a.Bmx, (size_t)a.Rx * a.n1);
+            if (a.Bm) ors_copy(a.Bm + s * r * a.n1, a.Bmx, nX * a.n1);
             break;
         case kRsBmd:
-            if (a.Bm && a.Bmd) copy(a.Bm + (size_t)s * a.r * a.n1 + (size_t)a.Rx * a.n1, a.Bmd + (size_t)i * a.Rd * a.n1, (size_t)a.Rd * a.n1);
+            if (a.Bm && a.Bmd) ors_copy(a.Bm + s * r * a.n1 + nX * a.n1, a.Bmd + i * nD * a.n1, nD * a.n1);
             break;
-        case kRsBdf:  // the fp32 image of the DFT dictionary this restart leaves (kRsBd writes B only when a.Bd is given)
+        case kRsBdf:  // the fp32 image of the DFT dictionary this restart leaves (kRsBd writes B only when a new one is given)
             if (a.Bdf) {
-                float* d = a.Bdf + (size_t)s * a.r * F;
-                const double* src = a.Bd ? a.Bd + (size_t)i * a.Rd * F : a.B + (size_t)s * a.r * F + (size_t)a.Rx * F;
-                for (size_t e = q0; e < (size_t)a.Rx * F; e += qs) d[e] = (float)a.Bx[e];
-                for (size_t e = q0; e < (size_t)a.Rd * F; e += qs) d[(size_t)a.Rx * F + e] = (float)src[e];
+                float* d = a.Bdf + s * r * F;
+                ors_copy(d, a.c.Bx + s * a.c.sBx, nX * F);
+                ors_copy(d + nX * F, a.c.Bd ? a.c.Bd + i * nD * F : a.c.B + s * r * F + nX * F, nD * F);
             }
             break;
         default: {  // kRsImg: k_obrefresh writes the r real columns of these; pads: dphv 1.0f (r < 8 * KB must divide by
                     // something finite: 0 * 0 / 0 was NaN in every pad activation and cost), the rest 0
             const size_t o = (size_t)s * a.rp;
-            fill(a.wx + o, 0.f, (size_t)a.rp);
-            fill(a.dphv + o, 1.f, (size_t)a.rp);
-            fill(a.Hin + o, 0.f, (size_t)a.rp);
-            fill(a.wn + o, 0.0, (size_t)a.rp);
+            ors_fill(a.wx + o, 0.f, (size_t)a.rp);
+            ors_fill(a.dphv + o, 1.f, (size_t)a.rp);
+            ors_fill(a.Hin + o, 0.f, (size_t)a.rp);
+            ors_fill(a.wn + o, 0.0, (size_t)a.rp);
         }
     }
 }
@@ -660,44 +594,5 @@ __global__ __launch_bounds__(256) void k_obrefresh(ORefreshArgs a) {
 // snmf_online_batch_common.h); grid (listed stream, kStN, kStParts).  k_obrefresh (slot list form) follows a put.
 __global__ __launch_bounds__(256) void k_obstate_get(OStateArgs<float> a) { ostate_xfer<float, false>(a); }
 __global__ __launch_bounds__(256) void k_obstate_put(OStateArgs<float> a) { ostate_xfer<float, true>(a); }
-
-// inverse STFT of every (frame, stream): stream s's frames go behind the nov-1 frames kept from its previous chunk
-template <int LOGN>
-__global__ __launch_bounds__(256) void k_obistft(OIstftArgs a, const int* nfr, int S, int64_t syn_stride, int nov) {
-    constexpr int N = 1 << LOGN;
-    __shared__ float2 bufA[N];
-    __shared__ float2 bufB[N];
-    const int i = blockIdx.x, s = blockIdx.y;
-    if (i >= nfr[s]) return;
-    const size_t slot = (size_t)i * S + s;
-    oistft_frame<LOGN, float>(a, a.mag + slot * a.ld, a.ph + slot * a.ld, a.syn + (size_t)s * syn_stride + (size_t)(nov - 1 + i) * a.sz, bufA,
-                       bufB);
-}
-
-// the nov-1 synthesis frames carried between chunks: into (dir 0) / out of (dir 1) each stream's synthesis buffer
-__global__ __launch_bounds__(256) void k_obtail(float* syn, float* tail, const int* nfr, int64_t syn_stride, int nov, int sz, int dir) {
-    const int s = blockIdx.x;
-    const size_t n = (size_t)(nov - 1) * sz;
-    float* sy = syn + (size_t)s * syn_stride + (dir ? (size_t)nfr[s] * sz : 0);
-    float* tl = tail + (size_t)s * n;
-    for (size_t e = threadIdx.x; e < n; e += 256) {
-        if (dir) tl[e] = sy[e];
-        else sy[e] = tl[e];
-    }
-}
-
-// Overlap-add and int16 output (oola_sample) per stream: grid (blocks, S); stream s writes its n_out[s] hops at out_off[s]
-__global__ __launch_bounds__(256) void k_obola(const float* __restrict__ syn, int64_t syn_stride, OBatchFrames b, const int* i_first,
-                                               const int* n_out, const int64_t* out_off, int delay, int sz, int hop, int nov,
-                                               float* __restrict__ outf, int16_t* __restrict__ out16) {
-    const int s = blockIdx.y;
-    const size_t n = (size_t)n_out[s] * hop;
-    const float* sy = syn + (size_t)s * syn_stride;
-    const int l0 = b.l0[s], i0 = i_first[s];
-    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
-        const int j = (int)(e / hop), q0 = (int)(e - (size_t)j * hop);
-        oola_sample<float>(sy, i0 + j, q0, l0, delay, sz, hop, nov, outf, out16, (size_t)out_off[s] + e);
-    }
-}
 
 }  // namespace snmf

@@ -11,8 +11,10 @@
 //   k_obclass64    the per-class reconstructions of a frame step, behind the solves and before the adaptation
 //   k_wadapt_batch64  the W-only adaptation solve of :296-336, ONE workgroup per due stream, gated on the device
 //   k_obassemble64 / k_obrefresh64  the re-assembly of :336 and the next frame solve's dictionary images, gated
-//   k_obistft64 / k_obtail64 / k_obola64  inverse STFT and overlap-add of src/NTF_sep_event_RT.m:104-124
+//   k_obistft<LOGN, double> / k_obtail<double> / k_obola<double>  inverse STFT and overlap-add of src/NTF_sep_event_RT.m:104-124
 //   k_obrestart64  the state of the listed streams back to init_buff, each from its own event dictionary
+// The synthesis kernels and the restart's body are written once over the element type in snmf_online_batch_common.h, and this
+// unit instantiates them with double; the re-assembly's body (all doubles) is there too.
 // Every stream has its own settings (OStreamSettings, a device table indexed by the stream) and its own B_DFT_x; the
 // geometry is the batch's.  DFT mode and the supervised frame solve only, as the single-stream fp64 mode.
 // Included by snmf_tu_online_batch_f64.hip only.
@@ -454,25 +456,12 @@ __global__ __launch_bounds__(kWb64NT) void k_wadapt_batch64(WBatch64Args a) {
     if (tid == 0) a.iters[(size_t)a.step * a.S + s] = stopped ? n_rec : max_iter;
 }
 
-// B_DFT_d = [B_d_rem, B_d_tmp, B_d_fix] (:336) of every stream whose adaptation ran (k_obassemble's form): one workgroup per
-// (column, stream), into Btmp (the kept columns are read from the dictionary the refresh overwrites).
+// the re-assembly of every stream whose adaptation ran (oassemble_cols, snmf_online_batch_common.h): the fixed columns are
+// the dictionary each stream started with, [S][Rd][F]; grid (Rd, S)
 __global__ __launch_bounds__(256) void k_obassemble64(const OnlineStatus* status, const int* nfr, int step, int S, const double* B,
                                                       const double* Wu, const double* Bfix, const uint8_t* rupa, int F, int r, int Rx,
                                                       int Ra, int Rd, double* Btmp) {
-    const int j = blockIdx.x, s = blockIdx.y;
-    if (j >= Rd || !ob_due(status, nfr, step, S, s)) return;
-    const double* Bd_old = B + (size_t)s * r * F + (size_t)Rx * F;
-    const uint8_t* rup = rupa + (size_t)s * Ra;
-    const double* src;
-    if (j >= Ra) {
-        src = Bfix + ((size_t)s * Rd + j) * F;
-    } else {
-        bool retrained;
-        const int k = oassemble_col(rup, Ra, j, &retrained);
-        src = retrained ? Wu + ((size_t)s * Ra + k) * F : Bd_old + (size_t)k * F;
-    }
-    double* dst = Btmp + ((size_t)s * Rd + j) * F;
-    for (int f = threadIdx.x; f < F; f += blockDim.x) dst[f] = src[f];
+    oassemble_cols(status, nfr, step, S, B, Wu, Bfix, (int64_t)Rd * F, rupa, F, r, Rx, Ra, Rd, Btmp);
 }
 
 struct ORefresh64Args {
@@ -500,119 +489,16 @@ __global__ __launch_bounds__(256) void k_obrefresh64(ORefresh64Args a) {
                 a.csum + (size_t)s * a.r, red);
 }
 
-// ---------------------------------------------------------------------------------------------
-// k_obrestart64: src/NTF_sep_event_RT.m:27-38 + src/init_buff.m:17-42 for the listed streams (k_obrestart's form; creation
-// restarts every stream through it).  Grid (listed stream, array, part); k_obrefresh64 (slot list form) follows.
-// ---------------------------------------------------------------------------------------------
-enum : int {
-    kRs64Bx, kRs64Bd, kRs64Bfix, kRs64H0, kRs64Ad0, kRs64Adblk, kRs64Ldblk, kRs64Rup, kRs64Lam, kRs64Xm, kRs64Rblk, kRs64Tail,
-    kRs64TailX, kRs64TailD, kRs64Dev, kRs64N
-};
-constexpr int kRs64Parts = 8;  // workgroups per (stream, array)
-
-struct ORestart64Args {
-    const int* slots;       // [n] the streams to restart (distinct, in range: checked on the host)
-    const double* Bx;       // [S][Rx][F] every stream's own event dictionary
-    const OStreamSettings* set;  // [S] (adapt_train_N of the stream decides its Ad_blk)
-    const double* Bd;       // [n][Rd][F] new noise dictionaries, or NULL = keep each stream's (carry; Bfix untouched)
-    const double* H0n;      // [n][r] or NULL = keep
-    const double* Adn;      // [n][Ra][ma] or NULL = the values the stream last started with (Ad0)
-    double *B, *Bfix;       // [S][r][F], [S][Rd][F]
-    double *H0, *Ad0, *adblk, *ldblk, *lambda_dav, *Xm_tilde, *r_blk, *tail, *tail_x, *tail_d;
-    uint8_t* rup;
-    OnlineDev* dev;
-    int F, r, Rx, Rd, Ra, ma, Pl;
-    int64_t ntail;
-};
-
-__global__ __launch_bounds__(256) void k_obrestart64(ORestart64Args a) {
-    const int i = blockIdx.x, arr = blockIdx.y, s = a.slots[i];
-    const size_t F = a.F, q0 = (size_t)blockIdx.z * 256 + threadIdx.x, qs = (size_t)kRs64Parts * 256;
-    auto copy = [&](auto* dst, const auto* src, size_t n) {
-        for (size_t e = q0; e < n; e += qs) dst[e] = src[e];
-    };
-    auto fill = [&](auto* dst, auto v, size_t n) {
-        for (size_t e = q0; e < n; e += qs) dst[e] = v;
-    };
-    const size_t nA = (size_t)a.Ra * a.ma;
-    switch (arr) {
-        case kRs64Bx: copy(a.B + (size_t)s * a.r * F, a.Bx + (size_t)s * a.Rx * F, (size_t)a.Rx * F); break;
-        case kRs64Bd:
-            if (a.Bd) copy(a.B + (size_t)s * a.r * F + (size_t)a.Rx * F, a.Bd + (size_t)i * a.Rd * F, (size_t)a.Rd * F);
-            break;
-        case kRs64Bfix:  // B_Mel_d in DFT mode (:328): set with a new dictionary, never adapted (:392)
-            if (a.Bd) copy(a.Bfix + (size_t)s * a.Rd * F, a.Bd + (size_t)i * a.Rd * F, (size_t)a.Rd * F);
-            break;
-        case kRs64H0:
-            if (a.H0n) copy(a.H0 + (size_t)s * a.r, a.H0n + (size_t)i * a.r, (size_t)a.r);
-            break;
-        case kRs64Ad0:
-            if (a.Adn) copy(a.Ad0 + s * nA, a.Adn + i * nA, nA);
-            break;
-        case kRs64Adblk:  // rand(R_a, m_a) (src/init_buff.m:39); zeros without adaptation
-            if (!a.set[s].adapt_train_N) fill(a.adblk + s * nA, 0.0, nA);
-            else copy(a.adblk + s * nA, a.Adn ? a.Adn + i * nA : a.Ad0 + s * nA, nA);
-            break;
-        case kRs64Ldblk: fill(a.ldblk + (size_t)s * F * a.ma, 0.0, F * a.ma); break;
-        case kRs64Rup: fill(a.rup + (size_t)s * a.Ra, (uint8_t)0, (size_t)a.Ra); break;
-        case kRs64Lam: fill(a.lambda_dav + s * F, 0.0, F); break;
-        case kRs64Xm: fill(a.Xm_tilde + s * F, 0.0, F); break;
-        case kRs64Rblk: fill(a.r_blk + s * F * a.Pl, 0.0, F * a.Pl); break;
-        case kRs64Tail: fill(a.tail + s * a.ntail, 0.0, (size_t)a.ntail); break;
-        case kRs64TailX:
-            if (a.tail_x) fill(a.tail_x + s * a.ntail, 0.0, (size_t)a.ntail);
-            break;
-        case kRs64TailD:
-            if (a.tail_d) fill(a.tail_d + s * a.ntail, 0.0, (size_t)a.ntail);
-            break;
-        default:  // kRs64Dev
-            if (q0 == 0) a.dev[s] = OnlineDev{0, 1, 0, 0};  // update_switch = 1 (src/init_buff.m:42)
-    }
+// k_obrestart64: the restart of the listed streams (orestart_common, snmf_online_batch_common.h; grid (listed stream,
+// kRsShared, kRsParts)): every stream from its own event dictionary, its Ad_blk by its own adapt_train_N.  k_obrefresh64
+// (slot list form) follows.
+__global__ __launch_bounds__(256) void k_obrestart64(ORestartCommon<double> a, const OStreamSettings* __restrict__ set) {
+    orestart_common(a, blockIdx.y, set[a.slots[blockIdx.x]].adapt_train_N != 0);
 }
 
 // The listed streams' state g into (k_obstate_get64) / out of (k_obstate_put64) a slab of records (ostate_xfer,
 // snmf_online_batch_common.h); grid (listed stream, kStN, kStParts).  k_obrefresh64 (slot list form) follows a put.
 __global__ __launch_bounds__(256) void k_obstate_get64(OStateArgs<double> a) { ostate_xfer<double, false>(a); }
 __global__ __launch_bounds__(256) void k_obstate_put64(OStateArgs<double> a) { ostate_xfer<double, true>(a); }
-
-// inverse STFT of every (frame, stream): stream s's frames go behind the nov-1 frames kept from its previous chunk;
-// dynamic LDS = 2 N double2
-template <int LOGN>
-__global__ __launch_bounds__(256) void k_obistft64(OIstftArgsT<double> a, const int* nfr, int S, int64_t syn_stride, int nov) {
-    constexpr int N = 1 << LOGN;
-    extern __shared__ __attribute__((aligned(16))) double2 fbuf[];
-    const int i = blockIdx.x, s = blockIdx.y;
-    if (i >= nfr[s]) return;
-    const size_t slot = (size_t)i * S + s;
-    oistft_frame<LOGN, double>(a, a.mag + slot * a.ld, a.ph + slot * a.ld, a.syn + (size_t)s * syn_stride + (size_t)(nov - 1 + i) * a.sz, fbuf,
-                               fbuf + N);
-}
-
-// the nov-1 synthesis frames carried between chunks: into (dir 0) / out of (dir 1) each stream's synthesis buffer
-__global__ __launch_bounds__(256) void k_obtail64(double* syn, double* tail, const int* nfr, int64_t syn_stride, int nov, int sz, int dir) {
-    const int s = blockIdx.x;
-    const size_t n = (size_t)(nov - 1) * sz;
-    double* sy = syn + (size_t)s * syn_stride + (dir ? (size_t)nfr[s] * sz : 0);
-    double* tl = tail + (size_t)s * n;
-    for (size_t e = threadIdx.x; e < n; e += 256) {
-        if (dir) tl[e] = sy[e];
-        else sy[e] = tl[e];
-    }
-}
-
-// Overlap-add and int16 output (oola_sample: the int16 stream is the fp64 value rounded half away from zero, as k_oola64)
-// per stream: grid (blocks, S); stream s writes its n_out[s] hops at out_off[s]
-__global__ __launch_bounds__(256) void k_obola64(const double* __restrict__ syn, int64_t syn_stride, OBatchFrames b, const int* i_first,
-                                                 const int* n_out, const int64_t* out_off, int delay, int sz, int hop, int nov,
-                                                 double* __restrict__ outf, int16_t* __restrict__ out16) {
-    const int s = blockIdx.y;
-    const size_t n = (size_t)n_out[s] * hop;
-    const double* sy = syn + (size_t)s * syn_stride;
-    const int l0 = b.l0[s], i0 = i_first[s];
-    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
-        const int j = (int)(e / hop), q0 = (int)(e - (size_t)j * hop);
-        oola_sample<double>(sy, i0 + j, q0, l0, delay, sz, hop, nov, outf, out16, (size_t)out_off[s] + e);
-    }
-}
 
 }  // namespace snmf

@@ -1,6 +1,7 @@
 // snmf_online_batch_host.h -- the host driver of the batched online separator, shared by its two precisions
 // (snmf_tu_online_batch.hip: fp32, handle snmf_online_batch; snmf_tu_online_batch_f64.hip: fp64, handle OnlineBatchF64).
-// Host code only: no kernel and no device function lives here.
+// Host code only: no kernel or device function is defined here.  The kernel templates both modes share are defined in
+// snmf_online_batch_common.h, and the driver launches them with the mode's element type.
 //
 // Per stream, the hop queue / history / flush logic of snmf_online_process_f32 (snmf_online_host.h); on the device, one fixed
 // sequence of launches per frame step for all streams (frame solve, post-filter, class spectra, gated adaptation) -- with
@@ -15,18 +16,17 @@
 //   int obm_post(H*, fr, step)                                   likewise
 //   int obm_class_spectra(H*, fr, step, C)                       likewise (only with a class partition set)
 //   int obm_adapt(H*, fr, step)                                  adaptation + re-assembly + dictionary refresh behind frame `step`
-//   int obm_tail(H*, tail, fr, syn_stride, store)                overlap-add tail into (0) / out of (1) the synthesis buffer
-//   int obm_istft(H*, mag, fr, C, syn_stride)                    inverse STFT of the kept frames
-//   int obm_ola(H*, gx, fr, syn_stride, d_if, d_no, d_oo, out, out16)   overlap-add to output hops
+//   size_t obm_lds_fft(const H*)                                 dynamic LDS of the inverse STFT's two FFT buffers (fp32: 0, they are static)
 //   void obm_state_mode(const H*, mel, mel_conv, n1)             get-state / set-state: the mode a record is taken under
-//   void obm_state_arrays(H*, OStateArgs<T>&)                    the mode's own masters (Mel: Bm, Bdf)
-//   int obm_state_launch(H*, const OStateArgs<T>&, n, put)       k_obstate_get / _put (k_obstate_get64 / _put64)
+//   int obm_state_launch(H*, const OStateArgs<T>&, n, put)       k_obstate_get / _put (k_obstate_get64 / _put64); fp32 adds its Mel masters (Bm, Bdf, n1: NULL / 0 as they come)
 //   int obm_state_refresh(H*, n)                                 the dictionary images of the streams in rs_slots, as a restart's
 //   void obm_state_installed(H*, n, slots)                       the mode's own host state behind a set
+// A restart is obatch_restart: the mode uploads what is its own, then passes the launch of its restart kernel.
 // The calls are resolved at compile time (argument-dependent lookup on the handle type); nothing is dispatched at run time.
 #pragma once
 #include "snmf_internal.h"
 #include "snmf_online_batch_common.h"
+#include "snmf_online_classes.h"  // by_logn: the FFT-size dispatch of the inverse STFT
 #include "snmf_online_host.h"  // online_frame_record: a frame's status as the trace holds it
 
 constexpr size_t kBTraceCap = 1u << 16;   // per stream: the newest 65536 frames, as snmf_online_trace
@@ -42,11 +42,19 @@ struct OBatchState {
     bool started = false;  // a process call was made (set_mel / set_classes must come first)
     bool failed = false;
     size_t ntail = 0;
-    // per stream, device
+    // per stream, device: the fp64 dictionaries [B_DFT_x | B_DFT_d] [S][r][F], the noise dictionary each stream started with
+    // and the re-assembly's scratch [S][Rd][F]; H0 [S][r], Ad_blk0 [S][Ra][ma] and the post-filter's state and rings
+    double *B = nullptr, *Bfix = nullptr, *Btmp = nullptr;
+    T *H0 = nullptr, *Ad0 = nullptr, *lambda_dav = nullptr, *Xm_tilde = nullptr, *r_blk = nullptr, *ldblk = nullptr, *adblk = nullptr;
     T *tail = nullptr, *tail_x = nullptr, *tail_d = nullptr;
     uint8_t* rup = nullptr;
     OnlineDev* dev = nullptr;
-    int* rs_slots = nullptr;     // restart upload (sized for all S streams)
+    double* Bxd = nullptr;       // B_DFT_x in fp64 as a recording starts with it: fp32 one [Rx][F] for all, fp64 [S][Rx][F]
+    T *win_s = nullptr, *win_i = nullptr;  // shared: the analysis / synthesis windows and the FFT's twiddles
+    ocplx<T>* tw = nullptr;
+    int* rs_slots = nullptr;     // restart uploads (sized for all S streams)
+    double* rs_B = nullptr;
+    T *rs_H = nullptr, *rs_A = nullptr;
     int* meta_i = nullptr;       // [6][S] nfr, nreal, l0, i_first, n_out, (pad)
     int64_t* meta_l = nullptr;   // [3][S] off, zoff, out_off
     // per-class outputs (set_classes): n_ev event classes then n_cls - n_ev noise classes; n_cls = 0: none set
@@ -106,6 +114,17 @@ void obatch_free_chunk(H* o) {
     o->iters = nullptr;
     o->C = 0;
     o->cap_sig = o->cap_out = 0;
+}
+
+// every device array of OBatchState (a mode's destroy frees its own besides)
+template <class H>
+void obatch_free_state(H* o) {
+    obatch_free_chunk(o);
+    void* ptrs[] = {o->B, o->Bfix, o->Btmp, o->H0, o->Ad0, o->lambda_dav, o->Xm_tilde, o->r_blk, o->ldblk, o->adblk, o->tail, o->tail_x,
+                    o->tail_d, o->rup, o->dev, o->Bxd, o->win_s, o->win_i, o->tw, o->rs_slots, o->rs_B, o->rs_H, o->rs_A, o->meta_i,
+                    o->meta_l, o->cls, o->tail_c, o->st_slab};
+    for (void* q : ptrs)
+        if (q) hipFree(q);
 }
 
 // chunk buffers for C frames per stream and the given signal / output sizes
@@ -202,6 +221,40 @@ void obatch_restart_host(H* o, int n, const int32_t* slots) {
     }
 }
 
+// The streams slots[0..n) start a new recording (src/NTF_sep_event_RT.m:27-38 + src/init_buff.m): the uploads, the mode's
+// restart kernel (launch(a): orestart_common on `a`, plus the mode's own arrays), the class tails, one refresh over the
+// streams' columns, and their host state.  Arguments are checked by the caller, and what is the mode's own (fp32: the Mel
+// uploads; fp64: the settings entries and event dictionaries) is on the stream already.  Bd is n x Rd x F fp64 or NULL
+// (carry), H0 n x r or NULL, Ad n x Ra x ma or NULL; sBx is the stride of Bxd per stream (0: one dictionary for all).
+// Ordered on ctx->stream, no synchronise (the uploads come from pageable host memory, which the runtime copies before it
+// returns).
+template <class H, class Launch>
+int obatch_restart(H* o, int n, const int32_t* slots, const double* Bd, const typename H::elem* H0, const typename H::elem* Ad, int64_t sBx,
+                   Launch launch) {
+    using T = typename H::elem;
+    const snmf_online_params& p = o->p;
+    hipStream_t st = o->ctx->stream;
+    const size_t F = o->F, nA = (size_t)o->Ra * o->ma;
+    HIP_TRY(hipMemcpyAsync(o->rs_slots, slots, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    if (Bd) HIP_TRY(hipMemcpyAsync(o->rs_B, Bd, (size_t)n * p.R_d * F * 8, hipMemcpyHostToDevice, st));
+    if (H0) HIP_TRY(hipMemcpyAsync(o->rs_H, H0, (size_t)n * o->r * sizeof(T), hipMemcpyHostToDevice, st));
+    if (Ad) HIP_TRY(hipMemcpyAsync(o->rs_A, Ad, (size_t)n * nA * sizeof(T), hipMemcpyHostToDevice, st));
+    ORestartCommon<T> a{};
+    a.slots = o->rs_slots; a.Bx = o->Bxd; a.sBx = sBx; a.Bd = Bd ? o->rs_B : nullptr; a.H0n = H0 ? o->rs_H : nullptr;
+    a.Adn = Ad ? o->rs_A : nullptr; a.B = o->B; a.Bfix = o->Bfix; a.H0 = o->H0; a.Ad0 = o->Ad0; a.adblk = o->adblk; a.ldblk = o->ldblk;
+    a.lambda_dav = o->lambda_dav; a.Xm_tilde = o->Xm_tilde; a.r_blk = o->r_blk; a.tail = o->tail; a.tail_x = o->tail_x;
+    a.tail_d = o->tail_d; a.rup = o->rup; a.dev = o->dev;
+    a.F = o->F; a.r = o->r; a.Rx = p.R_x; a.Rd = p.R_d; a.Ra = o->Ra; a.ma = o->ma; a.Pl = o->Pl; a.ntail = (int64_t)o->ntail;
+    launch(a);
+    HIP_TRY(hipGetLastError());
+    for (int i = 0; i < n && o->tail_c; ++i)  // the class tails of the stream, like tail_x / tail_d: one strided fill over its classes
+        HIP_TRY(hipMemset2DAsync(o->tail_c + (size_t)slots[i] * o->ntail, (size_t)o->S * o->ntail * sizeof(T), 0, o->ntail * sizeof(T),
+                                 (size_t)o->n_cls, st));
+    SN_TRY(obm_state_refresh(o, n));
+    obatch_restart_host(o, n, slots);
+    return SNMF_OK;
+}
+
 template <class H>
 int obatch_trace(const H* o, int32_t k, snmf_online_frame* out, int64_t cap, int64_t* n) {
     if (k < 0 || k >= o->S) return fail(SNMF_ERR_INVALID, "stream %d out of range [0, %d)", k, o->S);
@@ -272,17 +325,36 @@ int obatch_run_chunk(H* o, const std::vector<int>& nfr, const std::vector<int>& 
             SN_TRY(obm_adapt(o, fr, i));
         }
     }
-    // inverse STFT behind each stream's kept frames, overlap-add
+    // the synthesis of one signal: k_obtail (0: the streams' tails into the buffer's head), k_obistft behind each stream's
+    // kept frames, k_obola to the output hops, k_obtail (1: the tails back out)
     const int64_t syn_stride = (int64_t)(C + nov - 1) * sz;
+    const size_t lds_fft = obm_lds_fft(o);
+    OIstftArgsT<T> ia{};
+    ia.ph = o->Yph; ia.ld = F; ia.n_frames = C; ia.sz = sz; ia.dcb = p.dcbin_back; ia.powv = (T)p.pow;
+    ia.scale = (T)(p.overlapscale / (double)o->N); ia.preemph = (T)p.preemph; ia.win = o->win_i; ia.tw = o->tw; ia.syn = o->syn;
+    auto move_tail = [&](T* tail, int store) -> int {
+        if (nov > 1) hipLaunchKernelGGL(k_obtail<T>, dim3(S), dim3(256), 0, st, o->syn, tail, fr.nfr, syn_stride, nov, sz, store);
+        HIP_TRY(hipGetLastError());
+        return SNMF_OK;
+    };
     auto synth = [&](const T* mag, T* tail, T* of, int16_t* o16) -> int {
-        if (nov > 1) SN_TRY(obm_tail(o, tail, fr, syn_stride, 0));
-        SN_TRY(obm_istft(o, mag, fr, C, syn_stride));
+        SN_TRY(move_tail(tail, 0));
+        ia.mag = mag;
+        int rc = SNMF_OK;
+        by_logn([&](auto L) {
+            constexpr int LOGN = decltype(L)::value;
+            if (lds_fft) rc = ensure_dyn_lds(o->ctx->device, (const void*)k_obistft<LOGN, T>, lds_fft);
+            if (rc == SNMF_OK) hipLaunchKernelGGL((k_obistft<LOGN, T>), dim3(C, S), dim3(256), lds_fft, st, ia, fr.nfr, S, syn_stride, nov);
+        }, o->N);
+        SN_TRY(rc);
+        HIP_TRY(hipGetLastError());
         if (n_out > 0) {
             const int gx = std::max(1, std::min(64, (int)((size_t)C * hop / 256 + 1)));
-            SN_TRY(obm_ola(o, gx, fr, syn_stride, d_if, d_no, d_oo, of, o16));
+            hipLaunchKernelGGL(k_obola<T>, dim3(gx, S), dim3(256), 0, st, (const T*)o->syn, syn_stride, fr, d_if, d_no, d_oo, p.delay, sz, hop,
+                               nov, of, o16);
+            HIP_TRY(hipGetLastError());
         }
-        if (nov > 1) SN_TRY(obm_tail(o, tail, fr, syn_stride, 1));
-        return SNMF_OK;
+        return move_tail(tail, 1);
     };
     // the three signals go to the thirds of outf: x_tilde, x_hat, d_hat
     std::vector<T> hf, hx, hd;
@@ -529,8 +601,7 @@ OStateArgs<T> obatch_state_args(H* o, const snmf_online_state_info& q) {
     a.B = o->B; a.Bfix = o->Bfix; a.dev = o->dev;
     a.S = o->S; a.F = o->F; a.r = o->r; a.Rx = o->p.R_x; a.Rd = o->p.R_d; a.Ra = o->Ra; a.ma = o->ma; a.Pl = o->Pl; a.n_cls = o->n_cls;
     a.ntail = (int64_t)o->ntail;
-    obm_state_arrays(o, a);
-    return a;
+    return a;  // Bm, Bdf and n1 stay NULL / 0 here: DFT mode.  The fp32 unit's obm_state_launch sets them in Mel mode.
 }
 
 template <class H>

@@ -14,21 +14,14 @@ struct snmf_online_batch : OBatchState<float> {
     int Fs = 0;                                // rows of the solves: F, or F_order in Mel mode
     int mel = 0, mel_conv = 0, n1 = 0;         // B_sep_mode = 'Mel' (snmf_online_batch_set_mel)
     snmf_plan* hp = nullptr;  // the frame solve's geometry, sparsity and beta (one plan serves every stream)
-    // per stream, device
-    double *B = nullptr, *Bfix = nullptr, *Btmp = nullptr, *wn = nullptr, *Wu = nullptr;
-    float *Wcf = nullptr, *wx = nullptr, *dphv = nullptr, *Hin = nullptr, *H0 = nullptr, *Ad0 = nullptr;
-    float *lambda_dav = nullptr, *Xm_tilde = nullptr, *r_blk = nullptr, *ldblk = nullptr, *adblk = nullptr;
+    // per stream, device: the frame solve's images of the dictionary (k_obrefresh), k_wadapt_batch's result and scratch
+    double *wn = nullptr, *Wu = nullptr;
+    float *Wcf = nullptr, *wx = nullptr, *dphv = nullptr, *Hin = nullptr;
     float *G = nullptr, *P = nullptr, *Vt = nullptr;
-    float *win_s = nullptr, *win_i = nullptr;
-    float2* tw = nullptr;
-    double* Bxd = nullptr;  // B_DFT_x in fp64, shared
     // Mel mode: melmat [n1][F] and B_Mel_x [Rx][n1] (fp64) shared; per stream the fp64 Mel master [r][n1], the adaptation's
     // melmat * lambda_d_blk [ma][n1] and, with MelConv = 0, the fp32 [B_DFT_x | B_DFT_d] [r][F]
     float *melmat = nullptr, *Vm = nullptr, *Bdf = nullptr;
-    double *Bmx = nullptr, *Bm = nullptr, *rs_Bm = nullptr;
-    // restart uploads (sized for all S streams)
-    double* rs_B = nullptr;
-    float *rs_H = nullptr, *rs_A = nullptr;
+    double *Bmx = nullptr, *Bm = nullptr, *rs_Bm = nullptr;  // (rs_Bm: the restart upload of B_Mel_d, sized for all S streams)
     // per chunk, device (obm_reserve): the solve's input, Mel features, activations, reconstructions (Fs rows), state and histories
     float *Vp = nullptr, *Ymel = nullptr, *Hout = nullptr, *reco = nullptr;
     DevState* st = nullptr;
@@ -73,11 +66,8 @@ extern "C" void snmf_online_batch_destroy(snmf_online_batch* o) {
     hipSetDevice(o->ctx->device);
     hipStreamSynchronize(o->ctx->stream);
     if (o->hp) snmf_plan_destroy(o->hp);
-    obatch_free_chunk(o);
-    void* ptrs[] = {o->B, o->Bfix, o->Btmp, o->wn, o->Wu, o->Wcf, o->wx, o->dphv, o->Hin, o->H0, o->Ad0, o->lambda_dav, o->Xm_tilde,
-                    o->r_blk, o->ldblk, o->adblk, o->G, o->P, o->Vt, o->tail, o->tail_x, o->tail_d, o->rup, o->dev, o->win_s,
-                    o->win_i, o->tw, o->Bxd, o->rs_slots, o->rs_B, o->rs_H, o->rs_A, o->meta_i, o->meta_l, o->melmat, o->Vm, o->Bdf,
-                    o->Bmx, o->Bm, o->rs_Bm, o->cls, o->tail_c, o->st_slab};
+    obatch_free_state(o);
+    void* ptrs[] = {o->wn, o->Wu, o->Wcf, o->wx, o->dphv, o->Hin, o->G, o->P, o->Vt, o->melmat, o->Vm, o->Bdf, o->Bmx, o->Bm, o->rs_Bm};
     for (void* q : ptrs)
         if (q) hipFree(q);
     delete o;
@@ -125,36 +115,20 @@ static int obm_state_refresh(snmf_online_batch* o, int n) {
     return SNMF_OK;
 }
 
-// The streams slots[0..n) start a new recording (src/NTF_sep_event_RT.m:27-38 + src/init_buff.m): the uploads, one
-// k_obrestart, one k_obrefresh over their columns, and their host state.  Arguments are checked by the caller; Bd is
-// n x Rd x F fp64 or NULL (carry), Bmd (Mel mode) n x Rd x n1 fp64 or NULL (carry), H0 n x r or NULL, Ad n x Ra x ma or
-// NULL.  Ordered on ctx->stream, no synchronise (the uploads come from pageable host memory, which the runtime copies
-// before it returns).
+// The streams slots[0..n) start a new recording (obatch_restart): the fp32 mode's own are the upload of the new B_Mel_d and,
+// around the shared arguments, the frame solve's images and the Mel masters.  Arguments are checked by the caller; Bmd
+// (Mel mode) is n x Rd x n1 fp64 or NULL (carry).
 static int ob_restart(snmf_online_batch* o, int n, const int32_t* slots, const double* Bd, const double* Bmd, const float* H0,
                       const float* Ad) {
-    const snmf_online_params& p = o->p;
     hipStream_t st = o->ctx->stream;
-    const size_t F = o->F, nA = (size_t)o->Ra * o->ma;
-    HIP_TRY(hipMemcpyAsync(o->rs_slots, slots, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    if (Bd) HIP_TRY(hipMemcpyAsync(o->rs_B, Bd, (size_t)n * p.R_d * F * 8, hipMemcpyHostToDevice, st));
-    if (Bmd) HIP_TRY(hipMemcpyAsync(o->rs_Bm, Bmd, (size_t)n * p.R_d * o->n1 * 8, hipMemcpyHostToDevice, st));
-    if (H0) HIP_TRY(hipMemcpyAsync(o->rs_H, H0, (size_t)n * o->r * 4, hipMemcpyHostToDevice, st));
-    if (Ad) HIP_TRY(hipMemcpyAsync(o->rs_A, Ad, (size_t)n * nA * 4, hipMemcpyHostToDevice, st));
-    ORestartArgs a{};
-    a.slots = o->rs_slots; a.Bx = o->Bxd; a.Bd = Bd ? o->rs_B : nullptr; a.H0n = H0 ? o->rs_H : nullptr; a.Adn = Ad ? o->rs_A : nullptr;
-    a.B = o->B; a.Bfix = o->Bfix; a.H0 = o->H0; a.Ad0 = o->Ad0; a.adblk = o->adblk; a.ldblk = o->ldblk; a.lambda_dav = o->lambda_dav;
-    a.Xm_tilde = o->Xm_tilde; a.r_blk = o->r_blk; a.tail = o->tail; a.tail_x = o->tail_x; a.tail_d = o->tail_d; a.rup = o->rup;
-    a.dev = o->dev; a.Wcf = o->Wcf; a.wx = o->wx; a.dphv = o->dphv; a.Hin = o->Hin; a.wn = o->wn;
-    a.F = o->F; a.r = o->r; a.Rx = p.R_x; a.Rd = p.R_d; a.Ra = o->Ra; a.ma = o->ma; a.Pl = o->Pl; a.rp = o->hp->rp; a.Fp = o->hp->Fp;
-    a.adapt = p.adapt_train_N; a.ntail = (int64_t)o->ntail;
-    a.Bmx = o->Bmx; a.Bmd = Bmd ? o->rs_Bm : nullptr; a.Bm = o->Bm; a.Bdf = o->Bdf; a.n1 = o->n1;
-    hipLaunchKernelGGL(k_obrestart, dim3(n, kRsN, kRsParts), dim3(256), 0, st, a);
-    HIP_TRY(hipGetLastError());
-    for (int i = 0; i < n && o->tail_c; ++i)  // the class tails of the stream, like tail_x / tail_d: one strided fill over its classes
-        HIP_TRY(hipMemset2DAsync(o->tail_c + (size_t)slots[i] * o->ntail, (size_t)o->S * o->ntail * 4, 0, o->ntail * 4, (size_t)o->n_cls, st));
-    SN_TRY(obm_state_refresh(o, n));
-    obatch_restart_host(o, n, slots);
-    return SNMF_OK;
+    if (Bmd) HIP_TRY(hipMemcpyAsync(o->rs_Bm, Bmd, (size_t)n * o->p.R_d * o->n1 * 8, hipMemcpyHostToDevice, st));
+    return obatch_restart(o, n, slots, Bd, H0, Ad, 0, [&](const ORestartCommon<float>& c) {
+        ORestartArgs a{};
+        a.c = c; a.Wcf = o->Wcf; a.wx = o->wx; a.dphv = o->dphv; a.Hin = o->Hin; a.wn = o->wn;
+        a.Bmx = o->Bmx; a.Bmd = Bmd ? o->rs_Bm : nullptr; a.Bm = o->Bm; a.Bdf = o->Bdf;
+        a.rp = o->hp->rp; a.Fp = o->hp->Fp; a.adapt = o->p.adapt_train_N; a.n1 = o->n1;
+        hipLaunchKernelGGL(k_obrestart, dim3(n, kRsN, kRsParts), dim3(256), 0, st, a);
+    });
 }
 
 // the frame solve's plan: rows x 1, rank r, H-only (its register-resident kernel must admit the shape)
@@ -501,34 +475,7 @@ static int obm_post(snmf_online_batch* o, const OBatchFrames& fr, int step) {
     return SNMF_OK;
 }
 
-// the synthesis of one signal: k_obtail (store = 0: the stream's tail into the buffer's head; 1: back out), k_obistft, k_obola
-static int obm_tail(snmf_online_batch* o, float* tail, const OBatchFrames& fr, int64_t syn_stride, int store) {
-    hipLaunchKernelGGL(k_obtail, dim3(o->S), dim3(256), 0, o->ctx->stream, o->syn, tail, fr.nfr, syn_stride, o->nov, o->p.framelength, store);
-    HIP_TRY(hipGetLastError());
-    return SNMF_OK;
-}
-
-static int obm_istft(snmf_online_batch* o, const float* mag, const OBatchFrames& fr, int C, int64_t syn_stride) {
-    const snmf_online_params& p = o->p;
-    const int S = o->S, nov = o->nov;
-    hipStream_t st = o->ctx->stream;
-    OIstftArgs ia{};
-    ia.mag = mag; ia.ph = o->Yph; ia.ld = o->F; ia.n_frames = C; ia.sz = p.framelength; ia.dcb = p.dcbin_back; ia.powv = (float)p.pow;
-    ia.scale = (float)(p.overlapscale / (double)o->N); ia.preemph = (float)p.preemph; ia.win = o->win_i; ia.tw = o->tw; ia.syn = o->syn;
-    by_logn([&](auto L) { hipLaunchKernelGGL(k_obistft<decltype(L)::value>, dim3(C, S), dim3(256), 0, st, ia, fr.nfr, S, syn_stride, nov); },
-               o->N);
-    HIP_TRY(hipGetLastError());
-    return SNMF_OK;
-}
-
-static int obm_ola(snmf_online_batch* o, int gx, const OBatchFrames& fr, int64_t syn_stride, const int* d_if, const int* d_no,
-                   const int64_t* d_oo, float* of, int16_t* o16) {
-    const snmf_online_params& p = o->p;
-    hipLaunchKernelGGL(k_obola, dim3(gx, o->S), dim3(256), 0, o->ctx->stream, (const float*)o->syn, syn_stride, fr, d_if, d_no, d_oo, p.delay,
-                       p.framelength, p.frameshift, o->nov, of, o16);
-    HIP_TRY(hipGetLastError());
-    return SNMF_OK;
-}
+static size_t obm_lds_fft(const snmf_online_batch*) { return 0; }  // k_obistft<LOGN, float>'s FFT buffers are static LDS
 
 // snmf_online_batch_process_f32 / snmf_online_batch_process_classes_f32 (xhi_f32 / dhi_f32: the class signals, class-major at cap[s])
 static int ob_process(snmf_online_batch* o, const float* const* pcm, const int64_t* n, const int32_t* flush, float* const* xt_f32,
@@ -670,13 +617,12 @@ static void obm_state_mode(const snmf_online_batch* o, int* mel, int* mel_conv, 
     *n1 = o->n1;
 }
 
-static void obm_state_arrays(snmf_online_batch* o, OStateArgs<float>& a) {
+// the record's B_Mel_d and the fp32 image of its B_DFT_d go to the Mel masters
+static int obm_state_launch(snmf_online_batch* o, const OStateArgs<float>& a0, int n, bool put) {
+    OStateArgs<float> a = a0;
     a.Bm = o->mel ? o->Bm : nullptr;
     a.Bdf = o->Bdf;  // (allocated only in Mel mode with MelConv = 0)
     a.n1 = o->n1;
-}
-
-static int obm_state_launch(snmf_online_batch* o, const OStateArgs<float>& a, int n, bool put) {
     if (put) hipLaunchKernelGGL(k_obstate_put, dim3(n, kStN, kStParts), dim3(256), 0, o->ctx->stream, a);
     else hipLaunchKernelGGL(k_obstate_get, dim3(n, kStN, kStParts), dim3(256), 0, o->ctx->stream, a);
     HIP_TRY(hipGetLastError());

@@ -16,14 +16,8 @@ constexpr double kFlr64 = 1e-9;            // src/sparse_nmf.m:166, as a double
 
 struct OnlineBatchF64 : OBatchState<double> {
     // per stream, device
-    double *B = nullptr, *Bfix = nullptr, *Btmp = nullptr;                   // [B_DFT_x | B_DFT_d], the dictionary each stream started with, scratch
     double *Wn = nullptr, *WnT = nullptr, *wn = nullptr, *csum = nullptr;    // images of the frame solve (k_obrefresh64)
-    double *H0 = nullptr, *Ad0 = nullptr, *lambda_dav = nullptr, *Xm_tilde = nullptr, *r_blk = nullptr, *ldblk = nullptr, *adblk = nullptr;
     double *Wu = nullptr, *Wm = nullptr, *Q = nullptr, *P = nullptr, *Vt = nullptr;  // k_wadapt_batch64's result and scratch
-    double* Bxd = nullptr;                                      // [S][R_x][F] every stream's event dictionary, as it starts a recording
-    double *win_s = nullptr, *win_i = nullptr;                  // shared
-    double2* tw = nullptr;
-    double *rs_B = nullptr, *rs_H = nullptr, *rs_A = nullptr;  // restart uploads (sized for all S streams)
     // per chunk, device (obm_reserve): the frame solves' activations, reconstructions and iteration counts
     double *A = nullptr, *reco = nullptr;
     int* nit = nullptr;
@@ -136,7 +130,7 @@ static void b64_publish_adapt(OnlineBatchF64* o) {
     for (size_t k = 0; k < o->hset.size(); ++k) o->adapt_s[k] = (uint8_t)o->hset[k].adapt_train_N;
 }
 
-static size_t b64_lds_fft(const OnlineBatchF64* o) { return (size_t)2 * o->N * sizeof(double2); }
+static size_t obm_lds_fft(const OnlineBatchF64* o) { return (size_t)2 * o->N * sizeof(double2); }  // the driver's hook, and k_obstft64's
 static size_t b64_lds_solve(const OnlineBatchF64* o) { return (size_t)(4 * o->F + 3 * o->r + 32) * 8; }
 static size_t b64_lds_post(const OnlineBatchF64* o) { return (size_t)(o->r + 6 * o->F) * 8; }
 
@@ -164,10 +158,8 @@ void online_batch_f64_destroy(OnlineBatchF64* o) {
     if (!o) return;
     hipSetDevice(o->ctx->device);
     hipStreamSynchronize(o->ctx->stream);
-    obatch_free_chunk(o);
-    void* ptrs[] = {o->B, o->Bfix, o->Btmp, o->Wn, o->WnT, o->wn, o->csum, o->H0, o->Ad0, o->lambda_dav, o->Xm_tilde, o->r_blk, o->ldblk,
-                    o->adblk, o->Wu, o->Wm, o->Q, o->P, o->Vt, o->tail, o->tail_x, o->tail_d, o->rup, o->dev, o->win_s, o->win_i, o->Bxd,
-                    o->tw, o->rs_slots, o->rs_B, o->rs_H, o->rs_A, o->cls, o->tail_c, o->meta_i, o->meta_l, o->set, o->st_slab};
+    obatch_free_state(o);
+    void* ptrs[] = {o->Wn, o->WnT, o->wn, o->csum, o->Wu, o->Wm, o->Q, o->P, o->Vt, o->set};
     for (void* q : ptrs)
         if (q) hipFree(q);
     delete o;
@@ -184,14 +176,13 @@ static int obm_state_refresh(OnlineBatchF64* o, int n) {
     return SNMF_OK;
 }
 
-// The streams slots[0..n) start a new recording (ob_restart of snmf_tu_online_batch.hip): the uploads, one k_obrestart64, one
-// k_obrefresh64 over their columns, and their host state.  Ordered on ctx->stream, no synchronise.  Bx: n x Rx x F, the listed
-// streams' new event dictionaries, or NULL = each keeps its own; the settings table holds the listed streams' entries already.
-// Ad (n x Ra x ma) is read only when one of the listed streams adapts.
+// The streams slots[0..n) start a new recording (obatch_restart): the fp64 mode's own are the listed streams' settings entries
+// (the host table holds them already) and event dictionaries, uploaded ahead of the restart kernel, and has_ad0.  Bx: n x Rx x F,
+// the listed streams' new event dictionaries, or NULL = each keeps its own.  Ad (n x Ra x ma) is read only when one of the
+// listed streams adapts.
 static int b64_restart(OnlineBatchF64* o, int n, const int32_t* slots, const double* Bx, const double* Bd, const double* H0, const double* Ad) {
-    const snmf_online_params& p = o->p;
     hipStream_t st = o->ctx->stream;
-    const size_t F = o->F, nA = (size_t)o->Ra * o->ma, nX = (size_t)p.R_x * F;
+    const size_t nX = (size_t)o->p.R_x * o->F;
     bool adapts = false;
     for (int i = 0; i < n; ++i) adapts |= o->hset[slots[i]].adapt_train_N != 0;
     if (!adapts) Ad = nullptr;
@@ -200,23 +191,9 @@ static int b64_restart(OnlineBatchF64* o, int n, const int32_t* slots, const dou
         if (Bx) HIP_TRY(hipMemcpyAsync(o->Bxd + (size_t)slots[i] * nX, Bx + (size_t)i * nX, nX * 8, hipMemcpyHostToDevice, st));
         if (Ad) o->has_ad0[slots[i]] = 1;
     }
-    HIP_TRY(hipMemcpyAsync(o->rs_slots, slots, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    if (Bd) HIP_TRY(hipMemcpyAsync(o->rs_B, Bd, (size_t)n * p.R_d * F * 8, hipMemcpyHostToDevice, st));
-    if (H0) HIP_TRY(hipMemcpyAsync(o->rs_H, H0, (size_t)n * o->r * 8, hipMemcpyHostToDevice, st));
-    if (Ad) HIP_TRY(hipMemcpyAsync(o->rs_A, Ad, (size_t)n * nA * 8, hipMemcpyHostToDevice, st));
-    ORestart64Args a{};
-    a.slots = o->rs_slots; a.Bx = o->Bxd; a.set = o->set; a.Bd = Bd ? o->rs_B : nullptr; a.H0n = H0 ? o->rs_H : nullptr; a.Adn = Ad ? o->rs_A : nullptr;
-    a.B = o->B; a.Bfix = o->Bfix; a.H0 = o->H0; a.Ad0 = o->Ad0; a.adblk = o->adblk; a.ldblk = o->ldblk; a.lambda_dav = o->lambda_dav;
-    a.Xm_tilde = o->Xm_tilde; a.r_blk = o->r_blk; a.tail = o->tail; a.tail_x = o->tail_x; a.tail_d = o->tail_d; a.rup = o->rup;
-    a.dev = o->dev; a.F = o->F; a.r = o->r; a.Rx = p.R_x; a.Rd = p.R_d; a.Ra = o->Ra; a.ma = o->ma; a.Pl = o->Pl;
-    a.ntail = (int64_t)o->ntail;
-    hipLaunchKernelGGL(k_obrestart64, dim3(n, kRs64N, kRs64Parts), dim3(256), 0, st, a);
-    HIP_TRY(hipGetLastError());
-    for (int i = 0; i < n && o->tail_c; ++i)  // the class tails of the stream, like tail_x / tail_d: one strided fill over its classes
-        HIP_TRY(hipMemset2DAsync(o->tail_c + (size_t)slots[i] * o->ntail, (size_t)o->S * o->ntail * 8, 0, o->ntail * 8, (size_t)o->n_cls, st));
-    SN_TRY(obm_state_refresh(o, n));
-    obatch_restart_host(o, n, slots);
-    return SNMF_OK;
+    return obatch_restart(o, n, slots, Bd, H0, Ad, (int64_t)nX, [&](const ORestartCommon<double>& a) {
+        hipLaunchKernelGGL(k_obrestart64, dim3(n, kRsShared, kRsParts), dim3(256), 0, st, a, (const OStreamSettings*)o->set);
+    });
 }
 
 int online_batch_f64_create(snmf_ctx* ctx, const snmf_online_params* p, int32_t S, const double* Bx, int bx_per_stream, const double* Bd0,
@@ -237,7 +214,7 @@ int online_batch_f64_create(snmf_ctx* ctx, const snmf_online_params* p, int32_t 
     o->has_ad0.assign((size_t)S, 0);
     const B64Needs nd = b64_needs(o->hset);
     int s = SNMF_OK;
-    if (b64_lds_fft(o) > ctx->lds_max || b64_lds_solve(o) > ctx->lds_max || b64_lds_post(o) > ctx->lds_max)
+    if (obm_lds_fft(o) > ctx->lds_max || b64_lds_solve(o) > ctx->lds_max || b64_lds_post(o) > ctx->lds_max)
         s = fail(SNMF_ERR_UNSUPPORTED, "fp64 batched separator: fftlength %d with R_x + R_d = %d does not fit the LDS (%zu bytes)", N, r,
                  ctx->lds_max);
     if (s == SNMF_OK) s = b64_check_ring(ctx, *p, nd);
@@ -367,7 +344,7 @@ static int obm_begin_chunk(OnlineBatchF64* o, const OBatchFrames& fr, int C) {
     const snmf_online_params& p = o->p;
     const int S = o->S;
     hipStream_t st = o->ctx->stream;
-    const size_t lds_fft = b64_lds_fft(o);
+    const size_t lds_fft = obm_lds_fft(o);
     OStftArgsT<double> sa{};
     sa.sig = o->sig; sa.sz = p.framelength; sa.hop = p.frameshift; sa.dcbin = p.dcbin; sa.preemph = p.preemph; sa.win = o->win_s; sa.tw = o->tw;
     sa.powv = p.pow; sa.floorv = p.nonzerofloor; sa.Ym = o->Ym; sa.Yph = o->Yph; sa.ld = o->F; sa.n_frames = C;
@@ -393,40 +370,6 @@ static int obm_begin_chunk(OnlineBatchF64* o, const OBatchFrames& fr, int C) {
 static int obm_post(OnlineBatchF64* o, const OBatchFrames& fr, int step) {
     hipLaunchKernelGGL(k_obpost64, dim3(o->S), dim3(1024), b64_lds_post(o), o->ctx->stream, o->post_a, (const OStreamSettings*)o->set, fr,
                        step);
-    HIP_TRY(hipGetLastError());
-    return SNMF_OK;
-}
-
-// the synthesis of one signal: k_obtail64 (store = 0: the stream's tail into the buffer's head; 1: back out), k_obistft64, k_obola64
-static int obm_tail(OnlineBatchF64* o, double* tail, const OBatchFrames& fr, int64_t syn_stride, int store) {
-    hipLaunchKernelGGL(k_obtail64, dim3(o->S), dim3(256), 0, o->ctx->stream, o->syn, tail, fr.nfr, syn_stride, o->nov, o->p.framelength, store);
-    HIP_TRY(hipGetLastError());
-    return SNMF_OK;
-}
-
-static int obm_istft(OnlineBatchF64* o, const double* mag, const OBatchFrames& fr, int C, int64_t syn_stride) {
-    const snmf_online_params& p = o->p;
-    const int S = o->S, nov = o->nov;
-    hipStream_t st = o->ctx->stream;
-    const size_t lds_fft = b64_lds_fft(o);
-    OIstftArgsT<double> ia{};
-    ia.mag = mag; ia.ph = o->Yph; ia.ld = o->F; ia.n_frames = C; ia.sz = p.framelength; ia.dcb = p.dcbin_back; ia.powv = p.pow;
-    ia.scale = p.overlapscale / (double)o->N; ia.preemph = p.preemph; ia.win = o->win_i; ia.tw = o->tw; ia.syn = o->syn;
-    int rc = SNMF_OK;
-    by_logn([&](auto L) {
-        rc = ensure_dyn_lds(o->ctx->device, (const void*)k_obistft64<decltype(L)::value>, lds_fft);
-        if (rc == SNMF_OK) hipLaunchKernelGGL(k_obistft64<decltype(L)::value>, dim3(C, S), dim3(256), lds_fft, st, ia, fr.nfr, S, syn_stride, nov);
-    }, o->N);
-    SN_TRY(rc);
-    HIP_TRY(hipGetLastError());
-    return SNMF_OK;
-}
-
-static int obm_ola(OnlineBatchF64* o, int gx, const OBatchFrames& fr, int64_t syn_stride, const int* d_if, const int* d_no, const int64_t* d_oo,
-                   double* of, int16_t* o16) {
-    const snmf_online_params& p = o->p;
-    hipLaunchKernelGGL(k_obola64, dim3(gx, o->S), dim3(256), 0, o->ctx->stream, (const double*)o->syn, syn_stride, fr, d_if, d_no, d_oo, p.delay,
-                       p.framelength, p.frameshift, o->nov, of, o16);
     HIP_TRY(hipGetLastError());
     return SNMF_OK;
 }
@@ -492,12 +435,6 @@ int online_batch_f64_trace(OnlineBatchF64* o, int32_t k, snmf_online_frame* out,
 
 // ---- get-state / set-state (the driver's section in snmf_online_batch_host.h; kernels k_obstate_get64 / k_obstate_put64) ----
 static void obm_state_mode(const OnlineBatchF64*, int* mel, int* mel_conv, int* n1) { *mel = *mel_conv = *n1 = 0; }  // DFT mode only
-
-static void obm_state_arrays(OnlineBatchF64*, OStateArgs<double>& a) {
-    a.Bm = nullptr;
-    a.Bdf = nullptr;
-    a.n1 = 0;
-}
 
 static int obm_state_launch(OnlineBatchF64* o, const OStateArgs<double>& a, int n, bool put) {
     if (put) hipLaunchKernelGGL(k_obstate_put64, dim3(n, kStN, kStParts), dim3(256), 0, o->ctx->stream, a);

@@ -236,7 +236,7 @@ def test_variants_match_the_oracle(gpu_ctx, var):
 
 
 GEO_CASES = [
-    # a small transform (F = 65: 16 row blocks and one row; k_obstft64 / k_obistft64 at LOGN 7) with a short ring: R_a = 8 of
+    # a small transform (F = 65: 16 row blocks and one row; k_obstft64 / k_obistft<LOGN, double> at LOGN 7) with a short ring: R_a = 8 of
     # 64 column lanes, m_a = 12: one trip of the frame loop
     ((128, 100, 25, 16, 20, dict(P_len_k=12, P_len_l=5, init_N_len=5, DCbin=2, DCbin_back=2, R_a=8, m_a=12, overlap_m_a=0.1)), 36),
     # the ring at the envelope's edge at the shipped transform (F = 513 = 128 row blocks and one row): R_a = 64 fills the
