@@ -18,6 +18,10 @@ as well (snmf_batch_create_settings_fp64): a list of settings dicts for sparse_n
 divergence, sparsity weight, max_iter and conv_eps of its own for every problem, so that a sweep over them is one batch;
 cost_check, floor_v and the masks stay shared.  All arithmetic happens in libsnmf_hip.so on the GPU;
 this module does the reference's defaulting and its own errors (src/sparse_nmf.m:75-164, :260) on the host, before any device call.
+Every host rule has one statement, shared by all forms and by train.py: the problem list (_problem_arrays, _row_count), ints per
+problem (_ints_per_problem), rank and initial factors of a problem (_rank_and_init_w, _init_h; _batch_inits for the dict forms),
+the draws (_batch_draws), settings per problem (_problem_settings, _settings_array), the solve through the handle
+(_solve_through_handle).
 """
 from __future__ import annotations
 
@@ -59,17 +63,26 @@ def _h_ind_all_or_none(p, r):
     return h_ind
 
 
-def _rank_list(r, B):
-    """A rank per problem given as a sequence -> a list of B ints (its own errors); anything else -> None."""
-    if isinstance(r, (str, bytes)) or not isinstance(r, (list, tuple, np.ndarray)) or (isinstance(r, np.ndarray) and r.ndim == 0):
+def _is_seq(x):
+    return isinstance(x, (list, tuple)) or (isinstance(x, np.ndarray) and x.ndim > 0)
+
+
+def _at_least_1(v, k, name):
+    if v < 1:
+        raise SnmfError(1, f"{name} of problem {k} is {v} (at least 1)")
+
+
+def _ints_per_problem(x, n, name):
+    """An int per problem (a rank, a dictionary size) given as a sequence -> the list of n ints, none below 1; anything that is
+    no sequence (an int, None, a 0-d array) -> None.  Its own errors: a length that is not n (3), an entry below 1 (1)."""
+    if not _is_seq(x):
         return None
-    rs = [int(x) for x in np.asarray(r).reshape(-1)]
-    if len(rs) != B:
-        raise SnmfError(3, f"r is a list of {len(rs)}, the batch has {B} problems")
-    for k, x in enumerate(rs):
-        if x < 1:
-            raise SnmfError(1, f"problem {k} has rank {x} (at least 1)")
-    return rs
+    xs = [int(v) for v in np.asarray(x).reshape(-1)]
+    if len(xs) != n:
+        raise SnmfError(3, f"{name} is a list of {len(xs)}, the batch has {n} problems")
+    for k, v in enumerate(xs):
+        _at_least_1(v, k, name)
+    return xs
 
 
 def _mixed_rank_rules(sparsity, masks):
@@ -139,78 +152,93 @@ def _objective(div, cost, ni, max_iter, cost_check):
     return {"div": np.zeros(max_iter), "cost": np.zeros(max_iter), "n_iter": ni}
 
 
-def _batch_inits(p, vs, m, per_problem=False):
-    """src/sparse_nmf.m:116-140 for a batch: the list forms of init_w / init_h -> (r, init_w per problem or None, init_h list or None).
-    per_problem (the fp64 batch): p["r"] may be a list and the init_w arrays may differ in width; :116-131 is then applied to
-    every problem on its own and r is the list of the problems' ranks.  Otherwise one rank, as an int, and differing ranks are
-    SnmfError status 3."""
-    B = len(vs)
-    iw = p.get("init_w", None)
-    prs = _rank_list(p.get("r", None), B)
-    if prs is not None and not per_problem:
-        if len(set(prs)) > 1:
-            raise SnmfError(3, f"r is {prs}: a batch shares the rank")
-        p = dict(p, r=prs[0])
-    if per_problem:
-        if prs is None and p.get("r", None) is not None:
-            prs = [int(p["r"])] * B
-        if iw is None:
-            if prs is None:
-                raise SnmfError(2, "Number of components or initialization must be given")
-            iws = [None] * B
-            rs = list(prs)
-        else:
-            if isinstance(iw, (list, tuple)):
-                if len(iw) != B:
-                    raise SnmfError(3, f"init_w is a list of {len(iw)}, the batch has {B} problems")
-                iws = [np.asarray(x, dtype=np.float64) for x in iw]
-            else:
-                iws = [np.asarray(iw, dtype=np.float64)] * B
-            for x in iws:
-                if x.ndim != 2 or x.shape[0] != m or x.shape[1] < 1:
-                    raise SnmfError(3, f"init_w is {x.shape}, v has {m} rows")
-            rs = [prs[k] if (prs is not None and x.shape[1] < prs[k]) else x.shape[1] for k, x in enumerate(iws)]  # :123-130
-        return rs, iws, _batch_init_h(p, vs, rs)
+def _problem_arrays(vs, what="v"):
+    """The problems of a batch as a list of arrays, at least one (SnmfError status 1)."""
+    vs = [np.asarray(v) for v in vs]
+    if not vs:
+        raise SnmfError(1, f"the batch is empty: {what}s must hold at least one matrix")
+    return vs
+
+
+def _row_count(vs, what="v", masks=None):
+    """The problem-list check: every problem a 2-D matrix with at least one column (status 1) -- and, where the problems have
+    masks, a mask of its own shape (3) -- and one row count for all (3) -> that row count."""
+    for k, v in enumerate(vs):
+        if v.ndim != 2 or v.shape[1] < 1:
+            raise SnmfError(1, f"every {what} must be a 2-D matrix with at least one column")
+        if masks is not None and masks[k].shape != v.shape:
+            raise SnmfError(3, f"the mask of problem {k} is {masks[k].shape}, its {what} is {v.shape}")
+    m = vs[0].shape[0]  # src/sparse_nmf.m:71
+    for k, v in enumerate(vs):
+        if v.shape[0] != m:
+            raise SnmfError(3, f"{what} of problem {k} has {v.shape[0]} rows, problem 0 has {m}: a batch shares the row count")
+    return m
+
+
+def _rank_and_init_w(m, r, iw, empty_ok=False):
+    """src/sparse_nmf.m:116-131 for one problem: its r (or None) and init_w (or None) -> (rank, init_w as float64 or None).  The
+    rank is init_w's width, or r where that is larger (the missing columns are drawn).  empty_ok: an init_w without a column
+    counts as one (the engines with one rank take :123-130 as it stands); otherwise it is status 3."""
     if iw is None:
-        if p.get("r", None) is None:
+        if r is None:
             raise SnmfError(2, "Number of components or initialization must be given")
-        r = int(p["r"])
-        iws = [None] * B
-    else:
-        if isinstance(iw, (list, tuple)):
-            if len(iw) != B:
-                raise SnmfError(3, f"init_w is a list of {len(iw)}, the batch has {B} problems")
-            iws = [np.asarray(x, dtype=np.float64) for x in iw]
-        else:
-            iws = [np.asarray(iw, dtype=np.float64)] * B
-        for x in iws:
-            if x.ndim != 2 or x.shape[0] != m:
-                raise SnmfError(3, f"init_w is {x.shape}, v has {m} rows")
-            if x.shape[1] != iws[0].shape[1]:
-                raise SnmfError(3, f"init_w is {x.shape}, problem 0 has {iws[0].shape[1]} columns: a batch shares the rank")
-        ri = iws[0].shape[1]
-        r = int(p["r"]) if (p.get("r", None) is not None and ri < int(p["r"])) else ri
-    return r, iws, _batch_init_h(p, vs, [r] * B)
+        return int(r), None
+    iw = np.asarray(iw, dtype=np.float64)
+    if iw.ndim != 2 or iw.shape[0] != m or (iw.shape[1] < 1 and not empty_ok):
+        raise SnmfError(3, f"init_w is {iw.shape}, v has {m} rows")
+    return (int(r) if (r is not None and iw.shape[1] < int(r)) else iw.shape[1]), iw  # :123-130
+
+
+def _init_h(ih, r, T):
+    """src/sparse_nmf.m:133-140 for one problem: its init_h (or None) as float64, r x T (status 3 otherwise)."""
+    if ih is None:
+        return None
+    ih = np.asarray(ih, dtype=np.float64)
+    if ih.shape != (r, T):
+        raise SnmfError(3, f"init_h is {ih.shape}, expected ({r}, {T})")
+    return ih
+
+
+def _batch_inits(p, vs, m, per_problem=False):
+    """src/sparse_nmf.m:116-140 for a batch: the dict forms of r / init_w / init_h are spread into one (r, init_w) per problem,
+    each resolved by _rank_and_init_w, then init_h -> (r, init_w per problem or None, init_h list or None).
+    per_problem (the fp64 batch): p["r"] may be a list and the init_w arrays may differ in width, and r is the list of the
+    problems' ranks.  Otherwise one rank, as an int, and differing ranks or widths are SnmfError status 3."""
+    B = len(vs)
+    prs = _ints_per_problem(p.get("r", None), B, "r")
+    if prs is not None and not per_problem and len(set(prs)) > 1:
+        raise SnmfError(3, f"r is {prs}: a batch shares the rank")
+    iw = p.get("init_w", None)
+    if isinstance(iw, (list, tuple)):
+        if len(iw) != B:
+            raise SnmfError(3, f"init_w is a list of {len(iw)}, the batch has {B} problems")
+        iw = [np.asarray(x, dtype=np.float64) for x in iw]  # (only an absent key means "no init_w": a None entry is no matrix, status 3)
+    else:  # one array (or none) for every problem
+        iw = [iw if iw is None else np.asarray(iw, dtype=np.float64)] * B
+    rs, iws = [], []
+    for r, x in zip(prs or [p.get("r", None)] * B, iw):
+        r, x = _rank_and_init_w(m, r, x, empty_ok=not per_problem)
+        if not per_problem and iws and x is not None and x.shape[1] != iws[0].shape[1]:
+            raise SnmfError(3, f"init_w is {x.shape}, problem 0 has {iws[0].shape[1]} columns: a batch shares the rank")
+        rs.append(r)
+        iws.append(x)
+    return (rs if per_problem else rs[0]), iws, _batch_init_h(p, vs, rs)
 
 
 def _batch_init_h(p, vs, rs):
     """The list form of init_h (src/sparse_nmf.m:133-140): r_k x T_k arrays, or None when it is absent."""
-    B = len(vs)
     ih = p.get("init_h", None)
-    ihs = None
-    if ih is not None:
-        if isinstance(ih, str) or not isinstance(ih, (list, tuple)) or len(ih) != B:
-            raise SnmfError(3, f"init_h must be a list of {B} arrays (r x T_b each), or absent")
-        ihs = [np.asarray(x, dtype=np.float64) for x in ih]
-        for v, x, r in zip(vs, ihs, rs):
-            if x.shape != (r, v.shape[1]):
-                raise SnmfError(3, f"init_h is {x.shape}, expected ({r}, {v.shape[1]})")
-    return ihs
+    if ih is None:
+        return None
+    if isinstance(ih, str) or not isinstance(ih, (list, tuple)) or len(ih) != len(vs):
+        raise SnmfError(3, f"init_h must be a list of {len(vs)} arrays (r x T_b each), or absent")
+    return [_init_h(np.asarray(x, dtype=np.float64), r, v.shape[1]) for v, x, r in zip(vs, ih, rs)]  # (a None entry: status 3)
 
 
 def _batch_draws(vs, m, r, iws, ihs, rng, dt):
     """The initial factors of every problem, drawn in list order from one generator (w then h, as one solve draws them, each of
-    its own shape).  r: the shared rank, or a list with one per problem."""
+    its own shape) -- the only draw loop of the batched solves.  r: the shared rank, or a list with one per problem; ihs: None,
+    or a list in which None stands for a problem without init_h (the list of dicts)."""
     w0s, h0s = [], []
     rs = r if isinstance(r, list) else [r] * len(vs)
     for k, v in enumerate(vs):
@@ -221,10 +249,37 @@ def _batch_draws(vs, m, r, iws, ihs, rng, dt):
             w0 = np.concatenate([iws[k], rng.random_sample((m, r - iws[k].shape[1]))], axis=1)
         else:
             w0 = iws[k]
-        h0 = rng.random_sample((r, n)) if ihs is None else ihs[k]
+        h0 = rng.random_sample((r, n)) if ihs is None or ihs[k] is None else ihs[k]
         w0s.append(np.asfortranarray(w0, dtype=dt))
         h0s.append(np.asfortranarray(h0, dtype=dt))
     return w0s, h0s
+
+
+def _cost_check(p):
+    if "cost_check" not in p:  # src/sparse_nmf.m:260
+        raise SnmfError(4, "Reference to non-existent field 'cost_check'.")
+    return 1 if p["cost_check"] else 0
+
+
+def _ptrs(arrs):
+    """A list of arrays as the C array of their addresses; None stays None (NULL)."""
+    return (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs]) if arrs is not None else None
+
+
+def _ptr_or_null(a):
+    return _ptr(a) if a is not None else None
+
+
+def _lds(arrs):
+    """The leading dimensions of a list of column-major arrays (one column: the row count)."""
+    return np.array([(a.strides[1] // a.itemsize) if a.shape[1] > 1 else a.shape[0] for a in arrs], np.int64)
+
+
+def _one_shot_buffers(vs, m, r, max_iter, dt):
+    """What a one-shot entry takes beside the problems -> (Ts, W, H, div, cost, n_iter)."""
+    nh = max(max_iter, 1)
+    return (np.array([v.shape[1] for v in vs], np.int32), [np.empty((m, r), dtype=dt, order="F") for _ in vs], [np.empty((r, v.shape[1]), dtype=dt, order="F") for v in vs],
+            [np.zeros(nh) for _ in vs], [np.zeros(nh) for _ in vs], np.zeros(len(vs), np.int32))
 
 
 def sparse_nmf_batch(vs, p=None, *, ctx=None, dtype=np.float64, rng=None, precision="fp32"):
@@ -265,22 +320,13 @@ def sparse_nmf_batch_fp64(vs, p=None, *, ctx=None, rng=None):
 
 def _solve_batch(vs, p, ctx, dtype, rng, mode):
     """The one host side of sparse_nmf_batch and sparse_nmf_batch_fp64: the reference's defaulting, its errors and the batch's
-    refusals, the draws, then one call of the C entry of `mode`."""
+    refusals, the draws, then one call of the C entry of `mode` -- or, for differing ranks, the resident handle."""
     p = dict(p or {})
     dt = np.dtype(dtype)
     if dt not in (np.dtype(np.float64), np.dtype(np.float32)):
         raise SnmfError(1, "dtype must be float64 or float32")
-    vs = [np.asarray(v) for v in vs]
-    B = len(vs)
-    if B == 0:
-        raise SnmfError(1, "the batch is empty: vs must hold at least one matrix")
-    for v in vs:
-        if v.ndim != 2 or v.shape[1] < 1:
-            raise SnmfError(1, "every v must be a 2-D matrix with at least one column")
-    m = vs[0].shape[0]  # :71
-    for k, v in enumerate(vs):
-        if v.shape[0] != m:
-            raise SnmfError(3, f"v of problem {k} has {v.shape[0]} rows, problem 0 has {m}: a batch shares the row count")
+    vs = _problem_arrays(vs)
+    m, B = _row_count(vs), len(vs)
     max_iter = int(p.get("max_iter", 100))  # :79-81
     random_seed = p.get("random_seed", 1)  # :83-85
     conv_eps = float(p.get("conv_eps", 0))  # :91-93
@@ -291,14 +337,17 @@ def _solve_batch(vs, p, ctx, dtype, rng, mode):
     r, iws, ihs = _batch_inits(p, vs, m, per_problem=mode == "fp64")  # :116-131
     if isinstance(r, list) and len(set(r)) == 1:
         r = r[0]
-    if isinstance(r, list):  # differing ranks: the resident handle, no one-shot entry
-        return _solve_batch_ranks(vs, p, ctx, rng, m, r, iws, ihs, beta, max_iter, conv_eps)
+    if isinstance(r, list):  # differing ranks: the remaining checks and the draws, then the resident handle (no one-shot entry)
+        scalar, on = _mixed_rank_rules(p.get("sparsity", 0), {k: p.get(k, None) for k in ("w_update_ind", "h_update_ind")})
+        cost_check = _cost_check(p)
+        w0s, h0s = _batch_draws(vs, m, r, iws, ihs, rng, dt)
+        return _solve_through_handle(vs, ctx, m, r, w0s, h0s, [(beta, max_iter, conv_eps)] * B, [p.get("display", 0)] * B,
+                                     beta=beta, max_iter=max_iter, conv_eps=conv_eps, cost_check=cost_check, sparsity=scalar,
+                                     w_update_ind=bool(on["w_update_ind"]), h_update_ind=bool(on["h_update_ind"]))
     w_ind = _mask(p, "w_update_ind", r)
     h_ind = _h_ind_all_or_none(p, r)
     kind, scalar, sarr = _batch_sparsity(p.get("sparsity", 0), r)
-    if "cost_check" not in p:  # src/sparse_nmf.m:260
-        raise SnmfError(4, "Reference to non-existent field 'cost_check'.")
-    cost_check = 1 if p["cost_check"] else 0
+    cost_check = _cost_check(p)
 
     w0s, h0s = _batch_draws(vs, m, r, iws, ihs, rng, dt)  # the draws, in list order (:116-140)
 
@@ -306,24 +355,14 @@ def _solve_batch(vs, p, ctx, dtype, rng, mode):
     lib = _lib.load()
     ctx = ctx or default_context()
     vv = [_colmajor(v, dt) for v in vs]
-    Ts = np.array([v.shape[1] for v in vs], np.int32)
-    ldv = np.array([(v.strides[1] // dt.itemsize) if v.shape[1] > 1 else m for v in vv], np.int64)
-    W = [np.empty((m, r), dtype=dt, order="F") for _ in vs]
-    H = [np.empty((r, v.shape[1]), dtype=dt, order="F") for v in vs]
-    nh = max(max_iter, 1)
-    div = [np.zeros(nh) for _ in vs]
-    cost = [np.zeros(nh) for _ in vs]
-    n_iter = np.zeros(B, np.int32)
-
-    def ptrs(arrs):
-        return (C.c_void_p * B)(*[a.ctypes.data for a in arrs])
-
+    ldv = _lds(vv)
+    Ts, W, H, div, cost, n_iter = _one_shot_buffers(vs, m, r, max_iter, dt)
     if mode == "fp64":
         fn = lib.snmf_sparse_nmf_batch_fp64
     else:
         fn = lib.snmf_sparse_nmf_batch_f64 if dt == np.float64 else lib.snmf_sparse_nmf_batch_f32
-    _lib.check(fn(ctx._h, C.byref(sp), B, _ptr(Ts), ptrs(vv), _ptr(ldv), ptrs(w0s), ptrs(h0s), _ptr(sarr) if sarr is not None else None,
-                  ptrs(W), ptrs(H), ptrs(div), ptrs(cost), _ptr(n_iter)))
+    _lib.check(fn(ctx._h, C.byref(sp), B, _ptr(Ts), _ptrs(vv), _ptr(ldv), _ptrs(w0s), _ptrs(h0s), _ptr_or_null(sarr),
+                  _ptrs(W), _ptrs(H), _ptrs(div), _ptrs(cost), _ptr(n_iter)))
     out = []
     for k in range(B):
         ni = int(n_iter[k])
@@ -333,17 +372,12 @@ def _solve_batch(vs, p, ctx, dtype, rng, mode):
     return out
 
 
-def _solve_batch_ranks(vs, p, ctx, rng, m, rs, iws, ihs, beta, max_iter, conv_eps):
-    """sparse_nmf_batch_fp64 with differing ranks: the remaining checks and the draws, all before the library is loaded, then
-    BatchPlan64 with the ranks -- set every problem, run to the end, get."""
-    scalar, on = _mixed_rank_rules(p.get("sparsity", 0), {k: p.get(k, None) for k in ("w_update_ind", "h_update_ind")})
-    if "cost_check" not in p:  # src/sparse_nmf.m:260
-        raise SnmfError(4, "Reference to non-existent field 'cost_check'.")
-    cost_check = 1 if p["cost_check"] else 0
+def _solve_through_handle(vs, ctx, m, rs, w0s, h0s, per, displays, **plan_kw):
+    """The fp64 solves that have no one-shot entry (differing ranks, settings per problem), after every check and the draws:
+    BatchPlan64(ctx, m, rs, Ts, **plan_kw) -- set every problem, run to the end, get, close -- then the display and the
+    objective of every problem from per[k] = its (beta, max_iter, conv_eps) and displays[k] = its p["display"]."""
     dt = np.dtype(np.float64)
-    w0s, h0s = _batch_draws(vs, m, rs, iws, ihs, rng, dt)  # the draws, in list order (:116-140)
-    plan = BatchPlan64(ctx, m, rs, [v.shape[1] for v in vs], beta=beta, max_iter=max_iter, conv_eps=conv_eps, cost_check=cost_check,
-                       sparsity=scalar, w_update_ind=bool(on["w_update_ind"]), h_update_ind=bool(on["h_update_ind"]))
+    plan = BatchPlan64(ctx, m, rs, [v.shape[1] for v in vs], **plan_kw)
     try:
         for k, v in enumerate(vs):
             plan.set_problem(k, np.asarray(v, dtype=dt), w0s[k], h0s[k])
@@ -352,10 +386,11 @@ def _solve_batch_ranks(vs, p, ctx, rng, m, rs, iws, ihs, beta, max_iter, conv_ep
     finally:
         plan.close()
     out = []
-    for W, H, div, cost, ni in raw:
-        if p.get("display", 0) != 0:
-            _display(beta, div, cost, ni, max_iter, cost_check, conv_eps, False)
-        out.append((W, H, _objective(div, cost, ni, max_iter, cost_check)))
+    for (W, H, div, cost, ni), (beta, mi, eps), display in zip(raw, per, displays):
+        div, cost = div[:max(mi, 1)], cost[:max(mi, 1)]  # (the handle's vectors have the largest limit's length)
+        if display != 0:
+            _display(beta, div, cost, ni, mi, plan.cost_check, eps, False)
+        out.append((W, H, _objective(div, cost, ni, mi, plan.cost_check)))
     return out
 
 
@@ -366,21 +401,12 @@ def _mask_key(m):
 def _solve_batch_settings(vs, ps, ctx, rng):
     """sparse_nmf_batch_fp64 with a list of settings dicts: the reference's defaulting and errors per problem, the batch's
     refusals and the draws, all before the library is loaded; then BatchPlan64 with the settings (and the ranks, where they
-    differ) -- set every problem, run to the end, get."""
-    dt = np.dtype(np.float64)
-    vs = [np.asarray(v) for v in vs]
+    differ) through _solve_through_handle."""
+    vs = _problem_arrays(vs)
     B = len(vs)
-    if B == 0:
-        raise SnmfError(1, "the batch is empty: vs must hold at least one matrix")
     if len(ps) != B:
         raise SnmfError(3, f"p is a list of {len(ps)} settings, the batch has {B} problems")
-    for v in vs:
-        if v.ndim != 2 or v.shape[1] < 1:
-            raise SnmfError(1, "every v must be a 2-D matrix with at least one column")
-    m = vs[0].shape[0]  # :71
-    for k, v in enumerate(vs):
-        if v.shape[0] != m:
-            raise SnmfError(3, f"v of problem {k} has {v.shape[0]} rows, problem 0 has {m}: a batch shares the row count")
+    m = _row_count(vs)
     ps = [dict(q or {}) for q in ps]
     # ---- per problem: the settings (:79-110, :150-155) and the rank with its initial factors (:116-140)
     resolved, rs, iws, ihs = [], [], [], []
@@ -392,31 +418,15 @@ def _solve_batch_settings(vs, ps, ctx, rng):
         if mi < 0:
             raise SnmfError(1, f"problem {k}: max_iter must be >= 0")
         resolved.append((_cf_to_beta(q), float(sp.reshape(-1)[0]), mi, float(q.get("conv_eps", 0))))
-        iw, rk = q.get("init_w", None), q.get("r", None)
-        if iw is None:
-            if rk is None:
-                raise SnmfError(2, "Number of components or initialization must be given")
-            r = int(rk)
-            if r < 1:
-                raise SnmfError(1, f"problem {k} has rank {r} (at least 1)")
-        else:
-            iw = np.asarray(iw, dtype=np.float64)
-            if iw.ndim != 2 or iw.shape[0] != m or iw.shape[1] < 1:
-                raise SnmfError(3, f"init_w is {iw.shape}, v has {m} rows")
-            r = int(rk) if (rk is not None and iw.shape[1] < int(rk)) else iw.shape[1]  # :123-130
-        ih = q.get("init_h", None)
-        if ih is not None:
-            ih = np.asarray(ih, dtype=np.float64)
-            if ih.shape != (r, v.shape[1]):
-                raise SnmfError(3, f"init_h is {ih.shape}, expected ({r}, {v.shape[1]})")
+        r, iw = _rank_and_init_w(m, q.get("r", None), q.get("init_w", None))
+        _at_least_1(r, k, "r")  # (only a given r can fail: an init_w has a column)
         rs.append(r)
         iws.append(iw)
-        ihs.append(ih)
+        ihs.append(_init_h(q.get("init_h", None), r, v.shape[1]))
     # ---- shared: cost_check, the masks, random_seed
     for q in ps:
-        if "cost_check" not in q:  # src/sparse_nmf.m:260
-            raise SnmfError(4, "Reference to non-existent field 'cost_check'.")
-    cost_check = 1 if ps[0]["cost_check"] else 0
+        _cost_check(q)
+    cost_check = _cost_check(ps[0])
     seed = ps[0].get("random_seed", 1)
     mixed = len(set(rs)) > 1
     masks = {}
@@ -437,36 +447,11 @@ def _solve_batch_settings(vs, ps, ctx, rng):
         _h_ind_all_or_none(dict(h_update_ind=masks["h_update_ind"]), rs[0])
     if rng is None:  # :112-114
         rng = np.random.RandomState(int(seed) if seed and seed > 0 else None)
-    w0s, h0s = [], []
-    for k, v in enumerate(vs):  # the draws, in list order, w then h (:116-140)
-        n, r = v.shape[1], rs[k]
-        if iws[k] is None:
-            w0 = rng.random_sample((m, r))
-        elif iws[k].shape[1] < r:
-            w0 = np.concatenate([iws[k], rng.random_sample((m, r - iws[k].shape[1]))], axis=1)
-        else:
-            w0 = iws[k]
-        h0 = rng.random_sample((r, n)) if ihs[k] is None else ihs[k]
-        w0s.append(np.asfortranarray(w0, dtype=dt))
-        h0s.append(np.asfortranarray(h0, dtype=dt))
-    plan = BatchPlan64(ctx, m, rs if mixed else rs[0], [v.shape[1] for v in vs], cost_check=cost_check,
-                       w_update_ind=masks["w_update_ind"], h_update_ind=masks["h_update_ind"],
-                       settings=[dict(beta=b, sparsity=s, max_iter=mi, conv_eps=e) for b, s, mi, e in resolved])
-    try:
-        for k, v in enumerate(vs):
-            plan.set_problem(k, np.asarray(v, dtype=dt), w0s[k], h0s[k])
-        plan.run()
-        raw = [plan._get(k, dt) for k in range(B)]
-    finally:
-        plan.close()
-    out = []
-    for k, (W, H, div, cost, ni) in enumerate(raw):
-        beta, _, mi, eps = resolved[k]
-        div, cost = div[:max(mi, 1)], cost[:max(mi, 1)]
-        if ps[k].get("display", 0) != 0:
-            _display(beta, div, cost, ni, mi, cost_check, eps, False)
-        out.append((W, H, _objective(div, cost, ni, mi, cost_check)))
-    return out
+    w0s, h0s = _batch_draws(vs, m, rs, iws, ihs, rng, np.dtype(np.float64))  # the dict call's: list order, w then h (:116-140)
+    return _solve_through_handle(vs, ctx, m, rs if mixed else rs[0], w0s, h0s, [(b, mi, e) for b, _, mi, e in resolved],
+                                 [q.get("display", 0) for q in ps], cost_check=cost_check, w_update_ind=masks["w_update_ind"],
+                                 h_update_ind=masks["h_update_ind"],
+                                 settings=[dict(beta=b, sparsity=s, max_iter=mi, conv_eps=e) for b, s, mi, e in resolved])
 
 
 class BatchPlan:
@@ -495,31 +480,41 @@ class BatchPlan:
             self.settings = _problem_settings(settings, self.B, dict(beta=beta, sparsity=sparsity, max_iter=max_iter, conv_eps=conv_eps))
             max_iter = max(s[2] for s in self.settings)  # the handle's: the largest
             sparsity = 0.0  # (every problem has its own)
+        masks = dict(w_update_ind=w_update_ind, h_update_ind=h_update_ind)
         self.ranks = None  # a rank per problem (BatchPlan64 with a sequence for r); None: self.r for every problem
-        rs = _rank_list(r, self.B)
+        rs = _ints_per_problem(r, self.B, "r")
         if rs is not None:
-            r = self._take_ranks(rs, sparsity, w_update_ind, h_update_ind)
+            r = self._take_ranks(rs, sparsity, masks)
         self.F, self.r, self.max_iter = int(F), int(r), int(max_iter)
         self.cost_check = 1 if cost_check else 0
+        # ---- the masks and the sparsity under the rules of the form
+        self._sarr = self._rk = self._st = None
+        if self.ranks is not None:  # a rank per problem: a scalar, and masks of all ones or all zeros
+            kind = 0
+            scalar, on = _mixed_rank_rules(sparsity, masks)
+            self._w_ind, self._h_ind = (np.full(self.r, on[key], np.uint8) for key in ("w_update_ind", "h_update_ind"))
+            self._rk = np.array(self.ranks, np.int32)
+        else:
+            if self.settings is not None:  # (this form takes a bool for a mask, as the form with ranks does)
+                masks = {k: (np.full(self.r, m, np.uint8) if isinstance(m, (bool, np.bool_)) else m) for k, m in masks.items()}
+            self._w_ind = _mask(masks, "w_update_ind", self.r)
+            self._h_ind = _h_ind_all_or_none(masks, self.r)
+            kind, scalar, self._sarr = _batch_sparsity(sparsity, self.r)
         if self.settings is not None:
-            return self._init_settings(ctx, floor_v, w_update_ind, h_update_ind)
-        if self.ranks is not None:
-            return self._init_ranks(ctx, beta, conv_eps, floor_v, sparsity, w_update_ind, h_update_ind)
-        pd = dict(w_update_ind=w_update_ind, h_update_ind=h_update_ind)
-        self._w_ind = _mask(pd, "w_update_ind", self.r)
-        self._h_ind = _h_ind_all_or_none(pd, self.r)
-        kind, scalar, self._sarr = _batch_sparsity(sparsity, self.r)
-        sp = _make_params(F, 1, r, beta, max_iter, conv_eps, cost_check, floor_v, kind, scalar, self._w_ind, self._h_ind)
-        self._lib = _lib.load()
-        self.ctx = ctx or default_context()
-        h = C.c_void_p()
-        _lib.check(getattr(self._lib, self._create)(self.ctx._h, C.byref(sp), self.B, _ptr(self.Ts), C.byref(h)))
-        self._h = h
-        self.ctx._plans.add(self)
-        if self._sarr is not None:
-            _lib.check(self._lib.snmf_batch_set_sparsity_f64(self._h, _ptr(self._sarr)))
+            beta, scalar, _, conv_eps = self.settings[0]  # (the handle ignores these three fields of its params)
+        sp = _make_params(self.F, 1, self.r, beta, self.max_iter, conv_eps, self.cost_check, floor_v, kind, scalar, self._w_ind, self._h_ind)
+        # ---- the entry of the form
+        if self.settings is not None:
+            self._st = _settings_array(self.settings)
+            self._open(ctx, self._create_settings, sp, _ptr_or_null(self._rk), self._st)
+        elif self.ranks is not None:
+            self._open(ctx, self._create_ranks, sp, _ptr(self._rk))
+        else:
+            self._open(ctx, self._create, sp)
+            if self._sarr is not None:
+                _lib.check(self._lib.snmf_batch_set_sparsity_f64(self._h, _ptr(self._sarr)))
 
-    def _take_ranks(self, rs, sparsity, w_update_ind, h_update_ind):
+    def _take_ranks(self, rs, sparsity, masks):
         """r given as a sequence -> the rank the handle is made with.  Where the engine takes a rank per problem and the settings
         allow it, self.ranks is set (and the largest returned); equal ranks are otherwise that rank; differing ones are refused."""
         equal = len(set(rs)) == 1
@@ -528,7 +523,7 @@ class BatchPlan:
                 raise SnmfError(self._rank_status, f"r is {rs}: this batch shares the rank (a rank per problem: BatchPlan64)")
             return rs[0]
         try:
-            _mixed_rank_rules(sparsity, dict(w_update_ind=w_update_ind, h_update_ind=h_update_ind))
+            _mixed_rank_rules(sparsity, masks)
         except SnmfError:
             if not equal:
                 raise
@@ -536,43 +531,20 @@ class BatchPlan:
         self.ranks = rs
         return max(rs)
 
-    def _init_ranks(self, ctx, beta, conv_eps, floor_v, sparsity, w_update_ind, h_update_ind):
-        scalar, on = _mixed_rank_rules(sparsity, dict(w_update_ind=w_update_ind, h_update_ind=h_update_ind))
-        self._sarr = None
-        self._w_ind = np.full(self.r, on["w_update_ind"], np.uint8)
-        self._h_ind = np.full(self.r, on["h_update_ind"], np.uint8)
-        sp = _make_params(self.F, 1, self.r, beta, self.max_iter, conv_eps, self.cost_check, floor_v, 0, scalar, self._w_ind, self._h_ind)
-        self._rk = np.array(self.ranks, np.int32)
+    def _open(self, ctx, entry, sp, *extra):
+        """Load the library, take the context, create the handle through `entry` (params, B, Ts, *extra) and register it."""
         self._lib = _lib.load()
         self.ctx = ctx or default_context()
         h = C.c_void_p()
-        _lib.check(getattr(self._lib, self._create_ranks)(self.ctx._h, C.byref(sp), self.B, _ptr(self.Ts), _ptr(self._rk), C.byref(h)))
+        _lib.check(getattr(self._lib, entry)(self.ctx._h, C.byref(sp), self.B, _ptr(self.Ts), *extra, C.byref(h)))
         self._h = h
         self.ctx._plans.add(self)
 
-    def _init_settings(self, ctx, floor_v, w_update_ind, h_update_ind):
-        """The handle with settings per problem (and ranks, where self.ranks is set): the masks under the rules of the form."""
-        masks = dict(w_update_ind=w_update_ind, h_update_ind=h_update_ind)
-        if self.ranks is not None:
-            _, on = _mixed_rank_rules(0.0, masks)
-            self._w_ind = np.full(self.r, on["w_update_ind"], np.uint8)
-            self._h_ind = np.full(self.r, on["h_update_ind"], np.uint8)
-        else:
-            pd = {k: (np.full(self.r, m, np.uint8) if isinstance(m, (bool, np.bool_)) else m) for k, m in masks.items()}
-            self._w_ind = _mask(pd, "w_update_ind", self.r)
-            self._h_ind = _h_ind_all_or_none(pd, self.r)
-        self._sarr = None
-        beta, scalar, _, eps = self.settings[0]  # (the handle ignores these three fields of its params)
-        sp = _make_params(self.F, 1, self.r, beta, self.max_iter, eps, self.cost_check, floor_v, 0, scalar, self._w_ind, self._h_ind)
-        self._rk = np.array(self.ranks, np.int32) if self.ranks is not None else None
-        self._st = _settings_array(self.settings)
-        self._lib = _lib.load()
-        self.ctx = ctx or default_context()
-        h = C.c_void_p()
-        _lib.check(getattr(self._lib, self._create_settings)(self.ctx._h, C.byref(sp), self.B, _ptr(self.Ts),
-                                                             _ptr(self._rk) if self._rk is not None else None, self._st, C.byref(h)))
-        self._h = h
-        self.ctx._plans.add(self)
+    def _index(self, k):
+        k = int(k)
+        if not 0 <= k < self.B:
+            raise SnmfError(1, f"problem index {k} outside [0, {self.B})")
+        return k
 
     def rank(self, k):
         """The rank of problem k."""
@@ -583,14 +555,20 @@ class BatchPlan:
         return self.max_iter if self.settings is None else self.settings[k][2]
 
     def set_problem(self, k, v, w0, h0):
-        k = int(k)
-        if not 0 <= k < self.B:
-            raise SnmfError(1, f"problem index {k} outside [0, {self.B})")
+        self._set_problem(k, v, w0, h0)
+
+    def _set_problem(self, k, v, w0, h0, mask=None):
+        """set_problem of every engine; mask: the missing-data batch's (its one entry takes doubles)."""
+        k = self._index(k)
         v = np.asarray(v)
-        dt = np.dtype(np.float32) if v.dtype == np.float32 else np.dtype(np.float64)
+        if mask is not None:
+            mask = np.asarray(mask, dtype=np.float64)
+        dt = np.dtype(np.float32) if (mask is None and v.dtype == np.float32) else np.dtype(np.float64)
         T, r = int(self.Ts[k]), self.rank(k)
         if v.shape != (self.F, T):
             raise SnmfError(3, f"v is {v.shape}, problem {k} is ({self.F}, {T})")
+        if mask is not None and mask.shape != v.shape:
+            raise SnmfError(3, f"the mask is {mask.shape}, v is {v.shape}")
         w0, h0 = np.asarray(w0), np.asarray(h0)
         if w0.shape != (self.F, r):
             raise SnmfError(3, f"init_w is {w0.shape}, problem {k} is ({self.F}, {r})" if self.ranks is not None
@@ -600,8 +578,13 @@ class BatchPlan:
         vv = _colmajor(v, dt)
         w0 = np.asfortranarray(w0, dtype=dt)
         h0 = np.asfortranarray(h0, dtype=dt)
-        fn = self._lib.snmf_batch_set_problem_f64 if dt == np.float64 else self._lib.snmf_batch_set_problem_f32
-        _lib.check(fn(self._h, k, _ptr(vv), vv.strides[1] // dt.itemsize if T > 1 else self.F, _ptr(w0), _ptr(h0)))
+        ld = lambda a: a.strides[1] // dt.itemsize if T > 1 else self.F  # noqa: E731
+        if mask is None:
+            entry, extra = ("snmf_batch_set_problem_f64" if dt == np.float64 else "snmf_batch_set_problem_f32"), ()
+        else:
+            mm = _colmajor(mask, dt)
+            entry, extra = "snmf_batch_set_problem_mdi_f64", (_ptr(mm), ld(mm))
+        _lib.check(getattr(self._lib, entry)(self._h, k, _ptr(vv), ld(vv), *extra, _ptr(w0), _ptr(h0)))
         self.ctx.sync()  # (the host arrays may go out of scope)
 
     def run(self, n_iters=None):
@@ -613,9 +596,7 @@ class BatchPlan:
         return W, H, _objective(div[:max(mi, 1)], cost[:max(mi, 1)], ni, mi, self.cost_check)
 
     def _get(self, k, dt):
-        k = int(k)
-        if not 0 <= k < self.B:
-            raise SnmfError(1, f"problem index {k} outside [0, {self.B})")
+        k = self._index(k)
         W = np.empty((self.F, self.rank(k)), dtype=dt, order="F")
         H = np.empty((self.rank(k), int(self.Ts[k])), dtype=dt, order="F")
         nh = max(self.max_iter, 1)
@@ -687,22 +668,12 @@ def _mdi_batch(vs, masks, p, ctx, rng, info):
     refusals, all before the library is loaded; then one call of snmf_mdi_batch_fp64."""
     p = dict(p or {})
     dt = np.dtype(np.float64)
-    vs = [np.asarray(v) for v in vs]
     masks = [np.asarray(mk, dtype=np.float64) for mk in masks]
+    vs = _problem_arrays(vs)
     B = len(vs)
-    if B == 0:
-        raise SnmfError(1, "the batch is empty: vs must hold at least one matrix")
     if len(masks) != B:
         raise SnmfError(3, f"{len(masks)} masks for {B} problems")
-    for k, (v, mk) in enumerate(zip(vs, masks)):
-        if v.ndim != 2 or v.shape[1] < 1:
-            raise SnmfError(1, "every v must be a 2-D matrix with at least one column")
-        if mk.shape != v.shape:
-            raise SnmfError(3, f"the mask of problem {k} is {mk.shape}, its v is {v.shape}")
-    m = vs[0].shape[0]
-    for k, v in enumerate(vs):
-        if v.shape[0] != m:
-            raise SnmfError(3, f"v of problem {k} has {v.shape[0]} rows, problem 0 has {m}: a batch shares the row count")
+    m = _row_count(vs, masks=masks)
     max_iter = int(p.get("max_iter", 100))  # src/snmf_mdi.m:83-85
     seed = p.get("random_seed", 1)
     if "sparsity" not in p:  # :87-89 (the default is installed only when p.sparsity is ABSENT)
@@ -728,23 +699,11 @@ def _mdi_batch(vs, masks, p, ctx, rng, info):
     ctx = ctx or default_context()
     vv = [_colmajor(v, dt) for v in vs]
     mm = [_colmajor(mk, dt) for mk in masks]
-    Ts = np.array([v.shape[1] for v in vs], np.int32)
-    ld = lambda arrs: np.array([(a.strides[1] // dt.itemsize) if a.shape[1] > 1 else m for a in arrs], np.int64)  # noqa: E731
-    ldv, ldm = ld(vv), ld(mm)
+    ldv, ldm = _lds(vv), _lds(mm)
     Vm = [np.empty(v.shape, dtype=dt, order="F") for v in vs]
-    W = [np.empty((m, r), dtype=dt, order="F") for _ in vs]
-    H = [np.empty((r, v.shape[1]), dtype=dt, order="F") for v in vs]
-    nh = max(max_iter, 1)
-    div = [np.zeros(nh) for _ in vs]
-    cost = [np.zeros(nh) for _ in vs]
-    n_iter = np.zeros(B, np.int32)
-
-    def ptrs(arrs):
-        return (C.c_void_p * B)(*[a.ctypes.data for a in arrs])
-
-    _lib.check(lib.snmf_mdi_batch_fp64(ctx._h, C.byref(sp), B, _ptr(Ts), ptrs(vv), _ptr(ldv), ptrs(mm), _ptr(ldm), ptrs(w0s), ptrs(h0s),
-                                       _ptr(sarr) if sarr is not None else None, ptrs(Vm), None, ptrs(W), ptrs(H), ptrs(div), ptrs(cost),
-                                       _ptr(n_iter)))
+    Ts, W, H, div, cost, n_iter = _one_shot_buffers(vs, m, r, max_iter, dt)
+    _lib.check(lib.snmf_mdi_batch_fp64(ctx._h, C.byref(sp), B, _ptr(Ts), _ptrs(vv), _ptr(ldv), _ptrs(mm), _ptr(ldm), _ptrs(w0s), _ptrs(h0s),
+                                       _ptr_or_null(sarr), _ptrs(Vm), None, _ptrs(W), _ptrs(H), _ptrs(div), _ptrs(cost), _ptr(n_iter)))
     if info is not None:
         info["w"] = W
     out = []
@@ -767,39 +726,13 @@ class BatchPlanMdi64(BatchPlan64):
     _create_settings = None  # and the settings
 
     def set_problem(self, k, v, mask, w0, h0):
-        k = int(k)
-        if not 0 <= k < self.B:
-            raise SnmfError(1, f"problem index {k} outside [0, {self.B})")
-        dt = np.dtype(np.float64)
-        v, mask = np.asarray(v), np.asarray(mask, dtype=np.float64)
-        T = int(self.Ts[k])
-        if v.shape != (self.F, T):
-            raise SnmfError(3, f"v is {v.shape}, problem {k} is ({self.F}, {T})")
-        if mask.shape != v.shape:
-            raise SnmfError(3, f"the mask is {mask.shape}, v is {v.shape}")
-        w0, h0 = np.asarray(w0), np.asarray(h0)
-        if w0.shape != (self.F, self.r):
-            raise SnmfError(3, f"init_w is {w0.shape}, v has {self.F} rows")
-        if h0.shape != (self.r, T):
-            raise SnmfError(3, f"init_h is {h0.shape}, expected ({self.r}, {T})")
-        vv, mm = _colmajor(v, dt), _colmajor(mask, dt)
-        w0 = np.asfortranarray(w0, dtype=dt)
-        h0 = np.asfortranarray(h0, dtype=dt)
-        ld = lambda a: a.strides[1] // dt.itemsize if T > 1 else self.F  # noqa: E731
-        _lib.check(self._lib.snmf_batch_set_problem_mdi_f64(self._h, k, _ptr(vv), ld(vv), _ptr(mm), ld(mm), _ptr(w0), _ptr(h0)))
-        self.ctx.sync()  # (the host arrays may go out of scope)
+        self._set_problem(k, v, w0, h0, mask=mask)
 
     def get_v_mdi(self, k):
-        k = int(k)
-        if not 0 <= k < self.B:
-            raise SnmfError(1, f"problem index {k} outside [0, {self.B})")
+        k = self._index(k)
         out = np.empty((self.F, int(self.Ts[k])), dtype=np.float64, order="F")
         _lib.check(self._lib.snmf_batch_get_v_mdi_f64(self._h, k, _ptr(out), self.F))
         return out
-
-
-def _is_seq(x):
-    return isinstance(x, (list, tuple)) or (isinstance(x, np.ndarray) and x.ndim > 0)
 
 
 def _dnmf_rank_pairs(R_x, R_d, n, settings, precision):
@@ -811,22 +744,14 @@ def _dnmf_rank_pairs(R_x, R_d, n, settings, precision):
     if precision != "fp64":
         raise SnmfError(8, "a rank pair or settings per problem need precision='fp64': the fp32 batch engine has one rank and one "
                            "settings struct for all problems")
-    out = []
-    for name, R in (("R_x", R_x), ("R_d", R_d)):
-        Rs = [int(x) for x in np.asarray(R).reshape(-1)] if _is_seq(R) else [int(R)] * n
-        if len(Rs) != n:
-            raise SnmfError(3, f"{name} is a list of {len(Rs)}, the batch has {n} problems")
-        for k, x in enumerate(Rs):
-            if x < 1:
-                raise SnmfError(1, f"{name} of problem {k} is {x} (at least 1)")
-        out.append(Rs)
-    return out
+    return [_ints_per_problem(R if _is_seq(R) else [int(R)] * n, n, name) for name, R in (("R_x", R_x), ("R_d", R_d))]
 
 
-def _dnmf_rank_inputs(B, h0, rs, F, Ts, modes, seed):
-    """B and h0 of a DNMF batch with ranks rs[k] = R_x[k] + R_d[k] -> (Bs, H0s): B a list of F x rs[k] arrays, or one array when
-    every pair is the same; h0 one of the strings in `modes`, or a list of rs[k] x T_k arrays.  "host": rand(rs[k], T_k) per
-    problem, in list order, from one RandomState(seed) -- with equal ranks the uniform call's draw; another string: H0s is None.
+def _dnmf_rank_inputs(B, h0, rs, F, Ts, modes, p):
+    """B and h0 of a DNMF batch with ranks rs[k] = R_x[k] + R_d[k] (the uniform call: one rank n times) -> (Bs, H0s) as float64:
+    B a list of F x rs[k] arrays, or one array when every pair is the same; h0 one of the strings in `modes`, or a list of
+    rs[k] x T_k arrays.  "host": rand(rs[k], T_k) per problem, in list order, from one RandomState(p["random_seed"]) -- what
+    sparse_nmf draws for solve 1 of each problem (init_w is given, so h is its first draw); another string: H0s is None.
     All errors are SnmfError status 3."""
     n = len(Ts)
     if isinstance(B, (list, tuple)):
@@ -846,6 +771,7 @@ def _dnmf_rank_inputs(B, h0, rs, F, Ts, modes, seed):
             raise SnmfError(3, what)
         if h0 != "host":
             return Bs, None
+        seed = int(p.get("random_seed", 1))
         rng = np.random.RandomState(seed if seed > 0 else None)
         return Bs, [np.asfortranarray(rng.random_sample((r, T))) for r, T in zip(rs, Ts)]
     if not isinstance(h0, (list, tuple)) or len(h0) != n:
@@ -867,34 +793,6 @@ def _dnmf_rank_params(p, settings, n, F, r_max):
         max_iter = max(s[2] for s in st)
         sarr = _settings_array(st)
     return _make_params(F, 1, r_max, beta, max_iter, conv_eps, cost_check, True, 0, lam, None, None), sarr
-
-
-def _dnmf_batch_ranks(Ys, Xs, Ds, B, Rxs, Rds, p, ctx, dt, h0, info, settings):
-    """run_basis_dnmf_batch with a rank pair per problem (snmf_run_basis_dnmf_batch_ranks_fp64); the feature lists are checked."""
-    n, F = len(Ys), Ys[0].shape[0]
-    rs = [a + b for a, b in zip(Rxs, Rds)]
-    Ts = [y.shape[1] for y in Ys]
-    Bs, H0s = _dnmf_rank_inputs(B, h0, rs, F, Ts, ("host",), int(p.get("random_seed", 1)))
-    sp, sarr = _dnmf_rank_params(p, settings, n, F, max(rs))
-    if dt != np.dtype(np.float64):
-        raise SnmfError(1, "precision='fp64' needs dtype=np.float64 (the fp64 DNMF batch takes and returns doubles)")
-
-    lib = _lib.load()
-    ctx = ctx or default_context()
-    yy, xx, dd = ([np.asfortranarray(a, dtype=np.float64) for a in arrs] for arrs in (Ys, Xs, Ds))
-    B_hat = [np.empty((F, r), order="F") for r in rs]
-    A_hat = [np.empty((r, T), order="F") for r, T in zip(rs, Ts)]
-    n_iter = np.zeros(3 * n, np.int32)
-    Tv, rx, rd = np.array(Ts, np.int32), np.array(Rxs, np.int32), np.array(Rds, np.int32)
-
-    def ptrs(arrs):
-        return (C.c_void_p * n)(*[a.ctypes.data for a in arrs])
-
-    _lib.check(lib.snmf_run_basis_dnmf_batch_ranks_fp64(ctx._h, C.byref(sp), _ptr(rx), _ptr(rd), sarr, n, _ptr(Tv), ptrs(yy), ptrs(xx),
-                                                        ptrs(dd), ptrs(Bs), ptrs(H0s), ptrs(B_hat), ptrs(A_hat), _ptr(n_iter)))
-    if info is not None:
-        info["n_iter"] = [[int(v) for v in n_iter[3 * k:3 * k + 3]] for k in range(n)]
-    return list(zip(B_hat, A_hat))
 
 
 def run_basis_dnmf_batch(Ys, Xs, Ds, B, R_x, R_d, p, *, ctx=None, dtype=np.float64, h0="host", precision="fp32", info=None, settings=None):
@@ -920,74 +818,38 @@ def run_basis_dnmf_batch(Ys, Xs, Ds, B, R_x, R_d, p, *, ctx=None, dtype=np.float
     dt = np.dtype(dtype)
     if dt not in (np.dtype(np.float64), np.dtype(np.float32)):
         raise SnmfError(1, "dtype must be float64 or float32")
-    Ys, Xs, Ds = ([np.asarray(v) for v in vs] for vs in (Ys, Xs, Ds))
+    Xs, Ds = ([np.asarray(v) for v in vs] for vs in (Xs, Ds))
+    Ys = _problem_arrays(Ys, "Y")
     n = len(Ys)
-    if n == 0:
-        raise SnmfError(1, "the batch is empty: Ys must hold at least one matrix")
     if len(Xs) != n or len(Ds) != n:
         raise SnmfError(1, f"{n} mixtures, {len(Xs)} clean and {len(Ds)} noise feature sets: one of each per problem")
-    pairs = _dnmf_rank_pairs(R_x, R_d, n, settings, precision)
-    if pairs is None:
-        R_x, R_d = int(R_x), int(R_d)
-        r = R_x + R_d
-    for y in Ys:
-        if y.ndim != 2 or y.shape[1] < 1:
-            raise SnmfError(1, "every Y must be a 2-D matrix with at least one column")
-    F = Ys[0].shape[0]
+    pairs = _dnmf_rank_pairs(R_x, R_d, n, settings, precision)  # None: two scalars, the uniform entries
+    Rxs, Rds = pairs or ([int(R_x)] * n, [int(R_d)] * n)
+    F = _row_count(Ys, "Y")
     for k, (y, x, d) in enumerate(zip(Ys, Xs, Ds)):
-        if y.shape[0] != F:
-            raise SnmfError(3, f"Y of problem {k} has {y.shape[0]} rows, problem 0 has {F}: a batch shares the row count")
         if x.shape != y.shape or d.shape != y.shape:
             raise SnmfError(3, f"problem {k}: Y, X and D must have one size (got {y.shape}, {x.shape}, {d.shape})")
-    if pairs is not None:
-        return _dnmf_batch_ranks(Ys, Xs, Ds, B, pairs[0], pairs[1], p, ctx, dt, h0, info, settings)
-    if isinstance(B, (list, tuple)):
-        if len(B) != n:
-            raise SnmfError(3, f"B is a list of {len(B)}, the batch has {n} problems")
-        Bs = [np.asarray(b, dtype=np.float64) for b in B]
-    else:
-        Bs = [np.asarray(B, dtype=np.float64)] * n
-    for b in Bs:
-        if b.shape != (F, r):
-            raise SnmfError(3, f"B is {b.shape}, expected ({F}, {r})")
-    if isinstance(h0, str):
-        if h0 != "host":
-            raise SnmfError(3, f"h0 must be 'host' or a list of {n} arrays (r x T_k each)")
-        H0s = None
-    else:
-        if not isinstance(h0, (list, tuple)) or len(h0) != n:
-            raise SnmfError(3, f"h0 must be 'host' or a list of {n} arrays (r x T_k each)")
-        H0s = [np.asarray(h) for h in h0]
-        for h, y in zip(H0s, Ys):
-            if h.shape != (r, y.shape[1]):
-                raise SnmfError(3, f"init_h is {h.shape}, expected ({r}, {y.shape[1]})")
-    beta, max_iter, conv_eps, cost_check, lam = _solver_scalars(p)
+    rs = [a + b for a, b in zip(Rxs, Rds)]
+    Ts = [y.shape[1] for y in Ys]
+    Bs, H0s = _dnmf_rank_inputs(B, h0, rs, F, Ts, ("host",), p)
+    sp, sarr = _dnmf_rank_params(p, settings, n, F, max(rs))
     if precision == "fp64" and dt != np.dtype(np.float64):
         raise SnmfError(1, "precision='fp64' needs dtype=np.float64 (the fp64 DNMF batch takes and returns doubles)")
-    if H0s is None:  # what sparse_nmf draws for solve 1 of each problem (init_w is given, so h is its first draw)
-        seed = int(p.get("random_seed", 1))
-        rs = np.random.RandomState(seed if seed > 0 else None)
-        H0s = [rs.random_sample((r, y.shape[1])) for y in Ys]
-    sp = _make_params(F, 1, r, beta, max_iter, conv_eps, cost_check, True, 0, lam, None, None)
 
     lib = _lib.load()
     ctx = ctx or default_context()
-    tight = lambda arrs: [np.asfortranarray(a, dtype=dt) for a in arrs]  # noqa: E731
-    yy, xx, dd, bb, hh = tight(Ys), tight(Xs), tight(Ds), tight(Bs), tight(H0s)
-    Ts = np.array([y.shape[1] for y in Ys], np.int32)
-    B_hat = [np.empty((F, r), dtype=dt, order="F") for _ in Ys]
-    A_hat = [np.empty((r, y.shape[1]), dtype=dt, order="F") for y in Ys]
+    yy, xx, dd, bb, hh = ([np.asfortranarray(a, dtype=dt) for a in arrs] for arrs in (Ys, Xs, Ds, Bs, H0s))  # (fp32: float32 where asked)
+    B_hat = [np.empty((F, r), dtype=dt, order="F") for r in rs]
+    A_hat = [np.empty((r, T), dtype=dt, order="F") for r, T in zip(rs, Ts)]
     n_iter = np.zeros(3 * n, np.int32)
-
-    def ptrs(arrs):
-        return (C.c_void_p * n)(*[a.ctypes.data for a in arrs])
-
-    if precision == "fp64":
-        fn = lib.snmf_run_basis_dnmf_batch_fp64
+    Tv, rx, rd = np.array(Ts, np.int32), np.array(Rxs, np.int32), np.array(Rds, np.int32)
+    if pairs is not None:
+        entry, head = "snmf_run_basis_dnmf_batch_ranks_fp64", (_ptr(rx), _ptr(rd), sarr, n)
     else:
-        fn = lib.snmf_run_basis_dnmf_batch_f64 if dt == np.float64 else lib.snmf_run_basis_dnmf_batch_f32
-    _lib.check(fn(ctx._h, C.byref(sp), R_x, R_d, n, _ptr(Ts), ptrs(yy), ptrs(xx), ptrs(dd), ptrs(bb), ptrs(hh), ptrs(B_hat), ptrs(A_hat),
-                  _ptr(n_iter)))
+        entry = "snmf_run_basis_dnmf_batch_" + ("fp64" if precision == "fp64" else "f64" if dt == np.float64 else "f32")
+        head = (Rxs[0], Rds[0], n)
+    _lib.check(getattr(lib, entry)(ctx._h, C.byref(sp), *head, _ptr(Tv), _ptrs(yy), _ptrs(xx), _ptrs(dd), _ptrs(bb), _ptrs(hh), _ptrs(B_hat),
+                                   _ptrs(A_hat), _ptr(n_iter)))
     if info is not None:
         info["n_iter"] = [[int(v) for v in n_iter[3 * k:3 * k + 3]] for k in range(n)]
     return list(zip(B_hat, A_hat))

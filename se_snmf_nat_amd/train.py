@@ -22,7 +22,9 @@ import ctypes as C
 import numpy as np
 
 from . import _lib, frontend
-from .api import SnmfError, _check_precision, _fp64_rules, _make_params, _solver_scalars, default_context
+from .api import SnmfError, _check_precision, _fp64_rules, _make_params, _ptr, _solver_scalars, default_context
+from .batch import (_dnmf_rank_inputs, _dnmf_rank_pairs, _dnmf_rank_params, _ints_per_problem, _problem_settings, _ptr_or_null, _ptrs,
+                    _settings_array)
 
 
 def run_basis_train_signal(s_full, R, p, *, DC_bin=None, sample_idx=None, ctx=None, h0="host", precision="fp32", info=None):
@@ -136,7 +138,6 @@ def _train_settings(settings, n, p, precision):
         return None
     if precision != "fp64":
         raise SnmfError(8, "settings per problem need precision='fp64': the fp32 batch engine has one settings struct for all problems")
-    from .batch import _problem_settings
     beta, max_iter, conv_eps, _cc, lam = _solver_scalars(p)
     return _problem_settings(settings, n, dict(beta=beta, sparsity=lam, max_iter=max_iter, conv_eps=conv_eps))
 
@@ -145,15 +146,8 @@ def _train_ranks(R, n, precision):
     """R of the batched training calls: an int (one dictionary size for every problem) -> None; a sequence with one entry per
     problem -> the list when the entries differ (fp64 only: SnmfError status 8 in fp32), None when they are equal (the scalar
     call).  Its own errors: a length that is not n (3), an entry below 1 (1)."""
-    if not isinstance(R, (list, tuple, np.ndarray)) or (isinstance(R, np.ndarray) and R.ndim == 0):
-        return None
-    Rs = [int(x) for x in np.asarray(R).reshape(-1)]
-    if len(Rs) != n:
-        raise SnmfError(3, f"R is a list of {len(Rs)}, the batch has {n} problems")
-    for k, x in enumerate(Rs):
-        if x < 1:
-            raise SnmfError(1, f"R of problem {k} is {x} (at least 1)")
-    if len(set(Rs)) == 1:
+    Rs = _ints_per_problem(R, n, "R")
+    if Rs is None or len(set(Rs)) == 1:
         return None
     if precision != "fp64":
         raise SnmfError(8, "differing R need precision='fp64': the fp32 batch engine has one rank for all problems")
@@ -231,36 +225,20 @@ def _train_batch(signals, ts, R, p, *, DC_bin, sample_idx, ctx, h0, precision, i
         A_DFT = [np.empty((n_ex, T), order="F") for T, n_ex in zip(Ts, n_exs)]
         A_Mel = [np.empty((n_ex, T), order="F") for T, n_ex in zip(Ts, n_exs)]
     n_iter = np.zeros(2 * n, np.int32)
-    ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None  # noqa: E731
-    ptrs = lambda arrs: (C.c_void_p * n)(*[a.ctypes.data for a in arrs]) if arrs is not None else None  # noqa: E731
     alpha = float(p["alpha_eta"]) if p.get("domain_DD", 0) else -1.0
-    atoms = np.array(n_exs, np.int32)
-    tail = (ptrs(idx0), 1 if exemplar else 0, ptrs(H0s), ptr(seeds), ptrs(B_DFT), ptrs(A_DFT), ptrs(B_Mel), ptrs(A_Mel), ptr(n_iter))
-    if st is not None:  # settings per problem: the _ranks_fp64 lists (n_atoms NULL for one size) plus the settings
-        from .batch import _settings_array
-        sarr = _settings_array(st)
-        at = ptr(atoms) if Rk is not None else None
-        if ts is None:
-            lens = np.array(sizes, np.int64)
-            _lib.check(lib.snmf_run_basis_train_audio_batch_settings_fp64(ctx._h, C.byref(q), C.byref(sp), alpha, ptr(mel), M, n, ptrs(sigs),
-                                                                          ptr(lens), at, *tail, sarr))
-        else:
-            _lib.check(lib.snmf_run_basis_train_signals_batch_settings_fp64(ctx._h, C.byref(q), C.byref(sp), alpha, ptr(mel), M, ts._handle(),
-                                                                            at, *tail, sarr))
-    elif ts is None:
-        lens = np.array(sizes, np.int64)
-        if Rk is not None:
-            _lib.check(lib.snmf_run_basis_train_audio_batch_ranks_fp64(ctx._h, C.byref(q), C.byref(sp), alpha, ptr(mel), M, n, ptrs(sigs),
-                                                                       ptr(lens), ptr(atoms), *tail))
-        else:
-            fn = lib.snmf_run_basis_train_audio_batch_fp64 if f64 else lib.snmf_run_basis_train_audio_batch_f64
-            _lib.check(fn(ctx._h, C.byref(q), C.byref(sp), alpha, ptr(mel), M, n, ptrs(sigs), ptr(lens), *tail))
-    elif Rk is not None:
-        _lib.check(lib.snmf_run_basis_train_signals_batch_ranks_fp64(ctx._h, C.byref(q), C.byref(sp), alpha, ptr(mel), M, ts._handle(),
-                                                                     ptr(atoms), *tail))
-    else:
-        fn = lib.snmf_run_basis_train_signals_batch_fp64 if f64 else lib.snmf_run_basis_train_signals_batch_f64
-        _lib.check(fn(ctx._h, C.byref(q), C.byref(sp), alpha, ptr(mel), M, ts._handle(), *tail))
+    atoms, lens = np.array(n_exs, np.int32), np.array(sizes, np.int64)
+    # the entry: where the samples come from, then the form; its arguments: the source's head, n_atoms where the form has it
+    # (NULL for one size), the shared tail, the settings where the form has them
+    form = "settings_fp64" if st is not None else "ranks_fp64" if Rk is not None else "fp64" if f64 else "f64"
+    args = (n, _ptrs(sigs), _ptr(lens)) if ts is None else (ts._handle(),)
+    if st is not None or Rk is not None:
+        args += (_ptr(atoms) if Rk is not None else None,)
+    args += (_ptrs(idx0), 1 if exemplar else 0, _ptrs(H0s), _ptr_or_null(seeds), _ptrs(B_DFT), _ptrs(A_DFT), _ptrs(B_Mel), _ptrs(A_Mel),
+             _ptr(n_iter))
+    if st is not None:
+        args += (_settings_array(st),)
+    entry = getattr(lib, f"snmf_run_basis_train_{'audio' if ts is None else 'signals'}_batch_{form}")
+    _lib.check(entry(ctx._h, C.byref(q), C.byref(sp), alpha, _ptr(mel), M, *args))
     if info is not None:
         info["T"] = list(Ts)
         info["n_iter"] = [[int(v) for v in n_iter[2 * k:2 * k + 2]] for k in range(n)]
@@ -554,7 +532,10 @@ def _run_basis_dnmf_audio_batch(xs, ds, B, p, *, ctx, mel, h0, precision, dtype,
     """ONE call across the C ABI (snmf_run_basis_dnmf_audio_batch_f64; precision="fp64": _fp64) for every waveform pair: the
     waveforms go up as one slab, the three feature sets of all problems are formed in HBM by shared launches, and the three
     solves are three resident batches.  Every error that needs no device is raised before the library is loaded.
-    A sequence for p["R_x"] / p["R_d"] or settings per problem: snmf_run_basis_dnmf_audio_batch_ranks_fp64 (fp64 only)."""
+    A sequence for p["R_x"] / p["R_d"] or settings per problem: snmf_run_basis_dnmf_audio_batch_ranks_fp64 (fp64 only).  One body
+    for both: the uniform call is a rank pair n times (batch._dnmf_rank_inputs, _dnmf_rank_params), and only the entry and the
+    head of its argument list differ.  The host draw is rand(r_k, T_k) per problem in list order from one generator; the device
+    draw of problem k is philox_uniform(random_seed + k, r_k, T_k)."""
     _check_precision(precision)
     _check_dtype(dtype)
     f64 = precision == "fp64"
@@ -567,11 +548,9 @@ def _run_basis_dnmf_audio_batch(xs, ds, B, p, *, ctx, mel, h0, precision, dtype,
         raise SnmfError(1, "the batch is empty: xs must hold at least one waveform")
     if len(ds) != n:
         raise SnmfError(1, f"{n} clean and {len(ds)} noise waveforms: one of each per problem")
-    from .batch import _dnmf_rank_pairs
-    pairs = _dnmf_rank_pairs(p["R_x"], p["R_d"], n, settings, precision)
-    if pairs is None:
-        R_x, R_d = int(p["R_x"]), int(p["R_d"])
-        r = R_x + R_d
+    pairs = _dnmf_rank_pairs(p["R_x"], p["R_d"], n, settings, precision)  # None: two scalars, the uniform entry
+    Rxs, Rds = pairs or ([int(p["R_x"])] * n, [int(p["R_d"])] * n)
+    rs = [a + b for a, b in zip(Rxs, Rds)]
     K = 2 * int(p.get("Splice", 0)) + 1
     M = int(p["F_order"]) if mel else 0
     F = K * M if mel else K * (int(p["fftlength"]) // 2 + 1)
@@ -579,72 +558,13 @@ def _run_basis_dnmf_audio_batch(xs, ds, B, p, *, ctx, mel, h0, precision, dtype,
     for k, T in enumerate(Ts):
         if T < 1:
             raise SnmfError(3, f"the signals of problem {k} are shorter than one analysis frame")
-    if pairs is not None:
-        return _dnmf_audio_batch_ranks(xs, ds, B, p, pairs, settings, F, M, Ts, ctx=ctx, mel=mel, h0=h0, dtype=dtype, info=info)
-    if isinstance(B, (list, tuple)):
-        if len(B) != n:
-            raise SnmfError(3, f"B is a list of {len(B)}, the batch has {n} problems")
-        Bs = [np.asfortranarray(b, dtype=np.float64) for b in B]
-    else:
-        Bs = [np.asfortranarray(B, dtype=np.float64)] * n
-    for b in Bs:
-        if b.shape != (F, r):
-            raise SnmfError(3, f"B is {b.shape}, expected ({F}, {r})")
     seed = int(p.get("random_seed", 1))
-    H0s = seeds = None
-    if isinstance(h0, str):
-        if h0 not in ("host", "device"):
-            raise SnmfError(3, f"h0 must be 'host', 'device' or a list of {n} arrays (r x T_k each)")
-    else:
-        if not isinstance(h0, (list, tuple)) or len(h0) != n:
-            raise SnmfError(3, f"h0 must be 'host', 'device' or a list of {n} arrays (r x T_k each)")
-        H0s = [np.asfortranarray(h, dtype=np.float64) for h in h0]
-        for h, T in zip(H0s, Ts):
-            if h.shape != (r, T):
-                raise SnmfError(3, f"init_h is {h.shape}, expected ({r}, {T})")
-    beta, max_iter, conv_eps, cost_check, lam = _solver_scalars(p)
+    Bs, H0s = _dnmf_rank_inputs(B, h0, rs, F, Ts, ("host", "device"), p)  # "host": in list order from one generator
+    q, sarr = _dnmf_rank_params(p, settings, n, F, max(rs))
     if f64:  # (after the reference's own errors, before any device work)
         _fp64_rules(dtype, None, "the fp64 DNMF batch")
-    if H0s is None and h0 == "host":  # what sparse_nmf draws for solve 1 of each problem, in list order from one generator
-        rs = np.random.RandomState(seed if seed > 0 else None)
-        H0s = [np.asfortranarray(rs.random_sample((r, T))) for T in Ts]
-    if H0s is None:
-        seeds = np.array([seed + k for k in range(n)], np.uint64)
-    q = _make_params(F, 1, r, beta, max_iter, conv_eps, cost_check, True, 0, lam, None, None)
+    seeds = np.array([seed + k for k in range(n)], np.uint64) if H0s is None else None  # "device": philox_uniform(seed + k, r_k, T_k)
     melm = frontend._mel_table(p, sdt) if mel else None
-    sp, _win = frontend._params(p)
-
-    lib = _lib.load()
-    ctx = ctx or default_context()
-    B_hat = [np.empty((F, r), order="F") for _ in Ts]
-    A_hat = [np.empty((r, T), order="F") for T in Ts]
-    n_iter = np.zeros(3 * n, np.int32)
-    n_x, n_d = (np.array([a.size for a in v], np.int64) for v in (xs, ds))
-    ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None  # noqa: E731
-    ptrs = lambda arrs: (C.c_void_p * n)(*[a.ctypes.data for a in arrs]) if arrs is not None else None  # noqa: E731
-    fn = lib.snmf_run_basis_dnmf_audio_batch_fp64 if f64 else lib.snmf_run_basis_dnmf_audio_batch_f64
-    _lib.check(fn(ctx._h, C.byref(q), C.byref(sp), R_x, R_d, n, ptrs(xs), ptr(n_x), ptrs(ds), ptr(n_d), ptr(melm), M, ptrs(Bs),
-                  ptrs(H0s), ptr(seeds), ptrs(B_hat), ptrs(A_hat), ptr(n_iter)))
-    if info is not None:
-        info["n_iter"] = [[int(v) for v in n_iter[3 * k:3 * k + 3]] for k in range(n)]
-        info["T"] = list(Ts)
-    return list(zip(B_hat, A_hat))
-
-
-def _dnmf_audio_batch_ranks(xs, ds, B, p, pairs, settings, F, M, Ts, *, ctx, mel, h0, dtype, info):
-    """_run_basis_dnmf_audio_batch with a rank pair per problem, fp64 (snmf_run_basis_dnmf_audio_batch_ranks_fp64): the waveforms
-    and the frame counts are checked.  The host draw is rand(r_k, T_k) per problem in list order from one generator; the device
-    draw of problem k is philox_uniform(random_seed + k, r_k, T_k)."""
-    from .batch import _dnmf_rank_inputs, _dnmf_rank_params
-    n = len(xs)
-    Rxs, Rds = pairs
-    rs = [a + b for a, b in zip(Rxs, Rds)]
-    seed = int(p.get("random_seed", 1))
-    Bs, H0s = _dnmf_rank_inputs(B, h0, rs, F, Ts, ("host", "device"), seed)
-    q, sarr = _dnmf_rank_params(p, settings, n, F, max(rs))
-    _fp64_rules(dtype, None, "the fp64 DNMF batch")
-    seeds = np.array([seed + k for k in range(n)], np.uint64) if H0s is None else None
-    melm = frontend._mel_table(p, np.float64) if mel else None
     sp, _win = frontend._params(p)
 
     lib = _lib.load()
@@ -654,11 +574,13 @@ def _dnmf_audio_batch_ranks(xs, ds, B, p, pairs, settings, F, M, Ts, *, ctx, mel
     n_iter = np.zeros(3 * n, np.int32)
     n_x, n_d = (np.array([a.size for a in v], np.int64) for v in (xs, ds))
     rx, rd = np.array(Rxs, np.int32), np.array(Rds, np.int32)
-    ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None  # noqa: E731
-    ptrs = lambda arrs: (C.c_void_p * n)(*[a.ctypes.data for a in arrs]) if arrs is not None else None  # noqa: E731
-    _lib.check(lib.snmf_run_basis_dnmf_audio_batch_ranks_fp64(ctx._h, C.byref(q), C.byref(sp), ptr(rx), ptr(rd), sarr, n, ptrs(xs), ptr(n_x),
-                                                              ptrs(ds), ptr(n_d), ptr(melm), M, ptrs(Bs), ptrs(H0s), ptr(seeds), ptrs(B_hat),
-                                                              ptrs(A_hat), ptr(n_iter)))
+    if pairs is not None:
+        entry, head = lib.snmf_run_basis_dnmf_audio_batch_ranks_fp64, (_ptr(rx), _ptr(rd), sarr)
+    else:
+        entry = lib.snmf_run_basis_dnmf_audio_batch_fp64 if f64 else lib.snmf_run_basis_dnmf_audio_batch_f64
+        head = (Rxs[0], Rds[0])
+    _lib.check(entry(ctx._h, C.byref(q), C.byref(sp), *head, n, _ptrs(xs), _ptr(n_x), _ptrs(ds), _ptr(n_d),
+                     _ptr_or_null(melm), M, _ptrs(Bs), _ptrs(H0s), _ptr_or_null(seeds), _ptrs(B_hat), _ptrs(A_hat), _ptr(n_iter)))
     if info is not None:
         info["n_iter"] = [[int(v) for v in n_iter[3 * k:3 * k + 3]] for k in range(n)]
         info["T"] = list(Ts)
