@@ -738,6 +738,40 @@ int snmf_online_batch_set_state(snmf_online_batch* b, int32_t n, const int32_t* 
 int snmf_online_batch_trace(snmf_online_batch* b, int32_t k, snmf_online_frame* out, int64_t cap, int64_t* n);
 void snmf_online_batch_destroy(snmf_online_batch* b);
 
+/* ---- the single-stream separator (snmf_online): its state g as a record, and its next file in place ----
+ * Declared here because the record is the one above: the same snmf_online_state_info, the same fields at the offsets
+ * snmf_online_state_field reports, SNMF_ONLINE_STATE_VERSION 1.  A record taken from either kind of separator is accepted
+ * by the other of the same configuration (precision, mode, geometry, class count). */
+/* Added within 5.  The geometry and record size of this separator as it is now (after snmf_online_set_mel /
+ * snmf_online_set_classes), field by field what snmf_online_batch_state_info reports for a batch of its configuration:
+ * R_a, m_a and P_len_l are 1 where unused, elem_size is 4 (snmf_online_create) or 8 (snmf_online_create_f64), F_order is 0
+ * outside Mel mode. */
+int snmf_online_stream_state_info(snmf_online* o, snmf_online_state_info* out);
+/* Added within 5.  One record of info.bytes into `record` (cap bytes).  Allowed between process calls, also before the
+ * first one; a flushed separator or one whose earlier call failed returns SNMF_ERR_STATE.  The separator is not disturbed.
+ * One gather launch and one copy. */
+int snmf_online_get_state(snmf_online* o, void* record, int64_t cap);
+/* Added within 5.  The separator takes the record (`bytes` long).  Allowed on a fresh, running or finished separator; it is
+ * then a running stream at frame l with an empty trace, and its next frames have the bits of the stream the record came
+ * from.  The header checks and their status codes are those of snmf_online_batch_set_state: bad magic or version, or too
+ * few bytes: SNMF_ERR_INVALID; another element size, mode, geometry or class count: SNMF_ERR_DIM (the message names the
+ * field); n_push < 0, update_switch < 1, l < 1 or a pending count >= frameshift: SNMF_ERR_INVALID; a separator whose earlier
+ * call failed: SNMF_ERR_STATE.  A refused call changes nothing.  One upload, one scatter launch and the dictionary refresh
+ * a creation does. */
+int snmf_online_set_state(snmf_online* o, const void* record, int64_t bytes);
+/* Added within 5.  src/NTF_sep_event_RT.m:27-38 + init_buff for a finished (flushed) or never-fed separator: it starts a new
+ * recording in place, with the semantics of snmf_online_batch_restart / _restart_mel for one stream.  Every piece of state
+ * returns to what creation gives with these inputs.  B_DFT_d (F x R_d, fp64) NULL keeps the current fp64 master as it is
+ * (load('B_D_u.mat'), no fp32 round trip) and the fixed columns of :328; a new B_DFT_d also becomes the fixed columns.
+ * B_Mel_d (F_order x R_d, fp64) has the same rules on a Mel-mode separator; non-NULL outside Mel mode: SNMF_ERR_STATE.  H0
+ * (R_x + R_d) / Ad_blk0 (R_a x m_a) NULL: the values the separator last started with.  A separator that has consumed samples
+ * and was not flushed, one whose earlier call failed, or the entry of the other precision: SNMF_ERR_STATE.  Ordered on the
+ * context's stream; it does not synchronise beyond the uploads. */
+int snmf_online_restart_f32(snmf_online* o, const double* B_DFT_d, const double* B_Mel_d, const float* H0, const float* Ad_blk0);
+/* Added within 5.  snmf_online_restart_f32 for a separator made by snmf_online_create_f64: the draws cross in fp64.  (Mel mode
+ * is not an fp64 mode: a non-NULL B_Mel_d is SNMF_ERR_STATE.) */
+int snmf_online_restart_f64(snmf_online* o, const double* B_DFT_d, const double* B_Mel_d, const double* H0, const double* Ad_blk0);
+
 /* ---- multi-GPU solves: one process, several devices ------------------------------------- */
 /* The reference's host is ONE MATLAB interpreter (run_basis_train.m:88, run_basis_DNMF.m:40,47,53 call sparse_nmf from
  * a single thread), so the MEX shim cannot bring a process-per-GPU launcher with it: this is the entry that puts the

@@ -8,6 +8,7 @@
 // adaptation).  Included by snmf_tu_online.hip only.
 #pragma once
 #include "snmf_online_common.h"
+#include "snmf_online_batch_common.h"  // ostate_xfer: the state record's gather / scatter
 
 namespace snmf {
 
@@ -483,6 +484,29 @@ __global__ __launch_bounds__(kWaNT) void k_wadapt(WAdaptArgs a) {
 #ifdef SNMF_PROF_WA
     if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&g_wa_prof[9], 1ull);
 #endif
+}
+
+// The separator's state g into (k_ostate_get) / out of (k_ostate_put) one staging record: the batched separator's ostate_xfer
+// on the single-stream arrays, which are the batch's with S = 1 and the slot list {0}.  Grid (1, kStN, kStParts).  `l`: the
+// 1-based index of the next frame (a put reads it from the record).  In Mel mode a.Bm is the Mel master; a.Bdf stays NULL,
+// the fp32 mirrors are rebuilt by k_omirror behind a put.
+__global__ __launch_bounds__(256) void k_ostate_get(OStateArgs<float> a, int64_t l) {
+    const int slot0 = 0;
+    const int64_t l0 = l;
+    a.slots = &slot0;
+    a.l = &l0;
+    ostate_xfer<float, false>(a);
+}
+__global__ __launch_bounds__(256) void k_ostate_put(OStateArgs<float> a) {
+    const int slot0 = 0;
+    a.slots = &slot0;
+    a.l = nullptr;
+    ostate_xfer<float, true>(a);
+}
+
+// the fp32 mirror of n fp64 dictionary entries, rounded as k_oassemble rounds a re-assembled column
+__global__ __launch_bounds__(256) void k_omirror(const double* __restrict__ src, float* __restrict__ dst, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) dst[i] = (float)src[i];
 }
 
 }  // namespace snmf

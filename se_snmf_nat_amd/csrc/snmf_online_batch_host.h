@@ -509,61 +509,14 @@ int obatch_process(H* o, const T* const* pcm, const int64_t* n, const int32_t* f
 // Get-state / set-state (snmf_online_batch_state_info / _get_state / _set_state; include/snmf.h).  A stream's state g is
 // one record: [magic, version, snmf_online_state_info | the fields of snmf_online_state_field].  The device arrays cross
 // through one staging slab of records and one kernel (k_obstate_get / _put); the host state (pending, hist, l) is written
-// into / read from the same records here.
+// into / read from the same records here.  The record's layout, header checks and host fields are snmf_online_host.h's,
+// shared with the single-stream separator.
 // ---------------------------------------------------------------------------------------------
-struct OStateHeader {
-    uint32_t magic, version;
-    snmf_online_state_info info;
-};
-static_assert(sizeof(OStateHeader) == 80, "record header: 8 bytes and a tight snmf_online_state_info");
-
-// The layout of a record under `q`: per field its byte offset, element count and snmf_online_state_type.  Every offset is a
-// multiple of 8.  Returns the record's bytes, or -1 for an info no batch reports.
-inline int64_t ostate_layout(const snmf_online_state_info& q, int64_t* off, int64_t* cnt, int32_t* typ) {
-    if ((q.elem_size != 4 && q.elem_size != 8) || q.F < 1 || q.F_order < 0 || q.R_x < 1 || q.R_d < 1 || q.R_a < 1 || q.m_a < 1 ||
-        q.P_len_l < 1 || q.frameshift < 1 || q.framelength < q.frameshift || q.ntail < 0 || q.n_classes < 0 || (q.mel && q.F_order < 1))
-        return -1;
-    const int32_t E = q.elem_size == 4 ? SNMF_STATE_F32 : SNMF_STATE_F64;
-    const int64_t F = q.F, nt = q.ntail;
-    struct Row { int f; int64_t n; int32_t t; };
-    const Row rows[SNMF_STATE_FIELD_COUNT] = {
-        // the scalars first, then the arrays
-        {SNMF_STATE_N_PUSH, 1, SNMF_STATE_I32}, {SNMF_STATE_UPDATE_SWITCH, 1, SNMF_STATE_I32}, {SNMF_STATE_L, 1, SNMF_STATE_I64},
-        {SNMF_STATE_PENDING_COUNT, 1, SNMF_STATE_I32},
-        {SNMF_STATE_XM_TILDE, F, E}, {SNMF_STATE_LAMBDA_DAV, F, E}, {SNMF_STATE_R_BLK, F * q.P_len_l, E},
-        {SNMF_STATE_LAMBDA_D_BLK, F * q.m_a, E}, {SNMF_STATE_AD_BLK, (int64_t)q.R_a * q.m_a, E},
-        {SNMF_STATE_B_DFT_D, F * q.R_d, SNMF_STATE_F64}, {SNMF_STATE_B_FIX, F * q.R_d, SNMF_STATE_F64},
-        {SNMF_STATE_B_MEL_D, q.mel ? (int64_t)q.F_order * q.R_d : 0, SNMF_STATE_F64},
-        {SNMF_STATE_H0, (int64_t)q.R_x + q.R_d, E}, {SNMF_STATE_AD_BLK0, (int64_t)q.R_a * q.m_a, E},
-        {SNMF_STATE_Y_HIST, (int64_t)q.framelength - q.frameshift, E}, {SNMF_STATE_PENDING, (int64_t)q.frameshift, E},
-        {SNMF_STATE_X_TILDE_TAIL, nt, E}, {SNMF_STATE_X_HAT_TAIL, q.class_outputs ? nt : 0, E},
-        {SNMF_STATE_D_HAT_TAIL, q.class_outputs ? nt : 0, E}, {SNMF_STATE_CLASS_TAILS, nt * q.n_classes, E},
-    };
-    int64_t at = (int64_t)sizeof(OStateHeader);
-    for (const Row& w : rows) {
-        const int64_t sz = (w.t == SNMF_STATE_F32 || w.t == SNMF_STATE_I32) ? 4 : 8;
-        if (w.f == SNMF_STATE_UPDATE_SWITCH) at -= 4;  // n_push and update_switch are one pair of int32 (OnlineDev's head)
-        off[w.f] = at;
-        cnt[w.f] = w.n;
-        typ[w.f] = w.t;
-        at = (at + w.n * sz + 7) / 8 * 8;
-    }
-    return at;
-}
-
 template <class H>
 void obatch_state_info(const H* o, snmf_online_state_info* q) {
     int mel = 0, mel_conv = 0, n1 = 0;
     obm_state_mode(o, &mel, &mel_conv, &n1);
-    *q = snmf_online_state_info{};
-    q->elem_size = (int32_t)sizeof(typename H::elem);
-    q->mel = mel; q->mel_conv = mel_conv; q->F = o->F; q->F_order = mel ? n1 : 0;
-    q->R_x = o->p.R_x; q->R_d = o->p.R_d; q->R_a = o->Ra; q->m_a = o->ma; q->P_len_l = o->Pl;
-    q->framelength = o->p.framelength; q->frameshift = o->p.frameshift; q->ntail = (int32_t)o->ntail;
-    q->class_outputs = o->p.class_outputs ? 1 : 0; q->n_classes = o->n_cls;
-    int64_t off[SNMF_STATE_FIELD_COUNT], cnt[SNMF_STATE_FIELD_COUNT];
-    int32_t typ[SNMF_STATE_FIELD_COUNT];
-    q->bytes = ostate_layout(*q, off, cnt, typ);
+    ostate_info_of(o, mel, mel_conv, n1, o->ntail, q);
 }
 
 // the listed slots are valid and distinct, and the batch is usable
@@ -585,17 +538,9 @@ int obatch_state_slots(const H* o, int32_t n, const int32_t* slots, const char* 
 // the kernel's view of the batch and of a record under `q`
 template <class H, typename T = typename H::elem>
 OStateArgs<T> obatch_state_args(H* o, const snmf_online_state_info& q) {
-    int64_t off[SNMF_STATE_FIELD_COUNT], cnt[SNMF_STATE_FIELD_COUNT];
-    int32_t typ[SNMF_STATE_FIELD_COUNT];
-    ostate_layout(q, off, cnt, typ);
     OStateArgs<T> a{};
-    a.slots = o->rs_slots; a.slab = o->st_slab; a.stride = q.bytes; a.off_l = off[SNMF_STATE_L];
-    a.off[kStXm] = off[SNMF_STATE_XM_TILDE]; a.off[kStLam] = off[SNMF_STATE_LAMBDA_DAV]; a.off[kStRblk] = off[SNMF_STATE_R_BLK];
-    a.off[kStLdblk] = off[SNMF_STATE_LAMBDA_D_BLK]; a.off[kStAdblk] = off[SNMF_STATE_AD_BLK]; a.off[kStBd] = off[SNMF_STATE_B_DFT_D];
-    a.off[kStBfix] = off[SNMF_STATE_B_FIX]; a.off[kStBmd] = off[SNMF_STATE_B_MEL_D]; a.off[kStH0] = off[SNMF_STATE_H0];
-    a.off[kStAd0] = off[SNMF_STATE_AD_BLK0]; a.off[kStTail] = off[SNMF_STATE_X_TILDE_TAIL]; a.off[kStTailX] = off[SNMF_STATE_X_HAT_TAIL];
-    a.off[kStTailD] = off[SNMF_STATE_D_HAT_TAIL]; a.off[kStTailC] = off[SNMF_STATE_CLASS_TAILS]; a.off[kStDev] = off[SNMF_STATE_N_PUSH];
-    a.off[kStBdf] = 0;
+    ostate_arg_offsets(q, &a);
+    a.slots = o->rs_slots; a.slab = o->st_slab;
     a.Xm_tilde = o->Xm_tilde; a.lambda_dav = o->lambda_dav; a.r_blk = o->r_blk; a.ldblk = o->ldblk; a.adblk = o->adblk; a.H0 = o->H0;
     a.Ad0 = o->Ad0; a.tail = o->tail; a.tail_x = o->tail_x; a.tail_d = o->tail_d; a.tail_c = o->n_cls ? o->tail_c : nullptr;
     a.B = o->B; a.Bfix = o->Bfix; a.dev = o->dev;
@@ -643,37 +588,9 @@ int obatch_get_state(H* o, int32_t n, const int32_t* slots, void* records, int64
     HIP_TRY(hipMemcpyAsync(records, o->st_slab, total, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     // the header, the host state, and zeros wherever the device wrote nothing (two gets of one state are the same bytes)
-    int64_t off[SNMF_STATE_FIELD_COUNT], cnt[SNMF_STATE_FIELD_COUNT];
-    int32_t typ[SNMF_STATE_FIELD_COUNT];
-    ostate_layout(q, off, cnt, typ);
-    std::vector<std::pair<int64_t, int64_t>> span;  // [begin, end) of every field, in record order
-    for (int f = 0; f < SNMF_STATE_FIELD_COUNT; ++f)
-        span.push_back({off[f], off[f] + cnt[f] * ((typ[f] == SNMF_STATE_F32 || typ[f] == SNMF_STATE_I32) ? 4 : 8)});
-    std::sort(span.begin(), span.end());
     for (int i = 0; i < n; ++i) {
         const int s = slots[i];
-        unsigned char* rec = (unsigned char*)records + (size_t)i * rb;
-        OStateHeader h{};
-        h.magic = SNMF_ONLINE_STATE_MAGIC;
-        h.version = SNMF_ONLINE_STATE_VERSION;
-        h.info = q;
-        std::memcpy(rec, &h, sizeof h);
-        int64_t at = (int64_t)sizeof h;
-        for (const auto& sp : span) {  // the gaps between fields
-            if (sp.first > at) std::memset(rec + at, 0, (size_t)(sp.first - at));
-            at = std::max(at, sp.second);
-        }
-        if ((int64_t)rb > at) std::memset(rec + at, 0, rb - (size_t)at);
-        const int64_t l = o->l[s] + 1;
-        const int32_t np = (int32_t)o->pending[s].size();
-        std::memcpy(rec + off[SNMF_STATE_L], &l, 8);
-        std::memcpy(rec + off[SNMF_STATE_PENDING_COUNT], &np, 4);
-        T* hist = (T*)(rec + off[SNMF_STATE_Y_HIST]);
-        T* pend = (T*)(rec + off[SNMF_STATE_PENDING]);
-        std::fill_n(hist, (size_t)cnt[SNMF_STATE_Y_HIST], T(0));
-        std::copy(o->hist[s].begin(), o->hist[s].end(), hist);
-        std::fill_n(pend, (size_t)cnt[SNMF_STATE_PENDING], T(0));
-        std::copy(o->pending[s].begin(), o->pending[s].end(), pend);
+        ostate_write_host<T>((unsigned char*)records + (size_t)i * rb, q, o->l[s], o->pending[s], o->hist[s]);
     }
     return SNMF_OK;
 }
@@ -690,37 +607,7 @@ int obatch_set_state(H* o, int32_t n, const int32_t* slots, const void* records,
     int32_t typ[SNMF_STATE_FIELD_COUNT];
     ostate_layout(q, off, cnt, typ);
     // every header against the handle, before the device is touched
-    for (int i = 0; i < n; ++i) {
-        // record i begins where the handle's record size puts it; a record of another size fails its header check below
-        if (bytes < 0 || (uint64_t)bytes < (size_t)i * rb + sizeof(OStateHeader))
-            return fail(SNMF_ERR_INVALID, "records holds %lld bytes: too few for the header of record %d", (long long)bytes, i);
-        const unsigned char* rec = (const unsigned char*)records + (size_t)i * rb;
-        OStateHeader h;
-        std::memcpy(&h, rec, sizeof h);
-        if (h.magic != SNMF_ONLINE_STATE_MAGIC) return fail(SNMF_ERR_INVALID, "record %d: not a stream state (bad magic)", i);
-        if (h.version != SNMF_ONLINE_STATE_VERSION)
-            return fail(SNMF_ERR_INVALID, "record %d: layout version %u, this library reads %d", i, h.version, SNMF_ONLINE_STATE_VERSION);
-        const snmf_online_state_info& r = h.info;
-#define OSTATE_SAME(field)                                                                                                      \
-    if (r.field != q.field)                                                                                                     \
-        return fail(SNMF_ERR_DIM, "record %d: " #field " = %d, the batch has " #field " = %d", i, (int)r.field, (int)q.field);
-        OSTATE_SAME(elem_size) OSTATE_SAME(mel) OSTATE_SAME(mel_conv) OSTATE_SAME(F) OSTATE_SAME(F_order) OSTATE_SAME(R_x) OSTATE_SAME(R_d)
-        OSTATE_SAME(R_a) OSTATE_SAME(m_a) OSTATE_SAME(P_len_l) OSTATE_SAME(framelength) OSTATE_SAME(frameshift) OSTATE_SAME(ntail)
-        OSTATE_SAME(class_outputs) OSTATE_SAME(n_classes)
-#undef OSTATE_SAME
-        if (r.bytes != q.bytes) return fail(SNMF_ERR_INVALID, "record %d: %lld bytes, the layout gives %lld", i, (long long)r.bytes, (long long)q.bytes);
-        if ((uint64_t)bytes < (size_t)(i + 1) * rb)
-            return fail(SNMF_ERR_INVALID, "records holds %lld bytes, %d records need %zu", (long long)bytes, n, total);
-        int32_t dv[2], np;
-        int64_t l;
-        std::memcpy(dv, rec + off[SNMF_STATE_N_PUSH], 8);
-        std::memcpy(&l, rec + off[SNMF_STATE_L], 8);
-        std::memcpy(&np, rec + off[SNMF_STATE_PENDING_COUNT], 4);
-        if (dv[0] < 0) return fail(SNMF_ERR_INVALID, "record %d: n_push = %d", i, dv[0]);
-        if (dv[1] < 1) return fail(SNMF_ERR_INVALID, "record %d: update_switch = %d", i, dv[1]);
-        if (l < 1) return fail(SNMF_ERR_INVALID, "record %d: l = %lld", i, (long long)l);
-        if (np < 0 || np >= q.frameshift) return fail(SNMF_ERR_INVALID, "record %d: %d pending samples at frameshift %d", i, np, q.frameshift);
-    }
+    for (int i = 0; i < n; ++i) SN_TRY(ostate_check_record(records, bytes, i, n, q, off, "batch"));
     (void)hipGetLastError();  // clean sticky error state, see PLAN_CHECK
     HIP_TRY(hipSetDevice(o->ctx->device));
     hipStream_t st = o->ctx->stream;
@@ -741,16 +628,7 @@ int obatch_set_state(H* o, int32_t n, const int32_t* slots, const void* records,
     }
     for (int i = 0; i < n; ++i) {
         const int s = slots[i];
-        const unsigned char* rec = (const unsigned char*)records + (size_t)i * rb;
-        int64_t l;
-        int32_t np;
-        std::memcpy(&l, rec + off[SNMF_STATE_L], 8);
-        std::memcpy(&np, rec + off[SNMF_STATE_PENDING_COUNT], 4);
-        const T* hist = (const T*)(rec + off[SNMF_STATE_Y_HIST]);
-        const T* pend = (const T*)(rec + off[SNMF_STATE_PENDING]);
-        o->hist[s].assign(hist, hist + cnt[SNMF_STATE_Y_HIST]);
-        o->pending[s].assign(pend, pend + np);
-        o->l[s] = l - 1;
+        ostate_read_host<T>((const unsigned char*)records + (size_t)i * rb, q, &o->l[s], &o->pending[s], &o->hist[s]);
         o->finished[s] = 0;
         o->trace[s].clear();  // the trace goes on from frame l
     }

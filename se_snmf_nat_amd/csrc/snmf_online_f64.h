@@ -16,6 +16,7 @@
 // Included by snmf_tu_online_f64.hip only.
 #pragma once
 #include "snmf_online_common.h"
+#include "snmf_online_batch_common.h"  // ostate_xfer: the state record's gather / scatter
 #include "snmf_online_f64_core.h"
 
 namespace snmf {
@@ -373,6 +374,22 @@ __global__ void k_oola64(const double* __restrict__ syn, int n_new, int l0, int 
         const int j = (int)(e / hop), s = (int)(e - (size_t)j * hop);
         oola_sample<double>(syn, i_first + j, s, l0, delay, sz, hop, nov, outf, out16, e);  // global frame l = l0 + i_first + j
     }
+}
+
+// The separator's state g into (k_ostate_get64) / out of (k_ostate_put64) one staging record: the batched separator's
+// ostate_xfer on the single-stream arrays (S = 1, slot list {0}), as k_ostate_get / _put in snmf_online.h.
+__global__ __launch_bounds__(256) void k_ostate_get64(OStateArgs<double> a, int64_t l) {
+    const int slot0 = 0;
+    const int64_t l0 = l;
+    a.slots = &slot0;
+    a.l = &l0;
+    ostate_xfer<double, false>(a);
+}
+__global__ __launch_bounds__(256) void k_ostate_put64(OStateArgs<double> a) {
+    const int slot0 = 0;
+    a.slots = &slot0;
+    a.l = nullptr;
+    ostate_xfer<double, true>(a);
 }
 
 }  // namespace snmf

@@ -14,3 +14,8 @@ int online_f64_set_classes(OnlineF64* o, int32_t event_num, const int32_t* event
 void online_f64_class_counts(OnlineF64* o, int* n_event, int* n_noise);  // (1, 1) without a partition
 int online_f64_get_basis(OnlineF64* o, double* Bd, int64_t ld);
 int online_f64_trace(OnlineF64* o, snmf_online_frame* out, int64_t cap, int64_t* n);
+// the state g as a record, and the next file in place (snmf_online_stream_state_info / _get_state / _set_state / _restart_f64)
+void online_f64_state_info(OnlineF64* o, snmf_online_state_info* out);
+int online_f64_get_state(OnlineF64* o, void* record, int64_t cap);
+int online_f64_set_state(OnlineF64* o, const void* record, int64_t bytes);
+int online_f64_restart(OnlineF64* o, const double* Bd, const double* H0, const double* Ad);

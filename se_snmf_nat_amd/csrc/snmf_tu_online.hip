@@ -205,8 +205,7 @@ extern "C" int snmf_online_create(snmf_ctx* ctx, const snmf_online_params* p, co
     hipMemcpyAsync(o->Bfix, hB.data() + (size_t)F * p->R_x, (size_t)F * p->R_d * 8, hipMemcpyHostToDevice, st);  // B_Mel_d in DFT mode (:328)
     hipMemcpyAsync(o->Bf, Bx, (size_t)F * p->R_x * 4, hipMemcpyHostToDevice, st);
     hipMemcpyAsync(o->Bf + (size_t)F * p->R_x, Bd, (size_t)F * p->R_d * 4, hipMemcpyHostToDevice, st);
-    online_upload_state(o, H0, win_stft, win_istft, htw);
-    if (p->adapt_train_N) hipMemcpyAsync(o->adblk, Ad0, (size_t)o->Ra * o->ma * 4, hipMemcpyHostToDevice, st);  // column-major R_a x m_a
+    online_upload_state(o, H0, Ad0, win_stft, win_istft, htw);
     hipError_t e = hipStreamSynchronize(st);
     if (e != hipSuccess) {
         snmf_online_destroy(o);
@@ -644,4 +643,84 @@ extern "C" int snmf_online_get_basis_f64(snmf_online* o, double* Bd, int64_t ld)
     if (!o || !Bd) return fail(SNMF_ERR_INVALID, "NULL argument");
     if (o->f64) return online_f64_get_basis(o->f64, Bd, ld);
     return online_get_basis_f64(o, Bd, ld);
+}
+
+// ---- the state g as a record, and the next file in place (the driver's last section; kernels k_ostate_get / k_ostate_put) ----
+static void om_state_mode(const snmf_online* o, int* mel, int* mel_conv, int* n1) {
+    *mel = o->mel;
+    *mel_conv = o->mel_conv;
+    *n1 = o->n1;
+}
+
+// the record's B_Mel_d goes to / comes from the Mel master
+static int om_state_launch(snmf_online* o, const OStateArgs<float>& a0, int64_t l, bool put) {
+    OStateArgs<float> a = a0;
+    a.Bm = o->mel ? o->Bm : nullptr;
+    a.n1 = o->n1;
+    if (put) hipLaunchKernelGGL(k_ostate_put, dim3(1, kStN, kStParts), dim3(256), 0, o->ctx->stream, a);
+    else hipLaunchKernelGGL(k_ostate_get, dim3(1, kStN, kStParts), dim3(256), 0, o->ctx->stream, a, l);
+    HIP_TRY(hipGetLastError());
+    return SNMF_OK;
+}
+
+// The noise columns of the fp64 masters changed (a restart, a set-state): their fp32 mirrors, and the dictionary of the
+// frame solves' plans as creation / snmf_online_set_mel and the adaptation leave it.
+static int om_refresh_dict(snmf_online* o) {
+    const snmf_online_params& p = o->p;
+    hipStream_t st = o->ctx->stream;
+    const size_t nD = (size_t)o->F * p.R_d, xD = (size_t)o->F * p.R_x;
+    hipLaunchKernelGGL(k_omirror, dim3(grid_for(nD)), dim3(256), 0, st, (const double*)(o->B + xD), o->Bf + xD, nD);
+    HIP_TRY(hipGetLastError());
+    if (o->mel) {
+        const size_t nM = (size_t)o->n1 * p.R_d, xM = (size_t)o->n1 * p.R_x;
+        hipLaunchKernelGGL(k_omirror, dim3(grid_for(nM)), dim3(256), 0, st, (const double*)(o->Bm + xM), o->Bmf + xM, nM);
+        HIP_TRY(hipGetLastError());
+    }
+    const double* W = o->mel ? o->Bm : o->B;
+    SN_TRY(set_w<double>(o->hp, W, o->Fs, 1));
+    if (o->hb) SN_TRY(set_w<double>(o->hb, W, o->Fs, 1));  // (the one-launch plan of a fixed dictionary holds its own copy)
+    return SNMF_OK;
+}
+
+extern "C" int snmf_online_stream_state_info(snmf_online* o, snmf_online_state_info* out) {
+    if (!o || !out) return fail(SNMF_ERR_INVALID, "NULL argument");
+    if (o->f64) online_f64_state_info(o->f64, out);
+    else online_state_info(o, out);
+    return SNMF_OK;
+}
+
+extern "C" int snmf_online_get_state(snmf_online* o, void* record, int64_t cap) {
+    if (!o) return fail(SNMF_ERR_INVALID, "online handle is NULL");
+    if (o->f64) return online_f64_get_state(o->f64, record, cap);
+    return online_get_state(o, record, cap);
+}
+
+extern "C" int snmf_online_set_state(snmf_online* o, const void* record, int64_t bytes) {
+    if (!o) return fail(SNMF_ERR_INVALID, "online handle is NULL");
+    if (o->f64) return online_f64_set_state(o->f64, record, bytes);
+    return online_set_state(o, record, bytes);
+}
+
+extern "C" int snmf_online_restart_f32(snmf_online* o, const double* Bd, const double* Bmd, const float* H0, const float* Ad) {
+    if (!o) return fail(SNMF_ERR_INVALID, "online handle is NULL");
+    if (o->f64) return fail(SNMF_ERR_STATE, "snmf_online_restart_f32 needs a separator made by snmf_online_create; an fp64 one takes snmf_online_restart_f64");
+    if (Bmd && !o->mel) return fail(SNMF_ERR_STATE, "B_Mel_d given to a separator that is not in Mel mode");
+    SN_TRY(online_restart_check(o));
+    (void)hipGetLastError();  // clean sticky error state, see PLAN_CHECK
+    HIP_TRY(hipSetDevice(o->ctx->device));
+    if (Bmd) {  // the Mel master's noise columns; its mirror follows in om_refresh_dict
+        const hipError_t e = hipMemcpyAsync(o->Bm + (size_t)o->n1 * o->p.R_x, Bmd, (size_t)o->n1 * o->p.R_d * 8, hipMemcpyHostToDevice, o->ctx->stream);
+        if (e != hipSuccess) {
+            o->failed = true;
+            return fail(SNMF_ERR_NO_DEVICE, "restart: upload of B_Mel_d: %s", hipGetErrorString(e));
+        }
+    }
+    return online_restart(o, Bd, H0, Ad);
+}
+
+extern "C" int snmf_online_restart_f64(snmf_online* o, const double* Bd, const double* Bmd, const double* H0, const double* Ad) {
+    if (!o) return fail(SNMF_ERR_INVALID, "online handle is NULL");
+    if (!o->f64) return fail(SNMF_ERR_STATE, "snmf_online_restart_f64 needs a separator made by snmf_online_create_f64");
+    if (Bmd) return fail(SNMF_ERR_STATE, "B_Mel_d given to a separator that is not in Mel mode");
+    return online_f64_restart(o->f64, Bd, H0, Ad);
 }

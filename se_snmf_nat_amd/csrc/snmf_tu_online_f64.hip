@@ -109,9 +109,8 @@ int online_f64_create(snmf_ctx* ctx, const snmf_online_params* p, const double* 
     hipMemcpyAsync(o->B, Bx, (size_t)F * p->R_x * 8, hipMemcpyHostToDevice, st);
     hipMemcpyAsync(o->B + (size_t)F * p->R_x, Bd, (size_t)F * p->R_d * 8, hipMemcpyHostToDevice, st);
     hipMemcpyAsync(o->Bfix, Bd, (size_t)F * p->R_d * 8, hipMemcpyHostToDevice, st);  // B_Mel_d in DFT mode (:328)
-    online_upload_state(o, H0, win_stft, win_istft, htw);
+    online_upload_state(o, H0, Ad0, win_stft, win_istft, htw);
     hipMemsetAsync(o->w_ind, 0, (size_t)Ra, st);
-    if (p->adapt_train_N) hipMemcpyAsync(o->adblk, Ad0, (size_t)Ra * ma * 8, hipMemcpyHostToDevice, st);  // column-major R_a x m_a
     s = f64_refresh_images(o);
     hipError_t e = hipStreamSynchronize(st);
     if (s == SNMF_OK && e != hipSuccess) s = fail(SNMF_ERR_NO_DEVICE, "fp64 online create: %s", hipGetErrorString(e));
@@ -242,6 +241,18 @@ static int om_ola(OnlineF64* o, const double* syn, int n, int l0, int i_first, i
     return SNMF_OK;
 }
 
+// ---- the state record and the restart (the driver's last section; kernels k_ostate_get64 / k_ostate_put64) ---------------
+static void om_state_mode(const OnlineF64*, int* mel, int* mel_conv, int* n1) { *mel = *mel_conv = *n1 = 0; }  // DFT mode only
+
+static int om_state_launch(OnlineF64* o, const OStateArgs<double>& a, int64_t l, bool put) {
+    if (put) hipLaunchKernelGGL(k_ostate_put64, dim3(1, kStN, kStParts), dim3(256), 0, o->ctx->stream, a);
+    else hipLaunchKernelGGL(k_ostate_get64, dim3(1, kStN, kStParts), dim3(256), 0, o->ctx->stream, a, l);
+    HIP_TRY(hipGetLastError());
+    return SNMF_OK;
+}
+
+static int om_refresh_dict(OnlineF64* o) { return f64_refresh_images(o); }
+
 // ---- the entries snmf_tu_online.hip forwards to ----------------------------------------------------------------------------
 int online_f64_process(OnlineF64* o, const double* pcm, int64_t n, int flush, double* xt, int16_t* xt_i16, double* xh, double* dh,
                        double* xhi, double* dhi, int64_t cap, int64_t* n_out) {
@@ -251,3 +262,14 @@ int online_f64_process(OnlineF64* o, const double* pcm, int64_t n, int flush, do
 int online_f64_get_basis(OnlineF64* o, double* Bd, int64_t ld) { return online_get_basis_f64(o, Bd, ld); }
 
 int online_f64_trace(OnlineF64* o, snmf_online_frame* out, int64_t cap, int64_t* n) { return online_trace_read(o, out, cap, n); }
+
+void online_f64_state_info(OnlineF64* o, snmf_online_state_info* out) { online_state_info(o, out); }
+int online_f64_get_state(OnlineF64* o, void* record, int64_t cap) { return online_get_state(o, record, cap); }
+int online_f64_set_state(OnlineF64* o, const void* record, int64_t bytes) { return online_set_state(o, record, bytes); }
+
+int online_f64_restart(OnlineF64* o, const double* Bd, const double* H0, const double* Ad) {
+    SN_TRY(online_restart_check(o));
+    (void)hipGetLastError();  // clean sticky error state, see PLAN_CHECK
+    HIP_TRY(hipSetDevice(o->ctx->device));
+    return online_restart(o, Bd, H0, Ad);
+}

@@ -48,8 +48,8 @@ from . import _lib
 from ._lib import SnmfError, SnmfOnlineFrame, SnmfOnlineParams, SnmfOnlineStreamSettings
 from .api import default_context
 
-__all__ = ["default_settings", "OnlineSeparator", "ntf_sep_event_rt", "OnlineBatchSeparator", "ntf_sep_event_rt_batch",
-           "ntf_sep_event_rt_chains"]
+__all__ = ["default_settings", "OnlineSeparator", "ntf_sep_event_rt", "ntf_sep_event_rt_chain", "OnlineBatchSeparator",
+           "ntf_sep_event_rt_batch", "ntf_sep_event_rt_chains"]
 
 
 def default_settings():
@@ -183,6 +183,131 @@ def _class_partition(p, R_x, R_d):
     return np.array(sides[0], dtype=np.int32), np.array(sides[1], dtype=np.int32)
 
 
+# ---- the state g as a value: what OnlineSeparator and OnlineBatchSeparator share (include/snmf.h: snmf_online_state_info) ----
+def _state_shapes(q, dt, F, R_x, R_d, adapt, R_a, m_a, blk_ring, n1, class_outputs, classes):
+    """Field name -> (shape, dtype) of one stream's state: the rows of include/snmf.h's snmf_online_state_field_id that exist
+    in the separator's mode (n1: F_order in Mel mode, else None).  Computed from the constructor's arguments alone."""
+    dt = np.dtype(dt)
+    r = R_x + R_d
+    Ra, ma = (R_a, m_a) if adapt else (1, 1)
+    Pl = int(q.P_len_l) if blk_ring else 1
+    sz, hop = int(q.framelength), int(q.frameshift)
+    ntail = max(1, (sz + hop - 1) // hop - 1) * sz
+    f8, i4, i8 = np.dtype(np.float64), np.dtype(np.int32), np.dtype(np.int64)
+    sh = {"Xm_tilde": ((F,), dt), "lambda_dav": ((F,), dt), "r_blk": ((F, Pl), dt), "lambda_d_blk": ((F, ma), dt),
+          "Ad_blk": ((Ra, ma), dt), "n_push": ((), i4), "update_switch": ((), i4), "B_DFT_d": ((F, R_d), f8), "B_fix": ((F, R_d), f8)}
+    if n1 is not None:
+        sh["B_Mel_d"] = ((n1, R_d), f8)
+    sh.update({"H0": ((r,), dt), "Ad_blk0": ((Ra, ma), dt), "l": ((), i8), "y_hist": ((sz - hop,), dt), "pending": (None, dt),
+               "x_tilde_tail": ((ntail,), dt)})
+    if class_outputs:
+        sh["x_hat_tail"], sh["d_hat_tail"] = ((ntail,), dt), ((ntail,), dt)
+    if classes is not None:
+        sh["class_tails"] = ((classes[0].size + classes[1].size, ntail), dt)
+    return sh
+
+
+def _state_layout(lib, info):
+    """{field: (offset, count, numpy dtype)} of a record under `info` (snmf_online_state_field)."""
+    lay = {}
+    for f, name in enumerate(_lib.STATE_FIELDS):
+        off, cnt, typ = C.c_int64(), C.c_int64(), C.c_int32()
+        _lib.check(lib.snmf_online_state_field(C.byref(info), f, C.byref(off), C.byref(cnt), C.byref(typ)))
+        lay[name] = (off.value, cnt.value, np.dtype(_lib.STATE_TYPES[typ.value]))
+    return lay
+
+
+def _state_from_record(rec, info, lay, shapes):
+    """One record (uint8 array of info.bytes) -> the dict get_state returns."""
+    st = {}
+    cnt_p = int(rec[lay["pending_count"][0]:lay["pending_count"][0] + 4].view("<i4")[0])
+    for name in shapes:
+        off, cnt, dt = lay[name]
+        a = rec[off:off + cnt * dt.itemsize].view(dt).copy()
+        if name == "pending":
+            st[name] = a[:cnt_p]
+        elif name == "class_tails":  # one tail per class, class-major in the record
+            st[name] = a.reshape(-1, int(info.ntail))
+        elif name in ("n_push", "update_switch", "l"):
+            st[name] = int(a[0])
+        else:
+            dims = {"r_blk": (info.F, info.P_len_l), "lambda_d_blk": (info.F, info.m_a), "Ad_blk": (info.R_a, info.m_a),
+                    "Ad_blk0": (info.R_a, info.m_a), "B_DFT_d": (info.F, info.R_d), "B_fix": (info.F, info.R_d),
+                    "B_Mel_d": (info.F_order, info.R_d)}.get(name)
+            st[name] = a.reshape(dims, order="F") if dims else a
+    st["record"] = rec.tobytes()
+    return st
+
+
+def _state_checked(st, shapes, hop, who, owner):
+    """A state as set_state takes it (a get_state dict or the bytes of a record) -> (record bytes or None, {field: flat
+    array}).  Unknown or missing keys raise SnmfError(1) and wrong shapes SnmfError(3), naming the field; nothing here needs
+    the library.  who: "state of stream 3" / "state"; owner: "batch" / "separator"."""
+    if isinstance(st, (bytes, bytearray, memoryview)):
+        return bytes(st), {}
+    if not isinstance(st, dict):
+        raise _invalid(f"{who}: a dict or the bytes of a record, not {type(st).__name__}")
+    unknown = [key for key in st if key != "record" and key not in shapes]
+    if unknown:
+        raise _invalid(f"{who}: no field {unknown[0]!r} in this {owner}'s mode")
+    if st.get("record") is None:
+        missing = [key for key in shapes if key not in st]
+        if missing:
+            raise _invalid(f"{who}: field {missing[0]!r} is missing (and there is no 'record')")
+    fields = {}
+    for key, (shape, dt) in shapes.items():
+        if key not in st:
+            continue
+        a = np.asarray(st[key])
+        if key == "pending":
+            a = a.reshape(-1)
+            if a.size >= hop:
+                raise _invalid(f"{who}: 'pending' holds {a.size} samples, frameshift is {hop}")
+        elif a.size == int(np.prod(shape)) and len(shape) <= 1:
+            a = a.reshape(shape)
+        if key != "pending" and a.shape != tuple(shape):
+            raise SnmfError(3, f"{who}: {key!r} is {a.shape}, expected {tuple(shape)}")  # SNMF_ERR_DIM
+        fields[key] = np.asarray(a, dtype=dt).ravel(order="C" if key == "class_tails" else "F")
+    for key, lo in (("n_push", 0), ("update_switch", 1), ("l", 1)):
+        if key in fields and int(fields[key][0]) < lo:
+            raise _invalid(f"{who}: {key!r} = {int(fields[key][0])}")
+    return (bytes(st["record"]) if st.get("record") is not None else None), fields
+
+
+def _state_records(parsed, info, lay, owner):
+    """The checked states of _state_checked -> the bytes set_state hands to the library: raw records as they are (the library
+    judges them), dicts as their record (a hand-built one: the header of this separator) with the fields written over it."""
+    rb = int(info.bytes)
+    buf = np.zeros(len(parsed) * rb, dtype=np.uint8)
+    at = 0
+    for rec, fields in parsed:
+        if rec is None:  # a hand-built state: the header of this separator
+            head = np.zeros(_lib.STATE_HEADER_BYTES, dtype=np.uint8)
+            head[:8].view("<u4")[:] = (_lib.STATE_MAGIC, _lib.STATE_VERSION)
+            head[8:] = np.frombuffer(bytes(info), dtype=np.uint8)
+            rec = head.tobytes()
+        if not fields:  # raw bytes go as they are: the library judges them
+            if at + len(rec) > buf.size:
+                buf = np.concatenate([buf, np.zeros(at + len(rec) - buf.size, dtype=np.uint8)])
+            buf[at:at + len(rec)] = np.frombuffer(rec, dtype=np.uint8)
+            at += len(rec)
+            continue
+        m = min(len(rec), rb)
+        row = buf[at:at + rb]
+        row[:m] = np.frombuffer(rec, dtype=np.uint8)[:m]
+        for key, a in fields.items():
+            off, cnt, dt = lay[key]
+            if key == "pending":
+                o2 = lay["pending_count"][0]
+                row[o2:o2 + 4].view("<i4")[0] = a.size
+                row[off:off + cnt * dt.itemsize] = 0
+            elif a.size != cnt:
+                raise SnmfError(3, f"state: {key!r} holds {a.size} elements, the {owner}'s record {cnt}")
+            row[off:off + a.size * dt.itemsize] = np.ascontiguousarray(a, dtype=dt).view(np.uint8).reshape(-1)
+        at += rb
+    return buf, at
+
+
 class OnlineSeparator:
     """State `g` of src/init_buff.m + the per-frame function, resident on the GPU."""
 
@@ -237,6 +362,8 @@ class OnlineSeparator:
         self._q = q
         self.class_outputs = bool(class_outputs)
         self.hop, self.delay = q.frameshift, q.delay
+        self.adapt, self.R_a, self.m_a = adapt, R_a, m_a
+        self._blk_ring = bool(p.get("blk_sparse", 0))  # the r_blk ring exists at P_len_l columns
         h = C.c_void_p()
         create = self._lib.snmf_online_create_f64 if precision == "fp64" else self._lib.snmf_online_create
         _lib.check(create(self.ctx._h, C.byref(q), Bx.ctypes.data, Bd.ctypes.data, H0.ctypes.data,
@@ -314,6 +441,72 @@ class OnlineSeparator:
         _lib.check(self._lib.snmf_online_get_mel_basis_f32(self._h, B.ctypes.data, self.n1))
         return B.astype(np.float64)
 
+    # ---- the state g as a value (snmf_online_get_state / _set_state), the next file in place (snmf_online_restart_*) ----
+    def _state_shapes(self):
+        """Field name -> (shape, dtype) of the state as this separator holds it: what a batch of one with the same arguments
+        reports.  Computed from the constructor's arguments alone."""
+        return _state_shapes(self._q, self._dt, self.F, self.R_x, self.R_d, self.adapt, self.R_a, self.m_a, self._blk_ring,
+                             self.n1 if self.mel else None, self.class_outputs, self._classes)
+
+    def _state_layout(self, lib):
+        """The separator's snmf_online_state_info and {field: (offset, count, numpy dtype)} of a record under it."""
+        info = _lib.SnmfOnlineStateInfo()
+        _lib.check(lib.snmf_online_stream_state_info(self._h, C.byref(info)))
+        return info, _state_layout(lib, info)
+
+    def get_state(self):
+        """The state g as a value: the dict OnlineBatchSeparator.get_state(k) returns for a stream (the fields of
+        snmf_online_state_field_id under their names, matrices F-ordered, rings in time order, plus 'record', the raw
+        self-describing bytes).  Allowed between process calls, also before the first; a flushed separator raises
+        SnmfError(7).  The separator is not disturbed.  The record is the batch's: either kind of separator of the same
+        configuration takes it."""
+        shapes = self._state_shapes()
+        lib = _lib.load()
+        info, lay = self._state_layout(lib)
+        buf = np.zeros(max(1, int(info.bytes)), dtype=np.uint8)
+        _lib.check(lib.snmf_online_get_state(self._h, buf.ctypes.data, buf.size))
+        return _state_from_record(buf[:int(info.bytes)], info, lay, shapes)
+
+    def set_state(self, state):
+        """The separator (fresh, running or finished) takes `state` -- what get_state returns here or on a batch, or the raw
+        bytes of a record -- and is then a running stream at frame l with an empty trace whose next frames have the bits of
+        the stream the state came from.  OnlineBatchSeparator.set_state's rules: in a dict the fields override its 'record';
+        a hand-built g (no 'record') needs every field; unknown or missing keys raise SnmfError(1) and wrong shapes
+        SnmfError(3), naming the field, before the library is reached; a record of another precision, mode, geometry or class
+        count is refused by the library with SnmfError(3) and changes nothing."""
+        parsed = [_state_checked(state, self._state_shapes(), int(self._q.frameshift), "state", "separator")]
+        lib = _lib.load()
+        info, lay = self._state_layout(lib)
+        buf, at = _state_records(parsed, info, lay, "separator")
+        _lib.check(lib.snmf_online_set_state(self._h, buf.ctypes.data, at))
+
+    def restart(self, B_DFT_d=None, H0=None, Ad_blk0=None, B_Mel_d=None):
+        """The next file in place (src/NTF_sep_event_RT.m:27-38 + init_buff) on a flushed or never-fed separator: every piece
+        of state as a new separator gives it.  `B_DFT_d` (F x R_d, fp64; Mel mode also `B_Mel_d`, F_order x R_d) None keeps
+        the current, adapted dictionary at full fp64 precision and the fixed columns; `H0` / `Ad_blk0` None keep the draws
+        the separator last started with.  Wrong shapes raise SnmfError(1) before the library is reached, as in
+        OnlineBatchSeparator.restart; a separator in the middle of a recording raises SnmfError(7), and so does a B_Mel_d
+        outside Mel mode."""
+        def arr(x, shape, name, dt):
+            if x is None:
+                return None
+            a = np.asarray(x, dtype=np.float64)
+            if len(shape) == 1 and a.size == shape[0]:
+                a = a.reshape(-1)
+            if a.shape != tuple(shape):
+                raise _invalid(f"{name} is {a.shape}, expected {tuple(shape)}")
+            return np.ascontiguousarray(np.asarray(a, dtype=dt).ravel(order="F"))
+        Bd = arr(B_DFT_d, (self.F, self.R_d), "B_DFT_d", np.float64)
+        H = arr(H0, (self.R_x + self.R_d,), "H0", self._dt)
+        Ad = arr(Ad_blk0, (self.R_a, self.m_a), "Ad_blk0", self._dt) if self.adapt else None
+        if B_Mel_d is not None and not self.mel:
+            raise SnmfError(7, "B_Mel_d given to a separator that is not in Mel mode")  # SNMF_ERR_STATE, as the C entry
+        Bm = arr(B_Mel_d, (self.n1, self.R_d), "B_Mel_d", np.float64) if self.mel else None
+        lib = _lib.load()
+        ptr = lambda a: a.ctypes.data if a is not None else None  # noqa: E731
+        restart = lib.snmf_online_restart_f64 if self.precision == "fp64" else lib.snmf_online_restart_f32
+        _lib.check(restart(self._h, ptr(Bd), ptr(Bm), ptr(H), ptr(Ad)))
+
     def trace(self):
         """Per-frame diagnostics: list of dicts (n_iter, trig, solved, n_up, adapt_iters, beta, A_x_mag, ...)."""
         n = C.c_int64()
@@ -352,6 +545,38 @@ def ntf_sep_event_rt(pcm, B_DFT_x, B_DFT_d, p, H0=None, Ad_blk0=None, ctx=None, 
             i16 = np.concatenate([q["x_tilde"] for q in parts])
             f32 = np.concatenate([q["x_tilde_f"] for q in parts])
         return i16.copy(), f32.astype(np.float64), (sep.mel_basis() if sep.mel else sep.basis())
+    finally:
+        sep.close()
+
+
+def ntf_sep_event_rt_chain(files, B_DFT_x, B_DFT_d, p, H0=None, Ad_blk0=None, ctx=None, chunk=None, B_Mel_x=None, B_Mel_d=None,
+                           precision="fp32", class_outputs=False):
+    """run_ntf_sep_RT.m on one separator: `files` (a list of PCM arrays) enhanced in turn by src/NTF_sep_event_RT.m, every file
+    after the first starting from the dictionary its predecessor adapted, carried on the device in fp64 by
+    OnlineSeparator.restart() (:27-38, :137-140; Mel mode carries B_Mel_d too) with the chain's H0 / Ad_blk0.  It is
+    ntf_sep_event_rt_chains for one chain on the single-stream kernels.  Returns (results, final): results[i] is file i's
+    (int16, float, final B_DFT_d) triple as ntf_sep_event_rt returns it (Mel mode: the final B_Mel_d; with class_outputs a
+    fourth entry, the dict of 'x_hat', 'd_hat', 'x_hat_i', 'd_hat_i'), and final = {'B_DFT_d': the fp64 master after the last
+    file, 'B_Mel_d': the Mel dictionary or None, 'traces': every file's OnlineSeparator.trace()}.  `chunk` (samples per
+    process() call) only changes how a file is fed."""
+    files = [np.asarray(x).reshape(-1) for x in files]
+    sep = OnlineSeparator(B_DFT_x, B_DFT_d, p, H0=H0, Ad_blk0=Ad_blk0, ctx=ctx, class_outputs=class_outputs, B_Mel_x=B_Mel_x,
+                          B_Mel_d=B_Mel_d, precision=precision)
+    try:
+        results, traces = [], []
+        for i, x in enumerate(files):
+            if i:
+                sep.restart()  # the carry
+            step = len(x) if chunk is None else int(chunk)
+            parts = [sep.process(x[j:j + step]) for j in range(0, len(x), max(1, step))]
+            parts.append(sep.process(x[:0], flush=True))
+            cat = lambda key: np.concatenate([q[key] for q in parts], axis=-1)  # noqa: E731
+            res = (cat("x_tilde").astype(np.int16), cat("x_tilde_f").astype(np.float64), sep.mel_basis() if sep.mel else sep.basis())
+            if class_outputs:
+                res += ({key: cat(key) for key in ("x_hat", "d_hat", "x_hat_i", "d_hat_i")},)
+            results.append(res)
+            traces.append(sep.trace())
+        return results, {"B_DFT_d": sep.basis_f64(), "B_Mel_d": sep.mel_basis() if sep.mel else None, "traces": traces}
     finally:
         sep.close()
 
@@ -642,24 +867,8 @@ class OnlineBatchSeparator:
     def _state_shapes(self):
         """Field name -> (shape, dtype) of one stream's state as this batch holds it: the rows of include/snmf.h's
         snmf_online_state_field_id that exist in its mode.  Computed from the constructor's arguments alone."""
-        q, dt = self._q, np.dtype(self._dt)
-        F, Rd, r = self.F, self.R_d, self.R_x + self.R_d
-        Ra, ma = (self.R_a, self.m_a) if self.adapt else (1, 1)
-        Pl = int(q.P_len_l) if self._blk_ring else 1
-        sz, hop = int(q.framelength), int(q.frameshift)
-        ntail = max(1, (sz + hop - 1) // hop - 1) * sz
-        f8, i4, i8 = np.dtype(np.float64), np.dtype(np.int32), np.dtype(np.int64)
-        sh = {"Xm_tilde": ((F,), dt), "lambda_dav": ((F,), dt), "r_blk": ((F, Pl), dt), "lambda_d_blk": ((F, ma), dt),
-              "Ad_blk": ((Ra, ma), dt), "n_push": ((), i4), "update_switch": ((), i4), "B_DFT_d": ((F, Rd), f8), "B_fix": ((F, Rd), f8)}
-        if self.mel:
-            sh["B_Mel_d"] = ((self.n1, Rd), f8)
-        sh.update({"H0": ((r,), dt), "Ad_blk0": ((Ra, ma), dt), "l": ((), i8), "y_hist": ((sz - hop,), dt), "pending": (None, dt),
-                   "x_tilde_tail": ((ntail,), dt)})
-        if self.class_outputs:
-            sh["x_hat_tail"], sh["d_hat_tail"] = ((ntail,), dt), ((ntail,), dt)
-        if self._classes is not None:
-            sh["class_tails"] = ((self._classes[0].size + self._classes[1].size, ntail), dt)
-        return sh
+        return _state_shapes(self._q, self._dt, self.F, self.R_x, self.R_d, self.adapt, self.R_a, self.m_a, self._blk_ring,
+                             self.n1 if self.mel else None, self.class_outputs, self._classes)
 
     def _stream_list(self, streams):
         ks = [int(streams)] if np.isscalar(streams) else [int(k) for k in streams]
@@ -674,12 +883,7 @@ class OnlineBatchSeparator:
         """The batch's snmf_online_state_info and {field: (offset, count, numpy dtype)} of a record under it."""
         info = _lib.SnmfOnlineStateInfo()
         _lib.check(lib.snmf_online_batch_state_info(self._h, C.byref(info)))
-        lay = {}
-        for f, name in enumerate(_lib.STATE_FIELDS):
-            off, cnt, typ = C.c_int64(), C.c_int64(), C.c_int32()
-            _lib.check(lib.snmf_online_state_field(C.byref(info), f, C.byref(off), C.byref(cnt), C.byref(typ)))
-            lay[name] = (off.value, cnt.value, np.dtype(_lib.STATE_TYPES[typ.value]))
-        return info, lay
+        return info, _state_layout(lib, info)
 
     def get_state(self, streams):
         """The state g of stream `streams` (an index: one dict; a list of distinct indices: a list of dicts), as the fourth
@@ -699,27 +903,7 @@ class OnlineBatchSeparator:
         sl = np.array(ks, dtype=np.int32)
         if n:
             _lib.check(lib.snmf_online_batch_get_state(self._h, n, sl.ctypes.data, buf.ctypes.data, buf.size))
-        out = []
-        for i in range(n):
-            rec = buf[i * rb:(i + 1) * rb]
-            st = {}
-            cnt_p = int(rec[lay["pending_count"][0]:lay["pending_count"][0] + 4].view("<i4")[0])
-            for name in shapes:
-                off, cnt, dt = lay[name]
-                a = rec[off:off + cnt * dt.itemsize].view(dt).copy()
-                if name == "pending":
-                    st[name] = a[:cnt_p]
-                elif name == "class_tails":  # one tail per class, class-major in the record
-                    st[name] = a.reshape(-1, int(info.ntail))
-                elif name in ("n_push", "update_switch", "l"):
-                    st[name] = int(a[0])
-                else:
-                    dims = {"r_blk": (info.F, info.P_len_l), "lambda_d_blk": (info.F, info.m_a), "Ad_blk": (info.R_a, info.m_a),
-                            "Ad_blk0": (info.R_a, info.m_a), "B_DFT_d": (info.F, info.R_d), "B_fix": (info.F, info.R_d),
-                            "B_Mel_d": (info.F_order, info.R_d)}.get(name)
-                    st[name] = a.reshape(dims, order="F") if dims else a
-            st["record"] = rec.tobytes()
-            out.append(st)
+        out = [_state_from_record(buf[i * rb:(i + 1) * rb], info, lay, shapes) for i in range(n)]
         return out[0] if one else out
 
     def set_state(self, streams, states):
@@ -737,70 +921,13 @@ class OnlineBatchSeparator:
             raise _invalid(f"{len(sts)} states for {len(ks)} streams")
         shapes = self._state_shapes()
         hop = int(self._q.frameshift)
-        parsed = []
-        for k, st in zip(ks, sts):
-            if isinstance(st, (bytes, bytearray, memoryview)):
-                parsed.append((bytes(st), {}))
-                continue
-            if not isinstance(st, dict):
-                raise _invalid(f"state of stream {k}: a dict or the bytes of a record, not {type(st).__name__}")
-            unknown = [key for key in st if key != "record" and key not in shapes]
-            if unknown:
-                raise _invalid(f"state of stream {k}: no field {unknown[0]!r} in this batch's mode")
-            if st.get("record") is None:
-                missing = [key for key in shapes if key not in st]
-                if missing:
-                    raise _invalid(f"state of stream {k}: field {missing[0]!r} is missing (and there is no 'record')")
-            fields = {}
-            for key, (shape, dt) in shapes.items():
-                if key not in st:
-                    continue
-                a = np.asarray(st[key])
-                if key == "pending":
-                    a = a.reshape(-1)
-                    if a.size >= hop:
-                        raise _invalid(f"state of stream {k}: 'pending' holds {a.size} samples, frameshift is {hop}")
-                elif a.size == int(np.prod(shape)) and len(shape) <= 1:
-                    a = a.reshape(shape)
-                if key != "pending" and a.shape != tuple(shape):
-                    raise SnmfError(3, f"state of stream {k}: {key!r} is {a.shape}, expected {tuple(shape)}")  # SNMF_ERR_DIM
-                fields[key] = np.asarray(a, dtype=dt).ravel(order="C" if key == "class_tails" else "F")
-            for key, lo in (("n_push", 0), ("update_switch", 1), ("l", 1)):
-                if key in fields and int(fields[key][0]) < lo:
-                    raise _invalid(f"state of stream {k}: {key!r} = {int(fields[key][0])}")
-            parsed.append((bytes(st["record"]) if st.get("record") is not None else None, fields))
+        parsed = [_state_checked(st, shapes, hop, f"state of stream {k}", "batch") for k, st in zip(ks, sts)]
         lib = _lib.load()
         info, lay = self._state_layout(lib)
-        n, rb = len(ks), int(info.bytes)
+        n = len(ks)
         if n == 0:
             return
-        buf = np.zeros(n * rb, dtype=np.uint8)
-        at = 0
-        for rec, fields in parsed:
-            if rec is None:  # a hand-built state: the header of this batch
-                head = np.zeros(_lib.STATE_HEADER_BYTES, dtype=np.uint8)
-                head[:8].view("<u4")[:] = (_lib.STATE_MAGIC, _lib.STATE_VERSION)
-                head[8:] = np.frombuffer(bytes(info), dtype=np.uint8)
-                rec = head.tobytes()
-            if not fields:  # raw bytes go as they are: the library judges them
-                if at + len(rec) > buf.size:
-                    buf = np.concatenate([buf, np.zeros(at + len(rec) - buf.size, dtype=np.uint8)])
-                buf[at:at + len(rec)] = np.frombuffer(rec, dtype=np.uint8)
-                at += len(rec)
-                continue
-            m = min(len(rec), rb)
-            row = buf[at:at + rb]
-            row[:m] = np.frombuffer(rec, dtype=np.uint8)[:m]
-            for key, a in fields.items():
-                off, cnt, dt = lay[key]
-                if key == "pending":
-                    o2 = lay["pending_count"][0]
-                    row[o2:o2 + 4].view("<i4")[0] = a.size
-                    row[off:off + cnt * dt.itemsize] = 0
-                elif a.size != cnt:
-                    raise SnmfError(3, f"state: {key!r} holds {a.size} elements, the batch's record {cnt}")
-                row[off:off + a.size * dt.itemsize] = np.ascontiguousarray(a, dtype=dt).view(np.uint8).reshape(-1)
-            at += rb
+        buf, at = _state_records(parsed, info, lay, "batch")
         sl = np.array(ks, dtype=np.int32)
         _lib.check(lib.snmf_online_batch_set_state(self._h, n, sl.ctypes.data, buf.ctypes.data, at))
 
