@@ -734,6 +734,52 @@ int snmf_online_batch_get_state(snmf_online_batch* b, int32_t n, const int32_t* 
  * pending count >= frameshift: SNMF_ERR_INVALID.  A refused call changes nothing.  One upload, one scatter launch and the
  * dictionary refresh of a restart, whatever n; the stream's next frames have the bits of the stream the record came from. */
 int snmf_online_batch_set_state(snmf_online_batch* b, int32_t n, const int32_t* slots, const void* records, int64_t bytes);
+/* Added within 5.  The output capacity that holds one flushed recording of n_samples fed in any number of calls:
+ * (n_samples / frameshift + delay + 3) * frameshift samples.  A pure function of the handle's settings; a NULL handle or a
+ * negative n_samples gives 0. */
+int64_t snmf_online_batch_out_capacity(const snmf_online_batch* b, int64_t n_samples);
+/* Added within 5.  A corpus on the batch: the per-target loop of Do_MultiBatch_IS16_20160324.m:183-205 with
+ * run_ntf_sep_RT.m:10-41 inside it.  A CHAIN is a list of recordings enhanced in turn by src/NTF_sep_event_RT.m: its first
+ * file starts from the chain's B_DFT_d (the delete('B_D_u.mat') of :187) and every later file from the dictionary its
+ * predecessor adapted, carried on the device in fp64.  The S streams of `b` are slots that take chains from a queue in
+ * chain order; a slot whose file ended is restarted before it is fed again, as snmf_online_batch_restart with all-NULL
+ * arrays for the next file of its chain and with the next chain's dictionary and draws for a new chain.  Chain c uses its
+ * own H0 / Ad_blk0 for all its files.  With fewer chains than slots the spare slots are never touched; a chain without
+ * files gives no outputs.  Every file's signals and final dictionary are bit for bit those of the same sequence of
+ * restart / process calls made by hand on one stream, and depend neither on S, chunk_hops, the slot nor the other chains.
+ * Files are numbered in chain order: file j of chain c is entry n_files[0] + ... + n_files[c - 1] + j of every per-file array.
+ *   n_chains, n_files[n_chains]          chains and files per chain (0 allowed)
+ *   pcm[i], n_samples[i]                 file i's samples (float for _f32, double for _f64; pcm[i] may be NULL when n_samples[i] is 0)
+ *   B_DFT_d    F x R_d x n_chains        every chain's start dictionary, fp64, as snmf_online_batch_restart takes it
+ *   B_Mel_d    F_order x R_d x n_chains  Mel batch: every chain's start B_Mel_d (required there; elsewhere NULL, otherwise SNMF_ERR_STATE)
+ *   H0         r x n_chains              float for _f32, double for _f64, as the restart entries take them
+ *   Ad_blk0    R_a x m_a x n_chains      likewise; required only when the batch adapts
+ *   chunk_hops                           hops fed to every busy slot per internal process call; 0 = one device chunk
+ *                                        (16384 / S hops, at least 1, at most 4096).  It changes no bit of the result.  Any
+ *                                        larger value is fine: more than the longest file holds means whole files per call,
+ *                                        and the driver's buffers are sized by the files, never by this number.
+ * Outputs, per file; each array and each entry may be NULL:
+ *   x_tilde_i16[i], x_tilde_f[i]         the enhanced signal, capacity cap[i] samples each (snmf_online_batch_out_capacity
+ *                                        suffices; less than (n_samples[i] / frameshift + delay + 1) * frameshift is SNMF_ERR_INVALID)
+ *   n_out[i]                             samples written for file i
+ *   B_out[i]                             the dictionary after file i, tight, fp64: the master snmf_online_batch_get_basis_f64
+ *                                        returns (F x R_d), on a Mel batch the one of _get_mel_basis_f64 (F_order x R_d)
+ * On a batch with class outputs only x_tilde is written.  Everything is checked before the device is touched:
+ * SNMF_ERR_INVALID for a NULL handle, NULL or inconsistent counts and arrays; SNMF_ERR_STATE (every n_out zeroed) for the
+ * entry of the other precision, for a failed batch and for a batch with a stream that has consumed samples and was not
+ * flushed -- the handle stays usable; SNMF_ERR_UNSUPPORTED on a batch with settings or event dictionaries per stream
+ * (snmf_online_batch_create_streams_f64, or snmf_online_batch_restart_streams_f64 with either): chains with settings of
+ * their own stay with the caller's own loop over restart_streams_f64 for now.  After SNMF_OK every used stream is flushed:
+ * the handle runs another corpus or is driven by hand.  An error of a restart or process call inside the run is returned
+ * as it is; n_out then holds the files that were finished. */
+int snmf_online_batch_run_chains_f32(snmf_online_batch* b, int32_t n_chains, const int32_t* n_files, const float* const* pcm,
+                                     const int64_t* n_samples, const double* B_DFT_d, const double* B_Mel_d, const float* H0,
+                                     const float* Ad_blk0, int32_t chunk_hops, int16_t* const* x_tilde_i16, float* const* x_tilde_f32,
+                                     const int64_t* cap, int64_t* n_out, double* const* B_out);
+int snmf_online_batch_run_chains_f64(snmf_online_batch* b, int32_t n_chains, const int32_t* n_files, const double* const* pcm,
+                                     const int64_t* n_samples, const double* B_DFT_d, const double* B_Mel_d, const double* H0,
+                                     const double* Ad_blk0, int32_t chunk_hops, int16_t* const* x_tilde_i16, double* const* x_tilde_f64,
+                                     const int64_t* cap, int64_t* n_out, double* const* B_out);
 /* Diagnostics of stream k's most recent frames (the newest 65536 per stream), as snmf_online_trace. */
 int snmf_online_batch_trace(snmf_online_batch* b, int32_t k, snmf_online_frame* out, int64_t cap, int64_t* n);
 void snmf_online_batch_destroy(snmf_online_batch* b);

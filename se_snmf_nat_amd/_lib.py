@@ -33,7 +33,7 @@ _TU_HDRS = {
     "snmf_tu_online_f64.hip": ["snmf_online_common.h", "snmf_online_batch_common.h", "snmf_online_f64_core.h", "snmf_online_f64.h",
                                "snmf_online_f64_host.h", "snmf_online_host.h", "snmf_online_classes.h"],
     "snmf_tu_online_batch.hip": ["snmf_online_common.h", "snmf_online_batch_common.h", "snmf_online_batch.h",
-                                 "snmf_online_batch_f64_host.h", "snmf_online_batch_host.h", "snmf_online_host.h",
+                                 "snmf_online_batch_chains.h", "snmf_online_batch_f64_host.h", "snmf_online_batch_host.h", "snmf_online_host.h",
                                  "snmf_online_classes.h"],
     "snmf_tu_online_batch_f64.hip": ["snmf_online_common.h", "snmf_online_batch_common.h", "snmf_online_f64_core.h",
                                      "snmf_online_batch_f64.h", "snmf_online_batch_f64_host.h", "snmf_online_batch_host.h",
@@ -80,6 +80,7 @@ SYMBOLS = [
     "snmf_online_batch_restart_f64",
     "snmf_online_batch_create_streams_f64", "snmf_online_batch_restart_streams_f64", "snmf_online_batch_get_settings",
     "snmf_online_batch_state_info", "snmf_online_state_field", "snmf_online_batch_get_state", "snmf_online_batch_set_state",
+    "snmf_online_batch_out_capacity", "snmf_online_batch_run_chains_f32", "snmf_online_batch_run_chains_f64",
     "snmf_online_stream_state_info", "snmf_online_get_state", "snmf_online_set_state", "snmf_online_restart_f32", "snmf_online_restart_f64",
     "snmf_multi_create", "snmf_multi_destroy", "snmf_multi_set_v_f64", "snmf_multi_set_v_f32", "snmf_multi_set_w_f64",
     "snmf_multi_set_w_f32", "snmf_multi_set_h_f64", "snmf_multi_set_h_f32", "snmf_multi_set_sparsity_f64",
@@ -361,6 +362,9 @@ def load():
     sig["snmf_online_state_field"] = (C.c_int, [C.POINTER(SnmfOnlineStateInfo), i32, C.POINTER(i64), C.POINTER(i64), C.POINTER(i32)])
     sig["snmf_online_batch_get_state"] = (C.c_int, [vp, i32, vp, vp, i64])
     sig["snmf_online_batch_set_state"] = (C.c_int, [vp, i32, vp, vp, i64])
+    sig["snmf_online_batch_out_capacity"] = (i64, [vp, i64])
+    for ty in ("f32", "f64"):  # counts, per-file arrays, per-chain arrays, chunk_hops, per-file outputs
+        sig[f"snmf_online_batch_run_chains_{ty}"] = (C.c_int, [vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp])
     sig["snmf_online_stream_state_info"] = (C.c_int, [vp, C.POINTER(SnmfOnlineStateInfo)])
     sig["snmf_online_get_state"] = (C.c_int, [vp, vp, i64])
     sig["snmf_online_set_state"] = (C.c_int, [vp, vp, i64])

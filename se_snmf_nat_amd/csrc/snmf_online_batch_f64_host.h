@@ -22,6 +22,7 @@ int online_batch_f64_restart(OnlineBatchF64* o, int32_t n, const int32_t* slots,
                              const double* Ad, const snmf_online_stream_settings* settings);
 int online_batch_f64_get_settings(OnlineBatchF64* o, int32_t k, snmf_online_stream_settings* out);
 void online_batch_f64_dims(OnlineBatchF64* o, int* r, int* ra_ma);  // lengths of one stream's H0 and Ad_blk0
+int online_batch_f64_idle(const OnlineBatchF64* o);  // obatch_idle_check: SNMF_ERR_STATE on a failed batch or a stream mid-recording
 int online_batch_f64_get_basis(OnlineBatchF64* o, int32_t k, double* Bd, int64_t ld);
 int online_batch_f64_trace(OnlineBatchF64* o, int32_t k, snmf_online_frame* out, int64_t cap, int64_t* n);
 // get-state / set-state (snmf_online_batch_state_info / _get_state / _set_state) of the fp64 batch

@@ -207,6 +207,16 @@ int obatch_restart_check(const H* o, int32_t n, const int32_t* slots) {
     return SNMF_OK;
 }
 
+// what a corpus run (snmf_online_batch_chains.h) must find: a batch that has not failed, with no stream in the middle of a recording
+template <class H>
+int obatch_idle_check(const H* o) {
+    if (o->failed) return fail(SNMF_ERR_STATE, "an earlier call failed midway through a chunk; the batch state is not reusable, create a new one");
+    for (int s = 0; s < o->S; ++s)
+        if (!o->finished[s] && (o->l[s] > 0 || !o->pending[s].empty()))
+            return fail(SNMF_ERR_STATE, "stream %d is in the middle of a recording; flush it before a run over chains", s);
+    return SNMF_OK;
+}
+
 // the host state of streams that start a new recording (src/init_buff.m)
 template <class H>
 void obatch_restart_host(H* o, int n, const int32_t* slots) {

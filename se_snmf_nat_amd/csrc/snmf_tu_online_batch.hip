@@ -2,14 +2,18 @@
 // snmf_online_batch.h.  A translation unit of its own, so that the single-stream kernels' code does not move.
 // The host driver (hop queues, chunk loop, framing, synthesis, trace) is snmf_online_batch_host.h, shared with the fp64 mode;
 // here are the handle, its creation / Mel conversion / restart, and the fp32 steps the driver calls (obm_*).
+#include <new>
+
 #include "snmf_internal.h"
 #include "snmf_online_batch.h"
+#include "snmf_online_batch_chains.h"
 #include "snmf_online_batch_f64_host.h"  // the fp64 mode's host entry points (its kernels live in snmf_tu_online_batch_f64.hip)
 #include "snmf_online_batch_host.h"
 #include "snmf_online_classes.h"
 
 struct snmf_online_batch : OBatchState<float> {
     OnlineBatchF64* f64 = nullptr;  // non-null: an fp64 batch (snmf_online_batch_create_f64); only ctx, p, S and F are then used
+    bool per_stream = false;        // fp64 batch: streams were given settings or event dictionaries of their own
     int RA2 = 64;
     int Fs = 0;                                // rows of the solves: F, or F_order in Mel mode
     int mel = 0, mel_conv = 0, n1 = 0;         // B_sep_mode = 'Mel' (snmf_online_batch_set_mel)
@@ -715,7 +719,9 @@ extern "C" int snmf_online_batch_create_streams_f64(snmf_ctx* ctx, const snmf_on
     (void)hipGetLastError();  // clean sticky error state, see PLAN_CHECK
     OnlineBatchF64* f = nullptr;
     SN_TRY(online_batch_f64_create(ctx, p, S, Bx, 1, Bd0, H0, Ad0, settings, win_stft, win_istft, &f));
-    return ob_wrap_f64(ctx, p, S, f, out);
+    SN_TRY(ob_wrap_f64(ctx, p, S, f, out));
+    (*out)->per_stream = true;
+    return SNMF_OK;
 }
 
 extern "C" int snmf_online_batch_restart_streams_f64(snmf_online_batch* o, int32_t n, const int32_t* slots, const double* Bx, const double* Bd,
@@ -727,7 +733,9 @@ extern "C" int snmf_online_batch_restart_streams_f64(snmf_online_batch* o, int32
         const snmf_online_params m = ob_with_settings(o->p, settings[i]);
         SN_TRY(ob_validate(&m, o->S));
     }
-    return online_batch_f64_restart(o->f64, n, slots, Bx, Bd, H0, Ad, settings);
+    SN_TRY(online_batch_f64_restart(o->f64, n, slots, Bx, Bd, H0, Ad, settings));
+    if (n > 0 && (Bx || settings)) o->per_stream = true;
+    return SNMF_OK;
 }
 
 extern "C" int snmf_online_batch_get_settings(snmf_online_batch* o, int32_t k, snmf_online_stream_settings* out) {
@@ -766,4 +774,95 @@ extern "C" int snmf_online_batch_restart_f64(snmf_online_batch* o, int32_t n, co
     if (!o) return fail(SNMF_ERR_INVALID, "online batch handle is NULL");
     if (!o->f64) return fail(SNMF_ERR_STATE, "snmf_online_batch_restart_f64 needs a batch made by snmf_online_batch_create_f64");
     return online_batch_f64_restart(o->f64, n, slots, nullptr, Bd, H0, Ad, nullptr);
+}
+
+// ---- chains of recordings over the batch's slots (snmf_online_batch_chains.h) ----
+extern "C" int64_t snmf_online_batch_out_capacity(const snmf_online_batch* o, int64_t n_samples) {
+    if (!o || n_samples < 0) return 0;
+    return (n_samples / o->p.frameshift + o->p.delay + 3) * (int64_t)o->p.frameshift;
+}
+
+// the three calls the driver makes are the public entries of the batch's precision
+template <typename T>
+struct ObChainOps;
+template <>
+struct ObChainOps<float> {
+    snmf_online_batch* o;
+    int restart(int n, const int32_t* slots, const double* Bd, const double* Bmd, const float* H0, const float* Ad) {
+        return snmf_online_batch_restart_mel(o, n, slots, Bd, Bmd, H0, Ad);
+    }
+    int process(const float* const* pcm, const int64_t* n, const int32_t* flush, float* const* xt, int16_t* const* x16, const int64_t* cap,
+                int64_t* n_out) {
+        return snmf_online_batch_process_f32(o, pcm, n, flush, xt, x16, nullptr, nullptr, cap, n_out);
+    }
+    int basis(int k, double* dst) {
+        return o->mel ? snmf_online_batch_get_mel_basis_f64(o, k, dst, o->n1) : snmf_online_batch_get_basis_f64(o, k, dst, o->F);
+    }
+};
+template <>
+struct ObChainOps<double> {
+    snmf_online_batch* o;
+    int restart(int n, const int32_t* slots, const double* Bd, const double*, const double* H0, const double* Ad) {
+        return snmf_online_batch_restart_f64(o, n, slots, Bd, H0, Ad);
+    }
+    int process(const double* const* pcm, const int64_t* n, const int32_t* flush, double* const* xt, int16_t* const* x16, const int64_t* cap,
+                int64_t* n_out) {
+        return snmf_online_batch_process_f64(o, pcm, n, flush, xt, x16, nullptr, nullptr, cap, n_out);
+    }
+    int basis(int k, double* dst) { return snmf_online_batch_get_basis_f64(o, k, dst, o->F); }
+};
+
+template <typename T>
+static int ob_run_chains(snmf_online_batch* o, const OChainsArgs<T>& a) {
+    if (!o) return fail(SNMF_ERR_INVALID, "online batch handle is NULL");
+    constexpr bool f64 = sizeof(T) == 8;
+    const snmf_online_params& p = o->p;
+    OChainsGeom g{};
+    g.S = o->S; g.hop = p.frameshift; g.delay = p.delay;
+    g.nB = (size_t)o->F * p.R_d;
+    g.step0 = std::max<int64_t>(1, std::min<int64_t>(4096, kBChunkSlots / o->S));
+    if (o->f64) {
+        int r = 0, na = 0;
+        online_batch_f64_dims(o->f64, &r, &na);
+        g.r = (size_t)r;
+        g.nA = p.adapt_train_N ? (size_t)na : 0;
+    } else {
+        g.r = (size_t)o->r;
+        g.nA = p.adapt_train_N ? (size_t)o->Ra * o->ma : 0;
+        g.nBm = o->mel ? (size_t)o->n1 * p.R_d : 0;
+    }
+    int64_t nf = 0;
+    SN_TRY(ochains_check_args(g, a, &nf));
+    if (a.n_out)
+        for (int64_t i = 0; i < nf; ++i) a.n_out[i] = 0;
+    if (f64 != (o->f64 != nullptr))
+        return fail(SNMF_ERR_STATE, f64 ? "snmf_online_batch_run_chains_f64 needs a batch made by snmf_online_batch_create_f64"
+                                        : "snmf_online_batch_run_chains_f32 on an fp64 batch: use snmf_online_batch_run_chains_f64");
+    if (o->per_stream)
+        return fail(SNMF_ERR_UNSUPPORTED, "run over chains: a batch with settings or event dictionaries per stream is not supported");
+    if (a.Bmd && !g.nBm) return fail(SNMF_ERR_STATE, "B_Mel_d given to a batch that is not in Mel mode");
+    SN_TRY(o->f64 ? online_batch_f64_idle(o->f64) : obatch_idle_check(o));
+    if (nf == 0) return SNMF_OK;
+    ObChainOps<T> ops{o};
+    try {
+        return ochains_run(g, a, ops);
+    } catch (const std::bad_alloc&) {  // the driver's own buffers (sized by the data, before the first call) or a copy of a chunk
+        return fail(SNMF_ERR_NOMEM, "run over chains: out of host memory");
+    }
+}
+
+extern "C" int snmf_online_batch_run_chains_f32(snmf_online_batch* o, int32_t n_chains, const int32_t* n_files, const float* const* pcm,
+                                                const int64_t* n_samples, const double* Bd, const double* Bmd, const float* H0,
+                                                const float* Ad, int32_t chunk_hops, int16_t* const* xt_i16, float* const* xt_f32,
+                                                const int64_t* cap, int64_t* n_out, double* const* B_out) {
+    return ob_run_chains<float>(o, OChainsArgs<float>{n_chains, n_files, pcm, n_samples, Bd, Bmd, H0, Ad, chunk_hops, xt_i16, xt_f32, cap,
+                                                      n_out, B_out});
+}
+
+extern "C" int snmf_online_batch_run_chains_f64(snmf_online_batch* o, int32_t n_chains, const int32_t* n_files, const double* const* pcm,
+                                                const int64_t* n_samples, const double* Bd, const double* Bmd, const double* H0,
+                                                const double* Ad, int32_t chunk_hops, int16_t* const* xt_i16, double* const* xt_f64,
+                                                const int64_t* cap, int64_t* n_out, double* const* B_out) {
+    return ob_run_chains<double>(o, OChainsArgs<double>{n_chains, n_files, pcm, n_samples, Bd, Bmd, H0, Ad, chunk_hops, xt_i16, xt_f64, cap,
+                                                        n_out, B_out});
 }

@@ -420,6 +420,8 @@ void online_batch_f64_dims(OnlineBatchF64* o, int* r, int* ra_ma) {
     *ra_ma = o->Ra * o->ma;
 }
 
+int online_batch_f64_idle(const OnlineBatchF64* o) { return obatch_idle_check(o); }
+
 int online_batch_f64_get_basis(OnlineBatchF64* o, int32_t k, double* Bd, int64_t ld) {
     if (k < 0 || k >= o->S) return fail(SNMF_ERR_INVALID, "stream %d out of range [0, %d)", k, o->S);
     if (ld < o->F) return fail(SNMF_ERR_INVALID, "ld < F");

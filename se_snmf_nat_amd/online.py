@@ -931,6 +931,77 @@ class OnlineBatchSeparator:
         sl = np.array(ks, dtype=np.int32)
         _lib.check(lib.snmf_online_batch_set_state(self._h, n, sl.ctypes.data, buf.ctypes.data, at))
 
+    def out_capacity(self, n_samples):
+        """Output samples that hold one flushed recording of `n_samples` (snmf_online_batch_out_capacity)."""
+        return int(self._lib.snmf_online_batch_out_capacity(self._h, int(n_samples)))
+
+    def run_chains(self, chains, B_DFT_d, H0=None, Ad_blk0=None, B_Mel_d=None, chunk_hops=None, masters=False):
+        """ntf_sep_event_rt_chains on this batch's slots in ONE library call (snmf_online_batch_run_chains_f32 / _f64): the
+        queue of chains, the carries and the restarts run in the library's host code.  `chains` is a list of chains, each a
+        list of PCM arrays; `B_DFT_d` (Mel mode also `B_Mel_d`) one start dictionary for all chains or one per chain, rounded
+        to fp32 on an fp32 batch as the Python driver rounds them; `H0` / `Ad_blk0` one array or one per chain, by default
+        drawn from RandomState(random_seed + c).  Returns what ntf_sep_event_rt_chains returns, bit for bit: per chain the
+        list of its files' (int16, float, final dictionary) triples (Mel mode: the final B_Mel_d); with `masters` the
+        dictionaries are the fp64 masters instead of their fp32 images (an fp64 batch returns the masters either way).
+        The batch must be idle (every fed stream flushed: SnmfError(7) otherwise) and is idle again afterwards; a batch with
+        settings per stream raises SnmfError(8)."""
+        chains = [[np.ascontiguousarray(np.asarray(x).reshape(-1), dtype=self._dt) for x in c] for c in chains]
+        nc = len(chains)
+        f64 = self.precision == "fp64"
+        r = self.R_x + self.R_d
+        Bds = _per_chain(B_DFT_d, nc, (self.F, self.R_d), "B_DFT_d", np.float64 if f64 else np.float32)
+        if B_Mel_d is not None and not self.mel:
+            raise SnmfError(7, "B_Mel_d given to a batch that is not in Mel mode")  # SNMF_ERR_STATE, as the C entry
+        if self.mel and B_Mel_d is None:
+            raise _invalid("a Mel batch needs every chain's start B_Mel_d")
+        Bms = _per_chain(B_Mel_d, nc, (self.n1, self.R_d), "B_Mel_d", np.float32) if self.mel else None
+        if H0 is not None:
+            H0 = _per_chain(H0, nc, (r,), "H0", np.float64)
+        if self.adapt and Ad_blk0 is not None:
+            Ad_blk0 = _per_chain(Ad_blk0, nc, (self.R_a, self.m_a), "Ad_blk0", np.float64)
+        if chunk_hops and int(chunk_hops) < 1:  # (None or 0: the default, as in ntf_sep_event_rt_chains and the C entry)
+            raise _invalid("chunk_hops must be >= 1")
+        seed = int(self._p.get("random_seed", 1))
+        hs, ads = [], []
+        for c in range(nc):  # ntf_sep_event_rt_chains' draws for chain c
+            rs = np.random.RandomState(seed + c)
+            h = rs.random_sample(r)
+            a = rs.random_sample((self.R_a, self.m_a)) if self.adapt else None
+            hs.append(h if H0 is None else H0[c])
+            if self.adapt:
+                ads.append(a if Ad_blk0 is None else Ad_blk0[c])
+        flat = lambda arrs, dt: np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=dt).ravel(order="F") for x in arrs]) if arrs  # noqa: E731
+                                                     else np.zeros(0, dt))
+        Bd_all, H_all = flat(Bds, np.float64), flat(hs, self._dt)
+        Bm_all = flat(Bms, np.float64) if self.mel else None
+        Ad_all = flat(ads, self._dt) if self.adapt else None
+        files = [x for c in chains for x in c]
+        nf = len(files)
+        n_files = np.array([len(c) for c in chains], dtype=np.int32)
+        n_samples = np.array([x.size for x in files], dtype=np.int64)
+        caps = np.array([self.out_capacity(x.size) for x in files], dtype=np.int64)
+        o16 = [np.zeros(c, np.int16) for c in caps]
+        of = [np.zeros(c, self._dt) for c in caps]
+        rows = self.n1 if self.mel else self.F
+        Bo = [np.zeros((rows, self.R_d), dtype=np.float64, order="F") for _ in files]
+        n_out = np.zeros(max(nf, 1), dtype=np.int64)
+        P = C.c_void_p * max(nf, 1)
+        ptrs = lambda arrs: P(*[a.ctypes.data if a.size else None for a in arrs])  # noqa: E731
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+        run = self._lib.snmf_online_batch_run_chains_f64 if f64 else self._lib.snmf_online_batch_run_chains_f32
+        _lib.check(run(self._h, nc, ptr(n_files), ptrs(files), ptr(n_samples), ptr(Bd_all), ptr(Bm_all), ptr(H_all), ptr(Ad_all),
+                       int(chunk_hops or 0), ptrs(o16), ptrs(of), ptr(caps), n_out.ctypes.data, ptrs(Bo)))
+        results, i = [], 0
+        for c in chains:
+            res = []
+            for _ in c:
+                m = int(n_out[i])
+                B = Bo[i] if (f64 or masters) else Bo[i].astype(np.float32).astype(np.float64)  # basis(k) / mel_basis(k) of the fp32 batch
+                res.append((o16[i][:m].copy(), of[i][:m].astype(np.float64), B))
+                i += 1
+            results.append(res)
+        return results
+
     def trace(self, k):
         """Per-frame diagnostics of stream k, as OnlineSeparator.trace."""
         n = C.c_int64()
