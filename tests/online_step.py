@@ -1,5 +1,8 @@
 """Element-wise judgement of ONE frame step of the batched online separator, from the device's own state g.  Test infrastructure
-(like elementwise.py): no test functions here; imported by tests/test_online_step_rules.py (CPU) and tests/test_gpu_online_step.py.
+(like elementwise.py): no test functions here; imported by tests/test_online_step_rules.py (CPU), tests/test_gpu_online_step.py and
+tests/test_gpu_online_single_step.py -- the single-stream OnlineSeparator returns the same record from get_state and is judged by
+the same functions, one separator per stream (run_single, judge_run, SINGLE_CASES and wadapt_regions below; why its kernels need
+no other bound is derived in that test's docstring).
 
 THE METHOD.  OnlineBatchSeparator.get_state returns a stream's whole state g as a value, in the oracle's field names and ring order.
 A batch of three streams is fed ONE hop per process call, with a get_state around every hop.  The fields of g_before are cast
@@ -117,13 +120,15 @@ RMS_FACTOR = 4.0
 TINY = {U: 2.0 ** -126, U64: 2.0 ** -1022}  # smallest normal number of the mode's format
 
 PLANTS = ("extra_row", "xs_column", "ad_last", "alpha_d_swapped", "q_prev", "ring_early", "swap_rem_tmp", "norm_neighbour",
-          "syn_shift", "init_long")
+          "syn_shift", "init_long", "wg_partial", "r_up_shift")
 # what the failure of each planted error must name: the field and the region (all of these substrings in one failure message)
 PLANT_FIELDS = {"extra_row": ("field Ad_blk,", "region all"), "xs_column": ("field r_blk,", "region all"),
                 "ad_last": ("field Ad_blk,", "region last_activation"), "alpha_d_swapped": ("field lambda_dav,", "region all"),
                 "q_prev": ("field Xm_tilde,", "region blk_bins"), "ring_early": ("field ring lambda_d_blk:",),
                 "swap_rem_tmp": ("field B_DFT_d,", "region rem"), "norm_neighbour": ("field B_DFT_d,", "region B_tmp:"),
-                "syn_shift": ("field x_tilde_tail,", "region all"), "init_long": ("frame 6:", "field Xm_tilde,", "region all")}
+                "syn_shift": ("field x_tilde_tail,", "region all"), "init_long": ("frame 6:", "field Xm_tilde,", "region all"),
+                # the two that belong to the single-stream adaptation (k_wadapt's exchange, the r_up mask k_oprep writes to w_ind)
+                "wg_partial": ("field B_DFT_d,", "region B_tmp.wg_low"), "r_up_shift": ("field B_DFT_d,", "region rem")}
 
 
 def beta_of(p):
@@ -233,6 +238,10 @@ def _w_step(ar, V, W0, H0, beta, flr, plant=None):
         dmw = Qm + ar.sum(P * W, axis=0)[None, :] * W
     Wn = W * dmw / np.fmax(dpw, flr)
     nrm = np.sqrt(ar.sum(Wn * Wn, axis=0))
+    if plant == "wg_partial":  # one workgroup's partial left out of the cross_sum: the column norm over rows that skip rows 8..15
+        keep = np.ones(Wn.shape[0], bool)
+        keep[8:16] = False
+        nrm = np.sqrt(ar.sum((Wn * Wn)[keep], axis=0))
     if plant == "norm_neighbour" and nrm.size >= 2:
         nrm = nrm.copy()
         nrm[0] = nrm[1]
@@ -302,9 +311,33 @@ def frame_step(g, y, l, p, H0, Bx, dt=np.float64, rev=False, plant=None, seq=Non
     W = c(W0 / wn)
     h = c(np.asarray(H0, np.float64) * wn)
     sp = c(p["sparsity"])
-    Wd = W[:-1] if plant == "extra_row" else W  # (the planted error: the extra row F - 1 left out of W' * ratio)
     assert p["conv_eps"] == 0  # (max_iter H steps without a stop: the one-step cases)
-    for _ in range(int(p["max_iter"])):
+    # the semi-supervised frame solve (:125-131; src/sparse_nmf.m:212-243): the noise (basis_update_N) or the event columns of the
+    # solve's PRIVATE W are updated after every H step and all columns renormalised, H not rescaled; the frame keeps A only
+    w_ind = None
+    if p.get("basis_update_N", 0):
+        w_ind = np.arange(Rx, W.shape[1])
+    elif p.get("basis_update_E", 0):
+        w_ind = np.arange(Rx)
+    n_it = int(p["max_iter"])
+    for it in range(n_it):
+        Wd = W[:-1] if plant == "extra_row" else W  # (the planted error: the extra row F - 1 left out of W' * ratio)
+        if it and w_ind is not None:  # the W step that closed the previous iteration (the last one's W is discarded)
+            lam = np.fmax(ar.mv(W, h), flr)
+            ww, hw = W[:, w_ind], h[w_ind][None, :]
+            if beta_div == 1:
+                G = (V / lam)[:, None] * hw
+                dpw = hw + ar.sum(G * ww, axis=0)[None, :] * ww
+                dmw = G + ar.sum(hw * ww, axis=0)[None, :] * ww
+            else:
+                P = (lam if beta_div == 2 else lam ** c(beta_div - 1.0))[:, None] * hw
+                Qm = (V if beta_div == 2 else V * lam ** c(beta_div - 2.0))[:, None] * hw
+                dpw = P + ar.sum(Qm * ww, axis=0)[None, :] * ww
+                dmw = Qm + ar.sum(P * ww, axis=0)[None, :] * ww
+            W = W.copy()
+            W[:, w_ind] = ww * dmw / np.fmax(dpw, flr)
+            W = W / np.sqrt(ar.sum(W * W, axis=0))[None, :]
+            Wd = W[:-1] if plant == "extra_row" else W
         lam = np.fmax(ar.mv(W, h), flr)
         if beta_div == 1:
             dph, num = ar.sum(W, axis=0) + sp, V / lam
@@ -388,6 +421,8 @@ def frame_step(g, y, l, p, H0, Bx, dt=np.float64, rev=False, plant=None, seq=Non
         ga["lambda_d_blk"], ga["Ad_blk"] = put(ga["lambda_d_blk"], D_ref), put(ga["Ad_blk"], a_new)
         ga["n_push"] += 1
         r_up = Q_control * (ar.sum(ga["Ad_blk"], axis=1) / c(ma)) > A_x_mag
+        if plant == "r_up_shift":  # the mask the adaptation solve reads, shifted by one column
+            r_up = np.roll(r_up, 1)
         n_up = int(r_up.sum())
         if ga["update_switch"] == int(np.floor(p["overlap_m_a"] * ma)):
             Bsrc = BMd if mel else Bd  # :224-230: Mel mode adapts B_Mel_d on melmat * lambda_d_blk, and its fix columns are its own
@@ -658,6 +693,19 @@ def field_regions(field, p, F, Ra):
     return None
 
 
+def wadapt_regions(Fw, n_up, last_lane):
+    """The updated columns (Fw x n_up, column-major) by the cooperative adaptation kernel's geometry: a workgroup holds 8 rows
+    (kWaRB), the exchange sums the workgroups below and from ceil(nwg / 2) on in two thread groups, the last workgroup holds
+    (Fw - 1) mod 8 + 1 rows, and column R_a - 1 of the solve's input (updated when its r_up is set: last_lane) is the last lane
+    of the padded rank.  A set that is empty at a shape is skipped by the comparison and not counted."""
+    idx = np.arange(Fw * n_up)
+    wg = (idx % Fw) // 8
+    nwg = (Fw + 7) // 8
+    half = (nwg + 1) // 2
+    return {"B_tmp.first_wg": idx[wg == 0], "B_tmp.last_wg": idx[wg == nwg - 1], "B_tmp.wg_low": idx[wg < half],
+            "B_tmp.wg_high": idx[wg >= half], "B_tmp.col_Ra-1": idx[idx.size - Fw:] if last_lane else idx[:0]}
+
+
 class Tally:
     """What a case's judged frames add up to: per field and region the worst error / bound and the squared relative errors."""
 
@@ -831,6 +879,7 @@ def judge(dev_after, dev_trace, g, ref, bnd, margins, p, Bx, tally, what, u=U, p
         Fw = Bd0.shape[0]
         regs = {"B_tmp": np.arange(up.size), "B_tmp.extra_row": np.arange(Fw - 1, up.size, Fw),
                 "B_tmp.last_column": np.arange(up.size - Fw, up.size)}
+        regs.update(wadapt_regions(Fw, n_up, bool(r_up[Ra - 1])))
         cmp(key, up.ravel(order="F"), Wn.ravel(order="F"), bnd["tau_w"](n_up) * Wn.ravel(order="F") + 4 * TINY[u], regs)
     return True
 
@@ -876,13 +925,77 @@ CASES = {
 }
 
 
+# ---- the single-stream separator (OnlineSeparator): the smallest shapes at which each of ITS paths can still go wrong -------------
+# s1: k_wadapt at the shipped row count: F = 513 -> 65 workgroups of 8 rows, both thread groups of cross_sum (33 + 32), a last
+#     workgroup of one row, R_a at kWaRP = 64, operand images (m_a = 64).  s2: m_a = 21 is no multiple of 4 (no operand images),
+#     F = 257 -> 33 workgroups (17 + 16), a last workgroup of one row.  s3: F = 1025 is past k_hsolve_frame (k_hsolve_small) and
+#     129 workgroups are past k_wadapt (the W-only plan loop on T = m_a); the rest as tests/test_online.py::GEOMETRIES' fft 2048
+#     row.  s4: r = 161 at F = 1025 is the smallest rank whose H-only plan has small_ok == false (rp = 192: the persistent kernel's
+#     (32 (rp + 4 + Fq + 4) + rp) 4 + 8192 B = 166 656 B > 160 KiB; r = 160 needs 162 432 B and fits) -- tests/
+#     test_online_step_rules.py asserts both from the plan's describe text.  s5: c1's geometry, the semi-supervised frame solve
+#     (the plan hsemi): at one iteration H is updated before W, so A is the supervised step's and the solve's private W must
+#     leave no trace.  s6: a fixed dictionary (adapt_train_N = 0): om_solve_run, all frames of a call in one launch_small.
+GEO_S1 = GEO4[:5] + (dict(R_a=64, m_a=64, overlap_m_a=0.05),)
+GEO_S2 = (512, 400, 100, 24, 40, dict(R_a=16, m_a=21, overlap_m_a=0.1, P_len_k=30, P_len_l=6, init_N_len=4, DCbin=3, DCbin_back=3))
+# (the fft 2048 row of GEOMETRIES has Ar_up = 2 and overlap_m_a = 0.05: every frame triggers and floor(0.05 * 30) = 1 keeps
+# update_switch at 1, which no seed changes; Ar_up = 1 -- the shipped value, the first of 1, 0.8, ... that leaves untriggered
+# frames -- and overlap_m_a = 0.1 (a solve every third push) are the smallest changes that meet coverage_ok)
+_FFT2048 = dict(R_a=24, m_a=30, overlap_m_a=0.1, Ar_up=1.0, P_len_k=100, P_len_l=6, init_N_len=4, DCbin=5, DCbin_back=5)
+GEO_S3 = (2048, 1600, 400, 40, 40, _FFT2048)
+GEO_S4 = (2048, 1600, 400, 61, 100, _FFT2048)
+
+
+def _sc(geo, hops, precision="fp32", seed=11, over=None, env=None, base=None, fixed=False):
+    return dict(geo=geo, hops=hops, precision=precision, seed=seed, over=over or {}, env=env or {}, base=base, fixed=fixed)
+
+
+_NO_WADAPT = dict(SNMF_NO_WADAPT="1")  # (read when the separator is created: the W-only plan loop instead of k_wadapt)
+# name -> geometry, hops, precision, seed (the rule of CASES), overrides on the one-step settings, environment of the device
+# run, base (the case whose CPU trajectory this one shares: the environment changes the device's path and nothing else), fixed
+# (no adaptation: the coverage rule is frames on both sides of init_N_len and of P_len_l).
+SINGLE_CASES = {
+    "s1_fft1024_kl_ra64_wadapt": _sc(GEO_S1, 72),
+    "s1_fft1024_kl_ra64_wadapt_fp64": _sc(GEO_S1, 72, "fp64"),
+    "s2_fft512_ma21_wadapt": _sc(GEO_S2, 40),
+    "s1_fft1024_kl_ra64_plan": _sc(GEO_S1, 72, env=_NO_WADAPT, base="s1_fft1024_kl_ra64_wadapt"),
+    "s2_fft512_ma21_plan": _sc(GEO_S2, 40, env=_NO_WADAPT, base="s2_fft512_ma21_wadapt"),
+    "c1_fft128_kl_plan": _sc(GEO1, 40, env=_NO_WADAPT, base="c1_fft128_kl"),
+    "s3_fft2048_small_plan": _sc(GEO_S3, 44),
+    "s4_fft2048_r161_planloop": _sc(GEO_S4, 44),
+    "s5_fft128_semi_N": _sc(GEO1, 40, over=dict(basis_update_N=1)),
+    "s5_fft128_semi_E_fixed": _sc(GEO1, 40, over=dict(basis_update_E=1, adapt_train_N=0), fixed=True),
+    # two iterations: the second H step sees the W the first iteration's W update left (the one-step cases never do); judged
+    # under stop_bounds(..., n_iter=2).  Only the fixed-dictionary configuration: with basis_update_N the adaptation solve would
+    # run two iterations too, and the rule has no bound for a two-step dictionary (amplification() measures no dictionary field)
+    "s5_fft128_semi_E_fixed_2it": _sc(GEO1, 40, over=dict(basis_update_E=1, adapt_train_N=0, max_iter=2), fixed=True),
+    "s6_fft128_fixed": _sc(GEO1, 40, over=dict(adapt_train_N=0), fixed=True),
+    "s6_fft2048_fixed": _sc(GEO_S3, 44, over=dict(adapt_train_N=0), fixed=True),
+}
+# the cases of CASES the single-stream separator is judged on too, one separator per stream (the per-stream-settings case has
+# no single-stream form)
+SINGLE_REUSED = [n for n in CASES if n != "c9_fft128_kl_fp64_streams"]
+
+
+def single_case(name):
+    """(environment of the device run, the case whose inputs and CPU trajectory it has, fixed dictionary?)."""
+    if name in CASES:
+        return {}, name, False
+    c = SINGLE_CASES[name]
+    return c["env"], c["base"] or name, c["fixed"]
+
+
 def case_inputs(name, seed=None):
     """(p, pcms, Bx, Bds, H0s, Ads, precision, settings) of a case: three streams as tests/test_online_batch.py::_geo_streams builds
     them (the second one shorter), the one-step settings.  A case with class outputs has its partition in p (EVENT_RANK /
     NOISE_RANK).  settings: None, or per stream the overrides on p, with Bx then a list of three event dictionaries
     (stream_view gives stream k's own p and Bx)."""
     from test_online_batch import _geo_streams, _settings
-    geo, hops, precision, seed0, classes = CASES[name]
+    over = {}
+    if name in CASES:
+        geo, hops, precision, seed0, classes = CASES[name]
+    else:  # a single-stream case: the same streams, its own overrides on the one-step settings
+        c = SINGLE_CASES[name]
+        geo, hops, precision, seed0, classes, over = c["geo"], c["hops"], c["precision"], c["seed"], None, c.get("over", {})
     p, pcms, Bx, Bds, H0s, Ads = _geo_streams(geo, hops, seed=seed0 if seed is None else seed)
     settings, mel = None, None
     if isinstance(classes, tuple):
@@ -891,7 +1004,7 @@ def case_inputs(name, seed=None):
         rs = np.random.RandomState(5)
         Bx = [Bx, Bx * (1.0 + 0.05 * rs.random_sample(Bx.shape)), Bx]
         settings, classes = [{}, dict(alpha_d=0.65), dict(sparsity=4)], None
-    p = _settings(dict(p, **ONE_STEP, **(classes or {}), **(mel or {})))
+    p = _settings(dict(p, **dict(ONE_STEP, **(classes or {}), **(mel or {}), **over)))
     if mel:  # the mode's configuration: the float image of melmat the device holds, the shared B_Mel_x, every stream's B_Mel_d
         from se_snmf_nat_amd.frontend import mel_matrix
         from test_online_batch_mel import _mel_dict, _melmat
@@ -961,6 +1074,148 @@ def advance(g, ga, frames, y, p, dt=np.float32):
         if k in g:
             gn[k] = r(tails[k])
     return gn
+
+
+# ---- judging a run: what tests/test_gpu_online_step.py (the batch) and tests/test_gpu_online_single_step.py share ------------------
+
+def case_bounds(g, y, p, Bx, ref, u):
+    """bounds() of a frame; a case with max_iter > 1 (the semi-supervised solve's W update) is judged under the project's rule
+    for a k-iteration solve, stop_bounds: 4 n_iter tau max(1, amp_e) with the reference's own amplification."""
+    bnd, margins = bounds(g, y, p, Bx, *ref, u=u)
+    if int(p["max_iter"]) > 1:
+        bnd = stop_bounds(bnd, amplification(g, y, p, Bx, ref)[0], n_iter=int(p["max_iter"]))
+    return bnd, margins
+
+
+def judge_run(name, views, precision, steps, fixed=False):
+    """Judge every (frame, stream) pair of a run and assert the whole verdict.  views: per stream (p, Bx); steps: per stream the
+    list of (state before, frame buffer, state after, trace entry), the states fp64-cast (state64).  Each pair is judged alone
+    against sep_frame from the device's own before-state under the derived bounds, with both float32 emulations from the same
+    state as the yardstick of the RMS check; one line per field and region is printed.  fixed: a run without adaptation, whose
+    coverage rule is frames on both sides of init_N_len and of P_len_l.  Returns the device's Tally."""
+    dt, u = (np.float32, U) if precision == "fp32" else (np.float64, U64)
+    dev, emu = Tally(), (Tally(), Tally())
+    records = []
+    for k, ((p, Bx), sk) in enumerate(zip(views, steps)):
+        rec = []
+        for g, y, after, trace in sk:
+            ref = reference(g, y, p, Bx)
+            bnd, margins = case_bounds(g, y, p, Bx, ref, u)
+            what = f"{name} stream {k} frame {g['l']}"
+            judge(after, trace, g, ref, bnd, margins, p, Bx, dev, what, u=u)
+            for rev, t in zip((False, True), emu):  # the yardstick of the RMS check, from the same state
+                ga, fr, tr = frame_step(g, y, g["l"], p, g["H0"], Bx, dt=dt, rev=rev, seq=True)
+                e = after_state(g, ga, fr, p["framelength"])
+                judge(e, tr, g, ref, bnd, margins, p, Bx, t, what + " (emulation)", u=u)
+            rec.append((g["l"], ref[2], after["n_push"], after["update_switch"]))
+        records.append(rec)
+    cov = coverage(records, views[0][0])
+    print(f"\n{name}: {dev.frames} (frame, stream) pairs, triggered {dev.triggered}, solved {dev.solved}, left out {dev.left_out} "
+          f"({100.0 * dev.left_out / dev.frames:.1f} %), r_up rows on the reference's margin {dev.border_rows} of {dev.rows}, elements "
+          f"left out for a floor {dev.elem_out}; {cov}")
+    rms_bad = []
+    for key in sorted(dev.worst):
+        yard = max(emu[0].rms(key) if key in emu[0].sq else 0.0, emu[1].rms(key) if key in emu[1].sq else 0.0, u / np.sqrt(3.0))
+        limit = RMS_FACTOR * yard
+        print(f"  {key:34s} worst/bound {dev.worst[key]:9.3e}  device rms {dev.rms(key):9.3e}  emulation rms {yard:9.3e}  ratio {dev.rms(key) / yard:6.2f}")
+        if key.startswith("trace.") and precision == "fp64":
+            continue  # (the trace is float in every mode: in the fp64 mode its RMS is that conversion's)
+        if not dev.rms(key) <= limit:
+            rms_bad.append(f"{key}: device rms {dev.rms(key):.3e} > {RMS_FACTOR} x emulation rms {yard:.3e}")
+    assert not dev.fails, f"{len(dev.fails)} failures:\n" + "\n".join(dev.fails[:12])
+    assert not emu[0].fails and not emu[1].fails, "\n".join((emu[0].fails + emu[1].fails)[:6])
+    assert not rms_bad, "\n".join(rms_bad)
+    assert (cov["init_both"] and cov["pl_both"]) if fixed else coverage_ok(cov), cov
+    assert dev.caps_ok(), (dev.left_out, dev.border_rows, dev.elem_out)
+    return dev
+
+
+# ---- the single-stream driver: one separator per stream, one hop per process call, a get_state around every hop -------------------
+
+class SimSeparator:
+    """The emulation behind OnlineSeparator's calls (process / get_state / trace / close): frame_step over the mode's number type
+    with the state rounded as the mode stores it.  The rules test runs the driver on it without a GPU ("a simulated device"),
+    with a planted error where one is asked for."""
+
+    def __init__(self, p, Bx, Bd, H0, Ad0, precision="fp32", rev=False, plant=None, B_Mel_d=None):
+        self.p, self.Bx, self.rev, self.plant = p, Bx, rev, plant
+        self.dt = np.float32 if precision == "fp32" else np.float64
+        self.g = initial_state(p, Bx, Bd, H0, Ad0, self.dt, B_Mel_d)
+        self._trace = []
+
+    def get_state(self):
+        return dict(self.g, pending=np.zeros(0))
+
+    def process(self, pcm):
+        hop = self.p["frameshift"]
+        pcm = np.asarray(pcm, np.float64)
+        assert pcm.size % hop == 0
+        for i in range(pcm.size // hop):
+            g = self.g
+            y = frame_buffer(g, pcm[i * hop:(i + 1) * hop])
+            ga, fr, tr = frame_step(g, y, g["l"], self.p, g["H0"], self.Bx, dt=self.dt, rev=self.rev, plant=self.plant, seq=True)
+            self._trace.append({k: (float(np.float32(v)) if isinstance(v, float) else v) for k, v in tr.items()
+                                if k in ("n_iter", "trig", "n_up", "solved", "adapt_iters", "beta", "A_x_mag", "A_d_mag", "Q_control")})
+            self.g = advance(g, ga, fr, y, self.p, self.dt)
+
+    def trace(self):
+        return list(self._trace)
+
+    def close(self):
+        pass
+
+
+def device_separator(ctx):
+    """make(k, p, Bx, Bd, H0, Ad0, precision, class_outputs, mel) for run_single: the library's OnlineSeparator on ctx."""
+    def make(k, p, Bx, Bd, H0, Ad0, precision, cls, mel):
+        from se_snmf_nat_amd.online import OnlineSeparator
+        return OnlineSeparator(Bx, Bd, p, H0=H0, Ad_blk0=Ad0, ctx=ctx, precision=precision, class_outputs=cls, **mel)
+    return make
+
+
+def sim_separator(rev=False, plant=None):
+    def make(k, p, Bx, Bd, H0, Ad0, precision, cls, mel):
+        return SimSeparator(p, Bx, Bd, H0, Ad0, precision, rev, plant, mel.get("B_Mel_d"))
+    return make
+
+
+def run_single(make, name, streams=(0, 1, 2), hops_per_call=1, keep_outputs=False):
+    """A case on single-stream separators, one per stream: per stream the list of (state before, frame buffer, state after,
+    trace entry) for every frame when hops_per_call is 1 -- the after-state of frame l is the before-state of frame l + 1.
+    With more hops per call (the fixed-dictionary path runs a whole call's frames in one launch) and keep_outputs: per stream
+    (the states after every call, what the calls returned, the trace) instead.  Returns (views, precision, steps)."""
+    _, base, _ = single_case(name)
+    p0, pcms, Bx0, Bds, H0s, Ads, precision, settings = case_inputs(base)
+    assert settings is None
+    hop = p0["frameshift"]
+    views, out, ns = [], [], []
+    for k in streams:
+        p, Bx = stream_view(p0, Bx0, settings, k)
+        cls = class_cols(p, Bx.shape[1], Bds[k].shape[1]) is not None
+        mel = dict(B_Mel_x=p["_B_Mel_x"], B_Mel_d=p["_B_Mel_ds"][k]) if "_melmat" in p else {}
+        sep = make(k, p, Bx, Bds[k], H0s[k], Ads[k], precision, cls, mel)
+        n = len(pcms[k]) // hop
+        before = state64(sep.get_state())
+        assert ("class_tails" in before) == cls and ("x_hat_tail" in before) == cls
+        steps, states, outs = [], [], []
+        for i in range(0, n, hops_per_call):
+            feed = pcms[k][i * hop:min(n, i + hops_per_call) * hop]
+            o = sep.process(feed)
+            after = state64(sep.get_state())
+            assert before["pending"].size == 0 and before["l"] == i + 1
+            if hops_per_call == 1:
+                steps.append((before, frame_buffer(before, feed), after))
+            states.append(after)
+            outs.append(o)
+            before = after
+        trace = sep.trace()
+        sep.close()
+        assert len(trace) == n
+        ns.append(n)
+        views.append((p, Bx))
+        out.append((states, outs, trace) if keep_outputs else [s + (trace[i],) for i, s in enumerate(steps)])
+    assert len(set(ns)) > 1 or len(streams) == 1  # the streams differ in length
+    return views, precision, out
 
 
 # ---- the stop-armed cases (shipped max_iter = 100, conv_eps = 1e-3) ----------------------------------------------------------------

@@ -52,41 +52,7 @@ def _run(ctx, name):
 @pytest.mark.parametrize("name", list(os_.CASES))
 def test_every_frame_step_is_inside_its_bounds(gpu_ctx, name):
     views, precision, steps = _run(gpu_ctx, name)
-    dt, u = (np.float32, os_.U) if precision == "fp32" else (np.float64, os_.U64)
-    dev, emu = os_.Tally(), (os_.Tally(), os_.Tally())
-    records = []
-    for k in range(3):
-        rec = []
-        p, Bx = views[k]
-        for g, y, after, trace in steps[k]:
-            ref = os_.reference(g, y, p, Bx)
-            bnd, margins = os_.bounds(g, y, p, Bx, *ref, u=u)
-            what = f"{name} stream {k} frame {g['l']}"
-            os_.judge(after, trace, g, ref, bnd, margins, p, Bx, dev, what, u=u)
-            for rev, t in zip((False, True), emu):  # the yardstick of the RMS check, from the same state
-                ga, fr, tr = os_.frame_step(g, y, g["l"], p, g["H0"], Bx, dt=dt, rev=rev, seq=True)
-                e = os_.after_state(g, ga, fr, p["framelength"])
-                os_.judge(e, tr, g, ref, bnd, margins, p, Bx, t, what + " (emulation)", u=u)
-            rec.append((g["l"], ref[2], after["n_push"], after["update_switch"]))
-        records.append(rec)
-    cov = os_.coverage(records, views[0][0])
-    print(f"\n{name}: {dev.frames} (frame, stream) pairs, triggered {dev.triggered}, solved {dev.solved}, left out {dev.left_out} "
-          f"({100.0 * dev.left_out / dev.frames:.1f} %), r_up rows on the reference's margin {dev.border_rows} of {dev.rows}, elements "
-          f"left out for a floor {dev.elem_out}; {cov}")
-    rms_bad = []
-    for key in sorted(dev.worst):
-        yard = max(emu[0].rms(key) if key in emu[0].sq else 0.0, emu[1].rms(key) if key in emu[1].sq else 0.0, u / np.sqrt(3.0))
-        limit = os_.RMS_FACTOR * yard
-        print(f"  {key:34s} worst/bound {dev.worst[key]:9.3e}  device rms {dev.rms(key):9.3e}  emulation rms {yard:9.3e}  ratio {dev.rms(key) / yard:6.2f}")
-        if key.startswith("trace.") and precision == "fp64":
-            continue  # (the trace is float in every mode: in the fp64 mode its RMS is that conversion's)
-        if not dev.rms(key) <= limit:
-            rms_bad.append(f"{key}: device rms {dev.rms(key):.3e} > {os_.RMS_FACTOR} x emulation rms {yard:.3e}")
-    assert not dev.fails, f"{len(dev.fails)} failures:\n" + "\n".join(dev.fails[:12])
-    assert not emu[0].fails and not emu[1].fails, "\n".join((emu[0].fails + emu[1].fails)[:6])
-    assert not rms_bad, "\n".join(rms_bad)
-    assert os_.coverage_ok(cov), cov
-    assert dev.caps_ok(), (dev.left_out, dev.border_rows, dev.elem_out)
+    os_.judge_run(name, views, precision, steps)  # (judges, prints and asserts: the single-stream test shares it)
 
 
 def test_one_rank_past_the_frame_kernel_is_refused(gpu_ctx):
